@@ -12,7 +12,12 @@ reference writes to disk) and gathers them to rank 0 over RCCL, the gather overl
 host-to-host rate of _infer's own contract (/root/reference/cpp/helper.cpp:674-682: host text in, host waveform out): text
 frontend -> pinned upload -> synthesis -> 16-bit PCM back in host memory, the copy of batch i overlapping batch i+1.
 --scaling weak (default): 128 utterances per GPU; --scaling strong: 128 utterances in all, 128/N per GPU.
-Synthetic text / styles / weights (no assets offline).  Prints ONE JSON line on rank 0."""
+Synthetic text / styles / weights (no assets offline).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, `config`).  Everything else
+— p50 latencies, the event-timed kernel pass and rooflines, the host-to-host loop, the other scaling mode (N > 1), the gather
+check (N > 1), the single-utterance record (fp32 and --dtype) and the CPU baseline — runs only with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs)."""
 import argparse
 import json
 import os
@@ -45,7 +50,15 @@ def parse():
     ap.add_argument("--eager", action="store_true", help="launch every step eagerly instead of replaying the captured hipGraphs (profiler runs: rocprofv3's kernel "
                                                          "trace of many graph launches crashes inside the ROCm 7.2 runtime; kernel durations are the same)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py starts the ranks itself (0: pick a free one)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline (latencies, kernel timing, host loop, "
+                                                        "other scaling, gather check, single utterance, CPU baseline); --no-* and --cpu-sample "
+                                                        "select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the waveforms and durations of the last timed step to DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def visible_gpus():
@@ -280,34 +293,38 @@ def main():
     # ---- timed region: exactly K steps (hipGraph replays of the post-duration pipeline) between barrier + synchronize -----------
     elapsed = timed(args.steps)
     replays_timed = eng.graph_replays - replays0
+    # read before --full's passes run further steps on the engine
+    dumped = dump_outputs(eng, args.dump_outputs, world, rank) if args.dump_outputs else None
 
     # ---- p50 per-utterance latency: completion time of the batch that contains the utterance ---------------------
-    lat = []
-    for _ in range(min(5, max(2, args.steps))):
-        fence()
-        t1 = time.perf_counter()
-        step()
-        fence()
-        lat.append((time.perf_counter() - t1) * 1e3)
-    p50 = float(np.median(lat))
-    # ---- the same lone batch on the critical path of a PREDICTED-duration run: the duration predictor, the device->host read of its
-    # result and the wait for it precede everything else (the forced-duration runs above skip the read: durations are known on the
-    # host).  Shapes stay the forced ones (stn_set_duration_read: synthetic weights predict meaningless lengths).
-    lat_pred = []
-    eng.set_duration_read(True)
-    for _ in range(min(5, max(2, args.steps)) + 1):
-        fence()
-        t1 = time.perf_counter()
-        step()
-        fence()
-        lat_pred.append((time.perf_counter() - t1) * 1e3)
-    eng.set_duration_read(False)
-    p50_pred = float(np.median(lat_pred[1:]))
+    p50 = p50_pred = None
+    if args.full:
+        lat = []
+        for _ in range(min(5, max(2, args.steps))):
+            fence()
+            t1 = time.perf_counter()
+            step()
+            fence()
+            lat.append((time.perf_counter() - t1) * 1e3)
+        p50 = float(np.median(lat))
+        # ---- the same lone batch on the critical path of a PREDICTED-duration run: the duration predictor, the device->host read of its
+        # result and the wait for it precede everything else (the forced-duration runs above skip the read: durations are known on the
+        # host).  Shapes stay the forced ones (stn_set_duration_read: synthetic weights predict meaningless lengths).
+        lat_pred = []
+        eng.set_duration_read(True)
+        for _ in range(min(5, max(2, args.steps)) + 1):
+            fence()
+            t1 = time.perf_counter()
+            step()
+            fence()
+            lat_pred.append((time.perf_counter() - t1) * 1e3)
+        eng.set_duration_read(False)
+        p50_pred = float(np.median(lat_pred[1:]))
 
     # ---- the gathered waveforms against the engine's own PCM fetch (N > 1 code path): rank 0's block of the last gather must be the
     # bytes stn_batch_fetch_pcm16 returns for the same resident batch, and every rank's block must have arrived with its shape ---------
     gather_check = None
-    if use_dist:
+    if use_dist and args.full:
         import zlib
         fence()
         k_last = (step_no[0] - 1) & 1
@@ -324,7 +341,7 @@ def main():
     # launch of that family give its live average duration (roofline.achieved) -------------------------------------------------
     dominant, fam_stats, roof, eager = None, {}, None, None
     sample_every = 1
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         eng.profile_filter(None)
         eng.profile_enable(True)
         eng.profile_reset()
@@ -382,7 +399,7 @@ def main():
 
     # ---- host-to-host: text frontend -> pinned upload -> synthesis -> 16-bit PCM in host memory, per batch --------------------
     hostrec = None
-    if not args.no_host_loop:
+    if args.full and not args.no_host_loop:
         hostrec = host_loop(eng, up, texts, sttl, sdp, durs, mine, args, fence)
 
     audio_per_step = audio_total(durs)
@@ -397,7 +414,7 @@ def main():
     # MI355X" (strong: 128 in all), the driver's efficiency curve wants fixed work per GPU (weak: 128 each).  `value` is --scaling's;
     # the other figure is reported beside it ------------------------------------------------------------------------------------
     other_scaling = None
-    if world > 1:
+    if world > 1 and args.full:
         om = "strong" if args.scaling == "weak" else "weak"
         so = make_shard(om)
         fence()
@@ -439,14 +456,18 @@ def main():
                        "warmup_steps_run": n_warm,
                        "hip_built": rt_info["hip_built"], "hip_runtime": rt_info["hip_runtime"], "torch_in_process": bool(rt_info["torch_preloaded"]),
                        "parallelism": f"utterance-sharded x{world}, RCCL gather of int16 PCM to rank 0 overlapped with the next step" if world > 1 else "single GPU"},
-            "p50_latency_ms": round(p50, 3),
-            "lone_batch_predicted_path": {"p50_ms": round(p50_pred, 3),
-                                          "note": "one batch alone with the duration predictor, the device->host read of its durations and the wait for it on the critical "
-                                                  "path, as when durations are predicted (the other figures run with durations known on the host: no read); shapes forced"},
-            "latency_note": "per-utterance latency = completion time of its 128-utterance batch (submit -> waveform in HBM), graph replay",
             "graph_replays_in_timed_region": replays_timed,
-            "roofline": roof,
         }
+        if dumped:
+            out["outputs"] = dumped
+        if args.full:
+            out["p50_latency_ms"] = round(p50, 3)
+            out["lone_batch_predicted_path"] = {
+                "p50_ms": round(p50_pred, 3),
+                "note": "one batch alone with the duration predictor, the device->host read of its durations and the wait for it on the critical "
+                        "path, as when durations are predicted (the other figures run with durations known on the host: no read); shapes forced"}
+            out["latency_note"] = "per-utterance latency = completion time of its 128-utterance batch (submit -> waveform in HBM), graph replay"
+            out["roofline"] = roof
         if eager:
             out["eager_sampled"] = eager
         if other_scaling:
@@ -505,9 +526,9 @@ def main():
             for k, v in fam_stats.items():
                 st_ms[k.split(".")[0]] = st_ms.get(k.split(".")[0], 0.0) + v["ms"]
             out["stage_ms_fully_profiled_step"] = {k: round(v, 3) for k, v in sorted(st_ms.items())}
-        if world == 1 and not args.no_b1 and not args.mixed:
+        if args.full and world == 1 and not args.no_b1 and not args.mixed:
             out["single_utterance"] = single_utterance(eng, arch, up, args)
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(arch, texts, ids, mask, sttl, sdp, durs, args)
         log_path = os.environ.get("STN_LAUNCH_LOG")
         if world == 1 and log_path:
@@ -536,6 +557,27 @@ def main():
         eng.sync()
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_WAV_BYTES = 56 << 20  # waveform bytes --dump-outputs writes over all ranks (the rest of the 64 MB: durations, row indices)
+
+
+def dump_outputs(eng, out_dir, world, rank):
+    """--dump-outputs: what a caller of the timed path receives from its last step (stn_batch_fetch): `wav` [rows, W] float32 and
+    `duration` [B] float32 (seconds, after /speed).  A batch whose waveforms exceed DUMP_WAV_BYTES / world is written as a fixed
+    sample of whole rows, numpy default_rng(0) without replacement, in ascending order, their indices in `wav_rows` (float64).
+    With N > 1 every rank writes its own shard, names suffixed _rank<r>.  Returns the record for the JSON line."""
+    wav, dur = eng.batch_fetch()
+    B, W = wav.shape
+    k = min(B, max(1, DUMP_WAV_BYTES // world // (4 * W)))
+    rows = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    arrays = {"wav": np.ascontiguousarray(wav[rows]), "duration": dur, "wav_rows": rows.astype(np.float64)}
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+    return {"dir": out_dir, "arrays": {name + sfx: list(a.shape) for name, a in arrays.items()},
+            "note": f"last timed step; wav rows: {'all' if k == B else f'a seeded sample of {k} of {B}'}"}
 
 
 def _pmc_traffic(kernel):

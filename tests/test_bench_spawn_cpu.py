@@ -48,3 +48,10 @@ def test_launcher_and_flag_must_agree():
     """WORLD_SIZE set by a launcher but different from --gpus: an error (before any GPU work), not a silent choice of one of them."""
     p = _run(["--gpus", "4", "--steps", "1", "--warmup", "1"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0", "STN_BENCH_STUB": "0"})
     assert p.returncode != 0 and "disagree" in p.stderr
+
+
+def test_steps_must_be_positive():
+    """`ms_per_step` divides by --steps: zero timed steps is an argument error, before any rank starts."""
+    p = _run(["--steps", "0", "--warmup", "1"], {"STN_BENCH_STUB": "1"})
+    assert p.returncode == 2 and "--steps must be >= 1" in p.stderr
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -3,7 +3,9 @@ import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "2", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -64,6 +66,40 @@ def test_bench_json_line_contract():
         assert r["traffic"] is None
 
 
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full the run times K steps and prints the headline only, spending < 30 s outside its steps; --dump-outputs writes the
+    last timed step's waveforms and durations, the same bits whatever K is (same arguments = same inputs)."""
+    runs = {}
+    for k in (2, 3):
+        t0 = time.perf_counter()
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(k), "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / f"k{k}")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        wall = time.perf_counter() - t0
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == k and d["graph_replays_in_timed_region"] == k and d["dtype"] == "bf16" and d["unit"] == "audio-sec/sec"
+        assert d["higher_is_better"] is True and d["value"] > 1000
+        assert abs(d["value"] - d["config"]["audio_sec_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+        for extra in ("p50_latency_ms", "roofline", "eager_sampled", "value_host", "two_in_flight", "single_utterance", "cpu_baseline",
+                      "kernel_time_share"):
+            assert extra not in d, extra
+        assert wall - (k + 1) * d["ms_per_step"] * 1e-3 < 30, (wall, d["ms_per_step"])
+        runs[k] = d
+    names = sorted(os.listdir(tmp_path / "k2"))
+    assert names == ["duration.npy", "wav.npy", "wav_rows.npy"] and sorted(os.listdir(tmp_path / "k3")) == names
+    assert sum(os.path.getsize(tmp_path / "k2" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "k2" / n), np.load(tmp_path / "k3" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    wav, dur, rows = (np.load(tmp_path / "k2" / n) for n in ("wav.npy", "duration.npy", "wav_rows.npy"))
+    assert dur.shape == (128,) and abs(float(dur.sum()) - runs[2]["config"]["audio_sec_per_step"]) < 0.05
+    assert wav.shape[0] == rows.size and np.all(np.diff(rows) > 0) and rows[-1] < 128
+    assert np.all(np.isfinite(wav)) and float(np.abs(wav).max()) > 0
+    assert runs[2]["outputs"]["arrays"]["wav"] == list(wav.shape)
+
+
 def test_bench_strong_scaling_flag():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--scaling", "strong",
                         "--no-host-loop", "--no-b1", "--no-profile"], capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -79,7 +115,7 @@ def test_bench_multi_gpu_code_path_at_world_1():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--no-host-loop", "--no-b1",
-                        "--no-profile"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+                        "--no-profile", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     g = d["gather_check"]

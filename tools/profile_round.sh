@@ -9,7 +9,7 @@
 # Every pass runs with --eager (rocprofv3's tracing of many hipGraph launches crashes inside the ROCm 7.2 runtime; the kernels and their
 # durations are the same as in the replayed pipeline) and with --no-profile: the engine's own event timing (events on dispatch packets) under rocprofv3's interception crashes
 # inside the ROCm 7.2 runtime, and a profiler run is timed by the profiler anyway; the launch log needs family tags only.
-# A sixth, un-profiled run of the default command is the round's bench line (profiles/<tag>_default_bench.json).
+# A sixth, un-profiled run of the default command with --full is the round's bench line (profiles/<tag>_default_bench.json).
 set -eo pipefail
 TAG=${1:-r02_a}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -39,7 +39,7 @@ cp "$S" "profiles/${TAG}_bench_kernel_stats.csv"
 grep '^{' "$OUT/bench.json" | tail -1 > "profiles/${TAG}_bench.json"
 python3 tools/pmc_families.py --dir "$OUT" --tag "$TAG" > "$OUT/families.log"
 # the un-profiled default run, AFTER the summaries exist: its roofline.traffic / mfma_util_pmc come from them (source-hash checked)
-(cd /tmp && python3 "$B" > "$OUT/default_bench.json" 2> "$OUT/default_bench.err") || echo "default bench failed" >&2
+(cd "$TMPDIR" && python3 "$B" --full > "$OUT/default_bench.json" 2> "$OUT/default_bench.err") || echo "default bench failed" >&2
 grep '^{' "$OUT/default_bench.json" | tail -1 > "profiles/${TAG}_default_bench.json"
 # the summaries travel back with gpurun_out/ (profiles/ on the box is not merged): copy them beside the raw output
 mkdir -p "$OUT/profiles" && cp profiles/l2_hit.json "$OUT/profiles/" 2>/dev/null || true
