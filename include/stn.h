@@ -179,6 +179,8 @@ int64_t stn_batch_ve_rows(const stn_handle* h);
  * was filled from the model's cached zero-latent response (bit-identical result; bf16 and f16 engines, packed row layout) */
 int64_t stn_batch_vo_rows(const stn_handle* h);
 int64_t stn_graph_replays(const stn_handle* h);
+/* B, L (latent frames, model rate) and the samples per utterance every fetch returns: L * chunk at the model's rate, or
+ * ceil(L * chunk * P / Q) with an output rate set (stn_set_output_rate) */
 int stn_batch_dims(const stn_handle* h, int* B, int* L, int64_t* wav_len_per_utt);
 int stn_batch_fetch(stn_handle* h, float* wav, size_t wav_capacity_floats, float* duration);
 /* same, as 16-bit PCM converted on the GPU exactly as writeWavFile does (clamp to [-1,1], *32767, truncation;
@@ -210,6 +212,35 @@ int stn_batch_copy_wav_device(stn_handle* h, void* dst_device, int64_t dst_strid
 /* same as 16-bit PCM (the conversion of writeWavFile, cpp/helper.cpp:986-987), e.g. straight into an RCCL gather payload:
  * half the bytes over xGMI; dst_stride in samples */
 int stn_batch_copy_pcm16_device(stn_handle* h, void* dst_device, int64_t dst_stride);
+
+/* ---- output rate ---------------------------------------------------------------------------------------
+ * The model synthesizes at its own rate (stn_arch.sample_rate, 44.1 kHz for the published model; the reference's hosts can only
+ * return that: cpp/helper.cpp:943-990).  With an output rate set, every fetch path — stn_batch_fetch, stn_batch_fetch_pcm16,
+ * stn_batch_fetch_pcm16_begin / _end (slots sized in output samples), stn_batch_copy_wav_device, stn_batch_copy_pcm16_device and
+ * through it the group gather — resamples the finished waveform on the handle's stream before its copy, so the host and the
+ * gather move output-rate samples.  stn_batch_dims and stn_batch_fetch_slot_dims report the samples at the output rate; durations
+ * stay in seconds; stn_batch_wav_device_ptr stays the model-rate waveform.  The latent geometry and the captured pipeline are the
+ * model rate's: setting the rate drops or re-keys no captured graph.
+ * Resampler: rational polyphase, P/Q = out/in reduced by their gcd; output n of a row uses phase (n*Q) mod P and the inputs from
+ * floor(n*Q/P) - off on (zero outside the row); W_out = ceil(W*P/Q); fp32 sums in a fixed tap order, the same for every output
+ * position (the first ceil(m*P/Q) outputs of a row that is zero past m are those of the row cut at m).  Filter: Kaiser-windowed
+ * sinc, passband within +-0.05 dB up to 0.85 * min(in, out)/2, >= 80 dB rejection from min(in, out)/2 on, every phase's gain 1 at
+ * DC.  Rates: [8000, 192000] Hz with a reduced P <= 640 (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000 Hz
+ * against 44.1 kHz among them); anything else is STN_ERR_INVALID with a message.  PCM conversion as writeWavFile (clamp, *32767,
+ * truncation): the PCM bytes are the fp32 output's converted.  DESIGN.md section 10 has the table sizes and the measured cost. */
+/* hz = 0 or the model's rate: off (the default: every fetch is byte for byte the native one, with no extra launch) */
+int stn_set_output_rate(stn_handle* h, int hz);
+/* the effective rate of the fetches: the output rate, or the model's rate when off (0 before a model is loaded) */
+int stn_get_output_rate(const stn_handle* h);
+/* the filter the resampler uses for in_hz -> out_hz (host only, no device needed): *phases = P, *taps_per_phase = T, taps
+ * [P][T] (tap j of phase p multiplies input floor(n*Q/P) - (T/2 - 1) + j) when taps != NULL and cap >= P*T.  STN_ERR_INVALID for a
+ * refused pair (stn_resample_error says why).  in_hz == out_hz gives the one-phase unit filter (a copy). */
+int stn_resample_filter(int in_hz, int out_hz, float* taps_or_null, size_t cap, int* phases, int* taps_per_phase);
+/* why a pair is refused ("" when it is supported); host only */
+const char* stn_resample_error(int in_hz, int out_hz);
+/* op-level: rows x W fp32 (host) at in_hz -> rows x ceil(W*P/Q) at out_hz, as fp32 (y) and / or int16 PCM (pcm); either may be
+ * NULL but not both.  1 <= rows <= 65535. */
+int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const float* x, float* y_or_null, int16_t* pcm_or_null);
 
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);

@@ -48,6 +48,10 @@ stn_handle* stn_group_handle(stn_group* g, int rank);
 int stn_group_load_synthetic(stn_group* g, const stn_arch* arch, uint64_t seed);
 int stn_group_load_dir(stn_group* g, const char* onnx_dir);
 
+/* output rate of every rank (stn_set_output_rate): the gather is then sized from the ranks' samples at that rate and
+ * stn_group_fetch_pcm16 returns output-rate PCM; 0 = the model's rate */
+int stn_group_set_output_rate(stn_group* g, int hz);
+
 /* The deal, host only: utterance i goes to rank rank_of[i] as row row_of[i] of that rank's shard.  lengths[B] = token counts.
  * Sorted by length descending (ties: caller order), dealt round-robin: the k-th longest goes to rank k % n as row k / n. */
 int stn_group_deal(int B, const int32_t* lengths, int n_ranks, int32_t* rank_of, int32_t* row_of);

@@ -191,6 +191,13 @@ def load():
     L.stn_group_deal.argtypes = [ci, _i32p, ci, _i32p, _i32p]
     L.stn_group_synthesize.argtypes = [vp, ci, ci, _i64p, _f32p, _f32p, _f32p, ci, cf, vp, cu64, ctypes.POINTER(ctypes.c_int64)]
     L.stn_group_fetch_pcm16.argtypes = [vp, vp, ctypes.c_size_t, vp]
+    L.stn_set_output_rate.argtypes = [vp, ci]
+    L.stn_get_output_rate.argtypes = [vp]
+    L.stn_resample_filter.argtypes = [ci, ci, vp, ctypes.c_size_t, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.stn_resample_error.argtypes = [ci, ci]
+    L.stn_resample_error.restype = ctypes.c_char_p
+    L.stn_op_resample.argtypes = [vp, ci, ci, ci, ci, _f32p, vp, vp]
+    L.stn_group_set_output_rate.argtypes = [vp, ci]
     L.stn_group_last_shards.argtypes = [vp, _i32p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
     _LIB = L
     return L
@@ -257,10 +264,37 @@ class Group:
         self._ck(self._lib.stn_group_fetch_pcm16(self._g, pcm.ctypes.data, pcm.size, dur.ctypes.data))
         return pcm, dur
 
+    def set_output_rate(self, hz):
+        """Output rate of every rank (0 or None = the model's rate): the gathered PCM is then at that rate."""
+        self._ck(self._lib.stn_group_set_output_rate(self._g, int(hz or 0)))
+
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
         self._ck(self._lib.stn_group_last_shards(self._g, rows, samples))
         return rows, samples
+
+
+SUPPORTED_OUTPUT_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000, 88200, 96000)
+
+
+def resample_filter(in_hz, out_hz):
+    """The output-rate resampler's filter for in_hz -> out_hz (host only): taps [P, T] float32; tap j of phase p multiplies input
+    floor(n*Q/P) - (T/2 - 1) + j of output n, whose phase is (n*Q) mod P.  Raises StnError for a refused pair."""
+    L = load()
+    P, T = ctypes.c_int(), ctypes.c_int()
+    rc = L.stn_resample_filter(int(in_hz), int(out_hz), None, 0, ctypes.byref(P), ctypes.byref(T))
+    if rc < 0:
+        raise StnError(rc, L.stn_resample_error(int(in_hz), int(out_hz)).decode())
+    taps = np.empty((P.value, T.value), np.float32)
+    rc = L.stn_resample_filter(int(in_hz), int(out_hz), taps.ctypes.data, taps.size, ctypes.byref(P), ctypes.byref(T))
+    if rc < 0:
+        raise StnError(rc, "stn_resample_filter failed")
+    return taps
+
+
+def resample_error(in_hz, out_hz):
+    """Why the pair is refused, or "" when it is supported (host only)."""
+    return load().stn_resample_error(int(in_hz), int(out_hz)).decode()
 
 
 def fold_run_frames(latent_lengths, n_cu=256):
@@ -437,6 +471,29 @@ class Engine:
     def set_vocoder_mode(self, length_aware):
         """False: the reference's batched vocoder (padding decoded as zero latent). True: every utterance ends at its own length."""
         self._ck(self._lib.stn_set_vocoder_mode(self._h, int(bool(length_aware))))
+
+    def set_output_rate(self, hz):
+        """Rate of every fetch (0 or None = the model's rate, the default): the finished waveform is resampled on the GPU."""
+        self._ck(self._lib.stn_set_output_rate(self._h, int(hz or 0)))
+
+    @property
+    def output_rate(self):
+        """The effective rate of the fetches (the model's rate when no output rate is set)."""
+        return self._lib.stn_get_output_rate(self._h)
+
+    def op_resample(self, x, in_hz, out_hz, pcm=False):
+        """rows x W fp32 at in_hz -> rows x ceil(W*P/Q) at out_hz on the GPU: fp32, or (pcm=True) the int16 PCM epilogue."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        P, T = resample_filter(in_hz, out_hz).shape
+        import math
+        g = math.gcd(int(in_hz), int(out_hz))
+        Q = int(in_hz) // g
+        W_out = -(-W * P // Q)
+        out = np.empty((rows, W_out), np.int16 if pcm else np.float32)
+        self._ck(self._lib.stn_op_resample(self._h, int(in_hz), int(out_hz), rows, W, x, None if pcm else out.ctypes.data,
+                                           out.ctypes.data if pcm else None))
+        return out
 
     def fetch_pcm16_begin(self, slot):
         """Start the PCM conversion + device->host copy of the finished batch on `slot` (0/1); returns at once."""

@@ -293,8 +293,33 @@ int stn_batch_dims(const stn_handle* h, int* B, int* L, int64_t* wav_len) {
     const auto& a = h->eng->arch();
     if (B) *B = b.B;
     if (L) *L = b.L;
-    if (wav_len) *wav_len = (int64_t)b.L * a.base_chunk_size * a.chunk_compress_factor;
+    if (wav_len) *wav_len = h->eng->out_len((int64_t)b.L * a.base_chunk_size * a.chunk_compress_factor);  // (at the output rate)
     return STN_OK;
+}
+int stn_set_output_rate(stn_handle* h, int hz) { STN_TRY(h, { h->eng->set_output_rate(hz); }) }
+int stn_get_output_rate(const stn_handle* h) { return h ? h->eng->output_rate() : STN_ERR_INVALID; }
+int stn_resample_filter(int in_hz, int out_hz, float* taps, size_t cap, int* phases, int* taps_per_phase) {
+    try {
+        stn::ResampleTable f;
+        if (!stn::resample_design(in_hz, out_hz, f).empty()) return STN_ERR_INVALID;
+        if (phases) *phases = f.P;
+        if (taps_per_phase) *taps_per_phase = f.T;
+        if (taps) {
+            if (cap < f.taps.size()) return STN_ERR_INVALID;
+            std::memcpy(taps, f.taps.data(), f.taps.size() * sizeof(float));
+        }
+        return STN_OK;
+    } catch (...) { return STN_ERR_INVALID; }
+}
+const char* stn_resample_error(int in_hz, int out_hz) {
+    static thread_local std::string why;
+    stn::ResampleTable f;
+    try { why = stn::resample_design(in_hz, out_hz, f); } catch (const std::exception& e) { why = e.what(); }
+    return why.c_str();
+}
+int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && (y || pcm), "stn_op_resample: bad argument (1 <= rows <= 65535, W >= 1, x and y or pcm)");
+                 h->eng->op_resample(in_hz, out_hz, rows, W, x, y, pcm); })
 }
 int stn_batch_fetch(stn_handle* h, float* wav, size_t cap, float* duration) {
     STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch(wav, cap, duration); })

@@ -254,6 +254,16 @@ class Engine {
     // the finished batch as int16 PCM (writeWavFile's conversion) straight into a device buffer, rows dst_stride apart
     void batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride);
 
+    // ---- output rate (engine_resample.cpp): 0 or the model's rate = off (the default; every fetch path is then exactly the
+    // native one).  On, every fetch path resamples the finished waveform on the handle's stream before its copy (kernels_resample.hip);
+    // the latent geometry, the captured pipeline and the durations stay at the model's rate.
+    void set_output_rate(int hz);
+    int output_rate() const { return resample_on() ? out_hz_ : a_.sample_rate; }
+    bool resample_on() const { return out_hz_ != 0 && out_hz_ != a_.sample_rate; }
+    int64_t out_len(int64_t W) const;  // samples per utterance a fetch returns for W native samples
+    // rows x W fp32 at in_hz -> rows x ceil(W * P / Q) at out_hz, as fp32 (y) and / or PCM (pcm); host pointers
+    void op_resample(int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -414,6 +424,16 @@ class Engine {
     int final_xt_ = 0;
     struct FetchSlot { int16_t* dev = nullptr; int16_t* pin = nullptr; size_t cap = 0, n = 0; hipEvent_t ready = nullptr, done = nullptr; bool busy = false; std::vector<float> dur; };
     FetchSlot fetch_[2];
+    int out_hz_ = 0;                  // requested output rate (0: the model's)
+    ResampleTable rs_, op_rs_;        // filter tables of the output rate and of op_resample (device copies owned here)
+    float* rs_f32_ = nullptr; size_t rs_f32_cap_ = 0;   // fetch-time scratch at the output rate (grow-only, outside the graph key)
+    int16_t* rs_pcm_ = nullptr; size_t rs_pcm_cap_ = 0;
+    void rs_prepare(ResampleTable& t, int in_hz, int out_hz);
+    const ResampleTable& rs_table();
+    void rs_release();
+    void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride);
+    float* rs_f32_buf(size_t n);
+    int16_t* rs_pcm_buf(size_t n);
     hipStream_t copy_s_ = nullptr;
     bool prof_on_ = false;
     std::vector<ProfSpan> spans_;

@@ -411,6 +411,19 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
 
 void Engine::batch_fetch(float* wav, size_t wav_capacity, float* duration) {
     Batch& b = bt_;
+    if (wav && resample_on()) {  // at the output rate: resampled on the stream, then copied
+        STN_HIP(hipSetDevice(device_));
+        const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, Wo = out_len(W);
+        const size_t no = (size_t)b.B * Wo;
+        if (wav_capacity < no) throw std::runtime_error("wav buffer too small: need " + std::to_string(no) + " floats");
+        const ResampleTable& t = rs_table();
+        float* d = rs_f32_buf(no);
+        resample_enqueue(t, b.wav, b.B, W, d, nullptr, Wo);
+        STN_HIP(hipMemcpyAsync(wav, d, no * 4, hipMemcpyDeviceToHost, s_));
+        sync();
+        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+        return;
+    }
     const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (wav) {
         if (wav_capacity < nw) throw std::runtime_error("wav buffer too small: need " + std::to_string(nw) + " floats");
@@ -424,6 +437,18 @@ void Engine::batch_fetch_pcm16(int16_t* pcm, size_t capacity, float* duration) {
     Batch& b = bt_;
     const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (resample_on()) {
+        const int64_t W = (int64_t)(nw / (size_t)b.B), Wo = out_len(W);
+        const size_t no = (size_t)b.B * Wo;
+        if (capacity < no) throw std::runtime_error("pcm buffer too small: need " + std::to_string(no) + " samples");
+        const ResampleTable& t = rs_table();
+        int16_t* d = rs_pcm_buf(no);
+        resample_enqueue(t, b.wav, b.B, W, nullptr, d, Wo);
+        STN_HIP(hipMemcpyAsync(pcm, d, no * 2, hipMemcpyDeviceToHost, s_));
+        sync();
+        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+        return;
+    }
     if (capacity < nw) throw std::runtime_error("pcm buffer too small: need " + std::to_string(nw) + " samples");
     ensure(b.pcm, b.pcm_cap, nw);
     launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)(nw / (size_t)b.B), b.pcm, (int64_t)(nw / (size_t)b.B));
@@ -436,7 +461,7 @@ void Engine::batch_fetch_pcm16_begin(int slot) {
     if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
     Batch& b = bt_;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    const size_t nw = (size_t)b.B * out_len((int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor);  // (output samples)
     FetchSlot& f = fetch_[slot];
     if (!copy_s_) STN_HIP(hipStreamCreateWithFlags(&copy_s_, hipStreamNonBlocking));
     if (!f.ready) { STN_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming)); STN_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming)); }
@@ -450,7 +475,12 @@ void Engine::batch_fetch_pcm16_begin(int slot) {
         STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap * sizeof(int16_t), hipHostMallocDefault));
         f.cap = cap;
     }
-    launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)(nw / (size_t)b.B), f.dev, (int64_t)(nw / (size_t)b.B));
+    if (resample_on()) {
+        const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+        resample_enqueue(rs_table(), b.wav, b.B, W, nullptr, f.dev, (int64_t)(nw / (size_t)b.B));
+    } else {
+        launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)(nw / (size_t)b.B), f.dev, (int64_t)(nw / (size_t)b.B));
+    }
     STN_HIP(hipEventRecord(f.ready, s_));
     STN_HIP(hipStreamWaitEvent(copy_s_, f.ready, 0));
     STN_HIP(hipMemcpyAsync(f.pin, f.dev, nw * sizeof(int16_t), hipMemcpyDeviceToHost, copy_s_));
@@ -472,6 +502,12 @@ void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) {
     Batch& b = bt_;
     const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (resample_on()) {
+        STN_HIP(hipSetDevice(device_));
+        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
+        resample_enqueue(rs_table(), b.wav, b.B, (int64_t)W, dst, nullptr, dst_stride);
+        return;
+    }
     if ((size_t)dst_stride < W) throw std::invalid_argument("dst_stride smaller than the waveform length");
     STN_HIP(hipMemcpy2DAsync(dst, (size_t)dst_stride * 4, b.wav, W * 4, W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
 }
@@ -480,6 +516,11 @@ void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) {
     Batch& b = bt_;
     const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (resample_on()) {
+        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
+        resample_enqueue(rs_table(), b.wav, b.B, (int64_t)W, nullptr, dst, dst_stride);
+        return;
+    }
     if ((size_t)dst_stride < W) throw std::invalid_argument("dst_stride smaller than the waveform length");
     launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)W, dst, dst_stride);
 }

@@ -213,6 +213,9 @@ static int for_all(stn_group* g, const char* what, int (*fn)(stn_handle*, const 
 int stn_group_load_synthetic(stn_group* g, const stn_arch* arch, uint64_t seed) {
     return for_all(g, "stn_load_synthetic", [](stn_handle* h, const void* a, uint64_t s) { return stn_load_synthetic(h, static_cast<const stn_arch*>(a), s); }, arch, seed);
 }
+int stn_group_set_output_rate(stn_group* g, int hz) {
+    return for_all(g, "stn_set_output_rate", [](stn_handle* h, const void*, uint64_t v) { return stn_set_output_rate(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)hz);
+}
 int stn_group_load_dir(stn_group* g, const char* onnx_dir) {
     return for_all(g, "stn_load_dir", [](stn_handle* h, const void* a, uint64_t) { return stn_load_dir(h, static_cast<const char*>(a)); }, onnx_dir, 0);
 }

@@ -2,6 +2,7 @@
 
 #include <cmath>
 #include <fstream>
+#include <numeric>
 #include <random>
 #include <stdexcept>
 
@@ -103,13 +104,14 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
     const SynthesisResult r = infer(chunks, std::vector<std::string>((size_t)n, lang), rep, total_step, speed);
     const size_t W = r.wav.size() / (size_t)n;
     const int chunk_size = cfgs_.ae.base_chunk_size * cfgs_.ttl.chunk_compress_factor;
-    const size_t n_sil = (size_t)(int)(silence_duration * (float)cfgs_.ae.sample_rate);
+    const size_t n_sil = (size_t)(int)(silence_duration * (float)getSampleRate());  // (zeros at the rate of the returned audio)
+    const int64_t rg = std::gcd(getSampleRate(), cfgs_.ae.sample_rate), rP = getSampleRate() / rg, rQ = cfgs_.ae.sample_rate / rg;
     SynthesisResult out;
     float dur_cat = 0.f;
     for (int i = 0; i < n; ++i) {
         const LatentGeometry g = latent_geometry({r.duration[(size_t)i]}, cfgs_.ae.sample_rate, cfgs_.ae.base_chunk_size,
                                                  cfgs_.ttl.chunk_compress_factor, cfgs_.ttl.latent_dim);
-        const size_t n_i = (size_t)g.L * (size_t)chunk_size;  // the wav length the chunk's own run would return
+        const size_t n_i = (size_t)(((int64_t)g.L * chunk_size * rP + rQ - 1) / rQ);  // the wav length the chunk's own run would return
         if (i > 0) {  // untrimmed chunk waves joined by zeros (cpp/helper.cpp:706-715)
             out.wav.insert(out.wav.end(), n_sil, 0.0f);
             dur_cat += r.duration[(size_t)i] + silence_duration;
@@ -171,8 +173,13 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         } else {
             throw std::runtime_error(load_err());
         }
+        if (opts.output_rate) {
+            if (grp) { if (stn_group_set_output_rate(grp, opts.output_rate) != STN_OK) throw std::runtime_error(std::string("output rate: ") + stn_group_last_error(grp)); }
+            else check(h, stn_set_output_rate(h, opts.output_rate));
+        }
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
+        tts->setOutputRate(opts.output_rate);
         if (synthetic) tts->markSynthetic();
         return tts;
     } catch (...) {

@@ -55,6 +55,8 @@ struct EngineOptions {
     int gpus = 1;                  // > 1: the batch is dealt over this many devices (include/stn_group.h: devices `device`, device + 1, ...;
                                    // weights replicated, 16-bit PCM gathered into the first over RCCL).  CLI --gpus N
     std::vector<int> devices;      // explicit ordinals instead (size = gpus); the same ordinal repeated = a rehearsal on one GPU
+    int output_rate = 0;           // Hz of the returned audio and the WAV files (resampled on the GPU, stn_set_output_rate); 0: the model's.
+                                   // CLI --sample-rate HZ
 };
 
 class TextToSpeech {
@@ -73,7 +75,9 @@ class TextToSpeech {
     // batch: one padded batch, no chunking (cpp/helper.cpp:725-734)
     SynthesisResult batch(const std::vector<std::string>& text_list, const std::vector<std::string>& lang_list,
                           const Style& style, int total_step, float speed = 1.05f);
-    int getSampleRate() const { return cfgs_.ae.sample_rate; }
+    // rate of the returned audio: the output rate when one is set, else the model's (cfgs.ae.sample_rate, which keeps sizing the latent)
+    int getSampleRate() const { return out_rate_ ? out_rate_ : cfgs_.ae.sample_rate; }
+    void setOutputRate(int hz) { out_rate_ = hz == cfgs_.ae.sample_rate ? 0 : hz; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
     bool synthetic() const { return synthetic_; }
@@ -88,6 +92,7 @@ class TextToSpeech {
     Config cfgs_;
     uint64_t noise_seed_;
     uint64_t calls_ = 0;
+    int out_rate_ = 0;  // 0: the model's rate
     bool synthetic_ = false;
 };
 

@@ -286,4 +286,22 @@ void launch_step_counters(hipStream_t s, float* tot /*[steps][B]*/, float* cur /
 // rows x W samples -> int16 PCM rows at pcm + row * dst_stride (dst_stride >= W)
 void launch_f32_to_pcm16(hipStream_t s, const float* w, int64_t rows, int W, int16_t* pcm, int64_t dst_stride);
 
+// Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
+// out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),
+// W_out = ceil(W * P / Q).  Supported: in and out rates in [8000, 192000] Hz with P <= 640.
+struct ResampleTable {
+    int in_hz = 0, out_hz = 0;
+    int P = 0, Q = 0, T = 0, off = 0;  // T: taps per phase (a multiple of 8); off: taps ahead of the centre tap
+    std::vector<float> taps;            // host copy, [P][T]
+    float* dev = nullptr;               // device copy (owned by whoever uploaded it)
+};
+constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P = 640;
+inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
+// Kaiser-windowed sinc for the pair (host only): fills f (not f.dev).  Empty string on success, else why the pair is refused.
+std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
+// rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride (dst_stride >= W_out): fp32, or int16 PCM converted exactly as
+// launch_f32_to_pcm16 converts (the PCM bytes are those of the fp32 output followed by that conversion)
+void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, float* y, int64_t dst_stride);
+void launch_resample_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int16_t* pcm, int64_t dst_stride);
+
 }  // namespace stn

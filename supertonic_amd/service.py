@@ -13,11 +13,11 @@ import os
 import threading
 import time
 import zipfile
-from typing import List, Union
+from typing import List, Optional, Union
 
 import numpy as np
 
-from . import host
+from . import binding, host
 from .tts import Style, load_text_to_speech, load_voice_style
 
 AVAILABLE_LANGS = host.AVAILABLE_LANGS
@@ -34,8 +34,8 @@ class _Job:
 
 class DynamicBatcher:
     """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed) into one engine batch.  A worker thread owns the engine: it takes the oldest job, waits up to
-    `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
+    (total_step, speed, output rate) into one engine batch (the engine's output rate covers a whole batch).  A worker thread owns
+    the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
     its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
 
     def __init__(self, tts, max_batch=128, max_wait_ms=3.0):
@@ -46,9 +46,10 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, total_step, speed):
-        """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n])."""
-        job = _Job(list(texts), lang, style, (int(total_step), float(speed)))
+    def submit(self, texts, lang, style, total_step, speed, sample_rate=None):
+        """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
+        waves (None: the model's)."""
+        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate)))
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -101,8 +102,9 @@ class DynamicBatcher:
                 langs = [j.lang for j in jobs for _ in j.texts]
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
-                step, speed = jobs[0].key
-                waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed)
+                step, speed, rate = jobs[0].key
+                extra = {} if rate is None else {"output_rate": rate}
+                waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
                 self.batches.append(len(texts))
                 o = 0
                 for j in jobs:
@@ -161,6 +163,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         speed: float = Field(1.05, gt=0.0)
         batch: bool = False
         silence_duration: float = Field(0.3, ge=0.0, description="Silence between chunks for non-batch mode.")
+        sample_rate: Optional[int] = Field(None, description="Output sample rate in Hz (resampled on the GPU); null: the model's rate.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -185,12 +188,19 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         except (OSError, KeyError, ValueError) as e:
             raise HTTPException(status_code=400, detail=f"voice_style: {e}")
         sr = tts.sample_rate
+        extra = {}
+        if req.sample_rate is not None:
+            why = binding.resample_error(tts.sample_rate, req.sample_rate)
+            if why:
+                raise HTTPException(status_code=400, detail=f"sample_rate {req.sample_rate} is not supported ({why}); supported: "
+                                                            + ", ".join(str(r) for r in binding.SUPPORTED_OUTPUT_RATES) + " Hz")
+            sr, extra = req.sample_rate, {"output_rate": req.sample_rate}
         if req.batch:
-            wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed)
+            wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
             chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
-            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed)
+            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate)
             wav, d = join_chunks(waves, durs, req.silence_duration, sr)
             chunks = [wav[: int(sr * d)]]
         if len(chunks) == 1:

@@ -6,6 +6,7 @@ Differences from the reference are confined to where the work happens: the four 
 (the C++ host is the contract where the reference's hosts disagree), and the chunks of a long text go
 through the engine as ONE batch (length-aware vocoder) instead of one `_infer` per chunk (py/helper.py:231-243)."""
 import json
+import math
 import os
 import secrets
 import threading
@@ -53,11 +54,15 @@ class TextToSpeech:
     returning (wav [B, W] float32, duration [B] float32).  One instance = one engine handle = one GPU; calls are
     serialised by a lock (the handle is single-threaded by contract)."""
 
-    def __init__(self, engine, text_processor, cfgs, noise_seed=None):
+    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None):
         self.engine = engine
         self.text_processor = text_processor
         self.cfgs = cfgs
-        self.sample_rate = cfgs["ae"]["sample_rate"]
+        self.sample_rate = cfgs["ae"]["sample_rate"]  # the model's rate: it sizes the latent (latent_geometry)
+        # rate of the returned audio (resampled on the GPU at fetch time, Engine.set_output_rate); None: the model's
+        self.output_rate = int(output_rate) if output_rate else self.sample_rate
+        if self.output_rate != self.sample_rate:
+            engine.set_output_rate(self.output_rate)
         self.base_chunk_size = cfgs["ae"]["base_chunk_size"]
         self.chunk_compress_factor = cfgs["ttl"]["chunk_compress_factor"]
         self.ldim = cfgs["ttl"]["latent_dim"]
@@ -71,7 +76,7 @@ class TextToSpeech:
         self._calls += 1
         return self.noise_seed + self._calls - 1
 
-    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False):
+    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None):
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         ids, mask = self.text_processor(text_list, lang_list)
@@ -81,11 +86,15 @@ class TextToSpeech:
             # just longer); a plain batch keeps the reference's exact [B, L * chunk] result
             self.engine.set_vocoder_mode(length_aware)
             self.engine.set_shape_buckets(length_aware)
+            if output_rate is not None:  # this call's rate (a fetch-time setting: no captured graph depends on it)
+                self.engine.set_output_rate(output_rate)
             try:
                 return self.engine.synthesize(ids, mask, style.ttl, style.dp, total_step, speed, noise_seed=self._seed())
             finally:
                 self.engine.set_vocoder_mode(False)
                 self.engine.set_shape_buckets(False)
+                if output_rate is not None:
+                    self.engine.set_output_rate(self.output_rate)
 
     def latent_lengths(self, durations):
         """Latent frames each utterance occupies (get_latent_mask, py/helper.py:276-282) from its returned duration."""
@@ -93,14 +102,21 @@ class TextToSpeech:
                                           self.chunk_compress_factor, self.ldim)
         return np.asarray(lens)
 
-    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05):
+    def out_samples(self, n, output_rate=None):
+        """Samples at the output rate that n model-rate samples resample to: ceil(n * P / Q)."""
+        out = int(output_rate or self.output_rate)
+        g = math.gcd(out, self.sample_rate)
+        P, Q = out // g, self.sample_rate // g
+        return -(-int(n) * P // Q)
+
+    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
-        returns a list of per-utterance waves of L_i * chunk_size samples and the durations.  The building block of the
-        long-form path and of the service's dynamic batching."""
-        wav, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True)
+        returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
+        and the durations.  The building block of the long-form path and of the service's dynamic batching."""
+        wav, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate)
         cs = self.base_chunk_size * self.chunk_compress_factor
         lens = [int(self.latent_lengths(dur[i:i + 1])[0]) for i in range(len(text_list))]
-        return [wav[i, : min(n * cs, wav.shape[1])] for i, n in enumerate(lens)], dur
+        return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
     def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3):
         if style.ttl.shape[0] != 1:
@@ -111,7 +127,7 @@ class TextToSpeech:
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
         waves, dur = self.solo_batch(chunks, [lang] * n, rep, total_step, speed)
-        silence = np.zeros(int(silence_duration * self.sample_rate), np.float32)
+        silence = np.zeros(int(silence_duration * self.output_rate), np.float32)
         parts, dur_cat = [], None
         for i, w in enumerate(waves):  # untrimmed chunk waves joined by zeros (py/helper.py:235-243)
             if i == 0:
@@ -122,8 +138,8 @@ class TextToSpeech:
             parts.append(w)
         return np.concatenate(parts)[None, :], np.array([dur_cat], np.float32)
 
-    def batch(self, text_list, lang_list, style, total_step, speed=1.05):
-        return self._infer(text_list, lang_list, style, total_step, speed)
+    def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None):
+        return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate)
 
 
 def load_cfgs(onnx_dir):
@@ -131,11 +147,12 @@ def load_cfgs(onnx_dir):
         return json.load(f)
 
 
-def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None):
+def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None):
     """py/helper.py:316-337.  use_gpu=True is the only mode (the reference only had the CPU one).  An unusable asset directory is an
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
-    weights (benchmarks and tests on machines without the Hugging Face assets), and it says so."""
+    weights (benchmarks and tests on machines without the Hugging Face assets), and it says so.  `output_rate` (Hz): the rate of the
+    returned audio, resampled on the GPU (include/stn.h, stn_set_output_rate); None returns the model's rate."""
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
     if not use_gpu:
@@ -157,6 +174,6 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
                 "ttl": {"chunk_compress_factor": a.chunk_compress_factor, "latent_dim": a.latent_dim}}
         tp = host.UnicodeProcessor(host.synthetic_indexer())
         synthetic = True
-    tts = TextToSpeech(eng, tp, cfgs, noise_seed)
+    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate)
     tts.synthetic = synthetic
     return tts
