@@ -274,6 +274,26 @@ int stn_dbg_fold_run_frames(const int32_t* latent_lengths, int B, int n_cu);
 /* ---- op-level entry points used by the kernel parity tests (host pointers) -------------------------- */
 int stn_op_gemm(stn_handle* h, int dtype, int M, int N, int K, const float* A /*[M,K]*/, const float* W /*[N,K]*/,
                 const float* bias_or_null, int act /*0 none,1 gelu,2 silu*/, float* out /*[M,N]*/);
+/* One GEMM, acc[m][n] = sum_k A[m][k] W[n][k], through the engine's launcher with the epilogue fields the engine uses (the kernel parity tests
+ * of every GEMM form).  Operands are rounded to the engine's format `dtype` first.  mode 0 (store): out[m*ldo + n] = act(acc + bias[n]) * keep(m),
+ * stored as out_dtype (STN_DTYPE_F32 or `dtype` itself); mode 1 (residual): out[m*ldo + n] = (out + gamma[n] (acc + bias[n]) + rowvec[seq(m)][n])
+ * * keep(m) in fp32; mode 2 (transposed store): out[(b*N + n)*L + t] = (acc + bias[n]) * keep(m) in fp32, row m = b*L + t.  act: 0 none,
+ * 1 GELU, 2 SiLU, 3 GELU in the tanh form.  keep(m) = 0 where len[b] <= t (len: nseq entries, 0..L); seq(m) = row_b[m] (packed rows, M
+ * entries in 0..nseq-1; not with len) or m / L.  rowvec: [nseq][N].  nt = 1: non-temporal 16-bit stores.  tr: -1 the launcher's choice,
+ * 0 / 1 force the tiled kernels' 16-bit store through the fp32 slab / the transposed image.  `out` is the caller's whole buffer of out_elems
+ * floats (modes 0, 1: at least M*ldo, ldo >= N; mode 2: at least ceil(M/L)*N*L, nseq >= ceil(M/L)): uploaded as given (rounded to
+ * out_dtype first) and written back whole (16-bit values widened to fp32, exactly), so what lies around the written region can be checked.
+ * form: the form that ran (as stn_dbg_gemm_form), NUL-terminated, truncated to form_cap; may be NULL. */
+int stn_op_gemm_ex(stn_handle* h, int dtype, int M, int N, int K, const float* A /*[M,K]*/, const float* W /*[N,K]*/, int mode, int act,
+                   int out_dtype, int ldo, const float* bias_or_null, const float* gamma_or_null, const int32_t* len_or_null, int L,
+                   const int32_t* row_b_or_null, const float* rowvec_or_null, int nseq, int nt, int tr, float* out, int64_t out_elems,
+                   char* form, size_t form_cap);
+/* diagnostics (no device needed): the form the engine's GEMM launcher takes for this call — kernel family, tile template arguments
+ * <BM,BN,WM,WN,NSTAGE,KS,ESZ> and configuration, 16-bit store form (tr = transposed image, slab = fp32 slab through LDS, lane = per-lane
+ * stores) and split-K factor, e.g. "tiled<128,128,2,4,4,64,2> cfg8 tr", "ring_vec slab", "splitk6+tiled<64,64,2,2,4,32,4> slab".
+ * Operands K-contiguous with lda = ldw = K and 16-byte aligned pointers; masked != 0: a row mask by length; tr as stn_op_gemm_ex.
+ * Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher refuses (STN_ERR_INVALID). */
+int stn_dbg_gemm_form(int dtype, int M, int N, int K, int mode, int out_dtype, int ldo, int masked, int tr, char* out, size_t cap);
 /* device-resident timing of one GEMM shape on random operands; mode 0 = bias+GELU store, 1 = residual epilogue */
 int stn_op_gemm_bench(stn_handle* h, int dtype, int M, int N, int K, int mode, int iters, double* avg_ms);
 /* diagnostics: shader-clock phase stamps of ONE launch of the tiled GEMM kernel on this shape (mode as above).  out6 = mean

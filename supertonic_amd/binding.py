@@ -14,7 +14,8 @@ _LIB = None
 F32, BF16, F16 = 0, 1, 2
 _DTYPES = {"f32": F32, "fp32": F32, "float32": F32, "bf16": BF16, "f16": F16, "fp16": F16, "float16": F16, "half": F16,
            F32: F32, BF16: BF16, F16: F16}
-ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
+ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_TANH = 0, 1, 2, 3
+EPI_STORE, EPI_RESID, EPI_STORE_T = 0, 1, 2  # GEMM epilogue modes (stn_op_gemm_ex)
 
 
 class StnError(RuntimeError):
@@ -156,6 +157,8 @@ def load():
     L.stn_dbg_xattn_hs_stamps.restype = ctypes.c_int64
     L.stn_dbg_fold_run_frames.argtypes = [vp, ctypes.c_int, ctypes.c_int]
     L.stn_dbg_fold_run_frames.restype = ctypes.c_int
+    L.stn_dbg_gemm_form.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_gemm_form.restype = ctypes.c_int
     L.stn_launch_log.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_launch_log.restype = ctypes.c_int64
     L.stn_profile_enable.argtypes = [vp, ci]
@@ -165,6 +168,8 @@ def load():
                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double)]
     L.stn_op_gemm.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, vp, ci, _f32p]
+    L.stn_op_gemm_ex.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, ci, ci, _f32p,
+                                 ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_gemm_bench.argtypes = [vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     L.stn_op_gemm_phases.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     L.stn_op_dwconv_ln.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -304,6 +309,17 @@ def fold_run_frames(latent_lengths, n_cu=256):
     if r < 0:
         raise StnError(r, "stn_dbg_fold_run_frames: bad arguments")
     return int(r)
+
+
+def gemm_form(dtype, M, N, K, mode=EPI_STORE, out_dtype="f32", ldo=None, masked=False, tr=-1):
+    """The form the engine's GEMM launcher takes for this call (stn_dbg_gemm_form; host-only), e.g. "tiled<128,128,2,4,4,64,2> cfg8 tr".
+    Where the form is tiled, the string names the kernel template arguments <BM,BN,WM,WN,NSTAGE,KS,ESZ>."""
+    buf = ctypes.create_string_buffer(128)
+    r = load().stn_dbg_gemm_form(_DTYPES[dtype], int(M), int(N), int(K), int(mode), _DTYPES[out_dtype], int(N if ldo is None else ldo),
+                                 int(bool(masked)), int(tr), buf, len(buf))
+    if r < 0:
+        raise StnError(r, "stn_dbg_gemm_form: the launcher refuses this call")
+    return buf.value.decode()
 
 
 def _c(a, dt):
@@ -630,6 +646,31 @@ class Engine:
         self._ck(self._lib.stn_op_gemm(self._h, self.dtype if dtype is None else _DTYPES[dtype], M, N, K,
                                        _c(A, np.float32), _c(W, np.float32), bptr, act, out))
         return out
+
+    def op_gemm_ex(self, A, W, out, mode=EPI_STORE, act=ACT_NONE, out_dtype="f32", ldo=None, bias=None, gamma=None, len=None, L=1,
+                   row_b=None, rowvec=None, nt=0, tr=-1, dtype=None):
+        """One GEMM through the engine's launcher with the given epilogue (stn_op_gemm_ex).  `out` is the whole destination buffer (the residual
+        for EPI_RESID): a copy goes up, the result comes back as a new fp32 array of the same shape.  len / rowvec: one entry / row per sequence.
+        Returns (result, form string)."""
+        M, K = A.shape
+        N = W.shape[0]
+        res = np.array(out, dtype=np.float32, order="C", copy=True)
+        nseq = 0
+        for v in (len, rowvec):
+            if v is not None:
+                nseq = max(nseq, np.asarray(v).shape[0])
+        if row_b is not None and rowvec is None:
+            nseq = max(nseq, int(np.max(row_b)) + 1)
+        _b, bp = _opt(bias, np.float32)
+        _g, gp = _opt(gamma, np.float32)
+        _l, lp = _opt(len, np.int32)
+        _r, rp = _opt(row_b, np.int32)
+        _v, vp_ = _opt(rowvec, np.float32)
+        form = ctypes.create_string_buffer(128)
+        self._ck(self._lib.stn_op_gemm_ex(self._h, self.dtype if dtype is None else _DTYPES[dtype], M, N, K, _c(A, np.float32), _c(W, np.float32),
+                                          int(mode), int(act), _DTYPES[out_dtype], int(N if ldo is None else ldo), bp, gp, lp, int(L), rp, vp_, nseq,
+                                          int(nt), int(tr), res.reshape(-1), res.size, form, ctypes.sizeof(form)))
+        return res, form.value.decode()
 
     def op_gemm_bench(self, M, N, K, mode=0, iters=20, dtype=None):
         ms = ctypes.c_double()

@@ -407,6 +407,43 @@ int stn_op_gemm(stn_handle* h, int dtype, int M, int N, int K, const float* A, c
                  need(K % (dtype != STN_DTYPE_F32 ? 8 : 4) == 0, "stn_op_gemm: K must be a multiple of 8 (bf16) / 4 (f32)");
                  h->eng->op_gemm(dtype, M, N, K, A, W, bias, act, out); })
 }
+int stn_op_gemm_ex(stn_handle* h, int dtype, int M, int N, int K, const float* A, const float* W, int mode, int act, int out_dtype, int ldo,
+                   const float* bias, const float* gamma, const int32_t* len, int L, const int32_t* row_b, const float* rowvec, int nseq, int nt,
+                   int tr, float* out, int64_t out_elems, char* form, size_t form_cap) {
+    STN_TRY(h, { need(M > 0 && N > 0 && K > 0 && A && W && out && L >= 1, "stn_op_gemm_ex: bad argument");
+                 need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_gemm_ex: unknown dtype");
+                 need(K % (dtype != STN_DTYPE_F32 ? 8 : 4) == 0, "stn_op_gemm_ex: K must be a multiple of 8 (16-bit) / 4 (f32)");
+                 need(mode == stn::EPI_STORE || mode == stn::EPI_RESID || mode == stn::EPI_STORE_T, "stn_op_gemm_ex: mode must be 0, 1 or 2");
+                 need(act >= stn::ACT_NONE && act <= stn::ACT_GELU_TANH, "stn_op_gemm_ex: unknown activation");
+                 need(out_dtype == STN_DTYPE_F32 || (mode == stn::EPI_STORE && out_dtype == dtype), "stn_op_gemm_ex: out_dtype must be f32 or the engine's dtype (store only)");
+                 need(nt == 0 || nt == 1, "stn_op_gemm_ex: nt must be 0 or 1");
+                 need(tr >= -1 && tr <= 1, "stn_op_gemm_ex: tr must be -1, 0 or 1");
+                 need(!(len && row_b), "stn_op_gemm_ex: len and row_b exclude each other");
+                 const int64_t seqs = ((int64_t)M + L - 1) / L;  // sequences m / L reaches
+                 if (mode == stn::EPI_STORE_T) {
+                     need(!row_b && nseq >= seqs && out_elems >= seqs * N * L, "stn_op_gemm_ex: mode 2 needs nseq >= ceil(M/L), out_elems >= ceil(M/L)*N*L, no row_b");
+                 } else {
+                     need(ldo >= N && out_elems >= (int64_t)M * ldo, "stn_op_gemm_ex: needs ldo >= N and out_elems >= M*ldo");
+                 }
+                 if (len || (rowvec && !row_b)) need(nseq >= seqs, "stn_op_gemm_ex: len / rowvec by m / L need nseq >= ceil(M/L)");
+                 if (rowvec || len || row_b) need(nseq > 0, "stn_op_gemm_ex: nseq must be > 0");
+                 if (len) for (int b = 0; b < nseq; ++b) need(len[b] >= 0 && len[b] <= L, "stn_op_gemm_ex: len out of [0, L]");
+                 if (row_b) for (int m = 0; m < M; ++m) need(row_b[m] >= 0 && row_b[m] < nseq, "stn_op_gemm_ex: row_b out of [0, nseq)");
+                 const std::string f = h->eng->op_gemm_ex(dtype, M, N, K, A, W, mode, act, out_dtype, ldo, bias, gamma, len, L, row_b, rowvec,
+                                                          nseq, nt, tr, out, out_elems);
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str()); })
+}
+int stn_dbg_gemm_form(int dtype, int M, int N, int K, int mode, int out_dtype, int ldo, int masked, int tr, char* out, size_t cap) {
+    if (M < 1 || N < 1 || K < 1 || (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16) || tr < -1 || tr > 1)
+        return STN_ERR_INVALID;
+    static const int dummy_len[4] = {};  // alignment is all the launcher reads of it
+    stn::Epilogue e;
+    e.mode = mode; e.out_dtype = out_dtype; e.ldo = ldo; e.len = masked ? dummy_len : nullptr; e.tr_force = tr;
+    std::string f;
+    try { f = stn::gemm_form(dtype, M, N, K, K, K, e, nullptr, nullptr).str(); } catch (const std::exception&) { return STN_ERR_INVALID; }
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
+}
 int stn_op_gemm_bench(stn_handle* h, int dtype, int M, int N, int K, int mode, int iters, double* avg_ms) {
     STN_TRY(h, { need(M > 0 && N > 0 && K > 0 && iters > 0 && avg_ms, "stn_op_gemm_bench: bad argument");
                  need(K % (dtype != STN_DTYPE_F32 ? 8 : 4) == 0, "K must be a multiple of 8 (bf16) / 4 (f32)");

@@ -529,14 +529,14 @@ void Engine::gemm(const char* tag, int dt, const void* A, int lda, const Linear&
         double out_b = (double)M * w.N * (e.mode == EPI_STORE ? (is_half(e.out_dtype) ? 2.0 : 4.0) : (e.mode == EPI_RESID ? 8.0 : 4.0));
         prof_begin(tag, 2.0 * M * (double)w.N * w.K, ((double)M * w.K + (double)w.N * w.K) * esz + out_b);
     }
-    const int sk = gemm_splitk_factor(dt, M, w.N, w.K, e);
-    if (sk > 1) {
+    const GemmForm f = gemm_form(dt, M, w.N, w.K, lda, w.K, e, A, w.w.as(dt));
+    if (f.split > 1) {
         const Arena::Mark mk = ar_.mark();
-        float* ws = f32_alloc((int64_t)sk * M * w.N);
-        launch_gemm_splitk(s_, dt, A, lda, w.w.as(dt), w.K, M, w.N, w.K, e, sk, ws);
+        float* ws = f32_alloc((int64_t)f.split * M * w.N);
+        launch_gemm_form(s_, f, A, lda, w.w.as(dt), w.K, M, w.N, w.K, e, ws);
         ar_.release(mk);  // stream order: the reduction has been enqueued behind the splits
     } else {
-        launch_gemm(s_, dt, A, lda, w.w.as(dt), w.K, M, w.N, w.K, e);
+        launch_gemm_form(s_, f, A, lda, w.w.as(dt), w.K, M, w.N, w.K, e, nullptr);
     }
     if (prof_on_) prof_end();
 }

@@ -275,6 +275,12 @@ class Engine {
 
     // ---- op-level test entry points (host pointers) ------------------------------------------------------
     void op_gemm(int dtype, int M, int N, int K, const float* A, const float* W, const float* bias, int act, float* out);
+    // one GEMM with the epilogue fields the engine uses (stn_op_gemm_ex): out [out_elems] fp32 is the whole destination buffer (EPI_RESID:
+    // the residual), uploaded as given (rounded to out_dtype first when that is 16-bit) and downloaded whole (widened back to fp32).
+    // len [nseq], row_b [M], rowvec [nseq][N].  tr >= 0 forces the tiled kernels' 16-bit store form.  Returns the form it ran (GemmForm::str).
+    std::string op_gemm_ex(int dtype, int M, int N, int K, const float* A, const float* W, int mode, int act, int out_dtype, int ldo,
+                           const float* bias, const float* gamma, const int* len, int L, const int* row_b, const float* rowvec, int nseq,
+                           int nt, int tr, float* out, int64_t out_elems);
     void op_attention(int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k, const float* v,
                       const int* qlen, const int* klen, int rope_mode, float* o);
     void op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,

@@ -30,11 +30,53 @@ void Engine::op_gemm(int dtype, int M, int N, int K, const float* A, const float
         pa = a16; pw = w16;
     }
     Epilogue e; e.mode = EPI_STORE; e.act = act; e.out_dtype = F32; e.out = dO; e.ldo = N; e.bias = dB;
-    const int sk = gemm_splitk_factor(dtype, M, N, K, e);  // the same decision the model path takes (Engine::gemm)
-    if (sk > 1) launch_gemm_splitk(s_, dtype, pa, K, pw, K, M, N, K, e, sk, f32_alloc((int64_t)sk * M * N));
-    else launch_gemm(s_, dtype, pa, K, pw, K, M, N, K, e);
+    const GemmForm f = gemm_form(dtype, M, N, K, K, K, e, pa, pw);  // the same decision the model path takes (Engine::gemm)
+    launch_gemm_form(s_, f, pa, K, pw, K, M, N, K, e, f.split > 1 ? f32_alloc((int64_t)f.split * M * N) : nullptr);
     STN_HIP(hipMemcpyAsync(out, dO, (size_t)M * N * 4, hipMemcpyDeviceToHost, s_));
     sync();
+}
+
+std::string Engine::op_gemm_ex(int dtype, int M, int N, int K, const float* A, const float* W, int mode, int act, int out_dtype, int ldo,
+                               const float* bias, const float* gamma, const int* len, int L, const int* row_b, const float* rowvec, int nseq,
+                               int nt, int tr, float* out, int64_t out_elems) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    float* dA = up(ar_, s_, A, (size_t)M * K);
+    float* dW = up(ar_, s_, W, (size_t)N * K);
+    const void* pa = dA;
+    const void* pw = dW;
+    if (is_half(dtype)) {
+        void* a16 = ar_.alloc((size_t)M * K * 2);
+        void* w16 = ar_.alloc((size_t)N * K * 2);
+        launch_cast(s_, dtype, dA, (int64_t)M * K, a16);
+        launch_cast(s_, dtype, dW, (int64_t)N * K, w16);
+        pa = a16; pw = w16;
+    }
+    float* dO = up(ar_, s_, out, (size_t)out_elems);
+    void* o16 = nullptr;
+    if (mode == EPI_STORE && out_dtype != F32) {
+        o16 = ar_.alloc((size_t)out_elems * 2);
+        launch_cast(s_, out_dtype, dO, out_elems, o16);
+    }
+    Epilogue e;
+    e.mode = mode; e.act = act; e.out_dtype = mode == EPI_STORE ? out_dtype : F32; e.ldo = ldo;
+    e.out = mode == EPI_RESID ? nullptr : (o16 ? o16 : static_cast<void*>(dO));
+    e.resid = mode == EPI_RESID ? dO : nullptr;
+    e.bias = bias ? up(ar_, s_, bias, (size_t)N) : nullptr;
+    e.gamma = gamma ? up(ar_, s_, gamma, (size_t)N) : nullptr;
+    e.len = len ? up(ar_, s_, len, (size_t)nseq) : nullptr;
+    e.L = L;
+    e.row_b = row_b ? up(ar_, s_, row_b, (size_t)M) : nullptr;
+    e.rowvec = rowvec ? up(ar_, s_, rowvec, (size_t)nseq * N) : nullptr;
+    e.rv_ld = N;
+    e.nt = nt;
+    e.tr_force = tr;
+    const GemmForm f = gemm_form(dtype, M, N, K, K, K, e, pa, pw);  // the split-K decision of Engine::gemm included
+    launch_gemm_form(s_, f, pa, K, pw, K, M, N, K, e, f.split > 1 ? f32_alloc((int64_t)f.split * M * N) : nullptr);
+    if (o16) launch_half_to_f32(s_, out_dtype, o16, out_elems, dO);
+    STN_HIP(hipMemcpyAsync(out, dO, (size_t)out_elems * 4, hipMemcpyDeviceToHost, s_));
+    sync();
+    return f.str();
 }
 
 void Engine::op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,

@@ -65,11 +65,11 @@ typedef _Float16 f16_t;                                          // storage type
 enum ActFn : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_GELU_TANH = 3 };  // GELU: erf form; GELU_TANH: 0.5 x (1 + tanh(sqrt(2/pi)(x + 0.044715 x^3)))
 
 // GEMM epilogue description:  acc[m][n] = sum_k A[m][k] * W[n][k]
+// (the order matters: EPI_STORE and EPI_RESID are the 16-byte vector epilogues, every mode above EPI_RESID transposes per lane)
 enum EpiMode : int {
     EPI_STORE = 0,    // out[m*ldo + n] = act(acc + bias[n]) * rowmask(m)        (out dtype = out_dtype)
-    EPI_RESID = 1,    // resid[m*ldo+n] = (resid + gamma[n]*(acc+bias[n])) * rowmask(m)      (fp32, in place)
-    EPI_EULER_T = 2,  // out[b][n][t] = (aux[b][n][t] + (acc+bias[n]) * row_scale[b]) * rowmask   (fp32, [B,N,L])
-    EPI_STORE_T = 3,  // out[b][n][t] = (acc+bias[n]) * rowmask                                  (fp32, [B,N,L])
+    EPI_RESID = 1,    // resid[m*ldo+n] = (resid + gamma[n]*(acc+bias[n]) + rowvec[b]) * rowmask(m)      (fp32, in place)
+    EPI_STORE_T = 2,  // out[b][n][t] = (acc+bias[n]) * rowmask                                  (fp32, [B,N,L])
 };
 
 struct Epilogue {
@@ -77,14 +77,12 @@ struct Epilogue {
     int act = ACT_NONE;
     int out_dtype = F32;         // EPI_STORE only
     const float* bias = nullptr; // [N] or null
-    void* out = nullptr;         // EPI_STORE / *_T destination
+    void* out = nullptr;         // EPI_STORE / EPI_STORE_T destination
     int ldo = 0;                 // row stride of out / resid (elements)
     const float* gamma = nullptr;// [N] layer-scale (EPI_RESID) or null
     float* resid = nullptr;      // EPI_RESID
     const int* len = nullptr;    // [B] valid rows per sequence (null -> no row mask)
     int L = 1;                   // rows per sequence (row m -> b = m / L, t = m % L)
-    const float* aux = nullptr;  // EPI_EULER_T: previous latent [B,N,L]
-    const float* row_scale = nullptr; // EPI_EULER_T: per-b scale (dt)
     const int* row_b = nullptr;       // packed rows: sequence of row m (replaces m / L for rowvec; len must be null then)
     const float* rowvec = nullptr;    // EPI_RESID: per-sequence vector [B][rv_ld] added to every row of sequence b (time
     int rv_ld = 0;                    //            conditioning): resid = (resid + gamma*(acc+bias) + rowvec[b]) * keep
@@ -94,14 +92,44 @@ struct Epilogue {
                                       // pw2 were measured too and cost +9 % (each A panel is read by two column tiles), non-temporal loads of the old residual in pw2's
                                       // epilogue +3 %: so there are none
     int tr_epilogue = 0;              // tiled kernels, bf16 store: wave-private transposed-image epilogue (set by the launcher)
+    int tr_force = -1;                // tests only (stn_op_gemm_ex; the engine never sets it): >= 0 replaces the launcher's choice of
+                                      // tr_epilogue with this value (0 = fp32 slab store, 1 = transposed image)
     unsigned long long* ts = nullptr; // diagnostics (tiled kernels): 4 shader-clock stamps per workgroup — entry, first
                                       // stage landed, K-loop done, epilogue done (stn_op_gemm_phases)
 };
 
-// A: [M][lda] (dtype), W: [N][ldw] (same dtype), K % 8 == 0 (bf16) / K % 4 == 0 (f32), 16-byte aligned rows.
+// The form a GEMM call takes — one decision, made by gemm_form and executed by launch_gemm_form, so that what the diagnostics report
+// (stn_dbg_gemm_form, stn_op_gemm_ex) is what runs:
+//   GK_TILED     gemm_tiled_kernel, configuration `cfg` (launch_tiled_auto's table: 1..18 for 16-bit operands, GEMM_CFG_F32_64 /
+//                GEMM_CFG_F32_128 for the fp32 tiles) with template arguments bm..esz
+//   GK_RING_VEC  gemm_bf16_ring_kernel<VEC = true>, GK_RING  <VEC = false>
+//   GK_REG       the register-staged gemm_bf16_kernel / gemm_f32_kernel
+// split > 1: deterministic split-K — the fields above describe the launch of the fp32 partial sums (plain store), and
+// splitk_reduce_kernel applies the real epilogue (per lane).
+enum GemmKernel : int { GK_TILED = 0, GK_RING_VEC = 1, GK_RING = 2, GK_REG = 3 };
+enum GemmEpiForm : int { GE_LANE = 0, GE_SLAB = 1, GE_TR = 2 };  // per-lane stores, fp32 slab through LDS, transposed 16-bit image
+constexpr int GEMM_CFG_F32_64 = 19, GEMM_CFG_F32_128 = 20;
+struct GemmForm {
+    int dtype = F32, mode = EPI_STORE;
+    int kernel = GK_REG;
+    int cfg = 0;
+    int bm = 128, bn = 128, wm = 2, wn = 2, nstage = 2, ks = 64, esz = 2;  // tile template arguments (GK_TILED)
+    int epi = GE_LANE;
+    int tr_epilogue = 0;              // the value the tiled kernel receives
+    int split = 1;
+    std::string str() const;          // e.g. "tiled<128,128,2,4,4,64,2> cfg8 tr", "ring_vec slab", "splitk6+tiled<64,64,2,2,4,32,4> slab"
+};
+// A: [M][lda] (dtype), W: [N][ldw] (same dtype), K % 8 == 0 (16-bit) / K % 4 == 0 (f32), 16-byte aligned rows.  A and W are read
+// for their alignment only (null is aligned); so are e.out / e.resid / e.bias / e.gamma.  allow_split = false: never split-K (a
+// caller without a workspace).  Throws std::invalid_argument where the operands violate the kernel contract.
+GemmForm gemm_form(int dtype, int M, int N, int K, int lda, int ldw, const Epilogue& e, const void* A, const void* W, bool allow_split = true);
+// runs form f (from gemm_form on the same arguments); workspace: [f.split][M][N] fp32 when f.split > 1, else unused
+void launch_gemm_form(hipStream_t s, const GemmForm& f, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                      const Epilogue& e, float* workspace);
+// gemm_form(..., allow_split = false) and launch_gemm_form in one call
 void launch_gemm(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                  const Epilogue& e);
-// Deterministic split-K for tiny-M, long-K GEMMs: gemm_splitk_factor says how many ways to split (1 = don't);
+// Deterministic split-K for tiny-M, long-K GEMMs: gemm_splitk_factor says how many ways to split (1 = don't; gemm_form's rule);
 // launch_gemm_splitk runs the splits into `workspace` ([S][M][N] fp32) and reduces them in split order with epilogue e.
 int gemm_splitk_factor(int dtype, int M, int N, int K, const Epilogue& e);
 void launch_gemm_splitk(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epilogue& e,

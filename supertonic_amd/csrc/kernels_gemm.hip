@@ -15,7 +15,8 @@
 //       row mask or packed-row sequence lookup, per-sequence time vector.
 //   gemm_bf16_ring_kernel   128x128, K % 32 == 0 but epilogue operands not 16-byte aligned (rare).
 //   gemm_bf16_kernel / gemm_f32_kernel   128x128, register-staged double buffer: any K % 8 (bf16) / % 4 (fp32), and the
-//       transposing epilogues (EPI_STORE_T, EPI_EULER_T) of the host-pointer stages.
+//       transposing epilogue (EPI_STORE_T) of the text encoder's [B,N,L] projection.
+// Which of them a call takes, with which tile and epilogue, is decided in one place: gemm_form (launch_gemm_form runs it).
 // Workgroup -> tile map is XCD-aware: the tiles that share an A row-panel are consecutive and land on
 // one XCD (private 4 MiB L2), the bijective remap of the CDNA4 guide.
 #include "kernels.hpp"
@@ -53,7 +54,7 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[2]
         bias[ni] = (ok && e.bias) ? e.bias[ncol[ni]] : 0.f;
         gam[ni] = (ok && e.gamma) ? e.gamma[ncol[ni]] : 1.f;
     }
-    const bool need_bt = (e.len != nullptr) || MODE >= EPI_EULER_T || (MODE == EPI_RESID && e.rowvec != nullptr);
+    const bool need_bt = (e.len != nullptr) || MODE == EPI_STORE_T || (MODE == EPI_RESID && e.rowvec != nullptr);
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
@@ -84,9 +85,6 @@ __device__ __forceinline__ void run_epilogue(const Epilogue& e, f32x16 (&acc)[2]
                     const size_t o = (size_t)m * e.ldo + n;
                     const float rv = e.rowvec ? e.rowvec[(size_t)b * e.rv_ld + n] : 0.f;
                     e.resid[o] = (e.resid[o] + gam[ni] * v + rv) * keep;
-                } else if (MODE == EPI_EULER_T) {
-                    const size_t o = ((size_t)b * N + n) * e.L + t;
-                    reinterpret_cast<float*>(e.out)[o] = keep != 0.f ? (e.aux[o] + v * e.row_scale[b]) : 0.f;
                 } else {  // EPI_STORE_T
                     const size_t o = ((size_t)b * N + n) * e.L + t;
                     reinterpret_cast<float*>(e.out)[o] = v * keep;
@@ -378,7 +376,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_ring_kernel(const uint16_t* _
     }
 #undef STN_ISSUE
 
-    if (!VEC || MODE >= EPI_EULER_T) {
+    if (!VEC || MODE > EPI_RESID) {
         run_epilogue<MODE, F16>(e, acc, m0 + wm * 64, n0 + wn * 64, M, N, lane);
         return;
     }
@@ -808,138 +806,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tiled_kernel(const void* __r
     }
 }
 
-template <int MODE, int BM_, int BN_, int WM, int WN, int NSTAGE, int KS, int ESZ = 2, bool F16 = false>
-static void launch_tiled(hipStream_t s, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epilogue& e) {
-    constexpr int RPP_ = 1024 / (KS * ESZ), NW_ = WM * WN;
-    constexpr bool GEN_ = (BM_ / RPP_) % NW_ != 0 || (BN_ / RPP_) % NW_ != 0;
-    constexpr size_t lds = (size_t)NSTAGE * (BM_ + BN_) * KS * ESZ + (GEN_ ? (size_t)NW_ * 1024 : 0);  // + padding-slot scratch
-    static PerDeviceOnce attr_once;
-    if (attr_once.need()) {
-        stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tiled_kernel<MODE, BM_, BN_, WM, WN, NSTAGE, KS, ESZ, F16>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "hipFuncSetAttribute(gemm_tiled)");
-    }
-    const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_, ntiles = tiles_m * tiles_n;
-    const int ksp = e.ksplit > 1 ? e.ksplit : 1;
-    if (ksp > 1 && (MODE != EPI_STORE || (K / KS) % ksp != 0)) { throw std::invalid_argument("split-K needs a plain store epilogue and K/KS divisible by the split"); }
-    STN_KLAUNCH((gemm_tiled_kernel<MODE, BM_, BN_, WM, WN, NSTAGE, KS, ESZ, F16>), dim3(ntiles * ksp), dim3(WM * WN * 64), lds, s, A, lda,
-                       W, ldw, M, N, K, tiles_n, ntiles, e);
-}
-
-// tile-shape selection for the vectorised-epilogue path; STN_GEMM_CFG=<n> forces one bf16 shape (experiments)
-static int g_gemm_cfg = -2;
-template <int MODE>
-static bool launch_tiled_auto(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                              const Epilogue& e) {
-    if (dtype == F32) {
-        // fp32 MFMA is 1/16 of the bf16 rate: always compute-bound, tile choice only has to keep the CUs busy
-        if (K % 32) return false;
-        // (a narrow N leaves few 128-wide tiles: the duration predictor's 9 k x 128 pw2 is 71 of them on 256 CUs)
-        if (M <= 64 || (long)((M + 127) / 128) * ((N + 127) / 128) < 160) launch_tiled<MODE, 64, 64, 2, 2, 4, 32, 4>(s, A, lda, W, ldw, M, N, K, e);
-        else launch_tiled<MODE, 128, 128, 2, 2, 3, 32, 4>(s, A, lda, W, ldw, M, N, K, e);
-        return true;
-    }
-    if (g_gemm_cfg == -2) { const char* c = stn::dev_env("STN_GEMM_CFG"); g_gemm_cfg = c ? atoi(c) : -1; }
-    int cfg = g_gemm_cfg;
-    if (cfg < 0) {
-        // measured on MI355X (tools/gemm_bench.py): the 256x256 tile halves the operand bytes per FLOP and wins whenever
-        // it still yields ~a full wave of workgroups (1 per CU); otherwise the 128x128 tile with 128-byte rows keeps more
-        // CUs busy; tiny M (single utterances) gets 64x64 tiles so that N is spread over more CUs.
-        const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-        if (N >= 256 && t256 >= 160) {  // (a packed batch leaves ~180 of these tiles: still better than 700 small ones)
-            const long t192 = (long)((M + 191) / 192) * ((N + 255) / 256);
-            if (t256 < 208 && t192 <= 256) cfg = 18;       // one thin round (packed batches): 192-row tiles refill the idle CUs (-7 %)
-            else if (t256 < 512) cfg = 11;                 // one round of tiles: 16 waves shorten the per-tile critical path
-            else if (K <= 512 && t256 >= 1024) cfg = 17;   // short K, many tiles: 256x128, 8 waves, 2 WGs/CU (4 % over the 4-wave form)
-            else cfg = 1;
-        } else if (K % 64 == 0) cfg = M <= 64 ? 12 : 8;
-        else return false;
-    }
-    if ((cfg == 5 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 12 || cfg == 13 || cfg == 14) && K % 64) return false;
-    static int g_tr = -2;
-    if (g_tr == -2) { const char* c = stn::dev_env("STN_GEMM_TR"); g_tr = c ? atoi(c) : 1; }
-    Epilogue et = e;
-    // the transposed-image epilogue stores 64-byte row segments (16 rows per instruction): a win where a CU runs one tile
-    // (-4 % ve.pw1, -15 % te.pw1), a loss where a co-resident workgroup's K loop competes for the vector-memory path (vo.pw1)
-    et.tr_epilogue = g_tr == 2 || (g_tr == 1 && (cfg == 11 || cfg == 8 || cfg == 12 || cfg == 13 || cfg == 14 || cfg == 18));
-    const Epilogue& e_ = et;
-    if (dtype == F16) {  // the shapes the heuristic above picks; STN_GEMM_CFG experiments stay bf16-only
-        switch (cfg) {
-            case 1: launch_tiled<MODE, 256, 256, 2, 4, 4, 32, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            case 8: launch_tiled<MODE, 128, 128, 2, 4, 4, 64, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            case 11: launch_tiled<MODE, 256, 256, 4, 4, 4, 32, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            case 12: launch_tiled<MODE, 64, 64, 2, 2, 4, 64, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            case 17: launch_tiled<MODE, 256, 128, 4, 2, 3, 32, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            case 18: launch_tiled<MODE, 192, 256, 3, 4, 4, 32, 2, true>(s, A, lda, W, ldw, M, N, K, e_); return true;
-            default: return false;
-        }
-    }
-    switch (cfg) {
-        case 1: launch_tiled<MODE, 256, 256, 2, 4, 4, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 2: launch_tiled<MODE, 256, 128, 4, 2, 5, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 3: launch_tiled<MODE, 128, 128, 2, 2, 8, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 4: launch_tiled<MODE, 128, 256, 2, 4, 5, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 5: launch_tiled<MODE, 128, 128, 2, 2, 4, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 6: launch_tiled<MODE, 128, 128, 2, 2, 3, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 7: launch_tiled<MODE, 256, 128, 4, 2, 3, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 8: launch_tiled<MODE, 128, 128, 2, 4, 4, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;
-        case 9: launch_tiled<MODE, 128, 256, 2, 2, 3, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;   // 72 KiB: 2 WGs / CU
-        case 10: launch_tiled<MODE, 256, 128, 2, 2, 3, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 72 KiB: 2 WGs / CU
-        case 11: launch_tiled<MODE, 256, 256, 4, 4, 4, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 16 waves
-        case 12: launch_tiled<MODE, 64, 64, 2, 2, 4, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;    // tiny M
-        case 13: launch_tiled<MODE, 128, 128, 4, 4, 4, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 16 waves, 4 per SIMD
-        case 14: launch_tiled<MODE, 128, 64, 4, 2, 4, 64>(s, A, lda, W, ldw, M, N, K, e_); return true;   // more tiles for narrow N
-        case 15: launch_tiled<MODE, 128, 128, 2, 2, 3, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 48 KiB: 3 WGs / CU
-        case 16: launch_tiled<MODE, 128, 256, 2, 4, 3, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 72 KiB, 8 waves: 2 WGs / CU
-        case 17: launch_tiled<MODE, 256, 128, 4, 2, 3, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 72 KiB, 8 waves: 2 WGs / CU
-        case 18: launch_tiled<MODE, 192, 256, 3, 4, 4, 32>(s, A, lda, W, ldw, M, N, K, e_); return true;  // 12 waves: 3/4 of config 11, same work per wave
-        default: return false;
-    }
-}
-
-void launch_gemm(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
-                 const Epilogue& e) {
-    if (M <= 0 || N <= 0) return;
-    const int kq = is_half(dtype) ? 8 : 4;
-    if (K <= 0 || K % kq || lda % kq || ldw % kq || (reinterpret_cast<uintptr_t>(A) & 15) ||
-        (reinterpret_cast<uintptr_t>(W) & 15)) { char m_[256]; snprintf(m_, sizeof m_, "launch_gemm: operand shape/alignment violates the kernel contract (K=%d lda=%d ldw=%d)", K,
-                lda, ldw); throw std::invalid_argument(m_); }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, ntiles = tiles_m * tiles_n;
-    // v2 ring kernel: bf16, K % 32 == 0.  Vectorised epilogue needs 16-B aligned 8-column groups.
-    const bool ring = is_half(dtype) && K % RK == 0;
-    const void* optr = e.mode == EPI_RESID ? static_cast<const void*>(e.resid) : e.out;
-    const bool vec_ok = e.mode <= EPI_RESID && N % 8 == 0 && e.ldo % 8 == 0 && !(reinterpret_cast<uintptr_t>(optr) & 15) &&
-                        (!e.bias || !(reinterpret_cast<uintptr_t>(e.bias) & 15)) && (!e.gamma || !(reinterpret_cast<uintptr_t>(e.gamma) & 15));
-    const bool vec = ring && vec_ok;
-    if (vec_ok && (ring || dtype == F32)) {
-        if (e.mode == EPI_STORE && launch_tiled_auto<EPI_STORE>(s, dtype, A, lda, W, ldw, M, N, K, e)) return;
-        if (e.mode == EPI_RESID && launch_tiled_auto<EPI_RESID>(s, dtype, A, lda, W, ldw, M, N, K, e)) return;
-    }
-#define STN_LAUNCH_H(MODE, F16_)                                                                                  \
-    if (ring && vec)                                                                                             \
-        STN_KLAUNCH((gemm_bf16_ring_kernel<MODE, true, F16_>), dim3(ntiles), dim3(NT), 0, s,                    \
-                           static_cast<const uint16_t*>(A), lda, static_cast<const uint16_t*>(W), ldw, M, N, K, tiles_n, ntiles, e); \
-    else if (ring)                                                                                               \
-        STN_KLAUNCH((gemm_bf16_ring_kernel<MODE, false, F16_>), dim3(ntiles), dim3(NT), 0, s,                   \
-                           static_cast<const uint16_t*>(A), lda, static_cast<const uint16_t*>(W), ldw, M, N, K, tiles_n, ntiles, e); \
-    else                                                                                                         \
-        STN_KLAUNCH((gemm_bf16_kernel<MODE, F16_>), dim3(ntiles), dim3(NT), 0, s, static_cast<const uint16_t*>(A), \
-                           lda, static_cast<const uint16_t*>(W), ldw, M, N, K, tiles_n, ntiles, e);
-#define STN_LAUNCH(MODE)                                                                                         \
-    if (dtype == F16) { STN_LAUNCH_H(MODE, true) }                                                               \
-    else if (dtype == BF16) { STN_LAUNCH_H(MODE, false) }                                                        \
-    else                                                                                                         \
-        STN_KLAUNCH(gemm_f32_kernel<MODE>, dim3(ntiles), dim3(NT), 0, s, static_cast<const float*>(A),     \
-                           lda, static_cast<const float*>(W), ldw, M, N, K, tiles_n, ntiles, e);
-    switch (e.mode) {
-        case EPI_STORE: STN_LAUNCH(EPI_STORE) break;
-        case EPI_RESID: STN_LAUNCH(EPI_RESID) break;
-        case EPI_EULER_T: STN_LAUNCH(EPI_EULER_T) break;
-        default: STN_LAUNCH(EPI_STORE_T) break;
-    }
-#undef STN_LAUNCH
-#undef STN_LAUNCH_H
-}
-
 // ---------------------------------------------------------------------------------------------
 // split-K reduction: out = epilogue(sum over splits, in split order, of the fp32 partials).  Tiny-M GEMMs with a long K
 // (a single utterance's 49 x 384 x 1536 in exact fp32) otherwise run 48 K-steps on 6 workgroups.
@@ -990,6 +856,242 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int S, int 
     }
 }
 
+template <int MODE, int BM_, int BN_, int WM, int WN, int NSTAGE, int KS, int ESZ = 2, bool F16 = false>
+static void launch_tiled(hipStream_t s, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epilogue& e) {
+    constexpr int RPP_ = 1024 / (KS * ESZ), NW_ = WM * WN;
+    constexpr bool GEN_ = (BM_ / RPP_) % NW_ != 0 || (BN_ / RPP_) % NW_ != 0;
+    constexpr size_t lds = (size_t)NSTAGE * (BM_ + BN_) * KS * ESZ + (GEN_ ? (size_t)NW_ * 1024 : 0);  // + padding-slot scratch
+    static PerDeviceOnce attr_once;
+    if (attr_once.need()) {
+        stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tiled_kernel<MODE, BM_, BN_, WM, WN, NSTAGE, KS, ESZ, F16>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "hipFuncSetAttribute(gemm_tiled)");
+    }
+    const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_, ntiles = tiles_m * tiles_n;
+    const int ksp = e.ksplit > 1 ? e.ksplit : 1;
+    if (ksp > 1 && (MODE != EPI_STORE || (K / KS) % ksp != 0)) { throw std::invalid_argument("split-K needs a plain store epilogue and K/KS divisible by the split"); }
+    STN_KLAUNCH((gemm_tiled_kernel<MODE, BM_, BN_, WM, WN, NSTAGE, KS, ESZ, F16>), dim3(ntiles * ksp), dim3(WM * WN * 64), lds, s, A, lda,
+                       W, ldw, M, N, K, tiles_n, ntiles, e);
+}
+
+// The tile configurations of gemm_tiled_kernel: <BM, BN, WM, WN, NSTAGE, KS, ESZ>.  1..18 are 16-bit (the heuristic in gemm_form picks
+// 1, 8, 11, 12, 17 and 18, the only ones instantiated for IEEE half; the rest are the tile sweeps STN_GEMM_CFG=<n> forces, bf16 only),
+// 19 and 20 the exact-fp32 tiles.  The launch instantiates the template from this table, so the form reported is the one launched.
+struct TileShape { int bm, bn, wm, wn, ns, ks, esz; };
+static constexpr TileShape kTiles[21] = {
+    {0, 0, 0, 0, 0, 0, 0},
+    {256, 256, 2, 4, 4, 32, 2},  // 1
+    {256, 128, 4, 2, 5, 32, 2},  // 2
+    {128, 128, 2, 2, 8, 32, 2},  // 3
+    {128, 256, 2, 4, 5, 32, 2},  // 4
+    {128, 128, 2, 2, 4, 64, 2},  // 5
+    {128, 128, 2, 2, 3, 64, 2},  // 6
+    {256, 128, 4, 2, 3, 64, 2},  // 7
+    {128, 128, 2, 4, 4, 64, 2},  // 8
+    {128, 256, 2, 2, 3, 32, 2},  // 9: 72 KiB, 2 WGs / CU
+    {256, 128, 2, 2, 3, 32, 2},  // 10: 72 KiB, 2 WGs / CU
+    {256, 256, 4, 4, 4, 32, 2},  // 11: 16 waves
+    {64, 64, 2, 2, 4, 64, 2},    // 12: tiny M
+    {128, 128, 4, 4, 4, 64, 2},  // 13: 16 waves, 4 per SIMD
+    {128, 64, 4, 2, 4, 64, 2},   // 14: more tiles for narrow N
+    {128, 128, 2, 2, 3, 32, 2},  // 15: 48 KiB, 3 WGs / CU
+    {128, 256, 2, 4, 3, 32, 2},  // 16: 72 KiB, 8 waves, 2 WGs / CU
+    {256, 128, 4, 2, 3, 32, 2},  // 17: 72 KiB, 8 waves, 2 WGs / CU
+    {192, 256, 3, 4, 4, 32, 2},  // 18: 12 waves, 3/4 of config 11, same work per wave
+    {64, 64, 2, 2, 4, 32, 4},    // 19 = GEMM_CFG_F32_64
+    {128, 128, 2, 2, 3, 32, 4},  // 20 = GEMM_CFG_F32_128
+};
+static bool cfg_has_f16(int cfg) { return cfg == 1 || cfg == 8 || cfg == 11 || cfg == 12 || cfg == 17 || cfg == 18; }
+static bool cfg_needs_k64(int cfg) { return kTiles[cfg].ks == 64; }  // 5, 6, 7, 8, 12, 13, 14
+
+template <int MODE, int C, bool F16 = false>
+static void launch_cfg(hipStream_t s, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epilogue& e) {
+    constexpr TileShape t = kTiles[C];
+    launch_tiled<MODE, t.bm, t.bn, t.wm, t.wn, t.ns, t.ks, t.esz, F16>(s, A, lda, W, ldw, M, N, K, e);
+}
+
+template <int MODE>
+static void launch_tiled_cfg(hipStream_t s, int dtype, int cfg, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                             const Epilogue& e) {
+#define STN_CFG(C, F16_) case C: launch_cfg<MODE, C, F16_>(s, A, lda, W, ldw, M, N, K, e); return;
+    if (dtype == F32) {
+        switch (cfg) { STN_CFG(19, false) STN_CFG(20, false) default: break; }
+    } else if (dtype == F16) {
+        switch (cfg) { STN_CFG(1, true) STN_CFG(8, true) STN_CFG(11, true) STN_CFG(12, true) STN_CFG(17, true) STN_CFG(18, true) default: break; }
+    } else {
+        switch (cfg) {
+            STN_CFG(1, false) STN_CFG(2, false) STN_CFG(3, false) STN_CFG(4, false) STN_CFG(5, false) STN_CFG(6, false)
+            STN_CFG(7, false) STN_CFG(8, false) STN_CFG(9, false) STN_CFG(10, false) STN_CFG(11, false) STN_CFG(12, false)
+            STN_CFG(13, false) STN_CFG(14, false) STN_CFG(15, false) STN_CFG(16, false) STN_CFG(17, false) STN_CFG(18, false)
+            default: break;
+        }
+    }
+#undef STN_CFG
+    throw std::invalid_argument("launch_gemm_form: no tiled configuration " + std::to_string(cfg) + " for this dtype");
+}
+
+// tile-shape selection for the vectorised-epilogue path (0: none, the shape takes a ring / register-staged kernel);
+// STN_GEMM_CFG=<n> forces one bf16 shape (experiments)
+static int tiled_cfg(int dtype, int M, int N, int K) {
+    if (dtype == F32) {
+        // fp32 MFMA is 1/16 of the bf16 rate: always compute-bound, tile choice only has to keep the CUs busy
+        if (K % 32) return 0;
+        // (a narrow N leaves few 128-wide tiles: the duration predictor's 9 k x 128 pw2 is 71 of them on 256 CUs)
+        return (M <= 64 || (long)((M + 127) / 128) * ((N + 127) / 128) < 160) ? GEMM_CFG_F32_64 : GEMM_CFG_F32_128;
+    }
+    static int g_gemm_cfg = -2;
+    if (g_gemm_cfg == -2) { const char* c = stn::dev_env("STN_GEMM_CFG"); g_gemm_cfg = c ? atoi(c) : -1; }
+    int cfg = g_gemm_cfg;
+    if (cfg < 0) {
+        // measured on MI355X (tools/gemm_bench.py): the 256x256 tile halves the operand bytes per FLOP and wins whenever
+        // it still yields ~a full wave of workgroups (1 per CU); otherwise the 128x128 tile with 128-byte rows keeps more
+        // CUs busy; tiny M (single utterances) gets 64x64 tiles so that N is spread over more CUs.
+        const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+        if (N >= 256 && t256 >= 160) {  // (a packed batch leaves ~180 of these tiles: still better than 700 small ones)
+            const long t192 = (long)((M + 191) / 192) * ((N + 255) / 256);
+            if (t256 < 208 && t192 <= 256) cfg = 18;       // one thin round (packed batches): 192-row tiles refill the idle CUs (-7 %)
+            else if (t256 < 512) cfg = 11;                 // one round of tiles: 16 waves shorten the per-tile critical path
+            else if (K <= 512 && t256 >= 1024) cfg = 17;   // short K, many tiles: 256x128, 8 waves, 2 WGs/CU (4 % over the 4-wave form)
+            else cfg = 1;
+        } else if (K % 64 == 0) cfg = M <= 64 ? 12 : 8;
+        else return 0;
+    }
+    if (cfg < 1 || cfg > 18) return 0;
+    if (cfg_needs_k64(cfg) && K % 64) return 0;
+    if (dtype == F16 && !cfg_has_f16(cfg)) return 0;  // the shapes the heuristic above picks; STN_GEMM_CFG experiments stay bf16-only
+    return cfg;
+}
+
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+GemmForm gemm_form(int dtype, int M, int N, int K, int lda, int ldw, const Epilogue& e, const void* A, const void* W, bool allow_split) {
+    const int kq = is_half(dtype) ? 8 : 4;
+    if (K <= 0 || K % kq || lda % kq || ldw % kq || misaligned16(A) || misaligned16(W)) { char m_[256]; snprintf(m_, sizeof m_, "launch_gemm: operand shape/alignment violates the kernel contract (K=%d lda=%d ldw=%d)", K,
+            lda, ldw); throw std::invalid_argument(m_); }
+    if (e.mode != EPI_STORE && e.mode != EPI_RESID && e.mode != EPI_STORE_T) throw std::invalid_argument("launch_gemm: unknown epilogue mode");
+    GemmForm f;
+    f.dtype = dtype;
+    f.mode = e.mode;
+    if (allow_split && e.ksplit <= 1) {
+        const int S = gemm_splitk_factor(dtype, M, N, K, e);
+        if (S > 1) {  // the partial sums: plain fp32 store into the [S][M][N] workspace (arena memory: 16-byte aligned)
+            Epilogue ep;
+            ep.mode = EPI_STORE; ep.out_dtype = F32; ep.ldo = N; ep.ksplit = S;
+            f = gemm_form(dtype, M, N, K, lda, ldw, ep, A, W, false);
+            f.mode = e.mode;
+            f.split = S;
+            return f;
+        }
+    }
+    // v2 ring kernel: bf16, K % 32 == 0.  Vectorised epilogue needs 16-B aligned 8-column groups.
+    const bool ring = is_half(dtype) && K % RK == 0;
+    const void* optr = e.mode == EPI_RESID ? static_cast<const void*>(e.resid) : e.out;
+    const bool vec_ok = e.mode <= EPI_RESID && N % 8 == 0 && e.ldo % 8 == 0 && !misaligned16(optr) && !misaligned16(e.bias) &&
+                        !misaligned16(e.gamma);
+    const int cfg = vec_ok && (ring || dtype == F32) ? tiled_cfg(dtype, M, N, K) : 0;
+    if (cfg > 0) {
+        const TileShape& t = kTiles[cfg];
+        f.kernel = GK_TILED;
+        f.cfg = cfg;
+        f.bm = t.bm; f.bn = t.bn; f.wm = t.wm; f.wn = t.wn; f.nstage = t.ns; f.ks = t.ks; f.esz = t.esz;
+        if (dtype == F32) {
+            f.tr_epilogue = e.tr_epilogue;
+        } else if (e.tr_force >= 0) {
+            f.tr_epilogue = e.tr_force != 0;
+        } else {
+            static int g_tr = -2;
+            if (g_tr == -2) { const char* c = stn::dev_env("STN_GEMM_TR"); g_tr = c ? atoi(c) : 1; }
+            // the transposed-image epilogue stores 64-byte row segments (16 rows per instruction): a win where a CU runs one tile
+            // (-4 % ve.pw1, -15 % te.pw1), a loss where a co-resident workgroup's K loop competes for the vector-memory path (vo.pw1)
+            f.tr_epilogue = g_tr == 2 || (g_tr == 1 && (cfg == 11 || cfg == 8 || cfg == 12 || cfg == 13 || cfg == 14 || cfg == 18));
+        }
+        // the kernel's own test (gemm_tiled_kernel): the image holds 16-bit values and has no row mask
+        f.epi = (e.mode == EPI_STORE && f.esz == 2 && e.out_dtype != F32 && e.len == nullptr && f.tr_epilogue) ? GE_TR : GE_SLAB;
+        return f;
+    }
+    f.kernel = ring && vec_ok ? GK_RING_VEC : ring ? GK_RING : GK_REG;
+    f.epi = f.kernel == GK_RING_VEC ? GE_SLAB : GE_LANE;
+    return f;
+}
+
+std::string GemmForm::str() const {
+    char b[128];
+    const char* ep = epi == GE_TR ? "tr" : epi == GE_SLAB ? "slab" : "lane";
+    char sp[16] = "";
+    if (split > 1) snprintf(sp, sizeof sp, "splitk%d+", split);
+    if (kernel == GK_TILED) {
+        char c[8] = "";
+        if (cfg <= 18) snprintf(c, sizeof c, " cfg%d", cfg);
+        snprintf(b, sizeof b, "%stiled<%d,%d,%d,%d,%d,%d,%d>%s %s", sp, bm, bn, wm, wn, nstage, ks, esz, c, ep);
+    } else {
+        snprintf(b, sizeof b, "%s%s %s", sp, kernel == GK_RING_VEC ? "ring_vec" : kernel == GK_RING ? "ring" : "reg", ep);
+    }
+    return b;
+}
+
+template <int MODE>
+static void launch_untiled(hipStream_t s, const GemmForm& f, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                           const Epilogue& e) {
+    const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, ntiles = tiles_m * tiles_n;
+    const uint16_t* A16 = static_cast<const uint16_t*>(A);
+    const uint16_t* W16 = static_cast<const uint16_t*>(W);
+#define STN_LAUNCH_H(F16_)                                                                                                       \
+    if (f.kernel == GK_RING_VEC) {                                                                                               \
+        if constexpr (MODE <= EPI_RESID)                                                                                         \
+            STN_KLAUNCH((gemm_bf16_ring_kernel<MODE, true, F16_>), dim3(ntiles), dim3(NT), 0, s, A16, lda, W16, ldw, M, N, K,      \
+                        tiles_n, ntiles, e);                                                                                      \
+    } else if (f.kernel == GK_RING)                                                                                              \
+        STN_KLAUNCH((gemm_bf16_ring_kernel<MODE, false, F16_>), dim3(ntiles), dim3(NT), 0, s, A16, lda, W16, ldw, M, N, K,         \
+                    tiles_n, ntiles, e);                                                                                          \
+    else                                                                                                                         \
+        STN_KLAUNCH((gemm_bf16_kernel<MODE, F16_>), dim3(ntiles), dim3(NT), 0, s, A16, lda, W16, ldw, M, N, K, tiles_n, ntiles, e);
+    if (f.dtype == F16) { STN_LAUNCH_H(true) }
+    else if (f.dtype == BF16) { STN_LAUNCH_H(false) }
+    else
+        STN_KLAUNCH(gemm_f32_kernel<MODE>, dim3(ntiles), dim3(NT), 0, s, static_cast<const float*>(A), lda, static_cast<const float*>(W),
+                    ldw, M, N, K, tiles_n, ntiles, e);
+#undef STN_LAUNCH_H
+}
+
+void launch_gemm_form(hipStream_t s, const GemmForm& f, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                      const Epilogue& e, float* workspace) {
+    if (M <= 0 || N <= 0) return;
+    if (f.mode != e.mode) throw std::invalid_argument("launch_gemm_form: the form was made for another epilogue mode");
+    if (f.split > 1) {
+        // deterministic split-K: the splits into `workspace`, then out = epilogue(sum over splits, in split order)
+        if (!workspace || misaligned16(workspace)) throw std::invalid_argument("launch_gemm_form: a split-K form needs a 16-byte aligned workspace of split * M * N floats");
+        Epilogue ep;  // partial sums: plain fp32 store, no bias, no mask
+        ep.mode = EPI_STORE; ep.out_dtype = F32; ep.out = workspace; ep.ldo = N; ep.ksplit = f.split;
+        GemmForm fp = f;
+        fp.mode = EPI_STORE;
+        fp.split = 1;
+        launch_gemm_form(s, fp, A, lda, W, ldw, M, N, K, ep, nullptr);
+        const int64_t n4 = (int64_t)M * (N / 4);
+        const dim3 grid((unsigned)((n4 + 255) / 256));
+        if (e.mode == EPI_RESID) STN_KLAUNCH(splitk_reduce_kernel<EPI_RESID>, grid, dim3(256), 0, s, workspace, f.split, M, N, e);
+        else STN_KLAUNCH(splitk_reduce_kernel<EPI_STORE>, grid, dim3(256), 0, s, workspace, f.split, M, N, e);
+        return;
+    }
+    if (f.kernel == GK_TILED) {
+        Epilogue et = e;
+        et.tr_epilogue = f.tr_epilogue;
+        if (e.mode == EPI_STORE) launch_tiled_cfg<EPI_STORE>(s, f.dtype, f.cfg, A, lda, W, ldw, M, N, K, et);
+        else if (e.mode == EPI_RESID) launch_tiled_cfg<EPI_RESID>(s, f.dtype, f.cfg, A, lda, W, ldw, M, N, K, et);
+        else throw std::invalid_argument("launch_gemm_form: the tiled kernels have no transposing epilogue");
+        return;
+    }
+    switch (e.mode) {
+        case EPI_STORE: launch_untiled<EPI_STORE>(s, f, A, lda, W, ldw, M, N, K, e); break;
+        case EPI_RESID: launch_untiled<EPI_RESID>(s, f, A, lda, W, ldw, M, N, K, e); break;
+        default: launch_untiled<EPI_STORE_T>(s, f, A, lda, W, ldw, M, N, K, e); break;
+    }
+}
+
+void launch_gemm(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
+                 const Epilogue& e) {
+    if (M <= 0 || N <= 0) return;
+    launch_gemm_form(s, gemm_form(dtype, M, N, K, lda, ldw, e, A, W, false), A, lda, W, ldw, M, N, K, e, nullptr);
+}
+
 int gemm_splitk_factor(int dtype, int M, int N, int K, const Epilogue& e) {
     // exact-fp32 GEMMs of one or two utterances: few 64x64 tiles, many K-steps of 32.
     // NOT for the 16-bit modes, although a single utterance's 49 x 384 x 1536 pw2 would gain from it (10.3 -> ~7 us, measured:
@@ -1003,17 +1105,6 @@ int gemm_splitk_factor(int dtype, int M, int N, int K, const Epilogue& e) {
     int sk = 1;
     for (int c : {8, 6, 4, 3, 2}) if (nk % c == 0 && nk / c >= 4 && tiles * c <= 256) { sk = c; break; }
     return sk;
-}
-
-void launch_gemm_splitk(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const Epilogue& e,
-                        int S, float* workspace /* [S][M][N] */) {
-    Epilogue ep;  // partial sums: plain fp32 store, no bias, no mask
-    ep.mode = EPI_STORE; ep.out_dtype = F32; ep.out = workspace; ep.ldo = N; ep.ksplit = S;
-    launch_gemm(s, dtype, A, lda, W, ldw, M, N, K, ep);
-    const int64_t n4 = (int64_t)M * (N / 4);
-    const dim3 grid((unsigned)((n4 + 255) / 256));
-    if (e.mode == EPI_RESID) STN_KLAUNCH(splitk_reduce_kernel<EPI_RESID>, grid, dim3(256), 0, s, workspace, S, M, N, e);
-    else STN_KLAUNCH(splitk_reduce_kernel<EPI_STORE>, grid, dim3(256), 0, s, workspace, S, M, N, e);
 }
 
 }  // namespace stn
