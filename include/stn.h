@@ -310,6 +310,39 @@ int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k
  * a separate pass first (the way the vector estimator's step-invariant text keys are handled) — same result */
 int stn_op_attention(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k,
                      const float* v, const int32_t* qlen_or_null, const int32_t* klen_or_null, int rope_mode, float* o);
+/* One attention through the engine's launcher in the layouts the engine runs (the kernel parity tests of every attention form).  Operands
+ * are rounded to `dtype` first.  q: q_elems floats, rows of ldq, head hh of a row at columns q_col + hh*dh; kv: kv_elems floats, rows of
+ * ldk, K at columns k_col + hh*dh, V at v_col + hh*dh (a fused QKV row, or the K/V pair of block blk of an nb*2C row); o: o_elems floats,
+ * rows of ldo, written at columns 0 .. H*dh.  Dense: sequence b owns rows b*Lq .. of q / o and b*Lk .. of kv; q_off / k_off (B entries
+ * each, with qlen / klen): packed rows, sequence b owns qlen[b] rows from q_off[b] (min(klen[b], Lk) from k_off[b]).  rope_mode as
+ * stn_op_attention.  k_rotated != 0: the keys are rotated first, in place, by the engine's one-time text-key pass (rot_groups groups
+ * rot_stride columns apart from column rot_col of each valid key row), and the attention takes them as rotated.  kv and o are the caller's
+ * whole buffers: uploaded as given (rounded to dtype) and written back whole (16-bit values widened to fp32, exactly), so what lies
+ * outside the written region can be checked.  form: the form that ran (as stn_dbg_attn_form), NUL-terminated, truncated to form_cap;
+ * may be NULL. */
+int stn_op_attention_ex(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, int64_t q_elems, int ldq,
+                        int q_col, float* kv, int64_t kv_elems, int ldk, int k_col, int v_col, float* o, int64_t o_elems, int ldo,
+                        const int32_t* qlen_or_null, const int32_t* klen_or_null, const int32_t* q_off_or_null,
+                        const int32_t* k_off_or_null, int rope_mode, int k_rotated, int rot_groups, int rot_stride, int rot_col,
+                        char* form, size_t form_cap);
+/* One launch of the vector estimator's head-split cross-attention block (16-bit engines; C = 384, 4 heads of 96):
+ * part[h*part_stride + row*384 + n] = (Wo[:, 96h .. 96h+96] . attention_h(Wq[96h .., :] . xn[row] + bq[96h ..], K_h, V_h))[n], 16-bit.
+ * xn [M,384] (packed query rows: utterance b owns qlen[b] <= L rows in order, sum qlen <= M); Wq, Wo [384,384] row-major (repacked here
+ * as at model load); bq: 384 floats or NULL.  kv: kv_elems floats, rows of ldk, K at columns k_col .., V at k_col + 384 ..; dense keys
+ * (utterance b owns rows b*Lk ..) or packed (k_off with klen).  Keys are taken as already rotated; rope_mode rotates the queries.
+ * pairs_mode 1: the utterances are paired by launch_xattn_hs_pairs and the table (2*ceil(B/2) ints) is written to pairs_out; 0: no table.
+ * part: part_elems floats (>= 3*part_stride + M*384, part_stride >= M*384), the caller's whole buffer, uploaded as given (rounded) and
+ * written back whole (widened to fp32, exactly).  form: as stn_dbg_attn_form kind 1. */
+int stn_op_xattn_hs(stn_handle* h, int dtype, int M, const float* xn, const float* Wq, const float* bq_or_null, const float* Wo,
+                    const float* kv, int64_t kv_elems, int ldk, int k_col, int B, int L, int Lk, const int32_t* qlen,
+                    const int32_t* klen_or_null, const int32_t* k_off_or_null, int rope_mode, int pairs_mode, int64_t part_stride,
+                    float* part, int64_t part_elems, int32_t* pairs_out_or_null, char* form, size_t form_cap);
+/* diagnostics (no device needed): the form the engine's attention launchers take.  kind 0, launch_attention: "mfma<DH,fmt> kcKC nchN"
+ * (keys per LDS chunk, chunks at Lk), "scalar<fmt,TPRn>" with, for fp32, "vec" / "elem" / "vec qkv-subset" (the operands staged with
+ * 16-byte loads).  misaligned: bit 0 / 1 / 2 = the q / k / v pointer is 4 bytes off 16-byte alignment.  kind 1, launch_xattn_hs (C =
+ * H*dh, L = Lq; ldq and misaligned unused): "xattn_hs<fmt,U> kcKC".  Returns the string's length (written with its NUL when it fits in
+ * cap), < 0 on a call the launcher refuses (STN_ERR_INVALID). */
+int stn_dbg_attn_form(int kind, int dtype, int B, int Lq, int Lk, int H, int dh, int ldq, int ldk, int misaligned, char* out, size_t cap);
 /* the pointwise pair of a ConvNeXt block on host operands (16-bit engines): x <- x + gamma * (W2 . GELU(W1 . xn + b1) + b2)
  * [+ rowvec[row_b[m]]], W1 [I,C], W2 [C,I], x [M,C] in place.  fused = 1: the K4 kernel, 0: the two tiled GEMM launches,
  * 2: K4-split (16-bit partial sums of the hidden quarters) followed by the fold. */

@@ -159,6 +159,8 @@ def load():
     L.stn_dbg_fold_run_frames.restype = ctypes.c_int
     L.stn_dbg_gemm_form.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_gemm_form.restype = ctypes.c_int
+    L.stn_dbg_attn_form.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_attn_form.restype = ctypes.c_int
     L.stn_launch_log.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_launch_log.restype = ctypes.c_int64
     L.stn_profile_enable.argtypes = [vp, ci]
@@ -175,6 +177,10 @@ def load():
     L.stn_op_dwconv_ln.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.stn_op_dwconv_ln_ragged.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p]
     L.stn_op_attention.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p]
+    L.stn_op_attention_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, ci, ci, _f32p, ctypes.c_int64, ci, ci, ci,
+                                      _f32p, ctypes.c_int64, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_op_xattn_hs.argtypes = [vp, ci, ci, _f32p, _f32p, vp, _f32p, _f32p, ctypes.c_int64, ci, ci, ci, ci, ci, _i32p, vp, vp, ci, ci,
+                                  ctypes.c_int64, _f32p, ctypes.c_int64, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_randn.argtypes = [vp, cu64, ci, ci, ci, vp, vp, _f32p]
     L.stn_op_ffn.argtypes = [vp, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, vp, vp, vp, vp, ci, _f32p, ci]
     L.stn_op_ffn_bench.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
@@ -319,6 +325,19 @@ def gemm_form(dtype, M, N, K, mode=EPI_STORE, out_dtype="f32", ldo=None, masked=
                                  int(bool(masked)), int(tr), buf, len(buf))
     if r < 0:
         raise StnError(r, "stn_dbg_gemm_form: the launcher refuses this call")
+    return buf.value.decode()
+
+
+def attn_form(dtype, B, Lq, Lk, H, dh, ldq=None, ldk=None, misaligned=0, kind=0):
+    """The form the engine's attention launchers take (stn_dbg_attn_form; host-only).  kind 0, launch_attention: e.g. "mfma<64,bf16> kc128
+    nch3", "scalar<f32,TPR8> vec"; misaligned: bits 1 / 2 / 4 = the q / k / v pointer 4 bytes off 16-byte alignment.  kind 1, the
+    head-split launch (C = H*dh, L = Lq): e.g. "xattn_hs<f16,U2> kc64".  ld defaults to H*dh."""
+    buf = ctypes.create_string_buffer(64)
+    C = H * dh
+    r = load().stn_dbg_attn_form(int(kind), _DTYPES[dtype], int(B), int(Lq), int(Lk), int(H), int(dh), int(C if ldq is None else ldq),
+                                 int(C if ldk is None else ldk), int(misaligned), buf, len(buf))
+    if r < 0:
+        raise StnError(r, "stn_dbg_attn_form: the launcher refuses this call")
     return buf.value.decode()
 
 
@@ -750,6 +769,45 @@ class Engine:
                                             C // H, _c(q, np.float32), _c(k, np.float32), _c(v, np.float32), qp, kp,
                                             rope_mode, o))
         return o
+
+    def op_attention_ex(self, q, kv, out, B, Lq, Lk, H, dh, q_col=0, k_col=0, v_col=None, qlen=None, klen=None, q_off=None, k_off=None,
+                        rope_mode=-1, k_rotated=False, rot_groups=1, rot_stride=0, rot_col=None, dtype=None):
+        """One attention through the engine's launcher in a given layout (stn_op_attention_ex).  q, kv, out: 2-D [rows, ld] buffers (their
+        row length is the stride); kv and out come back as new fp32 arrays of the same shapes, whole.  v_col defaults to k_col + H*dh,
+        rot_col to k_col.  Returns (out, kv, form string)."""
+        q = _c(q, np.float32)
+        kv_r = np.array(kv, dtype=np.float32, order="C", copy=True)
+        o_r = np.array(out, dtype=np.float32, order="C", copy=True)
+        _a, qlp = _opt(qlen, np.int32)
+        _b, klp = _opt(klen, np.int32)
+        _d, qop = _opt(q_off, np.int32)
+        _e, kop = _opt(k_off, np.int32)
+        form = ctypes.create_string_buffer(64)
+        self._ck(self._lib.stn_op_attention_ex(self._h, self.dtype if dtype is None else _DTYPES[dtype], int(B), int(Lq), int(Lk), int(H), int(dh),
+                                               q.reshape(-1), q.size, q.shape[1], int(q_col), kv_r.reshape(-1), kv_r.size, kv_r.shape[1],
+                                               int(k_col), int(k_col + H * dh if v_col is None else v_col), o_r.reshape(-1), o_r.size,
+                                               o_r.shape[1], qlp, klp, qop, kop, int(rope_mode), int(bool(k_rotated)), int(rot_groups),
+                                               int(rot_stride), int(k_col if rot_col is None else rot_col), form, ctypes.sizeof(form)))
+        return o_r, kv_r, form.value.decode()
+
+    def op_xattn_hs(self, xn, Wq, bq, Wo, kv, part, part_stride, B, L, Lk, qlen, k_col=0, klen=None, k_off=None, rope_mode=-1,
+                    pairs=False, dtype=None):
+        """One head-split cross-attention launch (stn_op_xattn_hs).  xn [M, 384]; kv: 2-D [rows, ldk]; part: the whole 1-D destination
+        buffer, returned as a new fp32 array.  Returns (part, pairs table or None, form string)."""
+        xn = _c(xn, np.float32)
+        kv = _c(kv, np.float32)
+        part_r = np.array(part, dtype=np.float32, order="C", copy=True).reshape(-1)
+        _b, bqp = _opt(bq, np.float32)
+        _k, klp = _opt(klen, np.int32)
+        _o, kop = _opt(k_off, np.int32)
+        pr = np.full(2 * ((B + 1) // 2), -7, np.int32) if pairs else None
+        form = ctypes.create_string_buffer(64)
+        self._ck(self._lib.stn_op_xattn_hs(self._h, self.dtype if dtype is None else _DTYPES[dtype], xn.shape[0], xn.reshape(-1),
+                                           _c(Wq, np.float32), bqp, _c(Wo, np.float32), kv.reshape(-1), kv.size, kv.shape[1], int(k_col),
+                                           int(B), int(L), int(Lk), _c(qlen, np.int32), klp, kop, int(rope_mode), int(bool(pairs)),
+                                           int(part_stride), part_r, part_r.size, None if pr is None else pr.ctypes.data, form,
+                                           ctypes.sizeof(form)))
+        return part_r, pr, form.value.decode()
 
     def op_randn(self, seed, B, D, L, utt_ids=None, length=None):
         out = np.empty((B, D, L), np.float32)

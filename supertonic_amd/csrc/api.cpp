@@ -1,6 +1,7 @@
 // api.cpp — the C ABI of include/stn.h over stn::Engine.  No exception leaves this file.
 #include "../../include/stn.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -472,6 +473,91 @@ int stn_op_attention(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int
     STN_TRY(h, { need(B > 0 && Lq > 0 && Lk > 0 && H > 0 && dh >= 8 && dh % 8 == 0 && dh <= 96 && q && k && v && o,
                       "stn_op_attention: bad argument");
                  h->eng->op_attention(dtype, B, Lq, Lk, H, dh, q, k, v, qlen, klen, rope_mode, o); })
+}
+// (the argument checks of the two entry points below declare several variables per statement: too many commas for STN_TRY's body)
+static void attention_ex_checked(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, int64_t q_elems, int ldq,
+                                 int q_col, float* kv, int64_t kv_elems, int ldk, int k_col, int v_col, float* o, int64_t o_elems, int ldo,
+                                 const int32_t* qlen, const int32_t* klen, const int32_t* q_off, const int32_t* k_off, int rope_mode,
+                                 int k_rotated, int rot_groups, int rot_stride, int rot_col, char* form, size_t form_cap) {
+    need(B > 0 && Lq > 0 && Lk > 0 && H > 0 && dh >= 8 && dh % 8 == 0 && dh <= 96 && q && kv && o, "stn_op_attention_ex: bad argument");
+    need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_attention_ex: unknown dtype");
+    need(rope_mode >= -1 && rope_mode <= 1, "stn_op_attention_ex: rope_mode must be -1, 0 or 1");
+    const int64_t C = (int64_t)H * dh;
+    need(ldq > 0 && ldk > 0 && ldo >= C && q_col >= 0 && k_col >= 0 && v_col >= 0 && q_col + C <= ldq && k_col + C <= ldk && v_col + C <= ldk,
+         "stn_op_attention_ex: the heads must lie inside the rows (col + H*dh <= ld, ldo >= H*dh)");
+    need((q_off == nullptr || qlen) && (k_off == nullptr || klen), "stn_op_attention_ex: packed rows need their lengths");
+    const int64_t qrows = q_elems / ldq, krows = kv_elems / ldk, orows = o_elems / ldo;
+    for (int b = 0; b < B; ++b) {
+        need(!qlen || qlen[b] >= 0, "stn_op_attention_ex: qlen < 0");
+        need(!klen || klen[b] >= 0, "stn_op_attention_ex: klen < 0");
+        if (q_off)
+            need(qlen[b] <= Lq && q_off[b] >= 0 && (int64_t)q_off[b] + qlen[b] <= std::min(qrows, orows),
+                 "stn_op_attention_ex: packed query rows outside q / o (or qlen > Lq)");
+        if (k_off) need(k_off[b] >= 0 && (int64_t)k_off[b] + std::min(klen[b], Lk) <= krows, "stn_op_attention_ex: packed key rows outside kv");
+    }
+    if (!q_off) need((int64_t)B * Lq <= std::min(qrows, orows), "stn_op_attention_ex: q / o hold fewer than B*Lq rows");
+    if (!k_off) need((int64_t)B * Lk <= krows, "stn_op_attention_ex: kv holds fewer than B*Lk rows");
+    if (k_rotated)
+        need(rot_groups >= 1 && rot_stride >= 0 && rot_col >= 0 && rot_col + (int64_t)(rot_groups - 1) * rot_stride + C <= ldk,
+             "stn_op_attention_ex: the rotated groups must lie inside the kv rows");
+    const std::string f = h->eng->op_attention_ex(dtype, B, Lq, Lk, H, dh, q, q_elems, ldq, q_col, kv, kv_elems, ldk, k_col, v_col, o, o_elems,
+                                                  ldo, qlen, klen, q_off, k_off, rope_mode, k_rotated, rot_groups, rot_stride, rot_col);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_attention_ex(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, int64_t q_elems, int ldq,
+                        int q_col, float* kv, int64_t kv_elems, int ldk, int k_col, int v_col, float* o, int64_t o_elems, int ldo,
+                        const int32_t* qlen, const int32_t* klen, const int32_t* q_off, const int32_t* k_off, int rope_mode, int k_rotated,
+                        int rot_groups, int rot_stride, int rot_col, char* form, size_t form_cap) {
+    STN_TRY(h, attention_ex_checked(h, dtype, B, Lq, Lk, H, dh, q, q_elems, ldq, q_col, kv, kv_elems, ldk, k_col, v_col, o, o_elems, ldo,
+                                    qlen, klen, q_off, k_off, rope_mode, k_rotated, rot_groups, rot_stride, rot_col, form, form_cap))
+}
+static void xattn_hs_checked(stn_handle* h, int dtype, int M, const float* xn, const float* Wq, const float* bq, const float* Wo, const float* kv,
+                             int64_t kv_elems, int ldk, int k_col, int B, int L, int Lk, const int32_t* qlen, const int32_t* klen,
+                             const int32_t* k_off, int rope_mode, int pairs_mode, int64_t part_stride, float* part, int64_t part_elems,
+                             int32_t* pairs_out, char* form, size_t form_cap) {
+    const int C = 384;
+    need(M > 0 && B > 0 && B <= 1024 && L > 0 && Lk > 0 && xn && Wq && Wo && kv && qlen && part, "stn_op_xattn_hs: bad argument");
+    need(stn::xattn_hs_supported(dtype, C, 4, L, Lk, ldk), "stn_op_xattn_hs: unsupported dtype or shape (xattn_hs_supported)");
+    need(rope_mode >= -1 && rope_mode <= 1 && (pairs_mode == 0 || pairs_mode == 1), "stn_op_xattn_hs: rope_mode -1..1, pairs_mode 0 or 1");
+    need(k_col >= 0 && k_col % 8 == 0 && k_col + 2 * C <= ldk, "stn_op_xattn_hs: K and V (k_col .. k_col + 768) must lie inside the rows, k_col % 8 == 0");
+    need(k_off == nullptr || klen, "stn_op_xattn_hs: packed keys need klen");
+    need(part_stride >= (int64_t)M * C && part_elems >= 3 * part_stride + (int64_t)M * C,
+         "stn_op_xattn_hs: part must hold 4 heads of M*384 values part_stride apart");
+    int64_t rows = 0;
+    const int64_t krows = kv_elems / ldk;
+    for (int b = 0; b < B; ++b) {
+        need(qlen[b] >= 0 && qlen[b] <= L, "stn_op_xattn_hs: qlen out of [0, L]");
+        rows += qlen[b];
+        need(!klen || klen[b] >= 0, "stn_op_xattn_hs: klen < 0");
+        if (k_off) need(k_off[b] >= 0 && (int64_t)k_off[b] + std::min(klen[b], Lk) <= krows, "stn_op_xattn_hs: packed key rows outside kv");
+    }
+    need(rows <= M, "stn_op_xattn_hs: sum qlen > M");
+    if (!k_off) need((int64_t)B * Lk <= krows, "stn_op_xattn_hs: kv holds fewer than B*Lk rows");
+    const std::string f = h->eng->op_xattn_hs(dtype, M, xn, Wq, bq, Wo, kv, kv_elems, ldk, k_col, B, L, Lk, qlen, klen, k_off, rope_mode,
+                                              pairs_mode, part_stride, part, part_elems, pairs_out);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_xattn_hs(stn_handle* h, int dtype, int M, const float* xn, const float* Wq, const float* bq, const float* Wo, const float* kv,
+                    int64_t kv_elems, int ldk, int k_col, int B, int L, int Lk, const int32_t* qlen, const int32_t* klen, const int32_t* k_off,
+                    int rope_mode, int pairs_mode, int64_t part_stride, float* part, int64_t part_elems, int32_t* pairs_out, char* form,
+                    size_t form_cap) {
+    STN_TRY(h, xattn_hs_checked(h, dtype, M, xn, Wq, bq, Wo, kv, kv_elems, ldk, k_col, B, L, Lk, qlen, klen, k_off, rope_mode, pairs_mode,
+                                part_stride, part, part_elems, pairs_out, form, form_cap))
+}
+int stn_dbg_attn_form(int kind, int dtype, int B, int Lq, int Lk, int H, int dh, int ldq, int ldk, int misaligned, char* out, size_t cap) {
+    if (B < 1 || Lq < 1 || Lk < 1 || H < 1 || (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16) || (kind != 0 && kind != 1))
+        return STN_ERR_INVALID;
+    std::string f;
+    try {
+        if (kind == 0) {
+            auto ptr = [&](int bit) { return reinterpret_cast<const void*>((uintptr_t)(misaligned & bit ? 4 : 0)); };  // read for alignment only
+            f = stn::attn_form(dtype, B, Lq, Lk, H, dh, ldq, ldk, ptr(1), ptr(2), ptr(4)).str();
+        } else {
+            f = stn::xattn_hs_form(dtype, H * dh, H, B, Lq, Lk, ldk).str();
+        }
+    } catch (const std::exception&) { return STN_ERR_INVALID; }
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
 }
 int stn_op_ffn(stn_handle* h, int M, int C, int I, const float* xn, const float* W1, const float* b1, const float* W2, const float* b2,
                const float* gamma, const float* rowvec, const int32_t* row_b, int nseq, float* x, int fused) {

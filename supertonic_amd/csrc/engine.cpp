@@ -850,8 +850,9 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
         const char* kp0 = static_cast<const char*>(kv_all) + (size_t)blk * 2 * C * esz;
         const auto fq = frag_w_.find(w.q.w.as(dt_));
         const auto foa = frag_acc_w_.find(w.o.w.as(dt_));
+        // (the partial sums are added by the next ConvNeXt block's fold_dwconv_ln: only where that kernel takes the block's shape, as for K4-split)
         if (fused_xattn_ && fsp && unit_vec_ && C <= 1024 && fq != frag_w_.end() && foa != frag_acc_w_.end() && xattn_hs_supported(dt_, C, H, L, Lk, nb * 2 * C) &&
-            M * C * 2 < 0x7FFFFFFFll) {
+            M * C * 2 < 0x7FFFFFFFll && fold_dwconv_ln_supported(C, a.ve_kernel, 1 << std::max(0, a.ve_dilated - 1))) {
             // HEAD-SPLIT: fold_ln (or LayerNorm), then ONE launch per block — q projection, rotation, attention and the head's share of the
             // output projection per (utterance pair, head), stored as four 16-bit per-head partial sums in K4-split's layout; the next
             // ConvNeXt block's fold_dwconv_ln adds them (and the output bias) to x in head order

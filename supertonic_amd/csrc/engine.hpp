@@ -281,6 +281,22 @@ class Engine {
     std::string op_gemm_ex(int dtype, int M, int N, int K, const float* A, const float* W, int mode, int act, int out_dtype, int ldo,
                            const float* bias, const float* gamma, const int* len, int L, const int* row_b, const float* rowvec, int nseq,
                            int nt, int tr, float* out, int64_t out_elems);
+    // one attention through launch_attention in the engine's layouts (stn_op_attention_ex): q [q_elems / ldq rows][ldq] with the heads from
+    // column q_col, K and V in the rows of kv [kv_elems / ldk][ldk] from columns k_col and v_col, o [o_elems / ldo][ldo] from column 0.
+    // kv and o are the caller's whole buffers: uploaded as given (rounded to dtype) and downloaded whole (widened to fp32).  k_rotated: the
+    // keys are rotated first by launch_rope_rows over rot_groups groups rot_stride apart from column rot_col, the estimator's text-key pass.
+    // Returns the form it ran (AttnForm::str).
+    std::string op_attention_ex(int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, int64_t q_elems, int ldq, int q_col,
+                                float* kv, int64_t kv_elems, int ldk, int k_col, int v_col, float* o, int64_t o_elems, int ldo,
+                                const int* qlen, const int* klen, const int* q_off, const int* k_off, int rope_mode, int k_rotated,
+                                int rot_groups, int rot_stride, int rot_col);
+    // one head-split launch (stn_op_xattn_hs): xn [M][384]; Wq, Wo [384][384] plain, repacked here as prepare_xattn_weights does; K at
+    // column k_col of kv's rows, V at k_col + 384; packed query rows from launch_row_map(qlen).  part [part_elems] is the caller's whole
+    // buffer (rounded to dtype going up, widened coming back); pairs_mode 1: launch_xattn_hs_pairs' table, written to pairs_out
+    // (2 * ceil(B / 2) ints).  Returns the form it ran (XattnHsForm::str).
+    std::string op_xattn_hs(int dtype, int M, const float* xn, const float* Wq, const float* bq, const float* Wo, const float* kv,
+                            int64_t kv_elems, int ldk, int k_col, int B, int L, int Lk, const int* qlen, const int* klen, const int* k_off,
+                            int rope_mode, int pairs_mode, int64_t part_stride, float* part, int64_t part_elems, int* pairs_out);
     void op_attention(int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k, const float* v,
                       const int* qlen, const int* klen, int rope_mode, float* o);
     void op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,

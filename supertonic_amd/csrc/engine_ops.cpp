@@ -129,6 +129,90 @@ void Engine::op_attention(int dtype, int B, int Lq, int Lk, int H, int dh, const
     sync();
 }
 
+// a host fp32 array -> device in format dtype (rounded; fp32 as it is)
+static void* up_as(Arena& ar, hipStream_t s, int dtype, const float* h, size_t n) {
+    float* d = up(ar, s, h, n);
+    if (!is_half(dtype)) return d;
+    void* d16 = ar.alloc(n * 2);
+    launch_cast(s, dtype, d, (int64_t)n, d16);
+    return d16;
+}
+
+std::string Engine::op_attention_ex(int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, int64_t q_elems, int ldq, int q_col,
+                                    float* kv, int64_t kv_elems, int ldk, int k_col, int v_col, float* o, int64_t o_elems, int ldo,
+                                    const int* qlen, const int* klen, const int* q_off, const int* k_off, int rope_mode, int k_rotated,
+                                    int rot_groups, int rot_stride, int rot_col) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const size_t esz = is_half(dtype) ? 2 : 4;
+    char* dq = static_cast<char*>(up_as(ar_, s_, dtype, q, (size_t)q_elems));
+    char* dkv = static_cast<char*>(up_as(ar_, s_, dtype, kv, (size_t)kv_elems));
+    char* dO = static_cast<char*>(up_as(ar_, s_, dtype, o, (size_t)o_elems));
+    const int* dql = qlen ? up(ar_, s_, qlen, (size_t)B) : nullptr;
+    const int* dkl = klen ? up(ar_, s_, klen, (size_t)B) : nullptr;
+    const int* dqo = q_off ? up(ar_, s_, q_off, (size_t)B) : nullptr;
+    const int* dko = k_off ? up(ar_, s_, k_off, (size_t)B) : nullptr;
+    const float rbase = a_.rope_base > 0 ? a_.rope_base : 10000.f, rgam = a_.larope_gamma > 0 ? a_.larope_gamma : 10.f;
+    // as ve_text_kv_dev: every group's keys of the valid rows, once, before any attention reads them
+    if (k_rotated) launch_rope_rows(s_, dtype, dkv + (size_t)rot_col * esz, ldk, B, Lk, dkl, rot_groups, rot_stride, H, dh, rope_mode, rbase, rgam, dko);
+    const AttnForm f = attn_form(dtype, B, Lq, Lk, H, dh, ldq, ldk, dq + (size_t)q_col * esz, dkv + (size_t)k_col * esz, dkv + (size_t)v_col * esz);
+    launch_attention(s_, dtype, dq + (size_t)q_col * esz, ldq, dkv + (size_t)k_col * esz, dkv + (size_t)v_col * esz, ldk, dO, ldo, B, Lq, Lk,
+                     H, dh, dql, dkl, rope_mode, rbase, rgam, k_rotated != 0, dqo, dko);
+    if (is_half(dtype)) {
+        float* w = f32_alloc(std::max(kv_elems, o_elems));
+        launch_half_to_f32(s_, dtype, dkv, kv_elems, w);
+        STN_HIP(hipMemcpyAsync(kv, w, (size_t)kv_elems * 4, hipMemcpyDeviceToHost, s_));
+        sync();
+        launch_half_to_f32(s_, dtype, dO, o_elems, w);
+        STN_HIP(hipMemcpyAsync(o, w, (size_t)o_elems * 4, hipMemcpyDeviceToHost, s_));
+    } else {
+        STN_HIP(hipMemcpyAsync(kv, dkv, (size_t)kv_elems * 4, hipMemcpyDeviceToHost, s_));
+        STN_HIP(hipMemcpyAsync(o, dO, (size_t)o_elems * 4, hipMemcpyDeviceToHost, s_));
+    }
+    sync();
+    return f.str();
+}
+
+std::string Engine::op_xattn_hs(int dtype, int M, const float* xn, const float* Wq, const float* bq, const float* Wo, const float* kv,
+                                int64_t kv_elems, int ldk, int k_col, int B, int L, int Lk, const int* qlen, const int* klen, const int* k_off,
+                                int rope_mode, int pairs_mode, int64_t part_stride, float* part, int64_t part_elems, int* pairs_out) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const int C = 384, H = 4;
+    const XattnHsForm f = xattn_hs_form(dtype, C, H, B, L, Lk, ldk);
+    void* dx = up_as(ar_, s_, dtype, xn, (size_t)M * C);
+    void* wq16 = up_as(ar_, s_, dtype, Wq, (size_t)C * C);
+    void* wo16 = up_as(ar_, s_, dtype, Wo, (size_t)C * C);
+    void* wqf = ar_.alloc((size_t)C * C * 2);
+    void* woa = ar_.alloc((size_t)C * C * 2);
+    launch_repack_frag(s_, wq16, C, C, wqf);
+    launch_repack_frag_acc(s_, wo16, C, C, woa);
+    const float* dbq = bq ? up(ar_, s_, bq, (size_t)C) : nullptr;
+    char* dkv = static_cast<char*>(up_as(ar_, s_, dtype, kv, (size_t)kv_elems));
+    void* dpart = up_as(ar_, s_, dtype, part, (size_t)part_elems);
+    const int* dql = up(ar_, s_, qlen, (size_t)B);
+    const int* dkl = klen ? up(ar_, s_, klen, (size_t)B) : nullptr;
+    const int* dko = k_off ? up(ar_, s_, k_off, (size_t)B) : nullptr;
+    int* qoff = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+    launch_row_map(s_, dql, B, qoff, nullptr);
+    const int np = 2 * ((B + 1) / 2);
+    int* pairs = nullptr;
+    if (pairs_mode) {
+        pairs = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)np));
+        launch_xattn_hs_pairs(s_, dql, B, pairs);
+    }
+    const float rbase = a_.rope_base > 0 ? a_.rope_base : 10000.f, rgam = a_.larope_gamma > 0 ? a_.larope_gamma : 10.f;
+    const char* kp = dkv + (size_t)k_col * 2;
+    launch_xattn_hs(s_, dtype, dx, M, wqf, dbq, kp, kp + (size_t)C * 2, ldk, woa, dpart, part_stride, B, L, Lk, dql, dkl, qoff, dko,
+                    rope_mode, rbase, rgam, nullptr, pairs);
+    float* w = f32_alloc(part_elems);
+    launch_half_to_f32(s_, dtype, dpart, part_elems, w);
+    STN_HIP(hipMemcpyAsync(part, w, (size_t)part_elems * 4, hipMemcpyDeviceToHost, s_));
+    if (pairs && pairs_out) STN_HIP(hipMemcpyAsync(pairs_out, pairs, sizeof(int) * (size_t)np, hipMemcpyDeviceToHost, s_));
+    sync();
+    return f.str();
+}
+
 double Engine::op_gemm_bench(int dtype, int M, int N, int K, int mode, int iters) {
     STN_HIP(hipSetDevice(device_));
     ar_.reset();

@@ -224,6 +224,24 @@ void launch_row_map(hipStream_t s, const int* len, int B, int* row_off /*[B+1]*/
 void launch_layernorm(hipStream_t s, int out_dtype, const float* x, int64_t M, int C, const float* g, const float* b,
                       float eps, void* y);
 
+// The form an attention call takes — one decision, made by attn_form and executed by launch_attention, so that what the diagnostics
+// report (stn_dbg_attn_form, stn_op_attention_ex) is what runs:
+//   mfma    attn_mfma_kernel<dh, F16> (16-bit, dh in {32, 64, 96}, ld % 8 == 0, 16-byte aligned q / k / v, operands < 2 GiB): keys
+//           through LDS in chunks of kc (a multiple of 32, <= 128), nch chunks at the longest context Lk
+//   scalar  attn_kernel<T, tpr> (everything else): tpr = 32 threads per query row when the grid has fewer than 96 workgroups of 32
+//           query rows, else 8; fp32 only: vec says which operands are staged with 16-byte loads (ATTN_VEC_*), the others element-wise
+enum AttnVec : int { ATTN_VEC_Q = 1, ATTN_VEC_K = 2, ATTN_VEC_V = 4 };
+struct AttnForm {
+    int dtype = F32;
+    bool mfma = false;
+    int dh = 0;
+    int kc = 0, nch = 0;   // mfma
+    int tpr = 8, vec = 0;  // scalar
+    size_t lds = 0;        // dynamic LDS bytes of the launch
+    std::string str() const;  // e.g. "mfma<64,bf16> kc128 nch3", "scalar<f32,TPR8> vec", "scalar<f32,TPR32> elem", "scalar<bf16,TPR32>"
+};
+// q / k / v are read for their alignment only (null is aligned).  Throws std::invalid_argument on a head dim the kernels do not take.
+AttnForm attn_form(int dtype, int B, int Lq, int Lk, int H, int dh, int ldq, int ldk, const void* q, const void* k, const void* v);
 // fused attention core: softmax(rope(q) rope(k)^T / sqrt(dh)) v, per (b, head).
 // q [B*Lq][ldq], k/v [B*Lk][ldk] (act dtype); o [B*Lq][ldo] (act dtype).
 // rope_mode: -1 none, 0 position index, 1 length-aware (gamma * t / len).
@@ -245,9 +263,17 @@ void launch_xattn_hs(hipStream_t s, int dtype, const void* xn, int64_t M, const 
                      const void* WoA, void* part, int64_t part_stride, int B, int L, int Lk, const int* qlen, const int* klen,
                      const int* q_off, const int* k_off, int rope_mode, float rope_base, float rope_gamma, unsigned long long* ts = nullptr,
                      const int* pairs = nullptr /* launch_xattn_hs_pairs' table: which two utterances share a workgroup (null: 2g, 2g + 1) */);
-// utterances per workgroup a launch of this shape takes (1 or 2), and the pairing for 2: sorted by length, longest with shortest, so that
-// the pairs' row-tile counts are as equal as the batch allows (pairs: 2 * ceil(B / 2) ints; once per synthesis, the lengths do not change)
-int xattn_hs_group(int B, int L, int Lk);
+// The form a head-split launch takes (decided by xattn_hs_form, executed by launch_xattn_hs): xattn_hs_kernel<F16, U> with U utterances
+// per workgroup (1 or 2), keys in slots of kc = Lk rounded up to 32.  Throws std::invalid_argument where !xattn_hs_supported.
+struct XattnHsForm {
+    bool f16 = false;
+    int U = 1, kc = 32;
+    size_t lds = 0;
+    std::string str() const;  // e.g. "xattn_hs<f16,U2> kc64"
+};
+XattnHsForm xattn_hs_form(int dtype, int C, int H, int B, int L, int Lk, int ldk);
+// the pairing for U = 2: sorted by length, longest with shortest, so that the pairs' row-tile counts are as equal as the batch allows
+// (pairs: 2 * ceil(B / 2) ints; once per synthesis, the lengths do not change)
 void launch_xattn_hs_pairs(hipStream_t s, const int* qlen, int B, int* pairs);
 // in-place RoPE of `groups` key blocks per row: element (row b*L+t, column g*group_stride + h*dh + i) for t < len[b]
 // (len null: all rows).  Keys that are reused by many attention launches (the vector estimator's text keys: every

@@ -32,7 +32,7 @@ __device__ __forceinline__ void st_act(uint16_t* p, float v) {
 // (i, i + dh/2) when rope_mode >= 0; rows at positions >= limit are zero-filled.
 // fp32 rows: 16-byte loads, ALL of them issued before the first is consumed.  (Element by element this staging is a chain of
 // rows*dh/512 dependent 4-byte loads per tensor and key tile — 12 for a 64 x 96 tile — and was 3/4 of the kernel's 63 us on a
-// single utterance.)  Needs dh % 8 == 0, ld % 4 == 0 and 16-byte aligned rows; at most AK rows.
+// single utterance.)  Needs dh % 8 == 0, ld % 4 == 0 and 16-byte aligned rows (attn_form decides: AttnForm::vec); at most AK rows.
 __device__ __forceinline__ void stage_rows_f32v(const float* __restrict__ src, int ld, int64_t seq_base, int pos0, int rows,
                                                 int limit, int dh, int ds, float* __restrict__ dst, int rope_mode,
                                                 float log_base, float gamma, int seq_len, float mul) {
@@ -78,12 +78,13 @@ __device__ __forceinline__ void stage_rows_f32v(const float* __restrict__ src, i
     }
 }
 
+// vec (fp32 only): this operand's rows take the 16-byte loads (attn_form's choice for the launch)
 template <typename T>
 __device__ __forceinline__ void stage_rows(const T* __restrict__ src, int ld, int64_t seq_base, int pos0, int rows,
                                            int limit, int dh, int ds, float* __restrict__ dst, int rope_mode,
-                                           float log_base, float gamma, int seq_len, float mul) {
+                                           float log_base, float gamma, int seq_len, float mul, bool vec) {
     if constexpr (sizeof(T) == 4) {
-        if (dh % 8 == 0 && ld % 4 == 0 && rows <= AK && blockDim.x == 256 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+        if (vec) {
             stage_rows_f32v(reinterpret_cast<const float*>(src), ld, seq_base, pos0, rows, limit, dh, ds, dst, rope_mode, log_base, gamma, seq_len, mul);
             return;
         }
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ q, int 
                                                    int Lk, int dh, const int* __restrict__ qlen,
                                                    const int* __restrict__ klen, int rope_mode, float log_base,
                                                    float gamma, int k_rot, const int* __restrict__ q_off,
-                                                   const int* __restrict__ k_off) {
+                                                   const int* __restrict__ k_off, int vec /* fp32: AttnVec bits */) {
     constexpr int QR = 256 / TPR;        // query rows per workgroup
     constexpr int KPT = AK / TPR;        // keys per thread and tile
     constexpr int OPT = (ADH_MAX + TPR - 1) / TPR;  // output columns per thread
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ q, int 
     const int64_t qrow0 = q_off ? (int64_t)q_off[b] : (int64_t)b * Lq;  // packed: the sequence owns nq rows from q_off[b]
     const int qrows = q_off ? nq : Lq;
     if (q0 >= qrows) return;  // uniform: nothing of this tile exists
-    stage_rows<T>(q + h * dh, ldq, qrow0, q0, QR, qrows, dh, ds, Qs, rope_mode, log_base, gamma, nq, sc);
+    stage_rows<T>(q + h * dh, ldq, qrow0, q0, QR, qrows, dh, ds, Qs, rope_mode, log_base, gamma, nq, sc, vec & ATTN_VEC_Q);
 
     float m_run = -1e30f, l_run = 0.f;
     float oacc[OPT];
@@ -151,8 +152,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ q, int 
     for (int k0 = 0; k0 < nk; k0 += AK) {
         __syncthreads();  // previous tile fully consumed (and Qs visible on the first pass)
         const int64_t krow0 = k_off ? (int64_t)k_off[b] : (int64_t)b * Lk;
-        stage_rows<T>(k + h * dh, ldk, krow0, k0, AK, nk, dh, ds, Ks, k_rot ? -1 : rope_mode, log_base, gamma, nk, 1.f);
-        stage_rows<T>(v + h * dh, ldk, krow0, k0, AK, nk, dh, ds, Vs, -1, 0.f, 0.f, 1, 1.f);
+        stage_rows<T>(k + h * dh, ldk, krow0, k0, AK, nk, dh, ds, Ks, k_rot ? -1 : rope_mode, log_base, gamma, nk, 1.f, vec & ATTN_VEC_K);
+        stage_rows<T>(v + h * dh, ldk, krow0, k0, AK, nk, dh, ds, Vs, -1, 0.f, 0.f, 1, 1.f, vec & ATTN_VEC_V);
         __syncthreads();
         float s[KPT];
 #pragma unroll
@@ -544,36 +545,69 @@ static void launch_attn_mfma(hipStream_t s, const uint16_t* q, int ldq, const ui
                        rope_mode, log_base, gamma, k_rot, q_off, k_off);
 }
 
+static const char* dtype_name(int dtype) { return dtype == F16 ? "f16" : dtype == BF16 ? "bf16" : "f32"; }
+
+AttnForm attn_form(int dtype, int B, int Lq, int Lk, int H, int dh, int ldq, int ldk, const void* q, const void* k, const void* v) {
+    if (dh > ADH_MAX || dh % 8 || dh < 8) { char m_[256]; snprintf(m_, sizeof m_, "attention head dim %d unsupported (multiple of 8, <= %d)", dh, ADH_MAX); throw std::invalid_argument(m_); }
+    AttnForm f;
+    f.dtype = dtype;
+    f.dh = dh;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // (the MFMA kernel addresses q, k and v through 32-bit buffer offsets: operands of 2 GiB and more take the scalar kernel)
+    if (is_half(dtype) && (dh == 32 || dh == 64 || dh == 96) && ldk % 8 == 0 && ldq % 8 == 0 && al16(v) && al16(q) && al16(k) &&
+        (int64_t)B * Lq * ldq * 2 < 0x7FFFFFFFll && (int64_t)B * Lk * ldk * 2 < 0x7FFFFFFFll) {
+        // keys go through LDS in chunks of at most 128 (one chunk covers the 50 style tokens and ~100-token texts; longer texts
+        // take several), so the MFMA kernel serves every context length at 2 workgroups per CU
+        const int lk_pad = (Lk + 31) & ~31;
+        f.mfma = true;
+        f.kc = lk_pad < 128 ? lk_pad : 128;
+        f.nch = Lk > 0 ? (Lk + f.kc - 1) / f.kc : 1;
+        f.lds = (size_t)128 * (dh * 2 + 16) + (size_t)f.kc * (dh * 2 + 16) + (size_t)dh * (f.kc * 2 + 8);
+        return f;
+    }
+    // few workgroups (single utterances): 32 threads per query row cut the work per thread, i.e. the launch's latency, by four
+    const bool wide = (int64_t)((Lq + AQ - 1) / AQ) * H * B < 96;
+    f.tpr = wide ? 32 : 8;
+    const int qr = 256 / f.tpr;
+    f.lds = sizeof(float) * ((size_t)(qr + 2 * AK) * (dh + 1) + (size_t)qr * (AK + 1));
+    if (dtype == F32)  // the rows of q + h*dh (likewise k, v) are 16-byte aligned when the base is: dh % 8 == 0
+        f.vec = (ldq % 4 == 0 && al16(q) ? ATTN_VEC_Q : 0) | (ldk % 4 == 0 && al16(k) ? ATTN_VEC_K : 0) | (ldk % 4 == 0 && al16(v) ? ATTN_VEC_V : 0);
+    return f;
+}
+
+std::string AttnForm::str() const {
+    char b[96];
+    if (mfma) {
+        snprintf(b, sizeof b, "mfma<%d,%s> kc%d nch%d", dh, dtype_name(dtype), kc, nch);
+    } else if (dtype == F32) {
+        char vs[16] = "elem";
+        if (vec == (ATTN_VEC_Q | ATTN_VEC_K | ATTN_VEC_V)) snprintf(vs, sizeof vs, "vec");
+        else if (vec) snprintf(vs, sizeof vs, "vec %s%s%s", vec & ATTN_VEC_Q ? "q" : "", vec & ATTN_VEC_K ? "k" : "", vec & ATTN_VEC_V ? "v" : "");
+        snprintf(b, sizeof b, "scalar<f32,TPR%d> %s", tpr, vs);
+    } else {
+        snprintf(b, sizeof b, "scalar<%s,TPR%d>", dtype_name(dtype), tpr);
+    }
+    return b;
+}
+
 void launch_attention(hipStream_t s, int dtype, const void* q, int ldq, const void* k, const void* v, int ldk, void* o,
                       int ldo, int B, int Lq, int Lk, int H, int dh, const int* qlen, const int* klen, int rope_mode,
                       float rope_base, float rope_gamma, bool k_rotated, const int* q_off, const int* k_off) {
     if (B == 0 || Lq == 0) return;
     if ((q_off && !qlen) || (k_off && !klen)) { throw std::invalid_argument("packed attention needs the lengths of the packed side"); }
-    if (dh > ADH_MAX || dh % 8 || dh < 8) { char m_[256]; snprintf(m_, sizeof m_, "attention head dim %d unsupported (multiple of 8, <= %d)", dh, ADH_MAX); throw std::invalid_argument(m_); }
-    // (the MFMA kernel addresses q, k and v through 32-bit buffer offsets: operands of 2 GiB and more take the scalar kernel)
-    if (is_half(dtype) && (dh == 32 || dh == 64 || dh == 96) && ldk % 8 == 0 && ldq % 8 == 0 && !(reinterpret_cast<uintptr_t>(v) & 15) &&
-        !(reinterpret_cast<uintptr_t>(q) & 15) && !(reinterpret_cast<uintptr_t>(k) & 15) && (int64_t)B * Lq * ldq * 2 < 0x7FFFFFFFll &&
-        (int64_t)B * Lk * ldk * 2 < 0x7FFFFFFFll) {
-        // keys go through LDS in chunks of at most 128 (one chunk covers the 50 style tokens and ~100-token texts; longer texts
-        // take several), so the MFMA kernel serves every context length at 2 workgroups per CU
-        const int lk_pad = (Lk + 31) & ~31;
-        const int kc = lk_pad < 128 ? lk_pad : 128;
-        const size_t need = (size_t)128 * (dh * 2 + 16) + (size_t)kc * (dh * 2 + 16) + (size_t)dh * (kc * 2 + 8);
+    const AttnForm f = attn_form(dtype, B, Lq, Lk, H, dh, ldq, ldk, q, k, v);
+    const float log_base = logf(rope_base);
+    if (f.mfma) {
         const uint16_t *q16 = static_cast<const uint16_t*>(q), *k16 = static_cast<const uint16_t*>(k), *v16 = static_cast<const uint16_t*>(v);
         uint16_t* o16 = static_cast<uint16_t*>(o);
-        const float lb = logf(rope_base);
-        if (dh == 32) { if (dtype == F16) launch_attn_mfma<32, true>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); else launch_attn_mfma<32, false>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); }
-        else if (dh == 64) { if (dtype == F16) launch_attn_mfma<64, true>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); else launch_attn_mfma<64, false>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); }
-        else { if (dtype == F16) launch_attn_mfma<96, true>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); else launch_attn_mfma<96, false>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, kc, need, qlen, klen, rope_mode, lb, rope_gamma, (int)k_rotated, q_off, k_off); }
+#define STN_ATTN_MFMA(DH_, F16_) launch_attn_mfma<DH_, F16_>(s, q16, ldq, k16, v16, ldk, o16, ldo, B, Lq, Lk, H, f.kc, f.lds, qlen, klen, rope_mode, log_base, rope_gamma, (int)k_rotated, q_off, k_off)
+        if (f.dh == 32) { if (dtype == F16) STN_ATTN_MFMA(32, true); else STN_ATTN_MFMA(32, false); }
+        else if (f.dh == 64) { if (dtype == F16) STN_ATTN_MFMA(64, true); else STN_ATTN_MFMA(64, false); }
+        else { if (dtype == F16) STN_ATTN_MFMA(96, true); else STN_ATTN_MFMA(96, false); }
+#undef STN_ATTN_MFMA
         return;
     }
-    const int ds = dh + 1;
-    const float log_base = logf(rope_base);
-    // few workgroups (single utterances): 32 threads per query row cut the work per thread, i.e. the launch's latency, by four
-    const bool wide = (int64_t)((Lq + AQ - 1) / AQ) * H * B < 96;
-    const int qr = wide ? 8 : AQ;
-    const size_t lds = sizeof(float) * ((size_t)(qr + 2 * AK) * ds + (size_t)qr * (AK + 1));
-    const dim3 grid((Lq + qr - 1) / qr, H, B);
+    const dim3 grid((Lq + 256 / f.tpr - 1) / (256 / f.tpr), H, B);
     static PerDeviceOnce attr_once;
     if (attr_once.need()) {
         stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<float, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "hipFuncSetAttribute(attn f32)");
@@ -584,9 +618,10 @@ void launch_attention(hipStream_t s, int dtype, const void* q, int ldq, const vo
         stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<f16_t, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "hipFuncSetAttribute(attn f16 wide)");
     }
 #define STN_ATTN_GO(T_, TPR_)                                                                                                  \
-    STN_KLAUNCH((attn_kernel<T_, TPR_>), grid, dim3(256), lds, s, static_cast<const T_*>(q), ldq, static_cast<const T_*>(k),      \
+    STN_KLAUNCH((attn_kernel<T_, TPR_>), grid, dim3(256), f.lds, s, static_cast<const T_*>(q), ldq, static_cast<const T_*>(k),    \
                 static_cast<const T_*>(v), ldk, static_cast<T_*>(o), ldo, Lq, Lk, dh, qlen, klen, rope_mode, log_base, rope_gamma, \
-                (int)k_rotated, q_off, k_off)
+                (int)k_rotated, q_off, k_off, f.vec)
+    const bool wide = f.tpr == 32;
     if (dtype == F16) { if (wide) STN_ATTN_GO(f16_t, 32); else STN_ATTN_GO(f16_t, 8); }
     else if (dtype == BF16) { if (wide) STN_ATTN_GO(uint16_t, 32); else STN_ATTN_GO(uint16_t, 8); }
     else { if (wide) STN_ATTN_GO(float, 32); else STN_ATTN_GO(float, 8); }

@@ -539,7 +539,20 @@ int hs_group(int B, int L, int kc) {
 
 }  // namespace
 
-int xattn_hs_group(int B, int L, int Lk) { return hs_group(B, L, (Lk + 31) & ~31); }
+XattnHsForm xattn_hs_form(int dtype, int C, int H, int B, int L, int Lk, int ldk) {
+    if (!xattn_hs_supported(dtype, C, H, L, Lk, ldk)) throw std::invalid_argument("xattn_hs_form: unsupported shape (callers check xattn_hs_supported)");
+    XattnHsForm f;
+    f.f16 = dtype == F16;
+    f.kc = (Lk + 31) & ~31;
+    f.U = hs_group(B, L, f.kc);
+    f.lds = (size_t)hs_lds_bytes(f.U, f.kc);
+    return f;
+}
+std::string XattnHsForm::str() const {
+    char b[48];
+    snprintf(b, sizeof b, "xattn_hs<%s,U%d> kc%d", f16 ? "f16" : "bf16", U, kc);
+    return b;
+}
 void launch_xattn_hs_pairs(hipStream_t s, const int* qlen, int B, int* pairs) {
     if (B < 1 || B > 1024) throw std::invalid_argument("launch_xattn_hs_pairs: 1 <= B <= 1024");
     STN_KLAUNCH(hs_pairs_kernel, dim3(1), dim3(1024), 0, s, qlen, B, pairs);
@@ -562,14 +575,14 @@ void launch_xattn_hs(hipStream_t s, int dtype, const void* xn, int64_t M, const 
     a.xn = static_cast<const uint16_t*>(xn); a.wq = static_cast<const uint16_t*>(WqF); a.bq = bq;
     a.kp = static_cast<const uint16_t*>(kp); a.vp = static_cast<const uint16_t*>(vp); a.wo = static_cast<const uint16_t*>(WoA);
     a.part = static_cast<uint16_t*>(part); a.part_stride = part_stride; a.M = M; a.ldk = ldk; a.B = B; a.Lk = Lk;
-    a.kc = (Lk + 31) & ~31;
-    const int U = hs_group(B, L, a.kc);
+    const XattnHsForm f = xattn_hs_form(dtype, HS_C, HS_H, B, L, Lk, ldk);
+    a.kc = f.kc;
+    const int U = f.U;
     a.G = (B + U - 1) / U; a.Gpad = (a.G + 7) & ~7;
     a.qlen = qlen; a.klen = klen; a.q_off = q_off; a.k_off = k_off; a.pairs = pairs;
     a.rope_mode = rope_mode; a.log_base = logf(rope_base); a.gamma = rope_gamma; a.ts = ts;
-    const size_t lds = (size_t)hs_lds_bytes(U, a.kc);
-    if (dtype == F16) { if (U == 2) hs_launch<true, 2>(s, a, lds); else hs_launch<true, 1>(s, a, lds); }
-    else { if (U == 2) hs_launch<false, 2>(s, a, lds); else hs_launch<false, 1>(s, a, lds); }
+    if (f.f16) { if (U == 2) hs_launch<true, 2>(s, a, f.lds); else hs_launch<true, 1>(s, a, f.lds); }
+    else { if (U == 2) hs_launch<false, 2>(s, a, f.lds); else hs_launch<false, 1>(s, a, f.lds); }
 }
 
 }  // namespace stn

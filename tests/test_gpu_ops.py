@@ -135,8 +135,11 @@ def test_dwconv_ln(eng, C, k, dil, B, L):
                                               (16, 2, 5, 6, 0), (64, 4, 200, 310, 0), (96, 2, 130, 50, -1), (32, 4, 129, 33, 1),
                                               # long contexts: keys stream through LDS in 128-key chunks (3 chunks here), partial last chunk
                                               (96, 4, 78, 311, 1), (96, 2, 140, 257, 0), (32, 2, 40, 129, -1),
-                                              # a handful of keys, no rotation (fp32: attn_fewkeys_f32_kernel; the duration predictor's 8 style tokens)
-                                              (64, 2, 70, 8, -1), (96, 1, 130, 16, -1), (16, 2, 5, 6, -1), (64, 2, 300, 1, -1)])
+                                              # a handful of keys, no rotation (the duration predictor's 8 style tokens): fp32 and dh = 16
+                                              # take the scalar attn_kernel<T, 32>, 16-bit dh = 64 / 96 the MFMA kernel with one 32-key chunk
+                                              (64, 2, 70, 8, -1), (96, 1, 130, 16, -1), (16, 2, 5, 6, -1), (64, 2, 300, 1, -1),
+                                              # 112 workgroups of 32 query rows: the scalar attn_kernel<T, 8> in every format (dh = 40)
+                                              (40, 8, 200, 70, 1)])
 def test_attention(eng, dh, H, Lq, Lk, rope):
     rng = np.random.default_rng(dh + Lq + Lk)
     B, C = 2, dh * H

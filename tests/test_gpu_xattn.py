@@ -64,6 +64,24 @@ def test_head_split_equals_four_launches(dtype, tol_max, tol_rms, n, min_words, 
     eng.set_fused_xattn(0)
 
 
+@pytest.mark.parametrize("field,value", [("ve_kernel", 3), ("ve_dilated", 6)])
+def test_head_split_needs_a_fold_reader(field, value):
+    """The head-split block leaves its four partial sums to the next ConvNeXt block's fold_dwconv_ln, so it may run only where that kernel
+    takes the block's shape.  ve_kernel = 3: no fold kernel (and no packed rows at all); ve_dilated = 6: the last dilated block's dilation
+    32 puts the fold's LDS image over 160 KiB while the packed rows and the head-split shapes stay.  Both must complete with the head-split
+    form requested, with the same bits as the four launches (it then takes them itself)."""
+    arch, ids, mask, sttl, sdp, durs, D, L, lens, lm = _inputs(5, 3, 9, 21)
+    setattr(arch, field, value)
+    assert L <= 256 and ids.shape[1] <= 128
+    fd = durs * np.float32(1.05)
+    noise = randn(23, 5, D, L)
+    eng = binding.Engine(0, "bf16")
+    eng.load_synthetic(arch, 7)
+    b = _batch_latent(eng, 1, ids, mask, sttl, sdp, fd, 2, noise)
+    a = _batch_latent(eng, 0, ids, mask, sttl, sdp, fd, 2, noise)
+    assert np.all(np.isfinite(b)) and np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("dtype,tol_max,tol_rms", [("bf16", 3e-1, 5e-2), ("f16", 4e-2, 8e-3)])
 def test_head_split_vs_oracle(dtype, tol_max, tol_rms):
     arch, ids, mask, sttl, sdp, durs, D, L, lens, lm = _inputs(6, 3, 9, 5)
