@@ -294,6 +294,15 @@ int stn_op_gemm_ex(stn_handle* h, int dtype, int M, int N, int K, const float* A
  * Operands K-contiguous with lda = ldw = K and 16-byte aligned pointers; masked != 0: a row mask by length; tr as stn_op_gemm_ex.
  * Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher refuses (STN_ERR_INVALID). */
 int stn_dbg_gemm_form(int dtype, int M, int N, int K, int mode, int out_dtype, int ldo, int masked, int tr, char* out, size_t cap);
+/* diagnostics (no device needed): the form a ConvNeXt block's pointwise pair takes — "gemms" (two tiled GEMM launches; "gemms nt": pw1
+ * stores its hidden activation non-temporally), "k4" (one fused launch) or "k4splitS" (S hidden shares, folded by the next reader of x).
+ * stage: 1 vocoder, 2 estimator, 4 text encoder / duration predictor; M: the launch's rows; gate_rows > 0: the row count the K4
+ * decision is taken on instead (a trimmed vocoder's dense B*T); packed: rows packed per sequence; k, max_dil: the stage's conv taps
+ * and largest dilation; mask, min_rows, split_min_rows: as stn_set_fused_ffn / stn_set_fused_ffn_min_rows (defaults 9, 18432, 1);
+ * nt_hints: the engine's non-temporal hints (default on).  Returns the string's length (written with its NUL when it fits in cap),
+ * < 0 on invalid arguments (STN_ERR_INVALID). */
+int stn_dbg_ffn_form(int dtype, int stage, int C, int I, int64_t M, int64_t gate_rows, int packed, int k, int max_dil, int mask,
+                     int64_t min_rows, int64_t split_min_rows, int nt_hints, char* out, size_t cap);
 /* device-resident timing of one GEMM shape on random operands; mode 0 = bias+GELU store, 1 = residual epilogue */
 int stn_op_gemm_bench(stn_handle* h, int dtype, int M, int N, int K, int mode, int iters, double* avg_ms);
 /* diagnostics: shader-clock phase stamps of ONE launch of the tiled GEMM kernel on this shape (mode as above).  out6 = mean

@@ -16,6 +16,7 @@ _DTYPES = {"f32": F32, "fp32": F32, "float32": F32, "bf16": BF16, "f16": F16, "f
            F32: F32, BF16: BF16, F16: F16}
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_TANH = 0, 1, 2, 3
 EPI_STORE, EPI_RESID, EPI_STORE_T = 0, 1, 2  # GEMM epilogue modes (stn_op_gemm_ex)
+FFN_VOCODER, FFN_ESTIMATOR, FFN_TEXT = 1, 2, 4  # ConvNeXt stages (ffn_form)
 
 
 class StnError(RuntimeError):
@@ -161,6 +162,9 @@ def load():
     L.stn_dbg_gemm_form.restype = ctypes.c_int
     L.stn_dbg_attn_form.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_attn_form.restype = ctypes.c_int
+    L.stn_dbg_ffn_form.argtypes = [ci, ci, ci, ci, ctypes.c_int64, ctypes.c_int64, ci, ci, ci, ci, ctypes.c_int64, ctypes.c_int64, ci,
+                                   ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_ffn_form.restype = ctypes.c_int
     L.stn_launch_log.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_launch_log.restype = ctypes.c_int64
     L.stn_profile_enable.argtypes = [vp, ci]
@@ -338,6 +342,17 @@ def attn_form(dtype, B, Lq, Lk, H, dh, ldq=None, ldk=None, misaligned=0, kind=0)
                                  int(C if ldk is None else ldk), int(misaligned), buf, len(buf))
     if r < 0:
         raise StnError(r, "stn_dbg_attn_form: the launcher refuses this call")
+    return buf.value.decode()
+
+
+def ffn_form(dtype, stage, C, I, M, gate_rows=0, packed=True, k=5, max_dil=1, mask=9, min_rows=18432, split_min_rows=1, nt_hints=True):
+    """The form a ConvNeXt block's pointwise pair takes (stn_dbg_ffn_form; host-only): "gemms", "gemms nt", "k4" or "k4splitS".
+    stage: FFN_VOCODER, FFN_ESTIMATOR or FFN_TEXT; the settings default to the engine's."""
+    buf = ctypes.create_string_buffer(32)
+    r = load().stn_dbg_ffn_form(_DTYPES[dtype], int(stage), int(C), int(I), int(M), int(gate_rows), int(bool(packed)), int(k), int(max_dil),
+                                int(mask), int(min_rows), int(split_min_rows), int(bool(nt_hints)), buf, len(buf))
+    if r < 0:
+        raise StnError(r, "stn_dbg_ffn_form: invalid arguments")
     return buf.value.decode()
 
 

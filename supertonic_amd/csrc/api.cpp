@@ -445,6 +445,15 @@ int stn_dbg_gemm_form(int dtype, int M, int N, int K, int mode, int out_dtype, i
     if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
     return (int)f.size();
 }
+int stn_dbg_ffn_form(int dtype, int stage, int C, int I, int64_t M, int64_t gate_rows, int packed, int k, int max_dil, int mask,
+                     int64_t min_rows, int64_t split_min_rows, int nt_hints, char* out, size_t cap) {
+    if (C < 1 || I < 1 || M < 1 || k < 1 || max_dil < 1 || (stage != stn::FFN_VOCODER && stage != stn::FFN_ESTIMATOR && stage != stn::FFN_TEXT) ||
+        (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16))
+        return STN_ERR_INVALID;
+    const std::string f = stn::ffn_form(dtype, stage, C, I, M, gate_rows, packed != 0, k, max_dil, mask, min_rows, split_min_rows, nt_hints != 0).str();
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
+}
 int stn_op_gemm_bench(stn_handle* h, int dtype, int M, int N, int K, int mode, int iters, double* avg_ms) {
     STN_TRY(h, { need(M > 0 && N > 0 && K > 0 && iters > 0 && avg_ms, "stn_op_gemm_bench: bad argument");
                  need(K % (dtype != STN_DTYPE_F32 ? 8 : 4) == 0, "K must be a multiple of 8 (bf16) / 4 (f32)");

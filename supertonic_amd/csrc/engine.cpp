@@ -548,10 +548,11 @@ void* Engine::to_act(const float* src, int64_t n) {
     return d;
 }
 
-// x <- (x + gamma * pw2(GELU(pw1(LN(dwconv(x)))))) * mask      (in place, x fp32 [B*L][C])
-void Engine::convnext(const ConvNeXt& p, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
+// x <- (x + gamma * pw2(GELU(pw1(LN(dwconv(x)))))) * mask      (in place, x fp32 [B*L][C]); the pointwise pair in form f
+void Engine::convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
                       const int* conv_len, const float* rowvec, int rv_ld, const Ragged* rg, FoldState* fs) {
     const int64_t M = rg ? (int64_t)rg->rows : (int64_t)B * L;
+    if (f.kind == FFN_K4_SPLIT && !(fs && rg)) throw std::logic_error("convnext: K4-split needs the stage's fold state and packed rows");
     const Arena::Mark mk = ar_.mark();
     void* xn = act_alloc(M * C);
     if (fs) x = fs->x;
@@ -569,59 +570,53 @@ void Engine::convnext(const ConvNeXt& p, float* x, int B, int L, int C, int hid,
         launch_dwconv_ln(s_, dt_, x, B, L, C, p.dw_t, p.dw_b, k, dil, p.ln.g, p.ln.b, a_.ln_eps, xn, rg ? len : conv_len, rg ? rg->off : nullptr);
         if (prof_on_) prof_end();
     }
-    // K4: pw1 -> GELU -> pw2 -> layer scale + residual in one launch, the hidden activation never leaves the registers
-    const int stage_bit = stage_[0] == 'v' && stage_[1] == 'o' ? 1 : (stage_[0] == 'v' ? 2 : 4);
-    const auto fw = ffn_w_.find(p.pw1.w.as(dt_));
-    // K4-split (the estimator at batch size: 59 slabs of 128 rows cannot fill 256 CUs, and a workgroup that streams both matrices
-    // for 128 rows is ingest-bound): four workgroups per slab, each over a quarter of the hidden units (a quarter of the weight
-    // stream), 16-bit partial sums; b2, layer scale, residual and time vector are applied by the next reader of x.  How many
-    // ways is ffn_split_choose's decision on the launch's row count (fs->S).  Packed rows only (the fold kernels index sequences through row_off).
-    if (fs && fs->S > 1 && rg && (fused_ffn_ & 8) && stage_bit == 2 && fw != ffn_w_.end() && fw->second.wsplit[split_slot(fs->S)] && M >= ffn_split_min_rows_ &&
-        M * C * 2 < 0x7FFFFFFFll && fold_dwconv_ln_supported(C, k, 1 << std::max(0, a_.ve_dilated - 1))) {
-        FfnArgs fa;
-        fa.xn = xn; fa.ldx = C; fa.wseq = fw->second.wsplit[split_slot(fs->S)]; fa.b1 = p.pw1.b; fa.M = (int)M; fa.I = hid;
-        fa.split = fs->S; fa.part = fs->part; fa.part_stride = fs->part_stride;
-        if (prof_on_) prof_begin("ffn_split", 4.0 * M * (double)C * hid, (double)M * C * (2.0 + 2.0 * fa.split) + 4.0 * C * hid);
-        launch_ffn_fused(s_, dt_, C, fa);
-        if (prof_on_) prof_end();
-        fs->pending = true;
-        fs->fold = FoldArgs{};
-        fs->fold.part = fs->part; fs->fold.S = fa.split; fs->fold.part_stride = fs->part_stride;
-        fs->fold.b2 = p.pw2.b; fs->fold.gamma = p.gamma; fs->fold.rowvec = rowvec; fs->fold.rv_ld = rv_ld; fs->fold.row_b = rowvec ? rg->row_b : nullptr;
-        ar_.release(mk);
-        return;
+    FfnArgs fa;
+    fa.xn = xn; fa.ldx = C; fa.b1 = p.pw1.b; fa.b2 = p.pw2.b; fa.gamma = p.gamma; fa.x = x; fa.ldo = C; fa.M = (int)M; fa.I = hid;
+    fa.rowvec = rowvec; fa.rv_ld = rv_ld; fa.row_b = (rg && rowvec) ? rg->row_b : nullptr;
+    fa.len = rg ? nullptr : len; fa.L = L;
+    if (f.kind != FFN_GEMMS) {  // (prepare_ffn_weights packs every stream ffn_form can ask for)
+        const auto fw = ffn_w_.find(p.pw1.w.as(dt_));
+        const int* s = std::find(std::begin(FFN_SPLITS), std::end(FFN_SPLITS), f.split);
+        fa.wseq = fw == ffn_w_.end() ? nullptr : f.kind == FFN_K4 ? fw->second.wseq : s != std::end(FFN_SPLITS) ? fw->second.wsplit[s - FFN_SPLITS] : nullptr;
+        if (!fa.wseq) throw std::logic_error("convnext: no packed weight stream for " + f.str());
     }
-    // ... where it pays: a workgroup streams both weight matrices whatever its share of the rows, so below ~half a chip of
-    // 128-row workgroups the two tiled launches win (tools/ffn_bench.py sweep, C = 512: 16384 rows 108 vs 107 us, 20480 rows
-    // 116 vs 141 us, 294 rows = one utterance 102 vs 29 us)
-    // (the vocoder decides on its DENSE frame count: a run that skips position-independent padding rows must take the same kernel
-    // as the dense run it is bit-identical to)
-    if ((fused_ffn_ & stage_bit) && (ffn_gate_rows_ > 0 ? ffn_gate_rows_ : M) >= ffn_min_rows_ && fw != ffn_w_.end() && ffn_fused_supported(dt_, C, hid) && M * C * 2 < 0x7FFFFFFFll) {
-        FfnArgs fa;
-        fa.xn = xn; fa.ldx = C; fa.wseq = fw->second.wseq; fa.b1 = p.pw1.b; fa.b2 = p.pw2.b; fa.gamma = p.gamma;
-        fa.x = x; fa.ldo = C; fa.M = (int)M; fa.I = hid; fa.rowvec = rowvec; fa.rv_ld = rv_ld;
-        fa.row_b = (rg && rowvec) ? rg->row_b : nullptr;
-        fa.len = rg ? nullptr : len; fa.L = L;
-        if (prof_on_) prof_begin("ffn_fused", 4.0 * M * (double)C * hid, (double)M * C * (2.0 + 8.0) + 4.0 * C * hid);
-        launch_ffn_fused(s_, dt_, C, fa);
-        if (prof_on_) prof_end();
-        ar_.release(mk);
-        return;
-    }
-    void* u = act_alloc(M * hid);
-    Epilogue e1;
-    e1.mode = EPI_STORE; e1.act = gelu_act_; e1.out_dtype = dt_; e1.out = u; e1.ldo = hid;
-    // a hidden activation larger than half the 256 MB Infinity Cache (the vocoder's: 245 MB per block at C3) is written once:
-    // non-temporal stores keep it from evicting the residual stream and the LayerNorm output (vo.pw1 181 -> 162 us).  Measured
-    // and rejected: non-temporal A loads in pw2 (+9 %: each panel is read by two column tiles); running pw1/pw2 slab by slab
-    // over the rows through a cache-sized hidden buffer (2 / 3 / 4 / 6 slabs: vocoder stage 4.08 -> 4.71 / 5.25 / 4.66 / 5.82 ms)
-    if (nt_hints_ && is_half(dt_) && (double)M * hid * 2.0 > 128e6) e1.nt = 1;
-    gemm("gemm_pw1_gelu", dt_, xn, C, p.pw1, (int)M, e1);
-    Epilogue e2;
-    e2.mode = EPI_RESID; e2.resid = x; e2.ldo = C; e2.gamma = p.gamma; e2.len = rg ? nullptr : len; e2.L = L; e2.rowvec = rowvec; e2.rv_ld = rv_ld;
-    e2.row_b = (rg && rowvec) ? rg->row_b : nullptr;
-    gemm("gemm_pw2_resid", dt_, u, hid, p.pw2, (int)M, e2);
+    if (f.kind == FFN_K4_SPLIT) { fa.part = fs->part; fa.part_stride = fs->part_stride; }
+    const FoldArgs pending = ffn_launch(f, C, fa, p.pw1, p.pw2);
+    if (f.kind == FFN_K4_SPLIT) { fs->fold = pending; fs->pending = true; }
     ar_.release(mk);
+}
+
+FoldArgs Engine::ffn_launch(const FfnForm& f, int C, const FfnArgs& a, const Linear& w1, const Linear& w2) {
+    const int64_t M = a.M;
+    const int hid = a.I;
+    FoldArgs pending;
+    if (f.kind == FFN_K4_SPLIT) {
+        // the split launch reads only these: b2, layer scale, residual and time vector are the fold's
+        FfnArgs sa;
+        sa.xn = a.xn; sa.ldx = a.ldx; sa.wseq = a.wseq; sa.b1 = a.b1; sa.M = a.M; sa.I = hid; sa.ts = a.ts;
+        sa.split = f.split; sa.part = a.part; sa.part_stride = a.part_stride;
+        if (prof_on_) prof_begin("ffn_split", 4.0 * M * (double)C * hid, (double)M * C * (2.0 + 2.0 * sa.split) + 4.0 * C * hid);
+        launch_ffn_fused(s_, dt_, C, sa);
+        if (prof_on_) prof_end();
+        pending = ffn_pending(f, a);
+    } else if (f.kind == FFN_K4) {
+        // pw1 -> GELU -> pw2 -> layer scale + residual in one launch, the hidden activation never leaves the registers
+        if (prof_on_) prof_begin("ffn_fused", 4.0 * M * (double)C * hid, (double)M * C * (2.0 + 8.0) + 4.0 * C * hid);
+        launch_ffn_fused(s_, dt_, C, a);
+        if (prof_on_) prof_end();
+    } else {
+        const Arena::Mark mk = ar_.mark();
+        void* u = act_alloc(M * hid);
+        Epilogue e1;
+        e1.mode = EPI_STORE; e1.act = gelu_act_; e1.out_dtype = dt_; e1.out = u; e1.ldo = hid; e1.bias = a.b1; e1.nt = f.nt ? 1 : 0;
+        gemm("gemm_pw1_gelu", dt_, a.xn, a.ldx, w1, (int)M, e1);
+        Epilogue e2;
+        e2.mode = EPI_RESID; e2.resid = a.x; e2.ldo = a.ldo; e2.bias = a.b2; e2.gamma = a.gamma; e2.len = a.len; e2.L = a.L;
+        e2.rowvec = a.rowvec; e2.rv_ld = a.rv_ld; e2.row_b = a.row_b;
+        gemm("gemm_pw2_resid", dt_, u, hid, w2, (int)M, e2);
+        ar_.release(mk);
+    }
+    return pending;
 }
 
 void Engine::fold_layernorm(FoldState& fs, int64_t M, int C, const LNorm& ln, void* xn, const char* tag) {
@@ -694,8 +689,9 @@ void Engine::duration_dev(int B, int Lt, const int64_t* ids, const float* style_
     const Arena::Mark mk = ar_.mark();
     float* x = f32_alloc(M * C);
     launch_embed(s_, ids, vecf("dp.emb"), a.vocab_size, B, Lt, C, tlen, x, toff);
+    const FfnForm ff = ffn_plan(FFN_TEXT, C, a.dp_hidden, M, 0, trg != nullptr, a.dp_kernel, 1);  // (fp32: two GEMMs)
     for (int i = 0; i < a.dp_conv_blocks; ++i)
-        convnext(convnext_w("dp.conv" + std::to_string(i)), x, B, Lt, C, a.dp_hidden, a.dp_kernel, 1, tlen, nullptr, nullptr, 0, trg);
+        convnext(convnext_w("dp.conv" + std::to_string(i)), ff, x, B, Lt, C, a.dp_hidden, a.dp_kernel, 1, tlen, nullptr, nullptr, 0, trg);
     void* st = to_act(style_dp, (int64_t)B * a.n_style_dp * a.d_style_dp);
     attn_block(attn_w("dp.st", false), x, B, Lt, C, a.dp_heads, st, a.n_style_dp, tlen, nullptr, -1, false, trg);
     float* xn = f32_alloc(M * C);
@@ -723,8 +719,9 @@ void Engine::text_enc_dev(int B, int Lt, const int64_t* ids, const float* style_
     const Arena::Mark mk = ar_.mark();
     float* x = f32_alloc(M * C);
     launch_embed(s_, ids, vecf("te.emb"), a.vocab_size, B, Lt, C, tlen, x, trg ? trg->off : nullptr);
+    const FfnForm ff = ffn_plan(FFN_TEXT, C, a.te_hidden, M, 0, trg != nullptr, a.te_kernel, 1);
     for (int i = 0; i < a.te_conv_blocks; ++i)
-        convnext(convnext_w("te.conv" + std::to_string(i)), x, B, Lt, C, a.te_hidden, a.te_kernel, 1, tlen, nullptr, nullptr, 0, trg);
+        convnext(convnext_w("te.conv" + std::to_string(i)), ff, x, B, Lt, C, a.te_hidden, a.te_kernel, 1, tlen, nullptr, nullptr, 0, trg);
     for (int i = 0; i < a.te_attn_blocks; ++i) {
         const std::string p = "te.sa" + std::to_string(i);
         attn_block(attn_w(p, true), x, B, Lt, C, a.te_heads, nullptr, Lt, tlen, tlen, 0, true, trg);
@@ -828,18 +825,17 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
     // the latent as rows for the input projection: the caller's persistent buffer when the step before left it there (euler_ncl writes both layouts)
     void* z = z_rows ? z_rows : act_alloc(M * Dp);
     if (!(z_rows && z_ready)) launch_ncl_to_rows(s_, dt_, noisy, B, D, L, z, Dp, llen, roff);
+    // one form for every ConvNeXt block of the stage (same C, I, k and rows)
+    const FfnForm ff = ffn_plan(FFN_ESTIMATOR, C, a.ve_hidden, M, 0, rg != nullptr, a.ve_kernel, 1 << std::max(0, a.ve_dilated - 1));
+    const bool split = ff.kind == FFN_K4_SPLIT;
     FoldState fs;  // the residual stream (and, with K4-split blocks, its pending update)
     fs.x = f32_alloc(M * C);
-    {
-        const int S = ffn_split_choose(dt_, C, a.ve_hidden, M);
-        if (rg && S > 1 && (fused_ffn_ & 8) && M >= ffn_split_min_rows_) {
-            fs.x_alt = f32_alloc(M * C);
-            fs.part_stride = ffn_split_rows(M) * C;
-            fs.part = act_alloc(fs.part_stride * S);
-            fs.S = S;
-        }
+    if (split) {   // the partial sums of a K4-split block or of a head-split cross-attention (H of them)
+        fs.x_alt = f32_alloc(M * C);
+        fs.part_stride = ffn_split_rows(M) * C;
+        fs.part = act_alloc(fs.part_stride * std::max(ff.split, H));
     }
-    FoldState* const fsp = fs.part ? &fs : nullptr;
+    FoldState* const fsp = split ? &fs : nullptr;
     Epilogue ein; ein.mode = EPI_STORE; ein.out_dtype = F32; ein.out = fs.x; ein.ldo = C; ein.len = rmask; ein.L = L;
     gemm("gemm_in", dt_, z, Dp, linear("ve.in_pad"), (int)M, ein);
     if (!tb) tb = ve_time_cond_dev(B, total_step, current_step);
@@ -850,9 +846,8 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
         const char* kp0 = static_cast<const char*>(kv_all) + (size_t)blk * 2 * C * esz;
         const auto fq = frag_w_.find(w.q.w.as(dt_));
         const auto foa = frag_acc_w_.find(w.o.w.as(dt_));
-        // (the partial sums are added by the next ConvNeXt block's fold_dwconv_ln: only where that kernel takes the block's shape, as for K4-split)
-        if (fused_xattn_ && fsp && unit_vec_ && C <= 1024 && fq != frag_w_.end() && foa != frag_acc_w_.end() && xattn_hs_supported(dt_, C, H, L, Lk, nb * 2 * C) &&
-            M * C * 2 < 0x7FFFFFFFll && fold_dwconv_ln_supported(C, a.ve_kernel, 1 << std::max(0, a.ve_dilated - 1))) {
+        // (the partial sums are folded in by the next reader of x, as a K4-split block's: only in a stage whose blocks are K4-split)
+        if (fused_xattn_ && split && unit_vec_ && C <= 1024 && fq != frag_w_.end() && foa != frag_acc_w_.end() && xattn_hs_supported(dt_, C, H, L, Lk, nb * 2 * C)) {
             // HEAD-SPLIT: fold_ln (or LayerNorm), then ONE launch per block — q projection, rotation, attention and the head's share of the
             // output projection per (utterance pair, head), stored as four 16-bit per-head partial sums in K4-split's layout; the next
             // ConvNeXt block's fold_dwconv_ln adds them (and the output bias) to x in head order
@@ -901,17 +896,17 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
         // the time conditioning x += tb[b] rides in the residual epilogue of the last dilated block (was a separate pass)
         for (int j = 0; j < a.ve_dilated; ++j) {
             const bool last = j == a.ve_dilated - 1;
-            convnext(convnext_w(p + ".dil" + std::to_string(j)), fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1 << j, llen, nullptr,
+            convnext(convnext_w(p + ".dil" + std::to_string(j)), ff, fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1 << j, llen, nullptr,
                      last ? tb + (size_t)blk * C : nullptr, nb * C, rg, fsp);
         }
         if (a.ve_dilated == 0) launch_add_rowvec(s_, fs.x, tb + (size_t)blk * C, nb * C, B, L, C, llen);  // (padded layout only)
-        convnext(convnext_w(p + ".cn_a"), fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
+        convnext(convnext_w(p + ".cn_a"), ff, fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
         cross(p + ".text", c.text_kv, blk, c.Lt, tlen, 1);
-        convnext(convnext_w(p + ".cn_b"), fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
+        convnext(convnext_w(p + ".cn_b"), ff, fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
         cross(p + ".style", c.style_kv, blk, a.n_style_ttl, nullptr, -1);
     }
     for (int j = 0; j < a.ve_tail_blocks; ++j)
-        convnext(convnext_w("ve.tail" + std::to_string(j)), fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
+        convnext(convnext_w("ve.tail" + std::to_string(j)), ff, fs.x, B, L, C, a.ve_hidden, a.ve_kernel, 1, llen, nullptr, nullptr, 0, rg, fsp);
     void* xn = act_alloc(M * C);
     fold_layernorm(fs, M, C, lnorm("ve.out_ln"), xn, nullptr);
     // Euler update fused into the output projection; dt[b] = 1 / total_step[b]
@@ -1019,15 +1014,15 @@ void Engine::prepare_ffn_weights() {
         launch_ffn_pack(s_, c.pw1.w.as(dt_), c.pw2.w.as(dt_), C, hid, tmp, wseq);
         sync();  // tmp is reused by the next block
         FfnW fw; fw.wseq = wseq;
-        if (p.compare(0, 3, "ve.") == 0)  // the estimator's blocks also as hidden-split stage streams, one copy per split
-            for (int S : {4, 8, 12}) {  // (the splits ffn_split_choose hands out)
-                if (!ffn_split_valid(dt_, C, hid, S)) continue;
+        if (p.compare(0, 3, "ve.") == 0)  // the estimator's blocks also as K4-split stage streams, one copy per split
+            for (size_t i = 0; i < std::size(FFN_SPLITS); ++i) {
+                if (!ffn_split_valid(dt_, C, hid, FFN_SPLITS[i])) continue;
                 void* ws = nullptr;
                 STN_HIP(hipMalloc(&ws, (size_t)2 * hid * C * 2));
                 owned_.push_back(ws);
-                launch_ffn_pack(s_, c.pw1.w.as(dt_), c.pw2.w.as(dt_), C, hid, tmp, ws, S);
+                launch_ffn_pack(s_, c.pw1.w.as(dt_), c.pw2.w.as(dt_), C, hid, tmp, ws, FFN_SPLITS[i]);
                 sync();
-                fw.wsplit[split_slot(S)] = ws;
+                fw.wsplit[i] = ws;
             }
         ffn_w_[c.pw1.w.as(dt_)] = fw;
     };
@@ -1096,7 +1091,6 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
     const bool packed = vlen && vrows > 0 && is_half(dt_) && B <= 1024 && dwconv_ln_supports_packed(C, a.vo_kernel);
     if (valid && !packed) throw std::runtime_error("trimmed vocoder needs the packed bf16 path");
     const int64_t M = packed ? (int64_t)vrows : (int64_t)B * T;
-    ffn_gate_rows_ = valid ? (int64_t)B * T : 0;
     const Arena::Mark mk = ar_.mark();
     Ragged rg;
     if (packed) {
@@ -1122,10 +1116,12 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
                           a.vo_in_kernel, x, vlen);
         if (prof_on_) prof_end();
     }
+    // (a trimmed run decides on its DENSE frame count: it must take the kernel of the dense run it is bit-identical to)
+    const FfnForm ff = ffn_plan(FFN_VOCODER, C, a.vo_hidden, M, valid ? (int64_t)B * T : 0, packed, a.vo_kernel,
+                                a.vo_blocks ? *std::max_element(a.vo_dilations, a.vo_dilations + a.vo_blocks) : 1);
     for (int i = 0; i < a.vo_blocks; ++i)
-        convnext(convnext_w("vo.blk" + std::to_string(i)), x, B, T, C, a.vo_hidden, a.vo_kernel, a.vo_dilations[i],
+        convnext(convnext_w("vo.blk" + std::to_string(i)), ff, x, B, T, C, a.vo_hidden, a.vo_kernel, a.vo_dilations[i],
                  packed ? vlen : nullptr, packed ? nullptr : vlen, nullptr, 0, rgp);
-    ffn_gate_rows_ = 0;
     void* xn = act_alloc(M * C);
     const LNorm ln = lnorm("vo.out_ln");
     launch_layernorm(s_, dt_, x, M, C, ln.g, ln.b, a.ln_eps, xn);

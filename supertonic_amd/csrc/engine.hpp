@@ -9,6 +9,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <iterator>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -137,8 +138,7 @@ class Engine {
     std::unordered_map<const void*, const void*> frag_acc_w_;  // ... -> its copy in accumulator-operand k order (Wo of the head-split block, kernels_xattn_hs.hip)
     void prepare_vocoder_constants();     // zero-latent response of the loaded model: quiet chunk and edge tail
     void prepare_ffn_weights();           // fragment-ordered copies of every ConvNeXt block's pw1 / pw2 (kernels_ffn.hip, K4)
-    struct FfnW { const void* wseq = nullptr; const void* wsplit[4] = {nullptr, nullptr, nullptr, nullptr}; };  // wsplit: the hidden-split stage streams for S = 4, 12, 24, 8
-    static int split_slot(int S) { return S == 4 ? 0 : S == 12 ? 1 : S == 24 ? 2 : 3; }
+    struct FfnW { const void *wseq = nullptr, *wsplit[std::size(FFN_SPLITS)] = {}; };  // wsplit: the estimator's K4-split streams, one per FFN_SPLITS entry
     std::unordered_map<const void*, FfnW> ffn_w_;  // key: the block's row-major 16-bit pw1 matrix
 
     // ---- host-pointer stages: 1:1 with the reference's four Run sites ------------------------------
@@ -215,8 +215,8 @@ class Engine {
     // cross-attention blocks of the estimator head-split (kernels_xattn_hs.hip) instead of four launches
     void set_fused_xattn(int mode) { fused_xattn_ = mode ? 1 : 0; }  // 0: four launches; otherwise head-split (fold_ln + one launch, kernels_xattn_hs.hip)
     // K4: the pointwise pair of a ConvNeXt block as one launch.  Bit mask over the stages: 1 = vocoder, 2 = vector estimator,
-    // 4 = text encoder / duration predictor.  bf16 engines, widths 256 / 384 / 512 (ffn_fused_supported)
-    // 8 = the estimator's blocks as K4-split (hidden dimension cut over 4 workgroups per 128-row slab, 16-bit partial sums folded
+    // 4 = text encoder / duration predictor.  16-bit engines, widths 384 / 512 (ffn_fused_supported)
+    // 8 = the estimator's blocks as K4-split (hidden dimension cut over 4, 8 or 12 workgroups per 128-row slab, 16-bit partial sums folded
     // by the next reader of x: fold_dwconv_ln / fold_ln); packed rows, from ffn_split_min_rows() rows on
     void set_fused_ffn(int mask) { fused_ffn_ = mask; }
     void set_fused_ffn_min_rows(int64_t k4_rows, int64_t split_rows) {
@@ -351,12 +351,25 @@ class Engine {
         float* x_alt = nullptr;  // second buffer: fold_dwconv_ln writes the folded stream there and the two swap
         void* part = nullptr;    // [S][rows padded to 128][C] 16-bit partial sums (one buffer: its reader runs before the next writer)
         int64_t part_stride = 0;
-        int S = 0;               // the split this stage's launches take (ffn_split_choose of its row count)
         bool pending = false;
         FoldArgs fold;           // the pending update
     };
-    // fs (optional): x is fs->x; the block may leave its pointwise pair pending in fs (the caller folds it with the next reader of x)
-    void convnext(const ConvNeXt& p, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
+    // the form of a stage's pointwise pairs (ffn_form with this engine's settings): every block of a stage has the same C, I, k and rows
+    FfnForm ffn_plan(int stage, int C, int I, int64_t M, int64_t gate_rows, bool packed, int k, int max_dil) const {
+        return ffn_form(dt_, stage, C, I, M, gate_rows, packed, k, max_dil, fused_ffn_, ffn_min_rows_, ffn_split_min_rows_, nt_hints_);
+    }
+    // the pointwise pair in form f.  a: its operands (a.wseq the stream packed for f; a.part / a.part_stride a K4-split's partial-sum buffer);
+    // w1 / w2: the plain matrices (two GEMMs).  K4-split leaves x alone and returns the pending update, for the next reader of x to fold.
+    FoldArgs ffn_launch(const FfnForm& f, int C, const FfnArgs& a, const Linear& w1, const Linear& w2);
+    static FoldArgs ffn_pending(const FfnForm& f, const FfnArgs& a) {  // the update a K4-split launch leaves pending
+        return FoldArgs{a.part, f.split, a.part_stride, a.b2, a.gamma, a.rowvec, a.rv_ld, a.row_b};
+    }
+    // the FFN op entry points' set-up: the form `mode` forces (0 two GEMMs, 1 K4, 2 K4-split with ffn_split_choose's S), W1 [I][C] / W2 [C][I]
+    // (fp32, device) in the 16-bit format, and the launch's shape, packed weight stream and partial-sum buffer in `a` (operands left to fill)
+    struct FfnOp { FfnForm f; Linear w1, w2; FfnArgs a; };
+    FfnOp op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2);
+    // fs: x is fs->x, and a K4-split block leaves its pointwise pair pending in fs (the caller folds it with the next reader of x)
+    void convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
                   const int* conv_len = nullptr, const float* rowvec = nullptr, int rv_ld = 0, const Ragged* rg = nullptr, FoldState* fs = nullptr);
     // LayerNorm of the stage's residual stream into xn, folding a pending update first
     void fold_layernorm(FoldState& fs, int64_t M, int C, const LNorm& ln, void* xn, const char* tag);
@@ -424,7 +437,6 @@ class Engine {
     hipEvent_t ev_te_ = nullptr, ev_copied_ = nullptr, ev_dp_ = nullptr;
     std::function<void()> text_gate_;  // armed by enqueue_after_duration, fired once by the first text cross-attention of the run
     bool copied_valid_ = false;
-    int64_t ffn_gate_rows_ = 0;     // row count the K4 decision is taken on when it is not the launch's own (trimmed dense vocoder)
     int64_t ffn_min_rows_ = 18432;  // K4 only from this many rows on (144 workgroups); STN_FFN_MIN_ROWS overrides
     int64_t ffn_split_min_rows_ = 1;     // K4-split from this many rows on (with the slab staged through LDS one utterance gains too: 20.0 vs 21.4 us per block); STN_FFN_SPLIT_MIN_ROWS overrides
     int fused_ffn_ = 9;         // K4 stages (set_fused_ffn): adopted where measured faster; STN_FFN=<mask> overrides

@@ -298,58 +298,55 @@ void Engine::op_gemm_phases(int dtype, int M, int N, int K, int mode, double* ou
     out6[3] = (double)(tend - tmin); out6[4] = (double)(tmax_in - tmin); out6[5] = (double)n;
 }
 
+Engine::FfnOp Engine::op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2) {
+    const std::string name(op);
+    if (!is_half(dt_)) throw std::invalid_argument(name + ": 16-bit engines only");
+    if (mode != FFN_GEMMS && !ffn_fused_supported(dt_, C, I)) throw std::invalid_argument(name + ": shape not supported by the fused kernel");
+    FfnOp o;
+    o.f.kind = mode;
+    if (mode == FFN_K4_SPLIT && (o.f.split = ffn_split_choose(dt_, C, I, M)) < 2)
+        throw std::invalid_argument(name + ": shape not supported by the hidden-split kernel");
+    o.f.nt = mode == FFN_GEMMS && nt_hints_ && (double)M * I * 2.0 > 128e6;  // (ffn_form's rule)
+    void *w1 = act_alloc((int64_t)I * C), *w2 = act_alloc((int64_t)I * C);
+    launch_cast(s_, dt_, W1, (int64_t)I * C, w1); launch_cast(s_, dt_, W2, (int64_t)I * C, w2);
+    o.w1.w.bf16 = static_cast<uint16_t*>(w1); o.w1.N = I; o.w1.K = C;
+    o.w2.w.bf16 = static_cast<uint16_t*>(w2); o.w2.N = C; o.w2.K = I;
+    o.a.ldx = o.a.ldo = C; o.a.M = o.a.L = M; o.a.I = I;
+    if (mode != FFN_GEMMS) {
+        void* tmp = act_alloc((int64_t)2 * I * C);
+        void* wseq = act_alloc((int64_t)2 * I * C);
+        launch_ffn_pack(s_, w1, w2, C, I, tmp, wseq, o.f.split);
+        o.a.wseq = wseq;
+    }
+    if (mode == FFN_K4_SPLIT) { o.a.part_stride = ffn_split_rows(M) * C; o.a.part = act_alloc(o.a.part_stride * o.f.split); }
+    return o;
+}
+
 void Engine::op_ffn(int M, int C, int I, const float* xn, const float* W1, const float* b1, const float* W2, const float* b2, const float* gamma,
                     const float* rowvec, const int* row_b, int nseq, float* x, int mode) {
     STN_HIP(hipSetDevice(device_));
-    const bool fused = mode != 0;
-    if (!is_half(dt_)) throw std::invalid_argument("op_ffn: 16-bit engines only");
-    if (fused && !ffn_fused_supported(dt_, C, I)) throw std::invalid_argument("op_ffn: shape not supported by the fused kernel");
-    if (mode == 2 && ffn_split_factor(dt_, C, I) < 2) throw std::invalid_argument("op_ffn: shape not supported by the hidden-split kernel");
     ar_.reset();
-    float* d_xn = up(ar_, s_, xn, (size_t)M * C);
     float* d_w1 = up(ar_, s_, W1, (size_t)I * C);
     float* d_w2 = up(ar_, s_, W2, (size_t)C * I);
-    float* d_b1 = up(ar_, s_, b1, (size_t)I);
-    float* d_b2 = b2 ? up(ar_, s_, b2, (size_t)C) : nullptr;
-    float* d_g = gamma ? up(ar_, s_, gamma, (size_t)C) : nullptr;
-    float* d_x = up(ar_, s_, x, (size_t)M * C);
-    float* d_rv = rowvec ? up(ar_, s_, rowvec, (size_t)nseq * C) : nullptr;
-    int* d_rb = (rowvec && row_b) ? up(ar_, s_, row_b, (size_t)M) : nullptr;
+    FfnOp op = op_ffn_setup("op_ffn", mode, M, C, I, d_w1, d_w2);
+    FfnArgs& fa = op.a;
+    float* d_xn = up(ar_, s_, xn, (size_t)M * C);
     void* xn16 = act_alloc((int64_t)M * C);
-    void* w1_16 = act_alloc((int64_t)I * C);
-    void* w2_16 = act_alloc((int64_t)I * C);
     launch_cast(s_, dt_, d_xn, (int64_t)M * C, xn16);
-    launch_cast(s_, dt_, d_w1, (int64_t)I * C, w1_16);
-    launch_cast(s_, dt_, d_w2, (int64_t)I * C, w2_16);
-    if (fused) {
-        void* tmp = act_alloc((int64_t)2 * I * C);
-        void* wseq = act_alloc((int64_t)2 * I * C);
-        const int S = mode == 2 ? ffn_split_choose(dt_, C, I, M) : 1;
-        launch_ffn_pack(s_, w1_16, w2_16, C, I, tmp, wseq, S);
-        FfnArgs fa;
-        fa.xn = xn16; fa.ldx = C; fa.wseq = wseq; fa.b1 = d_b1; fa.b2 = d_b2; fa.gamma = d_g; fa.x = d_x; fa.ldo = C;
-        fa.M = M; fa.I = I; fa.rowvec = d_rv; fa.rv_ld = C; fa.row_b = d_rb; fa.L = M;
-        if (mode == 2) {
-            fa.split = S; fa.part_stride = ffn_split_rows(M) * C; fa.part = act_alloc(fa.part_stride * S);
-            launch_ffn_fused(s_, dt_, C, fa);
-            // the pending update, folded by the LayerNorm form of the fold (its normalised output is not part of this op)
-            float* ones = f32_alloc(C);
-            launch_fill(s_, ones, C, 1.f);
-            float* zeros = f32_alloc(C);
-            launch_fill(s_, zeros, C, 0.f);
-            FoldArgs fo; fo.part = fa.part; fo.S = S; fo.part_stride = fa.part_stride; fo.b2 = d_b2 ? d_b2 : zeros; fo.gamma = d_g ? d_g : ones;
-            fo.rowvec = d_rv; fo.rv_ld = C; fo.row_b = d_rb;
-            void* y = act_alloc((int64_t)M * C);
-            launch_fold_ln(s_, dt_, d_x, M, C, fo, ones, ones, a_.ln_eps, y);
-        } else {
-            launch_ffn_fused(s_, dt_, C, fa);
-        }
-    } else {
-        void* u = act_alloc((int64_t)M * I);
-        Epilogue e1; e1.mode = EPI_STORE; e1.act = ACT_GELU; e1.out_dtype = dt_; e1.out = u; e1.ldo = I; e1.bias = d_b1;
-        launch_gemm(s_, dt_, xn16, C, w1_16, C, M, I, C, e1);
-        Epilogue e2; e2.mode = EPI_RESID; e2.resid = d_x; e2.ldo = C; e2.gamma = d_g; e2.bias = d_b2; e2.rowvec = d_rv; e2.rv_ld = C; e2.row_b = d_rb; e2.L = M;
-        launch_gemm(s_, dt_, u, I, w2_16, I, M, C, I, e2);
+    float* d_x = up(ar_, s_, x, (size_t)M * C);
+    fa.xn = xn16; fa.x = d_x; fa.b1 = up(ar_, s_, b1, (size_t)I); fa.b2 = b2 ? up(ar_, s_, b2, (size_t)C) : nullptr;
+    fa.gamma = gamma ? up(ar_, s_, gamma, (size_t)C) : nullptr;
+    fa.rowvec = rowvec ? up(ar_, s_, rowvec, (size_t)nseq * C) : nullptr; fa.rv_ld = C;
+    fa.row_b = (rowvec && row_b) ? up(ar_, s_, row_b, (size_t)M) : nullptr;
+    FoldArgs fo = ffn_launch(op.f, C, fa, op.w1, op.w2);
+    if (op.f.kind == FFN_K4_SPLIT) {
+        // the pending update, folded by the LayerNorm form of the fold (its normalised output is not part of this op)
+        float *ones = f32_alloc(C), *zeros = f32_alloc(C);
+        launch_fill(s_, ones, C, 1.f); launch_fill(s_, zeros, C, 0.f);
+        if (!fo.b2) fo.b2 = zeros;
+        if (!fo.gamma) fo.gamma = ones;
+        void* y = act_alloc((int64_t)M * C);
+        launch_fold_ln(s_, dt_, d_x, M, C, fo, ones, ones, a_.ln_eps, y);
     }
     STN_HIP(hipGetLastError());
     STN_HIP(hipMemcpyAsync(x, d_x, sizeof(float) * (size_t)M * C, hipMemcpyDeviceToHost, s_));
@@ -358,11 +355,6 @@ void Engine::op_ffn(int M, int C, int I, const float* xn, const float* W1, const
 
 void Engine::op_ffn_bench(int M, int C, int I, int mode, int iters, double* out5) {
     STN_HIP(hipSetDevice(device_));
-    const bool fused = mode != 0;
-    const int S = mode == 2 ? ffn_split_choose(dt_, C, I, M) : 1;
-    if (mode == 2 && S < 2) throw std::invalid_argument("op_ffn_bench: shape not supported by the hidden-split kernel");
-    if (!is_half(dt_)) throw std::invalid_argument("op_ffn_bench: 16-bit engines only");
-    if (fused && !ffn_fused_supported(dt_, C, I)) throw std::invalid_argument("op_ffn_bench: shape not supported by the fused kernel");
     ar_.reset();
     for (int i = 0; i < 5; ++i) out5[i] = 0.0;
     // random operands (the clock a chip holds on zeros is not the clock it holds on data)
@@ -371,45 +363,21 @@ void Engine::op_ffn_bench(int M, int C, int I, int mode, int iters, double* out5
     float* wr = f32_alloc((int64_t)I * C);
     launch_randn_masked(s_, 12, nullptr, 1, I, C, nullptr, wr);
     launch_scale(s_, wr, I * C, 0.05f);
+    FfnOp op = op_ffn_setup("op_ffn_bench", mode, M, C, I, wr, wr);
     void* xn16 = act_alloc((int64_t)M * C);
-    void* w1_16 = act_alloc((int64_t)I * C);
-    void* w2_16 = act_alloc((int64_t)I * C);
     launch_cast(s_, dt_, rnd, (int64_t)M * C, xn16);
-    launch_cast(s_, dt_, wr, (int64_t)I * C, w1_16);
-    launch_cast(s_, dt_, wr, (int64_t)I * C, w2_16);
     float* d_b1 = f32_alloc(I);
     float* d_b2 = f32_alloc(C);
     float* d_g = f32_alloc(C);
     launch_fill(s_, d_b1, I, 0.01f); launch_fill(s_, d_b2, C, 0.01f); launch_fill(s_, d_g, C, 0.1f);
     float* d_x = f32_alloc((int64_t)M * C);
     STN_HIP(hipMemsetAsync(d_x, 0, sizeof(float) * (size_t)M * C, s_));
-    void* wseq = nullptr;
-    if (fused) {
-        void* tmp = act_alloc((int64_t)2 * I * C);
-        wseq = act_alloc((int64_t)2 * I * C);
-        launch_ffn_pack(s_, w1_16, w2_16, C, I, tmp, wseq, S);
-    }
-    void* u = fused ? nullptr : act_alloc((int64_t)M * I);
-    const int64_t pstride = ffn_split_rows(M) * C;
-    void* part = mode == 2 ? act_alloc(pstride * S) : nullptr;
+    op.a.xn = xn16; op.a.b1 = d_b1; op.a.b2 = d_b2; op.a.gamma = d_g; op.a.x = d_x;
+    const int S = op.f.split;
     const int nslab = (M + 127) / 128;
-    const int nwg = mode == 2 ? (nslab + 7) / 8 * 8 * S : nslab;
+    const int nwg = S > 1 ? (nslab + 7) / 8 * 8 * S : nslab;
     unsigned long long* ts = static_cast<unsigned long long*>(ar_.alloc(sizeof(unsigned long long) * 4 * (size_t)nwg));
-    auto run = [&](unsigned long long* stamps) {
-        if (fused) {
-            FfnArgs fa;
-            fa.xn = xn16; fa.ldx = C; fa.wseq = wseq; fa.b1 = d_b1; fa.b2 = d_b2; fa.gamma = d_g; fa.x = d_x; fa.ldo = C;
-            fa.M = M; fa.I = I; fa.L = M; fa.ts = stamps;
-            if (mode == 2) { fa.split = S; fa.part = part; fa.part_stride = pstride; }
-            launch_ffn_fused(s_, dt_, C, fa);
-        } else {
-            Epilogue e1; e1.mode = EPI_STORE; e1.act = ACT_GELU; e1.out_dtype = dt_; e1.out = u; e1.ldo = I; e1.bias = d_b1;
-            if (nt_hints_ && (double)M * I * 2.0 > 128e6) e1.nt = 1;
-            launch_gemm(s_, dt_, xn16, C, w1_16, C, M, I, C, e1);
-            Epilogue e2; e2.mode = EPI_RESID; e2.resid = d_x; e2.ldo = C; e2.gamma = d_g; e2.bias = d_b2; e2.L = M;
-            launch_gemm(s_, dt_, u, I, w2_16, I, M, C, I, e2);
-        }
-    };
+    auto run = [&](unsigned long long* stamps) { op.a.ts = stamps; ffn_launch(op.f, C, op.a, op.w1, op.w2); };
     for (int i = 0; i < 3; ++i) run(nullptr);
     hipEvent_t a, b;
     STN_HIP(hipEventCreate(&a)); STN_HIP(hipEventCreate(&b));
@@ -421,7 +389,7 @@ void Engine::op_ffn_bench(int M, int C, int I, int mode, int iters, double* out5
     STN_HIP(hipEventElapsedTime(&ms, a, b));
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     out5[0] = ms / iters;
-    if (fused) {
+    if (op.f.kind != FFN_GEMMS) {
         STN_HIP(hipMemsetAsync(ts, 0, sizeof(unsigned long long) * 4 * (size_t)nwg, s_));
         run(ts);
         std::vector<unsigned long long> h((size_t)4 * nwg);
@@ -485,12 +453,13 @@ void Engine::op_fold_dwconv_ln(int B, int C, int k, int dil, int S, const int* s
 
 void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode, int iters, double* out2) {
     STN_HIP(hipSetDevice(device_));
-    if (!is_half(dt_)) throw std::invalid_argument("op_block_bench: 16-bit engines only");
-    const int S = ffn_split_choose(dt_, C, I, (int64_t)B * L);
-    if (mode == 2 && S < 2) throw std::invalid_argument("op_block_bench: shape not supported by the hidden-split kernel");
     ar_.reset();
     for (int i = 0; i < 6; ++i) out2[i] = 0.0;
     const int64_t M = (int64_t)B * L;
+    float* wr = f32_alloc((int64_t)I * C);
+    launch_randn_masked(s_, 12, nullptr, 1, I, C, nullptr, wr);
+    launch_scale(s_, wr, I * C, 0.05f);
+    FfnOp op = op_ffn_setup("op_block_bench", mode, (int)M, C, I, wr, wr);
     std::vector<int> len(B, L), off(B + 1);
     for (int i = 0; i <= B; ++i) off[i] = i * L;
     const int* dlen = up(ar_, s_, len.data(), (size_t)B);
@@ -498,13 +467,6 @@ void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode
     float* xa = f32_alloc(M * C);
     float* xb = f32_alloc(M * C);
     launch_randn_masked(s_, 11, nullptr, 1, (int)M, C, nullptr, xa);
-    float* wr = f32_alloc((int64_t)I * C);
-    launch_randn_masked(s_, 12, nullptr, 1, I, C, nullptr, wr);
-    launch_scale(s_, wr, I * C, 0.05f);
-    void* w1_16 = act_alloc((int64_t)I * C);
-    void* w2_16 = act_alloc((int64_t)I * C);
-    launch_cast(s_, dt_, wr, (int64_t)I * C, w1_16);
-    launch_cast(s_, dt_, wr, (int64_t)I * C, w2_16);
     float* d_b1 = f32_alloc(I);
     float* d_b2 = f32_alloc(C);
     float* d_g = f32_alloc(C);
@@ -513,34 +475,15 @@ void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode
     launch_fill(s_, d_b1, I, 0.01f); launch_fill(s_, d_b2, C, 0.01f); launch_fill(s_, d_g, C, 0.01f); launch_fill(s_, d_one, C, 1.f);
     launch_fill(s_, dwt, k * C, 1.f / k);
     void* xn = act_alloc(M * C);
-    void* u = mode == 2 ? nullptr : act_alloc(M * I);
-    void* wseq = nullptr;
-    const int64_t pstride = ffn_split_rows(M) * C;
-    void* part = nullptr;
-    if (mode == 2) {
-        void* tmp = act_alloc((int64_t)2 * I * C);
-        wseq = act_alloc((int64_t)2 * I * C);
-        launch_ffn_pack(s_, w1_16, w2_16, C, I, tmp, wseq, S);
-        part = act_alloc(pstride * S);
-        STN_HIP(hipMemsetAsync(part, 0, (size_t)pstride * S * 2, s_));
-    }
-    FoldArgs fo; fo.part = part; fo.S = S; fo.part_stride = pstride; fo.b2 = d_b2; fo.gamma = d_g;
+    op.a.xn = xn; op.a.b1 = d_b1; op.a.b2 = d_b2; op.a.gamma = d_g;
+    const bool split = op.f.kind == FFN_K4_SPLIT;
+    if (split) STN_HIP(hipMemsetAsync(op.a.part, 0, (size_t)op.a.part_stride * op.f.split * 2, s_));
+    FoldArgs fo = ffn_pending(op.f, op.a);  // (K4-split) every block leaves the same pending update
     auto conv = [&]() {
-        if (mode == 2) { launch_fold_dwconv_ln(s_, dt_, xa, xb, B, L, C, fo, dwt, d_b2, k, dil, d_one, d_b2, 1e-6f, xn, dlen, doff); std::swap(xa, xb); }
+        if (split) { launch_fold_dwconv_ln(s_, dt_, xa, xb, B, L, C, fo, dwt, d_b2, k, dil, d_one, d_b2, 1e-6f, xn, dlen, doff); std::swap(xa, xb); }
         else launch_dwconv_ln(s_, dt_, xa, B, L, C, dwt, d_b2, k, dil, d_one, d_b2, 1e-6f, xn, dlen, doff);
     };
-    auto block = [&]() {
-        conv();
-        if (mode == 2) {
-            FfnArgs fa; fa.xn = xn; fa.ldx = C; fa.wseq = wseq; fa.b1 = d_b1; fa.M = (int)M; fa.I = I; fa.split = S; fa.part = part; fa.part_stride = pstride;
-            launch_ffn_fused(s_, dt_, C, fa);
-        } else {
-            Epilogue e1; e1.mode = EPI_STORE; e1.act = ACT_GELU; e1.out_dtype = dt_; e1.out = u; e1.ldo = I; e1.bias = d_b1;
-            launch_gemm(s_, dt_, xn, C, w1_16, C, (int)M, I, C, e1);
-            Epilogue e2; e2.mode = EPI_RESID; e2.resid = xa; e2.ldo = C; e2.gamma = d_g; e2.bias = d_b2; e2.L = (int)M;
-            launch_gemm(s_, dt_, u, I, w2_16, I, (int)M, C, I, e2);
-        }
-    };
+    auto block = [&]() { conv(); op.a.x = xa; ffn_launch(op.f, C, op.a, op.w1, op.w2); };
     hipEvent_t a, b;
     STN_HIP(hipEventCreate(&a)); STN_HIP(hipEventCreate(&b));
     for (int which = 0; which < 2; ++which) {
@@ -554,7 +497,7 @@ void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode
         out2[which] = ms / iters;
     }
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    if (mode == 2) {  // phase stamps of one fold_dwconv_ln launch
+    if (split) {  // phase stamps of one fold_dwconv_ln launch
         const int nwg = B * ((L + 7) / 8);  // (runs of 8 frames when there are few sequences, of 32 otherwise: sized for the shorter)
         unsigned long long* ts = static_cast<unsigned long long*>(ar_.alloc(sizeof(unsigned long long) * 4 * (size_t)nwg));
         STN_HIP(hipMemsetAsync(ts, 0, sizeof(unsigned long long) * 4 * (size_t)nwg, s_));

@@ -162,7 +162,9 @@ struct FfnArgs {
 bool ffn_fused_supported(int dtype, int C, int I);
 // whether the block shape has a K4-split form at all (0: no; > 1: yes)
 int ffn_split_factor(int dtype, int C, int I);
-// splits a block shape can run with (4, 8, 12, 24: I / 32 / S hidden tiles per workgroup, an even number), and the one a launch of M rows
+// the splits K4-split runs with: one packed weight stream per entry (Engine::prepare_ffn_weights); ffn_split_choose hands out no other
+constexpr int FFN_SPLITS[] = {4, 8, 12};
+// splits a block shape can run with (FFN_SPLITS: I / 32 / S hidden tiles per workgroup, an even number), and the one a launch of M rows
 // takes: 12 ways up to 12 slabs (1536 rows), 8 ways up to 32 slabs (4096 rows: still one round of workgroups), 4 ways beyond.  The split is a function of the launch's ROW COUNT, so the order in which a
 // row's 16-bit partial sums are added depends on how many rows the launch has: results on either side of the boundary (an utterance
 // alone, a 16-utterance shard of a strong-scaling run, the unsharded batch) agree to rounding, not bit for bit (include/stn.h,
@@ -170,6 +172,20 @@ int ffn_split_factor(int dtype, int C, int I);
 bool ffn_split_valid(int dtype, int C, int I, int S);
 int ffn_split_choose(int dtype, int C, int I, int64_t M);
 inline int64_t ffn_split_rows(int64_t M) { return (M + 127) / 128 * 128; }
+// The form a ConvNeXt block's pointwise pair takes — one decision, made by ffn_form and executed by Engine::ffn_launch, so that what the
+// diagnostics report (stn_dbg_ffn_form) is what runs: two tiled GEMMs (nt: pw1's hidden activation stored non-temporally), K4, or K4-split
+// over `split` hidden shares whose update the next reader of x folds in.
+enum FfnKind : int { FFN_GEMMS = 0, FFN_K4 = 1, FFN_K4_SPLIT = 2 };
+enum FfnStage : int { FFN_VOCODER = 1, FFN_ESTIMATOR = 2, FFN_TEXT = 4 };  // (FFN_TEXT: also the duration predictor) the stage's bit of the K4 mask
+struct FfnForm {
+    int kind = FFN_GEMMS, split = 1;
+    bool nt = false;
+    std::string str() const;  // "gemms", "gemms nt", "k4", "k4split12"
+};
+// M: the launch's rows; gate_rows > 0: the rows K4 is decided on instead (a trimmed vocoder's dense B*T); packed: rows packed per sequence;
+// k, max_dil: the stage's conv taps and largest dilation (the fold kernel must take them); mask, min_rows, split_min_rows, nt_hints: the engine's settings.
+FfnForm ffn_form(int dtype, int stage, int C, int I, int64_t M, int64_t gate_rows, bool packed, int k, int max_dil, int mask, int64_t min_rows,
+                 int64_t split_min_rows, bool nt_hints);
 // K4's LDS layout, one definition for the kernel and its launcher: 4 ring buffers of C * 64 bytes | b2, gamma (C floats each) | b1 (I floats) |
 // at C = 384 a fifth buffer, KiB-aligned, for wave 0's rows of the slab in the prologue (kernels_ffn_body.inc)
 __host__ __device__ constexpr inline int ffn_lds_side_offset(int C, int I) { return (4 * C * 64 + (I + 2 * C) * 4 + 1023) & ~1023; }

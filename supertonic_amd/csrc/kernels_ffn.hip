@@ -36,6 +36,9 @@
 
 #include <stdio.h>
 
+#include <algorithm>
+#include <iterator>
+
 namespace stn {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -280,7 +283,7 @@ int ffn_split_factor(int dtype, int C, int I) {
     return 4;
 }
 bool ffn_split_valid(int dtype, int C, int I, int S) {
-    return ffn_split_factor(dtype, C, I) > 1 && (S == 4 || S == 8 || S == 12 || S == 24) && (I / 32) % (2 * S) == 0;
+    return ffn_split_factor(dtype, C, I) > 1 && std::count(std::begin(FFN_SPLITS), std::end(FFN_SPLITS), S) && (I / 32) % (2 * S) == 0;
 }
 // Few rows: more, shorter workgroups per slab (each still streams only ITS share of the weights, so the cost of a launch is one
 // workgroup's prologue + its T = I/32/S hidden tiles + epilogue, whatever the number of slabs).  Measured on B sequences of 58 frames
@@ -299,6 +302,30 @@ int ffn_split_choose(int dtype, int C, int I, int64_t M) {
     // sequences on 8 ways are two rounds (41.8 against 33.5) and 4 ways stay
     const int want = force ? force : nslab <= 12 ? 12 : nslab <= 32 ? 8 : 4;
     return ffn_split_valid(dtype, C, I, want) ? want : 4;
+}
+
+FfnForm ffn_form(int dtype, int stage, int C, int I, int64_t M, int64_t gate_rows, bool packed, int k, int max_dil, int mask, int64_t min_rows,
+                 int64_t split_min_rows, bool nt_hints) {
+    const bool fits = M * C * 2 < 0x7FFFFFFFll;
+    // K4-split (the estimator at batch size: 59 slabs of 128 rows cannot fill 256 CUs, and a workgroup that streams both matrices for 128 rows
+    // is ingest-bound): S workgroups per slab, each over 1/S of the hidden units (1/S of the weight stream), 16-bit partial sums; b2, layer
+    // scale, residual and time vector are applied by the next reader of x (fold_dwconv_ln / fold_ln)
+    const int S = ffn_split_choose(dtype, C, I, M);
+    if (packed && stage == FFN_ESTIMATOR && (mask & 8) && S > 1 && M >= split_min_rows && fits && fold_dwconv_ln_supported(C, k, max_dil))
+        return {FFN_K4_SPLIT, S, false};
+    // K4 where it pays: a workgroup streams both weight matrices whatever its share of the rows, so below ~half a chip of 128-row workgroups
+    // the two tiled launches win (tools/ffn_bench.py sweep, C = 512: 16384 rows 108 vs 107 us, 20480 rows 116 vs 141 us, 294 rows = one
+    // utterance 102 vs 29 us)
+    if ((mask & stage) && (gate_rows > 0 ? gate_rows : M) >= min_rows && ffn_fused_supported(dtype, C, I) && fits) return {FFN_K4, 1, false};
+    // a hidden activation larger than half the 256 MB Infinity Cache (the vocoder's: 245 MB per block at C3) is written once: non-temporal
+    // stores keep it from evicting the residual stream and the LayerNorm output (vo.pw1 181 -> 162 us).  Measured and rejected: non-temporal A
+    // loads in pw2 (+9 %: each panel is read by two column tiles); running pw1/pw2 slab by slab over the rows through a cache-sized hidden
+    // buffer (2 / 3 / 4 / 6 slabs: vocoder stage 4.08 -> 4.71 / 5.25 / 4.66 / 5.82 ms)
+    return {FFN_GEMMS, 1, nt_hints && is_half(dtype) && (double)M * I * 2.0 > 128e6};
+}
+
+std::string FfnForm::str() const {
+    return kind == FFN_K4_SPLIT ? "k4split" + std::to_string(split) : kind == FFN_K4 ? "k4" : nt ? "gemms nt" : "gemms";
 }
 
 template <int C>
@@ -343,7 +370,7 @@ void launch_ffn_fused(hipStream_t s, int dtype, int C, const FfnArgs& a) {
     if (!ffn_fused_supported(dtype, C, a.I)) throw std::invalid_argument("launch_ffn_fused: unsupported shape or dtype");
     if (a.split > 1 && (!ffn_split_valid(dtype, C, a.I, a.split) || !a.part || a.part_stride < ffn_split_rows(a.M) * C ||
                         (reinterpret_cast<uintptr_t>(a.part) & 15)))
-        throw std::invalid_argument("launch_ffn_fused: hidden split needs a valid split (4, 8, 12 or 24 dividing I / 64) and a 16-byte aligned part buffer of [split][rows padded to 128][C]");
+        throw std::invalid_argument("launch_ffn_fused: hidden split needs a valid split (FFN_SPLITS, dividing I / 64) and a 16-byte aligned part buffer of [split][rows padded to 128][C]");
     if (a.split <= 1 && a.part) throw std::invalid_argument("launch_ffn_fused: part without split");
     if ((size_t)a.M * a.ldx * 2 >= 0x7FFFFFFFull || a.ldx % 8 || (reinterpret_cast<uintptr_t>(a.xn) & 15) ||
         (a.split <= 1 && (a.ldo % 4 || !a.x || (reinterpret_cast<uintptr_t>(a.x) & 15) || (a.rowvec && (a.rv_ld % 4 || (reinterpret_cast<uintptr_t>(a.rowvec) & 15))))))

@@ -173,7 +173,8 @@ def test_ffn_split_vs_float64_and_two_launches(eng, M, nseq):
     got = eng.op_ffn(*ops[:7], rowvec=ops[7], row_b=ops[8], fused=2)
     assert np.all(np.isfinite(got))
     x = ops[6]
-    S = 12 if (M + 127) // 128 <= 12 else 8 if (M + 127) // 128 <= 32 else 4  # ffn_split_choose
+    S = int(binding.ffn_form("bf16", binding.FFN_ESTIMATOR, C, I, M).removeprefix("k4split"))  # ffn_split_choose
+    assert S == (12 if (M + 127) // 128 <= 12 else 8 if (M + 127) // 128 <= 32 else 4)
     mx, rms = rel_err(got - x, ref64_split(*ops, S=S) - x)
     assert rms < 3e-3 and mx < 3e-2, (mx, rms)
     # against the unsplit float64 reference and the two launches: the 16-bit partial sums add ~2^-9 of a quarter's contribution
