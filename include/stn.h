@@ -242,6 +242,34 @@ const char* stn_resample_error(int in_hz, int out_hz);
  * NULL but not both.  1 <= rows <= 65535. */
 int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const float* x, float* y_or_null, int16_t* pcm_or_null);
 
+/* ---- loudness --------------------------------------------------------------------------------------
+ * With normalization on, every fetch path — stn_batch_fetch, stn_batch_fetch_pcm16, stn_batch_fetch_pcm16_begin / _end,
+ * stn_batch_copy_wav_device, stn_batch_copy_pcm16_device and through it the group gather — measures the finished waveform at the
+ * output rate (after resampling when a rate is set, before the PCM conversion) and scales row b by one fp32 gain on the handle's
+ * stream before its copy.  Row b's span is its first n_b = min(W_out, (int64_t)(duration_b * (float)rate)) samples (duration_b: the
+ * reported duration); padding beyond it is not measured and is scaled by the same gain.
+ * Loudness L_b: ITU-R BS.1770-4 integrated loudness of one channel: K-weighting (shelf, then high-pass; stn_kweighting_filter), 400 ms
+ * blocks at a 100 ms hop of (rate + 5) / 10 samples (whole blocks inside the span only), absolute gate -70 LUFS, relative gate -10 LU;
+ * -inf when the span is shorter than one block or every block is gated out.
+ * Gain g_b = min(10^((target - L_b) / 20), 10^(ceiling / 20) / peak_b), peak_b = max |x| over the span; 1 when L_b is -inf.  The fp32
+ * output is x * g_b (one fp32 multiply); the PCM output is that product converted as writeWavFile converts.  A row's L_b, peak_b and
+ * g_b depend on its first n_b samples and the rate only (fixed-order sums, no atomics): not on the batch it was in.
+ * The latent geometry, the durations, stn_batch_wav_device_ptr (model rate, not normalized) and the captured pipeline are unchanged:
+ * the setting drops or re-keys no captured graph.  DESIGN.md section 11 has the decomposition, the cost and the accuracy. */
+/* on = 0: off (the default: every fetch is byte for byte the one without it, with no extra launch).  target_lufs in [-60, 0],
+ * ceiling_dbfs (sample peak) in [-30, 0]; out of range: STN_ERR_INVALID with a message, and the previous setting stays in force. */
+int stn_set_loudness(stn_handle* h, int on, float target_lufs, float ceiling_dbfs);
+int stn_get_loudness(const stn_handle* h, int* on, float* target_lufs, float* ceiling_dbfs);
+/* the finished batch measured at the current output rate, whether normalization is on or not: L_b (LUFS), peak_b and the gain the
+ * current setting applies (1 when off); each pointer [B] floats or NULL */
+int stn_batch_loudness(stn_handle* h, float* lufs, float* peak, float* gain);
+/* op-level: rows x W fp32 (host) at hz in [8000, 192000]; row r's first n[r] samples (n_or_null = NULL: all W) -> L (LUFS, -inf when
+ * undefined) and sample peak, [rows] floats each (either may be NULL).  1 <= rows <= 65535. */
+int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float* lufs, float* peak);
+/* the K-weighting biquads at hz (host only, no device needed): b[3] and a[3] (a[0] = 1) of the shelf and of the high-pass, in double;
+ * STN_ERR_INVALID outside [8000, 192000] Hz */
+int stn_kweighting_filter(int hz, double* shelf_b3, double* shelf_a3, double* hp_b3, double* hp_a3);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

@@ -51,6 +51,8 @@ int stn_group_load_dir(stn_group* g, const char* onnx_dir);
 /* output rate of every rank (stn_set_output_rate): the gather is then sized from the ranks' samples at that rate and
  * stn_group_fetch_pcm16 returns output-rate PCM; 0 = the model's rate */
 int stn_group_set_output_rate(stn_group* g, int hz);
+/* loudness normalization of every rank (stn_set_loudness): the gathered PCM is then normalized row by row */
+int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceiling_dbfs);
 
 /* The deal, host only: utterance i goes to rank rank_of[i] as row row_of[i] of that rank's shard.  lengths[B] = token counts.
  * Sorted by length descending (ties: caller order), dealt round-robin: the k-th longest goes to rank k % n as row k / n. */

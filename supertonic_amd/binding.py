@@ -213,6 +213,13 @@ def load():
     L.stn_resample_error.restype = ctypes.c_char_p
     L.stn_op_resample.argtypes = [vp, ci, ci, ci, ci, _f32p, vp, vp]
     L.stn_group_set_output_rate.argtypes = [vp, ci]
+    _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+    L.stn_set_loudness.argtypes = [vp, ci, cf, cf]
+    L.stn_get_loudness.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf), ctypes.POINTER(cf)]
+    L.stn_batch_loudness.argtypes = [vp, vp, vp, vp]
+    L.stn_op_loudness.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp]
+    L.stn_kweighting_filter.argtypes = [ci, _f64p, _f64p, _f64p, _f64p]
+    L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
     L.stn_group_last_shards.argtypes = [vp, _i32p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
     _LIB = L
     return L
@@ -283,6 +290,11 @@ class Group:
         """Output rate of every rank (0 or None = the model's rate): the gathered PCM is then at that rate."""
         self._ck(self._lib.stn_group_set_output_rate(self._g, int(hz or 0)))
 
+    def set_loudness(self, target_lufs=None, ceiling_dbfs=-1.0):
+        """Loudness normalization of every rank (Engine.set_loudness): the gathered PCM is then normalized row by row."""
+        on, t = _loudness_args(target_lufs)
+        self._ck(self._lib.stn_group_set_loudness(self._g, on, t, float(ceiling_dbfs)))
+
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
         self._ck(self._lib.stn_group_last_shards(self._g, rows, samples))
@@ -305,6 +317,21 @@ def resample_filter(in_hz, out_hz):
     if rc < 0:
         raise StnError(rc, "stn_resample_filter failed")
     return taps
+
+
+def kweighting_filter(hz):
+    """BS.1770-4 K-weighting at hz (host only): (shelf_b, shelf_a, hp_b, hp_a), float64 [3] each, a[0] = 1.  StnError outside
+    [8000, 192000] Hz."""
+    out = [np.zeros(3, np.float64) for _ in range(4)]
+    rc = load().stn_kweighting_filter(int(hz), *out)
+    if rc < 0:
+        raise StnError(rc, f"stn_kweighting_filter: {hz} Hz is outside [8000, 192000] Hz")
+    return tuple(out)
+
+
+def _loudness_args(target_lufs):
+    """(on, target) for stn_set_loudness: None = off (the target passed along is then the default, -23 LUFS)"""
+    return (0, -23.0) if target_lufs is None else (1, float(target_lufs))
 
 
 def resample_error(in_hz, out_hz):
@@ -544,6 +571,46 @@ class Engine:
         self._ck(self._lib.stn_op_resample(self._h, int(in_hz), int(out_hz), rows, W, x, None if pcm else out.ctypes.data,
                                            out.ctypes.data if pcm else None))
         return out
+
+    def set_loudness(self, target_lufs=None, ceiling_dbfs=-1.0):
+        """Normalize every fetch to target_lufs (BS.1770-4 integrated loudness, [-60, 0]) with the gain capped so that the sample
+        peak stays at or below ceiling_dbfs ([-30, 0]); None = off (the default).  Measured on the GPU at the output rate."""
+        on, t = _loudness_args(target_lufs)
+        self._ck(self._lib.stn_set_loudness(self._h, on, t, float(ceiling_dbfs)))
+
+    def _loudness(self):
+        on, t, c = ctypes.c_int(), ctypes.c_float(), ctypes.c_float()
+        self._ck(self._lib.stn_get_loudness(self._h, ctypes.byref(on), ctypes.byref(t), ctypes.byref(c)))
+        return bool(on.value), t.value, c.value
+
+    @property
+    def loudness(self):
+        """The normalization target in LUFS, or None when normalization is off."""
+        on, t, _ = self._loudness()
+        return t if on else None
+
+    @property
+    def loudness_ceiling(self):
+        """The sample-peak ceiling of the normalization gain, dBFS."""
+        return self._loudness()[2]
+
+    def batch_loudness(self):
+        """The finished batch measured at the output rate -> (lufs [B], peak [B], gain [B]) float32; gain is what the current setting
+        applies (1 when off); lufs is -inf where a row is shorter than one 400 ms block or every block is gated out."""
+        B = self.batch_dims()[0]
+        lufs, peak, gain = (np.empty(B, np.float32) for _ in range(3))
+        self._ck(self._lib.stn_batch_loudness(self._h, lufs.ctypes.data, peak.ctypes.data, gain.ctypes.data))
+        return lufs, peak, gain
+
+    def op_loudness(self, x, hz, n=None):
+        """rows x W fp32 at hz on the GPU -> (lufs [rows], peak [rows]) over row r's first n[r] samples (None: all W)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        lufs, peak = np.empty(rows, np.float32), np.empty(rows, np.float32)
+        self._ck(self._lib.stn_op_loudness(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, lufs.ctypes.data,
+                                           peak.ctypes.data))
+        return lufs, peak
 
     def fetch_pcm16_begin(self, slot):
         """Start the PCM conversion + device->host copy of the finished batch on `slot` (0/1); returns at once."""

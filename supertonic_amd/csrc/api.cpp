@@ -322,6 +322,32 @@ int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && (y || pcm), "stn_op_resample: bad argument (1 <= rows <= 65535, W >= 1, x and y or pcm)");
                  h->eng->op_resample(in_hz, out_hz, rows, W, x, y, pcm); })
 }
+int stn_set_loudness(stn_handle* h, int on, float target_lufs, float ceiling_dbfs) {
+    STN_TRY(h, { h->eng->set_loudness(on != 0, target_lufs, ceiling_dbfs); })
+}
+int stn_get_loudness(const stn_handle* h, int* on, float* target_lufs, float* ceiling_dbfs) {
+    if (!h) return STN_ERR_INVALID;
+    h->eng->get_loudness(on, target_lufs, ceiling_dbfs);
+    return STN_OK;
+}
+int stn_batch_loudness(stn_handle* h, float* lufs, float* peak, float* gain) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_loudness(lufs, peak, gain); })
+}
+int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 h->eng->op_loudness(hz, rows, W, x, n, lufs, peak); })
+}
+int stn_kweighting_filter(int hz, double* shelf_b, double* shelf_a, double* hp_b, double* hp_a) {
+    stn::KWeighting k;
+    if (!stn::kweighting_design(hz, k).empty()) return STN_ERR_INVALID;
+    for (int i = 0; i < 3; ++i) {
+        if (shelf_b) shelf_b[i] = k.shelf_b[i];
+        if (shelf_a) shelf_a[i] = k.shelf_a[i];
+        if (hp_b) hp_b[i] = k.hp_b[i];
+        if (hp_a) hp_a[i] = k.hp_a[i];
+    }
+    return STN_OK;
+}
 int stn_batch_fetch(stn_handle* h, float* wav, size_t cap, float* duration) {
     STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch(wav, cap, duration); })
 }

@@ -2,7 +2,8 @@
 //   --onnx-dir --total-step --speed --n-test --voice-style --text --lang --save-dir --batch
 // plus engine flags: --device N, --gpus N (deal the batch over N devices: include/stn_group.h), --devices a,b,.. (explicit ordinals),
 // --dtype {fp32,bf16,fp16}, --seed S (0 = unseeded noise, like the reference), --sample-rate HZ (WAV files at HZ, resampled on the GPU;
-// absent: the model's rate).
+// absent: the model's rate), --loudness LUFS (every utterance normalized to that BS.1770-4 integrated loudness on the GPU; absent: off),
+// --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -59,6 +60,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--dtype" && more) { const std::string d = argv[++i]; opts.dtype = d == "fp32" ? STN_DTYPE_F32 : d == "fp16" ? STN_DTYPE_F16 : STN_DTYPE_BF16; }
         else if (a == "--seed" && more) opts.noise_seed = std::strtoull(argv[++i], nullptr, 10);
         else if (a == "--sample-rate" && more) opts.output_rate = std::atoi(argv[++i]);  // Hz of the WAV files (resampled on the GPU); absent: the model's
+        else if (a == "--loudness" && more) opts.loudness_lufs = std::strtof(argv[++i], nullptr);  // LUFS of every utterance (BS.1770-4, on the GPU); absent: off
+        else if (a == "--peak-ceiling" && more) opts.loudness_ceiling_dbfs = std::strtof(argv[++i], nullptr);  // dBFS cap of the loudness gain (default -1)
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (voice_style.size() != text.size()) {

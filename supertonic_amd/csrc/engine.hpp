@@ -264,6 +264,18 @@ class Engine {
     // rows x W fp32 at in_hz -> rows x ceil(W * P / Q) at out_hz, as fp32 (y) and / or PCM (pcm); host pointers
     void op_resample(int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm);
 
+    // ---- loudness (engine_loudness.cpp): off is the default (every fetch path is then exactly the one without it).  On, every fetch
+    // path measures the finished waveform at the output rate (BS.1770-4 integrated loudness of row b's first
+    // n_b = min(W_out, (int64_t)(duration_b * (float)rate)) samples, kernels_loudness.hip) and scales row b by
+    // g_b = min(10^((target - L_b) / 20), 10^(ceiling / 20) / peak_b) before its conversion and copy; the gain stays on the device.
+    void set_loudness(bool on, float target_lufs, float ceiling_dbfs);
+    bool loudness_on() const { return lo_on_; }
+    void get_loudness(int* on, float* target_lufs, float* ceiling_dbfs) const;
+    // the finished batch at the output rate: L_b, peak_b and the gain the current setting applies (1 when off); [B] host floats or null
+    void batch_loudness(float* lufs, float* peak, float* gain);
+    // rows x W fp32 (host) at hz, row r's first n[r] samples (all W when n is null) -> L, peak [rows] (host)
+    void op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -468,6 +480,22 @@ class Engine {
     void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride);
     float* rs_f32_buf(size_t n);
     int16_t* rs_pcm_buf(size_t n);
+    bool lo_on_ = false;
+    float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
+    LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
+    char* lo_buf_ = nullptr; size_t lo_buf_cap_ = 0;  // fetch-time scratch of the measurement (grow-only, outside the graph key)
+    std::vector<int64_t> lo_n_;        // the row lengths last uploaded into lo_buf_, at lo_n_ptr_ (empty: none)
+    int64_t* lo_n_ptr_ = nullptr;
+    struct LoScratch { float *st, *pk, *pa, *pb, *res; int64_t* n; };
+    LoScratch lo_scratch(int64_t rows, int64_t W);
+    void lo_prepare(LoudTable& t, int hz);
+    void lo_release();
+    // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain]
+    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on);
+    // the finished batch at the output rate (b.wav, or resampled into the fp32 scratch) measured on the stream: returns the rows,
+    // sets Wo (samples per row) and gain (device [B])
+    const float* lo_batch(int64_t& Wo, const float** gain, bool on, float** res = nullptr);
+    void lo_gain_enqueue(const float* x, int64_t rows, int64_t W, const float* g, float* y, int16_t* pcm, int64_t dst_stride);
     hipStream_t copy_s_ = nullptr;
     bool prof_on_ = false;
     std::vector<ProfSpan> spans_;

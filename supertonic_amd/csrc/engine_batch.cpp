@@ -411,6 +411,19 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
 
 void Engine::batch_fetch(float* wav, size_t wav_capacity, float* duration) {
     Batch& b = bt_;
+    if (wav && loudness_on()) {  // at the output rate, measured and scaled on the stream, then copied
+        int64_t Wo = 0;
+        const float* g = nullptr;
+        const float* src = lo_batch(Wo, &g, true);
+        const size_t no = (size_t)b.B * Wo;
+        if (wav_capacity < no) throw std::runtime_error("wav buffer too small: need " + std::to_string(no) + " floats");
+        float* d = rs_f32_buf(no);  // (the resampled rows themselves when a rate is set: scaled in place)
+        lo_gain_enqueue(src, b.B, Wo, g, d, nullptr, Wo);
+        STN_HIP(hipMemcpyAsync(wav, d, no * 4, hipMemcpyDeviceToHost, s_));
+        sync();
+        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+        return;
+    }
     if (wav && resample_on()) {  // at the output rate: resampled on the stream, then copied
         STN_HIP(hipSetDevice(device_));
         const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, Wo = out_len(W);
@@ -437,6 +450,19 @@ void Engine::batch_fetch_pcm16(int16_t* pcm, size_t capacity, float* duration) {
     Batch& b = bt_;
     const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (loudness_on()) {
+        int64_t Wo = 0;
+        const float* g = nullptr;
+        const float* src = lo_batch(Wo, &g, true);
+        const size_t no = (size_t)b.B * Wo;
+        if (capacity < no) throw std::runtime_error("pcm buffer too small: need " + std::to_string(no) + " samples");
+        int16_t* d = rs_pcm_buf(no);
+        lo_gain_enqueue(src, b.B, Wo, g, nullptr, d, Wo);
+        STN_HIP(hipMemcpyAsync(pcm, d, no * 2, hipMemcpyDeviceToHost, s_));
+        sync();
+        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+        return;
+    }
     if (resample_on()) {
         const int64_t W = (int64_t)(nw / (size_t)b.B), Wo = out_len(W);
         const size_t no = (size_t)b.B * Wo;
@@ -475,7 +501,12 @@ void Engine::batch_fetch_pcm16_begin(int slot) {
         STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap * sizeof(int16_t), hipHostMallocDefault));
         f.cap = cap;
     }
-    if (resample_on()) {
+    if (loudness_on()) {
+        int64_t Wo = 0;
+        const float* g = nullptr;
+        const float* src = lo_batch(Wo, &g, true);
+        lo_gain_enqueue(src, b.B, Wo, g, nullptr, f.dev, Wo);
+    } else if (resample_on()) {
         const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
         resample_enqueue(rs_table(), b.wav, b.B, W, nullptr, f.dev, (int64_t)(nw / (size_t)b.B));
     } else {
@@ -502,6 +533,14 @@ void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) {
     Batch& b = bt_;
     const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (loudness_on()) {
+        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
+        int64_t Wo = 0;
+        const float* g = nullptr;
+        const float* src = lo_batch(Wo, &g, true);
+        lo_gain_enqueue(src, b.B, Wo, g, dst, nullptr, dst_stride);
+        return;
+    }
     if (resample_on()) {
         STN_HIP(hipSetDevice(device_));
         if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
@@ -516,6 +555,14 @@ void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) {
     Batch& b = bt_;
     const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    if (loudness_on()) {
+        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
+        int64_t Wo = 0;
+        const float* g = nullptr;
+        const float* src = lo_batch(Wo, &g, true);
+        lo_gain_enqueue(src, b.B, Wo, g, nullptr, dst, dst_stride);
+        return;
+    }
     if (resample_on()) {
         if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
         resample_enqueue(rs_table(), b.wav, b.B, (int64_t)W, nullptr, dst, dst_stride);

@@ -1,0 +1,245 @@
+// engine_loudness.cpp — loudness normalization of a handle's fetches: the K-weighting design (host only), the scan's power table, the
+// fetch-time scratch, and the launches every fetch path makes when normalization is on (engine_batch.cpp).  The kernels are
+// kernels_loudness.hip; DESIGN.md section 11 has the contract.
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace stn {
+
+// BS.1770-4 K-weighting at any rate: the analog prototypes of the standard's 48 kHz table (libebur128's derivation), bilinear-transformed
+// at hz.  At 48 kHz this is the published table to 1e-15.
+std::string kweighting_design(int hz, KWeighting& k) {
+    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
+        return "loudness: sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")";
+    const double fs = hz;
+    {  // high shelf, +4 dB above ~1.7 kHz (the head's acoustic effect)
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(M_PI * f0 / fs), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        k.shelf_b[0] = (Vh + Vb * K / Q + K * K) / a0;
+        k.shelf_b[1] = 2.0 * (K * K - Vh) / a0;
+        k.shelf_b[2] = (Vh - Vb * K / Q + K * K) / a0;
+        k.shelf_a[0] = 1.0;
+        k.shelf_a[1] = 2.0 * (K * K - 1.0) / a0;
+        k.shelf_a[2] = (1.0 - K / Q + K * K) / a0;
+    }
+    {  // RLB high-pass at ~38 Hz
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(M_PI * f0 / fs), a0 = 1.0 + K / Q + K * K;
+        k.hp_b[0] = 1.0; k.hp_b[1] = -2.0; k.hp_b[2] = 1.0;
+        k.hp_a[0] = 1.0;
+        k.hp_a[1] = 2.0 * (K * K - 1.0) / a0;
+        k.hp_a[2] = (1.0 - K / Q + K * K) / a0;
+    }
+    return "";
+}
+
+// The kernels' fp32 coefficients, and M = A^LO_CHUNK of the state transition A those coefficients define (state s1 s2 t1 t2 of the
+// two transposed direct form II sections, zero input), with its powers M^1 .. M^LO_SCAN, in double, stored as fp32.
+std::string loudness_design(int hz, LoudTable& t) {
+    KWeighting k;
+    const std::string why = kweighting_design(hz, k);
+    if (!why.empty()) return why;
+    t.hz = hz;
+    t.hop = (hz + 5) / 10;
+    const double src[10] = {k.shelf_b[0], k.shelf_b[1], k.shelf_b[2], k.shelf_a[1], k.shelf_a[2], k.hp_b[0], k.hp_b[1], k.hp_b[2], k.hp_a[1], k.hp_a[2]};
+    double c[10];
+    for (int i = 0; i < 10; ++i) { t.coef.c[i] = (float)src[i]; c[i] = t.coef.c[i]; }
+    // v = s1; s1' = -a1 v + s2; s2' = -a2 v; y = c0 v + t1; t1' = c1 v - d1 y + t2; t2' = c2 v - d2 y
+    const double A[16] = {-c[3], 1, 0, 0,
+                          -c[4], 0, 0, 0,
+                          c[6] - c[8] * c[5], 0, -c[8], 1,
+                          c[7] - c[9] * c[5], 0, -c[9], 0};
+    auto mul = [](const double* X, const double* Y, double* Z) {
+        for (int r = 0; r < 4; ++r)
+            for (int q = 0; q < 4; ++q) {
+                double s = 0.0;
+                for (int j = 0; j < 4; ++j) s += X[r * 4 + j] * Y[j * 4 + q];
+                Z[r * 4 + q] = s;
+            }
+    };
+    double M[16], T[16];
+    std::memcpy(M, A, sizeof(M));
+    for (int i = 1; i < LO_CHUNK; ++i) { mul(M, A, T); std::memcpy(M, T, sizeof(M)); }
+    t.mpow.assign((size_t)LO_SCAN * 16, 0.f);
+    double P[16];
+    std::memcpy(P, M, sizeof(P));
+    for (int i = 0; i < LO_SCAN; ++i) {
+        for (int j = 0; j < 16; ++j) t.mpow[(size_t)i * 16 + j] = (float)P[j];
+        mul(P, M, T);
+        std::memcpy(P, T, sizeof(P));
+    }
+    return "";
+}
+
+void Engine::lo_prepare(LoudTable& t, int hz) {
+    if (t.dev && t.hz == hz) return;
+    LoudTable n;
+    const std::string why = loudness_design(hz, n);
+    if (!why.empty()) throw std::invalid_argument(why);
+    STN_HIP(hipSetDevice(device_));
+    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.mpow.size() * sizeof(float)));
+    STN_HIP(hipMemcpyAsync(n.dev, n.mpow.data(), n.mpow.size() * sizeof(float), hipMemcpyHostToDevice, s_));
+    if (t.dev) { sync(); (void)hipFree(t.dev); }  // a fetch may still be reading the old table
+    t = std::move(n);
+}
+
+void Engine::lo_release() {
+    for (LoudTable* t : {&lo_, &op_lo_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
+    if (lo_buf_) (void)hipFree(lo_buf_);
+    lo_buf_ = nullptr; lo_buf_cap_ = 0;
+    lo_n_.clear();
+    lo_n_ptr_ = nullptr;
+}
+
+void Engine::set_loudness(bool on, float target, float ceiling) {
+    if (!(target >= -60.0f && target <= 0.0f))
+        throw std::invalid_argument("loudness target " + std::to_string(target) + " LUFS: must be in [-60, 0]");
+    if (!(ceiling >= -30.0f && ceiling <= 0.0f))
+        throw std::invalid_argument("loudness peak ceiling " + std::to_string(ceiling) + " dBFS: must be in [-30, 0]");
+    lo_on_ = on;
+    lo_target_ = target;
+    lo_ceiling_ = ceiling;
+}
+
+void Engine::get_loudness(int* on, float* target, float* ceiling) const {
+    if (on) *on = lo_on_ ? 1 : 0;
+    if (target) *target = lo_target_;
+    if (ceiling) *ceiling = lo_ceiling_;
+}
+
+// grow-only scratch (not part of the resident batch: growing it re-keys no captured graph): per chunk the state (16 B), the peak and
+// the two energy shares; per row the three results and the length
+Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
+    const size_t o_st = 0, o_pk = o_st + up(nc * 16), o_pa = o_pk + up(nc * 4), o_pb = o_pa + up(nc * 4), o_res = o_pb + up(nc * 4),
+                 o_n = o_res + up((size_t)rows * 12), need = o_n + up((size_t)rows * 8);
+    if (!lo_buf_ || need > lo_buf_cap_) {
+        sync();  // the previous fetch may still be reading it
+        if (lo_buf_) (void)hipFree(lo_buf_);
+        lo_buf_ = nullptr; lo_buf_cap_ = 0;
+        lo_n_.clear();
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&lo_buf_), need + need / 4));
+        lo_buf_cap_ = need + need / 4;
+    }
+    // (the row lengths sit behind the per-chunk arrays: another rows x W moves them, so lo_n_ptr_ remembers where they went)
+    LoScratch sc;
+    sc.st = reinterpret_cast<float*>(lo_buf_ + o_st);
+    sc.pk = reinterpret_cast<float*>(lo_buf_ + o_pk);
+    sc.pa = reinterpret_cast<float*>(lo_buf_ + o_pa);
+    sc.pb = reinterpret_cast<float*>(lo_buf_ + o_pb);
+    sc.res = reinterpret_cast<float*>(lo_buf_ + o_res);
+    sc.n = reinterpret_cast<int64_t*>(lo_buf_ + o_n);
+    return sc;
+}
+
+void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on) {
+    const char* saved = stage_;
+    stage_ = "out";
+    const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
+    auto span = [&](double flops, double bytes) { if (prof_on_) prof_begin("loudness", flops, bytes); };
+    auto done = [&]() { if (prof_on_) prof_end(); STN_HIP(hipGetLastError()); };
+    span(20.0 * samples, samples * 4 + chunks * 20);
+    launch_loudness_chunks(s_, false, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    done();
+    span(chunks * 32.0 * 11, chunks * 32);
+    launch_loudness_scan(s_, rows, W, sc.n, t, sc.st);
+    done();
+    span(22.0 * samples, samples * 4 + chunks * 24);
+    launch_loudness_chunks(s_, true, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    done();
+    span(chunks * 2, chunks * 12 + (double)rows * 12);
+    launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, lo_target_, lo_ceiling_, sc.res);
+    done();
+    stage_ = saved;
+}
+
+void Engine::lo_gain_enqueue(const float* x, int64_t rows, int64_t W, const float* g, float* y, int16_t* pcm, int64_t dst_stride) {
+    const char* saved = stage_;
+    stage_ = "out";
+    if (prof_on_) prof_begin("loudness_gain", (double)rows * W, (double)rows * W * (pcm ? 6 : 8));
+    if (pcm) launch_loudness_gain_pcm16(s_, x, rows, W, g, pcm, dst_stride);
+    else launch_loudness_gain(s_, x, rows, W, g, y, dst_stride);
+    if (prof_on_) prof_end();
+    stage_ = saved;
+    STN_HIP(hipGetLastError());
+}
+
+const float* Engine::lo_batch(int64_t& Wo, const float** gain, bool on, float** res) {
+    Batch& b = bt_;
+    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    STN_HIP(hipSetDevice(device_));
+    const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    Wo = out_len(W);
+    const float* src = b.wav;
+    if (resample_on()) {  // the signal delivered: the waveform at the output rate
+        float* d = rs_f32_buf((size_t)b.B * Wo);
+        resample_enqueue(rs_table(), b.wav, b.B, W, d, nullptr, Wo);
+        src = d;
+    }
+    const int hz = output_rate();
+    lo_prepare(lo_, hz);
+    // row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file
+    std::vector<int64_t> n((size_t)b.B);
+    int64_t max_seg = 0;
+    for (int i = 0; i < b.B; ++i) {
+        n[(size_t)i] = std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz));
+        if (n[(size_t)i] < 0) n[(size_t)i] = 0;
+        max_seg = std::max<int64_t>(max_seg, n[(size_t)i] / lo_.hop);
+    }
+    const LoScratch sc = lo_scratch(b.B, Wo);
+    // uploaded once per finished batch (and again only when the scratch moved): later fetches of the same batch reuse it
+    if (n != lo_n_ || lo_n_ptr_ != sc.n) {
+        lo_n_ = std::move(n);
+        lo_n_ptr_ = sc.n;
+        STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    }
+    lo_measure(lo_, src, b.B, Wo, sc, max_seg, on);
+    *gain = sc.res + 2 * (int64_t)b.B;
+    if (res) *res = sc.res;
+    return src;
+}
+
+void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
+    Batch& b = bt_;
+    int64_t Wo = 0;
+    const float* g = nullptr;
+    float* res = nullptr;
+    lo_batch(Wo, &g, lo_on_, &res);
+    const size_t B = (size_t)b.B;
+    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, B * 4, hipMemcpyDeviceToHost, s_));
+    if (peak) STN_HIP(hipMemcpyAsync(peak, res + B, B * 4, hipMemcpyDeviceToHost, s_));
+    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * B, B * 4, hipMemcpyDeviceToHost, s_));
+    sync();
+}
+
+void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
+    STN_HIP(hipSetDevice(device_));
+    lo_prepare(op_lo_, hz);
+    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
+    int64_t max_seg = 0;
+    for (int r = 0; r < rows; ++r) {
+        if (n) {
+            if (n[r] < 0 || n[r] > W) throw std::invalid_argument("op_loudness: n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
+            nn[(size_t)r] = n[r];
+        }
+        max_seg = std::max<int64_t>(max_seg, nn[(size_t)r] / op_lo_.hop);
+    }
+    ar_.reset();
+    const size_t nx = (size_t)rows * W;
+    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
+    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    const LoScratch sc = lo_scratch(rows, W);
+    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    lo_n_.clear();  // (the batch's lengths are no longer there)
+    lo_measure(op_lo_, dx, rows, W, sc, max_seg, false);
+    if (lufs) STN_HIP(hipMemcpyAsync(lufs, sc.res, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    if (peak) STN_HIP(hipMemcpyAsync(peak, sc.res + rows, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    sync();
+}
+
+}  // namespace stn

@@ -216,6 +216,12 @@ int stn_group_load_synthetic(stn_group* g, const stn_arch* arch, uint64_t seed) 
 int stn_group_set_output_rate(stn_group* g, int hz) {
     return for_all(g, "stn_set_output_rate", [](stn_handle* h, const void*, uint64_t v) { return stn_set_output_rate(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)hz);
 }
+int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceiling_dbfs) {
+    struct S { int on; float t, c; } v{on, target_lufs, ceiling_dbfs};
+    return for_all(g, "stn_set_loudness", [](stn_handle* h, const void* a, uint64_t) {
+        const S* p = static_cast<const S*>(a);
+        return stn_set_loudness(h, p->on, p->t, p->c); }, &v, 0);
+}
 int stn_group_load_dir(stn_group* g, const char* onnx_dir) {
     return for_all(g, "stn_load_dir", [](stn_handle* h, const void* a, uint64_t) { return stn_load_dir(h, static_cast<const char*>(a)); }, onnx_dir, 0);
 }

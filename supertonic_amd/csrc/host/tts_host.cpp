@@ -177,6 +177,14 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
             if (grp) { if (stn_group_set_output_rate(grp, opts.output_rate) != STN_OK) throw std::runtime_error(std::string("output rate: ") + stn_group_last_error(grp)); }
             else check(h, stn_set_output_rate(h, opts.output_rate));
         }
+        if (!std::isnan(opts.loudness_lufs)) {
+            if (grp) {
+                if (stn_group_set_loudness(grp, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs) != STN_OK)
+                    throw std::runtime_error(std::string("loudness: ") + stn_group_last_error(grp));
+            } else {
+                check(h, stn_set_loudness(h, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs));
+            }
+        }
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);

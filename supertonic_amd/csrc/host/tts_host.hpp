@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -57,6 +58,10 @@ struct EngineOptions {
     std::vector<int> devices;      // explicit ordinals instead (size = gpus); the same ordinal repeated = a rehearsal on one GPU
     int output_rate = 0;           // Hz of the returned audio and the WAV files (resampled on the GPU, stn_set_output_rate); 0: the model's.
                                    // CLI --sample-rate HZ
+    float loudness_lufs = std::numeric_limits<float>::quiet_NaN();  // normalize every utterance to this BS.1770-4 integrated loudness
+                                   // (measured and scaled on the GPU, stn_set_loudness; the WAV files carry the normalized PCM); NaN: off.
+                                   // CLI --loudness LUFS
+    float loudness_ceiling_dbfs = -1.0f;  // sample-peak ceiling that caps the normalization gain.  CLI --peak-ceiling DBFS
 };
 
 class TextToSpeech {

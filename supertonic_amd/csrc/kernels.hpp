@@ -374,4 +374,43 @@ std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, float* y, int64_t dst_stride);
 void launch_resample_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int16_t* pcm, int64_t dst_stride);
 
+// Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the enqueue are engine_loudness.cpp).
+// BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in
+// fp32) as one 4-state linear system x' = A x + B u.  Chunks of LO_CHUNK samples from sample 0: each is filtered from zero state
+// (end state e_k, max |x|), a per-row scan gives the true start states s_{k+1} = M s_k + e_k with M = A^LO_CHUNK, each chunk is
+// refiltered from s_k into per-chunk sums of y^2 split at the 100 ms segment boundary, and one workgroup per row gates the 400 ms blocks
+// and writes (L_b, peak_b, g_b).  Every hand-off is a launch boundary; every sum runs in a fixed order.
+constexpr int LO_CHUNK = 32;          // samples per lane
+constexpr int LO_WG = 256;            // lanes (chunks) per workgroup of the two chunk passes
+constexpr int LO_SCAN = 1024;         // chunks per scan tile; the power table holds M^1 .. M^LO_SCAN
+constexpr int LO_MAX_SEG = 16384;     // 100 ms segments per row the gate holds in LDS
+constexpr int LO_MIN_HZ = 8000, LO_MAX_HZ = 192000;
+struct KWeighting { double shelf_b[3], shelf_a[3], hp_b[3], hp_a[3]; };  // a[0] = 1
+// the BS.1770-4 K-weighting filter at hz (host only, libebur128's analog-prototype derivation); empty string, or why hz is refused
+std::string kweighting_design(int hz, KWeighting& k);
+struct LoudCoef { float c[10]; };     // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 (fp32, what the kernels multiply by)
+struct LoudTable {
+    int hz = 0, hop = 0;              // hop = (hz + 5) / 10 samples (100 ms)
+    LoudCoef coef{};
+    std::vector<float> mpow;          // host copy, [LO_SCAN][16]: M^(i+1) row-major, M = A^LO_CHUNK of the fp32 coefficients
+    float* dev = nullptr;             // device copy (owned by whoever uploaded it)
+};
+// fills t (not t.dev); empty string, or why hz is refused
+std::string loudness_design(int hz, LoudTable& t);
+__host__ __device__ inline int64_t lo_chunks(int64_t W) { return (W + LO_CHUNK - 1) / LO_CHUNK; }
+// Pass 1 (energy = false): rows x W fp32 (row stride W) with row lengths n[rows] (<= W) -> st[row][k] = end state of chunk k from zero
+// state, pk[row][k] = max |x| over chunk k.  Pass 2 (energy = true): st[row][k] = start state of chunk k -> pa/pb[row][k] = sum of y^2
+// over the chunk's samples in its first 100 ms segment / in the next one, counting only whole segments.  Ks = lo_chunks(W).
+void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
+                            float* st, float* pk, float* pa, float* pb);
+// in place: st[row][k] (end states) -> the start states of the chunks
+void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, float* st);
+// res[0][b] = L_b (-inf when undefined), res[1][b] = peak_b, res[2][b] = g_b (1 when off or L_b undefined); max_seg = max_b n_b / hop
+void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pk, const float* pa,
+                          const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res);
+// y[row * dst_stride + i] = x[row * W + i] * g[row] for i < W (y may be x when dst_stride == W), or the same product converted to int16
+// PCM exactly as launch_f32_to_pcm16 converts
+void launch_loudness_gain(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride);
+void launch_loudness_gain_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* pcm, int64_t dst_stride);
+
 }  // namespace stn

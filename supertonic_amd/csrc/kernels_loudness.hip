@@ -1,0 +1,351 @@
+// kernels_loudness.hip — BS.1770-4 integrated loudness of the finished waveform and the gain that normalizes it (gfx950, wave64).
+// Runs at fetch time, outside the captured pipeline, on rows x W fp32 samples of which row b's first n_b count.
+//
+// The K-weighting cascade (shelf biquad, then high-pass biquad, each in transposed direct form II) is one 4-state linear system
+// x' = A x + B u, state (s1, s2, t1, t2).  Decomposition:
+//   1. chunk pass: a lane owns LO_CHUNK consecutive samples of a row, counted from sample 0; a workgroup stages its LO_WG chunks in LDS
+//      with 16-byte loads (row stride 33 words: the lanes' walks fall on distinct banks), and each lane filters its chunk from zero
+//      state, writing the end state e_k and the chunk's max |x|;
+//   2. scan: one workgroup per row forms the true start states s_{k+1} = M s_k + e_k (M = A^LO_CHUNK, its powers from the host) by a
+//      Hillis-Steele scan over tiles of LO_SCAN chunks, in place;
+//   3. energy pass: each lane refilters its chunk from s_k and sums y^2 into the chunk's share of the 100 ms segment it starts in and
+//      of the next one (chunks and segments need not align);
+//   4. gate: one workgroup per row sums each segment's shares in a fixed order, forms the 400 ms block energies, applies the absolute
+//      and relative gates and writes (L_b, peak_b, g_b);
+//   5. gain: y = x * g_b per sample, as fp32 or as writeWavFile's 16-bit PCM.
+// Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
+// row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
+#include "kernels.hpp"
+
+#include <math.h>
+
+namespace stn {
+
+namespace {
+
+constexpr int LO_SPAN = LO_WG * LO_CHUNK;  // samples a workgroup of the chunk passes owns
+constexpr int LO_PAD = LO_CHUNK + 1;       // LDS words per chunk
+constexpr int LO_GATE = 1024;              // threads of the gate workgroup
+
+// one sample through the cascade: shelf (b0 b1 b2 a1 a2 = c[0..4]) then high-pass (c[5..9]), transposed direct form II
+__device__ __forceinline__ float lo_step(const LoudCoef& f, float u, float& s1, float& s2, float& t1, float& t2) {
+    const float v = __builtin_fmaf(f.c[0], u, s1);
+    s1 = __builtin_fmaf(-f.c[3], v, __builtin_fmaf(f.c[1], u, s2));
+    s2 = __builtin_fmaf(-f.c[4], v, f.c[2] * u);
+    const float y = __builtin_fmaf(f.c[5], v, t1);
+    t1 = __builtin_fmaf(-f.c[8], y, __builtin_fmaf(f.c[6], v, t2));
+    t2 = __builtin_fmaf(-f.c[9], y, f.c[7] * v);
+    return y;
+}
+
+template <bool kEnergy>
+__global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __restrict__ x, int64_t W, int vec, const int64_t* __restrict__ nrow,
+                                                               int64_t Ks, LoudCoef f, int hop, float* __restrict__ st, float* __restrict__ pk,
+                                                               float* __restrict__ pa, float* __restrict__ pb) {
+    __shared__ float win[LO_WG * LO_PAD];
+    const int64_t row = blockIdx.y;
+    const int64_t n = nrow[row];
+    const int64_t s0 = (int64_t)blockIdx.x * LO_SPAN;
+    if (s0 >= n) return;  // (the whole workgroup: nothing of the span lies in the row)
+    const int cnt = (int)(n - s0 < LO_SPAN ? n - s0 : LO_SPAN);
+    const float* __restrict__ xr = x + row * W + s0;
+    if (vec) {  // rows 16-byte aligned and W % 4 == 0: a float4 that starts below n ends at or below W
+        constexpr int U = LO_SPAN / 4 / LO_WG;
+        float4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = threadIdx.x + u * LO_WG;
+            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = 4 * (threadIdx.x + u * LO_WG);
+            if (i < cnt) {
+                float* d = win + (i / LO_CHUNK) * LO_PAD + (i % LO_CHUNK);  // (the four samples share a chunk)
+                d[0] = v[u].x;
+                if (i + 1 < cnt) d[1] = v[u].y;
+                if (i + 2 < cnt) d[2] = v[u].z;
+                if (i + 3 < cnt) d[3] = v[u].w;
+            }
+        }
+    } else {
+        for (int i0 = 0; i0 < LO_SPAN; i0 += 8 * LO_WG) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + threadIdx.x + u * LO_WG;
+                v[u] = i < cnt ? xr[i] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + threadIdx.x + u * LO_WG;
+                if (i < cnt) win[(i / LO_CHUNK) * LO_PAD + (i % LO_CHUNK)] = v[u];
+            }
+        }
+    }
+    __syncthreads();
+    const int c0 = threadIdx.x * LO_CHUNK;
+    if (c0 >= cnt) return;
+    const int len = cnt - c0 < LO_CHUNK ? cnt - c0 : LO_CHUNK;
+    const int64_t k = (int64_t)blockIdx.x * LO_WG + threadIdx.x;
+    const float* w = win + threadIdx.x * LO_PAD;
+    float4* sk = reinterpret_cast<float4*>(st) + row * Ks + k;
+    if (!kEnergy) {
+        float s1 = 0.f, s2 = 0.f, t1 = 0.f, t2 = 0.f, m = 0.f;
+#pragma unroll
+        for (int i = 0; i < LO_CHUNK; ++i) {
+            if (i < len) {
+                const float u = w[i];
+                m = fmaxf(m, fabsf(u));
+                (void)lo_step(f, u, s1, s2, t1, t2);
+            }
+        }
+        *sk = make_float4(s1, s2, t1, t2);
+        pk[row * Ks + k] = m;
+    } else {
+        const float4 s = *sk;
+        float s1 = s.x, s2 = s.y, t1 = s.z, t2 = s.w, a = 0.f, b = 0.f;
+        const int64_t g0 = s0 + c0;
+        const int64_t bound = (g0 / hop + 1) * hop;  // first sample of the next segment
+        const int64_t full = n / hop * hop;           // samples of whole segments
+#pragma unroll
+        for (int i = 0; i < LO_CHUNK; ++i) {
+            if (i < len) {
+                const float y = lo_step(f, w[i], s1, s2, t1, t2);
+                const float yy = y * y;
+                const int64_t g = g0 + i;
+                a += (g < bound && g < full) ? yy : 0.0f;
+                b += (g >= bound && g < full) ? yy : 0.0f;
+            }
+        }
+        pa[row * Ks + k] = a;
+        pb[row * Ks + k] = b;
+    }
+}
+
+// r = v + P o (P row-major 4 x 4), each row summed in the same order
+__device__ __forceinline__ float4 lo_affine(const float* __restrict__ P, float4 o, float4 v) {
+    float4 r;
+    r.x = v.x + (((P[0] * o.x + P[1] * o.y) + P[2] * o.z) + P[3] * o.w);
+    r.y = v.y + (((P[4] * o.x + P[5] * o.y) + P[6] * o.z) + P[7] * o.w);
+    r.z = v.z + (((P[8] * o.x + P[9] * o.y) + P[10] * o.z) + P[11] * o.w);
+    r.w = v.w + (((P[12] * o.x + P[13] * o.y) + P[14] * o.z) + P[15] * o.w);
+    return r;
+}
+
+// st[row][k]: end states from zero state in, start states out.  Tile t covers chunks t*LO_SCAN ..; after the inclusive scan, lane i
+// holds v_i = sum_{j <= i} M^(i-j) e_j, so the start state of chunk t*LO_SCAN + i is v_{i-1} + M^i c with c the tile's carry-in.
+__global__ void __launch_bounds__(LO_SCAN) loudness_scan_kernel(const int64_t* __restrict__ nrow, int64_t Ks, const float* __restrict__ mp,
+                                                                float* st) {
+    __shared__ float4 buf[LO_SCAN];
+    const int64_t row = blockIdx.x;
+    const int64_t K = lo_chunks(nrow[row]);
+    const int i = threadIdx.x;
+    float4* sr = reinterpret_cast<float4*>(st) + row * Ks;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 zero = c;
+    for (int64_t t0 = 0; t0 < K; t0 += LO_SCAN) {
+        const int64_t k = t0 + i;
+        float4 v = k < K ? sr[k] : zero;
+        for (int d = 1; d < LO_SCAN; d <<= 1) {
+            buf[i] = v;
+            __syncthreads();
+            if (i >= d) v = lo_affine(mp + (d - 1) * 16, buf[i - d], v);
+            __syncthreads();
+        }
+        buf[i] = v;
+        __syncthreads();
+        const float4 s = i == 0 ? c : lo_affine(mp + (i - 1) * 16, c, buf[i - 1]);
+        if (k < K) sr[k] = s;
+        c = lo_affine(mp + (LO_SCAN - 1) * 16, c, buf[LO_SCAN - 1]);
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ double lo_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// fixed-order sum over the workgroup: lane-strided partials, a butterfly per wave (lane 0's order), the waves in order
+__device__ double lo_block_sum(double v, double* red) {
+    v = lo_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int w = 0; w < LO_GATE / 64; ++w) s += red[w];
+    __syncthreads();
+    return s;
+}
+
+__global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* __restrict__ nrow, int64_t Ks, int hop, const float* __restrict__ pk,
+                                                                const float* __restrict__ pa, const float* __restrict__ pb, int on, float target,
+                                                                float ceiling, int64_t rows, float* __restrict__ res) {
+    extern __shared__ double seg[];
+    __shared__ double red[LO_GATE / 64];
+    __shared__ float redm[LO_GATE / 64];
+    const int64_t row = blockIdx.x;
+    const int64_t n = nrow[row];
+    const int64_t K = lo_chunks(n), nseg = n / hop;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* __restrict__ pkr = pk + row * Ks;
+    const float* __restrict__ par = pa + row * Ks;
+    const float* __restrict__ pbr = pb + row * Ks;
+    // sample peak: max is order-independent, so exact
+    float m = 0.f;
+    for (int64_t k = tid; k < K; k += LO_GATE) m = fmaxf(m, pkr[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) redm[wave] = m;
+    __syncthreads();
+    float peak = 0.f;
+    for (int w = 0; w < LO_GATE / 64; ++w) peak = fmaxf(peak, redm[w]);
+    // 100 ms segment sums: a wave per segment, its lanes strided over the chunks that touch it from the segment's first chunk on
+    for (int64_t j = wave; j < nseg; j += LO_GATE / 64) {
+        const int64_t k0 = j * hop / LO_CHUNK, k1 = ((j + 1) * hop - 1) / LO_CHUNK;
+        double a = 0.0;
+        for (int64_t k = k0 + lane; k <= k1; k += 64) a += (k * LO_CHUNK / hop == j) ? (double)par[k] : (double)pbr[k];
+        a = lo_wave_sum(a);
+        if (lane == 0) seg[j] = a;
+    }
+    __syncthreads();
+    // 400 ms blocks at a 100 ms hop, both gates
+    const int64_t nblk = nseg >= 4 ? nseg - 3 : 0;
+    const double inv = 1.0 / (4.0 * hop);
+    double zs = 0.0, zc = 0.0;
+    for (int64_t j = tid; j < nblk; j += LO_GATE) {
+        const double z = ((seg[j] + seg[j + 1]) + (seg[j + 2] + seg[j + 3])) * inv;
+        if (-0.691 + 10.0 * log10(z) > -70.0) { zs += z; zc += 1.0; }
+    }
+    zs = lo_block_sum(zs, red);
+    zc = lo_block_sum(zc, red);
+    double L = -INFINITY;
+    if (zc > 0.0) {
+        const double rel = -0.691 + 10.0 * log10(zs / zc) - 10.0;
+        double rs = 0.0, rc = 0.0;
+        for (int64_t j = tid; j < nblk; j += LO_GATE) {
+            const double z = ((seg[j] + seg[j + 1]) + (seg[j + 2] + seg[j + 3])) * inv;
+            const double l = -0.691 + 10.0 * log10(z);
+            if (l > -70.0 && l > rel) { rs += z; rc += 1.0; }
+        }
+        rs = lo_block_sum(rs, red);
+        rc = lo_block_sum(rc, red);
+        if (rc > 0.0) L = -0.691 + 10.0 * log10(rs / rc);
+    }
+    if (tid == 0) {
+        const float Lf = (float)L;
+        float g = 1.0f;
+        if (on && Lf > -INFINITY && peak > 0.f) {  // L_b undefined: gain 1
+            const double gl = pow(10.0, ((double)target - (double)Lf) / 20.0);
+            const double gc = pow(10.0, (double)ceiling / 20.0) / (double)peak;
+            g = (float)(gl < gc ? gl : gc);
+        }
+        res[row] = Lf;
+        res[rows + row] = peak;
+        res[2 * rows + row] = g;
+    }
+}
+
+__global__ void loudness_gain_kernel(const float* x, int64_t W, int64_t n, const float* __restrict__ g, float* y, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W]
+    if (i >= n) return;
+    const int64_t row = i / W;
+    y[row * dst_stride + (i - row * W)] = x[i] * g[row];
+}
+__global__ void loudness_gain4_kernel(const float* x, int64_t W4, int64_t n4, const float* __restrict__ g, float* y, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/4]
+    if (i >= n4) return;
+    const int64_t row = i / W4;
+    const float s = g[row];
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    *reinterpret_cast<float4*>(y + row * dst_stride + (i - row * W4) * 4) = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+__device__ __forceinline__ int lo_pcm(float v) { return (int)(fminf(1.0f, fmaxf(-1.0f, v)) * 32767.0f); }  // as pcm16_kernel
+__global__ void loudness_gain_pcm16_kernel(const float* __restrict__ x, int64_t W, int64_t n, const float* __restrict__ g, int16_t* __restrict__ pcm,
+                                           int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t row = i / W;
+    pcm[row * dst_stride + (i - row * W)] = (int16_t)lo_pcm(x[i] * g[row]);
+}
+__global__ void loudness_gain8_pcm16_kernel(const float* __restrict__ x, int64_t W8, int64_t n8, const float* __restrict__ g,
+                                            int16_t* __restrict__ pcm, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/8]
+    if (i >= n8) return;
+    const int64_t row = i / W8;
+    const float s = g[row];
+    const float4* src = reinterpret_cast<const float4*>(x) + i * 2;
+    const float4 a = src[0], b = src[1];
+    const float v[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
+    unsigned o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ((unsigned)lo_pcm(v[2 * j]) & 0xFFFFu) | ((unsigned)lo_pcm(v[2 * j + 1]) << 16);
+    *reinterpret_cast<uint4*>(pcm + row * dst_stride + (i - row * W8) * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
+
+void lo_check(int64_t rows, int64_t W, const LoudTable& t) {
+    if (rows > 65535) throw std::invalid_argument("loudness: more than 65535 rows");
+    if (!t.dev || t.hop < 1) throw std::runtime_error("loudness: filter table not prepared");
+    if (lo_chunks(W) > ((int64_t)1 << 31) / LO_WG) throw std::invalid_argument("loudness: row too long");
+}
+
+}  // namespace
+
+void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
+                            float* st, float* pk, float* pa, float* pb) {
+    if (rows <= 0 || W <= 0) return;
+    lo_check(rows, W, t);
+    const int vec = (W % 4 == 0 && aligned16(x)) ? 1 : 0;
+    const dim3 grid((unsigned)((W + LO_SPAN - 1) / LO_SPAN), (unsigned)rows);
+    if (energy) STN_KLAUNCH(loudness_chunk_kernel<true>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
+    else STN_KLAUNCH(loudness_chunk_kernel<false>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
+}
+
+void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, float* st) {
+    if (rows <= 0 || W <= 0) return;
+    lo_check(rows, W, t);
+    STN_KLAUNCH(loudness_scan_kernel, dim3((unsigned)rows), dim3(LO_SCAN), 0, s, n, lo_chunks(W), t.dev, st);
+}
+
+void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pk, const float* pa,
+                          const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res) {
+    if (rows <= 0 || W <= 0) return;
+    lo_check(rows, W, t);
+    if (max_seg > LO_MAX_SEG) throw std::invalid_argument("loudness: a row longer than " + std::to_string(LO_MAX_SEG) + " 100 ms segments");
+    const unsigned lds = (unsigned)((max_seg > 0 ? max_seg : 1) * sizeof(double));
+    static PerDeviceOnce attr_once;
+    if (attr_once.need())
+        stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&loudness_gate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(LO_MAX_SEG * sizeof(double))), "hipFuncSetAttribute(loudness_gate)");
+    STN_KLAUNCH(loudness_gate_kernel, dim3((unsigned)rows), dim3(LO_GATE), lds, s, n, lo_chunks(W), t.hop, pk, pa, pb, on ? 1 : 0, target_lufs,
+                ceiling_dbfs, rows, res);
+}
+
+void launch_loudness_gain(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride) {
+    const int64_t n = rows * W;
+    if (n <= 0) return;
+    if (dst_stride < W) throw std::invalid_argument("loudness gain: dst_stride smaller than the row length");
+    if (W % 4 == 0 && dst_stride % 4 == 0 && aligned16(x) && aligned16(y)) {
+        const int64_t n4 = n / 4;
+        STN_KLAUNCH(loudness_gain4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, W / 4, n4, g, y, dst_stride);
+    } else {
+        STN_KLAUNCH(loudness_gain_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, W, n, g, y, dst_stride);
+    }
+}
+
+void launch_loudness_gain_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* pcm, int64_t dst_stride) {
+    const int64_t n = rows * W;
+    if (n <= 0) return;
+    if (dst_stride < W) throw std::invalid_argument("loudness gain: dst_stride smaller than the row length");
+    if (W % 8 == 0 && dst_stride % 8 == 0 && aligned16(x) && aligned16(pcm)) {
+        const int64_t n8 = n / 8;
+        STN_KLAUNCH(loudness_gain8_pcm16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, x, W / 8, n8, g, pcm, dst_stride);
+    } else {
+        STN_KLAUNCH(loudness_gain_pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, W, n, g, pcm, dst_stride);
+    }
+}
+
+}  // namespace stn

@@ -34,7 +34,8 @@ class _Job:
 
 class DynamicBatcher:
     """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed, output rate) into one engine batch (the engine's output rate covers a whole batch).  A worker thread owns
+    (total_step, speed, output rate, loudness target and peak ceiling) into one engine batch (the engine's output rate and loudness
+    setting cover a whole batch; every row is still normalized with its own gain).  A worker thread owns
     the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
     its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
 
@@ -46,10 +47,12 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, total_step, speed, sample_rate=None):
+    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
-        waves (None: the model's)."""
-        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate)))
+        waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
+        the synthesizer's own setting)."""
+        lo = None if loudness is None else (float(loudness), float(peak_ceiling))
+        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo))
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -102,8 +105,10 @@ class DynamicBatcher:
                 langs = [j.lang for j in jobs for _ in j.texts]
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
-                step, speed, rate = jobs[0].key
+                step, speed, rate, lo = jobs[0].key
                 extra = {} if rate is None else {"output_rate": rate}
+                if lo is not None:
+                    extra["loudness"] = lo
                 waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
                 self.batches.append(len(texts))
                 o = 0
@@ -164,6 +169,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         batch: bool = False
         silence_duration: float = Field(0.3, ge=0.0, description="Silence between chunks for non-batch mode.")
         sample_rate: Optional[int] = Field(None, description="Output sample rate in Hz (resampled on the GPU); null: the model's rate.")
+        loudness: Optional[float] = Field(None, ge=-60.0, le=0.0, description="Normalize each utterance to this BS.1770-4 integrated "
+                                                                              "loudness in LUFS (on the GPU); null: off.")
+        peak_ceiling: float = Field(-1.0, ge=-30.0, le=0.0, description="Sample-peak ceiling in dBFS that caps the loudness gain.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -195,12 +203,14 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                 raise HTTPException(status_code=400, detail=f"sample_rate {req.sample_rate} is not supported ({why}); supported: "
                                                             + ", ".join(str(r) for r in binding.SUPPORTED_OUTPUT_RATES) + " Hz")
             sr, extra = req.sample_rate, {"output_rate": req.sample_rate}
+        if req.loudness is not None:
+            extra["loudness"] = (req.loudness, req.peak_ceiling)
         if req.batch:
             wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
             chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
-            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate)
+            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling)
             wav, d = join_chunks(waves, durs, req.silence_duration, sr)
             chunks = [wav[: int(sr * d)]]
         if len(chunks) == 1:

@@ -54,7 +54,7 @@ class TextToSpeech:
     returning (wav [B, W] float32, duration [B] float32).  One instance = one engine handle = one GPU; calls are
     serialised by a lock (the handle is single-threaded by contract)."""
 
-    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None):
+    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None):
         self.engine = engine
         self.text_processor = text_processor
         self.cfgs = cfgs
@@ -63,6 +63,11 @@ class TextToSpeech:
         self.output_rate = int(output_rate) if output_rate else self.sample_rate
         if self.output_rate != self.sample_rate:
             engine.set_output_rate(self.output_rate)
+        # loudness normalization of the returned audio (measured and scaled on the GPU at fetch time, Engine.set_loudness): None = off,
+        # a target in LUFS (peak ceiling -1 dBFS), or (target LUFS, ceiling dBFS)
+        self.loudness = _loudness_setting(loudness)
+        if self.loudness is not None:
+            engine.set_loudness(*self.loudness)
         self.base_chunk_size = cfgs["ae"]["base_chunk_size"]
         self.chunk_compress_factor = cfgs["ttl"]["chunk_compress_factor"]
         self.ldim = cfgs["ttl"]["latent_dim"]
@@ -76,7 +81,7 @@ class TextToSpeech:
         self._calls += 1
         return self.noise_seed + self._calls - 1
 
-    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None):
+    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None):
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         ids, mask = self.text_processor(text_list, lang_list)
@@ -88,6 +93,8 @@ class TextToSpeech:
             self.engine.set_shape_buckets(length_aware)
             if output_rate is not None:  # this call's rate (a fetch-time setting: no captured graph depends on it)
                 self.engine.set_output_rate(output_rate)
+            if loudness is not None:  # this call's normalization (fetch-time as well)
+                self.engine.set_loudness(*(_loudness_setting(loudness) or (None,)))
             try:
                 return self.engine.synthesize(ids, mask, style.ttl, style.dp, total_step, speed, noise_seed=self._seed())
             finally:
@@ -95,6 +102,8 @@ class TextToSpeech:
                 self.engine.set_shape_buckets(False)
                 if output_rate is not None:
                     self.engine.set_output_rate(self.output_rate)
+                if loudness is not None:
+                    self.engine.set_loudness(*(self.loudness or (None,)))
 
     def latent_lengths(self, durations):
         """Latent frames each utterance occupies (get_latent_mask, py/helper.py:276-282) from its returned duration."""
@@ -109,16 +118,22 @@ class TextToSpeech:
         P, Q = out // g, self.sample_rate // g
         return -(-int(n) * P // Q)
 
-    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None):
+    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
-        and the durations.  The building block of the long-form path and of the service's dynamic batching."""
-        wav, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate)
+        and the durations.  The building block of the long-form path and of the service's dynamic batching.
+        output_rate / loudness: this call's setting instead of the instance's (loudness: False = off for this call, a target in
+        LUFS, or (target, ceiling dBFS)); with normalization, each utterance is normalized on its own."""
+        wav, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
+                               loudness=loudness)
         cs = self.base_chunk_size * self.chunk_compress_factor
         lens = [int(self.latent_lengths(dur[i:i + 1])[0]) for i in range(len(text_list))]
         return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
     def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3):
+        """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence.  With
+        loudness normalization on, each chunk is normalized as its own row (its own gain); the joined text is not normalized as one
+        unit."""
         if style.ttl.shape[0] != 1:
             raise ValueError("Single speaker text to speech only supports single style")
         chunks = host.chunk_text(text, 120 if lang == "ko" else 300)
@@ -138,8 +153,19 @@ class TextToSpeech:
             parts.append(w)
         return np.concatenate(parts)[None, :], np.array([dur_cat], np.float32)
 
-    def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None):
-        return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate)
+    def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None):
+        return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness)
+
+
+def _loudness_setting(v):
+    """A loudness argument -> (target LUFS, ceiling dBFS), or None for off: None / False = off, a number = the target with a
+    -1 dBFS peak ceiling, a pair = (target, ceiling)."""
+    if v is None or v is False:
+        return None
+    if isinstance(v, (tuple, list)):
+        t, c = v
+        return float(t), float(c)
+    return float(v), -1.0
 
 
 def load_cfgs(onnx_dir):
@@ -147,12 +173,15 @@ def load_cfgs(onnx_dir):
         return json.load(f)
 
 
-def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None):
+def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None,
+                        loudness=None):
     """py/helper.py:316-337.  use_gpu=True is the only mode (the reference only had the CPU one).  An unusable asset directory is an
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
     weights (benchmarks and tests on machines without the Hugging Face assets), and it says so.  `output_rate` (Hz): the rate of the
-    returned audio, resampled on the GPU (include/stn.h, stn_set_output_rate); None returns the model's rate."""
+    returned audio, resampled on the GPU (include/stn.h, stn_set_output_rate); None returns the model's rate.  `loudness`: normalize
+    every utterance to this BS.1770-4 integrated loudness on the GPU (a target in LUFS, or (target, peak ceiling dBFS); include/stn.h,
+    stn_set_loudness); None leaves the level as synthesized."""
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
     if not use_gpu:
@@ -174,6 +203,6 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
                 "ttl": {"chunk_compress_factor": a.chunk_compress_factor, "latent_dim": a.latent_dim}}
         tp = host.UnicodeProcessor(host.synthetic_indexer())
         synthetic = True
-    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate)
+    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness)
     tts.synthetic = synthetic
     return tts
