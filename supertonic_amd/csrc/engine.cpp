@@ -182,6 +182,8 @@ Engine::~Engine() {
     if (seed_dev_) (void)hipFree(seed_dev_);
     rs_release();
     lo_release();
+    if (out_f32_) (void)hipFree(out_f32_);
+    if (out_pcm_) (void)hipFree(out_pcm_);
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);
         if (f.dev) (void)hipFree(f.dev);

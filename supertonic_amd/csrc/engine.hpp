@@ -167,7 +167,6 @@ class Engine {
         float* noise = nullptr; size_t noise_cap = 0;   // injected noise [B,D,L] (optional)
         float* xt[2] = {nullptr, nullptr}; size_t xt_cap[2] = {0, 0};
         float* wav = nullptr; size_t wav_cap = 0;        // [B, L*cs]
-        int16_t* pcm = nullptr; size_t pcm_cap = 0;      // [B, L*cs] int16 (on demand)
         // text-encoder output rows: written on the side stream (text_side), copied at the head of the main pipeline into the
         // buffer the captured graphs read (text_rows) — so the encoder of run i+1 can work while run i still reads its rows
         unsigned char* text_side = nullptr; size_t text_side_cap = 0;
@@ -472,14 +471,10 @@ class Engine {
     FetchSlot fetch_[2];
     int out_hz_ = 0;                  // requested output rate (0: the model's)
     ResampleTable rs_, op_rs_;        // filter tables of the output rate and of op_resample (device copies owned here)
-    float* rs_f32_ = nullptr; size_t rs_f32_cap_ = 0;   // fetch-time scratch at the output rate (grow-only, outside the graph key)
-    int16_t* rs_pcm_ = nullptr; size_t rs_pcm_cap_ = 0;
     void rs_prepare(ResampleTable& t, int in_hz, int out_hz);
     const ResampleTable& rs_table();
     void rs_release();
     void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride);
-    float* rs_f32_buf(size_t n);
-    int16_t* rs_pcm_buf(size_t n);
     bool lo_on_ = false;
     float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
     LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
@@ -492,10 +487,19 @@ class Engine {
     void lo_release();
     // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain]
     void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on);
-    // the finished batch at the output rate (b.wav, or resampled into the fp32 scratch) measured on the stream: returns the rows,
-    // sets Wo (samples per row) and gain (device [B])
-    const float* lo_batch(int64_t& Wo, const float** gain, bool on, float** res = nullptr);
-    void lo_gain_enqueue(const float* x, int64_t rows, int64_t W, const float* g, float* y, int16_t* pcm, int64_t dst_stride);
+    // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
+    float* lo_batch(const float* x, int64_t Wo, bool on);
+    // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
+    // fp32 or PCM); every fetch path runs it into a device destination of rows `stride` apart (one of f32 / pcm)
+    struct OutRows { float* f32 = nullptr; int16_t* pcm = nullptr; int64_t stride = 0; };
+    void enqueue_output(const OutRows& o);
+    int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
+    bool out_native() const;             // neither resampled nor normalized: the delivered fp32 rows are b.wav itself
+    const float* out_source(int64_t Wo);  // the finished batch at the output rate: b.wav, or resampled into the fp32 scratch
+    float* out_f32_buf(size_t n);
+    int16_t* out_pcm_buf(size_t n);
+    float* out_f32_ = nullptr; size_t out_f32_cap_ = 0;  // fetch scratch (grow-only, outside the graph key)
+    int16_t* out_pcm_ = nullptr; size_t out_pcm_cap_ = 0;
     hipStream_t copy_s_ = nullptr;
     bool prof_on_ = false;
     std::vector<ProfSpan> spans_;

@@ -1,5 +1,5 @@
 // engine_batch.cpp — the resident-batch pipeline (stn_batch_*): upload, the one duration read, the captured latent pipeline and its
-// graph cache, the fetches (see engine.hpp).
+// graph cache, the output stage and the fetches that run it (see engine.hpp).
 #include "engine.hpp"
 #include "engine_internal.hpp"
 
@@ -409,85 +409,102 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
     STN_HIP(hipGetLastError());  // a kernel launch that was rejected (bad configuration) must not pass silently
 }
 
+// =================================================================================================
+// output stage: the finished batch -> what a fetch delivers
+// =================================================================================================
+
+// grow-only fetch scratch (not part of the resident batch: growing it re-keys no captured graph)
+template <typename T>
+static T* out_grow(Engine& e, T*& p, size_t& cap, size_t n) {
+    if (p && n <= cap) return p;
+    e.sync();  // the previous fetch may still be reading it
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    STN_HIP(hipMalloc(reinterpret_cast<void**>(&p), (n + n / 4) * sizeof(T)));
+    cap = n + n / 4;
+    return p;
+}
+float* Engine::out_f32_buf(size_t n) { return out_grow(*this, out_f32_, out_f32_cap_, n); }
+int16_t* Engine::out_pcm_buf(size_t n) { return out_grow(*this, out_pcm_, out_pcm_cap_, n); }
+
+int64_t Engine::out_row_len() {
+    STN_HIP(hipSetDevice(device_));
+    const Batch& b = bt_;
+    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
+    return out_len((int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor);
+}
+
+bool Engine::out_native() const { return !loudness_on() && !resample_on(); }
+
+const float* Engine::out_source(int64_t Wo) {
+    const Batch& b = bt_;
+    if (!resample_on()) return b.wav;
+    float* d = out_f32_buf((size_t)b.B * Wo);
+    resample_enqueue(rs_table(), b.wav, b.B, (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, d, nullptr, Wo);
+    return d;
+}
+
+// Loudness on: the rows at the output rate are measured, then stored with the gain.  Off: resampled straight into the destination
+// when a rate is set; at the native rate converted to PCM, or copied.
+void Engine::enqueue_output(const OutRows& o) {
+    const Batch& b = bt_;
+    const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    if (o.stride < Wo)
+        throw std::invalid_argument(resample_on() ? "dst_stride smaller than the waveform length at the output rate" : "dst_stride smaller than the waveform length");
+    if (loudness_on()) {
+        const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.f32 alike: scaled in place)
+        const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
+        const char* saved = stage_;
+        stage_ = "out";
+        if (prof_on_) prof_begin("loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (o.pcm ? 6 : 8));
+        if (o.pcm) launch_store_rows(s_, src, b.B, Wo, g, o.pcm, o.stride);
+        else launch_store_rows(s_, src, b.B, Wo, g, o.f32, o.stride);
+        if (prof_on_) prof_end();
+        stage_ = saved;
+    } else if (resample_on()) {
+        resample_enqueue(rs_table(), b.wav, b.B, W, o.f32, o.pcm, o.stride);
+    } else if (o.pcm) {
+        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.pcm, o.stride);
+    } else {
+        STN_HIP(hipMemcpy2DAsync(o.f32, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
+    }
+    STN_HIP(hipGetLastError());
+}
+
+static void copy_durations(const std::vector<float>& dur, float* duration) {
+    if (duration) std::copy(dur.begin(), dur.end(), duration);
+}
+
 void Engine::batch_fetch(float* wav, size_t wav_capacity, float* duration) {
-    Batch& b = bt_;
-    if (wav && loudness_on()) {  // at the output rate, measured and scaled on the stream, then copied
-        int64_t Wo = 0;
-        const float* g = nullptr;
-        const float* src = lo_batch(Wo, &g, true);
-        const size_t no = (size_t)b.B * Wo;
-        if (wav_capacity < no) throw std::runtime_error("wav buffer too small: need " + std::to_string(no) + " floats");
-        float* d = rs_f32_buf(no);  // (the resampled rows themselves when a rate is set: scaled in place)
-        lo_gain_enqueue(src, b.B, Wo, g, d, nullptr, Wo);
-        STN_HIP(hipMemcpyAsync(wav, d, no * 4, hipMemcpyDeviceToHost, s_));
-        sync();
-        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
-        return;
-    }
-    if (wav && resample_on()) {  // at the output rate: resampled on the stream, then copied
-        STN_HIP(hipSetDevice(device_));
-        const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, Wo = out_len(W);
-        const size_t no = (size_t)b.B * Wo;
-        if (wav_capacity < no) throw std::runtime_error("wav buffer too small: need " + std::to_string(no) + " floats");
-        const ResampleTable& t = rs_table();
-        float* d = rs_f32_buf(no);
-        resample_enqueue(t, b.wav, b.B, W, d, nullptr, Wo);
-        STN_HIP(hipMemcpyAsync(wav, d, no * 4, hipMemcpyDeviceToHost, s_));
-        sync();
-        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
-        return;
-    }
-    const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (wav) {
-        if (wav_capacity < nw) throw std::runtime_error("wav buffer too small: need " + std::to_string(nw) + " floats");
-        STN_HIP(hipMemcpyAsync(wav, b.wav, nw * 4, hipMemcpyDeviceToHost, s_));
+        const int64_t Wo = out_row_len();
+        const size_t n = (size_t)bt_.B * Wo;
+        if (wav_capacity < n) throw std::runtime_error("wav buffer too small: need " + std::to_string(n) + " floats");
+        const float* src = bt_.wav;  // at the native rate the batch's own rows: no device copy
+        if (!out_native()) {
+            float* d = out_f32_buf(n);
+            enqueue_output({d, nullptr, Wo});
+            src = d;
+        }
+        STN_HIP(hipMemcpyAsync(wav, src, n * 4, hipMemcpyDeviceToHost, s_));
     }
     sync();
-    if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+    copy_durations(reported_dur_, duration);
 }
 void Engine::batch_fetch_pcm16(int16_t* pcm, size_t capacity, float* duration) {
-    STN_HIP(hipSetDevice(device_));
-    Batch& b = bt_;
-    const size_t nw = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
-    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    if (loudness_on()) {
-        int64_t Wo = 0;
-        const float* g = nullptr;
-        const float* src = lo_batch(Wo, &g, true);
-        const size_t no = (size_t)b.B * Wo;
-        if (capacity < no) throw std::runtime_error("pcm buffer too small: need " + std::to_string(no) + " samples");
-        int16_t* d = rs_pcm_buf(no);
-        lo_gain_enqueue(src, b.B, Wo, g, nullptr, d, Wo);
-        STN_HIP(hipMemcpyAsync(pcm, d, no * 2, hipMemcpyDeviceToHost, s_));
-        sync();
-        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
-        return;
-    }
-    if (resample_on()) {
-        const int64_t W = (int64_t)(nw / (size_t)b.B), Wo = out_len(W);
-        const size_t no = (size_t)b.B * Wo;
-        if (capacity < no) throw std::runtime_error("pcm buffer too small: need " + std::to_string(no) + " samples");
-        const ResampleTable& t = rs_table();
-        int16_t* d = rs_pcm_buf(no);
-        resample_enqueue(t, b.wav, b.B, W, nullptr, d, Wo);
-        STN_HIP(hipMemcpyAsync(pcm, d, no * 2, hipMemcpyDeviceToHost, s_));
-        sync();
-        if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
-        return;
-    }
-    if (capacity < nw) throw std::runtime_error("pcm buffer too small: need " + std::to_string(nw) + " samples");
-    ensure(b.pcm, b.pcm_cap, nw);
-    launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)(nw / (size_t)b.B), b.pcm, (int64_t)(nw / (size_t)b.B));
-    STN_HIP(hipMemcpyAsync(pcm, b.pcm, nw * 2, hipMemcpyDeviceToHost, s_));
+    const int64_t Wo = out_row_len();
+    const size_t n = (size_t)bt_.B * Wo;
+    if (capacity < n) throw std::runtime_error("pcm buffer too small: need " + std::to_string(n) + " samples");
+    int16_t* d = out_pcm_buf(n);
+    enqueue_output({nullptr, d, Wo});
+    STN_HIP(hipMemcpyAsync(pcm, d, n * 2, hipMemcpyDeviceToHost, s_));
     sync();
-    if (duration) std::copy(reported_dur_.begin(), reported_dur_.end(), duration);
+    copy_durations(reported_dur_, duration);
 }
 void Engine::batch_fetch_pcm16_begin(int slot) {
-    STN_HIP(hipSetDevice(device_));
     if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
-    Batch& b = bt_;
-    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    const size_t nw = (size_t)b.B * out_len((int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor);  // (output samples)
+    const int64_t Wo = out_row_len();
+    const size_t nw = (size_t)bt_.B * Wo;
     FetchSlot& f = fetch_[slot];
     if (!copy_s_) STN_HIP(hipStreamCreateWithFlags(&copy_s_, hipStreamNonBlocking));
     if (!f.ready) { STN_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming)); STN_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming)); }
@@ -501,17 +518,7 @@ void Engine::batch_fetch_pcm16_begin(int slot) {
         STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap * sizeof(int16_t), hipHostMallocDefault));
         f.cap = cap;
     }
-    if (loudness_on()) {
-        int64_t Wo = 0;
-        const float* g = nullptr;
-        const float* src = lo_batch(Wo, &g, true);
-        lo_gain_enqueue(src, b.B, Wo, g, nullptr, f.dev, Wo);
-    } else if (resample_on()) {
-        const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
-        resample_enqueue(rs_table(), b.wav, b.B, W, nullptr, f.dev, (int64_t)(nw / (size_t)b.B));
-    } else {
-        launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)(nw / (size_t)b.B), f.dev, (int64_t)(nw / (size_t)b.B));
-    }
+    enqueue_output({nullptr, f.dev, Wo});
     STN_HIP(hipEventRecord(f.ready, s_));
     STN_HIP(hipStreamWaitEvent(copy_s_, f.ready, 0));
     STN_HIP(hipMemcpyAsync(f.pin, f.dev, nw * sizeof(int16_t), hipMemcpyDeviceToHost, copy_s_));
@@ -527,50 +534,10 @@ void Engine::batch_fetch_pcm16_end(int slot, const int16_t** pcm, size_t* n, flo
     STN_HIP(hipEventSynchronize(f.done));
     if (pcm) *pcm = f.pin;
     if (n) *n = f.n;
-    if (duration) std::copy(f.dur.begin(), f.dur.end(), duration);
+    copy_durations(f.dur, duration);
 }
-void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) {
-    Batch& b = bt_;
-    const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
-    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    if (loudness_on()) {
-        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
-        int64_t Wo = 0;
-        const float* g = nullptr;
-        const float* src = lo_batch(Wo, &g, true);
-        lo_gain_enqueue(src, b.B, Wo, g, dst, nullptr, dst_stride);
-        return;
-    }
-    if (resample_on()) {
-        STN_HIP(hipSetDevice(device_));
-        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
-        resample_enqueue(rs_table(), b.wav, b.B, (int64_t)W, dst, nullptr, dst_stride);
-        return;
-    }
-    if ((size_t)dst_stride < W) throw std::invalid_argument("dst_stride smaller than the waveform length");
-    STN_HIP(hipMemcpy2DAsync(dst, (size_t)dst_stride * 4, b.wav, W * 4, W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
-}
-void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) {
-    STN_HIP(hipSetDevice(device_));
-    Batch& b = bt_;
-    const size_t W = (size_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
-    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    if (loudness_on()) {
-        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
-        int64_t Wo = 0;
-        const float* g = nullptr;
-        const float* src = lo_batch(Wo, &g, true);
-        lo_gain_enqueue(src, b.B, Wo, g, nullptr, dst, dst_stride);
-        return;
-    }
-    if (resample_on()) {
-        if (dst_stride < out_len((int64_t)W)) throw std::invalid_argument("dst_stride smaller than the waveform length at the output rate");
-        resample_enqueue(rs_table(), b.wav, b.B, (int64_t)W, nullptr, dst, dst_stride);
-        return;
-    }
-    if ((size_t)dst_stride < W) throw std::invalid_argument("dst_stride smaller than the waveform length");
-    launch_f32_to_pcm16(s_, b.wav, (int64_t)b.B, (int)W, dst, dst_stride);
-}
+void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) { enqueue_output({dst, nullptr, dst_stride}); }
+void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) { enqueue_output({nullptr, dst, dst_stride}); }
 void Engine::batch_fetch_latent(float* latent) {
     Batch& b = bt_;
     const size_t nx = (size_t)b.B * a_.latent_dim * a_.chunk_compress_factor * b.L;

@@ -1,5 +1,5 @@
 // engine_loudness.cpp — loudness normalization of a handle's fetches: the K-weighting design (host only), the scan's power table, the
-// fetch-time scratch, and the launches every fetch path makes when normalization is on (engine_batch.cpp).  The kernels are
+// measurement's scratch, and the measurement the output stage (engine_batch.cpp) and batch_loudness share.  The kernels are
 // kernels_loudness.hip; DESIGN.md section 11 has the contract.
 #include "engine.hpp"
 
@@ -158,29 +158,8 @@ void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_
     stage_ = saved;
 }
 
-void Engine::lo_gain_enqueue(const float* x, int64_t rows, int64_t W, const float* g, float* y, int16_t* pcm, int64_t dst_stride) {
-    const char* saved = stage_;
-    stage_ = "out";
-    if (prof_on_) prof_begin("loudness_gain", (double)rows * W, (double)rows * W * (pcm ? 6 : 8));
-    if (pcm) launch_loudness_gain_pcm16(s_, x, rows, W, g, pcm, dst_stride);
-    else launch_loudness_gain(s_, x, rows, W, g, y, dst_stride);
-    if (prof_on_) prof_end();
-    stage_ = saved;
-    STN_HIP(hipGetLastError());
-}
-
-const float* Engine::lo_batch(int64_t& Wo, const float** gain, bool on, float** res) {
-    Batch& b = bt_;
-    if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    STN_HIP(hipSetDevice(device_));
-    const int64_t W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
-    Wo = out_len(W);
-    const float* src = b.wav;
-    if (resample_on()) {  // the signal delivered: the waveform at the output rate
-        float* d = rs_f32_buf((size_t)b.B * Wo);
-        resample_enqueue(rs_table(), b.wav, b.B, W, d, nullptr, Wo);
-        src = d;
-    }
+float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
+    const Batch& b = bt_;
     const int hz = output_rate();
     lo_prepare(lo_, hz);
     // row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file
@@ -198,19 +177,14 @@ const float* Engine::lo_batch(int64_t& Wo, const float** gain, bool on, float** 
         lo_n_ptr_ = sc.n;
         STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
-    lo_measure(lo_, src, b.B, Wo, sc, max_seg, on);
-    *gain = sc.res + 2 * (int64_t)b.B;
-    if (res) *res = sc.res;
-    return src;
+    lo_measure(lo_, x, b.B, Wo, sc, max_seg, on);
+    return sc.res;
 }
 
 void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
-    Batch& b = bt_;
-    int64_t Wo = 0;
-    const float* g = nullptr;
-    float* res = nullptr;
-    lo_batch(Wo, &g, lo_on_, &res);
-    const size_t B = (size_t)b.B;
+    const int64_t Wo = out_row_len();
+    const float* res = lo_batch(out_source(Wo), Wo, lo_on_);
+    const size_t B = (size_t)bt_.B;
     if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, B * 4, hipMemcpyDeviceToHost, s_));
     if (peak) STN_HIP(hipMemcpyAsync(peak, res + B, B * 4, hipMemcpyDeviceToHost, s_));
     if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * B, B * 4, hipMemcpyDeviceToHost, s_));

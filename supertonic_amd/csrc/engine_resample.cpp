@@ -1,5 +1,5 @@
 // engine_resample.cpp — the output rate of a handle: the resampler's filter design (host only), its device table, and the launch
-// every fetch path makes when the rate is on (engine_batch.cpp).  The kernel is kernels_resample.hip.
+// the output stage makes when the rate is on (engine_batch.cpp).  The kernel is kernels_resample.hip.
 #include "engine.hpp"
 
 #include <cmath>
@@ -87,9 +87,6 @@ void Engine::rs_prepare(ResampleTable& t, int in_hz, int out_hz) {
 
 void Engine::rs_release() {
     for (ResampleTable* t : {&rs_, &op_rs_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
-    if (rs_f32_) (void)hipFree(rs_f32_);
-    if (rs_pcm_) (void)hipFree(rs_pcm_);
-    rs_f32_ = nullptr; rs_pcm_ = nullptr; rs_f32_cap_ = rs_pcm_cap_ = 0;
 }
 
 void Engine::set_output_rate(int hz) {
@@ -112,20 +109,6 @@ int64_t Engine::out_len(int64_t W) const {
     const int g = std::gcd(a_.sample_rate, out_hz_);
     return resample_out_len(W, out_hz_ / g, a_.sample_rate / g);
 }
-
-// grow-only scratch of the fetch paths (not part of the resident batch: growing it re-keys no captured graph)
-template <typename T>
-static T* rs_grow(Engine& e, T*& p, size_t& cap, size_t n) {
-    if (p && n <= cap) return p;
-    e.sync();  // the previous fetch may still be reading it
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&p), (n + n / 4) * sizeof(T)));
-    cap = n + n / 4;
-    return p;
-}
-float* Engine::rs_f32_buf(size_t n) { return rs_grow(*this, rs_f32_, rs_f32_cap_, n); }
-int16_t* Engine::rs_pcm_buf(size_t n) { return rs_grow(*this, rs_pcm_, rs_pcm_cap_, n); }
 
 void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride) {
     const char* saved = stage_;

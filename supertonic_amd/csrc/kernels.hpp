@@ -352,9 +352,11 @@ void launch_half_to_f32(hipStream_t s, int in_dtype, const void* in, int64_t n, 
 // total_step/current_step helper: fill n floats
 void launch_fill(hipStream_t s, float* x, int n, float v);
 void launch_step_counters(hipStream_t s, float* tot /*[steps][B]*/, float* cur /*[steps][B]*/, float* dt /*[B]*/, int B, int steps);
-// waveform epilogue: pcm[i] = int16(clamp(w[i], -1, 1) * 32767)  (truncation, cpp/helper.cpp:986-987)
-// rows x W samples -> int16 PCM rows at pcm + row * dst_stride (dst_stride >= W)
-void launch_f32_to_pcm16(hipStream_t s, const float* w, int64_t rows, int W, int16_t* pcm, int64_t dst_stride);
+// The final store of every fetch (the output stage, engine_batch.cpp): rows x W fp32 (row stride W), times g[row] when g (device [rows])
+// is not null, to y + row * dst_stride (dst_stride >= W) as fp32 or as int16 PCM by writeWavFile's rule (pcm16, kernels_dev.hpp:
+// int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987).  fp32 rows may be stored in place (y == x, dst_stride == W).
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride);
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* y, int64_t dst_stride);
 
 // Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
 // out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),
@@ -369,12 +371,12 @@ constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P =
 inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
 // Kaiser-windowed sinc for the pair (host only): fills f (not f.dev).  Empty string on success, else why the pair is refused.
 std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
-// rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride (dst_stride >= W_out): fp32, or int16 PCM converted exactly as
-// launch_f32_to_pcm16 converts (the PCM bytes are those of the fp32 output followed by that conversion)
+// rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride (dst_stride >= W_out): fp32, or int16 PCM by pcm16 (the PCM
+// bytes are those of the fp32 output followed by launch_store_rows without a gain)
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, float* y, int64_t dst_stride);
 void launch_resample_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int16_t* pcm, int64_t dst_stride);
 
-// Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the enqueue are engine_loudness.cpp).
+// Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the measurement are engine_loudness.cpp).
 // BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in
 // fp32) as one 4-state linear system x' = A x + B u.  Chunks of LO_CHUNK samples from sample 0: each is filtered from zero state
 // (end state e_k, max |x|), a per-row scan gives the true start states s_{k+1} = M s_k + e_k with M = A^LO_CHUNK, each chunk is
@@ -408,9 +410,6 @@ void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t*
 // res[0][b] = L_b (-inf when undefined), res[1][b] = peak_b, res[2][b] = g_b (1 when off or L_b undefined); max_seg = max_b n_b / hop
 void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pk, const float* pa,
                           const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res);
-// y[row * dst_stride + i] = x[row * W + i] * g[row] for i < W (y may be x when dst_stride == W), or the same product converted to int16
-// PCM exactly as launch_f32_to_pcm16 converts
-void launch_loudness_gain(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride);
-void launch_loudness_gain_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* pcm, int64_t dst_stride);
+// (the gain itself is applied by launch_store_rows with g = res + 2 * rows)
 
 }  // namespace stn

@@ -1,6 +1,6 @@
 // kernels_dev.hpp — device-side helpers shared by the MFMA kernels (kernels_gemm.hip, kernels_ffn.hip): vector types,
-// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms.  One definition, so that a fused
-// kernel and the launches it replaces round identically.
+// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; and the PCM rule of every fetch
+// (kernels_misc.hip, kernels_resample.hip).  One definition, so that a fused kernel and the launches it replaces round identically.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
@@ -23,6 +23,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, si
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, n, 0x00020000);
 }
 
+// fp32 -> 16-bit PCM exactly as the reference's writeWavFile (cpp/helper.cpp:986-987): clamp to [-1, 1], scale to full range, truncate
+__device__ __forceinline__ int pcm16(float v) { return (int)(fminf(1.0f, fmaxf(-1.0f, v)) * 32767.0f); }
 
 // erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7): GELU(x) = 0.5 x (1 + erf(x / sqrt2))
 __device__ __forceinline__ float gelu_f(float x) {

@@ -12,7 +12,7 @@
 //      of the next one (chunks and segments need not align);
 //   4. gate: one workgroup per row sums each segment's shares in a fixed order, forms the 400 ms block energies, applies the absolute
 //      and relative gates and writes (L_b, peak_b, g_b);
-//   5. gain: y = x * g_b per sample, as fp32 or as writeWavFile's 16-bit PCM.
+//   5. gain: y = x * g_b per sample, as fp32 or as writeWavFile's 16-bit PCM (launch_store_rows, kernels_misc.hip).
 // Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
 // row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
 #include "kernels.hpp"
@@ -247,43 +247,6 @@ __global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* _
     }
 }
 
-__global__ void loudness_gain_kernel(const float* x, int64_t W, int64_t n, const float* __restrict__ g, float* y, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W]
-    if (i >= n) return;
-    const int64_t row = i / W;
-    y[row * dst_stride + (i - row * W)] = x[i] * g[row];
-}
-__global__ void loudness_gain4_kernel(const float* x, int64_t W4, int64_t n4, const float* __restrict__ g, float* y, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/4]
-    if (i >= n4) return;
-    const int64_t row = i / W4;
-    const float s = g[row];
-    const float4 v = reinterpret_cast<const float4*>(x)[i];
-    *reinterpret_cast<float4*>(y + row * dst_stride + (i - row * W4) * 4) = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
-}
-__device__ __forceinline__ int lo_pcm(float v) { return (int)(fminf(1.0f, fmaxf(-1.0f, v)) * 32767.0f); }  // as pcm16_kernel
-__global__ void loudness_gain_pcm16_kernel(const float* __restrict__ x, int64_t W, int64_t n, const float* __restrict__ g, int16_t* __restrict__ pcm,
-                                           int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t row = i / W;
-    pcm[row * dst_stride + (i - row * W)] = (int16_t)lo_pcm(x[i] * g[row]);
-}
-__global__ void loudness_gain8_pcm16_kernel(const float* __restrict__ x, int64_t W8, int64_t n8, const float* __restrict__ g,
-                                            int16_t* __restrict__ pcm, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/8]
-    if (i >= n8) return;
-    const int64_t row = i / W8;
-    const float s = g[row];
-    const float4* src = reinterpret_cast<const float4*>(x) + i * 2;
-    const float4 a = src[0], b = src[1];
-    const float v[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};
-    unsigned o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = ((unsigned)lo_pcm(v[2 * j]) & 0xFFFFu) | ((unsigned)lo_pcm(v[2 * j + 1]) << 16);
-    *reinterpret_cast<uint4*>(pcm + row * dst_stride + (i - row * W8) * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 
 void lo_check(int64_t rows, int64_t W, const LoudTable& t) {
@@ -322,30 +285,6 @@ void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t*
                                           (int)(LO_MAX_SEG * sizeof(double))), "hipFuncSetAttribute(loudness_gate)");
     STN_KLAUNCH(loudness_gate_kernel, dim3((unsigned)rows), dim3(LO_GATE), lds, s, n, lo_chunks(W), t.hop, pk, pa, pb, on ? 1 : 0, target_lufs,
                 ceiling_dbfs, rows, res);
-}
-
-void launch_loudness_gain(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride) {
-    const int64_t n = rows * W;
-    if (n <= 0) return;
-    if (dst_stride < W) throw std::invalid_argument("loudness gain: dst_stride smaller than the row length");
-    if (W % 4 == 0 && dst_stride % 4 == 0 && aligned16(x) && aligned16(y)) {
-        const int64_t n4 = n / 4;
-        STN_KLAUNCH(loudness_gain4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, W / 4, n4, g, y, dst_stride);
-    } else {
-        STN_KLAUNCH(loudness_gain_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, W, n, g, y, dst_stride);
-    }
-}
-
-void launch_loudness_gain_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* pcm, int64_t dst_stride) {
-    const int64_t n = rows * W;
-    if (n <= 0) return;
-    if (dst_stride < W) throw std::invalid_argument("loudness gain: dst_stride smaller than the row length");
-    if (W % 8 == 0 && dst_stride % 8 == 0 && aligned16(x) && aligned16(pcm)) {
-        const int64_t n8 = n / 8;
-        STN_KLAUNCH(loudness_gain8_pcm16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, x, W / 8, n8, g, pcm, dst_stride);
-    } else {
-        STN_KLAUNCH(loudness_gain_pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, W, n, g, pcm, dst_stride);
-    }
 }
 
 }  // namespace stn

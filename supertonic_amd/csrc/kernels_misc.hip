@@ -5,9 +5,10 @@
 //                 k taps re-read neighbouring frames through L1/L2, HBM sees each frame once.
 //   layernorm     same reduction without the conv.
 //   vocoder_in    latent un-compress + the ld->C input conv of the vocoder, frame window staged in LDS.
-//   + gather / mask / transpose / noise / pcm helpers.
+//   + gather / mask / transpose / noise helpers, and the final store of every fetch (fp32 or PCM, with or without a gain).
 // All row-major [rows][channels]; see kernels.hpp for the contracts.
 #include "kernels.hpp"
+#include "kernels_dev.hpp"
 #include "dev_env.hpp"
 #include "kernels_fold.hpp"
 
@@ -1319,41 +1320,60 @@ void launch_mask_ncl(hipStream_t s, float* x, int B, int D, int L, const int* le
     STN_KLAUNCH(mask_ncl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, D, L, n, len);
 }
 
-// fp32 -> int16 PCM exactly as the reference's writeWavFile (clamp to [-1,1], * 32767, truncation toward zero), 8 samples
-// per thread (two 16-B loads, one 16-B store); rows of W samples may land with a destination stride (gather payloads).
-__global__ void pcm16_kernel(const float* __restrict__ w, int W8, int64_t n8, int16_t* __restrict__ pcm, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/8]
-    if (i >= n8) return;
-    const int64_t row = i / W8;
-    const int c = (int)(i - row * W8);
-    const float4* src = reinterpret_cast<const float4*>(w) + i * 2;
-    const float4 a = src[0], b = src[1];
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int lo = (int)(fminf(1.0f, fmaxf(-1.0f, v[2 * j])) * 32767.0f);
-        const int hi = (int)(fminf(1.0f, fmaxf(-1.0f, v[2 * j + 1])) * 32767.0f);
-        o[j] = ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16);
-    }
-    *reinterpret_cast<uint4*>(pcm + row * dst_stride + (int64_t)c * 8) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-__global__ void pcm16_scalar_kernel(const float* __restrict__ w, int W, int64_t n, int16_t* __restrict__ pcm, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t row = i / W;
-    const float c = fminf(1.0f, fmaxf(-1.0f, w[i]));
-    pcm[row * dst_stride + (i - row * W)] = (int16_t)(int)(c * 32767.0f);
-}
-void launch_f32_to_pcm16(hipStream_t s, const float* w, int64_t rows, int W, int16_t* pcm, int64_t dst_stride) {
-    const int64_t n = rows * W;
-    if (n == 0) return;
-    if (W % 8 == 0 && dst_stride % 8 == 0 && !(reinterpret_cast<uintptr_t>(pcm) & 15) && !(reinterpret_cast<uintptr_t>(w) & 15)) {
-        const int64_t n8 = n / 8;
-        STN_KLAUNCH(pcm16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, w, W / 8, n8, pcm, dst_stride);
+// The final store of a fetch: V samples per thread (V = 4 for fp32, 8 for PCM: 16-B loads and one 16-B store; or 1), times the row's
+// gain when kGain.  x and y may be the same fp32 rows (dst_stride == W: the gain applied in place), so neither is __restrict__.
+template <int V, bool kGain, typename OutT>
+__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, OutT* y, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/V]
+    if (i >= nv) return;
+    const int64_t row = i / Wv;
+    float v[V];
+    if constexpr (V == 1) {
+        v[0] = x[i];
     } else {
-        STN_KLAUNCH(pcm16_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, W, n, pcm, dst_stride);
+#pragma unroll
+        for (int j = 0; j < V / 4; ++j) {
+            const float4 a = reinterpret_cast<const float4*>(x)[i * (V / 4) + j];
+            v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+        }
     }
+    if constexpr (kGain) {
+        const float s = g[row];
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] *= s;
+    }
+    OutT* d = y + row * dst_stride + (i - row * Wv) * V;
+    if constexpr (std::is_same<OutT, float>::value) {
+        if constexpr (V == 1) *d = v[0];
+        else *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (V == 1) {
+        *d = (int16_t)pcm16(v[0]);
+    } else {
+        unsigned o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ((unsigned)pcm16(v[2 * j]) & 0xFFFFu) | ((unsigned)pcm16(v[2 * j + 1]) << 16);
+        *reinterpret_cast<uint4*>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+template <typename OutT>
+void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, OutT* y, int64_t dst_stride) {
+    const int64_t n = rows * W;
+    if (n <= 0) return;
+    if (dst_stride < W) throw std::invalid_argument("store_rows: dst_stride smaller than the row length");
+    constexpr int V = 16 / sizeof(OutT);
+    const bool vec = W % V == 0 && dst_stride % V == 0 && !(reinterpret_cast<uintptr_t>(x) & 15) && !(reinterpret_cast<uintptr_t>(y) & 15);
+    const int64_t nv = vec ? n / V : n;
+    const dim3 grid((unsigned)((nv + 255) / 256));
+    if (vec && g) STN_KLAUNCH((store_rows_kernel<V, true, OutT>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (vec) STN_KLAUNCH((store_rows_kernel<V, false, OutT>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (g) STN_KLAUNCH((store_rows_kernel<1, true, OutT>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+    else STN_KLAUNCH((store_rows_kernel<1, false, OutT>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+}
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride) {
+    launch_store_rows_t(s, x, rows, W, g, y, dst_stride);
+}
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* y, int64_t dst_stride) {
+    launch_store_rows_t(s, x, rows, W, g, y, dst_stride);
 }
 
 }  // namespace stn

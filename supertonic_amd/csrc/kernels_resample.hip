@@ -12,6 +12,7 @@
 // the row, the tile or the launch, and a read outside the row is 0.0f: a row whose samples past m are zero gives, in its first
 // ceil(m*P/Q) outputs, exactly what the row cut at m gives.
 #include "kernels.hpp"
+#include "kernels_dev.hpp"
 
 namespace stn {
 
@@ -27,9 +28,7 @@ __host__ __device__ inline int64_t rs_span(int G, int P, int Q, int T) {
 }
 
 __device__ __forceinline__ void rs_store(float* y, int64_t i, float v) { y[i] = v; }
-__device__ __forceinline__ void rs_store(int16_t* y, int64_t i, float v) {
-    y[i] = (int16_t)(int)(fminf(1.0f, fmaxf(-1.0f, v)) * 32767.0f);  // as pcm16_kernel (kernels_misc.hip)
-}
+__device__ __forceinline__ void rs_store(int16_t* y, int64_t i, float v) { y[i] = (int16_t)pcm16(v); }
 
 template <bool kLds, typename OutT>
 __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const float* __restrict__ x, int64_t W, int64_t W_out, int P, int Q, int T,

@@ -96,6 +96,51 @@ def test_pcm16_fetch_matches_reference_wav_conversion(eng):
         assert np.array_equal(got[:, :W], ref_pcm) and np.all(got[:, W:] == -7)
 
 
+@pytest.mark.parametrize("rate", [None, 16000])
+def test_every_fetch_path_checks_its_destination(eng, rate):
+    """The five fetch paths: a host buffer or a device stride one sample short of the rows delivered (at the output rate) is refused
+    with its message; without a finished batch every path with a destination is refused; batch_fetch(want_wav=False) still returns."""
+    from hip_util import DeviceBuffer
+    fresh = binding.Engine(0, "f32")
+    fresh.load_synthetic(tiny_arch(), 7)
+    fresh.set_output_rate(rate)
+    t = DeviceBuffer(np.zeros(4096, np.float32))
+    h, d = np.empty(4096, np.float32), np.empty(2, np.float32)
+    for call in (lambda: fresh._ck(fresh._lib.stn_batch_fetch(fresh._h, h.ctypes.data, 4096, d.ctypes.data)),
+                 lambda: fresh._ck(fresh._lib.stn_batch_fetch_pcm16(fresh._h, h.ctypes.data, 4096, d.ctypes.data)),
+                 lambda: fresh.fetch_pcm16_begin(0),
+                 lambda: fresh.batch_copy_wav_device(t.ptr, 1024),
+                 lambda: fresh.batch_copy_pcm16_device(t.ptr, 1024)):
+        with pytest.raises(binding.StnError, match="no finished batch"):
+            call()
+    fresh.close()
+
+    a = tiny_arch()
+    ids, mask, sttl, sdp = make_inputs(a, 2, 10, [10, 6], seed=4)
+    eng.set_output_rate(rate)
+    try:
+        _, dur = eng.synthesize(ids, mask, sttl, sdp, 2, 1.0, duration_override=np.array([0.2, 0.1], np.float32))
+        B, _, W = eng.batch_dims()
+        wav, pcm = np.empty(B * W, np.float32), np.empty(B * W, np.int16)
+        for fetch, buf, what in ((eng._lib.stn_batch_fetch, wav, "wav buffer too small"),
+                                 (eng._lib.stn_batch_fetch_pcm16, pcm, "pcm buffer too small")):
+            with pytest.raises(binding.StnError, match=what):
+                eng._ck(fetch(eng._h, buf.ctypes.data, B * W - 1, d.ctypes.data))
+        for copy, dtype in ((eng.batch_copy_wav_device, np.float32), (eng.batch_copy_pcm16_device, np.int16)):
+            dst = DeviceBuffer(np.full((B, W), -7, dtype))  # B rows of W: even a stride of W - 1 would land inside it
+            with pytest.raises(binding.StnError, match="dst_stride smaller than the waveform length"):
+                copy(dst.ptr, W - 1)
+            eng.sync()
+            assert np.all(dst.to_host() == -7)
+        eng.fetch_pcm16_begin(0)  # (the slot is the engine's own, sized by it)
+        p, d_slot = eng.fetch_pcm16_end(0)
+        assert p.shape == (B, W) and np.array_equal(d_slot, dur)
+        w, d_only = eng.batch_fetch(want_wav=False)
+        assert w is None and np.array_equal(d_only, dur)
+    finally:
+        eng.set_output_rate(None)
+
+
 def test_speed_scales_duration_and_length(eng):
     a = tiny_arch()
     ids, mask, sttl, sdp = make_inputs(a, 1, 8, [8], seed=6)

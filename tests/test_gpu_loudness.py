@@ -205,11 +205,14 @@ def test_off_is_the_native_path_and_graphs_survive_toggles():
     e.load_synthetic(a, 7)
     e.batch_upload(ids, mask, sttl, sdp, duration_override=durs)
     e.batch_run(2, 1.05, 4)
-    e.batch_fetch_pcm16()  # (the native PCM buffer is part of the resident batch: allocate it before the shape is captured)
     for _ in range(3):  # the second sighting captures the shape, the third replays it
         e.batch_run(2, 1.05, 4)
     cached, replays = e.graphs_cached, e.graph_replays
     assert cached >= 1 and replays >= 1
+    e.batch_fetch_pcm16()  # the first native PCM fetch allocates fetch scratch, which no captured graph reads: nothing is re-keyed
+    e.batch_run(2, 1.05, 4)
+    assert e.graphs_cached == cached and e.graph_replays == replays + 1
+    replays += 1
     e.set_loudness(-16.0)
     assert e.graphs_cached == cached
     assert any("loudness" in k for k in _launches(e, e.batch_fetch_pcm16))

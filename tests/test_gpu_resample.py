@@ -228,11 +228,14 @@ def test_rate_off_is_the_native_path_and_graphs_survive_a_switch():
     e.load_synthetic(a, 7)
     e.batch_upload(ids, mask, sttl, sdp, duration_override=durs)
     e.batch_run(2, 1.05, 4)
-    e.batch_fetch_pcm16()  # (the native PCM buffer is part of the resident batch: allocate it before the shape is captured)
     for _ in range(3):  # the second sighting captures the shape, the third replays it
         e.batch_run(2, 1.05, 4)
     cached, replays = e.graphs_cached, e.graph_replays
     assert cached >= 1 and replays >= 1
+    e.batch_fetch_pcm16()  # the first native PCM fetch allocates fetch scratch, which no captured graph reads: nothing is re-keyed
+    e.batch_run(2, 1.05, 4)
+    assert e.graphs_cached == cached and e.graph_replays == replays + 1
+    replays += 1
     e.set_output_rate(16000)
     assert e.graphs_cached == cached  # the rate is fetch-time state: no graph is dropped
     assert any("resample" in k for k in _launches(e, e.batch_fetch_pcm16))
