@@ -213,6 +213,37 @@ int stn_batch_copy_wav_device(stn_handle* h, void* dst_device, int64_t dst_strid
  * half the bytes over xGMI; dst_stride in samples */
 int stn_batch_copy_pcm16_device(stn_handle* h, void* dst_device, int64_t dst_stride);
 
+/* ---- sample encodings --------------------------------------------------------------------------------
+ * Every fetch path can deliver the waveform in one of these encodings.  The encoded signal is the one the fp32 fetch delivers (at the
+ * output rate when one is set, times the loudness gain when normalization is on); the encoding is the last step of the one store on
+ * the GPU.  v = that fp32 sample:
+ *   STN_ENC_F32    4 bytes  v                                                     (stn_batch_fetch)
+ *   STN_ENC_PCM16  2 bytes  pcm16(v) = (int16)(clamp(v, -1, 1) * 32767), truncation  (stn_batch_fetch_pcm16)
+ *   STN_ENC_PCM24  3 bytes  (int)(clamp(v, -1, 1) * 8388607.0f) in fp32, little-endian two's complement
+ *   STN_ENC_MULAW  1 byte   G.711 mu-law of pcm16(v): G.191 ulaw_compress of pcm16(v) >> 2, as audioop.lin2ulaw(s, 2)
+ *   STN_ENC_ALAW   1 byte   G.711 A-law of pcm16(v): G.191 alaw_compress of pcm16(v) >> 3, as audioop.lin2alaw(s, 2)
+ * A mu-law or A-law codeword is a pure function of the 16-bit sample.  Zero codewords (what silence and padding are): 0.0f, 0, 00 00 00,
+ * 0xFF (mu-law; 0x00 is its full-scale negative), 0xD5 (A-law).  Buffers are [B][W] samples of enc_bytes each, rows packed (host
+ * fetches) or dst_stride samples apart (device copies).  The encoding is a fetch argument, not a handle setting: the captured pipeline
+ * and stn_batch_wav_device_ptr are unchanged, and switching encodings drops or re-keys no captured graph.  DESIGN.md section 12. */
+#define STN_ENC_F32 0
+#define STN_ENC_PCM16 1
+#define STN_ENC_PCM24 2
+#define STN_ENC_MULAW 3
+#define STN_ENC_ALAW 4
+/* bytes per sample of an encoding; 0 for an unknown one */
+int stn_encoding_bytes(int enc);
+/* stn_batch_fetch in encoding enc: B * W * stn_encoding_bytes(enc) bytes into dst (may be NULL: durations only) */
+int stn_batch_fetch_encoded(stn_handle* h, int enc, void* dst, size_t capacity_bytes, float* duration);
+/* stn_batch_copy_wav_device in encoding enc; dst_stride in samples */
+int stn_batch_copy_encoded_device(stn_handle* h, int enc, void* dst_device, int64_t dst_stride);
+/* stn_batch_fetch_pcm16_begin / _end in encoding enc (the slot's pinned buffer holds *n_bytes bytes).  stn_batch_fetch_pcm16_begin is
+ * this with STN_ENC_PCM16; stn_batch_fetch_pcm16_end on a slot begun with another encoding is STN_ERR_STATE. */
+int stn_batch_fetch_encoded_begin(stn_handle* h, int slot, int enc);
+int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size_t* n_bytes, float* duration_or_null);
+/* op-level: rows x W fp32 (host) -> rows x W samples of encoding enc (host, rows packed): the fetch's store kernel without a gain */
+int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void* y);
+
 /* ---- output rate ---------------------------------------------------------------------------------------
  * The model synthesizes at its own rate (stn_arch.sample_rate, 44.1 kHz for the published model; the reference's hosts can only
  * return that: cpp/helper.cpp:943-990).  With an output rate set, every fetch path — stn_batch_fetch, stn_batch_fetch_pcm16,

@@ -9,7 +9,7 @@
  *     SURVEY.md section 8(e) — so every device gets the same share of long and short utterances; noise is keyed by the utterance's
  *     index in the CALLER's batch, so a dealt batch draws the noise of the undealt one;
  *   - every device runs DP -> text encoder -> noise -> Euler steps -> vocoder on its shard and converts to 16-bit PCM (the
- *     reference's final product: writeWavFile, cpp/helper.cpp:943-990) on the GPU;
+ *     reference's final product: writeWavFile, cpp/helper.cpp:943-990), or to the encoding stn_group_set_encoding chose, on the GPU;
  *   - ONE exchange: the PCM blocks travel to the first device over RCCL — ncclCommInitAll once at stn_group_create, then per
  *     synthesis ncclGroupStart; ncclSend (rank r -> 0) / ncclRecv (0 <- r), r = 1..n-1; ncclGroupEnd on the engines' own streams, so
  *     the exchange is ordered behind each device's kernels with no host synchronisation — and from there to the host in caller order.
@@ -53,6 +53,10 @@ int stn_group_load_dir(stn_group* g, const char* onnx_dir);
 int stn_group_set_output_rate(stn_group* g, int hz);
 /* loudness normalization of every rank (stn_set_loudness): the gathered PCM is then normalized row by row */
 int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceiling_dbfs);
+/* sample encoding (STN_ENC_*, stn.h) of the gather of the next stn_group_synthesize: every rank encodes its shard on its GPU and the
+ * blocks, the exchange and the host stage are sized in that encoding's bytes (a mu-law gather moves half the bytes of a PCM16 one).
+ * The default is STN_ENC_PCM16; an unknown encoding is STN_ERR_INVALID. */
+int stn_group_set_encoding(stn_group* g, int enc);
 
 /* The deal, host only: utterance i goes to rank rank_of[i] as row row_of[i] of that rank's shard.  lengths[B] = token counts.
  * Sorted by length descending (ties: caller order), dealt round-robin: the k-th longest goes to rank k % n as row k / n. */
@@ -64,7 +68,11 @@ int stn_group_deal(int B, const int32_t* lengths, int n_ranks, int32_t* rank_of,
 int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, const float* text_mask, const float* style_ttl,
                          const float* style_dp, int total_step, float speed, const float* duration_override_or_null, uint64_t noise_seed,
                          int64_t* samples_per_utt_out);
-/* the result of the last synthesis in CALLER order: pcm [B][W] int16 (capacity in samples), duration [B] seconds (after /speed) */
+/* the result of the last synthesis in CALLER order: [B][W] samples of the gather's encoding (capacity in bytes); a row past its
+ * shard's W_r is filled with the encoding's zero codeword (0xFF mu-law, 0xD5 A-law, zero bytes otherwise); duration [B] seconds
+ * (after /speed) */
+int stn_group_fetch_encoded(stn_group* g, void* dst, size_t capacity_bytes, float* duration);
+/* the same for a PCM16 gather: pcm [B][W] int16 (capacity in samples); STN_ERR_STATE when the last gather had another encoding */
 int stn_group_fetch_pcm16(stn_group* g, int16_t* pcm, size_t capacity_samples, float* duration);
 /* how the last synthesis was dealt: utterances and samples per utterance of every rank's block (n values each) */
 int stn_group_last_shards(const stn_group* g, int32_t* rows_per_rank, int64_t* samples_per_rank);

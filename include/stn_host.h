@@ -6,7 +6,7 @@
  *   stn_latent_geometry    TextToSpeech::sampleNoisyLatent (shapes)   cpp/helper.cpp:424-440,457 + getLatentMask :759-770
  *   stn_chunk_text         chunkText                                  cpp/helper.cpp:1117-1186
  *   stn_sanitize_filename  sanitizeFilename                           cpp/helper.cpp:1070-1111
- *   stn_wav_encode / stn_write_wav   writeWavFile                     cpp/helper.cpp:943-990
+ *   stn_wav_encode / stn_write_wav   writeWavFile                     cpp/helper.cpp:943-990 (stn_wav_encode_as: other encodings)
  *   stn_load_voice_style   loadVoiceStyle                             cpp/helper.cpp:829-897 (schema go/helper.go:87-98)
  * Strings are UTF-8, NUL-terminated.  Functions that produce text return the number of bytes needed
  * (excluding the NUL) and write at most `cap` bytes; a negative return is an STN_ERR_* code and
@@ -54,6 +54,11 @@ int64_t stn_bound_tensor(const char* onnx_dir, const char* canonical_name, float
 
 int64_t stn_wav_encode(const float* audio, size_t n, int sample_rate, unsigned char* out, size_t cap);
 int stn_write_wav(const char* path, const float* audio, size_t n, int sample_rate);
+/* n already-encoded mono samples (enc = STN_ENC_* of stn.h: fp32, int16, 24-bit little-endian, mu-law or A-law bytes, as the encoded
+ * fetches deliver them) -> a RIFF WAVE file in out; returns the bytes needed (copied when cap suffices), STN_ERR_INVALID for an unknown
+ * encoding.  PCM16 / PCM24: format tag 1, 16-byte fmt chunk.  F32: tag 3; A-law: tag 6; mu-law: tag 7; these three with an 18-byte
+ * fmt chunk (cbSize 0) and a fact chunk holding n.  An odd data size is followed by one pad byte.  stn_wav_encode is unchanged. */
+int64_t stn_wav_encode_as(int enc, const void* samples, size_t n, int sample_rate, unsigned char* out, size_t cap);
 
 /* Voice-style JSON files {"style_ttl": {"data": [[[..]]], "dims": [1, d1, d2]}, "style_dp": {...}} stacked along dim 0 in the
  * order given, row-major: ttl_out [n][d1][d2], dp_out [n][e1][e2].  dims6 = {n, d1, d2, n, e1, e2} (the first file's dims define

@@ -17,6 +17,29 @@ _DTYPES = {"f32": F32, "fp32": F32, "float32": F32, "bf16": BF16, "f16": F16, "f
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_TANH = 0, 1, 2, 3
 EPI_STORE, EPI_RESID, EPI_STORE_T = 0, 1, 2  # GEMM epilogue modes (stn_op_gemm_ex)
 FFN_VOCODER, FFN_ESTIMATOR, FFN_TEXT = 1, 2, 4  # ConvNeXt stages (ffn_form)
+# sample encodings of a fetch (STN_ENC_*, include/stn.h)
+ENC_F32, ENC_PCM16, ENC_PCM24, ENC_MULAW, ENC_ALAW = 0, 1, 2, 3, 4
+ENCODINGS = {"f32": ENC_F32, "pcm16": ENC_PCM16, "pcm24": ENC_PCM24, "mulaw": ENC_MULAW, "alaw": ENC_ALAW}
+ENCODING_NAMES = {v: k for k, v in ENCODINGS.items()}
+ENCODING_BYTES = {ENC_F32: 4, ENC_PCM16: 2, ENC_PCM24: 3, ENC_MULAW: 1, ENC_ALAW: 1}
+ZERO_CODEWORD = {ENC_F32: 0, ENC_PCM16: 0, ENC_PCM24: 0, ENC_MULAW: 0xFF, ENC_ALAW: 0xD5}  # silence / padding (0x00 is mu-law's -full scale)
+
+
+def encoding_id(enc):
+    """An encoding name ("f32", "pcm16", "pcm24", "mulaw", "alaw") or STN_ENC_* value -> the value."""
+    if isinstance(enc, str) and enc.lower() in ENCODINGS:
+        return ENCODINGS[enc.lower()]
+    if not isinstance(enc, str) and int(enc) in ENCODING_NAMES:
+        return int(enc)
+    raise ValueError(f"unknown sample encoding {enc!r}: one of {', '.join(ENCODINGS)}")
+
+
+def encoded_empty(enc, rows, W):
+    """An uninitialised array for rows x W samples of an encoding: float32 / int16 / uint8 [rows, W], uint8 [rows, W, 3] for PCM24."""
+    e = encoding_id(enc)
+    if e == ENC_PCM24:
+        return np.empty((rows, W, 3), np.uint8)
+    return np.empty((rows, W), {ENC_F32: np.float32, ENC_PCM16: np.int16}.get(e, np.uint8))
 
 
 class StnError(RuntimeError):
@@ -220,6 +243,14 @@ def load():
     L.stn_op_loudness.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp]
     L.stn_kweighting_filter.argtypes = [ci, _f64p, _f64p, _f64p, _f64p]
     L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
+    L.stn_encoding_bytes.argtypes = [ci]
+    L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
+    L.stn_batch_copy_encoded_device.argtypes = [vp, ci, vp, ctypes.c_int64]
+    L.stn_batch_fetch_encoded_begin.argtypes = [vp, ci, ci]
+    L.stn_batch_fetch_encoded_end.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), vp]
+    L.stn_op_encode.argtypes = [vp, ci, ci, ci, _f32p, vp]
+    L.stn_group_set_encoding.argtypes = [vp, ci]
+    L.stn_group_fetch_encoded.argtypes = [vp, vp, ctypes.c_size_t, vp]
     L.stn_group_last_shards.argtypes = [vp, _i32p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
     _LIB = L
     return L
@@ -236,8 +267,9 @@ def group_deal(lengths, n_ranks):
 
 
 class Group:
-    """n devices in one process (include/stn_group.h): one engine per device, utterances dealt by length, 16-bit PCM gathered into the
-    first device (RCCL when the devices are distinct; the same ordinal repeated is a rehearsal on one GPU)."""
+    """n devices in one process (include/stn_group.h): one engine per device, utterances dealt by length, 16-bit PCM (or the encoding
+    set_encoding chose) gathered into the first device (RCCL when the devices are distinct; the same ordinal repeated is a rehearsal on
+    one GPU)."""
 
     def __init__(self, devices, dtype="bf16"):
         self._lib = load()
@@ -249,6 +281,7 @@ class Group:
             self._g = None
             raise StnError(rc, self._lib.stn_group_last_error(None).decode())
         self.n = len(devices)
+        self._enc = ENC_PCM16
 
     def close(self):
         if getattr(self, "_g", None):
@@ -276,15 +309,22 @@ class Group:
         self._ck(self._lib.stn_group_load_dir(self._g, onnx_dir.encode()))
 
     def synthesize(self, text_ids, text_mask, style_ttl, style_dp, total_step=5, speed=1.05, duration_override=None, noise_seed=1234):
-        """-> (pcm [B, W] int16 in caller order, duration [B])"""
+        """-> (samples [B, W] in caller order in the gather's encoding: int16 PCM by default (encoded_empty's dtypes), duration [B])"""
         B, Lt = text_ids.shape
         _d, dptr = _opt(duration_override, np.float32)
         W = ctypes.c_int64()
+        enc = self._enc
         self._ck(self._lib.stn_group_synthesize(self._g, B, Lt, _c(text_ids, np.int64), _c(text_mask, np.float32), _c(style_ttl, np.float32),
                                                 _c(style_dp, np.float32), total_step, speed, dptr, noise_seed, ctypes.byref(W)))
-        pcm, dur = np.empty((B, W.value), np.int16), np.empty(B, np.float32)
-        self._ck(self._lib.stn_group_fetch_pcm16(self._g, pcm.ctypes.data, pcm.size, dur.ctypes.data))
-        return pcm, dur
+        out, dur = encoded_empty(enc, B, W.value), np.empty(B, np.float32)
+        self._ck(self._lib.stn_group_fetch_encoded(self._g, out.ctypes.data, out.nbytes, dur.ctypes.data))
+        return out, dur
+
+    def set_encoding(self, enc):
+        """Sample encoding of the next synthesize's gather (a name or ENC_*; "pcm16" is the default)."""
+        e = encoding_id(enc)
+        self._ck(self._lib.stn_group_set_encoding(self._g, e))
+        self._enc = e
 
     def set_output_rate(self, hz):
         """Output rate of every rank (0 or None = the model's rate): the gathered PCM is then at that rate."""
@@ -410,6 +450,7 @@ class Engine:
         self.dtype = _DTYPES[dtype]
         self.device = device
         self.arch = None
+        self._slot_enc = {}  # encoding each fetch slot was begun with
 
     def close(self):
         if getattr(self, "_h", None):
@@ -612,9 +653,50 @@ class Engine:
                                            peak.ctypes.data))
         return lufs, peak
 
+    def op_encode(self, x, enc):
+        """rows x W fp32 -> rows x W samples of an encoding on the GPU (the fetch's store kernel without a gain; encoded_empty's dtypes)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        e = encoding_id(enc)
+        out = encoded_empty(e, rows, W)
+        self._ck(self._lib.stn_op_encode(self._h, e, rows, W, x, out.ctypes.data))
+        return out
+
+    def batch_fetch_encoded(self, enc):
+        """The finished batch in an encoding -> (samples [B, W] (encoded_empty's dtypes), duration [B])."""
+        e = encoding_id(enc)
+        B, _, W = self.batch_dims()
+        out, dur = encoded_empty(e, B, W), np.empty(B, np.float32)
+        self._ck(self._lib.stn_batch_fetch_encoded(self._h, e, out.ctypes.data, out.nbytes, dur.ctypes.data))
+        return out, dur
+
+    def fetch_encoded_begin(self, slot, enc):
+        """fetch_pcm16_begin in an encoding."""
+        e = encoding_id(enc)
+        self._ck(self._lib.stn_batch_fetch_encoded_begin(self._h, int(slot), e))
+        self._slot_enc[int(slot)] = e
+
+    def fetch_encoded_end(self, slot, copy=True):
+        """Wait for the slot's copy -> (samples [B, W] in the slot's encoding, duration [B]); copy=False: a view of the pinned buffer."""
+        B, W = ctypes.c_int(), ctypes.c_int64()
+        self._ck(self._lib.stn_batch_fetch_slot_dims(self._h, int(slot), ctypes.byref(B), ctypes.byref(W)))
+        ptr, n = ctypes.c_void_p(), ctypes.c_size_t()
+        dur = np.empty(B.value, np.float32)
+        self._ck(self._lib.stn_batch_fetch_encoded_end(self._h, int(slot), ctypes.byref(ptr), ctypes.byref(n), dur.ctypes.data))
+        like = encoded_empty(self._slot_enc.get(int(slot), ENC_PCM16), B.value, W.value)
+        assert like.nbytes == n.value, (like.shape, n.value)
+        raw = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(n.value,))
+        arr = raw.view(like.dtype).reshape(like.shape)
+        return (arr.copy() if copy else arr), dur
+
+    def batch_copy_encoded_device(self, enc, dst_ptr, dst_stride):
+        """Device->device copy of the finished batch in an encoding; dst_stride in samples."""
+        self._ck(self._lib.stn_batch_copy_encoded_device(self._h, encoding_id(enc), dst_ptr, dst_stride))
+
     def fetch_pcm16_begin(self, slot):
         """Start the PCM conversion + device->host copy of the finished batch on `slot` (0/1); returns at once."""
         self._ck(self._lib.stn_batch_fetch_pcm16_begin(self._h, int(slot)))
+        self._slot_enc[int(slot)] = ENC_PCM16
 
     def fetch_pcm16_end(self, slot, copy=True):
         """Wait for the slot's copy -> (pcm [B, W] int16, duration [B]).  copy=False returns a view of the handle's pinned buffer

@@ -387,6 +387,24 @@ int stn_set_stream(stn_handle* h, void* hip_stream) { STN_TRY(h, { h->eng->set_s
 int stn_batch_copy_pcm16_device(stn_handle* h, void* dst, int64_t stride) {
     STN_TRY(h, { need(dst != nullptr, "dst is null"); h->eng->batch_copy_pcm16_device(static_cast<int16_t*>(dst), stride); })
 }
+static_assert(STN_ENC_F32 == stn::ENC_F32 && STN_ENC_PCM16 == stn::ENC_PCM16 && STN_ENC_PCM24 == stn::ENC_PCM24 && STN_ENC_MULAW == stn::ENC_MULAW &&
+              STN_ENC_ALAW == stn::ENC_ALAW, "include/stn.h and kernels.hpp disagree on the encodings");
+int stn_encoding_bytes(int enc) { return stn::enc_bytes(enc); }
+int stn_batch_fetch_encoded(stn_handle* h, int enc, void* dst, size_t cap, float* duration) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_encoded(enc, dst, cap, duration); })
+}
+int stn_batch_copy_encoded_device(stn_handle* h, int enc, void* dst, int64_t stride) {
+    STN_TRY(h, { need(dst != nullptr, "dst is null"); h->eng->batch_copy_encoded_device(enc, dst, stride); })
+}
+int stn_batch_fetch_encoded_begin(stn_handle* h, int slot, int enc) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_encoded_begin(slot, enc); })
+}
+int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size_t* n_bytes, float* duration) {
+    STN_TRY(h, { h->eng->batch_fetch_encoded_end(slot, data, n_bytes, duration); })
+}
+int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void* y) {
+    STN_TRY(h, { need(rows > 0 && W > 0 && x && y, "stn_op_encode: bad argument (rows >= 1, W >= 1, x and y)"); h->eng->op_encode(enc, rows, W, x, y); })
+}
 int stn_batch_copy_wav_device(stn_handle* h, void* dst, int64_t stride) {
     STN_TRY(h, { need(dst != nullptr, "dst is null"); h->eng->batch_copy_wav_device(static_cast<float*>(dst), stride); })
 }

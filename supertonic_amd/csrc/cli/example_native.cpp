@@ -3,7 +3,8 @@
 // plus engine flags: --device N, --gpus N (deal the batch over N devices: include/stn_group.h), --devices a,b,.. (explicit ordinals),
 // --dtype {fp32,bf16,fp16}, --seed S (0 = unseeded noise, like the reference), --sample-rate HZ (WAV files at HZ, resampled on the GPU;
 // absent: the model's rate), --loudness LUFS (every utterance normalized to that BS.1770-4 integrated loudness on the GPU; absent: off),
-// --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1).
+// --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1), --encoding {pcm16,pcm24,f32,mulaw,alaw} (sample format
+// of the WAV files, encoded on the GPU; default pcm16, writeWavFile's files).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -62,6 +63,11 @@ int main(int argc, char* argv[]) {
         else if (a == "--sample-rate" && more) opts.output_rate = std::atoi(argv[++i]);  // Hz of the WAV files (resampled on the GPU); absent: the model's
         else if (a == "--loudness" && more) opts.loudness_lufs = std::strtof(argv[++i], nullptr);  // LUFS of every utterance (BS.1770-4, on the GPU); absent: off
         else if (a == "--peak-ceiling" && more) opts.loudness_ceiling_dbfs = std::strtof(argv[++i], nullptr);  // dBFS cap of the loudness gain (default -1)
+        else if (a == "--encoding" && more) {  // sample format of the WAV files (encoded on the GPU); default pcm16
+            const std::string e = argv[++i];
+            opts.encoding = e == "pcm16" ? STN_ENC_PCM16 : e == "pcm24" ? STN_ENC_PCM24 : e == "f32" ? STN_ENC_F32 : e == "mulaw" ? STN_ENC_MULAW : e == "alaw" ? STN_ENC_ALAW : -1;
+            if (opts.encoding < 0) { std::cerr << "Error: --encoding " << e << ": one of pcm16, pcm24, f32, mulaw, alaw\n"; return 1; }
+        }
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (voice_style.size() != text.size()) {
@@ -92,13 +98,18 @@ int main(int argc, char* argv[]) {
                 return batch ? tts->batch(text, lang, style, total_step, speed) : tts->call(text[0], lang[0], style, total_step, speed);
             });
             const int sr = tts->getSampleRate();
-            const size_t per = result.wav.size() / (size_t)bsz;
+            const size_t eb = result.wav.empty() ? (size_t)stn_encoding_bytes(result.encoding) : 0;  // 0: the float waveform
+            const size_t per = (eb ? result.encoded.size() / eb : result.wav.size()) / (size_t)bsz;
             for (int b = 0; b < bsz; ++b) {
                 const std::string fname = sanitizeFilename(text[b], 20) + "_" + std::to_string(n + 1) + ".wav";
                 size_t wav_len = (size_t)(int)((float)sr * result.duration[b]);
                 if (wav_len > per) wav_len = per;
-                std::vector<float> out(result.wav.begin() + (long)(b * per), result.wav.begin() + (long)(b * per + wav_len));
-                writeWavFile(save_dir + "/" + fname, out, sr);
+                if (eb) {
+                    writeWavFileEncoded(save_dir + "/" + fname, result.encoding, result.encoded.data() + b * per * eb, wav_len, sr);
+                } else {
+                    std::vector<float> out(result.wav.begin() + (long)(b * per), result.wav.begin() + (long)(b * per + wav_len));
+                    writeWavFile(save_dir + "/" + fname, out, sr);
+                }
                 std::cout << "Saved: " << save_dir << "/" << fname << "\n";
             }
         }

@@ -183,7 +183,7 @@ Engine::~Engine() {
     rs_release();
     lo_release();
     if (out_f32_) (void)hipFree(out_f32_);
-    if (out_pcm_) (void)hipFree(out_pcm_);
+    if (out_enc_) (void)hipFree(out_enc_);
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);
         if (f.dev) (void)hipFree(f.dev);

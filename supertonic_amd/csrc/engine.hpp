@@ -252,6 +252,14 @@ class Engine {
     void batch_copy_wav_device(float* dst, int64_t dst_stride);
     // the finished batch as int16 PCM (writeWavFile's conversion) straight into a device buffer, rows dst_stride apart
     void batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride);
+    // ---- sample encodings (OutEnc, kernels.hpp): every fetch path above in any encoding, through the one output
+    // stage.  The fp32 and PCM16 calls above are the ENC_F32 and ENC_PCM16 cases of these.
+    void batch_fetch_encoded(int enc, void* dst, size_t capacity_bytes, float* duration);
+    void batch_fetch_encoded_begin(int slot, int enc);
+    void batch_fetch_encoded_end(int slot, const void** data, size_t* n_bytes, float* duration);
+    void batch_copy_encoded_device(int enc, void* dst, int64_t dst_stride);  // dst_stride in samples
+    // rows x W fp32 (host) -> rows x W samples of encoding enc (host, enc_bytes(enc) each): the store kernel without a gain
+    void op_encode(int enc, int rows, int W, const float* x, void* y);
 
     // ---- output rate (engine_resample.cpp): 0 or the model's rate = off (the default; every fetch path is then exactly the
     // native one).  On, every fetch path resamples the finished waveform on the handle's stream before its copy (kernels_resample.hip);
@@ -467,14 +475,15 @@ class Engine {
     bool pin_valid_ = false;
     unsigned long long* seed_dev_ = nullptr;
     int final_xt_ = 0;
-    struct FetchSlot { int16_t* dev = nullptr; int16_t* pin = nullptr; size_t cap = 0, n = 0; hipEvent_t ready = nullptr, done = nullptr; bool busy = false; std::vector<float> dur; };
+    // a pipelined fetch's buffers (bytes; n samples of encoding enc)
+    struct FetchSlot { unsigned char* dev = nullptr; unsigned char* pin = nullptr; size_t cap = 0, n = 0; int enc = ENC_PCM16; hipEvent_t ready = nullptr, done = nullptr; bool busy = false; std::vector<float> dur; };
     FetchSlot fetch_[2];
     int out_hz_ = 0;                  // requested output rate (0: the model's)
     ResampleTable rs_, op_rs_;        // filter tables of the output rate and of op_resample (device copies owned here)
     void rs_prepare(ResampleTable& t, int in_hz, int out_hz);
     const ResampleTable& rs_table();
     void rs_release();
-    void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride);
+    void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, int enc, void* y, int64_t dst_stride);
     bool lo_on_ = false;
     float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
     LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
@@ -490,16 +499,16 @@ class Engine {
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
     float* lo_batch(const float* x, int64_t Wo, bool on);
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
-    // fp32 or PCM); every fetch path runs it into a device destination of rows `stride` apart (one of f32 / pcm)
-    struct OutRows { float* f32 = nullptr; int16_t* pcm = nullptr; int64_t stride = 0; };
+    // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
+    struct OutRows { void* dst = nullptr; int enc = ENC_F32; int64_t stride = 0; };
     void enqueue_output(const OutRows& o);
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
     bool out_native() const;             // neither resampled nor normalized: the delivered fp32 rows are b.wav itself
     const float* out_source(int64_t Wo);  // the finished batch at the output rate: b.wav, or resampled into the fp32 scratch
     float* out_f32_buf(size_t n);
-    int16_t* out_pcm_buf(size_t n);
+    unsigned char* out_enc_buf(size_t bytes);
     float* out_f32_ = nullptr; size_t out_f32_cap_ = 0;  // fetch scratch (grow-only, outside the graph key)
-    int16_t* out_pcm_ = nullptr; size_t out_pcm_cap_ = 0;
+    unsigned char* out_enc_ = nullptr; size_t out_enc_cap_ = 0;  // (bytes)
     hipStream_t copy_s_ = nullptr;
     bool prof_on_ = false;
     std::vector<ProfSpan> spans_;

@@ -425,7 +425,7 @@ static T* out_grow(Engine& e, T*& p, size_t& cap, size_t n) {
     return p;
 }
 float* Engine::out_f32_buf(size_t n) { return out_grow(*this, out_f32_, out_f32_cap_, n); }
-int16_t* Engine::out_pcm_buf(size_t n) { return out_grow(*this, out_pcm_, out_pcm_cap_, n); }
+unsigned char* Engine::out_enc_buf(size_t bytes) { return out_grow(*this, out_enc_, out_enc_cap_, bytes); }
 
 int64_t Engine::out_row_len() {
     STN_HIP(hipSetDevice(device_));
@@ -440,33 +440,44 @@ const float* Engine::out_source(int64_t Wo) {
     const Batch& b = bt_;
     if (!resample_on()) return b.wav;
     float* d = out_f32_buf((size_t)b.B * Wo);
-    resample_enqueue(rs_table(), b.wav, b.B, (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, d, nullptr, Wo);
+    resample_enqueue(rs_table(), b.wav, b.B, (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, ENC_F32, d, Wo);
     return d;
 }
 
-// Loudness on: the rows at the output rate are measured, then stored with the gain.  Off: resampled straight into the destination
-// when a rate is set; at the native rate converted to PCM, or copied.
+static int need_enc(int enc) {
+    const int eb = enc_bytes(enc);
+    if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
+    return eb;
+}
+
+// Loudness on: the rows at the output rate are measured, then stored with the gain in the encoding.  Off: resampled straight into the
+// destination in the encoding when a rate is set; at the native rate encoded by the store kernel, or (fp32) copied.
 void Engine::enqueue_output(const OutRows& o) {
     const Batch& b = bt_;
+    const int eb = need_enc(o.enc);
     const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (o.stride < Wo)
         throw std::invalid_argument(resample_on() ? "dst_stride smaller than the waveform length at the output rate" : "dst_stride smaller than the waveform length");
     if (loudness_on()) {
-        const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.f32 alike: scaled in place)
+        const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
         const char* saved = stage_;
         stage_ = "out";
-        if (prof_on_) prof_begin("loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (o.pcm ? 6 : 8));
-        if (o.pcm) launch_store_rows(s_, src, b.B, Wo, g, o.pcm, o.stride);
-        else launch_store_rows(s_, src, b.B, Wo, g, o.f32, o.stride);
+        if (prof_on_) prof_begin("loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+        launch_store_rows(s_, src, b.B, Wo, g, o.enc, o.dst, o.stride);
         if (prof_on_) prof_end();
         stage_ = saved;
     } else if (resample_on()) {
-        resample_enqueue(rs_table(), b.wav, b.B, W, o.f32, o.pcm, o.stride);
-    } else if (o.pcm) {
-        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.pcm, o.stride);
+        resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
+    } else if (o.enc != ENC_F32) {
+        const char* saved = stage_;
+        stage_ = "out";
+        if (prof_on_) prof_begin("store_rows", (double)b.B * W, (double)b.B * W * (4 + eb));
+        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.enc, o.dst, o.stride);
+        if (prof_on_) prof_end();
+        stage_ = saved;
     } else {
-        STN_HIP(hipMemcpy2DAsync(o.f32, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
+        STN_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
     }
     STN_HIP(hipGetLastError());
 }
@@ -477,67 +488,95 @@ static void copy_durations(const std::vector<float>& dur, float* duration) {
 
 void Engine::batch_fetch(float* wav, size_t wav_capacity, float* duration) {
     if (wav) {
-        const int64_t Wo = out_row_len();
-        const size_t n = (size_t)bt_.B * Wo;
+        const size_t n = (size_t)bt_.B * out_row_len();
         if (wav_capacity < n) throw std::runtime_error("wav buffer too small: need " + std::to_string(n) + " floats");
-        const float* src = bt_.wav;  // at the native rate the batch's own rows: no device copy
-        if (!out_native()) {
-            float* d = out_f32_buf(n);
-            enqueue_output({d, nullptr, Wo});
+    }
+    batch_fetch_encoded(ENC_F32, wav, wav_capacity * 4, duration);
+}
+void Engine::batch_fetch_pcm16(int16_t* pcm, size_t capacity, float* duration) {
+    const size_t n = (size_t)bt_.B * out_row_len();
+    if (capacity < n) throw std::runtime_error("pcm buffer too small: need " + std::to_string(n) + " samples");
+    batch_fetch_encoded(ENC_PCM16, pcm, capacity * 2, duration);
+}
+void Engine::batch_fetch_encoded(int enc, void* dst, size_t capacity_bytes, float* duration) {
+    const int eb = need_enc(enc);
+    if (dst) {
+        const int64_t Wo = out_row_len();
+        const size_t n = (size_t)bt_.B * Wo, bytes = n * eb;
+        if (capacity_bytes < bytes) throw std::runtime_error("buffer too small: need " + std::to_string(bytes) + " bytes");
+        const void* src = bt_.wav;  // fp32 at the native rate: the batch's own rows, no device copy
+        if (enc != ENC_F32 || !out_native()) {
+            void* d = enc == ENC_F32 ? static_cast<void*>(out_f32_buf(n)) : static_cast<void*>(out_enc_buf(bytes));
+            enqueue_output({d, enc, Wo});
             src = d;
         }
-        STN_HIP(hipMemcpyAsync(wav, src, n * 4, hipMemcpyDeviceToHost, s_));
+        STN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_));
     }
     sync();
     copy_durations(reported_dur_, duration);
 }
-void Engine::batch_fetch_pcm16(int16_t* pcm, size_t capacity, float* duration) {
-    const int64_t Wo = out_row_len();
-    const size_t n = (size_t)bt_.B * Wo;
-    if (capacity < n) throw std::runtime_error("pcm buffer too small: need " + std::to_string(n) + " samples");
-    int16_t* d = out_pcm_buf(n);
-    enqueue_output({nullptr, d, Wo});
-    STN_HIP(hipMemcpyAsync(pcm, d, n * 2, hipMemcpyDeviceToHost, s_));
-    sync();
-    copy_durations(reported_dur_, duration);
-}
-void Engine::batch_fetch_pcm16_begin(int slot) {
+void Engine::batch_fetch_encoded_begin(int slot, int enc) {
     if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
+    const int eb = need_enc(enc);
     const int64_t Wo = out_row_len();
-    const size_t nw = (size_t)bt_.B * Wo;
+    const size_t nw = (size_t)bt_.B * Wo, bytes = nw * eb;
     FetchSlot& f = fetch_[slot];
     if (!copy_s_) STN_HIP(hipStreamCreateWithFlags(&copy_s_, hipStreamNonBlocking));
     if (!f.ready) { STN_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming)); STN_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming)); }
     if (f.busy) STN_HIP(hipEventSynchronize(f.done));  // the slot's previous copy (two batches ago) must be out before it is refilled
-    if (nw > f.cap) {
+    if (bytes > f.cap) {
         if (f.dev) (void)hipFree(f.dev);
         if (f.pin) (void)hipHostFree(f.pin);
-        f.dev = nullptr; f.pin = nullptr;
-        const size_t cap = nw + nw / 4;
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&f.dev), cap * sizeof(int16_t)));
-        STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap * sizeof(int16_t), hipHostMallocDefault));
+        f.dev = nullptr; f.pin = nullptr; f.cap = 0;
+        const size_t cap = bytes + bytes / 4;
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&f.dev), cap));
+        STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap, hipHostMallocDefault));
         f.cap = cap;
     }
-    enqueue_output({nullptr, f.dev, Wo});
+    enqueue_output({f.dev, enc, Wo});
     STN_HIP(hipEventRecord(f.ready, s_));
     STN_HIP(hipStreamWaitEvent(copy_s_, f.ready, 0));
-    STN_HIP(hipMemcpyAsync(f.pin, f.dev, nw * sizeof(int16_t), hipMemcpyDeviceToHost, copy_s_));
+    STN_HIP(hipMemcpyAsync(f.pin, f.dev, bytes, hipMemcpyDeviceToHost, copy_s_));
     STN_HIP(hipEventRecord(f.done, copy_s_));
     f.n = nw;
+    f.enc = enc;
     f.dur = reported_dur_;
     f.busy = true;
 }
-void Engine::batch_fetch_pcm16_end(int slot, const int16_t** pcm, size_t* n, float* duration) {
+void Engine::batch_fetch_encoded_end(int slot, const void** data, size_t* n_bytes, float* duration) {
     if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
     FetchSlot& f = fetch_[slot];
     if (!f.busy) throw std::runtime_error("no fetch in flight on this slot");
     STN_HIP(hipEventSynchronize(f.done));
-    if (pcm) *pcm = f.pin;
-    if (n) *n = f.n;
+    if (data) *data = f.pin;
+    if (n_bytes) *n_bytes = f.n * enc_bytes(f.enc);
     copy_durations(f.dur, duration);
 }
-void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) { enqueue_output({dst, nullptr, dst_stride}); }
-void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) { enqueue_output({nullptr, dst, dst_stride}); }
+void Engine::batch_fetch_pcm16_begin(int slot) { batch_fetch_encoded_begin(slot, ENC_PCM16); }
+void Engine::batch_fetch_pcm16_end(int slot, const int16_t** pcm, size_t* n, float* duration) {
+    if (slot >= 0 && slot <= 1 && fetch_[slot].busy && fetch_[slot].enc != ENC_PCM16)
+        throw std::runtime_error("the fetch on this slot is not 16-bit PCM (use stn_batch_fetch_encoded_end)");
+    const void* d = nullptr;
+    batch_fetch_encoded_end(slot, &d, nullptr, duration);
+    if (pcm) *pcm = static_cast<const int16_t*>(d);
+    if (n) *n = fetch_[slot].n;
+}
+void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) { enqueue_output({dst, ENC_F32, dst_stride}); }
+void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) { enqueue_output({dst, ENC_PCM16, dst_stride}); }
+void Engine::batch_copy_encoded_device(int enc, void* dst, int64_t dst_stride) { enqueue_output({dst, enc, dst_stride}); }
+void Engine::op_encode(int enc, int rows, int W, const float* x, void* y) {
+    const int eb = need_enc(enc);
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const size_t n = (size_t)rows * W;
+    float* dx = static_cast<float*>(ar_.alloc(n * 4));
+    void* dy = ar_.alloc(n * eb);
+    STN_HIP(hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, s_));
+    launch_store_rows(s_, dx, rows, W, nullptr, enc, dy, W);
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(y, dy, n * eb, hipMemcpyDeviceToHost, s_));
+    sync();
+}
 void Engine::batch_fetch_latent(float* latent) {
     Batch& b = bt_;
     const size_t nx = (size_t)b.B * a_.latent_dim * a_.chunk_compress_factor * b.L;

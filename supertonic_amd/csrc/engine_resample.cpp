@@ -110,15 +110,15 @@ int64_t Engine::out_len(int64_t W) const {
     return resample_out_len(W, out_hz_ / g, a_.sample_rate / g);
 }
 
-void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, float* y, int16_t* pcm, int64_t dst_stride) {
+void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, int enc, void* y, int64_t dst_stride) {
+    static const char* const names[] = {"resample", "resample_pcm16", "resample_pcm24", "resample_mulaw", "resample_alaw"};
     const char* saved = stage_;
     stage_ = "out";
     if (prof_on_) {
         const double n_out = (double)rows * resample_out_len(W, t.P, t.Q);
-        prof_begin(pcm ? "resample_pcm16" : "resample", 2.0 * n_out * t.T, (double)rows * W * 4 + n_out * (pcm ? 2 : 4));
+        prof_begin(names[enc >= ENC_F32 && enc <= ENC_ALAW ? enc : 0], 2.0 * n_out * t.T, (double)rows * W * 4 + n_out * enc_bytes(enc));
     }
-    if (pcm) launch_resample_pcm16(s_, x, rows, W, t, pcm, dst_stride);
-    else launch_resample(s_, x, rows, W, t, y, dst_stride);
+    launch_resample(s_, x, rows, W, t, enc, y, dst_stride);
     if (prof_on_) prof_end();
     stage_ = saved;
     STN_HIP(hipGetLastError());
@@ -134,12 +134,12 @@ void Engine::op_resample(int in_hz, int out_hz, int rows, int W, const float* x,
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     if (y) {
         float* dy = static_cast<float*>(ar_.alloc(ny * 4));
-        resample_enqueue(op_rs_, dx, rows, W, dy, nullptr, W_out);
+        resample_enqueue(op_rs_, dx, rows, W, ENC_F32, dy, W_out);
         STN_HIP(hipMemcpyAsync(y, dy, ny * 4, hipMemcpyDeviceToHost, s_));
     }
     if (pcm) {
         int16_t* dp = static_cast<int16_t*>(ar_.alloc(ny * 2));
-        resample_enqueue(op_rs_, dx, rows, W, nullptr, dp, W_out);
+        resample_enqueue(op_rs_, dx, rows, W, ENC_PCM16, dp, W_out);
         STN_HIP(hipMemcpyAsync(pcm, dp, ny * 2, hipMemcpyDeviceToHost, s_));
     }
     sync();

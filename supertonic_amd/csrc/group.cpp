@@ -56,7 +56,7 @@ struct Rank {
     stn_handle* h = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;     // rehearsal: the shard's PCM is in `send`
-    void* send = nullptr;          // this rank's PCM block [B_r][W_r] int16, on its device
+    void* send = nullptr;          // this rank's block [B_r][W_r] samples of the gather's encoding, on its device
     size_t send_cap = 0;
     void* recv = nullptr;          // ranks >= 1: the block's landing place on the first device
     size_t recv_cap = 0;
@@ -81,6 +81,8 @@ struct stn_group {
     size_t host_cap = 0;
     int B = 0;
     int64_t W = 0;
+    int enc = STN_ENC_PCM16;       // encoding of the next gather (stn_group_set_encoding)
+    int gathered_enc = STN_ENC_PCM16;  // encoding of the last one
     std::string err;
 };
 
@@ -222,6 +224,12 @@ int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceilin
         const S* p = static_cast<const S*>(a);
         return stn_set_loudness(h, p->on, p->t, p->c); }, &v, 0);
 }
+int stn_group_set_encoding(stn_group* g, int enc) {
+    if (!g) return STN_ERR_INVALID;
+    if (stn_encoding_bytes(enc) == 0) return fail(g, STN_ERR_INVALID, "stn_group_set_encoding: unknown encoding " + std::to_string(enc));
+    g->enc = enc;
+    return STN_OK;
+}
 int stn_group_load_dir(stn_group* g, const char* onnx_dir) {
     return for_all(g, "stn_load_dir", [](stn_handle* h, const void* a, uint64_t) { return stn_load_dir(h, static_cast<const char*>(a)); }, onnx_dir, 0);
 }
@@ -234,6 +242,8 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         return fail(g, STN_ERR_INVALID, "stn_group_synthesize: B, Lt, total_step >= 1, speed > 0 and non-null inputs");
     const int n = (int)g->ranks.size();
     g->B = 0;  // (a failed synthesis leaves nothing to fetch)
+    const int enc = g->enc;
+    const size_t eb = (size_t)stn_encoding_bytes(enc);
     stn_arch a;
     if (stn_get_arch(g->ranks[0].h, &a) != STN_OK) return fail(g, STN_ERR_STATE, std::string("stn_group_synthesize: ") + stn_last_error(g->ranks[0].h));
     const size_t ttl_n = (size_t)a.n_style_ttl * a.d_style_ttl, dp_n = (size_t)a.n_style_dp * a.d_style_dp;
@@ -251,7 +261,7 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         if ((int)k.idx.size() <= row_of[i]) k.idx.resize(row_of[i] + 1);
         k.idx[row_of[i]] = i;
     }
-    // every rank: its shard's inputs (token rows cut to the shard's longest), upload, run, PCM into its send block
+    // every rank: its shard's inputs (token rows cut to the shard's longest), upload, run, encoded samples into its send block
     std::vector<std::thread> th;
     for (int r = 0; r < n; ++r) {
         th.emplace_back([&, r] {
@@ -280,8 +290,8 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
                 if (k.rc == STN_OK) k.rc = stn_batch_dims(k.h, &Bd, &Ld, &Wd);
                 if (k.rc != STN_OK) { k.err = stn_last_error(k.h); return; }
                 k.B = Bd; k.W = Wd;
-                grow(&k.send, &k.send_cap, (size_t)Bd * Wd * sizeof(int16_t));
-                k.rc = stn_batch_copy_pcm16_device(k.h, k.send, Wd);  // enqueued on the rank's stream, behind the vocoder
+                grow(&k.send, &k.send_cap, (size_t)Bd * Wd * eb);
+                k.rc = stn_batch_copy_encoded_device(k.h, enc, k.send, Wd);  // enqueued on the rank's stream, behind the vocoder
                 if (k.rc != STN_OK) { k.err = stn_last_error(k.h); return; }
                 HIPG(hipEventRecord(k.done, k.stream));
             } catch (const std::exception& e) { k.rc = STN_ERR_DEVICE; k.err = e.what(); }
@@ -295,11 +305,11 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         Rank& root = g->ranks[0];
         HIPG(hipSetDevice(root.device));
         const int first_peer = g->self_rccl ? 0 : 1;
-        for (int r = first_peer; r < n; ++r) grow(&g->ranks[r].recv, &g->ranks[r].recv_cap, (size_t)g->ranks[r].B * g->ranks[r].W * sizeof(int16_t));
+        for (int r = first_peer; r < n; ++r) grow(&g->ranks[r].recv, &g->ranks[r].recv_cap, (size_t)g->ranks[r].B * g->ranks[r].W * eb);
         if (g->rccl) {
             ncclResult_t nr = g->nccl.GroupStart();
             for (int r = first_peer; r < n && nr == ncclSuccess; ++r) {
-                const size_t bytes = (size_t)g->ranks[r].B * g->ranks[r].W * sizeof(int16_t);
+                const size_t bytes = (size_t)g->ranks[r].B * g->ranks[r].W * eb;
                 if (!bytes) continue;
                 nr = g->nccl.Send(g->ranks[r].send, bytes, ncclInt8, 0, g->comms[r], g->ranks[r].stream);      // rank r -> 0, on r's stream
                 if (nr == ncclSuccess) nr = g->nccl.Recv(g->ranks[r].recv, bytes, ncclInt8, r, g->comms[0], root.stream);  // 0 <- r, on the root's
@@ -309,7 +319,7 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
             if (nr != ncclSuccess) return fail(g, STN_ERR_DEVICE, std::string("stn_group_synthesize: RCCL gather: ") + g->nccl.GetErrorString(nr));
         } else {
             for (int r = 1; r < n; ++r) {  // rehearsal: the ranks share the root's GPU
-                const size_t bytes = (size_t)g->ranks[r].B * g->ranks[r].W * sizeof(int16_t);
+                const size_t bytes = (size_t)g->ranks[r].B * g->ranks[r].W * eb;
                 if (!bytes) continue;
                 HIPG(hipStreamWaitEvent(root.stream, g->ranks[r].done, 0));
                 HIPG(hipMemcpyAsync(g->ranks[r].recv, g->ranks[r].send, bytes, hipMemcpyDeviceToDevice, root.stream));
@@ -317,7 +327,7 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         }
         // ---- blocks -> pinned host memory, back to back; durations through the handles ---------------------------------------------
         size_t total = 0;
-        for (Rank& k : g->ranks) total += (size_t)k.B * k.W * sizeof(int16_t);
+        for (Rank& k : g->ranks) total += (size_t)k.B * k.W * eb;
         if (total > g->host_cap) {
             if (g->host_stage) HIPG(hipHostFree(g->host_stage));
             g->host_stage = nullptr; g->host_cap = 0;
@@ -327,7 +337,7 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         size_t off = 0;
         for (int r = 0; r < n; ++r) {
             Rank& k = g->ranks[r];
-            const size_t bytes = (size_t)k.B * k.W * sizeof(int16_t);
+            const size_t bytes = (size_t)k.B * k.W * eb;
             if (bytes) HIPG(hipMemcpyAsync(static_cast<char*>(g->host_stage) + off, r < first_peer ? k.send : k.recv, bytes, hipMemcpyDeviceToHost, root.stream));
             off += bytes;
         }
@@ -339,30 +349,41 @@ int stn_group_synthesize(stn_group* g, int B, int Lt, const int64_t* text_ids, c
         for (int r = 1; r < n; ++r) { HIPG(hipSetDevice(g->ranks[r].device)); HIPG(hipStreamSynchronize(g->ranks[r].stream)); }
     } catch (const std::exception& e) { return fail(g, STN_ERR_DEVICE, std::string("stn_group_synthesize: ") + e.what()); }
     g->B = B;
+    g->gathered_enc = enc;
     g->W = 0;
     for (Rank& k : g->ranks) g->W = std::max(g->W, k.W);
     if (samples_per_utt_out) *samples_per_utt_out = g->W;
     return STN_OK;
 }
 
-int stn_group_fetch_pcm16(stn_group* g, int16_t* pcm, size_t capacity_samples, float* duration) {
+int stn_group_fetch_encoded(stn_group* g, void* dst, size_t capacity_bytes, float* duration) {
     if (!g) return STN_ERR_INVALID;
-    if (g->B == 0) return fail(g, STN_ERR_STATE, "stn_group_fetch_pcm16: no synthesis to fetch");
-    if (pcm && capacity_samples < (size_t)g->B * g->W) return fail(g, STN_ERR_INVALID, "stn_group_fetch_pcm16: capacity below B * samples_per_utt");
+    if (g->B == 0) return fail(g, STN_ERR_STATE, "stn_group_fetch_encoded: no synthesis to fetch");
+    const size_t eb = (size_t)stn_encoding_bytes(g->gathered_enc);
+    if (dst && capacity_bytes < (size_t)g->B * g->W * eb) return fail(g, STN_ERR_INVALID, "stn_group_fetch_encoded: capacity below B * samples_per_utt * bytes per sample");
+    // padding behind a shorter shard's rows: the encoding's zero codeword (mu-law 0xFF, A-law 0xD5; zero bytes otherwise)
+    const int zero = g->gathered_enc == STN_ENC_MULAW ? 0xFF : g->gathered_enc == STN_ENC_ALAW ? 0xD5 : 0;
     const char* src = static_cast<const char*>(g->host_stage);
     for (Rank& k : g->ranks) {
         for (int j = 0; j < k.B; ++j) {
             const int i = k.idx[j];
-            if (pcm) {
-                int16_t* row = pcm + (size_t)i * g->W;
-                std::memcpy(row, src + (size_t)j * k.W * sizeof(int16_t), (size_t)k.W * sizeof(int16_t));
-                if (k.W < g->W) std::memset(row + k.W, 0, (size_t)(g->W - k.W) * sizeof(int16_t));
+            if (dst) {
+                char* row = static_cast<char*>(dst) + (size_t)i * g->W * eb;
+                std::memcpy(row, src + (size_t)j * k.W * eb, (size_t)k.W * eb);
+                if (k.W < g->W) std::memset(row + k.W * eb, zero, (size_t)(g->W - k.W) * eb);
             }
             if (duration) duration[i] = k.dur[j];
         }
-        src += (size_t)k.B * k.W * sizeof(int16_t);
+        src += (size_t)k.B * k.W * eb;
     }
     return STN_OK;
+}
+int stn_group_fetch_pcm16(stn_group* g, int16_t* pcm, size_t capacity_samples, float* duration) {
+    if (!g) return STN_ERR_INVALID;
+    if (g->B == 0) return fail(g, STN_ERR_STATE, "stn_group_fetch_pcm16: no synthesis to fetch");
+    if (g->gathered_enc != STN_ENC_PCM16) return fail(g, STN_ERR_STATE, "stn_group_fetch_pcm16: the last gather was not 16-bit PCM (stn_group_fetch_encoded)");
+    if (pcm && capacity_samples < (size_t)g->B * g->W) return fail(g, STN_ERR_INVALID, "stn_group_fetch_pcm16: capacity below B * samples_per_utt");
+    return stn_group_fetch_encoded(g, pcm, capacity_samples * sizeof(int16_t), duration);
 }
 
 int stn_group_last_shards(const stn_group* g, int32_t* rows_per_rank, int64_t* samples_per_rank) {

@@ -127,6 +127,15 @@ int64_t stn_wav_encode(const float* audio, size_t n, int sample_rate, unsigned c
     });
 }
 
+int64_t stn_wav_encode_as(int enc, const void* samples, size_t n, int sample_rate, unsigned char* out, size_t cap) {
+    return guarded([&]() -> int64_t {
+        if (!samples && n) throw std::runtime_error("null argument");
+        const auto w = stn::host::wav_bytes_encoded(enc, samples, n, sample_rate);
+        if (out && cap >= w.size()) std::memcpy(out, w.data(), w.size());
+        return (int64_t)w.size();
+    });
+}
+
 int stn_write_wav(const char* path, const float* audio, size_t n, int sample_rate) {
     const int64_t rc = guarded([&]() -> int64_t {
         if (!path || (!audio && n)) throw std::runtime_error("null argument");

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <fstream>
 #include <stdexcept>
+#include <string>
 
 #include "json_min.hpp"
 
@@ -311,6 +312,30 @@ std::vector<unsigned char> wav_bytes(const float* audio, size_t n, int sample_ra
         const float c = std::max(-1.0f, std::min(1.0f, audio[i]));
         put16(44 + 2 * i, (int16_t)(c * 32767));  // truncation toward zero (cpp/helper.cpp:986-987)
     }
+    return w;
+}
+
+// RIFF WAVE of n already-encoded mono samples (encodings as STN_ENC_* of include/stn.h: 0 fp32, 1 int16, 2 24-bit, 3 mu-law, 4 A-law).
+// PCM (tag 1): the 16-byte fmt chunk.  fp32 (tag 3), A-law (6), mu-law (7): an 18-byte fmt chunk (cbSize 0) and a fact chunk with the
+// sample count.  An odd data size is followed by one pad byte (RIFF chunks are word-aligned); the data chunk's size excludes it.
+std::vector<unsigned char> wav_bytes_encoded(int enc, const void* samples, size_t n, int sample_rate) {
+    static const int bytes_of[] = {4, 2, 3, 1, 1}, tag_of[] = {3, 1, 1, 7, 6};
+    if (enc < 0 || enc > 4) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
+    const int bps = bytes_of[enc], tag = tag_of[enc];
+    const bool pcm = tag == 1;
+    const size_t data = n * bps, fmt = pcm ? 16 : 18, pad = data & 1;
+    const size_t total = 12 + 8 + fmt + (pcm ? 0 : 12) + 8 + data + pad;
+    if (total - 8 > 0xFFFFFFFFull) throw std::invalid_argument("WAV data above 4 GiB");
+    std::vector<unsigned char> w(total, 0);
+    auto put32 = [&](size_t off, uint32_t v) { std::memcpy(&w[off], &v, 4); };
+    auto put16 = [&](size_t off, uint16_t v) { std::memcpy(&w[off], &v, 2); };
+    std::memcpy(&w[0], "RIFF", 4); put32(4, (uint32_t)(total - 8)); std::memcpy(&w[8], "WAVEfmt ", 8);
+    put32(16, (uint32_t)fmt); put16(20, (uint16_t)tag); put16(22, 1); put32(24, (uint32_t)sample_rate); put32(28, (uint32_t)(sample_rate * bps));
+    put16(32, (uint16_t)bps); put16(34, (uint16_t)(8 * bps));
+    size_t off = 20 + fmt;  // (cbSize, when present, stays 0)
+    if (!pcm) { std::memcpy(&w[off], "fact", 4); put32(off + 4, 4); put32(off + 8, (uint32_t)n); off += 12; }
+    std::memcpy(&w[off], "data", 4); put32(off + 4, (uint32_t)data);
+    if (data) std::memcpy(&w[off + 8], samples, data);
     return w;
 }
 

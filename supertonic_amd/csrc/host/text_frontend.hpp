@@ -55,6 +55,7 @@ std::string sanitize_filename(const std::string& text, int max_len);
 
 // 16-bit PCM mono RIFF; sample = int16(clamp(x,-1,1) * 32767) truncated toward zero.
 std::vector<unsigned char> wav_bytes(const float* audio, size_t n, int sample_rate);
+std::vector<unsigned char> wav_bytes_encoded(int enc, const void* samples, size_t n, int sample_rate);
 void write_wav_file(const std::string& filename, const std::vector<float>& audio, int sample_rate);
 
 }  // namespace host

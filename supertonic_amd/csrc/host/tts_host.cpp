@@ -1,6 +1,7 @@
 #include "tts_host.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <numeric>
 #include <random>
@@ -45,11 +46,15 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
         if (stn_group_synthesize(grp_, bsz, tb.Lt, tb.ids.data(), mask.data(), style.getTtlData().data(), style.getDpData().data(), total_step, speed,
                                  nullptr, seed, &W) != STN_OK)
             throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(grp_));
-        std::vector<int16_t> pcm((size_t)bsz * (size_t)W);
         SynthesisResult r;
         r.duration.resize(bsz);
-        if (stn_group_fetch_pcm16(grp_, pcm.data(), pcm.size(), r.duration.data()) != STN_OK)
+        r.encoding = enc_;
+        std::vector<unsigned char> data((size_t)bsz * (size_t)W * stn_encoding_bytes(enc_));
+        if (stn_group_fetch_encoded(grp_, data.data(), data.size(), r.duration.data()) != STN_OK)
             throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(grp_));
+        if (enc_ != STN_ENC_PCM16) { r.encoded = std::move(data); return r; }
+        std::vector<int16_t> pcm((size_t)bsz * (size_t)W);
+        std::memcpy(pcm.data(), data.data(), data.size());
         r.wav.resize(pcm.size());
         for (size_t i = 0; i < pcm.size(); ++i) r.wav[i] = pcm[i] == 0 ? 0.f : ((float)pcm[i] + (pcm[i] > 0 ? 0.5f : -0.5f)) / 32767.0f;
         return r;
@@ -65,8 +70,14 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
     int64_t W = 0;
     check(h_, stn_batch_dims(h_, &B, &L, &W));
     SynthesisResult r;
-    r.wav.resize((size_t)B * W);
     r.duration.resize(B);
+    r.encoding = enc_;
+    if (enc_ != STN_ENC_PCM16) {
+        r.encoded.resize((size_t)B * W * stn_encoding_bytes(enc_));
+        check(h_, stn_batch_fetch_encoded(h_, enc_, r.encoded.data(), r.encoded.size(), r.duration.data()));
+        return r;
+    }
+    r.wav.resize((size_t)B * W);
     check(h_, stn_batch_fetch(h_, r.wav.data(), r.wav.size(), r.duration.data()));
     return r;
 }
@@ -102,26 +113,38 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
         ~ModeGuard() { for (stn_handle* h : hs) { (void)stn_set_vocoder_mode(h, 0); (void)stn_set_shape_buckets(h, 0); } }
     } guard(h_, grp_);
     const SynthesisResult r = infer(chunks, std::vector<std::string>((size_t)n, lang), rep, total_step, speed);
-    const size_t W = r.wav.size() / (size_t)n;
+    const size_t eb = r.encoding == STN_ENC_PCM16 ? 0 : (size_t)stn_encoding_bytes(r.encoding);  // 0: the float waveform
+    const size_t W = eb ? r.encoded.size() / eb / (size_t)n : r.wav.size() / (size_t)n;
+    // silence in the encoding: its zero codeword (mu-law 0xFF, A-law 0xD5, zero bytes otherwise)
+    const unsigned char zero = r.encoding == STN_ENC_MULAW ? 0xFF : r.encoding == STN_ENC_ALAW ? 0xD5 : 0;
     const int chunk_size = cfgs_.ae.base_chunk_size * cfgs_.ttl.chunk_compress_factor;
     const size_t n_sil = (size_t)(int)(silence_duration * (float)getSampleRate());  // (zeros at the rate of the returned audio)
     const int64_t rg = std::gcd(getSampleRate(), cfgs_.ae.sample_rate), rP = getSampleRate() / rg, rQ = cfgs_.ae.sample_rate / rg;
     SynthesisResult out;
+    out.encoding = r.encoding;
     float dur_cat = 0.f;
     for (int i = 0; i < n; ++i) {
         const LatentGeometry g = latent_geometry({r.duration[(size_t)i]}, cfgs_.ae.sample_rate, cfgs_.ae.base_chunk_size,
                                                  cfgs_.ttl.chunk_compress_factor, cfgs_.ttl.latent_dim);
         const size_t n_i = (size_t)(((int64_t)g.L * chunk_size * rP + rQ - 1) / rQ);  // the wav length the chunk's own run would return
         if (i > 0) {  // untrimmed chunk waves joined by zeros (cpp/helper.cpp:706-715)
-            out.wav.insert(out.wav.end(), n_sil, 0.0f);
+            if (eb) out.encoded.insert(out.encoded.end(), n_sil * eb, zero);
+            else out.wav.insert(out.wav.end(), n_sil, 0.0f);
             dur_cat += r.duration[(size_t)i] + silence_duration;
         } else {
             dur_cat = r.duration[0];
         }
-        out.wav.insert(out.wav.end(), r.wav.begin() + (size_t)i * W, r.wav.begin() + (size_t)i * W + std::min(n_i, W));
+        if (eb) out.encoded.insert(out.encoded.end(), r.encoded.begin() + (size_t)i * W * eb, r.encoded.begin() + ((size_t)i * W + std::min(n_i, W)) * eb);
+        else out.wav.insert(out.wav.end(), r.wav.begin() + (size_t)i * W, r.wav.begin() + (size_t)i * W + std::min(n_i, W));
     }
     out.duration = {dur_cat};
     return out;
+}
+
+void TextToSpeech::setEncoding(int enc) {
+    if (stn_encoding_bytes(enc) == 0) throw std::runtime_error("unknown sample encoding " + std::to_string(enc));
+    if (grp_ && stn_group_set_encoding(grp_, enc) != STN_OK) throw std::runtime_error(std::string("encoding: ") + stn_group_last_error(grp_));
+    enc_ = enc;
 }
 
 TextToSpeech::SynthesisResult TextToSpeech::batch(const std::vector<std::string>& text_list,
@@ -188,6 +211,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);
+        tts->setEncoding(opts.encoding);
         if (synthetic) tts->markSynthetic();
         return tts;
     } catch (...) {

@@ -8,6 +8,7 @@
 #pragma once
 #include <chrono>
 #include <cstdint>
+#include <fstream>
 #include <iomanip>
 #include <iostream>
 #include <limits>
@@ -62,11 +63,15 @@ struct EngineOptions {
                                    // (measured and scaled on the GPU, stn_set_loudness; the WAV files carry the normalized PCM); NaN: off.
                                    // CLI --loudness LUFS
     float loudness_ceiling_dbfs = -1.0f;  // sample-peak ceiling that caps the normalization gain.  CLI --peak-ceiling DBFS
+    int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
+                                   // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
 
 class TextToSpeech {
    public:
-    struct SynthesisResult { std::vector<float> wav; std::vector<float> duration; };
+    // wav: the float waveform [B][W].  With an encoding other than PCM16 (setEncoding) the audio is `encoded` instead: [B][W] samples
+    // of stn_encoding_bytes(encoding) bytes, as the engine's encoded fetch delivers them, and wav is empty.
+    struct SynthesisResult { std::vector<float> wav; std::vector<float> duration; std::vector<unsigned char> encoded; int encoding = STN_ENC_PCM16; };
 
     TextToSpeech(stn_handle* engine, UnicodeProcessor text_processor, const Config& cfgs, uint64_t noise_seed);
     // several devices: the group owns the handles (engine() is rank 0's); batch() / call() deal their utterances over the group
@@ -74,7 +79,8 @@ class TextToSpeech {
     ~TextToSpeech();
     TextToSpeech(const TextToSpeech&) = delete;
 
-    // long-form: chunkText -> one synthesis per chunk -> joined with `silence_duration` of zeros (cpp/helper.cpp:685-723)
+    // long-form: chunkText -> one synthesis per chunk -> joined with `silence_duration` of zeros (cpp/helper.cpp:685-723; the
+    // encoding's zero codeword with an encoding set)
     SynthesisResult call(const std::string& text, const std::string& lang, const Style& style, int total_step,
                          float speed = 1.05f, float silence_duration = 0.3f);
     // batch: one padded batch, no chunking (cpp/helper.cpp:725-734)
@@ -83,6 +89,8 @@ class TextToSpeech {
     // rate of the returned audio: the output rate when one is set, else the model's (cfgs.ae.sample_rate, which keeps sizing the latent)
     int getSampleRate() const { return out_rate_ ? out_rate_ : cfgs_.ae.sample_rate; }
     void setOutputRate(int hz) { out_rate_ = hz == cfgs_.ae.sample_rate ? 0 : hz; }
+    void setEncoding(int enc);  // STN_ENC_*: the encoding of the audio batch() / call() return (and of a group's gather)
+    int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
     bool synthetic() const { return synthetic_; }
@@ -98,6 +106,7 @@ class TextToSpeech {
     uint64_t noise_seed_;
     uint64_t calls_ = 0;
     int out_rate_ = 0;  // 0: the model's rate
+    int enc_ = STN_ENC_PCM16;
     bool synthetic_ = false;
 };
 
@@ -107,6 +116,13 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
 
 inline void writeWavFile(const std::string& filename, const std::vector<float>& audio_data, int sample_rate) {
     write_wav_file(filename, audio_data, sample_rate);
+}
+// already-encoded samples (TextToSpeech::SynthesisResult::encoded) as a WAV file (stn_wav_encode_as's layout)
+inline void writeWavFileEncoded(const std::string& filename, int enc, const unsigned char* samples, size_t n, int sample_rate) {
+    const std::vector<unsigned char> w = wav_bytes_encoded(enc, samples, n, sample_rate);
+    std::ofstream f(filename, std::ios::binary);
+    if (!f.is_open()) throw std::runtime_error("Failed to open file for writing: " + filename);
+    f.write(reinterpret_cast<const char*>(w.data()), (std::streamsize)w.size());
 }
 inline std::vector<std::string> chunkText(const std::string& text, int max_len = 300) { return chunk_text(text, max_len); }
 inline std::string sanitizeFilename(const std::string& text, int max_len) { return sanitize_filename(text, max_len); }

@@ -352,11 +352,17 @@ void launch_half_to_f32(hipStream_t s, int in_dtype, const void* in, int64_t n, 
 // total_step/current_step helper: fill n floats
 void launch_fill(hipStream_t s, float* x, int n, float v);
 void launch_step_counters(hipStream_t s, float* tot /*[steps][B]*/, float* cur /*[steps][B]*/, float* dt /*[B]*/, int B, int steps);
+// Sample encodings of a fetch (the values of STN_ENC_*, include/stn.h) and their bytes per sample.  The rules are
+// the device functions of kernels_dev.hpp (pcm16, pcm24, mulaw8, alaw8, enc_store1).
+enum OutEnc : int { ENC_F32 = 0, ENC_PCM16 = 1, ENC_PCM24 = 2, ENC_MULAW = 3, ENC_ALAW = 4 };
+constexpr int enc_bytes(int enc) {
+    return enc == ENC_F32 ? 4 : enc == ENC_PCM16 ? 2 : enc == ENC_PCM24 ? 3 : (enc == ENC_MULAW || enc == ENC_ALAW) ? 1 : 0;
+}
 // The final store of every fetch (the output stage, engine_batch.cpp): rows x W fp32 (row stride W), times g[row] when g (device [rows])
-// is not null, to y + row * dst_stride (dst_stride >= W) as fp32 or as int16 PCM by writeWavFile's rule (pcm16, kernels_dev.hpp:
-// int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987).  fp32 rows may be stored in place (y == x, dst_stride == W).
-void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride);
-void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* y, int64_t dst_stride);
+// is not null, to y + row * dst_stride samples (dst_stride >= W) in encoding enc: fp32, int16 PCM by writeWavFile's rule (pcm16,
+// kernels_dev.hpp: int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987), 24-bit PCM, or G.711 mu-law / A-law of the
+// 16-bit sample.  fp32 rows may be stored in place (y == x, dst_stride == W).
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride);
 
 // Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
 // out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),
@@ -371,10 +377,9 @@ constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P =
 inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
 // Kaiser-windowed sinc for the pair (host only): fills f (not f.dev).  Empty string on success, else why the pair is refused.
 std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
-// rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride (dst_stride >= W_out): fp32, or int16 PCM by pcm16 (the PCM
+// rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride samples (dst_stride >= W_out) in encoding enc (the encoded
 // bytes are those of the fp32 output followed by launch_store_rows without a gain)
-void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, float* y, int64_t dst_stride);
-void launch_resample_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int16_t* pcm, int64_t dst_stride);
+void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride);
 
 // Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the measurement are engine_loudness.cpp).
 // BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in

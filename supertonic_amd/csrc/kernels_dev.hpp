@@ -1,5 +1,5 @@
 // kernels_dev.hpp — device-side helpers shared by the MFMA kernels (kernels_gemm.hip, kernels_ffn.hip): vector types,
-// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; and the PCM rule of every fetch
+// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; and the sample encodings of every fetch
 // (kernels_misc.hip, kernels_resample.hip).  One definition, so that a fused kernel and the launches it replaces round identically.
 #pragma once
 #include <hip/hip_bf16.h>
@@ -25,6 +25,44 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, si
 
 // fp32 -> 16-bit PCM exactly as the reference's writeWavFile (cpp/helper.cpp:986-987): clamp to [-1, 1], scale to full range, truncate
 __device__ __forceinline__ int pcm16(float v) { return (int)(fminf(1.0f, fmaxf(-1.0f, v)) * 32767.0f); }
+// fp32 -> 24-bit PCM by the same rule: clamp, scale to 2^23 - 1 in fp32, truncate
+__device__ __forceinline__ int pcm24(float v) { return (int)(fminf(1.0f, fmaxf(-1.0f, v)) * 8388607.0f); }
+// G.711 mu-law codeword of a 16-bit sample s: G.191's ulaw_compress of the 14-bit p = s >> 2 as CPython's audioop.lin2ulaw(s, 2)
+// computes it (sign-magnitude |p|, magnitude clipped at 8159, bias 33; the all-ones clip codeword is reached at 8191).  Segment
+// e = floor(log2(m >> 5)) for m >= 32 (0 below), mantissa the four bits under it; every bit inverted, the sign bit clear for p < 0.
+// Branch-free: clz and selects.
+__device__ __forceinline__ unsigned mulaw8(int s) {
+    const int p = s >> 2;
+    const int m = min((p < 0 ? -p : p) + 33, 8191);
+    const int seg = 31 - __builtin_clz((unsigned)(m >> 5) | 1u);
+    return (unsigned)((seg << 4) | ((m >> (seg + 1)) & 0xF)) ^ (p < 0 ? 0x7Fu : 0xFFu);
+}
+// G.711 A-law codeword of a 16-bit sample s: G.191's alaw_compress of the 13-bit p = s >> 3 as audioop.lin2alaw(s, 2) computes it
+// (magnitude ~p for p < 0, segment e = floor(log2(m >> 4)) for m >= 32 (0 below), mantissa (m >> max(e, 1)) & 15, even bits inverted
+// by 0x55, sign bit set for p >= 0).
+__device__ __forceinline__ unsigned alaw8(int s) {
+    const int p = s >> 3;
+    const int m = p < 0 ? ~p : p;
+    const int seg = 31 - __builtin_clz((unsigned)(m >> 4) | 1u);
+    return (unsigned)((seg << 4) | ((m >> max(seg, 1)) & 0xF)) ^ (p < 0 ? 0x55u : 0xD5u);
+}
+// one sample v of encoding kEnc (OutEnc, kernels.hpp) stored at sample index i of y (enc_bytes(kEnc) bytes per sample)
+template <int kEnc>
+__device__ __forceinline__ void enc_store1(unsigned char* y, int64_t i, float v) {
+    if constexpr (kEnc == ENC_F32) {
+        reinterpret_cast<float*>(y)[i] = v;
+    } else if constexpr (kEnc == ENC_PCM16) {
+        reinterpret_cast<int16_t*>(y)[i] = (int16_t)pcm16(v);
+    } else if constexpr (kEnc == ENC_PCM24) {
+        const int c = pcm24(v);
+        y[3 * i] = (unsigned char)c; y[3 * i + 1] = (unsigned char)(c >> 8); y[3 * i + 2] = (unsigned char)(c >> 16);
+    } else if constexpr (kEnc == ENC_MULAW) {
+        y[i] = (unsigned char)mulaw8(pcm16(v));
+    } else {
+        static_assert(kEnc == ENC_ALAW, "unknown encoding");
+        y[i] = (unsigned char)alaw8(pcm16(v));
+    }
+}
 
 // erf by Abramowitz-Stegun 7.1.26 (|err| <= 1.5e-7): GELU(x) = 0.5 x (1 + erf(x / sqrt2))
 __device__ __forceinline__ float gelu_f(float x) {

@@ -1320,10 +1320,15 @@ void launch_mask_ncl(hipStream_t s, float* x, int B, int D, int L, const int* le
     STN_KLAUNCH(mask_ncl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, D, L, n, len);
 }
 
-// The final store of a fetch: V samples per thread (V = 4 for fp32, 8 for PCM: 16-B loads and one 16-B store; or 1), times the row's
-// gain when kGain.  x and y may be the same fp32 rows (dst_stride == W: the gain applied in place), so neither is __restrict__.
-template <int V, bool kGain, typename OutT>
-__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, OutT* y, int64_t dst_stride) {
+// The final store of a fetch: V samples per thread, times the row's gain when kGain, in encoding kEnc (kernels_dev.hpp).  Vector form:
+// 16-B loads, V = 4 (fp32: one 16-B store), 8 (PCM16: one 16-B store) or 16 (mu-law / A-law: one 16-B store; PCM24: three, 48 B);
+// scalar form (V = 1): one sample, enc_store1.  x and y may be the same fp32 rows (dst_stride == W: the gain applied in place), so
+// neither is __restrict__.
+template <int kEnc>
+constexpr int store_vec() { return kEnc == ENC_F32 ? 4 : kEnc == ENC_PCM16 ? 8 : 16; }
+
+template <int V, bool kGain, int kEnc>
+__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, unsigned char* y, int64_t dst_stride) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/V]
     if (i >= nv) return;
     const int64_t row = i / Wv;
@@ -1342,38 +1347,69 @@ __global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const 
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] *= s;
     }
-    OutT* d = y + row * dst_stride + (i - row * Wv) * V;
-    if constexpr (std::is_same<OutT, float>::value) {
-        if constexpr (V == 1) *d = v[0];
-        else *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
-    } else if constexpr (V == 1) {
-        *d = (int16_t)pcm16(v[0]);
-    } else {
+    const int64_t e = row * dst_stride + (i - row * Wv) * V;  // first destination sample
+    if constexpr (V == 1) {
+        enc_store1<kEnc>(y, e, v[0]);
+    } else if constexpr (kEnc == ENC_F32) {
+        *reinterpret_cast<float4*>(y + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (kEnc == ENC_PCM16) {
         unsigned o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = ((unsigned)pcm16(v[2 * j]) & 0xFFFFu) | ((unsigned)pcm16(v[2 * j + 1]) << 16);
-        *reinterpret_cast<uint4*>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint4*>(y + e * 2) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else if constexpr (kEnc == ENC_PCM24) {
+        // sample j's three bytes at 3j .. 3j+2 of 48: word w = bits [32w, 32w + 32) of the 384-bit little-endian run
+        unsigned o[12] = {};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned c = (unsigned)pcm24(v[j]) & 0xFFFFFFu;
+            const int b = 24 * j, w = b >> 5, sh = b & 31;
+            o[w] |= c << sh;
+            if (sh > 8) o[w + 1] |= c >> (32 - sh);
+        }
+        uint4* d = reinterpret_cast<uint4*>(y + e * 3);
+        d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+    } else {
+        unsigned o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned w = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int s16 = pcm16(v[4 * j + k]);
+                w |= (kEnc == ENC_MULAW ? mulaw8(s16) : alaw8(s16)) << (8 * k);
+            }
+            o[j] = w;
+        }
+        *reinterpret_cast<uint4*>(y + e) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
-template <typename OutT>
-void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, OutT* y, int64_t dst_stride) {
+template <int kEnc>
+void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, unsigned char* y, int64_t dst_stride) {
     const int64_t n = rows * W;
     if (n <= 0) return;
     if (dst_stride < W) throw std::invalid_argument("store_rows: dst_stride smaller than the row length");
-    constexpr int V = 16 / sizeof(OutT);
+    constexpr int V = store_vec<kEnc>();
     const bool vec = W % V == 0 && dst_stride % V == 0 && !(reinterpret_cast<uintptr_t>(x) & 15) && !(reinterpret_cast<uintptr_t>(y) & 15);
     const int64_t nv = vec ? n / V : n;
     const dim3 grid((unsigned)((nv + 255) / 256));
-    if (vec && g) STN_KLAUNCH((store_rows_kernel<V, true, OutT>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
-    else if (vec) STN_KLAUNCH((store_rows_kernel<V, false, OutT>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
-    else if (g) STN_KLAUNCH((store_rows_kernel<1, true, OutT>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
-    else STN_KLAUNCH((store_rows_kernel<1, false, OutT>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+    if (vec && g) STN_KLAUNCH((store_rows_kernel<V, true, kEnc>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (vec) STN_KLAUNCH((store_rows_kernel<V, false, kEnc>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (g) STN_KLAUNCH((store_rows_kernel<1, true, kEnc>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+    else STN_KLAUNCH((store_rows_kernel<1, false, kEnc>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
 }
-void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, float* y, int64_t dst_stride) {
-    launch_store_rows_t(s, x, rows, W, g, y, dst_stride);
-}
-void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int16_t* y, int64_t dst_stride) {
-    launch_store_rows_t(s, x, rows, W, g, y, dst_stride);
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride) {
+    unsigned char* d = static_cast<unsigned char*>(y);
+    switch (enc) {
+        case ENC_F32: launch_store_rows_t<ENC_F32>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_PCM16: launch_store_rows_t<ENC_PCM16>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_PCM24: launch_store_rows_t<ENC_PCM24>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_MULAW: launch_store_rows_t<ENC_MULAW>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_ALAW: launch_store_rows_t<ENC_ALAW>(s, x, rows, W, g, d, dst_stride); break;
+        default: throw std::invalid_argument("store_rows: unknown encoding " + std::to_string(enc));
+    }
 }
 
 }  // namespace stn

@@ -1,6 +1,6 @@
 // kernels_resample.hip — rational polyphase resampler of the finished waveform (gfx950, wave64).  Runs at fetch time, outside the
-// captured pipeline: rows x W fp32 samples at the model rate -> rows x W_out samples at P/Q times that rate, as fp32 or as 16-bit PCM
-// (writeWavFile's conversion), rows landing dst_stride apart.
+// captured pipeline: rows x W fp32 samples at the model rate -> rows x W_out samples at P/Q times that rate, in any fetch encoding
+// (fp32, 16- or 24-bit PCM, mu-law, A-law: enc_store1, kernels_dev.hpp), rows landing dst_stride samples apart.
 //
 // Output n of a row: phase (n*Q) mod P, first input floor(n*Q/P) - off, taps taps[phase][0 .. T) (resample_design, engine_resample.cpp).
 // Decomposition: write n = k*P + r.  For a fixed r every k has the same phase (r*Q mod P) and its first input
@@ -27,12 +27,9 @@ __host__ __device__ inline int64_t rs_span(int G, int P, int Q, int T) {
     return (int64_t)(G * RS_LANES - 1) * Q + (int64_t)(P - 1) * Q / P + T;
 }
 
-__device__ __forceinline__ void rs_store(float* y, int64_t i, float v) { y[i] = v; }
-__device__ __forceinline__ void rs_store(int16_t* y, int64_t i, float v) { y[i] = (int16_t)pcm16(v); }
-
-template <bool kLds, typename OutT>
+template <bool kLds, int kEnc>
 __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const float* __restrict__ x, int64_t W, int64_t W_out, int P, int Q, int T,
-                                                              int off, int G, const float* __restrict__ taps, OutT* __restrict__ y,
+                                                              int off, int G, const float* __restrict__ taps, unsigned char* __restrict__ y,
                                                               int64_t dst_stride) {
     extern __shared__ float win[];
     const int64_t row = blockIdx.y;
@@ -83,12 +80,12 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const float* __res
             }
         }
         const float s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-        if (n < W_out) rs_store(y, row * dst_stride + n, s);
+        if (n < W_out) enc_store1<kEnc>(y, row * dst_stride + n, s);  // byte encodings: plain stores at a stride of P
     }
 }
 
-template <typename OutT>
-void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, OutT* y, int64_t dst_stride) {
+template <int kEnc>
+void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, unsigned char* y, int64_t dst_stride) {
     if (rows <= 0 || W <= 0) return;
     if (f.T % 8 != 0 || f.T < 8 || f.P < 1 || f.Q < 1 || !f.dev) throw std::runtime_error("launch_resample: filter table not prepared");
     if (rows > 65535) throw std::invalid_argument("launch_resample: more than 65535 rows");
@@ -104,21 +101,26 @@ void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, c
     if (lds <= RS_LDS_MAX) {
         static PerDeviceOnce attr_once;
         if (attr_once.need())
-            stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_kernel<true, OutT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+            stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_kernel<true, kEnc>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)RS_LDS_MAX), "hipFuncSetAttribute(resample)");
-        STN_KLAUNCH((resample_kernel<true, OutT>), grid, dim3(RS_THREADS), (unsigned)lds, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
+        STN_KLAUNCH((resample_kernel<true, kEnc>), grid, dim3(RS_THREADS), (unsigned)lds, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
     } else {
-        STN_KLAUNCH((resample_kernel<false, OutT>), grid, dim3(RS_THREADS), 0, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
+        STN_KLAUNCH((resample_kernel<false, kEnc>), grid, dim3(RS_THREADS), 0, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
     }
 }
 
 }  // namespace
 
-void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, float* y, int64_t dst_stride) {
-    launch_resample_t(s, x, rows, W, f, y, dst_stride);
-}
-void launch_resample_pcm16(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int16_t* pcm, int64_t dst_stride) {
-    launch_resample_t(s, x, rows, W, f, pcm, dst_stride);
+void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride) {
+    unsigned char* d = static_cast<unsigned char*>(y);
+    switch (enc) {
+        case ENC_F32: launch_resample_t<ENC_F32>(s, x, rows, W, f, d, dst_stride); break;
+        case ENC_PCM16: launch_resample_t<ENC_PCM16>(s, x, rows, W, f, d, dst_stride); break;
+        case ENC_PCM24: launch_resample_t<ENC_PCM24>(s, x, rows, W, f, d, dst_stride); break;
+        case ENC_MULAW: launch_resample_t<ENC_MULAW>(s, x, rows, W, f, d, dst_stride); break;
+        case ENC_ALAW: launch_resample_t<ENC_ALAW>(s, x, rows, W, f, d, dst_stride); break;
+        default: throw std::invalid_argument("launch_resample: unknown encoding " + std::to_string(enc));
+    }
 }
 
 }  // namespace stn

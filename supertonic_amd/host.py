@@ -31,6 +31,8 @@ def _lib():
         L.stn_bind_graphs.argtypes = [c, ctypes.c_void_p, sz]
         L.stn_wav_encode.restype = i64
         L.stn_wav_encode.argtypes = [ctypes.c_void_p, sz, ctypes.c_int, ctypes.c_void_p, sz]
+        L.stn_wav_encode_as.restype = i64
+        L.stn_wav_encode_as.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_int, ctypes.c_void_p, sz]
         L.stn_write_wav.argtypes = [c, ctypes.c_void_p, sz, ctypes.c_int]
         L.stn_load_voice_style.argtypes = [ctypes.POINTER(c), ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_void_p, sz,
                                            ctypes.POINTER(ctypes.c_int64)]
@@ -161,8 +163,23 @@ def bound_tensor(onnx_dir: str, name: str) -> np.ndarray:
     return out
 
 
-def wav_bytes(audio, sample_rate: int) -> bytes:
+def wav_bytes(audio, sample_rate: int, encoding=None) -> bytes:
+    """A WAV file of one utterance.  encoding None: audio is float and is written as writeWavFile writes it (16-bit PCM).  Otherwise
+    audio holds samples already in that encoding (a name or binding.ENC_*, as the encoded fetches return them: float32, int16, uint8
+    [n, 3] for PCM24, uint8 for mu-law / A-law) and is written with its own format tag (stn_wav_encode_as)."""
     L = _lib()
+    if encoding is not None:
+        e = binding.encoding_id(encoding)
+        dt = {binding.ENC_F32: np.float32, binding.ENC_PCM16: np.int16}.get(e, np.uint8)
+        a = np.ascontiguousarray(audio, dt)
+        n = a.nbytes // binding.ENCODING_BYTES[e]
+        need = L.stn_wav_encode_as(e, a.ctypes.data, n, sample_rate, None, 0)
+        if need < 0:
+            _fail(L)
+        buf = ctypes.create_string_buffer(need)
+        if L.stn_wav_encode_as(e, a.ctypes.data, n, sample_rate, buf, need) != need:
+            _fail(L)
+        return buf.raw
     a = np.ascontiguousarray(audio, np.float32)
     n = 44 + 2 * a.size
     buf = ctypes.create_string_buffer(n)

@@ -34,7 +34,7 @@ class _Job:
 
 class DynamicBatcher:
     """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed, output rate, loudness target and peak ceiling) into one engine batch (the engine's output rate and loudness
+    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding) into one engine batch (the engine's output rate and loudness
     setting cover a whole batch; every row is still normalized with its own gain).  A worker thread owns
     the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
     its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
@@ -47,12 +47,13 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0):
+    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
-        the synthesizer's own setting)."""
+        the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32)."""
         lo = None if loudness is None else (float(loudness), float(peak_ceiling))
-        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo))
+        enc = None if encoding is None else binding.encoding_id(encoding)
+        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc))
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -105,10 +106,12 @@ class DynamicBatcher:
                 langs = [j.lang for j in jobs for _ in j.texts]
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
-                step, speed, rate, lo = jobs[0].key
+                step, speed, rate, lo, enc = jobs[0].key
                 extra = {} if rate is None else {"output_rate": rate}
                 if lo is not None:
                     extra["loudness"] = lo
+                if enc is not None:
+                    extra["encoding"] = enc
                 waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
                 self.batches.append(len(texts))
                 o = 0
@@ -123,9 +126,14 @@ class DynamicBatcher:
                 j.done.set()
 
 
-def join_chunks(waves, durs, silence_duration, sample_rate):
-    """TextToSpeech.__call__'s concatenation (py/helper.py:235-243): untrimmed chunk waves with zeros between."""
-    silence = np.zeros(int(silence_duration * sample_rate), np.float32)
+def join_chunks(waves, durs, silence_duration, sample_rate, encoding=None):
+    """TextToSpeech.__call__'s concatenation (py/helper.py:235-243): untrimmed chunk waves with zeros between (with an encoding: its
+    zero codeword between waves in that encoding)."""
+    if encoding is None:
+        silence = np.zeros(int(silence_duration * sample_rate), np.float32)
+    else:
+        silence = binding.encoded_empty(encoding, 1, int(silence_duration * sample_rate))[0]
+        silence[...] = binding.ZERO_CODEWORD[binding.encoding_id(encoding)]
     parts, dur = [], None
     for i, w in enumerate(waves):
         if i == 0:
@@ -172,6 +180,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         loudness: Optional[float] = Field(None, ge=-60.0, le=0.0, description="Normalize each utterance to this BS.1770-4 integrated "
                                                                               "loudness in LUFS (on the GPU); null: off.")
         peak_ceiling: float = Field(-1.0, ge=-30.0, le=0.0, description="Sample-peak ceiling in dBFS that caps the loudness gain.")
+        encoding: str = Field("pcm16", description="Sample format of the WAV files (encoded on the GPU): pcm16, pcm24, f32, mulaw, alaw.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -205,22 +214,28 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             sr, extra = req.sample_rate, {"output_rate": req.sample_rate}
         if req.loudness is not None:
             extra["loudness"] = (req.loudness, req.peak_ceiling)
+        if req.encoding not in binding.ENCODINGS:
+            raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
+        enc = None if req.encoding == "pcm16" else req.encoding  # pcm16: the float waves, written as writeWavFile writes them
+        if enc is not None:
+            extra["encoding"] = enc
         if req.batch:
             wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
             chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
-            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling)
-            wav, d = join_chunks(waves, durs, req.silence_duration, sr)
+            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
+                                         enc)
+            wav, d = join_chunks(waves, durs, req.silence_duration, sr, enc)
             chunks = [wav[: int(sr * d)]]
         if len(chunks) == 1:
             name = host.sanitize_filename(texts[0], 40) or "tts"
-            return Response(host.wav_bytes(chunks[0], sr), media_type="audio/wav",
+            return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav",
                             headers={"Content-Disposition": f'attachment; filename="{_ascii(name)}.wav"'})
         zbuf = io.BytesIO()
         with zipfile.ZipFile(zbuf, "w", compression=zipfile.ZIP_DEFLATED) as zf:
             for i, c in enumerate(chunks):
-                zf.writestr((host.sanitize_filename(texts[i], 40) or f"tts_{i + 1}") + ".wav", host.wav_bytes(c, sr))
+                zf.writestr((host.sanitize_filename(texts[i], 40) or f"tts_{i + 1}") + ".wav", host.wav_bytes(c, sr, enc))
         return Response(zbuf.getvalue(), media_type="application/zip",
                         headers={"Content-Disposition": 'attachment; filename="tts_outputs.zip"'})
 

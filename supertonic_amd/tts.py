@@ -81,7 +81,8 @@ class TextToSpeech:
         self._calls += 1
         return self.noise_seed + self._calls - 1
 
-    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None):
+    def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None,
+               encoding=None):
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         ids, mask = self.text_processor(text_list, lang_list)
@@ -96,7 +97,12 @@ class TextToSpeech:
             if loudness is not None:  # this call's normalization (fetch-time as well)
                 self.engine.set_loudness(*(_loudness_setting(loudness) or (None,)))
             try:
-                return self.engine.synthesize(ids, mask, style.ttl, style.dp, total_step, speed, noise_seed=self._seed())
+                if encoding is None:
+                    return self.engine.synthesize(ids, mask, style.ttl, style.dp, total_step, speed, noise_seed=self._seed())
+                # encoded on the GPU by the fetch (binding.encoded_empty's dtypes)
+                self.engine.batch_upload(ids, mask, style.ttl, style.dp)
+                self.engine.batch_run(total_step, speed, self._seed())
+                return self.engine.batch_fetch_encoded(encoding)
             finally:
                 self.engine.set_vocoder_mode(False)
                 self.engine.set_shape_buckets(False)
@@ -118,31 +124,37 @@ class TextToSpeech:
         P, Q = out // g, self.sample_rate // g
         return -(-int(n) * P // Q)
 
-    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None):
+    def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
         and the durations.  The building block of the long-form path and of the service's dynamic batching.
         output_rate / loudness: this call's setting instead of the instance's (loudness: False = off for this call, a target in
-        LUFS, or (target, ceiling dBFS)); with normalization, each utterance is normalized on its own."""
+        LUFS, or (target, ceiling dBFS)); with normalization, each utterance is normalized on its own.  encoding (a name or
+        binding.ENC_*; None: float32): the waves in that sample encoding, encoded on the GPU (binding.encoded_empty's dtypes)."""
         wav, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
-                               loudness=loudness)
+                               loudness=loudness, encoding=encoding)
         cs = self.base_chunk_size * self.chunk_compress_factor
         lens = [int(self.latent_lengths(dur[i:i + 1])[0]) for i in range(len(text_list))]
         return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
-    def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3):
+    def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None):
         """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence.  With
         loudness normalization on, each chunk is normalized as its own row (its own gain); the joined text is not normalized as one
-        unit."""
+        unit.  encoding: as solo_batch; the silence is then the encoding's zero codeword."""
         if style.ttl.shape[0] != 1:
             raise ValueError("Single speaker text to speech only supports single style")
         chunks = host.chunk_text(text, 120 if lang == "ko" else 300)
         if len(chunks) == 1:
-            return self._infer(chunks, [lang], style, total_step, speed)
+            return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding)
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
-        waves, dur = self.solo_batch(chunks, [lang] * n, rep, total_step, speed)
-        silence = np.zeros(int(silence_duration * self.output_rate), np.float32)
+        waves, dur = self.solo_batch(chunks, [lang] * n, rep, total_step, speed, encoding=encoding)
+        n_sil = int(silence_duration * self.output_rate)
+        if encoding is None:
+            silence = np.zeros(n_sil, np.float32)
+        else:
+            silence = binding.encoded_empty(encoding, 1, n_sil)[0]
+            silence[...] = binding.ZERO_CODEWORD[binding.encoding_id(encoding)]
         parts, dur_cat = [], None
         for i, w in enumerate(waves):  # untrimmed chunk waves joined by zeros (py/helper.py:235-243)
             if i == 0:
@@ -153,8 +165,11 @@ class TextToSpeech:
             parts.append(w)
         return np.concatenate(parts)[None, :], np.array([dur_cat], np.float32)
 
-    def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None):
-        return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness)
+    def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None):
+        """One padded batch -> (wav [B, W] float32, duration [B]); with an encoding (a name or binding.ENC_*), the rows in that sample
+        encoding instead, encoded on the GPU (binding.encoded_empty's dtypes)."""
+        return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness,
+                           encoding=encoding)
 
 
 def _loudness_setting(v):
