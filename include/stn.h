@@ -374,6 +374,42 @@ int stn_op_dwconv_ln(stn_handle* h, int dtype, int B, int L, int C, int k, int d
 int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x,
                             const float* w /*[C,k]*/, const float* bias, const float* ln_g, const float* ln_b,
                             const int32_t* seqlen /*[B], 0..L*/, float* y);
+/* The same launcher on the caller's whole buffers (the kernel parity tests of every dwconv + LayerNorm form).  x: x_rows rows of C, uploaded as
+ * given, padding rows included.  packed = 0: sequence b owns rows b*L .. b*L + L of x / y (seqlen optional; x_rows, y_rows >= B*L); packed != 0:
+ * seqlen[b] consecutive rows in order (needs seqlen; B <= 1024; x_rows, y_rows >= their sum), L >= every length.  ln_only != 0: plain
+ * LayerNorm over the B*L rows (w, bias, seqlen unused).  eps = 1e-6.  y: y_rows rows of C, the caller's whole buffer, uploaded as given
+ * (rounded to dtype) and written back whole (16-bit values widened to fp32, exactly), so what lies outside the written rows can be checked.
+ * form: the form that ran (as stn_dbg_dwconv_ln_form, or "layernorm"), NUL-terminated, truncated to form_cap; may be NULL. */
+int stn_op_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows,
+                        const float* w_or_null /*[C,k]*/, const float* bias_or_null, const float* ln_g, const float* ln_b,
+                        const int32_t* seqlen_or_null, int packed, int ln_only, float* y, int64_t y_rows, char* form, size_t form_cap);
+/* diagnostics (no device needed): the form the engine's depthwise-conv + LayerNorm launcher takes for B sequences of L rows, C channels,
+ * k taps, output format dtype, padded or packed rows: "v3<K,R>" (combs of R frames), "v3occ4<7,4>" (the same held to four waves per SIMD),
+ * "v2<K>" or "generic".  Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher refuses
+ * (STN_ERR_INVALID: C % 4, C > 1024, packed with C > 512 or k outside {5, 7}). */
+int stn_dbg_dwconv_ln_form(int dtype, int B, int L, int C, int k, int packed, char* out, size_t cap);
+/* The fold of a pending K4-split / head-split update fused with LayerNorm, on host operands: x [M,C] <- x + gamma * (((p0 + p1) + ...) + b2)
+ * [+ rowvec[row_b[m]]] in fp32, y [M,C] = LayerNorm(x) * ln_g + ln_b in dtype (STN_DTYPE_BF16 or STN_DTYPE_F16; fp32 copy).  part [S,M,C]:
+ * the partial sums, rounded to dtype first; S in {4, 8, 12, 24}.  rowvec [nseq,C] (row_b NULL: every row takes rowvec[0]). */
+int stn_op_fold_ln(stn_handle* h, int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma,
+                   const float* rowvec_or_null, const int32_t* row_b_or_null, int nseq, const float* ln_g, const float* ln_b, float* x,
+                   float* y);
+/* One layout kernel between the GEMMs on host operands (the bit-for-bit kernel tests).  which / p (int parameters) / operands:
+ *   0 row_map         p = {B, rows_padded, with_row_b}; len [B]; iout = row_off [B+1] followed by row_b (with_row_b: max(sum len, rows_padded) entries)
+ *   1 ncl_to_rows     p = {B, C, L, ld_out}; a [B,C,L]; out: rows of ld_out in dtype
+ *   2 euler_ncl       p = {B, D, L, with_z, ldz}; a = prev [B,D,L], b = velocity rows of D, c = dt [B]; out [B,D,L]; out2 (with_z): rows of ldz in dtype
+ *   3 unpack_rows     p = {B, T, W}; a: packed rows of W; len [B]; out [B,T,W]
+ *   4 embed           p = {vocab, B, L, C}; ids [B,L]; a = table [vocab,C]; len [B]; out: rows of C
+ *   5 masked_mean     p = {B, L, C}; a: rows of C (rounded to dtype); len [B]; out [B,C]
+ *   6 vocoder_im2col  p = {B, L, ld, ccf, k, kp}; a = latent [B, ld*ccf, L]; len = valid vocoder frames (<= L*ccf) or NULL; out: rows of kp in dtype
+ *   7 vocoder_in      p = {B, L, ld, ccf, C, k}; a = latent, b = weights [ld*k, C], c = bias [C]; len as above; out [B*L*ccf, C]
+ * packed != 0 (1, 2, 4, 5, 6): the rows (for 2: the velocity and z rows) are packed per sequence, len[b] each, and need len; else sequence b
+ * owns L (T, L*ccf) rows.  out / out2 / iout are the caller's whole buffers of out_n / out2_n / iout_n elements: uploaded as given (out of 1
+ * and 6, out2 of 2: rounded to dtype) and written back whole, so what a kernel must not touch can be checked.  Buffers too small for the
+ * extents a kernel addresses are refused (STN_ERR_INVALID), as is B > 1024. */
+int stn_op_layout(stn_handle* h, int which, int dtype, const int32_t* p, int n_p, const float* a, int64_t a_n, const float* b, int64_t b_n,
+                  const float* c, int64_t c_n, const int64_t* ids, int64_t ids_n, const int32_t* len, int packed, float* out, int64_t out_n,
+                  float* out2, int64_t out2_n, int32_t* iout, int64_t iout_n);
 /* rope_mode: -1 none, 0 RoPE on the position index, 1 length-aware RoPE; OR-ing 0x100 makes the engine rotate the keys in
  * a separate pass first (the way the vector estimator's step-invariant text keys are handled) — same result */
 int stn_op_attention(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k,

@@ -17,6 +17,8 @@ _DTYPES = {"f32": F32, "fp32": F32, "float32": F32, "bf16": BF16, "f16": F16, "f
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_TANH = 0, 1, 2, 3
 EPI_STORE, EPI_RESID, EPI_STORE_T = 0, 1, 2  # GEMM epilogue modes (stn_op_gemm_ex)
 FFN_VOCODER, FFN_ESTIMATOR, FFN_TEXT = 1, 2, 4  # ConvNeXt stages (ffn_form)
+# kernels of stn_op_layout
+LAYOUT_ROW_MAP, LAYOUT_NCL_TO_ROWS, LAYOUT_EULER_NCL, LAYOUT_UNPACK_ROWS, LAYOUT_EMBED, LAYOUT_MASKED_MEAN, LAYOUT_IM2COL, LAYOUT_VOCODER_IN = range(8)
 # sample encodings of a fetch (STN_ENC_*, include/stn.h)
 ENC_F32, ENC_PCM16, ENC_PCM24, ENC_MULAW, ENC_ALAW = 0, 1, 2, 3, 4
 ENCODINGS = {"f32": ENC_F32, "pcm16": ENC_PCM16, "pcm24": ENC_PCM24, "mulaw": ENC_MULAW, "alaw": ENC_ALAW}
@@ -204,6 +206,13 @@ def load():
     L.stn_op_dwconv_ln.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.stn_op_dwconv_ln_ragged.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p]
     L.stn_op_attention.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p]
+    L.stn_op_dwconv_ln_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, vp, vp, _f32p, _f32p, vp, ci, ci, _f32p, ctypes.c_int64,
+                                      ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_dwconv_ln_form.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_dwconv_ln_form.restype = ctypes.c_int
+    L.stn_op_fold_ln.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p, _f32p, _f32p, _f32p]
+    L.stn_op_layout.argtypes = [vp, ci, ci, _i32p, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci,
+                                vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64]
     L.stn_op_attention_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, ci, ci, _f32p, ctypes.c_int64, ci, ci, ci,
                                       _f32p, ctypes.c_int64, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_xattn_hs.argtypes = [vp, ci, ci, _f32p, _f32p, vp, _f32p, _f32p, ctypes.c_int64, ci, ci, ci, ci, ci, _i32p, vp, vp, ci, ci,
@@ -409,6 +418,16 @@ def attn_form(dtype, B, Lq, Lk, H, dh, ldq=None, ldk=None, misaligned=0, kind=0)
                                  int(C if ldk is None else ldk), int(misaligned), buf, len(buf))
     if r < 0:
         raise StnError(r, "stn_dbg_attn_form: the launcher refuses this call")
+    return buf.value.decode()
+
+
+def dwconv_ln_form(dtype, B, L, C, k, packed=False):
+    """The form the engine's depthwise-conv + LayerNorm launcher takes (stn_dbg_dwconv_ln_form; host-only): "v3<K,R>", "v3occ4<7,4>",
+    "v2<K>" or "generic".  Raises StnError where the launcher refuses the call."""
+    buf = ctypes.create_string_buffer(32)
+    r = load().stn_dbg_dwconv_ln_form(_DTYPES[dtype], int(B), int(L), int(C), int(k), int(bool(packed)), buf, len(buf))
+    if r < 0:
+        raise StnError(r, "stn_dbg_dwconv_ln_form: the launcher refuses this call")
     return buf.value.decode()
 
 
@@ -922,6 +941,56 @@ class Engine:
                                             _c(x, np.float32), _c(w, np.float32), _c(bias, np.float32),
                                             _c(g, np.float32), _c(b, np.float32), y))
         return y
+
+    def op_dwconv_ln_ex(self, x, w, bias, g, b, dil, out, B, L, seqlen=None, packed=False, ln_only=False, dtype=None):
+        """launch_dwconv_ln (ln_only: launch_layernorm over B*L rows) on whole buffers (stn_op_dwconv_ln_ex).  x, out: 2-D [rows, C], x
+        uploaded as given; packed: sequence b owns seqlen[b] consecutive rows.  w [C, k] (None with ln_only).  Returns (out as a new fp32
+        array, whole; form string)."""
+        x = _c(x, np.float32)
+        o_r = np.array(out, dtype=np.float32, order="C", copy=True)
+        C = x.shape[1]
+        _w, wp = _opt(w, np.float32)
+        _b, bp = _opt(bias, np.float32)
+        _l, lp = _opt(seqlen, np.int32)
+        form = ctypes.create_string_buffer(32)
+        self._ck(self._lib.stn_op_dwconv_ln_ex(self._h, self.dtype if dtype is None else _DTYPES[dtype], int(B), int(L), C,
+                                               1 if _w is None else _w.shape[1], int(dil), x.reshape(-1), x.shape[0], wp, bp, _c(g, np.float32),
+                                               _c(b, np.float32), lp, int(bool(packed)), int(bool(ln_only)), o_r.reshape(-1), o_r.shape[0], form,
+                                               ctypes.sizeof(form)))
+        return o_r, form.value.decode()
+
+    def op_fold_ln(self, x, part, b2, gamma, g, b, rowvec=None, row_b=None, dtype=None):
+        """launch_fold_ln on host operands (stn_op_fold_ln).  x [M, C], part [S, M, C] (rounded to the 16-bit dtype first), rowvec [nseq, C].
+        Returns (updated x, LayerNorm output as fp32)."""
+        x_r = np.array(x, dtype=np.float32, order="C", copy=True)
+        M, C = x_r.shape
+        part = _c(part, np.float32)
+        y = np.empty((M, C), np.float32)
+        _v, vp_ = _opt(rowvec, np.float32)
+        _r, rp = _opt(row_b, np.int32)
+        self._ck(self._lib.stn_op_fold_ln(self._h, self.dtype if dtype is None else _DTYPES[dtype], M, C, part.shape[0], part.reshape(-1),
+                                          _c(b2, np.float32), _c(gamma, np.float32), vp_, rp, 0 if _v is None else _v.shape[0],
+                                          _c(g, np.float32), _c(b, np.float32), x_r, y))
+        return x_r, y
+
+    def op_layout(self, which, p, a=None, b=None, c=None, ids=None, length=None, packed=False, out=None, out2=None, iout=None, dtype="f32"):
+        """One layout kernel of kernels_misc.hip on host operands (stn_op_layout; LAYOUT_* and the parameter lists: include/stn.h).
+        out / out2 (float32) and iout (int32) are whole destination buffers; they come back as new arrays (out, out2, iout)."""
+        def f32(v):
+            return (None, None, 0) if v is None else (lambda arr: (arr, arr.ctypes.data, arr.size))(_c(v, np.float32))
+        pa = _c(p, np.int32)
+        _a, ap, an = f32(a)
+        _b, bp, bn = f32(b)
+        _cc, cp, cn = f32(c)
+        _i, ip = _opt(ids, np.int64)
+        _l, lp = _opt(length, np.int32)
+        o1 = None if out is None else np.array(out, dtype=np.float32, order="C", copy=True)
+        o2 = None if out2 is None else np.array(out2, dtype=np.float32, order="C", copy=True)
+        io = None if iout is None else np.array(iout, dtype=np.int32, order="C", copy=True)
+        ptr = lambda v: (None, 0) if v is None else (v.ctypes.data, v.size)  # noqa: E731
+        self._ck(self._lib.stn_op_layout(self._h, int(which), _DTYPES[dtype], pa, len(pa), ap, an, bp, bn, cp, cn, ip, 0 if _i is None else _i.size,
+                                         lp, int(bool(packed)), *ptr(o1), *ptr(o2), *ptr(io)))
+        return o1, o2, io
 
     def op_attention(self, q, k, v, H, qlen=None, klen=None, rope_mode=-1, dtype=None):
         B, Lq, C = q.shape

@@ -521,6 +521,57 @@ int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k
                  for (int i = 0; i < B; ++i) need(seqlen[i] >= 0 && seqlen[i] <= L, "stn_op_dwconv_ln_ragged: seqlen out of [0, L]");
                  h->eng->op_dwconv_ln(dtype, B, L, C, k, dil, x, w, bias, g, b, y, seqlen); })
 }
+static void dwconv_ln_ex_checked(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
+                                 const float* bias, const float* g, const float* b, const int32_t* seqlen, int packed, int ln_only, float* y,
+                                 int64_t y_rows, char* form, size_t form_cap) {
+    need(B > 0 && L > 0 && C > 0 && C % 4 == 0 && C <= 1024 && k > 0 && (k & 1) && dil > 0 && x && g && b && y && x_rows > 0 && y_rows > 0,
+         "stn_op_dwconv_ln_ex: bad argument");
+    need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_dwconv_ln_ex: unknown dtype");
+    need(ln_only || (w && bias), "stn_op_dwconv_ln_ex: the conv needs w and bias");
+    need(!(packed && ln_only), "stn_op_dwconv_ln_ex: ln_only takes no packed layout");
+    need(!packed || (seqlen && B <= 1024), "stn_op_dwconv_ln_ex: packed rows need seqlen and B <= 1024");
+    int64_t rows = (int64_t)B * L;
+    if (seqlen && !ln_only) {
+        int64_t tot = 0;
+        for (int i = 0; i < B; ++i) { need(seqlen[i] >= 0 && seqlen[i] <= L, "stn_op_dwconv_ln_ex: seqlen out of [0, L]"); tot += seqlen[i]; }
+        if (packed) rows = tot;
+    }
+    need(x_rows >= rows && y_rows >= rows, "stn_op_dwconv_ln_ex: x / y hold fewer rows than the launch addresses");
+    const std::string f = h->eng->op_dwconv_ln_ex(dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, ln_only ? nullptr : seqlen, packed, ln_only, y, y_rows);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
+                        const float* bias, const float* g, const float* b, const int32_t* seqlen, int packed, int ln_only, float* y,
+                        int64_t y_rows, char* form, size_t form_cap) {
+    STN_TRY(h, dwconv_ln_ex_checked(h, dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, seqlen, packed, ln_only, y, y_rows, form, form_cap))
+}
+int stn_dbg_dwconv_ln_form(int dtype, int B, int L, int C, int k, int packed, char* out, size_t cap) {
+    if (B < 1 || L < 1 || C < 1 || k < 1 || !(k & 1) || (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16)) return STN_ERR_INVALID;
+    std::string f;
+    try { f = stn::dwconv_ln_form(dtype, B, L, C, k, packed != 0).str(); } catch (const std::exception&) { return STN_ERR_INVALID; }
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
+}
+int stn_op_fold_ln(stn_handle* h, int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma, const float* rowvec,
+                   const int32_t* row_b, int nseq, const float* g, const float* b, float* x, float* y) {
+    STN_TRY(h, { need(M > 0 && C > 0 && C % 4 == 0 && C <= 1024 && (S == 4 || S == 8 || S == 12 || S == 24) && part && b2 && gamma && g && b && x && y,
+                      "stn_op_fold_ln: bad argument");
+                 need(dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_fold_ln: a 16-bit format needed");
+                 need(!rowvec || nseq > 0, "stn_op_fold_ln: rowvec needs nseq > 0");
+                 if (rowvec && row_b) for (int m = 0; m < M; ++m) need(row_b[m] >= 0 && row_b[m] < nseq, "stn_op_fold_ln: row_b out of range");
+                 h->eng->op_fold_ln(dtype, M, C, S, part, b2, gamma, rowvec, row_b, nseq, g, b, x, y); })
+}
+int stn_op_layout(stn_handle* h, int which, int dtype, const int32_t* p, int n_p, const float* a, int64_t a_n, const float* b, int64_t b_n,
+                  const float* c, int64_t c_n, const int64_t* ids, int64_t ids_n, const int32_t* len, int packed, float* out, int64_t out_n,
+                  float* out2, int64_t out2_n, int32_t* iout, int64_t iout_n) {
+    static const int n_params[8] = {3, 4, 5, 3, 4, 3, 6, 6};
+    STN_TRY(h, { need(which >= 0 && which < 8 && p && n_p == n_params[which], "stn_op_layout: unknown kernel or parameter count");
+                 need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_layout: unknown dtype");
+                 need(a_n >= 0 && b_n >= 0 && c_n >= 0 && ids_n >= 0 && out_n >= 0 && out2_n >= 0 && iout_n >= 0 && (a || !a_n) && (b || !b_n) && (c || !c_n) &&
+                          (ids || !ids_n) && (out || !out_n) && (out2 || !out2_n) && (iout || !iout_n),
+                      "stn_op_layout: a buffer without a pointer");
+                 h->eng->op_layout(which, dtype, p, a, a_n, b, b_n, c, c_n, ids, ids_n, len, packed, out, out_n, out2, out2_n, iout, iout_n); })
+}
 int stn_op_attention(stn_handle* h, int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k,
                      const float* v, const int32_t* qlen, const int32_t* klen, int rope_mode, float* o) {
     STN_TRY(h, { need(B > 0 && Lq > 0 && Lk > 0 && H > 0 && dh >= 8 && dh % 8 == 0 && dh <= 96 && q && k && v && o,

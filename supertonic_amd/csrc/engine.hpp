@@ -320,6 +320,18 @@ class Engine {
                       const int* qlen, const int* klen, int rope_mode, float* o);
     void op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,
                       const float* g, const float* b, float* y, const int* seqlen = nullptr /* host [B] */);
+    // launch_dwconv_ln (or, ln_only, launch_layernorm over B*L rows) on the caller's whole buffers (stn_op_dwconv_ln_ex): x [x_rows][C] uploaded as
+    // given, padding rows included; packed: sequence b owns seqlen[b] consecutive rows of x / y (row_off from launch_row_map); y [y_rows][C]
+    // uploaded as given (rounded to dtype) and downloaded whole.  Returns the form it ran (DwconvLnForm::str, or "layernorm").
+    std::string op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w, const float* bias,
+                                const float* g, const float* b, const int* seqlen, int packed, int ln_only, float* y, int64_t y_rows);
+    // launch_fold_ln on host operands (stn_op_fold_ln): part [S][M][C] rounded to dtype (BF16 / F16), x [M][C] updated in place, y [M][C]
+    void op_fold_ln(int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma, const float* rowvec, const int* row_b,
+                    int nseq, const float* g, const float* b, float* x, float* y);
+    // one layout kernel of kernels_misc.hip on host operands (stn_op_layout; `which` and the parameter lists are documented there)
+    void op_layout(int which, int dtype, const int* p, const float* a, int64_t a_n, const float* b, int64_t b_n, const float* c, int64_t c_n,
+                   const int64_t* ids, int64_t ids_n, const int* len, int packed, float* out, int64_t out_n, float* out2, int64_t out2_n, int* iout,
+                   int64_t iout_n);
     // device-resident timing of one GEMM shape (random operands), HIP events around `iters` launches: avg ms
     double op_gemm_bench(int dtype, int M, int N, int K, int mode, int iters);
     // per-workgroup phase stamps of one launch of the tiled kernel: out[0..2] = mean cycles of (first stage landed, K loop,

@@ -521,6 +521,210 @@ void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode
     sync();
 }
 
+// the caller's whole fp32 buffer in format dtype on the device, and back (16-bit values widened, exactly)
+static void down_as(Arena& ar, hipStream_t s, int dtype, const void* d, float* h, size_t n) {
+    const float* src = static_cast<const float*>(d);
+    if (is_half(dtype)) {
+        float* w = static_cast<float*>(ar.alloc(n * 4));
+        launch_half_to_f32(s, dtype, d, (int64_t)n, w);
+        src = w;
+    }
+    STN_HIP(hipMemcpyAsync(h, src, n * 4, hipMemcpyDeviceToHost, s));
+}
+
+std::string Engine::op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
+                                    const float* bias, const float* g, const float* b, const int* seqlen, int packed, int ln_only, float* y,
+                                    int64_t y_rows) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const int* dlen = seqlen ? up(ar_, s_, seqlen, (size_t)B) : nullptr;
+    float* dx = up(ar_, s_, x, (size_t)x_rows * C);  // as given, padding rows included
+    float* dg = up(ar_, s_, g, (size_t)C);
+    float* dbt = up(ar_, s_, b, (size_t)C);
+    void* dy = up_as(ar_, s_, dtype, y, (size_t)y_rows * C);
+    std::string form = "layernorm";
+    if (ln_only) {
+        launch_layernorm(s_, dtype, dx, (int64_t)B * L, C, dg, dbt, 1e-6f, dy);
+    } else {
+        std::vector<float> wt((size_t)C * k);
+        for (int c = 0; c < C; ++c) for (int j = 0; j < k; ++j) wt[(size_t)j * C + c] = w[(size_t)c * k + j];
+        float* dw = up(ar_, s_, wt.data(), wt.size());
+        float* db = up(ar_, s_, bias, (size_t)C);
+        int* off = nullptr;
+        if (packed) {
+            off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+            launch_row_map(s_, dlen, B, off, nullptr);
+        }
+        form = dwconv_ln_form(dtype, B, L, C, k, packed != 0).str();  // the decision launch_dwconv_ln takes
+        launch_dwconv_ln(s_, dtype, dx, B, L, C, dw, db, k, dil, dg, dbt, 1e-6f, dy, dlen, off);
+    }
+    STN_HIP(hipGetLastError());
+    down_as(ar_, s_, dtype, dy, y, (size_t)y_rows * C);
+    sync();
+    return form;
+}
+
+void Engine::op_fold_ln(int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma, const float* rowvec,
+                        const int* row_b, int nseq, const float* g, const float* b, float* x, float* y) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const size_t n = (size_t)M * C;
+    FoldArgs fo;
+    fo.part = up_as(ar_, s_, dtype, part, n * S); fo.S = S; fo.part_stride = (int64_t)n;
+    fo.b2 = up(ar_, s_, b2, (size_t)C); fo.gamma = up(ar_, s_, gamma, (size_t)C);
+    fo.rowvec = rowvec ? up(ar_, s_, rowvec, (size_t)nseq * C) : nullptr; fo.rv_ld = C;
+    fo.row_b = (rowvec && row_b) ? up(ar_, s_, row_b, (size_t)M) : nullptr;
+    float* dx = up(ar_, s_, x, n);
+    float* dg = up(ar_, s_, g, (size_t)C);
+    float* dbt = up(ar_, s_, b, (size_t)C);
+    void* dy = ar_.alloc(n * 2);
+    launch_fold_ln(s_, dtype, dx, M, C, fo, dg, dbt, 1e-6f, dy);
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(x, dx, n * 4, hipMemcpyDeviceToHost, s_));
+    down_as(ar_, s_, dtype, dy, y, n);
+    sync();
+}
+
+// One layout kernel of kernels_misc.hip on host operands (stn_op_layout).  Every destination is the caller's whole buffer: uploaded as given,
+// downloaded whole.  Every extent a kernel addresses is checked against the buffers here, before anything is launched.
+void Engine::op_layout(int which, int dtype, const int* p, const float* a, int64_t a_n, const float* b, int64_t b_n, const float* c, int64_t c_n,
+                       const int64_t* ids, int64_t ids_n, const int* len, int packed, float* out, int64_t out_n, float* out2, int64_t out2_n,
+                       int* iout, int64_t iout_n) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    auto need = [](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string("stn_op_layout: ") + what); };
+    // rows a destination / source of `rows_per_seq` rows per sequence must hold: the padded B * rows_per_seq, or the packed sum of lengths
+    auto rows_needed = [&](int B, int rows_per_seq) -> int64_t {
+        if (!packed) return (int64_t)B * rows_per_seq;
+        int64_t t = 0;
+        for (int i = 0; i < B; ++i) t += len[i];
+        return t;
+    };
+    auto check_len = [&](int B, int hi, bool required) {
+        need(B > 0 && B <= 1024, "1 <= B <= 1024");
+        need(len || !(required || packed), "lengths needed");
+        if (len) for (int i = 0; i < B; ++i) need(len[i] >= 0 && len[i] <= hi, "a length outside [0, rows per sequence]");
+    };
+    auto row_off = [&](const int* dlen, int B) -> int* {
+        if (!packed) return nullptr;
+        int* off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+        launch_row_map(s_, dlen, B, off, nullptr);
+        return off;
+    };
+    switch (which) {
+    case 0: {  // row_map: p = {B, rows_padded, with_row_b}; iout = row_off [B + 1] then row_b
+        const int B = p[0], rows_padded = p[1], with_b = p[2];
+        need(B > 0 && len && iout && rows_padded >= 0, "row_map: B > 0, lengths and iout needed");
+        if (B > 1024) { launch_row_map(s_, nullptr, B, nullptr, nullptr); return; }  // (the launcher's refusal)
+        int64_t tot = 0;
+        for (int i = 0; i < B; ++i) { need(len[i] >= 0 && len[i] < (1 << 20), "row_map: length out of range"); tot += len[i]; }
+        need(iout_n >= B + 1 + (with_b ? std::max<int64_t>(tot, rows_padded) : 0), "row_map: iout too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        int* d = up(ar_, s_, iout, (size_t)iout_n);
+        launch_row_map(s_, dlen, B, d, with_b ? d + B + 1 : nullptr, rows_padded);
+        STN_HIP(hipMemcpyAsync(iout, d, (size_t)iout_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 1: {  // ncl_to_rows: p = {B, C, L, ld_out}; a [B][C][L]; out rows of ld_out in dtype
+        const int B = p[0], C = p[1], L = p[2], ldo = p[3];
+        need(C > 0 && L > 0 && ldo >= C && a && out, "ncl_to_rows: bad shape");
+        check_len(B, L, false);
+        need(a_n >= (int64_t)B * C * L && out_n >= rows_needed(B, L) * ldo, "ncl_to_rows: buffer too small");
+        const int* dlen = len ? up(ar_, s_, len, (size_t)B) : nullptr;
+        float* da = up(ar_, s_, a, (size_t)a_n);
+        void* d = up_as(ar_, s_, dtype, out, (size_t)out_n);
+        launch_ncl_to_rows(s_, dtype, da, B, C, L, d, ldo, dlen, row_off(dlen, B));
+        down_as(ar_, s_, dtype, d, out, (size_t)out_n);
+        break;
+    }
+    case 2: {  // euler_ncl: p = {B, D, L, with_z, ldz}; a = prev [B][D][L], b = v rows of D, c = dt [B]; out [B][D][L] fp32; out2 = z rows of ldz in dtype
+        const int B = p[0], D = p[1], L = p[2], with_z = p[3], ldz = p[4];
+        need(D > 0 && L > 0 && a && b && c && out && (!with_z || (out2 && ldz >= D)), "euler_ncl: bad shape");
+        check_len(B, L, false);
+        const int64_t vr = rows_needed(B, L);
+        need(a_n >= (int64_t)B * D * L && out_n >= (int64_t)B * D * L && c_n >= B && b_n >= vr * D && (!with_z || out2_n >= vr * ldz), "euler_ncl: buffer too small");
+        const int* dlen = len ? up(ar_, s_, len, (size_t)B) : nullptr;
+        float* dp = up(ar_, s_, a, (size_t)a_n);
+        float* dv = up(ar_, s_, b, (size_t)b_n);
+        float* ddt = up(ar_, s_, c, (size_t)c_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        void* dz = with_z ? up_as(ar_, s_, dtype, out2, (size_t)out2_n) : nullptr;
+        launch_euler_ncl(s_, dp, dv, ddt, dlen, B, D, L, d, row_off(dlen, B), dz, dtype, ldz);
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        if (dz) down_as(ar_, s_, dtype, dz, out2, (size_t)out2_n);
+        break;
+    }
+    case 3: {  // unpack_rows: p = {B, T, W}; a = packed rows [sum len][W]; out [B][T][W] fp32
+        const int B = p[0], T = p[1], W = p[2];
+        need(T > 0 && W > 0 && W % 4 == 0 && a && out, "unpack_rows: bad shape");
+        packed = 1;
+        check_len(B, T, true);
+        need(a_n >= rows_needed(B, T) * W && a_n > 0 && out_n >= (int64_t)B * T * W, "unpack_rows: buffer too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        float* da = up(ar_, s_, a, (size_t)a_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        launch_unpack_rows(s_, da, dlen, row_off(dlen, B), B, T, W, d);
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 4: {  // embed: p = {vocab, B, L, C}; ids [B][L]; a = table [vocab][C]; out rows of C fp32
+        const int vocab = p[0], B = p[1], L = p[2], C = p[3];
+        need(vocab > 0 && L > 0 && C > 0 && C % 4 == 0 && ids && a && out, "embed: bad shape");
+        check_len(B, L, true);
+        need(ids_n >= (int64_t)B * L && a_n >= (int64_t)vocab * C && out_n >= rows_needed(B, L) * C, "embed: buffer too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        int64_t* di = up(ar_, s_, ids, (size_t)ids_n);
+        float* da = up(ar_, s_, a, (size_t)a_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        launch_embed(s_, di, da, vocab, B, L, C, dlen, d, row_off(dlen, B));
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 5: {  // masked_mean: p = {B, L, C}; a = rows of C (rounded to dtype); out [B][C] fp32
+        const int B = p[0], L = p[1], C = p[2];
+        need(L > 0 && C > 0 && a && out, "masked_mean: bad shape");
+        check_len(B, L, true);
+        need(a_n >= rows_needed(B, L) * C && a_n > 0 && out_n >= (int64_t)B * C, "masked_mean: buffer too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        void* da = up_as(ar_, s_, dtype, a, (size_t)a_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        launch_masked_mean(s_, dtype, da, B, L, C, dlen, d, row_off(dlen, B));
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 6: {  // vocoder_im2col: p = {B, L, ld, ccf, k, kp}; a = latent [B][ld*ccf][L]; len = valid vocoder frames; out rows of kp in dtype
+        const int B = p[0], L = p[1], ld = p[2], ccf = p[3], k = p[4], kp = p[5];
+        need(L > 0 && ld > 0 && ccf > 0 && k > 0 && (k & 1) && kp > 0 && a && out, "vocoder_im2col: bad shape");
+        check_len(B, L * ccf, false);
+        need(a_n >= (int64_t)B * ld * ccf * L && out_n >= rows_needed(B, L * ccf) * kp, "vocoder_im2col: buffer too small");
+        const int* dlen = len ? up(ar_, s_, len, (size_t)B) : nullptr;
+        float* da = up(ar_, s_, a, (size_t)a_n);
+        void* d = up_as(ar_, s_, dtype, out, (size_t)out_n);
+        launch_vocoder_im2col(s_, dtype, da, B, L, ld, ccf, k, kp, d, dlen, row_off(dlen, B));
+        down_as(ar_, s_, dtype, d, out, (size_t)out_n);
+        break;
+    }
+    case 7: {  // vocoder_in: p = {B, L, ld, ccf, C, k}; a = latent, b = weights [ld*k][C], c = bias [C]; len = valid vocoder frames; out [B*T][C] fp32
+        const int B = p[0], L = p[1], ld = p[2], ccf = p[3], C = p[4], k = p[5];
+        need(L > 0 && ld > 0 && ccf > 0 && C > 0 && k > 0 && (k & 1) && (int64_t)(8 + k - 1) * ld * 4 <= 64 * 1024 && a && b && c && out, "vocoder_in: bad shape");
+        need(!packed, "vocoder_in: padded rows only");
+        check_len(B, L * ccf, false);
+        need(a_n >= (int64_t)B * ld * ccf * L && b_n >= (int64_t)ld * k * C && c_n >= C && out_n >= (int64_t)B * L * ccf * C, "vocoder_in: buffer too small");
+        const int* dlen = len ? up(ar_, s_, len, (size_t)B) : nullptr;
+        float* da = up(ar_, s_, a, (size_t)a_n);
+        float* dw = up(ar_, s_, b, (size_t)b_n);
+        float* db = up(ar_, s_, c, (size_t)c_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        launch_vocoder_in(s_, da, B, L, ld, ccf, dw, db, C, k, d, dlen);
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    default: need(false, "unknown kernel");
+    }
+    STN_HIP(hipGetLastError());
+    sync();
+}
+
 void Engine::op_randn(uint64_t seed, int B, int D, int L, const int64_t* utt_ids, const int* len, float* out) {
     STN_HIP(hipSetDevice(device_));
     ar_.reset();

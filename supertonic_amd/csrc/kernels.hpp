@@ -231,6 +231,22 @@ void launch_ffn_pack(hipStream_t s, const void* W1, const void* W2, int C, int I
 void launch_dwconv_ln(hipStream_t s, int out_dtype, const float* x, int B, int L, int C, const float* w_t,
                       const float* bias, int k, int dil, const float* ln_g, const float* ln_b, float eps, void* y,
                       const int* seqlen = nullptr, const int* row_off = nullptr);
+// The form a depthwise-conv + LayerNorm call takes — one decision, made by dwconv_ln_form and executed by launch_dwconv_ln, so that what
+// the diagnostics report (stn_dbg_dwconv_ln_form, stn_op_dwconv_ln_ex) is what runs:
+//   DW_V3       dwconv_ln_v3_kernel<OutT, K, R> (C <= 512, k in {5, 7}): combs of R frames; occ4: dwconv_ln_v3_occ4_kernel (k = 7, R = 4, not IEEE half)
+//   DW_V2       dwconv_ln_v2_kernel<OutT, K, 2> (padded rows, fewer than 4096 of them)
+//   DW_GENERIC  dwconv_ln_kernel<OutT, true> (C > 512 or another tap count; padded rows only)
+enum DwconvLnKernel : int { DW_V3 = 0, DW_V2 = 1, DW_GENERIC = 2 };
+struct DwconvLnForm {
+    int out_dtype = F32;
+    int kernel = DW_GENERIC;
+    int K = 0, R = 1;
+    bool occ4 = false;
+    std::string str() const;  // "v3<5,2>", "v3occ4<7,4>", "v2<7>", "generic"
+};
+// packed: rows packed per sequence (row_off given).  Throws std::invalid_argument where the launcher refuses: C % 4, C > 1024, packed with
+// C > 512 or k outside {5, 7}.
+DwconvLnForm dwconv_ln_form(int out_dtype, int B, int L, int C, int k, bool packed);
 // Packed ("ragged") rows: sequence b owns rows row_off[b] .. row_off[b] + len[b] of x / y and nothing else — no padding rows
 // exist.  row_off has B+1 entries (launch_row_map); supported where dwconv_ln_supports_packed(C, k).
 bool dwconv_ln_supports_packed(int C, int k);

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;  // wave-uniform
     const int Lv = (CONV && seqlen) ? seqlen[row / L] : L;       // valid frames of this row's sequence
-    const float live = (CONV && (int)(row % L) >= Lv) ? 0.f : 1.f;  // rows in the padding are written as zeros
+    const bool live = !(CONV && (int)(row % L) >= Lv);           // rows in the padding are written as zeros (+0: a select, not a product)
     const int C4 = C >> 2;
     const float4* x4 = reinterpret_cast<const float4*>(x);
     float4 h[LN_NI];
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict_
         const int c4 = lane + 64 * i;
         if (c4 < C4) {
             const float4 gg = g4[c4], bb = bt4[c4];
-            store4(y + row * C + c4 * 4, live * ((h[i].x - mean) * rstd * gg.x + bb.x), live * ((h[i].y - mean) * rstd * gg.y + bb.y),
-                   live * ((h[i].z - mean) * rstd * gg.z + bb.z), live * ((h[i].w - mean) * rstd * gg.w + bb.w));
+            store4(y + row * C + c4 * 4, live ? (h[i].x - mean) * rstd * gg.x + bb.x : 0.f, live ? (h[i].y - mean) * rstd * gg.y + bb.y : 0.f,
+                   live ? (h[i].z - mean) * rstd * gg.z + bb.z : 0.f, live ? (h[i].w - mean) * rstd * gg.w + bb.w : 0.f);
         }
     }
 }
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void dwconv_ln_v2_kernel(const float* __restri
             for (int j = 0; j < K; ++j) {
                 const int tt = tpos[r] + (j - HALF) * dil;
                 const int tc = tt < 0 ? 0 : (tt >= L ? L - 1 : tt);
-                xv[r][j] = x4[(base[r] + tc) * C4 + cc];  // clamped in-range load; zeroed below when outside [0, lv)
+                xv[r][j] = x4[(base[r] + tc) * C4 + cc];  // clamped in-range load; replaced by zero below when outside [0, lv)
             }
         const float4 bv = b4[cc];
 #pragma unroll
@@ -185,9 +185,11 @@ __global__ __launch_bounds__(256) void dwconv_ln_v2_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < K; ++j) {
                 const int tt = tpos[r] + (j - HALF) * dil;
-                const float keep = (tt >= 0 && tt < lv[r]) ? 1.f : 0.f;
-                a.x = fmaf(wv[j].x * keep, xv[r][j].x, a.x); a.y = fmaf(wv[j].y * keep, xv[r][j].y, a.y);
-                a.z = fmaf(wv[j].z * keep, xv[r][j].z, a.z); a.w = fmaf(wv[j].w * keep, xv[r][j].w, a.w);
+                // a select, not a product with 0: what the clamped load fetched from a padding row may be a NaN or an infinity
+                const bool keep = tt >= 0 && tt < lv[r];
+                const float4 v = keep ? xv[r][j] : make_float4(0.f, 0.f, 0.f, 0.f);
+                a.x = fmaf(wv[j].x, v.x, a.x); a.y = fmaf(wv[j].y, v.y, a.y);
+                a.z = fmaf(wv[j].z, v.z, a.z); a.w = fmaf(wv[j].w, v.w, a.w);
             }
             h[r][i] = act ? a : make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -207,14 +209,14 @@ __global__ __launch_bounds__(256) void dwconv_ln_v2_kernel(const float* __restri
             }
         const float rstd = rsqrtf(wave_sum(v) / (float)C + eps);
         if (!rowok[r]) continue;  // wave-uniform
-        const float live = tpos[r] < lv[r] ? 1.f : 0.f;  // rows in the padding are written as zeros
+        const bool live = tpos[r] < lv[r];  // rows in the padding are written as zeros (+0: a select, not a product)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c4 = lane + 64 * i;
             if (c4 < C4) {
                 const float4 gg = g4[c4], bb = bt4[c4];
-                store4(y + (r0 + r) * C + c4 * 4, live * ((h[r][i].x - mean) * rstd * gg.x + bb.x), live * ((h[r][i].y - mean) * rstd * gg.y + bb.y),
-                       live * ((h[r][i].z - mean) * rstd * gg.z + bb.z), live * ((h[r][i].w - mean) * rstd * gg.w + bb.w));
+                store4(y + (r0 + r) * C + c4 * 4, live ? (h[r][i].x - mean) * rstd * gg.x + bb.x : 0.f, live ? (h[r][i].y - mean) * rstd * gg.y + bb.y : 0.f,
+                       live ? (h[r][i].z - mean) * rstd * gg.z + bb.z : 0.f, live ? (h[r][i].w - mean) * rstd * gg.w + bb.w : 0.f);
             }
         }
     }
@@ -279,8 +281,8 @@ __device__ __forceinline__ void dwconv_ln_v3_body(const float* __restrict__ x, i
             const int hi_ = row_off ? Lv : L;  // clamp inside the rows this sequence owns
             const int tc = tt < 0 ? 0 : (tt >= hi_ ? hi_ - 1 : tt);
             const float4 v = x4[(int64_t)tc * C4 + cc];
-            const float keep = (tt >= 0 && tt < Lv) ? 1.f : 0.f;
-            win[q] = make_float4(v.x * keep, v.y * keep, v.z * keep, v.w * keep);
+            // a select, not a product with 0: what the clamped load fetched from a padding row may be a NaN or an infinity
+            win[q] = (tt >= 0 && tt < Lv) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         const float4 bv = b4[cc];
 #pragma unroll
@@ -351,60 +353,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 }
 
 template <typename OutT, int K, int R>
-static void launch_dwconv_ln_v3_kr(hipStream_t s, const float* x, int nseq, int L, int C, const float* w_t, const float* bias,
-                                   int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen,
-                                   const int* row_off = nullptr) {
+static void launch_dwconv_ln_v3_kr(hipStream_t s, bool occ4, const float* x, int nseq, int L, int C, const float* w_t, const float* bias,
+                                   int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
     const int wps = ((L + R * dil - 1) / (R * dil)) * dil;
     const int64_t nw = (int64_t)nseq * wps;
     static const int xcd_runs = [] { const char* e = stn::dev_env("STN_DWCONV_XCD"); return e ? atoi(e) : 1; }();  // A/B switch
-    // k = 7 combs of four (the vocoder at batch size): 130 VGPRs are three waves per SIMD, 127 are four — 42.5 -> 38.2 us per launch.  (The IEEE-half
-    // instantiation needs 184 and would spill: it keeps the plain kernel.)
-    if (K == 7 && R == 4 && !std::is_same<OutT, f16_t>::value)
-        STN_KLAUNCH((dwconv_ln_v3_occ4_kernel<OutT, K, R>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, x, nseq, L, C, w_t, bias,
-                           dil, wps, g, b, eps, y, seqlen, row_off, xcd_runs);
-    else
+    // (the occ4 kernel exists where dwconv_ln_form can choose it: the IEEE-half instantiation would need 184 VGPRs and spill)
+    if constexpr (K == 7 && R == 4 && !std::is_same<OutT, f16_t>::value) {
+        if (occ4) {
+            STN_KLAUNCH((dwconv_ln_v3_occ4_kernel<OutT, K, R>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, x, nseq, L, C, w_t, bias,
+                               dil, wps, g, b, eps, y, seqlen, row_off, xcd_runs);
+            return;
+        }
+    }
+    if (occ4) throw std::logic_error("dwconv_ln: no occ4 kernel for this form");
     STN_KLAUNCH((dwconv_ln_v3_kernel<OutT, K, R>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, x, nseq, L, C, w_t, bias,
                        dil, wps, g, b, eps, y, seqlen, row_off, xcd_runs);
-}
-
-template <typename OutT>
-static bool launch_dwconv_ln_v3(hipStream_t s, const float* x, int nseq, int L, int C, const float* w_t, const float* bias,
-                                int k, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen,
-                                const int* row_off = nullptr) {
-    if (C > 512 || (k != 5 && k != 7)) return false;
-    // enough wavefronts to fill the chip (256 CUs x ~8): long combs only when there are many frames
-    const int64_t M = (int64_t)nseq * L;
-    if (M >= 32768) {
-        // k = 7 (the vocoder, 60 k frames at C3): combs of 4 measured 51 us per launch against 57 us for combs of 8 (twice the wavefronts
-        // outweigh 2.5 instead of 1.75 loads per output; combs of 2: 58 us)
-        if (k == 5) launch_dwconv_ln_v3_kr<OutT, 5, 8>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    } else if (M >= 4096) {
-        // k = 5 below 16 k frames (the estimator at batch 128: 7.4 k): combs of 2 give twice the wavefronts for 1.5x the loads per output
-        // (9.5 -> 8.7 us per launch)
-        if (k == 5 && M < 16384) launch_dwconv_ln_v3_kr<OutT, 5, 2>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else if (k == 5) launch_dwconv_ln_v3_kr<OutT, 5, 4>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    } else if (row_off) {  // the packed layout only exists in this kernel
-        // (a single utterance: ~15 wavefronts at combs of 4 — combs of 2 halve the serial work per wavefront)
-        if (k == 5 && M < 1024) launch_dwconv_ln_v3_kr<OutT, 5, 2>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else if (k == 5) launch_dwconv_ln_v3_kr<OutT, 5, 4>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, x, nseq, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    } else {
-        return false;  // few frames: one wave per 2 frames (v2) exposes more parallelism
-    }
-    return true;
-}
-
-template <typename OutT>
-static bool launch_dwconv_ln_v2(hipStream_t s, const float* x, int64_t M, int L, int C, const float* w_t, const float* bias,
-                                int k, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen) {
-    constexpr int R = 2;
-    if (C > 512 || (k != 5 && k != 7)) return false;
-    const dim3 grid((unsigned)((M + 4 * R - 1) / (4 * R)));
-    if (k == 5) STN_KLAUNCH((dwconv_ln_v2_kernel<OutT, 5, R>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, dil, g, b, eps, y, seqlen);
-    else STN_KLAUNCH((dwconv_ln_v2_kernel<OutT, 7, R>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, dil, g, b, eps, y, seqlen);
-    return true;
 }
 
 static void check_ln_shape(int C) {
@@ -413,31 +377,77 @@ static void check_ln_shape(int C) {
 
 bool dwconv_ln_supports_packed(int C, int k) { return C <= 512 && C % 4 == 0 && (k == 5 || k == 7); }
 
+std::string DwconvLnForm::str() const {
+    if (kernel == DW_GENERIC) return "generic";
+    char m_[32];
+    if (kernel == DW_V2) snprintf(m_, sizeof m_, "v2<%d>", K);
+    else snprintf(m_, sizeof m_, "%s<%d,%d>", occ4 ? "v3occ4" : "v3", K, R);
+    return m_;
+}
+
+DwconvLnForm dwconv_ln_form(int out_dtype, int B, int L, int C, int k, bool packed) {
+    check_ln_shape(C);
+    if (packed && !dwconv_ln_supports_packed(C, k)) throw std::invalid_argument("packed dwconv_ln needs lengths, C <= 512, k in {5,7}");
+    DwconvLnForm f;
+    f.out_dtype = out_dtype == BF16 || out_dtype == F16 ? out_dtype : F32;
+    f.K = k;
+    if (C > 512 || (k != 5 && k != 7)) return f;  // the generic kernel: one wavefront per frame, run-time tap count
+    // enough wavefronts to fill the chip (256 CUs x ~8): long combs only when there are many frames
+    const int64_t M = (int64_t)B * L;
+    f.kernel = DW_V3;
+    if (M >= 32768) {
+        // k = 7 (the vocoder, 60 k frames at C3): combs of 4 measured 51 us per launch against 57 us for combs of 8 (twice the wavefronts
+        // outweigh 2.5 instead of 1.75 loads per output; combs of 2: 58 us)
+        f.R = k == 5 ? 8 : 4;
+    } else if (M >= 4096) {
+        // k = 5 below 16 k frames (the estimator at batch 128: 7.4 k): combs of 2 give twice the wavefronts for 1.5x the loads per output
+        // (9.5 -> 8.7 us per launch)
+        f.R = k == 5 ? (M < 16384 ? 2 : 4) : 4;
+    } else if (packed) {  // the packed layout only exists in the v3 kernel
+        // (a single utterance: ~15 wavefronts at combs of 4 — combs of 2 halve the serial work per wavefront)
+        f.R = k == 5 ? (M < 1024 ? 2 : 4) : 4;
+    } else {
+        f.kernel = DW_V2;  // few frames: one wave per 2 frames exposes more parallelism
+        f.R = 2;
+    }
+    // k = 7 combs of four (the vocoder at batch size): 130 VGPRs are three waves per SIMD, 127 are four — 42.5 -> 38.2 us per launch.  (The IEEE-half
+    // instantiation needs 184 and would spill: it keeps the plain kernel.)
+    f.occ4 = f.kernel == DW_V3 && f.K == 7 && f.R == 4 && f.out_dtype != F16;
+    return f;
+}
+
+template <typename OutT>
+static void launch_dwconv_ln_t(hipStream_t s, const DwconvLnForm& f, const float* x, int B, int L, int C, const float* w_t, const float* bias,
+                               int k, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
+    const int64_t M = (int64_t)B * L;
+    if (f.kernel == DW_V3) {
+        if (f.K == 5 && f.R == 2) launch_dwconv_ln_v3_kr<OutT, 5, 2>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+        else if (f.K == 5 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 5, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+        else if (f.K == 5 && f.R == 8) launch_dwconv_ln_v3_kr<OutT, 5, 8>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+        else if (f.K == 7 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+        else throw std::logic_error("dwconv_ln: no v3 kernel for form " + f.str());
+    } else if (f.kernel == DW_V2) {
+        constexpr int R = 2;
+        const dim3 grid((unsigned)((M + 4 * R - 1) / (4 * R)));
+        if (f.K == 5) STN_KLAUNCH((dwconv_ln_v2_kernel<OutT, 5, R>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, dil, g, b, eps, y, seqlen);
+        else if (f.K == 7) STN_KLAUNCH((dwconv_ln_v2_kernel<OutT, 7, R>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, dil, g, b, eps, y, seqlen);
+        else throw std::logic_error("dwconv_ln: no v2 kernel for form " + f.str());
+    } else {
+        const dim3 grid((unsigned)((M + 3) / 4));
+        STN_KLAUNCH((dwconv_ln_kernel<OutT, true>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, k, dil, g, b, eps, y, seqlen);
+    }
+}
+
 void launch_dwconv_ln(hipStream_t s, int out_dtype, const float* x, int B, int L, int C, const float* w_t,
                       const float* bias, int k, int dil, const float* ln_g, const float* ln_b, float eps, void* y,
                       const int* seqlen, const int* row_off) {
     check_ln_shape(C);
-    const int64_t M = (int64_t)B * L;
-    if (M == 0) return;
-    if (row_off && (!seqlen || !dwconv_ln_supports_packed(C, k))) { throw std::invalid_argument("packed dwconv_ln needs lengths, C <= 512, k in {5,7}"); }
-    if (out_dtype == BF16 ? launch_dwconv_ln_v3(s, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<uint16_t*>(y), seqlen, row_off)
-        : out_dtype == F16 ? launch_dwconv_ln_v3(s, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<f16_t*>(y), seqlen, row_off)
-                          : launch_dwconv_ln_v3(s, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<float*>(y), seqlen, row_off))
-        return;
-    if (out_dtype == BF16 ? launch_dwconv_ln_v2(s, x, M, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<uint16_t*>(y), seqlen)
-        : out_dtype == F16 ? launch_dwconv_ln_v2(s, x, M, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<f16_t*>(y), seqlen)
-                          : launch_dwconv_ln_v2(s, x, M, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<float*>(y), seqlen))
-        return;
-    const dim3 grid((unsigned)((M + 3) / 4));
-    if (out_dtype == F16)
-        STN_KLAUNCH((dwconv_ln_kernel<f16_t, true>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, k, dil, ln_g,
-                           ln_b, eps, static_cast<f16_t*>(y), seqlen);
-    else if (out_dtype == BF16)
-        STN_KLAUNCH((dwconv_ln_kernel<uint16_t, true>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, k, dil, ln_g,
-                           ln_b, eps, static_cast<uint16_t*>(y), seqlen);
-    else
-        STN_KLAUNCH((dwconv_ln_kernel<float, true>), grid, dim3(256), 0, s, x, M, L, C, w_t, bias, k, dil, ln_g, ln_b,
-                           eps, static_cast<float*>(y), seqlen);
+    if ((int64_t)B * L == 0) return;
+    if (row_off && !seqlen) { throw std::invalid_argument("packed dwconv_ln needs lengths, C <= 512, k in {5,7}"); }
+    const DwconvLnForm f = dwconv_ln_form(out_dtype, B, L, C, k, row_off != nullptr);  // the one place the thresholds live
+    if (f.out_dtype == BF16) launch_dwconv_ln_t(s, f, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<uint16_t*>(y), seqlen, row_off);
+    else if (f.out_dtype == F16) launch_dwconv_ln_t(s, f, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<f16_t*>(y), seqlen, row_off);
+    else launch_dwconv_ln_t(s, f, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<float*>(y), seqlen, row_off);
 }
 
 void launch_layernorm(hipStream_t s, int out_dtype, const float* x, int64_t M, int C, const float* g, const float* b,
