@@ -244,6 +244,62 @@ int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size
 /* op-level: rows x W fp32 (host) -> rows x W samples of encoding enc (host, rows packed): the fetch's store kernel without a gain */
 int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void* y);
 
+/* ---- join ----------------------------------------------------------------------------------------------
+ * Consecutive rows of the finished batch concatenated on the GPU, with a run of silence between them, into G programmes (the chunks of
+ * a long text, cpp/helper.cpp:685-723): a joined fetch delivers [G][W_join] samples instead of [B][W], in any encoding, at the output
+ * rate.  Programme g is seg_0 gap seg_1 gap ... seg_{k-1}: prog_len[g] = sum len_i + (k - 1) * gap_samples[g], W_join = max_g prog_len[g];
+ * every gap and everything behind prog_len[g] in the row is the encoding's zero codeword (0xFF / 0xD5 for the G.711 laws).  prog_dur[g]
+ * is the reference's fp32 sum in member order: d = dur_0; d += dur_i + gap_seconds[g] (cpp/helper.cpp:708,714).  The gap is given in
+ * samples (at the current output rate) and in seconds: each host keeps its own rounding of silence_duration * rate.
+ * Member i's length: STN_JOIN_WHOLE, its own run's whole wave, min(W, ceil(L_i * chunk * P / Q)) samples (cpp/helper.cpp:706-715);
+ * STN_JOIN_TRIM, the first min(that, (int64_t)(duration_i * (float)rate)) of them (rust/src/helper.rs:700-702).
+ * With loudness off, or on with STN_JOIN_GAIN_ROW (every member keeps its own gain g_b), sample s of a segment is the sample the
+ * per-row fetch in the same encoding delivers at that row and column: the joined fetch is byte for byte the host concatenation of
+ * stn_batch_fetch_encoded's rows.  STN_JOIN_GAIN_PROG: the joined fp32 signal, gaps included, is measured as G rows with span
+ * n_g = min(prog_len[g], (int64_t)(prog_dur[g] * (float)rate)) and stored with one gain per programme (the rule of stn_set_loudness).
+ * The join is a fetch argument, not a handle setting: no other fetch changes, the captured pipeline and stn_batch_wav_device_ptr are
+ * untouched, and a joined fetch drops or re-captures no graph.  Refused with STN_ERR_INVALID and a message: rows that do not sum to B, a
+ * count < 1, a negative gap, an unknown mode / scope / encoding, dst_stride < W_join, a buffer that is too small (the message states
+ * the bytes needed); STN_ERR_STATE without a finished batch.  A group (stn_group_*) deals a batch's rows over devices and has no
+ * joined fetch.  DESIGN.md section 13. */
+#define STN_JOIN_WHOLE 0
+#define STN_JOIN_TRIM 1
+#define STN_JOIN_GAIN_ROW 0
+#define STN_JOIN_GAIN_PROG 1
+typedef struct stn_join {
+    int32_t n_prog;              /* G >= 1 */
+    const int32_t* rows;         /* [G] members per programme, each >= 1, sum == B; members are consecutive rows */
+    const int64_t* gap_samples;  /* [G] zeros between two members, at the current output rate, >= 0 */
+    const float* gap_seconds;    /* [G] what the duration sum adds per gap */
+    int32_t mode;                /* STN_JOIN_WHOLE / STN_JOIN_TRIM */
+    int32_t gain_scope;          /* STN_JOIN_GAIN_ROW / STN_JOIN_GAIN_PROG (ignored with loudness off) */
+} stn_join;
+/* host only, no device: the plan for B members of whole lengths member_len (each in [0, W_out]) and durations member_dur at rate hz
+ * (hz is used by STN_JOIN_TRIM only).  Out: *W_join, prog_len [G], prog_dur [G]; seg_len [B] (the members' lengths under j->mode) and
+ * seg_dst [B] (their first sample in the programme's row), each of the two may be NULL.  STN_ERR_INVALID for a refused argument
+ * (stn_join_plan_error says why). */
+int stn_join_plan(const stn_join* j, int B, int64_t W_out, int hz, const int64_t* member_len, const float* member_dur, int64_t* W_join,
+                  int64_t* prog_len, float* prog_dur, int64_t* seg_len_or_null, int64_t* seg_dst_or_null);
+const char* stn_join_plan_error(void);
+/* the plan of the finished batch under j: *W_join, prog_len [G] and prog_dur [G] (each may be NULL) */
+int stn_batch_join_dims(stn_handle* h, const stn_join* j, int64_t* W_join, int64_t* prog_len, float* prog_dur);
+/* G * W_join * stn_encoding_bytes(enc) bytes into dst, rows packed (dst may be NULL: lengths and durations only) */
+int stn_batch_fetch_joined(stn_handle* h, const stn_join* j, int enc, void* dst, size_t capacity_bytes, int64_t* prog_len, float* prog_dur);
+/* the joined rows into a device buffer, rows dst_stride samples apart (>= W_join), on the handle's stream */
+int stn_batch_copy_joined_device(stn_handle* h, const stn_join* j, int enc, void* dst_device, int64_t dst_stride);
+/* the pipelined fetch of the joined rows; ended by stn_batch_fetch_encoded_end (durations: prog_dur [G]); stn_batch_fetch_slot_dims
+ * reports G and W_join */
+int stn_batch_fetch_joined_begin(stn_handle* h, int slot, const stn_join* j, int enc);
+/* the joined signal at the output rate measured as G programmes, whether normalization is on or not: L_g (LUFS), peak_g and the gain
+ * STN_JOIN_GAIN_PROG applies under the current setting (1 when off); each pointer [G] floats or NULL */
+int stn_batch_join_loudness(stn_handle* h, const stn_join* j, float* lufs, float* peak, float* gain);
+/* op-level, host operands: rows x W fp32 at hz, row r's first n[r] samples are member r's segment (j->mode is not applied) -> y
+ * [G][W_join] samples of enc, rows packed (W_join as stn_join_plan gives it).  loudness_on: every programme measured over its prog_len
+ * samples and stored with its own gain, *prog_lufs / *prog_peak / *prog_gain [G] (each may be NULL; with loudness off the gain is 1
+ * and nothing is measured unless one of them is asked for). */
+int stn_op_join(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, int loudness_on,
+                float target_lufs, float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain);
+
 /* ---- output rate ---------------------------------------------------------------------------------------
  * The model synthesizes at its own rate (stn_arch.sample_rate, 44.1 kHz for the published model; the reference's hosts can only
  * return that: cpp/helper.cpp:943-990).  With an output rate set, every fetch path — stn_batch_fetch, stn_batch_fetch_pcm16,

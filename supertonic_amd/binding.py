@@ -44,6 +44,52 @@ def encoded_empty(enc, rows, W):
     return np.empty((rows, W), {ENC_F32: np.float32, ENC_PCM16: np.int16}.get(e, np.uint8))
 
 
+# a joined fetch (stn_join, include/stn.h)
+JOIN_WHOLE, JOIN_TRIM = 0, 1
+JOIN_MODES = {"whole": JOIN_WHOLE, "trim": JOIN_TRIM, JOIN_WHOLE: JOIN_WHOLE, JOIN_TRIM: JOIN_TRIM}
+JOIN_GAIN_ROW, JOIN_GAIN_PROG = 0, 1
+JOIN_SCOPES = {"row": JOIN_GAIN_ROW, "programme": JOIN_GAIN_PROG, "prog": JOIN_GAIN_PROG, JOIN_GAIN_ROW: JOIN_GAIN_ROW, JOIN_GAIN_PROG: JOIN_GAIN_PROG}
+
+
+class StnJoin(ctypes.Structure):
+    _fields_ = [("n_prog", ctypes.c_int32), ("rows", ctypes.c_void_p), ("gap_samples", ctypes.c_void_p), ("gap_seconds", ctypes.c_void_p),
+                ("mode", ctypes.c_int32), ("gain_scope", ctypes.c_int32)]
+
+
+def _join(rows, gap_samples, gap_seconds, mode="whole", gain_scope="row"):
+    """(stn_join, the arrays it points to).  rows: members per programme; the gaps: one value, or one per programme.  mode and
+    gain_scope: a name of JOIN_MODES / JOIN_SCOPES, or any integer (passed on as given: the library refuses what it does not know)."""
+    rows = np.ascontiguousarray(np.atleast_1d(rows), np.int32)
+    G = rows.size
+    gs = np.ascontiguousarray(np.broadcast_to(np.asarray(gap_samples, np.int64), (G,)))
+    gt = np.ascontiguousarray(np.broadcast_to(np.asarray(gap_seconds, np.float32), (G,)))
+    j = StnJoin(G, rows.ctypes.data, gs.ctypes.data, gt.ctypes.data, int(JOIN_MODES.get(mode, mode)), int(JOIN_SCOPES.get(gain_scope, gain_scope)))
+    return j, (rows, gs, gt)
+
+
+def join_plan(rows, gap_samples, gap_seconds, member_len, member_dur, W_out, hz, mode="whole", gain_scope="row"):
+    """stn_join_plan (host only, no device): B members of whole lengths member_len (each within [0, W_out]) and durations member_dur at
+    rate hz, joined into len(rows) programmes -> dict(W_join, prog_len [G], prog_dur [G] float32, seg_len [B], seg_dst [B]).
+    A refused argument raises StnError(STN_ERR_INVALID) with the reason."""
+    L = load()
+    L.stn_join_plan.argtypes = [ctypes.POINTER(StnJoin), ctypes.c_int, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 7
+    L.stn_join_plan_error.restype = ctypes.c_char_p
+    j, keep = _join(rows, gap_samples, gap_seconds, mode, gain_scope)
+    ml = np.ascontiguousarray(np.atleast_1d(member_len), np.int64)
+    md = np.ascontiguousarray(np.atleast_1d(member_dur), np.float32)
+    if md.size != ml.size:
+        raise ValueError("member_len and member_dur must have one entry per member")
+    B, G = ml.size, keep[0].size
+    wj = ctypes.c_int64()
+    prog_len, prog_dur = np.zeros(G, np.int64), np.zeros(G, np.float32)
+    seg_len, seg_dst = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    rc = L.stn_join_plan(ctypes.byref(j), B, int(W_out), int(hz), ml.ctypes.data, md.ctypes.data, ctypes.addressof(wj), prog_len.ctypes.data,
+                         prog_dur.ctypes.data, seg_len.ctypes.data, seg_dst.ctypes.data)
+    if rc != 0:
+        raise StnError(rc, L.stn_join_plan_error().decode())
+    return {"W_join": wj.value, "prog_len": prog_len, "prog_dur": prog_dur, "seg_len": seg_len, "seg_dst": seg_dst}
+
+
 class StnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"stn error {code}: {msg}")
@@ -258,6 +304,13 @@ def load():
     L.stn_batch_fetch_encoded_begin.argtypes = [vp, ci, ci]
     L.stn_batch_fetch_encoded_end.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), vp]
     L.stn_op_encode.argtypes = [vp, ci, ci, ci, _f32p, vp]
+    jp = ctypes.POINTER(StnJoin)
+    L.stn_batch_join_dims.argtypes = [vp, jp, ctypes.POINTER(ctypes.c_int64), vp, vp]
+    L.stn_batch_fetch_joined.argtypes = [vp, jp, ci, vp, ctypes.c_size_t, vp, vp]
+    L.stn_batch_copy_joined_device.argtypes = [vp, jp, ci, vp, ctypes.c_int64]
+    L.stn_batch_fetch_joined_begin.argtypes = [vp, ci, jp, ci]
+    L.stn_batch_join_loudness.argtypes = [vp, jp, vp, vp, vp]
+    L.stn_op_join.argtypes = [vp, ci, ci, ci, _f32p, _i64p, jp, ci, ci, cf, cf, vp, vp, vp, vp]
     L.stn_group_set_encoding.argtypes = [vp, ci]
     L.stn_group_fetch_encoded.argtypes = [vp, vp, ctypes.c_size_t, vp]
     L.stn_group_last_shards.argtypes = [vp, _i32p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")]
@@ -688,6 +741,71 @@ class Engine:
         out, dur = encoded_empty(e, B, W), np.empty(B, np.float32)
         self._ck(self._lib.stn_batch_fetch_encoded(self._h, e, out.ctypes.data, out.nbytes, dur.ctypes.data))
         return out, dur
+
+    def batch_join_dims(self, rows, gap_samples, gap_seconds, mode="whole", gain_scope="row"):
+        """The finished batch's plan under a join -> (W_join, prog_len [G] int64, prog_dur [G] float32)."""
+        j, keep = _join(rows, gap_samples, gap_seconds, mode, gain_scope)
+        G = keep[0].size
+        wj, prog_len, prog_dur = ctypes.c_int64(), np.zeros(G, np.int64), np.zeros(G, np.float32)
+        self._ck(self._lib.stn_batch_join_dims(self._h, ctypes.byref(j), ctypes.byref(wj), prog_len.ctypes.data, prog_dur.ctypes.data))
+        return wj.value, prog_len, prog_dur
+
+    def batch_fetch_joined(self, rows, gap_samples, gap_seconds, mode="whole", gain_scope="row", encoding=None, cut=True):
+        """Consecutive rows of the finished batch joined on the GPU into len(rows) programmes (rows[g] members each, gap_samples[g] samples
+        of silence between two members, gap_seconds[g] added to the duration per gap) -> (list of G arrays cut at prog_len, prog_dur [G]);
+        cut=False: (the padded [G, W_join] array, prog_len, prog_dur).  mode "whole" | "trim", gain_scope "row" | "programme" (with
+        loudness normalization on: one gain per member row, or one per programme measured as a whole).  encoding: as batch_fetch_encoded
+        (None: float32)."""
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        j, keep = _join(rows, gap_samples, gap_seconds, mode, gain_scope)
+        G = keep[0].size
+        wj, prog_len, prog_dur = ctypes.c_int64(), np.zeros(G, np.int64), np.zeros(G, np.float32)
+        self._ck(self._lib.stn_batch_join_dims(self._h, ctypes.byref(j), ctypes.byref(wj), None, None))
+        out = encoded_empty(e, G, wj.value)
+        self._ck(self._lib.stn_batch_fetch_joined(self._h, ctypes.byref(j), e, out.ctypes.data, out.nbytes, prog_len.ctypes.data, prog_dur.ctypes.data))
+        if not cut:
+            return out, prog_len, prog_dur
+        return [out[g, : int(prog_len[g])] for g in range(G)], prog_dur
+
+    def fetch_joined_begin(self, slot, rows, gap_samples, gap_seconds, mode="whole", gain_scope="row", encoding=None):
+        """fetch_encoded_begin of the joined rows; ended by fetch_encoded_end -> (samples [G, W_join], prog_dur [G])."""
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        j, _keep = _join(rows, gap_samples, gap_seconds, mode, gain_scope)
+        self._ck(self._lib.stn_batch_fetch_joined_begin(self._h, int(slot), ctypes.byref(j), e))
+        self._slot_enc[int(slot)] = e
+
+    def batch_copy_joined_device(self, rows, gap_samples, gap_seconds, dst_ptr, dst_stride, mode="whole", gain_scope="row", encoding=None):
+        """Device->device copy of the joined rows in an encoding; dst_stride in samples (>= W_join)."""
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        j, _keep = _join(rows, gap_samples, gap_seconds, mode, gain_scope)
+        self._ck(self._lib.stn_batch_copy_joined_device(self._h, ctypes.byref(j), e, dst_ptr, dst_stride))
+
+    def batch_join_loudness(self, rows, gap_samples, gap_seconds, mode="whole"):
+        """The joined signal measured as programmes -> (lufs [G], peak [G], gain [G]); gain: what gain_scope="programme" applies."""
+        j, keep = _join(rows, gap_samples, gap_seconds, mode, JOIN_GAIN_PROG)
+        G = keep[0].size
+        lufs, peak, gain = (np.empty(G, np.float32) for _ in range(3))
+        self._ck(self._lib.stn_batch_join_loudness(self._h, ctypes.byref(j), lufs.ctypes.data, peak.ctypes.data, gain.ctypes.data))
+        return lufs, peak, gain
+
+    def op_join(self, x, n, rows, gap_samples, hz, encoding=None, loudness=None, measure=False):
+        """rows x W fp32 at hz, row r's first n[r] samples member r's segment, joined on the GPU -> y [G, W_join] in the encoding
+        (encoded_empty's dtypes).  loudness = (target LUFS, ceiling dBFS): every programme normalized as a whole; then, or with
+        measure=True, returns (y, lufs [G], peak [G], gain [G])."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        R, W = x.shape
+        nn = np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (R,)))
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        j, keep = _join(rows, gap_samples, 0.0)
+        G = keep[0].size
+        plan = join_plan(rows, gap_samples, 0.0, nn, np.zeros(R, np.float32), W, hz)
+        y = encoded_empty(e, G, plan["W_join"])
+        lufs, peak, gain = (np.empty(G, np.float32) for _ in range(3))
+        want = loudness is not None or measure
+        t, c = loudness if loudness is not None else (-23.0, -1.0)
+        self._ck(self._lib.stn_op_join(self._h, int(hz), R, W, x, nn, ctypes.byref(j), e, int(loudness is not None), float(t), float(c), y.ctypes.data,
+                                       lufs.ctypes.data if want else None, peak.ctypes.data if want else None, gain.ctypes.data if want else None))
+        return (y, lufs, peak, gain) if want else y
 
     def fetch_encoded_begin(self, slot, enc):
         """fetch_pcm16_begin in an encoding."""

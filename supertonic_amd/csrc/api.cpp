@@ -405,6 +405,34 @@ int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size
 int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void* y) {
     STN_TRY(h, { need(rows > 0 && W > 0 && x && y, "stn_op_encode: bad argument (rows >= 1, W >= 1, x and y)"); h->eng->op_encode(enc, rows, W, x, y); })
 }
+static_assert(STN_JOIN_WHOLE == 0 && STN_JOIN_TRIM == 1 && STN_JOIN_GAIN_ROW == 0 && STN_JOIN_GAIN_PROG == 1, "include/stn.h: join constants");
+static void need_batch(stn_handle* h) {
+    if (!(h->eng->batch().B > 0 && h->eng->batch().L > 0)) throw std::runtime_error("no finished batch");  // (STN_ERR_STATE)
+}
+int stn_batch_join_dims(stn_handle* h, const stn_join* j, int64_t* W_join, int64_t* prog_len, float* prog_dur) {
+    STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h);
+                 const stn::JoinPlan p = h->eng->batch_join_plan(j);
+                 if (W_join) *W_join = p.W_join;
+                 if (prog_len) std::copy(p.prog_len.begin(), p.prog_len.end(), prog_len);
+                 if (prog_dur) std::copy(p.prog_dur.begin(), p.prog_dur.end(), prog_dur); })
+}
+int stn_batch_fetch_joined(stn_handle* h, const stn_join* j, int enc, void* dst, size_t cap, int64_t* prog_len, float* prog_dur) {
+    STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h); h->eng->batch_fetch_joined(j, enc, dst, cap, prog_len, prog_dur); })
+}
+int stn_batch_copy_joined_device(stn_handle* h, const stn_join* j, int enc, void* dst, int64_t stride) {
+    STN_TRY(h, { need(j != nullptr && dst != nullptr, "join or dst is null"); need_batch(h); h->eng->batch_copy_joined_device(j, enc, dst, stride); })
+}
+int stn_batch_fetch_joined_begin(stn_handle* h, int slot, const stn_join* j, int enc) {
+    STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h); h->eng->batch_fetch_joined_begin(slot, j, enc); })
+}
+int stn_batch_join_loudness(stn_handle* h, const stn_join* j, float* lufs, float* peak, float* gain) {
+    STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h); h->eng->batch_join_loudness(j, lufs, peak, gain); })
+}
+int stn_op_join(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, int loudness_on, float target_lufs,
+                float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && n && j && y, "stn_op_join: bad argument (1 <= rows <= 65535, W >= 1, x, n, j and y)");
+                 h->eng->op_join(hz, rows, W, x, n, j, enc, loudness_on != 0, target_lufs, ceiling_dbfs, y, prog_lufs, prog_peak, prog_gain); })
+}
 int stn_batch_copy_wav_device(stn_handle* h, void* dst, int64_t stride) {
     STN_TRY(h, { need(dst != nullptr, "dst is null"); h->eng->batch_copy_wav_device(static_cast<float*>(dst), stride); })
 }

@@ -4,7 +4,9 @@
 // --dtype {fp32,bf16,fp16}, --seed S (0 = unseeded noise, like the reference), --sample-rate HZ (WAV files at HZ, resampled on the GPU;
 // absent: the model's rate), --loudness LUFS (every utterance normalized to that BS.1770-4 integrated loudness on the GPU; absent: off),
 // --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1), --encoding {pcm16,pcm24,f32,mulaw,alaw} (sample format
-// of the WAV files, encoded on the GPU; default pcm16, writeWavFile's files).
+// of the WAV files, encoded on the GPU; default pcm16, writeWavFile's files), --loudness-scope {chunk,text} (a long text with --loudness:
+// every chunk normalized on its own, the default, or the joined text as one programme with one gain; text needs one GPU),
+// --trim-chunks (a long text's chunks cut at their durations before they are joined).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -68,6 +70,12 @@ int main(int argc, char* argv[]) {
             opts.encoding = e == "pcm16" ? STN_ENC_PCM16 : e == "pcm24" ? STN_ENC_PCM24 : e == "f32" ? STN_ENC_F32 : e == "mulaw" ? STN_ENC_MULAW : e == "alaw" ? STN_ENC_ALAW : -1;
             if (opts.encoding < 0) { std::cerr << "Error: --encoding " << e << ": one of pcm16, pcm24, f32, mulaw, alaw\n"; return 1; }
         }
+        else if (a == "--loudness-scope" && more) {  // long texts with --loudness: every chunk its own gain (chunk), or the joined text one gain (text)
+            const std::string v = argv[++i];
+            if (v != "chunk" && v != "text") { std::cerr << "Error: --loudness-scope " << v << ": chunk or text\n"; return 1; }
+            opts.loudness_scope_text = v == "text";
+        }
+        else if (a == "--trim-chunks") opts.trim_chunks = true;  // long texts: every chunk cut at its duration before the join
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (voice_style.size() != text.size()) {

@@ -184,6 +184,7 @@ Engine::~Engine() {
     lo_release();
     if (out_f32_) (void)hipFree(out_f32_);
     if (out_enc_) (void)hipFree(out_enc_);
+    if (join_tab_) (void)hipFree(join_tab_);
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);
         if (f.dev) (void)hipFree(f.dev);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/stn_arch.h"
+#include "host/join_plan.hpp"
 #include "kernels.hpp"
 
 namespace stn {
@@ -260,6 +261,17 @@ class Engine {
     void batch_copy_encoded_device(int enc, void* dst, int64_t dst_stride);  // dst_stride in samples
     // rows x W fp32 (host) -> rows x W samples of encoding enc (host, enc_bytes(enc) each): the store kernel without a gain
     void op_encode(int enc, int rows, int W, const float* x, void* y);
+    // ---- join (include/stn.h "join"): consecutive rows concatenated with gaps into programmes by the output
+    // stage; every fetch path above with a join delivers [G][W_join] instead of [B][W].  A fetch argument: nothing here is handle state.
+    JoinPlan batch_join_plan(const stn_join* j);  // the finished batch's plan at the current output rate (throws what the ABI refuses)
+    void batch_fetch_joined(const stn_join* j, int enc, void* dst, size_t capacity_bytes, int64_t* prog_len, float* prog_dur);
+    void batch_fetch_joined_begin(int slot, const stn_join* j, int enc);  // ended by batch_fetch_encoded_end (durations: prog_dur)
+    void batch_copy_joined_device(const stn_join* j, int enc, void* dst, int64_t dst_stride);
+    void batch_join_loudness(const stn_join* j, float* lufs, float* peak, float* gain);  // [G] host floats or null
+    // rows x W fp32 (host) at hz, row r's first n[r] samples its segment -> y [G][W_join] samples of enc (host); with loudness, every
+    // programme measured over its whole length and stored with its own gain
+    void op_join(int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, bool loudness_on, float target_lufs,
+                 float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain);
 
     // ---- output rate (engine_resample.cpp): 0 or the model's rate = off (the default; every fetch path is then exactly the
     // native one).  On, every fetch path resamples the finished waveform on the handle's stream before its copy (kernels_resample.hip);
@@ -507,13 +519,30 @@ class Engine {
     void lo_prepare(LoudTable& t, int hz);
     void lo_release();
     // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain]
-    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on);
+    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling);
+    // rows x W fp32 on the device (x) with row spans n measured on the stream against table t: returns res (device [3][rows]: L, peak,
+    // gain).  n is uploaded only when it differs from what the scratch holds.
+    float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling);
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
     float* lo_batch(const float* x, int64_t Wo, bool on);
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
     // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
-    struct OutRows { void* dst = nullptr; int enc = ENC_F32; int64_t stride = 0; };
+    // With a join plan the G programme rows of the plan instead of the B rows (scope: STN_JOIN_GAIN_*)
+    struct OutRows { void* dst = nullptr; int enc = ENC_F32; int64_t stride = 0; const JoinPlan* join = nullptr; int scope = 0; };
     void enqueue_output(const OutRows& o);
+    void enqueue_joined(const OutRows& o);
+    void slot_begin(int slot, OutRows o, int64_t rows, int64_t width, const std::vector<float>& dur);  // the pipelined fetch behind both _begin calls
+    // the joined fp32 signal of the finished batch at the output rate in the fetch scratch (rows W_join apart) and its measurement
+    // (device [3][G]); the two halves of a per-programme gain
+    const float* join_f32(const JoinPlan& p);
+    float* join_measure(const JoinPlan& p, const float* joined, bool on);
+    // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
+    struct JoinTables { const JoinSeg* seg; const JoinProg* prog; };
+    JoinTables join_tables(const JoinPlan& p);
+    static std::vector<int64_t> join_table_words(const JoinPlan& p, const int64_t* src_row_or_null);
+    void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride);
+    int64_t* join_tab_ = nullptr; size_t join_tab_cap_ = 0;
+    std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
     bool out_native() const;             // neither resampled nor normalized: the delivered fp32 rows are b.wav itself
     const float* out_source(int64_t Wo);  // the finished batch at the output rate: b.wav, or resampled into the fp32 scratch

@@ -444,6 +444,7 @@ const float* Engine::out_source(int64_t Wo) {
     return d;
 }
 
+static int64_t join_stride(const JoinPlan& p);
 static int need_enc(int enc) {
     const int eb = enc_bytes(enc);
     if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
@@ -453,6 +454,7 @@ static int need_enc(int enc) {
 // Loudness on: the rows at the output rate are measured, then stored with the gain in the encoding.  Off: resampled straight into the
 // destination in the encoding when a rate is set; at the native rate encoded by the store kernel, or (fp32) copied.
 void Engine::enqueue_output(const OutRows& o) {
+    if (o.join) { enqueue_joined(o); return; }
     const Batch& b = bt_;
     const int eb = need_enc(o.enc);
     const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
@@ -517,9 +519,21 @@ void Engine::batch_fetch_encoded(int enc, void* dst, size_t capacity_bytes, floa
 }
 void Engine::batch_fetch_encoded_begin(int slot, int enc) {
     if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
-    const int eb = need_enc(enc);
+    need_enc(enc);
     const int64_t Wo = out_row_len();
-    const size_t nw = (size_t)bt_.B * Wo, bytes = nw * eb;
+    slot_begin(slot, {nullptr, enc, Wo}, bt_.B, Wo, reported_dur_);
+}
+void Engine::batch_fetch_joined_begin(int slot, const stn_join* j, int enc) {
+    if (slot < 0 || slot > 1) throw std::invalid_argument("fetch slot must be 0 or 1");
+    need_enc(enc);
+    const JoinPlan p = batch_join_plan(j);
+    slot_begin(slot, {nullptr, enc, join_stride(p), &p, j->gain_scope}, p.G, p.W_join, p.prog_dur);  // (the slot hands out G rows of W_join: fetch_slot_dims)
+}
+// rows of `width` samples through the output stage into the slot's device buffer, o.stride >= width samples apart (o.dst is set here), then
+// packed into its pinned buffer on the copy stream
+void Engine::slot_begin(int slot, OutRows o, int64_t rows, int64_t width, const std::vector<float>& dur) {
+    const size_t eb = (size_t)enc_bytes(o.enc), nw = (size_t)rows * width, bytes = (size_t)rows * o.stride * eb;
+    const int enc = o.enc;
     FetchSlot& f = fetch_[slot];
     if (!copy_s_) STN_HIP(hipStreamCreateWithFlags(&copy_s_, hipStreamNonBlocking));
     if (!f.ready) { STN_HIP(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming)); STN_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming)); }
@@ -533,14 +547,16 @@ void Engine::batch_fetch_encoded_begin(int slot, int enc) {
         STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&f.pin), cap, hipHostMallocDefault));
         f.cap = cap;
     }
-    enqueue_output({f.dev, enc, Wo});
+    o.dst = f.dev;
+    enqueue_output(o);
     STN_HIP(hipEventRecord(f.ready, s_));
     STN_HIP(hipStreamWaitEvent(copy_s_, f.ready, 0));
-    STN_HIP(hipMemcpyAsync(f.pin, f.dev, bytes, hipMemcpyDeviceToHost, copy_s_));
+    if (o.stride == width || rows == 1) STN_HIP(hipMemcpyAsync(f.pin, f.dev, nw * eb, hipMemcpyDeviceToHost, copy_s_));
+    else STN_HIP(hipMemcpy2DAsync(f.pin, (size_t)width * eb, f.dev, (size_t)o.stride * eb, (size_t)width * eb, (size_t)rows, hipMemcpyDeviceToHost, copy_s_));
     STN_HIP(hipEventRecord(f.done, copy_s_));
     f.n = nw;
     f.enc = enc;
-    f.dur = reported_dur_;
+    f.dur = dur;
     f.busy = true;
 }
 void Engine::batch_fetch_encoded_end(int slot, const void** data, size_t* n_bytes, float* duration) {
@@ -575,6 +591,199 @@ void Engine::op_encode(int enc, int rows, int W, const float* x, void* y) {
     launch_store_rows(s_, dx, rows, W, nullptr, enc, dy, W);
     STN_HIP(hipGetLastError());
     STN_HIP(hipMemcpyAsync(y, dy, n * eb, hipMemcpyDeviceToHost, s_));
+    sync();
+}
+// =================================================================================================
+// join: the output stage's joined form
+// =================================================================================================
+
+JoinPlan Engine::batch_join_plan(const stn_join* j) {
+    const int64_t Wo = out_row_len();  // (throws without a finished batch)
+    const Batch& b = bt_;
+    const int64_t cs = (int64_t)a_.base_chunk_size * a_.chunk_compress_factor;
+    // member i's whole wave: what its own run would return, L_i * chunk samples at the output rate (cpp/helper.cpp:706-715)
+    std::vector<int64_t> len((size_t)b.B);
+    for (int i = 0; i < b.B; ++i) len[(size_t)i] = std::min<int64_t>(Wo, out_len((int64_t)b.h_llen[(size_t)i] * cs));
+    JoinPlan p;
+    const std::string why = join_plan(j, b.B, Wo, output_rate(), len.data(), reported_dur_.data(), p);
+    if (!why.empty()) throw std::invalid_argument(why);
+    if (p.G > 65535) throw std::invalid_argument("join: more than 65535 programmes");
+    return p;
+}
+
+// [B] members {dst, len, source row} then [G] programmes {len, first | count << 32}: the words of JoinSeg / JoinProg
+std::vector<int64_t> Engine::join_table_words(const JoinPlan& p, const int64_t* src_row) {
+    static_assert(sizeof(JoinSeg) == 24 && sizeof(JoinProg) == 16, "the join tables are uploaded as int64 words");
+    std::vector<int64_t> w((size_t)p.B * 3 + (size_t)p.G * 2);
+    for (int i = 0; i < p.B; ++i) {
+        w[(size_t)i * 3] = p.seg_dst[(size_t)i];
+        w[(size_t)i * 3 + 1] = p.seg_len[(size_t)i];
+        w[(size_t)i * 3 + 2] = src_row ? src_row[i] : i;
+    }
+    for (int g = 0; g < p.G; ++g) {
+        const int32_t first = p.first[(size_t)g], count = (g + 1 < p.G ? p.first[(size_t)g + 1] : p.B) - first;
+        JoinProg pg{p.prog_len[(size_t)g], first, count};
+        std::memcpy(&w[(size_t)p.B * 3 + (size_t)g * 2], &pg, sizeof(pg));
+    }
+    return w;
+}
+
+Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
+    std::vector<int64_t> w = join_table_words(p, nullptr);
+    const bool moved = !join_tab_ || w.size() > join_tab_cap_;
+    int64_t* d = out_grow(*this, join_tab_, join_tab_cap_, w.size());
+    if (moved || w != join_tab_host_) {  // later fetches of the same batch under the same join reuse the upload
+        join_tab_host_ = std::move(w);
+        STN_HIP(hipMemcpyAsync(d, join_tab_host_.data(), join_tab_host_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    }
+    return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
+}
+
+void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride) {
+    const char* saved = stage_;
+    stage_ = "out";
+    if (prof_on_) prof_begin("join", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + enc_bytes(enc)));
+    launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
+    if (prof_on_) prof_end();
+    stage_ = saved;
+    STN_HIP(hipGetLastError());
+}
+
+// the fetch scratch of a joined fetch: the resampled rows (when a rate is set) in front, the joined fp32 rows (per-programme gain) behind
+static size_t join_f32_offset(size_t n_rows) { return (n_rows + 3) / 4 * 4; }
+
+const float* Engine::join_f32(const JoinPlan& p) {
+    const Batch& b = bt_;
+    const int64_t Wo = out_row_len();
+    const size_t off = resample_on() ? join_f32_offset((size_t)b.B * Wo) : 0;
+    float* base = out_f32_buf(off + (size_t)p.G * p.W_join);  // (sized once: out_source below then finds room and moves nothing)
+    const float* src = out_source(Wo);
+    join_enqueue(src, resample_on() ? Wo : (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, join_tables(p), p, nullptr, ENC_F32, base + off, p.W_join);
+    return base + off;
+}
+
+float* Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
+    const int hz = output_rate();
+    lo_prepare(lo_, hz);
+    // programme g's span: what the reference's hosts write to a file, its duration at the output rate (section 11's rule)
+    std::vector<int64_t> n((size_t)p.G);
+    for (int g = 0; g < p.G; ++g)
+        n[(size_t)g] = std::max<int64_t>(0, std::min<int64_t>(p.prog_len[(size_t)g], (int64_t)(p.prog_dur[(size_t)g] * (float)hz)));
+    return lo_rows(lo_, joined, p.G, p.W_join, std::move(n), on, lo_target_, lo_ceiling_);
+}
+
+// Loudness off: one join launch behind the optional resample.  On, per member row: the rows measured as every fetch measures them, then
+// the join with g_b.  On, per programme: joined as fp32, measured as G rows, stored with g_g by the store kernel.
+void Engine::enqueue_joined(const OutRows& o) {
+    const Batch& b = bt_;
+    const JoinPlan& p = *o.join;
+    const int eb = need_enc(o.enc);
+    const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    if (o.stride < p.W_join) throw std::invalid_argument("dst_stride smaller than the joined length W_join = " + std::to_string(p.W_join));
+    if (p.W_join == 0) return;
+    if (loudness_on() && o.scope == STN_JOIN_GAIN_PROG) {
+        const float* joined = join_f32(p);
+        const float* g = join_measure(p, joined, true) + 2 * (int64_t)p.G;
+        const char* saved = stage_;
+        stage_ = "out";
+        if (prof_on_) prof_begin("loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
+        launch_store_rows(s_, joined, p.G, p.W_join, g, o.enc, o.dst, o.stride);
+        if (prof_on_) prof_end();
+        stage_ = saved;
+        STN_HIP(hipGetLastError());
+        return;
+    }
+    const float* src = out_source(Wo);
+    const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
+    join_enqueue(src, resample_on() ? Wo : W, join_tables(p), p, g, o.enc, o.dst, o.stride);
+}
+
+static int64_t join_stride(const JoinPlan& p) { return (p.W_join + 15) / 16 * 16; }  // a multiple of every encoding's vector
+
+static void copy_plan(const JoinPlan& p, int64_t* prog_len, float* prog_dur) {
+    if (prog_len) std::copy(p.prog_len.begin(), p.prog_len.end(), prog_len);
+    if (prog_dur) std::copy(p.prog_dur.begin(), p.prog_dur.end(), prog_dur);
+}
+
+void Engine::batch_fetch_joined(const stn_join* j, int enc, void* dst, size_t capacity_bytes, int64_t* prog_len, float* prog_dur) {
+    const int eb = need_enc(enc);
+    const JoinPlan p = batch_join_plan(j);
+    if (dst) {
+        const size_t bytes = (size_t)p.G * p.W_join * eb;
+        if (capacity_bytes < bytes) throw std::invalid_argument("joined buffer too small: need " + std::to_string(bytes) + " bytes");
+        if (bytes) {
+            // on the device the rows lie join_stride samples apart, so that every row starts 16-byte aligned and the join stores full
+            // width whatever W_join is; the copy packs them
+            const int64_t Ws = join_stride(p);
+            void* d = out_enc_buf((size_t)p.G * Ws * eb);
+            enqueue_output({d, enc, Ws, &p, j->gain_scope});
+            if (Ws == p.W_join || p.G == 1) STN_HIP(hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, s_));
+            else STN_HIP(hipMemcpy2DAsync(dst, (size_t)p.W_join * eb, d, (size_t)Ws * eb, (size_t)p.W_join * eb, (size_t)p.G, hipMemcpyDeviceToHost, s_));
+        }
+    }
+    sync();
+    copy_plan(p, prog_len, prog_dur);
+}
+
+void Engine::batch_copy_joined_device(const stn_join* j, int enc, void* dst, int64_t dst_stride) {
+    need_enc(enc);
+    const JoinPlan p = batch_join_plan(j);
+    enqueue_output({dst, enc, dst_stride, &p, j->gain_scope});
+}
+
+void Engine::batch_join_loudness(const stn_join* j, float* lufs, float* peak, float* gain) {
+    const JoinPlan p = batch_join_plan(j);
+    const size_t G = (size_t)p.G;
+    if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
+    const float* res = join_measure(p, join_f32(p), lo_on_);
+    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, G * 4, hipMemcpyDeviceToHost, s_));
+    if (peak) STN_HIP(hipMemcpyAsync(peak, res + G, G * 4, hipMemcpyDeviceToHost, s_));
+    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * G, G * 4, hipMemcpyDeviceToHost, s_));
+    sync();
+}
+
+void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, bool loudness_on, float target_lufs,
+                     float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
+    const int eb = need_enc(enc);
+    STN_HIP(hipSetDevice(device_));
+    JoinPlan p;
+    stn_join jj = *j;
+    jj.mode = STN_JOIN_WHOLE;  // (the lengths are the caller's)
+    if (j->mode != STN_JOIN_WHOLE && j->mode != STN_JOIN_TRIM) throw std::invalid_argument("join: unknown mode " + std::to_string(j->mode));
+    const std::string why = join_plan(&jj, rows, W, hz, n, nullptr, p);
+    if (!why.empty()) throw std::invalid_argument(why);
+    if (p.G > 65535) throw std::invalid_argument("join: more than 65535 programmes");
+    const bool measure = loudness_on || prog_lufs || prog_peak || prog_gain;
+    if (measure) {
+        if (!(target_lufs >= -60.0f && target_lufs <= 0.0f)) throw std::invalid_argument("loudness target " + std::to_string(target_lufs) + " LUFS: must be in [-60, 0]");
+        if (!(ceiling_dbfs >= -30.0f && ceiling_dbfs <= 0.0f)) throw std::invalid_argument("loudness peak ceiling " + std::to_string(ceiling_dbfs) + " dBFS: must be in [-30, 0]");
+        lo_prepare(op_lo_, hz);
+    }
+    if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
+    ar_.reset();
+    const size_t nx = (size_t)rows * W, ny = (size_t)p.G * p.W_join;
+    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
+    void* dy = ar_.alloc(ny * eb);
+    const std::vector<int64_t> words = join_table_words(p, nullptr);
+    int64_t* dt = static_cast<int64_t*>(ar_.alloc(words.size() * sizeof(int64_t)));
+    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMemcpyAsync(dt, words.data(), words.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    const JoinTables t{reinterpret_cast<const JoinSeg*>(dt), reinterpret_cast<const JoinProg*>(dt + (size_t)rows * 3)};
+    if (!measure) {
+        join_enqueue(dx, W, t, p, nullptr, enc, dy, p.W_join);
+    } else {
+        float* dj = static_cast<float*>(ar_.alloc(ny * 4));
+        join_enqueue(dx, W, t, p, nullptr, ENC_F32, dj, p.W_join);
+        const float* res = lo_rows(op_lo_, dj, p.G, p.W_join, p.prog_len, loudness_on, target_lufs, ceiling_dbfs);
+        lo_n_.clear();  // (op_lo_'s rows, not the batch's)
+        launch_store_rows(s_, dj, p.G, p.W_join, res + 2 * (size_t)p.G, enc, dy, p.W_join);
+        STN_HIP(hipGetLastError());
+        const size_t G = (size_t)p.G;
+        if (prog_lufs) STN_HIP(hipMemcpyAsync(prog_lufs, res, G * 4, hipMemcpyDeviceToHost, s_));
+        if (prog_peak) STN_HIP(hipMemcpyAsync(prog_peak, res + G, G * 4, hipMemcpyDeviceToHost, s_));
+        if (prog_gain) STN_HIP(hipMemcpyAsync(prog_gain, res + 2 * G, G * 4, hipMemcpyDeviceToHost, s_));
+    }
+    STN_HIP(hipMemcpyAsync(y, dy, ny * eb, hipMemcpyDeviceToHost, s_));
     sync();
 }
 void Engine::batch_fetch_latent(float* latent) {

@@ -137,7 +137,7 @@ Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
     return sc;
 }
 
-void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on) {
+void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling) {
     const char* saved = stage_;
     stage_ = "out";
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
@@ -153,7 +153,7 @@ void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_
     launch_loudness_chunks(s_, true, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
     done();
     span(chunks * 2, chunks * 12 + (double)rows * 12);
-    launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, lo_target_, lo_ceiling_, sc.res);
+    launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, target, ceiling, sc.res);
     done();
     stage_ = saved;
 }
@@ -164,20 +164,25 @@ float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     lo_prepare(lo_, hz);
     // row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file
     std::vector<int64_t> n((size_t)b.B);
-    int64_t max_seg = 0;
     for (int i = 0; i < b.B; ++i) {
         n[(size_t)i] = std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz));
         if (n[(size_t)i] < 0) n[(size_t)i] = 0;
-        max_seg = std::max<int64_t>(max_seg, n[(size_t)i] / lo_.hop);
     }
-    const LoScratch sc = lo_scratch(b.B, Wo);
-    // uploaded once per finished batch (and again only when the scratch moved): later fetches of the same batch reuse it
+    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_ceiling_);
+}
+
+float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling) {
+    int64_t max_seg = 0;
+    for (int64_t v : n) max_seg = std::max<int64_t>(max_seg, v / t.hop);
+    const LoScratch sc = lo_scratch(rows, W);
+    // uploaded once per finished batch (and again only when the scratch moved or other rows were measured in between): later fetches
+    // of the same batch reuse it
     if (n != lo_n_ || lo_n_ptr_ != sc.n) {
         lo_n_ = std::move(n);
         lo_n_ptr_ = sc.n;
         STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
-    lo_measure(lo_, x, b.B, Wo, sc, max_seg, on);
+    lo_measure(t, x, rows, W, sc, max_seg, on, target, ceiling);
     return sc.res;
 }
 
@@ -210,7 +215,7 @@ void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t*
     const LoScratch sc = lo_scratch(rows, W);
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     lo_n_.clear();  // (the batch's lengths are no longer there)
-    lo_measure(op_lo_, dx, rows, W, sc, max_seg, false);
+    lo_measure(op_lo_, dx, rows, W, sc, max_seg, false, lo_target_, lo_ceiling_);
     if (lufs) STN_HIP(hipMemcpyAsync(lufs, sc.res, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
     if (peak) STN_HIP(hipMemcpyAsync(peak, sc.res + rows, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
     sync();

@@ -1,0 +1,26 @@
+// join_plan.hpp — the plan of a joined fetch (include/stn.h, "join"): where every member's segment lands in its
+// programme's row, the programmes' lengths and their durations.  Host arithmetic only: the engine's output stage, stn_join_plan and
+// the hosts that size buffers share it.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../../include/stn.h"
+
+namespace stn {
+
+struct JoinPlan {
+    int G = 0, B = 0;
+    int64_t W_join = 0;
+    std::vector<int32_t> first;                        // [G] first member (batch row) of each programme
+    std::vector<int64_t> seg_len, seg_dst;             // [B]
+    std::vector<int64_t> prog_len;                     // [G]
+    std::vector<float> prog_dur;                       // [G]
+};
+
+// Fills p from B members of whole lengths member_len (each in [0, W_out]) and durations member_dur (may be null with STN_JOIN_WHOLE:
+// prog_dur is then zero) at rate hz.  Empty string, or why the arguments are refused (p is then untouched).
+std::string join_plan(const stn_join* j, int B, int64_t W_out, int hz, const int64_t* member_len, const float* member_dur, JoinPlan& p);
+
+}  // namespace stn

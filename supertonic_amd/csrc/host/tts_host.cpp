@@ -59,13 +59,7 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
         for (size_t i = 0; i < pcm.size(); ++i) r.wav[i] = pcm[i] == 0 ? 0.f : ((float)pcm[i] + (pcm[i] > 0 ? 0.5f : -0.5f)) / 32767.0f;
         return r;
     }
-    check(h_, stn_batch_upload(h_, bsz, tb.Lt, tb.ids.data(), mask.data(), style.getTtlData().data(),
-                               style.getDpData().data(), nullptr, nullptr));
-    uint64_t seed = noise_seed_;
-    if (seed == 0) { std::random_device rd; seed = ((uint64_t)rd() << 32) | rd(); }  // unseeded, like cpp/helper.cpp:442-444
-    else seed += calls_;
-    ++calls_;
-    check(h_, stn_batch_run(h_, total_step, speed, seed));
+    runBatch(tb, mask, style, total_step, speed);
     int B = 0, L = 0;
     int64_t W = 0;
     check(h_, stn_batch_dims(h_, &B, &L, &W));
@@ -80,6 +74,24 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
     r.wav.resize((size_t)B * W);
     check(h_, stn_batch_fetch(h_, r.wav.data(), r.wav.size(), r.duration.data()));
     return r;
+}
+
+// one handle: the batch uploaded and run, ready for whichever fetch the caller wants
+void TextToSpeech::runBatch(const TokenBatch& tb, const std::vector<float>& mask, const Style& style, int total_step, float speed) {
+    check(h_, stn_batch_upload(h_, tb.B, tb.Lt, tb.ids.data(), mask.data(), style.getTtlData().data(),
+                               style.getDpData().data(), nullptr, nullptr));
+    uint64_t seed = noise_seed_;
+    if (seed == 0) { std::random_device rd; seed = ((uint64_t)rd() << 32) | rd(); }  // unseeded, like cpp/helper.cpp:442-444
+    else seed += calls_;
+    ++calls_;
+    check(h_, stn_batch_run(h_, total_step, speed, seed));
+}
+
+void TextToSpeech::setLoudnessScope(bool whole_text) {
+    if (whole_text && grp_)
+        throw std::runtime_error("loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
+                                 "(use one GPU, or the default scope 'chunk')");
+    scope_text_ = whole_text;
 }
 
 TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const std::string& lang, const Style& style,
@@ -112,6 +124,30 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
         }
         ~ModeGuard() { for (stn_handle* h : hs) { (void)stn_set_vocoder_mode(h, 0); (void)stn_set_shape_buckets(h, 0); } }
     } guard(h_, grp_);
+    if (!grp_) {
+        // one device: the join is the fetch's (stn_batch_fetch_joined): one programme of n members, the silence as the zero codeword
+        // at the rate of the returned audio, every chunk's whole wave or (setTrimChunks) cut at its duration
+        const TokenBatch tb = text_processor_(chunks, std::vector<std::string>((size_t)n, lang));
+        runBatch(tb, tb.mask(), rep, total_step, speed);
+        const int32_t members = n;
+        const int64_t gap = (int64_t)(int)(silence_duration * (float)getSampleRate());
+        stn_join j{1, &members, &gap, &silence_duration, trim_chunks_ ? STN_JOIN_TRIM : STN_JOIN_WHOLE, scope_text_ ? STN_JOIN_GAIN_PROG : STN_JOIN_GAIN_ROW};
+        int64_t W_join = 0;
+        check(h_, stn_batch_join_dims(h_, &j, &W_join, nullptr, nullptr));
+        SynthesisResult out;
+        out.encoding = enc_;
+        out.duration.resize(1);
+        if (enc_ != STN_ENC_PCM16) {
+            out.encoded.resize((size_t)W_join * stn_encoding_bytes(enc_));
+            check(h_, stn_batch_fetch_joined(h_, &j, enc_, out.encoded.data(), out.encoded.size(), nullptr, out.duration.data()));
+        } else {
+            out.wav.resize((size_t)W_join);
+            check(h_, stn_batch_fetch_joined(h_, &j, STN_ENC_F32, out.wav.data(), out.wav.size() * sizeof(float), nullptr, out.duration.data()));
+        }
+        return out;
+    }
+    // a group deals the chunks over its devices: its long form keeps the host join of the gathered rows
+    if (trim_chunks_) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
     const SynthesisResult r = infer(chunks, std::vector<std::string>((size_t)n, lang), rep, total_step, speed);
     const size_t eb = r.encoding == STN_ENC_PCM16 ? 0 : (size_t)stn_encoding_bytes(r.encoding);  // 0: the float waveform
     const size_t W = eb ? r.encoded.size() / eb / (size_t)n : r.wav.size() / (size_t)n;
@@ -159,6 +195,11 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
     stn_handle* h = nullptr;
     stn_group* grp = nullptr;
     if (opts.gpus > 1 || !opts.devices.empty()) {
+        // refused before anything is created: a group deals the chunks of a text over its devices and keeps the host join
+        if (opts.loudness_scope_text)
+            throw std::runtime_error("loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
+                                     "(use one GPU, or the default scope 'chunk')");
+        if (opts.trim_chunks) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
         std::vector<int> dev = opts.devices;
         if (dev.empty()) for (int i = 0; i < opts.gpus; ++i) dev.push_back(opts.device + i);
         if (stn_group_create((int)dev.size(), dev.data(), opts.dtype, &grp) != STN_OK) throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(nullptr));
@@ -212,6 +253,8 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);
         tts->setEncoding(opts.encoding);
+        tts->setLoudnessScope(opts.loudness_scope_text);
+        tts->setTrimChunks(opts.trim_chunks);
         if (synthetic) tts->markSynthetic();
         return tts;
     } catch (...) {

@@ -63,6 +63,9 @@ struct EngineOptions {
                                    // (measured and scaled on the GPU, stn_set_loudness; the WAV files carry the normalized PCM); NaN: off.
                                    // CLI --loudness LUFS
     float loudness_ceiling_dbfs = -1.0f;  // sample-peak ceiling that caps the normalization gain.  CLI --peak-ceiling DBFS
+    bool loudness_scope_text = false;  // long-form call() with loudness on: the joined text normalized as one programme with one gain instead
+                                   // of every chunk on its own.  One device only.  CLI --loudness-scope {chunk,text}
+    bool trim_chunks = false;      // long-form call(): every chunk cut at its duration before the join.  CLI --trim-chunks
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
@@ -79,8 +82,8 @@ class TextToSpeech {
     ~TextToSpeech();
     TextToSpeech(const TextToSpeech&) = delete;
 
-    // long-form: chunkText -> one synthesis per chunk -> joined with `silence_duration` of zeros (cpp/helper.cpp:685-723; the
-    // encoding's zero codeword with an encoding set)
+    // long-form: chunkText -> the chunks as one batch -> joined with `silence_duration` of zeros by the fetch on the GPU
+    // (cpp/helper.cpp:685-723; the encoding's zero codeword with an encoding set; on a group, joined on the host)
     SynthesisResult call(const std::string& text, const std::string& lang, const Style& style, int total_step,
                          float speed = 1.05f, float silence_duration = 0.3f);
     // batch: one padded batch, no chunking (cpp/helper.cpp:725-734)
@@ -90,6 +93,11 @@ class TextToSpeech {
     int getSampleRate() const { return out_rate_ ? out_rate_ : cfgs_.ae.sample_rate; }
     void setOutputRate(int hz) { out_rate_ = hz == cfgs_.ae.sample_rate ? 0 : hz; }
     void setEncoding(int enc);  // STN_ENC_*: the encoding of the audio batch() / call() return (and of a group's gather)
+    // call() with loudness normalization on: false (default), every chunk its own gain; true, the joined text measured as one
+    // BS.1770 programme and scaled by one gain (stn.h, STN_JOIN_GAIN_PROG).  Refused on a group: its chunks sit on several devices.
+    void setLoudnessScope(bool whole_text);
+    // call(): every chunk cut at its reported duration before the join (the reference's Rust host) instead of its whole wave
+    void setTrimChunks(bool on) { trim_chunks_ = on; }
     int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
@@ -99,6 +107,8 @@ class TextToSpeech {
    private:
     SynthesisResult infer(const std::vector<std::string>& text_list, const std::vector<std::string>& lang_list,
                           const Style& style, int total_step, float speed);
+    void runBatch(const TokenBatch& tb, const std::vector<float>& mask, const Style& style, int total_step, float speed);
+    bool scope_text_ = false, trim_chunks_ = false;
     stn_handle* h_;
     stn_group* grp_ = nullptr;
     UnicodeProcessor text_processor_;

@@ -379,6 +379,15 @@ constexpr int enc_bytes(int enc) {
 // kernels_dev.hpp: int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987), 24-bit PCM, or G.711 mu-law / A-law of the
 // 16-bit sample.  fp32 rows may be stored in place (y == x, dst_stride == W).
 void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride);
+// The join of a fetch: G programme rows of Wj samples at y + p * dst_stride samples (dst_stride >= Wj) in encoding
+// enc.  Programme p is members prog[p].first .. + prog[p].count of seg, in order: member m's first seg[m].len samples of source row
+// seg[m].row (fp32, rows src_stride apart, len <= src_stride), times g[seg[m].row] when g is not null, at output samples seg[m].dst ..;
+// the segments of a programme ascend and do not overlap, and end at or before prog[p].len <= Wj.  Every other sample of [0, Wj) is the
+// zero codeword.  Tables on the device.  G <= 65535.
+struct JoinSeg { int64_t dst, len, row; };
+struct JoinProg { int64_t len; int32_t first, count; };
+void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
+                      int enc, void* y, int64_t dst_stride);
 
 // Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
 // out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),

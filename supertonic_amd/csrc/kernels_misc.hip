@@ -1337,27 +1337,10 @@ void launch_mask_ncl(hipStream_t s, float* x, int B, int D, int L, const int* le
 template <int kEnc>
 constexpr int store_vec() { return kEnc == ENC_F32 ? 4 : kEnc == ENC_PCM16 ? 8 : 16; }
 
-template <int V, bool kGain, int kEnc>
-__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, unsigned char* y, int64_t dst_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/V]
-    if (i >= nv) return;
-    const int64_t row = i / Wv;
-    float v[V];
-    if constexpr (V == 1) {
-        v[0] = x[i];
-    } else {
-#pragma unroll
-        for (int j = 0; j < V / 4; ++j) {
-            const float4 a = reinterpret_cast<const float4*>(x)[i * (V / 4) + j];
-            v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
-        }
-    }
-    if constexpr (kGain) {
-        const float s = g[row];
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[j] *= s;
-    }
-    const int64_t e = row * dst_stride + (i - row * Wv) * V;  // first destination sample
+// V consecutive samples v, encoded, to sample index e of y: one sample by enc_store1 (V == 1), else V = store_vec<kEnc>() samples in
+// one 16-B store (three for PCM24); y + e samples is then 16-byte aligned
+template <int V, int kEnc>
+__device__ __forceinline__ void enc_store_vec(unsigned char* y, int64_t e, const float (&v)[V]) {
     if constexpr (V == 1) {
         enc_store1<kEnc>(y, e, v[0]);
     } else if constexpr (kEnc == ENC_F32) {
@@ -1396,6 +1379,29 @@ __global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const 
         *reinterpret_cast<uint4*>(y + e) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
+
+template <int V, bool kGain, int kEnc>
+__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, unsigned char* y, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/V]
+    if (i >= nv) return;
+    const int64_t row = i / Wv;
+    float v[V];
+    if constexpr (V == 1) {
+        v[0] = x[i];
+    } else {
+#pragma unroll
+        for (int j = 0; j < V / 4; ++j) {
+            const float4 a = reinterpret_cast<const float4*>(x)[i * (V / 4) + j];
+            v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+        }
+    }
+    if constexpr (kGain) {
+        const float s = g[row];
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] *= s;
+    }
+    enc_store_vec<V, kEnc>(y, row * dst_stride + (i - row * Wv) * V, v);  // (first destination sample)
+}
 template <int kEnc>
 void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, unsigned char* y, int64_t dst_stride) {
     const int64_t n = rows * W;
@@ -1419,6 +1425,121 @@ void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, c
         case ENC_MULAW: launch_store_rows_t<ENC_MULAW>(s, x, rows, W, g, d, dst_stride); break;
         case ENC_ALAW: launch_store_rows_t<ENC_ALAW>(s, x, rows, W, g, d, dst_stride); break;
         default: throw std::invalid_argument("store_rows: unknown encoding " + std::to_string(enc));
+    }
+}
+
+// The join of a fetch: programme p's output row is its members' segments with gaps between them,
+// seg[m].len samples of source row seg[m].row landing at seg[m].dst, everything else of [0, Wj) the encoding's zero codeword (the
+// encoding of +0.0f).  One workgroup per (tile of JOIN_WG * V * T output samples, programme): it stages the programme's members in LDS
+// once (one load per lane; members past JOIN_WG, which a chunked text never has, are read from the table), and a thread, which owns T vectors of V
+// consecutive output samples JOIN_WG * V apart, finds for each the first member that ends behind its first sample by a binary search over the members' ascending
+// ends in LDS.  Inside one segment the V samples are 16-B loads that ask for dword alignment only (a segment's offset against its row
+// is arbitrary: the hardware takes a dwordx4 at any dword address) and the store of store_rows_kernel; a vector that meets a segment
+// edge, a gap or the row's end selects per sample, and the last, partial vector of a row is stored sample by sample.  No sample
+// outside a member's [0, len) is read, nothing outside [0, Wj) of a row is written.  kGain: times g[source row], the product
+// store_rows_kernel forms.
+constexpr int JOIN_WG = 256;
+typedef float join_f4 __attribute__((ext_vector_type(4), aligned(4)));  // four floats at a dword-aligned address
+
+template <int V, int T, bool kGain, int kEnc>
+__global__ void __launch_bounds__(JOIN_WG) join_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSeg* __restrict__ seg,
+                                                            const JoinProg* __restrict__ prog, const float* __restrict__ g, int64_t Wj,
+                                                            unsigned char* __restrict__ y, int64_t dst_stride) {
+    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG];
+    const int p = blockIdx.y, tid = threadIdx.x;
+    const JoinProg pg = prog[p];
+    const JoinSeg* __restrict__ ps = seg + pg.first;
+    const int64_t t0 = (int64_t)blockIdx.x * (JOIN_WG * V * T);
+    const int k = t0 < pg.len ? pg.count : 0;  // (a tile behind the programme's end is padding: no member to find)
+    if (tid < k) { s_dst[tid] = ps[tid].dst; s_len[tid] = ps[tid].len; s_row[tid] = ps[tid].row; }
+    __syncthreads();
+    auto dst_of = [&](int r) { return r < JOIN_WG ? s_dst[r] : ps[r].dst; };
+    auto len_of = [&](int r) { return r < JOIN_WG ? s_len[r] : ps[r].len; };
+    auto row_of = [&](int r) { return r < JOIN_WG ? s_row[r] : ps[r].row; };
+    float v[T][V];
+    // all T vectors are loaded before the first is stored: the loads of a thread are in flight together
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;  // this vector's first output sample
+        if (o >= Wj) break;
+        int r = 0;
+        for (int hi = k; r < hi;) {  // the first member that ends behind o (the ends ascend)
+            const int mid = (r + hi) >> 1;
+            if (dst_of(mid) + len_of(mid) <= o) r = mid + 1; else hi = mid;
+        }
+        const int64_t d0 = r < k ? dst_of(r) : 0, l0 = r < k ? len_of(r) : 0;
+        if (r < k && o >= d0 && o + V <= d0 + l0) {  // the whole vector inside one segment
+            const int64_t row = row_of(r);
+            const float* __restrict__ src = x + row * src_stride + (o - d0);
+            if constexpr (V >= 4) {
+#pragma unroll
+                for (int j = 0; j < V / 4; ++j) {
+                    const join_f4 a = reinterpret_cast<const join_f4*>(src)[j];
+                    v[i][4 * j] = a.x; v[i][4 * j + 1] = a.y; v[i][4 * j + 2] = a.z; v[i][4 * j + 3] = a.w;
+                }
+            } else {
+                v[i][0] = src[0];
+            }
+            if constexpr (kGain) {
+                const float s = g[row];
+#pragma unroll
+                for (int j = 0; j < V; ++j) v[i][j] *= s;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int64_t oj = o + j;
+                while (r < k && dst_of(r) + len_of(r) <= oj) ++r;
+                float t = 0.f;
+                if (r < k && oj >= dst_of(r)) {
+                    const int64_t row = row_of(r);
+                    t = x[row * src_stride + (oj - dst_of(r))];
+                    if constexpr (kGain) t *= g[row];
+                }
+                v[i][j] = t;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;
+        if (o >= Wj) break;
+        const int64_t e = (int64_t)p * dst_stride + o;
+        if (V == 1 || o + V <= Wj) {
+            enc_store_vec<V, kEnc>(y, e, v[i]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (o + j < Wj) enc_store1<kEnc>(y, e + j, v[i][j]);
+        }
+    }
+}
+template <int kEnc>
+void launch_join_rows_t(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
+                        unsigned char* y, int64_t dst_stride) {
+    constexpr int V = store_vec<kEnc>();
+    constexpr int T = V == 16 ? 2 : 4;  // vectors per thread: a workgroup's table lookup is paid once for 32 (fp32: 16) samples a thread
+    const bool vec = (G == 1 || dst_stride % V == 0) && !(reinterpret_cast<uintptr_t>(y) & 15);  // (every row's start 16-byte aligned)
+    const int64_t tile = (int64_t)JOIN_WG * T * (vec ? V : 1);
+    const dim3 grid((unsigned)((Wj + tile - 1) / tile), (unsigned)G);
+    if (vec && g) STN_KLAUNCH((join_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else if (vec) STN_KLAUNCH((join_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else if (g) STN_KLAUNCH((join_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else STN_KLAUNCH((join_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+}
+void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
+                      int enc, void* y, int64_t dst_stride) {
+    if (G <= 0 || Wj <= 0) return;
+    if (G > 65535) throw std::invalid_argument("join_rows: more than 65535 programmes");
+    if (dst_stride < Wj) throw std::invalid_argument("join_rows: dst_stride smaller than the joined row length");
+    unsigned char* d = static_cast<unsigned char*>(y);
+    switch (enc) {
+        case ENC_F32: launch_join_rows_t<ENC_F32>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_PCM16: launch_join_rows_t<ENC_PCM16>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_PCM24: launch_join_rows_t<ENC_PCM24>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_MULAW: launch_join_rows_t<ENC_MULAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_ALAW: launch_join_rows_t<ENC_ALAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        default: throw std::invalid_argument("join_rows: unknown encoding " + std::to_string(enc));
     }
 }
 

@@ -24,17 +24,18 @@ AVAILABLE_LANGS = host.AVAILABLE_LANGS
 
 
 class _Job:
-    __slots__ = ("texts", "lang", "style", "key", "done", "waves", "durs", "error")
+    __slots__ = ("texts", "lang", "style", "key", "silence", "done", "waves", "durs", "error")
 
-    def __init__(self, texts, lang, style, key):
-        self.texts, self.lang, self.style, self.key = texts, lang, style, key
+    def __init__(self, texts, lang, style, key, silence=None):
+        self.texts, self.lang, self.style, self.key, self.silence = texts, lang, style, key, silence
         self.done = threading.Event()
         self.waves = self.durs = self.error = None
 
 
 class DynamicBatcher:
     """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding) into one engine batch (the engine's output rate and loudness
+    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding, and loudness scope / chunk trimming where a
+    request sets them) into one engine batch (the engine's output rate and loudness
     setting cover a whole batch; every row is still normalized with its own gain).  A worker thread owns
     the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
     its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
@@ -47,13 +48,21 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None):
+    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
+               silence_duration=None, loudness_scope="chunk", trim_chunks=False):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
-        the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32)."""
+        the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
+        silence_duration (seconds, not None): the job's utterances are the chunks of one text and come back as ONE wave, joined with
+        that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own gap), with its duration;
+        loudness_scope ("chunk": every chunk its own gain; "text": the joined wave normalized as one programme) and trim_chunks
+        (TextToSpeech.joined_batch) are part of the batch key: one fetch has one mode and one scope."""
         lo = None if loudness is None else (float(loudness), float(peak_ceiling))
         enc = None if encoding is None else binding.encoding_id(encoding)
-        job = _Job(list(texts), lang, style, (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc))
+        key = (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc)
+        if loudness_scope != "chunk" or trim_chunks:  # (requests that use neither batch exactly as before)
+            key += (str(loudness_scope), bool(trim_chunks))
+        job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -106,19 +115,36 @@ class DynamicBatcher:
                 langs = [j.lang for j in jobs for _ in j.texts]
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
-                step, speed, rate, lo, enc = jobs[0].key
+                step, speed, rate, lo, enc = jobs[0].key[:5]
+                scope, trim = jobs[0].key[5:] or ("chunk", False)
                 extra = {} if rate is None else {"output_rate": rate}
                 if lo is not None:
                     extra["loudness"] = lo
                 if enc is not None:
                     extra["encoding"] = enc
-                waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
-                self.batches.append(len(texts))
-                o = 0
-                for j in jobs:
-                    n = len(j.texts)
-                    j.waves, j.durs = waves[o:o + n], np.asarray(durs[o:o + n], np.float32)
-                    o += n
+                joined = getattr(self.tts, "joined_batch", None)
+                if joined is not None and all(j.silence is not None for j in jobs):
+                    # one programme per job, joined by the fetch on the GPU
+                    waves, durs = joined(texts, langs, Style(ttl, dp), step, speed, rows=[len(j.texts) for j in jobs],
+                                         silence_duration=[j.silence for j in jobs], loudness_scope=scope, trim_chunks=trim, **extra)
+                    self.batches.append(len(texts))
+                    for g, j in enumerate(jobs):
+                        j.waves, j.durs = [waves[g]], np.asarray(durs[g:g + 1], np.float32)
+                else:
+                    if scope != "chunk" or trim:
+                        raise RuntimeError("loudness_scope / trim_chunks need a synthesizer with a joined fetch (TextToSpeech.joined_batch)")
+                    # a synthesizer without a joined fetch (a stand-in), or a caller that wants the rows: per-utterance waves; a job
+                    # that asked for one wave gets the host join of them
+                    waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
+                    self.batches.append(len(texts))
+                    o = 0
+                    for j in jobs:
+                        n = len(j.texts)
+                        j.waves, j.durs = waves[o:o + n], np.asarray(durs[o:o + n], np.float32)
+                        if j.silence is not None:
+                            w, d = join_chunks(j.waves, j.durs, j.silence, rate or self.tts.sample_rate, enc)
+                            j.waves, j.durs = [w], np.array([d], np.float32)
+                        o += n
             except Exception as e:  # the requests fail, the worker lives on
                 for j in jobs:
                     j.error = e
@@ -181,6 +207,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                               "loudness in LUFS (on the GPU); null: off.")
         peak_ceiling: float = Field(-1.0, ge=-30.0, le=0.0, description="Sample-peak ceiling in dBFS that caps the loudness gain.")
         encoding: str = Field("pcm16", description="Sample format of the WAV files (encoded on the GPU): pcm16, pcm24, f32, mulaw, alaw.")
+        loudness_scope: str = Field("chunk", description="Non-batch mode with loudness: 'chunk' normalizes every chunk of a long text on its own, "
+                                                         "'text' the joined text as one BS.1770 programme with one gain.")
+        trim_chunks: bool = Field(False, description="Non-batch mode: cut every chunk at its duration before the join.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -216,6 +245,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             extra["loudness"] = (req.loudness, req.peak_ceiling)
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
+        if req.loudness_scope not in ("chunk", "text"):
+            raise HTTPException(status_code=400, detail=f"loudness_scope {req.loudness_scope!r} is not supported; supported: chunk, text")
         enc = None if req.encoding == "pcm16" else req.encoding  # pcm16: the float waves, written as writeWavFile writes them
         if enc is not None:
             extra["encoding"] = enc
@@ -225,8 +256,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
-                                         enc)
-            wav, d = join_chunks(waves, durs, req.silence_duration, sr, enc)
+                                         enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
+                                         trim_chunks=req.trim_chunks)
+            wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav[: int(sr * d)]]
         if len(chunks) == 1:
             name = host.sanitize_filename(texts[0], 40) or "tts"

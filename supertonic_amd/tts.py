@@ -82,7 +82,7 @@ class TextToSpeech:
         return self.noise_seed + self._calls - 1
 
     def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None,
-               encoding=None):
+               encoding=None, join=None):
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         ids, mask = self.text_processor(text_list, lang_list)
@@ -97,6 +97,10 @@ class TextToSpeech:
             if loudness is not None:  # this call's normalization (fetch-time as well)
                 self.engine.set_loudness(*(_loudness_setting(loudness) or (None,)))
             try:
+                if join is not None:  # joined on the GPU by the fetch (Engine.batch_fetch_joined's arguments)
+                    self.engine.batch_upload(ids, mask, style.ttl, style.dp)
+                    self.engine.batch_run(total_step, speed, self._seed())
+                    return self.engine.batch_fetch_joined(encoding=encoding, **join)
                 if encoding is None:
                     return self.engine.synthesize(ids, mask, style.ttl, style.dp, total_step, speed, noise_seed=self._seed())
                 # encoded on the GPU by the fetch (binding.encoded_empty's dtypes)
@@ -137,33 +141,44 @@ class TextToSpeech:
         lens = [int(self.latent_lengths(dur[i:i + 1])[0]) for i in range(len(text_list))]
         return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
-    def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None):
-        """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence.  With
-        loudness normalization on, each chunk is normalized as its own row (its own gain); the joined text is not normalized as one
-        unit.  encoding: as solo_batch; the silence is then the encoding's zero codeword."""
+    def joined_batch(self, text_list, lang_list, style, total_step, speed=1.05, rows=None, silence_duration=0.3, output_rate=None,
+                     loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False):
+        """solo_batch whose rows are joined on the GPU into len(rows) waves: rows[g] consecutive utterances each (None: all of them
+        in one), silence_duration (one value, or one per wave) seconds of silence between two of them — the encoding's zero codeword.
+        Returns (list of joined waves, their durations: the reference's fp32 sum d = dur_0; d += dur_i + silence).  loudness_scope,
+        with normalization on: "chunk", every utterance with its own gain (what joining solo_batch's rows gives, byte for byte);
+        "text", every joined wave measured as one BS.1770 programme, silences included, and scaled by one gain.  trim_chunks: every
+        utterance cut at its duration before the join (the reference's Rust host) instead of its whole wave (C++ / Python hosts)."""
+        if loudness_scope not in ("chunk", "text"):
+            raise ValueError(f"loudness_scope {loudness_scope!r}: 'chunk' or 'text'")
+        rows = [len(text_list)] if rows is None else [int(r) for r in rows]
+        rate = int(output_rate or self.output_rate)
+        sil = np.broadcast_to(np.asarray(silence_duration, np.float64), (len(rows),))
+        join = {"rows": rows, "gap_samples": [int(s * rate) for s in sil], "gap_seconds": sil.astype(np.float32),
+                "mode": "trim" if trim_chunks else "whole", "gain_scope": "programme" if loudness_scope == "text" else "row"}
+        waves, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
+                                 loudness=loudness, encoding=encoding, join=join)
+        return waves, dur
+
+    def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None, loudness_scope="chunk",
+                 trim_chunks=False):
+        """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence on the GPU
+        (one joined fetch: py/helper.py:235-243's untrimmed chunk waves with zeros between).  With loudness normalization on,
+        loudness_scope="chunk" normalizes each chunk as its own row (its own gain); "text" normalizes the joined text as one
+        BS.1770 programme with one gain, its internal dynamics kept.  trim_chunks: as joined_batch.  encoding: as solo_batch; the
+        silence is then the encoding's zero codeword."""
         if style.ttl.shape[0] != 1:
             raise ValueError("Single speaker text to speech only supports single style")
+        if loudness_scope not in ("chunk", "text"):
+            raise ValueError(f"loudness_scope {loudness_scope!r}: 'chunk' or 'text'")
         chunks = host.chunk_text(text, 120 if lang == "ko" else 300)
-        if len(chunks) == 1:
+        if len(chunks) == 1 and not trim_chunks:  # (one chunk is its own programme: the row's gain is the text's)
             return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding)
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
-        waves, dur = self.solo_batch(chunks, [lang] * n, rep, total_step, speed, encoding=encoding)
-        n_sil = int(silence_duration * self.output_rate)
-        if encoding is None:
-            silence = np.zeros(n_sil, np.float32)
-        else:
-            silence = binding.encoded_empty(encoding, 1, n_sil)[0]
-            silence[...] = binding.ZERO_CODEWORD[binding.encoding_id(encoding)]
-        parts, dur_cat = [], None
-        for i, w in enumerate(waves):  # untrimmed chunk waves joined by zeros (py/helper.py:235-243)
-            if i == 0:
-                dur_cat = np.float32(dur[0])
-            else:
-                parts.append(silence)
-                dur_cat = np.float32(dur_cat + np.float32(dur[i] + np.float32(silence_duration)))
-            parts.append(w)
-        return np.concatenate(parts)[None, :], np.array([dur_cat], np.float32)
+        waves, dur = self.joined_batch(chunks, [lang] * n, rep, total_step, speed, silence_duration=silence_duration, encoding=encoding,
+                                       loudness_scope=loudness_scope, trim_chunks=trim_chunks)
+        return waves[0][None, :], np.array([dur[0]], np.float32)
 
     def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None):
         """One padded batch -> (wav [B, W] float32, duration [B]); with an encoding (a name or binding.ENC_*), the rows in that sample
