@@ -509,6 +509,23 @@ int stn_dbg_attn_form(int kind, int dtype, int B, int Lq, int Lk, int H, int dh,
 int stn_op_ffn(stn_handle* h, int M, int C, int I, const float* xn /*[M,C]*/, const float* W1, const float* b1, const float* W2,
                const float* b2_or_null, const float* gamma_or_null, const float* rowvec_or_null /*[nseq,C]*/,
                const int32_t* row_b_or_null /*[M]*/, int nseq, float* x, int fused);
+/* The same pair through the engine's own launch (Engine::ffn_launch) on the caller's whole buffers (the kernel parity tests of every K4 and
+ * K4-split form).  dtype: STN_DTYPE_BF16 or STN_DTYPE_F16, and the engine's.  xn: xn_elems floats, rows of ldx (>= C, a multiple of 8; the
+ * columns past C are never read), rounded to dtype; W1 [I,C], W2 [C,I] rounded to dtype; b1 [I], b2 [C] (NULL: 0), gamma [C] (NULL: 1) fp32.
+ * x: x_elems floats, rows of ldo (>= C, a multiple of 4).  Modes 0 (two tiled launches) and 1 (K4):
+ *   x[m*ldo + n] = (x[m*ldo + n] + gamma[n] (y[m][n] + b2[n]) + rowvec[seq(m)*rv_ld + n]) * keep(m),  y = W2 . GELU(W1 . xn[m] + b1)
+ * with keep(m) = 0 where len[b] <= t for row m = b*L + t (len: nseq entries in 0..L) and seq(m) = row_b[m] (M entries in 0..nseq-1; not with
+ * len) or m / L; rowvec: nseq rows of rv_ld (>= C, a multiple of 4).  Mode 2 (K4-split): S = split, or the launcher's choice for M rows
+ * when split is 0; part[sp*part_stride + m*C + n] receives share sp's y as a 16-bit value and NO fold runs: x, b2, gamma, rowvec, len are
+ * not used and x comes back as it went in.  part_stride >= (M rounded up to 128) * C.  x and part (part_elems floats, rounded to dtype) are
+ * uploaded as given and written back whole (16-bit values widened to fp32, exactly), so what lies around the written region can be checked.
+ * Refused (STN_ERR_INVALID): fp32 engines, a shape the fused kernel does not take (modes 1, 2), a split the shape does not run with, buffers
+ * smaller than the extents the launch addresses, len together with row_b, split or part outside mode 2.  form: the form that ran (as
+ * stn_dbg_ffn_form), NUL-terminated, truncated to form_cap; may be NULL. */
+int stn_op_ffn_ex(stn_handle* h, int dtype, int M, int C, int I, const float* xn, int ldx, int64_t xn_elems, const float* W1, const float* b1,
+                  const float* W2, const float* b2_or_null, const float* gamma_or_null, const int32_t* len_or_null, int L,
+                  const int32_t* row_b_or_null, const float* rowvec_or_null, int rv_ld, int nseq, int mode, int split, float* x, int ldo,
+                  int64_t x_elems, float* part_or_null, int64_t part_stride, int64_t part_elems, char* form, size_t form_cap);
 /* timing of the same on random device-resident operands.  out5: avg ms per call; fused only: mean shader-clock cycles per
  * workgroup until the first stage landed / in the tile loop / in the epilogue, and the number of workgroups */
 int stn_op_ffn_bench(stn_handle* h, int M, int C, int I, int fused, int iters, double* out5);

@@ -265,6 +265,8 @@ def load():
                                   ctypes.c_int64, _f32p, ctypes.c_int64, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_randn.argtypes = [vp, cu64, ci, ci, ci, vp, vp, _f32p]
     L.stn_op_ffn.argtypes = [vp, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, vp, vp, vp, vp, ci, _f32p, ci]
+    L.stn_op_ffn_ex.argtypes = [vp, ci, ci, ci, ci, _f32p, ci, ctypes.c_int64, _f32p, _f32p, _f32p, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, _f32p, ci,
+                                ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_ffn_bench.argtypes = [vp, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     L.stn_set_fused_ffn.argtypes = [vp, ci]
     L.stn_set_fused_ffn_min_rows.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
@@ -1012,6 +1014,36 @@ class Engine:
         self._ck(self._lib.stn_op_ffn(self._h, M, C, I, _c(xn, np.float32), _c(W1, np.float32), _c(b1, np.float32), _c(W2, np.float32),
                                       b2p, gp, rvp, rbp, 0 if rva is None else rva.shape[0], out, int(fused)))
         return out
+
+    def op_ffn_ex(self, xn, W1, b1, W2, x, mode=1, b2=None, gamma=None, len=None, L=None, row_b=None, rowvec=None, split=0, part=None,
+                  part_stride=0, M=None, dtype=None):
+        """The pointwise pair through the engine's own launch on whole buffers (stn_op_ffn_ex).  xn [rows, ldx] and x [rows, ldo] are 2-D with
+        the launch's C = W1.shape[1] columns first; M (default: xn's rows) rows run.  len [nseq] with L, row_b [M], rowvec [nseq, rv_ld].
+        mode 0 two launches, 1 K4, 2 K4-split with `split` ways (0: the launcher's choice), which stops at the partial sums: part is the
+        whole buffer (any shape), its shares part_stride elements apart.  Returns (x, part or None, form string), x and part as new arrays."""
+        xn = _c(xn, np.float32)
+        I, C = W1.shape
+        M = xn.shape[0] if M is None else int(M)
+        x_r = np.array(x, dtype=np.float32, order="C", copy=True)
+        p_r = None if part is None else np.array(part, dtype=np.float32, order="C", copy=True)
+        nseq = 0
+        for v in (len, rowvec):
+            if v is not None:
+                nseq = max(nseq, np.asarray(v).shape[0])
+        if row_b is not None and rowvec is None:
+            nseq = max(nseq, int(np.max(row_b)) + 1)
+        _b, bp = _opt(b2, np.float32)
+        _g, gp = _opt(gamma, np.float32)
+        _l, lp = _opt(len, np.int32)
+        _r, rp = _opt(row_b, np.int32)
+        _v, vp_ = _opt(rowvec, np.float32)
+        form = ctypes.create_string_buffer(32)
+        self._ck(self._lib.stn_op_ffn_ex(self._h, self.dtype if dtype is None else _DTYPES[dtype], M, C, I, xn.reshape(-1), xn.shape[1], xn.size,
+                                         _c(W1, np.float32), _c(b1, np.float32), _c(W2, np.float32), bp, gp, lp, int(M if L is None else L), rp, vp_,
+                                         C if _v is None else _v.shape[1], nseq, int(mode), int(split), x_r.reshape(-1), x_r.shape[1], x_r.size,
+                                         None if p_r is None else p_r.ctypes.data, int(part_stride), 0 if p_r is None else p_r.size, form,
+                                         ctypes.sizeof(form)))
+        return x_r, p_r, form.value.decode()
 
     def op_ffn_bench(self, M, C, I, fused=True, iters=20):
         """fused: 0 / False two launches, 1 / True K4, 2 K4-split (partial sums only; the fold is part of op_block_bench)."""

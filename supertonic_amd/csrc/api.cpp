@@ -699,6 +699,42 @@ int stn_op_ffn(stn_handle* h, int M, int C, int I, const float* xn, const float*
                  need(fused >= 0 && fused <= 2, "stn_op_ffn: mode must be 0 (two launches), 1 (K4) or 2 (K4-split + fold)");
                  h->eng->op_ffn(M, C, I, xn, W1, b1, W2, b2, gamma, rowvec, row_b, nseq, x, fused); })
 }
+static void ffn_ex_checked(stn_handle* h, int dtype, int M, int C, int I, const float* xn, int ldx, int64_t xn_elems, const float* W1, const float* b1,
+                           const float* W2, const float* b2, const float* gamma, const int32_t* len, int L, const int32_t* row_b, const float* rowvec,
+                           int rv_ld, int nseq, int mode, int split, float* x, int ldo, int64_t x_elems, float* part, int64_t part_stride,
+                           int64_t part_elems, char* form, size_t form_cap) {
+    need(M > 0 && C > 0 && I > 0 && C % 8 == 0 && I % 8 == 0 && xn && W1 && b1 && W2 && x && L >= 1, "stn_op_ffn_ex: bad argument");
+    need((dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16) && dtype == h->eng->dtype(), "stn_op_ffn_ex: dtype must be the 16-bit format of the engine");
+    need(mode >= stn::FFN_GEMMS && mode <= stn::FFN_K4_SPLIT, "stn_op_ffn_ex: mode must be 0 (two launches), 1 (K4) or 2 (K4-split)");
+    need(mode == stn::FFN_GEMMS || stn::ffn_fused_supported(dtype, C, I), "stn_op_ffn_ex: shape not supported by the fused kernel");
+    need(ldx >= C && ldx % 8 == 0 && xn_elems >= (int64_t)M * ldx, "stn_op_ffn_ex: needs ldx >= C, ldx % 8 == 0 and xn_elems >= M*ldx");
+    need(ldo >= C && ldo % 4 == 0 && x_elems >= (int64_t)M * ldo, "stn_op_ffn_ex: needs ldo >= C, ldo % 4 == 0 and x_elems >= M*ldo");
+    need(!(len && row_b), "stn_op_ffn_ex: len and row_b exclude each other");
+    const int64_t seqs = ((int64_t)M + L - 1) / L;  // sequences m / L reaches
+    if (len || (rowvec && !row_b)) need(nseq >= seqs, "stn_op_ffn_ex: len / rowvec by m / L need nseq >= ceil(M/L)");
+    if (rowvec || len || row_b) need(nseq > 0, "stn_op_ffn_ex: nseq must be > 0");
+    if (rowvec) need(rv_ld >= C && rv_ld % 4 == 0, "stn_op_ffn_ex: needs rv_ld >= C and rv_ld % 4 == 0");
+    if (len) for (int b = 0; b < nseq; ++b) need(len[b] >= 0 && len[b] <= L, "stn_op_ffn_ex: len out of [0, L]");
+    if (row_b) for (int m = 0; m < M; ++m) need(row_b[m] >= 0 && row_b[m] < nseq, "stn_op_ffn_ex: row_b out of [0, nseq)");
+    if (mode == stn::FFN_K4_SPLIT) {
+        const int S = split ? split : stn::ffn_split_choose(dtype, C, I, M);
+        need(stn::ffn_split_valid(dtype, C, I, S), "stn_op_ffn_ex: not a split this shape runs with");
+        need(part && part_stride >= stn::ffn_split_rows(M) * C && part_stride % 8 == 0 && part_elems >= (int64_t)S * part_stride,
+             "stn_op_ffn_ex: mode 2 needs part, part_stride >= rows padded to 128 * C (a multiple of 8) and part_elems >= S * part_stride");
+    } else {
+        need(split == 0 && !part, "stn_op_ffn_ex: split and part belong to mode 2");
+    }
+    const std::string f = h->eng->op_ffn_ex(M, C, I, xn, ldx, xn_elems, W1, b1, W2, b2, gamma, len, L, row_b, rowvec, rv_ld, nseq, mode, split, x, ldo,
+                                            x_elems, part, part_stride, part_elems);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_ffn_ex(stn_handle* h, int dtype, int M, int C, int I, const float* xn, int ldx, int64_t xn_elems, const float* W1, const float* b1,
+                  const float* W2, const float* b2, const float* gamma, const int32_t* len, int L, const int32_t* row_b, const float* rowvec, int rv_ld,
+                  int nseq, int mode, int split, float* x, int ldo, int64_t x_elems, float* part, int64_t part_stride, int64_t part_elems, char* form,
+                  size_t form_cap) {
+    STN_TRY(h, ffn_ex_checked(h, dtype, M, C, I, xn, ldx, xn_elems, W1, b1, W2, b2, gamma, len, L, row_b, rowvec, rv_ld, nseq, mode, split, x, ldo,
+                              x_elems, part, part_stride, part_elems, form, form_cap))
+}
 int stn_op_ffn_bench(stn_handle* h, int M, int C, int I, int fused, int iters, double* out5) {
     STN_TRY(h, { need(M > 0 && C > 0 && I > 0 && C % 8 == 0 && I % 8 == 0 && iters > 0 && out5, "stn_op_ffn_bench: bad argument");
                  need(fused >= 0 && fused <= 2, "stn_op_ffn_bench: mode must be 0, 1 or 2");

@@ -355,6 +355,13 @@ class Engine {
     // mode: 0 = two tiled launches, 1 = K4, 2 = K4-split (partial sums) + fold_ln
     void op_ffn(int M, int C, int I, const float* xn, const float* W1, const float* b1, const float* W2, const float* b2, const float* gamma,
                 const float* rowvec /* [nseq][C] or null */, const int* row_b /* host [M] or null */, int nseq, float* x, int mode);
+    // the pointwise pair through ffn_launch on the caller's whole buffers (stn_op_ffn_ex; 16-bit engines): xn [xn_elems] rows of ldx, rounded to the
+    // engine's format; x [x_elems] rows of ldo, uploaded as given and downloaded whole; len [nseq] with L, row_b [M], rowvec [nseq][rv_ld] as
+    // FfnArgs.  mode 0 / 1 / 2 as op_ffn, split != 0 forces that S.  Mode 2 stops at the partial sums: part [part_elems] (shares part_stride
+    // apart) is uploaded as given (rounded) and downloaded whole, no fold runs and x is left alone.  Returns the form it ran (FfnForm::str).
+    std::string op_ffn_ex(int M, int C, int I, const float* xn, int ldx, int64_t xn_elems, const float* W1, const float* b1, const float* W2,
+                          const float* b2, const float* gamma, const int* len, int L, const int* row_b, const float* rowvec, int rv_ld, int nseq,
+                          int mode, int split, float* x, int ldo, int64_t x_elems, float* part, int64_t part_stride, int64_t part_elems);
     // fold_dwconv_ln on host operands (packed rows: sequence b owns seqlen[b] consecutive rows; M = sum): part [S][M][C] fp32 is rounded
     // to the engine's 16-bit format first.  x_out <- folded x, y <- LayerNorm(dwconv(folded x)) as fp32.
     void op_fold_dwconv_ln(int B, int C, int k, int dil, int S, const int* seqlen, const float* x, const float* part, const float* b2,
@@ -407,10 +414,10 @@ class Engine {
     static FoldArgs ffn_pending(const FfnForm& f, const FfnArgs& a) {  // the update a K4-split launch leaves pending
         return FoldArgs{a.part, f.split, a.part_stride, a.b2, a.gamma, a.rowvec, a.rv_ld, a.row_b};
     }
-    // the FFN op entry points' set-up: the form `mode` forces (0 two GEMMs, 1 K4, 2 K4-split with ffn_split_choose's S), W1 [I][C] / W2 [C][I]
+    // the FFN op entry points' set-up: the form `mode` forces (0 two GEMMs, 1 K4, 2 K4-split with ffn_split_choose's S, or with `split` where that is not 0), W1 [I][C] / W2 [C][I]
     // (fp32, device) in the 16-bit format, and the launch's shape, packed weight stream and partial-sum buffer in `a` (operands left to fill)
     struct FfnOp { FfnForm f; Linear w1, w2; FfnArgs a; };
-    FfnOp op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2);
+    FfnOp op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2, int split = 0);
     // fs: x is fs->x, and a K4-split block leaves its pointwise pair pending in fs (the caller folds it with the next reader of x)
     void convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
                   const int* conv_len = nullptr, const float* rowvec = nullptr, int rv_ld = 0, const Ragged* rg = nullptr, FoldState* fs = nullptr);

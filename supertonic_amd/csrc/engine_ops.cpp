@@ -298,14 +298,15 @@ void Engine::op_gemm_phases(int dtype, int M, int N, int K, int mode, double* ou
     out6[3] = (double)(tend - tmin); out6[4] = (double)(tmax_in - tmin); out6[5] = (double)n;
 }
 
-Engine::FfnOp Engine::op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2) {
+Engine::FfnOp Engine::op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2, int split) {
     const std::string name(op);
     if (!is_half(dt_)) throw std::invalid_argument(name + ": 16-bit engines only");
     if (mode != FFN_GEMMS && !ffn_fused_supported(dt_, C, I)) throw std::invalid_argument(name + ": shape not supported by the fused kernel");
     FfnOp o;
     o.f.kind = mode;
-    if (mode == FFN_K4_SPLIT && (o.f.split = ffn_split_choose(dt_, C, I, M)) < 2)
+    if (mode == FFN_K4_SPLIT && (o.f.split = split ? split : ffn_split_choose(dt_, C, I, M)) < 2)
         throw std::invalid_argument(name + ": shape not supported by the hidden-split kernel");
+    if (mode == FFN_K4_SPLIT && !ffn_split_valid(dt_, C, I, o.f.split)) throw std::invalid_argument(name + ": not a split this shape runs with");
     o.f.nt = mode == FFN_GEMMS && nt_hints_ && (double)M * I * 2.0 > 128e6;  // (ffn_form's rule)
     void *w1 = act_alloc((int64_t)I * C), *w2 = act_alloc((int64_t)I * C);
     launch_cast(s_, dt_, W1, (int64_t)I * C, w1); launch_cast(s_, dt_, W2, (int64_t)I * C, w2);
@@ -530,6 +531,37 @@ static void down_as(Arena& ar, hipStream_t s, int dtype, const void* d, float* h
         src = w;
     }
     STN_HIP(hipMemcpyAsync(h, src, n * 4, hipMemcpyDeviceToHost, s));
+}
+
+std::string Engine::op_ffn_ex(int M, int C, int I, const float* xn, int ldx, int64_t xn_elems, const float* W1, const float* b1, const float* W2,
+                              const float* b2, const float* gamma, const int* len, int L, const int* row_b, const float* rowvec, int rv_ld, int nseq,
+                              int mode, int split, float* x, int ldo, int64_t x_elems, float* part, int64_t part_stride, int64_t part_elems) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    float* d_w1 = up(ar_, s_, W1, (size_t)I * C);
+    float* d_w2 = up(ar_, s_, W2, (size_t)C * I);
+    FfnOp op = op_ffn_setup("op_ffn_ex", mode, M, C, I, d_w1, d_w2, split);
+    FfnArgs& fa = op.a;
+    fa.xn = up_as(ar_, s_, dt_, xn, (size_t)xn_elems); fa.ldx = ldx;  // as given, the columns past C of a wider row included
+    float* d_x = up(ar_, s_, x, (size_t)x_elems);
+    fa.x = d_x; fa.ldo = ldo;
+    fa.b1 = up(ar_, s_, b1, (size_t)I);
+    fa.b2 = b2 ? up(ar_, s_, b2, (size_t)C) : nullptr;
+    fa.gamma = gamma ? up(ar_, s_, gamma, (size_t)C) : nullptr;
+    fa.rowvec = rowvec ? up(ar_, s_, rowvec, (size_t)nseq * rv_ld) : nullptr; fa.rv_ld = rv_ld;
+    fa.row_b = row_b ? up(ar_, s_, row_b, (size_t)M) : nullptr;
+    fa.len = len ? up(ar_, s_, len, (size_t)nseq) : nullptr; fa.L = L;
+    void* d_part = nullptr;
+    if (op.f.kind == FFN_K4_SPLIT) {  // the caller's buffer takes the place of the set-up's: the partial sums are the result, no fold runs
+        d_part = up_as(ar_, s_, dt_, part, (size_t)part_elems);
+        fa.part = d_part; fa.part_stride = part_stride;
+    }
+    ffn_launch(op.f, C, fa, op.w1, op.w2);
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(x, d_x, sizeof(float) * (size_t)x_elems, hipMemcpyDeviceToHost, s_));
+    if (d_part) down_as(ar_, s_, dt_, d_part, part, (size_t)part_elems);
+    sync();
+    return op.f.str();
 }
 
 std::string Engine::op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,

@@ -1,6 +1,7 @@
 """The ConvNeXt pointwise pair's choice of form (ffn_form in csrc/kernels_ffn.hip, reported by stn_dbg_ffn_form without a device), pinned on
 both sides of every threshold: two GEMMs, K4 or K4-split.  tests/test_gpu_ffn.py checks each form's results; this file keeps a shape from
-drifting to another form unnoticed."""
+drifting to another form unnoticed.  tests/test_gpu_ffn_forms.py runs every K4 and K4-split form against float64 with the GELU form pinned here."""
+import numpy as np
 import pytest
 
 from supertonic_amd import binding
@@ -50,6 +51,40 @@ def test_split_ways_by_row_count():
     # the hidden width must split into an even number of 32-unit tiles per share: I = 1024 (32 tiles) takes 4 and 8 ways, not 12
     assert form("bf16", FFN_ESTIMATOR, (384, 1024), 1000) == "k4split4"
     assert form("bf16", FFN_ESTIMATOR, (384, 1024), 2000) == "k4split8"
+
+
+def test_split_fall_backs_and_lds_ceilings():
+    """ffn_split_choose / ffn_split_valid: a share is an even number of 32-unit tiles, (I / 32) % (2 S) == 0, else the launch falls back to 4 ways."""
+    lib = binding.load()
+    for dtype in ("bf16", "f16"):
+        # I = 1024 (32 tiles): no 12 ways; I = 2304 (72 tiles): no 8 ways; I = 1536 (48 tiles): all three
+        for I, ways in ((1024, (4, 4, 8, 8, 4)), (2304, (12, 12, 4, 4, 4)), (1536, (12, 12, 8, 8, 4)), (8192, (4, 4, 8, 8, 4))):
+            got = tuple(form(dtype, FFN_ESTIMATOR, (384, I), M) for M in (1, 1536, 1537, 4096, 4097))
+            assert got == tuple(f"k4split{w}" for w in ways), (dtype, I, got)
+        # the LDS ceilings (ring + biases + at C = 384 the fifth buffer <= 160 KiB; I <= 8192): K4 up to them, nothing one step of 64 past them
+        d = binding._DTYPES[dtype]
+        assert lib.stn_ffn_fused_forms(d, 384, 8192) == 2 and lib.stn_ffn_fused_forms(d, 384, 8256) == 0
+        assert lib.stn_ffn_fused_forms(d, 512, 7168) == 1 and lib.stn_ffn_fused_forms(d, 512, 7232) == 0
+        assert form(dtype, FFN_TEXT, (384, 8192), 4000, mask=15, min_rows=1) == "k4" and form(dtype, FFN_TEXT, (384, 8256), 4000, mask=15, min_rows=1) == "gemms"
+        assert form(dtype, FFN_VOCODER, (512, 7168), 4000, min_rows=1) == "k4" and form(dtype, FFN_VOCODER, (512, 7232), 4000, min_rows=1) == "gemms"
+        assert form(dtype, FFN_ESTIMATOR, (384, 8256), 1000) == "gemms"
+        # the smallest ring schedule and the floor: I = 128 runs K4 (no split: fewer than 1024 hidden units), I = 64 does not
+        assert lib.stn_ffn_fused_forms(d, 384, 128) == 1 and lib.stn_ffn_fused_forms(d, 512, 128) == 1
+        assert lib.stn_ffn_fused_forms(d, 384, 64) == 0 and lib.stn_ffn_fused_forms(d, 384, 160) == 0
+        assert form(dtype, FFN_ESTIMATOR, (384, 128), 1000) == "gemms" and form(dtype, FFN_ESTIMATOR, (384, 128), 1000, mask=2, min_rows=1) == "k4"
+
+
+def test_gelu_form_against_erf():
+    """The GELU form K4 computes in both formats and the tiled pw1 for bf16 outputs (gelu_bf16_f, kernels_dev.hpp; the asm blocks of
+    kernels_ffn_body.inc), x / (1 + exp2(x (x^2 * -0.10294324 - 2.30220819))), against the erf form in float64 on [-12, 12], grid 1e-5: the
+    largest deviation is 4.73e-4, at x = -2.70 and, both forms being x times a sigmoid-like factor, at +2.70.  The upper bound is what the kernels' comments promise; the lower one keeps the constants
+    from drifting unnoticed."""
+    from scipy.special import erf
+    x = np.arange(-1200000, 1200001) * 1e-5
+    got = x / (1.0 + np.exp2(x * (x * x * -0.10294324 - 2.30220819)))
+    err = np.abs(got - 0.5 * x * (1.0 + erf(x / np.sqrt(2.0))))
+    assert 4.5e-4 < err.max() <= 4.8e-4, err.max()
+    assert abs(abs(x[err.argmax()]) - 2.70) < 0.01, x[err.argmax()]
 
 
 def test_split_shapes():

@@ -65,7 +65,7 @@ def test_ffn_fused_vs_float64(eng, M, C, I, nseq):
     ref = ref64(*ops)
     upd = ref - ops[6]  # compare the UPDATE (the residual itself is copied through)
     mx, rms = rel_err(got - ops[6], upd)
-    # bf16 GELU form (|err| <= 3e-4 absolute before rounding) + one bf16 rounding of the hidden activation that may fall on the
+    # bf16 GELU form (|err| <= 4.8e-4 absolute before rounding) + one bf16 rounding of the hidden activation that may fall on the
     # other side of a tie than the float64 reference's: a few 1e-3 of the update's rms
     assert rms < 3e-3 and mx < 3e-2, (mx, rms)
     assert np.all(np.isfinite(got))
