@@ -535,6 +535,29 @@ int stn_op_ffn_bench(stn_handle* h, int M, int C, int I, int fused, int iters, d
 int stn_op_fold_dwconv_ln(stn_handle* h, int B, int C, int k, int dil, int S, const int32_t* seqlen, const float* x, const float* part,
                           const float* b2_or_null, const float* gamma_or_null, const float* rowvec_or_null /*[B,C]*/, const float* w /*[C,k]*/,
                           const float* bias, const float* ln_g, const float* ln_b, float* x_out, float* y);
+/* The same launcher (launch_fold_dwconv_ln, once) on the caller's whole buffers (the kernel parity tests of every fold + dwconv + LayerNorm
+ * form).  dtype: STN_DTYPE_BF16 or STN_DTYPE_F16, whatever the engine's format.  Packed rows: sequence b owns seqlen[b] (0 allowed) consecutive
+ * rows, M = their sum > 0, row offsets computed as the engine does; L >= every length (a larger L adds placeholder workgroups); B <= 1024.
+ * run_frames: FoldArgs::run_frames (0, 40, 48; other values are ignored by the launcher).  part: part_elems floats, split s at
+ * part + s*part_stride (part_stride >= M*C, a multiple of 8; part_elems >= (S-1)*part_stride + M*C), rounded to dtype on upload.  rowvec: B
+ * rows of rv_ld (>= C, a multiple of 4) or NULL; b2 (NULL: 0), gamma (NULL: 1).  x_in: x_rows rows of C.  x_out (x_out_rows rows) and y (y_rows
+ * rows) are the caller's whole buffers: uploaded as given (y rounded to dtype) and written back whole (16-bit values widened to fp32, exactly),
+ * so what lies outside the written rows can be checked.  eps = 1e-6.  Refused (STN_ERR_INVALID): what stn_dbg_fold_dwconv_ln_form refuses,
+ * buffers smaller than the extents the launch addresses, B > 1024.  form: the form that ran (as stn_dbg_fold_dwconv_ln_form), NUL-terminated,
+ * truncated to form_cap; may be NULL. */
+int stn_op_fold_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, int S, int run_frames, const int32_t* seqlen,
+                             const float* x_in, int64_t x_rows, const float* part, int64_t part_stride, int64_t part_elems,
+                             const float* b2_or_null, const float* gamma_or_null, const float* rowvec_or_null, int rv_ld,
+                             const float* w /*[C,k]*/, const float* bias, const float* ln_g, const float* ln_b, float* x_out, int64_t x_out_rows,
+                             float* y, int64_t y_rows, char* form, size_t form_cap);
+/* diagnostics (no device needed): the form the fold + depthwise conv + LayerNorm launcher takes for B packed sequences with padded length L:
+ * everything that selects code — "fold_dwconv_ln<fmt,K5|K7,rv|norv,ns3|ns4,S4|S8|S12|S24,U1|U2|U3> run R cps N": the kernel instantiation
+ * (ns: float4 slots per lane, 3 up to C = 384; U: window rows per thread and trip of phase 1), the run length R in frames (8 when
+ * B * ceil(L/32) < 64, else 32, or run_frames where that is 40 or 48 and its image fits 160 KiB of LDS) and the workgroups per sequence
+ * N = ceil(L / R); the grid is B * N.  Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher
+ * refuses (STN_ERR_INVALID: fp32, B or L < 1, C % 8, C > 512, k outside {5, 7}, S outside {4, 8, 12, 24}, a dilation whose 32-frame image
+ * does not fit LDS). */
+int stn_dbg_fold_dwconv_ln_form(int dtype, int B, int L, int C, int k, int dil, int S, int has_rowvec, int run_frames, char* out, size_t cap);
 /* timing of one estimator-style block on B packed sequences of L frames, random device-resident operands: mode 0 = dwconv_ln + pw1 +
  * pw2, mode 2 = fold_dwconv_ln + K4-split.  out6: avg ms per block, avg ms of its conv kernel alone; mode 2: mean shader-clock cycles per
  * fold_dwconv_ln workgroup in phase 1 / at the hand-over barrier / in phase 2, and the launch's span (first entry to last exit) */

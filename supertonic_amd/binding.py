@@ -271,6 +271,11 @@ def load():
     L.stn_set_fused_ffn.argtypes = [vp, ci]
     L.stn_set_fused_ffn_min_rows.argtypes = [vp, ctypes.c_int64, ctypes.c_int64]
     L.stn_op_fold_dwconv_ln.argtypes = [vp, ci, ci, ci, ci, ci, _i32p, _f32p, _f32p, vp, vp, vp, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
+    L.stn_op_fold_dwconv_ln_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, _i32p, _f32p, ctypes.c_int64, _f32p, ctypes.c_int64, ctypes.c_int64, vp, vp,
+                                           vp, ci, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_int64, _f32p, ctypes.c_int64, ctypes.c_char_p,
+                                           ctypes.c_size_t]
+    L.stn_dbg_fold_dwconv_ln_form.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_fold_dwconv_ln_form.restype = ctypes.c_int
     L.stn_op_block_bench.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
     # include/stn_group.h: several devices in one process
     L.stn_group_create.argtypes = [ci, vp, ci, ctypes.POINTER(vp)]
@@ -483,6 +488,18 @@ def dwconv_ln_form(dtype, B, L, C, k, packed=False):
     r = load().stn_dbg_dwconv_ln_form(_DTYPES[dtype], int(B), int(L), int(C), int(k), int(bool(packed)), buf, len(buf))
     if r < 0:
         raise StnError(r, "stn_dbg_dwconv_ln_form: the launcher refuses this call")
+    return buf.value.decode()
+
+
+def fold_dwconv_ln_form(dtype, B, L, C, k, dil, S, rowvec=True, run_frames=0):
+    """The form the fold + depthwise-conv + LayerNorm launcher takes (stn_dbg_fold_dwconv_ln_form; host-only), e.g.
+    "fold_dwconv_ln<bf16,K5,rv,ns3,S4,U3> run 40 cps 3": kernel instantiation, run length in frames, workgroups per sequence.  Raises
+    StnError where the launcher refuses the call."""
+    buf = ctypes.create_string_buffer(96)
+    r = load().stn_dbg_fold_dwconv_ln_form(_DTYPES[dtype], int(B), int(L), int(C), int(k), int(dil), int(S), int(bool(rowvec)), int(run_frames),
+                                           buf, len(buf))
+    if r < 0:
+        raise StnError(r, "stn_dbg_fold_dwconv_ln_form: the launcher refuses this call")
     return buf.value.decode()
 
 
@@ -1064,6 +1081,26 @@ class Engine:
         self._ck(self._lib.stn_op_fold_dwconv_ln(self._h, len(seqlen), C, k, dil, S, seqlen, _c(x, np.float32), _c(part, np.float32), p(b2a), p(ga), p(rva),
                                                  _c(w, np.float32), _c(bias, np.float32), _c(g, np.float32), _c(b, np.float32), xo, y))
         return xo, y
+
+    def op_fold_dwconv_ln_ex(self, seqlen, L, x_in, part, part_stride, S, b2, gamma, rowvec, w, bias, g, b, dil, x_out, y, run_frames=0, dtype=None):
+        """launch_fold_dwconv_ln on whole buffers (stn_op_fold_dwconv_ln_ex).  x_in, x_out, y: 2-D [rows, C]; part: flat, split s at
+        s * part_stride; rowvec [B, rv_ld] or None; w [C, k].  Returns (x_out, y as new fp32 arrays, whole; form string)."""
+        seqlen = _c(seqlen, np.int32)
+        x_in = _c(x_in, np.float32)
+        part = _c(part, np.float32).reshape(-1)
+        xo = np.array(x_out, dtype=np.float32, order="C", copy=True)
+        yo = np.array(y, dtype=np.float32, order="C", copy=True)
+        C = x_in.shape[1]
+        w = _c(w, np.float32)
+        _b2, b2p = _opt(b2, np.float32)
+        _g, gp = _opt(gamma, np.float32)
+        _v, vp_ = _opt(rowvec, np.float32)
+        form = ctypes.create_string_buffer(96)
+        self._ck(self._lib.stn_op_fold_dwconv_ln_ex(self._h, self.dtype if dtype is None else _DTYPES[dtype], len(seqlen), int(L), C, w.shape[1], int(dil),
+                                                    int(S), int(run_frames), seqlen, x_in.reshape(-1), x_in.shape[0], part, int(part_stride), part.size,
+                                                    b2p, gp, vp_, C if _v is None else _v.shape[1], w, _c(bias, np.float32), _c(g, np.float32),
+                                                    _c(b, np.float32), xo.reshape(-1), xo.shape[0], yo.reshape(-1), yo.shape[0], form, ctypes.sizeof(form)))
+        return xo, yo, form.value.decode()
 
     def op_block_bench(self, B, L, C, I, k, dil, mode, iters=20):
         out = (ctypes.c_double * 6)()

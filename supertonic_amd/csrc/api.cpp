@@ -750,6 +750,41 @@ int stn_op_fold_dwconv_ln(stn_handle* h, int B, int C, int k, int dil, int S, co
                  need(tot > 0, "stn_op_fold_dwconv_ln: no rows");
                  h->eng->op_fold_dwconv_ln(B, C, k, dil, S, seqlen, x, part, b2, gamma, rowvec, w, bias, g, b, x_out, y); })
 }
+static void fold_dwconv_ln_ex_checked(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, int S, int run_frames, const int32_t* seqlen,
+                                      const float* x_in, int64_t x_rows, const float* part, int64_t part_stride, int64_t part_elems, const float* b2,
+                                      const float* gamma, const float* rowvec, int rv_ld, const float* w, const float* bias, const float* g,
+                                      const float* b, float* x_out, int64_t x_out_rows, float* y, int64_t y_rows, char* form, size_t form_cap) {
+    const char* who = "stn_op_fold_dwconv_ln_ex";
+    auto req = [&](bool ok, const char* what) { need(ok, (std::string(who) + ": " + what).c_str()); };
+    req(B > 0 && L > 0 && C > 0 && seqlen && x_in && part && w && bias && g && b && x_out && y, "bad argument");
+    req(dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "a 16-bit format needed");
+    req(B <= 1024, "B <= 1024 needed");
+    try { (void)stn::fold_dwconv_ln_form(dtype, B, L, C, k, dil, S, rowvec != nullptr, run_frames); }
+    catch (const std::invalid_argument& e) { req(false, e.what()); }
+    int64_t tot = 0;
+    for (int i = 0; i < B; ++i) { req(seqlen[i] >= 0 && seqlen[i] <= L, "seqlen out of [0, L]"); tot += seqlen[i]; }
+    req(tot > 0, "no rows");
+    req(tot * C * 2 < 0x7FFFFFFFll, "too many rows");
+    req(x_rows >= tot && x_out_rows >= tot && y_rows >= tot, "x_in / x_out / y hold fewer rows than the launch addresses");
+    req(part_stride >= tot * C && part_stride % 8 == 0 && part_elems >= (int64_t)(S - 1) * part_stride + tot * C, "part smaller than the launch addresses, or a stride that is no multiple of 8");
+    req(!rowvec || (rv_ld >= C && rv_ld % 4 == 0), "rv_ld >= C, a multiple of 4, needed");
+    const std::string f = h->eng->op_fold_dwconv_ln_ex(dtype, B, L, C, k, dil, S, run_frames, seqlen, x_in, x_rows, part, part_stride, part_elems, b2, gamma,
+                                                       rowvec, rv_ld, w, bias, g, b, x_out, x_out_rows, y, y_rows);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_fold_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, int S, int run_frames, const int32_t* seqlen,
+                             const float* x_in, int64_t x_rows, const float* part, int64_t part_stride, int64_t part_elems, const float* b2,
+                             const float* gamma, const float* rowvec, int rv_ld, const float* w, const float* bias, const float* g, const float* b,
+                             float* x_out, int64_t x_out_rows, float* y, int64_t y_rows, char* form, size_t form_cap) {
+    STN_TRY(h, fold_dwconv_ln_ex_checked(h, dtype, B, L, C, k, dil, S, run_frames, seqlen, x_in, x_rows, part, part_stride, part_elems, b2, gamma, rowvec,
+                                         rv_ld, w, bias, g, b, x_out, x_out_rows, y, y_rows, form, form_cap))
+}
+int stn_dbg_fold_dwconv_ln_form(int dtype, int B, int L, int C, int k, int dil, int S, int has_rowvec, int run_frames, char* out, size_t cap) {
+    std::string f;
+    try { f = stn::fold_dwconv_ln_form(dtype, B, L, C, k, dil, S, has_rowvec != 0, run_frames).str(); } catch (const std::exception&) { return STN_ERR_INVALID; }
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
+}
 int stn_op_block_bench(stn_handle* h, int B, int L, int C, int I, int k, int dil, int mode, int iters, double* out2) {
     STN_TRY(h, { need(B > 0 && L > 0 && C > 0 && I > 0 && C % 8 == 0 && I % 8 == 0 && (k == 5 || k == 7) && dil > 0 && iters > 0 && out2 && (mode == 0 || mode == 2),
                       "stn_op_block_bench: bad argument");

@@ -367,6 +367,13 @@ class Engine {
     void op_fold_dwconv_ln(int B, int C, int k, int dil, int S, const int* seqlen, const float* x, const float* part, const float* b2,
                            const float* gamma, const float* rowvec /* [B][C] or null */, const float* w /*[C][k]*/, const float* bias,
                            const float* g, const float* b, float* x_out, float* y);
+    // launch_fold_dwconv_ln, once, on the caller's whole buffers (stn_op_fold_dwconv_ln_ex): dtype BF16 / F16 whatever the engine's; L >= every length;
+    // row_off from launch_row_map; part [part_elems] rounded to dtype, splits part_stride apart; rowvec [B][rv_ld]; x_in [x_rows][C]; x_out
+    // [x_out_rows][C] and y [y_rows][C] uploaded as given (y rounded) and downloaded whole.  Returns the form it ran (FoldDwconvLnForm::str).
+    std::string op_fold_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, int S, int run_frames, const int* seqlen, const float* x_in,
+                                     int64_t x_rows, const float* part, int64_t part_stride, int64_t part_elems, const float* b2, const float* gamma,
+                                     const float* rowvec, int rv_ld, const float* w, const float* bias, const float* g, const float* b, float* x_out,
+                                     int64_t x_out_rows, float* y, int64_t y_rows);
     // device-resident timing of the block's pointwise pair on random operands: out[0] = avg ms per call (fused: one launch,
     // unfused: pw1 + pw2); fused only: out[1..3] = mean cycles per workgroup to the first stage / in the tile loop / in the
     // epilogue, out[4] = workgroups

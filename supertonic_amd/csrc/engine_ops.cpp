@@ -413,43 +413,13 @@ void Engine::op_ffn_bench(int M, int C, int I, int mode, int iters, double* out5
 void Engine::op_fold_dwconv_ln(int B, int C, int k, int dil, int S, const int* seqlen, const float* x, const float* part, const float* b2,
                                const float* gamma, const float* rowvec, const float* w, const float* bias, const float* g, const float* b,
                                float* x_out, float* y) {
-    STN_HIP(hipSetDevice(device_));
     if (!is_half(dt_)) throw std::invalid_argument("op_fold_dwconv_ln: 16-bit engines only");
-    ar_.reset();
-    std::vector<int> off(B + 1, 0);
     int L = 0;
-    for (int i = 0; i < B; ++i) { off[i + 1] = off[i] + seqlen[i]; L = std::max(L, seqlen[i]); }
-    const int64_t M = off[B];
-    const size_t n = (size_t)M * C;
-    std::vector<float> wt((size_t)C * k);
-    for (int c = 0; c < C; ++c) for (int j = 0; j < k; ++j) wt[(size_t)j * C + c] = w[(size_t)c * k + j];
-    const int* dlen = up(ar_, s_, seqlen, (size_t)B);
-    const int* doff = up(ar_, s_, off.data(), (size_t)B + 1);
-    float* dx = up(ar_, s_, x, n);
-    float* dp32 = up(ar_, s_, part, n * S);
-    float* db2 = b2 ? up(ar_, s_, b2, (size_t)C) : nullptr;
-    float* dgm = gamma ? up(ar_, s_, gamma, (size_t)C) : nullptr;
-    float* drv = rowvec ? up(ar_, s_, rowvec, (size_t)B * C) : nullptr;
-    float* dw = up(ar_, s_, wt.data(), wt.size());
-    float* db = up(ar_, s_, bias, (size_t)C);
-    float* dg = up(ar_, s_, g, (size_t)C);
-    float* dbt = up(ar_, s_, b, (size_t)C);
-    void* dp16 = act_alloc((int64_t)n * S);
-    launch_cast(s_, dt_, dp32, (int64_t)n * S, dp16);
-    float* dxo = f32_alloc((int64_t)n);
-    void* dy = act_alloc((int64_t)n);
-    float* dy32 = f32_alloc((int64_t)n);
-    float* ones = f32_alloc(C);
-    launch_fill(s_, ones, C, 1.f);
-    float* zeros = f32_alloc(C);
-    launch_fill(s_, zeros, C, 0.f);
-    FoldArgs fo; fo.part = dp16; fo.S = S; fo.part_stride = (int64_t)n; fo.b2 = db2 ? db2 : zeros; fo.gamma = dgm ? dgm : ones; fo.rowvec = drv; fo.rv_ld = C;
-    launch_fold_dwconv_ln(s_, dt_, dx, dxo, B, L, C, fo, dw, db, k, dil, dg, dbt, 1e-6f, dy, dlen, doff);
-    launch_half_to_f32(s_, dt_, dy, (int64_t)n, dy32);
-    STN_HIP(hipGetLastError());
-    STN_HIP(hipMemcpyAsync(x_out, dxo, n * 4, hipMemcpyDeviceToHost, s_));
-    STN_HIP(hipMemcpyAsync(y, dy32, n * 4, hipMemcpyDeviceToHost, s_));
-    sync();
+    int64_t M = 0;
+    for (int i = 0; i < B; ++i) { M += seqlen[i]; L = std::max(L, seqlen[i]); }
+    std::fill(x_out, x_out + M * C, 0.f);  // (the caller's buffers are results only here: nothing of what they held goes to the device)
+    std::fill(y, y + M * C, 0.f);
+    op_fold_dwconv_ln_ex(dt_, B, L, C, k, dil, S, 0, seqlen, x, M, part, M * C, M * C * S, b2, gamma, rowvec, C, w, bias, g, b, x_out, M, y, M);
 }
 
 void Engine::op_block_bench(int B, int L, int C, int I, int k, int dil, int mode, int iters, double* out2) {
@@ -615,6 +585,41 @@ void Engine::op_fold_ln(int dtype, int M, int C, int S, const float* part, const
     STN_HIP(hipMemcpyAsync(x, dx, n * 4, hipMemcpyDeviceToHost, s_));
     down_as(ar_, s_, dtype, dy, y, n);
     sync();
+}
+
+std::string Engine::op_fold_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, int S, int run_frames, const int* seqlen, const float* x_in,
+                                         int64_t x_rows, const float* part, int64_t part_stride, int64_t part_elems, const float* b2, const float* gamma,
+                                         const float* rowvec, int rv_ld, const float* w, const float* bias, const float* g, const float* b, float* x_out,
+                                         int64_t x_out_rows, float* y, int64_t y_rows) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    std::vector<float> wt((size_t)C * k);
+    for (int c = 0; c < C; ++c) for (int j = 0; j < k; ++j) wt[(size_t)j * C + c] = w[(size_t)c * k + j];
+    const int* dlen = up(ar_, s_, seqlen, (size_t)B);
+    int* doff = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+    launch_row_map(s_, dlen, B, doff, nullptr);
+    float* dx = up(ar_, s_, x_in, (size_t)x_rows * C);  // as given, the rows behind the last sequence included
+    float* dxo = up(ar_, s_, x_out, (size_t)x_out_rows * C);
+    void* dy = up_as(ar_, s_, dtype, y, (size_t)y_rows * C);
+    float* dw = up(ar_, s_, wt.data(), wt.size());
+    float* db = up(ar_, s_, bias, (size_t)C);
+    float* dg = up(ar_, s_, g, (size_t)C);
+    float* dbt = up(ar_, s_, b, (size_t)C);
+    FoldArgs fo;
+    fo.part = up_as(ar_, s_, dtype, part, (size_t)part_elems); fo.S = S; fo.part_stride = part_stride;
+    if (b2) fo.b2 = up(ar_, s_, b2, (size_t)C);
+    else { float* z = f32_alloc(C); launch_fill(s_, z, C, 0.f); fo.b2 = z; }
+    if (gamma) fo.gamma = up(ar_, s_, gamma, (size_t)C);
+    else { float* o = f32_alloc(C); launch_fill(s_, o, C, 1.f); fo.gamma = o; }
+    fo.rowvec = rowvec ? up(ar_, s_, rowvec, (size_t)B * rv_ld) : nullptr; fo.rv_ld = rowvec ? rv_ld : C;
+    fo.run_frames = run_frames;
+    const std::string form = fold_dwconv_ln_form(dtype, B, L, C, k, dil, S, rowvec != nullptr, run_frames).str();  // the decision launch_fold_dwconv_ln takes
+    launch_fold_dwconv_ln(s_, dtype, dx, dxo, B, L, C, fo, dw, db, k, dil, dg, dbt, 1e-6f, dy, dlen, doff);
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(x_out, dxo, sizeof(float) * (size_t)x_out_rows * C, hipMemcpyDeviceToHost, s_));
+    down_as(ar_, s_, dtype, dy, y, (size_t)y_rows * C);
+    sync();
+    return form;
 }
 
 // One layout kernel of kernels_misc.hip on host operands (stn_op_layout).  Every destination is the caller's whole buffer: uploaded as given,

@@ -212,6 +212,20 @@ void launch_fold_ln(hipStream_t s, int act_dtype, float* x, int64_t M, int C, co
 // packed rows only (row_off / seqlen as launch_dwconv_ln): x_out <- folded x_in (x_out != x_in: a workgroup re-folds the halo rows
 // of its neighbours);  y <- LayerNorm(dwconv(folded x)).  k = 5 or 7, C % 8 == 0, C <= 512.
 bool fold_dwconv_ln_supported(int C, int k, int dil);
+// The form a fold + depthwise conv + LayerNorm call takes — one decision, made by fold_dwconv_ln_form and executed by launch_fold_dwconv_ln, so
+// that what the diagnostics report (stn_dbg_fold_dwconv_ln_form, stn_op_fold_dwconv_ln_ex) is what runs: the instantiation
+// fold_dwconv_ln_kernel<OutT / F16, K, RV, NSLOT, S> (NSLOT 3 up to C = 384, 4 above; U: window rows per thread and trip of phase 1), the run
+// length (8 when B * ceil(L / 32) < 64, else 32, else run_frames where that is 40 or 48 and its image fits 160 KiB of LDS), the workgroups per
+// sequence cps = ceil(L / run), the grid B * cps and the dynamic LDS bytes.
+struct FoldDwconvLnForm {
+    int act_dtype = BF16, K = 5, nslot = 3, S = 4, U = 1, run = 32, cps = 1;
+    bool rv = false;
+    unsigned grid = 0;
+    size_t lds = 0;
+    std::string str() const;  // "fold_dwconv_ln<bf16,K5,rv,ns3,S4,U3> run 40 cps 3" ("norv" without a per-sequence vector)
+};
+// Throws std::invalid_argument where the launcher refuses: fp32, B or L < 1, !fold_dwconv_ln_supported(C, k, dil), S outside {4, 8, 12, 24}.
+FoldDwconvLnForm fold_dwconv_ln_form(int act_dtype, int B, int L, int C, int k, int dil, int S, bool has_rowvec, int run_frames);
 void launch_fold_dwconv_ln(hipStream_t s, int act_dtype, const float* x_in, float* x_out, int B, int L, int C, const FoldArgs& f, const float* w_t,
                            const float* bias, int k, int dil, const float* ln_g, const float* ln_b, float eps, void* y, const int* seqlen,
                            const int* row_off);

@@ -563,6 +563,8 @@ void launch_fold_ln(hipStream_t s, int act_dtype, float* x, int64_t M, int C, co
 // Few sequences (a single utterance: two workgroups) are cut into runs of 8 frames instead: more workgroups, one pass of phase-1 loads each
 // instead of two to four dependent ones; a frame's arithmetic does not depend on the run it falls in, so the result is the same bit for bit.
 static constexpr int FOLD_TCH = 32, FOLD_TCH_FEW = 8, FOLD_TCH_MAX = 48, FOLD_NT = 1024;  // FOLD_TCH == 2 * wavefronts per workgroup (the longest run)
+// window rows a thread of phase 1 loads per trip (the kernel's U; fold_dwconv_ln_form reports the same value)
+constexpr int fold_phase1_rows(int S, int K, int nslot) { return S <= 4 ? (K == 5 && nslot <= 3 ? 3 : 2) : 1; }
 template <typename OutT, bool F16, int K, bool RV, int FOLD_NSLOT /* float4 slots per lane of a half wavefront: ceil(C / 128) */, int S>
 __global__ __launch_bounds__(FOLD_NT) void fold_dwconv_ln_kernel(const float* __restrict__ xin, float* __restrict__ xout, int cps, int C,
                                                                  const uint16_t* __restrict__ part, int64_t pstride,
@@ -603,7 +605,7 @@ __global__ __launch_bounds__(FOLD_NT) void fold_dwconv_ln_kernel(const float* __
     // Three rows per thread and trip when there are four partial sums: a run of 29 frames with a halo of 2 x 16 (dilation 8) is 61 rows = ONE trip of
     // 3 x 21 rows — one global round trip instead of two dependent ones.  The third row's loads are issued only by the threads that have one.
     // (the wider variants — C = 512, seven taps — keep two rows: three would spill; more splits: one row at a time, the partial sums in chunks of 12 loads)
-    constexpr int U = S <= 4 ? (K == 5 && FOLD_NSLOT <= 3 ? 3 : 2) : 1;
+    constexpr int U = fold_phase1_rows(S, K, FOLD_NSLOT);
     const int rpp = FOLD_NT / C8;  // rows per pass of the workgroup
     const int c8 = tid % C8, rq = tid / C8;
     if (rq < rpp) {
@@ -766,35 +768,59 @@ bool fold_dwconv_ln_supported(int C, int k, int dil) {
     return C % 8 == 0 && C <= 512 && (k == 5 || k == 7) && dil >= 1 && fold_dwconv_lds(C, k, dil) <= 160 * 1024;
 }
 
+std::string FoldDwconvLnForm::str() const {
+    char m_[96];
+    snprintf(m_, sizeof m_, "fold_dwconv_ln<%s,K%d,%s,ns%d,S%d,U%d> run %d cps %d", act_dtype == F16 ? "f16" : "bf16", K, rv ? "rv" : "norv", nslot, S, U, run, cps);
+    return m_;
+}
+
+// force: the launcher's A/B switch (8, 32, 40 or 48; 0: none)
+static FoldDwconvLnForm fold_dwconv_ln_form_forced(int act_dtype, int B, int L, int C, int k, int dil, int S, bool has_rowvec, int run_frames, int force) {
+    if (!is_half(act_dtype) || B < 1 || L < 1 || !fold_dwconv_ln_supported(C, k, dil) || (S != 4 && S != 8 && S != 12 && S != 24) ||
+        (int64_t)B * ((L + FOLD_TCH_FEW - 1) / FOLD_TCH_FEW) > 0x7FFFFFFFll)
+        throw std::invalid_argument("fold_dwconv_ln: 16-bit format, k in {5,7}, C % 8 == 0, C <= 512, 4, 8, 12 or 24 splits and an image within 160 KiB of LDS needed");
+    FoldDwconvLnForm f;
+    f.act_dtype = act_dtype; f.K = k; f.rv = has_rowvec; f.S = S;
+    f.nslot = C <= 384 ? 3 : 4;
+    f.U = fold_phase1_rows(S, k, f.nslot);
+    int tch = force == FOLD_TCH || force == FOLD_TCH_FEW ? force : (int64_t)B * ((L + FOLD_TCH - 1) / FOLD_TCH) < 64 ? FOLD_TCH_FEW : FOLD_TCH;
+    if ((force == 40 || force == 48) && fold_dwconv_lds(C, k, dil, force) <= 160 * 1024) tch = force;
+    if (!force && tch == FOLD_TCH && run_frames > FOLD_TCH && run_frames <= FOLD_TCH_MAX && run_frames % 8 == 0 && fold_dwconv_lds(C, k, dil, run_frames) <= 160 * 1024)
+        tch = run_frames;  // fewer rounds of workgroups for these lengths (fold_run_frames)
+    f.run = tch;
+    f.cps = (L + tch - 1) / tch;
+    f.grid = (unsigned)((int64_t)B * f.cps);
+    f.lds = fold_dwconv_lds(C, k, dil, tch);
+    return f;
+}
+FoldDwconvLnForm fold_dwconv_ln_form(int act_dtype, int B, int L, int C, int k, int dil, int S, bool has_rowvec, int run_frames) {
+    return fold_dwconv_ln_form_forced(act_dtype, B, L, C, k, dil, S, has_rowvec, run_frames, 0);
+}
+
 template <typename OutT, bool F16, int K, bool RV, int NSLOT, int S>
-static void launch_fold_dwconv_ln_t3(hipStream_t s, const float* x_in, float* x_out, int B, int L, int C, const FoldArgs& f, const float* w_t,
+static void launch_fold_dwconv_ln_t3(hipStream_t s, const FoldDwconvLnForm& fm, const float* x_in, float* x_out, int C, const FoldArgs& f, const float* w_t,
                                      const float* bias, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
     static PerDeviceOnce attr_once;
     if (attr_once.need())
         stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&fold_dwconv_ln_kernel<OutT, F16, K, RV, NSLOT, S>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           160 * 1024), "hipFuncSetAttribute(fold_dwconv_ln)");
-    static const int force = [] { const char* e = stn::dev_env("STN_FOLD_TCH"); return e ? atoi(e) : 0; }();  // A/B switch: 8, 32, 40 or 48
-    int tch = force == FOLD_TCH || force == FOLD_TCH_FEW ? force : (int64_t)B * ((L + FOLD_TCH - 1) / FOLD_TCH) < 64 ? FOLD_TCH_FEW : FOLD_TCH;
-    if ((force == 40 || force == 48) && fold_dwconv_lds(C, K, dil, force) <= 160 * 1024) tch = force;
-    if (!force && tch == FOLD_TCH && f.run_frames > FOLD_TCH && f.run_frames <= FOLD_TCH_MAX && f.run_frames % 8 == 0 && fold_dwconv_lds(C, K, dil, f.run_frames) <= 160 * 1024)
-        tch = f.run_frames;  // fewer rounds of workgroups for these lengths (fold_run_frames)
-    const int cps = (L + tch - 1) / tch;
-    STN_KLAUNCH((fold_dwconv_ln_kernel<OutT, F16, K, RV, NSLOT, S>), dim3((unsigned)((int64_t)B * cps)), dim3(FOLD_NT), fold_dwconv_lds(C, K, dil, tch), s, x_in, x_out, cps, C,
-                static_cast<const uint16_t*>(f.part), f.part_stride, f.b2, f.gamma, f.rowvec, f.rv_ld, w_t, bias, dil, g, b, eps, 1.0f / (float)C, y, seqlen, row_off, f.ts, tch);
+    if (fm.K != K || fm.rv != RV || fm.nslot != NSLOT || fm.S != S || fm.U != fold_phase1_rows(S, K, NSLOT)) throw std::logic_error("fold_dwconv_ln: no kernel for form " + fm.str());
+    STN_KLAUNCH((fold_dwconv_ln_kernel<OutT, F16, K, RV, NSLOT, S>), dim3(fm.grid), dim3(FOLD_NT), fm.lds, s, x_in, x_out, fm.cps, C,
+                static_cast<const uint16_t*>(f.part), f.part_stride, f.b2, f.gamma, f.rowvec, f.rv_ld, w_t, bias, dil, g, b, eps, 1.0f / (float)C, y, seqlen, row_off, f.ts, fm.run);
 }
 template <typename OutT, bool F16, int K, bool RV, int NSLOT>
-static void launch_fold_dwconv_ln_t2(hipStream_t s, const float* x_in, float* x_out, int B, int L, int C, const FoldArgs& f, const float* w_t,
+static void launch_fold_dwconv_ln_t2(hipStream_t s, const FoldDwconvLnForm& fm, const float* x_in, float* x_out, int C, const FoldArgs& f, const float* w_t,
                                      const float* bias, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
-    if (f.S == 4) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 4>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    else if (f.S == 8) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 8>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    else if (f.S == 12) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 12>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    else launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 24>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    if (fm.S == 4) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 4>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    else if (fm.S == 8) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 8>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    else if (fm.S == 12) launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 12>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    else launch_fold_dwconv_ln_t3<OutT, F16, K, RV, NSLOT, 24>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
 }
 template <typename OutT, bool F16, int K, bool RV>
-static void launch_fold_dwconv_ln_t(hipStream_t s, const float* x_in, float* x_out, int B, int L, int C, const FoldArgs& f, const float* w_t,
+static void launch_fold_dwconv_ln_t(hipStream_t s, const FoldDwconvLnForm& fm, const float* x_in, float* x_out, int C, const FoldArgs& f, const float* w_t,
                                     const float* bias, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
-    if (C <= 384) launch_fold_dwconv_ln_t2<OutT, F16, K, RV, 3>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-    else launch_fold_dwconv_ln_t2<OutT, F16, K, RV, 4>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    if (fm.nslot == 3) launch_fold_dwconv_ln_t2<OutT, F16, K, RV, 3>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+    else launch_fold_dwconv_ln_t2<OutT, F16, K, RV, 4>(s, fm, x_in, x_out, C, f, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
 }
 
 void launch_fold_dwconv_ln(hipStream_t s, int act_dtype, const float* x_in, float* x_out, int B, int L, int C, const FoldArgs& f, const float* w_t,
@@ -805,8 +831,10 @@ void launch_fold_dwconv_ln(hipStream_t s, int act_dtype, const float* x_in, floa
         (int64_t)B * ((L + FOLD_TCH_FEW - 1) / FOLD_TCH_FEW) > 0x7FFFFFFFll)
         throw std::invalid_argument("launch_fold_dwconv_ln: packed 16-bit rows, separate output, k in {5,7}, C % 8 == 0, C <= 512 needed");
     check_fold_args(f, 0, C, "launch_fold_dwconv_ln");
-#define STN_FOLD_DW(OUT, F16_, K_) do { if (f.rowvec) launch_fold_dwconv_ln_t<OUT, F16_, K_, true>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, ln_g, ln_b, eps, static_cast<OUT*>(y), seqlen, row_off); \
-                                        else launch_fold_dwconv_ln_t<OUT, F16_, K_, false>(s, x_in, x_out, B, L, C, f, w_t, bias, dil, ln_g, ln_b, eps, static_cast<OUT*>(y), seqlen, row_off); } while (0)
+    static const int force = [] { const char* e = stn::dev_env("STN_FOLD_TCH"); return e ? atoi(e) : 0; }();  // A/B switch: 8, 32, 40 or 48
+    const FoldDwconvLnForm fm = fold_dwconv_ln_form_forced(act_dtype, B, L, C, k, dil, f.S, f.rowvec != nullptr, f.run_frames, force);  // the one place the run length is chosen
+#define STN_FOLD_DW(OUT, F16_, K_) do { if (fm.rv) launch_fold_dwconv_ln_t<OUT, F16_, K_, true>(s, fm, x_in, x_out, C, f, w_t, bias, dil, ln_g, ln_b, eps, static_cast<OUT*>(y), seqlen, row_off); \
+                                        else launch_fold_dwconv_ln_t<OUT, F16_, K_, false>(s, fm, x_in, x_out, C, f, w_t, bias, dil, ln_g, ln_b, eps, static_cast<OUT*>(y), seqlen, row_off); } while (0)
     if (act_dtype == F16) { if (k == 5) STN_FOLD_DW(f16_t, true, 5); else STN_FOLD_DW(f16_t, true, 7); }
     else { if (k == 5) STN_FOLD_DW(uint16_t, false, 5); else STN_FOLD_DW(uint16_t, false, 7); }
 #undef STN_FOLD_DW
