@@ -1161,7 +1161,7 @@ class Engine:
         return x_r, y
 
     def op_layout(self, which, p, a=None, b=None, c=None, ids=None, length=None, packed=False, out=None, out2=None, iout=None, dtype="f32"):
-        """One layout kernel of kernels_misc.hip on host operands (stn_op_layout; LAYOUT_* and the parameter lists: include/stn.h).
+        """One layout kernel of kernels_layout.hip on host operands (stn_op_layout; LAYOUT_* and the parameter lists: include/stn.h).
         out / out2 (float32) and iout (int32) are whole destination buffers; they come back as new arrays (out, out2, iout)."""
         def f32(v):
             return (None, None, 0) if v is None else (lambda arr: (arr, arr.ctypes.data, arr.size))(_c(v, np.float32))

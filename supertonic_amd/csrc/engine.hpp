@@ -340,7 +340,7 @@ class Engine {
     // launch_fold_ln on host operands (stn_op_fold_ln): part [S][M][C] rounded to dtype (BF16 / F16), x [M][C] updated in place, y [M][C]
     void op_fold_ln(int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma, const float* rowvec, const int* row_b,
                     int nseq, const float* g, const float* b, float* x, float* y);
-    // one layout kernel of kernels_misc.hip on host operands (stn_op_layout; `which` and the parameter lists are documented there)
+    // one layout kernel of kernels_layout.hip on host operands (stn_op_layout; `which` and the parameter lists are documented there)
     void op_layout(int which, int dtype, const int* p, const float* a, int64_t a_n, const float* b, int64_t b_n, const float* c, int64_t c_n,
                    const int64_t* ids, int64_t ids_n, const int* len, int packed, float* out, int64_t out_n, float* out2, int64_t out2_n, int* iout,
                    int64_t iout_n);

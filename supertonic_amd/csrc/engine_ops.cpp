@@ -622,7 +622,7 @@ std::string Engine::op_fold_dwconv_ln_ex(int dtype, int B, int L, int C, int k, 
     return form;
 }
 
-// One layout kernel of kernels_misc.hip on host operands (stn_op_layout).  Every destination is the caller's whole buffer: uploaded as given,
+// One layout kernel of kernels_layout.hip on host operands (stn_op_layout).  Every destination is the caller's whole buffer: uploaded as given,
 // downloaded whole.  Every extent a kernel addresses is checked against the buffers here, before anything is launched.
 void Engine::op_layout(int which, int dtype, const int* p, const float* a, int64_t a_n, const float* b, int64_t b_n, const float* c, int64_t c_n,
                        const int64_t* ids, int64_t ids_n, const int* len, int packed, float* out, int64_t out_n, float* out2, int64_t out2_n,

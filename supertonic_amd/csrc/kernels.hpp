@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include <stdexcept>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include <string>
@@ -62,6 +63,20 @@ inline void stn_check_hip(hipError_t e, const char* what) {
 enum DType : int { F32 = 0, BF16 = 1, F16 = 2 };  // F16: IEEE half operands / activations (v_mfma_f32_32x32x16_f16), fp32 accumulate
 __host__ __device__ inline bool is_half(int dt) { return dt == BF16 || dt == F16; }  // 2-byte storage
 typedef _Float16 f16_t;                                          // storage type of the F16 mode (bf16 is raw uint16_t)
+// The storage type of a run-time format as a template argument: calls fn with a null pointer of float (F32 — and, as these launchers always
+// have, any value that is neither of the others), uint16_t (BF16) or f16_t (F16).  In the callee: using T = std::remove_pointer_t<decltype(tag)>.
+template <typename Fn>
+inline void with_out_type(int dtype, Fn&& fn) {
+    if (dtype == F16) fn(static_cast<f16_t*>(nullptr));
+    else if (dtype == BF16) fn(static_cast<uint16_t*>(nullptr));
+    else fn(static_cast<float*>(nullptr));
+}
+// the 16-bit pair only, for launchers that take nothing else: f16_t for F16, else uint16_t
+template <typename Fn>
+inline void with_half_type(int dtype, Fn&& fn) {
+    if (dtype == F16) fn(static_cast<f16_t*>(nullptr));
+    else fn(static_cast<uint16_t*>(nullptr));
+}
 enum ActFn : int { ACT_NONE = 0, ACT_GELU = 1, ACT_SILU = 2, ACT_GELU_TANH = 3 };  // GELU: erf form; GELU_TANH: 0.5 x (1 + tanh(sqrt(2/pi)(x + 0.044715 x^3)))
 
 // GEMM epilogue description:  acc[m][n] = sum_k A[m][k] * W[n][k]
@@ -266,6 +281,9 @@ DwconvLnForm dwconv_ln_form(int out_dtype, int B, int L, int C, int k, bool pack
 bool dwconv_ln_supports_packed(int C, int k);
 void launch_row_map(hipStream_t s, const int* len, int B, int* row_off /*[B+1]*/, int* row_b /*[sum len] or null*/,
                     int rows_padded = 0 /* row_b has this many entries: those behind sum len are set to sequence 0 (shape buckets) */);
+// the LayerNorm kernels (dwconv_ln_kernel, fold_ln_kernel) hold a row as LN_NI float4 slots per lane: C <= 4 * 64 * LN_NI = 1024
+constexpr int LN_NI = 4;
+void check_ln_shape(int C);  // throws std::invalid_argument unless C % 4 == 0 and C <= 1024
 // plain LayerNorm over C: x fp32 -> y act
 void launch_layernorm(hipStream_t s, int out_dtype, const float* x, int64_t M, int C, const float* g, const float* b,
                       float eps, void* y);
@@ -358,7 +376,7 @@ void launch_vocoder_im2col(hipStream_t s, int out_dtype, const float* latent, in
                            const int* row_off = nullptr /* packed destination rows (needs seqlen) */);
 // packed rows [sum len][W] -> padded [B][T][W], zeros past each sequence's length
 void launch_unpack_rows(hipStream_t s, const float* src, const int* len, const int* row_off, int B, int T, int W, float* dst);
-// exact trimmed dense vocoder (see kernels_misc.hip): extents per utterance, and the unpack that fills the position-independent tail
+// exact trimmed dense vocoder (see kernels_layout.hip): extents per utterance, and the unpack that fills the position-independent tail
 void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out);
 void launch_unpack_rows_quiet(hipStream_t s, const float* src, const int* valid, const int* row_off, int B, int T, int W, int rf,
                               const float* quiet, const float* edge, float* dst);

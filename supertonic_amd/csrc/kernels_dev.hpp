@@ -1,6 +1,7 @@
 // kernels_dev.hpp — device-side helpers shared by the MFMA kernels (kernels_gemm.hip, kernels_ffn.hip): vector types,
-// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; and the sample encodings of every fetch
-// (kernels_misc.hip, kernels_resample.hip).  One definition, so that a fused kernel and the launches it replaces round identically.
+// buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; the typed loads / stores and the wavefront sum of the
+// HBM-bound kernels (kernels_dwconv_ln.hip, kernels_fold.hip, kernels_layout.hip); and the sample encodings of every fetch
+// (kernels_output.hip, kernels_resample.hip).  One definition, so that a fused kernel and the launches it replaces round identically.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
@@ -119,6 +120,35 @@ __device__ __forceinline__ void act8(float (&v)[8], const float (&bias)[8], int 
 __device__ __forceinline__ uint16_t f2bf(float f) {
     __hip_bfloat16 h = __float2bfloat16(f);
     return *reinterpret_cast<uint16_t*>(&h);
+}
+__device__ __forceinline__ float bf2f_(uint16_t v) { return __uint_as_float(((unsigned)v) << 16); }
+
+// four consecutive / one element of an activation row in its storage type (float, bf16 as raw uint16_t, f16_t), to and from fp32
+__device__ __forceinline__ void store4(float* p, float a, float b, float c, float d) {
+    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+}
+__device__ __forceinline__ void store4(uint16_t* p, float a, float b, float c, float d) {
+    uint2 u;
+    u.x = (unsigned)f2bf(a) | ((unsigned)f2bf(b) << 16);
+    u.y = (unsigned)f2bf(c) | ((unsigned)f2bf(d) << 16);
+    *reinterpret_cast<uint2*>(p) = u;
+}
+__device__ __forceinline__ void store4(f16_t* p, float a, float b, float c, float d) {
+    typedef _Float16 h4_ __attribute__((ext_vector_type(4)));
+    h4_ h = {(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d};  // v_cvt_f16_f32: round to nearest even
+    *reinterpret_cast<h4_*>(p) = h;
+}
+__device__ __forceinline__ void store1(float* p, float a) { *p = a; }
+__device__ __forceinline__ void store1(uint16_t* p, float a) { *p = f2bf(a); }
+__device__ __forceinline__ void store1(f16_t* p, float a) { *p = (f16_t)a; }
+__device__ __forceinline__ float load1(const float* p) { return *p; }
+__device__ __forceinline__ float load1(const uint16_t* p) { return bf2f_(*p); }
+__device__ __forceinline__ float load1(const f16_t* p) { return (float)*p; }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
 // 16-bit formats: bf16 (F16 = false) or IEEE half (F16 = true, the STN_DTYPE_F16 mode): same tiles, same LDS images, same
 // MFMA timing (v_mfma_f32_32x32x16_f16); only the conversion and the instruction differ, both resolved at compile time.

@@ -43,136 +43,53 @@ namespace stn {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// the product kernel, bf16 operands ...
-#define STN_V_NODMA 0
-#define STN_V_NOGELU 0
-#define STN_V_EARLYRD 0
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
-#define STN_V_F16 0
+// the product kernel, bf16 operands (every switch of the body at its default, 0) ...
 #include "kernels_ffn_body.inc"
-#undef STN_V_F16
 // ... and IEEE-half operands (the engine's f16 mode).  Same instruction stream; the GELU inside the blocks is the exp2 form in both
 // (|err| <= 5e-4 absolute: about one half-precision ulp at |y| ~ 1, where the two-launch f16 path uses the erf form).
 namespace f16k {
 #define STN_V_F16 1
 #include "kernels_ffn_body.inc"
-#undef STN_V_F16
 }
-#define STN_V_F16 0
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 // timing-only variants (wrong results; each drops one ingredient of a block to see what it costs — DESIGN.md section 5d).
-// Not part of the product build: `make EXTRA=-DSTN_FFN_VARIANTS` compiles them in and STN_FFN_VAR=<1..5> selects one.
+// Not part of the product build: `make EXTRA=-DSTN_FFN_VARIANTS` compiles them in and STN_FFN_VAR=<1..10> selects one.
 #ifdef STN_FFN_VARIANTS
 namespace v_nodma {
 #define STN_V_NODMA 1
-#define STN_V_NOGELU 0
-#define STN_V_EARLYRD 0
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 }
 namespace v_nogelu {
-#define STN_V_NODMA 0
 #define STN_V_NOGELU 1
-#define STN_V_EARLYRD 0
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 }
 namespace v_earlyrd {
-#define STN_V_NODMA 0
-#define STN_V_NOGELU 0
 #define STN_V_EARLYRD 1
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 }
 namespace v_nord {
 #define STN_V_NODMA 1
 #define STN_V_NOGELU 1
 #define STN_V_EARLYRD 2
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 }
 namespace v_nobar {
-#define STN_V_NODMA 0
-#define STN_V_NOGELU 0
-#define STN_V_EARLYRD 0
 #define STN_V_NOBAR 1
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
-#undef STN_V_NOBAR
-#undef STN_HANDOVER
 }
 namespace v_nohand {
-#define STN_V_NODMA 0
-#define STN_V_NOGELU 0
-#define STN_V_EARLYRD 0
 #define STN_V_NOBAR 2
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
-#undef STN_V_NOBAR
-#undef STN_HANDOVER
 }
 namespace v_mfmaonly {
 #define STN_V_NODMA 1
 #define STN_V_NOGELU 1
 #define STN_V_EARLYRD 2
 #define STN_V_NOBAR 2
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
-#undef STN_V_NOBAR
-#undef STN_HANDOVER
 }
 namespace v_stamp {
-#define STN_V_NODMA 0
-#define STN_V_NOGELU 0
-#define STN_V_EARLYRD 0
 #define STN_V_STAGESTAMP 1
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
-#undef STN_V_STAGESTAMP
 }
 namespace v_stamp_mfma {
 #define STN_V_NODMA 1
@@ -180,30 +97,13 @@ namespace v_stamp_mfma {
 #define STN_V_EARLYRD 2
 #define STN_V_NOBAR 2
 #define STN_V_STAGESTAMP 1
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
-#undef STN_V_NOBAR
-#undef STN_V_STAGESTAMP
-#undef STN_HANDOVER
 }
 namespace v_bare {
 #define STN_V_NODMA 1
 #define STN_V_NOGELU 1
-#define STN_V_EARLYRD 0
-#ifndef STN_V_ACCA
-#define STN_V_ACCA 0
-#endif
 #include "kernels_ffn_body.inc"
-#undef STN_V_NODMA
-#undef STN_V_NOGELU
-#undef STN_V_EARLYRD
 }
-
 #endif
 
 // W2 [N = C][K = I] row-major 16-bit -> phase-2 A fragments in the accumulator-operand k order:

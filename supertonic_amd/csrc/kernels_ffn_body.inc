@@ -1,8 +1,31 @@
-// body of kernels_ffn.hip (one variant per inclusion: STN_V_NODMA / STN_V_NOGELU / STN_V_EARLYRD select timing-only variants)
+// body of kernels_ffn.hip, one kernel variant per inclusion.  The includer defines only the switches that differ from the product, which is all of
+// them 0; every switch it was given is undefined again at the end, except STN_V_ACCA, which the command line may set for the whole unit:
+//   STN_V_F16         1: IEEE-half operands (the f16k instantiation of the product); 0: bf16
+//   STN_V_NODMA, STN_V_NOGELU, STN_V_EARLYRD (1, 2), STN_V_STAGESTAMP      timing-only variants (kernels_ffn.hip: STN_FFN_VARIANTS)
+//   STN_V_NOBAR       timing-only variants: 1 drops the ring hand-over's barrier, 2 its counted vmcnt wait too
+#ifndef STN_V_F16
+#define STN_V_F16 0
+#endif
+#ifndef STN_V_NODMA
+#define STN_V_NODMA 0
+#endif
+#ifndef STN_V_NOGELU
+#define STN_V_NOGELU 0
+#endif
+#ifndef STN_V_EARLYRD
+#define STN_V_EARLYRD 0
+#endif
+#ifndef STN_V_NOBAR
+#define STN_V_NOBAR 0
+#endif
+#ifndef STN_V_STAGESTAMP
+#define STN_V_STAGESTAMP 0
+#endif
+#ifndef STN_V_ACCA
+#define STN_V_ACCA 0
+#endif
 
-// (STN_V_NOBAR, timing-only variants: 1 drops the ring hand-over's barrier, 2 its counted vmcnt wait too; undefined = 0 in the product)
-#undef STN_HANDOVER
-#if !defined(STN_V_NOBAR) || STN_V_NOBAR == 0
+#if STN_V_NOBAR == 0
 #define STN_HANDOVER(PER) do { wait_vm<PER>(); __builtin_amdgcn_s_barrier(); } while (0)
 #elif STN_V_NOBAR == 1
 #define STN_HANDOVER(PER) do { wait_vm<PER>(); } while (0)
@@ -423,7 +446,7 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(FfnArgs p) {
     const int lr = lane & 31, lh = lane >> 5;
     // Hidden split (p.split = S > 1): workgroup (slab, sp) computes the contribution of hidden tiles [sp*T, (sp+1)*T) of its 128
     // rows and stores it as a 16-bit partial sum (p.part); the fixed-order sum over sp, b2, the layer scale, the residual and the
-    // time vector are applied by the next kernel that reads x (fold_dwconv_ln / fold_ln, kernels_misc.hip).  S is chosen per launch
+    // time vector are applied by the next kernel that reads x (fold_dwconv_ln / fold_ln, kernels_fold.hip).  S is chosen per launch
     // from its row count (ffn_split_choose: 12 ways up to 1536 rows, 8 up to 4096, 4 beyond), so results agree across that boundary to the rounding
     // of the 16-bit partial sums, and bit for bit within one S.  The S workgroups of a slab have the same
     // blockIdx.x % 8 (one XCD under round-robin placement: they read the same xn rows; speed only).
@@ -519,7 +542,7 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(FfnArgs p) {
     ffn_stage_p1<C, false, 0>(hA, hA, g1, f, xf, ffn_src<SB, 2, true>(so, wb, base_w), ffn_src<SB, 3, true>(so + SB, wb, base_w), rsw, ring_ad, ring_ad2, voff, cb);
     so += SB;
     g0 = ffn_gelu_half(hA, 0);  // first half of tile 0 (later tiles: inside the preceding phase-2 stage)
-#if defined(STN_V_STAGESTAMP) && STN_V_STAGESTAMP
+#if STN_V_STAGESTAMP
     // diagnostic build only: stamps around the four stages of the loop's second trip replace the three phase stamps
     unsigned long long sg[5] = {0, 0, 0, 0, 0};
 #define STN_SG(i) do { if (t == 2) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sg[i]) :: "memory"); __builtin_amdgcn_sched_barrier(0); } } while (0)
@@ -590,7 +613,7 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(FfnArgs p) {
             __builtin_amdgcn_s_waitcnt(0);
             unsigned long long* tp = ts + (size_t)blockIdx.x * 4;
             tp[0] = t_in; tp[1] = t_first; tp[2] = t_loop; tp[3] = __builtin_readcyclecounter();
-#if defined(STN_V_STAGESTAMP) && STN_V_STAGESTAMP
+#if STN_V_STAGESTAMP
             tp[0] = sg[0]; tp[1] = sg[1]; tp[2] = sg[2]; tp[3] = sg[4];  // "first" = phase 1, "loop" = phase 2, "epilogue" = the next pair
 #endif
         }
@@ -655,3 +678,10 @@ __global__ __launch_bounds__(256, 1) void ffn_fused_kernel(FfnArgs p) {
 #undef STN_ACCC
 #undef STN_NOUT
 #undef STN_FIN
+#undef STN_HANDOVER
+#undef STN_V_F16
+#undef STN_V_NODMA
+#undef STN_V_NOGELU
+#undef STN_V_EARLYRD
+#undef STN_V_NOBAR
+#undef STN_V_STAGESTAMP

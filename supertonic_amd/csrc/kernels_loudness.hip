@@ -12,7 +12,7 @@
 //      of the next one (chunks and segments need not align);
 //   4. gate: one workgroup per row sums each segment's shares in a fixed order, forms the 400 ms block energies, applies the absolute
 //      and relative gates and writes (L_b, peak_b, g_b);
-//   5. gain: y = x * g_b per sample, in the fetch's sample encoding (launch_store_rows, kernels_misc.hip).
+//   5. gain: y = x * g_b per sample, in the fetch's sample encoding (launch_store_rows, kernels_output.hip).
 // Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
 // row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
 #include "kernels.hpp"

@@ -1,0 +1,221 @@
+// kernels_output.hip — the end of every fetch (gfx950, wave64): the one store (store_rows_kernel: fp32 or an encoding, with or without a gain) and
+// the GPU join of long-form chunks (join_rows_kernel).  The per-sample encoding rules are the device functions of kernels_dev.hpp.
+#include "kernels.hpp"
+#include "kernels_dev.hpp"
+
+namespace stn {
+
+// The final store of a fetch: V samples per thread, times the row's gain when kGain, in encoding kEnc (kernels_dev.hpp).  Vector form:
+// 16-B loads, V = 4 (fp32: one 16-B store), 8 (PCM16: one 16-B store) or 16 (mu-law / A-law: one 16-B store; PCM24: three, 48 B);
+// scalar form (V = 1): one sample, enc_store1.  x and y may be the same fp32 rows (dst_stride == W: the gain applied in place), so
+// neither is __restrict__.
+template <int kEnc>
+constexpr int store_vec() { return kEnc == ENC_F32 ? 4 : kEnc == ENC_PCM16 ? 8 : 16; }
+
+// V consecutive samples v, encoded, to sample index e of y: one sample by enc_store1 (V == 1), else V = store_vec<kEnc>() samples in
+// one 16-B store (three for PCM24); y + e samples is then 16-byte aligned
+template <int V, int kEnc>
+__device__ __forceinline__ void enc_store_vec(unsigned char* y, int64_t e, const float (&v)[V]) {
+    if constexpr (V == 1) {
+        enc_store1<kEnc>(y, e, v[0]);
+    } else if constexpr (kEnc == ENC_F32) {
+        *reinterpret_cast<float4*>(y + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    } else if constexpr (kEnc == ENC_PCM16) {
+        unsigned o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ((unsigned)pcm16(v[2 * j]) & 0xFFFFu) | ((unsigned)pcm16(v[2 * j + 1]) << 16);
+        *reinterpret_cast<uint4*>(y + e * 2) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else if constexpr (kEnc == ENC_PCM24) {
+        // sample j's three bytes at 3j .. 3j+2 of 48: word w = bits [32w, 32w + 32) of the 384-bit little-endian run
+        unsigned o[12] = {};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned c = (unsigned)pcm24(v[j]) & 0xFFFFFFu;
+            const int b = 24 * j, w = b >> 5, sh = b & 31;
+            o[w] |= c << sh;
+            if (sh > 8) o[w + 1] |= c >> (32 - sh);
+        }
+        uint4* d = reinterpret_cast<uint4*>(y + e * 3);
+        d[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        d[2] = make_uint4(o[8], o[9], o[10], o[11]);
+    } else {
+        unsigned o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned w = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int s16 = pcm16(v[4 * j + k]);
+                w |= (kEnc == ENC_MULAW ? mulaw8(s16) : alaw8(s16)) << (8 * k);
+            }
+            o[j] = w;
+        }
+        *reinterpret_cast<uint4*>(y + e) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+template <int V, bool kGain, int kEnc>
+__global__ void store_rows_kernel(const float* x, int64_t Wv, int64_t nv, const float* __restrict__ g, unsigned char* y, int64_t dst_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [rows][W/V]
+    if (i >= nv) return;
+    const int64_t row = i / Wv;
+    float v[V];
+    if constexpr (V == 1) {
+        v[0] = x[i];
+    } else {
+#pragma unroll
+        for (int j = 0; j < V / 4; ++j) {
+            const float4 a = reinterpret_cast<const float4*>(x)[i * (V / 4) + j];
+            v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+        }
+    }
+    if constexpr (kGain) {
+        const float s = g[row];
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] *= s;
+    }
+    enc_store_vec<V, kEnc>(y, row * dst_stride + (i - row * Wv) * V, v);  // (first destination sample)
+}
+template <int kEnc>
+void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, unsigned char* y, int64_t dst_stride) {
+    const int64_t n = rows * W;
+    if (n <= 0) return;
+    if (dst_stride < W) throw std::invalid_argument("store_rows: dst_stride smaller than the row length");
+    constexpr int V = store_vec<kEnc>();
+    const bool vec = W % V == 0 && dst_stride % V == 0 && !(reinterpret_cast<uintptr_t>(x) & 15) && !(reinterpret_cast<uintptr_t>(y) & 15);
+    const int64_t nv = vec ? n / V : n;
+    const dim3 grid((unsigned)((nv + 255) / 256));
+    if (vec && g) STN_KLAUNCH((store_rows_kernel<V, true, kEnc>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (vec) STN_KLAUNCH((store_rows_kernel<V, false, kEnc>), grid, dim3(256), 0, s, x, W / V, nv, g, y, dst_stride);
+    else if (g) STN_KLAUNCH((store_rows_kernel<1, true, kEnc>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+    else STN_KLAUNCH((store_rows_kernel<1, false, kEnc>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
+}
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride) {
+    unsigned char* d = static_cast<unsigned char*>(y);
+    switch (enc) {
+        case ENC_F32: launch_store_rows_t<ENC_F32>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_PCM16: launch_store_rows_t<ENC_PCM16>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_PCM24: launch_store_rows_t<ENC_PCM24>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_MULAW: launch_store_rows_t<ENC_MULAW>(s, x, rows, W, g, d, dst_stride); break;
+        case ENC_ALAW: launch_store_rows_t<ENC_ALAW>(s, x, rows, W, g, d, dst_stride); break;
+        default: throw std::invalid_argument("store_rows: unknown encoding " + std::to_string(enc));
+    }
+}
+
+// The join of a fetch: programme p's output row is its members' segments with gaps between them,
+// seg[m].len samples of source row seg[m].row landing at seg[m].dst, everything else of [0, Wj) the encoding's zero codeword (the
+// encoding of +0.0f).  One workgroup per (tile of JOIN_WG * V * T output samples, programme): it stages the programme's members in LDS
+// once (one load per lane; members past JOIN_WG, which a chunked text never has, are read from the table), and a thread, which owns T vectors of V
+// consecutive output samples JOIN_WG * V apart, finds for each the first member that ends behind its first sample by a binary search over the members' ascending
+// ends in LDS.  Inside one segment the V samples are 16-B loads that ask for dword alignment only (a segment's offset against its row
+// is arbitrary: the hardware takes a dwordx4 at any dword address) and the store of store_rows_kernel; a vector that meets a segment
+// edge, a gap or the row's end selects per sample, and the last, partial vector of a row is stored sample by sample.  No sample
+// outside a member's [0, len) is read, nothing outside [0, Wj) of a row is written.  kGain: times g[source row], the product
+// store_rows_kernel forms.
+constexpr int JOIN_WG = 256;
+typedef float join_f4 __attribute__((ext_vector_type(4), aligned(4)));  // four floats at a dword-aligned address
+
+template <int V, int T, bool kGain, int kEnc>
+__global__ void __launch_bounds__(JOIN_WG) join_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSeg* __restrict__ seg,
+                                                            const JoinProg* __restrict__ prog, const float* __restrict__ g, int64_t Wj,
+                                                            unsigned char* __restrict__ y, int64_t dst_stride) {
+    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG];
+    const int p = blockIdx.y, tid = threadIdx.x;
+    const JoinProg pg = prog[p];
+    const JoinSeg* __restrict__ ps = seg + pg.first;
+    const int64_t t0 = (int64_t)blockIdx.x * (JOIN_WG * V * T);
+    const int k = t0 < pg.len ? pg.count : 0;  // (a tile behind the programme's end is padding: no member to find)
+    if (tid < k) { s_dst[tid] = ps[tid].dst; s_len[tid] = ps[tid].len; s_row[tid] = ps[tid].row; }
+    __syncthreads();
+    auto dst_of = [&](int r) { return r < JOIN_WG ? s_dst[r] : ps[r].dst; };
+    auto len_of = [&](int r) { return r < JOIN_WG ? s_len[r] : ps[r].len; };
+    auto row_of = [&](int r) { return r < JOIN_WG ? s_row[r] : ps[r].row; };
+    float v[T][V];
+    // all T vectors are loaded before the first is stored: the loads of a thread are in flight together
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;  // this vector's first output sample
+        if (o >= Wj) break;
+        int r = 0;
+        for (int hi = k; r < hi;) {  // the first member that ends behind o (the ends ascend)
+            const int mid = (r + hi) >> 1;
+            if (dst_of(mid) + len_of(mid) <= o) r = mid + 1; else hi = mid;
+        }
+        const int64_t d0 = r < k ? dst_of(r) : 0, l0 = r < k ? len_of(r) : 0;
+        if (r < k && o >= d0 && o + V <= d0 + l0) {  // the whole vector inside one segment
+            const int64_t row = row_of(r);
+            const float* __restrict__ src = x + row * src_stride + (o - d0);
+            if constexpr (V >= 4) {
+#pragma unroll
+                for (int j = 0; j < V / 4; ++j) {
+                    const join_f4 a = reinterpret_cast<const join_f4*>(src)[j];
+                    v[i][4 * j] = a.x; v[i][4 * j + 1] = a.y; v[i][4 * j + 2] = a.z; v[i][4 * j + 3] = a.w;
+                }
+            } else {
+                v[i][0] = src[0];
+            }
+            if constexpr (kGain) {
+                const float s = g[row];
+#pragma unroll
+                for (int j = 0; j < V; ++j) v[i][j] *= s;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int64_t oj = o + j;
+                while (r < k && dst_of(r) + len_of(r) <= oj) ++r;
+                float t = 0.f;
+                if (r < k && oj >= dst_of(r)) {
+                    const int64_t row = row_of(r);
+                    t = x[row * src_stride + (oj - dst_of(r))];
+                    if constexpr (kGain) t *= g[row];
+                }
+                v[i][j] = t;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;
+        if (o >= Wj) break;
+        const int64_t e = (int64_t)p * dst_stride + o;
+        if (V == 1 || o + V <= Wj) {
+            enc_store_vec<V, kEnc>(y, e, v[i]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (o + j < Wj) enc_store1<kEnc>(y, e + j, v[i][j]);
+        }
+    }
+}
+template <int kEnc>
+void launch_join_rows_t(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
+                        unsigned char* y, int64_t dst_stride) {
+    constexpr int V = store_vec<kEnc>();
+    constexpr int T = V == 16 ? 2 : 4;  // vectors per thread: a workgroup's table lookup is paid once for 32 (fp32: 16) samples a thread
+    const bool vec = (G == 1 || dst_stride % V == 0) && !(reinterpret_cast<uintptr_t>(y) & 15);  // (every row's start 16-byte aligned)
+    const int64_t tile = (int64_t)JOIN_WG * T * (vec ? V : 1);
+    const dim3 grid((unsigned)((Wj + tile - 1) / tile), (unsigned)G);
+    if (vec && g) STN_KLAUNCH((join_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else if (vec) STN_KLAUNCH((join_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else if (g) STN_KLAUNCH((join_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+    else STN_KLAUNCH((join_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+}
+void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
+                      int enc, void* y, int64_t dst_stride) {
+    if (G <= 0 || Wj <= 0) return;
+    if (G > 65535) throw std::invalid_argument("join_rows: more than 65535 programmes");
+    if (dst_stride < Wj) throw std::invalid_argument("join_rows: dst_stride smaller than the joined row length");
+    unsigned char* d = static_cast<unsigned char*>(y);
+    switch (enc) {
+        case ENC_F32: launch_join_rows_t<ENC_F32>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_PCM16: launch_join_rows_t<ENC_PCM16>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_PCM24: launch_join_rows_t<ENC_PCM24>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_MULAW: launch_join_rows_t<ENC_MULAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        case ENC_ALAW: launch_join_rows_t<ENC_ALAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
+        default: throw std::invalid_argument("join_rows: unknown encoding " + std::to_string(enc));
+    }
+}
+
+}  // namespace stn

@@ -1,4 +1,4 @@
-"""dwconv_ln_form (csrc/kernels_misc.hip), the one decision launch_dwconv_ln executes, on both sides of every threshold — through
+"""dwconv_ln_form (csrc/kernels_dwconv_ln.hip), the one decision launch_dwconv_ln executes, on both sides of every threshold — through
 stn_dbg_dwconv_ln_form, which needs no device.  tests/test_gpu_dwconv_ln_forms.py asserts the same strings before it compares values, so a
 threshold that moves fails here first and there second.
 

@@ -1,4 +1,4 @@
-"""fold_dwconv_ln_form (csrc/kernels_misc.hip), the one decision launch_fold_dwconv_ln executes — kernel instantiation, run length, workgroups per
+"""fold_dwconv_ln_form (csrc/kernels_fold.hip), the one decision launch_fold_dwconv_ln executes — kernel instantiation, run length, workgroups per
 sequence — and fold_dwconv_ln_supported, the gate behind it, on both sides of every limit, through stn_dbg_fold_dwconv_ln_form, which needs no
 device.  tests/test_gpu_fold_dwconv_ln_forms.py asserts the same strings before it compares values, and takes its reference (fold_ref,
 conv_ln64) from here.

@@ -1,5 +1,5 @@
-"""Every form of the depthwise-conv + LayerNorm family (csrc/kernels_misc.hip: dwconv_ln_v3_kernel<OutT, K, R> for (K, R) in {(5,2), (5,4),
-(5,8), (7,4)}, dwconv_ln_v3_occ4_kernel, dwconv_ln_v2_kernel<OutT, K, 2>, dwconv_ln_kernel<OutT, true / false>, fold_ln_kernel<OutT, F16, RV,
+"""Every form of the depthwise-conv + LayerNorm family (csrc/kernels_dwconv_ln.hip: dwconv_ln_v3_kernel<OutT, K, R> for (K, R) in {(5,2), (5,4),
+(5,8), (7,4)}, dwconv_ln_v3_occ4_kernel, dwconv_ln_v2_kernel<OutT, K, 2>, dwconv_ln_kernel<OutT, true / false>; csrc/kernels_fold.hip: fold_ln_kernel<OutT, F16, RV,
 S>) against float64, through stn_op_dwconv_ln_ex and stn_op_fold_ln.  Each case first asserts the form it expects (binding.dwconv_ln_form
 pins the same strings without a GPU in tests/test_dwconv_ln_form_cpu.py), then the values.  The reference is plain numpy in float64:
 zero-padded dilated depthwise convolution inside each sequence (taps at t >= seqlen[b] read zero), bias, LayerNorm with eps = 1e-6 over

@@ -1,4 +1,4 @@
-"""Fetch encodings on an MI355X (include/stn.h STN_ENC_*; store_rows_kernel in kernels_misc.hip, the resampler's epilogue in
+"""Fetch encodings on an MI355X (include/stn.h STN_ENC_*; store_rows_kernel in kernels_output.hip, the resampler's epilogue in
 kernels_resample.hip, the device rules in kernels_dev.hpp): the op on every int16 cell centre in the vector and the scalar form,
 every fetch path byte for byte against the numpy rules applied to the fp32 / PCM16 fetch (three output rates and the native one,
 loudness off and on, bf16 and f16), position independence at 8 kHz mu-law, captured graphs kept across encoding switches, one launch

@@ -278,7 +278,7 @@ def test_fold_dwconv_ln_vs_numpy(eng, k, dil, C, S):
 
 
 def test_fold_dwconv_ln_run_length_does_not_change_a_bit(eng):
-    """Few sequences are cut into runs of 8 frames, many into runs of 32 (kernels_misc.hip, FOLD_TCH_FEW): a frame's arithmetic does not depend
+    """Few sequences are cut into runs of 8 frames, many into runs of 32 (kernels_fold.hip, FOLD_TCH_FEW): a frame's arithmetic does not depend
     on the run it falls in, so three sequences alone and the same three among forty give the same bits."""
     rng = np.random.default_rng(77)
     C, S, k = 384, 12, 5

@@ -1,4 +1,4 @@
-"""Every form of fold_dwconv_ln_kernel<OutT / F16, K, RV, NSLOT, S> (csrc/kernels_misc.hip: 2 formats x K {5, 7} x rowvec on / off x NSLOT {3, 4}
+"""Every form of fold_dwconv_ln_kernel<OutT / F16, K, RV, NSLOT, S> (csrc/kernels_fold.hip: 2 formats x K {5, 7} x rowvec on / off x NSLOT {3, 4}
 x S {4, 8, 12, 24} = 64 instantiations) and every run length (8, 32, 40, 48 frames per workgroup) against float64, through
 stn_op_fold_dwconv_ln_ex.  Each case first asserts the form it expects (binding.fold_dwconv_ln_form pins the same strings without a GPU in
 tests/test_fold_dwconv_ln_form_cpu.py), then the values.  No case sets an environment switch: the run lengths are reached the way the launcher

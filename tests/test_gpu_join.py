@@ -1,4 +1,4 @@
-"""The join of a fetch on an MI355X (include/stn.h "join"; join_rows_kernel, kernels_misc.hip): the op against
+"""The join of a fetch on an MI355X (include/stn.h "join"; join_rows_kernel, kernels_output.hip): the op against
 tests/join_ref.py applied to stn_op_encode's rows, every byte; every fetch path of a length-aware batch against the host join of
 batch_fetch_encoded's rows; the per-programme gain against a float64 BS.1770-4 (tests/loudness_ref.py); what the gain scope changes;
 the hosts; no side effects on other fetches or on captured graphs; and the event-timed cost against the store kernel on the same batch."""

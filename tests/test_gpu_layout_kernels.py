@@ -1,4 +1,4 @@
-"""The layout kernels between the GEMMs (csrc/kernels_misc.hip: row_map_kernel, ncl_to_rows_kernel, euler_ncl_kernel<ZT>, unpack_rows_kernel,
+"""The layout kernels between the GEMMs (csrc/kernels_layout.hip: row_map_kernel, ncl_to_rows_kernel, euler_ncl_kernel<ZT>, unpack_rows_kernel,
 embed_kernel, masked_mean_kernel, vocoder_im2col_kernel<OutT, FIXED>, vocoder_in_kernel), one at a time through stn_op_layout, against numpy
 statements of what each does.  Most only move or round data and are compared bit for bit; every destination is a buffer full of NaN (or -7)
 sentinels that comes back whole, so a row or column a kernel must not touch is seen; sources carry NaN where a kernel must not read.
