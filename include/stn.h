@@ -357,6 +357,54 @@ int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, cons
  * STN_ERR_INVALID outside [8000, 192000] Hz */
 int stn_kweighting_filter(int hz, double* shelf_b3, double* shelf_a3, double* hp_b3, double* hp_a3);
 
+/* ---- silence trimming --------------------------------------------------------------------------------
+ * With trimming on, every fetch path delivers each row without the silence in front of and behind its speech, found by level on the
+ * GPU at fetch time.  It composes with the rate, the loudness, the encoding and the join; the latent geometry, the reported durations,
+ * stn_batch_wav_device_ptr, the captured pipeline and the graph key are untouched, and toggling it drops or re-captures no graph.
+ * Signal measured: the row at the output rate hz (after resampling when a rate is set, before any gain), row b's first
+ * n_b = min(W_out, (int64_t)(duration_b * (float)hz)) samples (the loudness span).
+ * Edges: frames of F = (hz + 50) / 100 samples (10 ms) from sample 0 without overlap, K = ceil(n / F), frame k over
+ * [kF, min((k + 1)F, n)) with level m_k = mean of x^2 over its own samples; m_max = max m_k.  n = 0 or m_max <= 1e-7 (-70 dBFS mean
+ * square): no speech, start = 0 and end = n.  Otherwise frame k is active when m_k >= m_max * 10^(-top_db / 10); with f0 the first and
+ * f1 the last active frame and keep = (int64_t)(keep_ms * hz / 1000 + 0.5) (in double), start = max(0, f0 F - keep) and
+ * end = min(n, (f1 + 1)F + keep).  Silence inside the row is never touched.  Every sum runs in an order fixed by sample positions within
+ * the row (no float atomics): start and end depend on the row's first n samples, the rate and the parameters only, not on W, B or the
+ * row's neighbours.
+ * Fade: Fd = (int64_t)(fade_ms * hz / 1000 + 0.5), w[j] = float32(0.5 - 0.5 cos(pi (j + 0.5) / Fd)) (stn_silence_fade_window).  An edge
+ * that was cut (start > 0, respectively end < n) is faded over the segment's first, respectively last, min(Fd, len) samples: sample q
+ * of the segment times w[q], respectively w[len - 1 - q]; an edge that was not cut keeps its samples bit for bit.  A delivered sample is
+ * ((x * g) * w_in) * w_out, three fp32 multiplies in that order, each only where it applies, then the encoding's rule.
+ * Per-row fetches (stn_batch_fetch, _pcm16, _encoded, both pipelined slots, stn_batch_copy_*_device) still deliver [B][W_out] rows
+ * (stn_batch_dims is unchanged): row b holds its segment [start_b, end_b) from column 0 and the encoding's zero codeword behind
+ * len_b = end_b - start_b; the reported durations stay the model's; no host read is needed, so the pipelined _begin stays asynchronous.
+ * Joined fetches (every stn_batch_*joined* entry, stn_batch_join_dims, stn_batch_join_loudness): under either mode a member's segment
+ * is [start_b, end_b) and its duration in prog_dur's fp32 member-order sum is (float)len_b / (float)hz; the plan reads the edges with
+ * one device-to-host copy of 2 B integers per finished batch and setting.  stn_join_plan and the refused mode values are unchanged.
+ * Loudness: the per-row gain g_b stays the one measured over the untrimmed span n_b, so with fade_ms = 0 a trimmed row is byte for
+ * byte a slice of the untrimmed fetch; STN_JOIN_GAIN_PROG measures the joined, faded signal.  The group (stn_group_*) does not trim.
+ * DESIGN.md section 14 has the decomposition and the cost. */
+/* on = 0: off (the default: every fetch is byte for byte the one without it, with no extra launch or allocation).  top_db in [1, 120],
+ * keep_ms in [0, 1000], fade_ms in [0, 50]; out of range: STN_ERR_INVALID with a message, and the previous setting stays in force. */
+int stn_set_silence_trim(stn_handle* h, int on, float top_db, float keep_ms, float fade_ms);
+int stn_get_silence_trim(const stn_handle* h, int* on, float* top_db, float* keep_ms, float* fade_ms);
+/* the finished batch's edges at the current output rate under the current parameters, whether trimming is on or not; each pointer [B]
+ * integers or NULL */
+int stn_batch_silence_edges(stn_handle* h, int64_t* start, int64_t* end);
+/* op-level: rows x W fp32 (host) at hz in [8000, 192000]; row r's first n[r] samples (n_or_null = NULL: all W) -> start, end [rows]
+ * (either may be NULL).  1 <= rows <= 65535. */
+int stn_op_silence_edges(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float top_db, float keep_ms,
+                         int64_t* start, int64_t* end);
+/* the same, and y: [rows][W] samples of enc, row r's segment from column 0 (times gain_or_null[r], cut edges faded), zero codewords
+ * behind it */
+int stn_op_silence_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float top_db, float keep_ms,
+                        float fade_ms, const float* gain_or_null, int enc, void* y, int64_t* start, int64_t* end);
+/* the fade window at hz (host only, no device needed): *n = Fd, and w[0 .. min(Fd, cap)) when w is not NULL; STN_ERR_INVALID when
+ * fade_ms is outside [0, 50] or hz < 1 */
+int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_t* n);
+/* diagnostic: overwrite the finished batch's model-rate waveform with wav [B][L * chunk] (host; what stn_batch_dims reports at the model's
+ * rate) and forget every fetch-time measurement cached for it.  For tests that need rows with known silences. */
+int stn_dbg_batch_set_wav(stn_handle* h, const float* wav);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

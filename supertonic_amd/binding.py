@@ -305,6 +305,13 @@ def load():
     L.stn_op_loudness.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp]
     L.stn_kweighting_filter.argtypes = [ci, _f64p, _f64p, _f64p, _f64p]
     L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
+    L.stn_set_silence_trim.argtypes = [vp, ci, cf, cf, cf]
+    L.stn_get_silence_trim.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf), ctypes.POINTER(cf), ctypes.POINTER(cf)]
+    L.stn_batch_silence_edges.argtypes = [vp, vp, vp]
+    L.stn_op_silence_edges.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, vp, vp]
+    L.stn_op_silence_trim.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, vp, ci, vp, vp, vp]
+    L.stn_silence_fade_window.argtypes = [ci, cf, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
     L.stn_batch_copy_encoded_device.argtypes = [vp, ci, vp, ctypes.c_int64]
@@ -436,6 +443,45 @@ def kweighting_filter(hz):
     if rc < 0:
         raise StnError(rc, f"stn_kweighting_filter: {hz} Hz is outside [8000, 192000] Hz")
     return tuple(out)
+
+
+TRIM_KEEP_MS, TRIM_FADE_MS = 20.0, 5.0
+
+
+def silence_trim_args(trim_silence):
+    """A trim_silence argument -> (on, top_db, keep_ms, fade_ms) for stn_set_silence_trim: None = off, a number = top_db with 20 ms kept
+    and a 5 ms fade, or (top_db, keep_ms, fade_ms).  ValueError, with the ABI's ranges, for anything else."""
+    if trim_silence is None:
+        return 0, 40.0, TRIM_KEEP_MS, TRIM_FADE_MS
+    if isinstance(trim_silence, bool):
+        raise ValueError("trim_silence: None, top_db or (top_db, keep_ms, fade_ms), not a bool")
+    try:
+        t = tuple(float(v) for v in trim_silence) if isinstance(trim_silence, (tuple, list)) else (float(trim_silence), TRIM_KEEP_MS, TRIM_FADE_MS)
+    except (TypeError, ValueError):
+        raise ValueError(f"trim_silence: None, top_db or (top_db, keep_ms, fade_ms), not {trim_silence!r}") from None
+    if len(t) != 3:
+        raise ValueError(f"trim_silence: None, top_db or (top_db, keep_ms, fade_ms), not {trim_silence!r}")
+    db, keep, fade = t
+    if not 1.0 <= db <= 120.0:
+        raise ValueError(f"trim_silence top_db {db} dB: must be in [1, 120]")
+    if not 0.0 <= keep <= 1000.0:
+        raise ValueError(f"trim_silence keep {keep} ms: must be in [0, 1000]")
+    if not 0.0 <= fade <= 50.0:
+        raise ValueError(f"trim_silence fade {fade} ms: must be in [0, 50]")
+    return 1, db, keep, fade
+
+
+def silence_fade_window(hz, fade_ms):
+    """The fade of a cut edge at hz (host only): float32 [Fd], Fd = int(fade_ms * hz / 1000 + 0.5), w[j] = 0.5 - 0.5 cos(pi (j + 0.5) / Fd).
+    StnError when fade_ms is outside [0, 50]."""
+    L = load()
+    n = ctypes.c_int64()
+    if L.stn_silence_fade_window(int(hz), float(fade_ms), None, 0, ctypes.byref(n)) < 0:
+        raise StnError(-1, f"stn_silence_fade_window: fade {fade_ms} ms at {hz} Hz refused (fade_ms in [0, 50], hz >= 1)")
+    w = np.empty(n.value, np.float32)
+    if L.stn_silence_fade_window(int(hz), float(fade_ms), w.ctypes.data, w.size, ctypes.byref(n)) < 0:
+        raise StnError(-1, "stn_silence_fade_window failed")
+    return w
 
 
 def _loudness_args(target_lufs):
@@ -743,6 +789,62 @@ class Engine:
         self._ck(self._lib.stn_op_loudness(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, lufs.ctypes.data,
                                            peak.ctypes.data))
         return lufs, peak
+
+    def set_silence_trim(self, trim_silence=None):
+        """Trim leading and trailing silence of every fetch by level on the GPU: None = off (the default), top_db (frames more than
+        top_db below the row's loudest 10 ms frame are silence; 20 ms kept, 5 ms fade) or (top_db, keep_ms, fade_ms)."""
+        on, db, keep, fade = silence_trim_args(trim_silence)
+        self._ck(self._lib.stn_set_silence_trim(self._h, on, db, keep, fade))
+
+    @property
+    def silence_trim(self):
+        """(top_db, keep_ms, fade_ms), or None when trimming is off."""
+        on, db, keep, fade = ctypes.c_int(), ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        self._ck(self._lib.stn_get_silence_trim(self._h, ctypes.byref(on), ctypes.byref(db), ctypes.byref(keep), ctypes.byref(fade)))
+        return (db.value, keep.value, fade.value) if on.value else None
+
+    def batch_silence_edges(self):
+        """The finished batch's edges at the output rate under the current parameters, trimming on or off -> (start [B], end [B]) int64."""
+        B = self.batch_dims()[0]
+        start, end = np.empty(B, np.int64), np.empty(B, np.int64)
+        self._ck(self._lib.stn_batch_silence_edges(self._h, start.ctypes.data, end.ctypes.data))
+        return start, end
+
+    def op_silence_edges(self, x, hz, n=None, top_db=40.0, keep_ms=TRIM_KEEP_MS):
+        """rows x W fp32 at hz on the GPU -> (start [rows], end [rows]) over row r's first n[r] samples (None: all W)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(n, np.int64)
+        start, end = np.empty(rows, np.int64), np.empty(rows, np.int64)
+        self._ck(self._lib.stn_op_silence_edges(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(top_db), float(keep_ms),
+                                                start.ctypes.data, end.ctypes.data))
+        return start, end
+
+    def op_silence_trim(self, x, hz, n=None, top_db=40.0, keep_ms=TRIM_KEEP_MS, fade_ms=TRIM_FADE_MS, gain=None, encoding=None):
+        """Detection plus the trimmed store on the GPU -> (y [rows, W] in the encoding (encoded_empty's dtypes), start, end): row r's
+        segment from column 0, times gain[r], cut edges faded, zero codewords behind it."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        nn = None if n is None else np.ascontiguousarray(n, np.int64)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        y = encoded_empty(e, rows, W)
+        start, end = np.empty(rows, np.int64), np.empty(rows, np.int64)
+        self._ck(self._lib.stn_op_silence_trim(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(top_db), float(keep_ms),
+                                               float(fade_ms), None if g is None else g.ctypes.data, e, y.ctypes.data, start.ctypes.data,
+                                               end.ctypes.data))
+        return y, start, end
+
+    def dbg_batch_set_wav(self, wav):
+        """Diagnostic: overwrite the finished batch's model-rate waveform ([B, L * chunk] float32) for tests that need known silences."""
+        wav = np.ascontiguousarray(wav, np.float32)
+        B, L, _ = self.batch_dims()
+        a = StnArch()
+        self._ck(self._lib.stn_get_arch(self._h, ctypes.byref(a)))
+        W = L * a.base_chunk_size * a.chunk_compress_factor
+        if wav.shape != (B, W):
+            raise ValueError(f"dbg_batch_set_wav: wav must be [{B}, {W}], got {wav.shape}")
+        self._ck(self._lib.stn_dbg_batch_set_wav(self._h, wav))
 
     def op_encode(self, x, enc):
         """rows x W fp32 -> rows x W samples of an encoding on the GPU (the fetch's store kernel without a gain; encoded_empty's dtypes)."""

@@ -337,6 +337,41 @@ int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, cons
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness: bad argument (1 <= rows <= 65535, W >= 1, x)");
                  h->eng->op_loudness(hz, rows, W, x, n, lufs, peak); })
 }
+int stn_set_silence_trim(stn_handle* h, int on, float top_db, float keep_ms, float fade_ms) {
+    STN_TRY(h, { h->eng->set_silence_trim(on != 0, top_db, keep_ms, fade_ms); })
+}
+int stn_get_silence_trim(const stn_handle* h, int* on, float* top_db, float* keep_ms, float* fade_ms) {
+    if (!h) return STN_ERR_INVALID;
+    h->eng->get_silence_trim(on, top_db, keep_ms, fade_ms);
+    return STN_OK;
+}
+int stn_batch_silence_edges(stn_handle* h, int64_t* start, int64_t* end) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_silence_edges(start, end); })
+}
+int stn_op_silence_edges(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, int64_t* start,
+                         int64_t* end) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_silence_edges: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 h->eng->op_silence_edges(hz, rows, W, x, n, top_db, keep_ms, start, end); })
+}
+int stn_op_silence_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
+                        const float* gain, int enc, void* y, int64_t* start, int64_t* end) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_silence_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_silence_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, gain, enc, y, start, end); })
+}
+int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_t* n) {
+    if (hz < 1 || !stn::silence_check(1.0f, 0.0f, fade_ms).empty()) return STN_ERR_INVALID;
+    try {
+        const std::vector<float> v = stn::silence_fade_window(hz, fade_ms);
+        if (n) *n = (int64_t)v.size();
+        if (w) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap < 0 ? 0 : cap, (int64_t)v.size()), w);
+        return STN_OK;
+    } catch (const std::exception&) {
+        return STN_ERR_INVALID;
+    }
+}
+int stn_dbg_batch_set_wav(stn_handle* h, const float* wav) {
+    STN_TRY(h, { need(wav != nullptr, "wav is null"); need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->dbg_batch_set_wav(wav); })
+}
 int stn_kweighting_filter(int hz, double* shelf_b, double* shelf_a, double* hp_b, double* hp_a) {
     stn::KWeighting k;
     if (!stn::kweighting_design(hz, k).empty()) return STN_ERR_INVALID;

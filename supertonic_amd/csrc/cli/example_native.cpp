@@ -6,7 +6,9 @@
 // --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1), --encoding {pcm16,pcm24,f32,mulaw,alaw} (sample format
 // of the WAV files, encoded on the GPU; default pcm16, writeWavFile's files), --loudness-scope {chunk,text} (a long text with --loudness:
 // every chunk normalized on its own, the default, or the joined text as one programme with one gain; text needs one GPU),
-// --trim-chunks (a long text's chunks cut at their durations before they are joined).
+// --trim-chunks (a long text's chunks cut at their durations before they are joined), --trim-silence DB (leading and trailing silence of
+// every utterance trimmed by level on the GPU: frames more than DB below the loudest 10 ms frame; the files then hold the trimmed
+// segments; one GPU only), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -76,6 +78,9 @@ int main(int argc, char* argv[]) {
             opts.loudness_scope_text = v == "text";
         }
         else if (a == "--trim-chunks") opts.trim_chunks = true;  // long texts: every chunk cut at its duration before the join
+        else if (a == "--trim-silence" && more) opts.trim_silence_db = std::strtof(argv[++i], nullptr);  // dB below the loudest frame that counts as silence; absent: off
+        else if (a == "--trim-keep" && more) opts.trim_keep_ms = std::strtof(argv[++i], nullptr);  // ms kept around the speech (default 20)
+        else if (a == "--trim-fade" && more) opts.trim_fade_ms = std::strtof(argv[++i], nullptr);  // ms of fade over a cut edge (default 5)
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (voice_style.size() != text.size()) {
@@ -111,6 +116,7 @@ int main(int argc, char* argv[]) {
             for (int b = 0; b < bsz; ++b) {
                 const std::string fname = sanitizeFilename(text[b], 20) + "_" + std::to_string(n + 1) + ".wav";
                 size_t wav_len = (size_t)(int)((float)sr * result.duration[b]);
+                if (!result.length.empty()) wav_len = (size_t)result.length[(size_t)b];  // trimmed: the segment the GPU delivered
                 if (wav_len > per) wav_len = per;
                 if (eb) {
                     writeWavFileEncoded(save_dir + "/" + fname, result.encoding, result.encoded.data() + b * per * eb, wav_len, sr);

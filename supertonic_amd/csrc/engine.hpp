@@ -63,6 +63,12 @@ class Arena {
     size_t cur_ = 0, off_ = 0;
 };
 
+// Silence trimming's host arithmetic (engine_edges.cpp): why (top_db, keep_ms, fade_ms) is refused, or ""; a length in ms as samples at
+// hz, (int64)(ms * hz / 1000 + 0.5) in double; the raised-cosine fade of that many samples, float32(0.5 - 0.5 cos(pi (j + 0.5) / Fd))
+std::string silence_check(float top_db, float keep_ms, float fade_ms);
+int64_t silence_samples(int hz, float ms);
+std::vector<float> silence_fade_window(int hz, float fade_ms);
+
 struct KernelStat { double ms = 0; long launches = 0; double flops = 0; double bytes = 0; };
 
 class Engine {
@@ -294,6 +300,23 @@ class Engine {
     void batch_loudness(float* lufs, float* peak, float* gain);
     // rows x W fp32 (host) at hz, row r's first n[r] samples (all W when n is null) -> L, peak [rows] (host)
     void op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak);
+
+    // ---- silence trimming (engine_edges.cpp; include/stn.h "silence trimming"): off is the default (every fetch
+    // path is then exactly the one without it).  On, every fetch path finds row b's edges [start_b, end_b) by level at the output rate
+    // (kernels_edges.hip) and delivers that segment from column 0, cut edges faded; a joined fetch joins those segments.
+    void set_silence_trim(bool on, float top_db, float keep_ms, float fade_ms);
+    bool silence_trim_on() const { return st_on_; }
+    void get_silence_trim(int* on, float* top_db, float* keep_ms, float* fade_ms) const;
+    // the finished batch's edges at the output rate under the current parameters, on or off; [B] host integers or null
+    void batch_silence_edges(int64_t* start, int64_t* end);
+    // rows x W fp32 (host) at hz, row r's first n[r] samples (all W when n is null) -> start, end [rows] (host)
+    void op_silence_edges(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, int64_t* start, int64_t* end);
+    // the same, and y [rows][W] samples of enc (host): row r's segment from column 0 (times gain[r] when gain is not null, cut edges
+    // faded), zero codewords behind it
+    void op_silence_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, const float* gain,
+                         int enc, void* y, int64_t* start, int64_t* end);
+    // diagnostic: overwrite the finished batch's model-rate waveform ([B][L * chunk] host floats) and forget what was measured on it
+    void dbg_batch_set_wav(const float* wav);
 
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
@@ -539,6 +562,25 @@ class Engine {
     float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling);
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
     float* lo_batch(const float* x, int64_t Wo, bool on);
+    bool st_on_ = false;
+    float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
+    uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
+    char* ed_buf_ = nullptr; size_t ed_buf_cap_ = 0;  // fetch-time scratch of the detection (grow-only, outside the graph key)
+    struct EdScratch { float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; };
+    EdScratch ed_scratch(int64_t rows, int64_t W, int hz);
+    // what the scratch holds: the edges (and per-row programmes) of batch `seq` at rate hz under (db, keep, fade); host: read back
+    struct EdKey {
+        uint64_t seq = 0; int hz = 0; float db = 0, keep = 0, fade = 0; int64_t Wo = 0; const void* buf = nullptr;
+        bool operator==(const EdKey& o) const { return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf; }
+    };
+    EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
+    std::vector<int64_t> ed_host_, ed_n_;   // [B][2] edges read back; [B] spans
+    float* st_win_ = nullptr; size_t st_win_cap_ = 0; int st_win_hz_ = 0; float st_win_ms_ = -1.0f;  // the fade window on the device, per (rate, fade_ms)
+    const float* st_window(int hz);
+    // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already
+    EdScratch ed_batch(const float* x, int64_t Wo);
+    const std::vector<int64_t>& ed_batch_host();  // its edges on the host (one device->host read of 2 B integers per batch and setting)
+    void ed_release();
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
     // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
     // With a join plan the G programme rows of the plan instead of the B rows (scope: STN_JOIN_GAIN_*)
@@ -551,7 +593,7 @@ class Engine {
     const float* join_f32(const JoinPlan& p);
     float* join_measure(const JoinPlan& p, const float* joined, bool on);
     // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
-    struct JoinTables { const JoinSeg* seg; const JoinProg* prog; };
+    struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };  // tseg: trimmed sources (seg unused)
     JoinTables join_tables(const JoinPlan& p);
     static std::vector<int64_t> join_table_words(const JoinPlan& p, const int64_t* src_row_or_null);
     void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride);

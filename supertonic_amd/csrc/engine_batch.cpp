@@ -176,6 +176,7 @@ void Engine::batch_run(int total_step, float speed, uint64_t noise_seed) {
         throw std::runtime_error("injected noise has L=" + std::to_string(b.noise_L) + " but the durations imply L=" + std::to_string(L));
     b.L = L;
     reported_dur_ = dur;  // durations after /speed: what the reference returns (cpp/helper.cpp:680)
+    ++ed_seq_;            // (what was measured on the previous waveform at fetch time no longer holds)
     const size_t nx = (size_t)B * D * L, nw = (size_t)B * L * a.base_chunk_size * a.chunk_compress_factor;
     ensure(b.xt[0], b.xt_cap[0], nx);
     ensure(b.xt[1], b.xt_cap[1], nx);
@@ -445,6 +446,7 @@ const float* Engine::out_source(int64_t Wo) {
 }
 
 static int64_t join_stride(const JoinPlan& p);
+static size_t join_f32_offset(size_t n_rows);
 static int need_enc(int enc) {
     const int eb = enc_bytes(enc);
     if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
@@ -460,7 +462,22 @@ void Engine::enqueue_output(const OutRows& o) {
     const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
     if (o.stride < Wo)
         throw std::invalid_argument(resample_on() ? "dst_stride smaller than the waveform length at the output rate" : "dst_stride smaller than the waveform length");
-    if (loudness_on()) {
+    if (silence_trim_on()) {
+        // section 14: the rows at the output rate (resampled into the fetch scratch first when a rate is set), their edges and per-row
+        // programmes from the detection (cached per batch and setting), the gains as measured over the untrimmed spans, and the join's
+        // store with one member per programme: row b's segment from column 0, zero codewords behind it
+        const float* src = out_source(Wo);
+        if (src == o.dst) throw std::logic_error("trimmed fetch: source and destination rows are the same");
+        const EdScratch sc = ed_batch(src, Wo);
+        const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
+        const float* fade = st_window(output_rate());
+        const char* saved = stage_;
+        stage_ = "out";
+        if (prof_on_) prof_begin("trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+        launch_join_trim_rows(s_, src, resample_on() ? Wo : W, sc.seg, sc.prog, b.B, Wo, g, fade, o.enc, o.dst, o.stride);
+        if (prof_on_) prof_end();
+        stage_ = saved;
+    } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
         const char* saved = stage_;
@@ -507,8 +524,10 @@ void Engine::batch_fetch_encoded(int enc, void* dst, size_t capacity_bytes, floa
         const size_t n = (size_t)bt_.B * Wo, bytes = n * eb;
         if (capacity_bytes < bytes) throw std::runtime_error("buffer too small: need " + std::to_string(bytes) + " bytes");
         const void* src = bt_.wav;  // fp32 at the native rate: the batch's own rows, no device copy
-        if (enc != ENC_F32 || !out_native()) {
-            void* d = enc == ENC_F32 ? static_cast<void*>(out_f32_buf(n)) : static_cast<void*>(out_enc_buf(bytes));
+        if (enc != ENC_F32 || !out_native() || silence_trim_on()) {
+            // (a trimmed fp32 fetch at a set rate moves samples within their rows: its destination lies behind the resampled rows)
+            const size_t off = enc == ENC_F32 && silence_trim_on() && resample_on() ? join_f32_offset(n) : 0;
+            void* d = enc == ENC_F32 ? static_cast<void*>(out_f32_buf(off + n) + off) : static_cast<void*>(out_enc_buf(bytes));
             enqueue_output({d, enc, Wo});
             src = d;
         }
@@ -605,8 +624,32 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
     std::vector<int64_t> len((size_t)b.B);
     for (int i = 0; i < b.B; ++i) len[(size_t)i] = std::min<int64_t>(Wo, out_len((int64_t)b.h_llen[(size_t)i] * cs));
     JoinPlan p;
-    const std::string why = join_plan(j, b.B, Wo, output_rate(), len.data(), reported_dur_.data(), p);
-    if (!why.empty()) throw std::invalid_argument(why);
+    if (silence_trim_on() && j && (j->mode == STN_JOIN_WHOLE || j->mode == STN_JOIN_TRIM)) {
+        // section 14: a member's segment is [start_b, end_b) under either mode, its duration (float)len_b / (float)hz; the edges come
+        // from the device (one read of 2 B integers per finished batch and setting)
+        const std::vector<int64_t>& e = ed_batch_host();
+        const int hz = output_rate();
+        const int64_t fd = silence_samples(hz, st_fade_);
+        std::vector<float> dur((size_t)b.B);
+        for (int i = 0; i < b.B; ++i) {
+            len[(size_t)i] = e[(size_t)i * 2 + 1] - e[(size_t)i * 2];
+            dur[(size_t)i] = (float)len[(size_t)i] / (float)hz;
+        }
+        stn_join jj = *j;
+        jj.mode = STN_JOIN_WHOLE;  // (the lengths are the edges')
+        const std::string why = join_plan(&jj, b.B, Wo, hz, len.data(), dur.data(), p);
+        if (!why.empty()) throw std::invalid_argument(why);
+        p.seg_src.resize((size_t)b.B); p.seg_fin.resize((size_t)b.B); p.seg_fout.resize((size_t)b.B);
+        for (int i = 0; i < b.B; ++i) {
+            const int64_t st = e[(size_t)i * 2], en = e[(size_t)i * 2 + 1], fl = std::min<int64_t>(fd, en - st);
+            p.seg_src[(size_t)i] = st;
+            p.seg_fin[(size_t)i] = st > 0 ? (int32_t)fl : 0;
+            p.seg_fout[(size_t)i] = en < ed_n_[(size_t)i] ? (int32_t)fl : 0;
+        }
+    } else {
+        const std::string why = join_plan(j, b.B, Wo, output_rate(), len.data(), reported_dur_.data(), p);
+        if (!why.empty()) throw std::invalid_argument(why);
+    }
     if (p.G > 65535) throw std::invalid_argument("join: more than 65535 programmes");
     return p;
 }
@@ -628,14 +671,32 @@ std::vector<int64_t> Engine::join_table_words(const JoinPlan& p, const int64_t* 
     return w;
 }
 
+// trimmed sources: [B] members {dst, len, source row, src, fin | fout << 32}, the words of JoinSegT, then the programmes
+static std::vector<int64_t> join_trim_table_words(const JoinPlan& p) {
+    static_assert(sizeof(JoinSegT) == 40, "the join tables are uploaded as int64 words");
+    std::vector<int64_t> w((size_t)p.B * 5 + (size_t)p.G * 2);
+    for (int i = 0; i < p.B; ++i) {
+        JoinSegT sg{p.seg_dst[(size_t)i], p.seg_len[(size_t)i], i, p.seg_src[(size_t)i], p.seg_fin[(size_t)i], p.seg_fout[(size_t)i]};
+        std::memcpy(&w[(size_t)i * 5], &sg, sizeof(sg));
+    }
+    for (int g = 0; g < p.G; ++g) {
+        const int32_t first = p.first[(size_t)g], count = (g + 1 < p.G ? p.first[(size_t)g + 1] : p.B) - first;
+        JoinProg pg{p.prog_len[(size_t)g], first, count};
+        std::memcpy(&w[(size_t)p.B * 5 + (size_t)g * 2], &pg, sizeof(pg));
+    }
+    return w;
+}
+
 Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
-    std::vector<int64_t> w = join_table_words(p, nullptr);
+    const bool trim = !p.seg_src.empty();
+    std::vector<int64_t> w = trim ? join_trim_table_words(p) : join_table_words(p, nullptr);
     const bool moved = !join_tab_ || w.size() > join_tab_cap_;
     int64_t* d = out_grow(*this, join_tab_, join_tab_cap_, w.size());
     if (moved || w != join_tab_host_) {  // later fetches of the same batch under the same join reuse the upload
         join_tab_host_ = std::move(w);
         STN_HIP(hipMemcpyAsync(d, join_tab_host_.data(), join_tab_host_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
+    if (trim) return {nullptr, reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
     return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
 }
 
@@ -643,7 +704,8 @@ void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& 
     const char* saved = stage_;
     stage_ = "out";
     if (prof_on_) prof_begin("join", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + enc_bytes(enc)));
-    launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
+    if (t.tseg) launch_join_trim_rows(s_, x, src_stride, t.tseg, t.prog, p.G, p.W_join, g, t.fade, enc, y, dst_stride);
+    else launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
     if (prof_on_) prof_end();
     stage_ = saved;
     STN_HIP(hipGetLastError());

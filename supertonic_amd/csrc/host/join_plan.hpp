@@ -17,6 +17,10 @@ struct JoinPlan {
     std::vector<int64_t> seg_len, seg_dst;             // [B]
     std::vector<int64_t> prog_len;                     // [G]
     std::vector<float> prog_dur;                       // [G]
+    // [B] each, or all three empty: with silence trimming on the segment's first source sample and the samples
+    // faded at its head and its tail; the engine's output stage fills them, join_plan leaves them empty
+    std::vector<int64_t> seg_src;
+    std::vector<int32_t> seg_fin, seg_fout;
 };
 
 // Fills p from B members of whole lengths member_len (each in [0, W_out]) and durations member_dur (may be null with STN_JOIN_WHOLE:

@@ -16,6 +16,13 @@ namespace {
 void check(stn_handle* h, int rc) {
     if (rc != STN_OK) throw std::runtime_error(std::string("engine: ") + stn_last_error(h));
 }
+// with silence trimming on: the samples each row of the finished batch holds (the segments the fetch delivered)
+std::vector<int64_t> trimmed_lengths(stn_handle* h, int B) {
+    std::vector<int64_t> start((size_t)B), end((size_t)B);
+    check(h, stn_batch_silence_edges(h, start.data(), end.data()));
+    for (int b = 0; b < B; ++b) end[(size_t)b] -= start[(size_t)b];
+    return end;
+}
 }  // namespace
 
 TextToSpeech::TextToSpeech(stn_handle* engine, UnicodeProcessor tp, const Config& cfgs, uint64_t noise_seed)
@@ -69,12 +76,21 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
     if (enc_ != STN_ENC_PCM16) {
         r.encoded.resize((size_t)B * W * stn_encoding_bytes(enc_));
         check(h_, stn_batch_fetch_encoded(h_, enc_, r.encoded.data(), r.encoded.size(), r.duration.data()));
+        if (trim_silence_) r.length = trimmed_lengths(h_, B);
         return r;
     }
     r.wav.resize((size_t)B * W);
     check(h_, stn_batch_fetch(h_, r.wav.data(), r.wav.size(), r.duration.data()));
+    if (trim_silence_) r.length = trimmed_lengths(h_, B);
     return r;
 }
+
+void TextToSpeech::setSilenceTrim(bool on, float top_db, float keep_ms, float fade_ms) {
+    if (on && grp_) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
+    check(h_, stn_set_silence_trim(h_, on ? 1 : 0, top_db, keep_ms, fade_ms));
+    trim_silence_ = on;
+}
+
 
 // one handle: the batch uploaded and run, ready for whichever fetch the caller wants
 void TextToSpeech::runBatch(const TokenBatch& tb, const std::vector<float>& mask, const Style& style, int total_step, float speed) {
@@ -98,7 +114,7 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
                                                  int total_step, float speed, float silence_duration) {
     if (style.getTtlShape()[0] != 1) throw std::runtime_error("Single speaker text to speech only supports single style");
     const std::vector<std::string> chunks = chunk_text(text, lang == "ko" ? 120 : 300);
-    if (chunks.size() == 1) return infer({chunks[0]}, {lang}, style, total_step, speed);
+    if (chunks.size() == 1 && !trim_silence_) return infer({chunks[0]}, {lang}, style, total_step, speed);  // (trimmed: the join cuts the one segment)
     // The reference synthesizes the chunks one after another (cpp/helper.cpp:697-719: one _infer, i.e. four Run calls per
     // step, per chunk).  Here they form ONE batch with the speaker's style replicated; the length-aware vocoder mode makes
     // every chunk's wave over its own frames what the batch-of-one run gives, so the joined result keeps the reference's
@@ -144,6 +160,7 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
             out.wav.resize((size_t)W_join);
             check(h_, stn_batch_fetch_joined(h_, &j, STN_ENC_F32, out.wav.data(), out.wav.size() * sizeof(float), nullptr, out.duration.data()));
         }
+        if (trim_silence_) out.length = {W_join};  // (one programme: its length is the joined segments')
         return out;
     }
     // a group deals the chunks over its devices: its long form keeps the host join of the gathered rows
@@ -200,6 +217,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
             throw std::runtime_error("loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
                                      "(use one GPU, or the default scope 'chunk')");
         if (opts.trim_chunks) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
+        if (!std::isnan(opts.trim_silence_db)) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
         std::vector<int> dev = opts.devices;
         if (dev.empty()) for (int i = 0; i < opts.gpus; ++i) dev.push_back(opts.device + i);
         if (stn_group_create((int)dev.size(), dev.data(), opts.dtype, &grp) != STN_OK) throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(nullptr));
@@ -249,12 +267,15 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
                 check(h, stn_set_loudness(h, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs));
             }
         }
+        // (refused here, while this function still owns the handle: once tts owns it, a throw would destroy it twice)
+        if (!std::isnan(opts.trim_silence_db)) check(h, stn_set_silence_trim(h, 1, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms));
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);
         tts->setEncoding(opts.encoding);
         tts->setLoudnessScope(opts.loudness_scope_text);
         tts->setTrimChunks(opts.trim_chunks);
+        if (!std::isnan(opts.trim_silence_db)) tts->setSilenceTrim(true, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms);  // (accepted above)
         if (synthetic) tts->markSynthetic();
         return tts;
     } catch (...) {

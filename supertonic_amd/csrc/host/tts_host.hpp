@@ -66,6 +66,11 @@ struct EngineOptions {
     bool loudness_scope_text = false;  // long-form call() with loudness on: the joined text normalized as one programme with one gain instead
                                    // of every chunk on its own.  One device only.  CLI --loudness-scope {chunk,text}
     bool trim_chunks = false;      // long-form call(): every chunk cut at its duration before the join.  CLI --trim-chunks
+    float trim_silence_db = std::numeric_limits<float>::quiet_NaN();  // trim leading and trailing silence of every utterance by level on the
+                                   // GPU (stn_set_silence_trim): frames more than this many dB below the loudest 10 ms frame; NaN: off.  One
+                                   // device only.  CLI --trim-silence DB
+    float trim_keep_ms = 20.0f;    // milliseconds kept in front of and behind the speech.  CLI --trim-keep MS
+    float trim_fade_ms = 5.0f;     // raised-cosine fade over each cut edge.  CLI --trim-fade MS
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
@@ -74,7 +79,8 @@ class TextToSpeech {
    public:
     // wav: the float waveform [B][W].  With an encoding other than PCM16 (setEncoding) the audio is `encoded` instead: [B][W] samples
     // of stn_encoding_bytes(encoding) bytes, as the engine's encoded fetch delivers them, and wav is empty.
-    struct SynthesisResult { std::vector<float> wav; std::vector<float> duration; std::vector<unsigned char> encoded; int encoding = STN_ENC_PCM16; };
+    // length: with silence trimming on (setSilenceTrim), the samples each row holds from column 0, its trimmed segment (empty: off).
+    struct SynthesisResult { std::vector<float> wav; std::vector<float> duration; std::vector<unsigned char> encoded; int encoding = STN_ENC_PCM16; std::vector<int64_t> length; };
 
     TextToSpeech(stn_handle* engine, UnicodeProcessor text_processor, const Config& cfgs, uint64_t noise_seed);
     // several devices: the group owns the handles (engine() is rank 0's); batch() / call() deal their utterances over the group
@@ -98,6 +104,9 @@ class TextToSpeech {
     void setLoudnessScope(bool whole_text);
     // call(): every chunk cut at its reported duration before the join (the reference's Rust host) instead of its whole wave
     void setTrimChunks(bool on) { trim_chunks_ = on; }
+    // every utterance without its leading and trailing silence (stn_set_silence_trim; stn.h "silence trimming"): batch() rows hold the
+    // trimmed segment from column 0 (SynthesisResult::length), call() joins the segments.  Refused on a group.
+    void setSilenceTrim(bool on, float top_db = 40.0f, float keep_ms = 20.0f, float fade_ms = 5.0f);
     int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
@@ -108,7 +117,7 @@ class TextToSpeech {
     SynthesisResult infer(const std::vector<std::string>& text_list, const std::vector<std::string>& lang_list,
                           const Style& style, int total_step, float speed);
     void runBatch(const TokenBatch& tb, const std::vector<float>& mask, const Style& style, int total_step, float speed);
-    bool scope_text_ = false, trim_chunks_ = false;
+    bool scope_text_ = false, trim_chunks_ = false, trim_silence_ = false;
     stn_handle* h_;
     stn_group* grp_ = nullptr;
     UnicodeProcessor text_processor_;

@@ -420,6 +420,31 @@ struct JoinSeg { int64_t dst, len, row; };
 struct JoinProg { int64_t len; int32_t first, count; };
 void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
                       int enc, void* y, int64_t dst_stride);
+// The same join from trimmed sources: member m is the seg[m].len samples of source row seg[m].row from sample
+// seg[m].src on; its first seg[m].fin delivered samples are times fade[q], its last seg[m].fout times fade[len - 1 - q] (q the sample's
+// place in the segment; fade on the device, at least max(fin, fout) floats; both 0: no sample changes).  A delivered sample is
+// ((x * g) * w_in) * w_out, three fp32 multiplies in that order, each only where it applies.  The per-row trimmed fetch is this with one
+// member per programme (the tables launch_edges_rows writes).
+struct JoinSegT { int64_t dst, len, row, src; int32_t fin, fout; };
+void launch_join_trim_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSegT* seg, const JoinProg* prog, int G, int64_t Wj,
+                           const float* g, const float* fade, int enc, void* y, int64_t dst_stride);
+
+// Silence edges of the finished waveform by level (kernels_edges.hip; the setting and the caches are engine_edges.cpp; DESIGN.md section
+// 14).  Frames of F = edges_frame(hz) samples (10 ms) from sample 0 without overlap, level = mean of x^2 over the frame's own samples;
+// a frame is active at or above max level * 10^(-top_db / 10); a row whose max level is <= 1e-7, or that is empty, keeps [0, n).
+constexpr int ED_CHUNK = 32;          // samples per lane of the frame pass
+constexpr int ED_WG = 256;            // lanes (chunks) per workgroup of the frame pass
+__host__ __device__ inline int64_t ed_chunks(int64_t W) { return (W + ED_CHUNK - 1) / ED_CHUNK; }
+inline int edges_frame(int hz) { return (hz + 50) / 100; }
+inline int64_t edges_frames(int64_t W, int hz) { const int F = edges_frame(hz); return (W + F - 1) / F; }
+// rows x W fp32 (row stride W) with row lengths n[rows] (device, <= W) -> edges[row] = {start, end} with
+// start = max(0, f0 * F - keep), end = min(n, (f1 + 1) * F + keep) over the first and last active frame.  Scratch (device): pa, pb
+// [rows][ed_chunks(W)] floats, lev [rows][edges_frames(W, hz)] doubles (the levels, left there).  seg / prog (both or neither): the
+// per-row programmes {dst 0, len, row, src = start, fin / fout = min(fd, len) where that edge was cut} and {len, row, 1}.
+// Two launches, the hand-off between them a launch boundary: the frame pass (x -> pa, pb) and the row pass (pa, pb -> lev, edges, seg, prog).
+void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb);
+void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
+                       const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog);
 
 // Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
 // out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),

@@ -1,0 +1,192 @@
+// kernels_edges.hip — where the speech of a finished row starts and ends, by level (gfx950, wave64).  Runs at fetch
+// time, outside the captured pipeline, on rows x W fp32 samples of which row b's first n_b count.
+//
+// Frames of F samples (10 ms) from sample 0, the last one short; frame k's level m_k is the mean of x^2 over its own samples.
+//   1. frame pass: a lane owns ED_CHUNK consecutive samples of a row, counted from sample 0 (the energy pass of kernels_loudness.hip: a
+//      workgroup stages its ED_WG chunks in LDS with 16-byte loads, row stride 33 words), and sums x^2 in sample order into the chunk's
+//      share of the frame it starts in and of the next one (F > ED_CHUNK: a chunk meets two frames at most);
+//   2. row pass: one workgroup per row sums each frame's shares in chunk order (a thread per frame, in double), writes the levels,
+//      takes their maximum, finds the first and the last frame at or above the threshold, and writes the row's edges and the one-member
+//      programme of the per-row trimmed fetch (JoinSegT / JoinProg: the store is join_trim_rows_kernel, kernels_output.hip).
+// The hand-off is a launch boundary and every sum runs in an order fixed by the sample positions within the row: a row's edges depend
+// on its first n_b samples, the rate and the parameters only, not on W, the batch or the row's place in it.  Max, min and the
+// comparisons are order-independent.
+#include "kernels.hpp"
+
+#include <math.h>
+
+namespace stn {
+
+namespace {
+
+constexpr int ED_SPAN = ED_WG * ED_CHUNK;  // samples a workgroup of the frame pass owns
+constexpr int ED_PAD = ED_CHUNK + 1;       // LDS words per chunk
+constexpr int ED_ROW = 1024;               // threads of the row workgroup
+
+__global__ void __launch_bounds__(ED_WG) edges_chunk_kernel(const float* __restrict__ x, int64_t W, int vec, const int64_t* __restrict__ nrow,
+                                                            int64_t Ks, int F, float* __restrict__ pa, float* __restrict__ pb) {
+    __shared__ float win[ED_WG * ED_PAD];
+    const int64_t row = blockIdx.y;
+    const int64_t n = nrow[row];
+    const int64_t s0 = (int64_t)blockIdx.x * ED_SPAN;
+    if (s0 >= n) return;  // (the whole workgroup: nothing of the span lies in the row)
+    const int cnt = (int)(n - s0 < ED_SPAN ? n - s0 : ED_SPAN);
+    const float* __restrict__ xr = x + row * W + s0;
+    if (vec) {  // rows 16-byte aligned and W % 4 == 0: a float4 that starts below n ends at or below W
+        constexpr int U = ED_SPAN / 4 / ED_WG;
+        float4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = threadIdx.x + u * ED_WG;
+            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = 4 * (threadIdx.x + u * ED_WG);
+            if (i < cnt) {
+                float* d = win + (i / ED_CHUNK) * ED_PAD + (i % ED_CHUNK);  // (the four samples share a chunk)
+                d[0] = v[u].x;
+                if (i + 1 < cnt) d[1] = v[u].y;
+                if (i + 2 < cnt) d[2] = v[u].z;
+                if (i + 3 < cnt) d[3] = v[u].w;
+            }
+        }
+    } else {
+        for (int i0 = 0; i0 < ED_SPAN; i0 += 8 * ED_WG) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + threadIdx.x + u * ED_WG;
+                v[u] = i < cnt ? xr[i] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + threadIdx.x + u * ED_WG;
+                if (i < cnt) win[(i / ED_CHUNK) * ED_PAD + (i % ED_CHUNK)] = v[u];
+            }
+        }
+    }
+    __syncthreads();
+    const int c0 = threadIdx.x * ED_CHUNK;
+    if (c0 >= cnt) return;
+    const int len = cnt - c0 < ED_CHUNK ? cnt - c0 : ED_CHUNK;
+    const int64_t k = (int64_t)blockIdx.x * ED_WG + threadIdx.x;
+    const float* w = win + threadIdx.x * ED_PAD;
+    const int64_t g0 = s0 + c0;
+    const int split = (int)((g0 / F + 1) * F - g0);  // samples of this chunk before the next frame begins (>= 1)
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int i = 0; i < ED_CHUNK; ++i) {
+        if (i < len) {
+            const float xx = w[i] * w[i];
+            a += i < split ? xx : 0.0f;
+            b += i >= split ? xx : 0.0f;
+        }
+    }
+    pa[row * Ks + k] = a;
+    pb[row * Ks + k] = b;
+}
+
+// fixed places for the wave results of a workgroup-wide max / min
+template <typename T, typename Op>
+__device__ T ed_block_reduce(T v, T* red, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = red[0];
+    for (int w = 1; w < ED_ROW / 64; ++w) s = op(s, red[w]);
+    __syncthreads();
+    return s;
+}
+
+__global__ void __launch_bounds__(ED_ROW) edges_row_kernel(const int64_t* __restrict__ nrow, int64_t Ks, int64_t Kf, int F, double ratio, double floor_ms,
+                                                           int64_t keep, int64_t fd, const float* __restrict__ pa, const float* __restrict__ pb,
+                                                           double* lev, int64_t* __restrict__ edges, JoinSegT* __restrict__ seg,
+                                                           JoinProg* __restrict__ prog) {
+    __shared__ double redd[ED_ROW / 64];
+    __shared__ long long redi[ED_ROW / 64];
+    const int64_t row = blockIdx.x;
+    const int64_t n = nrow[row];
+    const int64_t K = (n + F - 1) / F;
+    const int tid = threadIdx.x;
+    const float* __restrict__ par = pa + row * Ks;
+    const float* __restrict__ pbr = pb + row * Ks;
+    double* levr = lev + row * Kf;
+    // frame levels: the shares of the chunks that touch the frame, in chunk order; a chunk that starts in the frame gives its first
+    // share, the one that started in the frame before its second
+    double mx = 0.0;
+    for (int64_t k = tid; k < K; k += ED_ROW) {
+        const int64_t lo = k * F, hi = lo + F < n ? lo + F : n;
+        const int64_t c0 = lo / ED_CHUNK, c1 = (hi - 1) / ED_CHUNK;
+        double s = 0.0;
+        for (int64_t c = c0; c <= c1; ++c) s += (c * ED_CHUNK / F == k) ? (double)par[c] : (double)pbr[c];
+        const double m = s / (double)(hi - lo);
+        levr[k] = m;  // (read back below by this thread only)
+        mx = fmax(mx, m);
+    }
+    mx = ed_block_reduce(mx, redd, [](double p, double q) { return fmax(p, q); });
+    const bool speech = n > 0 && mx > floor_ms;
+    const double thr = mx * ratio;
+    long long f0 = K, f1 = -1;
+    if (speech) {
+        for (int64_t k = tid; k < K; k += ED_ROW) {
+            if (levr[k] >= thr) {
+                if (k < f0) f0 = k;
+                if (k > f1) f1 = k;
+            }
+        }
+    }
+    f0 = ed_block_reduce(f0, redi, [](long long p, long long q) { return p < q ? p : q; });
+    f1 = ed_block_reduce(f1, redi, [](long long p, long long q) { return p > q ? p : q; });
+    if (tid == 0) {
+        int64_t start = 0, end = n;
+        if (speech && f1 >= f0) {
+            start = f0 * F - keep;
+            if (start < 0) start = 0;
+            end = (f1 + 1) * F + keep;
+            if (end > n) end = n;
+        }
+        edges[2 * row] = start;
+        edges[2 * row + 1] = end;
+        if (seg) {
+            const int64_t len = end - start, fl = fd < len ? fd : len;
+            JoinSegT sg;
+            sg.dst = 0; sg.len = len; sg.row = row; sg.src = start;
+            sg.fin = start > 0 ? (int32_t)fl : 0;
+            sg.fout = end < n ? (int32_t)fl : 0;
+            seg[row] = sg;
+            JoinProg pg;
+            pg.len = len; pg.first = (int32_t)row; pg.count = 1;
+            prog[row] = pg;
+        }
+    }
+}
+
+}  // namespace
+
+static int edges_check(int64_t rows, int64_t W, int hz) {
+    if (rows > 65535) throw std::invalid_argument("silence edges: more than 65535 rows");
+    const int F = edges_frame(hz);
+    if (F <= ED_CHUNK) throw std::invalid_argument("silence edges: the rate is too low for a 10 ms frame of more than " + std::to_string(ED_CHUNK) + " samples");
+    if (ed_chunks(W) > ((int64_t)1 << 31) / ED_WG) throw std::invalid_argument("silence edges: row too long");
+    return F;
+}
+
+void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb) {
+    if (rows <= 0 || W <= 0) return;
+    const int F = edges_check(rows, W, hz);
+    const int vec = (W % 4 == 0 && !(reinterpret_cast<uintptr_t>(x) & 15)) ? 1 : 0;
+    STN_KLAUNCH(edges_chunk_kernel, dim3((unsigned)((W + ED_SPAN - 1) / ED_SPAN), (unsigned)rows), dim3(ED_WG), 0, s, x, W, vec, n, ed_chunks(W), F, pa, pb);
+}
+
+void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
+                       const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog) {
+    if (rows <= 0 || W <= 0) return;
+    const int F = edges_check(rows, W, hz);
+    if (fd < 0 || fd > 0x7fffffff || keep < 0) throw std::invalid_argument("silence edges: bad keep or fade length");
+    STN_KLAUNCH(edges_row_kernel, dim3((unsigned)rows), dim3(ED_ROW), 0, s, n, ed_chunks(W), edges_frames(W, hz), F, std::pow(10.0, -top_db / 10.0), 1e-7,
+                keep, fd, pa, pb, lev, edges, seg, prog);
+}
+
+}  // namespace stn

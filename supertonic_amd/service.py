@@ -49,19 +49,24 @@ class DynamicBatcher:
         self._t.start()
 
     def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
-               silence_duration=None, loudness_scope="chunk", trim_chunks=False):
+               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
         the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
         silence_duration (seconds, not None): the job's utterances are the chunks of one text and come back as ONE wave, joined with
         that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own gap), with its duration;
         loudness_scope ("chunk": every chunk its own gain; "text": the joined wave normalized as one programme) and trim_chunks
-        (TextToSpeech.joined_batch) are part of the batch key: one fetch has one mode and one scope."""
+        (TextToSpeech.joined_batch) are part of the batch key: one fetch has one mode and one scope.  trim_silence (None: the
+        synthesizer's own setting; top_db or (top_db, keep_ms, fade_ms)): the waves without their leading and trailing silence; part of
+        the batch key as well (the setting covers a whole batch), and validated here."""
+        ts = None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:]
         lo = None if loudness is None else (float(loudness), float(peak_ceiling))
         enc = None if encoding is None else binding.encoding_id(encoding)
         key = (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc)
         if loudness_scope != "chunk" or trim_chunks:  # (requests that use neither batch exactly as before)
             key += (str(loudness_scope), bool(trim_chunks))
+        if ts is not None:  # (likewise: always the key's last element, a pair)
+            key += (("trim_silence", ts),)
         job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
         with self._cv:
             if self._stop:
@@ -116,8 +121,14 @@ class DynamicBatcher:
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
                 step, speed, rate, lo, enc = jobs[0].key[:5]
-                scope, trim = jobs[0].key[5:] or ("chunk", False)
+                tail = jobs[0].key[5:]
+                ts = None
+                if tail and isinstance(tail[-1], tuple):
+                    ts, tail = tail[-1][1], tail[:-1]
+                scope, trim = tail or ("chunk", False)
                 extra = {} if rate is None else {"output_rate": rate}
+                if ts is not None:
+                    extra["trim_silence"] = ts
                 if lo is not None:
                     extra["loudness"] = lo
                 if enc is not None:
@@ -210,6 +221,10 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         loudness_scope: str = Field("chunk", description="Non-batch mode with loudness: 'chunk' normalizes every chunk of a long text on its own, "
                                                          "'text' the joined text as one BS.1770 programme with one gain.")
         trim_chunks: bool = Field(False, description="Non-batch mode: cut every chunk at its duration before the join.")
+        trim_silence: Optional[float] = Field(None, ge=1.0, le=120.0, description="Trim leading and trailing silence by level (on the GPU): frames "
+                                                                                 "more than this many dB below the loudest 10 ms frame; null: off.")
+        trim_keep_ms: float = Field(20.0, ge=0.0, le=1000.0, description="Milliseconds kept in front of and behind the speech when trimming.")
+        trim_fade_ms: float = Field(5.0, ge=0.0, le=50.0, description="Raised-cosine fade over each cut edge, in milliseconds.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -248,18 +263,23 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         if req.loudness_scope not in ("chunk", "text"):
             raise HTTPException(status_code=400, detail=f"loudness_scope {req.loudness_scope!r} is not supported; supported: chunk, text")
         enc = None if req.encoding == "pcm16" else req.encoding  # pcm16: the float waves, written as writeWavFile writes them
+        ts = None if req.trim_silence is None else (req.trim_silence, req.trim_keep_ms, req.trim_fade_ms)
         if enc is not None:
             extra["encoding"] = enc
         if req.batch:
-            wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
-            chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
+            if ts is not None:  # every wave is its trimmed segment, cut at the length the GPU found
+                wav, dur, seg = tts.batch(texts, langs, style, req.total_step, req.speed, trim_silence=ts, lengths=True, **extra)
+                chunks = [wav[i, : int(seg[i])] for i in range(wav.shape[0])]
+            else:
+                wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
+                chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
-                                         trim_chunks=req.trim_chunks)
+                                         trim_chunks=req.trim_chunks, trim_silence=ts)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
-            chunks = [wav[: int(sr * d)]]
+            chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:
             name = host.sanitize_filename(texts[0], 40) or "tts"
             return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav",
