@@ -460,6 +460,26 @@ class Engine {
     struct ProfSpan { std::string tag; hipEvent_t a, b; double flops, bytes; };
     void prof_begin(const char* tag, double flops, double bytes);
     void prof_end();
+    // A launch of the output stage in its bracket: stage_ names the stage and, while profiling, a span `tag` is open, from here to the end
+    // of the scope, however it is left (launchers throw).  next(): the span ends and another begins under the same stage.
+    class StageSpan {
+       public:
+        StageSpan(Engine& e, const char* stage, const char* tag, double flops, double bytes) : e_(e), prev_(e.stage_) {
+            e_.stage_ = stage;
+            begin(tag, flops, bytes);
+        }
+        ~StageSpan() { end(); e_.stage_ = prev_; }
+        StageSpan(const StageSpan&) = delete;
+        StageSpan& operator=(const StageSpan&) = delete;
+        void next(const char* tag, double flops, double bytes) { end(); begin(tag, flops, bytes); }
+
+       private:
+        void begin(const char* tag, double flops, double bytes) { if ((begun_ = e_.prof_on_)) e_.prof_begin(tag, flops, bytes); }
+        void end() { if (begun_) e_.prof_end(); begun_ = false; }
+        Engine& e_;
+        const char* prev_;
+        bool begun_ = false;
+    };
 
     int device_, dt_;
     int n_cu_ = 256;  // compute units of the device (launch shapes that depend on rounds of workgroups)
@@ -595,7 +615,13 @@ class Engine {
     // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
     struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };  // tseg: trimmed sources (seg unused)
     JoinTables join_tables(const JoinPlan& p);
-    static std::vector<int64_t> join_table_words(const JoinPlan& p, const int64_t* src_row_or_null);
+    static std::vector<int64_t> join_table_words(const JoinPlan& p);  // members of 3 words (JoinSeg) or, trimmed sources, 5 (JoinSegT), then the programmes
+    // the pointers into those words on the device; for trimmed sources also the fade window of the output rate, uploaded here if need be
+    // (st_window: why this is no static function; op_join's plans have no trimmed sources and never get there)
+    JoinTables join_tables_at(const int64_t* d, const JoinPlan& p);
+    // res (device [3][n]: L, peak, gain) into whichever of the three host arrays is not null; the caller syncs
+    void lo_read_back(const float* res, size_t n, float* lufs, float* peak, float* gain);
+    int64_t native_row_len() const { return (int64_t)bt_.L * a_.base_chunk_size * a_.chunk_compress_factor; }  // samples of a row of b.wav
     void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride);
     int64_t* join_tab_ = nullptr; size_t join_tab_cap_ = 0;
     std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)

@@ -432,7 +432,7 @@ int64_t Engine::out_row_len() {
     STN_HIP(hipSetDevice(device_));
     const Batch& b = bt_;
     if (!b.wav || b.L == 0) throw std::runtime_error("no finished batch");
-    return out_len((int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor);
+    return out_len(native_row_len());
 }
 
 bool Engine::out_native() const { return !loudness_on() && !resample_on(); }
@@ -441,7 +441,7 @@ const float* Engine::out_source(int64_t Wo) {
     const Batch& b = bt_;
     if (!resample_on()) return b.wav;
     float* d = out_f32_buf((size_t)b.B * Wo);
-    resample_enqueue(rs_table(), b.wav, b.B, (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, ENC_F32, d, Wo);
+    resample_enqueue(rs_table(), b.wav, b.B, native_row_len(), ENC_F32, d, Wo);
     return d;
 }
 
@@ -459,7 +459,7 @@ void Engine::enqueue_output(const OutRows& o) {
     if (o.join) { enqueue_joined(o); return; }
     const Batch& b = bt_;
     const int eb = need_enc(o.enc);
-    const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    const int64_t Wo = out_row_len(), W = native_row_len();
     if (o.stride < Wo)
         throw std::invalid_argument(resample_on() ? "dst_stride smaller than the waveform length at the output rate" : "dst_stride smaller than the waveform length");
     if (silence_trim_on()) {
@@ -471,30 +471,18 @@ void Engine::enqueue_output(const OutRows& o) {
         const EdScratch sc = ed_batch(src, Wo);
         const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
         const float* fade = st_window(output_rate());
-        const char* saved = stage_;
-        stage_ = "out";
-        if (prof_on_) prof_begin("trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+        StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_join_trim_rows(s_, src, resample_on() ? Wo : W, sc.seg, sc.prog, b.B, Wo, g, fade, o.enc, o.dst, o.stride);
-        if (prof_on_) prof_end();
-        stage_ = saved;
     } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
-        const char* saved = stage_;
-        stage_ = "out";
-        if (prof_on_) prof_begin("loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+        StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, src, b.B, Wo, g, o.enc, o.dst, o.stride);
-        if (prof_on_) prof_end();
-        stage_ = saved;
     } else if (resample_on()) {
         resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
     } else if (o.enc != ENC_F32) {
-        const char* saved = stage_;
-        stage_ = "out";
-        if (prof_on_) prof_begin("store_rows", (double)b.B * W, (double)b.B * W * (4 + eb));
+        StageSpan span(*this, "out", "store_rows", (double)b.B * W, (double)b.B * W * (4 + eb));
         launch_store_rows(s_, b.wav, b.B, W, nullptr, o.enc, o.dst, o.stride);
-        if (prof_on_) prof_end();
-        stage_ = saved;
     } else {
         STN_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
     }
@@ -654,60 +642,52 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
     return p;
 }
 
-// [B] members {dst, len, source row} then [G] programmes {len, first | count << 32}: the words of JoinSeg / JoinProg
-std::vector<int64_t> Engine::join_table_words(const JoinPlan& p, const int64_t* src_row) {
-    static_assert(sizeof(JoinSeg) == 24 && sizeof(JoinProg) == 16, "the join tables are uploaded as int64 words");
-    std::vector<int64_t> w((size_t)p.B * 3 + (size_t)p.G * 2);
+// [B] members then [G] programmes {len, first | count << 32} as int64 words: a member is {dst, len, source row}, the words of JoinSeg, or,
+// from trimmed sources (p.seg_src set), {dst, len, source row, src, fin | fout << 32}, the words of JoinSegT
+std::vector<int64_t> Engine::join_table_words(const JoinPlan& p) {
+    static_assert(sizeof(JoinSeg) == 24 && sizeof(JoinSegT) == 40 && sizeof(JoinProg) == 16, "the join tables are uploaded as int64 words");
+    const bool trim = !p.seg_src.empty();
+    const size_t mw = trim ? 5 : 3;
+    std::vector<int64_t> w((size_t)p.B * mw + (size_t)p.G * 2);
     for (int i = 0; i < p.B; ++i) {
-        w[(size_t)i * 3] = p.seg_dst[(size_t)i];
-        w[(size_t)i * 3 + 1] = p.seg_len[(size_t)i];
-        w[(size_t)i * 3 + 2] = src_row ? src_row[i] : i;
+        if (trim) {
+            const JoinSegT sg{p.seg_dst[(size_t)i], p.seg_len[(size_t)i], i, p.seg_src[(size_t)i], p.seg_fin[(size_t)i], p.seg_fout[(size_t)i]};
+            std::memcpy(&w[(size_t)i * mw], &sg, sizeof(sg));
+        } else {
+            const JoinSeg sg{p.seg_dst[(size_t)i], p.seg_len[(size_t)i], i};
+            std::memcpy(&w[(size_t)i * mw], &sg, sizeof(sg));
+        }
     }
     for (int g = 0; g < p.G; ++g) {
         const int32_t first = p.first[(size_t)g], count = (g + 1 < p.G ? p.first[(size_t)g + 1] : p.B) - first;
-        JoinProg pg{p.prog_len[(size_t)g], first, count};
-        std::memcpy(&w[(size_t)p.B * 3 + (size_t)g * 2], &pg, sizeof(pg));
+        const JoinProg pg{p.prog_len[(size_t)g], first, count};
+        std::memcpy(&w[(size_t)p.B * mw + (size_t)g * 2], &pg, sizeof(pg));
     }
     return w;
 }
 
-// trimmed sources: [B] members {dst, len, source row, src, fin | fout << 32}, the words of JoinSegT, then the programmes
-static std::vector<int64_t> join_trim_table_words(const JoinPlan& p) {
-    static_assert(sizeof(JoinSegT) == 40, "the join tables are uploaded as int64 words");
-    std::vector<int64_t> w((size_t)p.B * 5 + (size_t)p.G * 2);
-    for (int i = 0; i < p.B; ++i) {
-        JoinSegT sg{p.seg_dst[(size_t)i], p.seg_len[(size_t)i], i, p.seg_src[(size_t)i], p.seg_fin[(size_t)i], p.seg_fout[(size_t)i]};
-        std::memcpy(&w[(size_t)i * 5], &sg, sizeof(sg));
-    }
-    for (int g = 0; g < p.G; ++g) {
-        const int32_t first = p.first[(size_t)g], count = (g + 1 < p.G ? p.first[(size_t)g + 1] : p.B) - first;
-        JoinProg pg{p.prog_len[(size_t)g], first, count};
-        std::memcpy(&w[(size_t)p.B * 5 + (size_t)g * 2], &pg, sizeof(pg));
-    }
-    return w;
+Engine::JoinTables Engine::join_tables_at(const int64_t* d, const JoinPlan& p) {
+    if (p.seg_src.empty()) return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
+    return {nullptr, reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
 }
 
 Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
-    const bool trim = !p.seg_src.empty();
-    std::vector<int64_t> w = trim ? join_trim_table_words(p) : join_table_words(p, nullptr);
+    std::vector<int64_t> w = join_table_words(p);
     const bool moved = !join_tab_ || w.size() > join_tab_cap_;
     int64_t* d = out_grow(*this, join_tab_, join_tab_cap_, w.size());
     if (moved || w != join_tab_host_) {  // later fetches of the same batch under the same join reuse the upload
         join_tab_host_ = std::move(w);
         STN_HIP(hipMemcpyAsync(d, join_tab_host_.data(), join_tab_host_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
-    if (trim) return {nullptr, reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
-    return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
+    return join_tables_at(d, p);
 }
 
 void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride) {
-    const char* saved = stage_;
-    stage_ = "out";
-    if (prof_on_) prof_begin("join", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + enc_bytes(enc)));
-    if (t.tseg) launch_join_trim_rows(s_, x, src_stride, t.tseg, t.prog, p.G, p.W_join, g, t.fade, enc, y, dst_stride);
-    else launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
-    if (prof_on_) prof_end();
-    stage_ = saved;
+    {
+        StageSpan span(*this, "out", "join", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + enc_bytes(enc)));
+        if (t.tseg) launch_join_trim_rows(s_, x, src_stride, t.tseg, t.prog, p.G, p.W_join, g, t.fade, enc, y, dst_stride);
+        else launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
+    }
     STN_HIP(hipGetLastError());
 }
 
@@ -720,7 +700,7 @@ const float* Engine::join_f32(const JoinPlan& p) {
     const size_t off = resample_on() ? join_f32_offset((size_t)b.B * Wo) : 0;
     float* base = out_f32_buf(off + (size_t)p.G * p.W_join);  // (sized once: out_source below then finds room and moves nothing)
     const float* src = out_source(Wo);
-    join_enqueue(src, resample_on() ? Wo : (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor, join_tables(p), p, nullptr, ENC_F32, base + off, p.W_join);
+    join_enqueue(src, resample_on() ? Wo : native_row_len(), join_tables(p), p, nullptr, ENC_F32, base + off, p.W_join);
     return base + off;
 }
 
@@ -740,18 +720,16 @@ void Engine::enqueue_joined(const OutRows& o) {
     const Batch& b = bt_;
     const JoinPlan& p = *o.join;
     const int eb = need_enc(o.enc);
-    const int64_t Wo = out_row_len(), W = (int64_t)b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    const int64_t Wo = out_row_len(), W = native_row_len();
     if (o.stride < p.W_join) throw std::invalid_argument("dst_stride smaller than the joined length W_join = " + std::to_string(p.W_join));
     if (p.W_join == 0) return;
     if (loudness_on() && o.scope == STN_JOIN_GAIN_PROG) {
         const float* joined = join_f32(p);
         const float* g = join_measure(p, joined, true) + 2 * (int64_t)p.G;
-        const char* saved = stage_;
-        stage_ = "out";
-        if (prof_on_) prof_begin("loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
-        launch_store_rows(s_, joined, p.G, p.W_join, g, o.enc, o.dst, o.stride);
-        if (prof_on_) prof_end();
-        stage_ = saved;
+        {
+            StageSpan span(*this, "out", "loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
+            launch_store_rows(s_, joined, p.G, p.W_join, g, o.enc, o.dst, o.stride);
+        }
         STN_HIP(hipGetLastError());
         return;
     }
@@ -795,12 +773,8 @@ void Engine::batch_copy_joined_device(const stn_join* j, int enc, void* dst, int
 
 void Engine::batch_join_loudness(const stn_join* j, float* lufs, float* peak, float* gain) {
     const JoinPlan p = batch_join_plan(j);
-    const size_t G = (size_t)p.G;
     if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
-    const float* res = join_measure(p, join_f32(p), lo_on_);
-    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, G * 4, hipMemcpyDeviceToHost, s_));
-    if (peak) STN_HIP(hipMemcpyAsync(peak, res + G, G * 4, hipMemcpyDeviceToHost, s_));
-    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * G, G * 4, hipMemcpyDeviceToHost, s_));
+    lo_read_back(join_measure(p, join_f32(p), lo_on_), (size_t)p.G, lufs, peak, gain);
     sync();
 }
 
@@ -826,11 +800,11 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
     const size_t nx = (size_t)rows * W, ny = (size_t)p.G * p.W_join;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     void* dy = ar_.alloc(ny * eb);
-    const std::vector<int64_t> words = join_table_words(p, nullptr);
+    const std::vector<int64_t> words = join_table_words(p);
     int64_t* dt = static_cast<int64_t*>(ar_.alloc(words.size() * sizeof(int64_t)));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dt, words.data(), words.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    const JoinTables t{reinterpret_cast<const JoinSeg*>(dt), reinterpret_cast<const JoinProg*>(dt + (size_t)rows * 3)};
+    const JoinTables t = join_tables_at(dt, p);
     if (!measure) {
         join_enqueue(dx, W, t, p, nullptr, enc, dy, p.W_join);
     } else {
@@ -840,10 +814,7 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
         lo_n_.clear();  // (op_lo_'s rows, not the batch's)
         launch_store_rows(s_, dj, p.G, p.W_join, res + 2 * (size_t)p.G, enc, dy, p.W_join);
         STN_HIP(hipGetLastError());
-        const size_t G = (size_t)p.G;
-        if (prog_lufs) STN_HIP(hipMemcpyAsync(prog_lufs, res, G * 4, hipMemcpyDeviceToHost, s_));
-        if (prog_peak) STN_HIP(hipMemcpyAsync(prog_peak, res + G, G * 4, hipMemcpyDeviceToHost, s_));
-        if (prog_gain) STN_HIP(hipMemcpyAsync(prog_gain, res + 2 * G, G * 4, hipMemcpyDeviceToHost, s_));
+        lo_read_back(res, (size_t)p.G, prog_lufs, prog_peak, prog_gain);
     }
     STN_HIP(hipMemcpyAsync(y, dy, ny * eb, hipMemcpyDeviceToHost, s_));
     sync();

@@ -125,18 +125,15 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo) {
     ed_n_.resize((size_t)b.B);
     for (int i = 0; i < b.B; ++i) ed_n_[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
     STN_HIP(hipMemcpyAsync(sc.n, ed_n_.data(), ed_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    const char* saved = stage_;
-    stage_ = "out";
-    const double samples = (double)b.B * Wo;
-    const double chunks = (double)b.B * ed_chunks(Wo);
-    if (prof_on_) prof_begin("edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
-    launch_edges_frames(s_, x, b.B, Wo, sc.n, hz, sc.pa, sc.pb);
-    if (prof_on_) prof_end();
-    if (prof_on_) prof_begin("edges_rows", chunks, chunks * 8 + (double)b.B * edges_frames(Wo, hz) * 16);
-    launch_edges_rows(s_, b.B, Wo, sc.n, hz, (double)st_db_, silence_samples(hz, st_keep_), silence_samples(hz, st_fade_), sc.pa, sc.pb, sc.lev, sc.edges,
-                      sc.seg, sc.prog);
-    if (prof_on_) prof_end();
-    stage_ = saved;
+    {
+        const double samples = (double)b.B * Wo;
+        const double chunks = (double)b.B * ed_chunks(Wo);
+        StageSpan span(*this, "out", "edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
+        launch_edges_frames(s_, x, b.B, Wo, sc.n, hz, sc.pa, sc.pb);
+        span.next("edges_rows", chunks, chunks * 8 + (double)b.B * edges_frames(Wo, hz) * 16);
+        launch_edges_rows(s_, b.B, Wo, sc.n, hz, (double)st_db_, silence_samples(hz, st_keep_), silence_samples(hz, st_fade_), sc.pa, sc.pb, sc.lev,
+                          sc.edges, sc.seg, sc.prog);
+    }
     STN_HIP(hipGetLastError());
     ed_key_ = key;
     ed_valid_ = true;
@@ -227,7 +224,7 @@ void Engine::dbg_batch_set_wav(const float* wav) {
     const int64_t Wo = out_row_len();  // (throws without a finished batch)
     (void)Wo;
     const Batch& b = bt_;
-    const size_t n = (size_t)b.B * b.L * a_.base_chunk_size * a_.chunk_compress_factor;
+    const size_t n = (size_t)b.B * native_row_len();
     sync();
     STN_HIP(hipMemcpy(b.wav, wav, n * sizeof(float), hipMemcpyHostToDevice));
     ++ed_seq_;

@@ -138,24 +138,23 @@ Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
 }
 
 void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling) {
-    const char* saved = stage_;
-    stage_ = "out";
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
-    auto span = [&](double flops, double bytes) { if (prof_on_) prof_begin("loudness", flops, bytes); };
-    auto done = [&]() { if (prof_on_) prof_end(); STN_HIP(hipGetLastError()); };
-    span(20.0 * samples, samples * 4 + chunks * 20);
+    StageSpan span(*this, "out", "loudness", 20.0 * samples, samples * 4 + chunks * 20);
+    auto next = [&](double flops, double bytes) { STN_HIP(hipGetLastError()); span.next("loudness", flops, bytes); };  // (the launch before it is checked)
     launch_loudness_chunks(s_, false, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
-    done();
-    span(chunks * 32.0 * 11, chunks * 32);
+    next(chunks * 32.0 * 11, chunks * 32);
     launch_loudness_scan(s_, rows, W, sc.n, t, sc.st);
-    done();
-    span(22.0 * samples, samples * 4 + chunks * 24);
+    next(22.0 * samples, samples * 4 + chunks * 24);
     launch_loudness_chunks(s_, true, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
-    done();
-    span(chunks * 2, chunks * 12 + (double)rows * 12);
+    next(chunks * 2, chunks * 12 + (double)rows * 12);
     launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, target, ceiling, sc.res);
-    done();
-    stage_ = saved;
+    STN_HIP(hipGetLastError());
+}
+
+void Engine::lo_read_back(const float* res, size_t n, float* lufs, float* peak, float* gain) {
+    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, n * 4, hipMemcpyDeviceToHost, s_));
+    if (peak) STN_HIP(hipMemcpyAsync(peak, res + n, n * 4, hipMemcpyDeviceToHost, s_));
+    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * n, n * 4, hipMemcpyDeviceToHost, s_));
 }
 
 float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
@@ -188,11 +187,7 @@ float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t
 
 void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
     const int64_t Wo = out_row_len();
-    const float* res = lo_batch(out_source(Wo), Wo, lo_on_);
-    const size_t B = (size_t)bt_.B;
-    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, B * 4, hipMemcpyDeviceToHost, s_));
-    if (peak) STN_HIP(hipMemcpyAsync(peak, res + B, B * 4, hipMemcpyDeviceToHost, s_));
-    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * B, B * 4, hipMemcpyDeviceToHost, s_));
+    lo_read_back(lo_batch(out_source(Wo), Wo, lo_on_), (size_t)bt_.B, lufs, peak, gain);
     sync();
 }
 
@@ -216,8 +211,7 @@ void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t*
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     lo_n_.clear();  // (the batch's lengths are no longer there)
     lo_measure(op_lo_, dx, rows, W, sc, max_seg, false, lo_target_, lo_ceiling_);
-    if (lufs) STN_HIP(hipMemcpyAsync(lufs, sc.res, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
-    if (peak) STN_HIP(hipMemcpyAsync(peak, sc.res + rows, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    lo_read_back(sc.res, (size_t)rows, lufs, peak, nullptr);
     sync();
 }
 

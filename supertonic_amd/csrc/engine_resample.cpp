@@ -112,15 +112,11 @@ int64_t Engine::out_len(int64_t W) const {
 
 void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, int enc, void* y, int64_t dst_stride) {
     static const char* const names[] = {"resample", "resample_pcm16", "resample_pcm24", "resample_mulaw", "resample_alaw"};
-    const char* saved = stage_;
-    stage_ = "out";
-    if (prof_on_) {
+    {
         const double n_out = (double)rows * resample_out_len(W, t.P, t.Q);
-        prof_begin(names[enc >= ENC_F32 && enc <= ENC_ALAW ? enc : 0], 2.0 * n_out * t.T, (double)rows * W * 4 + n_out * enc_bytes(enc));
+        StageSpan span(*this, "out", names[enc >= ENC_F32 && enc <= ENC_ALAW ? enc : 0], 2.0 * n_out * t.T, (double)rows * W * 4 + n_out * enc_bytes(enc));
+        launch_resample(s_, x, rows, W, t, enc, y, dst_stride);
     }
-    launch_resample(s_, x, rows, W, t, enc, y, dst_stride);
-    if (prof_on_) prof_end();
-    stage_ = saved;
     STN_HIP(hipGetLastError());
 }
 

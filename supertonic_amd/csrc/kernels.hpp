@@ -406,6 +406,19 @@ enum OutEnc : int { ENC_F32 = 0, ENC_PCM16 = 1, ENC_PCM24 = 2, ENC_MULAW = 3, EN
 constexpr int enc_bytes(int enc) {
     return enc == ENC_F32 ? 4 : enc == ENC_PCM16 ? 2 : enc == ENC_PCM24 ? 3 : (enc == ENC_MULAW || enc == ENC_ALAW) ? 1 : 0;
 }
+// An encoding as a template argument: calls fn with std::integral_constant<int, ENC_*>; any other value throws "<who>: unknown encoding <n>".
+// In the callee: constexpr int kEnc = decltype(tag)::value.
+template <typename Fn>
+inline void with_enc(int enc, const char* who, Fn&& fn) {
+    switch (enc) {
+        case ENC_F32: fn(std::integral_constant<int, ENC_F32>{}); break;
+        case ENC_PCM16: fn(std::integral_constant<int, ENC_PCM16>{}); break;
+        case ENC_PCM24: fn(std::integral_constant<int, ENC_PCM24>{}); break;
+        case ENC_MULAW: fn(std::integral_constant<int, ENC_MULAW>{}); break;
+        case ENC_ALAW: fn(std::integral_constant<int, ENC_ALAW>{}); break;
+        default: throw std::invalid_argument(std::string(who) + ": unknown encoding " + std::to_string(enc));
+    }
+}
 // The final store of every fetch (the output stage, engine_batch.cpp): rows x W fp32 (row stride W), times g[row] when g (device [rows])
 // is not null, to y + row * dst_stride samples (dst_stride >= W) in encoding enc: fp32, int16 PCM by writeWavFile's rule (pcm16,
 // kernels_dev.hpp: int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987), 24-bit PCM, or G.711 mu-law / A-law of the

@@ -1,5 +1,6 @@
 // kernels_output.hip — the end of every fetch (gfx950, wave64): the one store (store_rows_kernel: fp32 or an encoding, with or without a gain) and
-// the GPU join of long-form chunks (join_rows_kernel; join_trim_rows_kernel from trimmed, faded sources).  The per-sample encoding rules are the device functions of kernels_dev.hpp.
+// the GPU join of long-form chunks: one walk (join_walk) behind two entry points, join_rows_kernel and, from trimmed, faded sources,
+// join_trim_rows_kernel.  The per-sample encoding rules are the device functions of kernels_dev.hpp.
 #include "kernels.hpp"
 #include "kernels_dev.hpp"
 
@@ -92,15 +93,7 @@ void launch_store_rows_t(hipStream_t s, const float* x, int64_t rows, int64_t W,
     else STN_KLAUNCH((store_rows_kernel<1, false, kEnc>), grid, dim3(256), 0, s, x, W, nv, g, y, dst_stride);
 }
 void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride) {
-    unsigned char* d = static_cast<unsigned char*>(y);
-    switch (enc) {
-        case ENC_F32: launch_store_rows_t<ENC_F32>(s, x, rows, W, g, d, dst_stride); break;
-        case ENC_PCM16: launch_store_rows_t<ENC_PCM16>(s, x, rows, W, g, d, dst_stride); break;
-        case ENC_PCM24: launch_store_rows_t<ENC_PCM24>(s, x, rows, W, g, d, dst_stride); break;
-        case ENC_MULAW: launch_store_rows_t<ENC_MULAW>(s, x, rows, W, g, d, dst_stride); break;
-        case ENC_ALAW: launch_store_rows_t<ENC_ALAW>(s, x, rows, W, g, d, dst_stride); break;
-        default: throw std::invalid_argument("store_rows: unknown encoding " + std::to_string(enc));
-    }
+    with_enc(enc, "store_rows", [&](auto e) { launch_store_rows_t<decltype(e)::value>(s, x, rows, W, g, static_cast<unsigned char*>(y), dst_stride); });
 }
 
 // The join of a fetch: programme p's output row is its members' segments with gaps between them,
@@ -116,104 +109,30 @@ void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, c
 constexpr int JOIN_WG = 256;
 typedef float join_f4 __attribute__((ext_vector_type(4), aligned(4)));  // four floats at a dword-aligned address
 
-template <int V, int T, bool kGain, int kEnc>
-__global__ void __launch_bounds__(JOIN_WG) join_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSeg* __restrict__ seg,
-                                                            const JoinProg* __restrict__ prog, const float* __restrict__ g, int64_t Wj,
-                                                            unsigned char* __restrict__ y, int64_t dst_stride) {
-    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG];
+// The walk behind both entry points.  kTrim (the join from trimmed sources): a member's samples start at its
+// source offset seg[m].src, and its cut edges are faded by the window `fade` in global memory: a vector that meets a fade takes the
+// per-sample path.  A delivered sample is ((x * g) * w_in) * w_out, each multiply only where it applies.  The entry points declare the
+// LDS arrays (s_src and s_fade: the trimmed one only, null otherwise).
+template <int V, int T, bool kGain, int kEnc, bool kTrim>
+__device__ __forceinline__ void join_walk(const float* __restrict__ x, int64_t src_stride,
+                                          const std::conditional_t<kTrim, JoinSegT, JoinSeg>* __restrict__ seg, const JoinProg* __restrict__ prog,
+                                          const float* __restrict__ g, const float* __restrict__ fade, int64_t Wj, unsigned char* __restrict__ y,
+                                          int64_t dst_stride, int64_t* s_dst, int64_t* s_len, int64_t* s_row, int64_t* s_src, int2* s_fade) {
     const int p = blockIdx.y, tid = threadIdx.x;
     const JoinProg pg = prog[p];
-    const JoinSeg* __restrict__ ps = seg + pg.first;
-    const int64_t t0 = (int64_t)blockIdx.x * (JOIN_WG * V * T);
-    const int k = t0 < pg.len ? pg.count : 0;  // (a tile behind the programme's end is padding: no member to find)
-    if (tid < k) { s_dst[tid] = ps[tid].dst; s_len[tid] = ps[tid].len; s_row[tid] = ps[tid].row; }
-    __syncthreads();
-    auto dst_of = [&](int r) { return r < JOIN_WG ? s_dst[r] : ps[r].dst; };
-    auto len_of = [&](int r) { return r < JOIN_WG ? s_len[r] : ps[r].len; };
-    auto row_of = [&](int r) { return r < JOIN_WG ? s_row[r] : ps[r].row; };
-    float v[T][V];
-    // all T vectors are loaded before the first is stored: the loads of a thread are in flight together
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;  // this vector's first output sample
-        if (o >= Wj) break;
-        int r = 0;
-        for (int hi = k; r < hi;) {  // the first member that ends behind o (the ends ascend)
-            const int mid = (r + hi) >> 1;
-            if (dst_of(mid) + len_of(mid) <= o) r = mid + 1; else hi = mid;
-        }
-        const int64_t d0 = r < k ? dst_of(r) : 0, l0 = r < k ? len_of(r) : 0;
-        if (r < k && o >= d0 && o + V <= d0 + l0) {  // the whole vector inside one segment
-            const int64_t row = row_of(r);
-            const float* __restrict__ src = x + row * src_stride + (o - d0);
-            if constexpr (V >= 4) {
-#pragma unroll
-                for (int j = 0; j < V / 4; ++j) {
-                    const join_f4 a = reinterpret_cast<const join_f4*>(src)[j];
-                    v[i][4 * j] = a.x; v[i][4 * j + 1] = a.y; v[i][4 * j + 2] = a.z; v[i][4 * j + 3] = a.w;
-                }
-            } else {
-                v[i][0] = src[0];
-            }
-            if constexpr (kGain) {
-                const float s = g[row];
-#pragma unroll
-                for (int j = 0; j < V; ++j) v[i][j] *= s;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const int64_t oj = o + j;
-                while (r < k && dst_of(r) + len_of(r) <= oj) ++r;
-                float t = 0.f;
-                if (r < k && oj >= dst_of(r)) {
-                    const int64_t row = row_of(r);
-                    t = x[row * src_stride + (oj - dst_of(r))];
-                    if constexpr (kGain) t *= g[row];
-                }
-                v[i][j] = t;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-        const int64_t o = t0 + ((int64_t)i * JOIN_WG + tid) * V;
-        if (o >= Wj) break;
-        const int64_t e = (int64_t)p * dst_stride + o;
-        if (V == 1 || o + V <= Wj) {
-            enc_store_vec<V, kEnc>(y, e, v[i]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-                if (o + j < Wj) enc_store1<kEnc>(y, e + j, v[i][j]);
-        }
-    }
-}
-// The join from trimmed sources: join_rows_kernel's walk, as a kernel of its own so that the instantiations above
-// keep their code.  A member's samples start at its source offset seg[m].src, and its cut edges are faded by the window `fade` in global
-// memory: a vector that meets a fade takes the per-sample path.  Members past JOIN_WG are read from the table, as above.
-template <int V, int T, bool kGain, int kEnc>
-__global__ void __launch_bounds__(JOIN_WG) join_trim_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSegT* __restrict__ seg,
-                                                                 const JoinProg* __restrict__ prog, const float* __restrict__ g,
-                                                                 const float* __restrict__ fade, int64_t Wj, unsigned char* __restrict__ y,
-                                                                 int64_t dst_stride) {
-    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG], s_src[JOIN_WG];
-    __shared__ int2 s_fade[JOIN_WG];  // (samples faded at the head, at the tail)
-    const int p = blockIdx.y, tid = threadIdx.x;
-    const JoinProg pg = prog[p];
-    const JoinSegT* __restrict__ ps = seg + pg.first;
+    const auto* __restrict__ ps = seg + pg.first;
     const int64_t t0 = (int64_t)blockIdx.x * (JOIN_WG * V * T);
     const int k = t0 < pg.len ? pg.count : 0;  // (a tile behind the programme's end is padding: no member to find)
     if (tid < k) {
         s_dst[tid] = ps[tid].dst; s_len[tid] = ps[tid].len; s_row[tid] = ps[tid].row;
-        s_src[tid] = ps[tid].src; s_fade[tid] = make_int2(ps[tid].fin, ps[tid].fout);
+        if constexpr (kTrim) { s_src[tid] = ps[tid].src; s_fade[tid] = make_int2(ps[tid].fin, ps[tid].fout); }
     }
     __syncthreads();
     auto dst_of = [&](int r) { return r < JOIN_WG ? s_dst[r] : ps[r].dst; };
     auto len_of = [&](int r) { return r < JOIN_WG ? s_len[r] : ps[r].len; };
     auto row_of = [&](int r) { return r < JOIN_WG ? s_row[r] : ps[r].row; };
-    auto src_of = [&](int r) { return r < JOIN_WG ? s_src[r] : ps[r].src; };
-    auto fade_of = [&](int r) { return r < JOIN_WG ? s_fade[r] : make_int2(ps[r].fin, ps[r].fout); };
+    auto src_of = [&](auto r) { return r < JOIN_WG ? s_src[r] : ps[r].src; };  // (these two are generic: instantiated under kTrim only)
+    auto fade_of = [&](auto r) { return r < JOIN_WG ? s_fade[r] : make_int2(ps[r].fin, ps[r].fout); };
     float v[T][V];
     // all T vectors are loaded before the first is stored: the loads of a thread are in flight together
 #pragma unroll
@@ -227,13 +146,16 @@ __global__ void __launch_bounds__(JOIN_WG) join_trim_rows_kernel(const float* __
         }
         const int64_t d0 = r < k ? dst_of(r) : 0, l0 = r < k ? len_of(r) : 0;
         bool whole = r < k && o >= d0 && o + V <= d0 + l0;  // the whole vector inside one segment
-        if (whole) {  // ... and clear of its faded edges
-            const int2 f = fade_of(r);
-            whole = o - d0 >= f.x && o - d0 + V <= l0 - f.y;
+        if constexpr (kTrim) {
+            if (whole) {  // ... and clear of its faded edges
+                const int2 f = fade_of(r);
+                whole = o - d0 >= f.x && o - d0 + V <= l0 - f.y;
+            }
         }
         if (whole) {
             const int64_t row = row_of(r);
-            const float* __restrict__ src = x + row * src_stride + src_of(r) + (o - d0);
+            const float* __restrict__ src = x + row * src_stride + (o - d0);
+            if constexpr (kTrim) src = x + row * src_stride + src_of(r) + (o - d0);
             if constexpr (V >= 4) {
 #pragma unroll
                 for (int j = 0; j < V / 4; ++j) {
@@ -257,12 +179,15 @@ __global__ void __launch_bounds__(JOIN_WG) join_trim_rows_kernel(const float* __
                 if (r < k && oj >= dst_of(r)) {
                     const int64_t row = row_of(r);
                     const int64_t q = oj - dst_of(r);  // the sample's place in its segment
-                    t = x[row * src_stride + src_of(r) + q];
+                    if constexpr (kTrim) t = x[row * src_stride + src_of(r) + q];
+                    else t = x[row * src_stride + q];
                     if constexpr (kGain) t *= g[row];
-                    const int2 f = fade_of(r);
-                    const int64_t back = len_of(r) - 1 - q;
-                    if (q < f.x) t *= fade[q];
-                    if (back < f.y) t *= fade[back];
+                    if constexpr (kTrim) {
+                        const int2 f = fade_of(r);
+                        const int64_t back = len_of(r) - 1 - q;
+                        if (q < f.x) t *= fade[q];
+                        if (back < f.y) t *= fade[back];
+                    }
                 }
                 v[i][j] = t;
             }
@@ -282,62 +207,58 @@ __global__ void __launch_bounds__(JOIN_WG) join_trim_rows_kernel(const float* __
         }
     }
 }
-template <int kEnc>
-void launch_join_rows_t(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
-                        unsigned char* y, int64_t dst_stride) {
-    constexpr int V = store_vec<kEnc>();
-    constexpr int T = V == 16 ? 2 : 4;  // vectors per thread: a workgroup's table lookup is paid once for 32 (fp32: 16) samples a thread
-    const bool vec = (G == 1 || dst_stride % V == 0) && !(reinterpret_cast<uintptr_t>(y) & 15);  // (every row's start 16-byte aligned)
-    const int64_t tile = (int64_t)JOIN_WG * T * (vec ? V : 1);
-    const dim3 grid((unsigned)((Wj + tile - 1) / tile), (unsigned)G);
-    if (vec && g) STN_KLAUNCH((join_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
-    else if (vec) STN_KLAUNCH((join_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
-    else if (g) STN_KLAUNCH((join_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
-    else STN_KLAUNCH((join_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+template <int V, int T, bool kGain, int kEnc>
+__global__ void __launch_bounds__(JOIN_WG) join_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSeg* __restrict__ seg,
+                                                            const JoinProg* __restrict__ prog, const float* __restrict__ g, int64_t Wj,
+                                                            unsigned char* __restrict__ y, int64_t dst_stride) {
+    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG];
+    join_walk<V, T, kGain, kEnc, false>(x, src_stride, seg, prog, g, nullptr, Wj, y, dst_stride, s_dst, s_len, s_row, nullptr, nullptr);
+}
+template <int V, int T, bool kGain, int kEnc>
+__global__ void __launch_bounds__(JOIN_WG) join_trim_rows_kernel(const float* __restrict__ x, int64_t src_stride, const JoinSegT* __restrict__ seg,
+                                                                 const JoinProg* __restrict__ prog, const float* __restrict__ g,
+                                                                 const float* __restrict__ fade, int64_t Wj, unsigned char* __restrict__ y,
+                                                                 int64_t dst_stride) {
+    __shared__ int64_t s_dst[JOIN_WG], s_len[JOIN_WG], s_row[JOIN_WG], s_src[JOIN_WG];
+    __shared__ int2 s_fade[JOIN_WG];  // (samples faded at the head, at the tail)
+    join_walk<V, T, kGain, kEnc, true>(x, src_stride, seg, prog, g, fade, Wj, y, dst_stride, s_dst, s_len, s_row, s_src, s_fade);
+}
+
+// both public launchers: Seg = JoinSeg (fade unused) or JoinSegT picks the entry point
+template <typename Seg>
+void launch_join(const char* who, hipStream_t s, const float* x, int64_t src_stride, const Seg* seg, const JoinProg* prog, int G, int64_t Wj,
+                 const float* g, const float* fade, int enc, void* yv, int64_t dst_stride) {
+    if (G <= 0 || Wj <= 0) return;
+    if (G > 65535) throw std::invalid_argument(std::string(who) + ": more than 65535 programmes");
+    if (dst_stride < Wj) throw std::invalid_argument(std::string(who) + ": dst_stride smaller than the joined row length");
+    unsigned char* y = static_cast<unsigned char*>(yv);
+    with_enc(enc, who, [&](auto e) {
+        constexpr int kEnc = decltype(e)::value;
+        constexpr int V = store_vec<kEnc>();
+        constexpr int T = V == 16 ? 2 : 4;  // vectors per thread: a workgroup's table lookup is paid once for 32 (fp32: 16) samples a thread
+        const bool vec = (G == 1 || dst_stride % V == 0) && !(reinterpret_cast<uintptr_t>(y) & 15);  // (every row's start 16-byte aligned)
+        const int64_t tile = (int64_t)JOIN_WG * T * (vec ? V : 1);
+        const dim3 grid((unsigned)((Wj + tile - 1) / tile), (unsigned)G);
+        if constexpr (std::is_same_v<Seg, JoinSegT>) {
+            if (vec && g) STN_KLAUNCH((join_trim_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
+            else if (vec) STN_KLAUNCH((join_trim_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
+            else if (g) STN_KLAUNCH((join_trim_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
+            else STN_KLAUNCH((join_trim_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
+        } else {
+            if (vec && g) STN_KLAUNCH((join_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+            else if (vec) STN_KLAUNCH((join_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+            else if (g) STN_KLAUNCH((join_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+            else STN_KLAUNCH((join_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, Wj, y, dst_stride);
+        }
+    });
 }
 void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
                       int enc, void* y, int64_t dst_stride) {
-    if (G <= 0 || Wj <= 0) return;
-    if (G > 65535) throw std::invalid_argument("join_rows: more than 65535 programmes");
-    if (dst_stride < Wj) throw std::invalid_argument("join_rows: dst_stride smaller than the joined row length");
-    unsigned char* d = static_cast<unsigned char*>(y);
-    switch (enc) {
-        case ENC_F32: launch_join_rows_t<ENC_F32>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
-        case ENC_PCM16: launch_join_rows_t<ENC_PCM16>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
-        case ENC_PCM24: launch_join_rows_t<ENC_PCM24>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
-        case ENC_MULAW: launch_join_rows_t<ENC_MULAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
-        case ENC_ALAW: launch_join_rows_t<ENC_ALAW>(s, x, src_stride, seg, prog, G, Wj, g, d, dst_stride); break;
-        default: throw std::invalid_argument("join_rows: unknown encoding " + std::to_string(enc));
-    }
-}
-
-template <int kEnc>
-void launch_join_trim_rows_t(hipStream_t s, const float* x, int64_t src_stride, const JoinSegT* seg, const JoinProg* prog, int G, int64_t Wj,
-                             const float* g, const float* fade, unsigned char* y, int64_t dst_stride) {
-    constexpr int V = store_vec<kEnc>();
-    constexpr int T = V == 16 ? 2 : 4;
-    const bool vec = (G == 1 || dst_stride % V == 0) && !(reinterpret_cast<uintptr_t>(y) & 15);
-    const int64_t tile = (int64_t)JOIN_WG * T * (vec ? V : 1);
-    const dim3 grid((unsigned)((Wj + tile - 1) / tile), (unsigned)G);
-    if (vec && g) STN_KLAUNCH((join_trim_rows_kernel<V, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
-    else if (vec) STN_KLAUNCH((join_trim_rows_kernel<V, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
-    else if (g) STN_KLAUNCH((join_trim_rows_kernel<1, T, true, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
-    else STN_KLAUNCH((join_trim_rows_kernel<1, T, false, kEnc>), grid, dim3(JOIN_WG), 0, s, x, src_stride, seg, prog, g, fade, Wj, y, dst_stride);
+    launch_join("join_rows", s, x, src_stride, seg, prog, G, Wj, g, nullptr, enc, y, dst_stride);
 }
 void launch_join_trim_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSegT* seg, const JoinProg* prog, int G, int64_t Wj,
                            const float* g, const float* fade, int enc, void* y, int64_t dst_stride) {
-    if (G <= 0 || Wj <= 0) return;
-    if (G > 65535) throw std::invalid_argument("join_trim_rows: more than 65535 programmes");
-    if (dst_stride < Wj) throw std::invalid_argument("join_trim_rows: dst_stride smaller than the joined row length");
-    unsigned char* d = static_cast<unsigned char*>(y);
-    switch (enc) {
-        case ENC_F32: launch_join_trim_rows_t<ENC_F32>(s, x, src_stride, seg, prog, G, Wj, g, fade, d, dst_stride); break;
-        case ENC_PCM16: launch_join_trim_rows_t<ENC_PCM16>(s, x, src_stride, seg, prog, G, Wj, g, fade, d, dst_stride); break;
-        case ENC_PCM24: launch_join_trim_rows_t<ENC_PCM24>(s, x, src_stride, seg, prog, G, Wj, g, fade, d, dst_stride); break;
-        case ENC_MULAW: launch_join_trim_rows_t<ENC_MULAW>(s, x, src_stride, seg, prog, G, Wj, g, fade, d, dst_stride); break;
-        case ENC_ALAW: launch_join_trim_rows_t<ENC_ALAW>(s, x, src_stride, seg, prog, G, Wj, g, fade, d, dst_stride); break;
-        default: throw std::invalid_argument("join_trim_rows: unknown encoding " + std::to_string(enc));
-    }
+    launch_join("join_trim_rows", s, x, src_stride, seg, prog, G, Wj, g, fade, enc, y, dst_stride);
 }
 
 }  // namespace stn

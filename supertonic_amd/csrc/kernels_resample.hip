@@ -112,15 +112,7 @@ void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, c
 }  // namespace
 
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride) {
-    unsigned char* d = static_cast<unsigned char*>(y);
-    switch (enc) {
-        case ENC_F32: launch_resample_t<ENC_F32>(s, x, rows, W, f, d, dst_stride); break;
-        case ENC_PCM16: launch_resample_t<ENC_PCM16>(s, x, rows, W, f, d, dst_stride); break;
-        case ENC_PCM24: launch_resample_t<ENC_PCM24>(s, x, rows, W, f, d, dst_stride); break;
-        case ENC_MULAW: launch_resample_t<ENC_MULAW>(s, x, rows, W, f, d, dst_stride); break;
-        case ENC_ALAW: launch_resample_t<ENC_ALAW>(s, x, rows, W, f, d, dst_stride); break;
-        default: throw std::invalid_argument("launch_resample: unknown encoding " + std::to_string(enc));
-    }
+    with_enc(enc, "launch_resample", [&](auto e) { launch_resample_t<decltype(e)::value>(s, x, rows, W, f, static_cast<unsigned char*>(y), dst_stride); });
 }
 
 }  // namespace stn

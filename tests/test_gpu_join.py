@@ -73,6 +73,27 @@ def test_op_is_the_host_join_of_the_encoded_rows(eng, enc, W):
 
 
 @pytest.mark.parametrize("enc", ENCS)
+def test_op_with_more_members_than_the_workgroup_stages(eng, enc):
+    """Programmes of more than JOIN_WG = 256 members: the members past the 256 a workgroup stages in LDS are read from the table.  300
+    rows of 64 samples as one programme join to 9-10 k samples, more than one tile of every encoding (8192 samples for the 8-bit ones),
+    so the search runs past member 256 both in a first tile and in a later one; [257, 43] has one such member, and rows 16 bytes apart
+    only by chance (the sample-by-sample store), [1] * 300 none.  Only join_rows_kernel can be driven there: the trimmed entry point's
+    ops are one member per programme, and a trimmed batch join would need more than 256 chunks.  Its walk past member 256 is the same
+    code (join_walk, kernels_output.hip), and is covered here only through that."""
+    B, W = 300, 64
+    rng = np.random.default_rng(300 + ENCS.index(enc))  # (other rows and lengths for every encoding)
+    x, n = _op_rows(W, B, rng)
+    rows_enc = eng.op_encode(x, enc)
+    dur = np.zeros(B, np.float32)
+    for groups, gaps in itertools.product(([B], [257, 43], [1] * B), (0, 1, 3)):
+        G = len(groups)
+        gap = [gaps] * G
+        want = join_ref.padded(join_ref.join(rows_enc, n, groups, gap, ZERO[enc]), max(1, join_ref.plan(groups, gap, [0.0] * G, n, dur, 8000)["W_join"]), ZERO[enc])
+        got = eng.op_join(x, n, groups, gap, 8000, encoding=enc)
+        assert _same(got, want), (enc, groups[:2], gaps, np.flatnonzero((got != want).reshape(G, -1).any(0))[:8])
+
+
+@pytest.mark.parametrize("enc", ENCS)
 def test_device_copy_touches_nothing_outside_the_joined_rows(enc):
     """a sentinel-filled device buffer with dst_stride > W_join, even and odd: only [G][W_join] is written"""
     from hip_util import DeviceBuffer
