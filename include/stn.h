@@ -338,7 +338,8 @@ int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const
  * Loudness L_b: ITU-R BS.1770-4 integrated loudness of one channel: K-weighting (shelf, then high-pass; stn_kweighting_filter), 400 ms
  * blocks at a 100 ms hop of (rate + 5) / 10 samples (whole blocks inside the span only), absolute gate -70 LUFS, relative gate -10 LU;
  * -inf when the span is shorter than one block or every block is gated out.
- * Gain g_b = min(10^((target - L_b) / 20), 10^(ceiling / 20) / peak_b), peak_b = max |x| over the span; 1 when L_b is -inf.  The fp32
+ * Gain g_b = min(10^((target - L_b) / 20), 10^(ceiling / 20) / peak_b), peak_b = max |x| over the span; 1 when L_b is -inf (with the
+ * limiter on, "limiter" below, the first operand alone: the limiter then enforces the ceiling).  The fp32
  * output is x * g_b (one fp32 multiply); the PCM output is that product converted as writeWavFile converts.  A row's L_b, peak_b and
  * g_b depend on its first n_b samples and the rate only (fixed-order sums, no atomics): not on the batch it was in.
  * The latent geometry, the durations, stn_batch_wav_device_ptr (model rate, not normalized) and the captured pipeline are unchanged:
@@ -404,6 +405,47 @@ int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_
 /* diagnostic: overwrite the finished batch's model-rate waveform with wav [B][L * chunk] (host; what stn_batch_dims reports at the model's
  * rate) and forget every fetch-time measurement cached for it.  For tests that need rows with known silences. */
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav);
+
+/* ---- limiter -----------------------------------------------------------------------------------------
+ * A look-ahead peak limiter behind the loudness gain.  With the limiter on AND loudness on, the ceiling of stn_set_loudness is enforced
+ * by the limiter and no longer by capping the gain: a row gets the full loudness gain, and only the few milliseconds around a sample
+ * above the ceiling are turned down, smoothly, so that nothing exceeds it.  With loudness off the setting has no effect and adds no
+ * launch.  It composes with the rate, the encoding, the trimming and the join; the latent geometry, the reported durations,
+ * stn_batch_wav_device_ptr, the captured pipeline and the graph key are untouched, and toggling it drops or re-captures no graph.
+ * For a row at the output rate hz: n its span (the loudness span n_b), g = 10^((target - L) / 20) the UNCAPPED gain (1 when L is -inf),
+ * c = float32(10^(ceiling / 20)), A = (int64_t)(lookahead_ms * hz / 1000 + 0.5) (in double), and
+ *   v[i] = x[i] * g (one fp32 multiply);
+ *   r[j] = 1 where |v[j]| <= c, else c / |v[j]| (one fp32 divide), for 0 <= j < n; r[j] = 1 outside [0, n);
+ *   m[i] = min r[i .. i+A],  M[i] = min r[i-A .. i+A];
+ *   w[k] = 0.5 - 0.5 cos(2 pi (k + 1) / (A + 2)), k = 0 .. A, normalized to sum 1 in double, stored as fp32 (stn_limiter_window);
+ *   s[i] = 1 exactly when M[i] == 1; otherwise s[i] = min(sum_k w[k] m[i-k], r[i], 1 - 2^-24), the sum in fp32 in an order fixed by
+ *   the sample's position (every m[i-k] covers sample i, so s[i] <= r[i]; the last operand keeps s < 1 wherever M < 1 when the sum
+ *   rounds to 1); the sum is within (A + 8) * 2^-24 of its exact value;
+ *   y[i] = clamp(v[i] * s[i], -c, c) for i < n, and clamp(v[i], -c, c) for the padding i >= n;
+ * then the trim fades and the encoding's rule as without it.  So |y| <= c exactly for every delivered fp32 sample; a row with
+ * g * peak <= c is byte for byte the loudness-only fetch (same g, s = 1); and a row's output depends on its first n samples, the rate
+ * and the parameters only, not on W, B or its neighbours (no float atomics).  The loudness of a limited row ends slightly under the
+ * target; that is reported (stn_batch_limiter), not iterated away.
+ * Trimmed rows: the limiter runs on the untrimmed span, as the gain measurement does; with fade_ms = 0 a trimmed row stays a slice of
+ * the untrimmed fetch.  Joined fetches: with STN_JOIN_GAIN_ROW the segments are the limited rows; with STN_JOIN_GAIN_PROG the joined,
+ * faded fp32 signal is limited as G rows, each with its programme gain and span.  No host read is added, so the pipelined _begin stays
+ * asynchronous.  While the limiter is active stn_batch_loudness and stn_batch_join_loudness report the gain actually applied, the
+ * uncapped one.  DESIGN.md section 15 has the decomposition and the cost. */
+/* on = 0: off (the default: every fetch is byte for byte the one without it, with no extra launch or allocation).  lookahead_ms in
+ * [0.5, 10]; out of range: STN_ERR_INVALID with a message, and the previous setting stays in force. */
+int stn_set_limiter(stn_handle* h, int on, float lookahead_ms);
+int stn_get_limiter(const stn_handle* h, int* on, float* lookahead_ms);
+/* the finished batch as the current setting limits it: per row the deepest reduction -20 log10(min s) in dB and the number of samples
+ * of the span with M < 1 (both 0 while the limiter or loudness is off); each pointer [B] or NULL */
+int stn_batch_limiter(stn_handle* h, float* reduction_db, int64_t* limited);
+/* op-level: rows x W fp32 (host) at hz in [8000, 192000]; row r's first n[r] samples (n_or_null = NULL: all W) times gain_or_null[r]
+ * (NULL: 1) limited to ceiling_dbfs in [-30, 0] -> y and the curve s, [rows][W] floats each (s_or_null may be NULL), reduction_db and
+ * limited [rows] (either may be NULL).  1 <= rows <= 65535. */
+int stn_op_limiter(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, const float* gain_or_null,
+                   float ceiling_dbfs, float lookahead_ms, float* y, float* s_or_null, float* reduction_db, int64_t* limited);
+/* the weights at hz (host only, no device needed): *n = A + 1, and w[0 .. min(A + 1, cap)) when w is not NULL; STN_ERR_INVALID when
+ * lookahead_ms is outside [0.5, 10] or hz outside [8000, 192000] */
+int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_t* n);
 
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);

@@ -311,6 +311,12 @@ def load():
     L.stn_op_silence_edges.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, vp, vp]
     L.stn_op_silence_trim.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, vp, ci, vp, vp, vp]
     L.stn_silence_fade_window.argtypes = [ci, cf, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_set_limiter.argtypes = [vp, ci, cf]
+    L.stn_get_limiter.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf)]
+    L.stn_batch_limiter.argtypes = [vp, vp, vp]
+    L.stn_op_limiter.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, cf, cf, vp, vp, vp, vp]
+    L.stn_limiter_window.argtypes = [ci, cf, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_group_set_limiter.argtypes = [vp, ci, cf]
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
@@ -411,6 +417,11 @@ class Group:
         on, t = _loudness_args(target_lufs)
         self._ck(self._lib.stn_group_set_loudness(self._g, on, t, float(ceiling_dbfs)))
 
+    def set_limiter(self, lookahead_ms=None):
+        """Look-ahead peak limiter of every rank (Engine.set_limiter): the gathered PCM is then limited row by row."""
+        on, ms = limiter_args(lookahead_ms)
+        self._ck(self._lib.stn_group_set_limiter(self._g, on, ms))
+
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
         self._ck(self._lib.stn_group_last_shards(self._g, rows, samples))
@@ -481,6 +492,39 @@ def silence_fade_window(hz, fade_ms):
     w = np.empty(n.value, np.float32)
     if L.stn_silence_fade_window(int(hz), float(fade_ms), w.ctypes.data, w.size, ctypes.byref(n)) < 0:
         raise StnError(-1, "stn_silence_fade_window failed")
+    return w
+
+
+LIMITER_MS = 5.0
+
+
+def limiter_args(lookahead_ms):
+    """A limiter argument -> (on, lookahead_ms) for stn_set_limiter: None or False = off, True = 5 ms, a number = the look-ahead in
+    milliseconds.  ValueError, with the ABI's range, for anything else."""
+    if lookahead_ms is None or lookahead_ms is False:
+        return 0, LIMITER_MS
+    if lookahead_ms is True:
+        return 1, LIMITER_MS
+    try:
+        ms = float(lookahead_ms)
+    except (TypeError, ValueError):
+        raise ValueError(f"limiter: None, True or a look-ahead in milliseconds, not {lookahead_ms!r}") from None
+    if not 0.5 <= ms <= 10.0:
+        raise ValueError(f"limiter look-ahead {ms} ms: must be in [0.5, 10]")
+    return 1, ms
+
+
+def limiter_window(hz, lookahead_ms=LIMITER_MS):
+    """The limiter's weights at hz (host only): float32 [A + 1], A = int(lookahead_ms * hz / 1000 + 0.5), a Hann window
+    0.5 - 0.5 cos(2 pi (k + 1) / (A + 2)) normalized to sum 1.  StnError when lookahead_ms is outside [0.5, 10] or hz outside
+    [8000, 192000]."""
+    L = load()
+    n = ctypes.c_int64()
+    if L.stn_limiter_window(int(hz), float(lookahead_ms), None, 0, ctypes.byref(n)) < 0:
+        raise StnError(-1, f"stn_limiter_window: {lookahead_ms} ms at {hz} Hz refused (lookahead_ms in [0.5, 10], hz in [8000, 192000])")
+    w = np.empty(n.value, np.float32)
+    if L.stn_limiter_window(int(hz), float(lookahead_ms), w.ctypes.data, w.size, ctypes.byref(n)) < 0:
+        raise StnError(-1, "stn_limiter_window failed")
     return w
 
 
@@ -834,6 +878,41 @@ class Engine:
                                                float(fade_ms), None if g is None else g.ctypes.data, e, y.ctypes.data, start.ctypes.data,
                                                end.ctypes.data))
         return y, start, end
+
+    def set_limiter(self, lookahead_ms=None):
+        """Look-ahead peak limiter behind the loudness gain: None = off (the default), True = 5 ms, or the look-ahead in milliseconds
+        ([0.5, 10]).  With loudness on, every row then gets the full loudness gain and only the milliseconds around a sample above the
+        ceiling are turned down; with loudness off it has no effect."""
+        on, ms = limiter_args(lookahead_ms)
+        self._ck(self._lib.stn_set_limiter(self._h, on, ms))
+
+    @property
+    def limiter(self):
+        """The look-ahead in milliseconds, or None when the limiter is off."""
+        on, ms = ctypes.c_int(), ctypes.c_float()
+        self._ck(self._lib.stn_get_limiter(self._h, ctypes.byref(on), ctypes.byref(ms)))
+        return ms.value if on.value else None
+
+    def batch_limiter(self):
+        """The finished batch as the current setting limits it -> (reduction_db [B] float32, limited [B] int64): the deepest reduction
+        of each row and the samples of its span that are turned down (zeros while the limiter or loudness is off)."""
+        B = self.batch_dims()[0]
+        red, lim = np.empty(B, np.float32), np.empty(B, np.int64)
+        self._ck(self._lib.stn_batch_limiter(self._h, red.ctypes.data, lim.ctypes.data))
+        return red, lim
+
+    def op_limiter(self, x, hz, n=None, gain=None, ceiling_dbfs=-1.0, lookahead_ms=LIMITER_MS):
+        """rows x W fp32 at hz on the GPU, row r's first n[r] samples (None: all W) times gain[r] (None: 1), limited to ceiling_dbfs ->
+        (y [rows, W], s [rows, W], reduction_db [rows], limited [rows])."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(n, np.int64)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        y, s = np.empty((rows, W), np.float32), np.empty((rows, W), np.float32)
+        red, lim = np.empty(rows, np.float32), np.empty(rows, np.int64)
+        self._ck(self._lib.stn_op_limiter(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, None if g is None else g.ctypes.data,
+                                          float(ceiling_dbfs), float(lookahead_ms), y.ctypes.data, s.ctypes.data, red.ctypes.data, lim.ctypes.data))
+        return y, s, red, lim
 
     def dbg_batch_set_wav(self, wav):
         """Diagnostic: overwrite the finished batch's model-rate waveform ([B, L * chunk] float32) for tests that need known silences."""

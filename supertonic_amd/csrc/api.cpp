@@ -369,6 +369,33 @@ int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_
         return STN_ERR_INVALID;
     }
 }
+int stn_set_limiter(stn_handle* h, int on, float lookahead_ms) {
+    STN_TRY(h, { h->eng->set_limiter(on != 0, lookahead_ms); })
+}
+int stn_get_limiter(const stn_handle* h, int* on, float* lookahead_ms) {
+    if (!h) return STN_ERR_INVALID;
+    h->eng->get_limiter(on, lookahead_ms);
+    return STN_OK;
+}
+int stn_batch_limiter(stn_handle* h, float* reduction_db, int64_t* limited) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_limiter(reduction_db, limited); })
+}
+int stn_op_limiter(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs,
+                   float lookahead_ms, float* y, float* s, float* reduction_db, int64_t* limited) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_limiter: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_limiter(hz, rows, W, x, n, gain, ceiling_dbfs, lookahead_ms, y, s, reduction_db, limited); })
+}
+int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_t* n) {
+    if (!stn::limiter_check(hz, lookahead_ms).empty()) return STN_ERR_INVALID;
+    try {
+        const std::vector<float> v = stn::limiter_window(hz, lookahead_ms);
+        if (n) *n = (int64_t)v.size();
+        if (w) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap < 0 ? 0 : cap, (int64_t)v.size()), w);
+        return STN_OK;
+    } catch (const std::exception&) {
+        return STN_ERR_INVALID;
+    }
+}
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav) {
     STN_TRY(h, { need(wav != nullptr, "wav is null"); need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->dbg_batch_set_wav(wav); })
 }

@@ -183,6 +183,7 @@ Engine::~Engine() {
     rs_release();
     lo_release();
     ed_release();
+    lm_release();
     if (out_f32_) (void)hipFree(out_f32_);
     if (out_enc_) (void)hipFree(out_enc_);
     if (join_tab_) (void)hipFree(join_tab_);

@@ -5,6 +5,7 @@
 // enqueued on that stream with no host round trip except the single read of the predicted durations that
 // sizes the latent (cpp/helper.cpp:430-438 needs max(duration) on the host too).
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -68,6 +69,12 @@ class Arena {
 std::string silence_check(float top_db, float keep_ms, float fade_ms);
 int64_t silence_samples(int hz, float ms);
 std::vector<float> silence_fade_window(int hz, float fade_ms);
+// The limiter's host arithmetic (engine_limiter.cpp): why (hz, lookahead_ms) is refused, or ""; the look-ahead A in samples at hz,
+// (int64)(ms * hz / 1000 + 0.5) in double; the A + 1 Hann weights 0.5 - 0.5 cos(2 pi (k + 1) / (A + 2)), normalized to sum 1 in
+// double, as float32
+std::string limiter_check(int hz, float lookahead_ms);
+int64_t limiter_samples(int hz, float lookahead_ms);
+std::vector<float> limiter_window(int hz, float lookahead_ms);
 
 struct KernelStat { double ms = 0; long launches = 0; double flops = 0; double bytes = 0; };
 
@@ -317,6 +324,21 @@ class Engine {
                          int enc, void* y, int64_t* start, int64_t* end);
     // diagnostic: overwrite the finished batch's model-rate waveform ([B][L * chunk] host floats) and forget what was measured on it
     void dbg_batch_set_wav(const float* wav);
+
+    // ---- limiter (engine_limiter.cpp; include/stn.h "limiter"): off is the default, and without loudness it
+    // has no effect (every fetch path is then exactly the one without it).  On with loudness on, the loudness gain is the uncapped
+    // 10^((target - L_b) / 20) and the ceiling is enforced by a look-ahead peak limiter (kernels_limiter.hip) that writes the limited
+    // fp32 rows into fetch scratch; the store and join kernels then run on those rows without a gain.
+    void set_limiter(bool on, float lookahead_ms);
+    bool limiter_active() const { return lm_on_ && lo_on_; }
+    void get_limiter(int* on, float* lookahead_ms) const;
+    // the finished batch as a fetch limits it: per row the deepest reduction in dB and the samples whose curve is below 1 (both 0
+    // while the limiter is not active); [B] host arrays or null
+    void batch_limiter(float* reduction_db, int64_t* limited);
+    // rows x W fp32 (host) at hz, row r's first n[r] samples (all W when n is null) times gain[r] (1 when null) -> y, s [rows][W]
+    // (host; s may be null), reduction_db, limited [rows] (host, or null)
+    void op_limiter(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
+                    float* s, float* reduction_db, int64_t* limited);
 
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
@@ -601,6 +623,20 @@ class Engine {
     EdScratch ed_batch(const float* x, int64_t Wo);
     const std::vector<int64_t>& ed_batch_host();  // its edges on the host (one device->host read of 2 B integers per batch and setting)
     void ed_release();
+    bool lm_on_ = false;
+    float lm_ms_ = 5.0f;
+    float lo_cap() const { return limiter_active() ? INFINITY : lo_ceiling_; }  // the gate's ceiling: the limiter enforces it instead
+    char* lm_buf_ = nullptr; size_t lm_buf_cap_ = 0;  // fetch-time scratch of the limiter (grow-only, outside the graph key)
+    struct LmScratch { float* y; int* pcnt; float* pmin; int64_t* limited; float* red; };
+    static size_t lm_layout(int64_t rows, int64_t W, size_t* o);  // the scratch's five offsets (o) and its size in bytes
+    static LmScratch lm_at(char* base, const size_t* o);
+    LmScratch lm_scratch(int64_t rows, int64_t W);
+    float* lm_win_ = nullptr; size_t lm_win_cap_ = 0; int lm_win_hz_ = 0; float lm_win_ms_ = -1.0f;  // the weights on the device, per (rate, ms)
+    const float* lm_window(int hz);
+    // rows x W fp32 on the device (x) whose spans the measurement just uploaded (lo_n_ptr_), times g (device [rows]), limited into the
+    // scratch: returns the rows (row stride W)
+    LmScratch lm_rows(const float* x, int64_t rows, int64_t W, const float* g);
+    void lm_release();
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
     // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
     // With a join plan the G programme rows of the plan instead of the B rows (scope: STN_JOIN_GAIN_*)

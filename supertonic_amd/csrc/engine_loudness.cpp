@@ -167,7 +167,7 @@ float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
         n[(size_t)i] = std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz));
         if (n[(size_t)i] < 0) n[(size_t)i] = 0;
     }
-    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_ceiling_);
+    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_cap());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
 }
 
 float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling) {

@@ -224,6 +224,12 @@ int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceilin
         const S* p = static_cast<const S*>(a);
         return stn_set_loudness(h, p->on, p->t, p->c); }, &v, 0);
 }
+int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms) {
+    struct S { int on; float ms; } v{on, lookahead_ms};
+    return for_all(g, "stn_set_limiter", [](stn_handle* h, const void* a, uint64_t) {
+        const S* p = static_cast<const S*>(a);
+        return stn_set_limiter(h, p->on, p->ms); }, &v, 0);
+}
 int stn_group_set_encoding(stn_group* g, int enc) {
     if (!g) return STN_ERR_INVALID;
     if (stn_encoding_bytes(enc) == 0) return fail(g, STN_ERR_INVALID, "stn_group_set_encoding: unknown encoding " + std::to_string(enc));

@@ -512,4 +512,19 @@ void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t*
                           const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res);
 // (the gain itself is applied by launch_store_rows with g = res + 2 * rows)
 
+// Look-ahead peak limiter behind the loudness gain (kernels_limiter.hip; the setting, the window and the scratch are engine_limiter.cpp;
+// DESIGN.md section 15).  rows x W fp32 (row stride W) with row spans n[rows] (device, <= W) and gains gain[rows] (device; null: 1) ->
+// y (rows x W fp32, row stride W, not x): row b times gain[b], turned down around every sample above c so that |y| <= c, the curve s
+// smoothed over A + 1 samples by the weights wts (device, A + 1 floats that sum to 1); behind n[b] the clamped product.  s_out (device
+// rows x W, or null): the curve.  Scratch (device): pcnt, pmin [rows][lm_tiles(W)].  Results (device [rows]): limited = samples of the
+// span whose curve is below 1, red = -20 log10 of the curve's minimum.  Two launches, the hand-off between them a launch boundary: the
+// tiles (x -> y, s_out, pcnt, pmin), then the per-row results (pcnt, pmin -> limited, red).
+constexpr int LM_WG = 256;            // lanes per workgroup
+constexpr int LM_TILE = 2048;         // samples of a row a workgroup owns (8 consecutive ones per lane)
+constexpr int LM_MAX_A = 1920;        // 10 ms at 192 kHz
+inline int64_t lm_tiles(int64_t W) { return (W + LM_TILE - 1) / LM_TILE; }
+void launch_limiter(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, const float* gain, float c, int A, const float* wts,
+                    float* y, float* s_out, int* pcnt, float* pmin);
+void launch_limiter_rows(hipStream_t s, int64_t rows, int64_t W, const int* pcnt, const float* pmin, int64_t* limited, float* red);
+
 }  // namespace stn
