@@ -357,6 +357,24 @@ int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, cons
 /* the K-weighting biquads at hz (host only, no device needed): b[3] and a[3] (a[0] = 1) of the shelf and of the high-pass, in double;
  * STN_ERR_INVALID outside [8000, 192000] Hz */
 int stn_kweighting_filter(int hz, double* shelf_b3, double* shelf_a3, double* hp_b3, double* hp_a3);
+/* The same measurement (the same four launches through the same launchers) with its scratch laid open (the kernel tests of every pass).
+ * n_or_null as stn_op_loudness; on / target_lufs / ceiling_dbfs: the gate's gain as stn_set_loudness defines it (on = 0: gain 1; not
+ * range-checked).  x_misalign 0 / 1: x is uploaded 16-byte aligned / 4 bytes off, which forces the scalar staging path at W % 4 == 0.
+ * Before the first launch the whole scratch (st, pk, pa, pb and the results) is filled with the quiet NaN 0x7FC00000, so an element no
+ * launch wrote comes back as that.  With Ks = (W + 31) / 32 chunks per row: st_end [rows][Ks][4], the state buffer as launch 1 left it
+ * (chunk k's end state (s1, s2, t1, t2) from zero state); st_start [rows][Ks][4], the same buffer after the scan (chunk k's true start
+ * state); pk, pa, pb [rows][Ks] (chunk k's max |x|, its sum of y^2 inside the 100 ms segment it starts in, and inside the next one);
+ * lufs, peak, gain [rows].  Every output may be NULL.  form: the staging path that ran, "vec" (16-byte loads) or "scalar",
+ * NUL-terminated, truncated to form_cap; may be NULL.  Refuses what stn_op_loudness refuses, and an x_misalign outside {0, 1}. */
+int stn_op_loudness_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, int on, float target_lufs,
+                       float ceiling_dbfs, int x_misalign, float* st_end, float* st_start, float* pk, float* pa, float* pb, float* lufs,
+                       float* peak, float* gain, char* form, size_t form_cap);
+/* what the measurement's kernels are given at hz (host only, no device needed): coef[10], the fp32 coefficients they multiply by (shelf
+ * b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2); mpow, the first min(cap, 1024 * 16) entries of the scan's power table [1024][4][4],
+ * entry i = M^(i+1) row-major with M = A^32 of the zero-input state transition A (state s1 s2 t1 t2) those coefficients define (the
+ * scan reads the table in double; here it is rounded to fp32); *hop, the 100 ms segment in samples.  Each pointer may be NULL.
+ * STN_ERR_INVALID outside [8000, 192000] Hz. */
+int stn_loudness_table(int hz, float* coef10, float* mpow, size_t cap, int* hop);
 
 /* ---- silence trimming --------------------------------------------------------------------------------
  * With trimming on, every fetch path delivers each row without the silence in front of and behind its speech, found by level on the

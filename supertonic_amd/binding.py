@@ -304,6 +304,8 @@ def load():
     L.stn_batch_loudness.argtypes = [vp, vp, vp, vp]
     L.stn_op_loudness.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp]
     L.stn_kweighting_filter.argtypes = [ci, _f64p, _f64p, _f64p, _f64p]
+    L.stn_op_loudness_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_loudness_table.argtypes = [ci, vp, vp, ctypes.c_size_t, ctypes.POINTER(ci)]
     L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
     L.stn_set_silence_trim.argtypes = [vp, ci, cf, cf, cf]
     L.stn_get_silence_trim.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf), ctypes.POINTER(cf), ctypes.POINTER(cf)]
@@ -454,6 +456,18 @@ def kweighting_filter(hz):
     if rc < 0:
         raise StnError(rc, f"stn_kweighting_filter: {hz} Hz is outside [8000, 192000] Hz")
     return tuple(out)
+
+
+def loudness_table(hz):
+    """What the loudness kernels are given at hz (host only): (coef float32 [10]: shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2;
+    mpow float32 [1024, 4, 4]: entry i = M^(i+1), M the zero-input state transition over one 32-sample chunk, the scan's double table
+    rounded to fp32; hop: samples per 100 ms).
+    StnError outside [8000, 192000] Hz."""
+    coef, mpow, hop = np.zeros(10, np.float32), np.zeros((1024, 4, 4), np.float32), ctypes.c_int()
+    rc = load().stn_loudness_table(int(hz), coef.ctypes.data, mpow.ctypes.data, mpow.size, ctypes.byref(hop))
+    if rc < 0:
+        raise StnError(rc, f"stn_loudness_table: {hz} Hz is outside [8000, 192000] Hz")
+    return coef, mpow, hop.value
 
 
 TRIM_KEEP_MS, TRIM_FADE_MS = 20.0, 5.0
@@ -833,6 +847,25 @@ class Engine:
         self._ck(self._lib.stn_op_loudness(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, lufs.ctypes.data,
                                            peak.ctypes.data))
         return lufs, peak
+
+    def op_loudness_ex(self, x, hz, n=None, on=False, target_lufs=-23.0, ceiling_dbfs=-1.0, x_misalign=0):
+        """op_loudness with its scratch laid open (poisoned with the quiet NaN 0x7FC00000 first) -> dict: st_end, st_start [rows, Ks, 4]
+        (chunk end states from zero state; true start states after the scan), pk, pa, pb [rows, Ks], lufs, peak, gain [rows], form
+        ("vec" / "scalar": the staging path that ran).  x_misalign = 1 uploads x 4 bytes off 16-byte alignment."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        Ks = (W + 31) // 32
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        o = dict(st_end=np.empty((rows, Ks, 4), np.float32), st_start=np.empty((rows, Ks, 4), np.float32))
+        o.update({k: np.empty((rows, Ks), np.float32) for k in ("pk", "pa", "pb")})
+        o.update({k: np.empty(rows, np.float32) for k in ("lufs", "peak", "gain")})
+        form = ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_loudness_ex(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, int(bool(on)), float(target_lufs),
+                                              float(ceiling_dbfs), int(x_misalign), *(o[k].ctypes.data for k in ("st_end", "st_start", "pk", "pa", "pb",
+                                                                                                                 "lufs", "peak", "gain")),
+                                              form, ctypes.sizeof(form)))
+        o["form"] = form.value.decode()
+        return o
 
     def set_silence_trim(self, trim_silence=None):
         """Trim leading and trailing silence of every fetch by level on the GPU: None = off (the default), top_db (frames more than

@@ -337,6 +337,16 @@ int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, cons
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness: bad argument (1 <= rows <= 65535, W >= 1, x)");
                  h->eng->op_loudness(hz, rows, W, x, n, lufs, peak); })
 }
+int stn_op_loudness_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, int on, float target_lufs, float ceiling_dbfs,
+                       int x_misalign, float* st_end, float* st_start, float* pk, float* pa, float* pb, float* lufs, float* peak, float* gain,
+                       char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness_ex: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 need(x_misalign == 0 || x_misalign == 1, "stn_op_loudness_ex: x_misalign must be 0 or 1");
+                 stn::Engine::LoProbe p;
+                 p.x_misalign = x_misalign; p.st_end = st_end; p.st_start = st_start; p.pk = pk; p.pa = pa; p.pb = pb;
+                 h->eng->op_loudness_ex(hz, rows, W, x, n, on != 0, target_lufs, ceiling_dbfs, p, lufs, peak, gain);
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
 int stn_set_silence_trim(stn_handle* h, int on, float top_db, float keep_ms, float fade_ms) {
     STN_TRY(h, { h->eng->set_silence_trim(on != 0, top_db, keep_ms, fade_ms); })
 }
@@ -408,6 +418,14 @@ int stn_kweighting_filter(int hz, double* shelf_b, double* shelf_a, double* hp_b
         if (hp_b) hp_b[i] = k.hp_b[i];
         if (hp_a) hp_a[i] = k.hp_a[i];
     }
+    return STN_OK;
+}
+int stn_loudness_table(int hz, float* coef10, float* mpow, size_t cap, int* hop) {
+    stn::LoudTable t;
+    if (!stn::loudness_design(hz, t).empty()) return STN_ERR_INVALID;
+    if (coef10) std::copy(t.coef.c, t.coef.c + 10, coef10);
+    if (mpow) for (size_t i = 0; i < std::min(cap, t.mpow.size()); ++i) mpow[i] = (float)t.mpow[i];
+    if (hop) *hop = t.hop;
     return STN_OK;
 }
 int stn_batch_fetch(stn_handle* h, float* wav, size_t cap, float* duration) {

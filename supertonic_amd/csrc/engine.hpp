@@ -307,6 +307,16 @@ class Engine {
     void batch_loudness(float* lufs, float* peak, float* gain);
     // rows x W fp32 (host) at hz, row r's first n[r] samples (all W when n is null) -> L, peak [rows] (host)
     void op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak);
+    // The same measurement with its scratch laid open (the kernel tests): the scratch is filled with the quiet NaN 0x7FC00000 first, x is
+    // uploaded 4 bytes off 16-byte alignment when x_misalign is set, and the whole per-chunk buffers come back (host, Ks = lo_chunks(W)):
+    // st_end [rows][Ks][4] as the first launch left it, st_start the same after the scan, pk / pa / pb [rows][Ks]; any may be null.
+    struct LoProbe {
+        int x_misalign = 0;
+        float *st_end = nullptr, *st_start = nullptr, *pk = nullptr, *pa = nullptr, *pb = nullptr;
+        const char* form = "";  // out: the staging path that ran
+    };
+    void op_loudness_ex(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe& probe,
+                        float* lufs, float* peak, float* gain);
 
     // ---- silence trimming (engine_edges.cpp; include/stn.h "silence trimming"): off is the default (every fetch
     // path is then exactly the one without it).  On, every fetch path finds row b's edges [start_b, end_b) by level at the output rate
@@ -597,8 +607,13 @@ class Engine {
     LoScratch lo_scratch(int64_t rows, int64_t W);
     void lo_prepare(LoudTable& t, int hz);
     void lo_release();
-    // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain]
-    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling);
+    // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain];
+    // st_end (host, or null): the state buffer as the first launch left it, copied out before the scan overwrites it
+    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
+                    float* st_end = nullptr);
+    // op_loudness and op_loudness_ex: the upload, the measurement, the read-back
+    void lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
+               float* peak, float* gain);
     // rows x W fp32 on the device (x) with row spans n measured on the stream against table t: returns res (device [3][rows]: L, peak,
     // gain).  n is uploaded only when it differs from what the scratch holds.
     float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling);

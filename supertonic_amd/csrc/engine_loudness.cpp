@@ -38,7 +38,7 @@ std::string kweighting_design(int hz, KWeighting& k) {
 }
 
 // The kernels' fp32 coefficients, and M = A^LO_CHUNK of the state transition A those coefficients define (state s1 s2 t1 t2 of the
-// two transposed direct form II sections, zero input), with its powers M^1 .. M^LO_SCAN, in double, stored as fp32.
+// two transposed direct form II sections, zero input), with its powers M^1 .. M^LO_SCAN, in double: the scan reads them as they are.
 std::string loudness_design(int hz, LoudTable& t) {
     KWeighting k;
     const std::string why = kweighting_design(hz, k);
@@ -64,11 +64,11 @@ std::string loudness_design(int hz, LoudTable& t) {
     double M[16], T[16];
     std::memcpy(M, A, sizeof(M));
     for (int i = 1; i < LO_CHUNK; ++i) { mul(M, A, T); std::memcpy(M, T, sizeof(M)); }
-    t.mpow.assign((size_t)LO_SCAN * 16, 0.f);
+    t.mpow.assign((size_t)LO_SCAN * 16, 0.0);
     double P[16];
     std::memcpy(P, M, sizeof(P));
     for (int i = 0; i < LO_SCAN; ++i) {
-        for (int j = 0; j < 16; ++j) t.mpow[(size_t)i * 16 + j] = (float)P[j];
+        for (int j = 0; j < 16; ++j) t.mpow[(size_t)i * 16 + j] = P[j];
         mul(P, M, T);
         std::memcpy(P, T, sizeof(P));
     }
@@ -81,8 +81,8 @@ void Engine::lo_prepare(LoudTable& t, int hz) {
     const std::string why = loudness_design(hz, n);
     if (!why.empty()) throw std::invalid_argument(why);
     STN_HIP(hipSetDevice(device_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.mpow.size() * sizeof(float)));
-    STN_HIP(hipMemcpyAsync(n.dev, n.mpow.data(), n.mpow.size() * sizeof(float), hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.mpow.size() * sizeof(double)));
+    STN_HIP(hipMemcpyAsync(n.dev, n.mpow.data(), n.mpow.size() * sizeof(double), hipMemcpyHostToDevice, s_));
     if (t.dev) { sync(); (void)hipFree(t.dev); }  // a fetch may still be reading the old table
     t = std::move(n);
 }
@@ -137,11 +137,13 @@ Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
     return sc;
 }
 
-void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling) {
+void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
+                        float* st_end) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     StageSpan span(*this, "out", "loudness", 20.0 * samples, samples * 4 + chunks * 20);
     auto next = [&](double flops, double bytes) { STN_HIP(hipGetLastError()); span.next("loudness", flops, bytes); };  // (the launch before it is checked)
     launch_loudness_chunks(s_, false, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    if (st_end) STN_HIP(hipMemcpyAsync(st_end, sc.st, (size_t)rows * (size_t)lo_chunks(W) * 16, hipMemcpyDeviceToHost, s_));
     next(chunks * 32.0 * 11, chunks * 32);
     launch_loudness_scan(s_, rows, W, sc.n, t, sc.st);
     next(22.0 * samples, samples * 4 + chunks * 24);
@@ -191,7 +193,8 @@ void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
     sync();
 }
 
-void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
+void Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
+                   float* peak, float* gain) {
     STN_HIP(hipSetDevice(device_));
     lo_prepare(op_lo_, hz);
     std::vector<int64_t> nn((size_t)rows, (int64_t)W);
@@ -204,15 +207,35 @@ void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t*
         max_seg = std::max<int64_t>(max_seg, nn[(size_t)r] / op_lo_.hop);
     }
     ar_.reset();
-    const size_t nx = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
+    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
+    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     const LoScratch sc = lo_scratch(rows, W);
+    if (probe)  // every per-chunk array and the results: what a launch fails to write reads back as this, not as an earlier call's value
+        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, (size_t)(reinterpret_cast<char*>(sc.n) - reinterpret_cast<char*>(sc.st)) / 4, s_));
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     lo_n_.clear();  // (the batch's lengths are no longer there)
-    lo_measure(op_lo_, dx, rows, W, sc, max_seg, false, lo_target_, lo_ceiling_);
-    lo_read_back(sc.res, (size_t)rows, lufs, peak, nullptr);
+    lo_measure(op_lo_, dx, rows, W, sc, max_seg, on, target, ceiling, probe ? probe->st_end : nullptr);
+    lo_read_back(sc.res, (size_t)rows, lufs, peak, gain);
+    if (probe) {
+        const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
+        auto out = [&](float* dst, const float* src, size_t bytes) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_)); };
+        out(probe->st_start, sc.st, nc * 16);
+        out(probe->pk, sc.pk, nc * 4);
+        out(probe->pa, sc.pa, nc * 4);
+        out(probe->pb, sc.pb, nc * 4);
+        probe->form = loudness_staging_form(dx, W);
+    }
     sync();
+}
+
+void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
+    lo_op(hz, rows, W, x, n, false, lo_target_, lo_ceiling_, nullptr, lufs, peak, nullptr);
+}
+
+void Engine::op_loudness_ex(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe& probe,
+                            float* lufs, float* peak, float* gain) {
+    lo_op(hz, rows, W, x, n, on, target, ceiling, &probe, lufs, peak, gain);
 }
 
 }  // namespace stn

@@ -494,8 +494,8 @@ struct LoudCoef { float c[10]; };     // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b
 struct LoudTable {
     int hz = 0, hop = 0;              // hop = (hz + 5) / 10 samples (100 ms)
     LoudCoef coef{};
-    std::vector<float> mpow;          // host copy, [LO_SCAN][16]: M^(i+1) row-major, M = A^LO_CHUNK of the fp32 coefficients
-    float* dev = nullptr;             // device copy (owned by whoever uploaded it)
+    std::vector<double> mpow;         // host copy, [LO_SCAN][16]: M^(i+1) row-major, M = A^LO_CHUNK of the fp32 coefficients
+    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
 };
 // fills t (not t.dev); empty string, or why hz is refused
 std::string loudness_design(int hz, LoudTable& t);
@@ -505,6 +505,8 @@ __host__ __device__ inline int64_t lo_chunks(int64_t W) { return (W + LO_CHUNK -
 // over the chunk's samples in its first 100 ms segment / in the next one, counting only whole segments.  Ks = lo_chunks(W).
 void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
                             float* st, float* pk, float* pa, float* pb);
+// the staging path the two chunk passes take for these rows: "vec" (16-byte loads: W % 4 == 0 and x 16-byte aligned) or "scalar"
+const char* loudness_staging_form(const float* x, int64_t W);
 // in place: st[row][k] (end states) -> the start states of the chunks
 void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, float* st);
 // res[0][b] = L_b (-inf when undefined), res[1][b] = peak_b, res[2][b] = g_b (1 when off or L_b undefined); max_seg = max_b n_b / hop

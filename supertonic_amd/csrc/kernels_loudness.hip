@@ -124,8 +124,8 @@ __global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __re
 }
 
 // r = v + P o (P row-major 4 x 4), each row summed in the same order
-__device__ __forceinline__ float4 lo_affine(const float* __restrict__ P, float4 o, float4 v) {
-    float4 r;
+__device__ __forceinline__ double4 lo_affine(const double* __restrict__ P, double4 o, double4 v) {
+    double4 r;
     r.x = v.x + (((P[0] * o.x + P[1] * o.y) + P[2] * o.z) + P[3] * o.w);
     r.y = v.y + (((P[4] * o.x + P[5] * o.y) + P[6] * o.z) + P[7] * o.w);
     r.z = v.z + (((P[8] * o.x + P[9] * o.y) + P[10] * o.z) + P[11] * o.w);
@@ -135,30 +135,35 @@ __device__ __forceinline__ float4 lo_affine(const float* __restrict__ P, float4 
 
 // st[row][k]: end states from zero state in, start states out.  Tile t covers chunks t*LO_SCAN ..; after the inclusive scan, lane i
 // holds v_i = sum_{j <= i} M^(i-j) e_j, so the start state of chunk t*LO_SCAN + i is v_{i-1} + M^i c with c the tile's carry-in.
-__global__ void __launch_bounds__(LO_SCAN) loudness_scan_kernel(const int64_t* __restrict__ nrow, int64_t Ks, const float* __restrict__ mp,
+// The scan runs in double on a double table, and only the start states it stores are fp32: the high-pass's two poles nearly coincide,
+// so the powers of M hold entries near +-27 that almost cancel in P o, and in fp32 that rounding falls on the combination of t1 and t2
+// the filter's output is most sensitive to (five times what the sample-by-sample fp32 recurrence loses at 48 kHz).
+__global__ void __launch_bounds__(LO_SCAN) loudness_scan_kernel(const int64_t* __restrict__ nrow, int64_t Ks, const double* __restrict__ mp,
                                                                 float* st) {
-    __shared__ float4 buf[LO_SCAN];
+    __shared__ double4 buf[2][LO_SCAN];  // two images, written in turn: a level's readers are done before the level after next writes
     const int64_t row = blockIdx.x;
     const int64_t K = lo_chunks(nrow[row]);
     const int i = threadIdx.x;
     float4* sr = reinterpret_cast<float4*>(st) + row * Ks;
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 zero = c;
+    double4 c = make_double4(0.0, 0.0, 0.0, 0.0);
+    const double4 zero = c;
+    int p = 0;
     for (int64_t t0 = 0; t0 < K; t0 += LO_SCAN) {
         const int64_t k = t0 + i;
-        float4 v = k < K ? sr[k] : zero;
+        double4 v = zero;
+        if (k < K) { const float4 e = sr[k]; v = make_double4(e.x, e.y, e.z, e.w); }
         for (int d = 1; d < LO_SCAN; d <<= 1) {
-            buf[i] = v;
+            buf[p][i] = v;
             __syncthreads();
-            if (i >= d) v = lo_affine(mp + (d - 1) * 16, buf[i - d], v);
-            __syncthreads();
+            if (i >= d) v = lo_affine(mp + (d - 1) * 16, buf[p][i - d], v);
+            p ^= 1;
         }
-        buf[i] = v;
+        buf[p][i] = v;
         __syncthreads();
-        const float4 s = i == 0 ? c : lo_affine(mp + (i - 1) * 16, c, buf[i - 1]);
-        if (k < K) sr[k] = s;
-        c = lo_affine(mp + (LO_SCAN - 1) * 16, c, buf[LO_SCAN - 1]);
-        __syncthreads();
+        const double4 s = i == 0 ? c : lo_affine(mp + (i - 1) * 16, c, buf[p][i - 1]);
+        if (k < K) sr[k] = make_float4((float)s.x, (float)s.y, (float)s.z, (float)s.w);
+        c = lo_affine(mp + (LO_SCAN - 1) * 16, c, buf[p][LO_SCAN - 1]);
+        p ^= 1;
     }
 }
 
@@ -255,13 +260,17 @@ void lo_check(int64_t rows, int64_t W, const LoudTable& t) {
     if (lo_chunks(W) > ((int64_t)1 << 31) / LO_WG) throw std::invalid_argument("loudness: row too long");
 }
 
+bool lo_vec(const float* x, int64_t W) { return W % 4 == 0 && aligned16(x); }
+
 }  // namespace
+
+const char* loudness_staging_form(const float* x, int64_t W) { return lo_vec(x, W) ? "vec" : "scalar"; }
 
 void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
                             float* st, float* pk, float* pa, float* pb) {
     if (rows <= 0 || W <= 0) return;
     lo_check(rows, W, t);
-    const int vec = (W % 4 == 0 && aligned16(x)) ? 1 : 0;
+    const int vec = lo_vec(x, W) ? 1 : 0;
     const dim3 grid((unsigned)((W + LO_SPAN - 1) / LO_SPAN), (unsigned)rows);
     if (energy) STN_KLAUNCH(loudness_chunk_kernel<true>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
     else STN_KLAUNCH(loudness_chunk_kernel<false>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
