@@ -465,6 +465,62 @@ int stn_op_limiter(stn_handle* h, int hz, int rows, int W, const float* x, const
  * lookahead_ms is outside [0.5, 10] or hz outside [8000, 192000] */
 int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_t* n);
 
+/* ---- true peak ---------------------------------------------------------------------------------------
+ * The ceiling of stn_set_loudness as a TRUE-peak ceiling (dBTP, ITU-R BS.1770-4 Annex 2: the peak of the 4x oversampled signal), which
+ * is what a DAC, a codec or a later resampler sees; speech has inter-sample peaks 0.5 to 3 dB above its sample peaks.  The default,
+ * STN_PEAK_SAMPLE, is the sample-peak ceiling described above.  The mode has no effect while loudness is off; it composes with the rate,
+ * the encoding, the trimming, the limiter and the join; the latent geometry, the reported durations, stn_batch_wav_device_ptr, the
+ * captured pipeline and the graph key are untouched, and toggling it drops or re-captures no graph.
+ * Filter (stn_true_peak_filter): P = 4 phases of T = 16 taps, off = 7; tap j of phase p sits d = p - (j - 7) * 4 quarter samples from
+ * the output instant, h = sinc(d / 4) * I0(8 sqrt(1 - (d / 32)^2)) / I0(8) (Kaiser window, beta = 8, cutoff at the input Nyquist; sinc
+ * exactly 0 at the non-zero integers), every phase normalized in double to a DC gain of 1 and stored as fp32.  Phase 0 is the unit tap.
+ * The filter lives in normalized frequency: the same 64 floats serve every rate in [8000, 192000].
+ * For a row with span n (the loudness span n_b), with x = 0 outside [0, n):
+ *   u[i][ph] = sum_{j = 0..15} taps[ph][j] * x[i - 7 + j], one fp32 FMA chain with j ascending, for ph in {1, 2, 3} and i in [-1, n - 1]:
+ *   the value at i + ph/4;  U[i] = max_ph |u[i][ph]|;
+ *   envelope p[i] = max(|x[i]|, U[i-1], U[i]) for 0 <= i < n (every oversampled point strictly between i - 1 and i + 1), and
+ *   p[i] = |x[i]| for i >= n;
+ *   tp = max_{i < n} p[i] (0 when n = 0);  per chunk of 32 samples from sample 0, pk[k] = max p[i] over the chunk's samples inside the
+ *   span, +0.0 when there are none.
+ * Every value depends on the row's first n samples only, not on W, B or the row's neighbours (one chain order; max is exact).
+ * Loudness without the limiter: g_b = min(10^((target - L_b) / 20), c / tp_b), and stn_batch_loudness / stn_batch_join_loudness
+ * report tp_b as the peak.  With the limiter: the curve of "limiter" above with r[j] = 1 where e[j] <= c and c / e[j] elsewhere, e the
+ * envelope of v = x * g (r = 1 outside [0, n)); everything else of that contract is unchanged (m, M, w, s, y = clamp(v s, -c, c)).
+ * Modulating by s moves inter-sample peaks a little, so the limited row's true peak tp_y is measured and the delivered fp32 row is
+ * y * trim, trim = 1 where tp_y <= c, else c / tp_y (one fp32 divide, one fp32 multiply per sample); the trim is reported
+ * (stn_batch_true_peak).  While the limiter is active the peak stn_batch_loudness reports stays the sample peak (nothing caps the gain).
+ * Trimmed fetches measure and limit the untrimmed span; STN_JOIN_GAIN_ROW joins the limited, trimmed-gain rows; STN_JOIN_GAIN_PROG runs
+ * all of it on the G joined rows.  No host read is added, so the pipelined _begin stays asynchronous.  DESIGN.md section 16 has the
+ * decomposition, the filter's measured response and the traffic. */
+#define STN_PEAK_SAMPLE 0
+#define STN_PEAK_TRUE 1
+/* any other value: STN_ERR_INVALID with a message, and the previous setting stays in force */
+int stn_set_peak_mode(stn_handle* h, int mode);
+/* the mode, or STN_ERR_INVALID for a NULL handle */
+int stn_get_peak_mode(const stn_handle* h);
+/* the oversampling filter (host only, no device needed): *phases = 4, *taps_per_phase = 16, taps [4][16] when taps_or_null is not NULL
+ * and cap >= 64 (STN_ERR_INVALID when cap is smaller) */
+int stn_true_peak_filter(float* taps_or_null, size_t cap, int* phases, int* taps_per_phase);
+/* A reporting call, as stn_batch_loudness and stn_batch_limiter are: it runs the output stage's measurement again on the handle's
+ * stream (with the limiter on, the whole limiter chain and three true-peak passes), overwrites what those two calls last left in the
+ * shared fetch scratch, and synchronizes.  The finished batch at the current output rate, in any mode and whether loudness is on or
+ * not: tp_in, the true peak of the measured row; tp_out, the true peak of the fp32 row a per-row fetch without trimming delivers under the current settings; trim, 1 except with
+ * the limiter in true mode; each pointer [B] floats or NULL */
+int stn_batch_true_peak(stn_handle* h, float* tp_in, float* tp_out, float* trim);
+/* op-level: rows x W fp32 (host) at hz in [8000, 192000] (checked; the result does not depend on it); row r's first n[r] samples
+ * (n_or_null = NULL: all W) times gain_or_null[r] (NULL: 1; one fp32 multiply) -> tp [rows], env [rows][W] (the envelope p) and pk
+ * [rows][(W + 31) / 32]; each may be NULL.  Before the launches the device's tp, env and pk are filled with the quiet NaN 0x7FC00000.
+ * x_misalign 0 / 1: x is uploaded 16-byte aligned / 4 bytes off, which forces the scalar staging path at W % 4 == 0.  form: the staging
+ * path that ran, "vec" (16-byte loads and stores) or "scalar", NUL-terminated, truncated to form_cap; may be NULL.  1 <= rows <= 65535. */
+int stn_op_true_peak(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, const float* gain_or_null,
+                     int x_misalign, float* tp, float* env_or_null, float* pk_or_null, char* form, size_t form_cap);
+/* stn_op_limiter under a peak mode.  STN_PEAK_SAMPLE: stn_op_limiter, trim = 1, env untouched.  STN_PEAK_TRUE: the curve follows the
+ * envelope of x * gain (env_or_null [rows][W]); y is the limited row BEFORE the trim, and trim_or_null [rows] the scalar a fetch then
+ * applies. */
+int stn_op_limiter_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, const float* gain_or_null,
+                      float ceiling_dbfs, float lookahead_ms, float* y, float* s_or_null, float* reduction_db, int64_t* limited,
+                      int peak_mode, float* env_or_null, float* trim_or_null);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

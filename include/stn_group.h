@@ -55,6 +55,8 @@ int stn_group_set_output_rate(stn_group* g, int hz);
 int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceiling_dbfs);
 /* look-ahead peak limiter of every rank (stn_set_limiter; no effect without loudness): the gathered PCM is then limited row by row */
 int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms);
+/* peak mode of every rank (stn_set_peak_mode; no effect without loudness): STN_PEAK_SAMPLE or STN_PEAK_TRUE */
+int stn_group_set_peak_mode(stn_group* g, int mode);
 /* sample encoding (STN_ENC_*, stn.h) of the gather of the next stn_group_synthesize: every rank encodes its shard on its GPU and the
  * blocks, the exchange and the host stage are sized in that encoding's bytes (a mu-law gather moves half the bytes of a PCM16 one).
  * The default is STN_ENC_PCM16; an unknown encoding is STN_ERR_INVALID. */

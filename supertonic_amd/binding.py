@@ -319,6 +319,13 @@ def load():
     L.stn_op_limiter.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, cf, cf, vp, vp, vp, vp]
     L.stn_limiter_window.argtypes = [ci, cf, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.stn_group_set_limiter.argtypes = [vp, ci, cf]
+    L.stn_set_peak_mode.argtypes = [vp, ci]
+    L.stn_get_peak_mode.argtypes = [vp]
+    L.stn_group_set_peak_mode.argtypes = [vp, ci]
+    L.stn_true_peak_filter.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.stn_batch_true_peak.argtypes = [vp, vp, vp, vp]
+    L.stn_op_true_peak.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, ci, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_op_limiter_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, cf, cf, vp, vp, vp, vp, ci, vp, vp]
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
@@ -424,6 +431,10 @@ class Group:
         on, ms = limiter_args(lookahead_ms)
         self._ck(self._lib.stn_group_set_limiter(self._g, on, ms))
 
+    def set_peak_mode(self, mode="sample"):
+        """Peak mode of every rank (Engine.set_peak_mode): "sample" or "true"."""
+        self._ck(self._lib.stn_group_set_peak_mode(self._g, peak_mode_id(mode)))
+
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
         self._ck(self._lib.stn_group_last_shards(self._g, rows, samples))
@@ -526,6 +537,31 @@ def limiter_args(lookahead_ms):
     if not 0.5 <= ms <= 10.0:
         raise ValueError(f"limiter look-ahead {ms} ms: must be in [0.5, 10]")
     return 1, ms
+
+
+PEAK_SAMPLE, PEAK_TRUE = 0, 1
+PEAK_MODES = {"sample": PEAK_SAMPLE, "true": PEAK_TRUE}
+
+
+def peak_mode_id(mode):
+    """A peak-mode argument -> STN_PEAK_SAMPLE / STN_PEAK_TRUE: "sample" or "true" (None: "sample"); anything else is a ValueError."""
+    if mode is None:
+        return PEAK_SAMPLE
+    if isinstance(mode, str) and mode in PEAK_MODES:
+        return PEAK_MODES[mode]
+    raise ValueError(f"peak_mode: 'sample' or 'true', not {mode!r}")
+
+
+def true_peak_filter():
+    """The 4x oversampling filter of the true-peak mode (host only): float32 [4, 16], every phase's DC gain 1, phase 0 the unit tap."""
+    L = load()
+    P, T = ctypes.c_int(), ctypes.c_int()
+    if L.stn_true_peak_filter(None, 0, ctypes.byref(P), ctypes.byref(T)) < 0:
+        raise StnError(-1, "stn_true_peak_filter failed")
+    taps = np.empty((P.value, T.value), np.float32)
+    if L.stn_true_peak_filter(taps.ctypes.data, taps.size, ctypes.byref(P), ctypes.byref(T)) < 0:
+        raise StnError(-1, "stn_true_peak_filter failed")
+    return taps
 
 
 def limiter_window(hz, lookahead_ms=LIMITER_MS):
@@ -946,6 +982,60 @@ class Engine:
         self._ck(self._lib.stn_op_limiter(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, None if g is None else g.ctypes.data,
                                           float(ceiling_dbfs), float(lookahead_ms), y.ctypes.data, s.ctypes.data, red.ctypes.data, lim.ctypes.data))
         return y, s, red, lim
+
+    def op_limiter_ex(self, x, hz, n=None, gain=None, ceiling_dbfs=-1.0, lookahead_ms=LIMITER_MS, peak_mode="true"):
+        """op_limiter under a peak mode -> dict(y, s, env [rows, W], reduction_db, limited, trim [rows]): with "true" the curve follows
+        the true-peak envelope env of x * gain, y is the limited row before the trim, and trim = min(1, c / true peak of y)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(n, np.int64)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        o = dict(y=np.empty((rows, W), np.float32), s=np.empty((rows, W), np.float32), env=np.full((rows, W), np.nan, np.float32),
+                 reduction_db=np.empty(rows, np.float32), limited=np.empty(rows, np.int64), trim=np.empty(rows, np.float32))
+        mode = peak_mode if isinstance(peak_mode, int) else peak_mode_id(peak_mode)
+        self._ck(self._lib.stn_op_limiter_ex(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, None if g is None else g.ctypes.data,
+                                             float(ceiling_dbfs), float(lookahead_ms), o["y"].ctypes.data, o["s"].ctypes.data,
+                                             o["reduction_db"].ctypes.data, o["limited"].ctypes.data, mode, o["env"].ctypes.data, o["trim"].ctypes.data))
+        return o
+
+    def set_peak_mode(self, mode="sample"):
+        """The ceiling of set_loudness as a sample-peak ("sample", the default) or a true-peak ceiling ("true": 4x oversampled, ITU-R
+        BS.1770-4 Annex 2).  With loudness off it has no effect."""
+        self._ck(self._lib.stn_set_peak_mode(self._h, peak_mode_id(mode)))
+
+    @property
+    def peak_mode(self):
+        """"sample" or "true"."""
+        return "true" if self._ck_mode(self._lib.stn_get_peak_mode(self._h)) == PEAK_TRUE else "sample"
+
+    def _ck_mode(self, rc):
+        if rc < 0:
+            self._ck(rc)
+        return rc
+
+    def batch_true_peak(self):
+        """The finished batch at the output rate -> (tp_in, tp_out, trim) float32 [B]: the true peak of the measured row, of the fp32
+        row as a fetch delivers it under the current settings, and the limiter's trim (1 except with the limiter in true mode)."""
+        B = self.batch_dims()[0]
+        a, b, t = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32)
+        self._ck(self._lib.stn_batch_true_peak(self._h, a.ctypes.data, b.ctypes.data, t.ctypes.data))
+        return a, b, t
+
+    def op_true_peak(self, x, hz, n=None, gain=None, x_misalign=0, env=True):
+        """rows x W fp32 on the GPU, row r's first n[r] samples (None: all W) times gain[r] (None: 1) -> dict: tp [rows], env [rows, W]
+        (the envelope; None when env is False), pk [rows, Ks] (per chunk of 32), form ("vec" / "scalar").  The device buffers are
+        poisoned with the quiet NaN 0x7FC00000 first; x_misalign = 1 uploads x 4 bytes off 16-byte alignment."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        o = dict(tp=np.empty(rows, np.float32), env=np.empty((rows, W), np.float32) if env else None, pk=np.empty((rows, (W + 31) // 32), np.float32))
+        form = ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_true_peak(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, None if g is None else g.ctypes.data,
+                                            int(x_misalign), o["tp"].ctypes.data, None if o["env"] is None else o["env"].ctypes.data,
+                                            o["pk"].ctypes.data, form, ctypes.sizeof(form)))
+        o["form"] = form.value.decode()
+        return o
 
     def dbg_batch_set_wav(self, wav):
         """Diagnostic: overwrite the finished batch's model-rate waveform ([B, L * chunk] float32) for tests that need known silences."""

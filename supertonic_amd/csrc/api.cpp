@@ -406,6 +406,32 @@ int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_
         return STN_ERR_INVALID;
     }
 }
+int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
+int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
+int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {
+    if (phases) *phases = stn::TP_PHASES;
+    if (taps_per_phase) *taps_per_phase = stn::TP_TAPS;
+    if (taps) {
+        if (cap < (size_t)stn::TP_PHASES * stn::TP_TAPS) return STN_ERR_INVALID;
+        stn::truepeak_design(taps);
+    }
+    return STN_OK;
+}
+int stn_batch_true_peak(stn_handle* h, float* tp_in, float* tp_out, float* trim) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_true_peak(tp_in, tp_out, trim); })
+}
+int stn_op_true_peak(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp,
+                     float* env, float* pk, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_true_peak: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 need(x_misalign == 0 || x_misalign == 1, "stn_op_true_peak: x_misalign must be 0 or 1");
+                 const char* f = h->eng->op_true_peak(hz, rows, W, x, n, gain, x_misalign, tp, env, pk);
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", f); })
+}
+int stn_op_limiter_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs,
+                      float lookahead_ms, float* y, float* s, float* reduction_db, int64_t* limited, int peak_mode, float* env, float* trim) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_limiter_ex: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_limiter_ex(hz, rows, W, x, n, gain, ceiling_dbfs, lookahead_ms, y, s, reduction_db, limited, peak_mode, env, trim); })
+}
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav) {
     STN_TRY(h, { need(wav != nullptr, "wav is null"); need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->dbg_batch_set_wav(wav); })
 }

@@ -3,7 +3,8 @@
 // plus engine flags: --device N, --gpus N (deal the batch over N devices: include/stn_group.h), --devices a,b,.. (explicit ordinals),
 // --dtype {fp32,bf16,fp16}, --seed S (0 = unseeded noise, like the reference), --sample-rate HZ (WAV files at HZ, resampled on the GPU;
 // absent: the model's rate), --loudness LUFS (every utterance normalized to that BS.1770-4 integrated loudness on the GPU; absent: off),
-// --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1), --limiter MS (with --loudness: the full loudness gain,
+// --peak-ceiling DBFS (the sample peak the loudness gain may reach; default -1), --peak-mode {sample,true} (with --loudness: the ceiling
+// as a sample peak or as a true peak, 4x oversampled), --limiter MS (with --loudness: the full loudness gain,
 // and a look-ahead peak limiter of MS milliseconds, 0.5 to 10, holds the ceiling instead of a capped gain), --encoding {pcm16,pcm24,f32,mulaw,alaw} (sample format
 // of the WAV files, encoded on the GPU; default pcm16, writeWavFile's files), --loudness-scope {chunk,text} (a long text with --loudness:
 // every chunk normalized on its own, the default, or the joined text as one programme with one gain; text needs one GPU),
@@ -47,7 +48,7 @@ int main(int argc, char* argv[]) {
     std::vector<std::string> text = {"This morning, I took a walk in the park, and the sound of the birds and the breeze was so "
                                      "pleasant that I stopped for a long time just to listen."};
     std::vector<std::string> lang = {"en"};
-    bool batch = false;
+    bool batch = false, peak_mode_given = false;
     EngineOptions opts;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -70,6 +71,12 @@ int main(int argc, char* argv[]) {
         else if (a == "--loudness" && more) opts.loudness_lufs = std::strtof(argv[++i], nullptr);  // LUFS of every utterance (BS.1770-4, on the GPU); absent: off
         else if (a == "--peak-ceiling" && more) opts.loudness_ceiling_dbfs = std::strtof(argv[++i], nullptr);  // dBFS cap of the loudness gain (default -1)
         else if (a == "--limiter" && more) opts.limiter_ms = std::strtof(argv[++i], nullptr);  // ms of look-ahead of the peak limiter behind the loudness gain; absent: off
+        else if (a == "--peak-mode" && more) {  // with --loudness: the ceiling as a sample peak (default) or a true peak (dBTP, 4x oversampled on the GPU)
+            const std::string v = argv[++i];
+            if (v != "sample" && v != "true") { std::cerr << "Error: --peak-mode " << v << ": sample or true\n"; return 1; }
+            opts.true_peak = v == "true";
+            peak_mode_given = true;
+        }
         else if (a == "--encoding" && more) {  // sample format of the WAV files (encoded on the GPU); default pcm16
             const std::string e = argv[++i];
             opts.encoding = e == "pcm16" ? STN_ENC_PCM16 : e == "pcm24" ? STN_ENC_PCM24 : e == "f32" ? STN_ENC_F32 : e == "mulaw" ? STN_ENC_MULAW : e == "alaw" ? STN_ENC_ALAW : -1;
@@ -85,6 +92,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--trim-keep" && more) opts.trim_keep_ms = std::strtof(argv[++i], nullptr);  // ms kept around the speech (default 20)
         else if (a == "--trim-fade" && more) opts.trim_fade_ms = std::strtof(argv[++i], nullptr);  // ms of fade over a cut edge (default 5)
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
+    }
+    if (peak_mode_given && std::isnan(opts.loudness_lufs)) {
+        std::cerr << "Error: --peak-mode needs --loudness (it is the ceiling of the loudness gain)\n";
+        return 1;
     }
     if (!std::isnan(opts.limiter_ms) && std::isnan(opts.loudness_lufs)) {
         std::cerr << "Error: --limiter needs --loudness (the limiter holds the ceiling of the loudness gain)\n";

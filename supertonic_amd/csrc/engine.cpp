@@ -184,6 +184,7 @@ Engine::~Engine() {
     lo_release();
     ed_release();
     lm_release();
+    tp_release();
     if (out_f32_) (void)hipFree(out_f32_);
     if (out_enc_) (void)hipFree(out_enc_);
     if (join_tab_) (void)hipFree(join_tab_);

@@ -349,6 +349,24 @@ class Engine {
     // (host; s may be null), reduction_db, limited [rows] (host, or null)
     void op_limiter(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
                     float* s, float* reduction_db, int64_t* limited);
+    // the same under a peak mode: STN_PEAK_TRUE drives the curve by the true-peak envelope of x * gain (env [rows][W], host or null) and
+    // reports trim [rows] = min(1, c / true peak of y) (host or null; 1 in sample mode); y is the limited row before the trim
+    void op_limiter_ex(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
+                       float* s, float* reduction_db, int64_t* limited, int peak_mode, float* env, float* trim);
+
+    // ---- true peak (engine_truepeak.cpp; include/stn.h "true peak"): STN_PEAK_SAMPLE is the default (every
+    // fetch path is then exactly the one without it).  STN_PEAK_TRUE with loudness on: the ceiling is a true-peak ceiling (4x
+    // oversampled, kernels_truepeak.hip): the gate's peak is the row's true peak, and the limiter's curve follows the true-peak envelope
+    // and is followed by one trim per row.  Without loudness the setting has no effect.
+    void set_peak_mode(int mode);
+    int peak_mode() const { return pk_true_ ? 1 : 0; }
+    // the finished batch at the output rate: the true peak of the measured row, of the fp32 row as delivered under the current settings,
+    // and the limiter's trim (1 except with the limiter in true mode); [B] host floats or null
+    void batch_true_peak(float* tp_in, float* tp_out, float* trim);
+    // rows x W fp32 (host), row r's first n[r] samples (all W when n is null) times gain[r] (1 when null) -> tp [rows], env [rows][W],
+    // pk [rows][lo_chunks(W)] (host, or null); the scratch is filled with the quiet NaN 0x7FC00000 first; returns the staging form
+    const char* op_true_peak(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp, float* env,
+                             float* pk);
 
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
@@ -609,14 +627,20 @@ class Engine {
     void lo_release();
     // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain];
     // st_end (host, or null): the state buffer as the first launch left it, copied out before the scan overwrites it
+    // true_peak: a fifth launch between the energy pass and the gate replaces pk by the per-chunk true peaks (kernels_truepeak.hip)
     void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
-                    float* st_end = nullptr);
+                    float* st_end = nullptr, bool true_peak = false);
     // op_loudness and op_loudness_ex: the upload, the measurement, the read-back
     void lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
                float* peak, float* gain);
     // rows x W fp32 on the device (x) with row spans n measured on the stream against table t: returns res (device [3][rows]: L, peak,
     // gain).  n is uploaded only when it differs from what the scratch holds.
-    float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling);
+    // true_peak: the gate's peak is the row's true peak (section 16).  The callers that own the setting (lo_batch, join_measure) pass
+    // lo_true_peak(); the op-level callers keep the sample peak.
+    float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
+                   bool true_peak = false);
+    // (with the limiter active nothing caps the gain: the limiter measures the envelope of the scaled row itself)
+    bool lo_true_peak() const { return true_peak_on() && !limiter_active(); }
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
     float* lo_batch(const float* x, int64_t Wo, bool on);
     bool st_on_ = false;
@@ -642,7 +666,7 @@ class Engine {
     float lm_ms_ = 5.0f;
     float lo_cap() const { return limiter_active() ? INFINITY : lo_ceiling_; }  // the gate's ceiling: the limiter enforces it instead
     char* lm_buf_ = nullptr; size_t lm_buf_cap_ = 0;  // fetch-time scratch of the limiter (grow-only, outside the graph key)
-    struct LmScratch { float* y; int* pcnt; float* pmin; int64_t* limited; float* red; };
+    struct LmScratch { float* y; int* pcnt; float* pmin; int64_t* limited; float* red; const float* trim = nullptr; };
     static size_t lm_layout(int64_t rows, int64_t W, size_t* o);  // the scratch's five offsets (o) and its size in bytes
     static LmScratch lm_at(char* base, const size_t* o);
     LmScratch lm_scratch(int64_t rows, int64_t W);
@@ -650,8 +674,18 @@ class Engine {
     const float* lm_window(int hz);
     // rows x W fp32 on the device (x) whose spans the measurement just uploaded (lo_n_ptr_), times g (device [rows]), limited into the
     // scratch: returns the rows (row stride W)
+    // In true-peak mode the curve follows the envelope of x * g, and .trim (device [rows]) is the gain the store behind it applies
     LmScratch lm_rows(const float* x, int64_t rows, int64_t W, const float* g);
     void lm_release();
+    bool pk_true_ = false;             // the peak mode (engine_truepeak.cpp)
+    bool true_peak_on() const { return pk_true_ && lo_on_; }
+    char* tp_buf_ = nullptr; size_t tp_buf_cap_ = 0;  // fetch-time scratch of the true-peak mode (grow-only, outside the graph key)
+    struct TpScratch { float *pk, *tp_in, *tp_out, *tp_y, *trim, *env; };
+    // per chunk the peak, per row four results, and (with_env) the envelope rows
+    TpScratch tp_scratch(int64_t rows, int64_t W, bool with_env);
+    // tp[row] (and trim[row] against c when trim is not null) of rows x W times g (device [rows] or null), spans n (device)
+    void tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float c, float* tp, float* trim);
+    void tp_release();
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
     // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
     // With a join plan the G programme rows of the plan instead of the B rows (scope: STN_JOIN_GAIN_*)

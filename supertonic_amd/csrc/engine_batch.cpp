@@ -472,13 +472,13 @@ void Engine::enqueue_output(const OutRows& o) {
         const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
         const float* fade = st_window(output_rate());
         int64_t sw = resample_on() ? Wo : W;
-        if (limiter_active()) { src = lm_rows(src, b.B, Wo, g).y; g = nullptr; sw = Wo; }  // section 15: the untrimmed rows limited, then cut
+        if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; sw = Wo; }  // section 15: the untrimmed rows limited, then cut
         StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_join_trim_rows(s_, src, sw, sc.seg, sc.prog, b.B, Wo, g, fade, o.enc, o.dst, o.stride);
     } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
-        if (limiter_active()) { src = lm_rows(src, b.B, Wo, g).y; g = nullptr; }  // section 15: the store then runs on the limited rows
+        if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; }  // section 15: the store then runs on the limited rows
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, src, b.B, Wo, g, o.enc, o.dst, o.stride);
     } else if (resample_on()) {
@@ -714,7 +714,7 @@ float* Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
     std::vector<int64_t> n((size_t)p.G);
     for (int g = 0; g < p.G; ++g)
         n[(size_t)g] = std::max<int64_t>(0, std::min<int64_t>(p.prog_len[(size_t)g], (int64_t)(p.prog_dur[(size_t)g] * (float)hz)));
-    return lo_rows(lo_, joined, p.G, p.W_join, std::move(n), on, lo_target_, lo_cap());
+    return lo_rows(lo_, joined, p.G, p.W_join, std::move(n), on, lo_target_, lo_cap(), lo_true_peak());
 }
 
 // Loudness off: one join launch behind the optional resample.  On, per member row: the rows measured as every fetch measures them, then
@@ -729,7 +729,7 @@ void Engine::enqueue_joined(const OutRows& o) {
     if (loudness_on() && o.scope == STN_JOIN_GAIN_PROG) {
         const float* joined = join_f32(p);
         const float* g = join_measure(p, joined, true) + 2 * (int64_t)p.G;
-        if (limiter_active()) { joined = lm_rows(joined, p.G, p.W_join, g).y; g = nullptr; }  // section 15: G rows, each its programme's gain and span
+        if (limiter_active()) { const LmScratch lm = lm_rows(joined, p.G, p.W_join, g); joined = lm.y; g = lm.trim; }  // section 15: G rows, each its programme's gain and span
         {
             StageSpan span(*this, "out", "loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
             launch_store_rows(s_, joined, p.G, p.W_join, g, o.enc, o.dst, o.stride);
@@ -740,7 +740,7 @@ void Engine::enqueue_joined(const OutRows& o) {
     const float* src = out_source(Wo);
     const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
     int64_t sw = resample_on() ? Wo : W;
-    if (limiter_active()) { src = lm_rows(src, b.B, Wo, g).y; g = nullptr; sw = Wo; }  // section 15: the segments are the limited rows
+    if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; sw = Wo; }  // section 15: the segments are the limited rows
     join_enqueue(src, sw, join_tables(p), p, g, o.enc, o.dst, o.stride);
 }
 

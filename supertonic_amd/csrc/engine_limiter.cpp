@@ -99,18 +99,28 @@ Engine::LmScratch Engine::lm_scratch(int64_t rows, int64_t W) {
 Engine::LmScratch Engine::lm_rows(const float* x, int64_t rows, int64_t W, const float* g) {
     const int hz = output_rate();
     const float* w = lm_window(hz);
-    const LmScratch sc = lm_scratch(rows, W);
+    LmScratch sc = lm_scratch(rows, W);
     const float c = (float)std::pow(10.0, (double)lo_ceiling_ / 20.0);
+    const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
+    const TpScratch tp = pk_true_ ? tp_scratch(rows, W, true) : TpScratch{};
+    if (pk_true_) {  // section 16: the envelope of x * g drives the curve
+        StageSpan span(*this, "out", "true_peak", 97.0 * samples, samples * 8 + chunks * 4);
+        launch_truepeak(s_, x, rows, W, lo_n_ptr_, g, tp.pk, tp.env);
+        STN_HIP(hipGetLastError());
+    }
     {
-        const double samples = (double)rows * W;
         const double tiles = (double)rows * lm_tiles(W);
-        StageSpan span(*this, "out", "limiter", 4.0 * samples, samples * 8 + tiles * 8);
-        launch_limiter(s_, x, rows, W, lo_n_ptr_, g, c, (int)limiter_samples(hz, lm_ms_), w, sc.y, nullptr, sc.pcnt, sc.pmin);
+        StageSpan span(*this, "out", "limiter", 4.0 * samples, samples * (pk_true_ ? 12 : 8) + tiles * 8);
+        launch_limiter(s_, x, rows, W, lo_n_ptr_, g, c, (int)limiter_samples(hz, lm_ms_), w, sc.y, nullptr, sc.pcnt, sc.pmin, tp.env);
         STN_HIP(hipGetLastError());
         span.next("limiter_rows", tiles, tiles * 8 + (double)rows * 12);
         launch_limiter_rows(s_, rows, W, sc.pcnt, sc.pmin, sc.limited, sc.red);
     }
     STN_HIP(hipGetLastError());
+    if (pk_true_) {  // the curve moves inter-sample peaks a little: one scalar per row then holds the ceiling, and is reported
+        tp_rows(sc.y, rows, W, lo_n_ptr_, nullptr, tp.pk, c, tp.tp_y, tp.trim);
+        sc.trim = tp.trim;
+    }
     return sc;
 }
 
@@ -134,7 +144,15 @@ void Engine::batch_limiter(float* reduction_db, int64_t* limited) {
 
 void Engine::op_limiter(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
                         float* s, float* reduction_db, int64_t* limited) {
+    op_limiter_ex(hz, rows, W, x, n, gain, ceiling_dbfs, lookahead_ms, y, s, reduction_db, limited, STN_PEAK_SAMPLE, nullptr, nullptr);
+}
+
+void Engine::op_limiter_ex(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
+                           float* s, float* reduction_db, int64_t* limited, int peak_mode, float* env, float* trim) {
     STN_HIP(hipSetDevice(device_));
+    if (peak_mode != STN_PEAK_SAMPLE && peak_mode != STN_PEAK_TRUE)
+        throw std::invalid_argument("peak mode " + std::to_string(peak_mode) + ": must be STN_PEAK_SAMPLE (0) or STN_PEAK_TRUE (1)");
+    const bool tpm = peak_mode == STN_PEAK_TRUE;
     const std::string why = limiter_check(hz, lookahead_ms);
     if (!why.empty()) throw std::invalid_argument(why);
     if (!(ceiling_dbfs >= -30.0f && ceiling_dbfs <= 0.0f))
@@ -155,12 +173,19 @@ void Engine::op_limiter(int hz, int rows, int W, const float* x, const int64_t* 
     int64_t* dn = static_cast<int64_t*>(ar_.alloc((size_t)rows * 8));
     float* dw = static_cast<float*>(ar_.alloc(w.size() * 4));
     float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
+    float* denv = tpm ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
+    float* dpk = tpm ? static_cast<float*>(ar_.alloc((size_t)rows * (size_t)lo_chunks(W) * 4)) : nullptr;
+    float* dtp = tpm ? static_cast<float*>(ar_.alloc((size_t)rows * 8)) : nullptr;  // [rows] true peak of y, [rows] trim
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
     if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
-    launch_limiter(s_, dx, rows, W, dn, dg, (float)std::pow(10.0, (double)ceiling_dbfs / 20.0), (int)limiter_samples(hz, lookahead_ms), dw, sc.y, ds,
-                   sc.pcnt, sc.pmin);
+    const float c = (float)std::pow(10.0, (double)ceiling_dbfs / 20.0);
+    if (tpm) {
+        launch_truepeak(s_, dx, rows, W, dn, dg, dpk, denv);
+        STN_HIP(hipGetLastError());
+    }
+    launch_limiter(s_, dx, rows, W, dn, dg, c, (int)limiter_samples(hz, lookahead_ms), dw, sc.y, ds, sc.pcnt, sc.pmin, denv);
     STN_HIP(hipGetLastError());
     launch_limiter_rows(s_, rows, W, sc.pcnt, sc.pmin, sc.limited, sc.red);
     STN_HIP(hipGetLastError());
@@ -168,6 +193,16 @@ void Engine::op_limiter(int hz, int rows, int W, const float* x, const int64_t* 
     if (s) STN_HIP(hipMemcpyAsync(s, ds, nx * 4, hipMemcpyDeviceToHost, s_));
     if (reduction_db) STN_HIP(hipMemcpyAsync(reduction_db, sc.red, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
     if (limited) STN_HIP(hipMemcpyAsync(limited, sc.limited, (size_t)rows * 8, hipMemcpyDeviceToHost, s_));
+    if (tpm) {
+        launch_truepeak(s_, sc.y, rows, W, dn, nullptr, dpk, nullptr);
+        STN_HIP(hipGetLastError());
+        launch_truepeak_rows(s_, rows, W, dn, dpk, c, dtp, dtp + rows);
+        STN_HIP(hipGetLastError());
+        if (env) STN_HIP(hipMemcpyAsync(env, denv, nx * 4, hipMemcpyDeviceToHost, s_));
+        if (trim) STN_HIP(hipMemcpyAsync(trim, dtp + rows, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    } else if (trim) {
+        std::fill(trim, trim + rows, 1.0f);
+    }
     sync();  // (nn and w are read by the copies above until here)
 }
 

@@ -138,7 +138,7 @@ Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
 }
 
 void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
-                        float* st_end) {
+                        float* st_end, bool true_peak) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     StageSpan span(*this, "out", "loudness", 20.0 * samples, samples * 4 + chunks * 20);
     auto next = [&](double flops, double bytes) { STN_HIP(hipGetLastError()); span.next("loudness", flops, bytes); };  // (the launch before it is checked)
@@ -148,6 +148,11 @@ void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_
     launch_loudness_scan(s_, rows, W, sc.n, t, sc.st);
     next(22.0 * samples, samples * 4 + chunks * 24);
     launch_loudness_chunks(s_, true, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    if (true_peak) {  // section 16: pk becomes the per-chunk true peaks, and the gate, untouched, caps the gain by the row's true peak
+        STN_HIP(hipGetLastError());
+        span.next("true_peak", 97.0 * samples, samples * 4 + chunks * 4);
+        launch_truepeak(s_, x, rows, W, sc.n, nullptr, sc.pk, nullptr);
+    }
     next(chunks * 2, chunks * 12 + (double)rows * 12);
     launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, target, ceiling, sc.res);
     STN_HIP(hipGetLastError());
@@ -169,10 +174,11 @@ float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
         n[(size_t)i] = std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz));
         if (n[(size_t)i] < 0) n[(size_t)i] = 0;
     }
-    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_cap());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
+    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_cap(), lo_true_peak());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
 }
 
-float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling) {
+float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
+                       bool true_peak) {
     int64_t max_seg = 0;
     for (int64_t v : n) max_seg = std::max<int64_t>(max_seg, v / t.hop);
     const LoScratch sc = lo_scratch(rows, W);
@@ -183,7 +189,7 @@ float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t
         lo_n_ptr_ = sc.n;
         STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
-    lo_measure(t, x, rows, W, sc, max_seg, on, target, ceiling);
+    lo_measure(t, x, rows, W, sc, max_seg, on, target, ceiling, nullptr, true_peak);
     return sc.res;
 }
 

@@ -7,7 +7,6 @@
 
 namespace stn {
 
-namespace {
 // Zeroth-order modified Bessel function of the first kind (power series; the Kaiser window's shape)
 double bessel_i0(double x) {
     double sum = 1.0, term = 1.0;
@@ -19,7 +18,6 @@ double bessel_i0(double x) {
     }
     return sum;
 }
-}  // namespace
 
 // Kaiser-windowed sinc designed at the common rate in_hz * P.  Passband edge 0.85 * min(in, out) / 2, stopband
 // edge min(in, out) / 2, cutoff between the two, attenuation target 90 dB (the spec asks for 80 dB of rejection and +-0.05 dB of

@@ -1,0 +1,153 @@
+// engine_truepeak.cpp — the true-peak mode of the loudness ceiling: the 4x oversampling filter (host only), the setting, the fetch
+// scratch, the reporting call and the op-level entries.  The kernels are kernels_truepeak.hip; the measurement (engine_loudness.cpp) and
+// the limiter (engine_limiter.cpp) are its consumers; DESIGN.md section 16 has the contract.
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace stn {
+
+// resample_design's formula with P = 4, Q = 1, the cutoff at the input Nyquist and T = 16 given: tap j of phase p sits
+// d = p - (j - off) * 4 fine samples from the output instant, h = sinc(d / 4) * I0(beta * sqrt(1 - (d / 32)^2)) / I0(beta), every phase
+// normalized in double to a gain of 1 at DC.  sinc is exactly 0 at the non-zero integers, so phase 0 is the unit tap.  The filter lives
+// in normalized frequency: the same taps serve every rate.
+void truepeak_design(float* taps) {
+    constexpr int P = TP_PHASES, T = TP_TAPS;
+    const double half = (double)T * P / 2.0, i0b = bessel_i0(TP_BETA);
+    for (int p = 0; p < P; ++p) {
+        double h[T], sum = 0.0;
+        for (int j = 0; j < T; ++j) {
+            const int d = p - (j - TP_OFF) * P;
+            const double x = (double)d / P;
+            const double sinc = d == 0 ? 1.0 : (d % P == 0 ? 0.0 : std::sin(M_PI * x) / (M_PI * x));
+            const double r = (double)d / half;
+            const double w = r * r < 1.0 ? bessel_i0(TP_BETA * std::sqrt(1.0 - r * r)) / i0b : 0.0;
+            h[j] = sinc * w;
+            sum += h[j];
+        }
+        for (int j = 0; j < T; ++j) taps[p * T + j] = (float)(h[j] / sum);
+    }
+}
+
+TpCoef truepeak_coef() {
+    float taps[TP_PHASES * TP_TAPS];
+    truepeak_design(taps);
+    TpCoef c;
+    for (int p = 1; p < TP_PHASES; ++p)
+        for (int j = 0; j < TP_TAPS; ++j) c.h[p - 1][j] = taps[p * TP_TAPS + j];
+    return c;
+}
+
+void Engine::set_peak_mode(int mode) {
+    if (mode != STN_PEAK_SAMPLE && mode != STN_PEAK_TRUE)
+        throw std::invalid_argument("peak mode " + std::to_string(mode) + ": must be STN_PEAK_SAMPLE (0) or STN_PEAK_TRUE (1)");
+    pk_true_ = mode == STN_PEAK_TRUE;
+}
+
+void Engine::tp_release() {
+    if (tp_buf_) (void)hipFree(tp_buf_);
+    tp_buf_ = nullptr; tp_buf_cap_ = 0;
+}
+
+// grow-only scratch (not part of the resident batch: growing it re-keys no captured graph)
+Engine::TpScratch Engine::tp_scratch(int64_t rows, int64_t W, bool with_env) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t nc = (size_t)rows * (size_t)lo_chunks(W), r4 = up((size_t)rows * 4);
+    const size_t o_pk = 0, o_res = o_pk + up(nc * 4), o_env = o_res + 4 * r4, need = o_env + (with_env ? up((size_t)rows * (size_t)W * 4) : 0);
+    if (!tp_buf_ || need > tp_buf_cap_) {
+        sync();  // the previous fetch may still be reading it
+        if (tp_buf_) (void)hipFree(tp_buf_);
+        tp_buf_ = nullptr; tp_buf_cap_ = 0;
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&tp_buf_), need + need / 4));
+        tp_buf_cap_ = need + need / 4;
+    }
+    auto at = [&](size_t o) { return reinterpret_cast<float*>(tp_buf_ + o); };
+    return {at(o_pk), at(o_res), at(o_res + r4), at(o_res + 2 * r4), at(o_res + 3 * r4), with_env ? at(o_env) : nullptr};
+}
+
+void Engine::tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float c, float* tp, float* trim) {
+    const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
+    {
+        StageSpan span(*this, "out", "true_peak", 97.0 * samples, samples * 4 + chunks * 4);
+        launch_truepeak(s_, x, rows, W, n, g, pk, nullptr);
+        STN_HIP(hipGetLastError());
+        span.next("true_peak_rows", chunks, chunks * 4 + (double)rows * 8);
+        launch_truepeak_rows(s_, rows, W, n, pk, c, tp, trim);
+    }
+    STN_HIP(hipGetLastError());
+}
+
+void Engine::batch_true_peak(float* tp_in, float* tp_out, float* trim) {
+    const int64_t Wo = out_row_len();  // (throws without a finished batch)
+    const int64_t B = bt_.B;
+    const float c = (float)std::pow(10.0, (double)lo_ceiling_ / 20.0);
+    // a reporting call, as batch_limiter is: the stage runs again and 12 bytes per row are read back
+    const float* src = out_source(Wo);
+    const float* g = lo_batch(src, Wo, lo_on_) + 2 * B;  // (uploads the spans: lo_n_ptr_)
+    const bool lim_true = limiter_active() && pk_true_;
+    const TpScratch sc = tp_scratch(B, Wo, lim_true);   // (sized for the limiter's use below: it moves no more)
+    tp_rows(src, B, Wo, lo_n_ptr_, nullptr, sc.pk, c, sc.tp_in, nullptr);
+    const float* d_out = sc.tp_in;
+    const float* d_trim = nullptr;
+    if (lo_on_) {
+        if (limiter_active()) {
+            const LmScratch lm = lm_rows(src, B, Wo, g);
+            d_trim = lm.trim;
+            tp_rows(lm.y, B, Wo, lo_n_ptr_, lm.trim, sc.pk, c, sc.tp_out, nullptr);
+        } else {
+            tp_rows(src, B, Wo, lo_n_ptr_, g, sc.pk, c, sc.tp_out, nullptr);
+        }
+        d_out = sc.tp_out;
+    }
+    if (tp_in) STN_HIP(hipMemcpyAsync(tp_in, sc.tp_in, (size_t)B * 4, hipMemcpyDeviceToHost, s_));
+    if (tp_out) STN_HIP(hipMemcpyAsync(tp_out, d_out, (size_t)B * 4, hipMemcpyDeviceToHost, s_));
+    if (trim) {
+        if (d_trim) STN_HIP(hipMemcpyAsync(trim, d_trim, (size_t)B * 4, hipMemcpyDeviceToHost, s_));
+        else std::fill(trim, trim + B, 1.0f);
+    }
+    sync();
+}
+
+static std::vector<int64_t> tp_spans(const char* who, int rows, int W, const int64_t* n) {
+    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
+    for (int r = 0; r < rows && n; ++r) {
+        if (n[r] < 0 || n[r] > W) throw std::invalid_argument(std::string(who) + ": n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
+        nn[(size_t)r] = n[r];
+    }
+    return nn;
+}
+
+const char* Engine::op_true_peak(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp, float* env,
+                                 float* pk) {
+    STN_HIP(hipSetDevice(device_));
+    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
+        throw std::invalid_argument("true peak: sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")");
+    const std::vector<int64_t> nn = tp_spans("op_true_peak", rows, W, n);
+    ar_.reset();
+    const size_t nx = (size_t)rows * W, nc = (size_t)rows * (size_t)lo_chunks(W), off = x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
+    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
+    float* denv = env ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
+    float* dpk = static_cast<float*>(ar_.alloc(nc * 4));
+    float* dtp = static_cast<float*>(ar_.alloc((size_t)rows * 4));
+    int64_t* dn = static_cast<int64_t*>(ar_.alloc((size_t)rows * 8));
+    float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
+    // what a launch fails to write reads back as the quiet NaN, not as an earlier call's value
+    if (denv) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(denv), 0x7FC00000, nx, s_));
+    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dpk), 0x7FC00000, nc, s_));
+    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dtp), 0x7FC00000, (size_t)rows, s_));
+    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
+    launch_truepeak(s_, dx, rows, W, dn, dg, dpk, denv);
+    STN_HIP(hipGetLastError());
+    launch_truepeak_rows(s_, rows, W, dn, dpk, 1.0f, dtp, nullptr);
+    STN_HIP(hipGetLastError());
+    if (tp) STN_HIP(hipMemcpyAsync(tp, dtp, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    if (env) STN_HIP(hipMemcpyAsync(env, denv, nx * 4, hipMemcpyDeviceToHost, s_));
+    if (pk) STN_HIP(hipMemcpyAsync(pk, dpk, nc * 4, hipMemcpyDeviceToHost, s_));
+    sync();  // (nn is read by the copy above until here)
+    return truepeak_staging_form(dx, W, denv);
+}
+
+}  // namespace stn

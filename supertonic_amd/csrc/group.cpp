@@ -230,6 +230,9 @@ int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms) {
         const S* p = static_cast<const S*>(a);
         return stn_set_limiter(h, p->on, p->ms); }, &v, 0);
 }
+int stn_group_set_peak_mode(stn_group* g, int mode) {
+    return for_all(g, "stn_set_peak_mode", [](stn_handle* h, const void*, uint64_t v) { return stn_set_peak_mode(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)mode);
+}
 int stn_group_set_encoding(stn_group* g, int enc) {
     if (!g) return STN_ERR_INVALID;
     if (stn_encoding_bytes(enc) == 0) return fail(g, STN_ERR_INVALID, "stn_group_set_encoding: unknown encoding " + std::to_string(enc));

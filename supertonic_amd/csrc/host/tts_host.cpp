@@ -275,6 +275,14 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
                 check(h, stn_set_limiter(h, 1, opts.limiter_ms));
             }
         }
+        if (opts.true_peak) {
+            if (std::isnan(opts.loudness_lufs)) throw std::runtime_error("the true-peak mode needs loudness normalization (it is the ceiling of the loudness gain)");
+            if (grp) {
+                if (stn_group_set_peak_mode(grp, STN_PEAK_TRUE) != STN_OK) throw std::runtime_error(std::string("peak mode: ") + stn_group_last_error(grp));
+            } else {
+                check(h, stn_set_peak_mode(h, STN_PEAK_TRUE));
+            }
+        }
         // (refused here, while this function still owns the handle: once tts owns it, a throw would destroy it twice)
         if (!std::isnan(opts.trim_silence_db)) check(h, stn_set_silence_trim(h, 1, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms));
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)

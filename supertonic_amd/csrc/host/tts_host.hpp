@@ -65,6 +65,7 @@ struct EngineOptions {
     float loudness_ceiling_dbfs = -1.0f;  // sample-peak ceiling that caps the normalization gain.  CLI --peak-ceiling DBFS
     float limiter_ms = std::numeric_limits<float>::quiet_NaN();  // with loudness: the full loudness gain, the ceiling held by a look-ahead peak
                                    // limiter of this many milliseconds (stn_set_limiter, [0.5, 10]); NaN: off.  CLI --limiter MS
+    bool true_peak = false;        // with loudness: the ceiling is a true-peak ceiling (dBTP, 4x oversampled; stn_set_peak_mode).  CLI --peak-mode {sample,true}
     bool loudness_scope_text = false;  // long-form call() with loudness on: the joined text normalized as one programme with one gain instead
                                    // of every chunk on its own.  One device only.  CLI --loudness-scope {chunk,text}
     bool trim_chunks = false;      // long-form call(): every chunk cut at its duration before the join.  CLI --trim-chunks

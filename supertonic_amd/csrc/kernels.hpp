@@ -472,6 +472,7 @@ constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P =
 inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
 // Kaiser-windowed sinc for the pair (host only): fills f (not f.dev).  Empty string on success, else why the pair is refused.
 std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
+double bessel_i0(double x);  // the Kaiser window's shape (engine_resample.cpp)
 // rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride samples (dst_stride >= W_out) in encoding enc (the encoded
 // bytes are those of the fp32 output followed by launch_store_rows without a gain)
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride);
@@ -525,8 +526,30 @@ constexpr int LM_WG = 256;            // lanes per workgroup
 constexpr int LM_TILE = 2048;         // samples of a row a workgroup owns (8 consecutive ones per lane)
 constexpr int LM_MAX_A = 1920;        // 10 ms at 192 kHz
 inline int64_t lm_tiles(int64_t W) { return (W + LM_TILE - 1) / LM_TILE; }
+// env (device rows x W, or null): the true-peak envelope of the row times its gain (launch_truepeak).  Non-null, r[j] is 1 where
+// env[j] <= c and c / env[j] elsewhere (1 outside [0, n)) instead of the sample's own; everything else is unchanged.  Null is the
+// kernel without that argument.
 void launch_limiter(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, const float* gain, float c, int A, const float* wts,
-                    float* y, float* s_out, int* pcnt, float* pmin);
+                    float* y, float* s_out, int* pcnt, float* pmin, const float* env = nullptr);
 void launch_limiter_rows(hipStream_t s, int64_t rows, int64_t W, const int* pcnt, const float* pmin, int64_t* limited, float* red);
+
+// True peak by 4x oversampling (kernels_truepeak.hip; the filter design and the consumers are engine_truepeak.cpp; DESIGN.md section 16;
+// ITU-R BS.1770-4 Annex 2).  For a row with span n, x = 0 outside [0, n): u[i][ph] = sum_j taps[ph][j] x[i - 7 + j] (an fp32 FMA chain,
+// j ascending) is the value at i + ph/4 for ph in {1, 2, 3} and i in [-1, n - 1]; U[i] = max_ph |u[i][ph]|;
+// p[i] = max(|x[i]|, U[i-1], U[i]) for i < n and |x[i]| behind; pk[row][k] = max p over chunk k's samples inside the span (+0.0 when
+// there are none; chunks of LO_CHUNK samples, the loudness measurement's pk layout).
+constexpr int TP_PHASES = 4, TP_TAPS = 16, TP_OFF = 7;
+constexpr double TP_BETA = 8.0;
+struct TpCoef { float h[TP_PHASES - 1][TP_TAPS]; };  // phases 1..3 (phase 0 is the unit tap: the sample itself)
+// all four phases [4][16] as fp32, every phase normalized in double to DC gain 1 (host only; the same taps serve every rate)
+void truepeak_design(float* taps64);
+TpCoef truepeak_coef();
+// rows x W fp32 (row stride W) with spans n[rows] (device, <= W), times gain[row] (device, or null: one fp32 multiply at staging) ->
+// pk [rows][lo_chunks(W)] (every entry written) and, when env is not null, env [rows][W] = p (not x)
+void launch_truepeak(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, const float* gain, float* pk, float* env);
+// the staging path launch_truepeak takes: "vec" (16-byte loads and stores: W % 4 == 0, x and env 16-byte aligned) or "scalar"
+const char* truepeak_staging_form(const float* x, int64_t W, const float* env);
+// tp[row] = max of pk[row][..] over the span's chunks (0 for an empty span); trim[row] (or null) = 1 where tp <= c, else c / tp
+void launch_truepeak_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const float* pk, float c, float* tp, float* trim);
 
 }  // namespace stn

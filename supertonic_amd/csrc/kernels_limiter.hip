@@ -35,10 +35,13 @@ __device__ __forceinline__ float lm_r(float v, float c) {
 __device__ __forceinline__ float lm_clamp(float v, float c) { return v > c ? c : (v < -c ? -c : v); }
 __device__ __forceinline__ int lm_pad(int j) { return j + (j >> 3); }
 
+// kEnv: r comes from the true-peak envelope env (rows x W: launch_truepeak of x * g) instead of the sample itself
+template <bool kEnv>
 __global__ void __launch_bounds__(LM_WG) limiter_kernel(const float* __restrict__ x, int64_t W, int vec, const int64_t* __restrict__ nrow,
                                                         const float* __restrict__ gain, float c, int A, int bufw,
                                                         const float* __restrict__ wts, float* __restrict__ y, float* __restrict__ sout,
-                                                        int64_t tiles, int* __restrict__ pcnt, float* __restrict__ pmin) {
+                                                        int64_t tiles, int* __restrict__ pcnt, float* __restrict__ pmin,
+                                                        const float* __restrict__ env) {
     extern __shared__ float lds[];
     __shared__ int redc[LM_WG / 64];
     __shared__ float redm[LM_WG / 64];
@@ -49,6 +52,7 @@ __global__ void __launch_bounds__(LM_WG) limiter_kernel(const float* __restrict_
     const float* __restrict__ xr = x + row * W;
     float* __restrict__ yr = y + row * W;
     float* __restrict__ sr = sout ? sout + row * W : nullptr;
+    const float* __restrict__ er = kEnv ? env + row * W : nullptr;
     const int N = LM_TILE + 2 * A;  // staged samples: local j is sample t0 - A + j
     float* b0 = lds;
     float* b1 = lds + bufw;
@@ -57,7 +61,7 @@ __global__ void __launch_bounds__(LM_WG) limiter_kernel(const float* __restrict_
         for (int j = tid; j < N; j += LM_WG) {
             const int64_t i = t0 - A + j;
             float r = 1.0f;
-            if (i >= 0 && i < n) r = lm_r(xr[i] * g, c);
+            if (i >= 0 && i < n) r = kEnv ? lm_r(er[i], c) : lm_r(xr[i] * g, c);
             b0[j] = r;
             any |= r < 1.0f;
         }
@@ -136,7 +140,7 @@ __global__ void __launch_bounds__(LM_WG) limiter_kernel(const float* __restrict_
             if (i < n) {
                 const float sp = src[lm_pad(o)];
                 if (sp < 1.0f) {
-                    s = fminf(sp, lm_r(v, c));
+                    s = fminf(sp, kEnv ? lm_r(er[i], c) : lm_r(v, c));
                     ++cnt;
                     mn = fminf(mn, s);
                 }
@@ -195,7 +199,7 @@ int lm_bufw(int A) {
 }  // namespace
 
 void launch_limiter(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, const float* gain, float c, int A, const float* wts,
-                    float* y, float* s_out, int* pcnt, float* pmin) {
+                    float* y, float* s_out, int* pcnt, float* pmin, const float* env) {
     if (rows <= 0 || W <= 0) return;
     if (rows > 65535) throw std::invalid_argument("limiter: more than 65535 rows");
     if (A < 1 || A > LM_MAX_A) throw std::invalid_argument("limiter: look-ahead of " + std::to_string(A) + " samples outside [1, " + std::to_string(LM_MAX_A) + "]");
@@ -206,8 +210,10 @@ void launch_limiter(hipStream_t s, const float* x, int64_t rows, int64_t W, cons
     auto al16 = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
     const int vec = (W % 4 == 0 && al16(x) && al16(y) && (!s_out || al16(s_out))) ? 1 : 0;
     const int bufw = lm_bufw(A);
-    STN_KLAUNCH(limiter_kernel, dim3((unsigned)tiles, (unsigned)rows), dim3(LM_WG), (unsigned)(2 * bufw * sizeof(float)), s, x, W, vec, n, gain, c, A,
-                bufw, wts, y, s_out, tiles, pcnt, pmin);
+    if (env) STN_KLAUNCH(limiter_kernel<true>, dim3((unsigned)tiles, (unsigned)rows), dim3(LM_WG), (unsigned)(2 * bufw * sizeof(float)), s, x, W, vec, n,
+                         gain, c, A, bufw, wts, y, s_out, tiles, pcnt, pmin, env);
+    else STN_KLAUNCH(limiter_kernel<false>, dim3((unsigned)tiles, (unsigned)rows), dim3(LM_WG), (unsigned)(2 * bufw * sizeof(float)), s, x, W, vec, n,
+                     gain, c, A, bufw, wts, y, s_out, tiles, pcnt, pmin, env);
 }
 
 void launch_limiter_rows(hipStream_t s, int64_t rows, int64_t W, const int* pcnt, const float* pmin, int64_t* limited, float* red) {

@@ -13,7 +13,8 @@ import os
 import threading
 import time
 import zipfile
-from typing import List, Optional, Union
+from collections import namedtuple
+from typing import List, Literal, Optional, Union
 
 import numpy as np
 
@@ -21,6 +22,10 @@ from . import binding, host
 from .tts import Style, load_text_to_speech, load_voice_style
 
 AVAILABLE_LANGS = host.AVAILABLE_LANGS
+
+
+# the loudness entry of a batch key: requests merge only when all four agree (limiter_ms / peak_mode None: the synthesizer's own setting)
+LoudnessKey = namedtuple("LoudnessKey", "lufs ceiling limiter_ms peak_mode")
 
 
 class _Job:
@@ -49,7 +54,7 @@ class DynamicBatcher:
         self._t.start()
 
     def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
-               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None):
+               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
         the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
@@ -60,12 +65,14 @@ class DynamicBatcher:
         synthesizer's own setting; top_db or (top_db, keep_ms, fade_ms)): the waves without their leading and trailing silence; part of
         the batch key as well (the setting covers a whole batch), and validated here.  limiter_ms (with loudness; None: the
         synthesizer's own setting): the full loudness gain, the ceiling held by a look-ahead peak limiter of that many milliseconds;
-        validated here, part of the key's loudness entry, and without effect (and out of the key) when loudness is None."""
+        validated here, part of the key's loudness entry, and without effect (and out of the key) when loudness is None.  peak_mode
+        ("sample" or "true"; None: the synthesizer's own setting): peak_ceiling as a sample-peak or a true-peak ceiling; validated here
+        and part of the key's loudness entry in the same way."""
         lim = None if limiter_ms is None else binding.limiter_args(float(limiter_ms))[1]
+        if peak_mode is not None:
+            binding.peak_mode_id(peak_mode)
         ts = None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:]
-        lo = None if loudness is None else (float(loudness), float(peak_ceiling))
-        if lo is not None and lim is not None:
-            lo += (lim,)
+        lo = None if loudness is None else LoudnessKey(float(loudness), float(peak_ceiling), lim, None if peak_mode is None else str(peak_mode))
         enc = None if encoding is None else binding.encoding_id(encoding)
         key = (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc)
         if loudness_scope != "chunk" or trim_chunks:  # (requests that use neither batch exactly as before)
@@ -135,9 +142,11 @@ class DynamicBatcher:
                 if ts is not None:
                     extra["trim_silence"] = ts
                 if lo is not None:
-                    extra["loudness"] = lo[:2]
-                    if len(lo) == 3:
-                        extra["limiter"] = lo[2]
+                    extra["loudness"] = (lo.lufs, lo.ceiling)
+                    if lo.limiter_ms is not None:
+                        extra["limiter"] = lo.limiter_ms
+                    if lo.peak_mode is not None:
+                        extra["peak_mode"] = lo.peak_mode
                 if enc is not None:
                     extra["encoding"] = enc
                 joined = getattr(self.tts, "joined_batch", None)
@@ -226,6 +235,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         peak_ceiling: float = Field(-1.0, ge=-30.0, le=0.0, description="Sample-peak ceiling in dBFS that caps the loudness gain.")
         limiter_ms: Optional[float] = Field(None, ge=0.5, le=10.0, description="With loudness: the full loudness gain, and a look-ahead peak "
                                                                                "limiter of this many milliseconds holds peak_ceiling; null: off.")
+        peak_mode: Optional[Literal["sample", "true"]] = Field(None, description="With loudness: 'sample' holds peak_ceiling as a sample peak, 'true' as a true peak "
+                                                           "(dBTP, 4x oversampled on the GPU); null: the synthesizer's setting.")
         encoding: str = Field("pcm16", description="Sample format of the WAV files (encoded on the GPU): pcm16, pcm24, f32, mulaw, alaw.")
         loudness_scope: str = Field("chunk", description="Non-batch mode with loudness: 'chunk' normalizes every chunk of a long text on its own, "
                                                          "'text' the joined text as one BS.1770 programme with one gain.")
@@ -269,6 +280,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             extra["loudness"] = (req.loudness, req.peak_ceiling)
             if req.limiter_ms is not None:
                 extra["limiter"] = req.limiter_ms
+            if req.peak_mode is not None:
+                extra["peak_mode"] = req.peak_mode
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
@@ -288,7 +301,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
-                                         trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms)
+                                         trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:

@@ -54,7 +54,7 @@ class TextToSpeech:
     returning (wav [B, W] float32, duration [B] float32).  One instance = one engine handle = one GPU; calls are
     serialised by a lock (the handle is single-threaded by contract)."""
 
-    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None):
+    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None, peak_mode=None):
         self.engine = engine
         self.text_processor = text_processor
         self.cfgs = cfgs
@@ -78,6 +78,12 @@ class TextToSpeech:
         self.limiter = _limiter_setting(limiter)
         if self.limiter is not None:
             engine.set_limiter(self.limiter)
+        # the ceiling of the loudness gain as a sample-peak ("sample", the default) or a true-peak ceiling ("true": 4x oversampled,
+        # Engine.set_peak_mode); it acts only while loudness normalization is on
+        self.peak_mode = "sample" if peak_mode is None else peak_mode
+        binding.peak_mode_id(self.peak_mode)
+        if self.peak_mode != "sample":
+            engine.set_peak_mode(self.peak_mode)
         self.base_chunk_size = cfgs["ae"]["base_chunk_size"]
         self.chunk_compress_factor = cfgs["ttl"]["chunk_compress_factor"]
         self.ldim = cfgs["ttl"]["latent_dim"]
@@ -92,13 +98,14 @@ class TextToSpeech:
         return self.noise_seed + self._calls - 1
 
     def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None,
-               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None):
+               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None, peak_mode=None):
         """lengths: returns (wav, duration, len) with len [B] the samples each row holds from column 0: its trimmed segment with
         trimming on (Engine.batch_silence_edges, never a duration product), else None."""
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         trim = self.trim_silence if trim_silence is None else _trim_setting(trim_silence)  # (validated before anything is set)
         lim = None if limiter is None else _limiter_setting(limiter)
+        binding.peak_mode_id(peak_mode)
         ids, mask = self.text_processor(text_list, lang_list)
         with self._lock:
             # length-aware batches (the chunks of a long text, the service's merged requests) come in ever-changing lengths: shape
@@ -114,6 +121,8 @@ class TextToSpeech:
                 self.engine.set_silence_trim(trim)
             if limiter is not None:  # this call's limiter (fetch-time as well)
                 self.engine.set_limiter(lim)
+            if peak_mode is not None:  # this call's peak mode (fetch-time as well)
+                self.engine.set_peak_mode(peak_mode)
             try:
                 if join is not None:  # joined on the GPU by the fetch (Engine.batch_fetch_joined's arguments)
                     self.engine.batch_upload(ids, mask, style.ttl, style.dp)
@@ -142,6 +151,8 @@ class TextToSpeech:
                     self.engine.set_silence_trim(self.trim_silence)
                 if limiter is not None:
                     self.engine.set_limiter(self.limiter)
+                if peak_mode is not None:
+                    self.engine.set_peak_mode(self.peak_mode)
 
     def latent_lengths(self, durations):
         """Latent frames each utterance occupies (get_latent_mask, py/helper.py:276-282) from its returned duration."""
@@ -157,7 +168,7 @@ class TextToSpeech:
         return -(-int(n) * P // Q)
 
     def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None,
-                   trim_silence=None, limiter=None):
+                   trim_silence=None, limiter=None, peak_mode=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
         and the durations.  The building block of the long-form path and of the service's dynamic batching.
@@ -168,7 +179,7 @@ class TextToSpeech:
         length the GPU found.  limiter (this call's: False = off, True = 5 ms, or the look-ahead in ms): with normalization, every
         utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling."""
         wav, dur, seg = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
-                                    loudness=loudness, encoding=encoding, trim_silence=trim_silence, lengths=True, limiter=limiter)
+                                    loudness=loudness, encoding=encoding, trim_silence=trim_silence, lengths=True, limiter=limiter, peak_mode=peak_mode)
         if seg is not None:
             return [wav[i, : int(n)] for i, n in enumerate(seg)], dur
         cs = self.base_chunk_size * self.chunk_compress_factor
@@ -176,7 +187,7 @@ class TextToSpeech:
         return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
     def joined_batch(self, text_list, lang_list, style, total_step, speed=1.05, rows=None, silence_duration=0.3, output_rate=None,
-                     loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter=None):
+                     loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None):
         """solo_batch whose rows are joined on the GPU into len(rows) waves: rows[g] consecutive utterances each (None: all of them
         in one), silence_duration (one value, or one per wave) seconds of silence between two of them — the encoding's zero codeword.
         Returns (list of joined waves, their durations: the reference's fp32 sum d = dur_0; d += dur_i + silence).  loudness_scope,
@@ -193,11 +204,11 @@ class TextToSpeech:
         join = {"rows": rows, "gap_samples": [int(s * rate) for s in sil], "gap_seconds": sil.astype(np.float32),
                 "mode": "trim" if trim_chunks else "whole", "gain_scope": "programme" if loudness_scope == "text" else "row"}
         waves, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
-                                 loudness=loudness, encoding=encoding, join=join, trim_silence=trim_silence, limiter=limiter)
+                                 loudness=loudness, encoding=encoding, join=join, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
         return waves, dur
 
     def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None, loudness_scope="chunk",
-                 trim_chunks=False, trim_silence=None, limiter=None):
+                 trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None):
         """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence on the GPU
         (one joined fetch: py/helper.py:235-243's untrimmed chunk waves with zeros between).  With loudness normalization on,
         loudness_scope="chunk" normalizes each chunk as its own row (its own gain); "text" normalizes the joined text as one
@@ -211,21 +222,21 @@ class TextToSpeech:
         chunks = host.chunk_text(text, 120 if lang == "ko" else 300)
         trimming = (self.trim_silence if trim_silence is None else _trim_setting(trim_silence)) is not None
         if len(chunks) == 1 and not trim_chunks and not trimming:  # (one chunk is its own programme: the row's gain is the text's)
-            return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding, trim_silence=trim_silence, limiter=limiter)
+            return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
         waves, dur = self.joined_batch(chunks, [lang] * n, rep, total_step, speed, silence_duration=silence_duration, encoding=encoding,
-                                       loudness_scope=loudness_scope, trim_chunks=trim_chunks, trim_silence=trim_silence, limiter=limiter)
+                                       loudness_scope=loudness_scope, trim_chunks=trim_chunks, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
         return waves[0][None, :], np.array([dur[0]], np.float32)
 
     def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None, trim_silence=None,
-              lengths=False, limiter=None):
+              lengths=False, limiter=None, peak_mode=None):
         """One padded batch -> (wav [B, W] float32, duration [B]); with an encoding (a name or binding.ENC_*), the rows in that sample
         encoding instead, encoded on the GPU (binding.encoded_empty's dtypes).  trim_silence (as solo_batch): row b holds its trimmed
         segment from column 0 and the zero codeword behind it; lengths=True adds a third result, the segments' lengths [B] (None with
         trimming off)."""
         return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness,
-                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter)
+                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter, peak_mode=peak_mode)
 
 
 def _limiter_setting(v):
@@ -260,7 +271,7 @@ def load_cfgs(onnx_dir):
 
 
 def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None,
-                        loudness=None, trim_silence=None, limiter=None):
+                        loudness=None, trim_silence=None, limiter=None, peak_mode=None):
     """py/helper.py:316-337.  use_gpu=True is the only mode (the reference only had the CPU one).  An unusable asset directory is an
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
@@ -270,9 +281,12 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
     stn_set_loudness); None leaves the level as synthesized.  `trim_silence`: trim leading and trailing silence of every utterance by
     level on the GPU (top_db, or (top_db, keep_ms, fade_ms); include/stn.h, stn_set_silence_trim); None returns the waves as synthesized.
     `limiter`: with `loudness`, every utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling (True = 5 ms of
-    look-ahead, or milliseconds in [0.5, 10]; include/stn.h, stn_set_limiter); None keeps the capped gain."""
+    look-ahead, or milliseconds in [0.5, 10]; include/stn.h, stn_set_limiter); None keeps the capped gain.
+    `peak_mode`: "true" makes the ceiling of `loudness` a true-peak ceiling (dBTP, 4x oversampled; include/stn.h, stn_set_peak_mode); None
+    or "sample" keeps the sample-peak ceiling."""
     _trim_setting(trim_silence)  # (refused before the engine is created)
     _limiter_setting(limiter)
+    binding.peak_mode_id(peak_mode)
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
     if not use_gpu:
@@ -294,6 +308,6 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
                 "ttl": {"chunk_compress_factor": a.chunk_compress_factor, "latent_dim": a.latent_dim}}
         tp = host.UnicodeProcessor(host.synthetic_indexer())
         synthetic = True
-    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter)
+    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter, peak_mode)
     tts.synthetic = synthetic
     return tts
