@@ -181,13 +181,7 @@ Engine::~Engine() {
     if (pin_seed_) (void)hipHostFree(pin_seed_);
     if (seed_dev_) (void)hipFree(seed_dev_);
     rs_release();
-    lo_release();
-    ed_release();
-    lm_release();
-    tp_release();
-    if (out_f32_) (void)hipFree(out_f32_);
-    if (out_enc_) (void)hipFree(out_enc_);
-    if (join_tab_) (void)hipFree(join_tab_);
+    lo_release();  // (the fetch scratch, DevBuf members, goes with the members)
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);
         if (f.dev) (void)hipFree(f.dev);

@@ -76,6 +76,46 @@ std::string limiter_check(int hz, float lookahead_ms);
 int64_t limiter_samples(int hz, float lookahead_ms);
 std::vector<float> limiter_window(int hz, float lookahead_ms);
 
+// Argument checks the settings and the op entries share (engine_loudness.cpp).  rate_check: why hz is refused for the feature named
+// `what`, or ""; loudness_check: why a target (not checked when null) or a ceiling is refused, or ""; refuse: throws a reason that is
+// not ""; spans: row r's span n[r] (W when n is null) of rows x W, or throws "<who>: n[r] = ... outside [0, W]"
+std::string rate_check(const char* what, int hz);
+std::string loudness_check(const float* target_lufs, float ceiling_dbfs);
+inline void refuse(const std::string& why) { if (!why.empty()) throw std::invalid_argument(why); }
+std::vector<int64_t> spans(const char* who, int rows, int W, const int64_t* n);
+
+class Engine;
+// One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
+// graph).  reserve returns the block, of at least `bytes`; a block too small is replaced, behind a sync of the engine (a fetch in
+// flight may still read it), by one a quarter larger than asked, and *moved (when given) says so: what the old block held is gone.
+// A pointer from reserve is valid until the next larger reserve on the same buffer: a caller that hands one out sizes the buffer up
+// front for every use that follows.  Freed with the engine, after its streams are drained.
+class DevBuf {
+   public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    char* reserve(Engine& e, size_t bytes, bool* moved = nullptr);
+    const void* get() const { return p_; }
+
+   private:
+    char* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// Consecutive arrays from a block, each on a 256-byte boundary of it.  Without a block (null) no pointer is formed: off, the bytes
+// taken so far, is then the size the same sequence of take calls needs.
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    template <typename T> T* take(size_t count) {
+        const size_t o = off;
+        off += (count * sizeof(T) + 255) / 256 * 256;
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+};
+
 struct KernelStat { double ms = 0; long launches = 0; double flops = 0; double bytes = 0; };
 
 class Engine {
@@ -618,10 +658,15 @@ class Engine {
     bool lo_on_ = false;
     float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
     LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
-    char* lo_buf_ = nullptr; size_t lo_buf_cap_ = 0;  // fetch-time scratch of the measurement (grow-only, outside the graph key)
+    DevBuf lo_buf_;                    // fetch-time scratch of the measurement
     std::vector<int64_t> lo_n_;        // the row lengths last uploaded into lo_buf_, at lo_n_ptr_ (empty: none)
     int64_t* lo_n_ptr_ = nullptr;
-    struct LoScratch { float *st, *pk, *pa, *pb, *res; int64_t* n; };
+    // what a measurement leaves on the device, [rows] each, and the spans it measured
+    struct LoRes { const float *lufs = nullptr, *peak = nullptr, *gain = nullptr; const int64_t* n = nullptr; };
+    // per chunk the state (16 B), the peak and the two energy shares; per row the three results (res [3][rows], as the gate writes them:
+    // `out` names them) and the length; bytes: the size of it all
+    struct LoScratch { float *st, *pk, *pa, *pb, *res; int64_t* n; LoRes out; size_t bytes; };
+    static LoScratch lo_layout(char* base, int64_t rows, int64_t W);
     LoScratch lo_scratch(int64_t rows, int64_t W);
     void lo_prepare(LoudTable& t, int hz);
     void lo_release();
@@ -633,21 +678,24 @@ class Engine {
     // op_loudness and op_loudness_ex: the upload, the measurement, the read-back
     void lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
                float* peak, float* gain);
-    // rows x W fp32 on the device (x) with row spans n measured on the stream against table t: returns res (device [3][rows]: L, peak,
-    // gain).  n is uploaded only when it differs from what the scratch holds.
+    // rows x W fp32 on the device (x) with row spans n measured on the stream against table t.  n is uploaded only when it differs from
+    // what the scratch holds.
     // true_peak: the gate's peak is the row's true peak (section 16).  The callers that own the setting (lo_batch, join_measure) pass
     // lo_true_peak(); the op-level callers keep the sample peak.
-    float* lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
-                   bool true_peak = false);
+    LoRes lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
+                  bool true_peak = false);
     // (with the limiter active nothing caps the gain: the limiter measures the envelope of the scaled row itself)
     bool lo_true_peak() const { return true_peak_on() && !limiter_active(); }
-    // the finished batch's B rows x Wo at the output rate (x) measured on the stream: returns res (device [3][B]: L, peak, gain)
-    float* lo_batch(const float* x, int64_t Wo, bool on);
+    // the finished batch's B rows x Wo at the output rate (x) measured on the stream
+    LoRes lo_batch(const float* x, int64_t Wo, bool on);
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
-    char* ed_buf_ = nullptr; size_t ed_buf_cap_ = 0;  // fetch-time scratch of the detection (grow-only, outside the graph key)
-    struct EdScratch { float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; };
+    DevBuf ed_buf_;                    // fetch-time scratch of the detection
+    // per chunk the two frame shares, per frame the level, per row the edges, the span and the one-member programme of the per-row
+    // trimmed fetch
+    struct EdScratch { float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; size_t bytes; };
+    static EdScratch ed_layout(char* base, int64_t rows, int64_t W, int hz);
     EdScratch ed_scratch(int64_t rows, int64_t W, int hz);
     // what the scratch holds: the edges (and per-row programmes) of batch `seq` at rate hz under (db, keep, fade); host: read back
     struct EdKey {
@@ -656,36 +704,42 @@ class Engine {
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
     std::vector<int64_t> ed_host_, ed_n_;   // [B][2] edges read back; [B] spans
-    float* st_win_ = nullptr; size_t st_win_cap_ = 0; int st_win_hz_ = 0; float st_win_ms_ = -1.0f;  // the fade window on the device, per (rate, fade_ms)
+    DevBuf st_win_; int st_win_hz_ = 0; float st_win_ms_ = -1.0f;  // the fade window on the device, per (rate, fade_ms)
     const float* st_window(int hz);
+    // the two detection launches on rows x W fp32 (x) at hz with the spans in sc.n: the edges and per-row programmes into sc
+    void ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc);
     // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already
     EdScratch ed_batch(const float* x, int64_t Wo);
     const std::vector<int64_t>& ed_batch_host();  // its edges on the host (one device->host read of 2 B integers per batch and setting)
-    void ed_release();
     bool lm_on_ = false;
     float lm_ms_ = 5.0f;
     float lo_cap() const { return limiter_active() ? INFINITY : lo_ceiling_; }  // the gate's ceiling: the limiter enforces it instead
-    char* lm_buf_ = nullptr; size_t lm_buf_cap_ = 0;  // fetch-time scratch of the limiter (grow-only, outside the graph key)
-    struct LmScratch { float* y; int* pcnt; float* pmin; int64_t* limited; float* red; const float* trim = nullptr; };
-    static size_t lm_layout(int64_t rows, int64_t W, size_t* o);  // the scratch's five offsets (o) and its size in bytes
-    static LmScratch lm_at(char* base, const size_t* o);
+    DevBuf lm_buf_;                    // fetch-time scratch of the limiter
+    // the limited rows, per tile the two partial results, per row the two results
+    struct LmScratch { float* y; int* pcnt; float* pmin; int64_t* limited; float* red; size_t bytes; const float* trim = nullptr; };
+    static LmScratch lm_layout(char* base, int64_t rows, int64_t W);
     LmScratch lm_scratch(int64_t rows, int64_t W);
-    float* lm_win_ = nullptr; size_t lm_win_cap_ = 0; int lm_win_hz_ = 0; float lm_win_ms_ = -1.0f;  // the weights on the device, per (rate, ms)
+    DevBuf lm_win_; int lm_win_hz_ = 0; float lm_win_ms_ = -1.0f;  // the weights on the device, per (rate, ms)
     const float* lm_window(int hz);
-    // rows x W fp32 on the device (x) whose spans the measurement just uploaded (lo_n_ptr_), times g (device [rows]), limited into the
-    // scratch: returns the rows (row stride W)
-    // In true-peak mode the curve follows the envelope of x * g, and .trim (device [rows]) is the gain the store behind it applies
-    LmScratch lm_rows(const float* x, int64_t rows, int64_t W, const float* g);
-    void lm_release();
+    // (engine_truepeak.cpp) per chunk the peak, per row four results, and (with_env) the envelope rows
+    struct TpScratch { float *pk, *tp_in, *tp_out, *tp_y, *trim, *env; size_t bytes; };
+    // The limiter's launches on rows x W fp32 (x) with spans n, times g (device [rows] or null), against the ceiling c with the A + 1
+    // weights w: the limited rows and the per-row results into sc, the curve into s (device [rows][W], or null).  tp (true-peak mode, or
+    // null): the envelope of x * g is taken first and drives the curve, and behind the limiter tp->tp_y and tp->trim are the true peak of
+    // the limited row and the gain that holds it at c
+    void lm_enqueue(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float c, int64_t A, const float* w, const LmScratch& sc,
+                    float* s, const TpScratch* tp);
+    // rows x W fp32 on the device (x) with spans n (device), times g (device [rows]), limited into the scratch: returns the rows (row
+    // stride W).  In true-peak mode .trim (device [rows]) is the gain the store behind it applies
+    LmScratch lm_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g);
     bool pk_true_ = false;             // the peak mode (engine_truepeak.cpp)
     bool true_peak_on() const { return pk_true_ && lo_on_; }
-    char* tp_buf_ = nullptr; size_t tp_buf_cap_ = 0;  // fetch-time scratch of the true-peak mode (grow-only, outside the graph key)
-    struct TpScratch { float *pk, *tp_in, *tp_out, *tp_y, *trim, *env; };
-    // per chunk the peak, per row four results, and (with_env) the envelope rows
+    DevBuf tp_buf_;                    // fetch-time scratch of the true-peak mode
+    static TpScratch tp_layout(char* base, int64_t rows, int64_t W, bool with_env);
     TpScratch tp_scratch(int64_t rows, int64_t W, bool with_env);
-    // tp[row] (and trim[row] against c when trim is not null) of rows x W times g (device [rows] or null), spans n (device)
-    void tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float c, float* tp, float* trim);
-    void tp_release();
+    // tp[row] (and trim[row] against c when trim is not null) of rows x W times g (device [rows] or null), spans n (device); env (device
+    // [rows][W], or null): the true-peak envelope of x * g
+    void tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float* env, float c, float* tp, float* trim);
     // ---- output stage (engine_batch.cpp): the one place that turns the finished batch into what a fetch delivers (rate, loudness,
     // sample encoding); every fetch path runs it into a device destination of rows `stride` samples apart, enc_bytes(enc) bytes each
     // With a join plan the G programme rows of the plan instead of the B rows (scope: STN_JOIN_GAIN_*)
@@ -693,10 +747,15 @@ class Engine {
     void enqueue_output(const OutRows& o);
     void enqueue_joined(const OutRows& o);
     void slot_begin(int slot, OutRows o, int64_t rows, int64_t width, const std::vector<float>& dur);  // the pipelined fetch behind both _begin calls
-    // the joined fp32 signal of the finished batch at the output rate in the fetch scratch (rows W_join apart) and its measurement
-    // (device [3][G]); the two halves of a per-programme gain
+    // The gain step between the measurement m and the store: the rows to store from, their gains and their row stride.  Those are src,
+    // m.gain and `stride`; with the limiter active (section 15) the rows x W limited in the fetch scratch, their trim (null outside true
+    // mode) and W.  Without loudness m is empty, and so is the gain.
+    struct GainedRows { const float* src; const float* g; int64_t stride; };
+    GainedRows gain_step(const float* src, int64_t rows, int64_t W, int64_t stride, const LoRes& m);
+    // the joined fp32 signal of the finished batch at the output rate in the fetch scratch (rows W_join apart) and its measurement; the
+    // two halves of a per-programme gain
     const float* join_f32(const JoinPlan& p);
-    float* join_measure(const JoinPlan& p, const float* joined, bool on);
+    LoRes join_measure(const JoinPlan& p, const float* joined, bool on);
     // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
     struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };  // tseg: trimmed sources (seg unused)
     JoinTables join_tables(const JoinPlan& p);
@@ -704,19 +763,18 @@ class Engine {
     // the pointers into those words on the device; for trimmed sources also the fade window of the output rate, uploaded here if need be
     // (st_window: why this is no static function; op_join's plans have no trimmed sources and never get there)
     JoinTables join_tables_at(const int64_t* d, const JoinPlan& p);
-    // res (device [3][n]: L, peak, gain) into whichever of the three host arrays is not null; the caller syncs
-    void lo_read_back(const float* res, size_t n, float* lufs, float* peak, float* gain);
+    // n rows' results into whichever of the three host arrays is not null; the caller syncs
+    void lo_read_back(const LoRes& m, size_t n, float* lufs, float* peak, float* gain);
     int64_t native_row_len() const { return (int64_t)bt_.L * a_.base_chunk_size * a_.chunk_compress_factor; }  // samples of a row of b.wav
     void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride);
-    int64_t* join_tab_ = nullptr; size_t join_tab_cap_ = 0;
+    DevBuf join_tab_;
     std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
     bool out_native() const;             // neither resampled nor normalized: the delivered fp32 rows are b.wav itself
     const float* out_source(int64_t Wo);  // the finished batch at the output rate: b.wav, or resampled into the fp32 scratch
-    float* out_f32_buf(size_t n);
-    unsigned char* out_enc_buf(size_t bytes);
-    float* out_f32_ = nullptr; size_t out_f32_cap_ = 0;  // fetch scratch (grow-only, outside the graph key)
-    unsigned char* out_enc_ = nullptr; size_t out_enc_cap_ = 0;  // (bytes)
+    float* out_f32_buf(size_t n) { return reinterpret_cast<float*>(out_f32_.reserve(*this, n * sizeof(float))); }
+    void* out_enc_buf(size_t bytes) { return out_enc_.reserve(*this, bytes); }
+    DevBuf out_f32_, out_enc_;        // fetch scratch: fp32 rows at the output rate, rows in the fetch's encoding
     hipStream_t copy_s_ = nullptr;
     bool prof_on_ = false;
     std::vector<ProfSpan> spans_;

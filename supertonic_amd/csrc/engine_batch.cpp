@@ -414,19 +414,18 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
 // output stage: the finished batch -> what a fetch delivers
 // =================================================================================================
 
-// grow-only fetch scratch (not part of the resident batch: growing it re-keys no captured graph)
-template <typename T>
-static T* out_grow(Engine& e, T*& p, size_t& cap, size_t n) {
-    if (p && n <= cap) return p;
+// the fetch scratch: the one place where it grows (engine.hpp has the rule for the pointers handed out)
+char* DevBuf::reserve(Engine& e, size_t bytes, bool* moved) {
+    const bool grow = !p_ || bytes > cap_;
+    if (moved) *moved = grow;
+    if (!grow) return p_;
     e.sync();  // the previous fetch may still be reading it
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&p), (n + n / 4) * sizeof(T)));
-    cap = n + n / 4;
-    return p;
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr; cap_ = 0;
+    STN_HIP(hipMalloc(reinterpret_cast<void**>(&p_), bytes + bytes / 4));
+    cap_ = bytes + bytes / 4;
+    return p_;
 }
-float* Engine::out_f32_buf(size_t n) { return out_grow(*this, out_f32_, out_f32_cap_, n); }
-unsigned char* Engine::out_enc_buf(size_t bytes) { return out_grow(*this, out_enc_, out_enc_cap_, bytes); }
 
 int64_t Engine::out_row_len() {
     STN_HIP(hipSetDevice(device_));
@@ -443,6 +442,13 @@ const float* Engine::out_source(int64_t Wo) {
     float* d = out_f32_buf((size_t)b.B * Wo);
     resample_enqueue(rs_table(), b.wav, b.B, native_row_len(), ENC_F32, d, Wo);
     return d;
+}
+
+// section 15: with the limiter active the store, the cut and the join run on the limited rows
+Engine::GainedRows Engine::gain_step(const float* src, int64_t rows, int64_t W, int64_t stride, const LoRes& m) {
+    if (!limiter_active()) return {src, m.gain, stride};
+    const LmScratch lm = lm_rows(src, rows, W, m.n, m.gain);
+    return {lm.y, lm.trim, W};
 }
 
 static int64_t join_stride(const JoinPlan& p);
@@ -469,18 +475,16 @@ void Engine::enqueue_output(const OutRows& o) {
         const float* src = out_source(Wo);
         if (src == o.dst) throw std::logic_error("trimmed fetch: source and destination rows are the same");
         const EdScratch sc = ed_batch(src, Wo);
-        const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
+        const LoRes m = loudness_on() ? lo_batch(src, Wo, true) : LoRes{};
         const float* fade = st_window(output_rate());
-        int64_t sw = resample_on() ? Wo : W;
-        if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; sw = Wo; }  // section 15: the untrimmed rows limited, then cut
+        const GainedRows r = gain_step(src, b.B, Wo, resample_on() ? Wo : W, m);  // (the untrimmed rows limited, then cut)
         StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-        launch_join_trim_rows(s_, src, sw, sc.seg, sc.prog, b.B, Wo, g, fade, o.enc, o.dst, o.stride);
+        launch_join_trim_rows(s_, r.src, r.stride, sc.seg, sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride);
     } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
-        const float* g = lo_batch(src, Wo, true) + 2 * (int64_t)b.B;
-        if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; }  // section 15: the store then runs on the limited rows
+        const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-        launch_store_rows(s_, src, b.B, Wo, g, o.enc, o.dst, o.stride);
+        launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride);
     } else if (resample_on()) {
         resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
     } else if (o.enc != ENC_F32) {
@@ -676,8 +680,8 @@ Engine::JoinTables Engine::join_tables_at(const int64_t* d, const JoinPlan& p) {
 
 Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
     std::vector<int64_t> w = join_table_words(p);
-    const bool moved = !join_tab_ || w.size() > join_tab_cap_;
-    int64_t* d = out_grow(*this, join_tab_, join_tab_cap_, w.size());
+    bool moved = false;
+    int64_t* d = reinterpret_cast<int64_t*>(join_tab_.reserve(*this, w.size() * sizeof(int64_t), &moved));
     if (moved || w != join_tab_host_) {  // later fetches of the same batch under the same join reuse the upload
         join_tab_host_ = std::move(w);
         STN_HIP(hipMemcpyAsync(d, join_tab_host_.data(), join_tab_host_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
@@ -707,7 +711,7 @@ const float* Engine::join_f32(const JoinPlan& p) {
     return base + off;
 }
 
-float* Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
+Engine::LoRes Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
     const int hz = output_rate();
     lo_prepare(lo_, hz);
     // programme g's span: what the reference's hosts write to a file, its duration at the output rate (section 11's rule)
@@ -728,20 +732,17 @@ void Engine::enqueue_joined(const OutRows& o) {
     if (p.W_join == 0) return;
     if (loudness_on() && o.scope == STN_JOIN_GAIN_PROG) {
         const float* joined = join_f32(p);
-        const float* g = join_measure(p, joined, true) + 2 * (int64_t)p.G;
-        if (limiter_active()) { const LmScratch lm = lm_rows(joined, p.G, p.W_join, g); joined = lm.y; g = lm.trim; }  // section 15: G rows, each its programme's gain and span
+        const GainedRows r = gain_step(joined, p.G, p.W_join, p.W_join, join_measure(p, joined, true));  // (G rows, each its programme's gain and span)
         {
             StageSpan span(*this, "out", "loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
-            launch_store_rows(s_, joined, p.G, p.W_join, g, o.enc, o.dst, o.stride);
+            launch_store_rows(s_, r.src, p.G, p.W_join, r.g, o.enc, o.dst, o.stride);
         }
         STN_HIP(hipGetLastError());
         return;
     }
     const float* src = out_source(Wo);
-    const float* g = loudness_on() ? lo_batch(src, Wo, true) + 2 * (int64_t)b.B : nullptr;
-    int64_t sw = resample_on() ? Wo : W;
-    if (limiter_active()) { const LmScratch lm = lm_rows(src, b.B, Wo, g); src = lm.y; g = lm.trim; sw = Wo; }  // section 15: the segments are the limited rows
-    join_enqueue(src, sw, join_tables(p), p, g, o.enc, o.dst, o.stride);
+    const GainedRows r = gain_step(src, b.B, Wo, resample_on() ? Wo : W, loudness_on() ? lo_batch(src, Wo, true) : LoRes{});  // (the segments are the limited rows)
+    join_enqueue(r.src, r.stride, join_tables(p), p, r.g, o.enc, o.dst, o.stride);
 }
 
 static int64_t join_stride(const JoinPlan& p) { return (p.W_join + 15) / 16 * 16; }  // a multiple of every encoding's vector
@@ -797,8 +798,7 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
     if (p.G > 65535) throw std::invalid_argument("join: more than 65535 programmes");
     const bool measure = loudness_on || prog_lufs || prog_peak || prog_gain;
     if (measure) {
-        if (!(target_lufs >= -60.0f && target_lufs <= 0.0f)) throw std::invalid_argument("loudness target " + std::to_string(target_lufs) + " LUFS: must be in [-60, 0]");
-        if (!(ceiling_dbfs >= -30.0f && ceiling_dbfs <= 0.0f)) throw std::invalid_argument("loudness peak ceiling " + std::to_string(ceiling_dbfs) + " dBFS: must be in [-30, 0]");
+        refuse(loudness_check(&target_lufs, ceiling_dbfs));
         lo_prepare(op_lo_, hz);
     }
     if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
@@ -816,9 +816,9 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
     } else {
         float* dj = static_cast<float*>(ar_.alloc(ny * 4));
         join_enqueue(dx, W, t, p, nullptr, ENC_F32, dj, p.W_join);
-        const float* res = lo_rows(op_lo_, dj, p.G, p.W_join, p.prog_len, loudness_on, target_lufs, ceiling_dbfs);
+        const LoRes res = lo_rows(op_lo_, dj, p.G, p.W_join, p.prog_len, loudness_on, target_lufs, ceiling_dbfs);
         lo_n_.clear();  // (op_lo_'s rows, not the batch's)
-        launch_store_rows(s_, dj, p.G, p.W_join, res + 2 * (size_t)p.G, enc, dy, p.W_join);
+        launch_store_rows(s_, dj, p.G, p.W_join, res.gain, enc, dy, p.W_join);
         STN_HIP(hipGetLastError());
         lo_read_back(res, (size_t)p.G, prog_lufs, prog_peak, prog_gain);
     }

@@ -27,15 +27,8 @@ std::vector<float> silence_fade_window(int hz, float fade_ms) {
     return w;
 }
 
-static std::string silence_rate_check(int hz) {
-    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
-        return "silence trim: sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")";
-    return "";
-}
-
 void Engine::set_silence_trim(bool on, float top_db, float keep_ms, float fade_ms) {
-    const std::string why = silence_check(top_db, keep_ms, fade_ms);
-    if (!why.empty()) throw std::invalid_argument(why);
+    refuse(silence_check(top_db, keep_ms, fade_ms));
     st_on_ = on;
     st_db_ = top_db;
     st_keep_ = keep_ms;
@@ -49,92 +42,63 @@ void Engine::get_silence_trim(int* on, float* top_db, float* keep_ms, float* fad
     if (fade_ms) *fade_ms = st_fade_;
 }
 
-void Engine::ed_release() {
-    if (ed_buf_) (void)hipFree(ed_buf_);
-    if (st_win_) (void)hipFree(st_win_);
-    ed_buf_ = nullptr; ed_buf_cap_ = 0;
-    st_win_ = nullptr; st_win_cap_ = 0; st_win_hz_ = 0; st_win_ms_ = -1.0f;
-    ed_valid_ = ed_host_valid_ = false;
-}
-
 // uploaded once per (rate, fade_ms); at least one float, so that the kernel's pointer is never null
 const float* Engine::st_window(int hz) {
-    if (st_win_ && st_win_hz_ == hz && st_win_ms_ == st_fade_) return st_win_;
+    if (st_win_.get() && st_win_hz_ == hz && st_win_ms_ == st_fade_) return static_cast<const float*>(st_win_.get());
     const std::vector<float> w = silence_fade_window(hz, st_fade_);
-    const size_t need = std::max<size_t>(w.size(), 1);
-    if (!st_win_ || need > st_win_cap_) {
-        sync();  // a fetch may still be reading the old window
-        if (st_win_) (void)hipFree(st_win_);
-        st_win_ = nullptr; st_win_cap_ = 0;
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&st_win_), need * sizeof(float)));
-        st_win_cap_ = need;
-    } else {
-        sync();
-    }
-    if (!w.empty()) STN_HIP(hipMemcpy(st_win_, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    float* d = reinterpret_cast<float*>(st_win_.reserve(*this, std::max<size_t>(w.size(), 1) * sizeof(float)));
+    sync();  // a fetch may still be reading the old window
+    if (!w.empty()) STN_HIP(hipMemcpy(d, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
     st_win_hz_ = hz; st_win_ms_ = st_fade_;
-    return st_win_;
+    return d;
 }
 
-// grow-only scratch (not part of the resident batch: growing it re-keys no captured graph): per chunk the two frame shares, per frame
-// the level, per row the edges, the span and the one-member programme of the per-row trimmed fetch
-static size_t ed_up(size_t b) { return (b + 255) / 256 * 256; }
-static size_t ed_layout(int64_t rows, int64_t W, int hz, size_t* o) {
+Engine::EdScratch Engine::ed_layout(char* base, int64_t rows, int64_t W, int hz) {
     const size_t nc = (size_t)rows * (size_t)ed_chunks(W), nf = (size_t)rows * (size_t)edges_frames(W, hz);
-    o[0] = 0;                                  // pa
-    o[1] = o[0] + ed_up(nc * 4);               // pb
-    o[2] = o[1] + ed_up(nc * 4);               // lev
-    o[3] = o[2] + ed_up(nf * 8);               // edges
-    o[4] = o[3] + ed_up((size_t)rows * 16);    // n
-    o[5] = o[4] + ed_up((size_t)rows * 8);     // seg
-    o[6] = o[5] + ed_up((size_t)rows * sizeof(JoinSegT));  // prog
-    return o[6] + ed_up((size_t)rows * sizeof(JoinProg));
+    Carve c{base};
+    EdScratch sc{};
+    sc.pa = c.take<float>(nc);
+    sc.pb = c.take<float>(nc);
+    sc.lev = c.take<double>(nf);
+    sc.edges = c.take<int64_t>((size_t)rows * 2);
+    sc.n = c.take<int64_t>((size_t)rows);
+    sc.seg = c.take<JoinSegT>((size_t)rows);
+    sc.prog = c.take<JoinProg>((size_t)rows);
+    sc.bytes = c.off;
+    return sc;
 }
 
 Engine::EdScratch Engine::ed_scratch(int64_t rows, int64_t W, int hz) {
-    size_t o[7];
-    const size_t need = ed_layout(rows, W, hz, o);
-    if (!ed_buf_ || need > ed_buf_cap_) {
-        sync();  // the previous fetch may still be reading it
-        if (ed_buf_) (void)hipFree(ed_buf_);
-        ed_buf_ = nullptr; ed_buf_cap_ = 0;
-        ed_valid_ = ed_host_valid_ = false;
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&ed_buf_), need + need / 4));
-        ed_buf_cap_ = need + need / 4;
+    bool moved = false;
+    char* base = ed_buf_.reserve(*this, ed_layout(nullptr, rows, W, hz).bytes, &moved);
+    if (moved) ed_valid_ = ed_host_valid_ = false;
+    return ed_layout(base, rows, W, hz);
+}
+
+void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc) {
+    const double samples = (double)rows * W, chunks = (double)rows * ed_chunks(W);
+    {
+        StageSpan span(*this, "out", "edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
+        launch_edges_frames(s_, x, rows, W, sc.n, hz, sc.pa, sc.pb);
+        span.next("edges_rows", chunks, chunks * 8 + (double)rows * edges_frames(W, hz) * 16);
+        launch_edges_rows(s_, rows, W, sc.n, hz, (double)top_db, silence_samples(hz, keep_ms), silence_samples(hz, fade_ms), sc.pa, sc.pb, sc.lev,
+                          sc.edges, sc.seg, sc.prog);
     }
-    EdScratch sc;
-    sc.pa = reinterpret_cast<float*>(ed_buf_ + o[0]);
-    sc.pb = reinterpret_cast<float*>(ed_buf_ + o[1]);
-    sc.lev = reinterpret_cast<double*>(ed_buf_ + o[2]);
-    sc.edges = reinterpret_cast<int64_t*>(ed_buf_ + o[3]);
-    sc.n = reinterpret_cast<int64_t*>(ed_buf_ + o[4]);
-    sc.seg = reinterpret_cast<JoinSegT*>(ed_buf_ + o[5]);
-    sc.prog = reinterpret_cast<JoinProg*>(ed_buf_ + o[6]);
-    return sc;
+    STN_HIP(hipGetLastError());
 }
 
 Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo) {
     const Batch& b = bt_;
     const int hz = output_rate();
-    const std::string why = silence_rate_check(hz);
-    if (!why.empty()) throw std::invalid_argument(why);
+    refuse(rate_check("silence trim", hz));
     const EdScratch sc = ed_scratch(b.B, Wo, hz);
-    const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_};
+    const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_.get()};
     if (ed_valid_ && key == ed_key_) return sc;
     // row b's span: section 11's, its reported duration at the output rate
     ed_n_.resize((size_t)b.B);
     for (int i = 0; i < b.B; ++i) ed_n_[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
     STN_HIP(hipMemcpyAsync(sc.n, ed_n_.data(), ed_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    {
-        const double samples = (double)b.B * Wo;
-        const double chunks = (double)b.B * ed_chunks(Wo);
-        StageSpan span(*this, "out", "edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
-        launch_edges_frames(s_, x, b.B, Wo, sc.n, hz, sc.pa, sc.pb);
-        span.next("edges_rows", chunks, chunks * 8 + (double)b.B * edges_frames(Wo, hz) * 16);
-        launch_edges_rows(s_, b.B, Wo, sc.n, hz, (double)st_db_, silence_samples(hz, st_keep_), silence_samples(hz, st_fade_), sc.pa, sc.pb, sc.lev,
-                          sc.edges, sc.seg, sc.prog);
-    }
-    STN_HIP(hipGetLastError());
+    ed_enqueue(x, b.B, Wo, hz, st_db_, st_keep_, st_fade_, sc);
     ed_key_ = key;
     ed_valid_ = true;
     ed_host_valid_ = false;
@@ -143,7 +107,7 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo) {
 
 const std::vector<int64_t>& Engine::ed_batch_host() {
     const int64_t Wo = out_row_len();
-    const EdKey key{ed_seq_, output_rate(), st_db_, st_keep_, st_fade_, Wo, ed_buf_};
+    const EdKey key{ed_seq_, output_rate(), st_db_, st_keep_, st_fade_, Wo, ed_buf_.get()};
     if (ed_valid_ && ed_host_valid_ && key == ed_key_) return ed_host_;
     const EdScratch sc = (ed_valid_ && key == ed_key_) ? ed_scratch(bt_.B, Wo, output_rate()) : ed_batch(out_source(Wo), Wo);
     ed_host_.resize((size_t)bt_.B * 2);
@@ -168,36 +132,20 @@ void Engine::op_silence_edges(int hz, int rows, int W, const float* x, const int
 void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, const float* gain,
                              int enc, void* y, int64_t* start, int64_t* end) {
     STN_HIP(hipSetDevice(device_));
-    std::string why = silence_check(top_db, keep_ms, fade_ms);
-    if (why.empty()) why = silence_rate_check(hz);
-    if (!why.empty()) throw std::invalid_argument(why);
+    refuse(silence_check(top_db, keep_ms, fade_ms));
+    refuse(rate_check("silence trim", hz));
     const int eb = enc_bytes(enc);
     if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
-    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    for (int r = 0; r < rows && n; ++r) {
-        if (n[r] < 0 || n[r] > W) throw std::invalid_argument("op_silence: n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
-        nn[(size_t)r] = n[r];
-    }
+    const std::vector<int64_t> nn = spans("op_silence", rows, W, n);
     ar_.reset();
-    size_t o[7];
-    const size_t need = ed_layout(rows, W, hz, o);
-    char* base = static_cast<char*>(ar_.alloc(need));
+    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz).bytes)), rows, W, hz);
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    int64_t* dn = reinterpret_cast<int64_t*>(base + o[4]);
-    int64_t* de = reinterpret_cast<int64_t*>(base + o[3]);
-    JoinSegT* seg = reinterpret_cast<JoinSegT*>(base + o[5]);
-    JoinProg* prog = reinterpret_cast<JoinProg*>(base + o[6]);
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    const int64_t fd = silence_samples(hz, fade_ms);
-    float* pa = reinterpret_cast<float*>(base + o[0]);
-    float* pb = reinterpret_cast<float*>(base + o[1]);
-    launch_edges_frames(s_, dx, rows, W, dn, hz, pa, pb);
-    launch_edges_rows(s_, rows, W, dn, hz, (double)top_db, silence_samples(hz, keep_ms), fd, pa, pb, reinterpret_cast<double*>(base + o[2]), de, seg, prog);
-    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc);
     std::vector<int64_t> e((size_t)rows * 2);
-    STN_HIP(hipMemcpyAsync(e.data(), de, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
     if (y) {
         const std::vector<float> w = silence_fade_window(hz, fade_ms);
         float* dw = static_cast<float*>(ar_.alloc(std::max<size_t>(w.size(), 1) * 4));
@@ -209,7 +157,7 @@ void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int6
         }
         const int64_t Ws = ((int64_t)W + 15) / 16 * 16;  // rows 16-byte aligned in every encoding: the store runs full width
         void* dy = ar_.alloc((size_t)rows * Ws * eb);
-        launch_join_trim_rows(s_, dx, W, seg, prog, rows, W, dg, dw, enc, dy, Ws);
+        launch_join_trim_rows(s_, dx, W, sc.seg, sc.prog, rows, W, dg, dw, enc, dy, Ws);
         STN_HIP(hipGetLastError());
         STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
     }

@@ -9,11 +9,32 @@
 
 namespace stn {
 
+std::string rate_check(const char* what, int hz) {
+    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
+        return std::string(what) + ": sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")";
+    return "";
+}
+
+std::string loudness_check(const float* target, float ceiling) {
+    if (target && !(*target >= -60.0f && *target <= 0.0f)) return "loudness target " + std::to_string(*target) + " LUFS: must be in [-60, 0]";
+    if (!(ceiling >= -30.0f && ceiling <= 0.0f)) return "loudness peak ceiling " + std::to_string(ceiling) + " dBFS: must be in [-30, 0]";
+    return "";
+}
+
+std::vector<int64_t> spans(const char* who, int rows, int W, const int64_t* n) {
+    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
+    for (int r = 0; r < rows && n; ++r) {
+        if (n[r] < 0 || n[r] > W) throw std::invalid_argument(std::string(who) + ": n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
+        nn[(size_t)r] = n[r];
+    }
+    return nn;
+}
+
 // BS.1770-4 K-weighting at any rate: the analog prototypes of the standard's 48 kHz table (libebur128's derivation), bilinear-transformed
 // at hz.  At 48 kHz this is the published table to 1e-15.
 std::string kweighting_design(int hz, KWeighting& k) {
-    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
-        return "loudness: sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")";
+    const std::string why = rate_check("loudness", hz);
+    if (!why.empty()) return why;
     const double fs = hz;
     {  // high shelf, +4 dB above ~1.7 kHz (the head's acoustic effect)
         const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
@@ -78,8 +99,7 @@ std::string loudness_design(int hz, LoudTable& t) {
 void Engine::lo_prepare(LoudTable& t, int hz) {
     if (t.dev && t.hz == hz) return;
     LoudTable n;
-    const std::string why = loudness_design(hz, n);
-    if (!why.empty()) throw std::invalid_argument(why);
+    refuse(loudness_design(hz, n));
     STN_HIP(hipSetDevice(device_));
     STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.mpow.size() * sizeof(double)));
     STN_HIP(hipMemcpyAsync(n.dev, n.mpow.data(), n.mpow.size() * sizeof(double), hipMemcpyHostToDevice, s_));
@@ -89,17 +109,10 @@ void Engine::lo_prepare(LoudTable& t, int hz) {
 
 void Engine::lo_release() {
     for (LoudTable* t : {&lo_, &op_lo_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
-    if (lo_buf_) (void)hipFree(lo_buf_);
-    lo_buf_ = nullptr; lo_buf_cap_ = 0;
-    lo_n_.clear();
-    lo_n_ptr_ = nullptr;
 }
 
 void Engine::set_loudness(bool on, float target, float ceiling) {
-    if (!(target >= -60.0f && target <= 0.0f))
-        throw std::invalid_argument("loudness target " + std::to_string(target) + " LUFS: must be in [-60, 0]");
-    if (!(ceiling >= -30.0f && ceiling <= 0.0f))
-        throw std::invalid_argument("loudness peak ceiling " + std::to_string(ceiling) + " dBFS: must be in [-30, 0]");
+    refuse(loudness_check(&target, ceiling));
     lo_on_ = on;
     lo_target_ = target;
     lo_ceiling_ = ceiling;
@@ -111,30 +124,27 @@ void Engine::get_loudness(int* on, float* target, float* ceiling) const {
     if (ceiling) *ceiling = lo_ceiling_;
 }
 
-// grow-only scratch (not part of the resident batch: growing it re-keys no captured graph): per chunk the state (16 B), the peak and
-// the two energy shares; per row the three results and the length
-Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+Engine::LoScratch Engine::lo_layout(char* base, int64_t rows, int64_t W) {
     const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
-    const size_t o_st = 0, o_pk = o_st + up(nc * 16), o_pa = o_pk + up(nc * 4), o_pb = o_pa + up(nc * 4), o_res = o_pb + up(nc * 4),
-                 o_n = o_res + up((size_t)rows * 12), need = o_n + up((size_t)rows * 8);
-    if (!lo_buf_ || need > lo_buf_cap_) {
-        sync();  // the previous fetch may still be reading it
-        if (lo_buf_) (void)hipFree(lo_buf_);
-        lo_buf_ = nullptr; lo_buf_cap_ = 0;
-        lo_n_.clear();
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&lo_buf_), need + need / 4));
-        lo_buf_cap_ = need + need / 4;
-    }
+    Carve c{base};
+    LoScratch sc{};
+    sc.st = c.take<float>(nc * 4);
+    sc.pk = c.take<float>(nc);
+    sc.pa = c.take<float>(nc);
+    sc.pb = c.take<float>(nc);
+    sc.res = c.take<float>((size_t)rows * 3);
     // (the row lengths sit behind the per-chunk arrays: another rows x W moves them, so lo_n_ptr_ remembers where they went)
-    LoScratch sc;
-    sc.st = reinterpret_cast<float*>(lo_buf_ + o_st);
-    sc.pk = reinterpret_cast<float*>(lo_buf_ + o_pk);
-    sc.pa = reinterpret_cast<float*>(lo_buf_ + o_pa);
-    sc.pb = reinterpret_cast<float*>(lo_buf_ + o_pb);
-    sc.res = reinterpret_cast<float*>(lo_buf_ + o_res);
-    sc.n = reinterpret_cast<int64_t*>(lo_buf_ + o_n);
+    sc.n = c.take<int64_t>((size_t)rows);
+    if (base) sc.out = {sc.res, sc.res + rows, sc.res + 2 * rows, sc.n};
+    sc.bytes = c.off;
     return sc;
+}
+
+Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
+    bool moved = false;
+    char* base = lo_buf_.reserve(*this, lo_layout(nullptr, rows, W).bytes, &moved);
+    if (moved) lo_n_.clear();
+    return lo_layout(base, rows, W);
 }
 
 void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
@@ -158,13 +168,13 @@ void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_
     STN_HIP(hipGetLastError());
 }
 
-void Engine::lo_read_back(const float* res, size_t n, float* lufs, float* peak, float* gain) {
-    if (lufs) STN_HIP(hipMemcpyAsync(lufs, res, n * 4, hipMemcpyDeviceToHost, s_));
-    if (peak) STN_HIP(hipMemcpyAsync(peak, res + n, n * 4, hipMemcpyDeviceToHost, s_));
-    if (gain) STN_HIP(hipMemcpyAsync(gain, res + 2 * n, n * 4, hipMemcpyDeviceToHost, s_));
+void Engine::lo_read_back(const LoRes& m, size_t n, float* lufs, float* peak, float* gain) {
+    if (lufs) STN_HIP(hipMemcpyAsync(lufs, m.lufs, n * 4, hipMemcpyDeviceToHost, s_));
+    if (peak) STN_HIP(hipMemcpyAsync(peak, m.peak, n * 4, hipMemcpyDeviceToHost, s_));
+    if (gain) STN_HIP(hipMemcpyAsync(gain, m.gain, n * 4, hipMemcpyDeviceToHost, s_));
 }
 
-float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
+Engine::LoRes Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     const Batch& b = bt_;
     const int hz = output_rate();
     lo_prepare(lo_, hz);
@@ -177,8 +187,8 @@ float* Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_cap(), lo_true_peak());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
 }
 
-float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
-                       bool true_peak) {
+Engine::LoRes Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target,
+                              float ceiling, bool true_peak) {
     int64_t max_seg = 0;
     for (int64_t v : n) max_seg = std::max<int64_t>(max_seg, v / t.hop);
     const LoScratch sc = lo_scratch(rows, W);
@@ -190,7 +200,7 @@ float* Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t
         STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     }
     lo_measure(t, x, rows, W, sc, max_seg, on, target, ceiling, nullptr, true_peak);
-    return sc.res;
+    return sc.out;
 }
 
 void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
@@ -203,15 +213,9 @@ void Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bo
                    float* peak, float* gain) {
     STN_HIP(hipSetDevice(device_));
     lo_prepare(op_lo_, hz);
-    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
+    const std::vector<int64_t> nn = spans("op_loudness", rows, W, n);
     int64_t max_seg = 0;
-    for (int r = 0; r < rows; ++r) {
-        if (n) {
-            if (n[r] < 0 || n[r] > W) throw std::invalid_argument("op_loudness: n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
-            nn[(size_t)r] = n[r];
-        }
-        max_seg = std::max<int64_t>(max_seg, nn[(size_t)r] / op_lo_.hop);
-    }
+    for (int64_t v : nn) max_seg = std::max<int64_t>(max_seg, v / op_lo_.hop);
     ar_.reset();
     const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
     float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
@@ -222,7 +226,7 @@ void Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bo
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     lo_n_.clear();  // (the batch's lengths are no longer there)
     lo_measure(op_lo_, dx, rows, W, sc, max_seg, on, target, ceiling, probe ? probe->st_end : nullptr);
-    lo_read_back(sc.res, (size_t)rows, lufs, peak, gain);
+    lo_read_back(sc.out, (size_t)rows, lufs, peak, gain);
     if (probe) {
         const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
         auto out = [&](float* dst, const float* src, size_t bytes) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_)); };

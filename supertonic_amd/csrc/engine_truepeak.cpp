@@ -45,32 +45,28 @@ void Engine::set_peak_mode(int mode) {
     pk_true_ = mode == STN_PEAK_TRUE;
 }
 
-void Engine::tp_release() {
-    if (tp_buf_) (void)hipFree(tp_buf_);
-    tp_buf_ = nullptr; tp_buf_cap_ = 0;
+Engine::TpScratch Engine::tp_layout(char* base, int64_t rows, int64_t W, bool with_env) {
+    Carve c{base};
+    TpScratch sc{};
+    sc.pk = c.take<float>((size_t)rows * (size_t)lo_chunks(W));
+    sc.tp_in = c.take<float>((size_t)rows);
+    sc.tp_out = c.take<float>((size_t)rows);
+    sc.tp_y = c.take<float>((size_t)rows);
+    sc.trim = c.take<float>((size_t)rows);
+    if (with_env) sc.env = c.take<float>((size_t)rows * (size_t)W);
+    sc.bytes = c.off;
+    return sc;
 }
 
-// grow-only scratch (not part of the resident batch: growing it re-keys no captured graph)
 Engine::TpScratch Engine::tp_scratch(int64_t rows, int64_t W, bool with_env) {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t nc = (size_t)rows * (size_t)lo_chunks(W), r4 = up((size_t)rows * 4);
-    const size_t o_pk = 0, o_res = o_pk + up(nc * 4), o_env = o_res + 4 * r4, need = o_env + (with_env ? up((size_t)rows * (size_t)W * 4) : 0);
-    if (!tp_buf_ || need > tp_buf_cap_) {
-        sync();  // the previous fetch may still be reading it
-        if (tp_buf_) (void)hipFree(tp_buf_);
-        tp_buf_ = nullptr; tp_buf_cap_ = 0;
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&tp_buf_), need + need / 4));
-        tp_buf_cap_ = need + need / 4;
-    }
-    auto at = [&](size_t o) { return reinterpret_cast<float*>(tp_buf_ + o); };
-    return {at(o_pk), at(o_res), at(o_res + r4), at(o_res + 2 * r4), at(o_res + 3 * r4), with_env ? at(o_env) : nullptr};
+    return tp_layout(tp_buf_.reserve(*this, tp_layout(nullptr, rows, W, with_env).bytes), rows, W, with_env);
 }
 
-void Engine::tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float c, float* tp, float* trim) {
+void Engine::tp_rows(const float* x, int64_t rows, int64_t W, const int64_t* n, const float* g, float* pk, float* env, float c, float* tp, float* trim) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     {
-        StageSpan span(*this, "out", "true_peak", 97.0 * samples, samples * 4 + chunks * 4);
-        launch_truepeak(s_, x, rows, W, n, g, pk, nullptr);
+        StageSpan span(*this, "out", "true_peak", 97.0 * samples, samples * (env ? 8 : 4) + chunks * 4);
+        launch_truepeak(s_, x, rows, W, n, g, pk, env);
         STN_HIP(hipGetLastError());
         span.next("true_peak_rows", chunks, chunks * 4 + (double)rows * 8);
         launch_truepeak_rows(s_, rows, W, n, pk, c, tp, trim);
@@ -84,19 +80,19 @@ void Engine::batch_true_peak(float* tp_in, float* tp_out, float* trim) {
     const float c = (float)std::pow(10.0, (double)lo_ceiling_ / 20.0);
     // a reporting call, as batch_limiter is: the stage runs again and 12 bytes per row are read back
     const float* src = out_source(Wo);
-    const float* g = lo_batch(src, Wo, lo_on_) + 2 * B;  // (uploads the spans: lo_n_ptr_)
+    const LoRes m = lo_batch(src, Wo, lo_on_);
     const bool lim_true = limiter_active() && pk_true_;
     const TpScratch sc = tp_scratch(B, Wo, lim_true);   // (sized for the limiter's use below: it moves no more)
-    tp_rows(src, B, Wo, lo_n_ptr_, nullptr, sc.pk, c, sc.tp_in, nullptr);
+    tp_rows(src, B, Wo, m.n, nullptr, sc.pk, nullptr, c, sc.tp_in, nullptr);
     const float* d_out = sc.tp_in;
     const float* d_trim = nullptr;
     if (lo_on_) {
         if (limiter_active()) {
-            const LmScratch lm = lm_rows(src, B, Wo, g);
+            const LmScratch lm = lm_rows(src, B, Wo, m.n, m.gain);
             d_trim = lm.trim;
-            tp_rows(lm.y, B, Wo, lo_n_ptr_, lm.trim, sc.pk, c, sc.tp_out, nullptr);
+            tp_rows(lm.y, B, Wo, m.n, lm.trim, sc.pk, nullptr, c, sc.tp_out, nullptr);
         } else {
-            tp_rows(src, B, Wo, lo_n_ptr_, g, sc.pk, c, sc.tp_out, nullptr);
+            tp_rows(src, B, Wo, m.n, m.gain, sc.pk, nullptr, c, sc.tp_out, nullptr);
         }
         d_out = sc.tp_out;
     }
@@ -109,45 +105,30 @@ void Engine::batch_true_peak(float* tp_in, float* tp_out, float* trim) {
     sync();
 }
 
-static std::vector<int64_t> tp_spans(const char* who, int rows, int W, const int64_t* n) {
-    std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    for (int r = 0; r < rows && n; ++r) {
-        if (n[r] < 0 || n[r] > W) throw std::invalid_argument(std::string(who) + ": n[" + std::to_string(r) + "] = " + std::to_string(n[r]) + " outside [0, W]");
-        nn[(size_t)r] = n[r];
-    }
-    return nn;
-}
-
 const char* Engine::op_true_peak(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp, float* env,
                                  float* pk) {
     STN_HIP(hipSetDevice(device_));
-    if (hz < LO_MIN_HZ || hz > LO_MAX_HZ)
-        throw std::invalid_argument("true peak: sample rate must be in [" + std::to_string(LO_MIN_HZ) + ", " + std::to_string(LO_MAX_HZ) + "] Hz (got " + std::to_string(hz) + ")");
-    const std::vector<int64_t> nn = tp_spans("op_true_peak", rows, W, n);
+    refuse(rate_check("true peak", hz));
+    const std::vector<int64_t> nn = spans("op_true_peak", rows, W, n);
     ar_.reset();
     const size_t nx = (size_t)rows * W, nc = (size_t)rows * (size_t)lo_chunks(W), off = x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
     float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
-    float* denv = env ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
-    float* dpk = static_cast<float*>(ar_.alloc(nc * 4));
-    float* dtp = static_cast<float*>(ar_.alloc((size_t)rows * 4));
+    const TpScratch sc = tp_layout(static_cast<char*>(ar_.alloc(tp_layout(nullptr, rows, W, env != nullptr).bytes)), rows, W, env != nullptr);
     int64_t* dn = static_cast<int64_t*>(ar_.alloc((size_t)rows * 8));
     float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
     // what a launch fails to write reads back as the quiet NaN, not as an earlier call's value
-    if (denv) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(denv), 0x7FC00000, nx, s_));
-    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dpk), 0x7FC00000, nc, s_));
-    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dtp), 0x7FC00000, (size_t)rows, s_));
+    if (sc.env) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.env), 0x7FC00000, nx, s_));
+    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pk), 0x7FC00000, nc, s_));
+    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.tp_in), 0x7FC00000, (size_t)rows, s_));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
-    launch_truepeak(s_, dx, rows, W, dn, dg, dpk, denv);
-    STN_HIP(hipGetLastError());
-    launch_truepeak_rows(s_, rows, W, dn, dpk, 1.0f, dtp, nullptr);
-    STN_HIP(hipGetLastError());
-    if (tp) STN_HIP(hipMemcpyAsync(tp, dtp, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
-    if (env) STN_HIP(hipMemcpyAsync(env, denv, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (pk) STN_HIP(hipMemcpyAsync(pk, dpk, nc * 4, hipMemcpyDeviceToHost, s_));
+    tp_rows(dx, rows, W, dn, dg, sc.pk, sc.env, 1.0f, sc.tp_in, nullptr);
+    if (tp) STN_HIP(hipMemcpyAsync(tp, sc.tp_in, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    if (env) STN_HIP(hipMemcpyAsync(env, sc.env, nx * 4, hipMemcpyDeviceToHost, s_));
+    if (pk) STN_HIP(hipMemcpyAsync(pk, sc.pk, nc * 4, hipMemcpyDeviceToHost, s_));
     sync();  // (nn is read by the copy above until here)
-    return truepeak_staging_form(dx, W, denv);
+    return truepeak_staging_form(dx, W, sc.env);
 }
 
 }  // namespace stn
