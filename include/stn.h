@@ -328,6 +328,11 @@ const char* stn_resample_error(int in_hz, int out_hz);
 /* op-level: rows x W fp32 (host) at in_hz -> rows x ceil(W*P/Q) at out_hz, as fp32 (y) and / or int16 PCM (pcm); either may be
  * NULL but not both.  1 <= rows <= 65535. */
 int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const float* x, float* y_or_null, int16_t* pcm_or_null);
+/* the form the resampler's launcher takes for rows of W samples (host only, no device needed): "resample lds G<n>" (a workgroup's
+ * input span staged in LDS, n groups of 64 output periods per workgroup: 16, 8, 4, 2 or 1) or "resample cache G<n>" (a span above
+ * 160 KiB, read through the caches).  Returns the string's length (written NUL-terminated when cap is larger), STN_ERR_INVALID for
+ * W < 1 or a refused pair. */
+int stn_dbg_resample_form(int in_hz, int out_hz, int64_t W, char* out, size_t cap);
 
 /* ---- loudness --------------------------------------------------------------------------------------
  * With normalization on, every fetch path — stn_batch_fetch, stn_batch_fetch_pcm16, stn_batch_fetch_pcm16_begin / _end,

@@ -254,6 +254,8 @@ def load():
     L.stn_op_attention.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p]
     L.stn_op_dwconv_ln_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, vp, vp, _f32p, _f32p, vp, ci, ci, _f32p, ctypes.c_int64,
                                       ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_resample_form.argtypes = [ci, ci, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_dbg_resample_form.restype = ctypes.c_int
     L.stn_dbg_dwconv_ln_form.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_dwconv_ln_form.restype = ctypes.c_int
     L.stn_op_fold_ln.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p, _f32p, _f32p, _f32p]
@@ -586,6 +588,17 @@ def _loudness_args(target_lufs):
 def resample_error(in_hz, out_hz):
     """Why the pair is refused, or "" when it is supported (host only)."""
     return load().stn_resample_error(int(in_hz), int(out_hz)).decode()
+
+
+def resample_form(in_hz, out_hz, W):
+    """The form the resampler's launcher takes for rows of W samples (stn_dbg_resample_form; host-only): "resample lds G<n>" or
+    "resample cache G<n>", n the groups of 64 output periods a workgroup owns."""
+    buf = ctypes.create_string_buffer(64)
+    r = load().stn_dbg_resample_form(int(in_hz), int(out_hz), int(W), buf, len(buf))
+    if r < 0:
+        why = resample_error(in_hz, out_hz)
+        raise StnError(r, f"stn_dbg_resample_form: {why}" if why else f"stn_dbg_resample_form: W = {W}, W >= 1 is required")
+    return buf.value.decode()
 
 
 def fold_run_frames(latent_lengths, n_cu=256):

@@ -322,6 +322,16 @@ int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && (y || pcm), "stn_op_resample: bad argument (1 <= rows <= 65535, W >= 1, x and y or pcm)");
                  h->eng->op_resample(in_hz, out_hz, rows, W, x, y, pcm); })
 }
+int stn_dbg_resample_form(int in_hz, int out_hz, int64_t W, char* out, size_t cap) {
+    std::string f;
+    try {
+        stn::ResampleTable t;
+        if (W < 1 || !stn::resample_design(in_hz, out_hz, t).empty()) return STN_ERR_INVALID;
+        f = stn::resample_form(W, t).str();  // the decision launch_resample takes
+    } catch (const std::exception&) { return STN_ERR_INVALID; }
+    if (out && cap > f.size()) std::memcpy(out, f.c_str(), f.size() + 1);
+    return (int)f.size();
+}
 int stn_set_loudness(stn_handle* h, int on, float target_lufs, float ceiling_dbfs) {
     STN_TRY(h, { h->eng->set_loudness(on != 0, target_lufs, ceiling_dbfs); })
 }

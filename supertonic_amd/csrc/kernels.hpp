@@ -476,6 +476,18 @@ double bessel_i0(double x);  // the Kaiser window's shape (engine_resample.cpp)
 // rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride samples (dst_stride >= W_out) in encoding enc (the encoded
 // bytes are those of the fp32 output followed by launch_store_rows without a gain)
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride);
+// The form a resample call takes — one decision, made by resample_form (host only: P, Q and T of f) and executed by launch_resample, so
+// that what the diagnostics report (stn_dbg_resample_form) is what runs.  A workgroup owns G * 64 consecutive k of a row (output
+// n = k * P + r) and every r; G doubles from 1 while G * P < 16 (the waves have pairs to walk), G * 64 < K (the row has the k) and the
+// span of 2 G groups fits in 160 KiB of LDS; a span of G groups above 160 KiB reads the row through the caches.
+struct ResampleForm {
+    int G = 1;
+    bool lds = true;        // the span is staged in LDS (else read through the caches)
+    int64_t lds_bytes = 0;  // dynamic LDS of the launch (0 on the cache path)
+    int64_t grid_x = 0;     // workgroups per row
+    std::string str() const;  // "resample lds G4", "resample cache G1"
+};
+ResampleForm resample_form(int64_t W, const ResampleTable& f);  // throws std::invalid_argument for W < 1 or a table without a design
 
 // Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the measurement are engine_loudness.cpp).
 // BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in

@@ -7,7 +7,8 @@
 // steps by Q, so a wavefront takes one r and 64 consecutive k: its taps are wave-uniform (scalar loads, SGPR operands of the FMAs —
 // the table never enters LDS or VGPRs), and the lanes read the input at a stride of Q.  A workgroup (16 waves) owns G*64 consecutive
 // k of one row and every r: its input span (G*64*Q + T samples) is staged once in LDS, zero outside [0, W), and the waves walk the
-// (k group, r) pairs.  Spans above 160 KiB (Q > ~620) read the row through the caches instead, with the same arithmetic.
+// (k group, r) pairs.  Spans above 160 KiB (Q > ~620) read the row through the caches instead, with the same arithmetic.  G and the path
+// are ONE host decision, resample_form.
 // Every output sums its T products in the same order (eight interleaved fp32 FMA chains, then a fixed tree) whatever its position in
 // the row, the tile or the launch, and a read outside the row is 0.0f: a row whose samples past m are zero gives, in its first
 // ceil(m*P/Q) outputs, exactly what the row cut at m gives.
@@ -91,25 +92,37 @@ void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, c
     if (rows > 65535) throw std::invalid_argument("launch_resample: more than 65535 rows");
     const int64_t W_out = resample_out_len(W, f.P, f.Q);
     if (dst_stride < W_out) throw std::invalid_argument("launch_resample: dst_stride smaller than the output row length");
-    const int64_t K = (W_out + f.P - 1) / f.P;  // k values of a row
-    // G k groups per workgroup: enough (k group, r) pairs for the 16 waves where the span still fits in LDS
-    int G = 1;
-    while (G * f.P < RS_THREADS / RS_LANES && (int64_t)G * RS_LANES < K && rs_span(2 * G, f.P, f.Q, f.T) * 4 <= RS_LDS_MAX) G *= 2;
-    const int64_t lds = rs_span(G, f.P, f.Q, f.T) * 4;
-    const int64_t blocks = (K + (int64_t)G * RS_LANES - 1) / ((int64_t)G * RS_LANES);
-    const dim3 grid((unsigned)blocks, (unsigned)rows);
-    if (lds <= RS_LDS_MAX) {
+    const ResampleForm fm = resample_form(W, f);  // the one place G and the staging path are chosen
+    const dim3 grid((unsigned)fm.grid_x, (unsigned)rows);
+    if (fm.lds) {
         static PerDeviceOnce attr_once;
         if (attr_once.need())
             stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&resample_kernel<true, kEnc>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)RS_LDS_MAX), "hipFuncSetAttribute(resample)");
-        STN_KLAUNCH((resample_kernel<true, kEnc>), grid, dim3(RS_THREADS), (unsigned)lds, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
+        STN_KLAUNCH((resample_kernel<true, kEnc>), grid, dim3(RS_THREADS), (unsigned)fm.lds_bytes, s, x, W, W_out, f.P, f.Q, f.T, f.off, fm.G, f.dev, y, dst_stride);
     } else {
-        STN_KLAUNCH((resample_kernel<false, kEnc>), grid, dim3(RS_THREADS), 0, s, x, W, W_out, f.P, f.Q, f.T, f.off, G, f.dev, y, dst_stride);
+        STN_KLAUNCH((resample_kernel<false, kEnc>), grid, dim3(RS_THREADS), 0, s, x, W, W_out, f.P, f.Q, f.T, f.off, fm.G, f.dev, y, dst_stride);
     }
 }
 
 }  // namespace
+
+std::string ResampleForm::str() const { return std::string(lds ? "resample lds G" : "resample cache G") + std::to_string(G); }
+
+ResampleForm resample_form(int64_t W, const ResampleTable& f) {
+    if (W < 1 || f.T % 8 != 0 || f.T < 8 || f.P < 1 || f.Q < 1) throw std::invalid_argument("resample_form: no row or no filter");
+    const int64_t K = (resample_out_len(W, f.P, f.Q) + f.P - 1) / f.P;  // k values of a row
+    ResampleForm fm;
+    // G k groups per workgroup: enough (k group, r) pairs for the 16 waves where the span still fits in LDS
+    int G = 1;
+    while (G * f.P < RS_THREADS / RS_LANES && (int64_t)G * RS_LANES < K && rs_span(2 * G, f.P, f.Q, f.T) * 4 <= RS_LDS_MAX) G *= 2;
+    const int64_t span_bytes = rs_span(G, f.P, f.Q, f.T) * 4;
+    fm.G = G;
+    fm.lds = span_bytes <= RS_LDS_MAX;
+    fm.lds_bytes = fm.lds ? span_bytes : 0;
+    fm.grid_x = (K + (int64_t)G * RS_LANES - 1) / ((int64_t)G * RS_LANES);
+    return fm;
+}
 
 void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride) {
     with_enc(enc, "launch_resample", [&](auto e) { launch_resample_t<decltype(e)::value>(s, x, rows, W, f, static_cast<unsigned char*>(y), dst_stride); });

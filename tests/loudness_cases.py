@@ -4,9 +4,12 @@ Rows (six per call, the same at every rate): a 30 Hz + 997 Hz tone on a 0.1 DC o
 boundary), coloured noise under an envelope, a quiet-then-loud row (the relative gate), a row of 4 hop - 1 samples (one short of a
 block), an all-zero row and a row of n = 0.  Behind n[r] every row is NaN.  W = 3 * 32768 + 40: three full scan tiles of 1024 chunks
 and the start of a fourth, 13 workgroup spans of 8192 samples; the GPU tests run it as W (16-byte loads), W + 1 and W uploaded 4 bytes
-off alignment (scalar loads).  The lengths walk every boundary of the decomposition (LENGTHS below).
+off alignment (scalar loads).  At 176.4 and 192 kHz W = 6 * 32768 + 40 (width(hz)): 7 gating blocks at 192 kHz as at 96 kHz, seven scan
+tiles, 25 spans.  The lengths walk every boundary of the decomposition (lengths() below).
 
-Everything is computed once per process (case(hz)) and handed out read-only.
+Everything is computed once per process (case(hz)) and handed out read-only.  The restatement loops over the samples in Python with the
+six rows side by side; case(hz) takes about 3.5 s up to 96 kHz and 6 to 6.5 s at 176.4 and 192 kHz (twice the samples) on one CPU core, so the
+rows stay as they are and W is not shrunk.
 
 Bounds.  None is taken from a kernel.  Each comes from the float32 restatement of the same recurrence (loudness_ref.cascade_states and
 chunk_shares with dtype = float32: sequential from sample 0, every product and sum rounded, no fused multiply-add) held against the
@@ -21,9 +24,11 @@ import numpy as np
 
 from loudness_ref import CHUNK, cascade_states, chunk_shares, chunks, gate_from_segments, hop, segments_from_shares
 
-RATES = (8000, 11025, 22050, 44100, 48000)
-STRADDLING = (11025, 22050, 44100)  # hop 1103, 2205, 4410: no multiple of 32, so chunks straddle segments
+HIGH = (88200, 96000, 176400, 192000)
+RATES = (8000, 11025, 22050, 44100, 48000) + HIGH
+STRADDLING = (11025, 22050, 44100, 88200, 176400)  # hop 1103, 2205, 4410, 8820, 17640: no multiple of 32, so chunks straddle segments
 W = 3 * 32768 + 40
+W_WIDE = 6 * 32768 + 40
 SPAN, TILE = 8192, 32768  # samples per workgroup of the chunk passes, per scan tile
 TONE, NOISE, QUIET_LOUD, SHORT, ZERO, EMPTY = range(6)
 NAMES = ("tone", "noise", "quiet_loud", "short", "zero", "empty")
@@ -31,15 +36,28 @@ SAFETY = 4.0
 SEED = 20
 
 
+def width(hz):
+    """W at hz: up to 96 kHz three full scan tiles and the start of a fourth (7 gating blocks at 96 kHz); at 176.4 and 192 kHz six and the
+    start of a seventh (7 blocks at 192 kHz), or the quiet-then-loud row has too few blocks for the relative gate to decide anything."""
+    return W if hz <= 96000 else W_WIDE
+
+
 def lengths(hz):
-    """n[6] at hz.  Over the five rates: 0, 1, 31, 32, 33, 8191, 8192, 8193, 32767, 32768, 32769, 65536 + 5, a multiple of hop and one
-    more and one less, n % 4 in {1, 2, 3}, and at every rate a row that runs into the fourth scan tile."""
-    h = hop(hz)
+    """n[6] at hz.  Over the rates up to 48 kHz: 0, 1, 31, 32, 33, 8191, 8192, 8193, 32767, 32768, 32769, 65536 + 5, a multiple of hop and
+    one more and one less, n % 4 in {1, 2, 3}, and at every rate a row that runs into the last scan tile.  Each of the four HIGH rates has
+    all of these by itself: the last tile (w - 2, n % 4 = 2), m hop, m hop + 1 and m hop - 1 (n % 4 = 0, 1, 3: these hops are multiples of
+    4), and they change rows from rate to rate, so that the tone, the noise and the quiet-then-loud row each end on a whole segment, one
+    sample past one and one sample short of one at some rate.  The quiet-then-loud row keeps at least 9 segments everywhere."""
+    h, w = hop(hz), width(hz)
     free = {8000: (W, 65536 + 5, 32769, 1),
             11025: (31, W - 1, 60 * h, 8192),
             22050: (W - 2, 32, 40 * h + 1, 32767),
             44100: (32768, W - 3, W, 33),
-            48000: (W, 8193, W - 1, 8191)}[hz]
+            48000: (W, 8193, W - 1, 8191),
+            88200: (w - 2, 11 * h, 10 * h + 1, 9 * h - 1),
+            96000: (10 * h - 1, w - 2, 10 * h, 9 * h + 1),
+            176400: (11 * h + 1, 10 * h - 1, w - 2, 11 * h),
+            192000: (10 * h, 9 * h + 1, 10 * h - 1, w - 2)}[hz]
     return np.array([free[0], free[1], free[2], 4 * h - 1, free[3], 0], np.int64)
 
 
@@ -47,9 +65,9 @@ REQUIRED_LENGTHS = (0, 1, 31, 32, 33, 8191, 8192, 8193, 32767, 32768, 32769, 655
 
 
 def signals(hz):
-    """x [6, W + 1] float32 with NaN behind n[r], and n."""
+    """x [6, width(hz) + 1] float32 with NaN behind n[r], and n."""
     rng = np.random.default_rng(SEED + hz)
-    N = W + 1
+    N = width(hz) + 1
     t = np.arange(N) / hz
     n = lengths(hz)
     white = rng.standard_normal(N)
@@ -114,7 +132,7 @@ def case(hz):
     """x, n, the table, the float64 reference of every pass, the float32 restatement's deviations and the bounds at hz"""
     from supertonic_amd import binding
     c = Case()
-    c.hz, c.hop = hz, hop(hz)
+    c.hz, c.hop, c.W = hz, hop(hz), width(hz)
     c.coef, c.mpow, table_hop = binding.loudness_table(hz)
     assert table_hop == c.hop
     c.x, c.n = signals(hz)

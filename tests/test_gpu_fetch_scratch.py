@@ -18,11 +18,11 @@ SMALL = ([9, 6], np.array([0.50, 0.46], np.float32), 3)
 BIG = ([14, 9, 5, 12, 7, 11], np.array([0.95, 1.10, 0.88, 1.21, 1.02, 0.91], np.float32), 2)
 
 
-def _handle(a):
+def _handle(a, rate=RATE):
     e = binding.Engine(0, "bf16")
     e.load_synthetic(a, 7)
     e.set_vocoder_mode(1)
-    e.set_output_rate(RATE)
+    e.set_output_rate(rate)
     e.set_loudness(TARGET, CEIL)
     e.set_limiter(MS)
     e.set_peak_mode("true")
@@ -30,7 +30,7 @@ def _handle(a):
     return e
 
 
-def _load(a, e, batch):
+def _load(a, e, batch, rate=RATE):
     lens, durs, seed = batch
     ids, mask, sttl, sdp = make_inputs(a, len(lens), max(lens), lens, seed=seed)
     e.batch_upload(ids, mask, sttl, sdp, duration_override=durs)
@@ -38,7 +38,7 @@ def _load(a, e, batch):
     B, L, _ = e.batch_dims()
     W = L * a.base_chunk_size * a.chunk_compress_factor
     spans = [min(W, int(np.float32(d / np.float32(SPEED)) * np.float32(a.sample_rate))) for d in durs]
-    e.dbg_batch_set_wav(fetch_rows.rows(a.sample_rate, W, spans, RATE, MS, 40 + seed))
+    e.dbg_batch_set_wav(fetch_rows.rows(a.sample_rate, W, spans, rate, MS, 40 + seed))
 
 
 def _take(e, slot):
@@ -100,4 +100,24 @@ def test_scratch_grows_under_a_live_handle_and_is_reused_dirty(fresh):
     e.op_loudness(x, RATE, np.array([5000, 4100, 3000], np.int64))
     _assert_same(_take(e, 0), fresh["small"], "small batch in the big batch's scratch, after op_loudness")
     _assert_same(_take(e, 1), fresh["small"], "the same again, from what the handle cached")
+    e.close()
+
+
+def test_scratch_grows_and_is_reused_at_192_khz():
+    """the same at the top of the range: W_out is 4.35 W, and every carve, span guard and join plan is computed from it"""
+    a, rate = tiny_arch(), 192000
+    want = {}
+    for name, batch in (("small", SMALL), ("big", BIG)):
+        f = _handle(a, rate)
+        _load(a, f, batch, rate)
+        want[name] = _take(f, 0)
+        f.close()
+        assert np.any(want[name]["limited"] > 0) and np.all(want[name]["end"] > want[name]["start"]) and np.all(np.isfinite(want[name]["lufs"])), name
+    e = _handle(a, rate)
+    _load(a, e, SMALL, rate)
+    _assert_same(_take(e, 0), want["small"], "first small batch")
+    _load(a, e, BIG, rate)
+    _assert_same(_take(e, 1), want["big"], "big batch after a small one")
+    _load(a, e, SMALL, rate)
+    _assert_same(_take(e, 1), want["small"], "small batch in the big batch's scratch")
     e.close()

@@ -6,7 +6,13 @@ event-timed cost on a C3-sized batch.
 
 Bounds: s is compared within (A + 8) * 2^-24 (limiter_ref.s_tol: sequential summation of A + 1 non-negative terms of total weight <= 1,
 plus the weight, divide and final roundings), y within that times |v| plus 2^-23 |v| (the multiply's and the clamp's roundings).  Where
-s == 1, the sample counts and the padding are compared exactly."""
+s == 1, the sample counts and the padding are compared exactly.
+
+Above 48 kHz the op runs limiter_ref.long_case's rows (width max(20011, 20 A + 4096), tests/test_limiter_cpu.py proves what they hold) at
+A = 1920 (192 kHz, 10 ms: LM_MAX_A), 960, 441 and 88, the envelope path at A = 1920, and the batch-level tests fetch at 88.2 and 192 kHz
+(5 ms, and 10 ms at 192 kHz: the engine's own path to A = 1920).  Measured on an MI355X, worst |y - ref| / bound and |s - ref| / bound per
+case: A = 4 0.151 / 0.171, A = 221 0.041 / 0.041, A = 1920 0.014 / 0.014, A = 960 0.026 / 0.018, A = 441 0.027 / 0.024, A = 88 0.058 / 0.057,
+A = 1920 with the envelope 0.015 / 0.015; batch fetches 0.027 (88.2 kHz), 0.022 (192 kHz, 5 ms) and 0.014 (192 kHz, 10 ms)."""
 import math
 
 import numpy as np
@@ -39,6 +45,7 @@ def _same(a, b):
 def _check_rows(got_y, got_s, outs, n, hz, ms, what):
     """device rows against the reference's: exact where the contract is exact, within the bounds elsewhere"""
     tol = ref.s_tol(hz, ms)
+    worst_y = worst_s = 0.0
     for b, o in enumerate(outs):
         nb, c = int(n[b]), o["c"]
         y = got_y[b, : o["y"].size]
@@ -46,41 +53,92 @@ def _check_rows(got_y, got_s, outs, n, hz, ms, what):
         assert _same(y[nb:], np.clip(o["v"][nb:], -c, c)), (what, b)  # the padding: the clamped product
         v = np.abs(o["v"].astype(np.float64))
         err = np.abs(y.astype(np.float64) - o["y"])
+        worst_y = max(worst_y, float(np.max(err / (tol * v + 2.0 ** -23 * v + 1e-300))))
         print(f"{what} row {b} (n {nb}): limited {o['limited']}, max |y - ref| / bound {np.max(err / (tol * v + 2.0 ** -23 * v + 1e-300)):.3f}")
         assert np.all(err <= tol * v + 2.0 ** -23 * v), (what, b, float(err.max()))
         if got_s is not None:
             s = got_s[b]
             assert np.array_equal(s == 1.0, o["s"] == 1.0), (what, b)
             serr = np.abs(s.astype(np.float64) - o["s"])
+            worst_s = max(worst_s, float(serr.max()) / tol)
             print(f"    max |s - ref| {serr.max():.3g} (bound {tol:.3g})")
             assert np.all(serr <= tol), (what, b, float(serr.max()))
             assert np.all(s[:nb] <= o["r"][:nb]), (what, b)
+    return worst_y, worst_s
 
 
 # ---- 1. the op against the reference ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("hz,ms", [(8000, 0.5), (44100, 5.0)])
+OP_CASES = [(8000, 0.5), (44100, 5.0)] + list(ref.LONG_CASES)  # A = 4, 221, then 1920 (LM_MAX_A), 960, 441, 88 above 48 kHz
+
+
+def _op_rows(hz, ms, rep):
+    """(x, n, g, outs, W): the rows of repeat rep and the reference's results; above 48 kHz the rows that scale with A (limiter_ref.long_case)"""
+    if (hz, ms) in ref.LONG_CASES:
+        x, n, g, outs = ref.long_case(hz, ms, CEIL, rep)
+        return x, n, g, outs, x.shape[1]
+    x, n, g = ref.peaky_rows(hz, ms, CEIL, W_OP, rep)
+    return x, n, g, ref.limit_rows(x, n, g, CEIL, hz, ms), W_OP
+
+
+@pytest.mark.parametrize("hz,ms", OP_CASES)
 def test_op_equals_the_reference(eng, hz, ms):
     A = ref.samples(hz, ms)
     seen = []
+    worst = [0.0, 0.0]
     for rep in (0, 1):
-        x, n, g = ref.peaky_rows(hz, ms, CEIL, W_OP, rep)
+        x, n, g, outs, W = _op_rows(hz, ms, rep)
         seen += n.tolist()
-        outs = ref.limit_rows(x, n, g, CEIL, hz, ms)
         y, s, red, lim = eng.op_limiter(x, hz, n, g, CEIL, ms)
-        _check_rows(y, s, outs, n, hz, ms, f"{hz} Hz rep {rep}")
+        worst = np.maximum(worst, _check_rows(y, s, outs, n, hz, ms, f"{hz} Hz rep {rep}")).tolist()
         assert lim.tolist() == [o["limited"] for o in outs]
         for b, o in enumerate(outs):
             smin = 10.0 ** (-o["reduction_db"] / 20.0)
             assert abs(float(red[b]) - o["reduction_db"]) <= 20.0 / math.log(10.0) * ref.s_tol(hz, ms) / smin + 1e-6 * o["reduction_db"], (b, red[b])
-    assert set(seen) >= {0, 1, A, A + 1, 2 * A + 1, 4096, 4097, 8191, 16385, W_OP}
-    # no lengths, no gain, an even width (the 16-byte path of an untouched tile), no curve asked for
-    x = np.ascontiguousarray(ref.peaky_rows(hz, ms, CEIL, W_OP + 1, 1)[0])
+    if (hz, ms) in ref.LONG_CASES:
+        tiles = range(ref.TILE, W, ref.TILE)
+        assert set(seen) >= {0, 1, A, A + 1, 2 * A + 1, W, W - 1}
+        assert sum(k - 1 in seen for k in tiles) >= 2 and sum(k + 1 in seen for k in tiles) >= 2
+    else:
+        assert set(seen) >= {0, 1, A, A + 1, 2 * A + 1, 4096, 4097, 8191, 16385, W_OP}
+    # no lengths, no gain, a width that is a multiple of 4 (the 16-byte path of an untouched tile), no curve asked for
+    if (hz, ms) in ref.LONG_CASES:
+        x = np.pad(_op_rows(hz, ms, 1)[0], ((0, 0), (0, -W % 4)))
+    else:
+        x = np.ascontiguousarray(ref.peaky_rows(hz, ms, CEIL, W_OP + 1, 1)[0])
+    Ww = x.shape[1]
+    assert Ww % 4 == 0
     outs = ref.limit_rows(x, None, None, CEIL, hz, ms)
     y = np.empty_like(x)
     lim = np.empty(6, np.int64)
-    eng._ck(eng._lib.stn_op_limiter(eng._h, hz, 6, W_OP + 1, x, None, None, CEIL, ms, y.ctypes.data, None, None, lim.ctypes.data))
-    _check_rows(y, None, outs, [W_OP + 1] * 6, hz, ms, f"{hz} Hz whole rows")
+    eng._ck(eng._lib.stn_op_limiter(eng._h, hz, 6, Ww, x, None, None, CEIL, ms, y.ctypes.data, None, None, lim.ctypes.data))
+    worst[0] = max(worst[0], _check_rows(y, None, outs, [Ww] * 6, hz, ms, f"{hz} Hz whole rows")[0])
     assert lim.tolist() == [o["limited"] for o in outs]
+    print(f"{hz} Hz, {ms} ms (A = {A}): worst |y - ref| / bound {worst[0]:.3f}, worst |s - ref| / bound {worst[1]:.3f}")
+
+
+def test_op_follows_the_true_peak_envelope_at_the_longest_look_ahead(eng):
+    """A = 1920 with r from the envelope (stn_op_limiter_ex, peak mode "true": limiter_kernel<true>): the curve of the reference driven
+    by the device's own envelope, within the bounds above; the envelope itself within truepeak_ref's bound."""
+    import truepeak_ref as R
+    hz, ms = 192000, 10.0
+    A = ref.samples(hz, ms)
+    seen = []
+    wy = ws = 0.0
+    for rep in (0, 1):  # the short spans 0, 1, A, A + 1, 2A + 1 and W, then the tile multiples +- 1 and W - 1
+        x, n, g, _, W = _op_rows(hz, ms, rep)
+        seen += n.tolist()
+        op = eng.op_limiter_ex(x, hz, n, g, CEIL, ms, "true")
+        outs = []
+        for b in range(6):
+            assert R.env_violations(op["env"][b], x[b], n[b], g[b]).size == 0, (rep, b)
+            outs.append(dict(R.limit_row_env(x[b], n[b], g[b], CEIL, hz, ms, env=op["env"][b])))
+            outs[b]["limited"] = int(np.count_nonzero(outs[b]["M"][: n[b]] < 1.0))
+        y_s = _check_rows(op["y"], op["s"], outs, n, hz, ms, f"{hz} Hz true-peak envelope rep {rep}")
+        wy, ws = max(wy, y_s[0]), max(ws, y_s[1])
+        assert op["limited"].tolist() == [o["limited"] for o in outs]
+        assert np.array_equal(op["limited"] > 0, n > 0)  # every row with a sample has its peak at sample 0
+    assert set(seen) >= {0, 1, A, A + 1, 2 * A + 1, W, W - 1}
+    print(f"{hz} Hz, {ms} ms, envelope: worst |y - ref| / bound {wy:.3f}, worst |s - ref| / bound {ws:.3f}")
 
 
 # ---- 2. a row that never exceeds the ceiling ----------------------------------------------------------------------------------------------
@@ -99,9 +157,17 @@ def test_a_row_under_the_ceiling_is_the_plain_product(eng):
 
 # ---- 3. independence ---------------------------------------------------------------------------------------------------------------------
 def test_a_rows_output_does_not_depend_on_the_batch(eng):
-    hz, ms = 44100, 5.0
+    _alone_equals_batched(eng, 44100, 5.0)
+
+
+@pytest.mark.parametrize("hz,ms", ref.LONG_CASES)
+def test_a_rows_output_does_not_depend_on_the_batch_above_48_khz(eng, hz, ms):
+    _alone_equals_batched(eng, hz, ms)
+
+
+def _alone_equals_batched(eng, hz, ms):
     for rep in (0, 1):
-        x, n, g = ref.peaky_rows(hz, ms, CEIL, W_OP, rep)
+        x, n, g = _op_rows(hz, ms, rep)[:3]
         y, s, red, lim = eng.op_limiter(x, hz, n, g, CEIL, ms)
         for k in range(6):
             nk = int(n[k])
@@ -158,8 +224,17 @@ def _source(e):
     return x, _spans(e, dur)
 
 
-@pytest.mark.parametrize("rate", [None, 16000])
+@pytest.mark.parametrize("rate", [None, 16000, 88200, 192000])
 def test_batch_fetch_equals_the_reference_on_the_source_rows(rate):
+    _batch_fetch_case(rate, MS)
+
+
+def test_batch_fetch_at_192_khz_and_the_longest_look_ahead():
+    """the engine's own path to A = 1920 (LM_MAX_A): 10 ms at 192 kHz"""
+    _batch_fetch_case(192000, 10.0)
+
+
+def _batch_fetch_case(rate, ms):
     a, e = _engine()
     e.set_output_rate(rate)
     hz = e.output_rate
@@ -167,14 +242,14 @@ def test_batch_fetch_equals_the_reference_on_the_source_rows(rate):
     off = e.batch_fetch()[0]  # today's fetch: the gain capped
     g_cap = e.batch_loudness()[2]
     assert e.limiter is None and not e.batch_limiter()[0].any()
-    e.set_limiter(MS)
-    assert e.limiter == MS
+    e.set_limiter(ms)
+    assert e.limiter == ms
     lufs, peak, g = e.batch_loudness()
     want_g = np.array([10.0 ** ((TARGET - float(l)) / 20.0) for l in lufs])
     assert np.all(np.abs(g - want_g) <= 2.0 ** -23 * want_g) and np.all(g > g_cap)  # the gain applied: uncapped (the cap bound before)
-    outs = ref.limit_rows(x, n, g, CEIL, hz, MS)
+    outs = ref.limit_rows(x, n, g, CEIL, hz, ms)
     got, dur = e.batch_fetch()
-    _check_rows(got, None, outs, n, hz, MS, f"batch at {hz} Hz")
+    _check_rows(got, None, outs, n, hz, ms, f"batch at {hz} Hz")
     for enc in ("pcm16", "mulaw", "pcm24"):
         assert _same(e.batch_fetch_encoded(enc)[0], e.op_encode(got, enc)), enc
     for slot in (0, 1):
@@ -187,7 +262,7 @@ def test_batch_fetch_equals_the_reference_on_the_source_rows(rate):
     assert lim.tolist() == [o["limited"] for o in outs] and np.all(lim > 0)
     for b, o in enumerate(outs):
         smin = 10.0 ** (-o["reduction_db"] / 20.0)
-        assert abs(float(red[b]) - o["reduction_db"]) <= 20.0 / math.log(10.0) * ref.s_tol(hz, MS) / smin + 1e-6 * o["reduction_db"], (b, red[b])
+        assert abs(float(red[b]) - o["reduction_db"]) <= 20.0 / math.log(10.0) * ref.s_tol(hz, ms) / smin + 1e-6 * o["reduction_db"], (b, red[b])
         l_on = loudness_ref.integrated_loudness(got[b, : n[b]], hz)
         l_off = loudness_ref.integrated_loudness(off[b, : n[b]], hz)
         print(f"row {b}: {l_off:.2f} LUFS capped, {l_on:.2f} LUFS limited (target {TARGET}), reduction {red[b]:.2f} dB over {lim[b]} samples")
@@ -196,7 +271,7 @@ def test_batch_fetch_equals_the_reference_on_the_source_rows(rate):
 
 
 # ---- 5. composition --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rate", [None, 16000])
+@pytest.mark.parametrize("rate", [None, 16000, 88200, 192000])
 def test_trimmed_and_joined_fetches_compose(rate):
     a, e = _engine()
     e.set_output_rate(rate)

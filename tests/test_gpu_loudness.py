@@ -47,7 +47,7 @@ def _signals(hz, rng):
     return x, n
 
 
-@pytest.mark.parametrize("hz", [8000, 11025, 16000, 22050, 44100, 48000])
+@pytest.mark.parametrize("hz", [8000, 11025, 16000, 22050, 44100, 48000, 88200, 96000, 176400, 192000])
 def test_op_against_float64(eng, hz):
     rng = np.random.default_rng(hz)
     x, n = _signals(hz, rng)
@@ -248,7 +248,7 @@ def test_off_is_the_native_path_and_graphs_survive_toggles():
     fresh.close()
 
 
-@pytest.mark.parametrize("rate", [None, 16000])
+@pytest.mark.parametrize("rate", [None, 16000, 88200, 192000])
 def test_length_aware_rows_are_position_independent(rate):
     """vocoder mode 1: each row's L, peak and gain are those of its own span measured alone, and its normalized span is that gain
     applied to the span: bit for bit, whatever the row was batched with"""

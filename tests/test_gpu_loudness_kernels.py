@@ -15,8 +15,18 @@ comes from a kernel.  The restatement's own deviation / the largest the MI355X s
     22050    1.0e-04 / 7.9e-05    4.4e-04 / 3.5e-04    1.2e-04 / 1.1e-04    1.6e-05 / 1.0e-05
     44100    2.3e-04 / 1.9e-04    1.5e-03 / 1.2e-03    4.7e-04 / 3.3e-04    3.1e-05 / 2.4e-05
     48000    2.8e-04 / 2.3e-04    1.8e-03 / 1.2e-03    3.8e-04 / 3.7e-04    4.8e-05 / 4.3e-05
+    88200    4.4e-04 / 2.9e-04    7.1e-03 / 4.3e-03    1.0e-03 / 1.5e-03    7.8e-05 / 1.4e-04
+    96000    5.2e-04 / 3.1e-04    9.6e-03 / 5.9e-03    1.0e-03 / 1.1e-03    1.6e-04 / 1.2e-04
+    176400   8.7e-04 / 5.2e-04    2.1e-02 / 1.6e-02    2.9e-03 / 2.7e-03    1.5e-04 / 5.9e-04
+    192000   1.1e-03 / 6.9e-04    2.5e-02 / 1.8e-02    3.1e-03 / 3.6e-03    2.8e-04 / 3.6e-04
 
-and |dL| at most 2.2e-05 LU (48 kHz, the tone row) against the float64 L under the same coefficients.
+and |dL| against the float64 L under the same coefficients at most 2.2e-05 LU up to 48 kHz (48 kHz, the tone row) and 4.5e-05, 1.5e-04,
+3.3e-04 and 7.7e-05 LU at 88.2, 96, 176.4 and 192 kHz (the tone row each time; allowed there 1.4e-03 to 4.8e-03).  Measured over bound
+at the four rates above 48 kHz, worst pass: 0.45, 0.27, 0.96 and 0.32.  The 0.96 is the segment sums at 176.4 kHz (5.9e-04 of the tone
+row's largest segment against 4 x 1.5e-04): the kernels' error there is 3.8 x the restatement's although pa / pb stay at its level, the
+closest any pass comes to its bound.  Above 48 kHz W is per rate (loudness_cases.width: 6 * 32768 + 40 at 176.4 and 192 kHz, seven
+scan tiles, WIDE_SEAMS), and pb must be nonzero at exactly the chunks a segment boundary cuts (9, 9, 8, 2 on the four live rows at
+88.2 kHz; 8, 6, 8, 2 at 176.4 kHz).
 
 These tests found a fault.  With the scan in fp32, pa on the tone row (0.1 DC offset) was 2.23e-03 at 44.1 kHz and 2.12e-03 at 48 kHz,
 4.7 and 5.5 x the restatement, and L of that row was off by 8.5e-04 LU, although the start states were within their bound component by
@@ -37,9 +47,14 @@ from loudness_ref import CHUNK, chunks, gate_from_segments, integrated_loudness,
 pytestmark = pytest.mark.gpu
 POISON = 0x7FC00000
 SEAMS = (255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049)  # chunks around a workgroup span's end and the scan's tile ends
+WIDE_SEAMS = SEAMS + (3071, 3072, 3073, 4095, 4096, 4097, 5119, 5120, 5121, 6143, 6144, 6145)  # at 176.4 and 192 kHz: seven tiles
 FORMS = ("vec", "scalar_w1", "scalar_misaligned")
 TARGET, CEIL = -20.0, -1.0
 MEASURED = {}
+
+
+def _seams(c):
+    return WIDE_SEAMS if c.W == lc.W_WIDE else SEAMS
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +71,7 @@ def _run(eng, hz, form):
     """one call per (rate, form), shared by the tests and left unchanged: W with 16-byte loads, W + 1, and W uploaded 4 bytes off"""
     if (hz, form) not in _runs:
         c = lc.case(hz)
-        x = c.x if form == "scalar_w1" else np.ascontiguousarray(c.x[:, : lc.W])
+        x = c.x if form == "scalar_w1" else np.ascontiguousarray(c.x[:, : c.W])
         o = eng.op_loudness_ex(x, hz, c.n, on=True, target_lufs=TARGET, ceiling_dbfs=CEIL, x_misalign=int(form == "scalar_misaligned"))
         for v in o.values():
             if isinstance(v, np.ndarray):
@@ -92,7 +107,7 @@ def _check_states(c, got, ref, scale, bound, what, hz, form):
     with np.errstate(divide="ignore", invalid="ignore"):
         rel = np.where(s > 0, d / s, np.where(d > 0, np.inf, 0.0))
     bad = np.argwhere(rel > bound)
-    seams = {k: float(rel[:, k].max()) for k in SEAMS if k < K}
+    seams = {k: float(rel[:, k].max()) for k in _seams(c) if k < K}
     assert bad.size == 0, (what, hz, form, f"bound {bound:.2e}", [(lc.NAMES[r], f"chunk {k}", "s1 s2 t1 t2".split()[q], f"{rel[r, k, q]:.2e}")
                                                                  for r, k, q in bad[:6]], "at the seams", seams)
     _worst(what, hz, float(rel.max()))
@@ -121,10 +136,11 @@ def test_scan_start_states_at_every_chunk(eng, hz, form):
     c, o = lc.case(hz), _run(eng, hz, form)
     _form_ran(o, form)
     K = c.ref["start"].shape[1]
-    assert all(not np.isnan(c.ref["start"][:, k]).all() for k in SEAMS), "a row reaches every seam"
-    assert K > 3 * 1024 and (c.n > 12 * lc.SPAN).any()  # four scan tiles, thirteen workgroup spans
+    assert all(not np.isnan(c.ref["start"][:, k]).all() for k in _seams(c)), "a row reaches every seam"
+    # a row in the last tile and the last span: at W = 3 * 32768 + 40 four scan tiles and 13 workgroup spans, at 6 * 32768 + 40 seven and 25
+    assert K > c.W // lc.TILE * 1024 and (c.n > c.W // lc.SPAN * lc.SPAN).any()
     seams = _check_states(c, o["st_start"], c.ref["start"], c.scale["start"], c.bound["start"], "start", hz, form)
-    assert set(seams) == set(SEAMS)
+    assert set(seams) == set(_seams(c))
     assert np.all(_bits(o["st_start"][:, 0])[c.n > 0] == 0)  # the first chunk starts from +0.0
 
 
@@ -156,7 +172,11 @@ def test_energy_shares_and_segments(eng, hz, form):
     nz = live & (o["pb"][:, :K] != 0)
     assert np.all(has["pb"][nz]) and np.all(nz[has["pb"] & (c.ref["pb"] > 0)]), (hz, form)
     if hz in lc.STRADDLING:
-        assert nz.sum(axis=1).max() >= 20 and (nz.sum(axis=1) >= 2).sum() >= 3, (hz, nz.sum(axis=1))
+        # the segment boundaries inside a row's whole segments that fall inside a chunk: 20 or more on the longest row up to 48 kHz, all
+        # there are above (9 of 10 at 88.2 kHz, where 8 hop is a multiple of 32; 8 of 10 at 176.4 kHz, where 4 hop and 8 hop are)
+        cuts = np.array([sum(j * c.hop % CHUNK != 0 for j in range(1, int(c.n[r]) // c.hop)) for r in range(6)])
+        assert np.array_equal(nz.sum(axis=1)[: lc.ZERO], cuts[: lc.ZERO]), (hz, nz.sum(axis=1), cuts)
+        assert nz.sum(axis=1).max() >= (8 if hz in lc.HIGH else 20) and (nz.sum(axis=1) >= 2).sum() >= 3, (hz, nz.sum(axis=1))
     else:
         assert not has["pb"].any() and not nz.any()
     for r in range(6):
@@ -176,7 +196,7 @@ def test_energy_shares_and_segments(eng, hz, form):
 def test_gate_from_the_devices_own_shares(eng, hz, form):
     c, o = lc.case(hz), _run(eng, hz, form)
     _form_ran(o, form)
-    off = eng.op_loudness_ex(np.ascontiguousarray(c.x[:, : lc.W]), hz, c.n, on=False, target_lufs=TARGET, ceiling_dbfs=CEIL)
+    off = eng.op_loudness_ex(np.ascontiguousarray(c.x[:, : c.W]), hz, c.n, on=False, target_lufs=TARGET, ceiling_dbfs=CEIL)
     assert np.all(_bits(off["gain"]) == _bits(np.float32(1.0))) and np.array_equal(_bits(off["lufs"]), _bits(_run(eng, hz, "vec")["lufs"]))
     defined = capped = 0
     for r in range(6):
@@ -222,7 +242,7 @@ def test_forms_and_batches_agree_bit_for_bit(eng, hz):
     v, w1, mis = (_run(eng, hz, f) for f in FORMS)
     _form_ran(v, "vec"), _form_ran(w1, "scalar_w1"), _form_ran(mis, "scalar_misaligned")
     Ks = v["pk"].shape[1]
-    assert w1["pk"].shape[1] == chunks(lc.W + 1) == Ks
+    assert w1["pk"].shape[1] == chunks(c.W + 1) == Ks
     live = _live(c, Ks)
     for key in ("st_end", "st_start", "pk", "pa", "pb", "lufs", "peak", "gain"):
         assert np.array_equal(_bits(v[key]), _bits(mis[key])), (hz, key)  # the same W: the whole buffers, poison included
@@ -261,12 +281,12 @@ def test_poison_stays_behind_every_row_and_no_nan_comes_in(eng, hz, form):
 def test_the_plain_op_is_the_same_measurement_and_ignores_dirty_scratch(eng, hz):
     c, o = lc.case(hz), _run(eng, hz, "vec")
     _form_ran(o, "vec")
-    x = np.ascontiguousarray(c.x[:, : lc.W])
+    x = np.ascontiguousarray(c.x[:, : c.W])
     lufs, peak = eng.op_loudness(x, hz, c.n)
     assert np.array_equal(_bits(lufs), _bits(o["lufs"])) and np.array_equal(_bits(peak), _bits(o["peak"]))
     # a larger call of other rows leaves its values all over the grow-only scratch; the smaller call after it reads none of them
     rng = np.random.default_rng(hz)
-    eng.op_loudness(rng.standard_normal((8, lc.W + 4096)).astype(np.float32), hz)
+    eng.op_loudness(rng.standard_normal((8, c.W + 4096)).astype(np.float32), hz)
     sub = [lc.NOISE, lc.QUIET_LOUD, lc.SHORT, lc.TONE]
     l2, p2 = eng.op_loudness(x[sub], hz, c.n[sub])
     assert np.array_equal(_bits(l2), _bits(o["lufs"][sub])) and np.array_equal(_bits(p2), _bits(o["peak"][sub]))

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "supertonic_amd", "example_native")
 ENCS = ["f32", "pcm16", "pcm24", "mulaw", "alaw"]
 ZERO = {e: binding.ZERO_CODEWORD[binding.ENCODINGS[e]] for e in ENCS}
-RATES = [8000, 11025, 16000, 22050, 44100, 48000]
+RATES = [8000, 11025, 16000, 22050, 44100, 48000, 88200, 96000, 176400, 192000]  # frames of 80 to 1920 samples
 MARGIN_DB = 0.01
 
 

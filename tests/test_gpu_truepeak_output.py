@@ -148,7 +148,7 @@ def test_sample_mode_overshoots_and_true_mode_holds_the_ceiling(rate):
     e.close()
 
 
-@pytest.mark.parametrize("rate", [None, 16000])
+@pytest.mark.parametrize("rate", [None, 16000, 88200, 192000])
 def test_encodings_trimmed_and_joined_fetches_compose(rate):
     a, e = _engine(rate)
     hz = e.output_rate

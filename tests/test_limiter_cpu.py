@@ -61,6 +61,57 @@ def test_reference_keeps_the_contracts_properties(hz, ms):
                 assert abs(o["y"][nb + 5]) == c  # the over-level sample of the padding, clamped
 
 
+@pytest.mark.parametrize("hz,ms", ref.LONG_CASES)
+def test_long_look_ahead_rows_hold_what_the_kernel_can_get_wrong(hz, ms):
+    """the rows of limiter_ref.long_case (A = 1920, 960, 441, 88), read off the reference's own r and M: in each whole-span row an
+    isolated peak with 2A + 1 clear samples each side, two peaks A apart, two 2A + 1 apart with nothing between, a plateau of 3A
+    samples, peaks on both sides of tile boundaries, a tile the reference leaves untouched (the kernel's early exit) and, at the
+    largest A, a peak whose reach covers three tiles; the spans; and the contract's properties on every row."""
+    A = ref.samples(hz, ms)
+    lay = ref.long_layout(A)
+    W, T = lay["W"], ref.TILE
+    assert W == max(20011, 20 * A + 4096)
+    spans = ref.long_spans(A)
+    assert set(spans) >= {0, 1, A, A + 1, 2 * A + 1, W, W - 1} and len(spans) == 12
+    assert sum(s % T == T - 1 for s in spans) >= 2 and sum(s % T == 1 and s > 1 for s in spans) >= 2  # tile multiples -+ 1
+    whole = 0
+    for rep in (0, 1):
+        x, n, g, outs = ref.long_case(hz, ms, -1.0, rep)
+        assert x.shape == (6, W) and n.tolist() == spans[6 * rep:6 * rep + 6]
+        for b, o in enumerate(outs):
+            c, nb = float(o["c"]), int(n[b])
+            assert np.abs(o["y"]).max() <= c
+            assert np.all(o["s"][:nb] <= o["r"][:nb].astype(np.float64))
+            assert np.array_equal(o["s"][:nb] == 1.0, o["M"][:nb] == 1.0)
+            assert np.all(o["s"] > 0.0) and np.all(o["s"][nb:] == 1.0)
+            assert o["limited"] == np.count_nonzero(o["s"][:nb] < 1.0)
+            if nb + 5 < W:
+                assert abs(o["y"][nb + 5]) == c
+            if nb < W - 1:
+                continue
+            whole += 1
+            hot = o["r"] < 1.0
+            iso = lay["iso"]
+            assert hot[iso] and not hot[iso - 2 * A - 1:iso].any() and not hot[iso + 1:iso + 2 * A + 2].any()
+            assert np.all(o["M"][iso - A:iso + A + 1] < 1.0) and o["M"][iso - A - 1] == 1.0 and o["M"][iso + A + 1] == 1.0  # its reach, no more
+            p, q = lay["pair"]
+            assert q - p == A and hot[p] and hot[q] and not hot[p + 1:q].any()
+            p, q = lay["wide"]
+            assert q - p == 2 * A + 1 and hot[p] and hot[q] and not hot[p + 1:q].any() and o["M"][p + A + 1] < 1.0  # (m[i - A] reaches q)
+            p, q = lay["plateau"]
+            assert q - p == 3 * A and hot[p:q].all()
+            assert len(lay["bounds"]) >= 2 and all(hot[k - 1] and hot[k + 1] for k in lay["bounds"])
+            tiles = o["M"][:W // T * T].reshape(-1, T)
+            untouched = np.flatnonzero(np.all(tiles == 1.0, axis=1))
+            assert untouched.size >= 1  # r == 1 over the tile and A samples each side
+            for t in untouched:
+                assert not hot[max(0, t * T - A):t * T + T + A].any()
+            assert np.any(tiles < 1.0)
+            if A == 1920:  # the isolated peak at 4440 turns down samples of tiles 1, 2 and 3
+                assert len({(iso - A) // T, iso // T, (iso + A) // T}) == 3
+    assert whole == 2
+
+
 def test_reference_leaves_a_row_under_the_ceiling_alone():
     x = (0.3 * np.sin(np.arange(5000) / 7.0)).astype(np.float32)
     o = ref.limit_row(x, 4000, 1.7, -1.0, 16000, 5.0)

@@ -32,24 +32,36 @@ def test_reference_equals_the_scipy_reference(hz):
     assert defined >= 1
 
 
+def _kinds(n, h):
+    seen = set()
+    for v in n:
+        seen.add(int(v))
+        if v and v % h == 0:
+            seen.add("hop")
+        if v > 1 and v % h == 1:
+            seen.add("hop+1")
+        if v % h == h - 1:
+            seen.add("hop-1")
+        if v % 4:
+            seen.add(f"mod4={v % 4}")  # with W % 4 == 0: the 16-byte path's last load runs past n
+    return seen
+
+
 def test_the_lengths_walk_every_boundary():
+    kinds = {"hop", "hop+1", "hop-1", "mod4=1", "mod4=2", "mod4=3"}
     seen = set()
     for hz in lc.RATES:
-        n, h = lc.lengths(hz), lc.hop(hz)
-        assert np.all(n <= lc.W) and n[lc.SHORT] == 4 * h - 1 and n[lc.EMPTY] == 0
-        assert n.max() > 3 * lc.TILE + CHUNK  # a chunk beyond the third tile
-        for v in n:
-            seen.add(int(v))
-            if v and v % h == 0:
-                seen.add("hop")
-            if v > 1 and v % h == 1:
-                seen.add("hop+1")
-            if v % h == h - 1:
-                seen.add("hop-1")
-            if v % 4:
-                seen.add(f"mod4={v % 4}")  # with W % 4 == 0: the 16-byte path's last load runs past n
-    assert lc.W % 4 == 0
-    assert seen >= set(lc.REQUIRED_LENGTHS) | {"hop", "hop+1", "hop-1", "mod4=1", "mod4=2", "mod4=3"}, seen
+        n, h, w = lc.lengths(hz), lc.hop(hz), lc.width(hz)
+        assert w % 4 == 0 and w % lc.TILE == 40 and w // h >= 10  # at least 7 gating blocks in a full row
+        assert np.all(n <= w) and n[lc.SHORT] == 4 * h - 1 and n[lc.EMPTY] == 0
+        assert n.max() > w // lc.TILE * lc.TILE + CHUNK  # a chunk beyond the last full tile
+        seen |= _kinds(n, h)
+        if hz in lc.HIGH:  # each of these rates walks the hop and the 16-byte tail by itself, on rows long enough to have a loudness
+            long_rows = n[[lc.TONE, lc.NOISE, lc.QUIET_LOUD, lc.ZERO]]
+            assert _kinds(long_rows, h) >= kinds and long_rows.min() >= 9 * h - 1, (hz, n)
+    assert [lc.width(hz) for hz in lc.RATES] == [lc.W] * 7 + [lc.W_WIDE] * 2 and lc.W == 3 * 32768 + 40 and lc.W_WIDE == 6 * 32768 + 40
+    assert set(lc.STRADDLING) == {hz for hz in lc.RATES if lc.hop(hz) % CHUNK}
+    assert seen >= set(lc.REQUIRED_LENGTHS) | kinds, seen
 
 
 def test_gate_margins_of_the_rows():
@@ -129,7 +141,14 @@ def test_bounds_see_every_injected_fault(hz):
       the next-segment share dropped: the pa / pb bound and the segment bound, at the rates whose hop is no multiple of 32 (at 8 and
         48 kHz no chunk straddles, pb is all zeros and there is nothing to drop: the GPU test asserts those zeros exactly);
       the last chunk of the last whole segment dropped: the pa / pb bound.
-    Every one misses its bound by at least 10 x; the change of L it causes is printed next to that."""
+    Every one misses its bound by at least 10 x; the change of L it causes is printed next to that.
+    One pair cannot reach 10 x, by arithmetic and not by the choice of rows: the dropped share against the segment bound at 176.4 kHz.  A
+    chunk hands at most 31 samples to the next segment (24 there: the boundaries fall 8, 16 and 24 samples into a chunk) out of hop =
+    17640, and a tone's y^2 is at most twice its mean, so the fault moves a segment by at most about 2 * 31 / 17640 = 3.5e-3 of the
+    largest one (2.7e-3 on these rows, the tone row), while the fp32 restatement itself moves the tone row's segments by 1.5e-4 and the
+    bound is 4 x that: 10 x the bound is 6.2e-3, more than the fault can be.  The pass that breaks is held to the share bound, which the
+    fault misses by 43 x there; against the segment bound it is asserted to fail (ratio above 1; 4.3 on the float64 model) and the
+    ratio is printed, so the segment check alone is about 4 x sharp at that rate."""
     c = lc.case(hz)
     assert all(v > 0 for v in c.bound.values())
     lines = []
@@ -145,5 +164,9 @@ def test_bounds_see_every_injected_fault(hz):
         ratio = _ratio(c, got, keys)
         dL = max(abs(lc.loudness_of(c, got, r) - c.gate[r][0]) for r in range(6) if np.isfinite(c.gate[r][0]))
         lines.append(f"{name}: {ratio:.0f} x its bound, moves L by {dL:.4f} LU")
-        assert ratio >= 10.0, (hz, name, ratio)
+        need = 10.0
+        if hz == 176400 and name == "pb dropped (segments)":
+            assert 10.0 * c.bound["seg"] > 2 * 31 / c.hop  # out of the fault's reach (docstring); it still has to fail the bound
+            need = 1.0 + 1e-9
+        assert ratio >= need, (hz, name, ratio)
     print(f"\n{hz} Hz: " + "; ".join(lines))

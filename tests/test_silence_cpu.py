@@ -28,6 +28,7 @@ def _row(n, spans, amp=0.5):
 def test_reference_rules_on_hand_made_rows():
     assert ref.frame(44100) == 441 and ref.frame(11025) == 110 and ref.frame(8000) == 80 and ref.samples(HZ, 20.0) == 320
     assert ref.samples(44100, 5.0) == 221 and ref.samples(8000, 0.05) == 0  # int(x + 0.5)
+    assert [ref.frame(hz) for hz in (88200, 96000, 176400, 192000)] == [882, 960, 1764, 1920]
     # an all-zero row and a row below the -70 dBFS floor: no speech, nothing is cut
     assert ref.edges(np.zeros(4000, np.float32), 4000, HZ, 40.0, 20.0)[:2] == (0, 4000)
     assert ref.edges(np.full(4000, 3e-4, np.float32), 4000, HZ, 40.0, 20.0)[:2] == (0, 4000)  # 9e-8 <= 1e-7
@@ -75,7 +76,7 @@ def test_reference_fade_is_three_float32_multiplies():
     assert ref.trimmed_row(x, 4000, 1000, 1000, HZ, 5.0).size == 0
 
 
-@pytest.mark.parametrize("hz", [8000, 11025, 16000, 22050, 44100, 48000])
+@pytest.mark.parametrize("hz", [8000, 11025, 16000, 22050, 44100, 48000, 88200, 96000, 176400, 192000])
 def test_library_fade_window_is_the_float64_formula_rounded(hz):
     for ms in (0.0, 0.4, 5.0, 12.5, 50.0):
         fd = int(float(np.float32(ms)) * hz / 1000.0 + 0.5)
@@ -86,6 +87,18 @@ def test_library_fade_window_is_the_float64_formula_rounded(hz):
         binding.silence_fade_window(hz, 50.5)
     with pytest.raises(binding.StnError):
         binding.silence_fade_window(hz, -1.0)
+
+
+@pytest.mark.parametrize("hz", [88200, 96000, 176400, 192000])
+def test_reference_decides_the_gpu_rows_above_48_khz_with_margin(hz):
+    """the rows tests/test_gpu_silence.py runs at the rates above 48 kHz (frames of 882 to 1920 samples): the float64 reference decides
+    every edge at least 0.01 dB from its threshold, so the kernel's fp32 levels cannot move one"""
+    import itertools
+    x, n = ref.speech_rows(hz, 6, 2.4, hz)
+    for top_db, keep_ms in itertools.product((30.0, 40.0, 50.0), (20.0, 0.0)):
+        s, e, margin = ref.batch_edges(x, n, hz, top_db, keep_ms)
+        assert margin.min() >= 0.01, (hz, top_db, margin)
+        assert s[0] == 0 and e[1] == n[1] and np.all(e > s) and np.any(s > 0) and np.any(e < n)
 
 
 def test_setting_ranges_and_messages_at_the_python_host():
