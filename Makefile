@@ -62,8 +62,15 @@ build_asan/host_fuzz: tools/host_fuzz.cpp $(HOST_ONLY) $(HDRS)
 	@mkdir -p build_asan
 	g++ $(ASAN_FLAGS) -o $@ tools/host_fuzz.cpp $(HOST_ONLY)
 
+# the pause limit's host rule (csrc/host/pause_plan.cpp) as a stand-alone program under the same sanitizers: tools/pause_plan_check.cpp feeds it
+# the CPU cases and a sample-by-sample second implementation (tests/test_pause_asan_cpu.py runs it)
+pause-asan: build_asan/pause_plan_check
+build_asan/pause_plan_check: tools/pause_plan_check.cpp $(CSRC)/host/pause_plan.cpp $(CSRC)/host/pause_plan.hpp include/stn.h
+	@mkdir -p build_asan
+	g++ $(ASAN_FLAGS) -o $@ tools/pause_plan_check.cpp $(CSRC)/host/pause_plan.cpp
+
 clean:
 	rm -rf build build_asan supertonic_amd/libstn.so supertonic_amd/example_native
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean probe probe-ingest probe-launch host-asan
+.PHONY: all oracle clean probe probe-ingest probe-launch host-asan pause-asan

@@ -429,6 +429,43 @@ int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_
  * rate) and forget every fetch-time measurement cached for it.  For tests that need rows with known silences. */
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav);
 
+/* ---- pause limit -------------------------------------------------------------------------------------
+ * With silence trimming on AND the pause limit on, every pause inside a row's speech that is longer than max_pause_ms is shortened to
+ * max_pause_ms on the GPU at fetch time.  Without trimming the setting has no effect and adds no launch or allocation.  It uses
+ * trimming's top_db, keep_ms and fade_ms and the same signal, span n, frames F, levels m_k, threshold, f0, f1, start and end.  The latent
+ * geometry, the reported durations, the captured pipeline and the graph key are untouched; toggling it drops or re-captures no graph.
+ * Pauses: a maximal run of inactive frames a .. b - 1 with f0 < a and b <= f1 (frames a - 1 and b are active); its samples are
+ * [aF, bF), its length P = (b - a) F.  Mp = (int64_t)(max_pause_ms * hz / 1000 + 0.5) (in double).  A pause with P > Mp is cut: samples
+ * [aF + hl, bF - hr) are dropped, hl = Mp - Mp / 2 and hr = Mp / 2, so exactly Mp samples of the row's own pause remain.  A pause with
+ * P <= Mp, and a row without speech, is untouched.  At most 255 cuts are made per row: the first 255 in time order.
+ * Segments: with cuts c_1 .. c_m the row's segments are [start, c_1.lo), [c_1.hi, c_2.lo), ..., [c_m.hi, end), laid end to end from
+ * column 0; no silence is inserted.  Each segment edge made by a cut (and start > 0, end < n as under trimming) is faded over
+ * min(Fd, segment length) samples with trimming's window and sample rule.  When Mp / 2 < Fd the fade reaches past the kept half of the
+ * pause into the neighbouring speech frame; this is allowed.  len_b is the sum of the segment lengths.
+ * Everything else follows trimming with len_b and the segment list in place of [start, end): per-row fetches deliver [B][W_out] with
+ * zero codewords behind len_b and need no host read; joined fetches take a member's segments in order, its duration in prog_dur is
+ * (float)len_b / (float)hz, and the plan reads the rows' cut lists with one device-to-host copy per finished batch and setting;
+ * the per-row loudness gain stays the one of the untrimmed span; stn_batch_silence_edges keeps reporting start and end.  A row's table
+ * depends on its own levels and the parameters only.  The group refuses the setting.  DESIGN.md section 17. */
+/* on = 0: off (the default).  max_pause_ms in [20, 5000]; out of range: STN_ERR_INVALID with a message, and the previous setting stays. */
+int stn_set_pause_limit(stn_handle* h, int on, float max_pause_ms);
+int stn_get_pause_limit(const stn_handle* h, int* on, float* max_pause_ms);
+/* the finished batch as the current trimming parameters and max_pause_ms cut it, whether either setting is on or not: len [B] = len_b,
+ * n_cuts [B], and cuts_or_null [B][cap_pairs][2] = (lo, hi) of row b's first min(n_cuts[b], cap_pairs) cuts (the rest of a row's
+ * pairs is left untouched).  Each pointer may be NULL. */
+int stn_batch_pauses(stn_handle* h, int64_t* len, int32_t* n_cuts, int64_t* cuts_or_null, int cap_pairs);
+/* op-level, on host operands as stn_op_silence_trim: y [rows][W] samples of enc, row r's segments end to end from column 0 (times
+ * gain_or_null[r], cut edges faded), zero codewords behind len[r] */
+int stn_op_pause_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float top_db, float keep_ms,
+                      float fade_ms, float max_pause_ms, const float* gain_or_null, int enc, void* y, int64_t* start, int64_t* end,
+                      int64_t* len, int32_t* n_cuts, int64_t* cuts_or_null, int cap_pairs);
+/* the rule on the host, no device needed: n samples at hz in K = ceil(n / F) frames with levels level[K] -> start, end, *n_cuts and
+ * cuts [cap_pairs][2] (the first min(*n_cuts, cap_pairs) pairs).  Each output pointer may be NULL.  STN_ERR_INVALID (why:
+ * stn_pause_plan_error) for a parameter out of range or K != ceil(n / F). */
+int stn_pause_plan(int hz, int64_t n, const double* level, int64_t K, float top_db, float keep_ms, float max_pause_ms, int64_t* start,
+                   int64_t* end, int64_t* cuts, int cap_pairs, int32_t* n_cuts);
+const char* stn_pause_plan_error(void);
+
 /* ---- limiter -----------------------------------------------------------------------------------------
  * A look-ahead peak limiter behind the loudness gain.  With the limiter on AND loudness on, the ceiling of stn_set_loudness is enforced
  * by the limiter and no longer by capping the gain: a row gets the full loudness gain, and only the few milliseconds around a sample

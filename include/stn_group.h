@@ -57,6 +57,9 @@ int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceilin
 int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms);
 /* peak mode of every rank (stn_set_peak_mode; no effect without loudness): STN_PEAK_SAMPLE or STN_PEAK_TRUE */
 int stn_group_set_peak_mode(stn_group* g, int mode);
+/* the pause limit (stn_set_pause_limit) works inside trimmed rows, and the group does not trim: on != 0 is refused with
+ * STN_ERR_INVALID and a message; on = 0 is accepted and changes nothing */
+int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms);
 /* sample encoding (STN_ENC_*, stn.h) of the gather of the next stn_group_synthesize: every rank encodes its shard on its GPU and the
  * blocks, the exchange and the host stage are sized in that encoding's bytes (a mu-law gather moves half the bytes of a PCM16 one).
  * The default is STN_ENC_PCM16; an unknown encoding is STN_ERR_INVALID. */

@@ -315,6 +315,11 @@ def load():
     L.stn_op_silence_edges.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, vp, vp]
     L.stn_op_silence_trim.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, vp, ci, vp, vp, vp]
     L.stn_silence_fade_window.argtypes = [ci, cf, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_set_pause_limit.argtypes = [vp, ci, cf]
+    L.stn_get_pause_limit.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf)]
+    L.stn_batch_pauses.argtypes = [vp, vp, vp, vp, ci]
+    L.stn_op_pause_trim.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, cf, vp, ci, vp, vp, vp, vp, vp, vp, ci]
+    L.stn_group_set_pause_limit.argtypes = [vp, ci, cf]
     L.stn_set_limiter.argtypes = [vp, ci, cf]
     L.stn_get_limiter.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf)]
     L.stn_batch_limiter.argtypes = [vp, vp, vp]
@@ -428,6 +433,11 @@ class Group:
         on, t = _loudness_args(target_lufs)
         self._ck(self._lib.stn_group_set_loudness(self._g, on, t, float(ceiling_dbfs)))
 
+    def set_pause_limit(self, max_pause=None):
+        """The group does not trim, so it refuses the pause limit (StnError with the reason); None or False is accepted."""
+        on, ms = pause_limit_args(max_pause)
+        self._ck(self._lib.stn_group_set_pause_limit(self._g, on, ms))
+
     def set_limiter(self, lookahead_ms=None):
         """Look-ahead peak limiter of every rank (Engine.set_limiter): the gathered PCM is then limited row by row."""
         on, ms = limiter_args(lookahead_ms)
@@ -520,6 +530,44 @@ def silence_fade_window(hz, fade_ms):
     if L.stn_silence_fade_window(int(hz), float(fade_ms), w.ctypes.data, w.size, ctypes.byref(n)) < 0:
         raise StnError(-1, "stn_silence_fade_window failed")
     return w
+
+
+MAX_PAUSE_MS = 300.0  # what stn_get_pause_limit reports while the limit was never set
+PAUSE_MAX_CUTS = 255
+
+
+def pause_limit_args(max_pause):
+    """A max_pause argument -> (on, max_pause_ms) for stn_set_pause_limit: None or False = off, a number = the longest pause left inside
+    an utterance in milliseconds.  ValueError, with the ABI's range, for anything else."""
+    if max_pause is None or max_pause is False:
+        return 0, MAX_PAUSE_MS
+    if isinstance(max_pause, bool):
+        raise ValueError("max_pause: None, False or milliseconds in [20, 5000], not True")
+    try:
+        ms = float(max_pause)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_pause: None, False or milliseconds in [20, 5000], not {max_pause!r}") from None
+    if not 20.0 <= ms <= 5000.0:
+        raise ValueError(f"max_pause {ms} ms: must be in [20, 5000]")
+    return 1, ms
+
+
+def pause_plan(level, n, hz, top_db=40.0, keep_ms=None, max_pause_ms=MAX_PAUSE_MS, cap_pairs=PAUSE_MAX_CUTS):
+    """stn_pause_plan (host only, no device): one row's frame levels (float64 [K], K = ceil(n / F)) -> (start, end, cuts [n_cuts, 2]
+    int64 as (lo, hi), n_cuts); cuts holds the first min(n_cuts, cap_pairs) pairs.  A refused argument raises StnError with the reason."""
+    L = load()
+    L.stn_pause_plan.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    L.stn_pause_plan_error.restype = ctypes.c_char_p
+    lv = np.ascontiguousarray(level, np.float64)
+    start, end, nc = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    cuts = np.zeros((max(int(cap_pairs), 0), 2), np.int64)
+    rc = L.stn_pause_plan(int(hz), int(n), lv.ctypes.data, lv.size, float(top_db), float(TRIM_KEEP_MS if keep_ms is None else keep_ms),
+                          float(max_pause_ms), ctypes.addressof(start), ctypes.addressof(end), cuts.ctypes.data if cuts.size else None,
+                          cuts.shape[0], ctypes.addressof(nc))
+    if rc != 0:
+        raise StnError(rc, L.stn_pause_plan_error().decode())
+    return start.value, end.value, cuts[:min(nc.value, cuts.shape[0])], nc.value
 
 
 LIMITER_MS = 5.0
@@ -960,6 +1008,47 @@ class Engine:
                                                float(fade_ms), None if g is None else g.ctypes.data, e, y.ctypes.data, start.ctypes.data,
                                                end.ctypes.data))
         return y, start, end
+
+    def set_pause_limit(self, max_pause=None):
+        """Shorten every pause inside an utterance that is longer than max_pause milliseconds ([20, 5000]) to max_pause, on the GPU at
+        fetch time: None or False = off (the default).  It has effect only while silence trimming is on, and uses its parameters."""
+        on, ms = pause_limit_args(max_pause)
+        self._ck(self._lib.stn_set_pause_limit(self._h, on, ms))
+
+    @property
+    def pause_limit(self):
+        """max_pause in milliseconds, or None when the limit is off."""
+        on, ms = ctypes.c_int(), ctypes.c_float()
+        self._ck(self._lib.stn_get_pause_limit(self._h, ctypes.byref(on), ctypes.byref(ms)))
+        return ms.value if on.value else None
+
+    def batch_pauses(self, cap_pairs=PAUSE_MAX_CUTS):
+        """The finished batch as the current trimming parameters and max_pause cut it, either setting on or off -> (len [B] int64,
+        n_cuts [B] int32, cuts [B, cap_pairs, 2] int64 as (lo, hi); pairs behind a row's n_cuts are -1)."""
+        B = self.batch_dims()[0]
+        ln, nc = np.empty(B, np.int64), np.empty(B, np.int32)
+        cuts = np.full((B, max(int(cap_pairs), 1), 2), -1, np.int64)
+        self._ck(self._lib.stn_batch_pauses(self._h, ln.ctypes.data, nc.ctypes.data, cuts.ctypes.data, cuts.shape[1]))
+        return ln, nc, cuts
+
+    def op_pause_trim(self, x, hz, n=None, top_db=40.0, keep_ms=TRIM_KEEP_MS, fade_ms=TRIM_FADE_MS, max_pause_ms=MAX_PAUSE_MS, gain=None, encoding=None,
+                      cap_pairs=PAUSE_MAX_CUTS):
+        """Detection, the pause limit's cuts and the store on the GPU -> dict(y [rows, W] in the encoding, start, end, len [rows] int64,
+        n_cuts [rows] int32, cuts [rows, cap_pairs, 2] int64 with -1 behind a row's n_cuts): row r's segments end to end from column 0,
+        times gain[r], cut edges faded, zero codewords behind len[r]."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        e = ENC_F32 if encoding is None else encoding_id(encoding)
+        nn = None if n is None else np.ascontiguousarray(n, np.int64)
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        y = encoded_empty(e, rows, W)
+        start, end, ln = np.empty(rows, np.int64), np.empty(rows, np.int64), np.empty(rows, np.int64)
+        nc = np.empty(rows, np.int32)
+        cuts = np.full((rows, max(int(cap_pairs), 1), 2), -1, np.int64)
+        self._ck(self._lib.stn_op_pause_trim(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(top_db), float(keep_ms),
+                                             float(fade_ms), float(max_pause_ms), None if g is None else g.ctypes.data, e, y.ctypes.data,
+                                             start.ctypes.data, end.ctypes.data, ln.ctypes.data, nc.ctypes.data, cuts.ctypes.data, cuts.shape[1]))
+        return dict(y=y, start=start, end=end, len=ln, n_cuts=nc, cuts=cuts)
 
     def set_limiter(self, lookahead_ms=None):
         """Look-ahead peak limiter behind the loudness gain: None = off (the default), True = 5 ms, or the look-ahead in milliseconds

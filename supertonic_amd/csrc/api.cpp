@@ -378,6 +378,23 @@ int stn_op_silence_trim(stn_handle* h, int hz, int rows, int W, const float* x, 
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_silence_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
                  h->eng->op_silence_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, gain, enc, y, start, end); })
 }
+int stn_set_pause_limit(stn_handle* h, int on, float max_pause_ms) {
+    STN_TRY(h, { h->eng->set_pause_limit(on != 0, max_pause_ms); })
+}
+int stn_get_pause_limit(const stn_handle* h, int* on, float* max_pause_ms) {
+    if (!h) return STN_ERR_INVALID;
+    h->eng->get_pause_limit(on, max_pause_ms);
+    return STN_OK;
+}
+int stn_batch_pauses(stn_handle* h, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_pauses(len, n_cuts, cuts, cap_pairs); })
+}
+int stn_op_pause_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
+                      float max_pause_ms, const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts,
+                      int64_t* cuts, int cap_pairs) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pause_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_pause_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, gain, enc, y, start, end, len, n_cuts, cuts, cap_pairs); })
+}
 int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_t* n) {
     if (hz < 1 || !stn::silence_check(1.0f, 0.0f, fade_ms).empty()) return STN_ERR_INVALID;
     try {

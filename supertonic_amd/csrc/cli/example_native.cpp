@@ -10,7 +10,7 @@
 // every chunk normalized on its own, the default, or the joined text as one programme with one gain; text needs one GPU),
 // --trim-chunks (a long text's chunks cut at their durations before they are joined), --trim-silence DB (leading and trailing silence of
 // every utterance trimmed by level on the GPU: frames more than DB below the loudest 10 ms frame; the files then hold the trimmed
-// segments; one GPU only), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5).
+// segments; one GPU only), --max-pause MS (with --trim-silence: pauses inside an utterance longer than MS shortened to MS), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -89,12 +89,17 @@ int main(int argc, char* argv[]) {
         }
         else if (a == "--trim-chunks") opts.trim_chunks = true;  // long texts: every chunk cut at its duration before the join
         else if (a == "--trim-silence" && more) opts.trim_silence_db = std::strtof(argv[++i], nullptr);  // dB below the loudest frame that counts as silence; absent: off
+        else if (a == "--max-pause" && more) opts.max_pause_ms = std::strtof(argv[++i], nullptr);  // ms: longer pauses inside an utterance are shortened to this; absent: off
         else if (a == "--trim-keep" && more) opts.trim_keep_ms = std::strtof(argv[++i], nullptr);  // ms kept around the speech (default 20)
         else if (a == "--trim-fade" && more) opts.trim_fade_ms = std::strtof(argv[++i], nullptr);  // ms of fade over a cut edge (default 5)
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (peak_mode_given && std::isnan(opts.loudness_lufs)) {
         std::cerr << "Error: --peak-mode needs --loudness (it is the ceiling of the loudness gain)\n";
+        return 1;
+    }
+    if (!std::isnan(opts.max_pause_ms) && std::isnan(opts.trim_silence_db)) {
+        std::cerr << "Error: --max-pause needs --trim-silence (pauses are shortened inside trimmed utterances)\n";
         return 1;
     }
     if (!std::isnan(opts.limiter_ms) && std::isnan(opts.loudness_lufs)) {

@@ -18,6 +18,7 @@
 
 #include "../../include/stn_arch.h"
 #include "host/join_plan.hpp"
+#include "host/pause_plan.hpp"
 #include "kernels.hpp"
 
 namespace stn {
@@ -372,6 +373,19 @@ class Engine {
     // faded), zero codewords behind it
     void op_silence_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, const float* gain,
                          int enc, void* y, int64_t* start, int64_t* end);
+    // ---- pause limit (engine_edges.cpp; include/stn.h "pause limit"): off is the default, and without silence
+    // trimming it has no effect (every fetch path is then exactly the one without it).  On with trimming on, the detection is followed by
+    // one launch (pause_rows_kernel) that cuts every pause inside a row's [start, end) longer than max_pause_ms down to it; the trimmed
+    // store and the join then run on the row's several segments.
+    void set_pause_limit(bool on, float max_pause_ms);
+    bool pause_limit_active() const { return pl_on_ && st_on_; }
+    void get_pause_limit(int* on, float* max_pause_ms) const;
+    // the finished batch as the current parameters cut it (limit and trimming on or off): len [B], n_cuts [B], cuts [B][cap_pairs][2]
+    // (lo, hi; the first min(n_cuts, cap_pairs) pairs of a row); host arrays or null
+    void batch_pauses(int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs);
+    // op_silence_trim with the pause limit: y rows hold the row's segments end to end from column 0
+    void op_pause_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
+                       const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs);
     // diagnostic: overwrite the finished batch's model-rate waveform ([B][L * chunk] host floats) and forget what was measured on it
     void dbg_batch_set_wav(const float* wav);
 
@@ -694,23 +708,38 @@ class Engine {
     DevBuf ed_buf_;                    // fetch-time scratch of the detection
     // per chunk the two frame shares, per frame the level, per row the edges, the span and the one-member programme of the per-row
     // trimmed fetch
-    struct EdScratch { float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; size_t bytes; };
-    static EdScratch ed_layout(char* base, int64_t rows, int64_t W, int hz);
-    EdScratch ed_scratch(int64_t rows, int64_t W, int hz);
+    // With the pause limit (S > 0; section 17) also S segments, one programme and 2 S words {cuts, len, lo, hi, ...} per row, behind the
+    // rest: S = 0 carves exactly what trimming alone needs
+    struct EdScratch {
+        float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; size_t bytes;
+        JoinSegT* pseg = nullptr; JoinProg* pprog = nullptr; int64_t* pcut = nullptr; int S = 0;
+    };
+    static EdScratch ed_layout(char* base, int64_t rows, int64_t W, int hz, int S);
+    EdScratch ed_scratch(int64_t rows, int64_t W, int hz, int S);
+    bool pl_on_ = false;
+    float pl_ms_ = 300.0f;
+    int pl_stride(bool pauses, int64_t W, int hz) const { return pauses ? pause_stride(W, hz, pause_samples(hz, pl_ms_)) : 0; }
     // what the scratch holds: the edges (and per-row programmes) of batch `seq` at rate hz under (db, keep, fade); host: read back
     struct EdKey {
         uint64_t seq = 0; int hz = 0; float db = 0, keep = 0, fade = 0; int64_t Wo = 0; const void* buf = nullptr;
-        bool operator==(const EdKey& o) const { return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf; }
+        float mp = 0;  // max_pause_ms of the cuts held beside the edges; 0: none
+        bool operator==(const EdKey& o) const {
+            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp;
+        }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
     std::vector<int64_t> ed_host_, ed_n_;   // [B][2] edges read back; [B] spans
+    std::vector<int64_t> pz_host_; int pz_S_ = 0;  // [B][2 S] the rows' cut lists read back with the edges (key.mp != 0)
     DevBuf st_win_; int st_win_hz_ = 0; float st_win_ms_ = -1.0f;  // the fade window on the device, per (rate, fade_ms)
     const float* st_window(int hz);
     // the two detection launches on rows x W fp32 (x) at hz with the spans in sc.n: the edges and per-row programmes into sc
-    void ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc);
-    // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already
-    EdScratch ed_batch(const float* x, int64_t Wo);
-    const std::vector<int64_t>& ed_batch_host();  // its edges on the host (one device->host read of 2 B integers per batch and setting)
+    // (sc.S > 0: and the pause limit's launch behind them, Mp samples: the rows' segment tables and cut lists into sc)
+    void ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp = 0);
+    // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already; pauses: with the
+    // cuts under pl_ms_ (the fetch paths pass pause_limit_active())
+    EdScratch ed_batch(const float* x, int64_t Wo, bool pauses);
+    // its edges on the host (one device->host read of 2 B integers per batch and setting), and with pauses its cut lists in pz_host_
+    const std::vector<int64_t>& ed_batch_host(bool pauses);
     bool lm_on_ = false;
     float lm_ms_ = 5.0f;
     float lo_cap() const { return limiter_active() ? INFINITY : lo_ceiling_; }  // the gate's ceiling: the limiter enforces it instead
@@ -759,7 +788,7 @@ class Engine {
     // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
     struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };  // tseg: trimmed sources (seg unused)
     JoinTables join_tables(const JoinPlan& p);
-    static std::vector<int64_t> join_table_words(const JoinPlan& p);  // members of 3 words (JoinSeg) or, trimmed sources, 5 (JoinSegT), then the programmes
+    static std::vector<int64_t> join_table_words(const JoinPlan& p);  // members of 3 words (JoinSeg) or, trimmed sources, 5 (JoinSegT) per piece, then the programmes
     // the pointers into those words on the device; for trimmed sources also the fade window of the output rate, uploaded here if need be
     // (st_window: why this is no static function; op_join's plans have no trimmed sources and never get there)
     JoinTables join_tables_at(const int64_t* d, const JoinPlan& p);

@@ -474,12 +474,12 @@ void Engine::enqueue_output(const OutRows& o) {
         // store with one member per programme: row b's segment from column 0, zero codewords behind it
         const float* src = out_source(Wo);
         if (src == o.dst) throw std::logic_error("trimmed fetch: source and destination rows are the same");
-        const EdScratch sc = ed_batch(src, Wo);
+        const EdScratch sc = ed_batch(src, Wo, pause_limit_active());  // (section 17: with the pause limit, the rows' several segments)
         const LoRes m = loudness_on() ? lo_batch(src, Wo, true) : LoRes{};
         const float* fade = st_window(output_rate());
         const GainedRows r = gain_step(src, b.B, Wo, resample_on() ? Wo : W, m);  // (the untrimmed rows limited, then cut)
         StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-        launch_join_trim_rows(s_, r.src, r.stride, sc.seg, sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride);
+        launch_join_trim_rows(s_, r.src, r.stride, sc.S > 0 ? sc.pseg : sc.seg, sc.S > 0 ? sc.pprog : sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride);
     } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
@@ -622,12 +622,14 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
     if (silence_trim_on() && j && (j->mode == STN_JOIN_WHOLE || j->mode == STN_JOIN_TRIM)) {
         // section 14: a member's segment is [start_b, end_b) under either mode, its duration (float)len_b / (float)hz; the edges come
         // from the device (one read of 2 B integers per finished batch and setting)
-        const std::vector<int64_t>& e = ed_batch_host();
+        // (section 17: with the pause limit its length is len_b, what the cuts leave, and the rows' cut lists come with the edges)
+        const bool pauses = pause_limit_active();
+        const std::vector<int64_t>& e = ed_batch_host(pauses);
         const int hz = output_rate();
         const int64_t fd = silence_samples(hz, st_fade_);
         std::vector<float> dur((size_t)b.B);
         for (int i = 0; i < b.B; ++i) {
-            len[(size_t)i] = e[(size_t)i * 2 + 1] - e[(size_t)i * 2];
+            len[(size_t)i] = pauses ? pz_host_[(size_t)i * 2 * pz_S_ + 1] : e[(size_t)i * 2 + 1] - e[(size_t)i * 2];
             dur[(size_t)i] = (float)len[(size_t)i] / (float)hz;
         }
         stn_join jj = *j;
@@ -641,6 +643,17 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
             p.seg_fin[(size_t)i] = st > 0 ? (int32_t)fl : 0;
             p.seg_fout[(size_t)i] = en < ed_n_[(size_t)i] ? (int32_t)fl : 0;
         }
+        if (pauses) {  // member i's pieces: its row's segments in order, from the member's place in the programme
+            p.piece_first.assign(1, 0);
+            for (int i = 0; i < b.B; ++i) {
+                const int64_t* wr = &pz_host_[(size_t)i * 2 * pz_S_];
+                for (const PausePiece& q : pause_pieces(e[(size_t)i * 2], e[(size_t)i * 2 + 1], ed_n_[(size_t)i], wr + 2, (int)wr[0], fd)) {
+                    p.piece_dst.push_back(p.seg_dst[(size_t)i] + q.dst); p.piece_len.push_back(q.len); p.piece_src.push_back(q.src);
+                    p.piece_fin.push_back(q.fin); p.piece_fout.push_back(q.fout);
+                }
+                p.piece_first.push_back((int32_t)p.piece_dst.size());
+            }
+        }
     } else {
         const std::string why = join_plan(j, b.B, Wo, output_rate(), len.data(), reported_dur_.data(), p);
         if (!why.empty()) throw std::invalid_argument(why);
@@ -653,11 +666,16 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
 // from trimmed sources (p.seg_src set), {dst, len, source row, src, fin | fout << 32}, the words of JoinSegT
 std::vector<int64_t> Engine::join_table_words(const JoinPlan& p) {
     static_assert(sizeof(JoinSeg) == 24 && sizeof(JoinSegT) == 40 && sizeof(JoinProg) == 16, "the join tables are uploaded as int64 words");
-    const bool trim = !p.seg_src.empty();
-    const size_t mw = trim ? 5 : 3;
-    std::vector<int64_t> w((size_t)p.B * mw + (size_t)p.G * 2);
+    const bool trim = !p.seg_src.empty(), pieces = !p.piece_first.empty();
+    const size_t mw = trim ? 5 : 3, nm = p.pieces();
+    std::vector<int64_t> w(nm * mw + (size_t)p.G * 2);
     for (int i = 0; i < p.B; ++i) {
-        if (trim) {
+        if (pieces) {  // (the pause limit: several words of the member's row)
+            for (int32_t q = p.piece_first[(size_t)i]; q < p.piece_first[(size_t)i + 1]; ++q) {
+                const JoinSegT sg{p.piece_dst[(size_t)q], p.piece_len[(size_t)q], i, p.piece_src[(size_t)q], p.piece_fin[(size_t)q], p.piece_fout[(size_t)q]};
+                std::memcpy(&w[(size_t)q * mw], &sg, sizeof(sg));
+            }
+        } else if (trim) {
             const JoinSegT sg{p.seg_dst[(size_t)i], p.seg_len[(size_t)i], i, p.seg_src[(size_t)i], p.seg_fin[(size_t)i], p.seg_fout[(size_t)i]};
             std::memcpy(&w[(size_t)i * mw], &sg, sizeof(sg));
         } else {
@@ -666,16 +684,17 @@ std::vector<int64_t> Engine::join_table_words(const JoinPlan& p) {
         }
     }
     for (int g = 0; g < p.G; ++g) {
-        const int32_t first = p.first[(size_t)g], count = (g + 1 < p.G ? p.first[(size_t)g + 1] : p.B) - first;
-        const JoinProg pg{p.prog_len[(size_t)g], first, count};
-        std::memcpy(&w[(size_t)p.B * mw + (size_t)g * 2], &pg, sizeof(pg));
+        int32_t first = p.first[(size_t)g], last = g + 1 < p.G ? p.first[(size_t)g + 1] : p.B;
+        if (pieces) { first = p.piece_first[(size_t)first]; last = p.piece_first[(size_t)last]; }
+        const JoinProg pg{p.prog_len[(size_t)g], first, last - first};
+        std::memcpy(&w[nm * mw + (size_t)g * 2], &pg, sizeof(pg));
     }
     return w;
 }
 
 Engine::JoinTables Engine::join_tables_at(const int64_t* d, const JoinPlan& p) {
     if (p.seg_src.empty()) return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
-    return {nullptr, reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
+    return {nullptr, reinterpret_cast<const JoinProg*>(d + p.pieces() * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
 }
 
 Engine::JoinTables Engine::join_tables(const JoinPlan& p) {

@@ -2,6 +2,7 @@
 // detection's scratch, and the edges cached per finished batch and (rate, parameters) that the output stage (engine_batch.cpp),
 // batch_silence_edges and the join plan share.  The kernels are kernels_edges.hip and join_trim_rows_kernel (kernels_output.hip);
 // DESIGN.md section 14 has the contract.
+// The pause limit lives here too: its setting, its launch behind the detection, and the cuts cached beside the edges.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -53,7 +54,7 @@ const float* Engine::st_window(int hz) {
     return d;
 }
 
-Engine::EdScratch Engine::ed_layout(char* base, int64_t rows, int64_t W, int hz) {
+Engine::EdScratch Engine::ed_layout(char* base, int64_t rows, int64_t W, int hz, int S) {
     const size_t nc = (size_t)rows * (size_t)ed_chunks(W), nf = (size_t)rows * (size_t)edges_frames(W, hz);
     Carve c{base};
     EdScratch sc{};
@@ -64,18 +65,24 @@ Engine::EdScratch Engine::ed_layout(char* base, int64_t rows, int64_t W, int hz)
     sc.n = c.take<int64_t>((size_t)rows);
     sc.seg = c.take<JoinSegT>((size_t)rows);
     sc.prog = c.take<JoinProg>((size_t)rows);
+    if (S > 0) {  // the pause limit's tables (section 17)
+        sc.pseg = c.take<JoinSegT>((size_t)rows * S);
+        sc.pprog = c.take<JoinProg>((size_t)rows);
+        sc.pcut = c.take<int64_t>((size_t)rows * 2 * S);
+        sc.S = S;
+    }
     sc.bytes = c.off;
     return sc;
 }
 
-Engine::EdScratch Engine::ed_scratch(int64_t rows, int64_t W, int hz) {
+Engine::EdScratch Engine::ed_scratch(int64_t rows, int64_t W, int hz, int S) {
     bool moved = false;
-    char* base = ed_buf_.reserve(*this, ed_layout(nullptr, rows, W, hz).bytes, &moved);
+    char* base = ed_buf_.reserve(*this, ed_layout(nullptr, rows, W, hz, S).bytes, &moved);
     if (moved) ed_valid_ = ed_host_valid_ = false;
-    return ed_layout(base, rows, W, hz);
+    return ed_layout(base, rows, W, hz, S);
 }
 
-void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc) {
+void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp) {
     const double samples = (double)rows * W, chunks = (double)rows * ed_chunks(W);
     {
         StageSpan span(*this, "out", "edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
@@ -83,42 +90,53 @@ void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float t
         span.next("edges_rows", chunks, chunks * 8 + (double)rows * edges_frames(W, hz) * 16);
         launch_edges_rows(s_, rows, W, sc.n, hz, (double)top_db, silence_samples(hz, keep_ms), silence_samples(hz, fade_ms), sc.pa, sc.pb, sc.lev,
                           sc.edges, sc.seg, sc.prog);
+        if (sc.S > 0) {
+            const double frames = (double)rows * edges_frames(W, hz);
+            span.next("pause_rows", frames, frames * 8 + (double)rows * sc.S * (sizeof(JoinSegT) + 16));
+            launch_pause_rows(s_, rows, W, sc.n, hz, (double)top_db, silence_samples(hz, fade_ms), Mp, sc.S, sc.lev, sc.edges, sc.pseg, sc.pprog, sc.pcut);
+        }
     }
     STN_HIP(hipGetLastError());
 }
 
-Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo) {
+Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo, bool pauses) {
     const Batch& b = bt_;
     const int hz = output_rate();
     refuse(rate_check("silence trim", hz));
-    const EdScratch sc = ed_scratch(b.B, Wo, hz);
-    const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_.get()};
+    const EdScratch sc = ed_scratch(b.B, Wo, hz, pl_stride(pauses, Wo, hz));
+    const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_.get(), pauses ? pl_ms_ : 0.0f};
     if (ed_valid_ && key == ed_key_) return sc;
     // row b's span: section 11's, its reported duration at the output rate
     ed_n_.resize((size_t)b.B);
     for (int i = 0; i < b.B; ++i) ed_n_[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
     STN_HIP(hipMemcpyAsync(sc.n, ed_n_.data(), ed_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ed_enqueue(x, b.B, Wo, hz, st_db_, st_keep_, st_fade_, sc);
+    ed_enqueue(x, b.B, Wo, hz, st_db_, st_keep_, st_fade_, sc, pauses ? pause_samples(hz, pl_ms_) : 0);
     ed_key_ = key;
     ed_valid_ = true;
     ed_host_valid_ = false;
     return sc;
 }
 
-const std::vector<int64_t>& Engine::ed_batch_host() {
+const std::vector<int64_t>& Engine::ed_batch_host(bool pauses) {
     const int64_t Wo = out_row_len();
-    const EdKey key{ed_seq_, output_rate(), st_db_, st_keep_, st_fade_, Wo, ed_buf_.get()};
+    const EdKey key{ed_seq_, output_rate(), st_db_, st_keep_, st_fade_, Wo, ed_buf_.get(), pauses ? pl_ms_ : 0.0f};
     if (ed_valid_ && ed_host_valid_ && key == ed_key_) return ed_host_;
-    const EdScratch sc = (ed_valid_ && key == ed_key_) ? ed_scratch(bt_.B, Wo, output_rate()) : ed_batch(out_source(Wo), Wo);
+    const EdScratch sc = (ed_valid_ && key == ed_key_) ? ed_scratch(bt_.B, Wo, output_rate(), pl_stride(pauses, Wo, output_rate()))
+                                                       : ed_batch(out_source(Wo), Wo, pauses);
     ed_host_.resize((size_t)bt_.B * 2);
     STN_HIP(hipMemcpyAsync(ed_host_.data(), sc.edges, ed_host_.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    if (sc.S > 0) {  // the rows' cut lists: one read per finished batch and setting
+        pz_host_.resize((size_t)bt_.B * 2 * sc.S);
+        pz_S_ = sc.S;
+        STN_HIP(hipMemcpyAsync(pz_host_.data(), sc.pcut, pz_host_.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    }
     sync();
     ed_host_valid_ = true;
     return ed_host_;
 }
 
 void Engine::batch_silence_edges(int64_t* start, int64_t* end) {
-    const std::vector<int64_t>& e = ed_batch_host();
+    const std::vector<int64_t>& e = ed_batch_host(pause_limit_active());
     for (int i = 0; i < bt_.B; ++i) {
         if (start) start[i] = e[(size_t)i * 2];
         if (end) end[i] = e[(size_t)i * 2 + 1];
@@ -138,7 +156,7 @@ void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int6
     if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
     const std::vector<int64_t> nn = spans("op_silence", rows, W, n);
     ar_.reset();
-    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz).bytes)), rows, W, hz);
+    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, 0).bytes)), rows, W, hz, 0);
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
@@ -166,6 +184,84 @@ void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int6
         if (start) start[r] = e[(size_t)r * 2];
         if (end) end[r] = e[(size_t)r * 2 + 1];
     }
+}
+
+// ---- pause limit
+
+void Engine::set_pause_limit(bool on, float max_pause_ms) {
+    refuse(pause_check(max_pause_ms));
+    pl_on_ = on;
+    pl_ms_ = max_pause_ms;
+}
+
+void Engine::get_pause_limit(int* on, float* max_pause_ms) const {
+    if (on) *on = pl_on_ ? 1 : 0;
+    if (max_pause_ms) *max_pause_ms = pl_ms_;
+}
+
+// row r's words {cuts, len, lo, hi, ...} of a cut list read back -> the caller's arrays
+static void pause_copy_out(const int64_t* w, int S, int rows, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    for (int r = 0; r < rows; ++r) {
+        const int64_t* wr = w + (size_t)r * 2 * S;
+        if (n_cuts) n_cuts[r] = (int32_t)wr[0];
+        if (len) len[r] = wr[1];
+        if (cuts)
+            for (int c = 0; c < (int)wr[0] && c < cap_pairs; ++c) {
+                cuts[((size_t)r * cap_pairs + c) * 2] = wr[2 + 2 * c];
+                cuts[((size_t)r * cap_pairs + c) * 2 + 1] = wr[3 + 2 * c];
+            }
+    }
+}
+
+void Engine::batch_pauses(int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument("batch_pauses: cuts needs cap_pairs >= 1");
+    ed_batch_host(true);
+    pause_copy_out(pz_host_.data(), pz_S_, bt_.B, len, n_cuts, cuts, cap_pairs);
+}
+
+void Engine::op_pause_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
+                           const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    STN_HIP(hipSetDevice(device_));
+    refuse(silence_check(top_db, keep_ms, fade_ms));
+    refuse(pause_check(max_pause_ms));
+    refuse(rate_check("pause limit", hz));
+    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument("op_pause_trim: cuts needs cap_pairs >= 1");
+    const int eb = enc_bytes(enc);
+    if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
+    const std::vector<int64_t> nn = spans("op_pause", rows, W, n);
+    const int64_t Mp = pause_samples(hz, max_pause_ms);
+    const int S = pause_stride(W, hz, Mp);
+    ar_.reset();
+    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, S).bytes)), rows, W, hz, S);
+    const size_t nx = (size_t)rows * W;
+    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
+    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc, Mp);
+    std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
+    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    const std::vector<float> w = silence_fade_window(hz, fade_ms);
+    if (y) {
+        float* dw = static_cast<float*>(ar_.alloc(std::max<size_t>(w.size(), 1) * 4));
+        if (!w.empty()) STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
+        float* dg = nullptr;
+        if (gain) {
+            dg = static_cast<float*>(ar_.alloc((size_t)rows * 4));
+            STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
+        }
+        const int64_t Ws = ((int64_t)W + 15) / 16 * 16;  // rows 16-byte aligned in every encoding: the store runs full width
+        void* dy = ar_.alloc((size_t)rows * Ws * eb);
+        launch_join_trim_rows(s_, dx, W, sc.pseg, sc.pprog, rows, W, dg, dw, enc, dy, Ws);
+        STN_HIP(hipGetLastError());
+        STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
+    }
+    sync();  // (w, nn, e and pz are read or written by the copies above until here)
+    for (int r = 0; r < rows; ++r) {
+        if (start) start[r] = e[(size_t)r * 2];
+        if (end) end[r] = e[(size_t)r * 2 + 1];
+    }
+    pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
 }
 
 void Engine::dbg_batch_set_wav(const float* wav) {

@@ -233,6 +233,12 @@ int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms) {
 int stn_group_set_peak_mode(stn_group* g, int mode) {
     return for_all(g, "stn_set_peak_mode", [](stn_handle* h, const void*, uint64_t v) { return stn_set_peak_mode(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)mode);
 }
+int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms) {
+    if (!g) return STN_ERR_INVALID;
+    (void)max_pause_ms;
+    if (on) return fail(g, STN_ERR_INVALID, "stn_group_set_pause_limit: the pause limit shortens pauses inside trimmed rows, and a group does not trim (use one device)");
+    return STN_OK;
+}
 int stn_group_set_encoding(stn_group* g, int enc) {
     if (!g) return STN_ERR_INVALID;
     if (stn_encoding_bytes(enc) == 0) return fail(g, STN_ERR_INVALID, "stn_group_set_encoding: unknown encoding " + std::to_string(enc));

@@ -21,6 +21,12 @@ struct JoinPlan {
     // faded at its head and its tail; the engine's output stage fills them, join_plan leaves them empty
     std::vector<int64_t> seg_src;
     std::vector<int32_t> seg_fin, seg_fout;
+    // with the pause limit a member is several pieces of its row, laid end to end from seg_dst: member i's are
+    // [piece_first[i], piece_first[i + 1]) (B + 1 entries), piece_dst counted in the programme's row.  All empty: a member is one piece
+    // and seg_* describe it.  seg_len stays the member's delivered length.  Filled by the engine's output stage only.
+    std::vector<int32_t> piece_first, piece_fin, piece_fout;
+    std::vector<int64_t> piece_dst, piece_len, piece_src;
+    size_t pieces() const { return piece_first.empty() ? (size_t)B : piece_dst.size(); }
 };
 
 // Fills p from B members of whole lengths member_len (each in [0, W_out]) and durations member_dur (may be null with STN_JOIN_WHOLE:

@@ -17,7 +17,12 @@ void check(stn_handle* h, int rc) {
     if (rc != STN_OK) throw std::runtime_error(std::string("engine: ") + stn_last_error(h));
 }
 // with silence trimming on: the samples each row of the finished batch holds (the segments the fetch delivered)
-std::vector<int64_t> trimmed_lengths(stn_handle* h, int B) {
+std::vector<int64_t> trimmed_lengths(stn_handle* h, int B, bool pause_limit) {
+    if (pause_limit) {  // what the cuts leave of the segment
+        std::vector<int64_t> len((size_t)B);
+        check(h, stn_batch_pauses(h, len.data(), nullptr, nullptr, 0));
+        return len;
+    }
     std::vector<int64_t> start((size_t)B), end((size_t)B);
     check(h, stn_batch_silence_edges(h, start.data(), end.data()));
     for (int b = 0; b < B; ++b) end[(size_t)b] -= start[(size_t)b];
@@ -76,12 +81,12 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
     if (enc_ != STN_ENC_PCM16) {
         r.encoded.resize((size_t)B * W * stn_encoding_bytes(enc_));
         check(h_, stn_batch_fetch_encoded(h_, enc_, r.encoded.data(), r.encoded.size(), r.duration.data()));
-        if (trim_silence_) r.length = trimmed_lengths(h_, B);
+        if (trim_silence_) r.length = trimmed_lengths(h_, B, pause_limit_);
         return r;
     }
     r.wav.resize((size_t)B * W);
     check(h_, stn_batch_fetch(h_, r.wav.data(), r.wav.size(), r.duration.data()));
-    if (trim_silence_) r.length = trimmed_lengths(h_, B);
+    if (trim_silence_) r.length = trimmed_lengths(h_, B, pause_limit_);
     return r;
 }
 
@@ -89,6 +94,13 @@ void TextToSpeech::setSilenceTrim(bool on, float top_db, float keep_ms, float fa
     if (on && grp_) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
     check(h_, stn_set_silence_trim(h_, on ? 1 : 0, top_db, keep_ms, fade_ms));
     trim_silence_ = on;
+}
+
+void TextToSpeech::setPauseLimit(bool on, float max_pause_ms) {
+    if (on && grp_) throw std::runtime_error("the pause limit needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --max-pause out)");
+    if (on && !trim_silence_) throw std::runtime_error("the pause limit needs silence trimming (it shortens pauses inside trimmed utterances)");
+    check(h_, stn_set_pause_limit(h_, on ? 1 : 0, max_pause_ms));
+    pause_limit_ = on;
 }
 
 
@@ -218,6 +230,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
                                      "(use one GPU, or the default scope 'chunk')");
         if (opts.trim_chunks) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
         if (!std::isnan(opts.trim_silence_db)) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
+        if (!std::isnan(opts.max_pause_ms)) throw std::runtime_error("the pause limit needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --max-pause out)");
         std::vector<int> dev = opts.devices;
         if (dev.empty()) for (int i = 0; i < opts.gpus; ++i) dev.push_back(opts.device + i);
         if (stn_group_create((int)dev.size(), dev.data(), opts.dtype, &grp) != STN_OK) throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(nullptr));
@@ -285,6 +298,10 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         }
         // (refused here, while this function still owns the handle: once tts owns it, a throw would destroy it twice)
         if (!std::isnan(opts.trim_silence_db)) check(h, stn_set_silence_trim(h, 1, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms));
+        if (!std::isnan(opts.max_pause_ms)) {
+            if (std::isnan(opts.trim_silence_db)) throw std::runtime_error("the pause limit needs silence trimming (it shortens pauses inside trimmed utterances)");
+            check(h, stn_set_pause_limit(h, 1, opts.max_pause_ms));
+        }
         auto tts = grp ? std::make_unique<TextToSpeech>(grp, std::move(tp), cfgs, opts.noise_seed)
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);
@@ -292,6 +309,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         tts->setLoudnessScope(opts.loudness_scope_text);
         tts->setTrimChunks(opts.trim_chunks);
         if (!std::isnan(opts.trim_silence_db)) tts->setSilenceTrim(true, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms);  // (accepted above)
+        if (!std::isnan(opts.max_pause_ms)) tts->setPauseLimit(true, opts.max_pause_ms);
         if (synthetic) tts->markSynthetic();
         return tts;
     } catch (...) {

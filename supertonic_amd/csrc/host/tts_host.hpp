@@ -72,6 +72,8 @@ struct EngineOptions {
     float trim_silence_db = std::numeric_limits<float>::quiet_NaN();  // trim leading and trailing silence of every utterance by level on the
                                    // GPU (stn_set_silence_trim): frames more than this many dB below the loudest 10 ms frame; NaN: off.  One
                                    // device only.  CLI --trim-silence DB
+    float max_pause_ms = std::numeric_limits<float>::quiet_NaN();  // with trim_silence_db: pauses inside an utterance longer than this many
+                                   // milliseconds shortened to it on the GPU (stn_set_pause_limit); NaN: off.  CLI --max-pause MS
     float trim_keep_ms = 20.0f;    // milliseconds kept in front of and behind the speech.  CLI --trim-keep MS
     float trim_fade_ms = 5.0f;     // raised-cosine fade over each cut edge.  CLI --trim-fade MS
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
@@ -110,6 +112,9 @@ class TextToSpeech {
     // every utterance without its leading and trailing silence (stn_set_silence_trim; stn.h "silence trimming"): batch() rows hold the
     // trimmed segment from column 0 (SynthesisResult::length), call() joins the segments.  Refused on a group.
     void setSilenceTrim(bool on, float top_db = 40.0f, float keep_ms = 20.0f, float fade_ms = 5.0f);
+    // with silence trimming on: every pause inside an utterance longer than max_pause_ms shortened to it (stn_set_pause_limit; stn.h
+    // "pause limit"); the lengths are then what the cuts leave.  One device only, and refused without trimming.
+    void setPauseLimit(bool on, float max_pause_ms = 300.0f);
     int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
@@ -120,7 +125,7 @@ class TextToSpeech {
     SynthesisResult infer(const std::vector<std::string>& text_list, const std::vector<std::string>& lang_list,
                           const Style& style, int total_step, float speed);
     void runBatch(const TokenBatch& tb, const std::vector<float>& mask, const Style& style, int total_step, float speed);
-    bool scope_text_ = false, trim_chunks_ = false, trim_silence_ = false;
+    bool scope_text_ = false, trim_chunks_ = false, trim_silence_ = false, pause_limit_ = false;
     stn_handle* h_;
     stn_group* grp_ = nullptr;
     UnicodeProcessor text_processor_;

@@ -458,6 +458,13 @@ inline int64_t edges_frames(int64_t W, int hz) { const int F = edges_frame(hz); 
 void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb);
 void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
                        const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog);
+// The pause limit, behind launch_edges_rows on the same stream: lev and edges as that launch left them -> row r's
+// segments seg[r * S .. r * S + count) (the row's [start, end) without the middle of every pause longer than Mp samples, at most S - 1
+// cuts, the first in time order), prog[r] = {len_r, r * S, count} and cuts[r][2 S] = {count - 1, len_r, lo_0, hi_0, lo_1, ...}.
+// 1 <= S <= 256.
+constexpr int PZ_MAX_CUTS = 255;
+void launch_pause_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t fd, int64_t Mp, int S, const double* lev,
+                       const int64_t* edges, JoinSegT* seg, JoinProg* prog, int64_t* cuts);
 
 // Output-rate resampling of the finished waveform (kernels_resample.hip; the filter design is engine_resample.cpp).  Rational polyphase:
 // out_hz / in_hz = P / Q reduced; output n of a row = sum_j taps[(n*Q) mod P][j] * x[floor(n*Q/P) - off + j] (x = 0 outside the row),

@@ -11,6 +11,9 @@
 // The hand-off is a launch boundary and every sum runs in an order fixed by the sample positions within the row: a row's edges depend
 // on its first n_b samples, the rate and the parameters only, not on W, the batch or the row's place in it.  Max, min and the
 // comparisons are order-independent.
+// With the pause limit a third launch follows the row pass:
+//   3. pause pass: one workgroup per row reads the levels and the edges and writes the row's several segments, the row without the
+//      middle of every pause inside it that is longer than the limit (pause_rows_kernel, below the row pass).
 #include "kernels.hpp"
 
 #include <math.h>
@@ -163,6 +166,116 @@ __global__ void __launch_bounds__(ED_ROW) edges_row_kernel(const int64_t* __rest
     }
 }
 
+
+// The pause limit: a row's frame levels -> its segment table with every pause inside [f0, f1] longer than Mp
+// shortened to Mp.  One workgroup per row.  The threshold and f0, f1 are recomputed from lev as edges_row_kernel computed them (max, min
+// and comparisons: no order to depend on).  The frames are then walked in tiles of ED_ROW, a thread per frame: an active frame b whose
+// previous active frame is pa closes the pause a = pa + 1 .. b - 1, and cuts it when (b - a) F > Mp.  "The previous active frame" is an
+// exclusive max-scan of (active ? k : -1), the cut's index and the samples dropped up to it are inclusive sum-scans of the cut flag and
+// of P - Mp; each is a shuffle scan inside the wave, the waves' totals combined through LDS in wave order, and a carry from tile to
+// tile.  Cut j < cap is staged in LDS as {lo, hi, dropped through j}; behind the walk thread j writes segment j from cuts j - 1 and j,
+// so that no table entry has two writers.  No atomics: a row's table depends on its own levels and the parameters only.
+struct PauseCarry { long long last; int cuts; long long drop; };
+
+template <typename T>
+__device__ __forceinline__ T pz_shfl_up(T v, int o) { return __shfl_up(v, o, 64); }
+
+__global__ void __launch_bounds__(ED_ROW) pause_rows_kernel(const int64_t* __restrict__ nrow, int64_t Kf, int F, double ratio, double floor_ms, int64_t fd,
+                                                            int64_t Mp, int S, const double* __restrict__ lev, const int64_t* __restrict__ edges,
+                                                            JoinSegT* __restrict__ seg, JoinProg* __restrict__ prog, int64_t* __restrict__ cuts) {
+    constexpr int NW = ED_ROW / 64;
+    __shared__ double redd[NW];
+    __shared__ long long w_last[NW], w_drop[NW];
+    __shared__ int w_cuts[NW];
+    __shared__ long long c_lo[PZ_MAX_CUTS], c_hi[PZ_MAX_CUTS], c_drop[PZ_MAX_CUTS];
+    const int64_t row = blockIdx.x;
+    const int64_t n = nrow[row];
+    const int64_t K = (n + F - 1) / F;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cap = S - 1 < PZ_MAX_CUTS ? S - 1 : PZ_MAX_CUTS;
+    const double* __restrict__ levr = lev + row * Kf;
+    double mx = 0.0;
+    for (int64_t k = tid; k < K; k += ED_ROW) mx = fmax(mx, levr[k]);
+    mx = ed_block_reduce(mx, redd, [](double p, double q) { return fmax(p, q); });
+    const bool speech = n > 0 && mx > floor_ms;
+    const double thr = mx * ratio;
+    const int64_t hr = Mp / 2, hl = Mp - hr;
+    PauseCarry carry{-1, 0, 0};  // (every thread keeps the same copy)
+    const int64_t tiles = speech ? (K + ED_ROW - 1) / ED_ROW : 0;
+    for (int64_t t = 0; t < tiles; ++t) {
+        const int64_t k = t * ED_ROW + tid;
+        const bool active = k < K && levr[k] >= thr;
+        // the last active frame at or before k within the wave, then before k
+        long long inc = active ? (long long)k : -1;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long u = pz_shfl_up(inc, o);
+            if (lane >= o && u > inc) inc = u;
+        }
+        long long prev = pz_shfl_up(inc, 1);
+        if (lane == 0) prev = -1;
+        if (lane == 63) w_last[wave] = inc;
+        __syncthreads();
+        long long before = carry.last, tile_last = carry.last;
+        for (int w = 0; w < NW; ++w) {
+            if (w < wave && w_last[w] > before) before = w_last[w];
+            if (w_last[w] > tile_last) tile_last = w_last[w];
+        }
+        if (before > prev) prev = before;
+        // frame k closes a pause when it is active, an active frame lies before it, and frames lie between them
+        const long long a = prev + 1;
+        const long long P = (active && prev >= 0) ? ((long long)k - a) * F : 0;
+        const bool cut = P > Mp;
+        int ci = cut ? 1 : 0;
+        long long di = cut ? P - Mp : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int uc = pz_shfl_up(ci, o);
+            const long long ud = pz_shfl_up(di, o);
+            if (lane >= o) { ci += uc; di += ud; }
+        }
+        if (lane == 63) { w_cuts[wave] = ci; w_drop[wave] = di; }
+        __syncthreads();
+        int cb = carry.cuts, ct = carry.cuts;
+        long long db = carry.drop, dt = carry.drop;
+        for (int w = 0; w < NW; ++w) {
+            if (w < wave) { cb += w_cuts[w]; db += w_drop[w]; }
+            ct += w_cuts[w]; dt += w_drop[w];
+        }
+        // cuts behind the cap stay whole: a dropped count that includes one is never used (the walk ends at the cap below)
+        if (cut) {
+            const int j = cb + ci - 1;
+            if (j < cap) { c_lo[j] = a * F + hl; c_hi[j] = (long long)k * F - hr; c_drop[j] = db + di; }
+        }
+        carry.last = tile_last; carry.cuts = ct; carry.drop = dt;
+        __syncthreads();  // (w_* are rewritten by the next tile)
+        if (carry.cuts >= cap) break;  // (uniform: every thread holds the same carry)
+    }
+    __syncthreads();
+    const int m = carry.cuts < cap ? carry.cuts : cap;
+    const int64_t start = edges[2 * row], end = edges[2 * row + 1];
+    if (tid <= m) {
+        const int64_t src = tid == 0 ? start : (int64_t)c_hi[tid - 1];
+        const int64_t stop = tid == m ? end : (int64_t)c_lo[tid];
+        const int64_t gone = tid == 0 ? 0 : (int64_t)c_drop[tid - 1];
+        const int64_t len = stop - src, fl = fd < len ? fd : len;
+        JoinSegT sg;
+        sg.dst = src - start - gone; sg.len = len; sg.row = row; sg.src = src;
+        sg.fin = (tid > 0 || start > 0) ? (int32_t)fl : 0;
+        sg.fout = (tid < m || end < n) ? (int32_t)fl : 0;
+        seg[row * S + tid] = sg;
+    }
+    int64_t* cr = cuts + row * (2 * (int64_t)S);
+    if (tid < m) { cr[2 + 2 * tid] = c_lo[tid]; cr[3 + 2 * tid] = c_hi[tid]; }
+    if (tid == 0) {
+        const int64_t len = end - start - (m > 0 ? (int64_t)c_drop[m - 1] : 0);
+        JoinProg pg;
+        pg.len = len; pg.first = (int32_t)(row * S); pg.count = m + 1;
+        prog[row] = pg;
+        cr[0] = m; cr[1] = len;
+    }
+}
+
 }  // namespace
 
 static int edges_check(int64_t rows, int64_t W, int hz) {
@@ -187,6 +300,16 @@ void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n,
     if (fd < 0 || fd > 0x7fffffff || keep < 0) throw std::invalid_argument("silence edges: bad keep or fade length");
     STN_KLAUNCH(edges_row_kernel, dim3((unsigned)rows), dim3(ED_ROW), 0, s, n, ed_chunks(W), edges_frames(W, hz), F, std::pow(10.0, -top_db / 10.0), 1e-7,
                 keep, fd, pa, pb, lev, edges, seg, prog);
+}
+
+void launch_pause_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t fd, int64_t Mp, int S, const double* lev,
+                       const int64_t* edges, JoinSegT* seg, JoinProg* prog, int64_t* cuts) {
+    if (rows <= 0 || W <= 0) return;
+    const int F = edges_check(rows, W, hz);
+    if (fd < 0 || fd > 0x7fffffff || Mp < 1) throw std::invalid_argument("pause limit: bad fade or pause length");
+    if (S < 1 || S > PZ_MAX_CUTS + 1) throw std::invalid_argument("pause limit: table stride outside [1, 256]");
+    STN_KLAUNCH(pause_rows_kernel, dim3((unsigned)rows), dim3(ED_ROW), 0, s, n, edges_frames(W, hz), F, std::pow(10.0, -top_db / 10.0), 1e-7, fd, Mp, S, lev,
+                edges, seg, prog, cuts);
 }
 
 }  // namespace stn

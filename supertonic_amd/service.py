@@ -54,7 +54,8 @@ class DynamicBatcher:
         self._t.start()
 
     def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
-               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None):
+               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None,
+               max_pause_ms=None):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
         the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
@@ -67,7 +68,10 @@ class DynamicBatcher:
         synthesizer's own setting): the full loudness gain, the ceiling held by a look-ahead peak limiter of that many milliseconds;
         validated here, part of the key's loudness entry, and without effect (and out of the key) when loudness is None.  peak_mode
         ("sample" or "true"; None: the synthesizer's own setting): peak_ceiling as a sample-peak or a true-peak ceiling; validated here
-        and part of the key's loudness entry in the same way."""
+        and part of the key's loudness entry in the same way.  max_pause_ms (with trim_silence; None: the synthesizer's own setting):
+        every pause inside an utterance longer than that is shortened to it; validated here, part of the key's trimming entry, and
+        without effect (and out of the key) when trim_silence is None."""
+        mp = None if max_pause_ms is None else binding.pause_limit_args(float(max_pause_ms))[1]
         lim = None if limiter_ms is None else binding.limiter_args(float(limiter_ms))[1]
         if peak_mode is not None:
             binding.peak_mode_id(peak_mode)
@@ -78,7 +82,7 @@ class DynamicBatcher:
         if loudness_scope != "chunk" or trim_chunks:  # (requests that use neither batch exactly as before)
             key += (str(loudness_scope), bool(trim_chunks))
         if ts is not None:  # (likewise: always the key's last element, a pair)
-            key += (("trim_silence", ts),)
+            key += (("trim_silence", ts) if mp is None else ("trim_silence", ts, mp),)
         job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
         with self._cv:
             if self._stop:
@@ -134,13 +138,15 @@ class DynamicBatcher:
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
                 step, speed, rate, lo, enc = jobs[0].key[:5]
                 tail = jobs[0].key[5:]
-                ts = None
+                ts = mp = None
                 if tail and isinstance(tail[-1], tuple):
-                    ts, tail = tail[-1][1], tail[:-1]
+                    ts, mp, tail = tail[-1][1], (tail[-1][2] if len(tail[-1]) > 2 else None), tail[:-1]
                 scope, trim = tail or ("chunk", False)
                 extra = {} if rate is None else {"output_rate": rate}
                 if ts is not None:
                     extra["trim_silence"] = ts
+                if mp is not None:
+                    extra["max_pause"] = mp
                 if lo is not None:
                     extra["loudness"] = (lo.lufs, lo.ceiling)
                     if lo.limiter_ms is not None:
@@ -245,6 +251,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                                  "more than this many dB below the loudest 10 ms frame; null: off.")
         trim_keep_ms: float = Field(20.0, ge=0.0, le=1000.0, description="Milliseconds kept in front of and behind the speech when trimming.")
         trim_fade_ms: float = Field(5.0, ge=0.0, le=50.0, description="Raised-cosine fade over each cut edge, in milliseconds.")
+        max_pause_ms: Optional[float] = Field(None, ge=20.0, le=5000.0, description="With trim_silence: every pause inside an utterance longer than "
+                                                                                    "this many milliseconds is shortened to it (on the GPU); null: off.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -288,10 +296,14 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             raise HTTPException(status_code=400, detail=f"loudness_scope {req.loudness_scope!r} is not supported; supported: chunk, text")
         enc = None if req.encoding == "pcm16" else req.encoding  # pcm16: the float waves, written as writeWavFile writes them
         ts = None if req.trim_silence is None else (req.trim_silence, req.trim_keep_ms, req.trim_fade_ms)
+        if req.max_pause_ms is not None and ts is None:
+            raise HTTPException(status_code=400, detail="max_pause_ms needs trim_silence: pauses are shortened inside trimmed utterances")
         if enc is not None:
             extra["encoding"] = enc
         if req.batch:
             if ts is not None:  # every wave is its trimmed segment, cut at the length the GPU found
+                if req.max_pause_ms is not None:
+                    extra["max_pause"] = req.max_pause_ms
                 wav, dur, seg = tts.batch(texts, langs, style, req.total_step, req.speed, trim_silence=ts, lengths=True, **extra)
                 chunks = [wav[i, : int(seg[i])] for i in range(wav.shape[0])]
             else:
@@ -301,7 +313,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
-                                         trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode)
+                                         trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
+                                         max_pause_ms=req.max_pause_ms)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:

@@ -54,7 +54,7 @@ class TextToSpeech:
     returning (wav [B, W] float32, duration [B] float32).  One instance = one engine handle = one GPU; calls are
     serialised by a lock (the handle is single-threaded by contract)."""
 
-    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None, peak_mode=None):
+    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
         self.engine = engine
         self.text_processor = text_processor
         self.cfgs = cfgs
@@ -73,6 +73,11 @@ class TextToSpeech:
         self.trim_silence = _trim_setting(trim_silence)
         if self.trim_silence is not None:
             engine.set_silence_trim(self.trim_silence)
+        # pauses inside an utterance longer than this many milliseconds shortened to it (Engine.set_pause_limit): None = off; it acts only
+        # while silence trimming is on
+        self.max_pause = _pause_setting(max_pause)
+        if self.max_pause is not None:
+            engine.set_pause_limit(self.max_pause)
         # look-ahead peak limiter behind the loudness gain (Engine.set_limiter): None = off, True = 5 ms, or the look-ahead in ms; it
         # acts only while loudness normalization is on
         self.limiter = _limiter_setting(limiter)
@@ -98,13 +103,14 @@ class TextToSpeech:
         return self.noise_seed + self._calls - 1
 
     def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None,
-               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None, peak_mode=None):
+               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None, peak_mode=None, max_pause=None):
         """lengths: returns (wav, duration, len) with len [B] the samples each row holds from column 0: its trimmed segment with
-        trimming on (Engine.batch_silence_edges, never a duration product), else None."""
+        trimming on (Engine.batch_silence_edges, never a duration product; with the pause limit Engine.batch_pauses' len_b), else None."""
         if len(text_list) != style.ttl.shape[0]:
             raise ValueError("Number of texts must match number of style vectors")
         trim = self.trim_silence if trim_silence is None else _trim_setting(trim_silence)  # (validated before anything is set)
         lim = None if limiter is None else _limiter_setting(limiter)
+        pause = self.max_pause if max_pause is None else _pause_setting(max_pause)
         binding.peak_mode_id(peak_mode)
         ids, mask = self.text_processor(text_list, lang_list)
         with self._lock:
@@ -119,6 +125,8 @@ class TextToSpeech:
                 self.engine.set_loudness(*(_loudness_setting(loudness) or (None,)))
             if trim_silence is not None:  # this call's trimming (fetch-time as well)
                 self.engine.set_silence_trim(trim)
+            if max_pause is not None:  # this call's pause limit (fetch-time as well)
+                self.engine.set_pause_limit(pause)
             if limiter is not None:  # this call's limiter (fetch-time as well)
                 self.engine.set_limiter(lim)
             if peak_mode is not None:  # this call's peak mode (fetch-time as well)
@@ -138,6 +146,8 @@ class TextToSpeech:
                     return out
                 if trim is None:
                     return out[0], out[1], None
+                if pause is not None:
+                    return out[0], out[1], self.engine.batch_pauses()[0]
                 start, end = self.engine.batch_silence_edges()
                 return out[0], out[1], end - start
             finally:
@@ -149,6 +159,8 @@ class TextToSpeech:
                     self.engine.set_loudness(*(self.loudness or (None,)))
                 if trim_silence is not None:
                     self.engine.set_silence_trim(self.trim_silence)
+                if max_pause is not None:
+                    self.engine.set_pause_limit(self.max_pause)
                 if limiter is not None:
                     self.engine.set_limiter(self.limiter)
                 if peak_mode is not None:
@@ -168,7 +180,7 @@ class TextToSpeech:
         return -(-int(n) * P // Q)
 
     def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None,
-                   trim_silence=None, limiter=None, peak_mode=None):
+                   trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
         and the durations.  The building block of the long-form path and of the service's dynamic batching.
@@ -177,9 +189,12 @@ class TextToSpeech:
         binding.ENC_*; None: float32): the waves in that sample encoding, encoded on the GPU (binding.encoded_empty's dtypes).
         trim_silence (this call's: False = off, top_db, or (top_db, keep_ms, fade_ms)): every wave is its trimmed segment, cut at the
         length the GPU found.  limiter (this call's: False = off, True = 5 ms, or the look-ahead in ms): with normalization, every
-        utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling."""
+        utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling.  max_pause (this call's: False = off, or
+        milliseconds in [20, 5000]; with trimming only): every pause inside an utterance longer than that is shortened to it, and the
+        wave is cut at what remains."""
         wav, dur, seg = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
-                                    loudness=loudness, encoding=encoding, trim_silence=trim_silence, lengths=True, limiter=limiter, peak_mode=peak_mode)
+                                    loudness=loudness, encoding=encoding, trim_silence=trim_silence, lengths=True, limiter=limiter, peak_mode=peak_mode,
+                                    max_pause=max_pause)
         if seg is not None:
             return [wav[i, : int(n)] for i, n in enumerate(seg)], dur
         cs = self.base_chunk_size * self.chunk_compress_factor
@@ -187,7 +202,8 @@ class TextToSpeech:
         return [wav[i, : min(self.out_samples(n * cs, output_rate), wav.shape[1])] for i, n in enumerate(lens)], dur
 
     def joined_batch(self, text_list, lang_list, style, total_step, speed=1.05, rows=None, silence_duration=0.3, output_rate=None,
-                     loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None):
+                     loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None,
+                     max_pause=None):
         """solo_batch whose rows are joined on the GPU into len(rows) waves: rows[g] consecutive utterances each (None: all of them
         in one), silence_duration (one value, or one per wave) seconds of silence between two of them — the encoding's zero codeword.
         Returns (list of joined waves, their durations: the reference's fp32 sum d = dur_0; d += dur_i + silence).  loudness_scope,
@@ -195,7 +211,8 @@ class TextToSpeech:
         "text", every joined wave measured as one BS.1770 programme, silences included, and scaled by one gain.  trim_chunks: every
         utterance cut at its duration before the join (the reference's Rust host) instead of its whole wave (C++ / Python hosts).
         trim_silence (as solo_batch): every utterance is its trimmed segment, so the pause between two of them is the silence asked for
-        plus twice the kept margin; the durations are then those of the segments."""
+        plus twice the kept margin; the durations are then those of the segments.  max_pause (as solo_batch): the pauses inside an
+        utterance are bounded as well."""
         if loudness_scope not in ("chunk", "text"):
             raise ValueError(f"loudness_scope {loudness_scope!r}: 'chunk' or 'text'")
         rows = [len(text_list)] if rows is None else [int(r) for r in rows]
@@ -204,17 +221,18 @@ class TextToSpeech:
         join = {"rows": rows, "gap_samples": [int(s * rate) for s in sil], "gap_seconds": sil.astype(np.float32),
                 "mode": "trim" if trim_chunks else "whole", "gain_scope": "programme" if loudness_scope == "text" else "row"}
         waves, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
-                                 loudness=loudness, encoding=encoding, join=join, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
+                                 loudness=loudness, encoding=encoding, join=join, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
+                                 max_pause=max_pause)
         return waves, dur
 
     def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None, loudness_scope="chunk",
-                 trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None):
+                 trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
         """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence on the GPU
         (one joined fetch: py/helper.py:235-243's untrimmed chunk waves with zeros between).  With loudness normalization on,
         loudness_scope="chunk" normalizes each chunk as its own row (its own gain); "text" normalizes the joined text as one
         BS.1770 programme with one gain, its internal dynamics kept.  trim_chunks: as joined_batch.  encoding: as solo_batch; the
         silence is then the encoding's zero codeword.  trim_silence: as joined_batch; the returned wave then ends with the speech.
-        limiter: as solo_batch; with loudness_scope="text" the joined text is limited as one programme."""
+        limiter: as solo_batch; with loudness_scope="text" the joined text is limited as one programme.  max_pause: as joined_batch."""
         if style.ttl.shape[0] != 1:
             raise ValueError("Single speaker text to speech only supports single style")
         if loudness_scope not in ("chunk", "text"):
@@ -222,27 +240,35 @@ class TextToSpeech:
         chunks = host.chunk_text(text, 120 if lang == "ko" else 300)
         trimming = (self.trim_silence if trim_silence is None else _trim_setting(trim_silence)) is not None
         if len(chunks) == 1 and not trim_chunks and not trimming:  # (one chunk is its own programme: the row's gain is the text's)
-            return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
+            return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
+                               max_pause=max_pause)
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
         waves, dur = self.joined_batch(chunks, [lang] * n, rep, total_step, speed, silence_duration=silence_duration, encoding=encoding,
-                                       loudness_scope=loudness_scope, trim_chunks=trim_chunks, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode)
+                                       loudness_scope=loudness_scope, trim_chunks=trim_chunks, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
+                                       max_pause=max_pause)
         return waves[0][None, :], np.array([dur[0]], np.float32)
 
     def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None, trim_silence=None,
-              lengths=False, limiter=None, peak_mode=None):
+              lengths=False, limiter=None, peak_mode=None, max_pause=None):
         """One padded batch -> (wav [B, W] float32, duration [B]); with an encoding (a name or binding.ENC_*), the rows in that sample
         encoding instead, encoded on the GPU (binding.encoded_empty's dtypes).  trim_silence (as solo_batch): row b holds its trimmed
         segment from column 0 and the zero codeword behind it; lengths=True adds a third result, the segments' lengths [B] (None with
-        trimming off)."""
+        trimming off).  max_pause: as solo_batch; the row then holds its segments end to end."""
         return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness,
-                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter, peak_mode=peak_mode)
+                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter, peak_mode=peak_mode, max_pause=max_pause)
 
 
 def _limiter_setting(v):
     """A limiter argument -> the look-ahead in ms, or None for off: None / False = off, True = 5 ms, a number = the look-ahead.
     ValueError outside the ABI's range."""
     on, ms = binding.limiter_args(v)
+    return ms if on else None
+
+
+def _pause_setting(v):
+    """A max_pause argument -> milliseconds, or None for off: None / False = off.  ValueError outside the ABI's range."""
+    on, ms = binding.pause_limit_args(v)
     return ms if on else None
 
 
@@ -271,7 +297,7 @@ def load_cfgs(onnx_dir):
 
 
 def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None,
-                        loudness=None, trim_silence=None, limiter=None, peak_mode=None):
+                        loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
     """py/helper.py:316-337.  use_gpu=True is the only mode (the reference only had the CPU one).  An unusable asset directory is an
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
@@ -283,8 +309,10 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
     `limiter`: with `loudness`, every utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling (True = 5 ms of
     look-ahead, or milliseconds in [0.5, 10]; include/stn.h, stn_set_limiter); None keeps the capped gain.
     `peak_mode`: "true" makes the ceiling of `loudness` a true-peak ceiling (dBTP, 4x oversampled; include/stn.h, stn_set_peak_mode); None
-    or "sample" keeps the sample-peak ceiling."""
+    or "sample" keeps the sample-peak ceiling.  `max_pause`: with `trim_silence`, every pause inside an utterance longer than this many
+    milliseconds ([20, 5000]) is shortened to it on the GPU (include/stn.h, stn_set_pause_limit); None leaves the pauses as synthesized."""
     _trim_setting(trim_silence)  # (refused before the engine is created)
+    _pause_setting(max_pause)
     _limiter_setting(limiter)
     binding.peak_mode_id(peak_mode)
     if allow_synthetic is None:
@@ -308,6 +336,6 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
                 "ttl": {"chunk_compress_factor": a.chunk_compress_factor, "latent_dim": a.latent_dim}}
         tp = host.UnicodeProcessor(host.synthetic_indexer())
         synthetic = True
-    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter, peak_mode)
+    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter, peak_mode, max_pause)
     tts.synthetic = synthetic
     return tts
