@@ -563,6 +563,67 @@ int stn_op_limiter_ex(stn_handle* h, int hz, int rows, int W, const float* x, co
                       float ceiling_dbfs, float lookahead_ms, float* y, float* s_or_null, float* reduction_db, int64_t* limited,
                       int peak_mode, float* env_or_null, float* trim_or_null);
 
+/* ---- filter chain -----------------------------------------------------------------------------------
+ * A chain of 1 to STN_MAX_FILTERS second-order sections (biquads) applied to every row of every fetch, on the GPU, at the output rate:
+ * a high-pass / DC blocker in front of the level-based steps, the telephone band in front of G.711, tone shaping.  Off (n = 0) is the
+ * default: every fetch is then byte for byte the one without the feature, and no filter launch runs.
+ * Order of the output stage: native rows -> resample (if a rate is set) -> FILTER CHAIN -> silence edges / pause cuts -> loudness
+ * measurement -> gain / limiter / true peak -> encoding store / join.  Everything behind the chain sees the filtered signal: every
+ * fetch path (synchronous, both pipelined slots, device copies, joined, the group's gather) and every report (stn_batch_loudness,
+ * _silence_edges, _pauses, _limiter, _true_peak, stn_batch_join_loudness).  stn_batch_wav_device_ptr, stn_batch_fetch_latent, the
+ * batch's own waveform, the captured pipeline and the graph key are untouched: the filtered rows live in fetch scratch, and setting,
+ * changing or clearing the chain drops or re-captures no graph.
+ * Each row is filtered on its own, causally, from zero state at its sample 0, over the row's whole width W_out (padding included; the
+ * tail that decays into the padding is delivered like any other sample).  Identities:
+ *   the delivered fp32 row == stn_op_filter(the fp32 row delivered with the chain off), bit for bit;
+ *   a row's first n samples do not depend on W, the batch or the row's place in it;
+ *   a joined fetch == the host join of the per-row fetch, byte for byte, as without the chain.
+ * Section: transposed direct form II in fp32 with fp32 coefficients (b0 b1 b2 a1 a2, a0 = 1),
+ *   y = fma(b0, u, s1);  s1 = fma(-a1, y, fma(b1, u, s2));  s2 = fma(-a2, y, b2 * u),
+ * the signal between sections fp32.  The reference of every numeric claim is this recurrence in float64 on the same fp32-rounded
+ * coefficients.  Design: the RBJ Audio-EQ-Cookbook forms in double, w0 = 2 pi freq_hz / rate, alpha = sin(w0) / (2 q),
+ * A = 10^(gain_db / 40), normalized by a0 (stn_filter_coefs); HIGHPASS, LOWPASS and NOTCH ignore gain_db.
+ * Refused with STN_ERR_INVALID and a message that names the field, against the output rate in force: n outside [0, STN_MAX_FILTERS],
+ * an unknown type, q outside [0.3, 8], |gain_db| > 18, freq_hz above 0.45 rate, and freq_hz below rate / 2400 (high-pass and low-pass
+ * with q in [0.5, 1.5]) or rate / 800 (every other filter): below those corners the fp32 rounding of the coefficients moves the
+ * response by more than 0.1 dB.  The previous chain stays in force.  stn_set_output_rate to a rate at which the chain in force breaks
+ * a limit is refused the same way, and the rate stays as it was.  DESIGN.md section 18 has the decomposition and the measurements. */
+#define STN_FILT_HIGHPASS 0
+#define STN_FILT_LOWPASS 1
+#define STN_FILT_NOTCH 2
+#define STN_FILT_PEAK 3
+#define STN_FILT_LOWSHELF 4
+#define STN_FILT_HIGHSHELF 5
+#define STN_MAX_FILTERS 8
+typedef struct stn_filter { int type; float freq_hz; float q; float gain_db; } stn_filter;
+/* n = 0 (f may then be NULL): off */
+int stn_set_filters(stn_handle* h, int n, const stn_filter* f);
+/* *n and out[0 .. *n); out holds STN_MAX_FILTERS entries; either may be NULL */
+int stn_get_filters(const stn_handle* h, int* n, stn_filter* out);
+/* op-level: rows x W fp32 (host) at hz through the chain f[0 .. n), 1 <= n <= STN_MAX_FILTERS -> y [rows][W] (host).  1 <= rows <= 65535. */
+int stn_op_filter(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y);
+/* The same with its scratch laid open (the kernel tests).  The chain runs as P = (n + 1) / 2 section passes of two biquads (an odd n
+ * padded with the identity biquad), each three launches: chunks of 32 samples from zero state, the scan of the chunk states in double,
+ * the chunks again from their start states, writing y.  st_end [P][rows][Ks][4] (Ks = (W + 31) / 32): pass p's chunk end states as its
+ * first launch left them; st_start, the same shape: its chunks' start states (s1, s2 of the first biquad, then of the second) after the
+ * scan.  Either may be NULL.  The device's state buffer is filled with the quiet NaN 0x7FC00000 before every pass, and x and y lie with
+ * 64 poisoned floats in front of and behind them: *guard_ok = 1 when all of those came back untouched.  x_misalign 0 / 1: x and y lie
+ * 16-byte aligned / 4 bytes off, which forces the scalar staging path at W % 4 == 0.  form: the staging path that ran, "vec" or
+ * "scalar", NUL-terminated, truncated to form_cap; may be NULL. */
+int stn_op_filter_ex(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, int x_misalign, float* y,
+                     float* st_end, float* st_start, int* guard_ok, char* form, size_t form_cap);
+/* host only, no device needed: the section at rate_hz.  c: b0 b1 b2 a1 a2 of the double design; c32: the same rounded to fp32, what
+ * the GPU multiplies by.  Either may be NULL.  Refuses (STN_ERR_INVALID) what stn_set_filters refuses at that rate. */
+int stn_filter_coefs(const stn_filter* f, int rate_hz, double c[5], float c32[5]);
+/* host only: why stn_set_filters would refuse f[0 .. n) at an output rate of rate_hz ("" when it would not), as stn_resample_error;
+ * the string is the calling thread's until its next call */
+const char* stn_filter_error(int n, const stn_filter* f, int rate_hz);
+/* host only: the magnitude response in dB of the fp32-rounded chain (what is actually run) at freq_hz[0 .. n_freq) */
+int stn_filter_response(int n, const stn_filter* f, int rate_hz, int n_freq, const double* freq_hz, double* mag_db);
+/* the decomposition's constants: samples per chunk, samples a workgroup of the chunk launches owns, chunks per scan tile, biquads per
+ * section pass; each may be NULL */
+int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int* biquads_per_section);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

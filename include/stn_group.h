@@ -57,6 +57,8 @@ int stn_group_set_loudness(stn_group* g, int on, float target_lufs, float ceilin
 int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms);
 /* peak mode of every rank (stn_set_peak_mode; no effect without loudness): STN_PEAK_SAMPLE or STN_PEAK_TRUE */
 int stn_group_set_peak_mode(stn_group* g, int mode);
+/* filter chain of every rank (stn_set_filters): rows are filtered on their own, so the gathered rows are the single engine's */
+int stn_group_set_filters(stn_group* g, int n, const stn_filter* f);
 /* the pause limit (stn_set_pause_limit) works inside trimmed rows, and the group does not trim: on != 0 is refused with
  * STN_ERR_INVALID and a message; on = 0 is accepted and changes nothing */
 int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms);

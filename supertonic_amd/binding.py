@@ -90,6 +90,120 @@ def join_plan(rows, gap_samples, gap_seconds, member_len, member_dur, W_out, hz,
     return {"W_join": wj.value, "prog_len": prog_len, "prog_dur": prog_dur, "seg_len": seg_len, "seg_dst": seg_dst}
 
 
+FILTER_TYPES = {"highpass": 0, "lowpass": 1, "notch": 2, "peak": 3, "lowshelf": 4, "highshelf": 5}
+FILTER_TYPE_NAMES = {v: k for k, v in FILTER_TYPES.items()}
+MAX_FILTERS = 8
+FILTER_Q = 0.7071
+# presets expand on the host (the C ABI takes only the list): a rumble high-pass; the telephone band as a 4th-order Butterworth
+# high-pass at 300 Hz and low-pass at 3400 Hz, each two sections of Q 0.541 and 1.307
+FILTER_PRESETS = {
+    "rumble": (("highpass", 80.0, FILTER_Q, 0.0),),
+    "telephone": (("highpass", 300.0, 0.541, 0.0), ("highpass", 300.0, 1.307, 0.0), ("lowpass", 3400.0, 0.541, 0.0), ("lowpass", 3400.0, 1.307, 0.0)),
+}
+
+
+class StnFilter(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int), ("freq_hz", ctypes.c_float), ("q", ctypes.c_float), ("gain_db", ctypes.c_float)]
+
+
+def parse_filter_spec(spec):
+    """A command-line filter "TYPE:FREQ[:Q[:GAIN_DB]]" (Q 0.7071 and 0 dB when left out) -> (type, freq_hz, q, gain_db).  ValueError
+    naming what is wrong."""
+    parts = str(spec).split(":")
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"filter {spec!r}: expected TYPE:FREQ[:Q[:GAIN_DB]]")
+    if parts[0] not in FILTER_TYPES:
+        raise ValueError(f"filter {spec!r}: type must be one of {', '.join(FILTER_TYPES)}")
+    try:
+        nums = [float(v) for v in parts[1:]]
+    except ValueError:
+        raise ValueError(f"filter {spec!r}: FREQ, Q and GAIN_DB must be numbers") from None
+    return (parts[0], nums[0], nums[1] if len(nums) > 1 else FILTER_Q, nums[2] if len(nums) > 2 else 0.0)
+
+
+def filter_args(filters, preset=None):
+    """A filters argument -> tuple of (type name, freq_hz, q, gain_db): None = no chain; a list whose entries are
+    {"type", "freq", "q" (0.7071), "gain_db" (0)} dicts, (type, freq[, q[, gain_db]]) tuples or "TYPE:FREQ[:Q[:GAIN_DB]]" strings.
+    preset ("rumble" / "telephone") expands here, in front of the list.  ValueError naming the field for a malformed entry, an unknown
+    type or preset, or more than 8 sections; the numeric limits are the C ABI's (filter_error, Engine.set_filters)."""
+    out = []
+    if preset is not None:
+        if preset not in FILTER_PRESETS:
+            raise ValueError(f"filter_preset {preset!r}: must be one of {', '.join(FILTER_PRESETS)}")
+        out.extend(FILTER_PRESETS[preset])
+    if filters is not None:
+        if isinstance(filters, (str, bytes, dict)) or not hasattr(filters, "__iter__"):
+            raise ValueError(f"filters: a list of filters, not {filters!r}")
+        for i, f in enumerate(filters):
+            if isinstance(f, str):
+                out.append(parse_filter_spec(f))
+                continue
+            if isinstance(f, dict):
+                unknown = set(f) - {"type", "freq", "q", "gain_db"}
+                if unknown:
+                    raise ValueError(f"filters[{i}]: unknown field {sorted(unknown)[0]!r} (type, freq, q, gain_db)")
+                if "type" not in f or "freq" not in f:
+                    raise ValueError(f"filters[{i}]: {'type' if 'type' not in f else 'freq'} is required")
+                f = (f["type"], f["freq"], f.get("q", FILTER_Q), f.get("gain_db", 0.0))
+            if not isinstance(f, (tuple, list)) or not 2 <= len(f) <= 4:
+                raise ValueError(f"filters[{i}]: a dict, a TYPE:FREQ[:Q[:GAIN_DB]] string or (type, freq[, q[, gain_db]]), not {f!r}")
+            t = FILTER_TYPE_NAMES.get(f[0], f[0]) if isinstance(f[0], int) and not isinstance(f[0], bool) else f[0]
+            if t not in FILTER_TYPES:
+                raise ValueError(f"filters[{i}]: type {f[0]!r} must be one of {', '.join(FILTER_TYPES)}")
+            vals = list(f[1:]) + [FILTER_Q, 0.0][len(f) - 2:]
+            for name, v in zip(("freq", "q", "gain_db"), vals):
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                    raise ValueError(f"filters[{i}]: {name} must be a finite number, not {v!r}")
+            out.append((t, float(vals[0]), float(vals[1]), float(vals[2])))
+    if len(out) > MAX_FILTERS:
+        raise ValueError(f"filters: {len(out)} sections, at most {MAX_FILTERS}")
+    return tuple(out)
+
+
+def _filter_array(filters):
+    f = filter_args(filters)
+    arr = (StnFilter * max(len(f), 1))()
+    for i, (t, fr, q, g) in enumerate(f):
+        arr[i] = StnFilter(FILTER_TYPES[t], fr, q, g)
+    return len(f), arr
+
+
+def filter_error(filters, rate_hz):
+    """Why Engine.set_filters would refuse the chain at an output rate of rate_hz (host only): "" when it would not; the message names
+    the filter and the field."""
+    n, arr = _filter_array(filters)
+    return load().stn_filter_error(n, arr, int(rate_hz)).decode()
+
+
+def filter_coefs(f, rate_hz):
+    """One section at rate_hz (host only) -> (c float64 [5]: b0 b1 b2 a1 a2 of the double design, a0 = 1; c32 float32 [5]: what the GPU
+    multiplies by).  StnError for what set_filters refuses at that rate."""
+    n, arr = _filter_array([f])
+    c, c32 = np.zeros(5, np.float64), np.zeros(5, np.float32)
+    rc = load().stn_filter_coefs(arr, int(rate_hz), c, c32)
+    if rc < 0:
+        raise StnError(rc, filter_error([f], rate_hz) or "stn_filter_coefs failed")
+    return c, c32
+
+
+def filter_response(filters, rate_hz, freq_hz):
+    """Magnitude in dB of the fp32-rounded chain (what is actually run) at the frequencies freq_hz (host only)."""
+    n, arr = _filter_array(filters)
+    fr = np.ascontiguousarray(np.atleast_1d(freq_hz), np.float64)
+    out = np.zeros(fr.shape, np.float64)
+    rc = load().stn_filter_response(n, arr, int(rate_hz), fr.size, fr, out)
+    if rc < 0:
+        raise StnError(rc, filter_error(filters, rate_hz) or "stn_filter_response failed")
+    return out
+
+
+def filter_geometry():
+    """(chunk, wg_span, scan_tile_chunks, biquads_per_section) of the filter passes' decomposition."""
+    v = [ctypes.c_int() for _ in range(4)]
+    load().stn_dbg_filter_geometry(*(ctypes.byref(x) for x in v))
+    return tuple(x.value for x in v)
+
+
 class StnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"stn error {code}: {msg}")
@@ -333,6 +447,17 @@ def load():
     L.stn_batch_true_peak.argtypes = [vp, vp, vp, vp]
     L.stn_op_true_peak.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, ci, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_limiter_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, cf, cf, vp, vp, vp, vp, ci, vp, vp]
+    fp = ctypes.POINTER(StnFilter)
+    L.stn_set_filters.argtypes = [vp, ci, fp]
+    L.stn_get_filters.argtypes = [vp, ctypes.POINTER(ci), fp]
+    L.stn_group_set_filters.argtypes = [vp, ci, fp]
+    L.stn_op_filter.argtypes = [vp, ci, ci, ci, _f32p, ci, fp, _f32p]
+    L.stn_op_filter_ex.argtypes = [vp, ci, ci, ci, _f32p, ci, fp, ci, _f32p, vp, vp, ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_filter_error.argtypes = [ci, fp, ci]
+    L.stn_filter_error.restype = ctypes.c_char_p
+    L.stn_filter_coefs.argtypes = [fp, ci, _f64p, _f32p]
+    L.stn_filter_response.argtypes = [ci, fp, ci, ci, _f64p, _f64p]
+    L.stn_dbg_filter_geometry.argtypes = [ctypes.POINTER(ci)] * 4
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
@@ -446,6 +571,11 @@ class Group:
     def set_peak_mode(self, mode="sample"):
         """Peak mode of every rank (Engine.set_peak_mode): "sample" or "true"."""
         self._ck(self._lib.stn_group_set_peak_mode(self._g, peak_mode_id(mode)))
+
+    def set_filters(self, filters=None):
+        """Filter chain of every rank (Engine.set_filters): the gathered rows are then the single engine's filtered rows."""
+        n, arr = _filter_array(filters)
+        self._ck(self._lib.stn_group_set_filters(self._g, n, arr))
 
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
@@ -904,6 +1034,45 @@ class Engine:
         self._ck(self._lib.stn_op_resample(self._h, int(in_hz), int(out_hz), rows, W, x, None if pcm else out.ctypes.data,
                                            out.ctypes.data if pcm else None))
         return out
+
+    def set_filters(self, filters=None):
+        """Filter every row of every fetch through a chain of up to 8 biquads on the GPU, at the output rate, after the resampler and
+        before everything else (trimming, loudness, limiter, encoding, join): None or [] = off (the default).  Entries as filter_args
+        takes them, e.g. [("highpass", 80)] or [{"type": "peak", "freq": 3000, "q": 1, "gain_db": 4}].  StnError naming the field for a
+        value outside the limits at the output rate in force (include/stn.h, "filter chain")."""
+        n, arr = _filter_array(filters)
+        self._ck(self._lib.stn_set_filters(self._h, n, arr))
+
+    def get_filters(self):
+        """The chain in force: a tuple of (type name, freq_hz, q, gain_db), empty when off."""
+        n, arr = ctypes.c_int(), (StnFilter * MAX_FILTERS)()
+        self._ck(self._lib.stn_get_filters(self._h, ctypes.byref(n), arr))
+        return tuple((FILTER_TYPE_NAMES[arr[i].type], arr[i].freq_hz, arr[i].q, arr[i].gain_db) for i in range(n.value))
+
+    def op_filter(self, x, hz, filters):
+        """rows x W fp32 at hz through the chain on the GPU -> y [rows, W] float32, every row from zero state."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        n, arr = _filter_array(filters)
+        y = np.empty_like(x)
+        self._ck(self._lib.stn_op_filter(self._h, int(hz), x.shape[0], x.shape[1], x, n, arr, y))
+        return y
+
+    def op_filter_ex(self, x, hz, filters, x_misalign=0):
+        """op_filter with its scratch laid open -> dict: y [rows, W]; st_end, st_start [P, rows, Ks, 4] (per section pass of two biquads:
+        the chunks' end states from zero state, their start states after the scan; the state buffer is poisoned with the quiet NaN
+        0x7FC00000 before every pass); guard_ok (the poisoned floats around x and y came back whole); form ("vec" / "scalar").
+        x_misalign = 1 places x and y 4 bytes off 16-byte alignment."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        n, arr = _filter_array(filters)
+        P, Ks = (n + 1) // 2, (W + 31) // 32
+        o = dict(y=np.empty_like(x), st_end=np.empty((P, rows, Ks, 4), np.float32), st_start=np.empty((P, rows, Ks, 4), np.float32))
+        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_filter_ex(self._h, int(hz), rows, W, x, n, arr, int(x_misalign), o["y"], o["st_end"].ctypes.data,
+                                            o["st_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
+        o["guard_ok"] = bool(ok.value)
+        o["form"] = form.value.decode()
+        return o
 
     def set_loudness(self, target_lufs=None, ceiling_dbfs=-1.0):
         """Normalize every fetch to target_lufs (BS.1770-4 integrated loudness, [-60, 0]) with the gain capped so that the sample

@@ -2,6 +2,7 @@
 #include "../../include/stn.h"
 
 #include <algorithm>
+#include <complex>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -432,6 +433,70 @@ int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_
     } catch (const std::exception&) {
         return STN_ERR_INVALID;
     }
+}
+int stn_set_filters(stn_handle* h, int n, const stn_filter* f) { STN_TRY(h, { h->eng->set_filters(n, f); }) }
+int stn_get_filters(const stn_handle* h, int* n, stn_filter* out) {
+    if (!h) return STN_ERR_INVALID;
+    const std::vector<stn_filter>& f = h->eng->filters();
+    if (n) *n = (int)f.size();
+    if (out) std::copy(f.begin(), f.end(), out);
+    return STN_OK;
+}
+int stn_op_filter(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && f && y, "stn_op_filter: bad argument (1 <= rows <= 65535, W >= 1, x, f and y)");
+                 h->eng->op_filter(hz, rows, W, x, n, f, y, nullptr); })
+}
+int stn_op_filter_ex(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, int x_misalign, float* y, float* st_end,
+                     float* st_start, int* guard_ok, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && f && y, "stn_op_filter_ex: bad argument (1 <= rows <= 65535, W >= 1, x, f and y)");
+                 need(x_misalign == 0 || x_misalign == 1, "stn_op_filter_ex: x_misalign must be 0 or 1");
+                 stn::Engine::FlProbe p;
+                 p.x_misalign = x_misalign; p.st_end = st_end; p.st_start = st_start;
+                 h->eng->op_filter(hz, rows, W, x, n, f, y, &p);
+                 if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0;
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
+const char* stn_filter_error(int n, const stn_filter* f, int rate_hz) {
+    static thread_local std::string why;
+    why = rate_hz > 0 ? stn::filter_check(n, f, rate_hz) : "filters: rate_hz must be positive";
+    return why.c_str();
+}
+int stn_filter_coefs(const stn_filter* f, int rate_hz, double c[5], float c32[5]) {
+    if (!f || rate_hz <= 0 || !stn::filter_check(1, f, rate_hz).empty()) return STN_ERR_INVALID;
+    double d[5];
+    stn::filter_design(*f, rate_hz, d);
+    for (int i = 0; i < 5; ++i) {
+        if (c) c[i] = d[i];
+        if (c32) c32[i] = (float)d[i];
+    }
+    return STN_OK;
+}
+int stn_filter_response(int n, const stn_filter* f, int rate_hz, int n_freq, const double* freq_hz, double* mag_db) {
+    if (n < 1 || rate_hz <= 0 || n_freq < 0 || (n_freq > 0 && (!freq_hz || !mag_db)) || !stn::filter_check(n, f, rate_hz).empty()) return STN_ERR_INVALID;
+    std::vector<float> c32((size_t)n * 5);
+    for (int i = 0; i < n; ++i) {
+        double d[5];
+        stn::filter_design(f[i], rate_hz, d);
+        for (int j = 0; j < 5; ++j) c32[(size_t)i * 5 + j] = (float)d[j];
+    }
+    for (int k = 0; k < n_freq; ++k) {
+        const double w = 2.0 * M_PI * freq_hz[k] / rate_hz;
+        const std::complex<double> z1 = std::polar(1.0, -w), z2 = std::polar(1.0, -2.0 * w);
+        double db = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const float* c = &c32[(size_t)i * 5];
+            db += 20.0 * std::log10(std::abs(((double)c[0] + (double)c[1] * z1 + (double)c[2] * z2) / (1.0 + (double)c[3] * z1 + (double)c[4] * z2)));
+        }
+        mag_db[k] = db;
+    }
+    return STN_OK;
+}
+int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int* biquads_per_section) {
+    if (chunk) *chunk = stn::LO_CHUNK;
+    if (wg_span) *wg_span = stn::LO_WG * stn::LO_CHUNK;
+    if (scan_tile_chunks) *scan_tile_chunks = stn::LO_SCAN;
+    if (biquads_per_section) *biquads_per_section = 2;
+    return STN_OK;
 }
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }

@@ -10,7 +10,10 @@
 // every chunk normalized on its own, the default, or the joined text as one programme with one gain; text needs one GPU),
 // --trim-chunks (a long text's chunks cut at their durations before they are joined), --trim-silence DB (leading and trailing silence of
 // every utterance trimmed by level on the GPU: frames more than DB below the loudest 10 ms frame; the files then hold the trimmed
-// segments; one GPU only), --max-pause MS (with --trim-silence: pauses inside an utterance longer than MS shortened to MS), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5).
+// segments; one GPU only), --max-pause MS (with --trim-silence: pauses inside an utterance longer than MS shortened to MS), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5),
+// --filter TYPE:FREQ[:Q[:GAIN_DB]] (repeatable, up to 8: every utterance through that biquad on the GPU, after the resampler and before
+// everything else; TYPE one of highpass, lowpass, notch, peak, lowshelf, highshelf; Q 0.7071 when left out), --filter-preset
+// {rumble,telephone} (a high-pass at 80 Hz; the 300 to 3400 Hz telephone band, in front of any --filter).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -92,7 +95,23 @@ int main(int argc, char* argv[]) {
         else if (a == "--max-pause" && more) opts.max_pause_ms = std::strtof(argv[++i], nullptr);  // ms: longer pauses inside an utterance are shortened to this; absent: off
         else if (a == "--trim-keep" && more) opts.trim_keep_ms = std::strtof(argv[++i], nullptr);  // ms kept around the speech (default 20)
         else if (a == "--trim-fade" && more) opts.trim_fade_ms = std::strtof(argv[++i], nullptr);  // ms of fade over a cut edge (default 5)
+        else if (a == "--filter" && more) {  // one biquad of the chain every utterance goes through on the GPU; repeatable
+            stn_filter f;
+            const std::string why = parseFilterSpec(argv[++i], f);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+            opts.filters.push_back(f);
+        }
+        else if (a == "--filter-preset" && more) {  // a named chain, expanded here, in front of any --filter
+            std::vector<stn_filter> p;
+            const std::string why = filterPreset(argv[++i], p);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+            opts.filters.insert(opts.filters.begin(), p.begin(), p.end());
+        }
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
+    }
+    if (opts.filters.size() > (size_t)STN_MAX_FILTERS) {
+        std::cerr << "Error: --filter / --filter-preset: " << opts.filters.size() << " sections, at most " << STN_MAX_FILTERS << "\n";
+        return 1;
     }
     if (peak_mode_given && std::isnan(opts.loudness_lufs)) {
         std::cerr << "Error: --peak-mode needs --loudness (it is the ceiling of the loudness gain)\n";

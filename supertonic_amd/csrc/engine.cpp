@@ -181,6 +181,7 @@ Engine::~Engine() {
     if (pin_seed_) (void)hipHostFree(pin_seed_);
     if (seed_dev_) (void)hipFree(seed_dev_);
     rs_release();
+    fl_release();
     lo_release();  // (the fetch scratch, DevBuf members, goes with the members)
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);

@@ -84,6 +84,17 @@ std::string rate_check(const char* what, int hz);
 std::string loudness_check(const float* target_lufs, float ceiling_dbfs);
 inline void refuse(const std::string& why) { if (!why.empty()) throw std::invalid_argument(why); }
 std::vector<int64_t> spans(const char* who, int rows, int W, const int64_t* n);
+// The filter chain's host arithmetic (engine_filter.cpp).  filter_check: why f[0 .. n) is refused at rate_hz, naming the field, or "";
+// filter_design: one section's b0 b1 b2 a1 a2 in double (RBJ cookbook, a0 = 1); FilterTable: the chain at hz as section passes of two
+// biquads (an odd count padded with the identity), each a LoudTable of fp32 coefficients and scan powers (hop = 1, unused)
+std::string filter_check(int n, const stn_filter* f, int rate_hz);
+void filter_design(const stn_filter& f, int rate_hz, double c[5]);
+struct FilterTable {
+    int hz = 0;
+    std::vector<stn_filter> f;
+    std::vector<LoudTable> pass;
+};
+void filter_table(int hz, int n, const stn_filter* f, FilterTable& t);  // fills t (no device copies); throws what filter_check refuses
 
 class Engine;
 // One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
@@ -422,6 +433,22 @@ class Engine {
     const char* op_true_peak(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp, float* env,
                              float* pk);
 
+    // ---- filter chain (engine_filter.cpp; include/stn.h "filter chain"): empty is the default (every fetch path is
+    // then exactly the one without it).  Set, out_source() delivers the rows at the output rate filtered in the fetch scratch
+    // (kernels_filter.hip), and everything behind it (edges, pauses, loudness, limiter, true peak, stores, joins) runs on those.
+    void set_filters(int n, const stn_filter* f);
+    bool filter_on() const { return !fl_set_.empty(); }
+    const std::vector<stn_filter>& filters() const { return fl_set_; }
+    // the op-level probe: st_end / st_start [P][rows][Ks][4] (host, or null), the poisoned guards around x and y, the staging form
+    struct FlProbe {
+        int x_misalign = 0;
+        float *st_end = nullptr, *st_start = nullptr;
+        bool guard_ok = false;   // out
+        const char* form = "";   // out
+    };
+    // rows x W fp32 (host) at hz through f[0 .. n) -> y (host)
+    void op_filter(int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y, FlProbe* probe);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -702,6 +729,22 @@ class Engine {
     bool lo_true_peak() const { return true_peak_on() && !limiter_active(); }
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream
     LoRes lo_batch(const float* x, int64_t Wo, bool on);
+    // ---- filter chain (engine_filter.cpp)
+    std::vector<stn_filter> fl_set_;   // the chain in force
+    uint64_t fl_gen_ = 0;              // bumped by every set_filters: part of EdKey (edges found on other rows must not be reused)
+    FilterTable fl_, op_fl_;           // the section passes of the chain at the output rate, and of op_filter (device copies owned here)
+    DevBuf fl_buf_;                    // fetch-time scratch of the section passes
+    // per chunk the state (16 B) and pass 1's peak (unused), per row the length (every row's is W): what the measurement's launches take
+    struct FlScratch { float *st, *pk; int64_t* n; size_t bytes; };
+    static FlScratch fl_layout(char* base, int64_t rows, int64_t W);
+    int64_t fl_n_rows_ = 0, fl_n_W_ = 0; const int64_t* fl_n_ptr_ = nullptr;  // the lengths fl_buf_ holds (rows of W at fl_n_ptr_)
+    void fl_prepare(FilterTable& t, int hz, int n, const stn_filter* f);
+    void fl_release();
+    // the chain's section passes on rows x W fp32 (x; row stride W) into y (may be x; every pass after the first runs in place in y);
+    // probe (or null): the states of every pass read out, the state buffer poisoned before each
+    void fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const FlScratch& sc, float* y, FlProbe* probe);
+    void fl_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) through the chain in force into y (may be x)
+    bool out_in_scratch() const { return resample_on() || filter_on(); }  // out_source() returns fetch scratch (row stride Wo), not b.wav
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
@@ -723,8 +766,9 @@ class Engine {
     struct EdKey {
         uint64_t seq = 0; int hz = 0; float db = 0, keep = 0, fade = 0; int64_t Wo = 0; const void* buf = nullptr;
         float mp = 0;  // max_pause_ms of the cuts held beside the edges; 0: none
+        uint64_t fl = 0;  // fl_gen_ of the filter chain the rows went through
         bool operator==(const EdKey& o) const {
-            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp;
+            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl;
         }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
@@ -799,8 +843,9 @@ class Engine {
     DevBuf join_tab_;
     std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
-    bool out_native() const;             // neither resampled nor normalized: the delivered fp32 rows are b.wav itself
-    const float* out_source(int64_t Wo);  // the finished batch at the output rate: b.wav, or resampled into the fp32 scratch
+    bool out_native() const;             // neither resampled, filtered nor normalized: the delivered fp32 rows are b.wav itself
+    // the finished batch at the output rate: b.wav, or resampled and / or filtered (section 18) into the fp32 scratch, row stride Wo
+    const float* out_source(int64_t Wo);
     float* out_f32_buf(size_t n) { return reinterpret_cast<float*>(out_f32_.reserve(*this, n * sizeof(float))); }
     void* out_enc_buf(size_t bytes) { return out_enc_.reserve(*this, bytes); }
     DevBuf out_f32_, out_enc_;        // fetch scratch: fp32 rows at the output rate, rows in the fetch's encoding

@@ -434,13 +434,15 @@ int64_t Engine::out_row_len() {
     return out_len(native_row_len());
 }
 
-bool Engine::out_native() const { return !loudness_on() && !resample_on(); }
+bool Engine::out_native() const { return !loudness_on() && !out_in_scratch(); }
 
 const float* Engine::out_source(int64_t Wo) {
     const Batch& b = bt_;
-    if (!resample_on()) return b.wav;
+    if (!out_in_scratch()) return b.wav;
     float* d = out_f32_buf((size_t)b.B * Wo);
-    resample_enqueue(rs_table(), b.wav, b.B, native_row_len(), ENC_F32, d, Wo);
+    if (resample_on()) resample_enqueue(rs_table(), b.wav, b.B, native_row_len(), ENC_F32, d, Wo);
+    // section 18: the chain runs on the rows at the output rate, in place behind the resampler, out of b.wav (left as it is) otherwise
+    if (filter_on()) fl_batch(resample_on() ? d : b.wav, Wo, d);
     return d;
 }
 
@@ -477,7 +479,7 @@ void Engine::enqueue_output(const OutRows& o) {
         const EdScratch sc = ed_batch(src, Wo, pause_limit_active());  // (section 17: with the pause limit, the rows' several segments)
         const LoRes m = loudness_on() ? lo_batch(src, Wo, true) : LoRes{};
         const float* fade = st_window(output_rate());
-        const GainedRows r = gain_step(src, b.B, Wo, resample_on() ? Wo : W, m);  // (the untrimmed rows limited, then cut)
+        const GainedRows r = gain_step(src, b.B, Wo, out_in_scratch() ? Wo : W, m);  // (the untrimmed rows limited, then cut)
         StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_join_trim_rows(s_, r.src, r.stride, sc.S > 0 ? sc.pseg : sc.seg, sc.S > 0 ? sc.pprog : sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride);
     } else if (loudness_on()) {
@@ -485,6 +487,13 @@ void Engine::enqueue_output(const OutRows& o) {
         const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride);
+    } else if (filter_on()) {
+        // section 18: the filtered rows are in the fetch scratch; an fp32 fetch that was handed that scratch as its destination is done
+        const float* src = out_source(Wo);
+        if (src != o.dst) {
+            StageSpan span(*this, "out", "store_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+            launch_store_rows(s_, src, b.B, Wo, nullptr, o.enc, o.dst, o.stride);
+        }
     } else if (resample_on()) {
         resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
     } else if (o.enc != ENC_F32) {
@@ -520,8 +529,8 @@ void Engine::batch_fetch_encoded(int enc, void* dst, size_t capacity_bytes, floa
         if (capacity_bytes < bytes) throw std::runtime_error("buffer too small: need " + std::to_string(bytes) + " bytes");
         const void* src = bt_.wav;  // fp32 at the native rate: the batch's own rows, no device copy
         if (enc != ENC_F32 || !out_native() || silence_trim_on()) {
-            // (a trimmed fp32 fetch at a set rate moves samples within their rows: its destination lies behind the resampled rows)
-            const size_t off = enc == ENC_F32 && silence_trim_on() && resample_on() ? join_f32_offset(n) : 0;
+            // (a trimmed fp32 fetch of rows in the scratch moves samples within their rows: its destination lies behind those rows)
+            const size_t off = enc == ENC_F32 && silence_trim_on() && out_in_scratch() ? join_f32_offset(n) : 0;
             void* d = enc == ENC_F32 ? static_cast<void*>(out_f32_buf(off + n) + off) : static_cast<void*>(out_enc_buf(bytes));
             enqueue_output({d, enc, Wo});
             src = d;
@@ -717,16 +726,17 @@ void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& 
     STN_HIP(hipGetLastError());
 }
 
-// the fetch scratch of a joined fetch: the resampled rows (when a rate is set) in front, the joined fp32 rows (per-programme gain) behind
+// the fetch scratch of a joined fetch: the resampled and / or filtered rows (when there are any) in front, the joined fp32 rows
+// (per-programme gain) behind
 static size_t join_f32_offset(size_t n_rows) { return (n_rows + 3) / 4 * 4; }
 
 const float* Engine::join_f32(const JoinPlan& p) {
     const Batch& b = bt_;
     const int64_t Wo = out_row_len();
-    const size_t off = resample_on() ? join_f32_offset((size_t)b.B * Wo) : 0;
+    const size_t off = out_in_scratch() ? join_f32_offset((size_t)b.B * Wo) : 0;
     float* base = out_f32_buf(off + (size_t)p.G * p.W_join);  // (sized once: out_source below then finds room and moves nothing)
     const float* src = out_source(Wo);
-    join_enqueue(src, resample_on() ? Wo : native_row_len(), join_tables(p), p, nullptr, ENC_F32, base + off, p.W_join);
+    join_enqueue(src, out_in_scratch() ? Wo : native_row_len(), join_tables(p), p, nullptr, ENC_F32, base + off, p.W_join);
     return base + off;
 }
 
@@ -760,7 +770,7 @@ void Engine::enqueue_joined(const OutRows& o) {
         return;
     }
     const float* src = out_source(Wo);
-    const GainedRows r = gain_step(src, b.B, Wo, resample_on() ? Wo : W, loudness_on() ? lo_batch(src, Wo, true) : LoRes{});  // (the segments are the limited rows)
+    const GainedRows r = gain_step(src, b.B, Wo, out_in_scratch() ? Wo : W, loudness_on() ? lo_batch(src, Wo, true) : LoRes{});  // (the segments are the limited rows)
     join_enqueue(r.src, r.stride, join_tables(p), p, r.g, o.enc, o.dst, o.stride);
 }
 

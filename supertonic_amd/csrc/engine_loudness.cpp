@@ -58,17 +58,11 @@ std::string kweighting_design(int hz, KWeighting& k) {
     return "";
 }
 
-// The kernels' fp32 coefficients, and M = A^LO_CHUNK of the state transition A those coefficients define (state s1 s2 t1 t2 of the
-// two transposed direct form II sections, zero input), with its powers M^1 .. M^LO_SCAN, in double: the scan reads them as they are.
-std::string loudness_design(int hz, LoudTable& t) {
-    KWeighting k;
-    const std::string why = kweighting_design(hz, k);
-    if (!why.empty()) return why;
-    t.hz = hz;
-    t.hop = (hz + 5) / 10;
-    const double src[10] = {k.shelf_b[0], k.shelf_b[1], k.shelf_b[2], k.shelf_a[1], k.shelf_a[2], k.hp_b[0], k.hp_b[1], k.hp_b[2], k.hp_a[1], k.hp_a[2]};
+// M = A^LO_CHUNK of the state transition A the fp32 coefficients define (state s1 s2 t1 t2 of the two transposed direct form II
+// sections, zero input), with its powers M^1 .. M^LO_SCAN, in double: the scan reads them as they are.
+void cascade_powers(const LoudCoef& coef, std::vector<double>& mpow) {
     double c[10];
-    for (int i = 0; i < 10; ++i) { t.coef.c[i] = (float)src[i]; c[i] = t.coef.c[i]; }
+    for (int i = 0; i < 10; ++i) c[i] = coef.c[i];
     // v = s1; s1' = -a1 v + s2; s2' = -a2 v; y = c0 v + t1; t1' = c1 v - d1 y + t2; t2' = c2 v - d2 y
     const double A[16] = {-c[3], 1, 0, 0,
                           -c[4], 0, 0, 0,
@@ -85,14 +79,26 @@ std::string loudness_design(int hz, LoudTable& t) {
     double M[16], T[16];
     std::memcpy(M, A, sizeof(M));
     for (int i = 1; i < LO_CHUNK; ++i) { mul(M, A, T); std::memcpy(M, T, sizeof(M)); }
-    t.mpow.assign((size_t)LO_SCAN * 16, 0.0);
+    mpow.assign((size_t)LO_SCAN * 16, 0.0);
     double P[16];
     std::memcpy(P, M, sizeof(P));
     for (int i = 0; i < LO_SCAN; ++i) {
-        for (int j = 0; j < 16; ++j) t.mpow[(size_t)i * 16 + j] = P[j];
+        for (int j = 0; j < 16; ++j) mpow[(size_t)i * 16 + j] = P[j];
         mul(P, M, T);
         std::memcpy(P, T, sizeof(P));
     }
+}
+
+// The kernels' fp32 coefficients and the scan's powers for them
+std::string loudness_design(int hz, LoudTable& t) {
+    KWeighting k;
+    const std::string why = kweighting_design(hz, k);
+    if (!why.empty()) return why;
+    t.hz = hz;
+    t.hop = (hz + 5) / 10;
+    const double src[10] = {k.shelf_b[0], k.shelf_b[1], k.shelf_b[2], k.shelf_a[1], k.shelf_a[2], k.hp_b[0], k.hp_b[1], k.hp_b[2], k.hp_a[1], k.hp_a[2]};
+    for (int i = 0; i < 10; ++i) t.coef.c[i] = (float)src[i];
+    cascade_powers(t.coef, t.mpow);
     return "";
 }
 

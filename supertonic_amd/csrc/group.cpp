@@ -233,6 +233,12 @@ int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms) {
 int stn_group_set_peak_mode(stn_group* g, int mode) {
     return for_all(g, "stn_set_peak_mode", [](stn_handle* h, const void*, uint64_t v) { return stn_set_peak_mode(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)mode);
 }
+int stn_group_set_filters(stn_group* g, int n, const stn_filter* f) {
+    struct S { int n; const stn_filter* f; } v{n, f};
+    return for_all(g, "stn_set_filters", [](stn_handle* h, const void* a, uint64_t) {
+        const S* p = static_cast<const S*>(a);
+        return stn_set_filters(h, p->n, p->f); }, &v, 0);
+}
 int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms) {
     if (!g) return STN_ERR_INVALID;
     (void)max_pause_ms;

@@ -218,6 +218,38 @@ TextToSpeech::SynthesisResult TextToSpeech::batch(const std::vector<std::string>
     return infer(text_list, lang_list, style, total_step, speed);
 }
 
+std::string parseFilterSpec(const std::string& spec, stn_filter& f) {
+    static const char* const names[] = {"highpass", "lowpass", "notch", "peak", "lowshelf", "highshelf"};
+    std::vector<std::string> parts;
+    size_t a = 0, p;
+    while ((p = spec.find(':', a)) != std::string::npos) { parts.push_back(spec.substr(a, p - a)); a = p + 1; }
+    parts.push_back(spec.substr(a));
+    const std::string who = "filter '" + spec + "': ";
+    if (parts.size() < 2 || parts.size() > 4) return who + "expected TYPE:FREQ[:Q[:GAIN_DB]]";
+    f = stn_filter{-1, 0.0f, 0.7071f, 0.0f};
+    for (int t = 0; t < 6; ++t) if (parts[0] == names[t]) f.type = t;
+    if (f.type < 0) return who + "type must be one of highpass, lowpass, notch, peak, lowshelf, highshelf";
+    float* dst[3] = {&f.freq_hz, &f.q, &f.gain_db};
+    for (size_t i = 1; i < parts.size(); ++i) {
+        char* end = nullptr;
+        *dst[i - 1] = std::strtof(parts[i].c_str(), &end);
+        if (parts[i].empty() || *end) return who + "FREQ, Q and GAIN_DB must be numbers";
+    }
+    return "";
+}
+
+std::string filterPreset(const std::string& name, std::vector<stn_filter>& out) {
+    if (name == "rumble") {
+        out.push_back({STN_FILT_HIGHPASS, 80.0f, 0.7071f, 0.0f});
+    } else if (name == "telephone") {
+        for (int type : {STN_FILT_HIGHPASS, STN_FILT_LOWPASS})
+            for (float q : {0.541f, 1.307f}) out.push_back({type, type == STN_FILT_HIGHPASS ? 300.0f : 3400.0f, q, 0.0f});
+    } else {
+        return "filter-preset '" + name + "': rumble or telephone";
+    }
+    return "";
+}
+
 std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool use_gpu, const EngineOptions& opts) {
     if (!use_gpu) throw std::runtime_error("CPU mode is not supported: this engine runs on MI355X only");
     const char* dt_name = opts.dtype == STN_DTYPE_BF16 ? "bf16" : opts.dtype == STN_DTYPE_F16 ? "fp16" : "fp32";
@@ -271,6 +303,10 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         if (opts.output_rate) {
             if (grp) { if (stn_group_set_output_rate(grp, opts.output_rate) != STN_OK) throw std::runtime_error(std::string("output rate: ") + stn_group_last_error(grp)); }
             else check(h, stn_set_output_rate(h, opts.output_rate));
+        }
+        if (!opts.filters.empty()) {  // (after the rate: a chain is checked against the output rate in force)
+            if (grp) { if (stn_group_set_filters(grp, (int)opts.filters.size(), opts.filters.data()) != STN_OK) throw std::runtime_error(std::string("filters: ") + stn_group_last_error(grp)); }
+            else check(h, stn_set_filters(h, (int)opts.filters.size(), opts.filters.data()));
         }
         if (!std::isnan(opts.loudness_lufs)) {
             if (grp) {

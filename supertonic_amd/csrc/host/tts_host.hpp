@@ -76,9 +76,19 @@ struct EngineOptions {
                                    // milliseconds shortened to it on the GPU (stn_set_pause_limit); NaN: off.  CLI --max-pause MS
     float trim_keep_ms = 20.0f;    // milliseconds kept in front of and behind the speech.  CLI --trim-keep MS
     float trim_fade_ms = 5.0f;     // raised-cosine fade over each cut edge.  CLI --trim-fade MS
+    std::vector<stn_filter> filters;  // every utterance through this chain of up to STN_MAX_FILTERS biquads on the GPU, after the resampler
+                                   // and before everything above (stn_set_filters); empty: off.  CLI --filter TYPE:FREQ[:Q[:GAIN_DB]]
+                                   // (repeatable) and --filter-preset {rumble,telephone}
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
+
+// The command line's filter arguments (host only).  parseFilterSpec: "TYPE:FREQ[:Q[:GAIN_DB]]" (TYPE one of highpass, lowpass, notch,
+// peak, lowshelf, highshelf; Q 0.7071 and 0 dB when left out) into f, or why not.  filterPreset: "rumble" (a high-pass at 80 Hz) or
+// "telephone" (a 4th-order Butterworth band: high-pass 300 Hz and low-pass 3400 Hz, each as sections of Q 0.541 and 1.307) appended to
+// out, or why not.  The numeric limits are stn_set_filters' own.
+std::string parseFilterSpec(const std::string& spec, stn_filter& f);
+std::string filterPreset(const std::string& name, std::vector<stn_filter>& out);
 
 class TextToSpeech {
    public:

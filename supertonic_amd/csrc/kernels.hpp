@@ -533,6 +533,18 @@ void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t*
 void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pk, const float* pa,
                           const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res);
 // (the gain itself is applied by launch_store_rows with g = res + 2 * rows)
+// the powers M^1 .. M^LO_SCAN ([LO_SCAN][16], double) of M = A^LO_CHUNK for the two-section cascade with the fp32 coefficients c
+// (b0 b1 b2 a1 a2 twice): what the scan reads, for the K-weighting and for a section pass of the filter chain alike (host only)
+void cascade_powers(const LoudCoef& c, std::vector<double>& mpow);
+
+// Fetch-time biquad chain (kernels_filter.hip; the designer, the tables and the section passes are engine_filter.cpp; DESIGN.md section
+// 18).  A section pass is two biquads as the 4-state system above, every row W long: launch_loudness_chunks (energy = false) and
+// launch_loudness_scan on a LoudTable of the section's coefficients and powers (hop = 1, unused), then this launch, which refilters
+// every chunk from its start state st[row][k] and writes y (row stride W, as x).  y may be x: a workgroup reads its LO_WG * LO_CHUNK
+// samples before it stores any, and touches no other workgroup's.
+void launch_filter_write(hipStream_t s, const float* x, int64_t rows, int64_t W, const LoudTable& t, const float* st, float* y);
+// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
+const char* filter_staging_form(const float* x, const float* y, int64_t W);
 
 // Look-ahead peak limiter behind the loudness gain (kernels_limiter.hip; the setting, the window and the scratch are engine_limiter.cpp;
 // DESIGN.md section 15).  rows x W fp32 (row stride W) with row spans n[rows] (device, <= W) and gains gain[rows] (device; null: 1) ->

@@ -39,8 +39,8 @@ class _Job:
 
 class DynamicBatcher:
     """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding, and loudness scope / chunk trimming where a
-    request sets them) into one engine batch (the engine's output rate and loudness
+    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding, and loudness scope / chunk trimming / filter chain
+    where a request sets them) into one engine batch (the engine's output rate and loudness
     setting cover a whole batch; every row is still normalized with its own gain).  A worker thread owns
     the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
     its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
@@ -55,7 +55,7 @@ class DynamicBatcher:
 
     def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
                silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None,
-               max_pause_ms=None):
+               max_pause_ms=None, filters=None):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
         waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
         the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
@@ -70,7 +70,14 @@ class DynamicBatcher:
         ("sample" or "true"; None: the synthesizer's own setting): peak_ceiling as a sample-peak or a true-peak ceiling; validated here
         and part of the key's loudness entry in the same way.  max_pause_ms (with trim_silence; None: the synthesizer's own setting):
         every pause inside an utterance longer than that is shortened to it; validated here, part of the key's trimming entry, and
-        without effect (and out of the key) when trim_silence is None."""
+        without effect (and out of the key) when trim_silence is None.  filters (None: the synthesizer's own setting; a list as
+        binding.filter_args takes it, [] = off): the biquad chain every wave goes through first; validated here against the job's rate
+        and part of the batch key (the chain covers a whole batch): requests merge only when their chains are equal."""
+        chain = None if filters is None else binding.filter_args(filters)
+        if chain:
+            why = binding.filter_error(chain, int(sample_rate or self.tts.sample_rate))
+            if why:
+                raise ValueError(why)
         mp = None if max_pause_ms is None else binding.pause_limit_args(float(max_pause_ms))[1]
         lim = None if limiter_ms is None else binding.limiter_args(float(limiter_ms))[1]
         if peak_mode is not None:
@@ -83,6 +90,8 @@ class DynamicBatcher:
             key += (str(loudness_scope), bool(trim_chunks))
         if ts is not None:  # (likewise: always the key's last element, a pair)
             key += (("trim_silence", ts) if mp is None else ("trim_silence", ts, mp),)
+        if chain is not None:  # (likewise; behind everything else)
+            key += (("filters", chain),)
         job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
         with self._cv:
             if self._stop:
@@ -138,7 +147,9 @@ class DynamicBatcher:
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
                 step, speed, rate, lo, enc = jobs[0].key[:5]
                 tail = jobs[0].key[5:]
-                ts = mp = None
+                ts = mp = chain = None
+                if tail and isinstance(tail[-1], tuple) and tail[-1][0] == "filters":
+                    chain, tail = tail[-1][1], tail[:-1]
                 if tail and isinstance(tail[-1], tuple):
                     ts, mp, tail = tail[-1][1], (tail[-1][2] if len(tail[-1]) > 2 else None), tail[:-1]
                 scope, trim = tail or ("chunk", False)
@@ -155,6 +166,8 @@ class DynamicBatcher:
                         extra["peak_mode"] = lo.peak_mode
                 if enc is not None:
                     extra["encoding"] = enc
+                if chain is not None:
+                    extra["filters"] = list(chain)
                 joined = getattr(self.tts, "joined_batch", None)
                 if joined is not None and all(j.silence is not None for j in jobs):
                     # one programme per job, joined by the fetch on the GPU
@@ -253,6 +266,11 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         trim_fade_ms: float = Field(5.0, ge=0.0, le=50.0, description="Raised-cosine fade over each cut edge, in milliseconds.")
         max_pause_ms: Optional[float] = Field(None, ge=20.0, le=5000.0, description="With trim_silence: every pause inside an utterance longer than "
                                                                                     "this many milliseconds is shortened to it (on the GPU); null: off.")
+        filters: Optional[List[dict]] = Field(None, description="Biquad chain every utterance goes through on the GPU, after the resampler and before "
+                                                                "everything else: up to 8 of {type: highpass | lowpass | notch | peak | lowshelf | "
+                                                                "highshelf, freq (Hz), q (0.7071), gain_db (0)}; null: off.")
+        filter_preset: Optional[str] = Field(None, description="A named chain in front of filters: 'rumble' (high-pass at 80 Hz) or 'telephone' "
+                                                               "(300 to 3400 Hz, 4th-order Butterworth).")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -290,6 +308,16 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                 extra["limiter"] = req.limiter_ms
             if req.peak_mode is not None:
                 extra["peak_mode"] = req.peak_mode
+        chain = None
+        if req.filters is not None or req.filter_preset is not None:
+            try:
+                chain = binding.filter_args(req.filters, req.filter_preset)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            why = binding.filter_error(chain, sr) if chain else ""
+            if why:
+                raise HTTPException(status_code=400, detail=f"filters: {why}")
+            extra["filters"] = list(chain)
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
@@ -314,7 +342,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                          trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                         max_pause_ms=req.max_pause_ms)
+                                         max_pause_ms=req.max_pause_ms, filters=chain)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:

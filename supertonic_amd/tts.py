@@ -54,7 +54,8 @@ class TextToSpeech:
     returning (wav [B, W] float32, duration [B] float32).  One instance = one engine handle = one GPU; calls are
     serialised by a lock (the handle is single-threaded by contract)."""
 
-    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
+    def __init__(self, engine, text_processor, cfgs, noise_seed=None, output_rate=None, loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None,
+                 filters=None):
         self.engine = engine
         self.text_processor = text_processor
         self.cfgs = cfgs
@@ -63,6 +64,11 @@ class TextToSpeech:
         self.output_rate = int(output_rate) if output_rate else self.sample_rate
         if self.output_rate != self.sample_rate:
             engine.set_output_rate(self.output_rate)
+        # a chain of up to 8 biquads every returned row goes through on the GPU at fetch time, after the resampler and before everything
+        # below (Engine.set_filters): None = off, or a list as binding.filter_args takes it
+        self.filters = _filter_setting(filters)
+        if self.filters:
+            engine.set_filters(self.filters)
         # loudness normalization of the returned audio (measured and scaled on the GPU at fetch time, Engine.set_loudness): None = off,
         # a target in LUFS (peak ceiling -1 dBFS), or (target LUFS, ceiling dBFS)
         self.loudness = _loudness_setting(loudness)
@@ -103,7 +109,7 @@ class TextToSpeech:
         return self.noise_seed + self._calls - 1
 
     def _infer(self, text_list, lang_list, style, total_step, speed=1.05, length_aware=False, output_rate=None, loudness=None,
-               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None, peak_mode=None, max_pause=None):
+               encoding=None, join=None, trim_silence=None, lengths=False, limiter=None, peak_mode=None, max_pause=None, filters=None):
         """lengths: returns (wav, duration, len) with len [B] the samples each row holds from column 0: its trimmed segment with
         trimming on (Engine.batch_silence_edges, never a duration product; with the pause limit Engine.batch_pauses' len_b), else None."""
         if len(text_list) != style.ttl.shape[0]:
@@ -112,6 +118,7 @@ class TextToSpeech:
         lim = None if limiter is None else _limiter_setting(limiter)
         pause = self.max_pause if max_pause is None else _pause_setting(max_pause)
         binding.peak_mode_id(peak_mode)
+        chain = None if filters is None else _filter_setting(filters)
         ids, mask = self.text_processor(text_list, lang_list)
         with self._lock:
             # length-aware batches (the chunks of a long text, the service's merged requests) come in ever-changing lengths: shape
@@ -119,6 +126,8 @@ class TextToSpeech:
             # just longer); a plain batch keeps the reference's exact [B, L * chunk] result
             self.engine.set_vocoder_mode(length_aware)
             self.engine.set_shape_buckets(length_aware)
+            if filters is not None:  # this call's chain (fetch-time as well); off while the rate changes: a chain is checked against the rate in force
+                self.engine.set_filters(None)
             if output_rate is not None:  # this call's rate (a fetch-time setting: no captured graph depends on it)
                 self.engine.set_output_rate(output_rate)
             if loudness is not None:  # this call's normalization (fetch-time as well)
@@ -132,6 +141,8 @@ class TextToSpeech:
             if peak_mode is not None:  # this call's peak mode (fetch-time as well)
                 self.engine.set_peak_mode(peak_mode)
             try:
+                if chain:
+                    self.engine.set_filters(chain)
                 if join is not None:  # joined on the GPU by the fetch (Engine.batch_fetch_joined's arguments)
                     self.engine.batch_upload(ids, mask, style.ttl, style.dp)
                     self.engine.batch_run(total_step, speed, self._seed())
@@ -153,8 +164,12 @@ class TextToSpeech:
             finally:
                 self.engine.set_vocoder_mode(False)
                 self.engine.set_shape_buckets(False)
+                if filters is not None:
+                    self.engine.set_filters(None)
                 if output_rate is not None:
                     self.engine.set_output_rate(self.output_rate)
+                if filters is not None:
+                    self.engine.set_filters(self.filters)
                 if loudness is not None:
                     self.engine.set_loudness(*(self.loudness or (None,)))
                 if trim_silence is not None:
@@ -180,7 +195,7 @@ class TextToSpeech:
         return -(-int(n) * P // Q)
 
     def solo_batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None,
-                   trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
+                   trim_silence=None, limiter=None, peak_mode=None, max_pause=None, filters=None):
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
         and the durations.  The building block of the long-form path and of the service's dynamic batching.
@@ -191,10 +206,11 @@ class TextToSpeech:
         length the GPU found.  limiter (this call's: False = off, True = 5 ms, or the look-ahead in ms): with normalization, every
         utterance gets the full loudness gain and a look-ahead peak limiter holds the ceiling.  max_pause (this call's: False = off, or
         milliseconds in [20, 5000]; with trimming only): every pause inside an utterance longer than that is shortened to it, and the
-        wave is cut at what remains."""
+        wave is cut at what remains.  filters (this call's: False or [] = off, or a list as binding.filter_args takes it): every
+        utterance goes through that biquad chain before all of the above."""
         wav, dur, seg = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
                                     loudness=loudness, encoding=encoding, trim_silence=trim_silence, lengths=True, limiter=limiter, peak_mode=peak_mode,
-                                    max_pause=max_pause)
+                                    max_pause=max_pause, filters=filters)
         if seg is not None:
             return [wav[i, : int(n)] for i, n in enumerate(seg)], dur
         cs = self.base_chunk_size * self.chunk_compress_factor
@@ -203,7 +219,7 @@ class TextToSpeech:
 
     def joined_batch(self, text_list, lang_list, style, total_step, speed=1.05, rows=None, silence_duration=0.3, output_rate=None,
                      loudness=None, encoding=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None,
-                     max_pause=None):
+                     max_pause=None, filters=None):
         """solo_batch whose rows are joined on the GPU into len(rows) waves: rows[g] consecutive utterances each (None: all of them
         in one), silence_duration (one value, or one per wave) seconds of silence between two of them — the encoding's zero codeword.
         Returns (list of joined waves, their durations: the reference's fp32 sum d = dur_0; d += dur_i + silence).  loudness_scope,
@@ -212,7 +228,7 @@ class TextToSpeech:
         utterance cut at its duration before the join (the reference's Rust host) instead of its whole wave (C++ / Python hosts).
         trim_silence (as solo_batch): every utterance is its trimmed segment, so the pause between two of them is the silence asked for
         plus twice the kept margin; the durations are then those of the segments.  max_pause (as solo_batch): the pauses inside an
-        utterance are bounded as well."""
+        utterance are bounded as well.  filters: as solo_batch; every utterance is filtered on its own, then joined."""
         if loudness_scope not in ("chunk", "text"):
             raise ValueError(f"loudness_scope {loudness_scope!r}: 'chunk' or 'text'")
         rows = [len(text_list)] if rows is None else [int(r) for r in rows]
@@ -222,17 +238,17 @@ class TextToSpeech:
                 "mode": "trim" if trim_chunks else "whole", "gain_scope": "programme" if loudness_scope == "text" else "row"}
         waves, dur = self._infer(text_list, lang_list, style, total_step, speed, length_aware=True, output_rate=output_rate,
                                  loudness=loudness, encoding=encoding, join=join, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
-                                 max_pause=max_pause)
+                                 max_pause=max_pause, filters=filters)
         return waves, dur
 
     def __call__(self, text, lang, style, total_step, speed=1.05, silence_duration=0.3, encoding=None, loudness_scope="chunk",
-                 trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
+                 trim_chunks=False, trim_silence=None, limiter=None, peak_mode=None, max_pause=None, filters=None):
         """Long-form synthesis: the text is chunked, the chunks run as one length-aware batch and are joined with silence on the GPU
         (one joined fetch: py/helper.py:235-243's untrimmed chunk waves with zeros between).  With loudness normalization on,
         loudness_scope="chunk" normalizes each chunk as its own row (its own gain); "text" normalizes the joined text as one
         BS.1770 programme with one gain, its internal dynamics kept.  trim_chunks: as joined_batch.  encoding: as solo_batch; the
         silence is then the encoding's zero codeword.  trim_silence: as joined_batch; the returned wave then ends with the speech.
-        limiter: as solo_batch; with loudness_scope="text" the joined text is limited as one programme.  max_pause: as joined_batch."""
+        limiter: as solo_batch; with loudness_scope="text" the joined text is limited as one programme.  max_pause, filters: as joined_batch."""
         if style.ttl.shape[0] != 1:
             raise ValueError("Single speaker text to speech only supports single style")
         if loudness_scope not in ("chunk", "text"):
@@ -241,22 +257,30 @@ class TextToSpeech:
         trimming = (self.trim_silence if trim_silence is None else _trim_setting(trim_silence)) is not None
         if len(chunks) == 1 and not trim_chunks and not trimming:  # (one chunk is its own programme: the row's gain is the text's)
             return self._infer(chunks, [lang], style, total_step, speed, encoding=encoding, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
-                               max_pause=max_pause)
+                               max_pause=max_pause, filters=filters)
         n = len(chunks)
         rep = Style(np.repeat(style.ttl, n, axis=0), np.repeat(style.dp, n, axis=0))
         waves, dur = self.joined_batch(chunks, [lang] * n, rep, total_step, speed, silence_duration=silence_duration, encoding=encoding,
                                        loudness_scope=loudness_scope, trim_chunks=trim_chunks, trim_silence=trim_silence, limiter=limiter, peak_mode=peak_mode,
-                                       max_pause=max_pause)
+                                       max_pause=max_pause, filters=filters)
         return waves[0][None, :], np.array([dur[0]], np.float32)
 
     def batch(self, text_list, lang_list, style, total_step, speed=1.05, output_rate=None, loudness=None, encoding=None, trim_silence=None,
-              lengths=False, limiter=None, peak_mode=None, max_pause=None):
+              lengths=False, limiter=None, peak_mode=None, max_pause=None, filters=None):
         """One padded batch -> (wav [B, W] float32, duration [B]); with an encoding (a name or binding.ENC_*), the rows in that sample
         encoding instead, encoded on the GPU (binding.encoded_empty's dtypes).  trim_silence (as solo_batch): row b holds its trimmed
         segment from column 0 and the zero codeword behind it; lengths=True adds a third result, the segments' lengths [B] (None with
-        trimming off).  max_pause: as solo_batch; the row then holds its segments end to end."""
+        trimming off).  max_pause: as solo_batch; the row then holds its segments end to end.  filters: as
+        solo_batch."""
         return self._infer(text_list, lang_list, style, total_step, speed, output_rate=output_rate, loudness=loudness,
-                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter, peak_mode=peak_mode, max_pause=max_pause)
+                           encoding=encoding, trim_silence=trim_silence, lengths=lengths, limiter=limiter, peak_mode=peak_mode, max_pause=max_pause,
+                           filters=filters)
+
+
+def _filter_setting(v):
+    """A filters argument -> a tuple of (type, freq_hz, q, gain_db), empty for off: None / False / [] = off.  ValueError naming the field
+    for a malformed entry (binding.filter_args); the numeric limits are checked by the engine against the output rate in force."""
+    return binding.filter_args(None if v is False else v)
 
 
 def _limiter_setting(v):
@@ -297,7 +321,7 @@ def load_cfgs(onnx_dir):
 
 
 def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_synthetic=None, weight_seed=7, noise_seed=None, output_rate=None,
-                        loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None):
+                        loudness=None, trim_silence=None, limiter=None, peak_mode=None, max_pause=None, filters=None):
     """py/helper.py:316-337.  use_gpu=True is the only mode (the reference only had the CPU one).  An unusable asset directory is an
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
@@ -310,11 +334,14 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
     look-ahead, or milliseconds in [0.5, 10]; include/stn.h, stn_set_limiter); None keeps the capped gain.
     `peak_mode`: "true" makes the ceiling of `loudness` a true-peak ceiling (dBTP, 4x oversampled; include/stn.h, stn_set_peak_mode); None
     or "sample" keeps the sample-peak ceiling.  `max_pause`: with `trim_silence`, every pause inside an utterance longer than this many
-    milliseconds ([20, 5000]) is shortened to it on the GPU (include/stn.h, stn_set_pause_limit); None leaves the pauses as synthesized."""
+    milliseconds ([20, 5000]) is shortened to it on the GPU (include/stn.h, stn_set_pause_limit); None leaves the pauses as synthesized.
+    `filters`: every utterance goes through this chain of up to 8 biquads on the GPU, after the resampler and before everything above (a
+    list as binding.filter_args takes it, e.g. [("highpass", 80)]; include/stn.h, stn_set_filters); None leaves the spectrum as synthesized."""
     _trim_setting(trim_silence)  # (refused before the engine is created)
     _pause_setting(max_pause)
     _limiter_setting(limiter)
     binding.peak_mode_id(peak_mode)
+    _filter_setting(filters)
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
     if not use_gpu:
@@ -336,6 +363,6 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
                 "ttl": {"chunk_compress_factor": a.chunk_compress_factor, "latent_dim": a.latent_dim}}
         tp = host.UnicodeProcessor(host.synthetic_indexer())
         synthetic = True
-    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter, peak_mode, max_pause)
+    tts = TextToSpeech(eng, tp, cfgs, noise_seed, output_rate, loudness, trim_silence, limiter, peak_mode, max_pause, filters)
     tts.synthetic = synthetic
     return tts
