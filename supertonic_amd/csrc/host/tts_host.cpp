@@ -28,6 +28,18 @@ std::vector<int64_t> trimmed_lengths(stn_handle* h, int B, bool pause_limit) {
     for (int b = 0; b < B; ++b) end[(size_t)b] -= start[(size_t)b];
     return end;
 }
+// what a group (several devices) refuses, said once: loadTextToSpeech refuses before anything is created, the instance where it is asked
+std::string groupRefusesScopeText() {
+    return "loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
+           "(use one GPU, or the default scope 'chunk')";
+}
+std::string groupRefusesTrimChunks() { return "trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)"; }
+std::string groupRefusesSilenceTrim() {
+    return "silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)";
+}
+std::string groupRefusesPauseLimit() {
+    return "the pause limit needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --max-pause out)";
+}
 }  // namespace
 
 TextToSpeech::TextToSpeech(stn_handle* engine, UnicodeProcessor tp, const Config& cfgs, uint64_t noise_seed)
@@ -91,13 +103,13 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
 }
 
 void TextToSpeech::setSilenceTrim(bool on, float top_db, float keep_ms, float fade_ms) {
-    if (on && grp_) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
+    if (on && grp_) throw std::runtime_error(groupRefusesSilenceTrim());
     check(h_, stn_set_silence_trim(h_, on ? 1 : 0, top_db, keep_ms, fade_ms));
     trim_silence_ = on;
 }
 
 void TextToSpeech::setPauseLimit(bool on, float max_pause_ms) {
-    if (on && grp_) throw std::runtime_error("the pause limit needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --max-pause out)");
+    if (on && grp_) throw std::runtime_error(groupRefusesPauseLimit());
     if (on && !trim_silence_) throw std::runtime_error("the pause limit needs silence trimming (it shortens pauses inside trimmed utterances)");
     check(h_, stn_set_pause_limit(h_, on ? 1 : 0, max_pause_ms));
     pause_limit_ = on;
@@ -116,9 +128,7 @@ void TextToSpeech::runBatch(const TokenBatch& tb, const std::vector<float>& mask
 }
 
 void TextToSpeech::setLoudnessScope(bool whole_text) {
-    if (whole_text && grp_)
-        throw std::runtime_error("loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
-                                 "(use one GPU, or the default scope 'chunk')");
+    if (whole_text && grp_) throw std::runtime_error(groupRefusesScopeText());
     scope_text_ = whole_text;
 }
 
@@ -176,7 +186,7 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
         return out;
     }
     // a group deals the chunks over its devices: its long form keeps the host join of the gathered rows
-    if (trim_chunks_) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
+    if (trim_chunks_) throw std::runtime_error(groupRefusesTrimChunks());
     const SynthesisResult r = infer(chunks, std::vector<std::string>((size_t)n, lang), rep, total_step, speed);
     const size_t eb = r.encoding == STN_ENC_PCM16 ? 0 : (size_t)stn_encoding_bytes(r.encoding);  // 0: the float waveform
     const size_t W = eb ? r.encoded.size() / eb / (size_t)n : r.wav.size() / (size_t)n;
@@ -257,12 +267,10 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
     stn_group* grp = nullptr;
     if (opts.gpus > 1 || !opts.devices.empty()) {
         // refused before anything is created: a group deals the chunks of a text over its devices and keeps the host join
-        if (opts.loudness_scope_text)
-            throw std::runtime_error("loudness scope 'text' needs the chunks of a text on one device: a group deals them over its devices "
-                                     "(use one GPU, or the default scope 'chunk')");
-        if (opts.trim_chunks) throw std::runtime_error("trimmed chunks need the chunks of a text on one device (a group keeps the untrimmed host join)");
-        if (!std::isnan(opts.trim_silence_db)) throw std::runtime_error("silence trimming needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --trim-silence out)");
-        if (!std::isnan(opts.max_pause_ms)) throw std::runtime_error("the pause limit needs every utterance on one device: a group (--gpus N, --devices) does not trim (use one GPU, or leave --max-pause out)");
+        if (opts.loudness_scope_text) throw std::runtime_error(groupRefusesScopeText());
+        if (opts.trim_chunks) throw std::runtime_error(groupRefusesTrimChunks());
+        if (!std::isnan(opts.trim_silence_db)) throw std::runtime_error(groupRefusesSilenceTrim());
+        if (!std::isnan(opts.max_pause_ms)) throw std::runtime_error(groupRefusesPauseLimit());
         std::vector<int> dev = opts.devices;
         if (dev.empty()) for (int i = 0; i < opts.gpus; ++i) dev.push_back(opts.device + i);
         if (stn_group_create((int)dev.size(), dev.data(), opts.dtype, &grp) != STN_OK) throw std::runtime_error(std::string("engine group: ") + stn_group_last_error(nullptr));
@@ -300,37 +308,25 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         } else {
             throw std::runtime_error(load_err());
         }
-        if (opts.output_rate) {
-            if (grp) { if (stn_group_set_output_rate(grp, opts.output_rate) != STN_OK) throw std::runtime_error(std::string("output rate: ") + stn_group_last_error(grp)); }
-            else check(h, stn_set_output_rate(h, opts.output_rate));
-        }
-        if (!opts.filters.empty()) {  // (after the rate: a chain is checked against the output rate in force)
-            if (grp) { if (stn_group_set_filters(grp, (int)opts.filters.size(), opts.filters.data()) != STN_OK) throw std::runtime_error(std::string("filters: ") + stn_group_last_error(grp)); }
-            else check(h, stn_set_filters(h, (int)opts.filters.size(), opts.filters.data()));
-        }
-        if (!std::isnan(opts.loudness_lufs)) {
-            if (grp) {
-                if (stn_group_set_loudness(grp, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs) != STN_OK)
-                    throw std::runtime_error(std::string("loudness: ") + stn_group_last_error(grp));
-            } else {
-                check(h, stn_set_loudness(h, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs));
-            }
-        }
+        // rc: what the group's setter (every rank) or the single handle's returned
+        auto applied = [&](const char* what, int rc) {
+            if (grp) { if (rc != STN_OK) throw std::runtime_error(std::string(what) + ": " + stn_group_last_error(grp)); }
+            else check(h, rc);
+        };
+        const int nf = (int)opts.filters.size();
+        if (opts.output_rate) applied("output rate", grp ? stn_group_set_output_rate(grp, opts.output_rate) : stn_set_output_rate(h, opts.output_rate));
+        // (after the rate: a chain is checked against the output rate in force)
+        if (nf) applied("filters", grp ? stn_group_set_filters(grp, nf, opts.filters.data()) : stn_set_filters(h, nf, opts.filters.data()));
+        if (!std::isnan(opts.loudness_lufs))
+            applied("loudness", grp ? stn_group_set_loudness(grp, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs)
+                                    : stn_set_loudness(h, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs));
         if (!std::isnan(opts.limiter_ms)) {
             if (std::isnan(opts.loudness_lufs)) throw std::runtime_error("the limiter needs loudness normalization (it holds the ceiling of the loudness gain)");
-            if (grp) {
-                if (stn_group_set_limiter(grp, 1, opts.limiter_ms) != STN_OK) throw std::runtime_error(std::string("limiter: ") + stn_group_last_error(grp));
-            } else {
-                check(h, stn_set_limiter(h, 1, opts.limiter_ms));
-            }
+            applied("limiter", grp ? stn_group_set_limiter(grp, 1, opts.limiter_ms) : stn_set_limiter(h, 1, opts.limiter_ms));
         }
         if (opts.true_peak) {
             if (std::isnan(opts.loudness_lufs)) throw std::runtime_error("the true-peak mode needs loudness normalization (it is the ceiling of the loudness gain)");
-            if (grp) {
-                if (stn_group_set_peak_mode(grp, STN_PEAK_TRUE) != STN_OK) throw std::runtime_error(std::string("peak mode: ") + stn_group_last_error(grp));
-            } else {
-                check(h, stn_set_peak_mode(h, STN_PEAK_TRUE));
-            }
+            applied("peak mode", grp ? stn_group_set_peak_mode(grp, STN_PEAK_TRUE) : stn_set_peak_mode(h, STN_PEAK_TRUE));
         }
         // (refused here, while this function still owns the handle: once tts owns it, a throw would destroy it twice)
         if (!std::isnan(opts.trim_silence_db)) check(h, stn_set_silence_trim(h, 1, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms));

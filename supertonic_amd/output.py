@@ -1,0 +1,120 @@
+"""The fetch-time settings of the returned audio as one value (host only): what TextToSpeech keeps per instance, what a call overrides,
+and what the service's batch key compares."""
+import contextlib
+import dataclasses
+
+from . import binding
+
+
+def _loudness(v):
+    if isinstance(v, (tuple, list)):
+        t, c = v
+        return float(t), float(c)
+    return float(v), -1.0
+
+
+def _switched(args):
+    """A binding.*_args function, (on, value), as a parser: the value, or False for off"""
+    def parse(v):
+        on, ms = args(v)
+        return ms if on else False
+    return parse
+
+
+def _peak_mode(v):
+    binding.peak_mode_id(v)
+    return v
+
+
+# keyword -> its parser, for every value but None (unset); the order is the order the keywords are validated in
+_PARSE = {
+    "output_rate": int,
+    "filters": lambda v: binding.filter_args(None if v is False else v),
+    "loudness": lambda v: v is not False and _loudness(v),
+    "trim_silence": lambda v: v is not False and binding.silence_trim_args(v)[1:],
+    "max_pause": _switched(binding.pause_limit_args),
+    "limiter": _switched(binding.limiter_args),
+    "peak_mode": _peak_mode,
+}
+
+
+@dataclasses.dataclass(frozen=True)
+class OutputSettings:
+    """What happens to the audio on the GPU at fetch time (include/stn.h; no captured graph depends on any of it), in the order it
+    happens.  Every field is None (unset: the instance's value holds), off, or a value in one normalized form; equal settings compare
+    and hash equal.  The keywords of load_text_to_speech and of TextToSpeech's methods are these fields, as parse() takes them:
+
+    output_rate   Hz of the returned audio, resampled from the model's rate (stn_set_output_rate).  Off: 0, the model's rate.
+    filters       a chain of up to 8 biquads every utterance goes through, after the resampler and before everything below
+                  (stn_set_filters): a list as binding.filter_args takes it, e.g. [("highpass", 80)]; the numeric limits are checked by
+                  the engine against the output rate in force.  Normalized: a tuple of (type, freq_hz, q, gain_db).  Off: False or [], ().
+    loudness      every utterance normalized to this BS.1770-4 integrated loudness, measured at the output rate (stn_set_loudness): a
+                  target in LUFS (peak ceiling -1 dBFS) or (target, ceiling dBFS).  Normalized: (target, ceiling).  Off: False.
+    trim_silence  leading and trailing silence trimmed by level (stn_set_silence_trim): top_db (20 ms kept, 5 ms fade) or
+                  (top_db, keep_ms, fade_ms).  Normalized: the triple.  Off: False.
+    max_pause     every pause inside an utterance longer than this many milliseconds ([20, 5000]) shortened to it (stn_set_pause_limit);
+                  it acts only while trim_silence is on.  Off: False.
+    limiter       the full loudness gain, and a look-ahead peak limiter holds the ceiling (stn_set_limiter): True (5 ms) or the look-ahead
+                  in milliseconds ([0.5, 10]); it acts only while loudness is on.  Normalized: milliseconds.  Off: False, the capped gain.
+    peak_mode     the ceiling of loudness as a sample peak ("sample") or a true peak ("true": dBTP, 4x oversampled; stn_set_peak_mode);
+                  it acts only while loudness is on.  Off: "sample"."""
+    output_rate: object = None
+    filters: object = None
+    loudness: object = None
+    trim_silence: object = None
+    max_pause: object = None
+    limiter: object = None
+    peak_mode: object = None
+
+    @classmethod
+    def parse(cls, **kw):
+        """The keyword forms above -> the value; None leaves a field unset.  A refused value is binding's ValueError, an unknown keyword
+        a TypeError."""
+        for k in kw:
+            if k not in _PARSE:
+                raise TypeError(f"{k!r} is not an output setting ({', '.join(_PARSE)})")
+        return cls(**{k: p(kw[k]) for k, p in _PARSE.items() if kw.get(k) is not None})
+
+    def kwargs(self):
+        """The set fields under their keywords, as parse takes them (filters as a list)"""
+        kw = {k: getattr(self, k) for k in _PARSE if getattr(self, k) is not None}
+        if "filters" in kw:
+            kw["filters"] = list(self.filters)
+        return kw
+
+    def over(self, base):
+        """base with this value's set fields in force"""
+        return dataclasses.replace(base, **{k: getattr(self, k) for k in self.kwargs()})
+
+    def apply(self, engine):
+        """The set fields onto a binding.Engine, in the one order that works: a chain is checked against the output rate in force, so
+        it goes off before the rate changes and on after it.  The rest are independent of each other."""
+        if self.filters is not None:
+            engine.set_filters(None)
+        if self.output_rate is not None:
+            engine.set_output_rate(self.output_rate)
+        if self.filters:
+            engine.set_filters(self.filters)
+        if self.loudness is not None:
+            engine.set_loudness(*(self.loudness or (None,)))
+        if self.trim_silence is not None:
+            engine.set_silence_trim(self.trim_silence or None)
+        if self.max_pause is not None:
+            engine.set_pause_limit(self.max_pause or None)
+        if self.limiter is not None:
+            engine.set_limiter(self.limiter or None)
+        if self.peak_mode is not None:
+            engine.set_peak_mode(self.peak_mode)
+
+    @contextlib.contextmanager
+    def applied(self, engine, base):
+        """For the body, the engine (which holds base) holds self.over(base), which is what the body gets.  On every way out, a setter's
+        refusal part-way through included, the fields this value set are base's again."""
+        try:
+            self.apply(engine)
+            yield self.over(base)
+        finally:
+            OutputSettings(**{k: getattr(base, k) for k in self.kwargs()}).apply(engine)
+
+
+OutputSettings.OFF = OutputSettings(0, (), False, False, False, False, "sample")

@@ -8,6 +8,7 @@ included; a `batch: true` request keeps the reference's semantics (its own padde
 
     TTS_ONNX_DIR=assets/onnx TTS_DTYPE=bf16 uvicorn supertonic_amd.service:app
 """
+import dataclasses
 import io
 import os
 import threading
@@ -19,13 +20,41 @@ from typing import List, Literal, Optional, Union
 import numpy as np
 
 from . import binding, host
+from .output import OutputSettings
 from .tts import Style, load_text_to_speech, load_voice_style
 
 AVAILABLE_LANGS = host.AVAILABLE_LANGS
 
 
-# the loudness entry of a batch key: requests merge only when all four agree (limiter_ms / peak_mode None: the synthesizer's own setting)
-LoudnessKey = namedtuple("LoudnessKey", "lufs ceiling limiter_ms peak_mode")
+# what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
+BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings")
+
+
+def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
+              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None):
+    """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
+    of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
+    value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
+    sample_rate: the rate of the waves (the model's is model_rate).  loudness: normalize each wave to this many LUFS with the gain capped
+    at peak_ceiling dBFS.  limiter_ms, peak_mode ("sample" or "true"): OutputSettings' limiter and peak_mode; they act on the loudness
+    gain, so without loudness they (and peak_ceiling) are validated and dropped.  trim_silence: top_db or (top_db, keep_ms, fade_ms), no
+    bool.  max_pause_ms: without trim_silence, validated and dropped likewise.  filters: a list as binding.filter_args takes it, [] =
+    off, checked against the request's rate.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
+    loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode."""
+    chain = None if filters is None else binding.filter_args(filters)
+    why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
+    if why:
+        raise ValueError(why)
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, loudness=None if loudness is None else (loudness, peak_ceiling),
+                             trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
+                             max_pause=None if max_pause_ms is None else float(max_pause_ms),
+                             limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
+    if s.loudness is None:
+        s = dataclasses.replace(s, limiter=None, peak_mode=None)
+    if s.trim_silence is None:
+        s = dataclasses.replace(s, max_pause=None)
+    return BatchKey(int(total_step), float(speed), None if encoding is None else binding.encoding_id(encoding), str(loudness_scope),
+                    bool(trim_chunks), s)
 
 
 class _Job:
@@ -38,12 +67,10 @@ class _Job:
 
 
 class DynamicBatcher:
-    """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share
-    (total_step, speed, output rate, loudness target and peak ceiling, sample encoding, and loudness scope / chunk trimming / filter chain
-    where a request sets them) into one engine batch (the engine's output rate and loudness
-    setting cover a whole batch; every row is still normalized with its own gain).  A worker thread owns
-    the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch` utterances are queued), runs `tts.solo_batch` once and hands every job
-    its own rows.  Rows are independent by construction, so merging changes latency and throughput, not audio."""
+    """Merges concurrent single-speaker jobs (each: the chunks of one text, one language, one style) that share a BatchKey into one
+    engine batch.  A worker thread owns the engine: it takes the oldest job, waits up to `max_wait_ms` for company (or until `max_batch`
+    utterances are queued), runs `tts.solo_batch` once and hands every job its own rows.  Rows are independent by construction, so
+    merging changes latency and throughput, not audio."""
 
     def __init__(self, tts, max_batch=128, max_wait_ms=3.0):
         self.tts, self.max_batch, self.max_wait = tts, int(max_batch), max_wait_ms / 1e3
@@ -53,45 +80,12 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None,
-               silence_duration=None, loudness_scope="chunk", trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None,
-               max_pause_ms=None, filters=None):
-        """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  sample_rate: the rate of the
-        waves (None: the model's).  loudness: normalize each wave to this many LUFS with the gain capped at peak_ceiling dBFS (None:
-        the synthesizer's own setting).  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
-        silence_duration (seconds, not None): the job's utterances are the chunks of one text and come back as ONE wave, joined with
-        that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own gap), with its duration;
-        loudness_scope ("chunk": every chunk its own gain; "text": the joined wave normalized as one programme) and trim_chunks
-        (TextToSpeech.joined_batch) are part of the batch key: one fetch has one mode and one scope.  trim_silence (None: the
-        synthesizer's own setting; top_db or (top_db, keep_ms, fade_ms)): the waves without their leading and trailing silence; part of
-        the batch key as well (the setting covers a whole batch), and validated here.  limiter_ms (with loudness; None: the
-        synthesizer's own setting): the full loudness gain, the ceiling held by a look-ahead peak limiter of that many milliseconds;
-        validated here, part of the key's loudness entry, and without effect (and out of the key) when loudness is None.  peak_mode
-        ("sample" or "true"; None: the synthesizer's own setting): peak_ceiling as a sample-peak or a true-peak ceiling; validated here
-        and part of the key's loudness entry in the same way.  max_pause_ms (with trim_silence; None: the synthesizer's own setting):
-        every pause inside an utterance longer than that is shortened to it; validated here, part of the key's trimming entry, and
-        without effect (and out of the key) when trim_silence is None.  filters (None: the synthesizer's own setting; a list as
-        binding.filter_args takes it, [] = off): the biquad chain every wave goes through first; validated here against the job's rate
-        and part of the batch key (the chain covers a whole batch): requests merge only when their chains are equal."""
-        chain = None if filters is None else binding.filter_args(filters)
-        if chain:
-            why = binding.filter_error(chain, int(sample_rate or self.tts.sample_rate))
-            if why:
-                raise ValueError(why)
-        mp = None if max_pause_ms is None else binding.pause_limit_args(float(max_pause_ms))[1]
-        lim = None if limiter_ms is None else binding.limiter_args(float(limiter_ms))[1]
-        if peak_mode is not None:
-            binding.peak_mode_id(peak_mode)
-        ts = None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:]
-        lo = None if loudness is None else LoudnessKey(float(loudness), float(peak_ceiling), lim, None if peak_mode is None else str(peak_mode))
-        enc = None if encoding is None else binding.encoding_id(encoding)
-        key = (int(total_step), float(speed), None if sample_rate is None else int(sample_rate), lo, enc)
-        if loudness_scope != "chunk" or trim_chunks:  # (requests that use neither batch exactly as before)
-            key += (str(loudness_scope), bool(trim_chunks))
-        if ts is not None:  # (likewise: always the key's last element, a pair)
-            key += (("trim_silence", ts) if mp is None else ("trim_silence", ts, mp),)
-        if chain is not None:  # (likewise; behind everything else)
-            key += (("filters", chain),)
+    def submit(self, texts, lang, style, *request, silence_duration=None, **request_kw):
+        """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  request: total_step, speed and the
+        rest of batch_key's arguments.  silence_duration (seconds, not None): the job's utterances are the chunks of one text and come
+        back as ONE wave, joined with that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own
+        gap), with its duration."""
+        key = batch_key(self.tts.sample_rate, *request, **request_kw)
         job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
         with self._cv:
             if self._stop:
@@ -145,50 +139,31 @@ class DynamicBatcher:
                 langs = [j.lang for j in jobs for _ in j.texts]
                 ttl = np.concatenate([np.repeat(j.style.ttl, len(j.texts), axis=0) for j in jobs])
                 dp = np.concatenate([np.repeat(j.style.dp, len(j.texts), axis=0) for j in jobs])
-                step, speed, rate, lo, enc = jobs[0].key[:5]
-                tail = jobs[0].key[5:]
-                ts = mp = chain = None
-                if tail and isinstance(tail[-1], tuple) and tail[-1][0] == "filters":
-                    chain, tail = tail[-1][1], tail[:-1]
-                if tail and isinstance(tail[-1], tuple):
-                    ts, mp, tail = tail[-1][1], (tail[-1][2] if len(tail[-1]) > 2 else None), tail[:-1]
-                scope, trim = tail or ("chunk", False)
-                extra = {} if rate is None else {"output_rate": rate}
-                if ts is not None:
-                    extra["trim_silence"] = ts
-                if mp is not None:
-                    extra["max_pause"] = mp
-                if lo is not None:
-                    extra["loudness"] = (lo.lufs, lo.ceiling)
-                    if lo.limiter_ms is not None:
-                        extra["limiter"] = lo.limiter_ms
-                    if lo.peak_mode is not None:
-                        extra["peak_mode"] = lo.peak_mode
-                if enc is not None:
-                    extra["encoding"] = enc
-                if chain is not None:
-                    extra["filters"] = list(chain)
+                key = jobs[0].key
+                extra = key.settings.kwargs()  # (only what the requests set, as they set it)
+                if key.encoding is not None:
+                    extra["encoding"] = key.encoding
                 joined = getattr(self.tts, "joined_batch", None)
                 if joined is not None and all(j.silence is not None for j in jobs):
                     # one programme per job, joined by the fetch on the GPU
-                    waves, durs = joined(texts, langs, Style(ttl, dp), step, speed, rows=[len(j.texts) for j in jobs],
-                                         silence_duration=[j.silence for j in jobs], loudness_scope=scope, trim_chunks=trim, **extra)
+                    waves, durs = joined(texts, langs, Style(ttl, dp), key.total_step, key.speed, rows=[len(j.texts) for j in jobs],
+                                         silence_duration=[j.silence for j in jobs], loudness_scope=key.loudness_scope, trim_chunks=key.trim_chunks, **extra)
                     self.batches.append(len(texts))
                     for g, j in enumerate(jobs):
                         j.waves, j.durs = [waves[g]], np.asarray(durs[g:g + 1], np.float32)
                 else:
-                    if scope != "chunk" or trim:
+                    if key.loudness_scope != "chunk" or key.trim_chunks:
                         raise RuntimeError("loudness_scope / trim_chunks need a synthesizer with a joined fetch (TextToSpeech.joined_batch)")
                     # a synthesizer without a joined fetch (a stand-in), or a caller that wants the rows: per-utterance waves; a job
                     # that asked for one wave gets the host join of them
-                    waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), step, speed, **extra)
+                    waves, durs = self.tts.solo_batch(texts, langs, Style(ttl, dp), key.total_step, key.speed, **extra)
                     self.batches.append(len(texts))
                     o = 0
                     for j in jobs:
                         n = len(j.texts)
                         j.waves, j.durs = waves[o:o + n], np.asarray(durs[o:o + n], np.float32)
                         if j.silence is not None:
-                            w, d = join_chunks(j.waves, j.durs, j.silence, rate or self.tts.sample_rate, enc)
+                            w, d = join_chunks(j.waves, j.durs, j.silence, key.settings.output_rate or self.tts.sample_rate, key.encoding)
                             j.waves, j.durs = [w], np.array([d], np.float32)
                         o += n
             except Exception as e:  # the requests fail, the worker lives on
