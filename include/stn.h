@@ -624,6 +624,66 @@ int stn_filter_response(int n, const stn_filter* f, int rate_hz, int n_freq, con
  * section pass; each may be NULL */
 int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int* biquads_per_section);
 
+/* ---- compressor --------------------------------------------------------------------------------------
+ * A feed-forward, log-domain dynamic range compressor (Giannoulis, Massberg and Reiss, "Digital Dynamic Range Compressor Design", JAES
+ * 2012: level detector behind the gain computer, decoupled peak detector) applied to every row of every fetch, on the GPU, at the
+ * output rate: it narrows the distance between the loud and the quiet parts of an utterance, in front of G.711's 38 dB, for playback in
+ * noise, and so that the limiter is left the clicks.  Off is the default: every fetch is then byte for byte the one without the
+ * feature, and no compressor launch runs.
+ * Order of the output stage: native rows -> resample (if a rate is set) -> filter chain -> COMPRESSOR -> silence edges / pause cuts ->
+ * loudness measurement -> gain / limiter / true peak -> encoding store / join.  Everything behind it sees the compressed signal: every
+ * fetch path (synchronous, both pipelined slots, device copies, joined, the group's gather) and every report (stn_batch_loudness,
+ * _silence_edges, _pauses, _limiter, _true_peak, stn_batch_join_loudness).  One consequence: the silence trim's top_db is then relative
+ * to the loudest frame of the compressed signal, in which level differences above the threshold are smaller by the ratio.
+ * stn_batch_wav_device_ptr, stn_batch_fetch_latent, the batch's own waveform, the captured pipeline and the graph key are untouched: the
+ * compressed rows live in fetch scratch, and changing the setting drops or re-captures no graph.
+ * Each row is compressed on its own, from y1 = yL = 0 at its sample 0, over the row's whole width W_out (padding included).  Per
+ * sample, all values fp32:
+ *   level          xG = 20 log10(max(|x|, 1e-6))
+ *   gain computer  T = threshold_db, S = 1 / ratio - 1, K = knee_db, d = xG - T:
+ *                  z = 0 when 2 d < -K;  z = -S (d + K / 2)^2 / (2 K) when 2 |d| <= K (and K > 0);  z = -S d otherwise   (z >= 0, dB)
+ *   detector       y1 = max(z, fma(-kR, y1, y1));  yL = fma(kA, y1 - yL, yL);  k = -expm1(-1000 / (ms rate)), formed in double and
+ *                  rounded to fp32 (the k form, not alpha = 1 - k: at a 3 s release and 192 kHz the fp32 neighbours of alpha are 3 %
+ *                  apart in time constant)
+ *   output         y = x 10^((makeup_db - yL) / 20)
+ * The reference of every numeric claim is exactly this in float64 on the same fp32-rounded T, S, K, kA, kR and makeup.  Identities:
+ *   the delivered fp32 row == stn_op_compressor(the fp32 row delivered with the compressor off), bit for bit;
+ *   a row's first n samples do not depend on W, the batch or the row's place in it;
+ *   a joined fetch == the host join of the per-row fetch, byte for byte, as without the compressor.
+ * Refused with STN_ERR_INVALID and a message that names the field: threshold_db outside [-60, 0], ratio outside [1, 20], knee_db
+ * outside [0, 24], attack_ms outside [0.1, 300], release_ms outside [10, 3000], makeup_db outside [-12, 24], a non-finite field.  The
+ * previous setting stays in force.  None of the limits depends on the rate, so stn_set_output_rate never refuses on the compressor's
+ * account.  DESIGN.md section 20 has the decomposition and the measurements. */
+typedef struct stn_compressor { float threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db; } stn_compressor;
+/* on = 0: off, c may then be NULL (the values last set stay readable) */
+int stn_set_compressor(stn_handle* h, int on, const stn_compressor* c);
+/* either may be NULL; *out: the values last set (before the first set: -24 dB, 3:1, knee 6 dB, 5 ms, 120 ms, 0 dB) */
+int stn_get_compressor(const stn_handle* h, int* on, stn_compressor* out);
+/* per row of the finished batch: the maximum of yL, the reduction in dB, over the row's valid samples (its reported duration at the
+ * output rate); 0 for every row while the compressor is off */
+int stn_batch_compressor(stn_handle* h, float* max_reduction_db);
+/* op-level: rows x W fp32 (host) at hz through the compressor c -> y [rows][W] (host).  1 <= rows <= 65535. */
+int stn_op_compressor(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, float* y);
+/* The same with its scratch laid open (the kernel tests).  Five launches on chunks of 32 samples (Ks = (W + 31) / 32 per row): y1 of
+ * every chunk from zero (s1_end), the (max, x) scan of those in double (s1_start: y1 at every chunk's start), yL of every chunk from
+ * zero on its true y1 (s2_end), the linear scan in double (s2_start), and the write pass from both start values: y, and gr_db
+ * [rows][W] = yL.  Each of gr_db, s1_end, s1_start, s2_end, s2_start ([rows][Ks] each) may be NULL.  The device's scratch and gr_db
+ * are filled with the quiet NaN 0x7FC00000 before the first launch, and x and y lie with 64 poisoned floats in front of and behind
+ * them: *guard_ok = 1 when all of those came back untouched.  x_misalign 0 / 1: x and y lie 16-byte aligned / 4 bytes off, which forces
+ * the scalar staging path at W % 4 == 0.  in_place 0 / 1: y is written to rows of its own / over x on the device.  form: the staging
+ * path that ran, "vec" or "scalar", NUL-terminated, truncated to form_cap; may be NULL. */
+int stn_op_compressor_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, int x_misalign, int in_place,
+                         float* y, float* gr_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form,
+                         size_t form_cap);
+/* host only, no device needed: kA and kR at rate_hz.  k: -expm1(-1000 / (ms rate)) in double; k32: the same rounded to fp32, what the
+ * GPU multiplies by.  Either may be NULL.  Refuses (STN_ERR_INVALID) what stn_set_compressor refuses, and a rate outside [8000, 192000]. */
+int stn_compressor_coefs(const stn_compressor* c, int rate_hz, double k[2], float k32[2]);
+/* host only: the static curve, makeup included: out_db[i] = in_db[i] - z(in_db[i]) + makeup_db, in double on the fp32 T, S, K, makeup */
+int stn_compressor_curve(const stn_compressor* c, int n, const double* in_db, double* out_db);
+/* host only: why stn_set_compressor would refuse c ("" when it would not), as stn_filter_error; rate_hz > 0 is checked as well, 0 is
+ * "no rate"; the string is the calling thread's until its next call */
+const char* stn_compressor_error(const stn_compressor* c, int rate_hz);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

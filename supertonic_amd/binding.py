@@ -204,6 +204,96 @@ def filter_geometry():
     return tuple(x.value for x in v)
 
 
+COMPRESSOR_FIELDS = ("threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "makeup_db")
+# the documented "speech" default: -24 dB, 3:1, a 6 dB knee, 5 ms attack, 120 ms release, no makeup
+COMPRESSOR_SPEECH = (-24.0, 3.0, 6.0, 5.0, 120.0, 0.0)
+COMPRESSOR_PRESETS = {"speech": COMPRESSOR_SPEECH}
+# what a spelling that leaves fields out fills them with (THRESHOLD and RATIO are always given there)
+_COMPRESSOR_REST = COMPRESSOR_SPEECH[2:]
+
+
+class StnCompressor(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in COMPRESSOR_FIELDS]
+
+
+def parse_compressor_spec(spec):
+    """A command-line compressor "THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]" (the speech default's knee 6, attack 5,
+    release 120 and makeup 0 when left out) -> the 6-tuple of floats.  ValueError naming what is wrong."""
+    parts = str(spec).split(":")
+    if not 2 <= len(parts) <= 6:
+        raise ValueError(f"compressor {spec!r}: expected THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]")
+    try:
+        nums = [float(v) for v in parts]
+    except ValueError:
+        raise ValueError(f"compressor {spec!r}: THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and MAKEUP_DB must be numbers") from None
+    return tuple(nums) + _COMPRESSOR_REST[len(nums) - 2:]
+
+
+def compressor_args(compressor, preset=None):
+    """A compressor argument -> the 6-tuple of floats (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db), or None for off
+    (None or False).  True is the "speech" default (-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB); a dict names
+    fields and takes the others from that default; a 6-tuple gives all six; a "THRESHOLD:RATIO[:...]" string is the command line's
+    spelling.  preset ("speech") stands for True.  ValueError naming the field for a malformed value or an unknown field or preset; the
+    numeric limits are the C ABI's (compressor_error, Engine.set_compressor)."""
+    if preset is not None:
+        if preset not in COMPRESSOR_PRESETS:
+            raise ValueError(f"compressor_preset {preset!r}: must be one of {', '.join(COMPRESSOR_PRESETS)}")
+        if compressor is None or compressor is False:
+            compressor = True
+    if compressor is None or compressor is False:
+        return None
+    if compressor is True:
+        return COMPRESSOR_PRESETS[preset or "speech"]
+    if isinstance(compressor, str):
+        return parse_compressor_spec(compressor)
+    if isinstance(compressor, dict):
+        unknown = set(compressor) - set(COMPRESSOR_FIELDS)
+        if unknown:
+            raise ValueError(f"compressor: unknown field {sorted(unknown)[0]!r} ({', '.join(COMPRESSOR_FIELDS)})")
+        vals = [compressor.get(n, d) for n, d in zip(COMPRESSOR_FIELDS, COMPRESSOR_SPEECH)]
+    elif isinstance(compressor, (tuple, list)) and len(compressor) == 6:
+        vals = list(compressor)
+    else:
+        raise ValueError(f"compressor: True, a dict of {', '.join(COMPRESSOR_FIELDS)}, or a 6-tuple of them, not {compressor!r}")
+    for name, v in zip(COMPRESSOR_FIELDS, vals):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"compressor: {name} must be a finite number, not {v!r}")
+    return tuple(float(v) for v in vals)
+
+
+def _compressor_struct(compressor):
+    c = compressor_args(compressor)
+    if c is None:
+        raise ValueError("compressor: a setting is needed here, not off")
+    return StnCompressor(*c)
+
+
+def compressor_error(compressor, rate_hz=0):
+    """Why Engine.set_compressor would refuse the setting (host only): "" when it would not; the message names the field."""
+    return load().stn_compressor_error(ctypes.byref(_compressor_struct(compressor)), int(rate_hz)).decode()
+
+
+def compressor_coefs(compressor, rate_hz):
+    """(k float64 [2]: kA, kR = -expm1(-1000 / (ms rate)); k32 float32 [2]: what the GPU multiplies by) at rate_hz (host only)."""
+    c = _compressor_struct(compressor)
+    k, k32 = np.zeros(2, np.float64), np.zeros(2, np.float32)
+    rc = load().stn_compressor_coefs(ctypes.byref(c), int(rate_hz), k, k32)
+    if rc < 0:
+        raise StnError(rc, compressor_error(compressor, rate_hz) or "stn_compressor_coefs failed")
+    return k, k32
+
+
+def compressor_curve(compressor, in_db):
+    """The static curve, makeup included: output level in dB at the input levels in_db (host only, float64)."""
+    c = _compressor_struct(compressor)
+    x = np.ascontiguousarray(np.atleast_1d(in_db), np.float64)
+    out = np.zeros(x.shape, np.float64)
+    rc = load().stn_compressor_curve(ctypes.byref(c), x.size, x, out)
+    if rc < 0:
+        raise StnError(rc, compressor_error(compressor) or "stn_compressor_curve failed")
+    return out
+
+
 class StnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"stn error {code}: {msg}")
@@ -458,6 +548,17 @@ def load():
     L.stn_filter_coefs.argtypes = [fp, ci, _f64p, _f32p]
     L.stn_filter_response.argtypes = [ci, fp, ci, ci, _f64p, _f64p]
     L.stn_dbg_filter_geometry.argtypes = [ctypes.POINTER(ci)] * 4
+    cpp = ctypes.POINTER(StnCompressor)
+    L.stn_set_compressor.argtypes = [vp, ci, cpp]
+    L.stn_get_compressor.argtypes = [vp, ctypes.POINTER(ci), cpp]
+    L.stn_group_set_compressor.argtypes = [vp, ci, cpp]
+    L.stn_batch_compressor.argtypes = [vp, vp]
+    L.stn_op_compressor.argtypes = [vp, ci, ci, ci, _f32p, cpp, _f32p]
+    L.stn_op_compressor_ex.argtypes = [vp, ci, ci, ci, _f32p, cpp, ci, ci, _f32p, vp, vp, vp, vp, vp, ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_compressor_error.argtypes = [cpp, ci]
+    L.stn_compressor_error.restype = ctypes.c_char_p
+    L.stn_compressor_coefs.argtypes = [cpp, ci, _f64p, _f32p]
+    L.stn_compressor_curve.argtypes = [cpp, ci, _f64p, _f64p]
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
@@ -576,6 +677,11 @@ class Group:
         """Filter chain of every rank (Engine.set_filters): the gathered rows are then the single engine's filtered rows."""
         n, arr = _filter_array(filters)
         self._ck(self._lib.stn_group_set_filters(self._g, n, arr))
+
+    def set_compressor(self, compressor=None):
+        """Compressor of every rank (Engine.set_compressor): the gathered rows are then the single engine's compressed rows."""
+        c = compressor_args(compressor)
+        self._ck(self._lib.stn_group_set_compressor(self._g, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
 
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
@@ -1070,6 +1176,53 @@ class Engine:
         ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
         self._ck(self._lib.stn_op_filter_ex(self._h, int(hz), rows, W, x, n, arr, int(x_misalign), o["y"], o["st_end"].ctypes.data,
                                             o["st_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
+        o["guard_ok"] = bool(ok.value)
+        o["form"] = form.value.decode()
+        return o
+
+    def set_compressor(self, compressor=None):
+        """Compress the dynamic range of every row of every fetch on the GPU, at the output rate, behind the filter chain and before
+        everything else (trimming, loudness, limiter, encoding, join): None or False = off (the default); True = the "speech" default;
+        a dict or 6-tuple as compressor_args takes them, e.g. {"threshold_db": -20, "ratio": 4}.  StnError naming the field for a value
+        outside the limits (include/stn.h, "compressor")."""
+        c = compressor_args(compressor)
+        self._ck(self._lib.stn_set_compressor(self._h, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
+
+    def get_compressor(self):
+        """The setting in force: the 6-tuple (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db), or None when off."""
+        on, c = ctypes.c_int(), StnCompressor()
+        self._ck(self._lib.stn_get_compressor(self._h, ctypes.byref(on), ctypes.byref(c)))
+        return tuple(getattr(c, n) for n in COMPRESSOR_FIELDS) if on.value else None
+
+    def batch_compressor(self):
+        """Per row of the finished batch, the largest reduction in dB the compressor applied over the row's valid samples (float32 [B];
+        zeros while it is off)."""
+        out = np.zeros(self.batch_dims()[0], np.float32)
+        self._ck(self._lib.stn_batch_compressor(self._h, out.ctypes.data))
+        return out
+
+    def op_compressor(self, x, hz, compressor):
+        """rows x W fp32 at hz through the compressor on the GPU -> y [rows, W] float32, every row from zero state."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        y = np.empty_like(x)
+        self._ck(self._lib.stn_op_compressor(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_compressor_struct(compressor)), y))
+        return y
+
+    def op_compressor_ex(self, x, hz, compressor, x_misalign=0, in_place=0):
+        """op_compressor with its scratch laid open -> dict: y, gr_db (yL) [rows, W]; s1_end, s1_start, s2_end, s2_start [rows, Ks] (per
+        chunk of 32 samples: y1 at its end from zero, y1 at its start after the scan, yL at its end from zero, yL at its start; the
+        scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y came back whole); form
+        ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y over x on the device."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        Ks = (W + 31) // 32
+        o = dict(y=np.empty_like(x), gr_db=np.empty_like(x))
+        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
+            o[k] = np.empty((rows, Ks), np.float32)
+        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_compressor_ex(self._h, int(hz), rows, W, x, ctypes.byref(_compressor_struct(compressor)), int(x_misalign),
+                                                int(in_place), o["y"], o["gr_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
+                                                o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
         o["guard_ok"] = bool(ok.value)
         o["form"] = form.value.decode()
         return o

@@ -498,6 +498,52 @@ int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int
     if (biquads_per_section) *biquads_per_section = 2;
     return STN_OK;
 }
+int stn_set_compressor(stn_handle* h, int on, const stn_compressor* c) { STN_TRY(h, { h->eng->set_compressor(on != 0, c); }) }
+int stn_get_compressor(const stn_handle* h, int* on, stn_compressor* out) {
+    if (!h) return STN_ERR_INVALID;
+    if (on) *on = h->eng->compressor_on() ? 1 : 0;
+    if (out) *out = h->eng->compressor();
+    return STN_OK;
+}
+int stn_batch_compressor(stn_handle* h, float* max_reduction_db) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_compressor(max_reduction_db); })
+}
+int stn_op_compressor(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_compressor: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 h->eng->op_compressor(hz, rows, W, x, *c, y, nullptr); })
+}
+int stn_op_compressor_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, int x_misalign, int in_place, float* y,
+                         float* gr_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_compressor_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_compressor_ex: x_misalign and in_place must be 0 or 1");
+                 stn::Engine::CpProbe p;
+                 p.x_misalign = x_misalign; p.in_place = in_place; p.gr = gr_db;
+                 p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
+                 h->eng->op_compressor(hz, rows, W, x, *c, y, &p);
+                 if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0;
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
+const char* stn_compressor_error(const stn_compressor* c, int rate_hz) {
+    static thread_local std::string why;
+    why = stn::compressor_check(c);
+    if (why.empty() && rate_hz < 0) why = "compressor: rate_hz must not be negative";
+    if (why.empty() && rate_hz > 0) why = stn::rate_check("compressor", rate_hz);
+    return why.c_str();
+}
+int stn_compressor_coefs(const stn_compressor* c, int rate_hz, double k[2], float k32[2]) {
+    if (rate_hz <= 0 || *stn_compressor_error(c, rate_hz)) return STN_ERR_INVALID;
+    const double d[2] = {stn::compressor_k(c->attack_ms, rate_hz), stn::compressor_k(c->release_ms, rate_hz)};
+    for (int i = 0; i < 2; ++i) {
+        if (k) k[i] = d[i];
+        if (k32) k32[i] = (float)d[i];
+    }
+    return STN_OK;
+}
+int stn_compressor_curve(const stn_compressor* c, int n, const double* in_db, double* out_db) {
+    if (n < 0 || (n > 0 && (!in_db || !out_db)) || !stn::compressor_check(c).empty()) return STN_ERR_INVALID;
+    for (int i = 0; i < n; ++i) out_db[i] = stn::compressor_curve(*c, in_db[i]);
+    return STN_OK;
+}
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
 int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {

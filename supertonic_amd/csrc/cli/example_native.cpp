@@ -13,7 +13,10 @@
 // segments; one GPU only), --max-pause MS (with --trim-silence: pauses inside an utterance longer than MS shortened to MS), --trim-keep MS (kept in front of and behind the speech; default 20), --trim-fade MS (fade over a cut edge; default 5),
 // --filter TYPE:FREQ[:Q[:GAIN_DB]] (repeatable, up to 8: every utterance through that biquad on the GPU, after the resampler and before
 // everything else; TYPE one of highpass, lowpass, notch, peak, lowshelf, highshelf; Q 0.7071 when left out), --filter-preset
-// {rumble,telephone} (a high-pass at 80 Hz; the 300 to 3400 Hz telephone band, in front of any --filter).
+// {rumble,telephone} (a high-pass at 80 Hz; the 300 to 3400 Hz telephone band, in front of any --filter),
+// --compressor THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]] (every utterance through the dynamic range compressor on the
+// GPU, behind the filters and before everything else; knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB when left out),
+// --compressor-preset speech (-24 dB, 3:1 and those).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -106,6 +109,11 @@ int main(int argc, char* argv[]) {
             const std::string why = filterPreset(argv[++i], p);
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.filters.insert(opts.filters.begin(), p.begin(), p.end());
+        }
+        else if ((a == "--compressor" || a == "--compressor-preset") && more) {  // the dynamic range compressor every utterance goes through on the GPU
+            const std::string why = a == "--compressor" ? parseCompressorSpec(argv[++i], opts.compressor) : compressorPreset(argv[++i], opts.compressor);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+            opts.compressor_on = true;
         }
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }

@@ -95,6 +95,13 @@ struct FilterTable {
     std::vector<LoudTable> pass;
 };
 void filter_table(int hz, int n, const stn_filter* f, FilterTable& t);  // fills t (no device copies); throws what filter_check refuses
+// The compressor's host arithmetic (engine_compressor.cpp).  compressor_check: why c is refused, naming the field, or "" (no limit
+// depends on the rate); compressor_k: k = -expm1(-1000 / (ms rate)) in double; compressor_curve: the static curve in double on the
+// fp32-rounded T, S, K and makeup; compressor_table: coefficients and scan powers at hz (no device copy), throws what the check refuses
+std::string compressor_check(const stn_compressor* c);
+double compressor_k(float ms, int rate_hz);
+double compressor_curve(const stn_compressor& c, double in_db);
+void compressor_table(int hz, const stn_compressor& c, CompTable& t);
 
 class Engine;
 // One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
@@ -449,6 +456,23 @@ class Engine {
     // rows x W fp32 (host) at hz through f[0 .. n) -> y (host)
     void op_filter(int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y, FlProbe* probe);
 
+    // ---- compressor (engine_compressor.cpp; include/stn.h "compressor"): off is the default (every fetch path is
+    // then exactly the one without it).  On, out_source() delivers the rows at the output rate compressed in place in the fetch scratch,
+    // behind the filter chain (kernels_compressor.hip), and everything behind it runs on those.
+    void set_compressor(bool on, const stn_compressor* c);
+    bool compressor_on() const { return cp_on_; }
+    const stn_compressor& compressor() const { return cp_set_; }
+    void batch_compressor(float* max_reduction_db);
+    // the op-level probe: gr [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
+    struct CpProbe {
+        int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
+        float *gr = nullptr, *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
+        bool guard_ok = false;   // out
+        const char* form = "";   // out
+    };
+    // rows x W fp32 (host) at hz through the compressor c -> y (host)
+    void op_compressor(int hz, int rows, int W, const float* x, const stn_compressor& c, float* y, CpProbe* probe);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -744,7 +768,30 @@ class Engine {
     // probe (or null): the states of every pass read out, the state buffer poisoned before each
     void fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const FlScratch& sc, float* y, FlProbe* probe);
     void fl_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) through the chain in force into y (may be x)
-    bool out_in_scratch() const { return resample_on() || filter_on(); }  // out_source() returns fetch scratch (row stride Wo), not b.wav
+    // ---- compressor (engine_compressor.cpp)
+    bool cp_on_ = false;
+    stn_compressor cp_set_{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};  // the setting in force (the "speech" default until one is set)
+    uint64_t cp_gen_ = 0;              // bumped by every change of the setting: part of EdKey, as fl_gen_
+    CompTable cp_, op_cp_;             // the tables at the output rate, and of op_compressor (device copies owned here)
+    DevBuf cp_buf_;                    // fetch-time scratch of the five launches
+    // per chunk y1 and yL (end values, then start values) and the maximum of yL, per row that maximum and the valid length
+    struct CpScratch { float *s1, *s2, *cmax, *rmax; int64_t* n; size_t bytes; };
+    static CpScratch cp_layout(char* base, int64_t rows, int64_t W);
+    std::vector<int64_t> cp_n_; const int64_t* cp_n_ptr_ = nullptr;  // the lengths cp_buf_ holds
+    // what the row maxima in cp_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
+    struct CpKey {
+        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, cp = 0; int64_t Wo = 0; const void* buf = nullptr;
+        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf; }
+    };
+    CpKey cp_key_; bool cp_valid_ = false;
+    void cp_prepare(CompTable& t, int hz, const stn_compressor& c);
+    void cp_release();
+    // the five launches and the row maxima on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read
+    // out where the sequence leaves it
+    void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
+    CpScratch cp_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) compressed into y (may be x)
+    // out_source() returns fetch scratch (row stride Wo), not b.wav
+    bool out_in_scratch() const { return resample_on() || filter_on() || compressor_on(); }
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
@@ -767,8 +814,9 @@ class Engine {
         uint64_t seq = 0; int hz = 0; float db = 0, keep = 0, fade = 0; int64_t Wo = 0; const void* buf = nullptr;
         float mp = 0;  // max_pause_ms of the cuts held beside the edges; 0: none
         uint64_t fl = 0;  // fl_gen_ of the filter chain the rows went through
+        uint64_t cp = 0;  // cp_gen_ of the compressor setting they went through
         bool operator==(const EdKey& o) const {
-            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl;
+            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp;
         }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;

@@ -260,6 +260,29 @@ std::string filterPreset(const std::string& name, std::vector<stn_filter>& out) 
     return "";
 }
 
+std::string compressorPreset(const std::string& name, stn_compressor& c) {
+    if (name != "speech") return "compressor-preset '" + name + "': speech";
+    c = stn_compressor{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};
+    return "";
+}
+
+std::string parseCompressorSpec(const std::string& spec, stn_compressor& c) {
+    std::vector<std::string> parts;
+    size_t a = 0, p;
+    while ((p = spec.find(':', a)) != std::string::npos) { parts.push_back(spec.substr(a, p - a)); a = p + 1; }
+    parts.push_back(spec.substr(a));
+    const std::string who = "compressor '" + spec + "': ";
+    if (parts.size() < 2 || parts.size() > 6) return who + "expected THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]";
+    (void)compressorPreset("speech", c);  // what the fields left out take
+    float* dst[6] = {&c.threshold_db, &c.ratio, &c.knee_db, &c.attack_ms, &c.release_ms, &c.makeup_db};
+    for (size_t i = 0; i < parts.size(); ++i) {
+        char* end = nullptr;
+        *dst[i] = std::strtof(parts[i].c_str(), &end);
+        if (parts[i].empty() || *end) return who + "THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and MAKEUP_DB must be numbers";
+    }
+    return "";
+}
+
 std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool use_gpu, const EngineOptions& opts) {
     if (!use_gpu) throw std::runtime_error("CPU mode is not supported: this engine runs on MI355X only");
     const char* dt_name = opts.dtype == STN_DTYPE_BF16 ? "bf16" : opts.dtype == STN_DTYPE_F16 ? "fp16" : "fp32";
@@ -317,6 +340,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         if (opts.output_rate) applied("output rate", grp ? stn_group_set_output_rate(grp, opts.output_rate) : stn_set_output_rate(h, opts.output_rate));
         // (after the rate: a chain is checked against the output rate in force)
         if (nf) applied("filters", grp ? stn_group_set_filters(grp, nf, opts.filters.data()) : stn_set_filters(h, nf, opts.filters.data()));
+        if (opts.compressor_on) applied("compressor", grp ? stn_group_set_compressor(grp, 1, &opts.compressor) : stn_set_compressor(h, 1, &opts.compressor));
         if (!std::isnan(opts.loudness_lufs))
             applied("loudness", grp ? stn_group_set_loudness(grp, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs)
                                     : stn_set_loudness(h, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs));

@@ -79,6 +79,9 @@ struct EngineOptions {
     std::vector<stn_filter> filters;  // every utterance through this chain of up to STN_MAX_FILTERS biquads on the GPU, after the resampler
                                    // and before everything above (stn_set_filters); empty: off.  CLI --filter TYPE:FREQ[:Q[:GAIN_DB]]
                                    // (repeatable) and --filter-preset {rumble,telephone}
+    bool compressor_on = false;    // every utterance through the dynamic range compressor on the GPU, behind the filters and before everything
+    stn_compressor compressor{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};  // above (stn_set_compressor); these are the "speech" preset's values.
+                                   // CLI --compressor THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]] and --compressor-preset speech
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
@@ -89,6 +92,11 @@ struct EngineOptions {
 // out, or why not.  The numeric limits are stn_set_filters' own.
 std::string parseFilterSpec(const std::string& spec, stn_filter& f);
 std::string filterPreset(const std::string& name, std::vector<stn_filter>& out);
+// The command line's compressor arguments (host only).  parseCompressorSpec: "THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]"
+// (the speech preset's knee 6 dB, attack 5 ms, release 120 ms and makeup 0 dB when left out) into c, or why not.  compressorPreset:
+// "speech" (-24 dB, 3:1 and those) into c, or why not.  The numeric limits are stn_set_compressor's own.
+std::string parseCompressorSpec(const std::string& spec, stn_compressor& c);
+std::string compressorPreset(const std::string& name, stn_compressor& c);
 
 class TextToSpeech {
    public:

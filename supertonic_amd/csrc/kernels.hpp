@@ -546,6 +546,28 @@ void launch_filter_write(hipStream_t s, const float* x, int64_t rows, int64_t W,
 // "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
 const char* filter_staging_form(const float* x, const float* y, int64_t W);
 
+// Fetch-time dynamic range compressor (kernels_compressor.hip; the limits, the tables and the sequence are engine_compressor.cpp;
+// DESIGN.md section 20).  Every row W long, chunks of LO_CHUNK samples from sample 0, workgroups of LO_WG chunks, scan tiles of LO_SCAN.
+struct CompCoef { float T, S, K, kA, kR, makeup; };  // threshold dB, 1 / ratio - 1, knee dB, attack and release k, makeup dB (fp32)
+struct CompTable {
+    int hz = 0;
+    float set[6] = {};                // the stn_compressor fields the table was made from
+    CompCoef coef{};
+    std::vector<double> pw;           // host copy, [2][LO_SCAN]: D^(i+1) then E^(i+1), D = (1 - kR)^LO_CHUNK, E = (1 - kA)^LO_CHUNK
+    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
+};
+// pass 1: s1[row][k] = y1 at the end of chunk k from zero.  pass 2: s1 = y1 at the chunk's start -> s2[row][k] = yL at its end from
+// zero.  pass 3: s1, s2 = the start values -> y (row stride W; may be x), gr (rows x W yL, or null), cmax[row][k] = max of yL over the
+// chunk's samples below n[row] (device; null: W).  The staging form of all three is that of (x, y, W).
+void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const CompTable& t, float* s1,
+                              float* s2, float* y, float* gr, float* cmax);
+// in place: st[row][k] end values from zero -> the chunks' start values; stage 1 the (max, x) scan, stage 2 the linear one
+void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const CompTable& t, float* st);
+// out[row] = max_k cmax[row][k]
+void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const float* cmax, float* out);
+// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
+const char* compressor_staging_form(const float* x, const float* y, int64_t W);
+
 // Look-ahead peak limiter behind the loudness gain (kernels_limiter.hip; the setting, the window and the scratch are engine_limiter.cpp;
 // DESIGN.md section 15).  rows x W fp32 (row stride W) with row spans n[rows] (device, <= W) and gains gain[rows] (device; null: 1) ->
 // y (rows x W fp32, row stride W, not x): row b times gain[b], turned down around every sample above c so that |y| <= c, the curve s

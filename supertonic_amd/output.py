@@ -30,6 +30,7 @@ def _peak_mode(v):
 _PARSE = {
     "output_rate": int,
     "filters": lambda v: binding.filter_args(None if v is False else v),
+    "compressor": lambda v: binding.compressor_args(v) or False,
     "loudness": lambda v: v is not False and _loudness(v),
     "trim_silence": lambda v: v is not False and binding.silence_trim_args(v)[1:],
     "max_pause": _switched(binding.pause_limit_args),
@@ -48,6 +49,9 @@ class OutputSettings:
     filters       a chain of up to 8 biquads every utterance goes through, after the resampler and before everything below
                   (stn_set_filters): a list as binding.filter_args takes it, e.g. [("highpass", 80)]; the numeric limits are checked by
                   the engine against the output rate in force.  Normalized: a tuple of (type, freq_hz, q, gain_db).  Off: False or [], ().
+    compressor    the dynamic range of every utterance compressed, behind the chain and before everything below (stn_set_compressor): True
+                  (the "speech" default: -24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB), a dict of those fields or
+                  a 6-tuple, as binding.compressor_args takes them.  Normalized: the 6-tuple of floats.  Off: False.
     loudness      every utterance normalized to this BS.1770-4 integrated loudness, measured at the output rate (stn_set_loudness): a
                   target in LUFS (peak ceiling -1 dBFS) or (target, ceiling dBFS).  Normalized: (target, ceiling).  Off: False.
     trim_silence  leading and trailing silence trimmed by level (stn_set_silence_trim): top_db (20 ms kept, 5 ms fade) or
@@ -65,6 +69,7 @@ class OutputSettings:
     max_pause: object = None
     limiter: object = None
     peak_mode: object = None
+    compressor: object = None  # (declared last: OFF and positional construction keep their seven fields; applied behind filters)
 
     @classmethod
     def parse(cls, **kw):
@@ -95,6 +100,8 @@ class OutputSettings:
             engine.set_output_rate(self.output_rate)
         if self.filters:
             engine.set_filters(self.filters)
+        if self.compressor is not None:
+            engine.set_compressor(self.compressor or None)
         if self.loudness is not None:
             engine.set_loudness(*(self.loudness or (None,)))
         if self.trim_silence is not None:
@@ -117,4 +124,6 @@ class OutputSettings:
             OutputSettings(**{k: getattr(base, k) for k in self.kwargs()}).apply(engine)
 
 
+# OFF leaves compressor unset (a base that does not name the field compares equal after over(OFF)); ALL_OFF names every field
 OutputSettings.OFF = OutputSettings(0, (), False, False, False, False, "sample")
+OutputSettings.ALL_OFF = dataclasses.replace(OutputSettings.OFF, compressor=False)

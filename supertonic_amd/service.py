@@ -31,7 +31,7 @@ BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
-              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None):
+              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -39,13 +39,18 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     at peak_ceiling dBFS.  limiter_ms, peak_mode ("sample" or "true"): OutputSettings' limiter and peak_mode; they act on the loudness
     gain, so without loudness they (and peak_ceiling) are validated and dropped.  trim_silence: top_db or (top_db, keep_ms, fade_ms), no
     bool.  max_pause_ms: without trim_silence, validated and dropped likewise.  filters: a list as binding.filter_args takes it, [] =
-    off, checked against the request's rate.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
+    off, checked against the request's rate.  compressor: True, a dict or a 6-tuple as binding.compressor_args takes it, False = off,
+    checked against the engine's limits.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
     loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
     if why:
         raise ValueError(why)
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, loudness=None if loudness is None else (loudness, peak_ceiling),
+    comp = None if compressor is None else (binding.compressor_args(compressor) or False)
+    why = comp and binding.compressor_error(comp, int(sample_rate or model_rate))
+    if why:
+        raise ValueError(why)
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, compressor=comp, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
@@ -246,6 +251,11 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                 "highshelf, freq (Hz), q (0.7071), gain_db (0)}; null: off.")
         filter_preset: Optional[str] = Field(None, description="A named chain in front of filters: 'rumble' (high-pass at 80 Hz) or 'telephone' "
                                                                "(300 to 3400 Hz, 4th-order Butterworth).")
+        compressor: Optional[Union[bool, dict]] = Field(None, description="Dynamic range compressor every utterance goes through on the GPU, behind "
+                                                                          "the filters and before everything else: true (the speech default: "
+                                                                          "-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB) or "
+                                                                          "{threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db}, the "
+                                                                          "fields left out from that default; false: off; null: the server's.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -293,6 +303,16 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             if why:
                 raise HTTPException(status_code=400, detail=f"filters: {why}")
             extra["filters"] = list(chain)
+        comp = None
+        if req.compressor is not None:
+            try:
+                comp = binding.compressor_args(req.compressor) or False
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            why = binding.compressor_error(comp, sr) if comp else ""
+            if why:
+                raise HTTPException(status_code=400, detail=why)
+            extra["compressor"] = comp
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
@@ -317,7 +337,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                          trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                         max_pause_ms=req.max_pause_ms, filters=chain)
+                                         max_pause_ms=req.max_pause_ms, filters=chain, compressor=comp)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:
