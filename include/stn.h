@@ -684,6 +684,73 @@ int stn_compressor_curve(const stn_compressor* c, int n, const double* in_db, do
  * "no rate"; the string is the calling thread's until its next call */
 const char* stn_compressor_error(const stn_compressor* c, int rate_hz);
 
+/* ---- de-esser -----------------------------------------------------------------------------------------
+ * A split-band de-esser applied to every row of every fetch, on the GPU, at the output rate: the compressor's detector listens to a
+ * band of the signal (everything above freq_hz, a 4th-order Butterworth high-pass) and its gain turns down that band alone (split) or
+ * the whole signal (wide), and only while a sibilant happens.  The filter chain is linear and cannot do that; the compressor detects on
+ * the full band, where a vowel hides the "s".  Off is the default: every fetch is then byte for byte the one without the feature, and
+ * no de-esser launch runs.
+ * Order of the output stage: native rows -> resample (if a rate is set) -> filter chain -> DE-ESSER -> compressor -> silence edges /
+ * pause cuts -> loudness measurement -> gain / limiter / true peak -> encoding store / join.  Everything behind it sees the de-essed
+ * signal: every fetch path and every report (stn_batch_compressor, _loudness, _silence_edges, _pauses, _limiter, _true_peak,
+ * stn_batch_join_loudness).  stn_batch_wav_device_ptr, stn_batch_fetch_latent, the batch's own waveform, the captured pipeline and the
+ * graph key are untouched: the de-essed rows live in fetch scratch, and changing the setting drops or re-captures no graph.
+ * Each row is de-essed on its own, from zero state at its sample 0, over the row's whole width W_out (padding included).  Per sample,
+ * all values fp32:
+ *   band           h  = HP4(x): two RBJ high-pass biquads at freq_hz with q = (float)0.54119610 and (float)1.30656296 (4th-order
+ *                  Butterworth), designed in double and rounded to fp32 exactly as stn_filter_coefs does, run as ONE section pass of
+ *                  the chain's 4-state system (the arithmetic of "filter chain", operation for operation)
+ *   level          hG = 20 log10(max(|h|, 1e-6))
+ *   gain computer  z  = min(range_db, zc(hG)),  zc the compressor's curve with T = threshold_db, S = 1 / ratio - 1, K = knee_db
+ *   detector       y1 = max(z, fma(-kR, y1, y1));  yL = fma(kA, y1 - yL, yL),  k as stn_compressor_coefs forms it
+ *   output         g  = 10^(-yL / 20)
+ *                  STN_DEESS_SPLIT:  y = fma(-(1 - g), h, x)   only the band is turned down; where g == 1 (yL == 0) y is x itself,
+ *                                    bit for bit, the sign of a zero included
+ *                  STN_DEESS_WIDE:   y = x g
+ * The reference of every numeric claim is exactly this in float64 on the same fp32-rounded coefficients.  Identities:
+ *   the delivered fp32 row == stn_op_deesser(the fp32 row delivered with the de-esser off), bit for bit;
+ *   a row's first n samples do not depend on W, the batch or the row's place in it;
+ *   a joined fetch == the host join of the per-row fetch, byte for byte, as without the de-esser;
+ *   in split mode a row whose band never reaches the knee is delivered bit for bit as without the feature.
+ * Refused with STN_ERR_INVALID and a message that names the field: freq_hz outside [2000, 12000], above 0.45 x the output rate or below
+ * the output rate / 2400 (the chain's corners for a high-pass with q in [0.5, 1.5]); threshold_db outside [-60, 0], ratio outside
+ * [1, 20], knee_db outside [0, 24], attack_ms outside [0.1, 300], release_ms outside [10, 3000], range_db outside [1, 24]; an unknown
+ * mode; a non-finite field.  The previous setting stays in force.  stn_set_output_rate to a rate at which the de-esser in force breaks
+ * a limit is refused the same way, and the rate stays as it was (the speech default is refused at 8 kHz).  DESIGN.md section 21 has the
+ * decomposition and the measurements. */
+#define STN_DEESS_SPLIT 0
+#define STN_DEESS_WIDE 1
+typedef struct stn_deesser { float freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db; int mode; } stn_deesser;
+/* on = 0: off, c may then be NULL (the values last set stay readable) */
+int stn_set_deesser(stn_handle* h, int on, const stn_deesser* c);
+/* either may be NULL; *out: the values last set (before the first set, the speech default: 5500 Hz, -30 dB, 4:1, knee 6 dB, 1 ms,
+ * 40 ms, range 12 dB, split) */
+int stn_get_deesser(const stn_handle* h, int* on, stn_deesser* out);
+/* per row of the finished batch: the maximum of yL, the reduction in dB, over the row's valid samples (its reported duration at the
+ * output rate); 0 for every row while the de-esser is off */
+int stn_batch_deesser(stn_handle* h, float* max_reduction_db);
+/* op-level: rows x W fp32 (host) at hz through the de-esser c -> y [rows][W] (host).  1 <= rows <= 65535. */
+int stn_op_deesser(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, float* y);
+/* The same with its scratch laid open (the kernel tests).  Eight launches on chunks of 32 samples (Ks = (W + 31) / 32 per row): the
+ * band's state of every chunk from zero (st_end) and its scan in double (st_start: the state at every chunk's start; both
+ * [rows][Ks][4] = s1 s2 t1 t2, as stn_op_filter_ex); y1 of every chunk from zero (s1_end), the (max, x) scan (s1_start), yL of every
+ * chunk from zero on its true y1 (s2_end), the linear scan (s2_start; these four [rows][Ks]); the write pass from every start value:
+ * y, band [rows][W] = h and gr_db [rows][W] = yL; and the row maxima.  Each of band, gr_db and the six state arrays may be NULL.  The
+ * device's scratch, band and gr_db are filled with the quiet NaN 0x7FC00000 before the first launch, and x and y lie with 64 poisoned
+ * floats in front of and behind them: *guard_ok = 1 when all of those came back untouched.  x_misalign, in_place, form: as
+ * stn_op_compressor_ex. */
+int stn_op_deesser_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, int x_misalign, int in_place, float* y,
+                      float* band, float* gr_db, float* st_end, float* st_start, float* s1_end, float* s1_start, float* s2_end,
+                      float* s2_start, int* guard_ok, char* form, size_t form_cap);
+/* host only, no device needed: the band's two sections at rate_hz, b0 b1 b2 a1 a2 each.  c: the double design; c32: the same rounded
+ * to fp32, what the GPU multiplies by.  Either may be NULL.  Refuses (STN_ERR_INVALID) what stn_set_deesser refuses at that rate. */
+int stn_deesser_band(const stn_deesser* c, int rate_hz, double c10[10], float c32[10]);
+/* host only: kA and kR at rate_hz, as stn_compressor_coefs */
+int stn_deesser_coefs(const stn_deesser* c, int rate_hz, double k[2], float k32[2]);
+/* host only: why stn_set_deesser would refuse c at an output rate of rate_hz ("" when it would not); rate_hz = 0 is "no rate": the
+ * limits that do not depend on it; the string is the calling thread's until its next call */
+const char* stn_deesser_error(const stn_deesser* c, int rate_hz);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

@@ -294,6 +294,107 @@ def compressor_curve(compressor, in_db):
     return out
 
 
+DEESSER_FIELDS = ("freq_hz", "threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "range_db", "mode")
+DEESSER_MODES = ("split", "wide")  # STN_DEESS_SPLIT, STN_DEESS_WIDE
+# the documented "speech" default: 5500 Hz, -30 dB, 4:1, a 6 dB knee, 1 ms attack, 40 ms release, at most 12 dB, on the band alone
+DEESSER_SPEECH = (5500.0, -30.0, 4.0, 6.0, 1.0, 40.0, 12.0, "split")
+DEESSER_PRESETS = {"speech": DEESSER_SPEECH}
+_DEESSER_SPELLING = "FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]"
+
+
+class StnDeesser(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in DEESSER_FIELDS[:7]] + [("mode", ctypes.c_int)]
+
+
+def _deesser_mode(v):
+    if isinstance(v, str) and v in DEESSER_MODES:
+        return v
+    if not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 0 <= int(v) < len(DEESSER_MODES):
+        return DEESSER_MODES[int(v)]
+    raise ValueError(f"deesser: mode must be one of {', '.join(DEESSER_MODES)}, not {v!r}")
+
+
+def parse_deesser_spec(spec):
+    """A command-line de-esser "FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]" (the speech default's values for
+    what is left out; MODE split or wide) -> the 8-tuple.  ValueError naming what is wrong."""
+    parts = str(spec).split(":")
+    if not 2 <= len(parts) <= 8:
+        raise ValueError(f"deesser {spec!r}: expected {_DEESSER_SPELLING}")
+    try:
+        nums = [float(v) for v in parts[:7]]
+    except ValueError:
+        raise ValueError(f"deesser {spec!r}: FREQ, THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and RANGE_DB must be numbers") from None
+    if len(parts) == 8 and parts[7] not in DEESSER_MODES:
+        raise ValueError(f"deesser {spec!r}: MODE must be one of {', '.join(DEESSER_MODES)}")
+    return tuple(nums) + DEESSER_SPEECH[len(nums):7] + (parts[7] if len(parts) == 8 else DEESSER_SPEECH[7],)
+
+
+def deesser_args(deesser, preset=None):
+    """A de-esser argument -> the 8-tuple (freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db as floats, mode "split"
+    or "wide"), or None for off (None or False).  True is the "speech" default (5500 Hz, -30 dB, 4:1, knee 6 dB, attack 1 ms, release
+    40 ms, range 12 dB, split); a dict names fields and takes the others from that default; an 8-tuple gives all eight (mode by name, or
+    0 / 1); a "FREQ:THRESHOLD[:...]" string is the command line's spelling.  preset ("speech") stands for True.  ValueError naming the
+    field for a malformed value or an unknown field or preset; the numeric limits are the C ABI's (deesser_error, Engine.set_deesser)."""
+    if preset is not None:
+        if preset not in DEESSER_PRESETS:
+            raise ValueError(f"deesser_preset {preset!r}: must be one of {', '.join(DEESSER_PRESETS)}")
+        if deesser is None or deesser is False:
+            deesser = True
+    if deesser is None or deesser is False:
+        return None
+    if deesser is True:
+        return DEESSER_PRESETS[preset or "speech"]
+    if isinstance(deesser, str):
+        return parse_deesser_spec(deesser)
+    if isinstance(deesser, dict):
+        unknown = set(deesser) - set(DEESSER_FIELDS)
+        if unknown:
+            raise ValueError(f"deesser: unknown field {sorted(unknown)[0]!r} ({', '.join(DEESSER_FIELDS)})")
+        vals = [deesser.get(n, d) for n, d in zip(DEESSER_FIELDS, DEESSER_SPEECH)]
+    elif isinstance(deesser, (tuple, list)) and len(deesser) == 8:
+        vals = list(deesser)
+    else:
+        raise ValueError(f"deesser: True, a dict of {', '.join(DEESSER_FIELDS)}, or an 8-tuple of them, not {deesser!r}")
+    for name, v in zip(DEESSER_FIELDS[:7], vals):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"deesser: {name} must be a finite number, not {v!r}")
+    return tuple(float(v) for v in vals[:7]) + (_deesser_mode(vals[7]),)
+
+
+def _deesser_struct(deesser):
+    c = deesser_args(deesser)
+    if c is None:
+        raise ValueError("deesser: a setting is needed here, not off")
+    return StnDeesser(*c[:7], DEESSER_MODES.index(c[7]))
+
+
+def deesser_error(deesser, rate_hz=0):
+    """Why Engine.set_deesser would refuse the setting at an output rate of rate_hz (host only; 0: the limits that need no rate): ""
+    when it would not; the message names the field."""
+    return load().stn_deesser_error(ctypes.byref(_deesser_struct(deesser)), int(rate_hz)).decode()
+
+
+def deesser_band(deesser, rate_hz):
+    """(c float64 [2, 5], c32 float32 [2, 5]): the band's two high-pass sections b0 b1 b2 a1 a2 at rate_hz, the double design and what
+    the GPU multiplies by (host only)."""
+    s = _deesser_struct(deesser)
+    c, c32 = np.zeros(10, np.float64), np.zeros(10, np.float32)
+    rc = load().stn_deesser_band(ctypes.byref(s), int(rate_hz), c, c32)
+    if rc < 0:
+        raise StnError(rc, deesser_error(deesser, rate_hz) or "stn_deesser_band failed")
+    return c.reshape(2, 5), c32.reshape(2, 5)
+
+
+def deesser_coefs(deesser, rate_hz):
+    """(k float64 [2]: kA, kR = -expm1(-1000 / (ms rate)); k32 float32 [2]: what the GPU multiplies by) at rate_hz (host only)."""
+    s = _deesser_struct(deesser)
+    k, k32 = np.zeros(2, np.float64), np.zeros(2, np.float32)
+    rc = load().stn_deesser_coefs(ctypes.byref(s), int(rate_hz), k, k32)
+    if rc < 0:
+        raise StnError(rc, deesser_error(deesser, rate_hz) or "stn_deesser_coefs failed")
+    return k, k32
+
+
 class StnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"stn error {code}: {msg}")
@@ -559,6 +660,17 @@ def load():
     L.stn_compressor_error.restype = ctypes.c_char_p
     L.stn_compressor_coefs.argtypes = [cpp, ci, _f64p, _f32p]
     L.stn_compressor_curve.argtypes = [cpp, ci, _f64p, _f64p]
+    dsp = ctypes.POINTER(StnDeesser)
+    L.stn_set_deesser.argtypes = [vp, ci, dsp]
+    L.stn_get_deesser.argtypes = [vp, ctypes.POINTER(ci), dsp]
+    L.stn_group_set_deesser.argtypes = [vp, ci, dsp]
+    L.stn_batch_deesser.argtypes = [vp, vp]
+    L.stn_op_deesser.argtypes = [vp, ci, ci, ci, _f32p, dsp, _f32p]
+    L.stn_op_deesser_ex.argtypes = [vp, ci, ci, ci, _f32p, dsp, ci, ci, _f32p] + [vp] * 8 + [ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_deesser_error.argtypes = [dsp, ci]
+    L.stn_deesser_error.restype = ctypes.c_char_p
+    L.stn_deesser_band.argtypes = [dsp, ci, _f64p, _f32p]
+    L.stn_deesser_coefs.argtypes = [dsp, ci, _f64p, _f32p]
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
@@ -682,6 +794,11 @@ class Group:
         """Compressor of every rank (Engine.set_compressor): the gathered rows are then the single engine's compressed rows."""
         c = compressor_args(compressor)
         self._ck(self._lib.stn_group_set_compressor(self._g, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
+
+    def set_deesser(self, deesser=None):
+        """De-esser of every rank (Engine.set_deesser): the gathered rows are then the single engine's de-essed rows."""
+        c = deesser_args(deesser)
+        self._ck(self._lib.stn_group_set_deesser(self._g, int(c is not None), ctypes.byref(_deesser_struct(c)) if c else None))
 
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
@@ -1223,6 +1340,56 @@ class Engine:
         self._ck(self._lib.stn_op_compressor_ex(self._h, int(hz), rows, W, x, ctypes.byref(_compressor_struct(compressor)), int(x_misalign),
                                                 int(in_place), o["y"], o["gr_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
                                                 o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
+        o["guard_ok"] = bool(ok.value)
+        o["form"] = form.value.decode()
+        return o
+
+    def set_deesser(self, deesser=None):
+        """Turn down the sibilants of every row of every fetch on the GPU, at the output rate, behind the filter chain and in front of the
+        compressor and everything else: None or False = off (the default); True = the "speech" default; a dict or 8-tuple as deesser_args
+        takes them, e.g. {"freq_hz": 6000, "threshold_db": -28}.  StnError naming the field for a value outside the limits, the two that
+        depend on the output rate in force included (include/stn.h, "de-esser")."""
+        c = deesser_args(deesser)
+        self._ck(self._lib.stn_set_deesser(self._h, int(c is not None), ctypes.byref(_deesser_struct(c)) if c else None))
+
+    def get_deesser(self):
+        """The setting in force: the 8-tuple (freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db, mode), or None when off."""
+        on, c = ctypes.c_int(), StnDeesser()
+        self._ck(self._lib.stn_get_deesser(self._h, ctypes.byref(on), ctypes.byref(c)))
+        return tuple(getattr(c, n) for n in DEESSER_FIELDS[:7]) + (DEESSER_MODES[c.mode],) if on.value else None
+
+    def batch_deesser(self):
+        """Per row of the finished batch, the largest reduction in dB the de-esser applied over the row's valid samples (float32 [B];
+        zeros while it is off)."""
+        out = np.zeros(self.batch_dims()[0], np.float32)
+        self._ck(self._lib.stn_batch_deesser(self._h, out.ctypes.data))
+        return out
+
+    def op_deesser(self, x, hz, deesser):
+        """rows x W fp32 at hz through the de-esser on the GPU -> y [rows, W] float32, every row from zero state."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        y = np.empty_like(x)
+        self._ck(self._lib.stn_op_deesser(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_deesser_struct(deesser)), y))
+        return y
+
+    def op_deesser_ex(self, x, hz, deesser, x_misalign=0, in_place=0):
+        """op_deesser with its scratch laid open -> dict: y, band (h), gr_db (yL) [rows, W]; st_end, st_start [rows, Ks, 4] (the band's
+        state per chunk of 32 samples: at its end from zero, at its start after the scan); s1_end, s1_start, s2_end, s2_start [rows, Ks]
+        (y1 and yL likewise; the scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y
+        came back whole); form ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y
+        over x on the device."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        Ks = (W + 31) // 32
+        o = dict(y=np.empty_like(x), band=np.empty_like(x), gr_db=np.empty_like(x))
+        for k in ("st_end", "st_start"):
+            o[k] = np.empty((rows, Ks, 4), np.float32)
+        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
+            o[k] = np.empty((rows, Ks), np.float32)
+        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
+        probes = [o[k].ctypes.data for k in ("band", "gr_db", "st_end", "st_start", "s1_end", "s1_start", "s2_end", "s2_start")]
+        self._ck(self._lib.stn_op_deesser_ex(self._h, int(hz), rows, W, x, ctypes.byref(_deesser_struct(deesser)), int(x_misalign), int(in_place),
+                                             o["y"], *probes, ctypes.byref(ok), form, ctypes.sizeof(form)))
         o["guard_ok"] = bool(ok.value)
         o["form"] = form.value.decode()
         return o

@@ -544,6 +544,60 @@ int stn_compressor_curve(const stn_compressor* c, int n, const double* in_db, do
     for (int i = 0; i < n; ++i) out_db[i] = stn::compressor_curve(*c, in_db[i]);
     return STN_OK;
 }
+int stn_set_deesser(stn_handle* h, int on, const stn_deesser* c) { STN_TRY(h, { h->eng->set_deesser(on != 0, c); }) }
+int stn_get_deesser(const stn_handle* h, int* on, stn_deesser* out) {
+    if (!h) return STN_ERR_INVALID;
+    if (on) *on = h->eng->deesser_on() ? 1 : 0;
+    if (out) *out = h->eng->deesser();
+    return STN_OK;
+}
+int stn_batch_deesser(stn_handle* h, float* max_reduction_db) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_deesser(max_reduction_db); })
+}
+int stn_op_deesser(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_deesser: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 h->eng->op_deesser(hz, rows, W, x, *c, y, nullptr); })
+}
+int stn_op_deesser_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, int x_misalign, int in_place, float* y,
+                      float* band, float* gr_db, float* st_end, float* st_start, float* s1_end, float* s1_start, float* s2_end,
+                      float* s2_start, int* guard_ok, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_deesser_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_deesser_ex: x_misalign and in_place must be 0 or 1");
+                 stn::Engine::DsProbe p;
+                 p.x_misalign = x_misalign; p.in_place = in_place; p.band = band; p.gr = gr_db; p.st_end = st_end; p.st_start = st_start;
+                 p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
+                 h->eng->op_deesser(hz, rows, W, x, *c, y, &p);
+                 if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0;
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
+const char* stn_deesser_error(const stn_deesser* c, int rate_hz) {
+    static thread_local std::string why;
+    why = rate_hz < 0 ? "deesser: rate_hz must not be negative" : stn::deesser_check(c, rate_hz);
+    return why.c_str();
+}
+int stn_deesser_band(const stn_deesser* c, int rate_hz, double c10[10], float c32[10]) {
+    if (rate_hz <= 0 || *stn_deesser_error(c, rate_hz)) return STN_ERR_INVALID;
+    stn_filter f[2];
+    stn::deesser_band(*c, f);
+    for (int h = 0; h < 2; ++h) {
+        double d[5];
+        stn::filter_design(f[h], rate_hz, d);
+        for (int i = 0; i < 5; ++i) {
+            if (c10) c10[h * 5 + i] = d[i];
+            if (c32) c32[h * 5 + i] = (float)d[i];
+        }
+    }
+    return STN_OK;
+}
+int stn_deesser_coefs(const stn_deesser* c, int rate_hz, double k[2], float k32[2]) {
+    if (rate_hz <= 0 || *stn_deesser_error(c, rate_hz)) return STN_ERR_INVALID;
+    const double d[2] = {stn::compressor_k(c->attack_ms, rate_hz), stn::compressor_k(c->release_ms, rate_hz)};
+    for (int i = 0; i < 2; ++i) {
+        if (k) k[i] = d[i];
+        if (k32) k32[i] = (float)d[i];
+    }
+    return STN_OK;
+}
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
 int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {

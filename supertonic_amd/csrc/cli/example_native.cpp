@@ -16,7 +16,11 @@
 // {rumble,telephone} (a high-pass at 80 Hz; the 300 to 3400 Hz telephone band, in front of any --filter),
 // --compressor THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]] (every utterance through the dynamic range compressor on the
 // GPU, behind the filters and before everything else; knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB when left out),
-// --compressor-preset speech (-24 dB, 3:1 and those).
+// --compressor-preset speech (-24 dB, 3:1 and those),
+// --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] (every utterance through the de-esser on the GPU,
+// behind the filters and in front of the compressor: the band above FREQ turned down by up to RANGE_DB while its level is over THRESHOLD;
+// ratio 4, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, MODE split (the band alone; wide: the whole signal) when left out),
+// --deesser-preset speech (5500 Hz, -30 dB and those).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -114,6 +118,11 @@ int main(int argc, char* argv[]) {
             const std::string why = a == "--compressor" ? parseCompressorSpec(argv[++i], opts.compressor) : compressorPreset(argv[++i], opts.compressor);
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.compressor_on = true;
+        }
+        else if ((a == "--deesser" || a == "--deesser-preset") && more) {  // the de-esser every utterance goes through on the GPU
+            const std::string why = a == "--deesser" ? parseDeesserSpec(argv[++i], opts.deesser) : deesserPreset(argv[++i], opts.deesser);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+            opts.deesser_on = true;
         }
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }

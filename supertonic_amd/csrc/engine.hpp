@@ -102,6 +102,12 @@ std::string compressor_check(const stn_compressor* c);
 double compressor_k(float ms, int rate_hz);
 double compressor_curve(const stn_compressor& c, double in_db);
 void compressor_table(int hz, const stn_compressor& c, CompTable& t);
+// The de-esser's host arithmetic (engine_deesser.cpp).  deesser_check: why c is refused at rate_hz (0: the limits that need no rate
+// only), naming the field, or ""; deesser_band: the two Butterworth high-pass sections at c.freq_hz, as filter_check takes them;
+// deesser_table: band, detector coefficients and the scans' powers at hz (no device copies), throws what the check refuses
+std::string deesser_check(const stn_deesser* c, int rate_hz);
+void deesser_band(const stn_deesser& c, stn_filter f[2]);
+void deesser_table(int hz, const stn_deesser& c, DeessTable& t);
 
 class Engine;
 // One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
@@ -473,6 +479,25 @@ class Engine {
     // rows x W fp32 (host) at hz through the compressor c -> y (host)
     void op_compressor(int hz, int rows, int W, const float* x, const stn_compressor& c, float* y, CpProbe* probe);
 
+    // ---- de-esser (engine_deesser.cpp; include/stn.h "de-esser"): off is the default (every fetch path is then
+    // exactly the one without it).  On, out_source() delivers the rows at the output rate de-essed in place in the fetch scratch, behind
+    // the filter chain and in front of the compressor (kernels_deesser.hip), and everything behind it runs on those.
+    void set_deesser(bool on, const stn_deesser* c);
+    bool deesser_on() const { return ds_on_; }
+    const stn_deesser& deesser() const { return ds_set_; }
+    void batch_deesser(float* max_reduction_db);
+    // the op-level probe: band and gr [rows][W], the band's states [rows][Ks][4] and the detector's four arrays [rows][Ks] (host, or
+    // null), the poisoned guards, the staging form
+    struct DsProbe {
+        int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
+        float *band = nullptr, *gr = nullptr, *st_end = nullptr, *st_start = nullptr;
+        float *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
+        bool guard_ok = false;   // out
+        const char* form = "";   // out
+    };
+    // rows x W fp32 (host) at hz through the de-esser c -> y (host)
+    void op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -781,7 +806,8 @@ class Engine {
     // what the row maxima in cp_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
     struct CpKey {
         uint64_t seq = 0; int hz = 0; uint64_t fl = 0, cp = 0; int64_t Wo = 0; const void* buf = nullptr;
-        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf; }
+        uint64_t ds = 0;  // ds_gen_ of the de-esser setting in front of it
+        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds; }
     };
     CpKey cp_key_; bool cp_valid_ = false;
     void cp_prepare(CompTable& t, int hz, const stn_compressor& c);
@@ -790,8 +816,31 @@ class Engine {
     // out where the sequence leaves it
     void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
     CpScratch cp_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) compressed into y (may be x)
+    // ---- de-esser (engine_deesser.cpp)
+    bool ds_on_ = false;
+    stn_deesser ds_set_{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};  // the setting in force (the "speech" default until one is set)
+    uint64_t ds_gen_ = 0;              // bumped by every change of the setting: part of EdKey and of CpKey (both see the de-essed rows)
+    DeessTable ds_, op_ds_;            // the tables at the output rate, and of op_deesser (device copies owned here)
+    DevBuf ds_buf_;                    // fetch-time scratch of the eight launches
+    // per chunk the band's state, y1 and yL (end values, then start values), the band pass's max |x| (unused) and the maximum of yL; per
+    // row that maximum, the width (the band's launches) and the valid length (the maxima)
+    struct DsScratch { float *st, *pk, *s1, *s2, *cmax, *rmax; int64_t *nw, *n; size_t bytes; };
+    static DsScratch ds_layout(char* base, int64_t rows, int64_t W);
+    std::vector<int64_t> ds_n_; const int64_t* ds_n_ptr_ = nullptr; int64_t ds_n_W_ = 0;  // the lengths ds_buf_ holds
+    // what the row maxima in ds_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
+    struct DsKey {
+        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, ds = 0; int64_t Wo = 0; const void* buf = nullptr;
+        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf; }
+    };
+    DsKey ds_key_; bool ds_valid_ = false;
+    void ds_prepare(DeessTable& t, int hz, const stn_deesser& c);
+    void ds_release();
+    // the eight launches on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read out where the
+    // sequence leaves it
+    void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
+    DsScratch ds_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) de-essed into y (may be x)
     // out_source() returns fetch scratch (row stride Wo), not b.wav
-    bool out_in_scratch() const { return resample_on() || filter_on() || compressor_on(); }
+    bool out_in_scratch() const { return resample_on() || filter_on() || deesser_on() || compressor_on(); }
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
@@ -815,8 +864,9 @@ class Engine {
         float mp = 0;  // max_pause_ms of the cuts held beside the edges; 0: none
         uint64_t fl = 0;  // fl_gen_ of the filter chain the rows went through
         uint64_t cp = 0;  // cp_gen_ of the compressor setting they went through
+        uint64_t ds = 0;  // ds_gen_ of the de-esser setting they went through
         bool operator==(const EdKey& o) const {
-            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp;
+            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp && ds == o.ds;
         }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;

@@ -283,6 +283,33 @@ std::string parseCompressorSpec(const std::string& spec, stn_compressor& c) {
     return "";
 }
 
+std::string deesserPreset(const std::string& name, stn_deesser& c) {
+    if (name != "speech") return "deesser-preset '" + name + "': speech";
+    c = stn_deesser{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};
+    return "";
+}
+
+std::string parseDeesserSpec(const std::string& spec, stn_deesser& c) {
+    std::vector<std::string> parts;
+    size_t a = 0, p;
+    while ((p = spec.find(':', a)) != std::string::npos) { parts.push_back(spec.substr(a, p - a)); a = p + 1; }
+    parts.push_back(spec.substr(a));
+    const std::string who = "deesser '" + spec + "': ";
+    if (parts.size() < 2 || parts.size() > 8) return who + "expected FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]";
+    (void)deesserPreset("speech", c);  // what the fields left out take
+    float* dst[7] = {&c.freq_hz, &c.threshold_db, &c.ratio, &c.knee_db, &c.attack_ms, &c.release_ms, &c.range_db};
+    for (size_t i = 0; i < parts.size() && i < 7; ++i) {
+        char* end = nullptr;
+        *dst[i] = std::strtof(parts[i].c_str(), &end);
+        if (parts[i].empty() || *end) return who + "FREQ, THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and RANGE_DB must be numbers";
+    }
+    if (parts.size() == 8) {
+        if (parts[7] != "split" && parts[7] != "wide") return who + "MODE must be one of split, wide";
+        c.mode = parts[7] == "wide" ? STN_DEESS_WIDE : STN_DEESS_SPLIT;
+    }
+    return "";
+}
+
 std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool use_gpu, const EngineOptions& opts) {
     if (!use_gpu) throw std::runtime_error("CPU mode is not supported: this engine runs on MI355X only");
     const char* dt_name = opts.dtype == STN_DTYPE_BF16 ? "bf16" : opts.dtype == STN_DTYPE_F16 ? "fp16" : "fp32";
@@ -340,6 +367,8 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         if (opts.output_rate) applied("output rate", grp ? stn_group_set_output_rate(grp, opts.output_rate) : stn_set_output_rate(h, opts.output_rate));
         // (after the rate: a chain is checked against the output rate in force)
         if (nf) applied("filters", grp ? stn_group_set_filters(grp, nf, opts.filters.data()) : stn_set_filters(h, nf, opts.filters.data()));
+        // (after the rate as well: freq_hz is checked against the output rate in force)
+        if (opts.deesser_on) applied("deesser", grp ? stn_group_set_deesser(grp, 1, &opts.deesser) : stn_set_deesser(h, 1, &opts.deesser));
         if (opts.compressor_on) applied("compressor", grp ? stn_group_set_compressor(grp, 1, &opts.compressor) : stn_set_compressor(h, 1, &opts.compressor));
         if (!std::isnan(opts.loudness_lufs))
             applied("loudness", grp ? stn_group_set_loudness(grp, 1, opts.loudness_lufs, opts.loudness_ceiling_dbfs)

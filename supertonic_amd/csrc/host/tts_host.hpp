@@ -82,6 +82,9 @@ struct EngineOptions {
     bool compressor_on = false;    // every utterance through the dynamic range compressor on the GPU, behind the filters and before everything
     stn_compressor compressor{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};  // above (stn_set_compressor); these are the "speech" preset's values.
                                    // CLI --compressor THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]] and --compressor-preset speech
+    bool deesser_on = false;       // every utterance through the de-esser on the GPU, behind the filters and in front of the compressor
+    stn_deesser deesser{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};  // (stn_set_deesser); these are the "speech" preset's values.
+                                   // CLI --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] and --deesser-preset speech
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
 };
@@ -97,6 +100,11 @@ std::string filterPreset(const std::string& name, std::vector<stn_filter>& out);
 // "speech" (-24 dB, 3:1 and those) into c, or why not.  The numeric limits are stn_set_compressor's own.
 std::string parseCompressorSpec(const std::string& spec, stn_compressor& c);
 std::string compressorPreset(const std::string& name, stn_compressor& c);
+// The command line's de-esser arguments (host only).  parseDeesserSpec: "FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]"
+// (the speech preset's values for what is left out; MODE split or wide) into c, or why not.  deesserPreset: "speech" (5500 Hz, -30 dB,
+// 4:1, knee 6 dB, 1 ms, 40 ms, range 12 dB, split) into c, or why not.  The numeric limits are stn_set_deesser's own.
+std::string parseDeesserSpec(const std::string& spec, stn_deesser& c);
+std::string deesserPreset(const std::string& name, stn_deesser& c);
 
 class TextToSpeech {
    public:

@@ -568,6 +568,28 @@ void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const floa
 // "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
 const char* compressor_staging_form(const float* x, const float* y, int64_t W);
 
+// Fetch-time de-esser (kernels_deesser.hip; the limits, the tables and the sequence of eight launches are engine_deesser.cpp; DESIGN.md
+// section 21): the compressor's detector on the level of a band h = HP4(x), its gain on the band (split) or on x (wide).  The band's
+// chunk pass and scan are the loudness measurement's on `band`, the detector's scans the compressor's on `det`.
+struct DeessCoef { LoudCoef band; float T, S, K, kA, kR, range; };  // the two high-pass sections; threshold dB, 1 / ratio - 1, knee dB, k, range dB
+struct DeessTable {
+    int hz = 0;
+    float set[7] = {};                // the stn_deesser fields the table was made from, and its mode
+    int mode = 0;
+    bool split = true;                // mode == STN_DEESS_SPLIT
+    DeessCoef coef{};
+    LoudTable band;                   // the band's section pass: coefficients and the powers of its M (hop = 1, unused)
+    CompTable det;                    // the scans' powers from the same attack and release (makeup 0; its T, S, K are not read)
+};
+// Every pass regenerates h from x and st[row][k], the band's state at the start of chunk k.  pass 1: s1[row][k] = y1 at the end of chunk
+// k from zero.  pass 2: s1 = y1 at the chunk's start -> s2[row][k] = yL at its end from zero.  pass 3: s1, s2 = the start values -> y
+// (row stride W; may be x), band and gr (rows x W h and yL, or null), cmax[row][k] = max of yL over the chunk's samples below n[row]
+// (device; null: W).  The staging form of all three is that of (x, y, W).
+void launch_deesser_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const DeessTable& t, const float* st,
+                           float* s1, float* s2, float* y, float* band, float* gr, float* cmax);
+// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
+const char* deesser_staging_form(const float* x, const float* y, int64_t W);
+
 // Look-ahead peak limiter behind the loudness gain (kernels_limiter.hip; the setting, the window and the scratch are engine_limiter.cpp;
 // DESIGN.md section 15).  rows x W fp32 (row stride W) with row spans n[rows] (device, <= W) and gains gain[rows] (device; null: 1) ->
 // y (rows x W fp32, row stride W, not x): row b times gain[b], turned down around every sample above c so that |y| <= c, the curve s

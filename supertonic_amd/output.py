@@ -30,6 +30,7 @@ def _peak_mode(v):
 _PARSE = {
     "output_rate": int,
     "filters": lambda v: binding.filter_args(None if v is False else v),
+    "deesser": lambda v: binding.deesser_args(v) or False,
     "compressor": lambda v: binding.compressor_args(v) or False,
     "loudness": lambda v: v is not False and _loudness(v),
     "trim_silence": lambda v: v is not False and binding.silence_trim_args(v)[1:],
@@ -49,7 +50,11 @@ class OutputSettings:
     filters       a chain of up to 8 biquads every utterance goes through, after the resampler and before everything below
                   (stn_set_filters): a list as binding.filter_args takes it, e.g. [("highpass", 80)]; the numeric limits are checked by
                   the engine against the output rate in force.  Normalized: a tuple of (type, freq_hz, q, gain_db).  Off: False or [], ().
-    compressor    the dynamic range of every utterance compressed, behind the chain and before everything below (stn_set_compressor): True
+    deesser       the sibilants of every utterance turned down, behind the chain and in front of the compressor (stn_set_deesser): True (the
+                  "speech" default: 5500 Hz, -30 dB, 4:1, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, split), a dict of those
+                  fields or an 8-tuple, as binding.deesser_args takes them; freq_hz is checked by the engine against the output rate in
+                  force.  Normalized: the 8-tuple (seven floats and the mode's name).  Off: False.
+    compressor    the dynamic range of every utterance compressed, behind the chain and the de-esser and before everything below (stn_set_compressor): True
                   (the "speech" default: -24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB), a dict of those fields or
                   a 6-tuple, as binding.compressor_args takes them.  Normalized: the 6-tuple of floats.  Off: False.
     loudness      every utterance normalized to this BS.1770-4 integrated loudness, measured at the output rate (stn_set_loudness): a
@@ -70,6 +75,11 @@ class OutputSettings:
     limiter: object = None
     peak_mode: object = None
     compressor: object = None  # (declared last: OFF and positional construction keep their seven fields; applied behind filters)
+    # (applied between filters and compressor.)  Not a constructor argument: it is set by parse() and replace() only, so that positional
+    # construction, OFF, and dataclasses.replace of a value that names no de-esser keep meaning what they meant before the field was
+    # there (dataclasses.replace copies constructor arguments only: it leaves this field unset, and refuses to be given it).  Compared
+    # and hashed like every other field.
+    deesser: object = dataclasses.field(default=None, init=False)
 
     @classmethod
     def parse(cls, **kw):
@@ -78,7 +88,15 @@ class OutputSettings:
         for k in kw:
             if k not in _PARSE:
                 raise TypeError(f"{k!r} is not an output setting ({', '.join(_PARSE)})")
-        return cls(**{k: p(kw[k]) for k, p in _PARSE.items() if kw.get(k) is not None})
+        return cls().replace(**{k: p(kw[k]) for k, p in _PARSE.items() if kw.get(k) is not None})
+
+    def replace(self, **changes):
+        """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser
+        included"""
+        deesser = changes.pop("deesser", self.deesser)
+        new = dataclasses.replace(self, **changes)
+        object.__setattr__(new, "deesser", deesser)
+        return new
 
     def kwargs(self):
         """The set fields under their keywords, as parse takes them (filters as a list)"""
@@ -89,17 +107,21 @@ class OutputSettings:
 
     def over(self, base):
         """base with this value's set fields in force"""
-        return dataclasses.replace(base, **{k: getattr(self, k) for k in self.kwargs()})
+        return base.replace(**{k: getattr(self, k) for k in self.kwargs()})
 
     def apply(self, engine):
         """The set fields onto a binding.Engine, in the one order that works: a chain is checked against the output rate in force, so
-        it goes off before the rate changes and on after it.  The rest are independent of each other."""
+        it goes off before the rate changes and on after it, and so does the de-esser.  The rest are independent of each other."""
         if self.filters is not None:
             engine.set_filters(None)
+        if self.deesser is not None and (self.output_rate is not None or not self.deesser):
+            engine.set_deesser(None)
         if self.output_rate is not None:
             engine.set_output_rate(self.output_rate)
         if self.filters:
             engine.set_filters(self.filters)
+        if self.deesser:
+            engine.set_deesser(self.deesser)
         if self.compressor is not None:
             engine.set_compressor(self.compressor or None)
         if self.loudness is not None:
@@ -121,9 +143,9 @@ class OutputSettings:
             self.apply(engine)
             yield self.over(base)
         finally:
-            OutputSettings(**{k: getattr(base, k) for k in self.kwargs()}).apply(engine)
+            OutputSettings().replace(**{k: getattr(base, k) for k in self.kwargs()}).apply(engine)
 
 
-# OFF leaves compressor unset (a base that does not name the field compares equal after over(OFF)); ALL_OFF names every field
+# OFF leaves compressor and deesser unset (a base that does not name them compares equal after over(OFF)); ALL_OFF names every field
 OutputSettings.OFF = OutputSettings(0, (), False, False, False, False, "sample")
-OutputSettings.ALL_OFF = dataclasses.replace(OutputSettings.OFF, compressor=False)
+OutputSettings.ALL_OFF = OutputSettings.OFF.replace(compressor=False, deesser=False)

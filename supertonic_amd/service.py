@@ -8,7 +8,6 @@ included; a `batch: true` request keeps the reference's semantics (its own padde
 
     TTS_ONNX_DIR=assets/onnx TTS_DTYPE=bf16 uvicorn supertonic_amd.service:app
 """
-import dataclasses
 import io
 import os
 import threading
@@ -31,7 +30,7 @@ BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
-              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, compressor=None):
+              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -39,25 +38,30 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     at peak_ceiling dBFS.  limiter_ms, peak_mode ("sample" or "true"): OutputSettings' limiter and peak_mode; they act on the loudness
     gain, so without loudness they (and peak_ceiling) are validated and dropped.  trim_silence: top_db or (top_db, keep_ms, fade_ms), no
     bool.  max_pause_ms: without trim_silence, validated and dropped likewise.  filters: a list as binding.filter_args takes it, [] =
-    off, checked against the request's rate.  compressor: True, a dict or a 6-tuple as binding.compressor_args takes it, False = off,
+    off, checked against the request's rate.  deesser: True, a dict or an 8-tuple as binding.deesser_args takes it, False = off, checked
+    against the request's rate as well.  compressor: True, a dict or a 6-tuple as binding.compressor_args takes it, False = off,
     checked against the engine's limits.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
     loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
     if why:
         raise ValueError(why)
+    dees = None if deesser is None else (binding.deesser_args(deesser) or False)
+    why = dees and binding.deesser_error(dees, int(sample_rate or model_rate))
+    if why:
+        raise ValueError(why)
     comp = None if compressor is None else (binding.compressor_args(compressor) or False)
     why = comp and binding.compressor_error(comp, int(sample_rate or model_rate))
     if why:
         raise ValueError(why)
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, compressor=comp, loudness=None if loudness is None else (loudness, peak_ceiling),
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
     if s.loudness is None:
-        s = dataclasses.replace(s, limiter=None, peak_mode=None)
+        s = s.replace(limiter=None, peak_mode=None)
     if s.trim_silence is None:
-        s = dataclasses.replace(s, max_pause=None)
+        s = s.replace(max_pause=None)
     return BatchKey(int(total_step), float(speed), None if encoding is None else binding.encoding_id(encoding), str(loudness_scope),
                     bool(trim_chunks), s)
 
@@ -251,6 +255,12 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                 "highshelf, freq (Hz), q (0.7071), gain_db (0)}; null: off.")
         filter_preset: Optional[str] = Field(None, description="A named chain in front of filters: 'rumble' (high-pass at 80 Hz) or 'telephone' "
                                                                "(300 to 3400 Hz, 4th-order Butterworth).")
+        deesser: Optional[Union[bool, dict]] = Field(None, description="De-esser every utterance goes through on the GPU, behind the filters and in "
+                                                                       "front of the compressor: true (the speech default: 5500 Hz, -30 dB, "
+                                                                       "4:1, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, split) or "
+                                                                       "{freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db, "
+                                                                       "mode}, the fields left out from that default; false: off; null: the "
+                                                                       "server's.")
         compressor: Optional[Union[bool, dict]] = Field(None, description="Dynamic range compressor every utterance goes through on the GPU, behind "
                                                                           "the filters and before everything else: true (the speech default: "
                                                                           "-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB) or "
@@ -303,6 +313,16 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             if why:
                 raise HTTPException(status_code=400, detail=f"filters: {why}")
             extra["filters"] = list(chain)
+        dees = None
+        if req.deesser is not None:
+            try:
+                dees = binding.deesser_args(req.deesser) or False
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            why = binding.deesser_error(dees, sr) if dees else ""
+            if why:
+                raise HTTPException(status_code=400, detail=why)
+            extra["deesser"] = dees
         comp = None
         if req.compressor is not None:
             try:
@@ -337,7 +357,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                          enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                          trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                         max_pause_ms=req.max_pause_ms, filters=chain, compressor=comp)
+                                         max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp)
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:

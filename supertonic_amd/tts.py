@@ -138,7 +138,7 @@ class TextToSpeech:
         """Independent utterances as one batch whose rows equal what each would give alone (length-aware vocoder):
         returns a list of per-utterance waves of L_i * chunk_size samples (at the output rate: the resampled length of those)
         and the durations.  The building block of the long-form path and of the service's dynamic batching.
-        out: this call's OutputSettings keywords instead of the instance's; every utterance is filtered, compressed, normalized and limited on its
+        out: this call's OutputSettings keywords instead of the instance's; every utterance is filtered, de-essed, compressed, normalized and limited on its
         own, and with trim_silence every wave is its trimmed segment (max_pause: what the cuts leave of it), cut at the length the GPU
         found.  encoding (a name or binding.ENC_*; None: float32): the waves in that sample encoding, encoded on the GPU
         (binding.encoded_empty's dtypes)."""
@@ -218,7 +218,7 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
     weights (benchmarks and tests on machines without the Hugging Face assets), and it says so.  out: the instance's OutputSettings
-    keywords (output_rate, filters, compressor, loudness, trim_silence, max_pause, limiter, peak_mode), each off when left out."""
+    keywords (output_rate, filters, deesser, compressor, loudness, trim_silence, max_pause, limiter, peak_mode), each off when left out."""
     settings = OutputSettings.parse(**out)  # (refused before the engine is created)
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
