@@ -681,6 +681,7 @@ class Engine {
     std::vector<void*> batch_retired_;  // outgrown buffers: freed at the next upload, after the stream has drained
     template <typename T> void ensure(T*& p, size_t& cap, size_t need);
     std::vector<float> reported_dur_;
+    std::vector<int64_t> out_spans(int64_t Wo, int hz) const;  // the finished batch's valid samples per row at the output rate (engine_loudness.cpp)
     void enqueue_after_duration(int total_step, const std::function<void()>& take_text_rows);
     // A captured graph holds raw pointers: everything it can have baked in is part of its key — the batch buffers (`gen`, bumped
     // by every reallocation), the weights (`wgen`, bumped by every load), the pinned staging the copy nodes read, the stream.

@@ -1,7 +1,7 @@
 // engine_compressor.cpp — the fetch-time dynamic range compressor of a handle: its limits, coefficients and static curve (host only),
 // the scan tables and the scratch, the sequence of launches and the op-level entry.  The kernels are kernels_compressor.hip; the hook
 // is Engine::out_source (engine_batch.cpp); DESIGN.md section 20 has the contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -10,12 +10,6 @@
 namespace stn {
 
 namespace {
-
-std::string num(double v) {
-    char b[48];
-    std::snprintf(b, sizeof(b), "%g", v);
-    return b;
-}
 
 void fields(const stn_compressor& c, float out[6]) {
     const float v[6] = {c.threshold_db, c.ratio, c.knee_db, c.attack_ms, c.release_ms, c.makeup_db};
@@ -42,12 +36,9 @@ CompCoef static_coef(const stn_compressor& c) {
 
 std::string compressor_check(const stn_compressor* c) {
     if (!c) return "compressor: c is null";
-    struct Lim { const char* name; float v, lo, hi; };
     const Lim lim[6] = {{"threshold_db", c->threshold_db, -60.0f, 0.0f}, {"ratio", c->ratio, 1.0f, 20.0f},       {"knee_db", c->knee_db, 0.0f, 24.0f},
                         {"attack_ms", c->attack_ms, 0.1f, 300.0f},       {"release_ms", c->release_ms, 10.0f, 3000.0f}, {"makeup_db", c->makeup_db, -12.0f, 24.0f}};
-    for (const Lim& l : lim)  // (a NaN fails both comparisons)
-        if (!(l.v >= l.lo && l.v <= l.hi)) return std::string("compressor: ") + l.name + " " + num(l.v) + " must be in [" + num(l.lo) + ", " + num(l.hi) + "]";
-    return "";
+    return range_check("compressor", lim);
 }
 
 double compressor_k(float ms, int rate_hz) { return -std::expm1(-1000.0 / ((double)ms * (double)rate_hz)); }
@@ -166,8 +157,7 @@ Engine::CpScratch Engine::cp_batch(const float* x, int64_t Wo, float* y) {
     char* base = cp_buf_.reserve(*this, cp_layout(nullptr, b.B, Wo).bytes, &moved);
     const CpScratch sc = cp_layout(base, b.B, Wo);
     // row b's valid samples: section 11's span, its reported duration at the output rate; uploaded once per finished batch
-    std::vector<int64_t> n((size_t)b.B);
-    for (int i = 0; i < b.B; ++i) n[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
+    std::vector<int64_t> n = out_spans(Wo, hz);
     if (moved || n != cp_n_ || cp_n_ptr_ != sc.n) {
         cp_n_ = std::move(n);
         cp_n_ptr_ = sc.n;
@@ -199,39 +189,24 @@ void Engine::op_compressor(int hz, int rows, int W, const float* x, const stn_co
     STN_HIP(hipSetDevice(device_));
     cp_prepare(op_cp_, hz, c);
     ar_.reset();
-    // [guard][x][guard] and [guard][y][guard], the guards poisoned; misaligned: both 4 bytes off (the arena's blocks are 256-byte aligned)
-    constexpr size_t G = 64;
-    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;
-    float* bx = static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    const bool in_place = probe && probe->in_place;
-    float* by = in_place ? bx : static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    float *dx = bx + G + off, *dy = by + G + off;
+    const size_t nx = (size_t)rows * W;
+    GuardedRows r(*this, nx, x, probe, probe && probe->x_misalign, probe && probe->in_place);
     float* dgr = probe && probe->gr ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
     const size_t sc_bytes = cp_layout(nullptr, rows, W).bytes;
     char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
     const CpScratch sc = cp_layout(sb, rows, W);
     if (probe) {
-        for (float* b : {bx, by}) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx + 2 * G + off, s_));
         if (dgr) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dgr), 0x7FC00000, nx, s_));
         STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
     }
     const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    cp_enqueue(op_cp_, dx, rows, W, sc, dy, dgr, probe);
-    STN_HIP(hipMemcpyAsync(y, dy, nx * 4, hipMemcpyDeviceToHost, s_));
+    cp_enqueue(op_cp_, r.dx, rows, W, sc, r.dy, dgr, probe);
+    r.download(y);
     if (dgr) STN_HIP(hipMemcpyAsync(probe->gr, dgr, nx * 4, hipMemcpyDeviceToHost, s_));
     if (probe) {
-        std::vector<uint32_t> g(4 * G + 2 * off);
-        uint32_t* p = g.data();
-        for (float* b : {bx, by}) {
-            STN_HIP(hipMemcpyAsync(p, b, (G + off) * 4, hipMemcpyDeviceToHost, s_));
-            STN_HIP(hipMemcpyAsync(p + G + off, b + G + off + nx, G * 4, hipMemcpyDeviceToHost, s_));
-            p += 2 * G + off;
-        }
-        sync();
-        probe->guard_ok = std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == 0x7FC00000u; });
-        probe->form = compressor_staging_form(dx, dy, W);
+        probe->guard_ok = r.guards_ok();
+        probe->form = compressor_staging_form(r.dx, r.dy, W);
     }
     sync();
 }

@@ -2,7 +2,7 @@
 // the sequence of eight launches and the op-level entry.  The chunk passes are kernels_deesser.hip, the band's first two launches the
 // loudness measurement's (kernels_loudness.hip), the detector's scans and the row maxima the compressor's (kernels_compressor.hip); the
 // hook is Engine::out_source (engine_batch.cpp); DESIGN.md section 21 has the contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -11,12 +11,6 @@
 namespace stn {
 
 namespace {
-
-std::string num(double v) {
-    char b[48];
-    std::snprintf(b, sizeof(b), "%g", v);
-    return b;
-}
 
 void fields(const stn_deesser& c, float out[7]) {
     const float v[7] = {c.freq_hz, c.threshold_db, c.ratio, c.knee_db, c.attack_ms, c.release_ms, c.range_db};
@@ -40,12 +34,11 @@ void deesser_band(const stn_deesser& c, stn_filter f[2]) {
 
 std::string deesser_check(const stn_deesser* c, int rate_hz) {
     if (!c) return "deesser: c is null";
-    struct Lim { const char* name; float v, lo, hi; };
     const Lim lim[7] = {{"freq_hz", c->freq_hz, 2000.0f, 12000.0f}, {"threshold_db", c->threshold_db, -60.0f, 0.0f}, {"ratio", c->ratio, 1.0f, 20.0f},
                         {"knee_db", c->knee_db, 0.0f, 24.0f},       {"attack_ms", c->attack_ms, 0.1f, 300.0f},       {"release_ms", c->release_ms, 10.0f, 3000.0f},
                         {"range_db", c->range_db, 1.0f, 24.0f}};
-    for (const Lim& l : lim)  // (a NaN fails both comparisons)
-        if (!(l.v >= l.lo && l.v <= l.hi)) return std::string("deesser: ") + l.name + " " + num(l.v) + " must be in [" + num(l.lo) + ", " + num(l.hi) + "]";
+    const std::string out = range_check("deesser", lim);
+    if (!out.empty()) return out;
     if (c->mode != STN_DEESS_SPLIT && c->mode != STN_DEESS_WIDE) return "deesser: mode " + std::to_string(c->mode) + " is not STN_DEESS_SPLIT (0) or STN_DEESS_WIDE (1)";
     if (rate_hz <= 0) return "";  // (no model loaded yet: the corners are checked when the band is first designed)
     const std::string why = rate_check("deesser", rate_hz);
@@ -190,8 +183,7 @@ Engine::DsScratch Engine::ds_batch(const float* x, int64_t Wo, float* y) {
     const DsScratch sc = ds_layout(base, b.B, Wo);
     // row b's valid samples: section 11's span, its reported duration at the output rate; uploaded once per finished batch, with the
     // width the band's two launches take as every row's length
-    std::vector<int64_t> n((size_t)b.B);
-    for (int i = 0; i < b.B; ++i) n[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
+    std::vector<int64_t> n = out_spans(Wo, hz);
     if (moved || n != ds_n_ || ds_n_ptr_ != sc.n || ds_n_W_ != Wo) {
         ds_n_ = std::move(n);
         ds_n_ptr_ = sc.n;
@@ -226,43 +218,28 @@ void Engine::op_deesser(int hz, int rows, int W, const float* x, const stn_deess
     STN_HIP(hipSetDevice(device_));
     ds_prepare(op_ds_, hz, c);
     ar_.reset();
-    // [guard][x][guard] and [guard][y][guard], the guards poisoned; misaligned: both 4 bytes off (the arena's blocks are 256-byte aligned)
-    constexpr size_t G = 64;
-    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;
-    float* bx = static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    const bool in_place = probe && probe->in_place;
-    float* by = in_place ? bx : static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    float *dx = bx + G + off, *dy = by + G + off;
+    const size_t nx = (size_t)rows * W;
+    GuardedRows r(*this, nx, x, probe, probe && probe->x_misalign, probe && probe->in_place);
     float* dband = probe && probe->band ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
     float* dgr = probe && probe->gr ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
     const size_t sc_bytes = ds_layout(nullptr, rows, W).bytes;
     char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
     const DsScratch sc = ds_layout(sb, rows, W);
     if (probe) {
-        for (float* b : {bx, by}) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx + 2 * G + off, s_));
         for (float* b : {dband, dgr})
             if (b) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx, s_));
         STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
     }
     const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.nw, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ds_enqueue(op_ds_, dx, rows, W, sc, dy, probe, dband, dgr);
-    STN_HIP(hipMemcpyAsync(y, dy, nx * 4, hipMemcpyDeviceToHost, s_));
+    ds_enqueue(op_ds_, r.dx, rows, W, sc, r.dy, probe, dband, dgr);
+    r.download(y);
     if (dband) STN_HIP(hipMemcpyAsync(probe->band, dband, nx * 4, hipMemcpyDeviceToHost, s_));
     if (dgr) STN_HIP(hipMemcpyAsync(probe->gr, dgr, nx * 4, hipMemcpyDeviceToHost, s_));
     if (probe) {
-        std::vector<uint32_t> g(4 * G + 2 * off);
-        uint32_t* p = g.data();
-        for (float* b : {bx, by}) {
-            STN_HIP(hipMemcpyAsync(p, b, (G + off) * 4, hipMemcpyDeviceToHost, s_));
-            STN_HIP(hipMemcpyAsync(p + G + off, b + G + off + nx, G * 4, hipMemcpyDeviceToHost, s_));
-            p += 2 * G + off;
-        }
-        sync();
-        probe->guard_ok = std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == 0x7FC00000u; });
-        probe->form = deesser_staging_form(dx, dy, W);
+        probe->guard_ok = r.guards_ok();
+        probe->form = deesser_staging_form(r.dx, r.dy, W);
     }
     sync();
 }

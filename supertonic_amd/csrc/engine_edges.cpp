@@ -107,8 +107,7 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo, bool pauses) {
     const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_.get(), pauses ? pl_ms_ : 0.0f, fl_gen_, cp_gen_, ds_gen_};
     if (ed_valid_ && key == ed_key_) return sc;
     // row b's span: section 11's, its reported duration at the output rate
-    ed_n_.resize((size_t)b.B);
-    for (int i = 0; i < b.B; ++i) ed_n_[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
+    ed_n_ = out_spans(Wo, hz);
     STN_HIP(hipMemcpyAsync(sc.n, ed_n_.data(), ed_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     ed_enqueue(x, b.B, Wo, hz, st_db_, st_keep_, st_fade_, sc, pauses ? pause_samples(hz, pl_ms_) : 0);
     ed_key_ = key;

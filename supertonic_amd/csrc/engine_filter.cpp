@@ -2,7 +2,7 @@
 // scratch, the passes themselves and the op-level entry.  The write kernel is kernels_filter.hip, the other two launches of a pass are
 // the loudness measurement's (kernels_loudness.hip); the hook is Engine::out_source (engine_batch.cpp); DESIGN.md section 18 has the
 // contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -14,12 +14,6 @@ namespace stn {
 namespace {
 
 const char* const kTypeNames[] = {"highpass", "lowpass", "notch", "peak", "lowshelf", "highshelf"};
-
-std::string num(double v) {
-    char b[48];
-    std::snprintf(b, sizeof(b), "%g", v);
-    return b;
-}
 
 bool same_chain(const std::vector<stn_filter>& a, int n, const stn_filter* f) {
     if ((int)a.size() != n) return false;
@@ -192,31 +186,15 @@ void Engine::op_filter(int hz, int rows, int W, const float* x, int n, const stn
     if (n < 1) throw std::invalid_argument("op_filter: n = " + std::to_string(n) + " must be in [1, " + std::to_string(STN_MAX_FILTERS) + "]");
     fl_prepare(op_fl_, hz, n, f);
     ar_.reset();
-    // [guard][x][guard] and [guard][y][guard], the guards poisoned; misaligned: both 4 bytes off (the arena's blocks are 256-byte aligned)
-    constexpr size_t G = 64;
-    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;
-    float* bx = static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    float* by = static_cast<float*>(ar_.alloc((nx + 2 * G + off) * 4));
-    float *dx = bx + G + off, *dy = by + G + off;
+    GuardedRows r(*this, (size_t)rows * W, x, probe, probe && probe->x_misalign, false);
     const FlScratch sc = fl_layout(static_cast<char*>(ar_.alloc(fl_layout(nullptr, rows, W).bytes)), rows, W);
-    if (probe)
-        for (float* b : {bx, by}) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx + 2 * G + off, s_));
     const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    fl_enqueue(op_fl_, dx, rows, W, sc, dy, probe);
-    STN_HIP(hipMemcpyAsync(y, dy, nx * 4, hipMemcpyDeviceToHost, s_));
+    fl_enqueue(op_fl_, r.dx, rows, W, sc, r.dy, probe);
+    r.download(y);
     if (probe) {
-        std::vector<uint32_t> g(4 * G + 2 * off);
-        uint32_t* p = g.data();
-        for (float* b : {bx, by}) {
-            STN_HIP(hipMemcpyAsync(p, b, (G + off) * 4, hipMemcpyDeviceToHost, s_));
-            STN_HIP(hipMemcpyAsync(p + G + off, b + G + off + nx, G * 4, hipMemcpyDeviceToHost, s_));
-            p += 2 * G + off;
-        }
-        sync();
-        probe->guard_ok = std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == 0x7FC00000u; });
-        probe->form = filter_staging_form(dx, dy, W);
+        probe->guard_ok = r.guards_ok();
+        probe->form = filter_staging_form(r.dx, r.dy, W);
     }
     sync();
 }

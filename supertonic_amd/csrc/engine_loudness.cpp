@@ -180,17 +180,18 @@ void Engine::lo_read_back(const LoRes& m, size_t n, float* lufs, float* peak, fl
     if (gain) STN_HIP(hipMemcpyAsync(gain, m.gain, n * 4, hipMemcpyDeviceToHost, s_));
 }
 
+// row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file, inside [0, Wo]
+std::vector<int64_t> Engine::out_spans(int64_t Wo, int hz) const {
+    std::vector<int64_t> n((size_t)bt_.B);
+    for (int i = 0; i < bt_.B; ++i) n[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
+    return n;
+}
+
 Engine::LoRes Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     const Batch& b = bt_;
     const int hz = output_rate();
     lo_prepare(lo_, hz);
-    // row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file
-    std::vector<int64_t> n((size_t)b.B);
-    for (int i = 0; i < b.B; ++i) {
-        n[(size_t)i] = std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz));
-        if (n[(size_t)i] < 0) n[(size_t)i] = 0;
-    }
-    return lo_rows(lo_, x, b.B, Wo, std::move(n), on, lo_target_, lo_cap(), lo_true_peak());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
+    return lo_rows(lo_, x, b.B, Wo, out_spans(Wo, hz), on, lo_target_, lo_cap(), lo_true_peak());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
 }
 
 Engine::LoRes Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target,

@@ -10,12 +10,13 @@
 //   3. chunk pass 2: y1 from its start, yL from zero -> c_k  4. scan 2 (+, x) in double -> yL at every chunk's start
 //   5. write pass: both stages from their start states -> y, optionally yL, and the chunk's max of yL over the row's valid samples
 // and a sixth, small one: the row maxima of those chunk maxima (stn_batch_compressor).
-// Chunks are LO_CHUNK samples counted from sample 0, a workgroup stages LO_WG of them through LDS exactly as filter_write_kernel does
-// (16-byte loads and stores or the scalar form, row stride 33 words), and every pass restates the one before it operation for
-// operation (cp_want, cp_peak, cp_smooth): the start states the scans form are exact for this arithmetic only.
+// Chunks are LO_CHUNK samples counted from sample 0, a workgroup stages LO_WG of them through LDS as filter_write_kernel does
+// (chunk_stage_in / chunk_stage_out, kernels_chunk.hpp: 16-byte loads and stores or the scalar form, row stride 33 words), and every
+// pass calls the same gain_want, gain_peak and gain_smooth (the same header): the start states the scans form are exact for this
+// arithmetic only.
 // In place (y == x) is allowed: a workgroup reads the samples it owns into LDS before the first barrier and stores after the second.
 // A row's y[0 .. n) depends on x[0 .. n) of that row and the coefficients only: the scans' order is fixed by the chunk index.
-#include "kernels.hpp"
+#include "kernels_chunk.hpp"
 
 #include <math.h>
 
@@ -27,21 +28,6 @@ constexpr int CP_SPAN = LO_WG * LO_CHUNK;  // samples a workgroup owns
 constexpr int CP_PAD = LO_CHUNK + 1;       // LDS words per chunk: the lanes' walks fall on distinct banks
 constexpr int CP_ROWMAX = 256;             // threads of the row-maximum workgroup
 
-// the gain computer: the reduction wanted at a sample, in dB (>= 0).  The knee's quadratic only where there is a knee: with K = 0 and
-// d = 0 it would be 0 / 0, and the hard corner gives 0 there.
-__device__ __forceinline__ float cp_want(const CompCoef& f, float x) {
-    const float xg = 20.0f * log10f(fmaxf(fabsf(x), 1e-6f));
-    const float d = xg - f.T;
-    const float d2 = 2.0f * d;
-    if (d2 < -f.K) return 0.0f;
-    if (f.K > 0.0f && fabsf(d2) <= f.K) {
-        const float t = d + 0.5f * f.K;
-        return (-f.S * (t * t)) / (2.0f * f.K);
-    }
-    return -f.S * d;
-}
-__device__ __forceinline__ float cp_peak(const CompCoef& f, float z, float y1) { return fmaxf(z, __builtin_fmaf(-f.kR, y1, y1)); }
-__device__ __forceinline__ float cp_smooth(const CompCoef& f, float y1, float yl) { return __builtin_fmaf(f.kA, y1 - yl, yl); }
 __device__ __forceinline__ float cp_apply(const CompCoef& f, float x, float yl) { return x * exp10f((f.makeup - yl) / 20.0f); }
 
 // kPass 1: s1[row][k] = y1 at the end of chunk k from y1 = 0.
@@ -58,37 +44,7 @@ __global__ void __launch_bounds__(LO_WG) compressor_chunk_kernel(const float* x,
     const int64_t s0 = (int64_t)blockIdx.x * CP_SPAN;
     const int cnt = (int)(W - s0 < CP_SPAN ? W - s0 : CP_SPAN);
     const float* xr = x + row * W + s0;
-    constexpr int U = CP_SPAN / 4 / LO_WG;
-    if (vec) {  // rows 16-byte aligned and W % 4 == 0: cnt % 4 == 0, a float4 that starts below cnt ends at or below it
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * LO_WG;
-            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = 4 * (threadIdx.x + u * LO_WG);
-            if (i < cnt) {
-                float* d = win + (i / LO_CHUNK) * CP_PAD + (i % LO_CHUNK);  // (the four samples share a chunk)
-                d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
-            }
-        }
-    } else {
-        for (int i0 = 0; i0 < CP_SPAN; i0 += 8 * LO_WG) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                v[u] = i < cnt ? xr[i] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                if (i < cnt) win[(i / LO_CHUNK) * CP_PAD + (i % LO_CHUNK)] = v[u];
-            }
-        }
-    }
+    chunk_stage_in<LO_WG, LO_CHUNK, false>(win, xr, cnt, vec);  // (W % 4 == 0 in the 16-byte form: so is cnt)
     __syncthreads();
     const int c0 = threadIdx.x * LO_CHUNK;
     if (c0 < cnt) {
@@ -99,15 +55,15 @@ __global__ void __launch_bounds__(LO_WG) compressor_chunk_kernel(const float* x,
             float y1 = 0.0f;
 #pragma unroll
             for (int i = 0; i < LO_CHUNK; ++i)
-                if (i < len) y1 = cp_peak(f, cp_want(f, w[i]), y1);
+                if (i < len) y1 = gain_peak(f.kR, gain_want(f.T, f.S, f.K, w[i]), y1);
             s1[row * Ks + k] = y1;
         } else if (kPass == 2) {
             float y1 = s1[row * Ks + k], yl = 0.0f;
 #pragma unroll
             for (int i = 0; i < LO_CHUNK; ++i) {
                 if (i < len) {
-                    y1 = cp_peak(f, cp_want(f, w[i]), y1);
-                    yl = cp_smooth(f, y1, yl);
+                    y1 = gain_peak(f.kR, gain_want(f.T, f.S, f.K, w[i]), y1);
+                    yl = gain_smooth(f.kA, y1, yl);
                 }
             }
             s2[row * Ks + k] = yl;
@@ -119,8 +75,8 @@ __global__ void __launch_bounds__(LO_WG) compressor_chunk_kernel(const float* x,
             for (int i = 0; i < LO_CHUNK; ++i) {
                 if (i < len) {
                     const float u = w[i];
-                    y1 = cp_peak(f, cp_want(f, u), y1);
-                    yl = cp_smooth(f, y1, yl);
+                    y1 = gain_peak(f.kR, gain_want(f.T, f.S, f.K, u), y1);
+                    yl = gain_smooth(f.kA, y1, yl);
                     if (g0 + i < n) m = fmaxf(m, yl);
                     if (gr) gr[row * W + g0 + i] = yl;  // (the op-level probe only: a fetch passes null)
                     w[i] = cp_apply(f, u, yl);
@@ -132,18 +88,7 @@ __global__ void __launch_bounds__(LO_WG) compressor_chunk_kernel(const float* x,
     if (kPass != 3) return;
     __syncthreads();
     float* yr = y + row * W + s0;
-    if (vec) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * LO_WG, i = 4 * q;
-            if (i < cnt) {
-                const float* d = win + (i / LO_CHUNK) * CP_PAD + (i % LO_CHUNK);
-                reinterpret_cast<float4*>(yr)[q] = make_float4(d[0], d[1], d[2], d[3]);
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < cnt; i += LO_WG) yr[i] = win[(i / LO_CHUNK) * CP_PAD + (i % LO_CHUNK)];
-    }
+    chunk_stage_out<LO_WG, LO_CHUNK>(win, yr, cnt, vec);
 }
 
 // kMax: (D, b) . v = max(v, D o); otherwise the linear v + E o
@@ -196,26 +141,17 @@ __global__ void __launch_bounds__(CP_ROWMAX) compressor_rowmax_kernel(int64_t K,
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
-bool cp_aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
-
-void cp_shape(int64_t rows, int64_t W) {
-    if (rows > 65535) throw std::invalid_argument("compressor: more than 65535 rows");
-    if (lo_chunks(W) > ((int64_t)1 << 31) / LO_WG) throw std::invalid_argument("compressor: row too long");
-}
-
 }  // namespace
 
-const char* compressor_staging_form(const float* x, const float* y, int64_t W) {
-    return W % 4 == 0 && cp_aligned16(x) && cp_aligned16(y) ? "vec" : "scalar";
-}
+const char* compressor_staging_form(const float* x, const float* y, int64_t W) { return chunk_vec(x, y, W) ? "vec" : "scalar"; }
 
 void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const CompTable& t, float* s1,
                               float* s2, float* y, float* gr, float* cmax) {
     if (rows <= 0 || W <= 0) return;
-    cp_shape(rows, W);
+    chunk_shape("compressor", rows, W);
     if (pass < 1 || pass > 3) throw std::invalid_argument("compressor: pass must be 1, 2 or 3");
     if (!x || !y || !s1 || (pass > 1 && !s2) || (pass == 3 && !cmax)) throw std::invalid_argument("compressor: null buffer");
-    const int vec = compressor_staging_form(x, y, W)[0] == 'v' ? 1 : 0;  // (one form for the three passes: that of the rows read and written)
+    const int vec = chunk_vec(x, y, W);  // (one form for the three passes: that of the rows read and written)
     const dim3 grid((unsigned)((W + CP_SPAN - 1) / CP_SPAN), (unsigned)rows);
     const int64_t Ks = lo_chunks(W);
     if (pass == 1) STN_KLAUNCH(compressor_chunk_kernel<1>, grid, dim3(LO_WG), 0, s, x, y, W, vec, Ks, t.coef, n, s1, s2, gr, cmax);
@@ -225,7 +161,7 @@ void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t r
 
 void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const CompTable& t, float* st) {
     if (rows <= 0 || W <= 0) return;
-    cp_shape(rows, W);
+    chunk_shape("compressor", rows, W);
     if (!t.dev || !st) throw std::invalid_argument("compressor: scan without its table or states");
     if (stage == 1) STN_KLAUNCH(compressor_scan_kernel<true>, dim3((unsigned)rows), dim3(LO_SCAN), 0, s, lo_chunks(W), t.dev, st);
     else STN_KLAUNCH(compressor_scan_kernel<false>, dim3((unsigned)rows), dim3(LO_SCAN), 0, s, lo_chunks(W), t.dev + LO_SCAN, st);
@@ -233,7 +169,7 @@ void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, c
 
 void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const float* cmax, float* out) {
     if (rows <= 0 || W <= 0) return;
-    cp_shape(rows, W);
+    chunk_shape("compressor", rows, W);
     STN_KLAUNCH(compressor_rowmax_kernel, dim3((unsigned)rows), dim3(CP_ROWMAX), 0, s, lo_chunks(W), cmax, out);
 }
 

@@ -15,11 +15,11 @@
 // is bound by its read of the rows, and a stored band would be one more write and three more reads of them.
 // Geometry and staging are compressor_chunk_kernel's: LO_WG chunks of LO_CHUNK samples through LDS at a row stride of 33 words, 16-byte
 // loads and stores or the scalar form by (x, y, W), in place allowed (a workgroup reads the samples it owns before the first barrier
-// and stores after the second).  ds_step restates fl_step (kernels_filter.hip) and ds_want / ds_peak / ds_smooth restate cp_want /
-// cp_peak / cp_smooth (kernels_compressor.hip) operation for operation: the start states the scans form are exact for that arithmetic
-// only, and those two units stay as they are.
+// and stores after the second).  The band's step is the filter chain's biquad2_step and the detector's steps are the compressor's
+// gain_want / gain_peak / gain_smooth (kernels_chunk.hpp, one definition each): the start states the scans form are exact for that
+// arithmetic only.
 // A row's y[0 .. n) depends on x[0 .. n) of that row and the coefficients only: the scans' order is fixed by the chunk index.
-#include "kernels.hpp"
+#include "kernels_chunk.hpp"
 
 #include <math.h>
 
@@ -30,31 +30,8 @@ namespace {
 constexpr int DS_SPAN = LO_WG * LO_CHUNK;  // samples a workgroup owns
 constexpr int DS_PAD = LO_CHUNK + 1;       // LDS words per chunk: the lanes' walks fall on distinct banks
 
-// one sample through the band's two sections: fl_step
-__device__ __forceinline__ float ds_step(const LoudCoef& f, float u, float& s1, float& s2, float& t1, float& t2) {
-    const float v = __builtin_fmaf(f.c[0], u, s1);
-    s1 = __builtin_fmaf(-f.c[3], v, __builtin_fmaf(f.c[1], u, s2));
-    s2 = __builtin_fmaf(-f.c[4], v, f.c[2] * u);
-    const float y = __builtin_fmaf(f.c[5], v, t1);
-    t1 = __builtin_fmaf(-f.c[8], y, __builtin_fmaf(f.c[6], v, t2));
-    t2 = __builtin_fmaf(-f.c[9], y, f.c[7] * v);
-    return y;
-}
-// the gain computer on the band's level: cp_want, then the range cap
-__device__ __forceinline__ float ds_want(const DeessCoef& f, float h) {
-    const float xg = 20.0f * log10f(fmaxf(fabsf(h), 1e-6f));
-    const float d = xg - f.T;
-    const float d2 = 2.0f * d;
-    float z;
-    if (d2 < -f.K) z = 0.0f;
-    else if (f.K > 0.0f && fabsf(d2) <= f.K) {
-        const float t = d + 0.5f * f.K;
-        z = (-f.S * (t * t)) / (2.0f * f.K);
-    } else z = -f.S * d;
-    return fminf(f.range, z);
-}
-__device__ __forceinline__ float ds_peak(const DeessCoef& f, float z, float y1) { return fmaxf(z, __builtin_fmaf(-f.kR, y1, y1)); }
-__device__ __forceinline__ float ds_smooth(const DeessCoef& f, float y1, float yl) { return __builtin_fmaf(f.kA, y1 - yl, yl); }
+// the gain computer on the band's level, capped at the range
+__device__ __forceinline__ float ds_want(const DeessCoef& f, float h) { return fminf(f.range, gain_want(f.T, f.S, f.K, h)); }
 // split: only the band is turned down.  g == 1 (yL == 0) hands x on as it is: the fma would turn a -0.0 under a negative h into +0.0
 template <bool kSplit>
 __device__ __forceinline__ float ds_apply(float x, float h, float yl) {
@@ -79,37 +56,7 @@ __global__ void __launch_bounds__(LO_WG) deesser_chunk_kernel(const float* x, fl
     const int64_t s0 = (int64_t)blockIdx.x * DS_SPAN;
     const int cnt = (int)(W - s0 < DS_SPAN ? W - s0 : DS_SPAN);
     const float* xr = x + row * W + s0;
-    constexpr int U = DS_SPAN / 4 / LO_WG;
-    if (vec) {  // rows 16-byte aligned and W % 4 == 0: cnt % 4 == 0, a float4 that starts below cnt ends at or below it
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * LO_WG;
-            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = 4 * (threadIdx.x + u * LO_WG);
-            if (i < cnt) {
-                float* d = win + (i / LO_CHUNK) * DS_PAD + (i % LO_CHUNK);  // (the four samples share a chunk)
-                d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
-            }
-        }
-    } else {
-        for (int i0 = 0; i0 < DS_SPAN; i0 += 8 * LO_WG) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                v[u] = i < cnt ? xr[i] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                if (i < cnt) win[(i / LO_CHUNK) * DS_PAD + (i % LO_CHUNK)] = v[u];
-            }
-        }
-    }
+    chunk_stage_in<LO_WG, LO_CHUNK, false>(win, xr, cnt, vec);  // (W % 4 == 0 in the 16-byte form: so is cnt)
     __syncthreads();
     const int c0 = threadIdx.x * LO_CHUNK;
     if (c0 < cnt) {
@@ -122,15 +69,15 @@ __global__ void __launch_bounds__(LO_WG) deesser_chunk_kernel(const float* x, fl
             float y1 = 0.0f;
 #pragma unroll
             for (int i = 0; i < LO_CHUNK; ++i)
-                if (i < len) y1 = ds_peak(f, ds_want(f, ds_step(f.band, w[i], b1, b2, b3, b4)), y1);
+                if (i < len) y1 = gain_peak(f.kR, ds_want(f, biquad2_step(f.band, w[i], b1, b2, b3, b4)), y1);
             s1[row * Ks + k] = y1;
         } else if (kPass == 2) {
             float y1 = s1[row * Ks + k], yl = 0.0f;
 #pragma unroll
             for (int i = 0; i < LO_CHUNK; ++i) {
                 if (i < len) {
-                    y1 = ds_peak(f, ds_want(f, ds_step(f.band, w[i], b1, b2, b3, b4)), y1);
-                    yl = ds_smooth(f, y1, yl);
+                    y1 = gain_peak(f.kR, ds_want(f, biquad2_step(f.band, w[i], b1, b2, b3, b4)), y1);
+                    yl = gain_smooth(f.kA, y1, yl);
                 }
             }
             s2[row * Ks + k] = yl;
@@ -142,9 +89,9 @@ __global__ void __launch_bounds__(LO_WG) deesser_chunk_kernel(const float* x, fl
             for (int i = 0; i < LO_CHUNK; ++i) {
                 if (i < len) {
                     const float u = w[i];
-                    const float h = ds_step(f.band, u, b1, b2, b3, b4);
-                    y1 = ds_peak(f, ds_want(f, h), y1);
-                    yl = ds_smooth(f, y1, yl);
+                    const float h = biquad2_step(f.band, u, b1, b2, b3, b4);
+                    y1 = gain_peak(f.kR, ds_want(f, h), y1);
+                    yl = gain_smooth(f.kA, y1, yl);
                     if (g0 + i < n) m = fmaxf(m, yl);
                     if (band) band[row * W + g0 + i] = h;  // (the op-level probes only: a fetch passes null for both)
                     if (gr) gr[row * W + g0 + i] = yl;
@@ -157,36 +104,20 @@ __global__ void __launch_bounds__(LO_WG) deesser_chunk_kernel(const float* x, fl
     if (kPass != 3) return;
     __syncthreads();
     float* yr = y + row * W + s0;
-    if (vec) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * LO_WG, i = 4 * q;
-            if (i < cnt) {
-                const float* d = win + (i / LO_CHUNK) * DS_PAD + (i % LO_CHUNK);
-                reinterpret_cast<float4*>(yr)[q] = make_float4(d[0], d[1], d[2], d[3]);
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < cnt; i += LO_WG) yr[i] = win[(i / LO_CHUNK) * DS_PAD + (i % LO_CHUNK)];
-    }
+    chunk_stage_out<LO_WG, LO_CHUNK>(win, yr, cnt, vec);
 }
-
-bool ds_aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 
 }  // namespace
 
-const char* deesser_staging_form(const float* x, const float* y, int64_t W) {
-    return W % 4 == 0 && ds_aligned16(x) && ds_aligned16(y) ? "vec" : "scalar";
-}
+const char* deesser_staging_form(const float* x, const float* y, int64_t W) { return chunk_vec(x, y, W) ? "vec" : "scalar"; }
 
 void launch_deesser_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const DeessTable& t, const float* st,
                            float* s1, float* s2, float* y, float* band, float* gr, float* cmax) {
     if (rows <= 0 || W <= 0) return;
-    if (rows > 65535) throw std::invalid_argument("deesser: more than 65535 rows");
-    if (lo_chunks(W) > ((int64_t)1 << 31) / LO_WG) throw std::invalid_argument("deesser: row too long");
+    chunk_shape("deesser", rows, W);
     if (pass < 1 || pass > 3) throw std::invalid_argument("deesser: pass must be 1, 2 or 3");
     if (!x || !y || !st || !s1 || (pass > 1 && !s2) || (pass == 3 && !cmax)) throw std::invalid_argument("deesser: null buffer");
-    const int vec = deesser_staging_form(x, y, W)[0] == 'v' ? 1 : 0;  // (one form for the three passes: that of the rows read and written)
+    const int vec = chunk_vec(x, y, W);  // (one form for the three passes: that of the rows read and written)
     const dim3 grid((unsigned)((W + DS_SPAN - 1) / DS_SPAN), (unsigned)rows);
     const int64_t Ks = lo_chunks(W);
     if (pass == 1) STN_KLAUNCH((deesser_chunk_kernel<1, true>), grid, dim3(LO_WG), 0, s, x, y, W, vec, Ks, t.coef, n, st, s1, s2, band, gr, cmax);

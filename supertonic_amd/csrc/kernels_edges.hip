@@ -3,7 +3,7 @@
 //
 // Frames of F samples (10 ms) from sample 0, the last one short; frame k's level m_k is the mean of x^2 over its own samples.
 //   1. frame pass: a lane owns ED_CHUNK consecutive samples of a row, counted from sample 0 (the energy pass of kernels_loudness.hip: a
-//      workgroup stages its ED_WG chunks in LDS with 16-byte loads, row stride 33 words), and sums x^2 in sample order into the chunk's
+//      workgroup stages its ED_WG chunks in LDS with 16-byte loads, row stride 33 words: chunk_stage_in, kernels_chunk.hpp), and sums x^2 in sample order into the chunk's
 //      share of the frame it starts in and of the next one (F > ED_CHUNK: a chunk meets two frames at most);
 //   2. row pass: one workgroup per row sums each frame's shares in chunk order (a thread per frame, in double), writes the levels,
 //      takes their maximum, finds the first and the last frame at or above the threshold, and writes the row's edges and the one-member
@@ -14,7 +14,7 @@
 // With the pause limit a third launch follows the row pass:
 //   3. pause pass: one workgroup per row reads the levels and the edges and writes the row's several segments, the row without the
 //      middle of every pause inside it that is longer than the limit (pause_rows_kernel, below the row pass).
-#include "kernels.hpp"
+#include "kernels_chunk.hpp"
 
 #include <math.h>
 
@@ -35,40 +35,7 @@ __global__ void __launch_bounds__(ED_WG) edges_chunk_kernel(const float* __restr
     if (s0 >= n) return;  // (the whole workgroup: nothing of the span lies in the row)
     const int cnt = (int)(n - s0 < ED_SPAN ? n - s0 : ED_SPAN);
     const float* __restrict__ xr = x + row * W + s0;
-    if (vec) {  // rows 16-byte aligned and W % 4 == 0: a float4 that starts below n ends at or below W
-        constexpr int U = ED_SPAN / 4 / ED_WG;
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * ED_WG;
-            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = 4 * (threadIdx.x + u * ED_WG);
-            if (i < cnt) {
-                float* d = win + (i / ED_CHUNK) * ED_PAD + (i % ED_CHUNK);  // (the four samples share a chunk)
-                d[0] = v[u].x;
-                if (i + 1 < cnt) d[1] = v[u].y;
-                if (i + 2 < cnt) d[2] = v[u].z;
-                if (i + 3 < cnt) d[3] = v[u].w;
-            }
-        }
-    } else {
-        for (int i0 = 0; i0 < ED_SPAN; i0 += 8 * ED_WG) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * ED_WG;
-                v[u] = i < cnt ? xr[i] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * ED_WG;
-                if (i < cnt) win[(i / ED_CHUNK) * ED_PAD + (i % ED_CHUNK)] = v[u];
-            }
-        }
-    }
+    chunk_stage_in<ED_WG, ED_CHUNK, true>(win, xr, cnt, vec);  // (a float4 that starts below n ends at or below W)
     __syncthreads();
     const int c0 = threadIdx.x * ED_CHUNK;
     if (c0 >= cnt) return;
@@ -289,7 +256,7 @@ static int edges_check(int64_t rows, int64_t W, int hz) {
 void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb) {
     if (rows <= 0 || W <= 0) return;
     const int F = edges_check(rows, W, hz);
-    const int vec = (W % 4 == 0 && !(reinterpret_cast<uintptr_t>(x) & 15)) ? 1 : 0;
+    const int vec = chunk_vec(x, nullptr, W);
     STN_KLAUNCH(edges_chunk_kernel, dim3((unsigned)((W + ED_SPAN - 1) / ED_SPAN), (unsigned)rows), dim3(ED_WG), 0, s, x, W, vec, n, ed_chunks(W), F, pa, pb);
 }
 

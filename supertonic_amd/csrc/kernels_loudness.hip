@@ -4,8 +4,8 @@
 // The K-weighting cascade (shelf biquad, then high-pass biquad, each in transposed direct form II) is one 4-state linear system
 // x' = A x + B u, state (s1, s2, t1, t2).  Decomposition:
 //   1. chunk pass: a lane owns LO_CHUNK consecutive samples of a row, counted from sample 0; a workgroup stages its LO_WG chunks in LDS
-//      with 16-byte loads (row stride 33 words: the lanes' walks fall on distinct banks), and each lane filters its chunk from zero
-//      state, writing the end state e_k and the chunk's max |x|;
+//      with 16-byte loads (row stride 33 words: the lanes' walks fall on distinct banks; chunk_stage_in, kernels_chunk.hpp), and each
+//      lane filters its chunk from zero state (biquad2_step, the same header), writing the end state e_k and the chunk's max |x|;
 //   2. scan: one workgroup per row forms the true start states s_{k+1} = M s_k + e_k (M = A^LO_CHUNK, its powers from the host) by a
 //      Hillis-Steele scan over tiles of LO_SCAN chunks, in place;
 //   3. energy pass: each lane refilters its chunk from s_k and sums y^2 into the chunk's share of the 100 ms segment it starts in and
@@ -15,7 +15,7 @@
 //   5. gain: y = x * g_b per sample, in the fetch's sample encoding (launch_store_rows, kernels_output.hip).
 // Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
 // row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
-#include "kernels.hpp"
+#include "kernels_chunk.hpp"
 
 #include <math.h>
 
@@ -26,17 +26,6 @@ namespace {
 constexpr int LO_SPAN = LO_WG * LO_CHUNK;  // samples a workgroup of the chunk passes owns
 constexpr int LO_PAD = LO_CHUNK + 1;       // LDS words per chunk
 constexpr int LO_GATE = 1024;              // threads of the gate workgroup
-
-// one sample through the cascade: shelf (b0 b1 b2 a1 a2 = c[0..4]) then high-pass (c[5..9]), transposed direct form II
-__device__ __forceinline__ float lo_step(const LoudCoef& f, float u, float& s1, float& s2, float& t1, float& t2) {
-    const float v = __builtin_fmaf(f.c[0], u, s1);
-    s1 = __builtin_fmaf(-f.c[3], v, __builtin_fmaf(f.c[1], u, s2));
-    s2 = __builtin_fmaf(-f.c[4], v, f.c[2] * u);
-    const float y = __builtin_fmaf(f.c[5], v, t1);
-    t1 = __builtin_fmaf(-f.c[8], y, __builtin_fmaf(f.c[6], v, t2));
-    t2 = __builtin_fmaf(-f.c[9], y, f.c[7] * v);
-    return y;
-}
 
 template <bool kEnergy>
 __global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __restrict__ x, int64_t W, int vec, const int64_t* __restrict__ nrow,
@@ -49,40 +38,7 @@ __global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __re
     if (s0 >= n) return;  // (the whole workgroup: nothing of the span lies in the row)
     const int cnt = (int)(n - s0 < LO_SPAN ? n - s0 : LO_SPAN);
     const float* __restrict__ xr = x + row * W + s0;
-    if (vec) {  // rows 16-byte aligned and W % 4 == 0: a float4 that starts below n ends at or below W
-        constexpr int U = LO_SPAN / 4 / LO_WG;
-        float4 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = threadIdx.x + u * LO_WG;
-            if (4 * q < cnt) v[u] = reinterpret_cast<const float4*>(xr)[q];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = 4 * (threadIdx.x + u * LO_WG);
-            if (i < cnt) {
-                float* d = win + (i / LO_CHUNK) * LO_PAD + (i % LO_CHUNK);  // (the four samples share a chunk)
-                d[0] = v[u].x;
-                if (i + 1 < cnt) d[1] = v[u].y;
-                if (i + 2 < cnt) d[2] = v[u].z;
-                if (i + 3 < cnt) d[3] = v[u].w;
-            }
-        }
-    } else {
-        for (int i0 = 0; i0 < LO_SPAN; i0 += 8 * LO_WG) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                v[u] = i < cnt ? xr[i] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + threadIdx.x + u * LO_WG;
-                if (i < cnt) win[(i / LO_CHUNK) * LO_PAD + (i % LO_CHUNK)] = v[u];
-            }
-        }
-    }
+    chunk_stage_in<LO_WG, LO_CHUNK, true>(win, xr, cnt, vec);  // (a float4 that starts below n ends at or below W)
     __syncthreads();
     const int c0 = threadIdx.x * LO_CHUNK;
     if (c0 >= cnt) return;
@@ -97,7 +53,7 @@ __global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __re
             if (i < len) {
                 const float u = w[i];
                 m = fmaxf(m, fabsf(u));
-                (void)lo_step(f, u, s1, s2, t1, t2);
+                (void)biquad2_step(f, u, s1, s2, t1, t2);
             }
         }
         *sk = make_float4(s1, s2, t1, t2);
@@ -111,7 +67,7 @@ __global__ void __launch_bounds__(LO_WG) loudness_chunk_kernel(const float* __re
 #pragma unroll
         for (int i = 0; i < LO_CHUNK; ++i) {
             if (i < len) {
-                const float y = lo_step(f, w[i], s1, s2, t1, t2);
+                const float y = biquad2_step(f, w[i], s1, s2, t1, t2);
                 const float yy = y * y;
                 const int64_t g = g0 + i;
                 a += (g < bound && g < full) ? yy : 0.0f;
@@ -252,25 +208,21 @@ __global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* _
     }
 }
 
-bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
-
 void lo_check(int64_t rows, int64_t W, const LoudTable& t) {
     if (rows > 65535) throw std::invalid_argument("loudness: more than 65535 rows");
     if (!t.dev || t.hop < 1) throw std::runtime_error("loudness: filter table not prepared");
     if (lo_chunks(W) > ((int64_t)1 << 31) / LO_WG) throw std::invalid_argument("loudness: row too long");
 }
 
-bool lo_vec(const float* x, int64_t W) { return W % 4 == 0 && aligned16(x); }
-
 }  // namespace
 
-const char* loudness_staging_form(const float* x, int64_t W) { return lo_vec(x, W) ? "vec" : "scalar"; }
+const char* loudness_staging_form(const float* x, int64_t W) { return chunk_vec(x, nullptr, W) ? "vec" : "scalar"; }
 
 void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
                             float* st, float* pk, float* pa, float* pb) {
     if (rows <= 0 || W <= 0) return;
     lo_check(rows, W, t);
-    const int vec = lo_vec(x, W) ? 1 : 0;
+    const int vec = chunk_vec(x, nullptr, W);
     const dim3 grid((unsigned)((W + LO_SPAN - 1) / LO_SPAN), (unsigned)rows);
     if (energy) STN_KLAUNCH(loudness_chunk_kernel<true>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
     else STN_KLAUNCH(loudness_chunk_kernel<false>, grid, dim3(LO_WG), 0, s, x, W, vec, n, lo_chunks(W), t.coef, t.hop, st, pk, pa, pb);
