@@ -465,6 +465,20 @@ int stn_op_pause_trim(stn_handle* h, int hz, int rows, int W, const float* x, co
 int stn_pause_plan(int hz, int64_t n, const double* level, int64_t K, float top_db, float keep_ms, float max_pause_ms, int64_t* start,
                    int64_t* end, int64_t* cuts, int cap_pairs, int32_t* n_cuts);
 const char* stn_pause_plan_error(void);
+/* The same detection (the same launches through the same launchers: the frame pass, the row pass and, with max_pause_ms > 0, the pause
+ * pass) on host operands with its scratch laid open (the kernel tests of every pass).  n_or_null, top_db, keep_ms and fade_ms as
+ * stn_op_silence_trim; max_pause_ms = 0: no pause pass (len = end - start, n_cuts = 0, cuts untouched), else as stn_op_pause_trim.
+ * x_misalign 0 / 1: x is uploaded 16-byte aligned / 4 bytes off, which forces the scalar staging path at W % 4 == 0.  Before the first
+ * launch every 32-bit word of the whole scratch (pa, pb, lev, the edges and the cut tables) is filled with 0x7FC00000 (a quiet NaN as a
+ * float; two such words as a double are 2^1021 * 1.0000005, no level), so an element no launch wrote comes back as that.  With
+ * Ks = (W + 31) / 32 chunks and Kf = ceil(W / F) frames per row: pa, pb [rows][Ks] (chunk k's sum of x^2 over its samples inside the
+ * span that lie before the next frame boundary, and over those from it on); lev [rows][Kf] (the frame levels m_k); start, end, len,
+ * n_cuts [rows] and cuts_or_null [rows][cap_pairs][2] as stn_op_pause_trim.  Every output may be NULL.  form: the staging path that ran, "vec" (16-byte
+ * loads) or "scalar", NUL-terminated, truncated to form_cap; may be NULL.  Refuses what stn_op_silence_trim and (with max_pause_ms
+ * != 0) stn_op_pause_trim refuse, and an x_misalign outside {0, 1}. */
+int stn_op_silence_edges_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float top_db, float keep_ms,
+                            float fade_ms, float max_pause_ms, int x_misalign, float* pa, float* pb, double* lev, int64_t* start,
+                            int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts_or_null, int cap_pairs, char* form, size_t form_cap);
 
 /* ---- limiter -----------------------------------------------------------------------------------------
  * A look-ahead peak limiter behind the loudness gain.  With the limiter on AND loudness on, the ceiling of stn_set_loudness is enforced

@@ -624,6 +624,8 @@ def load():
     L.stn_get_pause_limit.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf)]
     L.stn_batch_pauses.argtypes = [vp, vp, vp, vp, ci]
     L.stn_op_pause_trim.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, cf, vp, ci, vp, vp, vp, vp, vp, vp, ci]
+    L.stn_op_silence_edges_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ctypes.c_char_p,
+                                          ctypes.c_size_t]
     L.stn_group_set_pause_limit.argtypes = [vp, ci, cf]
     L.stn_set_limiter.argtypes = [vp, ci, cf]
     L.stn_get_limiter.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf)]
@@ -1538,6 +1540,27 @@ class Engine:
                                              float(fade_ms), float(max_pause_ms), None if g is None else g.ctypes.data, e, y.ctypes.data,
                                              start.ctypes.data, end.ctypes.data, ln.ctypes.data, nc.ctypes.data, cuts.ctypes.data, cuts.shape[1]))
         return dict(y=y, start=start, end=end, len=ln, n_cuts=nc, cuts=cuts)
+
+    def op_silence_edges_ex(self, x, hz, n=None, top_db=40.0, keep_ms=TRIM_KEEP_MS, fade_ms=TRIM_FADE_MS, max_pause_ms=0.0, x_misalign=0,
+                            cap_pairs=PAUSE_MAX_CUTS):
+        """The detection (and, with max_pause_ms > 0, the pause pass) with its scratch laid open (every 32-bit word 0x7FC00000 first) ->
+        dict: pa, pb [rows, Ks] float32 (the chunks' two frame shares), lev [rows, Kf] float64 (the frame levels), start, end, len [rows]
+        int64, n_cuts [rows] int32, cuts [rows, cap_pairs, 2] int64 with -1 behind a row's n_cuts, form ("vec" / "scalar": the staging
+        path that ran).  x_misalign = 1 uploads x 4 bytes off 16-byte alignment."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        F = max((int(hz) + 50) // 100, 1)
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        o = dict(pa=np.empty((rows, (W + 31) // 32), np.float32), pb=np.empty((rows, (W + 31) // 32), np.float32),
+                 lev=np.empty((rows, -(-W // F)), np.float64), start=np.empty(rows, np.int64), end=np.empty(rows, np.int64),
+                 len=np.empty(rows, np.int64), n_cuts=np.empty(rows, np.int32), cuts=np.full((rows, max(int(cap_pairs), 1), 2), -1, np.int64))
+        form = ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_silence_edges_ex(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(top_db), float(keep_ms),
+                                                   float(fade_ms), float(max_pause_ms), int(x_misalign),
+                                                   *(o[k].ctypes.data for k in ("pa", "pb", "lev", "start", "end", "len", "n_cuts", "cuts")),
+                                                   o["cuts"].shape[1], form, ctypes.sizeof(form)))
+        o["form"] = form.value.decode()
+        return o
 
     def set_limiter(self, lookahead_ms=None):
         """Look-ahead peak limiter behind the loudness gain: None = off (the default), True = 5 ms, or the look-ahead in milliseconds

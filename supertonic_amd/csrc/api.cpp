@@ -396,6 +396,16 @@ int stn_op_pause_trim(stn_handle* h, int hz, int rows, int W, const float* x, co
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pause_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
                  h->eng->op_pause_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, gain, enc, y, start, end, len, n_cuts, cuts, cap_pairs); })
 }
+int stn_op_silence_edges_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
+                            float max_pause_ms, int x_misalign, float* pa, float* pb, double* lev, int64_t* start, int64_t* end, int64_t* len,
+                            int32_t* n_cuts, int64_t* cuts, int cap_pairs, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_silence_edges_ex: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 need(x_misalign == 0 || x_misalign == 1, "stn_op_silence_edges_ex: x_misalign must be 0 or 1");
+                 stn::Engine::EdProbe p;
+                 p.x_misalign = x_misalign; p.pa = pa; p.pb = pb; p.lev = lev;
+                 h->eng->op_silence_edges_ex(hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, p, start, end, len, n_cuts, cuts, cap_pairs);
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
 int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_t* n) {
     if (hz < 1 || !stn::silence_check(1.0f, 0.0f, fade_ms).empty()) return STN_ERR_INVALID;
     try {

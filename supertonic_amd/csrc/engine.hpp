@@ -410,6 +410,19 @@ class Engine {
     // op_silence_trim with the pause limit: y rows hold the row's segments end to end from column 0
     void op_pause_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
                        const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs);
+    // The same detection (ed_enqueue itself: the frame pass, the row pass and, with max_pause_ms > 0, the pause pass) with its scratch
+    // laid open (the kernel tests): every 32-bit word of the scratch is 0x7FC00000 before the first launch (a NaN as a float; two of
+    // them as a double are 2^1021 * 1.0000005), x is uploaded 4 bytes off 16-byte alignment when x_misalign is set, and the per-chunk
+    // shares and the frame levels come back whole (host): pa / pb [rows][ed_chunks(W)], lev [rows][edges_frames(W, hz)]; any may be
+    // null.  max_pause_ms = 0: no pause pass, len = end - start and n_cuts = 0.
+    struct EdProbe {
+        int x_misalign = 0;
+        float *pa = nullptr, *pb = nullptr;
+        double* lev = nullptr;
+        const char* form = "";  // out: the staging path that ran
+    };
+    void op_silence_edges_ex(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
+                             EdProbe& probe, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs);
     // diagnostic: overwrite the finished batch's model-rate waveform ([B][L * chunk] host floats) and forget what was measured on it
     void dbg_batch_set_wav(const float* wav);
 

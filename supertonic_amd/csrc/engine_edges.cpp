@@ -263,6 +263,47 @@ void Engine::op_pause_trim(int hz, int rows, int W, const float* x, const int64_
     pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
 }
 
+void Engine::op_silence_edges_ex(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
+                                 EdProbe& probe, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    STN_HIP(hipSetDevice(device_));
+    const bool pauses = max_pause_ms != 0.0f;
+    refuse(silence_check(top_db, keep_ms, fade_ms));
+    if (pauses) refuse(pause_check(max_pause_ms));
+    refuse(rate_check(pauses ? "pause limit" : "silence trim", hz));
+    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument("op_silence_edges_ex: cuts needs cap_pairs >= 1");
+    const std::vector<int64_t> nn = spans("op_silence", rows, W, n);
+    const int64_t Mp = pauses ? pause_samples(hz, max_pause_ms) : 0;
+    const int S = pauses ? pause_stride(W, hz, Mp) : 0;
+    ar_.reset();
+    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, S).bytes)), rows, W, hz, S);
+    const size_t nx = (size_t)rows * W, off = probe.x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
+    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
+    // the whole scratch, the shares, the levels, the edges and the tables: what a launch fails to write reads back as this, not as an
+    // earlier call's value (every carved array is a multiple of 256 bytes)
+    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pa), 0x7FC00000, sc.bytes / 4, s_));
+    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc, Mp);
+    std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
+    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    if (S > 0) STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
+    const size_t nc = (size_t)rows * (size_t)ed_chunks(W), nf = (size_t)rows * (size_t)edges_frames(W, hz);
+    if (probe.pa) STN_HIP(hipMemcpyAsync(probe.pa, sc.pa, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
+    if (probe.pb) STN_HIP(hipMemcpyAsync(probe.pb, sc.pb, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
+    if (probe.lev) STN_HIP(hipMemcpyAsync(probe.lev, sc.lev, nf * sizeof(double), hipMemcpyDeviceToHost, s_));
+    probe.form = edges_staging_form(dx, W);
+    sync();  // (nn, e and pz are read or written by the copies above until here)
+    for (int r = 0; r < rows; ++r) {
+        if (start) start[r] = e[(size_t)r * 2];
+        if (end) end[r] = e[(size_t)r * 2 + 1];
+        if (S == 0) {
+            if (len) len[r] = e[(size_t)r * 2 + 1] - e[(size_t)r * 2];
+            if (n_cuts) n_cuts[r] = 0;
+        }
+    }
+    if (S > 0) pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
+}
+
 void Engine::dbg_batch_set_wav(const float* wav) {
     const int64_t Wo = out_row_len();  // (throws without a finished batch)
     (void)Wo;

@@ -458,6 +458,8 @@ inline int64_t edges_frames(int64_t W, int hz) { const int F = edges_frame(hz); 
 void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb);
 void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
                        const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog);
+// the staging path the frame pass takes for these rows: "vec" (16-byte loads: W % 4 == 0 and x 16-byte aligned) or "scalar"
+const char* edges_staging_form(const float* x, int64_t W);
 // The pause limit, behind launch_edges_rows on the same stream: lev and edges as that launch left them -> row r's
 // segments seg[r * S .. r * S + count) (the row's [start, end) without the middle of every pause longer than Mp samples, at most S - 1
 // cuts, the first in time order), prog[r] = {len_r, r * S, count} and cuts[r][2 S] = {count - 1, len_r, lo_0, hi_0, lo_1, ...}.

@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "supertonic_amd", "example_native")
 ENCS = ["f32", "pcm16", "pcm24", "mulaw", "alaw"]
 ZERO = {e: binding.ZERO_CODEWORD[binding.ENCODINGS[e]] for e in ENCS}
-RATES = [8000, 11025, 16000, 44100, 48000]
+RATES = [8000, 11025, 16000, 44100, 48000, 88200, 96000, 176400, 192000]  # frames of 80 to 1920 samples, as the edges run
 CAP = 8  # pairs of the cut tables asked for where a row has a handful of cuts
 
 
@@ -62,7 +62,7 @@ def _check_tables(got, want, cap):
     assert np.array_equal(got["cuts"], pz.cuts_array(want["cuts"], cap))
 
 
-# ---- 1. row shapes at five rates ---------------------------------------------------------------------------------------------------------
+# ---- 1. row shapes at nine rates ---------------------------------------------------------------------------------------------------------
 # frames: burst (first, count).  Designed for max_pause 20 ms (2 frames) and 100 ms (10 frames); the counts per row are stated beside them
 SHAPES = [
     ([(3, 40)], 0, 0),                                  # no pause

@@ -5,7 +5,8 @@ a batch whose waveform stn_dbg_batch_set_wav replaced with rows of known silence
 fetches; position independence; the off path; and the event-timed cost beside the store and the join on the same batch.
 
 Why the edges may be compared exactly: the device sums a frame's squares in fp32 chunks of 32 and the chunk shares in double, so a
-level is within about 1e-4 dB of the float64 mean (F <= 1920 terms); a row whose frames all lie 0.01 dB or more from the threshold,
+level is within 34 * 2^-24 relative, under 1e-5 dB, of the float64 mean at every F (tests/test_gpu_silence_kernels.py checks that bound
+on every frame); a row whose frames all lie 0.01 dB or more from the threshold,
 and whose loudest frame lies that far from the -70 dBFS floor, decides every frame as float64 does.  MARGIN_DB is that bound, and every
 row of every input here is asserted to clear it."""
 import itertools
