@@ -381,6 +381,41 @@ int stn_op_loudness_ex(stn_handle* h, int hz, int rows, int W, const float* x, c
  * STN_ERR_INVALID outside [8000, 192000] Hz. */
 int stn_loudness_table(int hz, float* coef10, float* mpow, size_t cap, int* hop);
 
+/* ---- loudness range ------------------------------------------------------------------------------------
+ * A report, not a setting: maximum momentary loudness, maximum short-term loudness (the limits of EBU R 128 s1, short-form content)
+ * and loudness range (LRA, EBU Tech 3342) of the signal, rows and spans that stn_batch_loudness measures, under every combination of
+ * settings (output rate, filters, de-esser, compressor, trimming, pause limit): the signal BEFORE the loudness gain.  LRA does not
+ * depend on the gain; while the limiter is off the two maxima after normalization are the reported values plus 20 log10(gain).
+ * Nothing is launched unless a report is asked for: no fetch, setting or captured graph changes.
+ * Row b's span is its first n_b samples, hop = (rate + 5) / 10 samples, seg[j] the sum of y^2 (K-weighted) over segment j,
+ * nseg = n_b / hop:
+ *   momentary   M_j = -0.691 + 10 log10((seg[j] + .. + seg[j+3]) / (4 hop)), j = 0 .. nseg - 4: the very blocks of the integrated
+ *               measurement, summed as (seg[j] + seg[j+1]) + (seg[j+2] + seg[j+3]).  m_max = max_j M_j, -inf when nseg < 4.
+ *   short-term  S_j = -0.691 + 10 log10((seg[j] + .. + seg[j+29]) / (30 hop)), j = 0 .. nseg - 30: whole 3 s windows inside the span
+ *               at a 100 ms hop, the 30 terms added left to right.  s_max = max_j S_j, -inf when nseg < 30.
+ *   range       of the S_j keep those with S_j > -70 (absolute gate); rel = -0.691 + 10 log10(mean of their window powers) - 20; keep
+ *               those with S_j > rel as well (relative gate).  n_st is the number kept; s[0 .. n_st - 1] the kept values ascending;
+ *               lra = s[floor((n_st - 1) * 0.95 + 0.5)] - s[floor((n_st - 1) * 0.10 + 0.5)] (the index rule of Tech 3342's reference
+ *               code), 0 when n_st < 2.
+ * A row's four numbers depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it (fixed-order
+ * sums, no atomics): the same bits run twice, alone or among others.  A row may hold at most 8192 segments (13 min 39 s; the
+ * integrated measurement takes 16384): beyond that STN_ERR_INVALID with a message that names the cap.  stn_group has no such report:
+ * ask the ranks' handles.  DESIGN.md section 22 has the decomposition, the LDS layout, the accuracy and the cost. */
+/* the finished batch at the current output rate, whether normalization is on or not; each pointer [B] or NULL.  STN_ERR_STATE without
+ * a finished batch. */
+int stn_batch_loudness_range(stn_handle* h, float* m_max, float* s_max, float* lra, int32_t* n_st);
+/* the joined signal measured as G programmes over the spans stn_batch_join_loudness uses; each pointer [G] or NULL; refuses what that
+ * call refuses */
+int stn_batch_join_loudness_range(stn_handle* h, const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st);
+/* op-level, host operands: rows x W fp32 at hz, row r's first n[r] samples (n_or_null = NULL: all W); each result [rows] or NULL.
+ * Refuses what stn_op_loudness refuses. */
+int stn_op_loudness_range(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float* m_max, float* s_max,
+                          float* lra, int32_t* n_st);
+/* The rule itself (host only, no device needed): the definition above in double on given segment sums seg[nseg] of hop samples each.
+ * Each result may be NULL.  STN_ERR_INVALID for hop < 1, nseg < 0 or seg NULL with nseg > 0.  The kernel's decisions are tested
+ * against this function. */
+int stn_loudness_range_rule(int hop, int64_t nseg, const double* seg, double* m_max, double* s_max, double* lra, int32_t* n_st);
+
 /* ---- silence trimming --------------------------------------------------------------------------------
  * With trimming on, every fetch path delivers each row without the silence in front of and behind its speech, found by level on the
  * GPU at fetch time.  It composes with the rate, the loudness, the encoding and the join; the latent geometry, the reported durations,

@@ -614,6 +614,8 @@ def load():
     L.stn_op_loudness_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_loudness_table.argtypes = [ci, vp, vp, ctypes.c_size_t, ctypes.POINTER(ci)]
     L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
+    L.stn_batch_loudness_range.argtypes = [vp, vp, vp, vp, vp]
+    L.stn_op_loudness_range.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp, vp, vp]
     L.stn_set_silence_trim.argtypes = [vp, ci, cf, cf, cf]
     L.stn_get_silence_trim.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf), ctypes.POINTER(cf), ctypes.POINTER(cf)]
     L.stn_batch_silence_edges.argtypes = [vp, vp, vp]
@@ -686,6 +688,7 @@ def load():
     L.stn_batch_copy_joined_device.argtypes = [vp, jp, ci, vp, ctypes.c_int64]
     L.stn_batch_fetch_joined_begin.argtypes = [vp, ci, jp, ci]
     L.stn_batch_join_loudness.argtypes = [vp, jp, vp, vp, vp]
+    L.stn_batch_join_loudness_range.argtypes = [vp, jp, vp, vp, vp, vp]
     L.stn_op_join.argtypes = [vp, ci, ci, ci, _f32p, _i64p, jp, ci, ci, cf, cf, vp, vp, vp, vp]
     L.stn_group_set_encoding.argtypes = [vp, ci]
     L.stn_group_fetch_encoded.argtypes = [vp, vp, ctypes.c_size_t, vp]
@@ -923,6 +926,22 @@ def pause_plan(level, n, hz, top_db=40.0, keep_ms=None, max_pause_ms=MAX_PAUSE_M
     if rc != 0:
         raise StnError(rc, L.stn_pause_plan_error().decode())
     return start.value, end.value, cuts[:min(nc.value, cuts.shape[0])], nc.value
+
+
+def loudness_range_rule(seg, hop):
+    """stn_loudness_range_rule (host only, no device): one row's 100 ms segment sums (float64 [nseg], sums of K-weighted y^2 over hop
+    samples each) -> (m_max, s_max, lra, n_st): maximum momentary and maximum short-term loudness (LUFS, -inf without a block / a
+    window), loudness range (LU, EBU Tech 3342) and the number of 3 s windows behind both gates.  include/stn.h "loudness range"."""
+    L = load()
+    L.stn_loudness_range_rule.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+    sg = np.ascontiguousarray(seg, np.float64).reshape(-1)
+    m, s, r, k = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int32()
+    rc = L.stn_loudness_range_rule(int(hop), sg.size, sg.ctypes.data if sg.size else None, ctypes.addressof(m), ctypes.addressof(s),
+                                   ctypes.addressof(r), ctypes.addressof(k))
+    if rc != 0:
+        raise StnError(rc, f"stn_loudness_range_rule: hop {hop} must be at least 1")
+    return m.value, s.value, r.value, k.value
 
 
 LIMITER_MS = 5.0
@@ -1435,6 +1454,36 @@ class Engine:
         self._ck(self._lib.stn_op_loudness(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, lufs.ctypes.data,
                                            peak.ctypes.data))
         return lufs, peak
+
+    @staticmethod
+    def _range_out(rows):
+        out = tuple(np.empty(rows, np.float32) for _ in range(3)) + (np.empty(rows, np.int32),)
+        return out, [a.ctypes.data for a in out]
+
+    def batch_loudness_range(self):
+        """The finished batch measured at the output rate, over the spans of batch_loudness -> (max_momentary [B], max_short_term [B],
+        range [B]) float32 and n_short_term [B] int32: the 400 ms and 3 s maxima in LUFS (-inf where the span holds no block / no
+        window), the loudness range in LU (EBU Tech 3342) and the 3 s windows behind its gates.  Measured before the loudness gain."""
+        out, ptr = self._range_out(self.batch_dims()[0])
+        self._ck(self._lib.stn_batch_loudness_range(self._h, *ptr))
+        return out
+
+    def batch_join_loudness_range(self, rows, gap_samples, gap_seconds, mode="whole"):
+        """batch_loudness_range of the joined signal measured as programmes (batch_join_loudness's spans) -> four arrays [G]."""
+        j, keep = _join(rows, gap_samples, gap_seconds, mode, JOIN_GAIN_PROG)
+        out, ptr = self._range_out(keep[0].size)
+        self._ck(self._lib.stn_batch_join_loudness_range(self._h, ctypes.byref(j), *ptr))
+        return out
+
+    def op_loudness_range(self, x, hz, n=None):
+        """rows x W fp32 at hz on the GPU -> (max_momentary, max_short_term, range, n_short_term) [rows] over row r's first n[r] samples
+        (None: all W)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        out, ptr = self._range_out(rows)
+        self._ck(self._lib.stn_op_loudness_range(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, *ptr))
+        return out
 
     def op_loudness_ex(self, x, hz, n=None, on=False, target_lufs=-23.0, ceiling_dbfs=-1.0, x_misalign=0):
         """op_loudness with its scratch laid open (poisoned with the quiet NaN 0x7FC00000 first) -> dict: st_end, st_start [rows, Ks, 4]

@@ -736,6 +736,17 @@ int stn_batch_fetch_joined_begin(stn_handle* h, int slot, const stn_join* j, int
 int stn_batch_join_loudness(stn_handle* h, const stn_join* j, float* lufs, float* peak, float* gain) {
     STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h); h->eng->batch_join_loudness(j, lufs, peak, gain); })
 }
+int stn_batch_loudness_range(stn_handle* h, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    STN_TRY(h, { need_batch(h); h->eng->batch_loudness_range(m_max, s_max, lra, n_st); })
+}
+int stn_batch_join_loudness_range(stn_handle* h, const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h); h->eng->batch_join_loudness_range(j, m_max, s_max, lra, n_st); })
+}
+int stn_op_loudness_range(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float* m_max, float* s_max, float* lra,
+                          int32_t* n_st) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness_range: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 h->eng->op_loudness_range(hz, rows, W, x, n, m_max, s_max, lra, n_st); })
+}
 int stn_op_join(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, int loudness_on, float target_lufs,
                 float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && n && j && y, "stn_op_join: bad argument (1 <= rows <= 65535, W >= 1, x, n, j and y)");

@@ -20,13 +20,17 @@
 // --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] (every utterance through the de-esser on the GPU,
 // behind the filters and in front of the compressor: the band above FREQ turned down by up to RANGE_DB while its level is over THRESHOLD;
 // ratio 4, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, MODE split (the band alone; wide: the whole signal) when left out),
-// --deesser-preset speech (5500 Hz, -30 dB and those).
+// --deesser-preset speech (5500 Hz, -30 dB and those),
+// --loudness-report (after each saved file one line "Loudness: integrated .. LUFS, range .. LU, max momentary .. LUFS, max short-term ..
+// LUFS (N short-term windows), peak .., gain ..": measured on the GPU before the loudness gain, three decimals, a long text as the
+// joined programme; one GPU only).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
 
 #include <cmath>
 #include <cstdlib>
+#include <cstdio>
 #include <fstream>
 #include <iostream>
 
@@ -43,6 +47,12 @@ std::vector<std::string> split(const std::string& s, char delim) {
     return out;
 }
 bool exists(const std::string& p) { std::ifstream f(p); return f.is_open(); }
+std::string db3(float v) {  // three decimals, the infinities spelled "-inf" / "inf"
+    if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
+    char buf[32];
+    std::snprintf(buf, sizeof(buf), "%.3f", (double)v);
+    return buf;
+}
 void make_dirs(const std::string& path) {
     for (size_t i = 1; i <= path.size(); ++i)
         if (i == path.size() || path[i] == '/') ::mkdir(path.substr(0, i).c_str(), 0755);
@@ -58,7 +68,7 @@ int main(int argc, char* argv[]) {
     std::vector<std::string> text = {"This morning, I took a walk in the park, and the sound of the birds and the breeze was so "
                                      "pleasant that I stopped for a long time just to listen."};
     std::vector<std::string> lang = {"en"};
-    bool batch = false, peak_mode_given = false;
+    bool batch = false, peak_mode_given = false, loudness_report = false;
     EngineOptions opts;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -124,6 +134,7 @@ int main(int argc, char* argv[]) {
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.deesser_on = true;
         }
+        else if (a == "--loudness-report") loudness_report = true;  // one line of loudness figures after each saved file
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (opts.filters.size() > (size_t)STN_MAX_FILTERS) {
@@ -140,6 +151,10 @@ int main(int argc, char* argv[]) {
     }
     if (!std::isnan(opts.limiter_ms) && std::isnan(opts.loudness_lufs)) {
         std::cerr << "Error: --limiter needs --loudness (the limiter holds the ceiling of the loudness gain)\n";
+        return 1;
+    }
+    if (loudness_report && (opts.gpus > 1 || opts.devices.size() > 1)) {
+        std::cerr << "Error: --loudness-report needs the batch on one device (leave --gpus N / --devices out)\n";
         return 1;
     }
     if (voice_style.size() != text.size()) {
@@ -170,6 +185,8 @@ int main(int argc, char* argv[]) {
                 return batch ? tts->batch(text, lang, style, total_step, speed) : tts->call(text[0], lang[0], style, total_step, speed);
             });
             const int sr = tts->getSampleRate();
+            TextToSpeech::LoudnessReport rep;
+            if (loudness_report) rep = tts->loudnessReport();
             const size_t eb = result.wav.empty() ? (size_t)stn_encoding_bytes(result.encoding) : 0;  // 0: the float waveform
             const size_t per = (eb ? result.encoded.size() / eb : result.wav.size()) / (size_t)bsz;
             for (int b = 0; b < bsz; ++b) {
@@ -184,6 +201,10 @@ int main(int argc, char* argv[]) {
                     writeWavFile(save_dir + "/" + fname, out, sr);
                 }
                 std::cout << "Saved: " << save_dir << "/" << fname << "\n";
+                if (loudness_report && (size_t)b < rep.integrated.size())
+                    std::cout << "Loudness: integrated " << db3(rep.integrated[b]) << " LUFS, range " << db3(rep.range[b]) << " LU, max momentary "
+                              << db3(rep.max_momentary[b]) << " LUFS, max short-term " << db3(rep.max_short_term[b]) << " LUFS ("
+                              << rep.n_short_term[b] << " short-term windows), peak " << db3(rep.peak[b]) << ", gain " << db3(rep.gain[b]) << "\n";
             }
         }
     } catch (const std::exception& e) {

@@ -382,6 +382,12 @@ class Engine {
     };
     void op_loudness_ex(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe& probe,
                         float* lufs, float* peak, float* gain);
+    // ---- loudness report (engine_loudness.cpp; include/stn.h "loudness range"): maximum momentary loudness,
+    // maximum short-term loudness, loudness range and the number of 3 s windows behind its gates, of the rows and spans the calls above
+    // measure.  One more launch behind the measurement's, on its scratch; a report only: no fetch launches it.  [rows] host values or null.
+    void batch_loudness_range(float* m_max, float* s_max, float* lra, int32_t* n_st);
+    void batch_join_loudness_range(const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st);  // [G]
+    void op_loudness_range(int hz, int rows, int W, const float* x, const int64_t* n, float* m_max, float* s_max, float* lra, int32_t* n_st);
 
     // ---- silence trimming (engine_edges.cpp; include/stn.h "silence trimming"): off is the default (every fetch
     // path is then exactly the one without it).  On, every fetch path finds row b's edges [start_b, end_b) by level at the output rate
@@ -792,6 +798,11 @@ class Engine {
     bool lo_true_peak() const { return true_peak_on() && !limiter_active(); }
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream
     LoRes lo_batch(const float* x, int64_t Wo, bool on);
+    // the report's launch on what the measurement of rows x W just left in lo_buf_ (pa, pb and the lengths) and its read-back, no sync;
+    // max_seg: the longest span in segments (lr_max_seg: of the lengths lo_rows uploaded last)
+    DevBuf lr_buf_;                    // the report's results: [3][rows] floats, [rows] counts
+    int64_t lr_max_seg(const LoudTable& t) const;
+    void lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st);
     // ---- filter chain (engine_filter.cpp)
     std::vector<stn_filter> fl_set_;   // the chain in force
     uint64_t fl_gen_ = 0;              // bumped by every set_filters: part of EdKey (edges found on other rows must not be reused)

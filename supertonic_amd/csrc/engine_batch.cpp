@@ -818,6 +818,14 @@ void Engine::batch_join_loudness(const stn_join* j, float* lufs, float* peak, fl
     sync();
 }
 
+void Engine::batch_join_loudness_range(const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    const JoinPlan p = batch_join_plan(j);
+    if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
+    (void)join_measure(p, join_f32(p), lo_on_);
+    lr_report(lo_, p.G, p.W_join, lr_max_seg(lo_), m_max, s_max, lra, n_st);
+    sync();
+}
+
 void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, bool loudness_on, float target_lufs,
                      float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
     const int eb = need_enc(enc);

@@ -250,6 +250,53 @@ void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t*
     lo_op(hz, rows, W, x, n, false, lo_target_, lo_ceiling_, nullptr, lufs, peak, nullptr);
 }
 
+// ---- the loudness report
+
+int64_t Engine::lr_max_seg(const LoudTable& t) const {
+    int64_t m = 0;
+    for (int64_t v : lo_n_) m = std::max<int64_t>(m, v / t.hop);
+    return m;
+}
+
+void Engine::lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    refuse(loudness_range_check(max_seg));
+    const LoScratch sc = lo_scratch(rows, W);  // (as the measurement carved it: the same size moves nothing)
+    Carve sz{nullptr};
+    sz.take<float>((size_t)rows * 3);
+    sz.take<int32_t>((size_t)rows);
+    Carve c{lr_buf_.reserve(*this, sz.off)};
+    float* res = c.take<float>((size_t)rows * 3);
+    int32_t* nst = c.take<int32_t>((size_t)rows);
+    {
+        const double chunks = (double)rows * lo_chunks(W);
+        StageSpan span(*this, "out", "loudness_range", chunks * 2, chunks * 8 + (double)rows * 16);
+        launch_loudness_range(s_, rows, W, sc.n, t, sc.pa, sc.pb, max_seg, res, nst);
+    }
+    STN_HIP(hipGetLastError());
+    const size_t n = (size_t)rows;
+    if (m_max) STN_HIP(hipMemcpyAsync(m_max, res, n * 4, hipMemcpyDeviceToHost, s_));
+    if (s_max) STN_HIP(hipMemcpyAsync(s_max, res + n, n * 4, hipMemcpyDeviceToHost, s_));
+    if (lra) STN_HIP(hipMemcpyAsync(lra, res + 2 * n, n * 4, hipMemcpyDeviceToHost, s_));
+    if (n_st) STN_HIP(hipMemcpyAsync(n_st, nst, n * 4, hipMemcpyDeviceToHost, s_));
+}
+
+void Engine::batch_loudness_range(float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    const int64_t Wo = out_row_len();
+    (void)lo_batch(out_source(Wo), Wo, lo_on_);
+    lr_report(lo_, bt_.B, Wo, lr_max_seg(lo_), m_max, s_max, lra, n_st);
+    sync();
+}
+
+void Engine::op_loudness_range(int hz, int rows, int W, const float* x, const int64_t* n, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+    refuse(rate_check("loudness", hz));
+    int64_t max_seg = 0;
+    for (int64_t v : spans("op_loudness_range", rows, W, n)) max_seg = std::max<int64_t>(max_seg, v / ((hz + 5) / 10));
+    refuse(loudness_range_check(max_seg));  // (before the upload and the measurement, which a longer row passes)
+    lo_op(hz, rows, W, x, n, false, lo_target_, lo_ceiling_, nullptr, nullptr, nullptr, nullptr);
+    lr_report(op_lo_, rows, W, max_seg, m_max, s_max, lra, n_st);
+    sync();
+}
+
 void Engine::op_loudness_ex(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe& probe,
                             float* lufs, float* peak, float* gain) {
     lo_op(hz, rows, W, x, n, on, target, ceiling, &probe, lufs, peak, gain);

@@ -84,6 +84,7 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
         return r;
     }
     runBatch(tb, mask, style, total_step, speed);
+    join_members_ = 0;
     int B = 0, L = 0;
     int64_t W = 0;
     check(h_, stn_batch_dims(h_, &B, &L, &W));
@@ -183,6 +184,8 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
             check(h_, stn_batch_fetch_joined(h_, &j, STN_ENC_F32, out.wav.data(), out.wav.size() * sizeof(float), nullptr, out.duration.data()));
         }
         if (trim_silence_) out.length = {W_join};  // (one programme: its length is the joined segments')
+        join_members_ = members;
+        join_silence_ = silence_duration;
         return out;
     }
     // a group deals the chunks over its devices: its long form keeps the host join of the gathered rows
@@ -214,6 +217,30 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
     }
     out.duration = {dur_cat};
     return out;
+}
+
+TextToSpeech::LoudnessReport TextToSpeech::loudnessReport() {
+    if (grp_) throw std::runtime_error("the loudness report needs the batch on one device: a group has none (use one GPU)");
+    LoudnessReport r;
+    auto size = [&](size_t n) {
+        for (std::vector<float>* v : {&r.integrated, &r.peak, &r.gain, &r.max_momentary, &r.max_short_term, &r.range}) v->resize(n);
+        r.n_short_term.resize(n);
+    };
+    if (join_members_ > 0) {  // the joined text as call() joined it
+        const int64_t gap = (int64_t)(int)(join_silence_ * (float)getSampleRate());
+        stn_join j{1, &join_members_, &gap, &join_silence_, trim_chunks_ ? STN_JOIN_TRIM : STN_JOIN_WHOLE, STN_JOIN_GAIN_PROG};
+        size(1);
+        check(h_, stn_batch_join_loudness(h_, &j, r.integrated.data(), r.peak.data(), r.gain.data()));
+        check(h_, stn_batch_join_loudness_range(h_, &j, r.max_momentary.data(), r.max_short_term.data(), r.range.data(), r.n_short_term.data()));
+        return r;
+    }
+    int B = 0, L = 0;
+    int64_t W = 0;
+    check(h_, stn_batch_dims(h_, &B, &L, &W));
+    size((size_t)B);
+    check(h_, stn_batch_loudness(h_, r.integrated.data(), r.peak.data(), r.gain.data()));
+    check(h_, stn_batch_loudness_range(h_, r.max_momentary.data(), r.max_short_term.data(), r.range.data(), r.n_short_term.data()));
+    return r;
 }
 
 void TextToSpeech::setEncoding(int enc) {

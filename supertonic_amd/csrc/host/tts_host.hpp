@@ -141,6 +141,12 @@ class TextToSpeech {
     // with silence trimming on: every pause inside an utterance longer than max_pause_ms shortened to it (stn_set_pause_limit; stn.h
     // "pause limit"); the lengths are then what the cuts leave.  One device only, and refused without trimming.
     void setPauseLimit(bool on, float max_pause_ms = 300.0f);
+    // The loudness of what the last batch() / call() returned, measured on the GPU before the loudness gain (stn.h "loudness range"):
+    // per row after batch() (and after a call() that was one chunk), one entry for the joined text after call().  integrated, peak and
+    // gain as stn_batch_loudness / stn_batch_join_loudness report them; max_momentary and max_short_term in LUFS (-inf where the
+    // audio is shorter than 400 ms / 3 s); range in LU; n_short_term the 3 s windows behind the range's gates.  Refused on a group.
+    struct LoudnessReport { std::vector<float> integrated, peak, gain, max_momentary, max_short_term, range; std::vector<int32_t> n_short_term; };
+    LoudnessReport loudnessReport();
     int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device
@@ -160,6 +166,8 @@ class TextToSpeech {
     uint64_t calls_ = 0;
     int out_rate_ = 0;  // 0: the model's rate
     int enc_ = STN_ENC_PCM16;
+    int32_t join_members_ = 0;  // the last result: a join of this many rows with join_silence_ between them (0: the batch's rows)
+    float join_silence_ = 0.f;
     bool synthetic_ = false;
 };
 

@@ -535,6 +535,14 @@ void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t*
 void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pk, const float* pa,
                           const float* pb, int64_t max_seg, bool on, float target_lufs, float ceiling_dbfs, float* res);
 // (the gain itself is applied by launch_store_rows with g = res + 2 * rows)
+// The loudness report on the pa / pb the energy pass left: res[0][b] = maximum momentary loudness, res[1][b] =
+// maximum short-term loudness (-inf without a block / a window), res[2][b] = loudness range, nst[b] = the 3 s windows behind both
+// gates.  The rule is host/loudness_range.hpp's.  The kernel holds a row's segments and its window powers in LDS side by side, so it
+// takes LR_MAX_SEG segments per row where the gate takes LO_MAX_SEG; beyond that std::invalid_argument names the cap.
+constexpr int LR_MAX_SEG = 8192;      // 100 ms segments per row (13 min 39 s); a power of two
+std::string loudness_range_check(int64_t max_seg);  // why rows of up to max_seg segments are refused (it names the cap), or ""
+void launch_loudness_range(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pa, const float* pb,
+                           int64_t max_seg, float* res, int32_t* nst);
 // the powers M^1 .. M^LO_SCAN ([LO_SCAN][16], double) of M = A^LO_CHUNK for the two-section cascade with the fp32 coefficients c
 // (b0 b1 b2 a1 a2 twice): what the scan reads, for the K-weighting and for a section pass of the filter chain alike (host only)
 void cascade_powers(const LoudCoef& c, std::vector<double>& mpow);

@@ -16,6 +16,7 @@
 // Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
 // row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
 #include "kernels_chunk.hpp"
+#include "host/loudness_range.hpp"
 
 #include <math.h>
 
@@ -140,6 +141,19 @@ __device__ double lo_block_sum(double v, double* red) {
     return s;
 }
 
+// 100 ms segment sums of a row (the gate's and the range kernel's): a wave per segment, its lanes strided over the chunks that touch it
+// from the segment's first chunk on.  The caller synchronizes before it reads seg.
+__device__ __forceinline__ void lo_segments(const float* __restrict__ par, const float* __restrict__ pbr, int64_t nseg, int hop, double* seg) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t j = threadIdx.x >> 6; j < nseg; j += LO_GATE / 64) {
+        const int64_t k0 = j * hop / LO_CHUNK, k1 = ((j + 1) * hop - 1) / LO_CHUNK;
+        double a = 0.0;
+        for (int64_t k = k0 + lane; k <= k1; k += 64) a += (k * LO_CHUNK / hop == j) ? (double)par[k] : (double)pbr[k];
+        a = lo_wave_sum(a);
+        if (lane == 0) seg[j] = a;
+    }
+}
+
 __global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* __restrict__ nrow, int64_t Ks, int hop, const float* __restrict__ pk,
                                                                 const float* __restrict__ pa, const float* __restrict__ pb, int on, float target,
                                                                 float ceiling, int64_t rows, float* __restrict__ res) {
@@ -162,14 +176,7 @@ __global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* _
     __syncthreads();
     float peak = 0.f;
     for (int w = 0; w < LO_GATE / 64; ++w) peak = fmaxf(peak, redm[w]);
-    // 100 ms segment sums: a wave per segment, its lanes strided over the chunks that touch it from the segment's first chunk on
-    for (int64_t j = wave; j < nseg; j += LO_GATE / 64) {
-        const int64_t k0 = j * hop / LO_CHUNK, k1 = ((j + 1) * hop - 1) / LO_CHUNK;
-        double a = 0.0;
-        for (int64_t k = k0 + lane; k <= k1; k += 64) a += (k * LO_CHUNK / hop == j) ? (double)par[k] : (double)pbr[k];
-        a = lo_wave_sum(a);
-        if (lane == 0) seg[j] = a;
-    }
+    lo_segments(par, pbr, nseg, hop, seg);
     __syncthreads();
     // 400 ms blocks at a 100 ms hop, both gates
     const int64_t nblk = nseg >= 4 ? nseg - 3 : 0;
@@ -205,6 +212,82 @@ __global__ void __launch_bounds__(LO_GATE) loudness_gate_kernel(const int64_t* _
         res[row] = Lf;
         res[rows + row] = peak;
         res[2 * rows + row] = g;
+    }
+}
+
+// the workgroup's maximum of v (order-independent, so exact)
+__device__ double lo_block_max(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = red[0];
+    for (int w = 1; w < LO_GATE / 64; ++w) m = fmax(m, red[w]);
+    __syncthreads();
+    return m;
+}
+
+// The loudness report behind the same three passes: one workgroup per row.  LDS: seg[segcap] (the row's segment
+// sums, formed as the gate forms them) and behind it key[P], the powers of the 3 s windows, P the power of two at or above the row's
+// window count.  A window the gates drop, and the padding, hold +inf, so an ascending bitonic sort of key leaves the n_st kept powers
+// in front; the power is monotone in the level, so the order statistics are read there.  Every compare-exchange of a sort stage owns
+// its two elements and the stages are separated by barriers: nothing depends on thread timing.  res [3][rows]: m_max, s_max, lra.
+__global__ void __launch_bounds__(LO_GATE) loudness_range_kernel(const int64_t* __restrict__ nrow, int64_t Ks, int hop, const float* __restrict__ pa,
+                                                                 const float* __restrict__ pb, int segcap, int64_t rows, float* __restrict__ res,
+                                                                 int32_t* __restrict__ nst) {
+    extern __shared__ double seg[];
+    __shared__ double red[LO_GATE / 64];
+    double* key = seg + segcap;
+    const int64_t row = blockIdx.x;
+    int64_t nseg = nrow[row] / hop;
+    if (nseg > segcap) nseg = segcap;  // (never taken: the launcher sized the LDS by the longest row)
+    const int tid = threadIdx.x;
+    lo_segments(pa + row * Ks, pb + row * Ks, nseg, hop, seg);
+    __syncthreads();
+    const int nblk = nseg >= LR_BLOCK ? (int)nseg - (LR_BLOCK - 1) : 0, nwin = nseg >= LR_WINDOW ? (int)nseg - (LR_WINDOW - 1) : 0;
+    double zm = -1.0;
+    for (int j = tid; j < nblk; j += LO_GATE) zm = fmax(zm, lr_block_power(seg + j, hop));
+    zm = lo_block_max(zm, red);
+    int P = 1;
+    while (P < nwin) P <<= 1;
+    // the window powers, their maximum and the absolute gate (thread tid owns key[tid], key[tid + LO_GATE], ... in this pass and the next)
+    double zs = -1.0, as = 0.0, ac = 0.0;
+    for (int j = tid; j < P; j += LO_GATE) {
+        double z = INFINITY;
+        if (j < nwin) {
+            z = lr_window_power(seg + j, hop);
+            zs = fmax(zs, z);
+            if (lr_level(z) > LR_ABS_GATE) { as += z; ac += 1.0; }
+        }
+        key[j] = z;
+    }
+    zs = lo_block_max(zs, red);
+    as = lo_block_sum(as, red);
+    ac = lo_block_sum(ac, red);
+    // the relative gate
+    double kc = 0.0;
+    const double rel = ac > 0.0 ? lr_level(as / ac) + LR_REL_GATE : INFINITY;
+    for (int j = tid; j < nwin; j += LO_GATE) {
+        const double l = lr_level(key[j]);
+        if (l > LR_ABS_GATE && l > rel) kc += 1.0;
+        else key[j] = INFINITY;
+    }
+    kc = lo_block_sum(kc, red);  // (its barriers also order the writes above before the sort's reads)
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P / 2; t += LO_GATE) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                const double a = key[i], b = key[p];
+                if ((a > b) == ((i & k) == 0)) { key[i] = b; key[p] = a; }
+            }
+            __syncthreads();
+        }
+    if (tid == 0) {
+        const int64_t n = (int64_t)kc;
+        res[row] = zm < 0.0 ? -INFINITY : (float)lr_level(zm);
+        res[rows + row] = zs < 0.0 ? -INFINITY : (float)lr_level(zs);
+        res[2 * rows + row] = n < 2 ? 0.0f : (float)(lr_level(key[lr_index(n, LR_HIGH)]) - lr_level(key[lr_index(n, LR_LOW)]));
+        nst[row] = (int32_t)n;
     }
 }
 
@@ -246,6 +329,28 @@ void launch_loudness_gate(hipStream_t s, int64_t rows, int64_t W, const int64_t*
                                           (int)(LO_MAX_SEG * sizeof(double))), "hipFuncSetAttribute(loudness_gate)");
     STN_KLAUNCH(loudness_gate_kernel, dim3((unsigned)rows), dim3(LO_GATE), lds, s, n, lo_chunks(W), t.hop, pk, pa, pb, on ? 1 : 0, target_lufs,
                 ceiling_dbfs, rows, res);
+}
+
+std::string loudness_range_check(int64_t max_seg) {
+    if (max_seg <= LR_MAX_SEG) return "";
+    return "loudness range: a row of " + std::to_string(max_seg) + " 100 ms segments, and the report takes at most " + std::to_string(LR_MAX_SEG);
+}
+
+void launch_loudness_range(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pa, const float* pb,
+                           int64_t max_seg, float* res, int32_t* nst) {
+    if (rows <= 0 || W <= 0) return;
+    lo_check(rows, W, t);
+    const std::string why = loudness_range_check(max_seg);
+    if (!why.empty()) throw std::invalid_argument(why);
+    const int segcap = (int)(max_seg > 0 ? max_seg : 1);
+    int P = 1;
+    while (P < segcap - (LR_WINDOW - 1)) P <<= 1;
+    static PerDeviceOnce attr_once;
+    if (attr_once.need())
+        stn_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&loudness_range_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(2 * LR_MAX_SEG * sizeof(double))), "hipFuncSetAttribute(loudness_range)");
+    STN_KLAUNCH(loudness_range_kernel, dim3((unsigned)rows), dim3(LO_GATE), (unsigned)((segcap + P) * sizeof(double)), s, n, lo_chunks(W), t.hop, pa, pb,
+                segcap, rows, res, nst);
 }
 
 }  // namespace stn

@@ -8,6 +8,7 @@ included; a `batch: true` request keeps the reference's semantics (its own padde
 
     TTS_ONNX_DIR=assets/onnx TTS_DTYPE=bf16 uvicorn supertonic_amd.service:app
 """
+import contextlib
 import io
 import os
 import threading
@@ -23,6 +24,9 @@ from .output import OutputSettings
 from .tts import Style, load_text_to_speech, load_voice_style
 
 AVAILABLE_LANGS = host.AVAILABLE_LANGS
+# response header -> its entry of TextToSpeech.loudness_report (a request with "loudness_report": true; three decimals, -inf spelled so)
+REPORT_HEADERS = {"X-Loudness-Integrated": "integrated", "X-Loudness-Range": "range", "X-Loudness-Max-Momentary": "max_momentary",
+                  "X-Loudness-Max-Short-Term": "max_short_term"}
 
 
 # what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
@@ -67,12 +71,13 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
 
 
 class _Job:
-    __slots__ = ("texts", "lang", "style", "key", "silence", "done", "waves", "durs", "error")
+    __slots__ = ("texts", "lang", "style", "key", "silence", "done", "waves", "durs", "error", "want_report", "report")
 
-    def __init__(self, texts, lang, style, key, silence=None):
+    def __init__(self, texts, lang, style, key, silence=None, want_report=False):
         self.texts, self.lang, self.style, self.key, self.silence = texts, lang, style, key, silence
         self.done = threading.Event()
         self.waves = self.durs = self.error = None
+        self.want_report, self.report = bool(want_report), None
 
 
 class DynamicBatcher:
@@ -89,13 +94,15 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, *request, silence_duration=None, **request_kw):
+    def submit(self, texts, lang, style, *request, silence_duration=None, loudness_report=False, **request_kw):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  request: total_step, speed and the
         rest of batch_key's arguments.  silence_duration (seconds, not None): the job's utterances are the chunks of one text and come
         back as ONE wave, joined with that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own
-        gap), with its duration."""
+        gap), with its duration.  loudness_report (no part of the key: it changes no audio): a third result, the job's entry of
+        TextToSpeech.loudness_report for its joined wave as a dict of floats, or None when the synthesizer has no such report or the
+        job is not joined on the GPU."""
         key = batch_key(self.tts.sample_rate, *request, **request_kw)
-        job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration))
+        job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration), loudness_report)
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -104,7 +111,7 @@ class DynamicBatcher:
         job.done.wait()
         if job.error is not None:
             raise job.error
-        return job.waves, job.durs
+        return (job.waves, job.durs, job.report) if loudness_report else (job.waves, job.durs)
 
     def close(self):
         with self._cv:
@@ -154,9 +161,18 @@ class DynamicBatcher:
                     extra["encoding"] = key.encoding
                 joined = getattr(self.tts, "joined_batch", None)
                 if joined is not None and all(j.silence is not None for j in jobs):
-                    # one programme per job, joined by the fetch on the GPU
-                    waves, durs = joined(texts, langs, Style(ttl, dp), key.total_step, key.speed, rows=[len(j.texts) for j in jobs],
-                                         silence_duration=[j.silence for j in jobs], loudness_scope=key.loudness_scope, trim_chunks=key.trim_chunks, **extra)
+                    # one programme per job, joined by the fetch on the GPU; the report, when a job asked for one, is about the batch
+                    # the engine then holds, so nothing else may run on the synthesizer in between
+                    report = getattr(self.tts, "loudness_report", None) if any(j.want_report for j in jobs) else None
+                    with getattr(self.tts, "exclusive", contextlib.nullcontext)() if report is not None else contextlib.nullcontext():
+                        waves, durs = joined(texts, langs, Style(ttl, dp), key.total_step, key.speed, rows=[len(j.texts) for j in jobs],
+                                             silence_duration=[j.silence for j in jobs], loudness_scope=key.loudness_scope, trim_chunks=key.trim_chunks, **extra)
+                        if report is not None:
+                            rep = report(rows=[len(j.texts) for j in jobs], silence_duration=[j.silence for j in jobs],
+                                         trim_chunks=key.trim_chunks, **key.settings.kwargs())
+                            for g, j in enumerate(jobs):
+                                if j.want_report:
+                                    j.report = {k: float(v[g]) for k, v in rep.items()}
                     self.batches.append(len(texts))
                     for g, j in enumerate(jobs):
                         j.waves, j.durs = [waves[g]], np.asarray(durs[g:g + 1], np.float32)
@@ -244,6 +260,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         loudness_scope: str = Field("chunk", description="Non-batch mode with loudness: 'chunk' normalizes every chunk of a long text on its own, "
                                                          "'text' the joined text as one BS.1770 programme with one gain.")
         trim_chunks: bool = Field(False, description="Non-batch mode: cut every chunk at its duration before the join.")
+        loudness_report: Optional[bool] = Field(None, description="True: a single-utterance response carries the headers X-Loudness-Integrated, "
+                                                                  "X-Loudness-Range, X-Loudness-Max-Momentary and X-Loudness-Max-Short-Term "
+                                                                  "(LUFS / LU, measured on the GPU before the loudness gain).  It changes no audio.")
         trim_silence: Optional[float] = Field(None, ge=1.0, le=120.0, description="Trim leading and trailing silence by level (on the GPU): frames "
                                                                                  "more than this many dB below the loudest 10 ms frame; null: off.")
         trim_keep_ms: float = Field(20.0, ge=0.0, le=1000.0, description="Milliseconds kept in front of and behind the speech when trimming.")
@@ -343,27 +362,38 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             raise HTTPException(status_code=400, detail="max_pause_ms needs trim_silence: pauses are shortened inside trimmed utterances")
         if enc is not None:
             extra["encoding"] = enc
+        # the report of a single-utterance response (a synthesizer without loudness_report yields no headers)
+        reporter = getattr(tts, "loudness_report", None) if req.loudness_report and len(texts) == 1 else None
+        report = None
         if req.batch:
-            if ts is not None:  # every wave is its trimmed segment, cut at the length the GPU found
-                if req.max_pause_ms is not None:
-                    extra["max_pause"] = req.max_pause_ms
-                wav, dur, seg = tts.batch(texts, langs, style, req.total_step, req.speed, trim_silence=ts, lengths=True, **extra)
-                chunks = [wav[i, : int(seg[i])] for i in range(wav.shape[0])]
-            else:
-                wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
-                chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
+            with getattr(tts, "exclusive", contextlib.nullcontext)() if reporter else contextlib.nullcontext():
+                if ts is not None:  # every wave is its trimmed segment, cut at the length the GPU found
+                    if req.max_pause_ms is not None:
+                        extra["max_pause"] = req.max_pause_ms
+                    wav, dur, seg = tts.batch(texts, langs, style, req.total_step, req.speed, trim_silence=ts, lengths=True, **extra)
+                    chunks = [wav[i, : int(seg[i])] for i in range(wav.shape[0])]
+                else:
+                    wav, dur = tts.batch(texts, langs, style, req.total_step, req.speed, **extra)
+                    chunks = [wav[i, : int(sr * float(dur[i]))] for i in range(wav.shape[0])]  # _slice_audio, py/service.py:62-71
+                if reporter:  # (the settings of the call above, without what is no output setting)
+                    kw = {k: v for k, v in extra.items() if k != "encoding"}
+                    report = {k: float(v[0]) for k, v in reporter(**(kw if ts is None else dict(kw, trim_silence=ts))).items()}
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
-            waves, durs = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
-                                         enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
-                                         trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                         max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp)
+            more = {"loudness_report": True} if reporter else {}  # (absent otherwise: the call is today's)
+            waves, durs, *rep = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
+                                               enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
+                                               trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
+                                               max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp, **more)
+            report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:
             name = host.sanitize_filename(texts[0], 40) or "tts"
-            return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav",
-                            headers={"Content-Disposition": f'attachment; filename="{_ascii(name)}.wav"'})
+            headers = {"Content-Disposition": f'attachment; filename="{_ascii(name)}.wav"'}
+            if report:
+                headers.update({h: f"{report[k]:.3f}" for h, k in REPORT_HEADERS.items()})
+            return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav", headers=headers)
         zbuf = io.BytesIO()
         with zipfile.ZipFile(zbuf, "w", compression=zipfile.ZIP_DEFLATED) as zf:
             for i, c in enumerate(chunks):

@@ -67,8 +67,13 @@ class TextToSpeech:
         self.chunk_compress_factor = cfgs["ttl"]["chunk_compress_factor"]
         self.ldim = cfgs["ttl"]["latent_dim"]
         self.noise_seed = noise_seed  # None: fresh noise per call, like np.random.randn in the reference
-        self._lock = threading.Lock()
+        self._lock = threading.RLock()  # (re-entrant: a caller inside exclusive() calls the methods that take it)
         self._calls = 0
+
+    def exclusive(self):
+        """A context in which no other thread's call runs on this instance: a synthesis and the loudness_report of its batch belong in
+        one, since the report is about whatever batch the engine holds when it runs."""
+        return self._lock
 
     def _seed(self):
         if self.noise_seed is None:
@@ -196,6 +201,28 @@ class TextToSpeech:
         trim_silence row b holds its trimmed segment (max_pause: its segments end to end) from column 0 and the zero codeword behind
         it, and lengths=True adds a third result, the segments' lengths [B] (None with trimming off)."""
         return self._infer(text_list, lang_list, style, total_step, speed, OutputSettings.parse(**out), encoding=encoding, lengths=lengths)
+
+    def loudness_report(self, rows=None, silence_duration=0.3, trim_chunks=False, **out):
+        """The loudness of the batch the engine holds (after batch, solo_batch, joined_batch or __call__), measured on the GPU before the
+        loudness gain -> dict of arrays: integrated (LUFS), peak, gain (Engine.batch_loudness), max_momentary and max_short_term (LUFS:
+        the 400 ms and 3 s maxima EBU R 128 s1 limits; -inf where the audio is shorter), range (LU, EBU Tech 3342) and n_short_term (the
+        3 s windows behind the range's gates; under 2 the range is 0).  rows None: one entry per row of the batch.  rows (as
+        joined_batch's, with its silence_duration and trim_chunks): one entry per joined wave, measured as one programme, silences
+        included.  out: the OutputSettings keywords the audio was asked with, when they were a call's and not the instance's.  While the
+        limiter is off, a maximum after normalization is the reported one plus 20 log10(gain); the range does not depend on the gain."""
+        call = OutputSettings.parse(**out)
+        with self._lock, call.applied(self.engine, self.settings) as now:
+            if rows is None:
+                lufs, peak, gain = self.engine.batch_loudness()
+                m, s, lra, n_st = self.engine.batch_loudness_range()
+            else:
+                rows = [int(r) for r in rows]
+                rate = self._rate(now)
+                sil = np.broadcast_to(np.asarray(silence_duration, np.float64), (len(rows),))
+                join = (rows, [int(v * rate) for v in sil], sil.astype(np.float32), "trim" if trim_chunks else "whole")
+                lufs, peak, gain = self.engine.batch_join_loudness(*join)
+                m, s, lra, n_st = self.engine.batch_join_loudness_range(*join)
+        return {"integrated": lufs, "peak": peak, "gain": gain, "max_momentary": m, "max_short_term": s, "range": lra, "n_short_term": n_st}
 
 
 def _trim_setting(v):
