@@ -244,6 +244,50 @@ int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size
 /* op-level: rows x W fp32 (host) -> rows x W samples of encoding enc (host, rows packed): the fetch's store kernel without a gain */
 int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void* y);
 
+/* ---- dither --------------------------------------------------------------------------------------------
+ * The 16- and 24-bit PCM stores above truncate toward zero (the reference's writeWavFile rule): a dead zone 2 LSB wide around zero and
+ * an error that is correlated with the signal.  With a mode set, every fetch path (stn_batch_fetch_pcm16*, _encoded*, the begin / end
+ * slots, stn_batch_copy_*_device, stn_batch_fetch_joined*) quantizes those two encodings as follows instead; v is the fp32 sample the
+ * store encodes today (after gain and fades), S = 32767 (PCM16) or 8388607 (PCM24):
+ *   vc = fminf(1, fmaxf(-1, v))  (fp32);  t = (double)vc * S + 0.5 + (double)d;  q = clamp((int)floor(t), -S, S)
+ *   STN_DITHER_OFF      the default: truncation, byte for byte what the handle delivers without this setting
+ *   STN_DITHER_ROUND    d = 0: round to nearest, no noise
+ *   STN_DITHER_TPDF     d = (a - b) / 65536: triangular density over (-1, 1) LSB; the total error has zero mean and variance LSB^2 / 4
+ *                       whatever the signal
+ *   STN_DITHER_TPDF_HP  d = (a_n - a_{n-1}) / 65536, a_{-1} := b_0: the same density and power, about 4.5 times as much of it in the
+ *                       upper half of the band as in the lower
+ * a and b are the halves of a Philox4x32-10 word: sample n (0-based in the delivered row or programme; n < 2^34) of stream (kind, id)
+ * takes word [n & 3] of the block with counter {(uint32)(n >> 2), (uint32)id, (uint32)(id >> 32), 0xD17E0000 | kind} and key
+ * {(uint32)seed, (uint32)(seed >> 32)}; a = w & 0xFFFF, b = w >> 16.  Streams: a per-row fetch (trimmed or not) keys row b by kind 0 and
+ * its utterance id (stn_batch_upload's utt_ids; the row index without them), so an utterance's bytes do not depend on the batch it is
+ * in; a joined fetch keys programme g by kind 1 and g.  Every sample of the row is dithered (a trimmed row's and a programme's: those
+ * of its length, the gaps between members included; behind the length the zero codeword stays).  STN_ENC_F32, _MULAW and _ALAW
+ * fetches are unaffected by any mode, byte for byte (dither in front of a logarithmic quantizer means nothing).  With loudness on, the
+ * peak ceiling then holds to within 1.5 LSB of the encoding instead of exactly.  Handle state that no captured graph depends on; with
+ * a rate set, a dithered PCM fetch resamples into fp32 scratch and ends in the common store (one more pass).  DESIGN.md section 23. */
+#define STN_DITHER_OFF 0
+#define STN_DITHER_ROUND 1
+#define STN_DITHER_TPDF 2
+#define STN_DITHER_TPDF_HP 3
+#define STN_DITHER_ROW 0  /* stream kinds */
+#define STN_DITHER_PROG 1
+/* any other mode: STN_ERR_INVALID with a message, and the previous setting stays in force */
+int stn_set_dither(stn_handle* h, int mode, uint64_t seed);
+/* the mode (and the seed when seed_or_null is not NULL), or STN_ERR_INVALID for a NULL handle */
+int stn_get_dither(const stn_handle* h, uint64_t* seed_or_null);
+/* Host only (no device, no handle): the same rule on the CPU.  d[i] = the dither of sample n0 + i, i < n, of stream (kind, id) under
+ * mode and seed, in LSB (0 for STN_DITHER_OFF and _ROUND) */
+int stn_dither_noise(int mode, uint64_t seed, int kind, uint64_t id, int64_t n0, int64_t n, float* d);
+/* ... and out[i] = the code of v[i] at stream index n0 + i in encoding enc (STN_ENC_PCM16: int16; STN_ENC_PCM24: three bytes), by the
+ * mode's rule (STN_DITHER_OFF: truncation).  STN_ERR_INVALID: another encoding, an unknown mode or kind, n0 < 0 or n0 + n > 2^34 */
+int stn_dither_quantize(int enc, int mode, uint64_t seed, int kind, uint64_t id, int64_t n0, int64_t n, const float* v, void* out);
+/* op-level: the fetch's store kernel on the caller's whole buffers.  x [rows][W] fp32 (host), placed x_misalign (0 .. 3) floats behind a
+ * 16-byte boundary on the device (not 0: the kernel's one-sample form); times gain[row] unless NULL; row's stream is (0, row_id[row]), or
+ * (0, row) without row_id; y [rows][dst_stride] samples of enc (host): copied to the device, stored into, copied back, so samples
+ * [W, dst_stride) of a row come back as they went in.  mode STN_DITHER_OFF is stn_op_encode with a gain and a stride. */
+int stn_op_encode_ex(stn_handle* h, int enc, int rows, int W, const float* x, int x_misalign, const float* gain_or_null, const int64_t* row_id_or_null,
+                     int mode, uint64_t seed, int64_t dst_stride, void* y);
+
 /* ---- join ----------------------------------------------------------------------------------------------
  * Consecutive rows of the finished batch concatenated on the GPU, with a run of silence between them, into G programmes (the chunks of
  * a long text, cpp/helper.cpp:685-723): a joined fetch delivers [G][W_join] samples instead of [B][W], in any encoding, at the output

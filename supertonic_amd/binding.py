@@ -682,6 +682,10 @@ def load():
     L.stn_batch_fetch_encoded_begin.argtypes = [vp, ci, ci]
     L.stn_batch_fetch_encoded_end.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t), vp]
     L.stn_op_encode.argtypes = [vp, ci, ci, ci, _f32p, vp]
+    L.stn_set_dither.argtypes = [vp, ci, cu64]
+    L.stn_get_dither.argtypes = [vp, ctypes.POINTER(cu64)]
+    L.stn_group_set_dither.argtypes = [vp, ci, cu64]
+    L.stn_op_encode_ex.argtypes = [vp, ci, ci, ci, _f32p, ci, vp, vp, ci, cu64, ctypes.c_int64, vp]
     jp = ctypes.POINTER(StnJoin)
     L.stn_batch_join_dims.argtypes = [vp, jp, ctypes.POINTER(ctypes.c_int64), vp, vp]
     L.stn_batch_fetch_joined.argtypes = [vp, jp, ci, vp, ctypes.c_size_t, vp, vp]
@@ -789,6 +793,11 @@ class Group:
     def set_peak_mode(self, mode="sample"):
         """Peak mode of every rank (Engine.set_peak_mode): "sample" or "true"."""
         self._ck(self._lib.stn_group_set_peak_mode(self._g, peak_mode_id(mode)))
+
+    def set_dither(self, dither=None, seed=None):
+        """Dither of every rank's 16- and 24-bit PCM store (Engine.set_dither): rows are keyed by the caller's utterance index."""
+        mode, seed = dither_args(dither, seed) or ("off", 0)
+        self._ck(self._lib.stn_group_set_dither(self._g, DITHER_MODES[mode], seed))
 
     def set_filters(self, filters=None):
         """Filter chain of every rank (Engine.set_filters): the gathered rows are then the single engine's filtered rows."""
@@ -974,6 +983,71 @@ def peak_mode_id(mode):
     if isinstance(mode, str) and mode in PEAK_MODES:
         return PEAK_MODES[mode]
     raise ValueError(f"peak_mode: 'sample' or 'true', not {mode!r}")
+
+
+# dither of the 16- and 24-bit PCM stores (STN_DITHER_*, include/stn.h "dither")
+DITHER_OFF, DITHER_ROUND, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2, 3
+DITHER_MODES = {"off": DITHER_OFF, "round": DITHER_ROUND, "tpdf": DITHER_TPDF, "tpdf-hp": DITHER_TPDF_HP}
+DITHER_NAMES = {v: k for k, v in DITHER_MODES.items()}
+DITHER_ROW, DITHER_PROG = 0, 1  # stream kinds: a row keyed by its utterance id, a joined programme keyed by its index
+
+
+def dither_mode_id(mode):
+    """A dither mode ("off", "round", "tpdf", "tpdf-hp"; "tpdf_hp" is read as the last) or STN_DITHER_* value -> the value."""
+    if isinstance(mode, str) and mode.lower().replace("_", "-") in DITHER_MODES:
+        return DITHER_MODES[mode.lower().replace("_", "-")]
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool) and int(mode) in DITHER_NAMES:
+        return int(mode)
+    raise ValueError(f"dither mode {mode!r}: one of {', '.join(DITHER_MODES)}")
+
+
+def dither_args(dither, seed=None):
+    """A dither argument -> None (off) or the normalized (mode name, seed): None, False or "off"; True ("tpdf"); a mode (name or
+    STN_DITHER_* value); (mode, seed); or a dict with "mode" and optionally "seed".  seed (here or in the argument; default 0) is an
+    integer in [0, 2^64).  Anything else is a ValueError."""
+    if dither is None or dither is False:
+        return None
+    if isinstance(dither, dict):
+        extra = set(dither) - {"mode", "seed"}
+        if extra or "mode" not in dither:
+            raise ValueError(f"dither: a dict of 'mode' and optionally 'seed', not {sorted(dither)}")
+        dither, seed = dither["mode"], dither.get("seed", seed)
+    elif isinstance(dither, (tuple, list)):
+        if len(dither) != 2:
+            raise ValueError(f"dither: a mode or (mode, seed), not {dither!r}")
+        dither, seed = dither
+    mode = DITHER_TPDF if dither is True else dither_mode_id(dither)
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"dither seed {seed!r}: an integer in [0, 2^64)")
+    return None if mode == DITHER_OFF else (DITHER_NAMES[mode], int(seed))
+
+
+def _dither_lib():
+    L = load()
+    i64, u64 = ctypes.c_int64, ctypes.c_uint64
+    L.stn_dither_noise.argtypes = [ctypes.c_int, u64, ctypes.c_int, u64, i64, i64, ctypes.c_void_p]
+    L.stn_dither_quantize.argtypes = [ctypes.c_int, ctypes.c_int, u64, ctypes.c_int, u64, i64, i64, ctypes.c_void_p, ctypes.c_void_p]
+    return L
+
+
+def dither_noise(mode, seed, kind, id, n0, n):
+    """The dither of samples n0 .. n0 + n of stream (kind, id) in LSB (host only; stn_dither_noise) -> float32 [n]."""
+    d = np.empty(int(n), np.float32)
+    if _dither_lib().stn_dither_noise(dither_mode_id(mode), int(seed), int(kind), int(id), int(n0), int(n), d.ctypes.data) < 0:
+        raise StnError(-1, "stn_dither_noise: bad argument")
+    return d
+
+
+def dither_quantize(enc, mode, seed, kind, id, n0, v):
+    """v (float32 [n]) as the samples n0 .. of stream (kind, id) in 16- or 24-bit PCM under a mode (host only; stn_dither_quantize) ->
+    int16 [n] or uint8 [n, 3]."""
+    v = np.ascontiguousarray(v, np.float32).ravel()
+    e = encoding_id(enc)
+    out = encoded_empty(e, 1, v.size)[0] if e in (ENC_PCM16, ENC_PCM24) else np.empty(v.size, np.uint8)
+    if _dither_lib().stn_dither_quantize(e, dither_mode_id(mode), int(seed), int(kind), int(id), int(n0), v.size, v.ctypes.data, out.ctypes.data) < 0:
+        raise StnError(-1, "stn_dither_quantize: bad argument")
+    return out
 
 
 def true_peak_filter():
@@ -1710,6 +1784,36 @@ class Engine:
         if wav.shape != (B, W):
             raise ValueError(f"dbg_batch_set_wav: wav must be [{B}, {W}], got {wav.shape}")
         self._ck(self._lib.stn_dbg_batch_set_wav(self._h, wav))
+
+    def set_dither(self, dither=None, seed=None):
+        """How the 16- and 24-bit PCM stores of every fetch quantize (stn_set_dither): None / False / "off" (the default: truncation),
+        "round", "tpdf" (True) or "tpdf-hp", as dither_args takes them; seed keys the noise, with the utterance id (per-row fetches)
+        or the programme index (joined fetches) and the sample index.  fp32, mu-law and A-law fetches are unaffected."""
+        mode, seed = dither_args(dither, seed) or ("off", 0)
+        self._ck(self._lib.stn_set_dither(self._h, DITHER_MODES[mode], seed))
+
+    @property
+    def dither(self):
+        """None (off) or (mode name, seed)."""
+        seed = ctypes.c_uint64()
+        mode = self._ck_mode(self._lib.stn_get_dither(self._h, ctypes.byref(seed)))
+        return None if mode == DITHER_OFF else (DITHER_NAMES[mode], seed.value)
+
+    def op_encode_ex(self, x, enc, dither="off", seed=0, gain=None, row_id=None, dst_stride=None, x_misalign=0, fill=0x5A):
+        """op_encode with the store's other arguments (stn_op_encode_ex) -> samples [rows, dst_stride] (encoded_empty's dtypes): times
+        gain [rows], row r's dither stream (0, row_id[r]) (None: r), rows dst_stride (None: W) samples apart in a buffer that goes in
+        as bytes `fill`, x placed x_misalign floats off 16-byte alignment on the device."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        e = encoding_id(enc)
+        stride = W if dst_stride is None else int(dst_stride)
+        out = encoded_empty(e, rows, stride)
+        out.view(np.uint8)[...] = fill
+        g = None if gain is None else np.ascontiguousarray(gain, np.float32)
+        ids = None if row_id is None else np.ascontiguousarray(row_id, np.int64)
+        self._ck(self._lib.stn_op_encode_ex(self._h, e, rows, W, x, int(x_misalign), None if g is None else g.ctypes.data,
+                                            None if ids is None else ids.ctypes.data, dither_mode_id(dither), int(seed), stride, out.ctypes.data))
+        return out
 
     def op_encode(self, x, enc):
         """rows x W fp32 -> rows x W samples of an encoding on the GPU (the fetch's store kernel without a gain; encoded_empty's dtypes)."""

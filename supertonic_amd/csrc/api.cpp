@@ -608,6 +608,17 @@ int stn_deesser_coefs(const stn_deesser* c, int rate_hz, double k[2], float k32[
     }
     return STN_OK;
 }
+int stn_set_dither(stn_handle* h, int mode, uint64_t seed) { STN_TRY(h, { h->eng->set_dither(mode, seed); }) }
+int stn_get_dither(const stn_handle* h, uint64_t* seed) {
+    if (!h) return STN_ERR_INVALID;
+    if (seed) *seed = h->eng->dither_seed();
+    return h->eng->dither_mode();
+}
+int stn_op_encode_ex(stn_handle* h, int enc, int rows, int W, const float* x, int x_misalign, const float* gain, const int64_t* row_id, int mode,
+                     uint64_t seed, int64_t dst_stride, void* y) {
+    STN_TRY(h, { need(rows > 0 && W > 0 && x && y, "stn_op_encode_ex: bad argument (rows >= 1, W >= 1, x and y)");
+                 h->eng->op_encode_ex(enc, rows, W, x, x_misalign, gain, row_id, mode, seed, dst_stride, y); })
+}
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
 int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {

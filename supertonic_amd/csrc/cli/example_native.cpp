@@ -134,6 +134,16 @@ int main(int argc, char* argv[]) {
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.deesser_on = true;
         }
+        else if (a == "--dither" && more) {  // how pcm16 / pcm24 files are quantized on the GPU: truncation (off, the default), rounding, or rounding behind dither
+            const std::string why = parseDitherMode(argv[++i], opts.dither);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+        }
+        else if (a == "--dither-seed" && more) {  // seed of the dither noise (default 0)
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            opts.dither_seed = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-') { std::cerr << "Error: --dither-seed '" << v << "': an unsigned integer\n"; return 1; }
+        }
         else if (a == "--loudness-report") loudness_report = true;  // one line of loudness figures after each saved file
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }

@@ -339,6 +339,16 @@ class Engine {
     void batch_copy_encoded_device(int enc, void* dst, int64_t dst_stride);  // dst_stride in samples
     // rows x W fp32 (host) -> rows x W samples of encoding enc (host, enc_bytes(enc) each): the store kernel without a gain
     void op_encode(int enc, int rows, int W, const float* x, void* y);
+    // ---- dither (include/stn.h "dither"): the 16- and 24-bit PCM stores of every fetch path round (DITHER_ROUND) or
+    // round behind triangular dither (DITHER_TPDF, DITHER_TPDF_HP) keyed by (seed, utterance id or programme index, sample index).  Off
+    // (the default): the truncating store, the kernels that run without the setting.  Handle state that no graph depends on.
+    void set_dither(int mode, uint64_t seed);
+    int dither_mode() const { return dither_.mode; }
+    uint64_t dither_seed() const { return dither_.seed; }
+    // launch_store_rows on the caller's whole buffers: x [rows][W] (host) placed x_misalign floats behind a 16-byte boundary on the
+    // device, gain and row_id [rows] (host) or null, y [rows][dst_stride] samples of enc (host; copied in, stored into, copied out)
+    void op_encode_ex(int enc, int rows, int W, const float* x, int x_misalign, const float* gain, const int64_t* row_id, int mode, uint64_t seed,
+                      int64_t dst_stride, void* y);
     // ---- join (include/stn.h "join"): consecutive rows concatenated with gaps into programmes by the output
     // stage; every fetch path above with a join delivers [G][W_join] instead of [B][W].  A fetch argument: nothing here is handle state.
     JoinPlan batch_join_plan(const stn_join* j);  // the finished batch's plan at the current output rate (throws what the ABI refuses)
@@ -942,6 +952,10 @@ class Engine {
     struct OutRows { void* dst = nullptr; int enc = ENC_F32; int64_t stride = 0; const JoinPlan* join = nullptr; int scope = 0; };
     void enqueue_output(const OutRows& o);
     void enqueue_joined(const OutRows& o);
+    Dither dither_;  // the setting (mode, seed); the streams of a fetch are out_dither's
+    // section 23: the per-row fetches key a row by its utterance id (the batch's device ids), the joined ones a programme by its index
+    Dither out_dither(unsigned kind) const { return {dither_.mode, dither_.seed, kind, kind == DITHER_ROW ? bt_.utt_ids : nullptr}; }
+    bool dithers(int enc) const { return dither_.mode != DITHER_OFF && (enc == ENC_PCM16 || enc == ENC_PCM24); }
     void slot_begin(int slot, OutRows o, int64_t rows, int64_t width, const std::vector<float>& dur);  // the pipelined fetch behind both _begin calls
     // The gain step between the measurement m and the store: the rows to store from, their gains and their row stride.  Those are src,
     // m.gain and `stride`; with the limiter active (section 15) the rows x W limited in the fetch scratch, their trim (null outside true
@@ -962,7 +976,8 @@ class Engine {
     // n rows' results into whichever of the three host arrays is not null; the caller syncs
     void lo_read_back(const LoRes& m, size_t n, float* lufs, float* peak, float* gain);
     int64_t native_row_len() const { return (int64_t)bt_.L * a_.base_chunk_size * a_.chunk_compress_factor; }  // samples of a row of b.wav
-    void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride);
+    void join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride,
+                      const Dither& d = {});
     DevBuf join_tab_;
     std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch

@@ -485,24 +485,32 @@ void Engine::enqueue_output(const OutRows& o) {
         const float* fade = st_window(output_rate());
         const GainedRows r = gain_step(src, b.B, Wo, out_in_scratch() ? Wo : W, m);  // (the untrimmed rows limited, then cut)
         StageSpan span(*this, "out", "trim_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-        launch_join_trim_rows(s_, r.src, r.stride, sc.S > 0 ? sc.pseg : sc.seg, sc.S > 0 ? sc.pprog : sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride);
+        launch_join_trim_rows(s_, r.src, r.stride, sc.S > 0 ? sc.pseg : sc.seg, sc.S > 0 ? sc.pprog : sc.prog, b.B, Wo, r.g, fade, o.enc, o.dst, o.stride,
+                              out_dither(DITHER_ROW));
     } else if (loudness_on()) {
         const float* src = out_source(Wo);  // (with an fp32 fetch at a set rate, the scratch is src and o.dst alike: scaled in place)
         const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-        launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride);
+        launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
     } else if (filter_on() || deesser_on() || compressor_on()) {
         // sections 18, 20 and 21: the filtered, de-essed and / or compressed rows are in the fetch scratch; an fp32 fetch that was handed that scratch as its destination is done
         const float* src = out_source(Wo);
         if (src != o.dst) {
             StageSpan span(*this, "out", "store_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
-            launch_store_rows(s_, src, b.B, Wo, nullptr, o.enc, o.dst, o.stride);
+            launch_store_rows(s_, src, b.B, Wo, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
         }
+    } else if (resample_on() && dithers(o.enc)) {
+        // section 23: the resampler's fused store truncates; a dithered fetch resamples into the fp32 scratch and ends in the one store
+        // (one definition of the quantizer, one more pass over the rows)
+        float* d = out_f32_buf((size_t)b.B * Wo);
+        resample_enqueue(rs_table(), b.wav, b.B, W, ENC_F32, d, Wo);
+        StageSpan span(*this, "out", "store_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
+        launch_store_rows(s_, d, b.B, Wo, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
     } else if (resample_on()) {
         resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
     } else if (o.enc != ENC_F32) {
         StageSpan span(*this, "out", "store_rows", (double)b.B * W, (double)b.B * W * (4 + eb));
-        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.enc, o.dst, o.stride);
+        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
     } else {
         STN_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
     }
@@ -607,6 +615,34 @@ void Engine::batch_fetch_pcm16_end(int slot, const int16_t** pcm, size_t* n, flo
 void Engine::batch_copy_wav_device(float* dst, int64_t dst_stride) { enqueue_output({dst, ENC_F32, dst_stride}); }
 void Engine::batch_copy_pcm16_device(int16_t* dst, int64_t dst_stride) { enqueue_output({dst, ENC_PCM16, dst_stride}); }
 void Engine::batch_copy_encoded_device(int enc, void* dst, int64_t dst_stride) { enqueue_output({dst, enc, dst_stride}); }
+void Engine::set_dither(int mode, uint64_t seed) {
+    if (mode != DITHER_OFF && mode != DITHER_ROUND && mode != DITHER_TPDF && mode != DITHER_TPDF_HP)
+        throw std::invalid_argument("dither mode " + std::to_string(mode) + ": must be STN_DITHER_OFF (0), _ROUND (1), _TPDF (2) or _TPDF_HP (3)");
+    dither_.mode = mode;
+    dither_.seed = seed;
+}
+void Engine::op_encode_ex(int enc, int rows, int W, const float* x, int x_misalign, const float* gain, const int64_t* row_id, int mode, uint64_t seed,
+                          int64_t dst_stride, void* y) {
+    const int eb = need_enc(enc);
+    if (mode < DITHER_OFF || mode > DITHER_TPDF_HP) throw std::invalid_argument("dither mode " + std::to_string(mode) + ": must be 0 .. 3");
+    if (x_misalign < 0 || x_misalign > 3) throw std::invalid_argument("x_misalign must be 0 .. 3 floats");
+    if (dst_stride < W) throw std::invalid_argument("dst_stride smaller than the row length");
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    const size_t n = (size_t)rows * W, ny = (size_t)rows * dst_stride * eb;
+    float* dx = static_cast<float*>(ar_.alloc((n + 4) * 4)) + x_misalign;
+    void* dy = ar_.alloc(ny);
+    float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
+    int64_t* di = row_id ? static_cast<int64_t*>(ar_.alloc((size_t)rows * 8)) : nullptr;
+    STN_HIP(hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, s_));
+    STN_HIP(hipMemcpyAsync(dy, y, ny, hipMemcpyHostToDevice, s_));
+    if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
+    if (di) STN_HIP(hipMemcpyAsync(di, row_id, (size_t)rows * 8, hipMemcpyHostToDevice, s_));
+    launch_store_rows(s_, dx, rows, W, dg, enc, dy, dst_stride, Dither{mode, seed, DITHER_ROW, di});
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(y, dy, ny, hipMemcpyDeviceToHost, s_));
+    sync();
+}
 void Engine::op_encode(int enc, int rows, int W, const float* x, void* y) {
     const int eb = need_enc(enc);
     STN_HIP(hipSetDevice(device_));
@@ -721,11 +757,12 @@ Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
     return join_tables_at(d, p);
 }
 
-void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride) {
+void Engine::join_enqueue(const float* x, int64_t src_stride, const JoinTables& t, const JoinPlan& p, const float* g, int enc, void* y, int64_t dst_stride,
+                          const Dither& d) {
     {
         StageSpan span(*this, "out", "join", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + enc_bytes(enc)));
-        if (t.tseg) launch_join_trim_rows(s_, x, src_stride, t.tseg, t.prog, p.G, p.W_join, g, t.fade, enc, y, dst_stride);
-        else launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride);
+        if (t.tseg) launch_join_trim_rows(s_, x, src_stride, t.tseg, t.prog, p.G, p.W_join, g, t.fade, enc, y, dst_stride, d);
+        else launch_join_rows(s_, x, src_stride, t.seg, t.prog, p.G, p.W_join, g, enc, y, dst_stride, d);
     }
     STN_HIP(hipGetLastError());
 }
@@ -766,16 +803,19 @@ void Engine::enqueue_joined(const OutRows& o) {
     if (loudness_on() && o.scope == STN_JOIN_GAIN_PROG) {
         const float* joined = join_f32(p);
         const GainedRows r = gain_step(joined, p.G, p.W_join, p.W_join, join_measure(p, joined, true));  // (G rows, each its programme's gain and span)
+        Dither d = out_dither(DITHER_PROG);
+        // (section 23: a programme's stream ends at its length; the lengths are the words of the plan's table, which join_f32 left on the device)
+        if (dithers(o.enc)) { d.lim = &join_tables(p).prog->len; d.lim_stride = sizeof(JoinProg) / sizeof(int64_t); }
         {
             StageSpan span(*this, "out", "loudness_gain", (double)p.G * p.W_join, (double)p.G * p.W_join * (4 + eb));
-            launch_store_rows(s_, r.src, p.G, p.W_join, r.g, o.enc, o.dst, o.stride);
+            launch_store_rows(s_, r.src, p.G, p.W_join, r.g, o.enc, o.dst, o.stride, d);
         }
         STN_HIP(hipGetLastError());
         return;
     }
     const float* src = out_source(Wo);
     const GainedRows r = gain_step(src, b.B, Wo, out_in_scratch() ? Wo : W, loudness_on() ? lo_batch(src, Wo, true) : LoRes{});  // (the segments are the limited rows)
-    join_enqueue(r.src, r.stride, join_tables(p), p, r.g, o.enc, o.dst, o.stride);
+    join_enqueue(r.src, r.stride, join_tables(p), p, r.g, o.enc, o.dst, o.stride, out_dither(DITHER_PROG));
 }
 
 static int64_t join_stride(const JoinPlan& p) { return (p.W_join + 15) / 16 * 16; }  // a multiple of every encoding's vector

@@ -233,6 +233,9 @@ int stn_group_set_limiter(stn_group* g, int on, float lookahead_ms) {
 int stn_group_set_peak_mode(stn_group* g, int mode) {
     return for_all(g, "stn_set_peak_mode", [](stn_handle* h, const void*, uint64_t v) { return stn_set_peak_mode(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)mode);
 }
+int stn_group_set_dither(stn_group* g, int mode, uint64_t seed) {
+    return for_all(g, "stn_set_dither", [](stn_handle* h, const void* a, uint64_t v) { return stn_set_dither(h, *static_cast<const int*>(a), v); }, &mode, seed);
+}
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f) {
     struct S { int n; const stn_filter* f; } v{n, f};
     return for_all(g, "stn_set_filters", [](stn_handle* h, const void* a, uint64_t) {

@@ -91,7 +91,7 @@ TextToSpeech::SynthesisResult TextToSpeech::infer(const std::vector<std::string>
     SynthesisResult r;
     r.duration.resize(B);
     r.encoding = enc_;
-    if (enc_ != STN_ENC_PCM16) {
+    if (encodedFetch()) {
         r.encoded.resize((size_t)B * W * stn_encoding_bytes(enc_));
         check(h_, stn_batch_fetch_encoded(h_, enc_, r.encoded.data(), r.encoded.size(), r.duration.data()));
         if (trim_silence_) r.length = trimmed_lengths(h_, B, pause_limit_);
@@ -176,7 +176,7 @@ TextToSpeech::SynthesisResult TextToSpeech::call(const std::string& text, const 
         SynthesisResult out;
         out.encoding = enc_;
         out.duration.resize(1);
-        if (enc_ != STN_ENC_PCM16) {
+        if (encodedFetch()) {
             out.encoded.resize((size_t)W_join * stn_encoding_bytes(enc_));
             check(h_, stn_batch_fetch_joined(h_, &j, enc_, out.encoded.data(), out.encoded.size(), nullptr, out.duration.data()));
         } else {
@@ -337,6 +337,13 @@ std::string parseDeesserSpec(const std::string& spec, stn_deesser& c) {
     return "";
 }
 
+std::string parseDitherMode(const std::string& name, int& mode) {
+    static const char* const names[] = {"off", "round", "tpdf", "tpdf-hp"};  // (STN_DITHER_* in order)
+    for (int m = 0; m < 4; ++m)
+        if (name == names[m]) { mode = m; return ""; }
+    return "dither '" + name + "': one of off, round, tpdf, tpdf-hp";
+}
+
 std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool use_gpu, const EngineOptions& opts) {
     if (!use_gpu) throw std::runtime_error("CPU mode is not supported: this engine runs on MI355X only");
     const char* dt_name = opts.dtype == STN_DTYPE_BF16 ? "bf16" : opts.dtype == STN_DTYPE_F16 ? "fp16" : "fp32";
@@ -408,6 +415,8 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
             if (std::isnan(opts.loudness_lufs)) throw std::runtime_error("the true-peak mode needs loudness normalization (it is the ceiling of the loudness gain)");
             applied("peak mode", grp ? stn_group_set_peak_mode(grp, STN_PEAK_TRUE) : stn_set_peak_mode(h, STN_PEAK_TRUE));
         }
+        if (opts.dither != STN_DITHER_OFF)
+            applied("dither", grp ? stn_group_set_dither(grp, opts.dither, opts.dither_seed) : stn_set_dither(h, opts.dither, opts.dither_seed));
         // (refused here, while this function still owns the handle: once tts owns it, a throw would destroy it twice)
         if (!std::isnan(opts.trim_silence_db)) check(h, stn_set_silence_trim(h, 1, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms));
         if (!std::isnan(opts.max_pause_ms)) {
@@ -418,6 +427,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
                        : std::make_unique<TextToSpeech>(h, std::move(tp), cfgs, opts.noise_seed);
         tts->setOutputRate(opts.output_rate);
         tts->setEncoding(opts.encoding);
+        tts->setDither(opts.dither);
         tts->setLoudnessScope(opts.loudness_scope_text);
         tts->setTrimChunks(opts.trim_chunks);
         if (!std::isnan(opts.trim_silence_db)) tts->setSilenceTrim(true, opts.trim_silence_db, opts.trim_keep_ms, opts.trim_fade_ms);  // (accepted above)

@@ -87,6 +87,9 @@ struct EngineOptions {
                                    // CLI --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] and --deesser-preset speech
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
+    int dither = STN_DITHER_OFF;   // how 16- and 24-bit PCM is quantized on the GPU (stn_set_dither): STN_DITHER_OFF truncates as writeWavFile;
+    uint64_t dither_seed = 0;      // _ROUND, _TPDF, _TPDF_HP round, behind dither keyed by this seed.  With a mode set, PCM16 is fetched as
+                                   // 16-bit samples (not as floats for writeWavFile).  CLI --dither {off,round,tpdf,tpdf-hp} and --dither-seed N
 };
 
 // The command line's filter arguments (host only).  parseFilterSpec: "TYPE:FREQ[:Q[:GAIN_DB]]" (TYPE one of highpass, lowpass, notch,
@@ -105,11 +108,13 @@ std::string compressorPreset(const std::string& name, stn_compressor& c);
 // 4:1, knee 6 dB, 1 ms, 40 ms, range 12 dB, split) into c, or why not.  The numeric limits are stn_set_deesser's own.
 std::string parseDeesserSpec(const std::string& spec, stn_deesser& c);
 std::string deesserPreset(const std::string& name, stn_deesser& c);
+// The command line's dither mode (host only): "off", "round", "tpdf" or "tpdf-hp" into mode (STN_DITHER_*), or why not
+std::string parseDitherMode(const std::string& name, int& mode);
 
 class TextToSpeech {
    public:
-    // wav: the float waveform [B][W].  With an encoding other than PCM16 (setEncoding) the audio is `encoded` instead: [B][W] samples
-    // of stn_encoding_bytes(encoding) bytes, as the engine's encoded fetch delivers them, and wav is empty.
+    // wav: the float waveform [B][W].  With an encoding other than PCM16 (setEncoding), or with a dither mode set (setDither), the audio
+    // is `encoded` instead: [B][W] samples of stn_encoding_bytes(encoding) bytes, as the engine's encoded fetch delivers them, and wav is empty.
     // length: with silence trimming on (setSilenceTrim), the samples each row holds from column 0, its trimmed segment (empty: off).
     struct SynthesisResult { std::vector<float> wav; std::vector<float> duration; std::vector<unsigned char> encoded; int encoding = STN_ENC_PCM16; std::vector<int64_t> length; };
 
@@ -129,6 +134,9 @@ class TextToSpeech {
     // rate of the returned audio: the output rate when one is set, else the model's (cfgs.ae.sample_rate, which keeps sizing the latent)
     int getSampleRate() const { return out_rate_ ? out_rate_ : cfgs_.ae.sample_rate; }
     void setOutputRate(int hz) { out_rate_ = hz == cfgs_.ae.sample_rate ? 0 : hz; }
+    // the engine's dither mode (set on it by loadTextToSpeech): with one set, PCM16 results are the GPU's 16-bit samples (`encoded`): the
+    // float waveform would be truncated by writeWavFile, without the dither.  A group's PCM16 gather is dithered as it is.
+    void setDither(int mode) { dither_ = mode; }
     void setEncoding(int enc);  // STN_ENC_*: the encoding of the audio batch() / call() return (and of a group's gather)
     // call() with loudness normalization on: false (default), every chunk its own gain; true, the joined text measured as one
     // BS.1770 programme and scaled by one gain (stn.h, STN_JOIN_GAIN_PROG).  Refused on a group: its chunks sit on several devices.
@@ -166,6 +174,8 @@ class TextToSpeech {
     uint64_t calls_ = 0;
     int out_rate_ = 0;  // 0: the model's rate
     int enc_ = STN_ENC_PCM16;
+    int dither_ = STN_DITHER_OFF;
+    bool encodedFetch() const { return enc_ != STN_ENC_PCM16 || dither_ != STN_DITHER_OFF; }
     int32_t join_members_ = 0;  // the last result: a join of this many rows with join_silence_ between them (0: the batch's rows)
     float join_silence_ = 0.f;
     bool synthetic_ = false;

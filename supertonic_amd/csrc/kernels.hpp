@@ -15,6 +15,8 @@
 #include <vector>
 #include <string>
 
+#include "dither.hpp"
+
 namespace stn {
 
 // Kernel-exact timing: when a pair of events is armed here, the NEXT kernel launched through STN_KLAUNCH carries them on
@@ -423,16 +425,25 @@ inline void with_enc(int enc, const char* who, Fn&& fn) {
 // is not null, to y + row * dst_stride samples (dst_stride >= W) in encoding enc: fp32, int16 PCM by writeWavFile's rule (pcm16,
 // kernels_dev.hpp: int16(clamp(v, -1, 1) * 32767), truncation, cpp/helper.cpp:986-987), 24-bit PCM, or G.711 mu-law / A-law of the
 // 16-bit sample.  fp32 rows may be stored in place (y == x, dst_stride == W).
-void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride);
+// Dither (the rule is dither.hpp's): with a mode set and enc 16- or 24-bit PCM, sample n of row r is quantized with
+// the dither of stream (kind, ids ? ids[r] : r) at index n, all W samples of every row (the kernel knows no lengths).  Every other
+// encoding, and the mode off, launch the kernels that run without it.  W <= 2^34 then.  lim (the store only; the join has its programmes'
+// lengths): row r's stream ends at lim[r * lim_stride], and at and behind it the store writes the zero codeword.
+struct Dither {
+    int mode = DITHER_OFF; uint64_t seed = 0; unsigned kind = DITHER_ROW; const int64_t* ids = nullptr;
+    const int64_t* lim = nullptr; int64_t lim_stride = 1;
+};
+void launch_store_rows(hipStream_t s, const float* x, int64_t rows, int64_t W, const float* g, int enc, void* y, int64_t dst_stride, const Dither& d = {});
 // The join of a fetch: G programme rows of Wj samples at y + p * dst_stride samples (dst_stride >= Wj) in encoding
 // enc.  Programme p is members prog[p].first .. + prog[p].count of seg, in order: member m's first seg[m].len samples of source row
 // seg[m].row (fp32, rows src_stride apart, len <= src_stride), times g[seg[m].row] when g is not null, at output samples seg[m].dst ..;
 // the segments of a programme ascend and do not overlap, and end at or before prog[p].len <= Wj.  Every other sample of [0, Wj) is the
-// zero codeword.  Tables on the device.  G <= 65535.
+// zero codeword.  Tables on the device.  G <= 65535.  Dither d: programme p's stream is (d.kind, d.ids ? d.ids[p] : p) over its samples
+// [0, prog[p].len), the gaps between members included; at and behind prog[p].len the zero codeword stays.
 struct JoinSeg { int64_t dst, len, row; };
 struct JoinProg { int64_t len; int32_t first, count; };
 void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSeg* seg, const JoinProg* prog, int G, int64_t Wj, const float* g,
-                      int enc, void* y, int64_t dst_stride);
+                      int enc, void* y, int64_t dst_stride, const Dither& d = {});
 // The same join from trimmed sources: member m is the seg[m].len samples of source row seg[m].row from sample
 // seg[m].src on; its first seg[m].fin delivered samples are times fade[q], its last seg[m].fout times fade[len - 1 - q] (q the sample's
 // place in the segment; fade on the device, at least max(fin, fout) floats; both 0: no sample changes).  A delivered sample is
@@ -440,7 +451,7 @@ void launch_join_rows(hipStream_t s, const float* x, int64_t src_stride, const J
 // member per programme (the tables launch_edges_rows writes).
 struct JoinSegT { int64_t dst, len, row, src; int32_t fin, fout; };
 void launch_join_trim_rows(hipStream_t s, const float* x, int64_t src_stride, const JoinSegT* seg, const JoinProg* prog, int G, int64_t Wj,
-                           const float* g, const float* fade, int enc, void* y, int64_t dst_stride);
+                           const float* g, const float* fade, int enc, void* y, int64_t dst_stride, const Dither& d = {});
 
 // Silence edges of the finished waveform by level (kernels_edges.hip; the setting and the caches are engine_edges.cpp; DESIGN.md section
 // 14).  Frames of F = edges_frame(hz) samples (10 ms) from sample 0 without overlap, level = mean of x^2 over the frame's own samples;

@@ -1,12 +1,13 @@
 // kernels_dev.hpp — device-side helpers shared by the MFMA kernels (kernels_gemm.hip, kernels_ffn.hip): vector types,
 // buffer descriptors, LDS-DMA, counted waits, the 16-bit conversions and the GELU forms; the typed loads / stores and the wavefront sum of the
 // HBM-bound kernels (kernels_dwconv_ln.hip, kernels_fold.hip, kernels_layout.hip); and the sample encodings of every fetch
-// (kernels_output.hip, kernels_resample.hip).  One definition, so that a fused kernel and the launches it replaces round identically.
+// (kernels_output.hip, kernels_resample.hip), with the Philox4x32-10 and the dithered quantizer of dither.hpp.  One definition, so that a fused kernel and the launches it replaces round identically.
 #pragma once
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dither.hpp"
 #include "kernels.hpp"
 
 namespace stn {

@@ -417,18 +417,8 @@ void launch_step_counters(hipStream_t s, float* tot, float* cur, float* dt, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller; element (utt, d, t) depends only on (seed, utt, d, t)
+// Philox4x32-10 (kernels_dev.hpp) + Box-Muller; element (utt, d, t) depends only on (seed, utt, d, t)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 __global__ void randn_masked_kernel(unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
                                     const int64_t* __restrict__ utt_ids, int D, int L, const int* __restrict__ len, int64_t n4,
                                     float* __restrict__ xt) {

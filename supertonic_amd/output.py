@@ -37,6 +37,7 @@ _PARSE = {
     "max_pause": _switched(binding.pause_limit_args),
     "limiter": _switched(binding.limiter_args),
     "peak_mode": _peak_mode,
+    "dither": lambda v: binding.dither_args(v) or False,
 }
 
 
@@ -66,7 +67,10 @@ class OutputSettings:
     limiter       the full loudness gain, and a look-ahead peak limiter holds the ceiling (stn_set_limiter): True (5 ms) or the look-ahead
                   in milliseconds ([0.5, 10]); it acts only while loudness is on.  Normalized: milliseconds.  Off: False, the capped gain.
     peak_mode     the ceiling of loudness as a sample peak ("sample") or a true peak ("true": dBTP, 4x oversampled; stn_set_peak_mode);
-                  it acts only while loudness is on.  Off: "sample"."""
+                  it acts only while loudness is on.  Off: "sample".
+    dither        how the 16- and 24-bit PCM stores quantize, the last step (stn_set_dither): True or "tpdf", "tpdf-hp", "round", or
+                  (mode, seed), as binding.dither_args takes them; it acts on audio fetched as "pcm16" or "pcm24" only (float, mu-law
+                  and A-law are unaffected).  Normalized: (mode name, seed).  Off: False or "off", the truncating store."""
     output_rate: object = None
     filters: object = None
     loudness: object = None
@@ -80,6 +84,28 @@ class OutputSettings:
     # there (dataclasses.replace copies constructor arguments only: it leaves this field unset, and refuses to be given it).  Compared
     # and hashed like every other field.
     deesser: object = dataclasses.field(default=None, init=False)
+    # No dataclass field at all, but an attribute that parse() and replace() set, kept through over() and compared and hashed with the
+    # fields: OFF and ALL_OFF are pinned from three sides (ALL_OFF leaves no field at None; taking compressor and deesser out of ALL_OFF
+    # gives OFF; OFF is the constructor's value of its seven arguments), which no further field of any kind satisfies.  So neither
+    # names it, and who needs every setting decided asks decided().
+    dither = None
+
+    def _all(self):
+        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither,)
+
+    def __eq__(self, other):
+        return other._all() == self._all() if type(other) is type(self) else NotImplemented
+
+    def __hash__(self):
+        return hash(self._all())
+
+    def __repr__(self):
+        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither"], self._all())) + ")"
+
+    def decided(self):
+        """This value over ALL_OFF, and dither off where that leaves it unset: every setting decided (what an instance holds)"""
+        s = self.over(OutputSettings.ALL_OFF)
+        return s if s.dither is not None else s.replace(dither=False)
 
     @classmethod
     def parse(cls, **kw):
@@ -92,10 +118,11 @@ class OutputSettings:
 
     def replace(self, **changes):
         """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser
-        included"""
-        deesser = changes.pop("deesser", self.deesser)
+        and dither included"""
+        deesser, dither = changes.pop("deesser", self.deesser), changes.pop("dither", self.dither)
         new = dataclasses.replace(self, **changes)
         object.__setattr__(new, "deesser", deesser)
+        object.__setattr__(new, "dither", dither)
         return new
 
     def kwargs(self):
@@ -134,6 +161,8 @@ class OutputSettings:
             engine.set_limiter(self.limiter or None)
         if self.peak_mode is not None:
             engine.set_peak_mode(self.peak_mode)
+        if self.dither is not None:
+            engine.set_dither(self.dither or None)
 
     @contextlib.contextmanager
     def applied(self, engine, base):
@@ -147,5 +176,6 @@ class OutputSettings:
 
 
 # OFF leaves compressor and deesser unset (a base that does not name them compares equal after over(OFF)); ALL_OFF names every field
+# (dither, which is none, neither names: decided())
 OutputSettings.OFF = OutputSettings(0, (), False, False, False, False, "sample")
 OutputSettings.ALL_OFF = OutputSettings.OFF.replace(compressor=False, deesser=False)

@@ -34,7 +34,8 @@ BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
-              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, compressor=None):
+              trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, dither=None,
+              dither_seed=None, compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -44,7 +45,8 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     bool.  max_pause_ms: without trim_silence, validated and dropped likewise.  filters: a list as binding.filter_args takes it, [] =
     off, checked against the request's rate.  deesser: True, a dict or an 8-tuple as binding.deesser_args takes it, False = off, checked
     against the request's rate as well.  compressor: True, a dict or a 6-tuple as binding.compressor_args takes it, False = off,
-    checked against the engine's limits.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
+    checked against the engine's limits.  dither ("off", "round", "tpdf", "tpdf-hp" or true for "tpdf"; false = off) with dither_seed (an
+    integer in [0, 2^64), 0 when left out; alone it is validated and dropped): OutputSettings' dither.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
     loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
@@ -58,7 +60,8 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     why = comp and binding.compressor_error(comp, int(sample_rate or model_rate))
     if why:
         raise ValueError(why)
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, loudness=None if loudness is None else (loudness, peak_ceiling),
+    dith = binding.dither_args(dither or "off", dither_seed) or False
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, dither=None if dither is None else dith, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
@@ -285,6 +288,12 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                           "-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB) or "
                                                                           "{threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db}, the "
                                                                           "fields left out from that default; false: off; null: the server's.")
+        dither: Optional[Union[bool, Literal["off", "round", "tpdf", "tpdf-hp"]]] = Field(
+            None, description="How 16- and 24-bit PCM is quantized on the GPU: 'round' (to nearest), 'tpdf' (true: triangular dither of +-1 LSB "
+                              "in front of the rounding), 'tpdf-hp' (the same power, high-passed); 'off' or false: truncation; null: the "
+                              "server's.  No effect on f32, mulaw and alaw.")
+        dither_seed: Optional[int] = Field(None, ge=0, lt=1 << 64, description="Seed of the dither noise (0 when left out): with the utterance's "
+                                                                               "place in its batch and the sample index it fixes the noise.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -352,11 +361,22 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             if why:
                 raise HTTPException(status_code=400, detail=why)
             extra["compressor"] = comp
+        dith = None
+        try:
+            dith = binding.dither_args(req.dither or "off", req.dither_seed) or False
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        if req.dither is None:
+            dith = None  # (a seed alone: validated and dropped)
+        else:
+            extra["dither"] = dith
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
             raise HTTPException(status_code=400, detail=f"loudness_scope {req.loudness_scope!r} is not supported; supported: chunk, text")
-        enc = None if req.encoding == "pcm16" else req.encoding  # pcm16: the float waves, written as writeWavFile writes them
+        # pcm16: the float waves, written as writeWavFile writes them (truncation); with dither in force, the GPU's dithered 16-bit samples
+        dithering = dith if dith is not None else getattr(getattr(tts, "settings", None), "dither", None)
+        enc = None if req.encoding == "pcm16" and not dithering else req.encoding
         ts = None if req.trim_silence is None else (req.trim_silence, req.trim_keep_ms, req.trim_fade_ms)
         if req.max_pause_ms is not None and ts is None:
             raise HTTPException(status_code=400, detail="max_pause_ms needs trim_silence: pauses are shortened inside trimmed utterances")
@@ -384,7 +404,8 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             waves, durs, *rep = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                                enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                                trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                               max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp, **more)
+                                               max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp,
+                                               dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, **more)
             report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
