@@ -288,6 +288,49 @@ int stn_dither_quantize(int enc, int mode, uint64_t seed, int kind, uint64_t id,
 int stn_op_encode_ex(stn_handle* h, int enc, int rows, int W, const float* x, int x_misalign, const float* gain_or_null, const int64_t* row_id_or_null,
                      int mode, uint64_t seed, int64_t dst_stride, void* y);
 
+/* ---- pitch ---------------------------------------------------------------------------------------------
+ * Every fetch path delivers the rows shifted by `semitones` without a change of length: each row is stretched in time by a / b, the
+ * fraction closest to 2^(semitones / 12), at the model's rate (WSOLA with a normalised search: the duration changes, the pitch stays), and
+ * resampled by b / a back to its length (the duration is restored, the pitch moves).  Both steps run in front of every other stage of
+ * the output stage, so rate, filters, de-esser, compressor, loudness, limiter, trim, pause limit, join, encodings and dither all see
+ * the shifted rows; row length, spans and reported durations do not change.  0 (the default) is off: nothing is launched and no scratch
+ * exists.  Formants move with the pitch (a resampling shifter), the value is one per handle, and the tempo is the model's `speed`.
+ * Handle state that no captured graph depends on.  DESIGN.md section 24.
+ *
+ * The stretch at rate hz: hop H, the smallest power of two with 128 H >= hz; grain N = 2 H; search radius D = 3 H / 4; window the periodic
+ * Hann w[i] = 0.5 (1 - cos(2 pi i / N)) as float32.  A row x of span n reads 0.0 outside [0, n).  Frame m is analysed at
+ * p_m = floor(m H b / a) and its grain starts at q_m = p_m + d_m - H, with d_0 = 0 and d_m, m >= 1, the d in [-D, D] of the largest
+ * score(d) = c(d) / sqrt(E(d) + 1e-9), c(d) = sum_i t[i] x[p_m + d - H + i], E(d) = sum_i x[p_m + d - H + i]^2 over i in [0, N), against
+ * the target t[i] = x[q_{m-1} + H + i]; among equal scores the smallest |d|, then the negative one.  The stretched row has
+ * Ws = ceil(W a / b) samples, y[m H + i] = w[H + i] x[q_m + H + i] + w[i] x[q_{m+1} + i] for i in [0, H), over M = Ws / H + 2 frames.
+ * From the end of the row's stretched span, ceil(n a / b), on y is 0.0: what the last grains leave there would reach the resampler in a
+ * wide batch and not in a narrow one, and a row's result depends on its own samples only.
+ * The resample back uses the resampler's design (section "resample") for P = b, Q = a, stated at the rates a k -> b k Hz with the
+ * smallest k that has min(a, b) k >= 8000: stn_op_pitch(x) is, bit for bit, the first W columns of stn_op_resample(a k, b k) of
+ * stn_op_time_stretch(x). */
+/* Host only: the fraction a / b, 1 <= a, b <= 640, closest to r = pow(2, semitones / 12) in log ratio (the smaller of q / r and r / q,
+ * q = a / b, in double); among equals the smaller b; always reduced.  The realised pitch is within 1.36 cents of the request.
+ * STN_ERR_INVALID unless semitones is finite and in [-12, 12]; stn_pitch_error gives the message ("" for a value that is taken; the
+ * string is the calling thread's until its next call). */
+int stn_pitch_ratio(float semitones, int* a, int* b);
+const char* stn_pitch_error(float semitones);
+/* Host only: the geometry at hz for rows of W samples stretched by a / b; each output may be NULL.  STN_ERR_INVALID for hz outside
+ * [8000, 192000], W < 0, or a term outside [1, 640] */
+int stn_pitch_plan(int hz, int64_t W, int a, int b, int* H, int* delta, int64_t* M, int64_t* Ws);
+/* Host only: the window at hz, the table the device multiplies by: *n = N, and w[0 .. min(N, cap)) when w is not NULL */
+int stn_pitch_window(int hz, float* w_or_null, size_t cap, int* n);
+/* 0: off (the default).  Not finite or outside [-12, 12]: STN_ERR_INVALID with stn_pitch_error's message, and the previous setting stays */
+int stn_set_pitch(stn_handle* h, float semitones);
+/* the setting and its ratio (1 / 1 when off); each output may be NULL */
+int stn_get_pitch(const stn_handle* h, float* semitones, int* a, int* b);
+/* op-level: the stretch of the batch path on the caller's rows.  x [rows][W] fp32 (host) at hz, row r's span n[r] in [0, W] (NULL: W);
+ * y [rows][Ws] fp32, delta [rows][M] int32 (delta[r][0] = 0) and score [rows][M] fp32 (the winners' scores; 0 for frame 0), host, each
+ * or NULL, with Ws and M from stn_pitch_plan */
+int stn_op_time_stretch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, int a, int b, float* y_or_null,
+                        int32_t* delta_or_null, float* score_or_null);
+/* ... and the whole shift: the stretch by stn_pitch_ratio(semitones) and the resample back, y [rows][W] fp32 (host) */
+int stn_op_pitch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float semitones, float* y);
+
 /* ---- join ----------------------------------------------------------------------------------------------
  * Consecutive rows of the finished batch concatenated on the GPU, with a run of silence between them, into G programmes (the chunks of
  * a long text, cpp/helper.cpp:685-723): a joined fetch delivers [G][W_join] samples instead of [B][W], in any encoding, at the output

@@ -60,6 +60,8 @@ int stn_group_set_peak_mode(stn_group* g, int mode);
 /* dither of every rank's 16- and 24-bit PCM store (stn_set_dither): the ranks key a row by the caller's utterance index, so the gathered
  * rows are the single engine's over every rank's own row length (behind a shorter shard's rows the gather pads with the zero codeword) */
 int stn_group_set_dither(stn_group* g, int mode, uint64_t seed);
+/* pitch of every rank (stn_set_pitch): rows are shifted on their own, so the gathered rows are the single engine's */
+int stn_group_set_pitch(stn_group* g, float semitones);
 /* filter chain of every rank (stn_set_filters): rows are filtered on their own, so the gathered rows are the single engine's */
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f);
 /* compressor of every rank (stn_set_compressor): rows are compressed on their own, so the gathered rows are the single engine's */

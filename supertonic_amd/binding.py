@@ -686,6 +686,11 @@ def load():
     L.stn_get_dither.argtypes = [vp, ctypes.POINTER(cu64)]
     L.stn_group_set_dither.argtypes = [vp, ci, cu64]
     L.stn_op_encode_ex.argtypes = [vp, ci, ci, ci, _f32p, ci, vp, vp, ci, cu64, ctypes.c_int64, vp]
+    L.stn_set_pitch.argtypes = [vp, cf]
+    L.stn_get_pitch.argtypes = [vp, ctypes.POINTER(cf), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.stn_group_set_pitch.argtypes = [vp, cf]
+    L.stn_op_time_stretch.argtypes = [vp, ci, ci, ci, _f32p, vp, ci, ci, vp, vp, vp]
+    L.stn_op_pitch.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, vp]
     jp = ctypes.POINTER(StnJoin)
     L.stn_batch_join_dims.argtypes = [vp, jp, ctypes.POINTER(ctypes.c_int64), vp, vp]
     L.stn_batch_fetch_joined.argtypes = [vp, jp, ci, vp, ctypes.c_size_t, vp, vp]
@@ -798,6 +803,10 @@ class Group:
         """Dither of every rank's 16- and 24-bit PCM store (Engine.set_dither): rows are keyed by the caller's utterance index."""
         mode, seed = dither_args(dither, seed) or ("off", 0)
         self._ck(self._lib.stn_group_set_dither(self._g, DITHER_MODES[mode], seed))
+
+    def set_pitch(self, semitones=None):
+        """Pitch of every rank (Engine.set_pitch): rows are shifted on their own, so the gathered rows are the single engine's."""
+        self._ck(self._lib.stn_group_set_pitch(self._g, pitch_args(semitones)))
 
     def set_filters(self, filters=None):
         """Filter chain of every rank (Engine.set_filters): the gathered rows are then the single engine's filtered rows."""
@@ -1021,6 +1030,68 @@ def dither_args(dither, seed=None):
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
         raise ValueError(f"dither seed {seed!r}: an integer in [0, 2^64)")
     return None if mode == DITHER_OFF else (DITHER_NAMES[mode], int(seed))
+
+
+def _pitch_lib():
+    L = load()
+    ci, cf, i64 = ctypes.c_int, ctypes.c_float, ctypes.c_int64
+    L.stn_pitch_ratio.argtypes = [cf, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.stn_pitch_error.argtypes = [cf]
+    L.stn_pitch_error.restype = ctypes.c_char_p
+    L.stn_pitch_plan.argtypes = [ci, i64, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    L.stn_pitch_window.argtypes = [ci, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ci)]
+    return L
+
+
+def pitch_error(semitones):
+    """Why the engine refuses a pitch of `semitones` (host only; stn_pitch_error), or "" for a value it takes."""
+    return _pitch_lib().stn_pitch_error(float(semitones)).decode()
+
+
+def pitch_args(pitch):
+    """A pitch argument -> semitones as a float: None or False is 0.0 (off); a number must be finite and in [-12, 12] (ValueError with
+    the engine's message otherwise)."""
+    if pitch is None or pitch is False:
+        return 0.0
+    if isinstance(pitch, bool) or not isinstance(pitch, (int, float, np.integer, np.floating)):
+        raise ValueError(f"pitch {pitch!r}: a number of semitones in [-12, 12]")
+    why = pitch_error(pitch)
+    if why:
+        raise ValueError(why)
+    return float(np.float32(pitch))
+
+
+def pitch_ratio(semitones):
+    """The fraction (a, b) closest to 2^(semitones / 12) with both terms in [1, 640] (host only; stn_pitch_ratio)."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    if _pitch_lib().stn_pitch_ratio(float(semitones), ctypes.byref(a), ctypes.byref(b)) < 0:
+        raise StnError(-1, pitch_error(semitones))
+    return a.value, b.value
+
+
+def pitch_cents(semitones):
+    """The realised shift of a request in cents: 1200 log2(a / b)."""
+    import math
+    a, b = pitch_ratio(semitones)
+    return 1200.0 * math.log2(a / b)
+
+
+def pitch_plan(hz, W, a, b):
+    """The stretcher's geometry (host only; stn_pitch_plan) -> dict H, N, delta, M, Ws."""
+    H, D, M, Ws = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+    if _pitch_lib().stn_pitch_plan(int(hz), int(W), int(a), int(b), ctypes.byref(H), ctypes.byref(D), ctypes.byref(M), ctypes.byref(Ws)) < 0:
+        raise StnError(-1, f"stn_pitch_plan: bad argument (hz {hz}, W {W}, {a}/{b})")
+    return dict(H=H.value, N=2 * H.value, delta=D.value, M=M.value, Ws=Ws.value)
+
+
+def pitch_window(hz):
+    """The stretcher's window at hz (host only; stn_pitch_window) -> float32 [N]."""
+    n = ctypes.c_int()
+    if _pitch_lib().stn_pitch_window(int(hz), None, 0, ctypes.byref(n)) < 0:
+        raise StnError(-1, f"stn_pitch_window: rate {hz} Hz outside [8000, 192000]")
+    w = np.empty(n.value, np.float32)
+    _pitch_lib().stn_pitch_window(int(hz), w.ctypes.data, w.size, ctypes.byref(n))
+    return w
 
 
 def _dither_lib():
@@ -1784,6 +1855,40 @@ class Engine:
         if wav.shape != (B, W):
             raise ValueError(f"dbg_batch_set_wav: wav must be [{B}, {W}], got {wav.shape}")
         self._ck(self._lib.stn_dbg_batch_set_wav(self._h, wav))
+
+    def set_pitch(self, semitones=None):
+        """Shift the pitch of every row of every fetch by `semitones` on the GPU, in front of every other fetch-time stage and without
+        a change of length (stn_set_pitch): None, False or 0 = off (the default).  ValueError with the engine's message for a value
+        that is not finite or outside [-12, 12]; the previous setting then stays."""
+        self._ck(self._lib.stn_set_pitch(self._h, pitch_args(semitones)))
+
+    @property
+    def pitch(self):
+        """(semitones, a, b): the setting and the ratio it is realised with (0.0, 1, 1 when off)."""
+        s, a, b = ctypes.c_float(), ctypes.c_int(), ctypes.c_int()
+        self._ck(self._lib.stn_get_pitch(self._h, ctypes.byref(s), ctypes.byref(a), ctypes.byref(b)))
+        return s.value, a.value, b.value
+
+    def op_time_stretch(self, x, hz, a, b, n=None):
+        """rows x W fp32 at hz, row r's span n[r] (None: W), stretched by a / b on the GPU (stn_op_time_stretch) -> (y [rows, Ws]
+        float32, delta [rows, M] int32, score [rows, M] float32)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        p = pitch_plan(hz, W, a, b)
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        y, d, sc = np.empty((rows, p["Ws"]), np.float32), np.empty((rows, p["M"]), np.int32), np.empty((rows, p["M"]), np.float32)
+        self._ck(self._lib.stn_op_time_stretch(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, int(a), int(b), y.ctypes.data,
+                                               d.ctypes.data, sc.ctypes.data))
+        return y, d, sc
+
+    def op_pitch(self, x, hz, semitones, n=None):
+        """rows x W fp32 at hz shifted by `semitones` on the GPU (stn_op_pitch: the stretch, then the resample back) -> [rows, W]."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        y = np.empty((rows, W), np.float32)
+        self._ck(self._lib.stn_op_pitch(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(semitones), y.ctypes.data))
+        return y
 
     def set_dither(self, dither=None, seed=None):
         """How the 16- and 24-bit PCM stores of every fetch quantize (stn_set_dither): None / False / "off" (the default: truncation),

@@ -619,6 +619,22 @@ int stn_op_encode_ex(stn_handle* h, int enc, int rows, int W, const float* x, in
     STN_TRY(h, { need(rows > 0 && W > 0 && x && y, "stn_op_encode_ex: bad argument (rows >= 1, W >= 1, x and y)");
                  h->eng->op_encode_ex(enc, rows, W, x, x_misalign, gain, row_id, mode, seed, dst_stride, y); })
 }
+int stn_set_pitch(stn_handle* h, float semitones) { STN_TRY(h, { h->eng->set_pitch(semitones); }) }
+int stn_get_pitch(const stn_handle* h, float* semitones, int* a, int* b) {
+    if (!h) return STN_ERR_INVALID;
+    if (semitones) *semitones = h->eng->pitch();
+    if (a) *a = h->eng->pitch_a();
+    if (b) *b = h->eng->pitch_b();
+    return STN_OK;
+}
+int stn_op_time_stretch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int32_t* delta, float* score) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_time_stretch: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 h->eng->op_time_stretch(hz, rows, W, x, n, a, b, y, delta, score); })
+}
+int stn_op_pitch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float semitones, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pitch: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_pitch(hz, rows, W, x, n, semitones, y); })
+}
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
 int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {

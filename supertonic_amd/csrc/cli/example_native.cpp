@@ -21,6 +21,8 @@
 // behind the filters and in front of the compressor: the band above FREQ turned down by up to RANGE_DB while its level is over THRESHOLD;
 // ratio 4, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, MODE split (the band alone; wide: the whole signal) when left out),
 // --deesser-preset speech (5500 Hz, -30 dB and those),
+// --pitch SEMITONES (every utterance shifted by that many semitones, -12 to 12, on the GPU without a change of length, in front of
+// everything else; absent or 0: off),
 // --loudness-report (after each saved file one line "Loudness: integrated .. LUFS, range .. LU, max momentary .. LUFS, max short-term ..
 // LUFS (N short-term windows), peak .., gain ..": measured on the GPU before the loudness gain, three decimals, a long text as the
 // joined programme; one GPU only).
@@ -133,6 +135,14 @@ int main(int argc, char* argv[]) {
             const std::string why = a == "--deesser" ? parseDeesserSpec(argv[++i], opts.deesser) : deesserPreset(argv[++i], opts.deesser);
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.deesser_on = true;
+        }
+        else if (a == "--pitch" && more) {  // every utterance shifted by this many semitones on the GPU (length unchanged); 0: off
+            const std::string v = argv[++i];
+            char* end = nullptr;
+            opts.pitch = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end) { std::cerr << "Error: --pitch '" << v << "': a number of semitones in [-12, 12]\n"; return 1; }
+            const char* why = stn_pitch_error(opts.pitch);
+            if (why[0]) { std::cerr << "Error: --" << why << "\n"; return 1; }
         }
         else if (a == "--dither" && more) {  // how pcm16 / pcm24 files are quantized on the GPU: truncation (off, the default), rounding, or rounding behind dither
             const std::string why = parseDitherMode(argv[++i], opts.dither);

@@ -19,6 +19,7 @@
 #include "../../include/stn_arch.h"
 #include "host/join_plan.hpp"
 #include "host/pause_plan.hpp"
+#include "host/pitch.hpp"
 #include "kernels.hpp"
 
 namespace stn {
@@ -345,6 +346,19 @@ class Engine {
     void set_dither(int mode, uint64_t seed);
     int dither_mode() const { return dither_.mode; }
     uint64_t dither_seed() const { return dither_.seed; }
+    // ---- pitch (include/stn.h "pitch"): every fetch path delivers the rows shifted by `semitones`: stretched by
+    // a / b ~ 2^(s/12) at the model's rate (WSOLA) and resampled by b / a back to their length, in front of every other stage.  0 (the
+    // default): off, nothing is launched.  Handle state that no graph depends on.
+    void set_pitch(float semitones);  // throws what pitch_check refuses; the previous setting then stays
+    float pitch() const { return ps_semi_; }
+    int pitch_a() const { return ps_a_; }
+    int pitch_b() const { return ps_b_; }
+    bool pitch_on() const { return ps_a_ != ps_b_; }
+    // rows x W fp32 (host) at hz, row r's span n[r] (host, or null: W), stretched by a / b: y [rows][Ws], delta and score [rows][M]
+    // (host, each or null; Ws and M: pitch_plan): the launches of the batch path on the caller's rows
+    void op_time_stretch(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int* delta, float* score);
+    // the same rows shifted by `semitones` -> y [rows][W] (host): the stretch and the resample behind it
+    void op_pitch(int hz, int rows, int W, const float* x, const int64_t* n, float semitones, float* y);
     // launch_store_rows on the caller's whole buffers: x [rows][W] (host) placed x_misalign floats behind a 16-byte boundary on the
     // device, gain and row_id [rows] (host) or null, y [rows][dst_stride] samples of enc (host; copied in, stored into, copied out)
     void op_encode_ex(int enc, int rows, int W, const float* x, int x_misalign, const float* gain, const int64_t* row_id, int mode, uint64_t seed,
@@ -775,6 +789,35 @@ class Engine {
     const ResampleTable& rs_table();
     void rs_release();
     void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, int enc, void* y, int64_t dst_stride);
+    // ---- pitch (engine_pitch.cpp)
+    float ps_semi_ = 0.0f;             // the setting in force and its ratio (1 / 1: off)
+    int ps_a_ = 1, ps_b_ = 1;
+    uint64_t ps_gen_ = 0;              // bumped by every set_pitch: part of EdKey, CpKey and DsKey (all see the shifted rows)
+    ResampleTable ps_rs_, op_ps_rs_;   // the b / a tables of the setting and of the op entries, cached per (a, b) (device copies owned here)
+    void ps_table(ResampleTable& t, int a, int b);
+    DevBuf ps_buf_;                    // fetch-time scratch of the shift: exists only once a fetch ran with pitch on
+    // per row the span, the window, per frame the offset and its score, the stretched rows [rows][Ws] and the shifted rows [rows][W]
+    struct PsScratch { int64_t* n; float* win; int* delta; float* score; float* ys; float* y; size_t bytes; };
+    static PsScratch ps_layout(char* base, int64_t rows, int64_t W, const PitchPlan& p);
+    std::vector<int64_t> ps_n_; std::vector<float> ps_win_;  // what the uploads into ps_buf_ read
+    // what ps_buf_'s shifted rows belong to: the finished batch's waveform, the setting, the shape, the scratch
+    struct PsKey {
+        uint64_t seq = 0, gen = 0; int64_t W = 0; int B = 0; const void* buf = nullptr;
+        bool operator==(const PsKey& o) const { return seq == o.seq && gen == o.gen && W == o.W && B == o.B && buf == o.buf; }
+    };
+    PsKey ps_key_; bool ps_valid_ = false;
+    // the two launches of the stretch on rows x W fp32 (x) with spans n (device) under win (device): the offsets, their scores and the
+    // stretched rows ys [rows][p.Ws]
+    void ps_enqueue(const float* x, int64_t rows, int64_t W, const int64_t* n, int a, int b, const PitchPlan& p, const float* win, int* delta, float* score,
+                    float* ys);
+    // the stretched rows resampled by t (b / a) into y [rows][W]: the first W outputs of each
+    void ps_resample(const ResampleTable& t, const float* ys, int64_t rows, int64_t Ws, int64_t W, float* y);
+    void ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out);
+    // the finished batch's B rows x W at the model's rate shifted into ps_buf_ (b.wav is left as it is): the rows every later stage
+    // reads, row stride W.  Enqueued unless the scratch holds them already
+    const float* ps_batch();
+    // the rows the output stage starts from: b.wav, or with pitch on the shifted rows
+    const float* wav_rows() { return pitch_on() ? ps_batch() : bt_.wav; }
     bool lo_on_ = false;
     float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
     LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
@@ -842,7 +885,8 @@ class Engine {
     struct CpKey {
         uint64_t seq = 0; int hz = 0; uint64_t fl = 0, cp = 0; int64_t Wo = 0; const void* buf = nullptr;
         uint64_t ds = 0;  // ds_gen_ of the de-esser setting in front of it
-        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds; }
+        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
+        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds && ps == o.ps; }
     };
     CpKey cp_key_; bool cp_valid_ = false;
     void cp_prepare(CompTable& t, int hz, const stn_compressor& c);
@@ -865,7 +909,8 @@ class Engine {
     // what the row maxima in ds_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
     struct DsKey {
         uint64_t seq = 0; int hz = 0; uint64_t fl = 0, ds = 0; int64_t Wo = 0; const void* buf = nullptr;
-        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf; }
+        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
+        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf && ps == o.ps; }
     };
     DsKey ds_key_; bool ds_valid_ = false;
     void ds_prepare(DeessTable& t, int hz, const stn_deesser& c);
@@ -874,7 +919,8 @@ class Engine {
     // sequence leaves it
     void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
     DsScratch ds_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) de-essed into y (may be x)
-    // out_source() returns fetch scratch (row stride Wo), not b.wav
+    // out_source() returns the fp32 fetch scratch (row stride Wo), not the rows the stage starts from (wav_rows(): b.wav, or with pitch on
+    // the shifted rows in the pitch scratch, row stride W like b.wav: pitch alone needs no second copy)
     bool out_in_scratch() const { return resample_on() || filter_on() || deesser_on() || compressor_on(); }
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
@@ -900,8 +946,10 @@ class Engine {
         uint64_t fl = 0;  // fl_gen_ of the filter chain the rows went through
         uint64_t cp = 0;  // cp_gen_ of the compressor setting they went through
         uint64_t ds = 0;  // ds_gen_ of the de-esser setting they went through
+        uint64_t ps = 0;  // ps_gen_ of the pitch they were shifted by
         bool operator==(const EdKey& o) const {
-            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp && ds == o.ds;
+            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp && ds == o.ds &&
+                   ps == o.ps;
         }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
@@ -981,7 +1029,7 @@ class Engine {
     DevBuf join_tab_;
     std::vector<int64_t> join_tab_host_;  // what join_tab_ holds (empty: nothing)
     int64_t out_row_len();               // samples per delivered row; sets the device and throws without a finished batch
-    bool out_native() const;             // neither resampled, filtered nor normalized: the delivered fp32 rows are b.wav itself
+    bool out_native() const;             // neither shifted, resampled, filtered nor normalized: the delivered fp32 rows are b.wav itself
     // the finished batch at the output rate: b.wav, or resampled and / or filtered (section 18) into the fp32 scratch, row stride Wo
     const float* out_source(int64_t Wo);
     float* out_f32_buf(size_t n) { return reinterpret_cast<float*>(out_f32_.reserve(*this, n * sizeof(float))); }

@@ -434,19 +434,21 @@ int64_t Engine::out_row_len() {
     return out_len(native_row_len());
 }
 
-bool Engine::out_native() const { return !loudness_on() && !out_in_scratch(); }
+bool Engine::out_native() const { return !pitch_on() && !loudness_on() && !out_in_scratch(); }
 
 const float* Engine::out_source(int64_t Wo) {
     const Batch& b = bt_;
-    if (!out_in_scratch()) return b.wav;
+    // section 24: with pitch on every stage starts from the shifted rows (pitch scratch, row stride W) instead of b.wav
+    const float* wav = wav_rows();
+    if (!out_in_scratch()) return wav;
     float* d = out_f32_buf((size_t)b.B * Wo);
-    if (resample_on()) resample_enqueue(rs_table(), b.wav, b.B, native_row_len(), ENC_F32, d, Wo);
+    if (resample_on()) resample_enqueue(rs_table(), wav, b.B, native_row_len(), ENC_F32, d, Wo);
     // section 18: the chain runs on the rows at the output rate, in place behind the resampler, out of b.wav (left as it is) otherwise
-    if (filter_on()) fl_batch(resample_on() ? d : b.wav, Wo, d);
+    if (filter_on()) fl_batch(resample_on() ? d : wav, Wo, d);
     // section 21: the de-esser behind the chain, in place in the scratch, out of b.wav (left as it is) when nothing ran in front of it
-    if (deesser_on()) ds_batch(resample_on() || filter_on() ? d : b.wav, Wo, d);
+    if (deesser_on()) ds_batch(resample_on() || filter_on() ? d : wav, Wo, d);
     // section 20: the compressor behind those, likewise
-    if (compressor_on()) cp_batch(resample_on() || filter_on() || deesser_on() ? d : b.wav, Wo, d);
+    if (compressor_on()) cp_batch(resample_on() || filter_on() || deesser_on() ? d : wav, Wo, d);
     return d;
 }
 
@@ -503,16 +505,17 @@ void Engine::enqueue_output(const OutRows& o) {
         // section 23: the resampler's fused store truncates; a dithered fetch resamples into the fp32 scratch and ends in the one store
         // (one definition of the quantizer, one more pass over the rows)
         float* d = out_f32_buf((size_t)b.B * Wo);
-        resample_enqueue(rs_table(), b.wav, b.B, W, ENC_F32, d, Wo);
+        resample_enqueue(rs_table(), wav_rows(), b.B, W, ENC_F32, d, Wo);
         StageSpan span(*this, "out", "store_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, d, b.B, Wo, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
     } else if (resample_on()) {
-        resample_enqueue(rs_table(), b.wav, b.B, W, o.enc, o.dst, o.stride);
+        resample_enqueue(rs_table(), wav_rows(), b.B, W, o.enc, o.dst, o.stride);
     } else if (o.enc != ENC_F32) {
+        const float* src = wav_rows();
         StageSpan span(*this, "out", "store_rows", (double)b.B * W, (double)b.B * W * (4 + eb));
-        launch_store_rows(s_, b.wav, b.B, W, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
+        launch_store_rows(s_, src, b.B, W, nullptr, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
     } else {
-        STN_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.stride * 4, b.wav, (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
+        STN_HIP(hipMemcpy2DAsync(o.dst, (size_t)o.stride * 4, wav_rows(), (size_t)W * 4, (size_t)W * 4, (size_t)b.B, hipMemcpyDeviceToDevice, s_));
     }
     STN_HIP(hipGetLastError());
 }

@@ -35,12 +35,17 @@ std::string resample_design(int in_hz, int out_hz, ResampleTable& f) {
     if (P > RESAMPLE_MAX_P)
         return "output rate " + std::to_string(out_hz) + " Hz against " + std::to_string(in_hz) + " Hz reduces to P/Q = " + std::to_string(P) + "/" +
                std::to_string(Q) + ": P must be <= " + std::to_string(RESAMPLE_MAX_P);
+    resample_design_pq(P, Q, in_hz, out_hz, f);
+    return "";
+}
+
+void resample_design_pq(int P, int Q, int in_hz, int out_hz, ResampleTable& f) {
     f.in_hz = in_hz; f.out_hz = out_hz; f.P = P; f.Q = Q;
     if (P == Q) {  // the same rate: one centred unit tap (a copy)
         f.T = 8; f.off = 3;
         f.taps.assign(8, 0.f);
         f.taps[3] = 1.f;
-        return "";
+        return;
     }
     constexpr double A = 90.0;
     const double beta = 0.1102 * (A - 8.7);
@@ -68,7 +73,6 @@ std::string resample_design(int in_hz, int out_hz, ResampleTable& f) {
         }
         for (int j = 0; j < f.T; ++j) f.taps[(size_t)p * T + j] = (float)(h[j] / sum);
     }
-    return "";
 }
 
 void Engine::rs_prepare(ResampleTable& t, int in_hz, int out_hz) {
@@ -84,7 +88,7 @@ void Engine::rs_prepare(ResampleTable& t, int in_hz, int out_hz) {
 }
 
 void Engine::rs_release() {
-    for (ResampleTable* t : {&rs_, &op_rs_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
+    for (ResampleTable* t : {&rs_, &op_rs_, &ps_rs_, &op_ps_rs_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
 }
 
 void Engine::set_output_rate(int hz) {

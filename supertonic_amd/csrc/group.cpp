@@ -236,6 +236,9 @@ int stn_group_set_peak_mode(stn_group* g, int mode) {
 int stn_group_set_dither(stn_group* g, int mode, uint64_t seed) {
     return for_all(g, "stn_set_dither", [](stn_handle* h, const void* a, uint64_t v) { return stn_set_dither(h, *static_cast<const int*>(a), v); }, &mode, seed);
 }
+int stn_group_set_pitch(stn_group* g, float semitones) {
+    return for_all(g, "stn_set_pitch", [](stn_handle* h, const void* a, uint64_t) { return stn_set_pitch(h, *static_cast<const float*>(a)); }, &semitones, 0);
+}
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f) {
     struct S { int n; const stn_filter* f; } v{n, f};
     return for_all(g, "stn_set_filters", [](stn_handle* h, const void* a, uint64_t) {

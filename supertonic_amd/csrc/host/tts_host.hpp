@@ -87,6 +87,8 @@ struct EngineOptions {
                                    // CLI --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] and --deesser-preset speech
     int encoding = STN_ENC_PCM16;  // sample encoding of the returned audio and the WAV files (STN_ENC_*, stn.h; encoded on the GPU).  PCM16
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
+    float pitch = 0.0f;            // every utterance shifted by this many semitones ([-12, 12]) on the GPU without a change of length, in front of
+                                   // everything above (stn_set_pitch); 0: off.  CLI --pitch SEMITONES
     int dither = STN_DITHER_OFF;   // how 16- and 24-bit PCM is quantized on the GPU (stn_set_dither): STN_DITHER_OFF truncates as writeWavFile;
     uint64_t dither_seed = 0;      // _ROUND, _TPDF, _TPDF_HP round, behind dither keyed by this seed.  With a mode set, PCM16 is fetched as
                                    // 16-bit samples (not as floats for writeWavFile).  CLI --dither {off,round,tpdf,tpdf-hp} and --dither-seed N

@@ -492,10 +492,14 @@ constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P =
 inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
 // Kaiser-windowed sinc for the pair (host only): fills f (not f.dev).  Empty string on success, else why the pair is refused.
 std::string resample_design(int in_hz, int out_hz, ResampleTable& f);
+// The design's arithmetic for the reduced pair P / Q, with the two rates it is stated in (in_hz = Q g, out_hz = P g for one g): what
+// resample_design runs behind its checks of the rates, and what the pitch shift (section 24) designs its a / b table with
+void resample_design_pq(int P, int Q, int in_hz, int out_hz, ResampleTable& f);
 double bessel_i0(double x);  // the Kaiser window's shape (engine_resample.cpp)
 // rows x W fp32 (row stride W) -> rows x W_out at y + row * dst_stride samples (dst_stride >= W_out) in encoding enc (the encoded
 // bytes are those of the fp32 output followed by launch_store_rows without a gain)
-void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride);
+// cap > 0: only the first min(cap, W_out) samples of a row are stored (dst_stride >= that); every stored sample is what it is without a cap
+void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride, int64_t cap = 0);
 // The form a resample call takes — one decision, made by resample_form (host only: P, Q and T of f) and executed by launch_resample, so
 // that what the diagnostics report (stn_dbg_resample_form) is what runs.  A workgroup owns G * 64 consecutive k of a row (output
 // n = k * P + r) and every r; G doubles from 1 while G * P < 16 (the waves have pairs to walk), G * 64 < K (the row has the k) and the
@@ -508,6 +512,16 @@ struct ResampleForm {
     std::string str() const;  // "resample lds G4", "resample cache G1"
 };
 ResampleForm resample_form(int64_t W, const ResampleTable& f);  // throws std::invalid_argument for W < 1 or a table without a design
+
+// Time-scale modification of the finished waveform (kernels_pitch.hip; the geometry is host/pitch.cpp, the rule DESIGN.md section 24):
+// WSOLA with a normalised search.  rows x W fp32 (row stride W), row r's span n[r] (device, clamped to [0, W]; null: W), hop H (a power
+// of two in [64, 2048]), stretched by a / b over M = ceil(W a / b) / H + 2 frames.  launch_pitch_search: one workgroup per row walks its
+// frames and writes delta [rows][M] (the offsets, delta[.][0] = 0) and score [rows][M] (the winners' scores, 0 for frame 0).
+// launch_pitch_ola: y [rows][Ws], Ws = ceil(W a / b), the overlap-add of the grains at those offsets under win (device, 2 H floats: the
+// periodic Hann of pitch_window), 0.0f from the row's stretched span ceil(n a / b) on.  A read outside a row's span is 0.0f.
+void launch_pitch_search(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int H, int64_t M, int a, int b, int* delta, float* score);
+void launch_pitch_ola(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int H, int64_t M, int64_t Ws, int a, int b, const int* delta,
+                      const float* win, float* y);
 
 // Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the measurement are engine_loudness.cpp).
 // BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in

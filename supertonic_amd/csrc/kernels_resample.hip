@@ -86,11 +86,13 @@ __global__ void __launch_bounds__(RS_THREADS) resample_kernel(const float* __res
 }
 
 template <int kEnc>
-void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, unsigned char* y, int64_t dst_stride) {
+void launch_resample_t(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, unsigned char* y, int64_t dst_stride, int64_t cap) {
     if (rows <= 0 || W <= 0) return;
     if (f.T % 8 != 0 || f.T < 8 || f.P < 1 || f.Q < 1 || !f.dev) throw std::runtime_error("launch_resample: filter table not prepared");
     if (rows > 65535) throw std::invalid_argument("launch_resample: more than 65535 rows");
-    const int64_t W_out = resample_out_len(W, f.P, f.Q);
+    if (cap < 0) throw std::invalid_argument("launch_resample: negative cap");
+    // (the kernel's W_out is its store guard only: a capped launch stores the first `cap` outputs of a row and computes them as ever)
+    const int64_t W_out = cap > 0 ? std::min(cap, resample_out_len(W, f.P, f.Q)) : resample_out_len(W, f.P, f.Q);
     if (dst_stride < W_out) throw std::invalid_argument("launch_resample: dst_stride smaller than the output row length");
     const ResampleForm fm = resample_form(W, f);  // the one place G and the staging path are chosen
     const dim3 grid((unsigned)fm.grid_x, (unsigned)rows);
@@ -124,8 +126,8 @@ ResampleForm resample_form(int64_t W, const ResampleTable& f) {
     return fm;
 }
 
-void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride) {
-    with_enc(enc, "launch_resample", [&](auto e) { launch_resample_t<decltype(e)::value>(s, x, rows, W, f, static_cast<unsigned char*>(y), dst_stride); });
+void launch_resample(hipStream_t s, const float* x, int64_t rows, int64_t W, const ResampleTable& f, int enc, void* y, int64_t dst_stride, int64_t cap) {
+    with_enc(enc, "launch_resample", [&](auto e) { launch_resample_t<decltype(e)::value>(s, x, rows, W, f, static_cast<unsigned char*>(y), dst_stride, cap); });
 }
 
 }  // namespace stn

@@ -38,6 +38,7 @@ _PARSE = {
     "limiter": _switched(binding.limiter_args),
     "peak_mode": _peak_mode,
     "dither": lambda v: binding.dither_args(v) or False,
+    "pitch": lambda v: binding.pitch_args(v) or False,
 }
 
 
@@ -70,7 +71,9 @@ class OutputSettings:
                   it acts only while loudness is on.  Off: "sample".
     dither        how the 16- and 24-bit PCM stores quantize, the last step (stn_set_dither): True or "tpdf", "tpdf-hp", "round", or
                   (mode, seed), as binding.dither_args takes them; it acts on audio fetched as "pcm16" or "pcm24" only (float, mu-law
-                  and A-law are unaffected).  Normalized: (mode name, seed).  Off: False or "off", the truncating store."""
+                  and A-law are unaffected).  Normalized: (mode name, seed).  Off: False or "off", the truncating store.
+    pitch         every utterance shifted by this many semitones ([-12, 12]) without a change of length, the first step: everything above
+                  sees the shifted audio (stn_set_pitch).  Normalized: a float.  Off: False or 0."""
     output_rate: object = None
     filters: object = None
     loudness: object = None
@@ -89,9 +92,13 @@ class OutputSettings:
     # gives OFF; OFF is the constructor's value of its seven arguments), which no further field of any kind satisfies.  So neither
     # names it, and who needs every setting decided asks decided().
     dither = None
+    # An attribute like dither, for the same reasons.  Unset and off compare and hash equal here, so that a value decided() made stays
+    # equal to ALL_OFF with dither off, as it was before the setting was there.  Where the difference matters (a request that names no
+    # pitch gets the server's, one that says 0 gets none) the service's BatchKey carries it beside the settings (pitch_set).
+    pitch = None
 
     def _all(self):
-        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither,)
+        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither, self.pitch or False)
 
     def __eq__(self, other):
         return other._all() == self._all() if type(other) is type(self) else NotImplemented
@@ -100,12 +107,12 @@ class OutputSettings:
         return hash(self._all())
 
     def __repr__(self):
-        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither"], self._all())) + ")"
+        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither", "pitch"], self._all())) + ")"
 
     def decided(self):
-        """This value over ALL_OFF, and dither off where that leaves it unset: every setting decided (what an instance holds)"""
+        """This value over ALL_OFF, and dither and pitch off where that leaves them unset: every setting decided (what an instance holds)"""
         s = self.over(OutputSettings.ALL_OFF)
-        return s if s.dither is not None else s.replace(dither=False)
+        return s.replace(dither=False if s.dither is None else s.dither, pitch=False if s.pitch is None else s.pitch)
 
     @classmethod
     def parse(cls, **kw):
@@ -117,12 +124,13 @@ class OutputSettings:
         return cls().replace(**{k: p(kw[k]) for k, p in _PARSE.items() if kw.get(k) is not None})
 
     def replace(self, **changes):
-        """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser
-        and dither included"""
-        deesser, dither = changes.pop("deesser", self.deesser), changes.pop("dither", self.dither)
+        """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser,
+        dither and pitch included"""
+        deesser, dither, pitch = changes.pop("deesser", self.deesser), changes.pop("dither", self.dither), changes.pop("pitch", self.pitch)
         new = dataclasses.replace(self, **changes)
         object.__setattr__(new, "deesser", deesser)
         object.__setattr__(new, "dither", dither)
+        object.__setattr__(new, "pitch", pitch)
         return new
 
     def kwargs(self):
@@ -138,7 +146,10 @@ class OutputSettings:
 
     def apply(self, engine):
         """The set fields onto a binding.Engine, in the one order that works: a chain is checked against the output rate in force, so
-        it goes off before the rate changes and on after it, and so does the de-esser.  The rest are independent of each other."""
+        it goes off before the rate changes and on after it, and so does the de-esser.  The rest are independent of each other; pitch,
+        the first stage of the chain, goes first."""
+        if self.pitch is not None:
+            engine.set_pitch(self.pitch or None)
         if self.filters is not None:
             engine.set_filters(None)
         if self.deesser is not None and (self.output_rate is not None or not self.deesser):
@@ -176,6 +187,6 @@ class OutputSettings:
 
 
 # OFF leaves compressor and deesser unset (a base that does not name them compares equal after over(OFF)); ALL_OFF names every field
-# (dither, which is none, neither names: decided())
+# (dither and pitch, which are none, neither names: decided())
 OutputSettings.OFF = OutputSettings(0, (), False, False, False, False, "sample")
 OutputSettings.ALL_OFF = OutputSettings.OFF.replace(compressor=False, deesser=False)

@@ -30,12 +30,14 @@ REPORT_HEADERS = {"X-Loudness-Integrated": "integrated", "X-Loudness-Range": "ra
 
 
 # what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
-BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings")
+# (pitch_set: whether the request names a pitch.  OutputSettings compares an unset pitch equal to an off one; the key must not: a request
+# that names none gets the synthesizer's own pitch, one that says 0 gets none)
+BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings pitch_set")
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
               trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, dither=None,
-              dither_seed=None, compressor=None):
+              dither_seed=None, pitch=None, compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -47,7 +49,9 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     against the request's rate as well.  compressor: True, a dict or a 6-tuple as binding.compressor_args takes it, False = off,
     checked against the engine's limits.  dither ("off", "round", "tpdf", "tpdf-hp" or true for "tpdf"; false = off) with dither_seed (an
     integer in [0, 2^64), 0 when left out; alone it is validated and dropped): OutputSettings' dither.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
-    loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode."""
+    loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode.  pitch: semitones in [-12, 12] (0 = off),
+    refused with the engine's message: requests of different pitch never share a batch, and neither do one that names none (the
+    synthesizer's own holds) and one that says 0."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
     if why:
@@ -61,7 +65,7 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     if why:
         raise ValueError(why)
     dith = binding.dither_args(dither or "off", dither_seed) or False
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, dither=None if dither is None else dith, loudness=None if loudness is None else (loudness, peak_ceiling),
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, dither=None if dither is None else dith, pitch=pitch, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
@@ -70,7 +74,7 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     if s.trim_silence is None:
         s = s.replace(max_pause=None)
     return BatchKey(int(total_step), float(speed), None if encoding is None else binding.encoding_id(encoding), str(loudness_scope),
-                    bool(trim_chunks), s)
+                    bool(trim_chunks), s, s.pitch is not None)
 
 
 class _Job:
@@ -294,6 +298,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                               "server's.  No effect on f32, mulaw and alaw.")
         dither_seed: Optional[int] = Field(None, ge=0, lt=1 << 64, description="Seed of the dither noise (0 when left out): with the utterance's "
                                                                                "place in its batch and the sample index it fixes the noise.")
+        pitch: Optional[float] = Field(None, description="Pitch shift in semitones, a number in [-12, 12], applied on the GPU in front of every other "
+                                                         "setting without a change of duration; 0: off; null: the server's.  The response's "
+                                                         "X-Pitch-Cents header carries the realised shift.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -370,6 +377,13 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             dith = None  # (a seed alone: validated and dropped)
         else:
             extra["dither"] = dith
+        pitch = None
+        if req.pitch is not None:
+            why = binding.pitch_error(req.pitch)
+            if why:
+                raise HTTPException(status_code=400, detail=why)
+            pitch = binding.pitch_args(req.pitch)
+            extra["pitch"] = pitch
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
@@ -405,13 +419,15 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                                trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
                                                max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp,
-                                               dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, **more)
+                                               dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, pitch=pitch, **more)
             report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
         if len(chunks) == 1:
             name = host.sanitize_filename(texts[0], 40) or "tts"
             headers = {"Content-Disposition": f'attachment; filename="{_ascii(name)}.wav"'}
+            in_force = pitch if pitch is not None else (getattr(getattr(tts, "settings", None), "pitch", None) or 0.0)
+            headers["X-Pitch-Cents"] = f"{binding.pitch_cents(in_force):.3f}"  # the realised shift (a / b), 0.000 when off
             if report:
                 headers.update({h: f"{report[k]:.3f}" for h, k in REPORT_HEADERS.items()})
             return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav", headers=headers)
