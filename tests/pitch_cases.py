@@ -69,6 +69,44 @@ def rows(hz):
     return x, np.asarray(ns, np.int64), tuple(names)
 
 
+# ---- the wide hops: H = 256, 1024 and 2048 (the rates above have 64, 128 and 512) ----------------------------------------------------------
+# H = 256 searches with 448 threads, the one geometry of 7 waves; at 1024 and 2048 the 1537 and 3073 candidates take the 1024 threads 2 and
+# 4 trips, the last by thread 0 alone for d = +D, and 2048 fills the prefetch registers and takes 73.9 KB of LDS
+WIDE_RATES = (24000, 96000, 192000)
+WIDE_W = {hz: 16 * pr.hop(hz) for hz in WIDE_RATES}  # 4096, 16384 and 32768 samples: 11 to 27 frames at the ratios below
+# the analysis position moves by H b / a a frame and the continuation by H, so on a row with one good candidate the offset moves by
+# H (1 - b / a) a frame until it leaves [-D, D].  8/5: 0, 3 H / 8, 3 H / 4 = +D exactly, then wherever the best of a bad lot lies;
+# 4/7: frame 1 lands on -3 H / 4 = -D exactly
+WIDE_RATIOS = ((8, 5), (4, 7), (3, 2), (640, 639))
+
+
+def noise(hz, W):
+    """white noise at 0.25 RMS: the only good candidate of a frame is the exact continuation of the grain before, so the ratio steers
+    the winners (above), and no slice of the candidates holds a second best that passes for the best"""
+    return (0.25 * np.random.default_rng(9).standard_normal(W)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_rows(hz):
+    """-> (x float32 [R][W], n [R], names) at one of WIDE_RATES: the noise row, the vowel row, the vowel row cut at 0.7 W with NaN behind
+    the span, an all-zero row, and the harmonic row at spans H - 1 and 1"""
+    w = WIDE_W[hz]
+    H = pr.hop(hz)
+    h, v = harmonic(hz, w), vowel(hz, w)
+    nan = v.copy()
+    n_nan = int(0.7 * w)
+    nan[n_nan:] = np.nan
+    x = np.stack([noise(hz, w), v, nan, np.zeros(w, np.float32), h, h])
+    x.setflags(write=False)
+    return x, np.asarray([w, w, n_nan, w, H - 1, 1], np.int64), ("noise", "vowel", "vowel+nan", "zero", f"harmonic[:{H - 1}]", "harmonic[:1]")
+
+
+def search_threads(hz):
+    """the workgroup of the search: a thread per candidate up to 1024, in whole waves (kernels_pitch.hip) -> (threads, candidates)"""
+    C = 2 * (3 * pr.hop(hz) // 4) + 1
+    return min(1024, -(-C // 64) * 64), C
+
+
 def steady(hz, Wn):
     """the steady part of a row of Wn samples: two grains in from either end, a whole number of 10-ms blocks"""
     N = 2 * pr.hop(hz)

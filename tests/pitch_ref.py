@@ -186,6 +186,26 @@ def decision_gaps(x, n, hz, a, b, delta):
     return gap, margin
 
 
+def judge(x, n, hz, a, b, delta):
+    """decision_gaps and tie_frames in one pass over the frames, and what settles a decision outright -> dict: gap [M], margin [M] (as
+    decision_gaps), ties (as tie_frames), lead [M] (the best float64 score minus the best of every other candidate's; 0 where two share
+    the top) and pick [M] (the rule's d_m given the table's own d_{m-1}).  Every fp32 score is within margin of its float64 value, so
+    where lead > 2 margin no rounding puts another candidate in front of the best and d_m must be pick."""
+    p = plan(hz, len(x), a, b)
+    row = Row(x, n)
+    out = dict(gap=np.zeros(p["M"]), margin=np.zeros(p["M"]), lead=np.zeros(p["M"]), pick=np.zeros(p["M"], np.int64), ties=[])
+    for m in range(1, p["M"]):
+        s, tn = frame_scores(row, p["H"], a, b, m, int(delta[m - 1]))
+        out["gap"][m] = s.max() - s[int(delta[m]) + p["delta"]]
+        out["margin"][m] = 4.0 * (p["N"] + 8) * 2.0 ** -24 * tn
+        top = np.partition(s, -2)[-2:]
+        out["lead"][m] = top[1] - top[0]
+        out["pick"][m] = pick(s, p["delta"])
+        if not np.any(s != 0.0):
+            out["ties"].append(m)
+    return out
+
+
 def tie_frames(x, n, hz, a, b, delta):
     """the frames m >= 1 whose target or whose every candidate is all zero given the table's own d_{m-1}: every score is 0 there and the
     rule pins d_m = 0"""

@@ -3,18 +3,25 @@ test_output_walk_cpu.py shows that a key short of one field fails them): a fetch
 force, and on nothing the handle did before.  One live handle (tiny arch, bf16, length-aware vocoder) plays a walk; after every step a
 fresh handle is created, loaded, given the step's batch and waveform and the step's settings once, in a fixed order, and everything the
 two deliver must be equal in dtype, shape and bytes: batch_fetch, two encodings that rotate through the five, a pipelined slot fetch, a
-device copy into a sentinel-filled buffer of odd stride, the joined fetch in both gain scopes, batch_join_loudness and all seven reports
-(a refused report must be refused by both with one code).  A refused set call must raise and change nothing; graphs_cached and
+device copy into a sentinel-filled buffer of odd stride, the joined fetch in both gain scopes, batch_join_loudness,
+batch_join_loudness_range and all eight reports (a refused report must be refused by both with one code; the rows are about a second
+long, short against the loudness range's 3 s window, which both handles then report alike).  A refused set call must raise and change nothing; graphs_cached and
 graph_replays of the live handle move on a batch step only.  A failure prints the seed, the walk, the step and the history up to it as
 a list that output_walk's steps replay, with the output and the row that differ.
 
 Over each walk the fresh handles' own results show every stage a walk enables at work (samples limited, dB taken off by the compressor
 and the de-esser, edges inside a span, pauses cut, a gain other than 1, a true peak over the sample peak); every walk prints its figures.
+Two figures are taken at every step that enables them, on the fresh handle once the comparison is over: `shifted`, the largest |fp32
+fetch - the same fetch with pitch off|, and `dithered`, the PCM16 samples that differ from the same fetch with dither off (at the steps
+whose encoded fetches hold a PCM encoding); either must be above 0 at every such step.
 
 Cost, measured on an MI355X against the clock alone: a fresh handle is 7 ms to create and load, 1.2 ms to upload and run its batch and
 2 ms to take (the process's first handle adds 1.7 s of runtime start, once); a step with both takes and the host's comparison comes to
-20 to 45 ms, a walk of 16 steps to 0.55 to 0.75 s, and the file's five walks to 4.1 s of wall time with the start.  A fresh handle per
-step fits: every step is compared.  The walks of 25 more seeds (2000 steps) were played once the same way and met no difference."""
+20 to 45 ms, a walk of 16 steps to 0.55 to 0.75 s, and the file's five walks to 4.1 s of wall time with the start.  With pitch, dither
+and the loudness-range outputs in every comparison: the seven walks take 0.65 to 0.80 s each (walk 5, whose every fresh handle shifts
+its batch and whose two op steps stretch 2 x 120011 samples, 0.80 s; walk 6 0.77 s), and the file 6.5 s of wall time with the start.
+A fresh handle per step fits: every step is compared.  The five walks of then were played the same way for 25 more seeds (2000
+steps), walks 5 and 6 for 12 more (384 steps, 0.25 to 0.41 s a walk once the process is warm), and met no difference."""
 import time
 
 import numpy as np
@@ -37,12 +44,16 @@ _SETTERS = dict(
     peak=lambda e, v: e.set_peak_mode(v),
     trim=lambda e, v: e.set_silence_trim(v),
     pause=lambda e, v: e.set_pause_limit(v),
+    pitch=lambda e, v: e.set_pitch(v),
+    dither=lambda e, v: e.set_dither(v),
 )
-# the three whose out-of-range values the binding's own parsers stop: through the C ABI itself, so that the engine is the one to refuse
+# the five whose out-of-range values the binding's own parsers stop: through the C ABI itself, so that the engine is the one to refuse
 _RAW = dict(
     limiter=lambda e, v: e._ck(e._lib.stn_set_limiter(e._h, 1, float(v))),
     trim=lambda e, v: e._ck(e._lib.stn_set_silence_trim(e._h, 1, *(float(x) for x in v))),
     pause=lambda e, v: e._ck(e._lib.stn_set_pause_limit(e._h, 1, float(v))),
+    pitch=lambda e, v: e._ck(e._lib.stn_set_pitch(e._h, float(v))),
+    dither=lambda e, v: e._ck(e._lib.stn_set_dither(e._h, int(v[0]), int(v[1]))),
 )
 _WAVS = {}
 
@@ -81,8 +92,8 @@ def _fresh(a, state):
     return e
 
 
-def _op_rows(variant):
-    rows, W = ((3, 5000), (7, 120011))[variant]
+def _op_rows(variant, most=7):
+    rows, W = ((3, 5000), (min(most, 7), 120011))[variant]
     t = np.arange(W)
     x = np.stack([(0.2 + 0.1 * r) * np.sin(t / (7.0 + r)) * ((t // 1500) % 3 != 1) for r in range(rows)]).astype(np.float32)
     x[:, ::997] = 0.95
@@ -91,7 +102,8 @@ def _op_rows(variant):
 
 def _op(e, family, variant):
     """one op-level call on rows that have nothing to do with the batch"""
-    x, n = _op_rows(variant)
+    # (the two stretches search their rows frame by frame, a workgroup per row: two rows in variant 1, about 295 and 200 frames each)
+    x, n = _op_rows(variant, most=2 if family in ("time_stretch", "pitch") else 7)
     hz = (16000, 48000)[variant]
     rows = x.shape[0]
     if family == "resample":
@@ -117,6 +129,14 @@ def _op(e, family, variant):
         e.op_join(x, n, [rows - 1, 1], 50, hz, encoding="pcm16", loudness=(-20.0, -1.0))
     elif family == "encode":
         e.op_encode(x, "mulaw")
+    elif family == "time_stretch":
+        e.op_time_stretch(x, hz, 5, 4, n=n)
+    elif family == "pitch":
+        e.op_pitch(x, hz, -3.0, n=n)
+    elif family == "loudness_range":
+        e.op_loudness_range(x, hz, n)
+    elif family == "encode_ex":
+        e.op_encode_ex(x, "pcm16", dither="tpdf-hp", seed=3, gain=np.full(rows, 0.5, np.float32))
     else:
         raise KeyError(family)
 
@@ -153,6 +173,8 @@ def _one(e, name, i, state):
         return e.batch_fetch_joined(*join, mode=mode, gain_scope=name[5:], encoding=encs[0] if name == "join_row" else None, cut=False)
     if name == "join_loudness":
         return e.batch_join_loudness(*join, mode=mode)
+    if name == "join_loudness_range":
+        return e.batch_join_loudness_range(*join, mode=mode)
     r = getattr(e, "batch_" + name)()
     return (r,) if isinstance(r, np.ndarray) else r
 
@@ -212,17 +234,31 @@ def _play(a, e, state, step):
     return ow.apply(state, step)
 
 
-def _busy(busy, state, want, f):
-    """what the fresh handle's results show of the stages the state enables"""
+def _busy(busy, state, want, f, i):
+    """what the fresh handle's results show of the stages the state enables (the comparison is over: the fresh handle is asked once
+    more with one setting off, for the figures that need the other fetch)"""
     on = lambda n: state[n] != ow.OFF[n]  # noqa: E731
     B, _, Wo = f.batch_dims()
+    if on("dither") and {"pcm16", "pcm24"} & set(ow.encodings(i)):
+        with_dither = f.batch_fetch_encoded("pcm16")[0]
+        f.set_dither(None)
+        n = int(np.count_nonzero(with_dither != f.batch_fetch_encoded("pcm16")[0]))
+        assert n > 0, "dither on and no PCM16 sample differs from the fetch without"
+        busy["dithered"] = max(busy.get("dithered", 0), n)
+    if on("pitch"):
+        with_pitch = f.batch_fetch()[0]
+        f.set_pitch(None)
+        d = float(np.abs(with_pitch - f.batch_fetch()[0]).max())
+        f.set_pitch(state["pitch"])  # (the figures below are the shifted rows')
+        assert d > 0.0, "pitch on and the fp32 fetch is the one without"
+        busy["shifted"] = max(busy.get("shifted", 0.0), d)
     if on("loudness"):
         busy["gain"] = max(busy.get("gain", 0.0), float(np.abs(want["loudness"][2] - 1.0).max()))
         if on("limiter"):
             busy["limited"] = max(busy.get("limited", 0), int(want["limiter"][1].max()))
         if on("peak") and "true_peak_over_sample_db" not in busy:
             tp = want["true_peak"][0]
-            f.set_peak_mode("sample")  # (the comparison is over: the fresh handle is asked once more, for the sample peaks)
+            f.set_peak_mode("sample")  # (once more, for the sample peaks)
             sp = f.batch_loudness()[1]
             busy["true_peak_over_sample_db"] = float((20 * np.log10(tp / sp)).max())
     if on("compressor"):
@@ -238,7 +274,7 @@ def _busy(busy, state, want, f):
 
 
 _NEEDS = dict(gain=("loudness",), limited=("loudness", "limiter"), true_peak_over_sample_db=("loudness", "peak"), compressor_db=("compressor",),
-              deesser_db=("deesser",), edges_inside=("trim",), cuts=("trim", "pause"))
+              deesser_db=("deesser",), edges_inside=("trim",), cuts=("trim", "pause"), shifted=("pitch",), dithered=("dither",))
 
 
 def _walk(w, walk):
@@ -261,9 +297,9 @@ def _walk(w, walk):
         history = f"seed {SEED}, walk {w}, step {i} {step!r}; replay with output_walk's steps:\n{walk[:i + 1]!r}"
         assert diff is None, f"output {diff[0]!r}, part {diff[1]}, rows {diff[2]} differ from a fresh handle's\n{history}"
         assert after == counters or step[0] == "batch", f"graphs_cached / graph_replays went {counters} -> {after}\n{history}"
-        _busy(busy, state, want, f)
+        _busy(busy, state, want, f, i)
         for k, needs in _NEEDS.items():
-            if all(state[n] != ow.OFF[n] for n in needs):
+            if all(state[n] != ow.OFF[n] for n in needs) and (k != "dithered" or {"pcm16", "pcm24"} & set(ow.encodings(i))):
                 enabled.add(k)
         f.close()
     e.close()
@@ -282,7 +318,8 @@ def test_every_setting_and_every_trim_field_changes_what_a_fresh_handle_delivers
     """(the comparison has something to see: on these rows, with everything on, a fresh handle one value away delivers other bytes, so
     a handle that kept the value before would be found out)"""
     a = tiny_arch()
-    base = dict(ow.start(), batch=2, rate=24000, peak="true", pause=60.0, **{n: ow.VALUES[n][0] for n in ("filters", "deesser", "compressor", "loudness", "limiter", "trim")})
+    base = dict(ow.start(), batch=2, rate=24000, peak="true", pause=60.0,
+                **{n: ow.VALUES[n][0] for n in ("filters", "deesser", "compressor", "loudness", "limiter", "trim", "pitch", "dither")})
     f = _fresh(a, base)
     want = _take(f, 0, base)
     f.close()

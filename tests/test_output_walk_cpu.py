@@ -1,6 +1,7 @@
 """The walks of output_walk.py, checked without a GPU: they hold every situation in which the output stage reuses something it kept (the
 coverage conditions), and they are sensitive: a fake engine built here, whose caches carry the fields of the real engine's keys
-(EdKey, CpKey, DsKey, the two windows' (rate, milliseconds), the span uploads' (rows, W); supertonic_amd/csrc/engine.hpp), delivers
+(EdKey, CpKey, DsKey, PsKey, the pitch's resample table per ratio, the two windows' (rate, milliseconds), the span uploads' (rows, W);
+supertonic_amd/csrc/engine.hpp, engine_pitch.cpp), delivers
 something else than a fresh fake on at least one walk as soon as one field is left out of one key.  The real engine is never edited to
 show that.
 
@@ -10,13 +11,19 @@ shown to be harmless instead of being passed over:
   * hz and Wo of the three keys: a batch's Wo is a function of its width and the rate, and another batch has another seq;
   * buf of the three keys: a grow-only buffer moves only when (rows, Wo) or the pause limit changed, which the key holds already;
   * (rows, W) of the loudness, compressor and de-esser span uploads: the uploaded spans themselves are compared beside the pointer, and
-    batches of unlike rows or W have unlike spans.  (The filter's upload holds no spans: there both are caught.)"""
+    batches of unlike rows or W have unlike spans.  (The filter's upload holds no spans: there both are caught.)
+  * W, B and buf of the shifted rows' key: another batch has another seq, and the pitch scratch moves only when the shape or the ratio
+    changed, which seq and gen hold already.
+
+Dither keeps nothing: the fake has no cache for it, and the setting enters only what a PCM16 / PCM24 output truly is (mode, seed, and
+whether the stream is a row's or a programme's)."""
 import hashlib
 import math
 
 import pytest
 
 import output_walk as ow
+import pitch_ref
 
 SEED = 0
 
@@ -33,7 +40,7 @@ def _changes(walk, name):
 # ---- the generator itself ---------------------------------------------------------------------------------------------------------------------
 def test_walks_are_fixed_and_every_step_is_valid(walks):
     assert walks == ow.walks(SEED) and walks != ow.walks(SEED + 1)
-    assert 3 <= len(walks) <= 5 and all(10 <= len(w) <= 16 for w in walks), [len(w) for w in walks]
+    assert 3 <= len(walks) <= 7 and all(10 <= len(w) <= 16 for w in walks), [len(w) for w in walks]
     for w in walks:
         s = ow.start()
         for step in w:
@@ -57,6 +64,23 @@ def test_walks_are_fixed_and_every_step_is_valid(walks):
             assert f <= 0.45 * lo and f >= hi / (2400.0 if kind in ("highpass", "lowpass") and 0.5 <= q <= 1.5 else 800.0), (kind, f)
     assert all(2000.0 <= d[0] <= 0.45 * lo and d[0] >= hi / 2400.0 for d in ow.VALUES["deesser"])
     assert 1000.0 * ow.PAUSE_S > max(ow.VALUES["pause"]) + 2 * max(t[1] for t in ow.VALUES["trim"])
+
+
+def test_the_first_five_walks_are_step_for_step_those_from_before_pitch_and_dither(walks):
+    """(the ten op families of then are shuffled and dealt as then; what walks 5 and 6 add takes nothing from the others' coverage)"""
+    assert all(len(w) == 16 for w in walks[:5])
+    assert hashlib.sha1(repr(ow.walks(0)[:5]).encode()).hexdigest() == "25c2934373e33ccc757aca21720d9115228b5fad"
+    assert {s[1] for w in walks[:5] for s in w if s[0] == "op"} == set(ow.OPS[:ow.N_SHUFFLED_OPS])
+    assert {s[1] for w in walks[5:] for s in w if s[0] == "op"} == set(ow.OPS[ow.N_SHUFFLED_OPS:])
+
+
+def test_the_pitch_values_are_realised_with_the_ratios_the_fake_keys_its_table_by():
+    for v, ab in zip(ow.VALUES["pitch"], ow.PITCH_RATIOS):
+        assert abs(v) < 12.0 and pitch_ref.ratio_brute(v) == ab == ow.pitch_ratio(v), (v, ab)
+    (a0, b0), (a1, b1), (a2, b2) = ow.PITCH_RATIOS
+    assert b0 == b1 and a0 != a1 and a0 == a2 and b0 != b2 and ow.pitch_ratio(None) == (1, 1)
+    assert ow.VALUES["dither"][0][0] == ow.VALUES["dither"][1][0] and ow.VALUES["dither"][0][1] != ow.VALUES["dither"][1][1]
+    assert {m for m, _ in ow.VALUES["dither"]} == {"round", "tpdf", "tpdf-hp"}
 
 
 # ---- coverage ---------------------------------------------------------------------------------------------------------------------------------
@@ -123,17 +147,48 @@ def test_dependent_settings_are_met_with_the_other_one_on_and_off(walks):
         assert any(on(s, dep) and on(s, needs) for s in st) and any(on(s, dep) and not on(s, needs) for s in st), (dep, needs)
 
 
+def test_the_pitch_walk_and_the_dither_walk_hold_their_situations(walks):
+    on = lambda s, n: s[n] != ow.OFF[n]  # noqa: E731
+    steps = lambda w: list(zip(range(len(w)), [ow.start()] + ow.states(w)[:-1], ow.states(w), w))  # noqa: E731
+    # walk 5: the shift under the compressor, the de-esser, trimming and loudness
+    w5 = steps(walks[5])
+    assert all(on(s, n) for _, _, s, _ in w5[4:] for n in ("compressor", "deesser", "trim", "loudness"))
+    moved = [i for i, p, s, k in w5 if k[:2] == ("set", "pitch") and on(p, "pitch") and on(s, "pitch") and p["pitch"] != s["pitch"]]
+    assert sorted(i % 4 for i in moved) == [0, 2]  # even steps: the compressor's report in front once, the de-esser's once
+    for i in moved:  # (each goes to a ratio that shares one term with the one before: the table of the way back is another one)
+        (a0, b0), (a1, b1) = (ow.pitch_ratio(x["pitch"]) for x in w5[i][1:3])
+        assert (a0 == a1) != (b0 == b1)
+    under = [(i, p, k) for i, p, s, k in w5 if on(p, "pitch") and on(s, "pitch")]
+    assert any(k[0] == "wav" and i % 2 == 0 for i, p, k in under)
+    assert [k[1] for i, p, k in under if k[0] == "batch"] == [2, 1, 0]  # a grow, a shrink and the row count alone (BATCHES), all shifted
+    assert {k[1] for _, _, _, k in w5 if k[0] == "op"} == {"time_stretch", "pitch"}
+    vals = [k[2] for _, _, _, k in w5 if k[:2] == ("set", "pitch")]
+    assert vals[-3] is not None and vals[-2] is None and vals[-1] == vals[-3]
+    assert ("refuse", "pitch", 12.5) in walks[5]
+    # walk 6: dither beside the rate, loudness and the limiter, each state at a step whose encoded fetches hold a PCM encoding
+    w6 = [(i, p, s, k) for i, p, s, k in steps(walks[6]) if {"pcm16", "pcm24"} & set(ow.encodings(i))]
+    assert len(w6) >= 12
+    assert any(on(s, "dither") and on(s, "rate") and not any(on(s, n) for n in ow.SETTINGS if n not in ("dither", "rate", "limiter")) for _, _, s, _ in w6)
+    assert any(on(s, "dither") and on(s, "loudness") and on(s, "limiter") for _, _, s, _ in w6)
+    assert any(on(s, "dither") and not on(s, "rate") for _, _, s, _ in w6)
+    assert any(i % 2 == 0 and k[:2] == ("set", "dither") and {p["dither"], s["dither"]} == set(ow.VALUES["dither"][:2]) for i, p, s, k in w6)
+    assert ("refuse", "dither", (4, 7)) in walks[6] and {k[1] for k in walks[6] if k[0] == "op"} == {"loudness_range", "encode_ex"}
+
+
 # ---- sensitivity: a fake engine with the real one's keys ------------------------------------------------------------------------------------
 KEYS = dict(
-    ed=("seq", "hz", "db", "keep", "fade", "Wo", "buf", "mp", "fl", "cp", "ds"),   # EdKey
-    cp=("seq", "hz", "fl", "cp", "Wo", "buf", "ds"),                               # CpKey
-    ds=("seq", "hz", "fl", "ds", "Wo", "buf"),                                     # DsKey
+    ed=("seq", "hz", "db", "keep", "fade", "Wo", "buf", "mp", "fl", "cp", "ds", "ps"),   # EdKey
+    cp=("seq", "hz", "fl", "cp", "Wo", "buf", "ds", "ps"),                               # CpKey
+    ds=("seq", "hz", "fl", "ds", "Wo", "buf", "ps"),                                     # DsKey
+    ps=("seq", "gen", "W", "B", "buf"),                                                  # PsKey
+    ps_rs=("a", "b"),                                                                    # ps_rs_: the table of the way back, per ratio
     st_win=("hz", "ms"), lm_win=("hz", "ms"),                                      # st_window, lm_window
     lo_n=("n", "base", "rows", "W"), cp_n=("n", "base", "rows", "W"), ds_n=("n", "base", "rows", "W"), fl_n=("base", "rows", "W"),
 )
 OMISSIONS = [(c, f) for c, fs in KEYS.items() for f in fs if f not in ("n", "base")]
 IMPLIED = ({(c, f) for c in ("ed", "cp", "ds") for f in ("hz", "Wo", "buf")}
-           | {(c, f) for c in ("lo_n", "cp_n", "ds_n") for f in ("rows", "W")})
+           | {(c, f) for c in ("lo_n", "cp_n", "ds_n") for f in ("rows", "W")}
+           | {("ps", f) for f in ("W", "B", "buf")})
 
 
 def _h(*parts):
@@ -147,16 +202,20 @@ class Fake:
 
     def __init__(self, omit=None):
         self.omit, self.s, self.seq = omit, ow.start(), 1
-        self.gen = dict(filters=0, compressor=0, deesser=0)
+        self.gen = dict(filters=0, compressor=0, deesser=0, pitch=0)  # (fl_gen_, cp_gen_, ds_gen_, ps_gen_: bumped by every set step)
         self.kept, self.cap, self.base = {}, {}, {}
         self.short_hits = self.wrong_hits = 0
 
     # -- geometry
-    def dims(self):
+    def native(self):
+        """(rows, W) at the model's rate: what the shift works on"""
         lens, durs, _ = ow.BATCHES[self.s["batch"]]
-        W = math.ceil(max(durs) / ow.SPEED * ow.NATIVE_HZ / 3072) * 3072
+        return len(lens), math.ceil(max(durs) / ow.SPEED * ow.NATIVE_HZ / 3072) * 3072
+
+    def dims(self):
+        B, W = self.native()
         hz = ow.rate_of(self.s)
-        return len(lens), hz, -(-W * hz // ow.NATIVE_HZ)
+        return B, hz, -(-W * hz // ow.NATIVE_HZ)
 
     def buf(self, name, need):
         if need > self.cap.get(name, 0):
@@ -200,13 +259,26 @@ class Fake:
 
     def chain_key(self):
         B, hz, Wo = self.dims()
-        return dict(seq=self.seq, hz=hz, Wo=Wo, fl=self.gen["filters"], cp=self.gen["compressor"], ds=self.gen["deesser"])
+        return dict(seq=self.seq, hz=hz, Wo=Wo, fl=self.gen["filters"], cp=self.gen["compressor"], ds=self.gen["deesser"], ps=self.gen["pitch"])
+
+    def shifted(self):
+        """ps_batch: the rows at the model's rate behind the shift, kept per batch and setting; the table of the way back is looked up
+        only when the rows are not kept"""
+        B, W = self.native()
+        a, b = ow.pitch_ratio(self.s["pitch"])
+        key = dict(seq=self.seq, gen=self.gen["pitch"], W=W, B=B, buf=self.buf("ps", B * (W + -(-W * a // b))))
+        had = self.kept.get("ps")
+        if had and had[0] == tuple(key[f] for f in KEYS["ps"] if ("ps", f) != self.omit):
+            return self.lookup("ps", key, None)
+        taps = self.lookup("ps_rs", dict(a=a, b=b), _h("taps", a, b))
+        return self.lookup("ps", key, _h("shifted", self.s["batch"], self.s["wav"], a, taps))
 
     def source(self):
-        """out_source: the rows behind resampler, chain, de-esser and compressor; the two reports' maxima are kept on the way"""
+        """out_source: the rows (with pitch on the shifted ones) behind resampler, chain, de-esser and compressor; the two reports' maxima
+        are kept on the way"""
         B, hz, Wo = self.dims()
         s, k = self.s, self.chain_key()
-        x = _h("src", s["batch"], s["wav"], hz)
+        x = _h("src", s["batch"], s["wav"], hz, self.shifted() if self.on("pitch") else None)
         spans = _h("spans", s["batch"], hz)
         if self.on("filters"):
             n = self.lookup("fl_n", dict(base=self.buf("fl", B * Wo), rows=B, W=Wo), (B, Wo))
@@ -255,7 +327,12 @@ class Fake:
         fade = (self.s["trim"] or (40.0, 20.0, 5.0))[2]
         return self.lookup("st_win", dict(hz=hz, ms=fade), _h("fade", hz, fade))
 
+    def dithered(self, enc, scope):
+        """what the store adds to an output's truth: nothing kept, and nothing at all unless the encoding is one dither applies to"""
+        return (self.s["dither"], scope) if self.on("dither") and enc in ("pcm16", "pcm24") else None
+
     def rows_out(self, enc):
+        enc = (enc, self.dithered(enc, "row"))
         B, hz, Wo = self.dims()
         spans = _h("spans", self.s["batch"], hz)
         if self.on("trim"):
@@ -295,12 +372,16 @@ class Fake:
             return self.rows_out(ow.encodings(i)[int(name[-1])])
         if name == "join_programme":
             return self.joined("programme")
-        if name == "join_row":
-            return self.joined("row")
+        if name == "join_row":  # (the one joined fetch taken in an encoding: the stream is the programme's)
+            return _h(self.joined("row"), self.dithered(ow.encodings(i)[0], "programme"))
         if name == "join_loudness":
             return self.joined("programme", measure_only=True)
+        if name == "join_loudness_range":
+            return _h("range", self.joined("programme", measure_only=True))
         if name == "loudness":
             return self.measure(self.source(), B, Wo, spans)
+        if name == "loudness_range":  # (batch_loudness_range: lo_batch over the same spans, then the report from its partial sums)
+            return _h("range", self.measure(self.source(), B, Wo, spans))
         if name == "limiter":
             if not (self.on("limiter") and self.on("loudness")):
                 return 0

@@ -153,6 +153,34 @@ def test_the_decision_margin_catches_a_search_over_half_the_candidates(hz):
                 assert caught >= 1, (names[r], a, b)
 
 
+@pytest.mark.parametrize("hz", pc.WIDE_RATES)
+def test_the_noise_row_rejects_a_search_blind_to_any_slice_of_the_candidates_or_to_either_end(hz):
+    """The wide rows are sensitive where the rows above are not (on a periodic row an equally good candidate lies a period away, inside
+    what a blind search still sees).  The search's workgroup takes the candidates T at a time: a search that never looks at one slice
+    [k T, (k + 1) T) of them, or at d = +D alone (the last trip's one candidate at 96 and 192 kHz), or at d = -D alone, picks another
+    offset on some frame of the noise row at 8/5 or at 4/7, and the decision margin the GPU tests apply rejects its table."""
+    T, C = pc.search_threads(hz)
+    x, n, names = pc.wide_rows(hz)
+    r = names.index("noise")
+    D = (C - 1) // 2
+    assert (T, C) == {24000: (448, 385), 96000: (1024, 1537), 192000: (1024, 3073)}[hz]
+    j = np.arange(C)
+    blind = {f"slice {k}": (j < k * T) | (j >= (k + 1) * T) for k in range(-(-C // T))}
+    blind["+D"], blind["-D"] = j != C - 1, j != 0
+    for a, b in ((8, 5), (4, 7)):
+        d, _ = pr.search(x[r], n[r], hz, a, b)
+        gap, margin = pr.decision_gaps(x[r], n[r], hz, a, b, d)
+        assert np.all(gap <= margin) and d[2 if a > b else 1] == (D if a > b else -D), (a, b, d[:4])
+    for name, allowed in blind.items():
+        rejected = False
+        for a, b in ((8, 5), (4, 7)):
+            if not rejected:
+                d, _ = pr.search(x[r], n[r], hz, a, b, allowed=allowed)
+                gap, margin = pr.decision_gaps(x[r], n[r], hz, a, b, d)
+                rejected = bool(np.any(gap > margin))
+        assert rejected, (hz, name)
+
+
 def test_recorded_envelope_figures_exist_and_the_reference_moves_the_pitch():
     for hz in pc.RATES:
         for s, (a, b) in pc.SHIFTS.items():
