@@ -887,6 +887,75 @@ int stn_deesser_coefs(const stn_deesser* c, int rate_hz, double k[2], float k32[
  * limits that do not depend on it; the string is the calling thread's until its next call */
 const char* stn_deesser_error(const stn_deesser* c, int rate_hz);
 
+/* ---- expander -----------------------------------------------------------------------------------------
+ * A feed-forward, log-domain downward expander / noise gate applied to every row of every fetch, on the GPU, at the output rate: it
+ * turns down what lies under a threshold (the vocoder's noise floor between words and around an utterance), by up to range_db, in
+ * front of the compressor's make-up gain, the loudness gain and G.711's finest segments.  A high ratio and no knee make it a gate.
+ * Off is the default: every fetch is then byte for byte the one without the feature, no expander launch runs and no scratch is owned.
+ * Order of the output stage: native or pitch-shifted rows -> resample (if a rate is set) -> filter chain -> EXPANDER -> de-esser ->
+ * compressor -> silence edges / pause cuts -> loudness measurement -> gain / limiter / true peak -> encoding store / join.  A DC
+ * blocker or rumble filter in the chain keeps an offset from holding it open.  Everything behind it sees the expanded signal: every
+ * fetch path and every report (stn_batch_deesser, _compressor, _loudness, _silence_edges, _pauses, _limiter, _true_peak,
+ * stn_batch_join_loudness).  One consequence: the silence trim's levels are then those of the gated signal, whose quiet frames lie up
+ * to range_db lower.  stn_batch_wav_device_ptr, stn_batch_fetch_latent, the batch's own waveform, the captured pipeline and the graph
+ * key are untouched: the expanded rows live in fetch scratch, and changing the setting drops or re-captures no graph.
+ * Each row is expanded on its own, from u = yL = 0 at its sample 0, over the row's whole width W_out (padding included): a row starts
+ * CLOSED, so a row that begins with speech gets an attack-long fade-in (the "from zero state" convention of the filter chain, the
+ * compressor and the de-esser).  Per sample, all values fp32:
+ *   level          xG = 20 log10(max(|x|, 1e-6));  d = T - xG   (how far UNDER the threshold)
+ *   gain computer  T = threshold_db, S = ratio - 1, K = knee_db, R = range_db:
+ *                  z = 0 when 2 d < -K;  z = S (d + K / 2)^2 / (2 K) when 2 |d| <= K (and K > 0);  z = S d otherwise;  z = min(z, R)
+ *   openness       o = R - z in [0, R];  t = o + Bh where z == 0 (fully open), t = o elsewhere
+ *   detector       u = max(t, u - delta): it opens at once, holds, then closes at a constant rate in dB;  y1 = min(u, R)
+ *   smoothing      yL = fma(kA, y1 - yL, yL)   (the attack)
+ *   output         y = x 10^((yL - R) / 20)    (attenuation R - yL, between 0 and R dB in the reference; see stn_batch_expander for the
+ *                                              few fp32 spacings of R by which the GPU's yL may exceed R)
+ * with kA = -expm1(-1000 / (attack_ms rate)), delta = R 1000 / (release_ms rate) dB per sample (release_ms: the time a fully open gate
+ * takes to close through the whole range), Hs = floor(hold_ms rate / 1000 + 0.5) samples and Bh = delta32 Hs, each formed in double
+ * and rounded to fp32.  After the last fully open sample y1 stays at R for Hs samples (exact arithmetic), then falls to 0 over
+ * release_ms; a zero crossing of the waveform is bridged by the detector.
+ * The reference of every numeric claim is exactly this in float64 on the same fp32-rounded T, S, K, R, kA, delta and Bh.  Identities:
+ *   the delivered fp32 row == stn_op_expander(the fp32 row delivered with the expander off), bit for bit;
+ *   a row's first n samples do not depend on W, the batch or the row's place in it;
+ *   a joined fetch == the host join of the per-row fetch, byte for byte, as without the expander (rows are gated one by one).
+ * Refused with STN_ERR_INVALID and a message that names the field: threshold_db outside [-90, -10], ratio outside [1, 20], knee_db
+ * outside [0, 24], range_db outside [1, 80], attack_ms outside [0.1, 300], hold_ms outside [0, 500], release_ms outside [10, 3000], a
+ * non-finite field.  The previous setting stays in force.  None of the limits depends on the rate.  DESIGN.md section 25 has the
+ * decomposition and the measurements. */
+typedef struct stn_expander { float threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms; } stn_expander;
+/* on = 0: off, c may then be NULL (the values last set stay readable) */
+int stn_set_expander(stn_handle* h, int on, const stn_expander* c);
+/* either may be NULL; *out: the values last set (before the first set, the speech default: -50 dB, 3:1, knee 6 dB, range 24 dB, 1 ms,
+ * 30 ms, 150 ms) */
+int stn_get_expander(const stn_handle* h, int* on, stn_expander* out);
+/* per row of the finished batch, over the row's valid samples (its reported duration at the output rate): the minimum of R - yL, the
+ * least attenuation in dB (well above 0: the threshold sits above the speech), and the count of samples with yL <= R / 2.  Either may
+ * be NULL; both are 0 for every row while the expander is off.  The minimum is reported as the GPU formed it, not clamped: a chunk's
+ * start value of yL comes from a scan (E s + c with c rounded to fp32, the sum rounded once more) and may leave
+ * yL an fp32 spacing of R above R on a fully open stretch, so a fully open row can report a slightly negative minimum (observed: one
+ * spacing, -3.8e-6 dB at R = 60, a gain of 1 + 4.4e-7; the tests allow four) */
+int stn_batch_expander(stn_handle* h, float* min_attenuation_db, int64_t* closed_samples);
+/* op-level: rows x W fp32 (host) at hz through the expander c -> y [rows][W] (host).  1 <= rows <= 65535. */
+int stn_op_expander(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, float* y);
+/* The same with its scratch laid open (the kernel tests).  Five launches on chunks of 32 samples (Ks = (W + 31) / 32 per row): u of
+ * every chunk from zero (s1_end), the (max, +) scan of those in double (s1_start: u at every chunk's start), yL of every chunk from
+ * zero on its true u (s2_end), the linear scan in double (s2_start), and the write pass from both start values: y, and open_db
+ * [rows][W] = yL.  Each of open_db, s1_end, s1_start, s2_end, s2_start ([rows][Ks] each) may be NULL.  The device's scratch and
+ * open_db are filled with the quiet NaN 0x7FC00000 before the first launch, and x and y lie with 64 poisoned floats in front of and
+ * behind them: *guard_ok = 1 when all of those came back untouched.  x_misalign, in_place, form: as stn_op_compressor_ex. */
+int stn_op_expander_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, int x_misalign, int in_place, float* y,
+                       float* open_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form,
+                       size_t form_cap);
+/* host only, no device needed: kA, delta and Bh at rate_hz, and Hs.  k: each in double (Bh from the fp32 delta); k32: the same rounded
+ * to fp32, what the GPU computes with.  Each may be NULL.  Refuses (STN_ERR_INVALID) what stn_set_expander refuses, and a rate outside
+ * [8000, 192000]. */
+int stn_expander_coefs(const stn_expander* c, int rate_hz, double k[3], float k32[3], int64_t* hold_samples);
+/* host only: the static curve: out_db[i] = in_db[i] - z(in_db[i]), in double on the fp32 T, S, K and R */
+int stn_expander_curve(const stn_expander* c, int n, const double* in_db, double* out_db);
+/* host only: why stn_set_expander would refuse c ("" when it would not), as stn_compressor_error; rate_hz > 0 is checked as well, 0 is
+ * "no rate"; the string is the calling thread's until its next call */
+const char* stn_expander_error(const stn_expander* c, int rate_hz);
+
 /* ---- measurement: HIP-event timing of kernel families on the engine's own stream ------------------- */
 int stn_profile_enable(stn_handle* h, int on);
 int stn_profile_reset(stn_handle* h);

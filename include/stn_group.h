@@ -66,6 +66,8 @@ int stn_group_set_pitch(stn_group* g, float semitones);
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f);
 /* compressor of every rank (stn_set_compressor): rows are compressed on their own, so the gathered rows are the single engine's */
 int stn_group_set_compressor(stn_group* g, int on, const stn_compressor* c);
+/* expander of every rank (stn_set_expander): rows are expanded on their own, so the gathered rows are the single engine's */
+int stn_group_set_expander(stn_group* g, int on, const stn_expander* c);
 /* de-esser of every rank (stn_set_deesser): rows are de-essed on their own, so the gathered rows are the single engine's */
 int stn_group_set_deesser(stn_group* g, int on, const stn_deesser* c);
 /* the pause limit (stn_set_pause_limit) works inside trimmed rows, and the group does not trim: on != 0 is refused with

@@ -294,6 +294,99 @@ def compressor_curve(compressor, in_db):
     return out
 
 
+EXPANDER_FIELDS = ("threshold_db", "ratio", "knee_db", "range_db", "attack_ms", "hold_ms", "release_ms")
+# the documented defaults: "speech" -50 dB, 3:1, a 6 dB knee, at most 24 dB, 1 ms attack, 30 ms hold, 150 ms release; "gate" -45 dB,
+# 20:1, no knee, 60 dB, 0.5 ms, 50 ms, 100 ms
+EXPANDER_SPEECH = (-50.0, 3.0, 6.0, 24.0, 1.0, 30.0, 150.0)
+EXPANDER_GATE = (-45.0, 20.0, 0.0, 60.0, 0.5, 50.0, 100.0)
+EXPANDER_PRESETS = {"speech": EXPANDER_SPEECH, "gate": EXPANDER_GATE}
+
+
+class StnExpander(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in EXPANDER_FIELDS]
+
+
+def parse_expander_spec(spec, preset=None):
+    """A command-line expander "THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]" (what is left out comes from the
+    preset, "speech" unless given) -> the 7-tuple of floats.  ValueError naming what is wrong."""
+    parts = str(spec).split(":")
+    if not 2 <= len(parts) <= 7:
+        raise ValueError(f"expander {spec!r}: expected THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]")
+    try:
+        nums = [float(v) for v in parts]
+    except ValueError:
+        raise ValueError(f"expander {spec!r}: THRESHOLD, RATIO, KNEE, RANGE_DB, ATTACK_MS, HOLD_MS and RELEASE_MS must be numbers") from None
+    return tuple(nums) + EXPANDER_PRESETS[preset or "speech"][len(nums):]
+
+
+def expander_args(expander, preset=None):
+    """An expander argument -> the 7-tuple of floats (threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms), or None
+    for off (None or False).  True is the preset ("speech" unless given: -50 dB, 3:1, knee 6 dB, range 24 dB, attack 1 ms, hold 30 ms,
+    release 150 ms; "gate": -45 dB, 20:1, knee 0, range 60 dB, 0.5 ms, 50 ms, 100 ms); a dict names fields and takes the others from
+    the preset; a 7-tuple gives all seven; a "THRESHOLD:RATIO[:...]" string is the command line's spelling.  A preset alone stands for
+    True.  ValueError naming the field for a malformed value or an unknown field or preset; the numeric limits are the C ABI's
+    (expander_error, Engine.set_expander)."""
+    if preset is not None:
+        if preset not in EXPANDER_PRESETS:
+            raise ValueError(f"expander_preset {preset!r}: must be one of {', '.join(EXPANDER_PRESETS)}")
+        if expander is None or expander is False:
+            expander = True
+    if expander is None or expander is False:
+        return None
+    base = EXPANDER_PRESETS[preset or "speech"]
+    if expander is True:
+        return base
+    if isinstance(expander, str):
+        return parse_expander_spec(expander, preset)
+    if isinstance(expander, dict):
+        unknown = set(expander) - set(EXPANDER_FIELDS)
+        if unknown:
+            raise ValueError(f"expander: unknown field {sorted(unknown)[0]!r} ({', '.join(EXPANDER_FIELDS)})")
+        vals = [expander.get(n, d) for n, d in zip(EXPANDER_FIELDS, base)]
+    elif isinstance(expander, (tuple, list)) and len(expander) == 7:
+        vals = list(expander)
+    else:
+        raise ValueError(f"expander: True, a dict of {', '.join(EXPANDER_FIELDS)}, or a 7-tuple of them, not {expander!r}")
+    for name, v in zip(EXPANDER_FIELDS, vals):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"expander: {name} must be a finite number, not {v!r}")
+    return tuple(float(v) for v in vals)
+
+
+def _expander_struct(expander):
+    c = expander_args(expander)
+    if c is None:
+        raise ValueError("expander: a setting is needed here, not off")
+    return StnExpander(*c)
+
+
+def expander_error(expander, rate_hz=0):
+    """Why Engine.set_expander would refuse the setting (host only): "" when it would not; the message names the field."""
+    return load().stn_expander_error(ctypes.byref(_expander_struct(expander)), int(rate_hz)).decode()
+
+
+def expander_coefs(expander, rate_hz):
+    """(k float64 [3]: kA = -expm1(-1000 / (attack_ms rate)), delta = range_db 1000 / (release_ms rate), Bh = delta32 Hs; k32 float32
+    [3]: what the GPU computes with; Hs: the hold in samples) at rate_hz (host only)."""
+    c = _expander_struct(expander)
+    k, k32, hs = np.zeros(3, np.float64), np.zeros(3, np.float32), ctypes.c_int64()
+    rc = load().stn_expander_coefs(ctypes.byref(c), int(rate_hz), k, k32, ctypes.byref(hs))
+    if rc < 0:
+        raise StnError(rc, expander_error(expander, rate_hz) or "stn_expander_coefs failed")
+    return k, k32, int(hs.value)
+
+
+def expander_curve(expander, in_db):
+    """The static curve: output level in dB at the input levels in_db (host only, float64)."""
+    c = _expander_struct(expander)
+    x = np.ascontiguousarray(np.atleast_1d(in_db), np.float64)
+    out = np.zeros(x.shape, np.float64)
+    rc = load().stn_expander_curve(ctypes.byref(c), x.size, x, out)
+    if rc < 0:
+        raise StnError(rc, expander_error(expander) or "stn_expander_curve failed")
+    return out
+
+
 DEESSER_FIELDS = ("freq_hz", "threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "range_db", "mode")
 DEESSER_MODES = ("split", "wide")  # STN_DEESS_SPLIT, STN_DEESS_WIDE
 # the documented "speech" default: 5500 Hz, -30 dB, 4:1, a 6 dB knee, 1 ms attack, 40 ms release, at most 12 dB, on the band alone
@@ -664,6 +757,17 @@ def load():
     L.stn_compressor_error.restype = ctypes.c_char_p
     L.stn_compressor_coefs.argtypes = [cpp, ci, _f64p, _f32p]
     L.stn_compressor_curve.argtypes = [cpp, ci, _f64p, _f64p]
+    xpp = ctypes.POINTER(StnExpander)
+    L.stn_set_expander.argtypes = [vp, ci, xpp]
+    L.stn_get_expander.argtypes = [vp, ctypes.POINTER(ci), xpp]
+    L.stn_group_set_expander.argtypes = [vp, ci, xpp]
+    L.stn_batch_expander.argtypes = [vp, vp, vp]
+    L.stn_op_expander.argtypes = [vp, ci, ci, ci, _f32p, xpp, _f32p]
+    L.stn_op_expander_ex.argtypes = [vp, ci, ci, ci, _f32p, xpp, ci, ci, _f32p, vp, vp, vp, vp, vp, ctypes.POINTER(ci), ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_expander_error.argtypes = [xpp, ci]
+    L.stn_expander_error.restype = ctypes.c_char_p
+    L.stn_expander_coefs.argtypes = [xpp, ci, _f64p, _f32p, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_expander_curve.argtypes = [xpp, ci, _f64p, _f64p]
     dsp = ctypes.POINTER(StnDeesser)
     L.stn_set_deesser.argtypes = [vp, ci, dsp]
     L.stn_get_deesser.argtypes = [vp, ctypes.POINTER(ci), dsp]
@@ -817,6 +921,11 @@ class Group:
         """Compressor of every rank (Engine.set_compressor): the gathered rows are then the single engine's compressed rows."""
         c = compressor_args(compressor)
         self._ck(self._lib.stn_group_set_compressor(self._g, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
+
+    def set_expander(self, expander=None):
+        """Expander of every rank (Engine.set_expander): the gathered rows are then the single engine's expanded rows."""
+        c = expander_args(expander)
+        self._ck(self._lib.stn_group_set_expander(self._g, int(c is not None), ctypes.byref(StnExpander(*c)) if c else None))
 
     def set_deesser(self, deesser=None):
         """De-esser of every rank (Engine.set_deesser): the gathered rows are then the single engine's de-essed rows."""
@@ -1506,6 +1615,56 @@ class Engine:
         self._ck(self._lib.stn_op_compressor_ex(self._h, int(hz), rows, W, x, ctypes.byref(_compressor_struct(compressor)), int(x_misalign),
                                                 int(in_place), o["y"], o["gr_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
                                                 o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
+        o["guard_ok"] = bool(ok.value)
+        o["form"] = form.value.decode()
+        return o
+
+    def set_expander(self, expander=None):
+        """Turn down what lies under a threshold (the noise floor between words) in every row of every fetch on the GPU, at the output
+        rate, behind the filter chain and in front of the de-esser, the compressor and everything else: None or False = off (the
+        default); True = the "speech" default; a dict or 7-tuple as expander_args takes them, e.g. {"threshold_db": -45}.  StnError
+        naming the field for a value outside the limits (include/stn.h, "expander")."""
+        c = expander_args(expander)
+        self._ck(self._lib.stn_set_expander(self._h, int(c is not None), ctypes.byref(StnExpander(*c)) if c else None))
+
+    def get_expander(self):
+        """The setting in force: the 7-tuple (threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms), or None when off."""
+        on, c = ctypes.c_int(), StnExpander()
+        self._ck(self._lib.stn_get_expander(self._h, ctypes.byref(on), ctypes.byref(c)))
+        return tuple(getattr(c, n) for n in EXPANDER_FIELDS) if on.value else None
+
+    expander = property(get_expander)
+
+    def batch_expander(self):
+        """Per row of the finished batch, over the row's valid samples: (min_attenuation_db float32 [B], the least attenuation the
+        expander applied; closed_samples int64 [B], the samples at least half closed).  Zeros while it is off."""
+        B = self.batch_dims()[0]
+        att, closed = np.zeros(B, np.float32), np.zeros(B, np.int64)
+        self._ck(self._lib.stn_batch_expander(self._h, att.ctypes.data, closed.ctypes.data))
+        return att, closed
+
+    def op_expander(self, x, hz, expander):
+        """rows x W fp32 at hz through the expander on the GPU -> y [rows, W] float32, every row from zero state (closed)."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        y = np.empty_like(x)
+        self._ck(self._lib.stn_op_expander(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_expander_struct(expander)), y))
+        return y
+
+    def op_expander_ex(self, x, hz, expander, x_misalign=0, in_place=0):
+        """op_expander with its scratch laid open -> dict: y, open_db (yL) [rows, W]; s1_end, s1_start, s2_end, s2_start [rows, Ks] (per
+        chunk of 32 samples: u at its end from zero, u at its start after the scan, yL at its end from zero, yL at its start; the
+        scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y came back whole); form
+        ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y over x on the device."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        Ks = (W + 31) // 32
+        o = dict(y=np.empty_like(x), open_db=np.empty_like(x))
+        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
+            o[k] = np.empty((rows, Ks), np.float32)
+        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
+        self._ck(self._lib.stn_op_expander_ex(self._h, int(hz), rows, W, x, ctypes.byref(_expander_struct(expander)), int(x_misalign),
+                                              int(in_place), o["y"], o["open_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
+                                              o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
         o["guard_ok"] = bool(ok.value)
         o["form"] = form.value.decode()
         return o

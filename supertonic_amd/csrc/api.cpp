@@ -608,6 +608,58 @@ int stn_deesser_coefs(const stn_deesser* c, int rate_hz, double k[2], float k32[
     }
     return STN_OK;
 }
+int stn_set_expander(stn_handle* h, int on, const stn_expander* c) { STN_TRY(h, { h->eng->set_expander(on != 0, c); }) }
+int stn_get_expander(const stn_handle* h, int* on, stn_expander* out) {
+    if (!h) return STN_ERR_INVALID;
+    if (on) *on = h->eng->expander_on() ? 1 : 0;
+    if (out) *out = h->eng->expander();
+    return STN_OK;
+}
+int stn_batch_expander(stn_handle* h, float* min_attenuation_db, int64_t* closed_samples) {
+    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_expander(min_attenuation_db, closed_samples); })
+}
+int stn_op_expander(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_expander: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 h->eng->op_expander(hz, rows, W, x, *c, y, nullptr); })
+}
+int stn_op_expander_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, int x_misalign, int in_place, float* y,
+                       float* open_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_expander_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_expander_ex: x_misalign and in_place must be 0 or 1");
+                 stn::Engine::XpProbe p;
+                 p.x_misalign = x_misalign; p.in_place = in_place; p.open = open_db;
+                 p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
+                 h->eng->op_expander(hz, rows, W, x, *c, y, &p);
+                 if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0;
+                 if (form && form_cap) std::snprintf(form, form_cap, "%s", p.form); })
+}
+const char* stn_expander_error(const stn_expander* c, int rate_hz) {
+    static thread_local std::string why;
+    why = stn::expander_check(c);
+    if (why.empty() && rate_hz < 0) why = "expander: rate_hz must not be negative";
+    if (why.empty() && rate_hz > 0) why = stn::rate_check("expander", rate_hz);
+    return why.c_str();
+}
+int stn_expander_coefs(const stn_expander* c, int rate_hz, double k[3], float k32[3], int64_t* hold_samples) {
+    if (rate_hz <= 0 || *stn_expander_error(c, rate_hz)) return STN_ERR_INVALID;
+    stn::ExpTable t;
+    stn::expander_table(rate_hz, *c, t);
+    // each in double from the setting's fp32 fields; Bh from the fp32 delta the GPU subtracts, as the table forms it
+    const double d[3] = {stn::compressor_k(c->attack_ms, rate_hz), (double)c->range_db * 1000.0 / ((double)c->release_ms * (double)rate_hz),
+                         (double)t.coef.delta * (double)t.hold};
+    const float f[3] = {t.coef.kA, t.coef.delta, t.coef.Bh};
+    for (int i = 0; i < 3; ++i) {
+        if (k) k[i] = d[i];
+        if (k32) k32[i] = f[i];
+    }
+    if (hold_samples) *hold_samples = t.hold;
+    return STN_OK;
+}
+int stn_expander_curve(const stn_expander* c, int n, const double* in_db, double* out_db) {
+    if (n < 0 || (n > 0 && (!in_db || !out_db)) || !stn::expander_check(c).empty()) return STN_ERR_INVALID;
+    for (int i = 0; i < n; ++i) out_db[i] = stn::expander_curve(*c, in_db[i]);
+    return STN_OK;
+}
 int stn_set_dither(stn_handle* h, int mode, uint64_t seed) { STN_TRY(h, { h->eng->set_dither(mode, seed); }) }
 int stn_get_dither(const stn_handle* h, uint64_t* seed) {
     if (!h) return STN_ERR_INVALID;

@@ -21,6 +21,10 @@
 // behind the filters and in front of the compressor: the band above FREQ turned down by up to RANGE_DB while its level is over THRESHOLD;
 // ratio 4, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, MODE split (the band alone; wide: the whole signal) when left out),
 // --deesser-preset speech (5500 Hz, -30 dB and those),
+// --expander THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]] (every utterance through the downward expander / noise
+// gate on the GPU, behind the filters and in front of the de-esser: what lies under THRESHOLD turned down by up to RANGE_DB; knee 6 dB,
+// range 24 dB, attack 1 ms, hold 30 ms, release 150 ms when left out, or the values of the preset given beside it),
+// --expander-preset {speech,gate} (-50 dB, 3:1 and those; -45 dB, 20:1, no knee, 60 dB, 0.5 ms, 50 ms, 100 ms),
 // --pitch SEMITONES (every utterance shifted by that many semitones, -12 to 12, on the GPU without a change of length, in front of
 // everything else; absent or 0: off),
 // --loudness-report (after each saved file one line "Loudness: integrated .. LUFS, range .. LU, max momentary .. LUFS, max short-term ..
@@ -71,6 +75,8 @@ int main(int argc, char* argv[]) {
                                      "pleasant that I stopped for a long time just to listen."};
     std::vector<std::string> lang = {"en"};
     bool batch = false, peak_mode_given = false, loudness_report = false;
+    std::string xp_spec, xp_preset = "speech";  // --expander and --expander-preset as given so far
+    bool xp_spelled = false;
     EngineOptions opts;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -135,6 +141,14 @@ int main(int argc, char* argv[]) {
             const std::string why = a == "--deesser" ? parseDeesserSpec(argv[++i], opts.deesser) : deesserPreset(argv[++i], opts.deesser);
             if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
             opts.deesser_on = true;
+        }
+        else if ((a == "--expander" || a == "--expander-preset") && more) {  // the downward expander / noise gate every utterance goes through on the GPU
+            // (a spelling takes what it leaves out from the preset given, "speech" without one, whichever of the two comes first)
+            if (a == "--expander") { xp_spec = argv[++i]; xp_spelled = true; }
+            else xp_preset = argv[++i];
+            const std::string why = xp_spelled ? parseExpanderSpec(xp_spec, opts.expander, xp_preset) : expanderPreset(xp_preset, opts.expander);
+            if (!why.empty()) { std::cerr << "Error: --" << why << "\n"; return 1; }
+            opts.expander_on = true;
         }
         else if (a == "--pitch" && more) {  // every utterance shifted by this many semitones on the GPU (length unchanged); 0: off
             const std::string v = argv[++i];

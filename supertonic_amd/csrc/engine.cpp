@@ -182,6 +182,7 @@ Engine::~Engine() {
     if (seed_dev_) (void)hipFree(seed_dev_);
     rs_release();
     fl_release();
+    xp_release();
     ds_release();
     cp_release();
     lo_release();  // (the fetch scratch, DevBuf members, goes with the members)

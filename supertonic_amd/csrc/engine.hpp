@@ -109,6 +109,12 @@ void compressor_table(int hz, const stn_compressor& c, CompTable& t);
 std::string deesser_check(const stn_deesser* c, int rate_hz);
 void deesser_band(const stn_deesser& c, stn_filter f[2]);
 void deesser_table(int hz, const stn_deesser& c, DeessTable& t);
+// The expander's host arithmetic (engine_expander.cpp).  expander_check: why c is refused, naming the field, or "" (no limit depends on
+// the rate); expander_curve: the static curve in double on the fp32-rounded T, S, K and R; expander_table: coefficients (kA, delta, Bh
+// and the hold in samples) and scan tables at hz (no device copy), throws what the check refuses
+std::string expander_check(const stn_expander* c);
+double expander_curve(const stn_expander& c, double in_db);
+void expander_table(int hz, const stn_expander& c, ExpTable& t);
 
 class Engine;
 // One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
@@ -541,6 +547,23 @@ class Engine {
     // rows x W fp32 (host) at hz through the de-esser c -> y (host)
     void op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe);
 
+    // ---- expander (engine_expander.cpp; include/stn.h "expander"): off is the default (every fetch path is then
+    // exactly the one without it).  On, out_source() delivers the rows at the output rate expanded in place in the fetch scratch, behind
+    // the filter chain and in front of the de-esser (kernels_expander.hip), and everything behind it runs on those.
+    void set_expander(bool on, const stn_expander* c);
+    bool expander_on() const { return xp_on_; }
+    const stn_expander& expander() const { return xp_set_; }
+    void batch_expander(float* min_attenuation_db, int64_t* closed_samples);
+    // the op-level probe: open [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
+    struct XpProbe {
+        int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
+        float *open = nullptr, *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
+        bool guard_ok = false;   // out
+        const char* form = "";   // out
+    };
+    // rows x W fp32 (host) at hz through the expander c -> y (host)
+    void op_expander(int hz, int rows, int W, const float* x, const stn_expander& c, float* y, XpProbe* probe);
+
     // ---- profiling (hipEvent pairs around launches of one kernel family, on this stream) ----------------
     void profile_enable(bool on) { if (on != prof_on_) profile_reset(); prof_on_ = on; }
     void launch_log_enable(bool on);   // record (family, kernel) of every launch while profiling is on (this thread's engine calls)
@@ -886,7 +909,8 @@ class Engine {
         uint64_t seq = 0; int hz = 0; uint64_t fl = 0, cp = 0; int64_t Wo = 0; const void* buf = nullptr;
         uint64_t ds = 0;  // ds_gen_ of the de-esser setting in front of it
         uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
-        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds && ps == o.ps; }
+        uint64_t xp = 0;  // xp_gen_ of the expander setting in front of it
+        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds && ps == o.ps && xp == o.xp; }
     };
     CpKey cp_key_; bool cp_valid_ = false;
     void cp_prepare(CompTable& t, int hz, const stn_compressor& c);
@@ -910,7 +934,8 @@ class Engine {
     struct DsKey {
         uint64_t seq = 0; int hz = 0; uint64_t fl = 0, ds = 0; int64_t Wo = 0; const void* buf = nullptr;
         uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
-        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf && ps == o.ps; }
+        uint64_t xp = 0;  // xp_gen_ of the expander setting in front of it
+        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf && ps == o.ps && xp == o.xp; }
     };
     DsKey ds_key_; bool ds_valid_ = false;
     void ds_prepare(DeessTable& t, int hz, const stn_deesser& c);
@@ -919,9 +944,33 @@ class Engine {
     // sequence leaves it
     void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
     DsScratch ds_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) de-essed into y (may be x)
+    // ---- expander (engine_expander.cpp)
+    bool xp_on_ = false;
+    stn_expander xp_set_{-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f};  // the setting in force (the "speech" default until one is set)
+    uint64_t xp_gen_ = 0;              // bumped by every change of the setting: part of EdKey, DsKey and CpKey (all see the expanded rows)
+    ExpTable xp_, op_xp_;              // the tables at the output rate, and of op_expander (device copies owned here)
+    DevBuf xp_buf_;                    // fetch-time scratch of the six launches: exists only once a fetch ran with the expander on
+    // per chunk u and yL (end values, then start values), the minimum of R - yL and the count of yL <= R / 2; per row those two and
+    // the valid length
+    struct XpScratch { float *s1, *s2, *cmin, *rmin; int32_t* ccnt; int64_t *rcnt, *n; size_t bytes; };
+    static XpScratch xp_layout(char* base, int64_t rows, int64_t W);
+    std::vector<int64_t> xp_n_; const int64_t* xp_n_ptr_ = nullptr;  // the lengths xp_buf_ holds
+    // what the row results in xp_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
+    struct XpKey {
+        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, xp = 0; int64_t Wo = 0; const void* buf = nullptr;
+        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
+        bool operator==(const XpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && xp == o.xp && Wo == o.Wo && buf == o.buf && ps == o.ps; }
+    };
+    XpKey xp_key_; bool xp_valid_ = false;
+    void xp_prepare(ExpTable& t, int hz, const stn_expander& c);
+    void xp_release();
+    // the six launches on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read out where the
+    // sequence leaves it
+    void xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const XpScratch& sc, float* y, float* open, XpProbe* probe);
+    XpScratch xp_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) expanded into y (may be x)
     // out_source() returns the fp32 fetch scratch (row stride Wo), not the rows the stage starts from (wav_rows(): b.wav, or with pitch on
     // the shifted rows in the pitch scratch, row stride W like b.wav: pitch alone needs no second copy)
-    bool out_in_scratch() const { return resample_on() || filter_on() || deesser_on() || compressor_on(); }
+    bool out_in_scratch() const { return resample_on() || filter_on() || expander_on() || deesser_on() || compressor_on(); }
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
@@ -947,9 +996,10 @@ class Engine {
         uint64_t cp = 0;  // cp_gen_ of the compressor setting they went through
         uint64_t ds = 0;  // ds_gen_ of the de-esser setting they went through
         uint64_t ps = 0;  // ps_gen_ of the pitch they were shifted by
+        uint64_t xp = 0;  // xp_gen_ of the expander setting they went through
         bool operator==(const EdKey& o) const {
             return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp && ds == o.ds &&
-                   ps == o.ps;
+                   ps == o.ps && xp == o.xp;
         }
     };
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;

@@ -446,9 +446,11 @@ const float* Engine::out_source(int64_t Wo) {
     // section 18: the chain runs on the rows at the output rate, in place behind the resampler, out of b.wav (left as it is) otherwise
     if (filter_on()) fl_batch(resample_on() ? d : wav, Wo, d);
     // section 21: the de-esser behind the chain, in place in the scratch, out of b.wav (left as it is) when nothing ran in front of it
-    if (deesser_on()) ds_batch(resample_on() || filter_on() ? d : wav, Wo, d);
+    // section 25: the expander behind the chain and in front of the de-esser, likewise
+    if (expander_on()) xp_batch(resample_on() || filter_on() ? d : wav, Wo, d);
+    if (deesser_on()) ds_batch(resample_on() || filter_on() || expander_on() ? d : wav, Wo, d);
     // section 20: the compressor behind those, likewise
-    if (compressor_on()) cp_batch(resample_on() || filter_on() || deesser_on() ? d : wav, Wo, d);
+    if (compressor_on()) cp_batch(resample_on() || filter_on() || expander_on() || deesser_on() ? d : wav, Wo, d);
     return d;
 }
 
@@ -494,8 +496,8 @@ void Engine::enqueue_output(const OutRows& o) {
         const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
-    } else if (filter_on() || deesser_on() || compressor_on()) {
-        // sections 18, 20 and 21: the filtered, de-essed and / or compressed rows are in the fetch scratch; an fp32 fetch that was handed that scratch as its destination is done
+    } else if (filter_on() || expander_on() || deesser_on() || compressor_on()) {
+        // sections 18, 20, 21 and 25: the filtered, expanded, de-essed and / or compressed rows are in the fetch scratch; an fp32 fetch that was handed that scratch as its destination is done
         const float* src = out_source(Wo);
         if (src != o.dst) {
             StageSpan span(*this, "out", "store_rows", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));

@@ -165,7 +165,7 @@ Engine::CpScratch Engine::cp_batch(const float* x, int64_t Wo, float* y) {
         sync();  // (the upload reads cp_n_, which the next batch's lengths replace; once per finished batch, as fl_batch)
     }
     cp_enqueue(cp_, x, b.B, Wo, sc, y, nullptr, nullptr);
-    cp_key_ = CpKey{ed_seq_, hz, fl_gen_, cp_gen_, Wo, cp_buf_.get(), ds_gen_, ps_gen_};
+    cp_key_ = CpKey{ed_seq_, hz, fl_gen_, cp_gen_, Wo, cp_buf_.get(), ds_gen_, ps_gen_, xp_gen_};
     cp_valid_ = true;
     return sc;
 }
@@ -178,7 +178,7 @@ void Engine::batch_compressor(float* max_reduction_db) {
         return;
     }
     // the row maxima a fetch of this batch under this rate, chain and setting left in cp_buf_ are the report; otherwise the sequence runs
-    const CpKey key{ed_seq_, output_rate(), fl_gen_, cp_gen_, Wo, cp_buf_.get(), ds_gen_, ps_gen_};
+    const CpKey key{ed_seq_, output_rate(), fl_gen_, cp_gen_, Wo, cp_buf_.get(), ds_gen_, ps_gen_, xp_gen_};
     if (!(cp_valid_ && key == cp_key_)) (void)out_source(Wo);
     const CpScratch sc = cp_layout(cp_buf_.reserve(*this, cp_layout(nullptr, bt_.B, Wo).bytes), bt_.B, Wo);
     STN_HIP(hipMemcpyAsync(max_reduction_db, sc.rmax, (size_t)bt_.B * 4, hipMemcpyDeviceToHost, s_));

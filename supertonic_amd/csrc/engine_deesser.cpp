@@ -194,7 +194,7 @@ Engine::DsScratch Engine::ds_batch(const float* x, int64_t Wo, float* y) {
         sync();  // (the uploads read ds_n_, which the next batch's lengths replace, and nw, this frame's; once per finished batch, as cp_batch)
     }
     ds_enqueue(ds_, x, b.B, Wo, sc, y, nullptr, nullptr, nullptr);
-    ds_key_ = DsKey{ed_seq_, hz, fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_};
+    ds_key_ = DsKey{ed_seq_, hz, fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_, xp_gen_};
     ds_valid_ = true;
     return sc;
 }
@@ -207,7 +207,7 @@ void Engine::batch_deesser(float* max_reduction_db) {
         return;
     }
     // the row maxima a fetch of this batch under this rate, chain and setting left in ds_buf_ are the report; otherwise the sequence runs
-    const DsKey key{ed_seq_, output_rate(), fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_};
+    const DsKey key{ed_seq_, output_rate(), fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_, xp_gen_};
     if (!(ds_valid_ && key == ds_key_)) (void)out_source(Wo);
     const DsScratch sc = ds_layout(ds_buf_.reserve(*this, ds_layout(nullptr, bt_.B, Wo).bytes), bt_.B, Wo);
     STN_HIP(hipMemcpyAsync(max_reduction_db, sc.rmax, (size_t)bt_.B * 4, hipMemcpyDeviceToHost, s_));

@@ -257,6 +257,12 @@ int stn_group_set_deesser(stn_group* g, int on, const stn_deesser* c) {
         const S* p = static_cast<const S*>(a);
         return stn_set_deesser(h, p->on, p->c); }, &v, 0);
 }
+int stn_group_set_expander(stn_group* g, int on, const stn_expander* c) {
+    struct S { int on; const stn_expander* c; } v{on, c};
+    return for_all(g, "stn_set_expander", [](stn_handle* h, const void* a, uint64_t) {
+        const S* p = static_cast<const S*>(a);
+        return stn_set_expander(h, p->on, p->c); }, &v, 0);
+}
 int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms) {
     if (!g) return STN_ERR_INVALID;
     (void)max_pause_ms;

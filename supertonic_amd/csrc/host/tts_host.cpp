@@ -310,6 +310,31 @@ std::string parseCompressorSpec(const std::string& spec, stn_compressor& c) {
     return "";
 }
 
+std::string expanderPreset(const std::string& name, stn_expander& c) {
+    if (name == "speech") c = stn_expander{-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f};
+    else if (name == "gate") c = stn_expander{-45.0f, 20.0f, 0.0f, 60.0f, 0.5f, 50.0f, 100.0f};
+    else return "expander-preset '" + name + "': speech or gate";
+    return "";
+}
+
+std::string parseExpanderSpec(const std::string& spec, stn_expander& c, const std::string& preset) {
+    std::vector<std::string> parts;
+    size_t a = 0, p;
+    while ((p = spec.find(':', a)) != std::string::npos) { parts.push_back(spec.substr(a, p - a)); a = p + 1; }
+    parts.push_back(spec.substr(a));
+    const std::string who = "expander '" + spec + "': ";
+    if (parts.size() < 2 || parts.size() > 7) return who + "expected THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]";
+    const std::string bad = expanderPreset(preset, c);  // what the fields left out take
+    if (!bad.empty()) return bad;
+    float* dst[7] = {&c.threshold_db, &c.ratio, &c.knee_db, &c.range_db, &c.attack_ms, &c.hold_ms, &c.release_ms};
+    for (size_t i = 0; i < parts.size(); ++i) {
+        char* end = nullptr;
+        *dst[i] = std::strtof(parts[i].c_str(), &end);
+        if (parts[i].empty() || *end) return who + "THRESHOLD, RATIO, KNEE, RANGE_DB, ATTACK_MS, HOLD_MS and RELEASE_MS must be numbers";
+    }
+    return "";
+}
+
 std::string deesserPreset(const std::string& name, stn_deesser& c) {
     if (name != "speech") return "deesser-preset '" + name + "': speech";
     c = stn_deesser{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};
@@ -402,6 +427,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         if (opts.output_rate) applied("output rate", grp ? stn_group_set_output_rate(grp, opts.output_rate) : stn_set_output_rate(h, opts.output_rate));
         // (after the rate: a chain is checked against the output rate in force)
         if (nf) applied("filters", grp ? stn_group_set_filters(grp, nf, opts.filters.data()) : stn_set_filters(h, nf, opts.filters.data()));
+        if (opts.expander_on) applied("expander", grp ? stn_group_set_expander(grp, 1, &opts.expander) : stn_set_expander(h, 1, &opts.expander));
         // (after the rate as well: freq_hz is checked against the output rate in force)
         if (opts.deesser_on) applied("deesser", grp ? stn_group_set_deesser(grp, 1, &opts.deesser) : stn_set_deesser(h, 1, &opts.deesser));
         if (opts.compressor_on) applied("compressor", grp ? stn_group_set_compressor(grp, 1, &opts.compressor) : stn_set_compressor(h, 1, &opts.compressor));

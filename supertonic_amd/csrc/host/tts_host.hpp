@@ -82,6 +82,9 @@ struct EngineOptions {
     bool compressor_on = false;    // every utterance through the dynamic range compressor on the GPU, behind the filters and before everything
     stn_compressor compressor{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};  // above (stn_set_compressor); these are the "speech" preset's values.
                                    // CLI --compressor THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]] and --compressor-preset speech
+    bool expander_on = false;      // every utterance through the downward expander / noise gate on the GPU, behind the filters and in front of
+    stn_expander expander{-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f};  // the de-esser (stn_set_expander); these are the "speech" preset's values.
+                                   // CLI --expander THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]] and --expander-preset {speech,gate}
     bool deesser_on = false;       // every utterance through the de-esser on the GPU, behind the filters and in front of the compressor
     stn_deesser deesser{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};  // (stn_set_deesser); these are the "speech" preset's values.
                                    // CLI --deesser FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]] and --deesser-preset speech
@@ -110,6 +113,12 @@ std::string compressorPreset(const std::string& name, stn_compressor& c);
 // 4:1, knee 6 dB, 1 ms, 40 ms, range 12 dB, split) into c, or why not.  The numeric limits are stn_set_deesser's own.
 std::string parseDeesserSpec(const std::string& spec, stn_deesser& c);
 std::string deesserPreset(const std::string& name, stn_deesser& c);
+// The command line's expander arguments (host only).  parseExpanderSpec: "THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]"
+// (the values of `preset` for what is left out, as binding.parse_expander_spec takes them) into c, or why not.  expanderPreset: "speech"
+// (-50 dB, 3:1, knee 6 dB, range 24 dB, 1 ms, 30 ms, 150 ms) or "gate" (-45 dB, 20:1, knee 0, range 60 dB, 0.5 ms, 50 ms, 100 ms) into c,
+// or why not.  The numeric limits are stn_set_expander's own.
+std::string parseExpanderSpec(const std::string& spec, stn_expander& c, const std::string& preset = "speech");
+std::string expanderPreset(const std::string& name, stn_expander& c);
 // The command line's dither mode (host only): "off", "round", "tpdf" or "tpdf-hp" into mode (STN_DITHER_*), or why not
 std::string parseDitherMode(const std::string& name, int& mode);
 

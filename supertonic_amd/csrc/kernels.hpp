@@ -598,10 +598,38 @@ void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t r
                               float* s2, float* y, float* gr, float* cmax);
 // in place: st[row][k] end values from zero -> the chunks' start values; stage 1 the (max, x) scan, stage 2 the linear one
 void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const CompTable& t, float* st);
+// the scan itself, for every stage whose chunks compose by one of these (pw: LO_SCAN doubles on the device): v + P o, max(v, P o) and
+// max(v, o - P) (the expander's detector, section 25); unit names the caller in what chunk_shape refuses
+enum ScanComb { SCAN_LINEAR = 0, SCAN_MAX_TIMES = 1, SCAN_MAX_PLUS = 2 };
+void launch_chunk_scan(hipStream_t s, ScanComb comb, const char* unit, int64_t rows, int64_t W, const double* pw, float* st);
 // out[row] = max_k cmax[row][k]
 void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const float* cmax, float* out);
 // "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
 const char* compressor_staging_form(const float* x, const float* y, int64_t W);
+
+// Fetch-time downward expander / noise gate (kernels_expander.hip; the limits, the tables and the sequence are engine_expander.cpp;
+// DESIGN.md section 25).  Every row W long, chunks of LO_CHUNK samples from sample 0, workgroups of LO_WG chunks, scan tiles of LO_SCAN.
+struct ExpCoef { float T, S, K, R, kA, delta, Bh; };  // threshold dB, ratio - 1, knee dB, range dB, attack k, release dB per sample, hold boost dB (fp32)
+struct ExpTable {
+    int hz = 0;
+    float set[7] = {};                // the stn_expander fields the table was made from
+    int64_t hold = 0;                 // Hs, the hold in samples
+    ExpCoef coef{};
+    std::vector<double> pw;           // host copy, [2][LO_SCAN]: (i + 1) LO_CHUNK delta then E^(i+1), E = (1 - kA)^LO_CHUNK
+    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
+};
+// pass 1: s1[row][k] = u at the end of chunk k from zero.  pass 2: s1 = u at the chunk's start -> s2[row][k] = yL at its end from zero.
+// pass 3: s1, s2 = the start values -> y (row stride W; may be x), open (rows x W yL, or null), cmin[row][k] = min of R - yL and
+// ccnt[row][k] = count of yL <= R / 2 over the chunk's samples below n[row] (device; null: W).  The staging form of all three is that
+// of (x, y, W).
+void launch_expander_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const ExpTable& t, float* s1,
+                            float* s2, float* y, float* open, float* cmin, int32_t* ccnt);
+// in place: st[row][k] end values from zero -> the chunks' start values; stage 1 the (max, +) scan, stage 2 the linear one
+void launch_expander_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const ExpTable& t, float* st);
+// omin[row] = min_k cmin[row][k], ocnt[row] = sum_k ccnt[row][k]
+void launch_expander_rows(hipStream_t s, int64_t rows, int64_t W, const ExpTable& t, const float* cmin, const int32_t* ccnt, float* omin, int64_t* ocnt);
+// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
+const char* expander_staging_form(const float* x, const float* y, int64_t W);
 
 // Fetch-time de-esser (kernels_deesser.hip; the limits, the tables and the sequence of eight launches are engine_deesser.cpp; DESIGN.md
 // section 21): the compressor's detector on the level of a band h = HP4(x), its gain on the band (split) or on x (wide).  The band's

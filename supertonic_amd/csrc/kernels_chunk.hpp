@@ -1,5 +1,5 @@
 // kernels_chunk.hpp — what the chunk kernels of the fetch-time stages share (kernels_loudness.hip, kernels_edges.hip, kernels_filter.hip,
-// kernels_compressor.hip, kernels_deesser.hip; DESIGN.md sections 11, 14, 18, 20, 21): the staging of a workgroup's span through LDS,
+// kernels_compressor.hip, kernels_deesser.hip, kernels_expander.hip; DESIGN.md sections 11, 14, 18, 20, 21, 25): the staging of a workgroup's span through LDS,
 // the two-section biquad step, the gain computer and the two detector recurrences, and the host's choice of the staging form.
 // One definition each: a pass and the pass that refilters from the start states the scan formed round identically by construction.
 #pragma once
@@ -99,6 +99,29 @@ __device__ __forceinline__ float gain_want(float T, float S, float K, float x) {
 // the decoupled peak detector y1 = max(z, y1 - kR y1) and its smoothing yL = yL + kA (y1 - yL)
 __device__ __forceinline__ float gain_peak(float kR, float z, float y1) { return fmaxf(z, __builtin_fmaf(-kR, y1, y1)); }
 __device__ __forceinline__ float gain_smooth(float kA, float y1, float yl) { return __builtin_fmaf(kA, y1 - yl, yl); }
+
+// the expander's gain computer (section 25), gain_want's sibling: the openness wanted at a sample, in dB, for threshold T, slope
+// S = ratio - 1, knee K and range R.  z in [0, R] is the attenuation wanted d = T - xG dB under the threshold, o = R - z the openness;
+// a fully open sample (z == 0) carries the hold boost Bh on top, which the (max, +) detector takes Bh / delta samples to walk down.
+__device__ __forceinline__ float expand_open(float T, float S, float K, float R, float Bh, float x) {
+    const float xg = 20.0f * log10f(fmaxf(fabsf(x), 1e-6f));
+    const float d = T - xg;
+    const float d2 = 2.0f * d;
+    float z;
+    if (d2 < -K) {
+        z = 0.0f;
+    } else if (K > 0.0f && fabsf(d2) <= K) {
+        const float t = d + 0.5f * K;
+        z = (S * (t * t)) / (2.0f * K);
+    } else {
+        z = S * d;
+    }
+    z = fminf(z, R);
+    const float o = R - z;
+    return z == 0.0f ? o + Bh : o;
+}
+// its detector u = max(t, u - delta): opens at once, holds, then closes at a constant rate in dB
+__device__ __forceinline__ float expand_detect(float delta, float t, float u) { return fmaxf(t, u - delta); }
 
 inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 // 1: the 16-byte form of chunk_stage_in / chunk_stage_out for rows of stride W read at x and written at y (null: not written)

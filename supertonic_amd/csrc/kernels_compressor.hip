@@ -91,16 +91,20 @@ __global__ void __launch_bounds__(LO_WG) compressor_chunk_kernel(const float* x,
     chunk_stage_out<LO_WG, LO_CHUNK>(win, yr, cnt, vec);
 }
 
-// kMax: (D, b) . v = max(v, D o); otherwise the linear v + E o
-template <bool kMax>
-__device__ __forceinline__ double cp_comb(double P, double o, double v) { return kMax ? fmax(v, P * o) : v + P * o; }
+// SCAN_MAX_TIMES: (D, b) . v = max(v, D o); SCAN_MAX_PLUS: (c, b) . v = max(v, o - c), the expander's detector (section 25);
+// otherwise the linear v + E o
+template <ScanComb kComb>
+__device__ __forceinline__ double cp_comb(double P, double o, double v) {
+    return kComb == SCAN_MAX_TIMES ? fmax(v, P * o) : kComb == SCAN_MAX_PLUS ? fmax(v, o - P) : v + P * o;
+}
 
 // st[row][k], K chunks per row: end values from zero in, start values out.  Tile t covers chunks t*LO_SCAN ..; after the inclusive
 // Hillis-Steele scan lane i holds v_i = the composition of chunks t*LO_SCAN .. t*LO_SCAN + i applied to 0, so the start value of chunk
 // t*LO_SCAN + i is v_{i-1} combined with P^i c, c the tile's carry-in.  pw[i] = P^(i+1), P = D or E of a whole chunk (only a row's last
-// chunk can be short, and nothing starts behind it).  In double; only the start values stored are fp32.  Lanes past K hold 0, the
-// neutral value of both families (every value is >= 0), so the order of the combinations is fixed by the chunk index, not by K.
-template <bool kMax>
+// chunk can be short, and nothing starts behind it); for SCAN_MAX_PLUS pw[i] = (i + 1) c, what i + 1 whole chunks subtract.  In double;
+// only the start values stored are fp32.  Lanes past K hold 0, the neutral value of all three families (every value is >= 0), so the
+// order of the combinations is fixed by the chunk index, not by K.
+template <ScanComb kComb>
 __global__ void __launch_bounds__(LO_SCAN) compressor_scan_kernel(int64_t K, const double* __restrict__ pw, float* st) {
     __shared__ double buf[2][LO_SCAN];  // two images, written in turn: a level's readers are done before the level after next writes
     const int64_t row = blockIdx.x;
@@ -114,14 +118,14 @@ __global__ void __launch_bounds__(LO_SCAN) compressor_scan_kernel(int64_t K, con
         for (int d = 1; d < LO_SCAN; d <<= 1) {
             buf[p][i] = v;
             __syncthreads();
-            if (i >= d) v = cp_comb<kMax>(pw[d - 1], buf[p][i - d], v);
+            if (i >= d) v = cp_comb<kComb>(pw[d - 1], buf[p][i - d], v);
             p ^= 1;
         }
         buf[p][i] = v;
         __syncthreads();
-        const double s = i == 0 ? c : cp_comb<kMax>(pw[i - 1], c, buf[p][i - 1]);
+        const double s = i == 0 ? c : cp_comb<kComb>(pw[i - 1], c, buf[p][i - 1]);
         if (k < K) sr[k] = (float)s;
-        c = cp_comb<kMax>(pw[LO_SCAN - 1], c, buf[p][LO_SCAN - 1]);
+        c = cp_comb<kComb>(pw[LO_SCAN - 1], c, buf[p][LO_SCAN - 1]);
         p ^= 1;
     }
 }
@@ -159,12 +163,21 @@ void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t r
     else STN_KLAUNCH(compressor_chunk_kernel<3>, grid, dim3(LO_WG), 0, s, x, y, W, vec, Ks, t.coef, n, s1, s2, gr, cmax);
 }
 
+void launch_chunk_scan(hipStream_t s, ScanComb comb, const char* unit, int64_t rows, int64_t W, const double* pw, float* st) {
+    if (rows <= 0 || W <= 0) return;
+    chunk_shape(unit, rows, W);
+    if (!pw || !st) throw std::invalid_argument(std::string(unit) + ": scan without its table or states");
+    const dim3 grid((unsigned)rows), wg(LO_SCAN);
+    if (comb == SCAN_MAX_TIMES) STN_KLAUNCH(compressor_scan_kernel<SCAN_MAX_TIMES>, grid, wg, 0, s, lo_chunks(W), pw, st);
+    else if (comb == SCAN_MAX_PLUS) STN_KLAUNCH(compressor_scan_kernel<SCAN_MAX_PLUS>, grid, wg, 0, s, lo_chunks(W), pw, st);
+    else STN_KLAUNCH(compressor_scan_kernel<SCAN_LINEAR>, grid, wg, 0, s, lo_chunks(W), pw, st);
+}
+
 void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const CompTable& t, float* st) {
     if (rows <= 0 || W <= 0) return;
-    chunk_shape("compressor", rows, W);
     if (!t.dev || !st) throw std::invalid_argument("compressor: scan without its table or states");
-    if (stage == 1) STN_KLAUNCH(compressor_scan_kernel<true>, dim3((unsigned)rows), dim3(LO_SCAN), 0, s, lo_chunks(W), t.dev, st);
-    else STN_KLAUNCH(compressor_scan_kernel<false>, dim3((unsigned)rows), dim3(LO_SCAN), 0, s, lo_chunks(W), t.dev + LO_SCAN, st);
+    if (stage == 1) launch_chunk_scan(s, SCAN_MAX_TIMES, "compressor", rows, W, t.dev, st);
+    else launch_chunk_scan(s, SCAN_LINEAR, "compressor", rows, W, t.dev + LO_SCAN, st);
 }
 
 void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const float* cmax, float* out) {

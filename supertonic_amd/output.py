@@ -30,6 +30,7 @@ def _peak_mode(v):
 _PARSE = {
     "output_rate": int,
     "filters": lambda v: binding.filter_args(None if v is False else v),
+    "expander": lambda v: binding.expander_args(v) or False,
     "deesser": lambda v: binding.deesser_args(v) or False,
     "compressor": lambda v: binding.compressor_args(v) or False,
     "loudness": lambda v: v is not False and _loudness(v),
@@ -52,6 +53,10 @@ class OutputSettings:
     filters       a chain of up to 8 biquads every utterance goes through, after the resampler and before everything below
                   (stn_set_filters): a list as binding.filter_args takes it, e.g. [("highpass", 80)]; the numeric limits are checked by
                   the engine against the output rate in force.  Normalized: a tuple of (type, freq_hz, q, gain_db).  Off: False or [], ().
+    expander      what lies under a threshold (the noise floor between words) turned down, behind the chain and in front of the de-esser
+                  (stn_set_expander): True (the "speech" default: -50 dB, 3:1, knee 6 dB, range 24 dB, attack 1 ms, hold 30 ms, release
+                  150 ms), a dict of those fields or a 7-tuple, as binding.expander_args takes them.  Normalized: the 7-tuple of floats.
+                  Off: False.
     deesser       the sibilants of every utterance turned down, behind the chain and in front of the compressor (stn_set_deesser): True (the
                   "speech" default: 5500 Hz, -30 dB, 4:1, knee 6 dB, attack 1 ms, release 40 ms, range 12 dB, split), a dict of those
                   fields or an 8-tuple, as binding.deesser_args takes them; freq_hz is checked by the engine against the output rate in
@@ -96,9 +101,12 @@ class OutputSettings:
     # equal to ALL_OFF with dither off, as it was before the setting was there.  Where the difference matters (a request that names no
     # pitch gets the server's, one that says 0 gets none) the service's BatchKey carries it beside the settings (pitch_set).
     pitch = None
+    # An attribute like pitch, for the same reasons, and with unset and off comparing equal as its are (applied between filters and
+    # deesser).  The service's BatchKey carries the difference (expander_set).
+    expander = None
 
     def _all(self):
-        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither, self.pitch or False)
+        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither, self.pitch or False, self.expander or False)
 
     def __eq__(self, other):
         return other._all() == self._all() if type(other) is type(self) else NotImplemented
@@ -107,12 +115,14 @@ class OutputSettings:
         return hash(self._all())
 
     def __repr__(self):
-        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither", "pitch"], self._all())) + ")"
+        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither", "pitch", "expander"], self._all())) + ")"
 
     def decided(self):
-        """This value over ALL_OFF, and dither and pitch off where that leaves them unset: every setting decided (what an instance holds)"""
+        """This value over ALL_OFF, and dither, pitch and expander off where that leaves them unset: every setting decided (what an
+        instance holds)"""
         s = self.over(OutputSettings.ALL_OFF)
-        return s.replace(dither=False if s.dither is None else s.dither, pitch=False if s.pitch is None else s.pitch)
+        return s.replace(dither=False if s.dither is None else s.dither, pitch=False if s.pitch is None else s.pitch,
+                         expander=False if s.expander is None else s.expander)
 
     @classmethod
     def parse(cls, **kw):
@@ -125,9 +135,11 @@ class OutputSettings:
 
     def replace(self, **changes):
         """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser,
-        dither and pitch included"""
+        dither, pitch and expander included"""
         deesser, dither, pitch = changes.pop("deesser", self.deesser), changes.pop("dither", self.dither), changes.pop("pitch", self.pitch)
+        expander = changes.pop("expander", self.expander)
         new = dataclasses.replace(self, **changes)
+        object.__setattr__(new, "expander", expander)
         object.__setattr__(new, "deesser", deesser)
         object.__setattr__(new, "dither", dither)
         object.__setattr__(new, "pitch", pitch)
@@ -158,6 +170,8 @@ class OutputSettings:
             engine.set_output_rate(self.output_rate)
         if self.filters:
             engine.set_filters(self.filters)
+        if self.expander is not None:
+            engine.set_expander(self.expander or None)
         if self.deesser:
             engine.set_deesser(self.deesser)
         if self.compressor is not None:

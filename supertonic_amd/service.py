@@ -31,13 +31,13 @@ REPORT_HEADERS = {"X-Loudness-Integrated": "integrated", "X-Loudness-Range": "ra
 
 # what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
 # (pitch_set: whether the request names a pitch.  OutputSettings compares an unset pitch equal to an off one; the key must not: a request
-# that names none gets the synthesizer's own pitch, one that says 0 gets none)
-BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings pitch_set")
+# that names none gets the synthesizer's own pitch, one that says 0 gets none.  expander_set: the same for the expander)
+BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings pitch_set expander_set")
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
               trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, dither=None,
-              dither_seed=None, pitch=None, compressor=None):
+              dither_seed=None, pitch=None, expander=None, compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -51,7 +51,8 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     integer in [0, 2^64), 0 when left out; alone it is validated and dropped): OutputSettings' dither.  encoding: the waves in that sample encoding (binding.ENC_* or a name; None: float32).
     loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode.  pitch: semitones in [-12, 12] (0 = off),
     refused with the engine's message: requests of different pitch never share a batch, and neither do one that names none (the
-    synthesizer's own holds) and one that says 0."""
+    synthesizer's own holds) and one that says 0.  expander: True, a dict or a 7-tuple as binding.expander_args takes it, False = off,
+    checked against the engine's limits; as with pitch, a request that names none and one that says false never share a batch."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
     if why:
@@ -64,8 +65,12 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     why = comp and binding.compressor_error(comp, int(sample_rate or model_rate))
     if why:
         raise ValueError(why)
+    xpd = None if expander is None else (binding.expander_args(expander) or False)
+    why = xpd and binding.expander_error(xpd, int(sample_rate or model_rate))
+    if why:
+        raise ValueError(why)
     dith = binding.dither_args(dither or "off", dither_seed) or False
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, deesser=dees, compressor=comp, dither=None if dither is None else dith, pitch=pitch, loudness=None if loudness is None else (loudness, peak_ceiling),
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, expander=xpd, deesser=dees, compressor=comp, dither=None if dither is None else dith, pitch=pitch, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
@@ -74,7 +79,7 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     if s.trim_silence is None:
         s = s.replace(max_pause=None)
     return BatchKey(int(total_step), float(speed), None if encoding is None else binding.encoding_id(encoding), str(loudness_scope),
-                    bool(trim_chunks), s, s.pitch is not None)
+                    bool(trim_chunks), s, s.pitch is not None, s.expander is not None)
 
 
 class _Job:
@@ -287,6 +292,12 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                                        "{freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db, "
                                                                        "mode}, the fields left out from that default; false: off; null: the "
                                                                        "server's.")
+        expander: Optional[Union[bool, dict]] = Field(None, description="Downward expander / noise gate every utterance goes through on the GPU, "
+                                                                        "behind the filters and in front of the de-esser: true (the speech "
+                                                                        "default: -50 dB, 3:1, knee 6 dB, range 24 dB, attack 1 ms, hold 30 ms, "
+                                                                        "release 150 ms) or {threshold_db, ratio, knee_db, range_db, attack_ms, "
+                                                                        "hold_ms, release_ms}, the fields left out from that default; false: "
+                                                                        "off; null: the server's.")
         compressor: Optional[Union[bool, dict]] = Field(None, description="Dynamic range compressor every utterance goes through on the GPU, behind "
                                                                           "the filters and before everything else: true (the speech default: "
                                                                           "-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB) or "
@@ -358,6 +369,16 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             if why:
                 raise HTTPException(status_code=400, detail=why)
             extra["deesser"] = dees
+        xpd = None
+        if req.expander is not None:
+            try:
+                xpd = binding.expander_args(req.expander) or False
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+            why = binding.expander_error(xpd, sr) if xpd else ""
+            if why:
+                raise HTTPException(status_code=400, detail=why)
+            extra["expander"] = xpd
         comp = None
         if req.compressor is not None:
             try:
@@ -418,7 +439,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             waves, durs, *rep = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                                enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                                trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
-                                               max_pause_ms=req.max_pause_ms, filters=chain, deesser=dees, compressor=comp,
+                                               max_pause_ms=req.max_pause_ms, filters=chain, expander=xpd, deesser=dees, compressor=comp,
                                                dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, pitch=pitch, **more)
             report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)

@@ -245,8 +245,8 @@ def load_text_to_speech(onnx_dir, use_gpu=True, device=0, dtype="bf16", allow_sy
     error, as in the reference (cpp/helper.cpp:805); only when the caller opts in — `allow_synthetic=True`, or TTS_ALLOW_SYNTHETIC=1
     in the environment when the argument is left at None — does the engine fall back to the default architecture on synthetic
     weights (benchmarks and tests on machines without the Hugging Face assets), and it says so.  out: the instance's OutputSettings
-    keywords (output_rate, filters, deesser, compressor, loudness, trim_silence, max_pause, limiter, peak_mode, dither, pitch), each off when
-    left out.  pitch=2.0 shifts every utterance up two semitones in front of everything else.  dither acts on what is fetched as "pcm16" or "pcm24" (encoding=); the float waves are the same with and without it."""
+    keywords (output_rate, filters, expander, deesser, compressor, loudness, trim_silence, max_pause, limiter, peak_mode, dither, pitch), each off when
+    left out.  expander=True turns the noise floor between words down by the "speech" default, expander={"threshold_db": -45} names fields.  pitch=2.0 shifts every utterance up two semitones in front of everything else.  dither acts on what is fetched as "pcm16" or "pcm24" (encoding=); the float waves are the same with and without it."""
     settings = OutputSettings.parse(**out)  # (refused before the engine is created)
     if allow_synthetic is None:
         allow_synthetic = os.getenv("TTS_ALLOW_SYNTHETIC", "0").strip().lower() in {"1", "true", "yes", "y", "on"}
