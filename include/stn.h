@@ -1038,6 +1038,13 @@ int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k
 int stn_op_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows,
                         const float* w_or_null /*[C,k]*/, const float* bias_or_null, const float* ln_g, const float* ln_b,
                         const int32_t* seqlen_or_null, int packed, int ln_only, float* y, int64_t y_rows, char* form, size_t form_cap);
+/* The tail-reading variant of the packed launch above (the dense vocoder trimmed to one receptive field): sequence b is the head of a row of
+ * T >= L frames whose frames from seqlen[b] on are not stored; a tap at a frame tt >= seqlen[b] reads tail[min(T - 1 - tt, rf)] (tail: rf + 1
+ * rows of C, indexed by the distance to the end of the row) and zero from T on; taps before the row's start read zero.  Packed rows only
+ * (seqlen needed, B <= 1024, C <= 512, k in {5, 7}); x, y, form as in stn_op_dwconv_ln_ex; only the rows the sequences own are written. */
+int stn_op_dwconv_ln_tail(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows,
+                          const float* w /*[C,k]*/, const float* bias, const float* ln_g, const float* ln_b, const int32_t* seqlen,
+                          const float* tail /*[rf+1,C]*/, int T, int rf, float* y, int64_t y_rows, char* form, size_t form_cap);
 /* diagnostics (no device needed): the form the engine's depthwise-conv + LayerNorm launcher takes for B sequences of L rows, C channels,
  * k taps, output format dtype, padded or packed rows: "v3<K,R>" (combs of R frames), "v3occ4<7,4>" (the same held to four waves per SIMD),
  * "v2<K>" or "generic".  Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher refuses

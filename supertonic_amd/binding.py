@@ -652,6 +652,8 @@ def load():
     L.stn_op_attention.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p]
     L.stn_op_dwconv_ln_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, vp, vp, _f32p, _f32p, vp, ci, ci, _f32p, ctypes.c_int64,
                                       ctypes.c_char_p, ctypes.c_size_t]
+    L.stn_op_dwconv_ln_tail.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p, ci, ci, _f32p,
+                                        ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_resample_form.argtypes = [ci, ci, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_resample_form.restype = ctypes.c_int
     L.stn_dbg_dwconv_ln_form.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
@@ -2479,6 +2481,24 @@ class Engine:
                                                1 if _w is None else _w.shape[1], int(dil), x.reshape(-1), x.shape[0], wp, bp, _c(g, np.float32),
                                                _c(b, np.float32), lp, int(bool(packed)), int(bool(ln_only)), o_r.reshape(-1), o_r.shape[0], form,
                                                ctypes.sizeof(form)))
+        return o_r, form.value.decode()
+
+    def op_dwconv_ln_tail(self, x, w, bias, g, b, dil, out, L, seqlen, tail, T, dtype=None):
+        """The tail-reading variant of the packed launch_dwconv_ln (stn_op_dwconv_ln_tail): sequence i owns seqlen[i] consecutive rows of x / out
+        and is the head of a row of T >= L frames; a tap at a frame tt >= seqlen[i] reads tail[min(T - 1 - tt, rf)] (tail [rf + 1, C]) and
+        zero from T on.  Returns (out as a new fp32 array, whole; form string)."""
+        x = _c(x, np.float32)
+        tail = _c(tail, np.float32)
+        o_r = np.array(out, dtype=np.float32, order="C", copy=True)
+        C = x.shape[1]
+        w = _c(w, np.float32)
+        seqlen = _c(seqlen, np.int32)
+        assert tail.ndim == 2 and tail.shape[1] == C and tail.shape[0] >= 1
+        form = ctypes.create_string_buffer(32)
+        self._ck(self._lib.stn_op_dwconv_ln_tail(self._h, self.dtype if dtype is None else _DTYPES[dtype], len(seqlen), int(L), C, w.shape[1],
+                                                 int(dil), x.reshape(-1), x.shape[0], w, _c(bias, np.float32), _c(g, np.float32),
+                                                 _c(b, np.float32), seqlen, tail.reshape(-1), int(T), tail.shape[0] - 1, o_r.reshape(-1),
+                                                 o_r.shape[0], form, ctypes.sizeof(form)))
         return o_r, form.value.decode()
 
     def op_fold_ln(self, x, part, b2, gamma, g, b, rowvec=None, row_b=None, dtype=None):

@@ -971,6 +971,25 @@ int stn_op_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, in
                         int64_t y_rows, char* form, size_t form_cap) {
     STN_TRY(h, dwconv_ln_ex_checked(h, dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, seqlen, packed, ln_only, y, y_rows, form, form_cap))
 }
+static void dwconv_ln_tail_checked(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
+                                   const float* bias, const float* g, const float* b, const int32_t* seqlen, const float* tail, int T, int rf,
+                                   float* y, int64_t y_rows, char* form, size_t form_cap) {
+    need(B > 0 && B <= 1024 && L > 0 && C > 0 && C % 4 == 0 && C <= 512 && (k == 5 || k == 7) && dil > 0 && x && w && bias && g && b && y && seqlen &&
+             x_rows > 0 && y_rows > 0,
+         "stn_op_dwconv_ln_tail: bad argument");
+    need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_dwconv_ln_tail: unknown dtype");
+    need(tail && rf >= 0 && T >= L, "stn_op_dwconv_ln_tail: needs a tail table of rf + 1 >= 1 rows and T >= L");
+    int64_t rows = 0;
+    for (int i = 0; i < B; ++i) { need(seqlen[i] >= 0 && seqlen[i] <= L, "stn_op_dwconv_ln_tail: seqlen out of [0, L]"); rows += seqlen[i]; }
+    need(x_rows >= rows && y_rows >= rows, "stn_op_dwconv_ln_tail: x / y hold fewer rows than the launch addresses");
+    const std::string f = h->eng->op_dwconv_ln_ex(dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, seqlen, 1, 0, y, y_rows, tail, T, rf);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_dwconv_ln_tail(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
+                          const float* bias, const float* g, const float* b, const int32_t* seqlen, const float* tail, int T, int rf, float* y,
+                          int64_t y_rows, char* form, size_t form_cap) {
+    STN_TRY(h, dwconv_ln_tail_checked(h, dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, seqlen, tail, T, rf, y, y_rows, form, form_cap))
+}
 int stn_dbg_dwconv_ln_form(int dtype, int B, int L, int C, int k, int packed, char* out, size_t cap) {
     if (B < 1 || L < 1 || C < 1 || k < 1 || !(k & 1) || (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16)) return STN_ERR_INVALID;
     std::string f;

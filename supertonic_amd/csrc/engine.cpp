@@ -171,8 +171,7 @@ Engine::~Engine() {
     free_weights();
     for (void* p : batch_owned_) (void)hipFree(p);
     for (void* p : batch_retired_) (void)hipFree(p);
-    if (vo_quiet_) (void)hipFree(vo_quiet_);
-    if (vo_edge_) (void)hipFree(vo_edge_);
+    free_vocoder_constants();
     if (tcond_.buf) (void)hipFree(tcond_.buf);
     for (auto& sp : spans_) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
@@ -555,12 +554,13 @@ void* Engine::to_act(const float* src, int64_t n) {
 
 // x <- (x + gamma * pw2(GELU(pw1(LN(dwconv(x)))))) * mask      (in place, x fp32 [B*L][C]); the pointwise pair in form f
 void Engine::convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
-                      const int* conv_len, const float* rowvec, int rv_ld, const Ragged* rg, FoldState* fs) {
+                      const int* conv_len, const float* rowvec, int rv_ld, const Ragged* rg, FoldState* fs, const DwconvTail& tl) {
     const int64_t M = rg ? (int64_t)rg->rows : (int64_t)B * L;
     if (f.kind == FFN_K4_SPLIT && !(fs && rg)) throw std::logic_error("convnext: K4-split needs the stage's fold state and packed rows");
     const Arena::Mark mk = ar_.mark();
     void* xn = act_alloc(M * C);
     if (fs) x = fs->x;
+    if (tl.tail && (fs || !rg)) throw std::logic_error("convnext: a tail table needs packed rows and no fold state");
     if (fs && fs->pending) {
         // the previous block's pointwise pair is still a set of partial sums: this block's conv kernel folds it on the way in
         if (prof_on_) prof_begin("fold_dwconv_ln", (double)M * C * (2.0 * k + 8 + 2.0 * fs->fold.S), (double)M * C * (8.0 + 2.0 + 2.0 * fs->fold.S));
@@ -572,7 +572,7 @@ void Engine::convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int 
         x = fs->x;
     } else {
         if (prof_on_) prof_begin("dwconv_ln", (double)M * C * (2.0 * k + 8), (double)M * C * (4.0 + (is_half(dt_) ? 2.0 : 4.0)));
-        launch_dwconv_ln(s_, dt_, x, B, L, C, p.dw_t, p.dw_b, k, dil, p.ln.g, p.ln.b, a_.ln_eps, xn, rg ? len : conv_len, rg ? rg->off : nullptr);
+        launch_dwconv_ln(s_, dt_, x, B, L, C, p.dw_t, p.dw_b, k, dil, p.ln.g, p.ln.b, a_.ln_eps, xn, rg ? len : conv_len, rg ? rg->off : nullptr, tl);
         if (prof_on_) prof_end();
     }
     FfnArgs fa;
@@ -1045,30 +1045,50 @@ void Engine::prepare_ffn_weights() {
     if (tmp) (void)hipFree(tmp);
 }
 
-void Engine::prepare_vocoder_constants() {
-    if (vo_quiet_) { (void)hipFree(vo_quiet_); vo_quiet_ = nullptr; }
-    if (vo_edge_) { (void)hipFree(vo_edge_); vo_edge_ = nullptr; }
+void Engine::free_vocoder_constants() {
+    for (VoConsts& c : vo_c_) {
+        if (c.quiet) (void)hipFree(c.quiet);
+        if (c.edge) (void)hipFree(c.edge);
+        if (c.tail) (void)hipFree(c.tail);
+        c = VoConsts();
+    }
     vo_rf_ = 0;
+}
+
+// One run per form of the blocks' pointwise pair a batch can take (two GEMMs below ffn_min_rows_, K4 from there on): the run itself has a few
+// hundred rows and would take the two GEMMs by its own count, but a batch that fills the rest of its rows from these constants must find in
+// them the bits its own kernels give.  (The other kernels of the stage give a row the same bits at every row count.)
+void Engine::prepare_vocoder_constants() {
+    free_vocoder_constants();
     const stn_arch& a = a_;
     if (!is_half(dt_) || !dwconv_ln_supports_packed(a.vo_dim, a.vo_kernel) || a.base_chunk_size % 4) return;
-    const int rf = vocoder_receptive_field(), ccf = a.chunk_compress_factor, W = a.base_chunk_size;
+    const int rf = vocoder_receptive_field(), ccf = a.chunk_compress_factor, W = a.base_chunk_size, C = a.vo_dim;
     const int Lz = (4 * rf + ccf) / ccf + 1, Tz = Lz * ccf, D = a.latent_dim * ccf;
-    ar_.reset();
-    float* lat = f32_alloc((int64_t)D * Lz);
-    float* wz = f32_alloc((int64_t)Tz * W);
-    STN_HIP(hipMemsetAsync(lat, 0, sizeof(float) * (size_t)D * Lz, s_));
-    vocoder_dev(1, Lz, lat, wz);
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&vo_quiet_), sizeof(float) * (size_t)W));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&vo_edge_), sizeof(float) * (size_t)rf * W));
-    STN_HIP(hipMemcpyAsync(vo_quiet_, wz + (size_t)2 * rf * W, sizeof(float) * (size_t)W, hipMemcpyDeviceToDevice, s_));
-    STN_HIP(hipMemcpyAsync(vo_edge_, wz + (size_t)(Tz - rf) * W, sizeof(float) * (size_t)rf * W, hipMemcpyDeviceToDevice, s_));
-    sync();
+    const bool k4 = a.vo_blocks > 0 && ffn_fused_supported(dt_, C, a.vo_hidden) && ffn_w_.count(convnext_w("vo.blk0").pw1.w.as(dt_));
+    for (int kind : {(int)FFN_GEMMS, (int)FFN_K4}) {
+        if (kind == FFN_K4 && !k4) continue;
+        VoConsts& c = vo_c_[kind == FFN_K4];
+        const size_t tail_n = (size_t)std::max(a.vo_blocks, 1) * (rf + 1) * C;
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&c.quiet), sizeof(float) * (size_t)W));
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&c.edge), sizeof(float) * (size_t)std::max(rf, 1) * W));
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(&c.tail), sizeof(float) * tail_n));
+        ar_.reset();
+        float* lat = f32_alloc((int64_t)D * Lz);
+        float* wz = f32_alloc((int64_t)Tz * W);
+        STN_HIP(hipMemsetAsync(lat, 0, sizeof(float) * (size_t)D * Lz, s_));
+        vo_force_ffn_ = kind; vo_capture_ = c.tail;
+        try { vocoder_dev(1, Lz, lat, wz); } catch (...) { vo_force_ffn_ = -1; vo_capture_ = nullptr; throw; }
+        vo_force_ffn_ = -1; vo_capture_ = nullptr;
+        STN_HIP(hipMemcpyAsync(c.quiet, wz + (size_t)2 * rf * W, sizeof(float) * (size_t)W, hipMemcpyDeviceToDevice, s_));
+        STN_HIP(hipMemcpyAsync(c.edge, wz + (size_t)(Tz - rf) * W, sizeof(float) * (size_t)rf * W, hipMemcpyDeviceToDevice, s_));
+        sync();
+    }
     vo_rf_ = rf;
 }
 
 // host mirror of trim_len_kernel: the packed row count (0 when trimming does not apply to this batch)
 int Engine::trimmed_rows(int B, int L, std::vector<int>* n_host) const {
-    if (!packed_ve_ || vo_ragged_ || !vo_quiet_ || vo_rf_ <= 0 || B > 1024) return 0;
+    if (!packed_ve_ || vo_ragged_ || !vo_c_[0].quiet || vo_rf_ <= 0 || B > 1024) return 0;
     const int ccf = a_.chunk_compress_factor, T = L * ccf, rf = vo_rf_;
     long tot = 0;
     bool any = false;
@@ -1084,17 +1104,34 @@ int Engine::trimmed_rows(int B, int L, std::vector<int>* n_host) const {
     return (any && tot * 10 <= (long)B * T * 9) ? (int)tot : 0;
 }
 
+// host mirror of trim_len_kernel's tail mode, against the same bar
+int Engine::tail_rows(int B, int L) const {
+    if (!packed_ve_ || vo_ragged_ || !vo_c_[0].tail || vo_rf_ <= 0 || B > 1024) return 0;
+    const int ccf = a_.chunk_compress_factor, T = L * ccf, rf = vo_rf_;
+    long tot = 0;
+    for (int i = 0; i < B; ++i) tot += std::min(bt_.h_llen[i] * ccf + rf, T);
+    return tot * 10 <= (long)B * T * 9 ? (int)tot : 0;
+}
+
+int Engine::vocoder_rows(int B, int L, int* form) const {
+    int rows = trimmed_rows(B, L, nullptr);
+    *form = rows ? VO_TRIM_2RF : VO_DENSE;
+    if (!rows && (rows = tail_rows(B, L))) *form = VO_TRIM_TAIL;
+    return rows;
+}
+
 // vlen == nullptr: every utterance is decoded over all T frames (the reference's batched vocoder Run: the padding is
 // zero latent, which the convolutions see as signal).  vlen != nullptr (length-aware): convolution taps beyond an
 // utterance's own length read as the zero padding of a batch-of-one run, so wav[b, :vlen[b]*hop] equals what
 // synthesizing utterance b alone gives; samples past that are written as zeros.
-void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen, int vrows, const int* valid) {
+void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen, int vrows, const int* valid, bool tails) {
     stage_ = "vo";
     const stn_arch& a = a_;
     const int C = a.vo_dim, T = L * a.chunk_compress_factor;
     // length-aware mode on packed rows: only the frames the utterances own exist (bf16 path; needs the comb dwconv kernel)
     const bool packed = vlen && vrows > 0 && is_half(dt_) && B <= 1024 && dwconv_ln_supports_packed(C, a.vo_kernel);
     if (valid && !packed) throw std::runtime_error("trimmed vocoder needs the packed bf16 path");
+    if (tails && !valid) throw std::logic_error("vocoder_dev: the tail form is a trimmed form");
     const int64_t M = packed ? (int64_t)vrows : (int64_t)B * T;
     const Arena::Mark mk = ar_.mark();
     Ragged rg;
@@ -1122,11 +1159,23 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
         if (prof_on_) prof_end();
     }
     // (a trimmed run decides on its DENSE frame count: it must take the kernel of the dense run it is bit-identical to)
-    const FfnForm ff = ffn_plan(FFN_VOCODER, C, a.vo_hidden, M, valid ? (int64_t)B * T : 0, packed, a.vo_kernel,
-                                a.vo_blocks ? *std::max_element(a.vo_dilations, a.vo_dilations + a.vo_blocks) : 1);
-    for (int i = 0; i < a.vo_blocks; ++i)
+    FfnForm ff = ffn_plan(FFN_VOCODER, C, a.vo_hidden, M, valid ? (int64_t)B * T : 0, packed, a.vo_kernel,
+                          a.vo_blocks ? *std::max_element(a.vo_dilations, a.vo_dilations + a.vo_blocks) : 1);
+    if (vo_force_ffn_ >= 0) ff = FfnForm{vo_force_ffn_, 1, false};
+    const VoConsts& vc = vo_c_[ff.kind == FFN_K4];  // the constants computed in this run's own pointwise form
+    if (valid && !(vc.quiet && vc.edge && vc.tail)) throw std::logic_error("vocoder_dev: no zero-latent constants for form " + ff.str());
+    DwconvTail tl;
+    for (int i = 0; i < a.vo_blocks; ++i) {
+        if (vo_capture_) {  // (load time, B == 1, dense) the last rf + 1 rows of this block's input, by distance to the end
+            const int rf = vocoder_receptive_field();
+            for (int j = 0; j <= rf; ++j)
+                STN_HIP(hipMemcpyAsync(vo_capture_ + ((size_t)i * (rf + 1) + j) * C, x + (size_t)(M - 1 - j) * C, sizeof(float) * (size_t)C,
+                                       hipMemcpyDeviceToDevice, s_));
+        }
+        if (tails) { tl.tail = vc.tail + (size_t)i * (vo_rf_ + 1) * C; tl.T = T; tl.rf = vo_rf_; }
         convnext(convnext_w("vo.blk" + std::to_string(i)), ff, x, B, T, C, a.vo_hidden, a.vo_kernel, a.vo_dilations[i],
-                 packed ? vlen : nullptr, packed ? nullptr : vlen, nullptr, 0, rgp);
+                 packed ? vlen : nullptr, packed ? nullptr : vlen, nullptr, 0, rgp, nullptr, tl);
+    }
     void* xn = act_alloc(M * C);
     const LNorm ln = lnorm("vo.out_ln");
     launch_layernorm(s_, dt_, x, M, C, ln.g, ln.b, a.ln_eps, xn);
@@ -1135,8 +1184,10 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
         float* wp = f32_alloc(M * a.base_chunk_size);
         Epilogue e; e.mode = EPI_STORE; e.out_dtype = F32; e.out = wp; e.ldo = a.base_chunk_size;
         gemm("gemm_head", dt_, xn, C, linear("vo.head"), (int)M, e);
-        if (valid) launch_unpack_rows_quiet(s_, wp, valid, rg.off, B, T, a.base_chunk_size, vo_rf_, vo_quiet_, vo_edge_, wav);
+        if (prof_on_) prof_begin("unpack_rows", 0.0, ((double)M + (double)B * T) * a.base_chunk_size * 4.0);
+        if (valid) launch_unpack_rows_quiet(s_, wp, valid, rg.off, B, T, a.base_chunk_size, vo_rf_, vc.quiet, vc.edge, wav);
         else launch_unpack_rows(s_, wp, vlen, rg.off, B, T, a.base_chunk_size, wav);
+        if (prof_on_) prof_end();
     } else {
         Epilogue e; e.mode = EPI_STORE; e.out_dtype = F32; e.out = wav; e.ldo = a.base_chunk_size; e.len = vlen; e.L = T;
         gemm("gemm_head", dt_, xn, C, linear("vo.head"), (int)M, e);

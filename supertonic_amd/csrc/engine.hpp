@@ -209,8 +209,9 @@ class Engine {
     // vrows > 0 (with vlen): run the vocoder on packed rows — vrows = sum of vlen — and unpack into the padded wav at the end
     // valid (with vlen, vrows): the exact trimmed DENSE mode — rows are computed on vlen[b] frames, exact below valid[b], and
     // the rest of each row is the cached zero-latent response (quiet chunk + edge tail)
+    // tails (with valid): the blocks' conv taps beyond vlen[b] read the cached per-layer tails instead of zero (VO_TRIM_TAIL)
     void vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen = nullptr, int vrows = 0,
-                     const int* valid = nullptr);
+                     const int* valid = nullptr, bool tails = false);
     int vocoder_receptive_field() const;  // frames on either side that one output frame depends on
     void prepare_xattn_weights();         // fragment-ordered copies of the estimator's cross-attention Wq / Wo (kernels_xattn_hs.hip)
     std::unordered_map<const void*, const void*> frag_w_;  // row-major 16-bit matrix -> its fragment-ordered copy
@@ -222,7 +223,7 @@ class Engine {
     static constexpr int HS_TS_WG = 8192;
     const float* unit_vec_ = nullptr;  // 1024 ones, then 1024 zeros: layer scale / bias of a fold that has none (the head-split block's output: gamma = 1)
     std::unordered_map<const void*, const void*> frag_acc_w_;  // ... -> its copy in accumulator-operand k order (Wo of the head-split block, kernels_xattn_hs.hip)
-    void prepare_vocoder_constants();     // zero-latent response of the loaded model: quiet chunk and edge tail
+    void prepare_vocoder_constants();     // zero-latent response of the loaded model: quiet chunk, edge tail and the per-layer tails
     void prepare_ffn_weights();           // fragment-ordered copies of every ConvNeXt block's pw1 / pw2 (kernels_ffn.hip, K4)
     struct FfnW { const void *wseq = nullptr, *wsplit[std::size(FFN_SPLITS)] = {}; };  // wsplit: the estimator's K4-split streams, one per FFN_SPLITS entry
     std::unordered_map<const void*, FfnW> ffn_w_;  // key: the block's row-major 16-bit pw1 matrix
@@ -604,8 +605,10 @@ class Engine {
     // launch_dwconv_ln (or, ln_only, launch_layernorm over B*L rows) on the caller's whole buffers (stn_op_dwconv_ln_ex): x [x_rows][C] uploaded as
     // given, padding rows included; packed: sequence b owns seqlen[b] consecutive rows of x / y (row_off from launch_row_map); y [y_rows][C]
     // uploaded as given (rounded to dtype) and downloaded whole.  Returns the form it ran (DwconvLnForm::str, or "layernorm").
+    // tail (optional, host [rf + 1][C]; packed rows): the tail-reading variant, rows of T >= L frames (stn_op_dwconv_ln_tail)
     std::string op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w, const float* bias,
-                                const float* g, const float* b, const int* seqlen, int packed, int ln_only, float* y, int64_t y_rows);
+                                const float* g, const float* b, const int* seqlen, int packed, int ln_only, float* y, int64_t y_rows,
+                                const float* tail = nullptr, int T = 0, int rf = 0);
     // launch_fold_ln on host operands (stn_op_fold_ln): part [S][M][C] rounded to dtype (BF16 / F16), x [M][C] updated in place, y [M][C]
     void op_fold_ln(int dtype, int M, int C, int S, const float* part, const float* b2, const float* gamma, const float* rowvec, const int* row_b,
                     int nseq, const float* g, const float* b, float* x, float* y);
@@ -696,7 +699,8 @@ class Engine {
     FfnOp op_ffn_setup(const char* op, int mode, int M, int C, int I, const float* W1, const float* W2, int split = 0);
     // fs: x is fs->x, and a K4-split block leaves its pointwise pair pending in fs (the caller folds it with the next reader of x)
     void convnext(const ConvNeXt& p, const FfnForm& f, float* x, int B, int L, int C, int hid, int k, int dil, const int* len,
-                  const int* conv_len = nullptr, const float* rowvec = nullptr, int rv_ld = 0, const Ragged* rg = nullptr, FoldState* fs = nullptr);
+                  const int* conv_len = nullptr, const float* rowvec = nullptr, int rv_ld = 0, const Ragged* rg = nullptr, FoldState* fs = nullptr,
+                  const DwconvTail& tl = DwconvTail() /* packed rows: what the conv's taps beyond a sequence's rows read (the vocoder's tail form) */);
     // LayerNorm of the stage's residual stream into xn, folding a pending update first
     void fold_layernorm(FoldState& fs, int64_t M, int C, const LNorm& ln, void* xn, const char* tag);
     void attn_block(const Attn& p, float* x, int B, int Lq, int C, int H, const void* ctx, int Lk, const int* qlen,
@@ -752,11 +756,11 @@ class Engine {
     // A captured graph holds raw pointers: everything it can have baked in is part of its key — the batch buffers (`gen`, bumped
     // by every reallocation), the weights (`wgen`, bumped by every load), the pinned staging the copy nodes read, the stream.
     struct GraphKey {
-        int B = 0, Lt = 0, L = 0, steps = 0; bool noise = false, ragged = false; int xattn = 0; int ffn = 0; int rows = 0, vrows = 0, trows = 0;
+        int B = 0, Lt = 0, L = 0, steps = 0; bool noise = false, ragged = false; int xattn = 0; int ffn = 0; int rows = 0, vrows = 0, trows = 0; int vform = 0;
         uint64_t gen = 0, wgen = 0; const void* p0 = nullptr; const void* p1 = nullptr; const void* pin = nullptr; hipStream_t s = nullptr;
         bool operator==(const GraphKey& o) const {
             return B == o.B && Lt == o.Lt && L == o.L && steps == o.steps && noise == o.noise && ragged == o.ragged && xattn == o.xattn && ffn == o.ffn &&
-                   rows == o.rows && vrows == o.vrows && trows == o.trows && gen == o.gen && wgen == o.wgen && p0 == o.p0 && p1 == o.p1 && pin == o.pin && s == o.s;
+                   rows == o.rows && vrows == o.vrows && vform == o.vform && trows == o.trows && gen == o.gen && wgen == o.wgen && p0 == o.p0 && p1 == o.p1 && pin == o.pin && s == o.s;
         }
     };
     // LRU cache of captured graphs (the reference's call() loop and the n_test loop alternate a few shapes,
@@ -793,10 +797,24 @@ class Engine {
     int fused_xattn_ = 1;  // cross-attention blocks of the estimator: head-split (fold_ln + one launch, kernels_xattn_hs.hip; the default) or, 0, four
                            // launches; STN_XATTN=<0|1> overrides
     int64_t last_ve_rows_ = 0, last_vo_rows_ = 0;
-    float* vo_quiet_ = nullptr;  // [base_chunk_size]      } zero-latent response of the vocoder (device, owned), 16-bit engines
-    float* vo_edge_ = nullptr;   // [rf][base_chunk_size]  }
+    // zero-latent response of the vocoder (device, owned), 16-bit engines: one set per form of the blocks' pointwise pair a batch can take
+    // (index: FfnForm::kind == FFN_K4), because the cached rows must carry the bits the batch's own kernels give
+    struct VoConsts {
+        float* quiet = nullptr;  // [base_chunk_size]
+        float* edge = nullptr;   // [rf][base_chunk_size]
+        float* tail = nullptr;   // [vo_blocks][rf + 1][vo_dim]: the residual stream at the input of block l, by distance to the end of the row
+    };
+    VoConsts vo_c_[2];
     int vo_rf_ = 0;
+    int vo_force_ffn_ = -1;          // prepare_vocoder_constants: the pointwise form vocoder_dev takes whatever the row count (-1: ffn_plan decides)
+    float* vo_capture_ = nullptr;    // prepare_vocoder_constants: where vocoder_dev copies the last rf + 1 rows of every block's input
+    void free_vocoder_constants();
+    enum VoForm : int { VO_DENSE = 0, VO_TRIM_2RF = 1, VO_TRIM_TAIL = 2 };
     int trimmed_rows(int B, int L, std::vector<int>* n_host) const;  // sum of the trimmed extents (0: trimming not applicable)
+    // the tail form, for the batches trimmed_rows leaves dense: every utterance on min(len*ccf + rf, T) frames, all of them exact, the blocks'
+    // conv taps beyond them read from VoConsts::tail.  Sum of the extents, 0 where the form does not apply or removes too little.
+    int tail_rows(int B, int L) const;
+    int vocoder_rows(int B, int L, int* form) const;  // trimmed_rows, else tail_rows; *form: the VoForm that gives the count
     long graph_replays_ = 0;
     int* pin_llen_ = nullptr; size_t pin_llen_cap_ = 0;   // pinned host staging read by the graph's memcpy node
     unsigned long long* pin_seed_ = nullptr;

@@ -213,7 +213,7 @@ void Engine::batch_run(int total_step, float speed, uint64_t noise_seed) {
     if (packed_rows_ok(B)) for (int v : b.h_llen) key.rows += v;
     if (shape_buckets_) key.rows = (int)bucket_up(key.rows, 64);
     last_ve_rows_ = key.rows ? key.rows : (int64_t)B * L;
-    key.vrows = trimmed_rows(B, L, nullptr);
+    key.vrows = vocoder_rows(B, L, &key.vform);  // (two forms with equal row counts must not share a capture)
     if (shape_buckets_) key.vrows = (int)bucket_up(key.vrows, 64 * a.chunk_compress_factor);
     key.trows = tpk ? b.trows : 0;
     last_vo_rows_ = (int64_t)B * L * a.chunk_compress_factor;
@@ -395,18 +395,19 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
     }
     int vrows = 0;
     const int* valid = nullptr;
+    bool tails = false;
     if (vo_ragged_ && packed_ve_) {
         for (int v : b.h_llen) vrows += v * a.chunk_compress_factor;
         if (shape_buckets_) vrows = (int)bucket_up(vrows, 64 * a.chunk_compress_factor);
-    } else if (int tr = trimmed_rows(B, L, nullptr)) {
+    } else if (int vform = VO_DENSE; int tr = vocoder_rows(B, L, &vform)) {
         if (shape_buckets_) tr = (int)bucket_up(tr, 64 * a.chunk_compress_factor);
         // reference (dense) semantics at the cost of the frames that are not position-independent
         int* n_dev = static_cast<int*>(ar_.alloc(sizeof(int) * B));
         int* v_dev = static_cast<int*>(ar_.alloc(sizeof(int) * B));
-        launch_trim_len(s_, b.llen, B, a.chunk_compress_factor, L * a.chunk_compress_factor, vo_rf_, n_dev, v_dev);
-        vlen = n_dev; valid = v_dev; vrows = tr;
+        launch_trim_len(s_, b.llen, B, a.chunk_compress_factor, L * a.chunk_compress_factor, vo_rf_, n_dev, v_dev, vform == VO_TRIM_TAIL);
+        vlen = n_dev; valid = v_dev; vrows = tr; tails = vform == VO_TRIM_TAIL;
     }
-    vocoder_dev(B, L, b.xt[cur], b.wav, vlen, vrows, valid);
+    vocoder_dev(B, L, b.xt[cur], b.wav, vlen, vrows, valid, tails);
     STN_HIP(hipGetLastError());  // a kernel launch that was rejected (bad configuration) must not pass silently
 }
 

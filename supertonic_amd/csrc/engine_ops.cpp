@@ -536,7 +536,7 @@ std::string Engine::op_ffn_ex(int M, int C, int I, const float* xn, int ldx, int
 
 std::string Engine::op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
                                     const float* bias, const float* g, const float* b, const int* seqlen, int packed, int ln_only, float* y,
-                                    int64_t y_rows) {
+                                    int64_t y_rows, const float* tail, int T, int rf) {
     STN_HIP(hipSetDevice(device_));
     ar_.reset();
     const int* dlen = seqlen ? up(ar_, s_, seqlen, (size_t)B) : nullptr;
@@ -557,8 +557,10 @@ std::string Engine::op_dwconv_ln_ex(int dtype, int B, int L, int C, int k, int d
             off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
             launch_row_map(s_, dlen, B, off, nullptr);
         }
+        DwconvTail tl;
+        if (tail) { tl.tail = up(ar_, s_, tail, (size_t)(rf + 1) * C); tl.T = T; tl.rf = rf; }
         form = dwconv_ln_form(dtype, B, L, C, k, packed != 0).str();  // the decision launch_dwconv_ln takes
-        launch_dwconv_ln(s_, dtype, dx, B, L, C, dw, db, k, dil, dg, dbt, 1e-6f, dy, dlen, off);
+        launch_dwconv_ln(s_, dtype, dx, B, L, C, dw, db, k, dil, dg, dbt, 1e-6f, dy, dlen, off, tl);
     }
     STN_HIP(hipGetLastError());
     down_as(ar_, s_, dtype, dy, y, (size_t)y_rows * C);

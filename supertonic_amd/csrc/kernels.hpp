@@ -259,12 +259,20 @@ void launch_ffn_pack(hipStream_t s, const void* W1, const void* W2, int C, int I
 // x fp32 [B*L][C] -> y act [B*L][C].  C % 4 == 0, C <= 1024.
 // seqlen (optional, [B]): frames at t >= seqlen[b] are treated as outside the sequence (zero taps, rows not written) — the
 // length-aware mode in which a padded batch reproduces what each sequence would give on its own
+// tl (packed rows only, optional): every sequence is the head of a row of tl.T >= L frames whose frames from seqlen[b] on are known without
+// being stored — a tap at tt >= seqlen[b] reads tl.tail[min(tl.T - 1 - tt, tl.rf)] (device, [tl.rf + 1][C] fp32, indexed by the distance to
+// the end of the row) and zero from tl.T on, instead of zero everywhere.  The same forms, in their tail-reading instantiation.
+struct DwconvTail {
+    const float* tail = nullptr;
+    int T = 0, rf = 0;
+};
 void launch_dwconv_ln(hipStream_t s, int out_dtype, const float* x, int B, int L, int C, const float* w_t,
                       const float* bias, int k, int dil, const float* ln_g, const float* ln_b, float eps, void* y,
-                      const int* seqlen = nullptr, const int* row_off = nullptr);
+                      const int* seqlen = nullptr, const int* row_off = nullptr, const DwconvTail& tl = DwconvTail());
 // The form a depthwise-conv + LayerNorm call takes — one decision, made by dwconv_ln_form and executed by launch_dwconv_ln, so that what
 // the diagnostics report (stn_dbg_dwconv_ln_form, stn_op_dwconv_ln_ex) is what runs:
-//   DW_V3       dwconv_ln_v3_kernel<OutT, K, R> (C <= 512, k in {5, 7}): combs of R frames; occ4: dwconv_ln_v3_occ4_kernel (k = 7, R = 4, not IEEE half)
+//   DW_V3       dwconv_ln_v3_kernel<OutT, K, R> (C <= 512, k in {5, 7}): combs of R frames; occ4: dwconv_ln_v3_occ4_kernel (k = 7, R = 4, not IEEE half);
+//               with a DwconvTail their tail-reading twins dwconv_ln_v3_tail_kernel / dwconv_ln_v3_tail_occ4_kernel (same form string)
 //   DW_V2       dwconv_ln_v2_kernel<OutT, K, 2> (padded rows, fewer than 4096 of them)
 //   DW_GENERIC  dwconv_ln_kernel<OutT, true> (C > 512 or another tap count; padded rows only)
 enum DwconvLnKernel : int { DW_V3 = 0, DW_V2 = 1, DW_GENERIC = 2 };
@@ -379,7 +387,7 @@ void launch_vocoder_im2col(hipStream_t s, int out_dtype, const float* latent, in
 // packed rows [sum len][W] -> padded [B][T][W], zeros past each sequence's length
 void launch_unpack_rows(hipStream_t s, const float* src, const int* len, const int* row_off, int B, int T, int W, float* dst);
 // exact trimmed dense vocoder (see kernels_layout.hip): extents per utterance, and the unpack that fills the position-independent tail
-void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out);
+void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out, bool tail_form = false);
 void launch_unpack_rows_quiet(hipStream_t s, const float* src, const int* valid, const int* row_off, int B, int T, int W, int rf,
                               const float* quiet, const float* edge, float* dst);
 // masked mean over valid rows: pooled[b][c] = sum_{t<len[b]} x[b*L+t][c] / max(len[b],1)   (x act dtype, out fp32)

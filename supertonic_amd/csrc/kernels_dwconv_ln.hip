@@ -185,12 +185,17 @@ __global__ __launch_bounds__(256) void dwconv_ln_v2_kernel(const float* __restri
 // registers as a sliding window — 1 + (K-1)/R loads per output instead of K, for ANY dilation.  Cuts the L2->CU traffic
 // of the vocoder's k=7 blocks by 4x at R=8 (HBM already saw each frame once; the re-reads were L2 bandwidth).
 // ---------------------------------------------------------------------------------------------
-template <typename OutT, int K, int R>
+// TAIL (packed rows only; the dense vocoder trimmed to one receptive field): sequence b is the head of a row of T frames whose frames from
+// seqlen[b] on are not stored because their value depends only on the distance to the end of the row.  A tap at tt >= seqlen[b] then reads
+// tail[min(T - 1 - tt, rf)] ([rf + 1][C] fp32; entry rf stands for every frame further from the end) and zero from T on; tt is wave-uniform,
+// so the choice is scalar address arithmetic.  The order of the tap FMAs and of the LayerNorm sums is the same in both variants.
+template <typename OutT, int K, int R, bool TAIL = false>
 __device__ __forceinline__ void dwconv_ln_v3_body(const float* __restrict__ x, int nseq, int L, int C,
                                                            const float* __restrict__ w_t, const float* __restrict__ bias,
                                                            int dil, int wps /*waves per sequence*/, const float* __restrict__ g,
                                                            const float* __restrict__ bt, float eps, OutT* __restrict__ y,
-                                                           const int* __restrict__ seqlen, const int* __restrict__ row_off, int xcd_runs) {
+                                                           const int* __restrict__ seqlen, const int* __restrict__ row_off, int xcd_runs,
+                                                           const float* __restrict__ tail = nullptr, int T = 0, int rf = 0) {
     const int lane = threadIdx.x & 63;
     // Workgroups are dealt to the 8 XCDs round-robin, and each XCD has its own L2: with the plain order the two workgroups that share a halo
     // (neighbours in time) sit on different XCDs and both fetch it over the fabric.  Give each XCD one contiguous run of tiles instead.
@@ -237,9 +242,21 @@ __device__ __forceinline__ void dwconv_ln_v3_body(const float* __restrict__ x, i
             const int tt = t0 + (q - HALF) * dil;
             const int hi_ = row_off ? Lv : L;  // clamp inside the rows this sequence owns
             const int tc = tt < 0 ? 0 : (tt >= hi_ ? hi_ - 1 : tt);
-            const float4 v = x4[(int64_t)tc * C4 + cc];
-            // a select, not a product with 0: what the clamped load fetched from a padding row may be a NaN or an infinity
-            win[q] = (tt >= 0 && tt < Lv) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (TAIL) {
+                const float4* src = x4 + (int64_t)tc * C4;
+                bool keep = tt >= 0 && tt < Lv;
+                if (tt >= Lv && tt < T) {  // wave-uniform: a frame of the row's position-dependent tail
+                    const int j = T - 1 - tt;
+                    src = reinterpret_cast<const float4*>(tail) + (int64_t)(j < rf ? j : rf) * C4;
+                    keep = true;
+                }
+                const float4 v = src[cc];
+                win[q] = keep ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                const float4 v = x4[(int64_t)tc * C4 + cc];
+                // a select, not a product with 0: what the clamped load fetched from a padding row may be a NaN or an infinity
+                win[q] = (tt >= 0 && tt < Lv) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
         }
         const float4 bv = b4[cc];
 #pragma unroll
@@ -309,12 +326,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     dwconv_ln_v3_body<OutT, K, R>(x, nseq, L, C, w_t, bias, dil, wps, g, bt, eps, y, seqlen, row_off, xcd_runs);
 }
 
+// the tail-reading variants (packed rows), plain and held to four waves per SIMD like the two above
+template <typename OutT, int K, int R>
+__global__ __launch_bounds__(256) void dwconv_ln_v3_tail_kernel(const float* __restrict__ x, int nseq, int L, int C, const float* __restrict__ w_t,
+                                                                const float* __restrict__ bias, int dil, int wps, const float* __restrict__ g,
+                                                                const float* __restrict__ bt, float eps, OutT* __restrict__ y,
+                                                                const int* __restrict__ seqlen, const int* __restrict__ row_off, int xcd_runs,
+                                                                const float* __restrict__ tail, int T, int rf) {
+    dwconv_ln_v3_body<OutT, K, R, true>(x, nseq, L, C, w_t, bias, dil, wps, g, bt, eps, y, seqlen, row_off, xcd_runs, tail, T, rf);
+}
+template <typename OutT, int K, int R>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void dwconv_ln_v3_tail_occ4_kernel(
+    const float* __restrict__ x, int nseq, int L, int C, const float* __restrict__ w_t, const float* __restrict__ bias, int dil, int wps,
+    const float* __restrict__ g, const float* __restrict__ bt, float eps, OutT* __restrict__ y, const int* __restrict__ seqlen,
+    const int* __restrict__ row_off, int xcd_runs, const float* __restrict__ tail, int T, int rf) {
+    dwconv_ln_v3_body<OutT, K, R, true>(x, nseq, L, C, w_t, bias, dil, wps, g, bt, eps, y, seqlen, row_off, xcd_runs, tail, T, rf);
+}
+
 template <typename OutT, int K, int R>
 static void launch_dwconv_ln_v3_kr(hipStream_t s, bool occ4, const float* x, int nseq, int L, int C, const float* w_t, const float* bias,
-                                   int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
+                                   int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off,
+                                   const DwconvTail& tl) {
     const int wps = ((L + R * dil - 1) / (R * dil)) * dil;
     const int64_t nw = (int64_t)nseq * wps;
     static const int xcd_runs = [] { const char* e = stn::dev_env("STN_DWCONV_XCD"); return e ? atoi(e) : 1; }();  // A/B switch
+    if (tl.tail) {
+        if constexpr (K == 7 && R == 4 && !std::is_same<OutT, f16_t>::value) {
+            if (occ4) {
+                STN_KLAUNCH((dwconv_ln_v3_tail_occ4_kernel<OutT, K, R>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, x, nseq, L, C, w_t, bias,
+                                   dil, wps, g, b, eps, y, seqlen, row_off, xcd_runs, tl.tail, tl.T, tl.rf);
+                return;
+            }
+        }
+        if (occ4) throw std::logic_error("dwconv_ln: no occ4 kernel for this form");
+        STN_KLAUNCH((dwconv_ln_v3_tail_kernel<OutT, K, R>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, x, nseq, L, C, w_t, bias,
+                           dil, wps, g, b, eps, y, seqlen, row_off, xcd_runs, tl.tail, tl.T, tl.rf);
+        return;
+    }
     // (the occ4 kernel exists where dwconv_ln_form can choose it: the IEEE-half instantiation would need 184 VGPRs and spill)
     if constexpr (K == 7 && R == 4 && !std::is_same<OutT, f16_t>::value) {
         if (occ4) {
@@ -375,13 +423,14 @@ DwconvLnForm dwconv_ln_form(int out_dtype, int B, int L, int C, int k, bool pack
 
 template <typename OutT>
 static void launch_dwconv_ln_t(hipStream_t s, const DwconvLnForm& f, const float* x, int B, int L, int C, const float* w_t, const float* bias,
-                               int k, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off) {
+                               int k, int dil, const float* g, const float* b, float eps, OutT* y, const int* seqlen, const int* row_off,
+                               const DwconvTail& tl) {
     const int64_t M = (int64_t)B * L;
     if (f.kernel == DW_V3) {
-        if (f.K == 5 && f.R == 2) launch_dwconv_ln_v3_kr<OutT, 5, 2>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else if (f.K == 5 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 5, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else if (f.K == 5 && f.R == 8) launch_dwconv_ln_v3_kr<OutT, 5, 8>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
-        else if (f.K == 7 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off);
+        if (f.K == 5 && f.R == 2) launch_dwconv_ln_v3_kr<OutT, 5, 2>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off, tl);
+        else if (f.K == 5 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 5, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off, tl);
+        else if (f.K == 5 && f.R == 8) launch_dwconv_ln_v3_kr<OutT, 5, 8>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off, tl);
+        else if (f.K == 7 && f.R == 4) launch_dwconv_ln_v3_kr<OutT, 7, 4>(s, f.occ4, x, B, L, C, w_t, bias, dil, g, b, eps, y, seqlen, row_off, tl);
         else throw std::logic_error("dwconv_ln: no v3 kernel for form " + f.str());
     } else if (f.kernel == DW_V2) {
         constexpr int R = 2;
@@ -397,14 +446,15 @@ static void launch_dwconv_ln_t(hipStream_t s, const DwconvLnForm& f, const float
 
 void launch_dwconv_ln(hipStream_t s, int out_dtype, const float* x, int B, int L, int C, const float* w_t,
                       const float* bias, int k, int dil, const float* ln_g, const float* ln_b, float eps, void* y,
-                      const int* seqlen, const int* row_off) {
+                      const int* seqlen, const int* row_off, const DwconvTail& tl) {
     check_ln_shape(C);
     if ((int64_t)B * L == 0) return;
     if (row_off && !seqlen) { throw std::invalid_argument("packed dwconv_ln needs lengths, C <= 512, k in {5,7}"); }
+    if (tl.tail && (!row_off || tl.T < L || tl.rf < 0)) { throw std::invalid_argument("dwconv_ln: a tail table needs packed rows, T >= L and rf >= 0"); }
     const DwconvLnForm f = dwconv_ln_form(out_dtype, B, L, C, k, row_off != nullptr);  // the one place the thresholds live
     with_out_type(f.out_dtype, [&](auto* tag) {
         using T = std::remove_pointer_t<decltype(tag)>;
-        launch_dwconv_ln_t(s, f, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<T*>(y), seqlen, row_off);
+        launch_dwconv_ln_t(s, f, x, B, L, C, w_t, bias, k, dil, ln_g, ln_b, eps, static_cast<T*>(y), seqlen, row_off, tl);
     });
 }
 

@@ -469,43 +469,65 @@ void launch_scale_len(hipStream_t s, const int* len, int B, int factor, int* out
 // Extents of the exact "trimmed" dense vocoder: an utterance whose zero-latent padding is longer than twice the receptive
 // field rf is computed on len*ccf + 2*rf frames (zero beyond), which is exact on its first len*ccf + rf output frames; the rest
 // of its row is position-independent (quiet chunk + edge tail, see Engine::prepare_vocoder_constants).
-__global__ void trim_len_kernel(const int* __restrict__ len, int B, int ccf, int T, int rf, int* __restrict__ n_out,
+// tail_form: every utterance is computed on its first min(len*ccf + rf, T) frames, all of them exact, because the convolutions read the
+// frames beyond from the cached per-layer tails instead of zeros (DwconvTail).
+__global__ void trim_len_kernel(const int* __restrict__ len, int B, int ccf, int T, int rf, int tail_form, int* __restrict__ n_out,
                                 int* __restrict__ valid_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B) return;
     const int l6 = len[i] * ccf;
+    if (tail_form) {
+        n_out[i] = valid_out[i] = l6 + rf < T ? l6 + rf : T;
+        return;
+    }
     const bool trim = l6 + 2 * rf <= T;  // the edge tail's whole receptive field [T - 2rf, T) is zero latent (quiet part may be empty)
     n_out[i] = trim ? l6 + 2 * rf : T;
     valid_out[i] = trim ? l6 + rf : T;
 }
-void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out) {
+void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out, bool tail_form) {
     if (B == 0) return;
-    STN_KLAUNCH(trim_len_kernel, dim3((B + 255) / 256), dim3(256), 0, s, len, B, ccf, T, rf, n_out, valid_out);
+    STN_KLAUNCH(trim_len_kernel, dim3((B + 255) / 256), dim3(256), 0, s, len, B, ccf, T, rf, tail_form ? 1 : 0, n_out, valid_out);
 }
 
-// packed rows -> padded [B][T][W]: computed frames below valid[b], then the quiet chunk, then the edge tail of rf frames
-__global__ void unpack_rows_quiet_kernel(const float* __restrict__ src, const int* __restrict__ valid, const int* __restrict__ row_off,
-                                         int T, int W4, int rf, const float* __restrict__ quiet, const float* __restrict__ edge,
-                                         int64_t n4, float* __restrict__ dst) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // over [B][T][W/4]
-    if (i >= n4) return;
-    const int c = (int)(i % W4);
-    const int64_t r = i / W4;
-    const int t = (int)(r % T);
-    const int b = (int)(r / T);
-    float4 v;
-    if (t < valid[b]) v = reinterpret_cast<const float4*>(src)[((int64_t)row_off[b] + t) * W4 + c];
-    else if (t >= T - rf) v = reinterpret_cast<const float4*>(edge)[(int64_t)(t - (T - rf)) * W4 + c];
-    else v = reinterpret_cast<const float4*>(quiet)[c];
-    reinterpret_cast<float4*>(dst)[i] = v;
+// packed rows -> padded [B][T][W]: computed frames below valid[b], then the quiet chunk, then the edge tail of rf frames.
+// A wavefront moves UNPACK_RW whole rows: where a row comes from is decided once per row (wave-uniform), and every 16-byte load of the rows is
+// issued before the first store — the pass is a copy of the whole waveform and should cost what its bytes cost (one thread per 16 bytes with
+// three run-time divisions each took 58 us for the 226 MB of a batch of 128, 3.9 TB/s).
+constexpr int UNPACK_RW = 4;
+__global__ __launch_bounds__(256) void unpack_rows_quiet_kernel(const float* __restrict__ src, const int* __restrict__ valid,
+                                                                const int* __restrict__ row_off, int T, int W4, int rf,
+                                                                const float* __restrict__ quiet, const float* __restrict__ edge, int64_t nrows,
+                                                                float* __restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * UNPACK_RW;  // over [B][T]
+    if (r0 >= nrows) return;
+    const float4* sp[UNPACK_RW];
+#pragma unroll
+    for (int i = 0; i < UNPACK_RW; ++i) {
+        const int64_t r = r0 + i < nrows ? r0 + i : nrows - 1;
+        const int b = (int)(r / T), t = (int)(r - (int64_t)b * T);
+        if (t < valid[b]) sp[i] = reinterpret_cast<const float4*>(src) + ((int64_t)row_off[b] + t) * W4;
+        else if (t >= T - rf) sp[i] = reinterpret_cast<const float4*>(edge) + (int64_t)(t - (T - rf)) * W4;
+        else sp[i] = reinterpret_cast<const float4*>(quiet);
+    }
+    float4* d4 = reinterpret_cast<float4*>(dst) + r0 * W4;
+    for (int c = lane; c < W4; c += 64) {
+        float4 v[UNPACK_RW];
+#pragma unroll
+        for (int i = 0; i < UNPACK_RW; ++i) v[i] = sp[i][c];
+#pragma unroll
+        for (int i = 0; i < UNPACK_RW; ++i)
+            if (r0 + i < nrows) d4[(int64_t)i * W4 + c] = v[i];
+    }
 }
 void launch_unpack_rows_quiet(hipStream_t s, const float* src, const int* valid, const int* row_off, int B, int T, int W, int rf,
                               const float* quiet, const float* edge, float* dst) {
-    const int64_t n4 = (int64_t)B * T * (W / 4);
-    if (n4 == 0) return;
+    const int64_t nrows = (int64_t)B * T;
+    if (nrows == 0 || W == 0) return;
     if (W % 4) { throw std::invalid_argument("unpack_rows needs W % 4 == 0"); }
-    STN_KLAUNCH(unpack_rows_quiet_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, src, valid, row_off, T, W / 4, rf, quiet, edge,
-                n4, dst);
+    STN_KLAUNCH(unpack_rows_quiet_kernel, dim3((unsigned)((nrows + 4 * UNPACK_RW - 1) / (4 * UNPACK_RW))), dim3(256), 0, s, src, valid, row_off, T,
+                W / 4, rf, quiet, edge, nrows, dst);
 }
 
 __global__ void mask_ncl_kernel(float* __restrict__ x, int D, int L, int64_t n, const int* __restrict__ len) {
