@@ -1029,6 +1029,13 @@ int stn_op_dwconv_ln(stn_handle* h, int dtype, int B, int L, int C, int k, int d
 int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x,
                             const float* w /*[C,k]*/, const float* bias, const float* ln_g, const float* ln_b,
                             const int32_t* seqlen /*[B], 0..L*/, float* y);
+/* One GEMM out = A W^T + bias (fp32 out) whose M rows are packed per sequence, stored through the slab epilogue's packed-row destination map (the
+ * vocoder head): sequence b owns rows[b] consecutive rows of A (rows past their sum, up to M, are dead); row t of sequence b is stored at row
+ * b*T + t of out [B,T,N] when t < valid[b] (0 <= valid[b] <= rows[b] <= T) and nowhere otherwise.  out: the caller's whole buffer of out_elems
+ * >= B*T*N floats, uploaded as given and written back whole.  Each stored row has the bits stn_op_gemm_ex's plain store gives that row.
+ * STN_ERR_INVALID for operands whose GEMM form has no slab epilogue (N % 8).  form as stn_op_gemm_ex. */
+int stn_op_gemm_rows(stn_handle* h, int dtype, int M, int N, int K, const float* A, const float* W, const float* bias_or_null, int B,
+                     const int32_t* rows, const int32_t* valid, int T, float* out, int64_t out_elems, char* form, size_t form_cap);
 /* The same launcher on the caller's whole buffers (the kernel parity tests of every dwconv + LayerNorm form).  x: x_rows rows of C, uploaded as
  * given, padding rows included.  packed = 0: sequence b owns rows b*L .. b*L + L of x / y (seqlen optional; x_rows, y_rows >= B*L); packed != 0:
  * seqlen[b] consecutive rows in order (needs seqlen; B <= 1024; x_rows, y_rows >= their sum), L >= every length.  ln_only != 0: plain
@@ -1045,6 +1052,14 @@ int stn_op_dwconv_ln_ex(stn_handle* h, int dtype, int B, int L, int C, int k, in
 int stn_op_dwconv_ln_tail(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows,
                           const float* w /*[C,k]*/, const float* bias, const float* ln_g, const float* ln_b, const int32_t* seqlen,
                           const float* tail /*[rf+1,C]*/, int T, int rf, float* y, int64_t y_rows, char* form, size_t form_cap);
+/* diagnostics (no device needed): the length tables a batch run uploads in front of its pipeline (csrc/host/len_tables.hpp), built on the host
+ * from the B latent lengths alone.  ve_rows: the estimator's packed row count with its dead rows (>= sum llen; 0: no row map); with_pairs:
+ * the head-split cross-attention's pairing (needs ve_rows > 0); vo_form: 0 none, 1 / 2 the dense vocoder's trim extents (trim_len_kernel,
+ * tail_form 0 / 1), 3 lengths scaled by ccf; T: vocoder frames of a padded row; rf: the vocoder's receptive field.  layout (9 words, may be
+ * NULL): word offsets of seed, llen, ve_off [B+1], ve_row_b [ve_rows], pairs [B+2], vo_n [B], vo_valid [B], vo_off [B+1] (-1: not built) and
+ * the total.  out (may be NULL; out_n >= total words): the block, the two seed words left as they are.  Returns the total, < 0 on a bad call. */
+int64_t stn_dbg_len_tables(int B, const int32_t* llen, int ve_rows, int with_pairs, int vo_form, int ccf, int T, int rf, int32_t* layout,
+                           int32_t* out, int64_t out_n);
 /* diagnostics (no device needed): the form the engine's depthwise-conv + LayerNorm launcher takes for B sequences of L rows, C channels,
  * k taps, output format dtype, padded or packed rows: "v3<K,R>" (combs of R frames), "v3occ4<7,4>" (the same held to four waves per SIMD),
  * "v2<K>" or "generic".  Returns the string's length (written with its NUL when it fits in cap), < 0 on a call the launcher refuses
@@ -1065,6 +1080,10 @@ int stn_op_fold_ln(stn_handle* h, int dtype, int M, int C, int S, const float* p
  *   5 masked_mean     p = {B, L, C}; a: rows of C (rounded to dtype); len [B]; out [B,C]
  *   6 vocoder_im2col  p = {B, L, ld, ccf, k, kp}; a = latent [B, ld*ccf, L]; len = valid vocoder frames (<= L*ccf) or NULL; out: rows of kp in dtype
  *   7 vocoder_in      p = {B, L, ld, ccf, C, k}; a = latent, b = weights [ld*k, C], c = bias [C]; len as above; out [B*L*ccf, C]
+ *   8 fill_rows       p = {B, T, W, rf, zeros}; len = valid [B]; out [B,T,W]: only rows t >= valid[b] are written — zeros != 0: with zeros; else
+ *                     a = quiet [W], b = edge [rf,W]: edge[t - (T - rf)] for t >= T - rf, quiet otherwise (what unpack_rows' dense twin writes there)
+ *   9 hs_pairs        p = {B}; len [B]; iout: the head-split cross-attention's pairing, 2 * ceil(B/2) words
+ *  10 trim_len        p = {B, ccf, T, rf, tail_form}; len [B] latent lengths (<= T / ccf); iout = n [B] followed by valid [B]
  * packed != 0 (1, 2, 4, 5, 6): the rows (for 2: the velocity and z rows) are packed per sequence, len[b] each, and need len; else sequence b
  * owns L (T, L*ccf) rows.  out / out2 / iout are the caller's whole buffers of out_n / out2_n / iout_n elements: uploaded as given (out of 1
  * and 6, out2 of 2: rounded to dtype) and written back whole, so what a kernel must not touch can be checked.  Buffers too small for the

@@ -19,6 +19,7 @@ EPI_STORE, EPI_RESID, EPI_STORE_T = 0, 1, 2  # GEMM epilogue modes (stn_op_gemm_
 FFN_VOCODER, FFN_ESTIMATOR, FFN_TEXT = 1, 2, 4  # ConvNeXt stages (ffn_form)
 # kernels of stn_op_layout
 LAYOUT_ROW_MAP, LAYOUT_NCL_TO_ROWS, LAYOUT_EULER_NCL, LAYOUT_UNPACK_ROWS, LAYOUT_EMBED, LAYOUT_MASKED_MEAN, LAYOUT_IM2COL, LAYOUT_VOCODER_IN = range(8)
+LAYOUT_FILL_ROWS, LAYOUT_HS_PAIRS, LAYOUT_TRIM_LEN = 8, 9, 10
 # sample encodings of a fetch (STN_ENC_*, include/stn.h)
 ENC_F32, ENC_PCM16, ENC_PCM24, ENC_MULAW, ENC_ALAW = 0, 1, 2, 3, 4
 ENCODINGS = {"f32": ENC_F32, "pcm16": ENC_PCM16, "pcm24": ENC_PCM24, "mulaw": ENC_MULAW, "alaw": ENC_ALAW}
@@ -650,6 +651,7 @@ def load():
     L.stn_op_dwconv_ln.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.stn_op_dwconv_ln_ragged.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p]
     L.stn_op_attention.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p]
+    L.stn_op_gemm_rows.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, vp, ci, _i32p, _i32p, ci, _f32p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_dwconv_ln_ex.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, vp, vp, _f32p, _f32p, vp, ci, ci, _f32p, ctypes.c_int64,
                                       ctypes.c_char_p, ctypes.c_size_t]
     L.stn_op_dwconv_ln_tail.argtypes = [vp, ci, ci, ci, ci, ci, ci, _f32p, ctypes.c_int64, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p, ci, ci, _f32p,
@@ -658,6 +660,8 @@ def load():
     L.stn_dbg_resample_form.restype = ctypes.c_int
     L.stn_dbg_dwconv_ln_form.argtypes = [ci, ci, ci, ci, ci, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.stn_dbg_dwconv_ln_form.restype = ctypes.c_int
+    L.stn_dbg_len_tables.argtypes = [ci, _i32p, ci, ci, ci, ci, ci, ci, _i32p, ctypes.c_void_p, ctypes.c_int64]
+    L.stn_dbg_len_tables.restype = ctypes.c_int64
     L.stn_op_fold_ln.argtypes = [vp, ci, ci, ci, ci, _f32p, _f32p, _f32p, vp, vp, ci, _f32p, _f32p, _f32p, _f32p]
     L.stn_op_layout.argtypes = [vp, ci, ci, _i32p, ci, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci,
                                 vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64]
@@ -1320,6 +1324,32 @@ def dwconv_ln_form(dtype, B, L, C, k, packed=False):
     if r < 0:
         raise StnError(r, "stn_dbg_dwconv_ln_form: the launcher refuses this call")
     return buf.value.decode()
+
+
+LEN_VO_NONE, LEN_VO_2RF, LEN_VO_TAIL, LEN_VO_SCALED = range(4)
+
+
+def len_tables(llen, ve_rows=0, with_pairs=False, vo_form=LEN_VO_NONE, ccf=6, T=0, rf=0):
+    """The length tables a batch run uploads in front of its pipeline, built on the host (stn_dbg_len_tables; no device).  Returns a dict of
+    int32 arrays: llen, and where built ve_off [B+1], ve_row_b [ve_rows], pairs [B+2], vo_n, vo_valid [B], vo_off [B+1]; 'total' (words)."""
+    llen = _c(llen, np.int32)
+    B = len(llen)
+    lay = np.zeros(9, np.int32)
+    args = (B, llen, int(ve_rows), int(bool(with_pairs)), int(vo_form), int(ccf), int(T), int(rf))
+    tot = load().stn_dbg_len_tables(*args, lay, None, 0)
+    if tot < 0:
+        raise StnError(int(tot), "stn_dbg_len_tables: bad argument")
+    out = np.full(tot, -12345, np.int32)
+    out[:2] = 7
+    assert load().stn_dbg_len_tables(*args, lay, out.ctypes.data, out.size) == tot
+    assert out[0] == 7 and out[1] == 7  # the seed words are the caller's
+    names = ("seed", "llen", "ve_off", "ve_row_b", "pairs", "vo_n", "vo_valid", "vo_off")
+    sizes = {"llen": B, "ve_off": B + 1, "ve_row_b": int(ve_rows), "pairs": B + 2, "vo_n": B, "vo_valid": B, "vo_off": B + 1}
+    res = {"total": int(tot)}
+    for i, n in enumerate(names):
+        if n != "seed" and lay[i] >= 0:
+            res[n] = out[lay[i]:lay[i] + sizes[n]].copy()
+    return res
 
 
 def fold_dwconv_ln_form(dtype, B, L, C, k, dil, S, rowvec=True, run_frames=0):
@@ -2465,6 +2495,21 @@ class Engine:
                                             _c(x, np.float32), _c(w, np.float32), _c(bias, np.float32),
                                             _c(g, np.float32), _c(b, np.float32), y))
         return y
+
+    def op_gemm_rows(self, A, W, out, rows, valid, T, bias=None, dtype=None):
+        """One GEMM whose packed rows are stored through the destination map (stn_op_gemm_rows).  A [M, K], W [N, K]; sequence b owns rows[b]
+        consecutive rows of A; out: the whole [B, T, N] destination (plus any guard), uploaded as given.  Returns (out as a new fp32 array, form)."""
+        A = _c(A, np.float32)
+        W = _c(W, np.float32)
+        rows = _c(rows, np.int32)
+        valid = _c(valid, np.int32)
+        o_r = np.array(out, dtype=np.float32, order="C", copy=True)
+        _b, bp = _opt(bias, np.float32)
+        form = ctypes.create_string_buffer(96)
+        self._ck(self._lib.stn_op_gemm_rows(self._h, self.dtype if dtype is None else _DTYPES[dtype], A.shape[0], W.shape[0], A.shape[1],
+                                            A.reshape(-1), W.reshape(-1), bp, len(rows), rows, valid, int(T), o_r.reshape(-1), o_r.size, form,
+                                            ctypes.sizeof(form)))
+        return o_r, form.value.decode()
 
     def op_dwconv_ln_ex(self, x, w, bias, g, b, dil, out, B, L, seqlen=None, packed=False, ln_only=False, dtype=None):
         """launch_dwconv_ln (ln_only: launch_layernorm over B*L rows) on whole buffers (stn_op_dwconv_ln_ex).  x, out: 2-D [rows, C], x

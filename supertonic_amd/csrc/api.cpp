@@ -947,6 +947,24 @@ int stn_op_dwconv_ln_ragged(stn_handle* h, int dtype, int B, int L, int C, int k
                  for (int i = 0; i < B; ++i) need(seqlen[i] >= 0 && seqlen[i] <= L, "stn_op_dwconv_ln_ragged: seqlen out of [0, L]");
                  h->eng->op_dwconv_ln(dtype, B, L, C, k, dil, x, w, bias, g, b, y, seqlen); })
 }
+static void gemm_rows_checked(stn_handle* h, int dtype, int M, int N, int K, const float* A, const float* W, const float* bias, int B,
+                              const int32_t* rows, const int32_t* valid, int T, float* out, int64_t out_elems, char* form, size_t form_cap) {
+    need(M > 0 && N > 0 && K > 0 && A && W && out && rows && valid && B > 0 && B <= 1024 && T > 0, "stn_op_gemm_rows: bad argument");
+    need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_gemm_rows: unknown dtype");
+    need(K % (dtype != STN_DTYPE_F32 ? 8 : 4) == 0, "stn_op_gemm_rows: K must be a multiple of 8 (16-bit) / 4 (f32)");
+    int64_t tot = 0;
+    for (int b = 0; b < B; ++b) {
+        need(rows[b] >= 0 && rows[b] <= T && valid[b] >= 0 && valid[b] <= rows[b], "stn_op_gemm_rows: needs 0 <= valid[b] <= rows[b] <= T");
+        tot += rows[b];
+    }
+    need(tot <= M && out_elems >= (int64_t)B * T * N, "stn_op_gemm_rows: needs sum rows <= M and out_elems >= B*T*N");
+    const std::string f = h->eng->op_gemm_rows(dtype, M, N, K, A, W, bias, B, rows, valid, T, out, out_elems);
+    if (form && form_cap) std::snprintf(form, form_cap, "%s", f.c_str());
+}
+int stn_op_gemm_rows(stn_handle* h, int dtype, int M, int N, int K, const float* A, const float* W, const float* bias, int B, const int32_t* rows,
+                     const int32_t* valid, int T, float* out, int64_t out_elems, char* form, size_t form_cap) {
+    STN_TRY(h, gemm_rows_checked(h, dtype, M, N, K, A, W, bias, B, rows, valid, T, out, out_elems, form, form_cap))
+}
 static void dwconv_ln_ex_checked(stn_handle* h, int dtype, int B, int L, int C, int k, int dil, const float* x, int64_t x_rows, const float* w,
                                  const float* bias, const float* g, const float* b, const int32_t* seqlen, int packed, int ln_only, float* y,
                                  int64_t y_rows, char* form, size_t form_cap) {
@@ -990,6 +1008,27 @@ int stn_op_dwconv_ln_tail(stn_handle* h, int dtype, int B, int L, int C, int k, 
                           int64_t y_rows, char* form, size_t form_cap) {
     STN_TRY(h, dwconv_ln_tail_checked(h, dtype, B, L, C, k, dil, x, x_rows, w, bias, g, b, seqlen, tail, T, rf, y, y_rows, form, form_cap))
 }
+int64_t stn_dbg_len_tables(int B, const int32_t* llen, int ve_rows, int with_pairs, int vo_form, int ccf, int T, int rf, int32_t* layout,
+                           int32_t* out, int64_t out_n) {
+    if (B < 1 || B > 1024 || !llen || ve_rows < 0 || vo_form < stn::LEN_VO_NONE || vo_form > stn::LEN_VO_SCALED || ccf < 1 || T < 0 || rf < 0) return STN_ERR_INVALID;
+    int64_t tot = 0;
+    for (int b = 0; b < B; ++b) {
+        if (llen[b] < 0 || llen[b] > (1 << 20)) return STN_ERR_INVALID;
+        tot += llen[b];
+    }
+    if (ve_rows > 0 && tot > ve_rows) return STN_ERR_INVALID;
+    if (with_pairs && ve_rows == 0) return STN_ERR_INVALID;
+    const stn::LenTables t = stn::len_tables_layout(B, ve_rows, with_pairs != 0, vo_form);
+    if (layout) {
+        const int v[9] = {t.seed, t.llen, t.ve_off, t.ve_row_b, t.pairs, t.vo_n, t.vo_valid, t.vo_off, t.total};
+        std::memcpy(layout, v, sizeof v);
+    }
+    if (out) {
+        if (out_n < t.total) return STN_ERR_INVALID;
+        stn::len_tables_build(t, llen, B, ve_rows, with_pairs != 0, vo_form, ccf, T, rf, out);
+    }
+    return t.total;
+}
 int stn_dbg_dwconv_ln_form(int dtype, int B, int L, int C, int k, int packed, char* out, size_t cap) {
     if (B < 1 || L < 1 || C < 1 || k < 1 || !(k & 1) || (dtype != STN_DTYPE_F32 && dtype != STN_DTYPE_BF16 && dtype != STN_DTYPE_F16)) return STN_ERR_INVALID;
     std::string f;
@@ -1009,8 +1048,8 @@ int stn_op_fold_ln(stn_handle* h, int dtype, int M, int C, int S, const float* p
 int stn_op_layout(stn_handle* h, int which, int dtype, const int32_t* p, int n_p, const float* a, int64_t a_n, const float* b, int64_t b_n,
                   const float* c, int64_t c_n, const int64_t* ids, int64_t ids_n, const int32_t* len, int packed, float* out, int64_t out_n,
                   float* out2, int64_t out2_n, int32_t* iout, int64_t iout_n) {
-    static const int n_params[8] = {3, 4, 5, 3, 4, 3, 6, 6};
-    STN_TRY(h, { need(which >= 0 && which < 8 && p && n_p == n_params[which], "stn_op_layout: unknown kernel or parameter count");
+    static const int n_params[11] = {3, 4, 5, 3, 4, 3, 6, 6, 5, 1, 5};
+    STN_TRY(h, { need(which >= 0 && which < 11 && p && n_p == n_params[which], "stn_op_layout: unknown kernel or parameter count");
                  need(dtype == STN_DTYPE_F32 || dtype == STN_DTYPE_BF16 || dtype == STN_DTYPE_F16, "stn_op_layout: unknown dtype");
                  need(a_n >= 0 && b_n >= 0 && c_n >= 0 && ids_n >= 0 && out_n >= 0 && out2_n >= 0 && iout_n >= 0 && (a || !a_n) && (b || !b_n) && (c || !c_n) &&
                           (ids || !ids_n) && (out || !out_n) && (out2 || !out2_n) && (iout || !iout_n),

@@ -176,9 +176,7 @@ Engine::~Engine() {
     for (auto& sp : spans_) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
     drop_graphs();
-    if (pin_llen_) (void)hipHostFree(pin_llen_);
-    if (pin_seed_) (void)hipHostFree(pin_seed_);
-    if (seed_dev_) (void)hipFree(seed_dev_);
+    if (pin_tab_) (void)hipHostFree(pin_tab_);
     rs_release();
     fl_release();
     xp_release();
@@ -829,7 +827,11 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
     const int Dp = (D + 63) / 64 * 64;
     // the latent as rows for the input projection: the caller's persistent buffer when the step before left it there (euler_ncl writes both layouts)
     void* z = z_rows ? z_rows : act_alloc(M * Dp);
-    if (!(z_rows && z_ready)) launch_ncl_to_rows(s_, dt_, noisy, B, D, L, z, Dp, llen, roff);
+    if (!(z_rows && z_ready)) {
+        if (prof_on_) prof_begin("ncl_to_rows", 0.0, (double)B * D * L * 4.0 + (double)M * Dp * esz);
+        launch_ncl_to_rows(s_, dt_, noisy, B, D, L, z, Dp, llen, roff);
+        if (prof_on_) prof_end();
+    }
     // one form for every ConvNeXt block of the stage (same C, I, k and rows)
     const FfnForm ff = ffn_plan(FFN_ESTIMATOR, C, a.ve_hidden, M, 0, rg != nullptr, a.ve_kernel, 1 << std::max(0, a.ve_dilated - 1));
     const bool split = ff.kind == FFN_K4_SPLIT;
@@ -925,7 +927,9 @@ void Engine::ve_step_dev(int B, int L, const VeCtx& c, const float* noisy, const
     float* vel = f32_alloc(M * D);
     Epilogue eo; eo.mode = EPI_STORE; eo.out_dtype = F32; eo.out = vel; eo.ldo = D;
     gemm("gemm_out", dt_, xn, C, linear("ve.out"), (int)M, eo);
+    if (prof_on_) prof_begin("euler", 2.0 * M * D, (double)M * D * 4.0 + (double)B * D * L * 8.0 + ((z_rows && z_next) ? (double)M * Dp * esz : 0.0));
     launch_euler_ncl(s_, noisy, vel, dtv, llen, B, D, L, denoised, roff, (z_rows && z_next) ? z_rows : nullptr, dt_, Dp);
+    if (prof_on_) prof_end();
     ar_.release(mk);
 }
 
@@ -1124,7 +1128,7 @@ int Engine::vocoder_rows(int B, int L, int* form) const {
 // zero latent, which the convolutions see as signal).  vlen != nullptr (length-aware): convolution taps beyond an
 // utterance's own length read as the zero padding of a batch-of-one run, so wav[b, :vlen[b]*hop] equals what
 // synthesizing utterance b alone gives; samples past that are written as zeros.
-void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen, int vrows, const int* valid, bool tails) {
+void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen, int vrows, const int* valid, bool tails, const int* voff) {
     stage_ = "vo";
     const stn_arch& a = a_;
     const int C = a.vo_dim, T = L * a.chunk_compress_factor;
@@ -1135,9 +1139,13 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
     const int64_t M = packed ? (int64_t)vrows : (int64_t)B * T;
     const Arena::Mark mk = ar_.mark();
     Ragged rg;
-    if (packed) {
+    if (packed && voff) {
+        rg.off = voff; rg.rows = vrows;
+    } else if (packed) {
         int* off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+        if (prof_on_) prof_begin("row_map", 0.0, (double)(2 * B + 1) * 4.0);
         launch_row_map(s_, vlen, B, off, nullptr);
+        if (prof_on_) prof_end();
         rg.off = off; rg.rows = vrows;
     }
     const Ragged* rgp = packed ? &rg : nullptr;
@@ -1146,8 +1154,10 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
         // input conv on the MFMA path: im2col (K = ld*k padded to 64) + GEMM; ~10x the direct fp32 VALU kernel
         const int kp = (a.latent_dim * a.vo_in_kernel + 63) / 64 * 64;
         void* cols = act_alloc(M * kp);
+        if (prof_on_) prof_begin("im2col", 0.0, (double)B * L * a.latent_dim * a.chunk_compress_factor * 4.0 + (double)M * kp * 2.0);
         launch_vocoder_im2col(s_, dt_, latent, B, L, a.latent_dim, a.chunk_compress_factor, a.vo_in_kernel, kp, cols, vlen,
                               packed ? rg.off : nullptr);
+        if (prof_on_) prof_end();
         Linear lin;
         lin.w = tensor("vo.in_gemm.w"); lin.b = vecf("vo.in.b"); lin.N = C; lin.K = kp;
         Epilogue ei; ei.mode = EPI_STORE; ei.out_dtype = F32; ei.out = x; ei.ldo = C;
@@ -1178,16 +1188,34 @@ void Engine::vocoder_dev(int B, int L, const float* latent, float* wav, const in
     }
     void* xn = act_alloc(M * C);
     const LNorm ln = lnorm("vo.out_ln");
+    if (prof_on_) prof_begin("layernorm", (double)M * C * 8, (double)M * C * (4.0 + (is_half(dt_) ? 2.0 : 4.0)));
     launch_layernorm(s_, dt_, x, M, C, ln.g, ln.b, a.ln_eps, xn);
+    if (prof_on_) prof_end();
     // head: transposed conv with kernel = stride = base_chunk_size == per-frame linear; rows of the GEMM output ARE the wave
     if (packed) {
-        float* wp = f32_alloc(M * a.base_chunk_size);
-        Epilogue e; e.mode = EPI_STORE; e.out_dtype = F32; e.out = wp; e.ldo = a.base_chunk_size;
-        gemm("gemm_head", dt_, xn, C, linear("vo.head"), (int)M, e);
-        if (prof_on_) prof_begin("unpack_rows", 0.0, ((double)M + (double)B * T) * a.base_chunk_size * 4.0);
-        if (valid) launch_unpack_rows_quiet(s_, wp, valid, rg.off, B, T, a.base_chunk_size, vo_rf_, vc.quiet, vc.edge, wav);
-        else launch_unpack_rows(s_, wp, vlen, rg.off, B, T, a.base_chunk_size, wav);
-        if (prof_on_) prof_end();
+        const int W = a.base_chunk_size;
+        const Linear& head = linear("vo.head");
+        // the head stores every packed row where it belongs in [B][T][W] (the slab epilogue's destination map) and a fill writes the rows it
+        // leaves out, the known rest of each utterance's row: no scratch image of the waveform, no copy of it
+        Epilogue e; e.mode = EPI_STORE; e.out_dtype = F32; e.out = wav; e.ldo = W; e.bias = head.b;
+        e.map_off = rg.off; e.map_valid = valid ? valid : vlen; e.map_B = B; e.map_T = T;
+        if (gemm_form_maps_rows(gemm_form(dt_, (int)M, head.N, head.K, C, head.K, e, xn, head.w.as(dt_)))) {
+            // (bytes: the rows the utterances do not own, B*T - M; the 2rf trim form fills rf more per trimmed utterance)
+            if (prof_on_) prof_begin("fill_rows", 0.0, std::max(0.0, (double)B * T - (double)M) * W * 4.0);
+            if (valid) launch_fill_rows(s_, valid, B, T, W, vo_rf_, vc.quiet, vc.edge, wav);
+            else launch_fill_rows(s_, vlen, B, T, W, 0, nullptr, nullptr, wav);
+            if (prof_on_) prof_end();
+            gemm("gemm_head", dt_, xn, C, head, (int)M, e);
+        } else {
+            // a form without the slab epilogue (operands that miss its alignment): packed rows into a scratch image, then the unpack pass
+            float* wp = f32_alloc(M * W);
+            Epilogue ep; ep.mode = EPI_STORE; ep.out_dtype = F32; ep.out = wp; ep.ldo = W;
+            gemm("gemm_head", dt_, xn, C, head, (int)M, ep);
+            if (prof_on_) prof_begin("unpack_rows", 0.0, ((double)M + (double)B * T) * W * 4.0);
+            if (valid) launch_unpack_rows_quiet(s_, wp, valid, rg.off, B, T, W, vo_rf_, vc.quiet, vc.edge, wav);
+            else launch_unpack_rows(s_, wp, vlen, rg.off, B, T, W, wav);
+            if (prof_on_) prof_end();
+        }
     } else {
         Epilogue e; e.mode = EPI_STORE; e.out_dtype = F32; e.out = wav; e.ldo = a.base_chunk_size; e.len = vlen; e.L = T;
         gemm("gemm_head", dt_, xn, C, linear("vo.head"), (int)M, e);

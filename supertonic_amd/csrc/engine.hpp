@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/stn_arch.h"
+#include "host/len_tables.hpp"
 #include "host/join_plan.hpp"
 #include "host/pause_plan.hpp"
 #include "host/pitch.hpp"
@@ -210,8 +211,9 @@ class Engine {
     // valid (with vlen, vrows): the exact trimmed DENSE mode — rows are computed on vlen[b] frames, exact below valid[b], and
     // the rest of each row is the cached zero-latent response (quiet chunk + edge tail)
     // tails (with valid): the blocks' conv taps beyond vlen[b] read the cached per-layer tails instead of zero (VO_TRIM_TAIL)
+    // voff (packed rows): the row offsets [B + 1] of vlen where the caller already holds them (the length tables); null: launch_row_map computes them
     void vocoder_dev(int B, int L, const float* latent, float* wav, const int* vlen = nullptr, int vrows = 0,
-                     const int* valid = nullptr, bool tails = false);
+                     const int* valid = nullptr, bool tails = false, const int* voff = nullptr);
     int vocoder_receptive_field() const;  // frames on either side that one output frame depends on
     void prepare_xattn_weights();         // fragment-ordered copies of the estimator's cross-attention Wq / Wo (kernels_xattn_hs.hip)
     std::unordered_map<const void*, const void*> frag_w_;  // row-major 16-bit matrix -> its fragment-ordered copy
@@ -249,7 +251,9 @@ class Engine {
         float* style_ttl = nullptr; size_t ttl_cap = 0;
         float* style_dp = nullptr; size_t dp_cap = 0;
         float* dur = nullptr; size_t dur_cap = 0;
-        int* llen = nullptr; size_t llen_cap = 0;
+        int* llen = nullptr;                      // the latent lengths: tab + LenTables::llen (set by batch_run)
+        int* tab = nullptr; size_t tab_cap = 0;   // the length tables of the run (host/len_tables.hpp), uploaded by the pipeline's one copy node
+        LenTables tl;                             // their layout
         int64_t* utt_ids = nullptr; size_t utt_cap = 0;
         float* noise = nullptr; size_t noise_cap = 0;   // injected noise [B,D,L] (optional)
         float* xt[2] = {nullptr, nullptr}; size_t xt_cap[2] = {0, 0};
@@ -600,6 +604,11 @@ class Engine {
                             int rope_mode, int pairs_mode, int64_t part_stride, float* part, int64_t part_elems, int* pairs_out);
     void op_attention(int dtype, int B, int Lq, int Lk, int H, int dh, const float* q, const float* k, const float* v,
                       const int* qlen, const int* klen, int rope_mode, float* o);
+    // one EPI_STORE GEMM, fp32 out, whose M rows are packed per sequence (sequence b owns rows[b] consecutive rows; rows past their sum are dead)
+    // and stored through the packed-row destination map into out [B][T][N]: row t of sequence b only for t < valid[b] (stn_op_gemm_rows).  out
+    // [out_elems] is the whole destination, uploaded as given and downloaded whole.  Returns the form; throws where it has no slab epilogue.
+    std::string op_gemm_rows(int dtype, int M, int N, int K, const float* A, const float* W, const float* bias, int B, const int* rows,
+                             const int* valid, int T, float* out, int64_t out_elems);
     void op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,
                       const float* g, const float* b, float* y, const int* seqlen = nullptr /* host [B] */);
     // launch_dwconv_ln (or, ln_only, launch_layernorm over B*L rows) on the caller's whole buffers (stn_op_dwconv_ln_ex): x [x_rows][C] uploaded as
@@ -816,10 +825,11 @@ class Engine {
     int tail_rows(int B, int L) const;
     int vocoder_rows(int B, int L, int* form) const;  // trimmed_rows, else tail_rows; *form: the VoForm that gives the count
     long graph_replays_ = 0;
-    int* pin_llen_ = nullptr; size_t pin_llen_cap_ = 0;   // pinned host staging read by the graph's memcpy node
-    unsigned long long* pin_seed_ = nullptr;
+    int* pin_tab_ = nullptr; size_t pin_tab_cap_ = 0;     // pinned host staging of the length tables (seed, lengths, row maps, pairing, vocoder
+    size_t pin_tab_n_ = 0;                                // extents: host/len_tables.hpp), read by the graph's memcpy node; words in use
     bool pin_valid_ = false;
-    unsigned long long* seed_dev_ = nullptr;
+    std::vector<int32_t> h_tab_;                          // the tables of the run being enqueued, before they are compared with the staging
+    unsigned long long* seed_dev_ = nullptr;              // the seed's words inside Batch::tab
     int final_xt_ = 0;
     // a pipelined fetch's buffers (bytes; n samples of encoding enc)
     struct FetchSlot { unsigned char* dev = nullptr; unsigned char* pin = nullptr; size_t cap = 0, n = 0; int enc = ENC_PCM16; hipEvent_t ready = nullptr, done = nullptr; bool busy = false; std::vector<float> dur; };

@@ -53,7 +53,6 @@ void Engine::batch_upload(int B, int Lt, const int64_t* ids, const float* text_m
     ensure(b.style_ttl, b.ttl_cap, n_ttl);
     ensure(b.style_dp, b.dp_cap, n_dp);
     ensure(b.dur, b.dur_cap, (size_t)B);
-    ensure(b.llen, b.llen_cap, (size_t)B);
     ensure(b.utt_ids, b.utt_cap, (size_t)B);
     if (Lt != Lt_in) {
         STN_HIP(hipMemsetAsync(b.ids, 0, sizeof(int64_t) * B * Lt, s_));
@@ -181,39 +180,50 @@ void Engine::batch_run(int total_step, float speed, uint64_t noise_seed) {
     ensure(b.xt[0], b.xt_cap[0], nx);
     ensure(b.xt[1], b.xt_cap[1], nx);
     ensure(b.wav, b.wav_cap, nw);
-    // per-call data of the captured region lives in pinned host memory (the graph's memcpy nodes re-read it at replay).
-    // Sized for 1024 utterances up front so that it is not reallocated under cached graphs; should it ever have to grow, its
-    // address is part of the graph key and the graphs that point at the old block are dropped before it is freed.
-    if ((size_t)B > pin_llen_cap_) {
-        if (pin_llen_) { sync(); drop_graphs(); (void)hipHostFree(pin_llen_); pin_llen_ = nullptr; }
-        const size_t cap = std::max<size_t>((size_t)B, 1024);
-        STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&pin_llen_), sizeof(int) * cap, hipHostMallocDefault));
-        pin_llen_cap_ = cap;
+    // Everything the pipeline derives from the lengths alone — the estimator's row map, the cross-attention's pairing, the vocoder's extents
+    // and offsets — is built here, on the host that already holds the lengths, and rides up with them and the seed in ONE copy node at the
+    // head of the chain (host/len_tables.hpp): four single-workgroup kernels leave every replay.
+    int ve_rows = 0;
+    if (packed_rows_ok(B)) for (int v : b.h_llen) ve_rows += v;
+    if (shape_buckets_) ve_rows = (int)bucket_up(ve_rows, 64);  // dead rows behind the last utterance
+    int vform = VO_DENSE;
+    const int tr_rows = vocoder_rows(B, L, &vform);  // (two forms with equal row counts must not share a capture)
+    const int tab_vo = vo_ragged_ ? LEN_VO_SCALED : !tr_rows ? LEN_VO_NONE : vform == VO_TRIM_TAIL ? LEN_VO_TAIL : LEN_VO_2RF;
+    const bool tab_pairs = ve_rows > 0 && fused_xattn_ && is_half(dt_) && B >= 2;
+    b.tl = len_tables_layout(B, ve_rows, tab_pairs, tab_vo);
+    h_tab_.assign((size_t)b.tl.total, 0);
+    len_tables_build(b.tl, b.h_llen.data(), B, ve_rows, tab_pairs, tab_vo, a.chunk_compress_factor, L * a.chunk_compress_factor, vo_rf_, h_tab_.data());
+    const unsigned long long seed64 = (unsigned long long)noise_seed;
+    std::memcpy(h_tab_.data() + b.tl.seed, &seed64, sizeof seed64);
+    ensure(b.tab, b.tab_cap, (size_t)b.tl.total);  // (a reallocation bumps b.gen: no graph keeps the old block)
+    b.llen = b.tab + b.tl.llen;
+    seed_dev_ = reinterpret_cast<unsigned long long*>(b.tab + b.tl.seed);
+    // per-call data of the captured region lives in pinned host memory (the graph's memcpy node re-reads it at replay).
+    // Sized for 1024 utterances of 64 latent frames up front so that it is not reallocated under cached graphs; should it ever have to grow,
+    // its address is part of the graph key and the graphs that point at the old block are dropped before it is freed.
+    if ((size_t)b.tl.total > pin_tab_cap_) {
+        if (pin_tab_) { sync(); drop_graphs(); (void)hipHostFree(pin_tab_); pin_tab_ = nullptr; }
+        const size_t cap = std::max<size_t>((size_t)b.tl.total + (size_t)b.tl.total / 4, (size_t)1024 * (64 + 8));
+        STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&pin_tab_), sizeof(int) * cap, hipHostMallocDefault));
+        pin_tab_cap_ = cap;
         pin_valid_ = false;
     }
-    if (!pin_seed_) {
-        STN_HIP(hipHostMalloc(reinterpret_cast<void**>(&pin_seed_), sizeof(unsigned long long), hipHostMallocDefault));
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&seed_dev_), sizeof(unsigned long long)));
-        pin_valid_ = false;
-    }
-    // a previous run's copy nodes may still be reading the staging: rewrite it only when the content changes, and then
+    // a previous run's copy node may still be reading the staging: rewrite it only when the content changes, and then
     // only after the stream has drained (steady-state replays of an unchanged batch never wait here)
-    if (!pin_valid_ || !std::equal(b.h_llen.begin(), b.h_llen.end(), pin_llen_) || *pin_seed_ != (unsigned long long)noise_seed) {
+    if (!pin_valid_ || pin_tab_n_ != h_tab_.size() || !std::equal(h_tab_.begin(), h_tab_.end(), pin_tab_)) {
         sync();
-        std::copy(b.h_llen.begin(), b.h_llen.end(), pin_llen_);
-        *pin_seed_ = (unsigned long long)noise_seed;
+        std::copy(h_tab_.begin(), h_tab_.end(), pin_tab_);
+        pin_tab_n_ = h_tab_.size();
         pin_valid_ = true;
     }
 
     ensure_time_cond(total_step, B);  // eager, on s_, ahead of whatever is replayed or captured below (same stream: ordered)
     GraphKey key;
     key.B = B; key.Lt = Lt; key.L = L; key.steps = total_step; key.noise = b.have_noise; key.ragged = vo_ragged_; key.xattn = fused_xattn_;
-    key.ffn = fused_ffn_; key.gen = b.gen; key.wgen = wgen_; key.pin = pin_llen_;
-    key.rows = 0;
-    if (packed_rows_ok(B)) for (int v : b.h_llen) key.rows += v;
-    if (shape_buckets_) key.rows = (int)bucket_up(key.rows, 64);
+    key.ffn = fused_ffn_; key.gen = b.gen; key.wgen = wgen_; key.pin = pin_tab_;
+    key.rows = ve_rows;
     last_ve_rows_ = key.rows ? key.rows : (int64_t)B * L;
-    key.vrows = vocoder_rows(B, L, &key.vform);  // (two forms with equal row counts must not share a capture)
+    key.vrows = tr_rows; key.vform = vform;
     if (shape_buckets_) key.vrows = (int)bucket_up(key.vrows, 64 * a.chunk_compress_factor);
     key.trows = tpk ? b.trows : 0;
     last_vo_rows_ = (int64_t)B * L * a.chunk_compress_factor;
@@ -324,8 +334,8 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
     const stn_arch& a = a_;
     const int B = b.B, Lt = b.Lt, L = b.L, D = a.latent_dim * a.chunk_compress_factor;
     const size_t nx = (size_t)B * D * L;
-    STN_HIP(hipMemcpyAsync(b.llen, pin_llen_, sizeof(int) * B, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(seed_dev_, pin_seed_, sizeof(unsigned long long), hipMemcpyHostToDevice, s_));
+    // the lengths, the seed and every table derived from the lengths (batch_run built them): one copy; its size follows from the graph key
+    STN_HIP(hipMemcpyAsync(b.tab, pin_tab_, sizeof(int) * (size_t)b.tl.total, hipMemcpyHostToDevice, s_));
     // 2. (the text encoder ran on the side stream: batch_run) its rows
     Ragged trg;
     const bool tpk = packed_text_ok(B) && b.trows > 0;
@@ -337,7 +347,10 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
         STN_HIP(hipMemcpyAsync(b.xt[0], b.noise, nx * 4, hipMemcpyDeviceToDevice, s_));
         launch_mask_ncl(s_, b.xt[0], B, D, L, b.llen);
     } else {
+        stage_ = "ve";
+        if (prof_on_) prof_begin("noise", 0.0, (double)nx * 4.0);
         launch_randn_masked(s_, 0, b.utt_ids, B, D, L, b.llen, b.xt[0], seed_dev_);
+        if (prof_on_) prof_end();
     }
     // 4. Euler loop: step-invariant K/V once, the time conditioning of every step in one pass, then total_step passes
     VeCtx c = ve_prepare_dev(B, Lt, text_rows, b.style_ttl, b.tlen, trgp, /*defer_text=*/true);
@@ -361,15 +374,15 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
         rg.rows = 0;
         for (int v : b.h_llen) rg.rows += v;
         if (shape_buckets_) rg.rows = (int)bucket_up(rg.rows, 64);  // dead rows behind the last utterance (as in the graph key)
-        int* off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
-        int* row_b = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)std::max(rg.rows, 1)));
-        launch_row_map(s_, b.llen, B, off, row_b, rg.rows);
+        if (b.tl.ve_off < 0 || b.tl.ve_row_b + rg.rows > b.tl.total) throw std::logic_error("batch_run: no row map in the length tables");
+        const int* off = b.tab + b.tl.ve_off;
+        const int* row_b = b.tab + b.tl.ve_row_b;
         rg.off = off; rg.row_b = row_b;
         // one 1024-thread workgroup of fold_dwconv_ln fits a CU: 271 runs of <= 32 frames (this bench's lengths) are two rounds, 256 runs of <= 40 one
         rg.fold_run = fold_run_frames(b.h_llen.data(), B, n_cu_);
         if (fused_xattn_ && is_half(dt_) && B >= 2) {  // the head-split cross-attention's pairing, once per synthesis (the lengths are the run's)
-            int* pairs = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 2)));
-            launch_xattn_hs_pairs(s_, b.llen, B, pairs);
+            if (b.tl.pairs < 0) throw std::logic_error("batch_run: no pairing in the length tables");
+            const int* pairs = b.tab + b.tl.pairs;
             rg.hs_pairs = pairs;
         }
         rgp = &rg;
@@ -388,11 +401,7 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
     final_xt_ = cur;
     // 5. vocoder
     const int* vlen = nullptr;
-    if (vo_ragged_) {
-        int* v = static_cast<int*>(ar_.alloc(sizeof(int) * B));
-        launch_scale_len(s_, b.llen, B, a.chunk_compress_factor, v);
-        vlen = v;
-    }
+    if (vo_ragged_) vlen = b.tab + b.tl.vo_n;  // len * ccf
     int vrows = 0;
     const int* valid = nullptr;
     bool tails = false;
@@ -402,12 +411,10 @@ void Engine::enqueue_after_duration(int total_step, const std::function<void()>&
     } else if (int vform = VO_DENSE; int tr = vocoder_rows(B, L, &vform)) {
         if (shape_buckets_) tr = (int)bucket_up(tr, 64 * a.chunk_compress_factor);
         // reference (dense) semantics at the cost of the frames that are not position-independent
-        int* n_dev = static_cast<int*>(ar_.alloc(sizeof(int) * B));
-        int* v_dev = static_cast<int*>(ar_.alloc(sizeof(int) * B));
-        launch_trim_len(s_, b.llen, B, a.chunk_compress_factor, L * a.chunk_compress_factor, vo_rf_, n_dev, v_dev, vform == VO_TRIM_TAIL);
-        vlen = n_dev; valid = v_dev; vrows = tr; tails = vform == VO_TRIM_TAIL;
+        vlen = b.tab + b.tl.vo_n; valid = b.tab + b.tl.vo_valid; vrows = tr; tails = vform == VO_TRIM_TAIL;
     }
-    vocoder_dev(B, L, b.xt[cur], b.wav, vlen, vrows, valid, tails);
+    if (vlen && b.tl.vo_n < 0) throw std::logic_error("batch_run: no vocoder extents in the length tables");
+    vocoder_dev(B, L, b.xt[cur], b.wav, vlen, vrows, valid, tails, vlen ? b.tab + b.tl.vo_off : nullptr);
     STN_HIP(hipGetLastError());  // a kernel launch that was rejected (bad configuration) must not pass silently
 }
 

@@ -79,6 +79,37 @@ std::string Engine::op_gemm_ex(int dtype, int M, int N, int K, const float* A, c
     return f.str();
 }
 
+std::string Engine::op_gemm_rows(int dtype, int M, int N, int K, const float* A, const float* W, const float* bias, int B, const int* rows,
+                                 const int* valid, int T, float* out, int64_t out_elems) {
+    STN_HIP(hipSetDevice(device_));
+    ar_.reset();
+    float* dA = up(ar_, s_, A, (size_t)M * K);
+    float* dW = up(ar_, s_, W, (size_t)N * K);
+    const void* pa = dA;
+    const void* pw = dW;
+    if (is_half(dtype)) {
+        void* a16 = ar_.alloc((size_t)M * K * 2);
+        void* w16 = ar_.alloc((size_t)N * K * 2);
+        launch_cast(s_, dtype, dA, (int64_t)M * K, a16);
+        launch_cast(s_, dtype, dW, (int64_t)N * K, w16);
+        pa = a16; pw = w16;
+    }
+    float* dO = up(ar_, s_, out, (size_t)out_elems);
+    const int* drows = up(ar_, s_, rows, (size_t)B);
+    int* off = static_cast<int*>(ar_.alloc(sizeof(int) * (size_t)(B + 1)));
+    launch_row_map(s_, drows, B, off, nullptr);
+    Epilogue e;
+    e.mode = EPI_STORE; e.out_dtype = F32; e.out = dO; e.ldo = N;
+    e.bias = bias ? up(ar_, s_, bias, (size_t)N) : nullptr;
+    e.map_off = off; e.map_valid = up(ar_, s_, valid, (size_t)B); e.map_B = B; e.map_T = T;
+    const GemmForm f = gemm_form(dtype, M, N, K, K, K, e, pa, pw, false);
+    launch_gemm_form(s_, f, pa, K, pw, K, M, N, K, e, nullptr);  // (throws for a form that cannot take the map)
+    STN_HIP(hipGetLastError());
+    STN_HIP(hipMemcpyAsync(out, dO, (size_t)out_elems * 4, hipMemcpyDeviceToHost, s_));
+    sync();
+    return f.str();
+}
+
 void Engine::op_dwconv_ln(int dtype, int B, int L, int C, int k, int dil, const float* x, const float* w, const float* bias,
                           const float* g, const float* b, float* y, const int* seqlen) {
     STN_HIP(hipSetDevice(device_));
@@ -756,6 +787,41 @@ void Engine::op_layout(int which, int dtype, const int* p, const float* a, int64
         float* d = up(ar_, s_, out, (size_t)out_n);
         launch_vocoder_in(s_, da, B, L, ld, ccf, dw, db, C, k, d, dlen);
         STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 8: {  // fill_rows: p = {B, T, W, rf, zeros}; len = valid [B]; a = quiet [W], b = edge [rf][W] (unused with zeros); out [B][T][W] fp32
+        const int B = p[0], T = p[1], W = p[2], rf = p[3], zeros = p[4];
+        need(T > 0 && W > 0 && W % 4 == 0 && rf >= 0 && rf <= T && out, "fill_rows: bad shape");
+        check_len(B, T, true);
+        need(out_n >= (int64_t)B * T * W, "fill_rows: buffer too small");
+        need(zeros || (a && a_n >= W && (rf == 0 || (b && b_n >= (int64_t)rf * W))), "fill_rows: the quiet rule needs quiet [W] and edge [rf][W]");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        const float* dq = zeros ? nullptr : up(ar_, s_, a, (size_t)a_n);
+        const float* de = (zeros || rf == 0) ? nullptr : up(ar_, s_, b, (size_t)b_n);
+        float* d = up(ar_, s_, out, (size_t)out_n);
+        launch_fill_rows(s_, dlen, B, T, W, rf, dq, de, d);
+        STN_HIP(hipMemcpyAsync(out, d, (size_t)out_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 9: {  // hs_pairs: p = {B}; len [B]; iout: the pairing, 2 * ceil(B / 2) words
+        const int B = p[0];
+        check_len(B, 1 << 20, true);
+        need(iout && iout_n >= 2 * ((B + 1) / 2), "hs_pairs: iout too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        int* d = up(ar_, s_, iout, (size_t)iout_n);
+        launch_xattn_hs_pairs(s_, dlen, B, d);
+        STN_HIP(hipMemcpyAsync(iout, d, (size_t)iout_n * 4, hipMemcpyDeviceToHost, s_));
+        break;
+    }
+    case 10: {  // trim_len: p = {B, ccf, T, rf, tail_form}; len [B] latent lengths; iout = n [B] then valid [B]
+        const int B = p[0], ccf = p[1], T = p[2], rf = p[3], tail_form = p[4];
+        need(ccf > 0 && T > 0 && rf >= 0, "trim_len: bad shape");
+        check_len(B, T / ccf, true);
+        need(iout && iout_n >= 2 * (int64_t)B, "trim_len: iout too small");
+        const int* dlen = up(ar_, s_, len, (size_t)B);
+        int* d = up(ar_, s_, iout, (size_t)iout_n);
+        launch_trim_len(s_, dlen, B, ccf, T, rf, d, d + B, tail_form != 0);
+        STN_HIP(hipMemcpyAsync(iout, d, (size_t)iout_n * 4, hipMemcpyDeviceToHost, s_));
         break;
     }
     default: need(false, "unknown kernel");

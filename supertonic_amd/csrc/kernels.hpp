@@ -103,6 +103,12 @@ struct Epilogue {
     const int* row_b = nullptr;       // packed rows: sequence of row m (replaces m / L for rowvec; len must be null then)
     const float* rowvec = nullptr;    // EPI_RESID: per-sequence vector [B][rv_ld] added to every row of sequence b (time
     int rv_ld = 0;                    //            conditioning): resid = (resid + gamma*(acc+bias) + rowvec[b]) * keep
+    // EPI_STORE, fp32 out, the tiled kernels' slab epilogue only (gemm_form_maps_rows): the rows of the GEMM are packed per sequence and each
+    // is stored where it belongs in a padded [map_B][map_T] destination — row r of sequence b (map_off[b] <= r < map_off[b + 1], t = r - map_off[b])
+    // goes to row b * map_T + t of out when t < map_valid[b] and is not stored otherwise (nor are rows from map_off[map_B] on).  len must be null.
+    const int* map_off = nullptr;     // [map_B + 1] row offsets (launch_row_map); null: no map, row m is stored at row m
+    const int* map_valid = nullptr;   // [map_B] rows of each sequence that are stored (<= the rows it owns)
+    int map_B = 0, map_T = 0;
     int ksplit = 1;                   // tiled kernels: split-K factor (plain fp32 store of partials; launch_gemm_splitk)
     int nt = 0;                       // tiled kernels: 1 = non-temporal 16-bit output stores, for a stream far larger than the Infinity Cache
                                       // (the vocoder's 245 MB hidden activation): vo.pw1 185 -> 166 us.  The matching non-temporal A loads in
@@ -143,6 +149,9 @@ GemmForm gemm_form(int dtype, int M, int N, int K, int lda, int ldw, const Epilo
 // runs form f (from gemm_form on the same arguments); workspace: [f.split][M][N] fp32 when f.split > 1, else unused
 void launch_gemm_form(hipStream_t s, const GemmForm& f, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                       const Epilogue& e, float* workspace);
+// whether form f can execute an Epilogue with a packed-row destination map (map_off): the tiled kernels' fp32 slab store, no split.
+// launch_gemm_form throws std::invalid_argument for a map on any other form.
+bool gemm_form_maps_rows(const GemmForm& f);
 // gemm_form(..., allow_split = false) and launch_gemm_form in one call
 void launch_gemm(hipStream_t s, int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                  const Epilogue& e);
@@ -385,6 +394,11 @@ void launch_vocoder_im2col(hipStream_t s, int out_dtype, const float* latent, in
                            const int* seqlen = nullptr /* valid vocoder frames per sequence */,
                            const int* row_off = nullptr /* packed destination rows (needs seqlen) */);
 // packed rows [sum len][W] -> padded [B][T][W], zeros past each sequence's length
+// The rows of a padded [B][T][W] fp32 destination that a packed-row GEMM with a destination map (Epilogue::map_off) does not store: row t of
+// sequence b for t >= valid[b].  quiet != null: the dense vocoder's position-independent rest of the row, as launch_unpack_rows_quiet decides
+// it — edge[t - (T - rf)] for t >= T - rf, quiet otherwise (quiet [W], edge [rf][W]); quiet == null: zeros (the length-aware form).  Rows below
+// valid[b] are not touched.  W % 4 == 0.
+void launch_fill_rows(hipStream_t s, const int* valid, int B, int T, int W, int rf, const float* quiet, const float* edge, float* dst);
 void launch_unpack_rows(hipStream_t s, const float* src, const int* len, const int* row_off, int B, int T, int W, float* dst);
 // exact trimmed dense vocoder (see kernels_layout.hip): extents per utterance, and the unpack that fills the position-independent tail
 void launch_trim_len(hipStream_t s, const int* len, int B, int ccf, int T, int rf, int* n_out, int* valid_out, bool tail_form = false);

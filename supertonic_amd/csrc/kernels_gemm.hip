@@ -720,8 +720,30 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tiled_kernel(const void* __r
         gam[0] = g0.x; gam[1] = g0.y; gam[2] = g0.z; gam[3] = g0.w; gam[4] = g1.x; gam[5] = g1.y; gam[6] = g1.z; gam[7] = g1.w;
     }
     const bool to_bf16 = e.out_dtype == BF16;
+    // packed-row destination map: the sequence b0 that owns the tile's first row, found by every wavefront in two rounds of parallel probes
+    // (64 offsets a round, counted by a ballot: two load latencies for any B <= 4096, where a bisection is log2 B of them in a chain), and the
+    // extents of b0 and of the sequence behind it in registers — a tile that meets at most one sequence boundary maps its rows without a load
+    int map_b0 = 0, map_lo0 = 0, map_hi0 = 0, map_vl0 = 0, map_hi1 = 0, map_vl1 = 0;
+    if (MODE == EPI_STORE && e.map_off) {
+        const int Bm = e.map_B, step = (Bm + 63) >> 6;
+        const int i0 = lane * step;
+        const int o0 = i0 < Bm ? e.map_off[i0] : 0;
+        const int c0 = __popcll(__ballot(i0 < Bm && o0 <= m0));  // >= 1: map_off[0] = 0 <= m0
+        int bq0 = (c0 - 1) * step;
+        if (step > 1) {
+            const int i1 = bq0 + lane;
+            const bool in1 = lane < step && i1 < Bm;
+            const int o1 = in1 ? e.map_off[i1] : 0;
+            bq0 += __popcll(__ballot(in1 && o1 <= m0)) - 1;  // >= 1 again: map_off[bq0] <= m0
+        }
+        map_b0 = __builtin_amdgcn_readfirstlane(bq0);
+        const int b1 = map_b0 + 1 < Bm ? map_b0 + 1 : Bm - 1;
+        map_lo0 = e.map_off[map_b0]; map_hi0 = e.map_off[map_b0 + 1]; map_vl0 = e.map_valid[map_b0];
+        map_hi1 = e.map_off[b1 + 1]; map_vl1 = e.map_valid[b1];
+    }
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi) {
+        int mb = map_b0, mlo = map_lo0, mhi = map_hi0, mvl = map_vl0;  // a thread's rows ascend within a pass: the tile's first sequence, then advanced
         // residual rows of this pass: issue the loads before the LDS hand-off so their latency hides behind it
         float4 r0[ITER], r1[ITER];
         bool ok[ITER];
@@ -742,6 +764,13 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_tiled_kernel(const void* __r
                 const int b = m / e.L;
                 bq[it] = b;
                 if (e.len && m - b * e.L >= e.len[b]) keep[it] = 0.f;
+            }
+            if (MODE == EPI_STORE && e.map_off && ok[it]) {
+                if (mb == map_b0 && m >= mhi && mb + 1 < e.map_B) { ++mb; mlo = mhi; mhi = map_hi1; mvl = map_vl1; }  // the first boundary: from the registers
+                while (m >= mhi && mb + 1 < e.map_B) { ++mb; mlo = mhi; mhi = e.map_off[mb + 1]; mvl = e.map_valid[mb]; }  // short sequences
+                const int t = m - mlo;
+                ok[it] = t < mvl;  // (rows from map_off[map_B] on land in the last sequence at t >= its rows >= map_valid)
+                off[it] = ((size_t)mb * e.map_T + t) * e.ldo + n;
             }
             if (MODE == EPI_RESID) {
                 r0[it] = make_float4(0.f, 0.f, 0.f, 0.f); r1[it] = r0[it];
@@ -1013,6 +1042,8 @@ GemmForm gemm_form(int dtype, int M, int N, int K, int lda, int ldw, const Epilo
     return f;
 }
 
+bool gemm_form_maps_rows(const GemmForm& f) { return f.kernel == GK_TILED && f.epi == GE_SLAB && f.split == 1 && f.mode == EPI_STORE; }
+
 std::string GemmForm::str() const {
     char b[128];
     const char* ep = epi == GE_TR ? "tr" : epi == GE_SLAB ? "slab" : "lane";
@@ -1056,6 +1087,8 @@ void launch_gemm_form(hipStream_t s, const GemmForm& f, const void* A, int lda, 
                       const Epilogue& e, float* workspace) {
     if (M <= 0 || N <= 0) return;
     if (f.mode != e.mode) throw std::invalid_argument("launch_gemm_form: the form was made for another epilogue mode");
+    if (e.map_off && !(gemm_form_maps_rows(f) && e.out_dtype == F32 && !e.len && e.map_valid && e.map_B > 0 && e.map_T > 0))
+        throw std::invalid_argument("launch_gemm_form: a packed-row destination map needs the tiled fp32 slab store, no row mask, and valid / B / T");
     if (f.split > 1) {
         // deterministic split-K: the splits into `workspace`, then out = epilogue(sum over splits, in split order)
         if (!workspace || misaligned16(workspace)) throw std::invalid_argument("launch_gemm_form: a split-K form needs a 16-byte aligned workspace of split * M * N floats");

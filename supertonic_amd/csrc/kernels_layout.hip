@@ -530,6 +530,34 @@ void launch_unpack_rows_quiet(hipStream_t s, const float* src, const int* valid,
                 W / 4, rf, quiet, edge, nrows, dst);
 }
 
+// The rows of [B][T][W] from valid[b] on, and nothing else: what a head GEMM that stores its packed rows in place (Epilogue::map_off) leaves to
+// write.  The same decision per row as unpack_rows_quiet_kernel (edge tail, else quiet chunk), or zeros where there are no constants (quiet ==
+// null: the length-aware form).  FILL_WG workgroups per sequence share its rest row by row, so every wavefront starts at a row it has to write;
+// the quiet chunk is loaded once per wavefront, beside the sequence's extent, and stored to all of its rows.
+constexpr int FILL_WG = 8;
+__global__ __launch_bounds__(256) void fill_rows_kernel(const int* __restrict__ valid, int T, int W4, int rf, const float* __restrict__ quiet,
+                                                        const float* __restrict__ edge, float* __restrict__ dst) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const int w = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6), nw = (int)gridDim.y * 4;  // this wavefront among the sequence's
+    const int v0 = valid[b];
+    float4* d4 = reinterpret_cast<float4*>(dst) + (int64_t)b * T * W4;
+    for (int c = lane; c < W4; c += 64) {
+        const float4 q = quiet ? reinterpret_cast<const float4*>(quiet)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int t = v0 + w; t < T; t += nw) {
+            float4 v = q;
+            if (quiet && t >= T - rf) v = reinterpret_cast<const float4*>(edge)[(int64_t)(t - (T - rf)) * W4 + c];
+            d4[(int64_t)t * W4 + c] = v;
+        }
+    }
+}
+void launch_fill_rows(hipStream_t s, const int* valid, int B, int T, int W, int rf, const float* quiet, const float* edge, float* dst) {
+    if (B <= 0 || T <= 0 || W == 0) return;
+    if (W % 4) { throw std::invalid_argument("fill_rows needs W % 4 == 0"); }
+    if (quiet && rf > 0 && !edge) { throw std::invalid_argument("fill_rows: the quiet rule needs the edge tail"); }
+    if (rf < 0 || rf > T) { throw std::invalid_argument("fill_rows: rf outside [0, T]"); }
+    STN_KLAUNCH(fill_rows_kernel, dim3((unsigned)B, FILL_WG), dim3(256), 0, s, valid, T, W / 4, rf, quiet, quiet ? edge : nullptr, dst);
+}
+
 __global__ void mask_ncl_kernel(float* __restrict__ x, int D, int L, int64_t n, const int* __restrict__ len) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
