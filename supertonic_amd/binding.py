@@ -212,181 +212,12 @@ COMPRESSOR_PRESETS = {"speech": COMPRESSOR_SPEECH}
 # what a spelling that leaves fields out fills them with (THRESHOLD and RATIO are always given there)
 _COMPRESSOR_REST = COMPRESSOR_SPEECH[2:]
 
-
-class StnCompressor(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_float) for n in COMPRESSOR_FIELDS]
-
-
-def parse_compressor_spec(spec):
-    """A command-line compressor "THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]" (the speech default's knee 6, attack 5,
-    release 120 and makeup 0 when left out) -> the 6-tuple of floats.  ValueError naming what is wrong."""
-    parts = str(spec).split(":")
-    if not 2 <= len(parts) <= 6:
-        raise ValueError(f"compressor {spec!r}: expected THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]")
-    try:
-        nums = [float(v) for v in parts]
-    except ValueError:
-        raise ValueError(f"compressor {spec!r}: THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and MAKEUP_DB must be numbers") from None
-    return tuple(nums) + _COMPRESSOR_REST[len(nums) - 2:]
-
-
-def compressor_args(compressor, preset=None):
-    """A compressor argument -> the 6-tuple of floats (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db), or None for off
-    (None or False).  True is the "speech" default (-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB); a dict names
-    fields and takes the others from that default; a 6-tuple gives all six; a "THRESHOLD:RATIO[:...]" string is the command line's
-    spelling.  preset ("speech") stands for True.  ValueError naming the field for a malformed value or an unknown field or preset; the
-    numeric limits are the C ABI's (compressor_error, Engine.set_compressor)."""
-    if preset is not None:
-        if preset not in COMPRESSOR_PRESETS:
-            raise ValueError(f"compressor_preset {preset!r}: must be one of {', '.join(COMPRESSOR_PRESETS)}")
-        if compressor is None or compressor is False:
-            compressor = True
-    if compressor is None or compressor is False:
-        return None
-    if compressor is True:
-        return COMPRESSOR_PRESETS[preset or "speech"]
-    if isinstance(compressor, str):
-        return parse_compressor_spec(compressor)
-    if isinstance(compressor, dict):
-        unknown = set(compressor) - set(COMPRESSOR_FIELDS)
-        if unknown:
-            raise ValueError(f"compressor: unknown field {sorted(unknown)[0]!r} ({', '.join(COMPRESSOR_FIELDS)})")
-        vals = [compressor.get(n, d) for n, d in zip(COMPRESSOR_FIELDS, COMPRESSOR_SPEECH)]
-    elif isinstance(compressor, (tuple, list)) and len(compressor) == 6:
-        vals = list(compressor)
-    else:
-        raise ValueError(f"compressor: True, a dict of {', '.join(COMPRESSOR_FIELDS)}, or a 6-tuple of them, not {compressor!r}")
-    for name, v in zip(COMPRESSOR_FIELDS, vals):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"compressor: {name} must be a finite number, not {v!r}")
-    return tuple(float(v) for v in vals)
-
-
-def _compressor_struct(compressor):
-    c = compressor_args(compressor)
-    if c is None:
-        raise ValueError("compressor: a setting is needed here, not off")
-    return StnCompressor(*c)
-
-
-def compressor_error(compressor, rate_hz=0):
-    """Why Engine.set_compressor would refuse the setting (host only): "" when it would not; the message names the field."""
-    return load().stn_compressor_error(ctypes.byref(_compressor_struct(compressor)), int(rate_hz)).decode()
-
-
-def compressor_coefs(compressor, rate_hz):
-    """(k float64 [2]: kA, kR = -expm1(-1000 / (ms rate)); k32 float32 [2]: what the GPU multiplies by) at rate_hz (host only)."""
-    c = _compressor_struct(compressor)
-    k, k32 = np.zeros(2, np.float64), np.zeros(2, np.float32)
-    rc = load().stn_compressor_coefs(ctypes.byref(c), int(rate_hz), k, k32)
-    if rc < 0:
-        raise StnError(rc, compressor_error(compressor, rate_hz) or "stn_compressor_coefs failed")
-    return k, k32
-
-
-def compressor_curve(compressor, in_db):
-    """The static curve, makeup included: output level in dB at the input levels in_db (host only, float64)."""
-    c = _compressor_struct(compressor)
-    x = np.ascontiguousarray(np.atleast_1d(in_db), np.float64)
-    out = np.zeros(x.shape, np.float64)
-    rc = load().stn_compressor_curve(ctypes.byref(c), x.size, x, out)
-    if rc < 0:
-        raise StnError(rc, compressor_error(compressor) or "stn_compressor_curve failed")
-    return out
-
-
 EXPANDER_FIELDS = ("threshold_db", "ratio", "knee_db", "range_db", "attack_ms", "hold_ms", "release_ms")
 # the documented defaults: "speech" -50 dB, 3:1, a 6 dB knee, at most 24 dB, 1 ms attack, 30 ms hold, 150 ms release; "gate" -45 dB,
 # 20:1, no knee, 60 dB, 0.5 ms, 50 ms, 100 ms
 EXPANDER_SPEECH = (-50.0, 3.0, 6.0, 24.0, 1.0, 30.0, 150.0)
 EXPANDER_GATE = (-45.0, 20.0, 0.0, 60.0, 0.5, 50.0, 100.0)
 EXPANDER_PRESETS = {"speech": EXPANDER_SPEECH, "gate": EXPANDER_GATE}
-
-
-class StnExpander(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_float) for n in EXPANDER_FIELDS]
-
-
-def parse_expander_spec(spec, preset=None):
-    """A command-line expander "THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]" (what is left out comes from the
-    preset, "speech" unless given) -> the 7-tuple of floats.  ValueError naming what is wrong."""
-    parts = str(spec).split(":")
-    if not 2 <= len(parts) <= 7:
-        raise ValueError(f"expander {spec!r}: expected THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]")
-    try:
-        nums = [float(v) for v in parts]
-    except ValueError:
-        raise ValueError(f"expander {spec!r}: THRESHOLD, RATIO, KNEE, RANGE_DB, ATTACK_MS, HOLD_MS and RELEASE_MS must be numbers") from None
-    return tuple(nums) + EXPANDER_PRESETS[preset or "speech"][len(nums):]
-
-
-def expander_args(expander, preset=None):
-    """An expander argument -> the 7-tuple of floats (threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms), or None
-    for off (None or False).  True is the preset ("speech" unless given: -50 dB, 3:1, knee 6 dB, range 24 dB, attack 1 ms, hold 30 ms,
-    release 150 ms; "gate": -45 dB, 20:1, knee 0, range 60 dB, 0.5 ms, 50 ms, 100 ms); a dict names fields and takes the others from
-    the preset; a 7-tuple gives all seven; a "THRESHOLD:RATIO[:...]" string is the command line's spelling.  A preset alone stands for
-    True.  ValueError naming the field for a malformed value or an unknown field or preset; the numeric limits are the C ABI's
-    (expander_error, Engine.set_expander)."""
-    if preset is not None:
-        if preset not in EXPANDER_PRESETS:
-            raise ValueError(f"expander_preset {preset!r}: must be one of {', '.join(EXPANDER_PRESETS)}")
-        if expander is None or expander is False:
-            expander = True
-    if expander is None or expander is False:
-        return None
-    base = EXPANDER_PRESETS[preset or "speech"]
-    if expander is True:
-        return base
-    if isinstance(expander, str):
-        return parse_expander_spec(expander, preset)
-    if isinstance(expander, dict):
-        unknown = set(expander) - set(EXPANDER_FIELDS)
-        if unknown:
-            raise ValueError(f"expander: unknown field {sorted(unknown)[0]!r} ({', '.join(EXPANDER_FIELDS)})")
-        vals = [expander.get(n, d) for n, d in zip(EXPANDER_FIELDS, base)]
-    elif isinstance(expander, (tuple, list)) and len(expander) == 7:
-        vals = list(expander)
-    else:
-        raise ValueError(f"expander: True, a dict of {', '.join(EXPANDER_FIELDS)}, or a 7-tuple of them, not {expander!r}")
-    for name, v in zip(EXPANDER_FIELDS, vals):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"expander: {name} must be a finite number, not {v!r}")
-    return tuple(float(v) for v in vals)
-
-
-def _expander_struct(expander):
-    c = expander_args(expander)
-    if c is None:
-        raise ValueError("expander: a setting is needed here, not off")
-    return StnExpander(*c)
-
-
-def expander_error(expander, rate_hz=0):
-    """Why Engine.set_expander would refuse the setting (host only): "" when it would not; the message names the field."""
-    return load().stn_expander_error(ctypes.byref(_expander_struct(expander)), int(rate_hz)).decode()
-
-
-def expander_coefs(expander, rate_hz):
-    """(k float64 [3]: kA = -expm1(-1000 / (attack_ms rate)), delta = range_db 1000 / (release_ms rate), Bh = delta32 Hs; k32 float32
-    [3]: what the GPU computes with; Hs: the hold in samples) at rate_hz (host only)."""
-    c = _expander_struct(expander)
-    k, k32, hs = np.zeros(3, np.float64), np.zeros(3, np.float32), ctypes.c_int64()
-    rc = load().stn_expander_coefs(ctypes.byref(c), int(rate_hz), k, k32, ctypes.byref(hs))
-    if rc < 0:
-        raise StnError(rc, expander_error(expander, rate_hz) or "stn_expander_coefs failed")
-    return k, k32, int(hs.value)
-
-
-def expander_curve(expander, in_db):
-    """The static curve: output level in dB at the input levels in_db (host only, float64)."""
-    c = _expander_struct(expander)
-    x = np.ascontiguousarray(np.atleast_1d(in_db), np.float64)
-    out = np.zeros(x.shape, np.float64)
-    rc = load().stn_expander_curve(ctypes.byref(c), x.size, x, out)
-    if rc < 0:
-        raise StnError(rc, expander_error(expander) or "stn_expander_curve failed")
-    return out
-
 
 DEESSER_FIELDS = ("freq_hz", "threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "range_db", "mode")
 DEESSER_MODES = ("split", "wide")  # STN_DEESS_SPLIT, STN_DEESS_WIDE
@@ -396,31 +227,208 @@ DEESSER_PRESETS = {"speech": DEESSER_SPEECH}
 _DEESSER_SPELLING = "FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]"
 
 
+class StnCompressor(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in COMPRESSOR_FIELDS]
+
+
+class StnExpander(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in EXPANDER_FIELDS]
+
+
 class StnDeesser(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in DEESSER_FIELDS[:7]] + [("mode", ctypes.c_int)]
 
 
-def _deesser_mode(v):
-    if isinstance(v, str) and v in DEESSER_MODES:
+class _Dynamics:
+    """What the three dynamics stages' arguments differ by: the unit's name, its fields (floats, and behind them the de-esser's mode),
+    its presets, the command line's spelling and its C struct.  Everything below that takes one is the same for all three."""
+
+    def __init__(self, unit, fields, presets, spelling, struct, modes=()):
+        self.unit, self.fields, self.presets, self.spelling, self.struct, self.modes = unit, fields, presets, spelling, struct, modes
+        self.nf = len(fields) - bool(modes)  # the float fields
+        self.words = spelling.replace("[", "").replace("]", "").split(":")[:self.nf]
+
+
+_COMPRESSOR = _Dynamics("compressor", COMPRESSOR_FIELDS, COMPRESSOR_PRESETS, "THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]", StnCompressor)
+_EXPANDER = _Dynamics("expander", EXPANDER_FIELDS, EXPANDER_PRESETS, "THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]", StnExpander)
+_DEESSER = _Dynamics("deesser", DEESSER_FIELDS, DEESSER_PRESETS, _DEESSER_SPELLING, StnDeesser, DEESSER_MODES)
+
+
+def _dyn_mode(d, v):
+    if isinstance(v, str) and v in d.modes:
         return v
-    if not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 0 <= int(v) < len(DEESSER_MODES):
-        return DEESSER_MODES[int(v)]
-    raise ValueError(f"deesser: mode must be one of {', '.join(DEESSER_MODES)}, not {v!r}")
+    if not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 0 <= int(v) < len(d.modes):
+        return d.modes[int(v)]
+    raise ValueError(f"{d.unit}: mode must be one of {', '.join(d.modes)}, not {v!r}")
+
+
+def _dyn_spec(d, spec, preset=None, base=None):
+    """the command line's spelling -> the tuple; what is left out comes from base, or from the preset ("speech" unless given)"""
+    parts = str(spec).split(":")
+    if not 2 <= len(parts) <= len(d.fields):
+        raise ValueError(f"{d.unit} {spec!r}: expected {d.spelling}")
+    try:
+        nums = [float(v) for v in parts[:d.nf]]
+    except ValueError:
+        raise ValueError(f"{d.unit} {spec!r}: {', '.join(d.words[:-1])} and {d.words[-1]} must be numbers") from None
+    if len(parts) > d.nf and parts[d.nf] not in d.modes:
+        raise ValueError(f"{d.unit} {spec!r}: MODE must be one of {', '.join(d.modes)}")
+    base = base or d.presets[preset or "speech"]
+    return tuple(nums) + base[len(nums):d.nf] + ((parts[d.nf] if len(parts) > d.nf else base[d.nf],) if d.modes else ())
+
+
+def _dyn_args(d, value, preset):
+    """a setting argument -> the tuple, or None for off (what compressor_args, expander_args and deesser_args document)"""
+    if preset is not None:
+        if preset not in d.presets:
+            raise ValueError(f"{d.unit}_preset {preset!r}: must be one of {', '.join(d.presets)}")
+        if value is None or value is False:
+            value = True
+    if value is None or value is False:
+        return None
+    base = d.presets[preset or "speech"]
+    if value is True:
+        return base
+    if isinstance(value, str):
+        return _dyn_spec(d, value, preset)
+    if isinstance(value, dict):
+        unknown = set(value) - set(d.fields)
+        if unknown:
+            raise ValueError(f"{d.unit}: unknown field {sorted(unknown)[0]!r} ({', '.join(d.fields)})")
+        vals = [value.get(n, v) for n, v in zip(d.fields, base)]
+    elif isinstance(value, (tuple, list)) and len(value) == len(d.fields):
+        vals = list(value)
+    else:
+        n = len(d.fields)
+        raise ValueError(f"{d.unit}: True, a dict of {', '.join(d.fields)}, or {'an' if n == 8 else 'a'} {n}-tuple of them, not {value!r}")
+    for name, v in zip(d.fields[:d.nf], vals):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{d.unit}: {name} must be a finite number, not {v!r}")
+    return tuple(float(v) for v in vals[:d.nf]) + ((_dyn_mode(d, vals[d.nf]),) if d.modes else ())
+
+
+def _dyn_struct(d, value, off_ok=False):
+    """the C struct of a setting argument (off_ok: None for off)"""
+    c = _dyn_args(d, value, None)
+    if c is None:
+        if off_ok:
+            return None
+        raise ValueError(f"{d.unit}: a setting is needed here, not off")
+    return d.struct(*c[:d.nf], *(d.modes.index(m) for m in c[d.nf:]))
+
+
+def _dyn_tuple(d, c):
+    """a C struct as the tuple the *_args give"""
+    return tuple(getattr(c, n) for n in d.fields[:d.nf]) + ((d.modes[c.mode],) if d.modes else ())
+
+
+def _set_dynamics(owner, fn, handle, d, value):
+    """stn_set_<unit> / stn_group_set_<unit> (fn) on an Engine's or a Group's handle"""
+    c = _dyn_struct(d, value, off_ok=True)
+    owner._ck(fn(handle, int(c is not None), None if c is None else ctypes.byref(c)))
+
+
+def _dyn_error(d, value, rate_hz):
+    return getattr(load(), f"stn_{d.unit}_error")(ctypes.byref(_dyn_struct(d, value)), int(rate_hz)).decode()
+
+
+def _dyn_ck(d, rc, what, value, rate_hz):
+    """the return code of the host-only entry stn_<unit>_<what>: StnError with the unit's own reason"""
+    if rc < 0:
+        raise StnError(rc, _dyn_error(d, value, rate_hz) or f"stn_{d.unit}_{what} failed")
+
+
+def _dyn_curve(d, value, in_db):
+    c = _dyn_struct(d, value)
+    x = np.ascontiguousarray(np.atleast_1d(in_db), np.float64)
+    out = np.zeros(x.shape, np.float64)
+    _dyn_ck(d, getattr(load(), f"stn_{d.unit}_curve")(ctypes.byref(c), x.size, x, out), "curve", value, 0)
+    return out
+
+
+def _dyn_coefs(d, value, rate_hz, n, *more):
+    c = _dyn_struct(d, value)
+    k, k32 = np.zeros(n, np.float64), np.zeros(n, np.float32)
+    _dyn_ck(d, getattr(load(), f"stn_{d.unit}_coefs")(ctypes.byref(c), int(rate_hz), k, k32, *more), "coefs", value, rate_hz)
+    return k, k32
+
+
+def parse_compressor_spec(spec):
+    """A command-line compressor "THRESHOLD:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:MAKEUP_DB]]]]" (the speech default's knee 6, attack 5,
+    release 120 and makeup 0 when left out) -> the 6-tuple of floats.  ValueError naming what is wrong."""
+    return _dyn_spec(_COMPRESSOR, spec, base=COMPRESSOR_SPEECH[:2] + _COMPRESSOR_REST)
+
+
+def compressor_args(compressor, preset=None):
+    """A compressor argument -> the 6-tuple of floats (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db), or None for off
+    (None or False).  True is the "speech" default (-24 dB, 3:1, knee 6 dB, attack 5 ms, release 120 ms, makeup 0 dB); a dict names
+    fields and takes the others from that default; a 6-tuple gives all six; a "THRESHOLD:RATIO[:...]" string is the command line's
+    spelling.  preset ("speech") stands for True.  ValueError naming the field for a malformed value or an unknown field or preset; the
+    numeric limits are the C ABI's (compressor_error, Engine.set_compressor)."""
+    return _dyn_args(_COMPRESSOR, compressor, preset)
+
+
+def _compressor_struct(compressor):
+    return _dyn_struct(_COMPRESSOR, compressor)
+
+
+def compressor_error(compressor, rate_hz=0):
+    """Why Engine.set_compressor would refuse the setting (host only): "" when it would not; the message names the field."""
+    return _dyn_error(_COMPRESSOR, compressor, rate_hz)
+
+
+def compressor_coefs(compressor, rate_hz):
+    """(k float64 [2]: kA, kR = -expm1(-1000 / (ms rate)); k32 float32 [2]: what the GPU multiplies by) at rate_hz (host only)."""
+    return _dyn_coefs(_COMPRESSOR, compressor, rate_hz, 2)
+
+
+def compressor_curve(compressor, in_db):
+    """The static curve, makeup included: output level in dB at the input levels in_db (host only, float64)."""
+    return _dyn_curve(_COMPRESSOR, compressor, in_db)
+
+
+def parse_expander_spec(spec, preset=None):
+    """A command-line expander "THRESHOLD:RATIO[:KNEE[:RANGE_DB[:ATTACK_MS[:HOLD_MS[:RELEASE_MS]]]]]" (what is left out comes from the
+    preset, "speech" unless given) -> the 7-tuple of floats.  ValueError naming what is wrong."""
+    return _dyn_spec(_EXPANDER, spec, preset)
+
+
+def expander_args(expander, preset=None):
+    """An expander argument -> the 7-tuple of floats (threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms), or None
+    for off (None or False).  True is the preset ("speech" unless given: -50 dB, 3:1, knee 6 dB, range 24 dB, attack 1 ms, hold 30 ms,
+    release 150 ms; "gate": -45 dB, 20:1, knee 0, range 60 dB, 0.5 ms, 50 ms, 100 ms); a dict names fields and takes the others from
+    the preset; a 7-tuple gives all seven; a "THRESHOLD:RATIO[:...]" string is the command line's spelling.  A preset alone stands for
+    True.  ValueError naming the field for a malformed value or an unknown field or preset; the numeric limits are the C ABI's
+    (expander_error, Engine.set_expander)."""
+    return _dyn_args(_EXPANDER, expander, preset)
+
+
+def _expander_struct(expander):
+    return _dyn_struct(_EXPANDER, expander)
+
+
+def expander_error(expander, rate_hz=0):
+    """Why Engine.set_expander would refuse the setting (host only): "" when it would not; the message names the field."""
+    return _dyn_error(_EXPANDER, expander, rate_hz)
+
+
+def expander_coefs(expander, rate_hz):
+    """(k float64 [3]: kA = -expm1(-1000 / (attack_ms rate)), delta = range_db 1000 / (release_ms rate), Bh = delta32 Hs; k32 float32
+    [3]: what the GPU computes with; Hs: the hold in samples) at rate_hz (host only)."""
+    hs = ctypes.c_int64()
+    k, k32 = _dyn_coefs(_EXPANDER, expander, rate_hz, 3, ctypes.byref(hs))
+    return k, k32, int(hs.value)
+
+
+def expander_curve(expander, in_db):
+    """The static curve: output level in dB at the input levels in_db (host only, float64)."""
+    return _dyn_curve(_EXPANDER, expander, in_db)
 
 
 def parse_deesser_spec(spec):
     """A command-line de-esser "FREQ:THRESHOLD[:RATIO[:KNEE[:ATTACK_MS[:RELEASE_MS[:RANGE_DB[:MODE]]]]]]" (the speech default's values for
     what is left out; MODE split or wide) -> the 8-tuple.  ValueError naming what is wrong."""
-    parts = str(spec).split(":")
-    if not 2 <= len(parts) <= 8:
-        raise ValueError(f"deesser {spec!r}: expected {_DEESSER_SPELLING}")
-    try:
-        nums = [float(v) for v in parts[:7]]
-    except ValueError:
-        raise ValueError(f"deesser {spec!r}: FREQ, THRESHOLD, RATIO, KNEE, ATTACK_MS, RELEASE_MS and RANGE_DB must be numbers") from None
-    if len(parts) == 8 and parts[7] not in DEESSER_MODES:
-        raise ValueError(f"deesser {spec!r}: MODE must be one of {', '.join(DEESSER_MODES)}")
-    return tuple(nums) + DEESSER_SPEECH[len(nums):7] + (parts[7] if len(parts) == 8 else DEESSER_SPEECH[7],)
+    return _dyn_spec(_DEESSER, spec)
 
 
 def deesser_args(deesser, preset=None):
@@ -429,43 +437,17 @@ def deesser_args(deesser, preset=None):
     40 ms, range 12 dB, split); a dict names fields and takes the others from that default; an 8-tuple gives all eight (mode by name, or
     0 / 1); a "FREQ:THRESHOLD[:...]" string is the command line's spelling.  preset ("speech") stands for True.  ValueError naming the
     field for a malformed value or an unknown field or preset; the numeric limits are the C ABI's (deesser_error, Engine.set_deesser)."""
-    if preset is not None:
-        if preset not in DEESSER_PRESETS:
-            raise ValueError(f"deesser_preset {preset!r}: must be one of {', '.join(DEESSER_PRESETS)}")
-        if deesser is None or deesser is False:
-            deesser = True
-    if deesser is None or deesser is False:
-        return None
-    if deesser is True:
-        return DEESSER_PRESETS[preset or "speech"]
-    if isinstance(deesser, str):
-        return parse_deesser_spec(deesser)
-    if isinstance(deesser, dict):
-        unknown = set(deesser) - set(DEESSER_FIELDS)
-        if unknown:
-            raise ValueError(f"deesser: unknown field {sorted(unknown)[0]!r} ({', '.join(DEESSER_FIELDS)})")
-        vals = [deesser.get(n, d) for n, d in zip(DEESSER_FIELDS, DEESSER_SPEECH)]
-    elif isinstance(deesser, (tuple, list)) and len(deesser) == 8:
-        vals = list(deesser)
-    else:
-        raise ValueError(f"deesser: True, a dict of {', '.join(DEESSER_FIELDS)}, or an 8-tuple of them, not {deesser!r}")
-    for name, v in zip(DEESSER_FIELDS[:7], vals):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"deesser: {name} must be a finite number, not {v!r}")
-    return tuple(float(v) for v in vals[:7]) + (_deesser_mode(vals[7]),)
+    return _dyn_args(_DEESSER, deesser, preset)
 
 
 def _deesser_struct(deesser):
-    c = deesser_args(deesser)
-    if c is None:
-        raise ValueError("deesser: a setting is needed here, not off")
-    return StnDeesser(*c[:7], DEESSER_MODES.index(c[7]))
+    return _dyn_struct(_DEESSER, deesser)
 
 
 def deesser_error(deesser, rate_hz=0):
     """Why Engine.set_deesser would refuse the setting at an output rate of rate_hz (host only; 0: the limits that need no rate): ""
     when it would not; the message names the field."""
-    return load().stn_deesser_error(ctypes.byref(_deesser_struct(deesser)), int(rate_hz)).decode()
+    return _dyn_error(_DEESSER, deesser, rate_hz)
 
 
 def deesser_band(deesser, rate_hz):
@@ -473,20 +455,13 @@ def deesser_band(deesser, rate_hz):
     the GPU multiplies by (host only)."""
     s = _deesser_struct(deesser)
     c, c32 = np.zeros(10, np.float64), np.zeros(10, np.float32)
-    rc = load().stn_deesser_band(ctypes.byref(s), int(rate_hz), c, c32)
-    if rc < 0:
-        raise StnError(rc, deesser_error(deesser, rate_hz) or "stn_deesser_band failed")
+    _dyn_ck(_DEESSER, load().stn_deesser_band(ctypes.byref(s), int(rate_hz), c, c32), "band", deesser, rate_hz)
     return c.reshape(2, 5), c32.reshape(2, 5)
 
 
 def deesser_coefs(deesser, rate_hz):
     """(k float64 [2]: kA, kR = -expm1(-1000 / (ms rate)); k32 float32 [2]: what the GPU multiplies by) at rate_hz (host only)."""
-    s = _deesser_struct(deesser)
-    k, k32 = np.zeros(2, np.float64), np.zeros(2, np.float32)
-    rc = load().stn_deesser_coefs(ctypes.byref(s), int(rate_hz), k, k32)
-    if rc < 0:
-        raise StnError(rc, deesser_error(deesser, rate_hz) or "stn_deesser_coefs failed")
-    return k, k32
+    return _dyn_coefs(_DEESSER, deesser, rate_hz, 2)
 
 
 class StnError(RuntimeError):
@@ -925,18 +900,15 @@ class Group:
 
     def set_compressor(self, compressor=None):
         """Compressor of every rank (Engine.set_compressor): the gathered rows are then the single engine's compressed rows."""
-        c = compressor_args(compressor)
-        self._ck(self._lib.stn_group_set_compressor(self._g, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
+        _set_dynamics(self, self._lib.stn_group_set_compressor, self._g, _COMPRESSOR, compressor)
 
     def set_expander(self, expander=None):
         """Expander of every rank (Engine.set_expander): the gathered rows are then the single engine's expanded rows."""
-        c = expander_args(expander)
-        self._ck(self._lib.stn_group_set_expander(self._g, int(c is not None), ctypes.byref(StnExpander(*c)) if c else None))
+        _set_dynamics(self, self._lib.stn_group_set_expander, self._g, _EXPANDER, expander)
 
     def set_deesser(self, deesser=None):
         """De-esser of every rank (Engine.set_deesser): the gathered rows are then the single engine's de-essed rows."""
-        c = deesser_args(deesser)
-        self._ck(self._lib.stn_group_set_deesser(self._g, int(c is not None), ctypes.byref(_deesser_struct(c)) if c else None))
+        _set_dynamics(self, self._lib.stn_group_set_deesser, self._g, _DEESSER, deesser)
 
     def last_shards(self):
         rows, samples = np.zeros(self.n, np.int32), np.zeros(self.n, np.int64)
@@ -1604,130 +1576,117 @@ class Engine:
         o["form"] = form.value.decode()
         return o
 
+    # ---- what the three dynamics stages' methods share (d: _COMPRESSOR, _EXPANDER or _DEESSER)
+    def _get_dynamics(self, d):
+        on, c = ctypes.c_int(), d.struct()
+        self._ck(getattr(self._lib, f"stn_get_{d.unit}")(self._h, ctypes.byref(on), ctypes.byref(c)))
+        return _dyn_tuple(d, c) if on.value else None
+
+    def _batch_rows(self, fn, *dtypes):
+        """a report of one array [B] per dtype -> the tuple of them"""
+        out = tuple(np.zeros(self.batch_dims()[0], t) for t in dtypes)
+        self._ck(fn(self._h, *(a.ctypes.data for a in out)))
+        return out
+
+    def _op_dynamics(self, d, x, hz, value):
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        y = np.empty_like(x)
+        self._ck(getattr(self._lib, f"stn_op_{d.unit}")(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_dyn_struct(d, value)), y))
+        return y
+
+    def _op_dynamics_ex(self, d, x, hz, value, x_misalign, in_place, per_sample, band_states=()):
+        """per_sample: the outputs [rows, W] behind y; band_states: those [rows, Ks, 4]; then the four [rows, Ks], guard_ok and form"""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        Ks = (W + 31) // 32
+        o = dict(y=np.empty_like(x), **{k: np.empty_like(x) for k in per_sample})
+        for k in band_states:
+            o[k] = np.empty((rows, Ks, 4), np.float32)
+        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
+            o[k] = np.empty((rows, Ks), np.float32)
+        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
+        probes = [a.ctypes.data for k, a in o.items() if k != "y"]
+        self._ck(getattr(self._lib, f"stn_op_{d.unit}_ex")(self._h, int(hz), rows, W, x, ctypes.byref(_dyn_struct(d, value)), int(x_misalign),
+                                                            int(in_place), o["y"], *probes, ctypes.byref(ok), form, ctypes.sizeof(form)))
+        o["guard_ok"] = bool(ok.value)
+        o["form"] = form.value.decode()
+        return o
+
     def set_compressor(self, compressor=None):
         """Compress the dynamic range of every row of every fetch on the GPU, at the output rate, behind the filter chain and before
         everything else (trimming, loudness, limiter, encoding, join): None or False = off (the default); True = the "speech" default;
         a dict or 6-tuple as compressor_args takes them, e.g. {"threshold_db": -20, "ratio": 4}.  StnError naming the field for a value
         outside the limits (include/stn.h, "compressor")."""
-        c = compressor_args(compressor)
-        self._ck(self._lib.stn_set_compressor(self._h, int(c is not None), ctypes.byref(StnCompressor(*c)) if c else None))
+        _set_dynamics(self, self._lib.stn_set_compressor, self._h, _COMPRESSOR, compressor)
 
     def get_compressor(self):
         """The setting in force: the 6-tuple (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db), or None when off."""
-        on, c = ctypes.c_int(), StnCompressor()
-        self._ck(self._lib.stn_get_compressor(self._h, ctypes.byref(on), ctypes.byref(c)))
-        return tuple(getattr(c, n) for n in COMPRESSOR_FIELDS) if on.value else None
+        return self._get_dynamics(_COMPRESSOR)
 
     def batch_compressor(self):
         """Per row of the finished batch, the largest reduction in dB the compressor applied over the row's valid samples (float32 [B];
         zeros while it is off)."""
-        out = np.zeros(self.batch_dims()[0], np.float32)
-        self._ck(self._lib.stn_batch_compressor(self._h, out.ctypes.data))
-        return out
+        return self._batch_rows(self._lib.stn_batch_compressor, np.float32)[0]
 
     def op_compressor(self, x, hz, compressor):
         """rows x W fp32 at hz through the compressor on the GPU -> y [rows, W] float32, every row from zero state."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        y = np.empty_like(x)
-        self._ck(self._lib.stn_op_compressor(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_compressor_struct(compressor)), y))
-        return y
+        return self._op_dynamics(_COMPRESSOR, x, hz, compressor)
 
     def op_compressor_ex(self, x, hz, compressor, x_misalign=0, in_place=0):
         """op_compressor with its scratch laid open -> dict: y, gr_db (yL) [rows, W]; s1_end, s1_start, s2_end, s2_start [rows, Ks] (per
         chunk of 32 samples: y1 at its end from zero, y1 at its start after the scan, yL at its end from zero, yL at its start; the
         scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y came back whole); form
         ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y over x on the device."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        rows, W = x.shape
-        Ks = (W + 31) // 32
-        o = dict(y=np.empty_like(x), gr_db=np.empty_like(x))
-        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
-            o[k] = np.empty((rows, Ks), np.float32)
-        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
-        self._ck(self._lib.stn_op_compressor_ex(self._h, int(hz), rows, W, x, ctypes.byref(_compressor_struct(compressor)), int(x_misalign),
-                                                int(in_place), o["y"], o["gr_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
-                                                o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
-        o["guard_ok"] = bool(ok.value)
-        o["form"] = form.value.decode()
-        return o
+        return self._op_dynamics_ex(_COMPRESSOR, x, hz, compressor, x_misalign, in_place, ("gr_db",))
 
     def set_expander(self, expander=None):
         """Turn down what lies under a threshold (the noise floor between words) in every row of every fetch on the GPU, at the output
         rate, behind the filter chain and in front of the de-esser, the compressor and everything else: None or False = off (the
         default); True = the "speech" default; a dict or 7-tuple as expander_args takes them, e.g. {"threshold_db": -45}.  StnError
         naming the field for a value outside the limits (include/stn.h, "expander")."""
-        c = expander_args(expander)
-        self._ck(self._lib.stn_set_expander(self._h, int(c is not None), ctypes.byref(StnExpander(*c)) if c else None))
+        _set_dynamics(self, self._lib.stn_set_expander, self._h, _EXPANDER, expander)
 
     def get_expander(self):
         """The setting in force: the 7-tuple (threshold_db, ratio, knee_db, range_db, attack_ms, hold_ms, release_ms), or None when off."""
-        on, c = ctypes.c_int(), StnExpander()
-        self._ck(self._lib.stn_get_expander(self._h, ctypes.byref(on), ctypes.byref(c)))
-        return tuple(getattr(c, n) for n in EXPANDER_FIELDS) if on.value else None
+        return self._get_dynamics(_EXPANDER)
 
     expander = property(get_expander)
 
     def batch_expander(self):
         """Per row of the finished batch, over the row's valid samples: (min_attenuation_db float32 [B], the least attenuation the
         expander applied; closed_samples int64 [B], the samples at least half closed).  Zeros while it is off."""
-        B = self.batch_dims()[0]
-        att, closed = np.zeros(B, np.float32), np.zeros(B, np.int64)
-        self._ck(self._lib.stn_batch_expander(self._h, att.ctypes.data, closed.ctypes.data))
-        return att, closed
+        return self._batch_rows(self._lib.stn_batch_expander, np.float32, np.int64)
 
     def op_expander(self, x, hz, expander):
         """rows x W fp32 at hz through the expander on the GPU -> y [rows, W] float32, every row from zero state (closed)."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        y = np.empty_like(x)
-        self._ck(self._lib.stn_op_expander(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_expander_struct(expander)), y))
-        return y
+        return self._op_dynamics(_EXPANDER, x, hz, expander)
 
     def op_expander_ex(self, x, hz, expander, x_misalign=0, in_place=0):
         """op_expander with its scratch laid open -> dict: y, open_db (yL) [rows, W]; s1_end, s1_start, s2_end, s2_start [rows, Ks] (per
         chunk of 32 samples: u at its end from zero, u at its start after the scan, yL at its end from zero, yL at its start; the
         scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y came back whole); form
         ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y over x on the device."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        rows, W = x.shape
-        Ks = (W + 31) // 32
-        o = dict(y=np.empty_like(x), open_db=np.empty_like(x))
-        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
-            o[k] = np.empty((rows, Ks), np.float32)
-        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
-        self._ck(self._lib.stn_op_expander_ex(self._h, int(hz), rows, W, x, ctypes.byref(_expander_struct(expander)), int(x_misalign),
-                                              int(in_place), o["y"], o["open_db"].ctypes.data, o["s1_end"].ctypes.data, o["s1_start"].ctypes.data,
-                                              o["s2_end"].ctypes.data, o["s2_start"].ctypes.data, ctypes.byref(ok), form, ctypes.sizeof(form)))
-        o["guard_ok"] = bool(ok.value)
-        o["form"] = form.value.decode()
-        return o
+        return self._op_dynamics_ex(_EXPANDER, x, hz, expander, x_misalign, in_place, ("open_db",))
 
     def set_deesser(self, deesser=None):
         """Turn down the sibilants of every row of every fetch on the GPU, at the output rate, behind the filter chain and in front of the
         compressor and everything else: None or False = off (the default); True = the "speech" default; a dict or 8-tuple as deesser_args
         takes them, e.g. {"freq_hz": 6000, "threshold_db": -28}.  StnError naming the field for a value outside the limits, the two that
         depend on the output rate in force included (include/stn.h, "de-esser")."""
-        c = deesser_args(deesser)
-        self._ck(self._lib.stn_set_deesser(self._h, int(c is not None), ctypes.byref(_deesser_struct(c)) if c else None))
+        _set_dynamics(self, self._lib.stn_set_deesser, self._h, _DEESSER, deesser)
 
     def get_deesser(self):
         """The setting in force: the 8-tuple (freq_hz, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db, mode), or None when off."""
-        on, c = ctypes.c_int(), StnDeesser()
-        self._ck(self._lib.stn_get_deesser(self._h, ctypes.byref(on), ctypes.byref(c)))
-        return tuple(getattr(c, n) for n in DEESSER_FIELDS[:7]) + (DEESSER_MODES[c.mode],) if on.value else None
+        return self._get_dynamics(_DEESSER)
 
     def batch_deesser(self):
         """Per row of the finished batch, the largest reduction in dB the de-esser applied over the row's valid samples (float32 [B];
         zeros while it is off)."""
-        out = np.zeros(self.batch_dims()[0], np.float32)
-        self._ck(self._lib.stn_batch_deesser(self._h, out.ctypes.data))
-        return out
+        return self._batch_rows(self._lib.stn_batch_deesser, np.float32)[0]
 
     def op_deesser(self, x, hz, deesser):
         """rows x W fp32 at hz through the de-esser on the GPU -> y [rows, W] float32, every row from zero state."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        y = np.empty_like(x)
-        self._ck(self._lib.stn_op_deesser(self._h, int(hz), x.shape[0], x.shape[1], x, ctypes.byref(_deesser_struct(deesser)), y))
-        return y
+        return self._op_dynamics(_DEESSER, x, hz, deesser)
 
     def op_deesser_ex(self, x, hz, deesser, x_misalign=0, in_place=0):
         """op_deesser with its scratch laid open -> dict: y, band (h), gr_db (yL) [rows, W]; st_end, st_start [rows, Ks, 4] (the band's
@@ -1735,21 +1694,7 @@ class Engine:
         (y1 and yL likewise; the scratch is poisoned with the quiet NaN 0x7FC00000 first); guard_ok (the poisoned floats around x and y
         came back whole); form ("vec" / "scalar").  x_misalign = 1 places x and y 4 bytes off 16-byte alignment; in_place = 1 writes y
         over x on the device."""
-        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
-        rows, W = x.shape
-        Ks = (W + 31) // 32
-        o = dict(y=np.empty_like(x), band=np.empty_like(x), gr_db=np.empty_like(x))
-        for k in ("st_end", "st_start"):
-            o[k] = np.empty((rows, Ks, 4), np.float32)
-        for k in ("s1_end", "s1_start", "s2_end", "s2_start"):
-            o[k] = np.empty((rows, Ks), np.float32)
-        ok, form = ctypes.c_int(), ctypes.create_string_buffer(16)
-        probes = [o[k].ctypes.data for k in ("band", "gr_db", "st_end", "st_start", "s1_end", "s1_start", "s2_end", "s2_start")]
-        self._ck(self._lib.stn_op_deesser_ex(self._h, int(hz), rows, W, x, ctypes.byref(_deesser_struct(deesser)), int(x_misalign), int(in_place),
-                                             o["y"], *probes, ctypes.byref(ok), form, ctypes.sizeof(form)))
-        o["guard_ok"] = bool(ok.value)
-        o["form"] = form.value.decode()
-        return o
+        return self._op_dynamics_ex(_DEESSER, x, hz, deesser, x_misalign, in_place, ("band", "gr_db"), ("st_end", "st_start"))
 
     def set_loudness(self, target_lufs=None, ceiling_dbfs=-1.0):
         """Normalize every fetch to target_lufs (BS.1770-4 integrated loudness, [-60, 0]) with the gain capped so that the sample

@@ -508,6 +508,11 @@ int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int
     if (biquads_per_section) *biquads_per_section = 2;
     return STN_OK;
 }
+// the argument checks the op entries of the three dynamics stages share (fn: the entry's name, as the message gives it; the flags: _ex's two)
+static void need_op_rows(const std::string& fn, int rows, int W, const void* x, const void* c, const void* y, int x_misalign = 0, int in_place = 0) {
+    need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, (fn + ": bad argument (1 <= rows <= 65535, W >= 1, x, c and y)").c_str());
+    need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), (fn + ": x_misalign and in_place must be 0 or 1").c_str());
+}
 int stn_set_compressor(stn_handle* h, int on, const stn_compressor* c) { STN_TRY(h, { h->eng->set_compressor(on != 0, c); }) }
 int stn_get_compressor(const stn_handle* h, int* on, stn_compressor* out) {
     if (!h) return STN_ERR_INVALID;
@@ -519,13 +524,12 @@ int stn_batch_compressor(stn_handle* h, float* max_reduction_db) {
     STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_compressor(max_reduction_db); })
 }
 int stn_op_compressor(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_compressor: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
                  h->eng->op_compressor(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_compressor_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, int x_misalign, int in_place, float* y,
                          float* gr_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_compressor_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
-                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_compressor_ex: x_misalign and in_place must be 0 or 1");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
                  stn::Engine::CpProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.gr = gr_db;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
@@ -565,14 +569,13 @@ int stn_batch_deesser(stn_handle* h, float* max_reduction_db) {
     STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_deesser(max_reduction_db); })
 }
 int stn_op_deesser(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_deesser: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
                  h->eng->op_deesser(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_deesser_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, int x_misalign, int in_place, float* y,
                       float* band, float* gr_db, float* st_end, float* st_start, float* s1_end, float* s1_start, float* s2_end,
                       float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_deesser_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
-                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_deesser_ex: x_misalign and in_place must be 0 or 1");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
                  stn::Engine::DsProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.band = band; p.gr = gr_db; p.st_end = st_end; p.st_start = st_start;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
@@ -619,13 +622,12 @@ int stn_batch_expander(stn_handle* h, float* min_attenuation_db, int64_t* closed
     STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_expander(min_attenuation_db, closed_samples); })
 }
 int stn_op_expander(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_expander: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
                  h->eng->op_expander(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_expander_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, int x_misalign, int in_place, float* y,
                        float* open_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, "stn_op_expander_ex: bad argument (1 <= rows <= 65535, W >= 1, x, c and y)");
-                 need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), "stn_op_expander_ex: x_misalign and in_place must be 0 or 1");
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
                  stn::Engine::XpProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.open = open_db;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;

@@ -179,9 +179,9 @@ Engine::~Engine() {
     if (pin_tab_) (void)hipHostFree(pin_tab_);
     rs_release();
     fl_release();
-    xp_release();
-    ds_release();
-    cp_release();
+    dyn_release(xp_);
+    dyn_release(ds_);
+    dyn_release(cp_);
     lo_release();  // (the fetch scratch, DevBuf members, goes with the members)
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);

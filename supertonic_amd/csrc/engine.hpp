@@ -8,8 +8,10 @@
 #include <cmath>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <iterator>
 #include <stdexcept>
 #include <string>
@@ -147,6 +149,29 @@ struct Carve {
         off += (count * sizeof(T) + 255) / 256 * 256;
         return base ? reinterpret_cast<T*>(base + o) : nullptr;
     }
+};
+
+// The output stage's chain: the stages that shape the rows a fetch delivers, in the order Engine::out_source runs them.  A stage sees
+// the rows of every stage in front of it and of none behind it.
+enum Stage : int { ST_PITCH, ST_RATE, ST_FILTER, ST_EXPANDER, ST_DEESSER, ST_COMPRESSOR, N_STAGES };
+// The rows at one point of the chain (Engine::rows_id): the finished batch's waveform, the output rate, the row length and the
+// generation of every stage up to and including that point; the later ones stay 0.  Whatever is kept of such rows holds one as its key.
+struct RowsId {
+    uint64_t seq = 0; int hz = 0; int64_t Wo = 0; uint64_t gen[N_STAGES] = {};
+    bool operator==(const RowsId& o) const { return seq == o.seq && hz == o.hz && Wo == o.Wo && std::equal(gen, gen + N_STAGES, o.gen); }
+};
+// One dynamics stage of the chain (expander, de-esser, compressor): what the shared host skeleton (engine_internal.hpp) works on.  The
+// limits, the curve, the table, the scratch layout and the launches are the stage's own (engine_<stage>.cpp).
+template <typename Set, typename Table>
+struct DynStage {
+    bool on = false;
+    Set set;                       // the setting in force (the "speech" default until one is set)
+    uint64_t gen = 0;              // bumped by every change of the setting
+    struct Made { Table t; Set from{}; };  // a table (device copies owned here) and the setting it was made from
+    Made tab, op_tab;              // at the output rate, and of the op entry
+    DevBuf buf;                    // fetch-time scratch of the launches: exists only once a fetch ran with the stage on
+    std::vector<int64_t> n; const int64_t* n_ptr = nullptr; int64_t n_W = 0;  // the spans buf holds, where, and (de-esser) beside which width
+    RowsId key; const void* key_buf = nullptr; bool valid = false;            // what the row results in buf belong to, and the scratch
 };
 
 struct KernelStat { double ms = 0; long launches = 0; double flops = 0; double bytes = 0; };
@@ -520,8 +545,8 @@ class Engine {
     // then exactly the one without it).  On, out_source() delivers the rows at the output rate compressed in place in the fetch scratch,
     // behind the filter chain (kernels_compressor.hip), and everything behind it runs on those.
     void set_compressor(bool on, const stn_compressor* c);
-    bool compressor_on() const { return cp_on_; }
-    const stn_compressor& compressor() const { return cp_set_; }
+    bool compressor_on() const { return cp_.on; }
+    const stn_compressor& compressor() const { return cp_.set; }
     void batch_compressor(float* max_reduction_db);
     // the op-level probe: gr [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
     struct CpProbe {
@@ -537,8 +562,8 @@ class Engine {
     // exactly the one without it).  On, out_source() delivers the rows at the output rate de-essed in place in the fetch scratch, behind
     // the filter chain and in front of the compressor (kernels_deesser.hip), and everything behind it runs on those.
     void set_deesser(bool on, const stn_deesser* c);
-    bool deesser_on() const { return ds_on_; }
-    const stn_deesser& deesser() const { return ds_set_; }
+    bool deesser_on() const { return ds_.on; }
+    const stn_deesser& deesser() const { return ds_.set; }
     void batch_deesser(float* max_reduction_db);
     // the op-level probe: band and gr [rows][W], the band's states [rows][Ks][4] and the detector's four arrays [rows][Ks] (host, or
     // null), the poisoned guards, the staging form
@@ -556,8 +581,8 @@ class Engine {
     // exactly the one without it).  On, out_source() delivers the rows at the output rate expanded in place in the fetch scratch, behind
     // the filter chain and in front of the de-esser (kernels_expander.hip), and everything behind it runs on those.
     void set_expander(bool on, const stn_expander* c);
-    bool expander_on() const { return xp_on_; }
-    const stn_expander& expander() const { return xp_set_; }
+    bool expander_on() const { return xp_.on; }
+    const stn_expander& expander() const { return xp_.set; }
     void batch_expander(float* min_attenuation_db, int64_t* closed_samples);
     // the op-level probe: open [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
     struct XpProbe {
@@ -843,7 +868,7 @@ class Engine {
     // ---- pitch (engine_pitch.cpp)
     float ps_semi_ = 0.0f;             // the setting in force and its ratio (1 / 1: off)
     int ps_a_ = 1, ps_b_ = 1;
-    uint64_t ps_gen_ = 0;              // bumped by every set_pitch: part of EdKey, CpKey and DsKey (all see the shifted rows)
+    uint64_t ps_gen_ = 0;              // bumped by every set_pitch
     ResampleTable ps_rs_, op_ps_rs_;   // the b / a tables of the setting and of the op entries, cached per (a, b) (device copies owned here)
     void ps_table(ResampleTable& t, int a, int b);
     DevBuf ps_buf_;                    // fetch-time scratch of the shift: exists only once a fetch ran with pitch on
@@ -909,7 +934,7 @@ class Engine {
     void lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st);
     // ---- filter chain (engine_filter.cpp)
     std::vector<stn_filter> fl_set_;   // the chain in force
-    uint64_t fl_gen_ = 0;              // bumped by every set_filters: part of EdKey (edges found on other rows must not be reused)
+    uint64_t fl_gen_ = 0;              // bumped by every set_filters
     FilterTable fl_, op_fl_;           // the section passes of the chain at the output rate, and of op_filter (device copies owned here)
     DevBuf fl_buf_;                    // fetch-time scratch of the section passes
     // per chunk the state (16 B) and pass 1's peak (unused), per row the length (every row's is W): what the measurement's launches take
@@ -922,83 +947,49 @@ class Engine {
     // probe (or null): the states of every pass read out, the state buffer poisoned before each
     void fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const FlScratch& sc, float* y, FlProbe* probe);
     void fl_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) through the chain in force into y (may be x)
-    // ---- compressor (engine_compressor.cpp)
-    bool cp_on_ = false;
-    stn_compressor cp_set_{-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f};  // the setting in force (the "speech" default until one is set)
-    uint64_t cp_gen_ = 0;              // bumped by every change of the setting: part of EdKey, as fl_gen_
-    CompTable cp_, op_cp_;             // the tables at the output rate, and of op_compressor (device copies owned here)
-    DevBuf cp_buf_;                    // fetch-time scratch of the five launches
-    // per chunk y1 and yL (end values, then start values) and the maximum of yL, per row that maximum and the valid length
-    struct CpScratch { float *s1, *s2, *cmax, *rmax; int64_t* n; size_t bytes; };
-    static CpScratch cp_layout(char* base, int64_t rows, int64_t W);
-    std::vector<int64_t> cp_n_; const int64_t* cp_n_ptr_ = nullptr;  // the lengths cp_buf_ holds
-    // what the row maxima in cp_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
-    struct CpKey {
-        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, cp = 0; int64_t Wo = 0; const void* buf = nullptr;
-        uint64_t ds = 0;  // ds_gen_ of the de-esser setting in front of it
-        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
-        uint64_t xp = 0;  // xp_gen_ of the expander setting in front of it
-        bool operator==(const CpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && cp == o.cp && Wo == o.Wo && buf == o.buf && ds == o.ds && ps == o.ps && xp == o.xp; }
-    };
-    CpKey cp_key_; bool cp_valid_ = false;
-    void cp_prepare(CompTable& t, int hz, const stn_compressor& c);
-    void cp_release();
-    // the five launches and the row maxima on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read
-    // out where the sequence leaves it
-    void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
-    CpScratch cp_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) compressed into y (may be x)
-    // ---- de-esser (engine_deesser.cpp)
-    bool ds_on_ = false;
-    stn_deesser ds_set_{5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT};  // the setting in force (the "speech" default until one is set)
-    uint64_t ds_gen_ = 0;              // bumped by every change of the setting: part of EdKey and of CpKey (both see the de-essed rows)
-    DeessTable ds_, op_ds_;            // the tables at the output rate, and of op_deesser (device copies owned here)
-    DevBuf ds_buf_;                    // fetch-time scratch of the eight launches
-    // per chunk the band's state, y1 and yL (end values, then start values), the band pass's max |x| (unused) and the maximum of yL; per
-    // row that maximum, the width (the band's launches) and the valid length (the maxima)
+    // ---- the chain's identity (engine_batch.cpp): the rows behind `stage`, Wo samples each, as everything kept of them is keyed
+    RowsId rows_id(Stage stage, int64_t Wo) const;
+    // ---- the three dynamics stages: each file holds its layout and its launches; the skeleton around them is shared (engine_internal.hpp)
+    // A scratch holds per chunk the stage's state arrays and partial results, per row the results and the valid length n; nw: the width
+    // as every row's length, which only the de-esser's band launches take (null in the others)
+    // compressor (engine_compressor.cpp): y1 and yL (end values, then start values) and the maximum of yL
+    struct CpScratch { float *s1, *s2, *cmax, *rmax; int64_t *n, *nw; size_t bytes; };
+    // de-esser (engine_deesser.cpp): the band's state and max |x| (unused) in front of the compressor's arrays
     struct DsScratch { float *st, *pk, *s1, *s2, *cmax, *rmax; int64_t *nw, *n; size_t bytes; };
+    // expander (engine_expander.cpp): u and yL, the minimum of R - yL and the count of yL <= R / 2
+    struct XpScratch { float *s1, *s2, *cmin, *rmin; int32_t* ccnt; int64_t *rcnt, *n, *nw; size_t bytes; };
+    static CpScratch cp_layout(char* base, int64_t rows, int64_t W);
     static DsScratch ds_layout(char* base, int64_t rows, int64_t W);
-    std::vector<int64_t> ds_n_; const int64_t* ds_n_ptr_ = nullptr; int64_t ds_n_W_ = 0;  // the lengths ds_buf_ holds
-    // what the row maxima in ds_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
-    struct DsKey {
-        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, ds = 0; int64_t Wo = 0; const void* buf = nullptr;
-        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
-        uint64_t xp = 0;  // xp_gen_ of the expander setting in front of it
-        bool operator==(const DsKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && ds == o.ds && Wo == o.Wo && buf == o.buf && ps == o.ps && xp == o.xp; }
-    };
-    DsKey ds_key_; bool ds_valid_ = false;
-    void ds_prepare(DeessTable& t, int hz, const stn_deesser& c);
-    void ds_release();
-    // the eight launches on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read out where the
-    // sequence leaves it
-    void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
-    DsScratch ds_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) de-essed into y (may be x)
-    // ---- expander (engine_expander.cpp)
-    bool xp_on_ = false;
-    stn_expander xp_set_{-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f};  // the setting in force (the "speech" default until one is set)
-    uint64_t xp_gen_ = 0;              // bumped by every change of the setting: part of EdKey, DsKey and CpKey (all see the expanded rows)
-    ExpTable xp_, op_xp_;              // the tables at the output rate, and of op_expander (device copies owned here)
-    DevBuf xp_buf_;                    // fetch-time scratch of the six launches: exists only once a fetch ran with the expander on
-    // per chunk u and yL (end values, then start values), the minimum of R - yL and the count of yL <= R / 2; per row those two and
-    // the valid length
-    struct XpScratch { float *s1, *s2, *cmin, *rmin; int32_t* ccnt; int64_t *rcnt, *n; size_t bytes; };
     static XpScratch xp_layout(char* base, int64_t rows, int64_t W);
-    std::vector<int64_t> xp_n_; const int64_t* xp_n_ptr_ = nullptr;  // the lengths xp_buf_ holds
-    // what the row results in xp_buf_ belong to: the finished batch's waveform, the output rate, the chain, the setting, the scratch
-    struct XpKey {
-        uint64_t seq = 0; int hz = 0; uint64_t fl = 0, xp = 0; int64_t Wo = 0; const void* buf = nullptr;
-        uint64_t ps = 0;  // ps_gen_ of the pitch the rows came with
-        bool operator==(const XpKey& o) const { return seq == o.seq && hz == o.hz && fl == o.fl && xp == o.xp && Wo == o.Wo && buf == o.buf && ps == o.ps; }
-    };
-    XpKey xp_key_; bool xp_valid_ = false;
-    void xp_prepare(ExpTable& t, int hz, const stn_expander& c);
-    void xp_release();
-    // the six launches on rows x W fp32 (x; row stride W) into y (may be x); probe (or null): every state array read out where the
-    // sequence leaves it
+    DynStage<stn_compressor, CompTable> cp_{false, {-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f}};
+    DynStage<stn_deesser, DeessTable> ds_{false, {5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT}};
+    DynStage<stn_expander, ExpTable> xp_{false, {-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f}};
+    // the stage's launches (five and the row maxima, eight, six) on rows x W fp32 (x; row stride W) into y (may be x); probe (or null):
+    // every state array read out where the sequence leaves it; gr / band / open: the per-sample outputs (rows x W on the device, or null)
+    void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
+    void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
     void xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const XpScratch& sc, float* y, float* open, XpProbe* probe);
-    XpScratch xp_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) expanded into y (may be x)
-    // out_source() returns the fp32 fetch scratch (row stride Wo), not the rows the stage starts from (wav_rows(): b.wav, or with pitch on
-    // the shifted rows in the pitch scratch, row stride W like b.wav: pitch alone needs no second copy)
-    bool out_in_scratch() const { return resample_on() || filter_on() || expander_on() || deesser_on() || compressor_on(); }
+    // out_source's hooks: the finished batch's B rows x Wo (x) through the stage into y (may be x)
+    void cp_batch(const float* x, int64_t Wo, float* y);
+    void ds_batch(const float* x, int64_t Wo, float* y);
+    void xp_batch(const float* x, int64_t Wo, float* y);
+    // the skeleton (engine_internal.hpp).  dyn_prepare: m is the table of (hz, c), made by `build` and uploaded unless it is that already.
+    // dyn_batch: the fetch hook around `run`, the stage's launches on the carved scratch (table, scratch, spans, launches, key).
+    // dyn_report: a report's preamble around `read`, which is given the scratch to read the rows' results from, or null while the stage
+    // is off (zeros).  dyn_op: the op entry around `run`; taps: the per-sample outputs (host, or null), in the order `run` is handed
+    // their device rows.  read_rows: one result per row of the batch device -> host (dev null: zeros; host null: nothing)
+    template <class Made, class Set, class Build> void dyn_prepare(Made& m, int hz, const Set& c, Build build);
+    template <class St, class Build, class Layout, class Run> void dyn_batch(St& st, Stage stage, int64_t Wo, Build build, Layout layout, Run run);
+    template <class St, class Layout, class Read> void dyn_report(St& st, Stage stage, Layout layout, bool wanted, Read read);
+    template <class St, class Set, class Probe, class Build, class Layout, class Run>
+    void dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& c, float* y, Probe* probe, Build build, Layout layout,
+                std::initializer_list<float*> taps, const char* (*form)(const float*, const float*, int64_t), Run run);
+    template <class T> void read_rows(T* host, const T* dev);
+    // shapes_rows: a stage behind the rate is on (the set enqueue_output's store-from-scratch branch asks for).  out_in_scratch:
+    // out_source() returns the fp32 fetch scratch (row stride Wo); otherwise, pitch or nothing, wav_rows(): b.wav or the shifted rows
+    // in the pitch scratch, row stride W like b.wav
+    bool shapes_rows() const { return filter_on() || expander_on() || deesser_on() || compressor_on(); }
+    bool out_in_scratch() const { return resample_on() || shapes_rows(); }
     bool st_on_ = false;
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
@@ -1016,20 +1007,13 @@ class Engine {
     bool pl_on_ = false;
     float pl_ms_ = 300.0f;
     int pl_stride(bool pauses, int64_t W, int hz) const { return pauses ? pause_stride(W, hz, pause_samples(hz, pl_ms_)) : 0; }
-    // what the scratch holds: the edges (and per-row programmes) of batch `seq` at rate hz under (db, keep, fade); host: read back
+    // what the scratch holds: the edges (and per-row programmes) of the rows behind the whole chain under (db, keep, fade) and mp, the
+    // max_pause_ms of the cuts held beside the edges (0: none); host: read back
     struct EdKey {
-        uint64_t seq = 0; int hz = 0; float db = 0, keep = 0, fade = 0; int64_t Wo = 0; const void* buf = nullptr;
-        float mp = 0;  // max_pause_ms of the cuts held beside the edges; 0: none
-        uint64_t fl = 0;  // fl_gen_ of the filter chain the rows went through
-        uint64_t cp = 0;  // cp_gen_ of the compressor setting they went through
-        uint64_t ds = 0;  // ds_gen_ of the de-esser setting they went through
-        uint64_t ps = 0;  // ps_gen_ of the pitch they were shifted by
-        uint64_t xp = 0;  // xp_gen_ of the expander setting they went through
-        bool operator==(const EdKey& o) const {
-            return seq == o.seq && hz == o.hz && db == o.db && keep == o.keep && fade == o.fade && Wo == o.Wo && buf == o.buf && mp == o.mp && fl == o.fl && cp == o.cp && ds == o.ds &&
-                   ps == o.ps && xp == o.xp;
-        }
+        RowsId rows; const void* buf = nullptr; float db = 0, keep = 0, fade = 0, mp = 0;
+        bool operator==(const EdKey& o) const { return rows == o.rows && buf == o.buf && db == o.db && keep == o.keep && fade == o.fade && mp == o.mp; }
     };
+    EdKey ed_key(int64_t Wo, bool pauses) const { return {rows_id(ST_COMPRESSOR, Wo), ed_buf_.get(), st_db_, st_keep_, st_fade_, pauses ? pl_ms_ : 0.0f}; }
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
     std::vector<int64_t> ed_host_, ed_n_;   // [B][2] edges read back; [B] spans
     std::vector<int64_t> pz_host_; int pz_S_ = 0;  // [B][2 S] the rows' cut lists read back with the edges (key.mp != 0)

@@ -450,16 +450,24 @@ const float* Engine::out_source(int64_t Wo) {
     const float* wav = wav_rows();
     if (!out_in_scratch()) return wav;
     float* d = out_f32_buf((size_t)b.B * Wo);
-    if (resample_on()) resample_enqueue(rs_table(), wav, b.B, native_row_len(), ENC_F32, d, Wo);
-    // section 18: the chain runs on the rows at the output rate, in place behind the resampler, out of b.wav (left as it is) otherwise
-    if (filter_on()) fl_batch(resample_on() ? d : wav, Wo, d);
-    // section 21: the de-esser behind the chain, in place in the scratch, out of b.wav (left as it is) when nothing ran in front of it
-    // section 25: the expander behind the chain and in front of the de-esser, likewise
-    if (expander_on()) xp_batch(resample_on() || filter_on() ? d : wav, Wo, d);
-    if (deesser_on()) ds_batch(resample_on() || filter_on() || expander_on() ? d : wav, Wo, d);
-    // section 20: the compressor behind those, likewise
-    if (compressor_on()) cp_batch(resample_on() || filter_on() || expander_on() || deesser_on() ? d : wav, Wo, d);
+    // the chain in the order of Stage, behind the pitch: the first stage that is on reads the rows it starts from (left as they are) and
+    // writes the scratch, every later one runs in place there (sections 18, 25, 21 and 20)
+    const float* cur = wav;
+    if (resample_on()) { resample_enqueue(rs_table(), cur, b.B, native_row_len(), ENC_F32, d, Wo); cur = d; }
+    if (filter_on()) { fl_batch(cur, Wo, d); cur = d; }
+    if (expander_on()) { xp_batch(cur, Wo, d); cur = d; }
+    if (deesser_on()) { ds_batch(cur, Wo, d); cur = d; }
+    if (compressor_on()) { cp_batch(cur, Wo, d); cur = d; }
     return d;
+}
+
+RowsId Engine::rows_id(Stage stage, int64_t Wo) const {
+    // the generation of every stage, in the order of Stage (the rate's is hz itself): the one list of what rows depend on
+    const uint64_t gen[] = {ps_gen_, 0, fl_gen_, xp_.gen, ds_.gen, cp_.gen};
+    static_assert(sizeof(gen) / sizeof(gen[0]) == N_STAGES, "one generation per stage of the chain");
+    RowsId id{ed_seq_, output_rate(), Wo, {}};
+    std::copy(gen, gen + stage + 1, id.gen);
+    return id;
 }
 
 // section 15: with the limiter active the store, the cut and the join run on the limited rows
@@ -504,7 +512,7 @@ void Engine::enqueue_output(const OutRows& o) {
         const GainedRows r = gain_step(src, b.B, Wo, Wo, lo_batch(src, Wo, true));
         StageSpan span(*this, "out", "loudness_gain", (double)b.B * Wo, (double)b.B * Wo * (4 + eb));
         launch_store_rows(s_, r.src, b.B, Wo, r.g, o.enc, o.dst, o.stride, out_dither(DITHER_ROW));
-    } else if (filter_on() || expander_on() || deesser_on() || compressor_on()) {
+    } else if (shapes_rows()) {
         // sections 18, 20, 21 and 25: the filtered, expanded, de-essed and / or compressed rows are in the fetch scratch; an fp32 fetch that was handed that scratch as its destination is done
         const float* src = out_source(Wo);
         if (src != o.dst) {

@@ -12,17 +12,6 @@ namespace stn {
 
 namespace {
 
-void fields(const stn_deesser& c, float out[7]) {
-    const float v[7] = {c.freq_hz, c.threshold_db, c.ratio, c.knee_db, c.attack_ms, c.release_ms, c.range_db};
-    std::copy(v, v + 7, out);
-}
-
-bool same_setting(const float a[7], int mode, const stn_deesser& c) {
-    float b[7];
-    fields(c, b);
-    return mode == c.mode && std::equal(a, a + 7, b);
-}
-
 // the Butterworth pair's q: 1 / (2 cos(pi / 8)) and 1 / (2 cos(3 pi / 8)), as the fp32 values the contract names
 constexpr float kQ[2] = {0.54119610f, 1.30656296f};
 
@@ -32,12 +21,15 @@ void deesser_band(const stn_deesser& c, stn_filter f[2]) {
     for (int i = 0; i < 2; ++i) f[i] = stn_filter{STN_FILT_HIGHPASS, c.freq_hz, kQ[i], 0.0f};
 }
 
+std::array<Lim, 7> limits(const stn_deesser& c) {
+    return {{{"freq_hz", c.freq_hz, 2000.0f, 12000.0f}, {"threshold_db", c.threshold_db, -60.0f, 0.0f}, {"ratio", c.ratio, 1.0f, 20.0f},
+             {"knee_db", c.knee_db, 0.0f, 24.0f},       {"attack_ms", c.attack_ms, 0.1f, 300.0f},       {"release_ms", c.release_ms, 10.0f, 3000.0f},
+             {"range_db", c.range_db, 1.0f, 24.0f}}};
+}
+
 std::string deesser_check(const stn_deesser* c, int rate_hz) {
     if (!c) return "deesser: c is null";
-    const Lim lim[7] = {{"freq_hz", c->freq_hz, 2000.0f, 12000.0f}, {"threshold_db", c->threshold_db, -60.0f, 0.0f}, {"ratio", c->ratio, 1.0f, 20.0f},
-                        {"knee_db", c->knee_db, 0.0f, 24.0f},       {"attack_ms", c->attack_ms, 0.1f, 300.0f},       {"release_ms", c->release_ms, 10.0f, 3000.0f},
-                        {"range_db", c->range_db, 1.0f, 24.0f}};
-    const std::string out = range_check("deesser", lim);
+    const std::string out = range_check("deesser", limits(*c));
     if (!out.empty()) return out;
     if (c->mode != STN_DEESS_SPLIT && c->mode != STN_DEESS_WIDE) return "deesser: mode " + std::to_string(c->mode) + " is not STN_DEESS_SPLIT (0) or STN_DEESS_WIDE (1)";
     if (rate_hz <= 0) return "";  // (no model loaded yet: the corners are checked when the band is first designed)
@@ -54,8 +46,6 @@ void deesser_table(int hz, const stn_deesser& c, DeessTable& t) {
     refuse(deesser_check(&c, hz));
     refuse(rate_check("deesser", hz));
     t.hz = hz;
-    fields(c, t.set);
-    t.mode = c.mode;
     t.split = c.mode == STN_DEESS_SPLIT;
     // the band: one section pass of the chain, designed and rounded as stn_filter_coefs does
     stn_filter f[2];
@@ -80,42 +70,7 @@ void deesser_table(int hz, const stn_deesser& c, DeessTable& t) {
     t.coef.range = c.range_db;
 }
 
-void Engine::ds_prepare(DeessTable& t, int hz, const stn_deesser& c) {
-    if (t.hz == hz && t.band.dev && t.det.dev && same_setting(t.set, t.mode, c)) return;
-    DeessTable nt;
-    deesser_table(hz, c, nt);
-    STN_HIP(hipSetDevice(device_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&nt.band.dev), nt.band.mpow.size() * sizeof(double)));
-    STN_HIP(hipMemcpyAsync(nt.band.dev, nt.band.mpow.data(), nt.band.mpow.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&nt.det.dev), nt.det.pw.size() * sizeof(double)));
-    STN_HIP(hipMemcpyAsync(nt.det.dev, nt.det.pw.data(), nt.det.pw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    sync();  // (the uploads read nt's host copies, and a fetch may still be reading the old tables)
-    if (t.band.dev) (void)hipFree(t.band.dev);
-    if (t.det.dev) (void)hipFree(t.det.dev);
-    t = std::move(nt);
-}
-
-void Engine::ds_release() {
-    for (DeessTable* t : {&ds_, &op_ds_}) {
-        if (t->band.dev) { (void)hipFree(t->band.dev); t->band.dev = nullptr; }
-        if (t->det.dev) { (void)hipFree(t->det.dev); t->det.dev = nullptr; }
-    }
-}
-
-void Engine::set_deesser(bool on, const stn_deesser* c) {
-    if (!on) {
-        if (ds_on_) ++ds_gen_;
-        ds_on_ = false;
-        return;
-    }
-    refuse(deesser_check(c, loaded_ ? output_rate() : 0));
-    float now[7];
-    fields(ds_set_, now);
-    if (ds_on_ && same_setting(now, ds_set_.mode, *c)) return;
-    ds_set_ = *c;
-    ds_on_ = true;
-    ++ds_gen_;
-}
+void Engine::set_deesser(bool on, const stn_deesser* c) { dyn_set(ds_, on, c, on ? deesser_check(c, loaded_ ? output_rate() : 0) : ""); }
 
 Engine::DsScratch Engine::ds_layout(char* base, int64_t rows, int64_t W) {
     const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
@@ -172,76 +127,17 @@ void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64
     STN_HIP(hipGetLastError());
 }
 
-// the hook of every fetch path: the finished batch's rows at the output rate (x: b.wav, or the rows already in y) de-essed into y, the
-// fetch scratch
-Engine::DsScratch Engine::ds_batch(const float* x, int64_t Wo, float* y) {
-    const Batch& b = bt_;
-    const int hz = output_rate();
-    ds_prepare(ds_, hz, ds_set_);
-    bool moved = false;
-    char* base = ds_buf_.reserve(*this, ds_layout(nullptr, b.B, Wo).bytes, &moved);
-    const DsScratch sc = ds_layout(base, b.B, Wo);
-    // row b's valid samples: section 11's span, its reported duration at the output rate; uploaded once per finished batch, with the
-    // width the band's two launches take as every row's length
-    std::vector<int64_t> n = out_spans(Wo, hz);
-    if (moved || n != ds_n_ || ds_n_ptr_ != sc.n || ds_n_W_ != Wo) {
-        ds_n_ = std::move(n);
-        ds_n_ptr_ = sc.n;
-        ds_n_W_ = Wo;
-        const std::vector<int64_t> nw((size_t)b.B, Wo);
-        STN_HIP(hipMemcpyAsync(sc.n, ds_n_.data(), ds_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-        STN_HIP(hipMemcpyAsync(sc.nw, nw.data(), nw.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-        sync();  // (the uploads read ds_n_, which the next batch's lengths replace, and nw, this frame's; once per finished batch, as cp_batch)
-    }
-    ds_enqueue(ds_, x, b.B, Wo, sc, y, nullptr, nullptr, nullptr);
-    ds_key_ = DsKey{ed_seq_, hz, fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_, xp_gen_};
-    ds_valid_ = true;
-    return sc;
+void Engine::ds_batch(const float* x, int64_t Wo, float* y) {
+    dyn_batch(ds_, ST_DEESSER, Wo, deesser_table, ds_layout, [&](const DsScratch& sc) { ds_enqueue(ds_.tab.t, x, bt_.B, Wo, sc, y, nullptr, nullptr, nullptr); });
 }
 
 void Engine::batch_deesser(float* max_reduction_db) {
-    const int64_t Wo = out_row_len();
-    if (!max_reduction_db) return;
-    if (!deesser_on()) {  // nothing is turned down
-        std::fill(max_reduction_db, max_reduction_db + bt_.B, 0.0f);
-        return;
-    }
-    // the row maxima a fetch of this batch under this rate, chain and setting left in ds_buf_ are the report; otherwise the sequence runs
-    const DsKey key{ed_seq_, output_rate(), fl_gen_, ds_gen_, Wo, ds_buf_.get(), ps_gen_, xp_gen_};
-    if (!(ds_valid_ && key == ds_key_)) (void)out_source(Wo);
-    const DsScratch sc = ds_layout(ds_buf_.reserve(*this, ds_layout(nullptr, bt_.B, Wo).bytes), bt_.B, Wo);
-    STN_HIP(hipMemcpyAsync(max_reduction_db, sc.rmax, (size_t)bt_.B * 4, hipMemcpyDeviceToHost, s_));
-    sync();
+    dyn_report(ds_, ST_DEESSER, ds_layout, max_reduction_db != nullptr, [&](const DsScratch* sc) { read_rows(max_reduction_db, sc ? sc->rmax : nullptr); });
 }
 
 void Engine::op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe) {
-    STN_HIP(hipSetDevice(device_));
-    ds_prepare(op_ds_, hz, c);
-    ar_.reset();
-    const size_t nx = (size_t)rows * W;
-    GuardedRows r(*this, nx, x, probe, probe && probe->x_misalign, probe && probe->in_place);
-    float* dband = probe && probe->band ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
-    float* dgr = probe && probe->gr ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
-    const size_t sc_bytes = ds_layout(nullptr, rows, W).bytes;
-    char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
-    const DsScratch sc = ds_layout(sb, rows, W);
-    if (probe) {
-        for (float* b : {dband, dgr})
-            if (b) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx, s_));
-        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
-    }
-    const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.nw, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ds_enqueue(op_ds_, r.dx, rows, W, sc, r.dy, probe, dband, dgr);
-    r.download(y);
-    if (dband) STN_HIP(hipMemcpyAsync(probe->band, dband, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (dgr) STN_HIP(hipMemcpyAsync(probe->gr, dgr, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (probe) {
-        probe->guard_ok = r.guards_ok();
-        probe->form = deesser_staging_form(r.dx, r.dy, W);
-    }
-    sync();
+    dyn_op(ds_, hz, rows, W, x, c, y, probe, deesser_table, ds_layout, {probe ? probe->band : nullptr, probe ? probe->gr : nullptr}, deesser_staging_form,
+           [&](const DeessTable& t, const DsScratch& sc, const float* dx, float* dy, float* const* tap) { ds_enqueue(t, dx, rows, W, sc, dy, probe, tap[0], tap[1]); });
 }
 
 }  // namespace stn

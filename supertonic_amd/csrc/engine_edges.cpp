@@ -104,7 +104,7 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo, bool pauses) {
     const int hz = output_rate();
     refuse(rate_check("silence trim", hz));
     const EdScratch sc = ed_scratch(b.B, Wo, hz, pl_stride(pauses, Wo, hz));
-    const EdKey key{ed_seq_, hz, st_db_, st_keep_, st_fade_, Wo, ed_buf_.get(), pauses ? pl_ms_ : 0.0f, fl_gen_, cp_gen_, ds_gen_, ps_gen_, xp_gen_};
+    const EdKey key = ed_key(Wo, pauses);
     if (ed_valid_ && key == ed_key_) return sc;
     // row b's span: section 11's, its reported duration at the output rate
     ed_n_ = out_spans(Wo, hz);
@@ -118,7 +118,7 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo, bool pauses) {
 
 const std::vector<int64_t>& Engine::ed_batch_host(bool pauses) {
     const int64_t Wo = out_row_len();
-    const EdKey key{ed_seq_, output_rate(), st_db_, st_keep_, st_fade_, Wo, ed_buf_.get(), pauses ? pl_ms_ : 0.0f, fl_gen_, cp_gen_, ds_gen_, ps_gen_, xp_gen_};
+    const EdKey key = ed_key(Wo, pauses);
     if (ed_valid_ && ed_host_valid_ && key == ed_key_) return ed_host_;
     const EdScratch sc = (ed_valid_ && key == ed_key_) ? ed_scratch(bt_.B, Wo, output_rate(), pl_stride(pauses, Wo, output_rate()))
                                                        : ed_batch(out_source(Wo), Wo, pauses);

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 
 namespace stn {
@@ -27,8 +28,8 @@ inline std::string num(double v) {
 
 // why a setting of `unit` is refused, or "": the first field outside its range, "<unit>: <name> <v> must be in [<lo>, <hi>]"
 struct Lim { const char* name; float v, lo, hi; };
-template <size_t N>
-inline std::string range_check(const char* unit, const Lim (&lim)[N]) {
+template <class Lims>
+inline std::string range_check(const char* unit, const Lims& lim) {
     for (const Lim& l : lim)  // (a NaN fails both comparisons)
         if (!(l.v >= l.lo && l.v <= l.hi)) return std::string(unit) + ": " + l.name + " " + num(l.v) + " must be in [" + num(l.lo) + ", " + num(l.hi) + "]";
     return "";
@@ -65,4 +66,147 @@ struct GuardedRows {
         return std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == 0x7FC00000u; });
     }
 };
+
+// ---- the host skeleton of the three dynamics stages (DynStage) --------------------------------------------------
+// A stage's fields with their limits, in the order of its struct: the one list its check and its equality walk (engine_<stage>.cpp)
+std::array<Lim, 6> limits(const stn_compressor& c);
+std::array<Lim, 7> limits(const stn_deesser& c);
+std::array<Lim, 7> limits(const stn_expander& c);
+template <class Set> inline bool same_tail(const Set&, const Set&) { return true; }
+inline bool same_tail(const stn_deesser& a, const stn_deesser& b) { return a.mode == b.mode; }
+// float == per field (so -0.0f is 0.0f, and a NaN, which no check lets in, is no setting's equal)
+template <class Set>
+inline bool same_setting(const Set& a, const Set& b) {
+    const auto x = limits(a), y = limits(b);
+    for (size_t i = 0; i < x.size(); ++i)
+        if (!(x[i].v == y[i].v)) return false;
+    return same_tail(a, b);
+}
+// a table's device copies with the host arrays they are made from, in upload order
+struct DevTab { double** dev; const std::vector<double>* host; };
+inline std::array<DevTab, 1> dev_tables(CompTable& t) { return {{{&t.dev, &t.pw}}}; }
+inline std::array<DevTab, 1> dev_tables(ExpTable& t) { return {{{&t.dev, &t.pw}}}; }
+inline std::array<DevTab, 2> dev_tables(DeessTable& t) { return {{{&t.band.dev, &t.band.mpow}, {&t.det.dev, &t.det.pw}}}; }
+
+// set_<stage>: off bumps the generation only if the stage was on, the same setting again bumps nothing, a refused one changes nothing
+template <class St, class Set>
+inline void dyn_set(St& st, bool on, const Set* c, const std::string& why) {
+    if (!on) {
+        if (st.on) ++st.gen;
+        st.on = false;
+        return;
+    }
+    refuse(why);
+    if (st.on && same_setting(st.set, *c)) return;
+    st.set = *c;
+    st.on = true;
+    ++st.gen;
+}
+
+template <class St>
+inline void dyn_release(St& st) {
+    for (auto* m : {&st.tab, &st.op_tab})
+        for (DevTab d : dev_tables(m->t))
+            if (*d.dev) { (void)hipFree(*d.dev); *d.dev = nullptr; }
+}
+
+template <class Made, class Set, class Build>
+void Engine::dyn_prepare(Made& m, int hz, const Set& c, Build build) {
+    const auto tabs = dev_tables(m.t);
+    if (m.t.hz == hz && std::all_of(tabs.begin(), tabs.end(), [](const DevTab& d) { return *d.dev != nullptr; }) && same_setting(m.from, c)) return;
+    Made nm;
+    build(hz, c, nm.t);
+    nm.from = c;
+    STN_HIP(hipSetDevice(device_));
+    for (DevTab d : dev_tables(nm.t)) {
+        STN_HIP(hipMalloc(reinterpret_cast<void**>(d.dev), d.host->size() * sizeof(double)));
+        STN_HIP(hipMemcpyAsync(*d.dev, d.host->data(), d.host->size() * sizeof(double), hipMemcpyHostToDevice, s_));
+    }
+    sync();  // (the uploads read nm's host copies, and a fetch may still be reading the old tables)
+    for (DevTab d : tabs)
+        if (*d.dev) (void)hipFree(*d.dev);
+    m = std::move(nm);
+}
+
+template <class St, class Build, class Layout, class Run>
+void Engine::dyn_batch(St& st, Stage stage, int64_t Wo, Build build, Layout layout, Run run) {
+    const int hz = output_rate();
+    dyn_prepare(st.tab, hz, st.set, build);
+    bool moved = false;
+    char* base = st.buf.reserve(*this, layout(nullptr, bt_.B, Wo).bytes, &moved);
+    const auto sc = layout(base, bt_.B, Wo);
+    // row b's valid samples: section 11's span, its reported duration at the output rate; uploaded once per finished batch, with the
+    // width where the stage's launches take one (sc.nw)
+    std::vector<int64_t> n = out_spans(Wo, hz);
+    if (moved || n != st.n || st.n_ptr != sc.n || (sc.nw && st.n_W != Wo)) {
+        st.n = std::move(n);
+        st.n_ptr = sc.n;
+        st.n_W = Wo;
+        const std::vector<int64_t> nw(sc.nw ? (size_t)bt_.B : 0, Wo);
+        STN_HIP(hipMemcpyAsync(sc.n, st.n.data(), st.n.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+        if (sc.nw) STN_HIP(hipMemcpyAsync(sc.nw, nw.data(), nw.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+        sync();  // (the uploads read st.n, which the next batch's lengths replace, and nw, this frame's; once per finished batch, as fl_batch)
+    }
+    run(sc);
+    st.key = rows_id(stage, Wo);
+    st.key_buf = st.buf.get();
+    st.valid = true;
+}
+
+template <class St, class Layout, class Read>
+void Engine::dyn_report(St& st, Stage stage, Layout layout, bool wanted, Read read) {
+    const int64_t Wo = out_row_len();
+    if (!wanted) return;
+    if (!st.on) {  // nothing is turned down
+        read(static_cast<decltype(layout(nullptr, 0, 0))*>(nullptr));
+        return;
+    }
+    // the row results a fetch of this batch under this rate, chain and setting left in the scratch are the report; otherwise the sequence runs
+    if (!(st.valid && st.key == rows_id(stage, Wo) && st.key_buf == st.buf.get())) (void)out_source(Wo);
+    const auto sc = layout(st.buf.reserve(*this, layout(nullptr, bt_.B, Wo).bytes), bt_.B, Wo);
+    read(&sc);
+    sync();
+}
+
+template <class T>
+void Engine::read_rows(T* host, const T* dev) {
+    if (!host) return;
+    if (!dev) std::fill(host, host + bt_.B, T(0));
+    else STN_HIP(hipMemcpyAsync(host, dev, (size_t)bt_.B * sizeof(T), hipMemcpyDeviceToHost, s_));
+}
+
+template <class St, class Set, class Probe, class Build, class Layout, class Run>
+void Engine::dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& c, float* y, Probe* probe, Build build, Layout layout,
+                    std::initializer_list<float*> taps, const char* (*form)(const float*, const float*, int64_t), Run run) {
+    STN_HIP(hipSetDevice(device_));
+    dyn_prepare(st.op_tab, hz, c, build);
+    ar_.reset();
+    const size_t nx = (size_t)rows * W;
+    GuardedRows r(*this, nx, x, probe, probe && probe->x_misalign, probe && probe->in_place);
+    std::vector<float*> dev;
+    for (float* h : taps) dev.push_back(h ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr);
+    const size_t sc_bytes = layout(nullptr, rows, W).bytes;
+    char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
+    const auto sc = layout(sb, rows, W);
+    if (probe) {
+        for (float* d : dev)
+            if (d) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7FC00000, nx, s_));
+        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
+    }
+    const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
+    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    if (sc.nw) STN_HIP(hipMemcpyAsync(sc.nw, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    run(st.op_tab.t, sc, r.dx, r.dy, dev.data());
+    r.download(y);
+    size_t i = 0;
+    for (float* h : taps) {
+        if (h) STN_HIP(hipMemcpyAsync(h, dev[i], nx * 4, hipMemcpyDeviceToHost, s_));
+        ++i;
+    }
+    if (probe) {
+        probe->guard_ok = r.guards_ok();
+        probe->form = form(r.dx, r.dy, W);
+    }
+    sync();
+}
 }  // namespace stn

@@ -98,7 +98,7 @@ void Engine::set_output_rate(int hz) {
     // (section 18) a chain in force must stay inside its limits at the new rate
     if (loaded_) refuse(filter_check((int)fl_set_.size(), fl_set_.data(), hz == 0 ? a_.sample_rate : hz));
     // (section 21) and so must a de-esser in force
-    if (loaded_ && ds_on_) refuse(deesser_check(&ds_set_, hz == 0 ? a_.sample_rate : hz));
+    if (loaded_ && ds_.on) refuse(deesser_check(&ds_.set, hz == 0 ? a_.sample_rate : hz));
     STN_HIP(hipSetDevice(device_));
     // with a model loaded the pair is designed now (a refused pair leaves the previous rate in force); otherwise at the first fetch
     if (loaded_ && hz != 0 && hz != a_.sample_rate) rs_prepare(rs_, a_.sample_rate, hz);

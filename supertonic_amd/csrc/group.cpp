@@ -245,24 +245,17 @@ int stn_group_set_filters(stn_group* g, int n, const stn_filter* f) {
         const S* p = static_cast<const S*>(a);
         return stn_set_filters(h, p->n, p->f); }, &v, 0);
 }
-int stn_group_set_compressor(stn_group* g, int on, const stn_compressor* c) {
-    struct S { int on; const stn_compressor* c; } v{on, c};
-    return for_all(g, "stn_set_compressor", [](stn_handle* h, const void* a, uint64_t) {
+// the three dynamics stages' settings: one forward, by the single engine's setter
+extern "C++" template <class Set, int (*set)(stn_handle*, int, const Set*)>
+static int set_dynamics(stn_group* g, const char* name, int on, const Set* c) {
+    struct S { int on; const Set* c; } v{on, c};
+    return for_all(g, name, [](stn_handle* h, const void* a, uint64_t) {
         const S* p = static_cast<const S*>(a);
-        return stn_set_compressor(h, p->on, p->c); }, &v, 0);
+        return set(h, p->on, p->c); }, &v, 0);
 }
-int stn_group_set_deesser(stn_group* g, int on, const stn_deesser* c) {
-    struct S { int on; const stn_deesser* c; } v{on, c};
-    return for_all(g, "stn_set_deesser", [](stn_handle* h, const void* a, uint64_t) {
-        const S* p = static_cast<const S*>(a);
-        return stn_set_deesser(h, p->on, p->c); }, &v, 0);
-}
-int stn_group_set_expander(stn_group* g, int on, const stn_expander* c) {
-    struct S { int on; const stn_expander* c; } v{on, c};
-    return for_all(g, "stn_set_expander", [](stn_handle* h, const void* a, uint64_t) {
-        const S* p = static_cast<const S*>(a);
-        return stn_set_expander(h, p->on, p->c); }, &v, 0);
-}
+int stn_group_set_compressor(stn_group* g, int on, const stn_compressor* c) { return set_dynamics<stn_compressor, stn_set_compressor>(g, "stn_set_compressor", on, c); }
+int stn_group_set_deesser(stn_group* g, int on, const stn_deesser* c) { return set_dynamics<stn_deesser, stn_set_deesser>(g, "stn_set_deesser", on, c); }
+int stn_group_set_expander(stn_group* g, int on, const stn_expander* c) { return set_dynamics<stn_expander, stn_set_expander>(g, "stn_set_expander", on, c); }
 int stn_group_set_pause_limit(stn_group* g, int on, float max_pause_ms) {
     if (!g) return STN_ERR_INVALID;
     (void)max_pause_ms;

@@ -608,7 +608,6 @@ const char* filter_staging_form(const float* x, const float* y, int64_t W);
 struct CompCoef { float T, S, K, kA, kR, makeup; };  // threshold dB, 1 / ratio - 1, knee dB, attack and release k, makeup dB (fp32)
 struct CompTable {
     int hz = 0;
-    float set[6] = {};                // the stn_compressor fields the table was made from
     CompCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: D^(i+1) then E^(i+1), D = (1 - kR)^LO_CHUNK, E = (1 - kA)^LO_CHUNK
     double* dev = nullptr;            // device copy (owned by whoever uploaded it)
@@ -634,7 +633,6 @@ const char* compressor_staging_form(const float* x, const float* y, int64_t W);
 struct ExpCoef { float T, S, K, R, kA, delta, Bh; };  // threshold dB, ratio - 1, knee dB, range dB, attack k, release dB per sample, hold boost dB (fp32)
 struct ExpTable {
     int hz = 0;
-    float set[7] = {};                // the stn_expander fields the table was made from
     int64_t hold = 0;                 // Hs, the hold in samples
     ExpCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: (i + 1) LO_CHUNK delta then E^(i+1), E = (1 - kA)^LO_CHUNK
@@ -659,8 +657,6 @@ const char* expander_staging_form(const float* x, const float* y, int64_t W);
 struct DeessCoef { LoudCoef band; float T, S, K, kA, kR, range; };  // the two high-pass sections; threshold dB, 1 / ratio - 1, knee dB, k, range dB
 struct DeessTable {
     int hz = 0;
-    float set[7] = {};                // the stn_deesser fields the table was made from, and its mode
-    int mode = 0;
     bool split = true;                // mode == STN_DEESS_SPLIT
     DeessCoef coef{};
     LoudTable band;                   // the band's section pass: coefficients and the powers of its M (hop = 1, unused)
