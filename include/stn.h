@@ -294,7 +294,8 @@ int stn_op_encode_ex(stn_handle* h, int enc, int rows, int W, const float* x, in
  * resampled by b / a back to its length (the duration is restored, the pitch moves).  Both steps run in front of every other stage of
  * the output stage, so rate, filters, de-esser, compressor, loudness, limiter, trim, pause limit, join, encodings and dither all see
  * the shifted rows; row length, spans and reported durations do not change.  0 (the default) is off: nothing is launched and no scratch
- * exists.  Formants move with the pitch (a resampling shifter), the value is one per handle, and the tempo is the model's `speed`.
+ * exists.  Formants move with the pitch (a resampling shifter) unless the pitch mode is STN_PITCH_FORMANT (section "formant" below);
+ * the value is one per handle, and the tempo is the model's `speed`.
  * Handle state that no captured graph depends on.  DESIGN.md section 24.
  *
  * The stretch at rate hz: hop H, the smallest power of two with 128 H >= hz; grain N = 2 H; search radius D = 3 H / 4; window the periodic
@@ -330,6 +331,44 @@ int stn_op_time_stretch(stn_handle* h, int hz, int rows, int W, const float* x, 
                         int32_t* delta_or_null, float* score_or_null);
 /* ... and the whole shift: the stretch by stn_pitch_ratio(semitones) and the resample back, y [rows][W] fp32 (host) */
 int stn_op_pitch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float semitones, float* y);
+
+/* ---- formant (the pitch mode) ----------------------------------------------------------------------------
+ * STN_PITCH_RESAMPLE (the default) delivers the shifted rows as the section above describes them.  STN_PITCH_FORMANT ends the pitch
+ * stage with a correction that puts the spectral envelope of the row before the shift back onto the shifted row, so that the pitch
+ * moves and the formants stay.  The mode has no effect while pitch is 0: nothing is launched and no scratch exists.  One value per
+ * handle; handle state that no captured graph depends on.  DESIGN.md section 26.
+ *
+ * The rule at rate hz, on x (the row before the shift) and y (the shifted row), both of span n and 0.0 outside [0, n): hop H and window
+ * w of the pitch stage, N = 2 H, frames m = 0 .. ceil(W / H) over [s_m, s_m + N), s_m = (m - 1) H, order
+ * p = min(48, max(10, 2 ceil(hz / 2000) + 2)).  Per frame and signal: xw[i] = float32(w[i] x[s_m + i]); R[k] = sum_i xw[i] xw[i + k],
+ * k = 0 .. p, in double; R'[0] = 1.0001 R[0] + 1e-9 and R'[k] = R[k] exp(-0.5 (2 pi 60 k / hz)^2); Levinson-Durbin in double gives
+ * a[0 .. p], a[0] = 1, and the final error E.  Per frame g = clamp(sqrt(E_x / E_y), 1/2, 2), and the float32 tables ax[k] = a_x[k],
+ * cy[k] = g a_y[k].  Frame m filters y from zero state at n0 = s_m - N (y taken as 0.0 before n0 and from n on):
+ * e[j] = sum_{k=0..p} cy[k] y[j - k], v_m[j] = e[j] - sum_{k=1..p} ax[k] v_m[j - k] for j in [n0, s_m + N), in float32.
+ * out[m H + i] = w[H + i] v_m[m H + i] + w[i] v_{m+1}[m H + i] for i in [0, H), and out[j] = 0.0 for j >= n.  The warm-up of N
+ * samples is part of the rule.  A row's result depends on its own samples only. */
+#define STN_PITCH_RESAMPLE 0
+#define STN_PITCH_FORMANT 1
+/* Host only: the geometry at hz for rows of W samples, each output or NULL, and the lag window lag[0 .. min(p + 1, cap)) in double when
+ * lag is not NULL.  STN_ERR_INVALID for hz outside [8000, 192000] or W outside [0, 2^40] */
+int stn_formant_plan(int hz, int64_t W, int* H, int* p, int64_t* frames, double* lag_or_null, size_t cap);
+/* Host only: the conditioning and the recursion in double on the caller's lags r[0 .. p], 1 <= p <= 48, at hz (the lag window's rate):
+ * a[0 .. p], *err = E and, when not NULL, the p reflection coefficients */
+int stn_formant_lpc(int hz, const double* r, int p, double* a, double* err, double* refl_or_null);
+/* any other value: STN_ERR_INVALID, and the previous mode stays */
+int stn_set_pitch_mode(stn_handle* h, int mode);
+/* the mode, or STN_ERR_INVALID for a NULL handle */
+int stn_get_pitch_mode(const stn_handle* h);
+/* op-level: the correction of the batch path on the caller's rows.  x and y [rows][W] fp32 (host) at hz, row r's span n[r] in [0, W]
+ * (NULL: W); out [rows][W] fp32 (host) */
+int stn_op_formant(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n_or_null, float* out);
+/* ... and with the tables handed out: ax and cy [rows][frames][p + 1] fp32, g, ex and ey [rows][frames] double (host, each or NULL),
+ * computed on scratch filled with NaN before the launches; *guard_ok: the 64 NaN words on either side of x, y and out on the device are
+ * still there */
+int stn_op_formant_ex(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n_or_null, float* out, float* ax_or_null,
+                      float* cy_or_null, double* g_or_null, double* ex_or_null, double* ey_or_null, int* guard_ok);
+/* stn_op_pitch under a mode.  STN_PITCH_FORMANT: bit for bit stn_op_formant(x, stn_op_pitch(x)) */
+int stn_op_pitch_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, float semitones, int mode, float* y);
 
 /* ---- join ----------------------------------------------------------------------------------------------
  * Consecutive rows of the finished batch concatenated on the GPU, with a run of silence between them, into G programmes (the chunks of

@@ -62,6 +62,8 @@ int stn_group_set_peak_mode(stn_group* g, int mode);
 int stn_group_set_dither(stn_group* g, int mode, uint64_t seed);
 /* pitch of every rank (stn_set_pitch): rows are shifted on their own, so the gathered rows are the single engine's */
 int stn_group_set_pitch(stn_group* g, float semitones);
+/* pitch mode of every rank (stn_set_pitch_mode; no effect without pitch): STN_PITCH_RESAMPLE or STN_PITCH_FORMANT */
+int stn_group_set_pitch_mode(stn_group* g, int mode);
 /* filter chain of every rank (stn_set_filters): rows are filtered on their own, so the gathered rows are the single engine's */
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f);
 /* compressor of every rank (stn_set_compressor): rows are compressed on their own, so the gathered rows are the single engine's */

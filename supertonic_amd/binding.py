@@ -776,7 +776,13 @@ def load():
     L.stn_group_set_pitch.argtypes = [vp, cf]
     L.stn_op_time_stretch.argtypes = [vp, ci, ci, ci, _f32p, vp, ci, ci, vp, vp, vp]
     L.stn_op_pitch.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, vp]
-    jp = ctypes.POINTER(StnJoin)
+    L.stn_set_pitch_mode.argtypes = [vp, ci]
+    L.stn_get_pitch_mode.argtypes = [vp]
+    L.stn_group_set_pitch_mode.argtypes = [vp, ci]
+    L.stn_op_formant.argtypes = [vp, ci, ci, ci, _f32p, _f32p, vp, vp]
+    L.stn_op_formant_ex.argtypes = [vp, ci, ci, ci, _f32p, _f32p, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(ci)]
+    L.stn_op_pitch_ex.argtypes = [vp, ci, ci, ci, _f32p, vp, cf, ci, vp]
+    jp =ctypes.POINTER(StnJoin)
     L.stn_batch_join_dims.argtypes = [vp, jp, ctypes.POINTER(ctypes.c_int64), vp, vp]
     L.stn_batch_fetch_joined.argtypes = [vp, jp, ci, vp, ctypes.c_size_t, vp, vp]
     L.stn_batch_copy_joined_device.argtypes = [vp, jp, ci, vp, ctypes.c_int64]
@@ -892,6 +898,10 @@ class Group:
     def set_pitch(self, semitones=None):
         """Pitch of every rank (Engine.set_pitch): rows are shifted on their own, so the gathered rows are the single engine's."""
         self._ck(self._lib.stn_group_set_pitch(self._g, pitch_args(semitones)))
+
+    def set_pitch_mode(self, mode="resample"):
+        """Pitch mode of every rank (Engine.set_pitch_mode): "resample" or "formant"."""
+        self._ck(self._lib.stn_group_set_pitch_mode(self._g, pitch_mode_id(mode)))
 
     def set_filters(self, filters=None):
         """Filter chain of every rank (Engine.set_filters): the gathered rows are then the single engine's filtered rows."""
@@ -1179,6 +1189,55 @@ def pitch_window(hz):
     w = np.empty(n.value, np.float32)
     _pitch_lib().stn_pitch_window(int(hz), w.ctypes.data, w.size, ctypes.byref(n))
     return w
+
+
+# the pitch mode (STN_PITCH_*, include/stn.h "formant")
+PITCH_RESAMPLE, PITCH_FORMANT = 0, 1
+PITCH_MODES = {"resample": PITCH_RESAMPLE, "formant": PITCH_FORMANT}
+PITCH_MODE_NAMES = {v: k for k, v in PITCH_MODES.items()}
+
+
+def pitch_mode_id(mode):
+    """A pitch-mode argument -> STN_PITCH_RESAMPLE / STN_PITCH_FORMANT: "resample" or "formant" (None: "resample"); anything else is a
+    ValueError."""
+    if mode is None:
+        return PITCH_RESAMPLE
+    if isinstance(mode, str) and mode in PITCH_MODES:
+        return PITCH_MODES[mode]
+    raise ValueError(f"pitch_mode: 'resample' or 'formant', not {mode!r}")
+
+
+def pitch_mode_name(mode):
+    """The normalized name of a pitch-mode argument: None reads as "resample"."""
+    return PITCH_MODE_NAMES[pitch_mode_id(mode)]
+
+
+def _formant_lib():
+    L = load()
+    ci, i64, dp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+    L.stn_formant_plan.argtypes = [ci, i64, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(i64), dp, ctypes.c_size_t]
+    L.stn_formant_lpc.argtypes = [ci, dp, ci, dp, ctypes.POINTER(ctypes.c_double), dp]
+    return L
+
+
+def formant_plan(hz, W):
+    """The formant correction's geometry (host only; stn_formant_plan) -> dict H, N, p, frames and lag (the lag window, float64 [p + 1])."""
+    H, p, F = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    lag = np.zeros(49, np.float64)
+    if _formant_lib().stn_formant_plan(int(hz), int(W), ctypes.byref(H), ctypes.byref(p), ctypes.byref(F), lag.ctypes.data, lag.size) < 0:
+        raise StnError(-1, f"stn_formant_plan: bad argument (hz {hz}, W {W})")
+    return dict(H=H.value, N=2 * H.value, p=p.value, frames=F.value, lag=lag[:p.value + 1].copy())
+
+
+def formant_lpc(hz, r):
+    """The conditioning and Levinson-Durbin in double on the lags r [p + 1] at hz (host only; stn_formant_lpc) -> (a float64 [p + 1],
+    the final error, the reflection coefficients float64 [p])."""
+    r = np.ascontiguousarray(r, np.float64)
+    p = r.size - 1
+    a, k, e = np.empty(p + 1, np.float64), np.empty(max(p, 0), np.float64), ctypes.c_double()
+    if _formant_lib().stn_formant_lpc(int(hz), r.ctypes.data, p, a.ctypes.data, ctypes.byref(e), k.ctypes.data) < 0:
+        raise StnError(-1, f"stn_formant_lpc: bad argument (hz {hz}, p {p})")
+    return a, e.value, k
 
 
 def _dither_lib():
@@ -2017,14 +2076,53 @@ class Engine:
                                                d.ctypes.data, sc.ctypes.data))
         return y, d, sc
 
-    def op_pitch(self, x, hz, semitones, n=None):
-        """rows x W fp32 at hz shifted by `semitones` on the GPU (stn_op_pitch: the stretch, then the resample back) -> [rows, W]."""
+    def op_pitch(self, x, hz, semitones, n=None, mode=None):
+        """rows x W fp32 at hz shifted by `semitones` on the GPU (stn_op_pitch: the stretch, then the resample back; mode="formant":
+        stn_op_pitch_ex, the formant correction behind them) -> [rows, W]."""
         x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
         rows, W = x.shape
         nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
         y = np.empty((rows, W), np.float32)
-        self._ck(self._lib.stn_op_pitch(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(semitones), y.ctypes.data))
+        if pitch_mode_id(mode) == PITCH_RESAMPLE:
+            self._ck(self._lib.stn_op_pitch(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(semitones), y.ctypes.data))
+        else:
+            self._ck(self._lib.stn_op_pitch_ex(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, float(semitones),
+                                               pitch_mode_id(mode), y.ctypes.data))
         return y
+
+    def set_pitch_mode(self, mode="resample"):
+        """What set_pitch delivers (stn_set_pitch_mode): "resample" (the default: formants move with the pitch) or "formant" (the
+        spectral envelope of the rows before the shift is put back onto the shifted rows on the GPU).  With pitch off it has no effect."""
+        self._ck(self._lib.stn_set_pitch_mode(self._h, pitch_mode_id(mode)))
+
+    @property
+    def pitch_mode(self):
+        """"resample" or "formant"."""
+        return PITCH_MODE_NAMES[self._ck_mode(self._lib.stn_get_pitch_mode(self._h))]
+
+    def op_formant(self, x, y, hz, n=None, ex=False):
+        """The formant correction on the caller's rows (stn_op_formant): x (before the shift) and y (shifted), rows x W fp32 at hz, row
+        r's span n[r] (None: W) -> out [rows, W].  ex=True (stn_op_formant_ex) -> dict out, ax and cy [rows, frames, p + 1] float32,
+        g, ex and ey [rows, frames] float64, and guard_ok."""
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        y = np.ascontiguousarray(np.atleast_2d(y), np.float32)
+        if x.shape != y.shape:
+            raise ValueError(f"op_formant: x {x.shape} and y {y.shape} must have one shape")
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        np_ = None if nn is None else nn.ctypes.data
+        out = np.empty((rows, W), np.float32)
+        if not ex:
+            self._ck(self._lib.stn_op_formant(self._h, int(hz), rows, W, x, y, np_, out.ctypes.data))
+            return out
+        p = formant_plan(hz, W)
+        o = dict(out=out, ax=np.empty((rows, p["frames"], p["p"] + 1), np.float32), cy=np.empty((rows, p["frames"], p["p"] + 1), np.float32),
+                 g=np.empty((rows, p["frames"]), np.float64), ex=np.empty((rows, p["frames"]), np.float64), ey=np.empty((rows, p["frames"]), np.float64))
+        ok = ctypes.c_int()
+        self._ck(self._lib.stn_op_formant_ex(self._h, int(hz), rows, W, x, y, np_, out.ctypes.data, o["ax"].ctypes.data, o["cy"].ctypes.data,
+                                             o["g"].ctypes.data, o["ex"].ctypes.data, o["ey"].ctypes.data, ctypes.byref(ok)))
+        o["guard_ok"] = bool(ok.value)
+        return o
 
     def set_dither(self, dither=None, seed=None):
         """How the 16- and 24-bit PCM stores of every fetch quantize (stn_set_dither): None / False / "off" (the default: truncation),

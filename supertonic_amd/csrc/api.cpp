@@ -689,6 +689,24 @@ int stn_op_pitch(stn_handle* h, int hz, int rows, int W, const float* x, const i
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pitch: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
                  h->eng->op_pitch(hz, rows, W, x, n, semitones, y); })
 }
+int stn_set_pitch_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_pitch_mode(mode); }) }
+int stn_get_pitch_mode(const stn_handle* h) { return h ? h->eng->pitch_mode() : STN_ERR_INVALID; }
+int stn_op_formant(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y && out, "stn_op_formant: bad argument (1 <= rows <= 65535, W >= 1, x, y and out)");
+                 h->eng->op_formant(hz, rows, W, x, y, n, out); })
+}
+int stn_op_formant_ex(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out, float* ax, float* cy, double* g,
+                      double* ex, double* ey, int* guard_ok) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y && out, "stn_op_formant_ex: bad argument (1 <= rows <= 65535, W >= 1, x, y and out)");
+                 stn::Engine::FormantProbe p;
+                 p.ax = ax; p.cy = cy; p.g = g; p.ex = ex; p.ey = ey;
+                 h->eng->op_formant(hz, rows, W, x, y, n, out, &p);
+                 if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0; })
+}
+int stn_op_pitch_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float semitones, int mode, float* y) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pitch_ex: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+                 h->eng->op_pitch_ex(hz, rows, W, x, n, semitones, mode, y); })
+}
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
 int stn_get_peak_mode(const stn_handle* h) { return h ? h->eng->peak_mode() : STN_ERR_INVALID; }
 int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_phase) {

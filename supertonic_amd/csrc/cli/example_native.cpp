@@ -27,6 +27,8 @@
 // --expander-preset {speech,gate} (-50 dB, 3:1 and those; -45 dB, 20:1, no knee, 60 dB, 0.5 ms, 50 ms, 100 ms),
 // --pitch SEMITONES (every utterance shifted by that many semitones, -12 to 12, on the GPU without a change of length, in front of
 // everything else; absent or 0: off),
+// --pitch-mode {resample,formant} (what --pitch does to the formants: they move with the pitch, the default, or the spectral envelope
+// of the audio before the shift is put back on the GPU),
 // --loudness-report (after each saved file one line "Loudness: integrated .. LUFS, range .. LU, max momentary .. LUFS, max short-term ..
 // LUFS (N short-term windows), peak .., gain ..": measured on the GPU before the loudness gain, three decimals, a long text as the
 // joined programme; one GPU only).
@@ -157,6 +159,12 @@ int main(int argc, char* argv[]) {
             if (v.empty() || *end) { std::cerr << "Error: --pitch '" << v << "': a number of semitones in [-12, 12]\n"; return 1; }
             const char* why = stn_pitch_error(opts.pitch);
             if (why[0]) { std::cerr << "Error: --" << why << "\n"; return 1; }
+        }
+        else if (a == "--pitch-mode" && more) {  // what --pitch does to the formants
+            const std::string v = argv[++i];
+            if (v == "resample") opts.pitch_mode = STN_PITCH_RESAMPLE;
+            else if (v == "formant") opts.pitch_mode = STN_PITCH_FORMANT;
+            else { std::cerr << "Error: --pitch-mode '" << v << "': resample or formant\n"; return 1; }
         }
         else if (a == "--dither" && more) {  // how pcm16 / pcm24 files are quantized on the GPU: truncation (off, the default), rounding, or rounding behind dither
             const std::string why = parseDitherMode(argv[++i], opts.dither);

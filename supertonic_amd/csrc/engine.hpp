@@ -22,6 +22,7 @@
 #include "host/len_tables.hpp"
 #include "host/join_plan.hpp"
 #include "host/pause_plan.hpp"
+#include "host/formant.hpp"
 #include "host/pitch.hpp"
 #include "kernels.hpp"
 
@@ -395,6 +396,23 @@ class Engine {
     void op_time_stretch(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int* delta, float* score);
     // the same rows shifted by `semitones` -> y [rows][W] (host): the stretch and the resample behind it
     void op_pitch(int hz, int rows, int W, const float* x, const int64_t* n, float semitones, float* y);
+    // ---- pitch mode (include/stn.h "formant"): STN_PITCH_RESAMPLE (the default) delivers the shifted rows as
+    // they are; STN_PITCH_FORMANT puts the spectral envelope of the rows before the shift back onto them (kernels_formant.hip) at the
+    // end of the pitch stage.  No effect while pitch is off: nothing is launched and no scratch exists.
+    void set_pitch_mode(int mode);  // throws for any other value; the previous mode then stays
+    int pitch_mode() const { return ps_mode_; }
+    // the op-level probe: the tables [rows][frames][p + 1] and the per-frame gain and errors [rows][frames] (host, each or null), on
+    // scratch poisoned before the launches, and whether the guard words around x, y and out still hold the poison
+    struct FormantProbe {
+        float *ax = nullptr, *cy = nullptr;
+        double *g = nullptr, *ex = nullptr, *ey = nullptr;
+        bool guard_ok = false;  // out
+    };
+    // x (the rows before the shift) and y (the shifted rows), rows x W fp32 (host) at hz with spans n (host, or null: W) -> out
+    // [rows][W] (host): the launches of the batch path on the caller's rows
+    void op_formant(int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out, FormantProbe* probe = nullptr);
+    // op_pitch under a mode: with STN_PITCH_FORMANT, bit for bit op_formant(x, op_pitch(x))
+    void op_pitch_ex(int hz, int rows, int W, const float* x, const int64_t* n, float semitones, int mode, float* y);
     // launch_store_rows on the caller's whole buffers: x [rows][W] (host) placed x_misalign floats behind a 16-byte boundary on the
     // device, gain and row_id [rows] (host) or null, y [rows][dst_stride] samples of enc (host; copied in, stored into, copied out)
     void op_encode_ex(int enc, int rows, int W, const float* x, int x_misalign, const float* gain, const int64_t* row_id, int mode, uint64_t seed,
@@ -868,7 +886,7 @@ class Engine {
     // ---- pitch (engine_pitch.cpp)
     float ps_semi_ = 0.0f;             // the setting in force and its ratio (1 / 1: off)
     int ps_a_ = 1, ps_b_ = 1;
-    uint64_t ps_gen_ = 0;              // bumped by every set_pitch
+    uint64_t ps_gen_ = 0;              // bumped by every set_pitch and by every change of the pitch mode
     ResampleTable ps_rs_, op_ps_rs_;   // the b / a tables of the setting and of the op entries, cached per (a, b) (device copies owned here)
     void ps_table(ResampleTable& t, int a, int b);
     DevBuf ps_buf_;                    // fetch-time scratch of the shift: exists only once a fetch ran with pitch on
@@ -888,7 +906,16 @@ class Engine {
                     float* ys);
     // the stretched rows resampled by t (b / a) into y [rows][W]: the first W outputs of each
     void ps_resample(const ResampleTable& t, const float* ys, int64_t rows, int64_t Ws, int64_t W, float* y);
-    void ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out);
+    void ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out,
+               int mode = 0);
+    // ---- formant correction (engine_formant.cpp): the end of the pitch stage under STN_PITCH_FORMANT
+    int ps_mode_ = 0;                  // STN_PITCH_RESAMPLE; every change bumps ps_gen_
+    // the lag window, per (row, frame) the two tables, the gain and the two errors, and the corrected rows [rows][W]
+    struct FmScratch { double* lagw; float *ax, *cy; double *g, *ex, *ey; float* out; size_t bytes; };
+    static FmScratch fm_layout(char* base, int64_t rows, int64_t W, const FormantPlan& f);
+    std::vector<double> fm_lagw_;      // what the upload into the scratch reads
+    // the two launches on rows x W fp32 x (before the shift) and y (shifted) with spans n (device) under win and sc.lagw (device)
+    void fm_enqueue(const float* x, const float* y, int64_t rows, int64_t W, const int64_t* n, const FormantPlan& f, const float* win, const FmScratch& sc);
     // the finished batch's B rows x W at the model's rate shifted into ps_buf_ (b.wav is left as it is): the rows every later stage
     // reads, row stride W.  Enqueued unless the scratch holds them already
     const float* ps_batch();

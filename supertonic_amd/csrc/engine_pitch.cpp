@@ -70,32 +70,50 @@ const float* Engine::ps_batch() {
     const int64_t W = native_row_len();
     PitchPlan p;
     refuse(pitch_plan(hz, W, ps_a_, ps_b_, p));
+    // section 26: under STN_PITCH_FORMANT the correction's scratch lies behind the shift's, and its rows are the stage's result
+    const bool formant = ps_mode_ == STN_PITCH_FORMANT;
+    FormantPlan f;
+    if (formant) refuse(formant_plan(hz, W, f));
+    const size_t ps_bytes = ps_layout(nullptr, b.B, W, p).bytes;
     bool moved = false;
-    char* base = ps_buf_.reserve(*this, ps_layout(nullptr, b.B, W, p).bytes, &moved);
+    char* base = ps_buf_.reserve(*this, ps_bytes + (formant ? fm_layout(nullptr, b.B, W, f).bytes : 0), &moved);
     const PsScratch sc = ps_layout(base, b.B, W, p);
+    const FmScratch fm = formant ? fm_layout(base + ps_bytes, b.B, W, f) : FmScratch{};
+    const float* res = formant ? fm.out : sc.y;
     const PsKey key{ed_seq_, ps_gen_, W, b.B, base};
-    if (!moved && ps_valid_ && key == ps_key_) return sc.y;  // later fetches of the same batch under the same shift reuse the rows
+    if (!moved && ps_valid_ && key == ps_key_) return res;  // later fetches of the same batch under the same shift and mode reuse the rows
     ps_n_ = out_spans(W, hz);
     ps_win_ = pitch_window(hz);
     STN_HIP(hipMemcpyAsync(sc.n, ps_n_.data(), ps_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.win, ps_win_.data(), ps_win_.size() * sizeof(float), hipMemcpyHostToDevice, s_));
+    if (formant) {
+        fm_lagw_ = formant_lag_window(hz, f.p);
+        STN_HIP(hipMemcpyAsync(fm.lagw, fm_lagw_.data(), fm_lagw_.size() * sizeof(double), hipMemcpyHostToDevice, s_));
+    }
     sync();  // (the uploads read ps_n_ and ps_win_, which the next batch or setting replaces; once per finished batch and setting, as cp_batch)
     ps_table(ps_rs_, ps_a_, ps_b_);
     ps_enqueue(b.wav, b.B, W, sc.n, ps_a_, ps_b_, p, sc.win, sc.delta, sc.score, sc.ys);
     ps_resample(ps_rs_, sc.ys, b.B, p.Ws, W, sc.y);
+    if (formant) fm_enqueue(b.wav, sc.y, b.B, W, sc.n, f, sc.win, fm);
     ps_key_ = key;
     ps_valid_ = true;
-    return sc.y;
+    return res;
 }
 
 // the stretch (and, with y, the resample behind it) on the caller's rows: the launches of ps_batch on arena buffers
-void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out) {
+void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out,
+                   int mode) {
     STN_HIP(hipSetDevice(device_));
     PitchPlan p;
     refuse(pitch_plan(hz, W, a, b, p));
     if (W < 1) throw std::invalid_argument("pitch: W must be >= 1");
+    if (mode != STN_PITCH_RESAMPLE && mode != STN_PITCH_FORMANT) throw std::invalid_argument("pitch mode: STN_PITCH_RESAMPLE or STN_PITCH_FORMANT");
+    const bool formant = mode == STN_PITCH_FORMANT && y_out;
+    FormantPlan f;
+    if (formant) refuse(formant_plan(hz, W, f));
     const std::vector<int64_t> nn = spans("op_pitch", rows, W, n);
     const std::vector<float> win = pitch_window(hz);
+    const std::vector<double> lagw = formant ? formant_lag_window(hz, f.p) : std::vector<double>();
     ar_.reset();
     const PsScratch sc = ps_layout(static_cast<char*>(ar_.alloc(ps_layout(nullptr, rows, W, p).bytes)), rows, W, p);
     const size_t nx = (size_t)rows * W;
@@ -107,12 +125,19 @@ void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, in
     ps_enqueue(dx, rows, W, sc.n, a, b, p, sc.win, sc.delta, sc.score, sc.ys);
     if (y_out) {
         ps_resample(op_ps_rs_, sc.ys, rows, p.Ws, W, sc.y);
-        STN_HIP(hipMemcpyAsync(y_out, sc.y, nx * 4, hipMemcpyDeviceToHost, s_));
+        const float* res = sc.y;
+        if (formant) {
+            const FmScratch fm = fm_layout(static_cast<char*>(ar_.alloc(fm_layout(nullptr, rows, W, f).bytes)), rows, W, f);
+            STN_HIP(hipMemcpyAsync(fm.lagw, lagw.data(), lagw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
+            fm_enqueue(dx, sc.y, rows, W, sc.n, f, sc.win, fm);
+            res = fm.out;
+        }
+        STN_HIP(hipMemcpyAsync(y_out, res, nx * 4, hipMemcpyDeviceToHost, s_));
     }
     if (ys_out) STN_HIP(hipMemcpyAsync(ys_out, sc.ys, (size_t)rows * p.Ws * 4, hipMemcpyDeviceToHost, s_));
     if (delta_out) STN_HIP(hipMemcpyAsync(delta_out, sc.delta, (size_t)rows * p.M * sizeof(int), hipMemcpyDeviceToHost, s_));
     if (score_out) STN_HIP(hipMemcpyAsync(score_out, sc.score, (size_t)rows * p.M * 4, hipMemcpyDeviceToHost, s_));
-    sync();  // (nn and win are read by the copies above until here)
+    sync();  // (nn, win and lagw are read by the copies above until here)
 }
 
 void Engine::op_time_stretch(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int* delta, float* score) {
@@ -123,6 +148,12 @@ void Engine::op_pitch(int hz, int rows, int W, const float* x, const int64_t* n,
     int a = 1, b = 1;
     if (!pitch_ratio(semitones, a, b)) throw std::invalid_argument(pitch_check(semitones));
     ps_op(hz, rows, W, x, n, a, b, nullptr, nullptr, nullptr, y);
+}
+
+void Engine::op_pitch_ex(int hz, int rows, int W, const float* x, const int64_t* n, float semitones, int mode, float* y) {
+    int a = 1, b = 1;
+    if (!pitch_ratio(semitones, a, b)) throw std::invalid_argument(pitch_check(semitones));
+    ps_op(hz, rows, W, x, n, a, b, nullptr, nullptr, nullptr, y, mode);
 }
 
 }  // namespace stn

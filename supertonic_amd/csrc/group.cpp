@@ -239,6 +239,9 @@ int stn_group_set_dither(stn_group* g, int mode, uint64_t seed) {
 int stn_group_set_pitch(stn_group* g, float semitones) {
     return for_all(g, "stn_set_pitch", [](stn_handle* h, const void* a, uint64_t) { return stn_set_pitch(h, *static_cast<const float*>(a)); }, &semitones, 0);
 }
+int stn_group_set_pitch_mode(stn_group* g, int mode) {
+    return for_all(g, "stn_set_pitch_mode", [](stn_handle* h, const void*, uint64_t v) { return stn_set_pitch_mode(h, (int)(int64_t)v); }, nullptr, (uint64_t)(int64_t)mode);
+}
 int stn_group_set_filters(stn_group* g, int n, const stn_filter* f) {
     struct S { int n; const stn_filter* f; } v{n, f};
     return for_all(g, "stn_set_filters", [](stn_handle* h, const void* a, uint64_t) {

@@ -424,6 +424,7 @@ std::unique_ptr<TextToSpeech> loadTextToSpeech(const std::string& onnx_dir, bool
         };
         const int nf = (int)opts.filters.size();
         if (opts.pitch != 0.0f) applied("pitch", grp ? stn_group_set_pitch(grp, opts.pitch) : stn_set_pitch(h, opts.pitch));
+        if (opts.pitch_mode != STN_PITCH_RESAMPLE) applied("pitch mode", grp ? stn_group_set_pitch_mode(grp, opts.pitch_mode) : stn_set_pitch_mode(h, opts.pitch_mode));
         if (opts.output_rate) applied("output rate", grp ? stn_group_set_output_rate(grp, opts.output_rate) : stn_set_output_rate(h, opts.output_rate));
         // (after the rate: a chain is checked against the output rate in force)
         if (nf) applied("filters", grp ? stn_group_set_filters(grp, nf, opts.filters.data()) : stn_set_filters(h, nf, opts.filters.data()));

@@ -92,6 +92,9 @@ struct EngineOptions {
                                    // keeps the float waveform and writeWavFile's files.  CLI --encoding {pcm16,pcm24,f32,mulaw,alaw}
     float pitch = 0.0f;            // every utterance shifted by this many semitones ([-12, 12]) on the GPU without a change of length, in front of
                                    // everything above (stn_set_pitch); 0: off.  CLI --pitch SEMITONES
+    int pitch_mode = STN_PITCH_RESAMPLE;  // what the shift does to the formants (stn_set_pitch_mode): they move with the pitch, or with
+                                   // STN_PITCH_FORMANT the spectral envelope is put back on the GPU; no effect while pitch is 0.
+                                   // CLI --pitch-mode {resample,formant}
     int dither = STN_DITHER_OFF;   // how 16- and 24-bit PCM is quantized on the GPU (stn_set_dither): STN_DITHER_OFF truncates as writeWavFile;
     uint64_t dither_seed = 0;      // _ROUND, _TPDF, _TPDF_HP round, behind dither keyed by this seed.  With a mode set, PCM16 is fetched as
                                    // 16-bit samples (not as floats for writeWavFile).  CLI --dither {off,round,tpdf,tpdf-hp} and --dither-seed N

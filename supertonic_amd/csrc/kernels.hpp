@@ -545,6 +545,17 @@ void launch_pitch_search(hipStream_t s, const float* x, int64_t rows, int64_t W,
 void launch_pitch_ola(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int H, int64_t M, int64_t Ws, int a, int b, const int* delta,
                       const float* win, float* y);
 
+// Formant correction of pitch-shifted rows (kernels_formant.hip; the geometry and the recursion's host statement are host/formant.cpp,
+// the rule DESIGN.md section 26).  x: the rows before the shift, y: the shifted rows, both rows x W fp32 with spans n as above; hop H,
+// frames F = ceil(W / H) + 1 of N = 2 H samples, order p in [1, 48].  launch_formant_lpc: per (row, frame) the LPC polynomials of x and
+// y under win (device, 2 H floats) and lagw (device, p + 1 doubles) -> ax and cy = g a_y [rows][F][p + 1] fp32, g, ex and ey [rows][F]
+// double.  launch_formant_filter: out [rows][W], the cross-faded outputs of g A_y / A_x per frame from zero state N samples ahead of
+// the frame, 0.0f from the row's span on.
+void launch_formant_lpc(hipStream_t s, const float* x, const float* y, int64_t rows, int64_t W, const int64_t* n, int H, int64_t F, int p, const float* win,
+                        const double* lagw, float* ax, float* cy, double* g, double* ex, double* ey);
+void launch_formant_filter(hipStream_t s, const float* y, int64_t rows, int64_t W, const int64_t* n, int H, int64_t F, int p, const float* win,
+                           const float* ax, const float* cy, float* out);
+
 // Loudness normalization of the finished waveform (kernels_loudness.hip; the filter design and the measurement are engine_loudness.cpp).
 // BS.1770-4 integrated loudness of row b's first n_b samples: K-weighting (shelf then high-pass biquad, transposed direct form II in
 // fp32) as one 4-state linear system x' = A x + B u.  Chunks of LO_CHUNK samples from sample 0: each is filtered from zero state

@@ -40,6 +40,7 @@ _PARSE = {
     "peak_mode": _peak_mode,
     "dither": lambda v: binding.dither_args(v) or False,
     "pitch": lambda v: binding.pitch_args(v) or False,
+    "pitch_mode": binding.pitch_mode_name,
 }
 
 
@@ -78,7 +79,9 @@ class OutputSettings:
                   (mode, seed), as binding.dither_args takes them; it acts on audio fetched as "pcm16" or "pcm24" only (float, mu-law
                   and A-law are unaffected).  Normalized: (mode name, seed).  Off: False or "off", the truncating store.
     pitch         every utterance shifted by this many semitones ([-12, 12]) without a change of length, the first step: everything above
-                  sees the shifted audio (stn_set_pitch).  Normalized: a float.  Off: False or 0."""
+                  sees the shifted audio (stn_set_pitch).  Normalized: a float.  Off: False or 0.
+    pitch_mode    what the shift does to the formants (stn_set_pitch_mode): "resample" (they move with the pitch) or "formant" (the
+                  spectral envelope of the audio before the shift is put back); it acts only while pitch is on.  Off: "resample"."""
     output_rate: object = None
     filters: object = None
     loudness: object = None
@@ -104,9 +107,13 @@ class OutputSettings:
     # An attribute like pitch, for the same reasons, and with unset and off comparing equal as its are (applied between filters and
     # deesser).  The service's BatchKey carries the difference (expander_set).
     expander = None
+    # An attribute like pitch, applied next to it.  Unset and "resample" compare equal; the service's BatchKey carries the difference
+    # (pitch_mode_set).
+    pitch_mode = None
 
     def _all(self):
-        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither, self.pitch or False, self.expander or False)
+        return tuple(getattr(self, f.name) for f in dataclasses.fields(self)) + (self.dither, self.pitch or False, self.expander or False,
+                                                                               self.pitch_mode or "resample")
 
     def __eq__(self, other):
         return other._all() == self._all() if type(other) is type(self) else NotImplemented
@@ -115,14 +122,14 @@ class OutputSettings:
         return hash(self._all())
 
     def __repr__(self):
-        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither", "pitch", "expander"], self._all())) + ")"
+        return "OutputSettings(" + ", ".join(f"{k}={v!r}" for k, v in zip([f.name for f in dataclasses.fields(self)] + ["dither", "pitch", "expander", "pitch_mode"], self._all())) + ")"
 
     def decided(self):
-        """This value over ALL_OFF, and dither, pitch and expander off where that leaves them unset: every setting decided (what an
-        instance holds)"""
+        """This value over ALL_OFF, and dither, pitch, expander and pitch_mode off where that leaves them unset: every setting decided
+        (what an instance holds)"""
         s = self.over(OutputSettings.ALL_OFF)
         return s.replace(dither=False if s.dither is None else s.dither, pitch=False if s.pitch is None else s.pitch,
-                         expander=False if s.expander is None else s.expander)
+                         expander=False if s.expander is None else s.expander, pitch_mode=s.pitch_mode or "resample")
 
     @classmethod
     def parse(cls, **kw):
@@ -135,10 +142,11 @@ class OutputSettings:
 
     def replace(self, **changes):
         """This value with the fields named in changes set to their (normalized) values: dataclasses.replace for every field, deesser,
-        dither, pitch and expander included"""
+        dither, pitch, expander and pitch_mode included"""
         deesser, dither, pitch = changes.pop("deesser", self.deesser), changes.pop("dither", self.dither), changes.pop("pitch", self.pitch)
-        expander = changes.pop("expander", self.expander)
+        expander, pitch_mode = changes.pop("expander", self.expander), changes.pop("pitch_mode", self.pitch_mode)
         new = dataclasses.replace(self, **changes)
+        object.__setattr__(new, "pitch_mode", pitch_mode)
         object.__setattr__(new, "expander", expander)
         object.__setattr__(new, "deesser", deesser)
         object.__setattr__(new, "dither", dither)
@@ -162,6 +170,8 @@ class OutputSettings:
         the first stage of the chain, goes first."""
         if self.pitch is not None:
             engine.set_pitch(self.pitch or None)
+        if self.pitch_mode is not None:
+            engine.set_pitch_mode(self.pitch_mode)
         if self.filters is not None:
             engine.set_filters(None)
         if self.deesser is not None and (self.output_rate is not None or not self.deesser):

@@ -31,13 +31,15 @@ REPORT_HEADERS = {"X-Loudness-Integrated": "integrated", "X-Loudness-Range": "ra
 
 # what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
 # (pitch_set: whether the request names a pitch.  OutputSettings compares an unset pitch equal to an off one; the key must not: a request
-# that names none gets the synthesizer's own pitch, one that says 0 gets none.  expander_set: the same for the expander)
-BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings pitch_set expander_set")
+# that names none gets the synthesizer's own pitch, one that says 0 gets none.  expander_set: the same for the expander.  pitch_mode: the
+# mode in force for the request, its own or else the synthesizer's: OutputSettings compares an unset mode equal to "resample", which is
+# the same request only where the synthesizer's own is "resample")
+BatchKey = namedtuple("BatchKey", "total_step speed encoding loudness_scope trim_chunks settings pitch_set expander_set pitch_mode")
 
 
 def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, peak_ceiling=-1.0, encoding=None, loudness_scope="chunk",
               trim_chunks=False, trim_silence=None, limiter_ms=None, peak_mode=None, max_pause_ms=None, filters=None, deesser=None, dither=None,
-              dither_seed=None, pitch=None, expander=None, compressor=None):
+              dither_seed=None, pitch=None, expander=None, pitch_mode=None, own_pitch_mode="resample", compressor=None):
     """A request's BatchKey: two requests merge if and only if their keys are equal.  Everything is validated here (ValueError), in front
     of the queue.  A field the request leaves at None is unset in the key (the synthesizer's own setting holds), never the synthesizer's
     value; key.settings.kwargs() is then exactly what the request set, which is what the synthesizer is called with.
@@ -52,7 +54,9 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     loudness_scope, trim_chunks (TextToSpeech.joined_batch): one fetch has one scope and one mode.  pitch: semitones in [-12, 12] (0 = off),
     refused with the engine's message: requests of different pitch never share a batch, and neither do one that names none (the
     synthesizer's own holds) and one that says 0.  expander: True, a dict or a 7-tuple as binding.expander_args takes it, False = off,
-    checked against the engine's limits; as with pitch, a request that names none and one that says false never share a batch."""
+    checked against the engine's limits; as with pitch, a request that names none and one that says false never share a batch.
+    pitch_mode: "resample" or "formant" (OutputSettings' pitch_mode), refused with binding.pitch_mode_id's message; own_pitch_mode: the
+    synthesizer's own, which a request that names none runs under: requests under different modes never share a batch."""
     chain = None if filters is None else binding.filter_args(filters)
     why = chain and binding.filter_error(chain, int(sample_rate or model_rate))
     if why:
@@ -70,7 +74,7 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     if why:
         raise ValueError(why)
     dith = binding.dither_args(dither or "off", dither_seed) or False
-    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, expander=xpd, deesser=dees, compressor=comp, dither=None if dither is None else dith, pitch=pitch, loudness=None if loudness is None else (loudness, peak_ceiling),
+    s = OutputSettings.parse(output_rate=sample_rate, filters=chain, expander=xpd, deesser=dees, compressor=comp, dither=None if dither is None else dith, pitch=pitch, pitch_mode=pitch_mode, loudness=None if loudness is None else (loudness, peak_ceiling),
                              trim_silence=None if trim_silence is None else binding.silence_trim_args(trim_silence)[1:],
                              max_pause=None if max_pause_ms is None else float(max_pause_ms),
                              limiter=None if limiter_ms is None else float(limiter_ms), peak_mode=None if peak_mode is None else str(peak_mode))
@@ -79,7 +83,7 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
     if s.trim_silence is None:
         s = s.replace(max_pause=None)
     return BatchKey(int(total_step), float(speed), None if encoding is None else binding.encoding_id(encoding), str(loudness_scope),
-                    bool(trim_chunks), s, s.pitch is not None, s.expander is not None)
+                    bool(trim_chunks), s, s.pitch is not None, s.expander is not None, s.pitch_mode or binding.pitch_mode_name(own_pitch_mode))
 
 
 class _Job:
@@ -113,7 +117,8 @@ class DynamicBatcher:
         gap), with its duration.  loudness_report (no part of the key: it changes no audio): a third result, the job's entry of
         TextToSpeech.loudness_report for its joined wave as a dict of floats, or None when the synthesizer has no such report or the
         job is not joined on the GPU."""
-        key = batch_key(self.tts.sample_rate, *request, **request_kw)
+        own = getattr(getattr(self.tts, "settings", None), "pitch_mode", None)
+        key = batch_key(self.tts.sample_rate, *request, own_pitch_mode=own, **request_kw)
         job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration), loudness_report)
         with self._cv:
             if self._stop:
@@ -312,6 +317,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         pitch: Optional[float] = Field(None, description="Pitch shift in semitones, a number in [-12, 12], applied on the GPU in front of every other "
                                                          "setting without a change of duration; 0: off; null: the server's.  The response's "
                                                          "X-Pitch-Cents header carries the realised shift.")
+        pitch_mode: Optional[str] = Field(None, description="What the pitch shift does to the formants: 'resample' (they move with the pitch) or "
+                                                            "'formant' (the spectral envelope is put back on the GPU); null: the server's.  No "
+                                                            "effect while pitch is off.")
 
     def ensure_list(v):
         return v if isinstance(v, list) else [v]
@@ -405,6 +413,11 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                 raise HTTPException(status_code=400, detail=why)
             pitch = binding.pitch_args(req.pitch)
             extra["pitch"] = pitch
+        if req.pitch_mode is not None:
+            try:
+                extra["pitch_mode"] = binding.pitch_mode_name(req.pitch_mode)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
         if req.encoding not in binding.ENCODINGS:
             raise HTTPException(status_code=400, detail=f"encoding {req.encoding!r} is not supported; supported: " + ", ".join(binding.ENCODINGS))
         if req.loudness_scope not in ("chunk", "text"):
@@ -440,7 +453,7 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                                                enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                                trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
                                                max_pause_ms=req.max_pause_ms, filters=chain, expander=xpd, deesser=dees, compressor=comp,
-                                               dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, pitch=pitch, **more)
+                                               dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, pitch=pitch, pitch_mode=extra.get("pitch_mode"), **more)
             report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
