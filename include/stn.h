@@ -589,6 +589,9 @@ int stn_silence_fade_window(int hz, float fade_ms, float* w, int64_t cap, int64_
 /* diagnostic: overwrite the finished batch's model-rate waveform with wav [B][L * chunk] (host; what stn_batch_dims reports at the model's
  * rate) and forget every fetch-time measurement cached for it.  For tests that need rows with known silences. */
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav);
+/* diagnostic: how often the handle has uploaded the finished batch's row spans (the n_b of "loudness") since it was created: once per
+ * finished batch and (rate, row length) that a fetch, a report or a stage asked for, whatever the number of fetches (0 for NULL) */
+int64_t stn_dbg_span_uploads(const stn_handle* h);
 
 /* ---- pause limit -------------------------------------------------------------------------------------
  * With silence trimming on AND the pause limit on, every pause inside a row's speech that is longer than max_pause_ms is shortened to

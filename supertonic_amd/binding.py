@@ -761,6 +761,8 @@ def load():
     L.stn_deesser_band.argtypes = [dsp, ci, _f64p, _f32p]
     L.stn_deesser_coefs.argtypes = [dsp, ci, _f64p, _f32p]
     L.stn_dbg_batch_set_wav.argtypes = [vp, _f32p]
+    L.stn_dbg_span_uploads.argtypes = [vp]
+    L.stn_dbg_span_uploads.restype = ctypes.c_int64
     L.stn_encoding_bytes.argtypes = [ci]
     L.stn_batch_fetch_encoded.argtypes = [vp, ci, vp, ctypes.c_size_t, vp]
     L.stn_batch_copy_encoded_device.argtypes = [vp, ci, vp, ctypes.c_int64]
@@ -2050,6 +2052,10 @@ class Engine:
         if wav.shape != (B, W):
             raise ValueError(f"dbg_batch_set_wav: wav must be [{B}, {W}], got {wav.shape}")
         self._ck(self._lib.stn_dbg_batch_set_wav(self._h, wav))
+
+    def span_uploads(self):
+        """Diagnostic: uploads of the finished batch's row spans since the handle was created (stn_dbg_span_uploads)."""
+        return int(self._lib.stn_dbg_span_uploads(self._h))
 
     def set_pitch(self, semitones=None):
         """Shift the pitch of every row of every fetch by `semitones` on the GPU, in front of every other fetch-time stage and without

@@ -736,6 +736,7 @@ int stn_op_limiter_ex(stn_handle* h, int hz, int rows, int W, const float* x, co
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav) {
     STN_TRY(h, { need(wav != nullptr, "wav is null"); need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->dbg_batch_set_wav(wav); })
 }
+int64_t stn_dbg_span_uploads(const stn_handle* h) { return h ? h->eng->span_uploads() : 0; }
 int stn_kweighting_filter(int hz, double* shelf_b, double* shelf_a, double* hp_b, double* hp_a) {
     stn::KWeighting k;
     if (!stn::kweighting_design(hz, k).empty()) return STN_ERR_INVALID;

@@ -177,12 +177,7 @@ Engine::~Engine() {
     for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
     drop_graphs();
     if (pin_tab_) (void)hipHostFree(pin_tab_);
-    rs_release();
-    fl_release();
-    dyn_release(xp_);
-    dyn_release(ds_);
-    dyn_release(cp_);
-    lo_release();  // (the fetch scratch, DevBuf members, goes with the members)
+    // (the fetch scratch and the stages' device tables, DevBuf and DeviceTable members, go with the members)
     for (auto& f : fetch_) {
         if (f.busy && f.done) (void)hipEventSynchronize(f.done);
         if (f.dev) (void)hipFree(f.dev);

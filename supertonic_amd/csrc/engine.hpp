@@ -140,6 +140,30 @@ class DevBuf {
     size_t cap_ = 0;
 };
 
+// The device copy of a constant host table, owned: freed with its owner (an engine member: after the destructor's body has drained the
+// streams, as DevBuf).  put replaces the contents from host memory and returns the new block: allocate, upload, wait, free the old one.
+// It always waits, because the upload reads the caller's host array and a fetch in flight may still read the old block: one wait per
+// handle and setting (a table is designed when its rate or setting changes), never one per fetch.
+class DeviceTable {
+   public:
+    DeviceTable() = default;
+    DeviceTable(const DeviceTable&) = delete;
+    DeviceTable& operator=(const DeviceTable&) = delete;
+    ~DeviceTable() { if (p_) (void)hipFree(p_); }
+    void* put(Engine& e, const void* host, size_t bytes);
+    template <typename T> T* put(Engine& e, const std::vector<T>& host) { return static_cast<T*>(put(e, host.data(), host.size() * sizeof(T))); }
+    explicit operator bool() const { return p_ != nullptr; }
+
+   private:
+    void* p_ = nullptr;
+};
+// A constant table as the launchers take it (t; its `dev` pointers point into dev) with the N device copies it needs
+template <typename Table, size_t N = 1>
+struct OnDevice { Table t; DeviceTable dev[N]; };
+
+// Row spans on the device, [rows] each: n[r] the valid samples of row r, full[r] the row width (the lengths of a launch over whole rows)
+struct RowSpans { const int64_t* n = nullptr; const int64_t* full = nullptr; };
+
 // Consecutive arrays from a block, each on a 256-byte boundary of it.  Without a block (null) no pointer is formed: off, the bytes
 // taken so far, is then the size the same sequence of take calls needs.
 struct Carve {
@@ -168,10 +192,9 @@ struct DynStage {
     bool on = false;
     Set set;                       // the setting in force (the "speech" default until one is set)
     uint64_t gen = 0;              // bumped by every change of the setting
-    struct Made { Table t; Set from{}; };  // a table (device copies owned here) and the setting it was made from
+    struct Made { Table t; Set from{}; DeviceTable dev[2]; };  // a table, the setting it was made from and its device copies
     Made tab, op_tab;              // at the output rate, and of the op entry
     DevBuf buf;                    // fetch-time scratch of the launches: exists only once a fetch ran with the stage on
-    std::vector<int64_t> n; const int64_t* n_ptr = nullptr; int64_t n_W = 0;  // the spans buf holds, where, and (de-esser) beside which width
     RowsId key; const void* key_buf = nullptr; bool valid = false;            // what the row results in buf belong to, and the scratch
 };
 
@@ -194,7 +217,7 @@ class Engine {
     int64_t param_count() const { return params_; }
     int dtype() const { return dt_; }
     hipStream_t stream() const { return s_; }
-    void sync() { STN_HIP(hipStreamSynchronize(s_)); if (dp_s_) STN_HIP(hipStreamSynchronize(dp_s_)); if (te_s_) STN_HIP(hipStreamSynchronize(te_s_)); }
+    void sync() { STN_HIP(hipStreamSynchronize(s_)); if (dp_s_) STN_HIP(hipStreamSynchronize(dp_s_)); if (te_s_) STN_HIP(hipStreamSynchronize(te_s_)); ++drains_; }
     // run on a caller-owned stream (e.g. torch's current stream, so RCCL ops order after the engine's kernels);
     // nullptr returns to the engine's own stream
     void set_stream(hipStream_t s);
@@ -509,6 +532,8 @@ class Engine {
                              EdProbe& probe, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs);
     // diagnostic: overwrite the finished batch's model-rate waveform ([B][L * chunk] host floats) and forget what was measured on it
     void dbg_batch_set_wav(const float* wav);
+    // diagnostic: uploads of the batch span table (batch_spans) since the engine was created
+    int64_t span_uploads() const { return sp_uploads_; }
 
     // ---- limiter (engine_limiter.cpp; include/stn.h "limiter"): off is the default, and without loudness it
     // has no effect (every fetch path is then exactly the one without it).  On with loudness on, the loudness gain is the uncapped
@@ -803,7 +828,24 @@ class Engine {
     std::vector<void*> batch_retired_;  // outgrown buffers: freed at the next upload, after the stream has drained
     template <typename T> void ensure(T*& p, size_t& cap, size_t need);
     std::vector<float> reported_dur_;
-    std::vector<int64_t> out_spans(int64_t Wo, int hz) const;  // the finished batch's valid samples per row at the output rate (engine_loudness.cpp)
+    uint64_t drains_ = 0;  // bumped by every sync(): a host array whose upload was enqueued under another count is no longer read
+    // ---- the finished batch's row spans (engine_loudness.cpp; DESIGN.md sections 11 and 11a).  out_spans is the rule: row b's valid
+    // samples at hz inside [0, W].  batch_spans is where they live: the device pair every stage of a fetch takes (n: the spans, full: W
+    // for every row) and the host copy (the spans first, W for every row behind them), uploaded once per finished batch and (hz, W)
+    std::vector<int64_t> out_spans(int64_t W, int hz) const;
+    struct BatchSpans {
+        RowSpans dev;
+        std::vector<int64_t> host;
+        uint64_t seq = 0, drains = ~0ull; int hz = 0; int64_t W = 0;  // the finished batch and (hz, W) it holds; drains_ at its upload
+    };
+    const BatchSpans& batch_spans(int hz, int64_t W);
+    BatchSpans sp_[2];     // at the model's rate and row length (what pitch reads, and everything else while no rate is set); at any other rate
+    DevBuf sp_buf_;
+    int64_t sp_uploads_ = 0;
+    // an op entry's spans (checked by spans()) and the width beside them, uploaded into the arena; the host copy stays here until the
+    // entry's closing sync()
+    RowSpans op_spans(int rows, int W, std::vector<int64_t> n);
+    std::vector<int64_t> op_sp_;
     void enqueue_after_duration(int total_step, const std::function<void()>& take_text_rows);
     // A captured graph holds raw pointers: everything it can have baked in is part of its key — the batch buffers (`gen`, bumped
     // by every reallocation), the weights (`wgen`, bumped by every load), the pinned staging the copy nodes read, the stream.
@@ -878,22 +920,22 @@ class Engine {
     struct FetchSlot { unsigned char* dev = nullptr; unsigned char* pin = nullptr; size_t cap = 0, n = 0; int enc = ENC_PCM16; hipEvent_t ready = nullptr, done = nullptr; bool busy = false; std::vector<float> dur; };
     FetchSlot fetch_[2];
     int out_hz_ = 0;                  // requested output rate (0: the model's)
-    ResampleTable rs_, op_rs_;        // filter tables of the output rate and of op_resample (device copies owned here)
-    void rs_prepare(ResampleTable& t, int in_hz, int out_hz);
+    using RsTable = OnDevice<ResampleTable>;
+    RsTable rs_, op_rs_;              // filter tables of the output rate and of op_resample
+    void rs_prepare(RsTable& m, int in_hz, int out_hz);
     const ResampleTable& rs_table();
-    void rs_release();
     void resample_enqueue(const ResampleTable& t, const float* x, int64_t rows, int64_t W, int enc, void* y, int64_t dst_stride);
     // ---- pitch (engine_pitch.cpp)
     float ps_semi_ = 0.0f;             // the setting in force and its ratio (1 / 1: off)
     int ps_a_ = 1, ps_b_ = 1;
     uint64_t ps_gen_ = 0;              // bumped by every set_pitch and by every change of the pitch mode
-    ResampleTable ps_rs_, op_ps_rs_;   // the b / a tables of the setting and of the op entries, cached per (a, b) (device copies owned here)
-    void ps_table(ResampleTable& t, int a, int b);
+    RsTable ps_rs_, op_ps_rs_;         // the b / a tables of the setting and of the op entries, cached per (a, b)
+    void ps_table(RsTable& m, int a, int b);
     DevBuf ps_buf_;                    // fetch-time scratch of the shift: exists only once a fetch ran with pitch on
-    // per row the span, the window, per frame the offset and its score, the stretched rows [rows][Ws] and the shifted rows [rows][W]
-    struct PsScratch { int64_t* n; float* win; int* delta; float* score; float* ys; float* y; size_t bytes; };
+    // the window, per frame the offset and its score, the stretched rows [rows][Ws] and the shifted rows [rows][W]
+    struct PsScratch { float* win; int* delta; float* score; float* ys; float* y; size_t bytes; };
     static PsScratch ps_layout(char* base, int64_t rows, int64_t W, const PitchPlan& p);
-    std::vector<int64_t> ps_n_; std::vector<float> ps_win_;  // what the uploads into ps_buf_ read
+    std::vector<float> ps_win_;        // what the upload into ps_buf_ reads
     // what ps_buf_'s shifted rows belong to: the finished batch's waveform, the setting, the shape, the scratch
     struct PsKey {
         uint64_t seq = 0, gen = 0; int64_t W = 0; int B = 0; const void* buf = nullptr;
@@ -923,85 +965,80 @@ class Engine {
     const float* wav_rows() { return pitch_on() ? ps_batch() : bt_.wav; }
     bool lo_on_ = false;
     float lo_target_ = -23.0f, lo_ceiling_ = -1.0f;
-    LoudTable lo_, op_lo_;             // K-weighting tables of the output rate and of op_loudness (device copies owned here)
+    OnDevice<LoudTable> lo_, op_lo_;   // K-weighting tables of the output rate and of op_loudness
     DevBuf lo_buf_;                    // fetch-time scratch of the measurement
-    std::vector<int64_t> lo_n_;        // the row lengths last uploaded into lo_buf_, at lo_n_ptr_ (empty: none)
-    int64_t* lo_n_ptr_ = nullptr;
     // what a measurement leaves on the device, [rows] each, and the spans it measured
     struct LoRes { const float *lufs = nullptr, *peak = nullptr, *gain = nullptr; const int64_t* n = nullptr; };
     // per chunk the state (16 B), the peak and the two energy shares; per row the three results (res [3][rows], as the gate writes them:
-    // `out` names them) and the length; bytes: the size of it all
-    struct LoScratch { float *st, *pk, *pa, *pb, *res; int64_t* n; LoRes out; size_t bytes; };
+    // `out` names them; its spans are the measurement's argument); bytes: the size of it all
+    struct LoScratch { float *st, *pk, *pa, *pb, *res; LoRes out; size_t bytes; };
     static LoScratch lo_layout(char* base, int64_t rows, int64_t W);
-    LoScratch lo_scratch(int64_t rows, int64_t W);
-    void lo_prepare(LoudTable& t, int hz);
-    void lo_release();
+    LoScratch lo_scratch(int64_t rows, int64_t W) { return lo_layout(lo_buf_.reserve(*this, lo_layout(nullptr, rows, W).bytes), rows, W); }
+    void lo_prepare(OnDevice<LoudTable>& m, int hz);
     // enqueues the four measurement launches on rows x W fp32 (row stride W) with row lengths n (device): res = [L][peak][gain];
     // st_end (host, or null): the state buffer as the first launch left it, copied out before the scan overwrites it
     // true_peak: a fifth launch between the energy pass and the gate replaces pk by the per-chunk true peaks (kernels_truepeak.hip)
-    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
-                    float* st_end = nullptr, bool true_peak = false);
-    // op_loudness and op_loudness_ex: the upload, the measurement, the read-back
-    void lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
+    void lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoScratch& sc, int64_t max_seg, bool on, float target,
+                    float ceiling, float* st_end = nullptr, bool true_peak = false);
+    // op_loudness and op_loudness_ex: the upload, the measurement, the read-back; returns the spans it measured (device, in the arena)
+    const int64_t* lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
                float* peak, float* gain);
-    // rows x W fp32 on the device (x) with row spans n measured on the stream against table t.  n is uploaded only when it differs from
-    // what the scratch holds.
+    // rows x W fp32 on the device (x) with row spans n (device; the longest max_seg hops of t) measured on the stream against table t
     // true_peak: the gate's peak is the row's true peak (section 16).  The callers that own the setting (lo_batch, join_measure) pass
     // lo_true_peak(); the op-level callers keep the sample peak.
-    LoRes lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target, float ceiling,
+    LoRes lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, int64_t max_seg, bool on, float target, float ceiling,
                   bool true_peak = false);
     // (with the limiter active nothing caps the gain: the limiter measures the envelope of the scaled row itself)
     bool lo_true_peak() const { return true_peak_on() && !limiter_active(); }
     // the finished batch's B rows x Wo at the output rate (x) measured on the stream
     LoRes lo_batch(const float* x, int64_t Wo, bool on);
-    // the report's launch on what the measurement of rows x W just left in lo_buf_ (pa, pb and the lengths) and its read-back, no sync;
-    // max_seg: the longest span in segments (lr_max_seg: of the lengths lo_rows uploaded last)
+    // the report's launch on what the measurement of rows x W with spans n (device) just left in lo_buf_ (pa, pb) and its read-back, no
+    // sync; max_seg: the longest span in segments (lr_max_seg: of the host spans n)
     DevBuf lr_buf_;                    // the report's results: [3][rows] floats, [rows] counts
-    int64_t lr_max_seg(const LoudTable& t) const;
-    void lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st);
+    static int64_t lr_max_seg(const LoudTable& t, const int64_t* n, size_t rows);
+    void lr_report(const LoudTable& t, int64_t rows, int64_t W, const int64_t* n, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st);
     // ---- filter chain (engine_filter.cpp)
     std::vector<stn_filter> fl_set_;   // the chain in force
     uint64_t fl_gen_ = 0;              // bumped by every set_filters
-    FilterTable fl_, op_fl_;           // the section passes of the chain at the output rate, and of op_filter (device copies owned here)
+    using FlTable = OnDevice<FilterTable, (STN_MAX_FILTERS + 1) / 2>;  // one device copy per section pass
+    FlTable fl_, op_fl_;               // the section passes of the chain at the output rate, and of op_filter
     DevBuf fl_buf_;                    // fetch-time scratch of the section passes
-    // per chunk the state (16 B) and pass 1's peak (unused), per row the length (every row's is W): what the measurement's launches take
-    struct FlScratch { float *st, *pk; int64_t* n; size_t bytes; };
+    // per chunk the state (16 B) and pass 1's peak (unused): what the measurement's launches take
+    struct FlScratch { float *st, *pk; size_t bytes; };
     static FlScratch fl_layout(char* base, int64_t rows, int64_t W);
-    int64_t fl_n_rows_ = 0, fl_n_W_ = 0; const int64_t* fl_n_ptr_ = nullptr;  // the lengths fl_buf_ holds (rows of W at fl_n_ptr_)
-    void fl_prepare(FilterTable& t, int hz, int n, const stn_filter* f);
-    void fl_release();
-    // the chain's section passes on rows x W fp32 (x; row stride W) into y (may be x; every pass after the first runs in place in y);
-    // probe (or null): the states of every pass read out, the state buffer poisoned before each
-    void fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const FlScratch& sc, float* y, FlProbe* probe);
+    void fl_prepare(FlTable& m, int hz, int n, const stn_filter* f);
+    // the chain's section passes on rows x W fp32 (x; row stride W; full: W as every row's length, device) into y (may be x; every pass
+    // after the first runs in place in y); probe (or null): the states of every pass read out, the state buffer poisoned before each
+    void fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const int64_t* full, const FlScratch& sc, float* y, FlProbe* probe);
     void fl_batch(const float* x, int64_t Wo, float* y);  // the finished batch's B rows x Wo (x) through the chain in force into y (may be x)
     // ---- the chain's identity (engine_batch.cpp): the rows behind `stage`, Wo samples each, as everything kept of them is keyed
     RowsId rows_id(Stage stage, int64_t Wo) const;
     // ---- the three dynamics stages: each file holds its layout and its launches; the skeleton around them is shared (engine_internal.hpp)
-    // A scratch holds per chunk the stage's state arrays and partial results, per row the results and the valid length n; nw: the width
-    // as every row's length, which only the de-esser's band launches take (null in the others)
+    // A scratch holds per chunk the stage's state arrays and partial results and per row the results; the launches take the rows' spans
+    // beside it (RowSpans::full: what only the de-esser's band launches read)
     // compressor (engine_compressor.cpp): y1 and yL (end values, then start values) and the maximum of yL
-    struct CpScratch { float *s1, *s2, *cmax, *rmax; int64_t *n, *nw; size_t bytes; };
+    struct CpScratch { float *s1, *s2, *cmax, *rmax; size_t bytes; };
     // de-esser (engine_deesser.cpp): the band's state and max |x| (unused) in front of the compressor's arrays
-    struct DsScratch { float *st, *pk, *s1, *s2, *cmax, *rmax; int64_t *nw, *n; size_t bytes; };
+    struct DsScratch { float *st, *pk, *s1, *s2, *cmax, *rmax; size_t bytes; };
     // expander (engine_expander.cpp): u and yL, the minimum of R - yL and the count of yL <= R / 2
-    struct XpScratch { float *s1, *s2, *cmin, *rmin; int32_t* ccnt; int64_t *rcnt, *n, *nw; size_t bytes; };
+    struct XpScratch { float *s1, *s2, *cmin, *rmin; int32_t* ccnt; int64_t* rcnt; size_t bytes; };
     static CpScratch cp_layout(char* base, int64_t rows, int64_t W);
     static DsScratch ds_layout(char* base, int64_t rows, int64_t W);
     static XpScratch xp_layout(char* base, int64_t rows, int64_t W);
     DynStage<stn_compressor, CompTable> cp_{false, {-24.0f, 3.0f, 6.0f, 5.0f, 120.0f, 0.0f}};
     DynStage<stn_deesser, DeessTable> ds_{false, {5500.0f, -30.0f, 4.0f, 6.0f, 1.0f, 40.0f, 12.0f, STN_DEESS_SPLIT}};
     DynStage<stn_expander, ExpTable> xp_{false, {-50.0f, 3.0f, 6.0f, 24.0f, 1.0f, 30.0f, 150.0f}};
-    // the stage's launches (five and the row maxima, eight, six) on rows x W fp32 (x; row stride W) into y (may be x); probe (or null):
-    // every state array read out where the sequence leaves it; gr / band / open: the per-sample outputs (rows x W on the device, or null)
-    void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
-    void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
-    void xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const XpScratch& sc, float* y, float* open, XpProbe* probe);
+    // the stage's launches (five and the row maxima, eight, six) on rows x W fp32 (x; row stride W) with spans n into y (may be x); probe
+    // (or null): every state array read out where the sequence leaves it; gr / band / open: the per-sample outputs (rows x W on the device, or null)
+    void cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const CpScratch& sc, float* y, float* gr, CpProbe* probe);
+    void ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const RowSpans& n, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr);
+    void xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const XpScratch& sc, float* y, float* open, XpProbe* probe);
     // out_source's hooks: the finished batch's B rows x Wo (x) through the stage into y (may be x)
     void cp_batch(const float* x, int64_t Wo, float* y);
     void ds_batch(const float* x, int64_t Wo, float* y);
     void xp_batch(const float* x, int64_t Wo, float* y);
     // the skeleton (engine_internal.hpp).  dyn_prepare: m is the table of (hz, c), made by `build` and uploaded unless it is that already.
-    // dyn_batch: the fetch hook around `run`, the stage's launches on the carved scratch (table, scratch, spans, launches, key).
+    // dyn_batch: the fetch hook around `run`, the stage's launches on the carved scratch and the batch's spans (table, scratch, launches, key).
     // dyn_report: a report's preamble around `read`, which is given the scratch to read the rows' results from, or null while the stage
     // is off (zeros).  dyn_op: the op entry around `run`; taps: the per-sample outputs (host, or null), in the order `run` is handed
     // their device rows.  read_rows: one result per row of the batch device -> host (dev null: zeros; host null: nothing)
@@ -1021,12 +1058,11 @@ class Engine {
     float st_db_ = 40.0f, st_keep_ = 20.0f, st_fade_ = 5.0f;
     uint64_t ed_seq_ = 0;              // the finished batch's waveform: bumped by every batch_run and by dbg_batch_set_wav
     DevBuf ed_buf_;                    // fetch-time scratch of the detection
-    // per chunk the two frame shares, per frame the level, per row the edges, the span and the one-member programme of the per-row
-    // trimmed fetch
+    // per chunk the two frame shares, per frame the level, per row the edges and the one-member programme of the per-row trimmed fetch
     // With the pause limit (S > 0; section 17) also S segments, one programme and 2 S words {cuts, len, lo, hi, ...} per row, behind the
     // rest: S = 0 carves exactly what trimming alone needs
     struct EdScratch {
-        float *pa, *pb; double* lev; int64_t *edges, *n; JoinSegT* seg; JoinProg* prog; size_t bytes;
+        float *pa, *pb; double* lev; int64_t* edges; JoinSegT* seg; JoinProg* prog; size_t bytes;
         JoinSegT* pseg = nullptr; JoinProg* pprog = nullptr; int64_t* pcut = nullptr; int S = 0;
     };
     static EdScratch ed_layout(char* base, int64_t rows, int64_t W, int hz, int S);
@@ -1042,13 +1078,13 @@ class Engine {
     };
     EdKey ed_key(int64_t Wo, bool pauses) const { return {rows_id(ST_COMPRESSOR, Wo), ed_buf_.get(), st_db_, st_keep_, st_fade_, pauses ? pl_ms_ : 0.0f}; }
     EdKey ed_key_; bool ed_valid_ = false, ed_host_valid_ = false;
-    std::vector<int64_t> ed_host_, ed_n_;   // [B][2] edges read back; [B] spans
+    std::vector<int64_t> ed_host_;          // [B][2] edges read back
     std::vector<int64_t> pz_host_; int pz_S_ = 0;  // [B][2 S] the rows' cut lists read back with the edges (key.mp != 0)
     DevBuf st_win_; int st_win_hz_ = 0; float st_win_ms_ = -1.0f;  // the fade window on the device, per (rate, fade_ms)
     const float* st_window(int hz);
-    // the two detection launches on rows x W fp32 (x) at hz with the spans in sc.n: the edges and per-row programmes into sc
+    // the two detection launches on rows x W fp32 (x) at hz with the spans n (device): the edges and per-row programmes into sc
     // (sc.S > 0: and the pause limit's launch behind them, Mp samples: the rows' segment tables and cut lists into sc)
-    void ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp = 0);
+    void ed_enqueue(const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp = 0);
     // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already; pauses: with the
     // cuts under pl_ms_ (the fetch paths pass pause_limit_active())
     EdScratch ed_batch(const float* x, int64_t Wo, bool pauses);
@@ -1104,9 +1140,13 @@ class Engine {
     const float* join_f32(const JoinPlan& p);
     LoRes join_measure(const JoinPlan& p, const float* joined, bool on);
     // the plan's device tables in grow-only fetch scratch, uploaded only when the plan differs from what the scratch holds
-    struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };  // tseg: trimmed sources (seg unused)
+    // tseg: trimmed sources (seg unused); span: the programmes' spans [G], what a measurement of the joined rows takes
+    struct JoinTables { const JoinSeg* seg; const JoinProg* prog; const int64_t* span; const JoinSegT* tseg = nullptr; const float* fade = nullptr; };
     JoinTables join_tables(const JoinPlan& p);
-    static std::vector<int64_t> join_table_words(const JoinPlan& p);  // members of 3 words (JoinSeg) or, trimmed sources, 5 (JoinSegT) per piece, then the programmes
+    // programme g's span: what the reference's hosts write to a file, its duration at the output rate (section 11's rule) inside its length
+    std::vector<int64_t> join_spans(const JoinPlan& p) const;
+    // members of 3 words (JoinSeg) or, trimmed sources, 5 (JoinSegT) per piece, then the programmes, then their spans
+    static std::vector<int64_t> join_table_words(const JoinPlan& p, const std::vector<int64_t>& span);
     // the pointers into those words on the device; for trimmed sources also the fade window of the output rate, uploaded here if need be
     // (st_window: why this is no static function; op_join's plans have no trimmed sources and never get there)
     JoinTables join_tables_at(const int64_t* d, const JoinPlan& p);

@@ -435,6 +435,16 @@ char* DevBuf::reserve(Engine& e, size_t bytes, bool* moved) {
     return p_;
 }
 
+// a constant table's device copy: the one place where one is replaced (engine.hpp has the rule; the caller has set the device)
+void* DeviceTable::put(Engine& e, const void* host, size_t bytes) {
+    void* p = nullptr;
+    STN_HIP(hipMalloc(&p, bytes));
+    STN_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, e.stream()));
+    e.sync();
+    if (p_) (void)hipFree(p_);
+    return p_ = p;
+}
+
 int64_t Engine::out_row_len() {
     STN_HIP(hipSetDevice(device_));
     const Batch& b = bt_;
@@ -696,6 +706,7 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
         const bool pauses = pause_limit_active();
         const std::vector<int64_t>& e = ed_batch_host(pauses);
         const int hz = output_rate();
+        const int64_t* n = batch_spans(hz, Wo).host.data();  // the rows' spans: a segment that ends before its row's does is faded out
         const int64_t fd = silence_samples(hz, st_fade_);
         std::vector<float> dur((size_t)b.B);
         for (int i = 0; i < b.B; ++i) {
@@ -711,13 +722,13 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
             const int64_t st = e[(size_t)i * 2], en = e[(size_t)i * 2 + 1], fl = std::min<int64_t>(fd, en - st);
             p.seg_src[(size_t)i] = st;
             p.seg_fin[(size_t)i] = st > 0 ? (int32_t)fl : 0;
-            p.seg_fout[(size_t)i] = en < ed_n_[(size_t)i] ? (int32_t)fl : 0;
+            p.seg_fout[(size_t)i] = en < n[(size_t)i] ? (int32_t)fl : 0;
         }
         if (pauses) {  // member i's pieces: its row's segments in order, from the member's place in the programme
             p.piece_first.assign(1, 0);
             for (int i = 0; i < b.B; ++i) {
                 const int64_t* wr = &pz_host_[(size_t)i * 2 * pz_S_];
-                for (const PausePiece& q : pause_pieces(e[(size_t)i * 2], e[(size_t)i * 2 + 1], ed_n_[(size_t)i], wr + 2, (int)wr[0], fd)) {
+                for (const PausePiece& q : pause_pieces(e[(size_t)i * 2], e[(size_t)i * 2 + 1], n[(size_t)i], wr + 2, (int)wr[0], fd)) {
                     p.piece_dst.push_back(p.seg_dst[(size_t)i] + q.dst); p.piece_len.push_back(q.len); p.piece_src.push_back(q.src);
                     p.piece_fin.push_back(q.fin); p.piece_fout.push_back(q.fout);
                 }
@@ -732,13 +743,14 @@ JoinPlan Engine::batch_join_plan(const stn_join* j) {
     return p;
 }
 
-// [B] members then [G] programmes {len, first | count << 32} as int64 words: a member is {dst, len, source row}, the words of JoinSeg, or,
-// from trimmed sources (p.seg_src set), {dst, len, source row, src, fin | fout << 32}, the words of JoinSegT
-std::vector<int64_t> Engine::join_table_words(const JoinPlan& p) {
+// [B] members, then [G] programmes {len, first | count << 32}, then the [G] spans of the programmes, as int64 words: a member is {dst,
+// len, source row}, the words of JoinSeg, or, from trimmed sources (p.seg_src set), {dst, len, source row, src, fin | fout << 32}, the
+// words of JoinSegT
+std::vector<int64_t> Engine::join_table_words(const JoinPlan& p, const std::vector<int64_t>& span) {
     static_assert(sizeof(JoinSeg) == 24 && sizeof(JoinSegT) == 40 && sizeof(JoinProg) == 16, "the join tables are uploaded as int64 words");
     const bool trim = !p.seg_src.empty(), pieces = !p.piece_first.empty();
     const size_t mw = trim ? 5 : 3, nm = p.pieces();
-    std::vector<int64_t> w(nm * mw + (size_t)p.G * 2);
+    std::vector<int64_t> w(nm * mw + (size_t)p.G * 3);
     for (int i = 0; i < p.B; ++i) {
         if (pieces) {  // (the pause limit: several words of the member's row)
             for (int32_t q = p.piece_first[(size_t)i]; q < p.piece_first[(size_t)i + 1]; ++q) {
@@ -759,16 +771,18 @@ std::vector<int64_t> Engine::join_table_words(const JoinPlan& p) {
         const JoinProg pg{p.prog_len[(size_t)g], first, last - first};
         std::memcpy(&w[nm * mw + (size_t)g * 2], &pg, sizeof(pg));
     }
+    std::copy(span.begin(), span.end(), w.end() - p.G);
     return w;
 }
 
 Engine::JoinTables Engine::join_tables_at(const int64_t* d, const JoinPlan& p) {
-    if (p.seg_src.empty()) return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(d + (size_t)p.B * 3)};
-    return {nullptr, reinterpret_cast<const JoinProg*>(d + p.pieces() * 5), reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
+    const int64_t* prog = d + p.pieces() * (p.seg_src.empty() ? 3 : 5);
+    if (p.seg_src.empty()) return {reinterpret_cast<const JoinSeg*>(d), reinterpret_cast<const JoinProg*>(prog), prog + (size_t)p.G * 2};
+    return {nullptr, reinterpret_cast<const JoinProg*>(prog), prog + (size_t)p.G * 2, reinterpret_cast<const JoinSegT*>(d), st_window(output_rate())};
 }
 
 Engine::JoinTables Engine::join_tables(const JoinPlan& p) {
-    std::vector<int64_t> w = join_table_words(p);
+    std::vector<int64_t> w = join_table_words(p, join_spans(p));
     bool moved = false;
     int64_t* d = reinterpret_cast<int64_t*>(join_tab_.reserve(*this, w.size() * sizeof(int64_t), &moved));
     if (moved || w != join_tab_host_) {  // later fetches of the same batch under the same join reuse the upload
@@ -802,14 +816,19 @@ const float* Engine::join_f32(const JoinPlan& p) {
     return base + off;
 }
 
-Engine::LoRes Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
+std::vector<int64_t> Engine::join_spans(const JoinPlan& p) const {
     const int hz = output_rate();
-    lo_prepare(lo_, hz);
-    // programme g's span: what the reference's hosts write to a file, its duration at the output rate (section 11's rule)
     std::vector<int64_t> n((size_t)p.G);
     for (int g = 0; g < p.G; ++g)
         n[(size_t)g] = std::max<int64_t>(0, std::min<int64_t>(p.prog_len[(size_t)g], (int64_t)(p.prog_dur[(size_t)g] * (float)hz)));
-    return lo_rows(lo_, joined, p.G, p.W_join, std::move(n), on, lo_target_, lo_cap(), lo_true_peak());
+    return n;
+}
+
+// (the programmes' spans ride in the plan's tables: whoever joined the rows, join_f32, has uploaded them, and join_tables finds them)
+Engine::LoRes Engine::join_measure(const JoinPlan& p, const float* joined, bool on) {
+    lo_prepare(lo_, output_rate());
+    const std::vector<int64_t> n = join_spans(p);
+    return lo_rows(lo_.t, joined, p.G, p.W_join, join_tables(p).span, lr_max_seg(lo_.t, n.data(), n.size()), on, lo_target_, lo_cap(), lo_true_peak());
 }
 
 // Loudness off: one join launch behind the optional resample.  On, per member row: the rows measured as every fetch measures them, then
@@ -882,8 +901,9 @@ void Engine::batch_join_loudness(const stn_join* j, float* lufs, float* peak, fl
 void Engine::batch_join_loudness_range(const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st) {
     const JoinPlan p = batch_join_plan(j);
     if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
-    (void)join_measure(p, join_f32(p), lo_on_);
-    lr_report(lo_, p.G, p.W_join, lr_max_seg(lo_), m_max, s_max, lra, n_st);
+    const LoRes m = join_measure(p, join_f32(p), lo_on_);
+    const std::vector<int64_t> n = join_spans(p);
+    lr_report(lo_.t, p.G, p.W_join, m.n, lr_max_seg(lo_.t, n.data(), n.size()), m_max, s_max, lra, n_st);
     sync();
 }
 
@@ -908,7 +928,7 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
     const size_t nx = (size_t)rows * W, ny = (size_t)p.G * p.W_join;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     void* dy = ar_.alloc(ny * eb);
-    const std::vector<int64_t> words = join_table_words(p);
+    const std::vector<int64_t> words = join_table_words(p, p.prog_len);  // (a programme is measured over its whole length)
     int64_t* dt = static_cast<int64_t*>(ar_.alloc(words.size() * sizeof(int64_t)));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dt, words.data(), words.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
@@ -918,8 +938,8 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
     } else {
         float* dj = static_cast<float*>(ar_.alloc(ny * 4));
         join_enqueue(dx, W, t, p, nullptr, ENC_F32, dj, p.W_join);
-        const LoRes res = lo_rows(op_lo_, dj, p.G, p.W_join, p.prog_len, loudness_on, target_lufs, ceiling_dbfs);
-        lo_n_.clear();  // (op_lo_'s rows, not the batch's)
+        const LoRes res = lo_rows(op_lo_.t, dj, p.G, p.W_join, t.span, lr_max_seg(op_lo_.t, p.prog_len.data(), p.prog_len.size()), loudness_on, target_lufs,
+                                  ceiling_dbfs);
         launch_store_rows(s_, dj, p.G, p.W_join, res.gain, enc, dy, p.W_join);
         STN_HIP(hipGetLastError());
         lo_read_back(res, (size_t)p.G, prog_lufs, prog_peak, prog_gain);

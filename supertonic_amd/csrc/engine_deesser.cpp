@@ -82,29 +82,28 @@ Engine::DsScratch Engine::ds_layout(char* base, int64_t rows, int64_t W) {
     sc.s2 = c.take<float>(nc);
     sc.cmax = c.take<float>(nc);
     sc.rmax = c.take<float>((size_t)rows);
-    sc.nw = c.take<int64_t>((size_t)rows);
-    sc.n = c.take<int64_t>((size_t)rows);
     sc.bytes = c.off;
     return sc;
 }
 
-void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const DsScratch& sc, float* y, DsProbe* probe, float* band, float* gr) {
+void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64_t W, const RowSpans& n, const DsScratch& sc, float* y, DsProbe* probe,
+                        float* band, float* gr) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
     auto out = [&](float* dst, const float* src, size_t per) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, nc * per * 4, hipMemcpyDeviceToHost, s_)); };
     // the band's state at every chunk's start: the first two launches of a section pass (section 18)
     StageSpan span(*this, "out", "deesser_band_chunks", 11.0 * samples, samples * 4 + chunks * 20);
-    launch_loudness_chunks(s_, false, x, rows, W, sc.nw, t.band, sc.st, sc.pk, nullptr, nullptr);
+    launch_loudness_chunks(s_, false, x, rows, W, n.full, t.band, sc.st, sc.pk, nullptr, nullptr);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->st_end, sc.st, 4);
     span.next("deesser_band_scan", chunks * 32.0 * 11, chunks * 32);
-    launch_loudness_scan(s_, rows, W, sc.nw, t.band, sc.st);
+    launch_loudness_scan(s_, rows, W, n.full, t.band, sc.st);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->st_start, sc.st, 4);
     // per sample: the two sections (11), log10 (about 20), the gain computer and its cap (9), the detector (3), the smoothing (2), the
     // gain 10^x and its use (about 23)
     span.next("deesser_chunks1", 43.0 * samples, samples * 4 + chunks * 20);
-    launch_deesser_chunks(s_, 1, x, rows, W, sc.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
+    launch_deesser_chunks(s_, 1, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s1_end, sc.s1, 1);
     span.next("deesser_scan1", chunks * 11 * 2, chunks * 8);
@@ -112,7 +111,7 @@ void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s1_start, sc.s1, 1);
     span.next("deesser_chunks2", 45.0 * samples, samples * 4 + chunks * 24);
-    launch_deesser_chunks(s_, 2, x, rows, W, sc.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
+    launch_deesser_chunks(s_, 2, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s2_end, sc.s2, 1);
     span.next("deesser_scan2", chunks * 11 * 2, chunks * 8);
@@ -120,7 +119,7 @@ void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s2_start, sc.s2, 1);
     span.next("deesser_write", 68.0 * samples, samples * (8 + (band ? 4 : 0) + (gr ? 4 : 0)) + chunks * 28);
-    launch_deesser_chunks(s_, 3, x, rows, W, sc.n, t, sc.st, sc.s1, sc.s2, y, band, gr, sc.cmax);
+    launch_deesser_chunks(s_, 3, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, band, gr, sc.cmax);
     STN_HIP(hipGetLastError());
     span.next("deesser_rowmax", chunks, chunks * 4 + (double)rows * 4);
     launch_compressor_rowmax(s_, rows, W, sc.cmax, sc.rmax);
@@ -128,7 +127,7 @@ void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64
 }
 
 void Engine::ds_batch(const float* x, int64_t Wo, float* y) {
-    dyn_batch(ds_, ST_DEESSER, Wo, deesser_table, ds_layout, [&](const DsScratch& sc) { ds_enqueue(ds_.tab.t, x, bt_.B, Wo, sc, y, nullptr, nullptr, nullptr); });
+    dyn_batch(ds_, ST_DEESSER, Wo, deesser_table, ds_layout, [&](const DsScratch& sc, const RowSpans& n) { ds_enqueue(ds_.tab.t, x, bt_.B, Wo, n, sc, y, nullptr, nullptr, nullptr); });
 }
 
 void Engine::batch_deesser(float* max_reduction_db) {
@@ -137,7 +136,7 @@ void Engine::batch_deesser(float* max_reduction_db) {
 
 void Engine::op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe) {
     dyn_op(ds_, hz, rows, W, x, c, y, probe, deesser_table, ds_layout, {probe ? probe->band : nullptr, probe ? probe->gr : nullptr}, deesser_staging_form,
-           [&](const DeessTable& t, const DsScratch& sc, const float* dx, float* dy, float* const* tap) { ds_enqueue(t, dx, rows, W, sc, dy, probe, tap[0], tap[1]); });
+           [&](const DeessTable& t, const DsScratch& sc, RowSpans n, const float* dx, float* dy, float* const* tap) { ds_enqueue(t, dx, rows, W, n, sc, dy, probe, tap[0], tap[1]); });
 }
 
 }  // namespace stn

@@ -3,7 +3,7 @@
 // batch_silence_edges and the join plan share.  The kernels are kernels_edges.hip and join_trim_rows_kernel (kernels_output.hip);
 // DESIGN.md section 14 has the contract.
 // The pause limit lives here too: its setting, its launch behind the detection, and the cuts cached beside the edges.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -62,7 +62,6 @@ Engine::EdScratch Engine::ed_layout(char* base, int64_t rows, int64_t W, int hz,
     sc.pb = c.take<float>(nc);
     sc.lev = c.take<double>(nf);
     sc.edges = c.take<int64_t>((size_t)rows * 2);
-    sc.n = c.take<int64_t>((size_t)rows);
     sc.seg = c.take<JoinSegT>((size_t)rows);
     sc.prog = c.take<JoinProg>((size_t)rows);
     if (S > 0) {  // the pause limit's tables (section 17)
@@ -82,18 +81,18 @@ Engine::EdScratch Engine::ed_scratch(int64_t rows, int64_t W, int hz, int S) {
     return ed_layout(base, rows, W, hz, S);
 }
 
-void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp) {
+void Engine::ed_enqueue(const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp) {
     const double samples = (double)rows * W, chunks = (double)rows * ed_chunks(W);
     {
         StageSpan span(*this, "out", "edges_frames", 2.0 * samples, samples * 4 + chunks * 8);
-        launch_edges_frames(s_, x, rows, W, sc.n, hz, sc.pa, sc.pb);
+        launch_edges_frames(s_, x, rows, W, n, hz, sc.pa, sc.pb);
         span.next("edges_rows", chunks, chunks * 8 + (double)rows * edges_frames(W, hz) * 16);
-        launch_edges_rows(s_, rows, W, sc.n, hz, (double)top_db, silence_samples(hz, keep_ms), silence_samples(hz, fade_ms), sc.pa, sc.pb, sc.lev,
+        launch_edges_rows(s_, rows, W, n, hz, (double)top_db, silence_samples(hz, keep_ms), silence_samples(hz, fade_ms), sc.pa, sc.pb, sc.lev,
                           sc.edges, sc.seg, sc.prog);
         if (sc.S > 0) {
             const double frames = (double)rows * edges_frames(W, hz);
             span.next("pause_rows", frames, frames * 8 + (double)rows * sc.S * (sizeof(JoinSegT) + 16));
-            launch_pause_rows(s_, rows, W, sc.n, hz, (double)top_db, silence_samples(hz, fade_ms), Mp, sc.S, sc.lev, sc.edges, sc.pseg, sc.pprog, sc.pcut);
+            launch_pause_rows(s_, rows, W, n, hz, (double)top_db, silence_samples(hz, fade_ms), Mp, sc.S, sc.lev, sc.edges, sc.pseg, sc.pprog, sc.pcut);
         }
     }
     STN_HIP(hipGetLastError());
@@ -106,10 +105,7 @@ Engine::EdScratch Engine::ed_batch(const float* x, int64_t Wo, bool pauses) {
     const EdScratch sc = ed_scratch(b.B, Wo, hz, pl_stride(pauses, Wo, hz));
     const EdKey key = ed_key(Wo, pauses);
     if (ed_valid_ && key == ed_key_) return sc;
-    // row b's span: section 11's, its reported duration at the output rate
-    ed_n_ = out_spans(Wo, hz);
-    STN_HIP(hipMemcpyAsync(sc.n, ed_n_.data(), ed_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ed_enqueue(x, b.B, Wo, hz, st_db_, st_keep_, st_fade_, sc, pauses ? pause_samples(hz, pl_ms_) : 0);
+    ed_enqueue(x, b.B, Wo, batch_spans(hz, Wo).dev.n, hz, st_db_, st_keep_, st_fade_, sc, pauses ? pause_samples(hz, pl_ms_) : 0);
     ed_key_ = key;
     ed_valid_ = true;
     ed_host_valid_ = false;
@@ -159,8 +155,7 @@ void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int6
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc);
+    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc);
     std::vector<int64_t> e((size_t)rows * 2);
     STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
     if (y) {
@@ -178,7 +173,7 @@ void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int6
         STN_HIP(hipGetLastError());
         STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
     }
-    sync();  // (w, nn and e are read or written by the copies above until here)
+    sync();  // (w and e are read or written by the copies above until here)
     for (int r = 0; r < rows; ++r) {
         if (start) start[r] = e[(size_t)r * 2];
         if (end) end[r] = e[(size_t)r * 2 + 1];
@@ -235,8 +230,7 @@ void Engine::op_pause_trim(int hz, int rows, int W, const float* x, const int64_
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc, Mp);
+    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc, Mp);
     std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
     STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
     STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
@@ -255,7 +249,7 @@ void Engine::op_pause_trim(int hz, int rows, int W, const float* x, const int64_
         STN_HIP(hipGetLastError());
         STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
     }
-    sync();  // (w, nn, e and pz are read or written by the copies above until here)
+    sync();  // (w, e and pz are read or written by the copies above until here)
     for (int r = 0; r < rows; ++r) {
         if (start) start[r] = e[(size_t)r * 2];
         if (end) end[r] = e[(size_t)r * 2 + 1];
@@ -282,8 +276,7 @@ void Engine::op_silence_edges_ex(int hz, int rows, int W, const float* x, const 
     // earlier call's value (every carved array is a multiple of 256 bytes)
     STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pa), 0x7FC00000, sc.bytes / 4, s_));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, hz, top_db, keep_ms, fade_ms, sc, Mp);
+    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc, Mp);
     std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
     STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
     if (S > 0) STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
@@ -292,7 +285,7 @@ void Engine::op_silence_edges_ex(int hz, int rows, int W, const float* x, const 
     if (probe.pb) STN_HIP(hipMemcpyAsync(probe.pb, sc.pb, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
     if (probe.lev) STN_HIP(hipMemcpyAsync(probe.lev, sc.lev, nf * sizeof(double), hipMemcpyDeviceToHost, s_));
     probe.form = edges_staging_form(dx, W);
-    sync();  // (nn, e and pz are read or written by the copies above until here)
+    sync();  // (e and pz are read or written by the copies above until here)
     for (int r = 0; r < rows; ++r) {
         if (start) start[r] = e[(size_t)r * 2];
         if (end) end[r] = e[(size_t)r * 2 + 1];

@@ -75,18 +75,17 @@ Engine::XpScratch Engine::xp_layout(char* base, int64_t rows, int64_t W) {
     sc.ccnt = c.take<int32_t>(nc);
     sc.rmin = c.take<float>((size_t)rows);
     sc.rcnt = c.take<int64_t>((size_t)rows);
-    sc.n = c.take<int64_t>((size_t)rows);
     sc.bytes = c.off;
     return sc;
 }
 
-void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const XpScratch& sc, float* y, float* open, XpProbe* probe) {
+void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const XpScratch& sc, float* y, float* open, XpProbe* probe) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     const size_t st_bytes = (size_t)rows * (size_t)lo_chunks(W) * 4;
     auto out = [&](float* dst, const float* src) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, st_bytes, hipMemcpyDeviceToHost, s_)); };
     // per sample: log10 (about 20), the gain computer (11), the detector (2), the clamp and the smoothing (3), the gain 10^x and its product (about 22)
     StageSpan span(*this, "out", "expander_chunks1", 33.0 * samples, samples * 4 + chunks * 4);
-    launch_expander_chunks(s_, 1, x, rows, W, sc.n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
+    launch_expander_chunks(s_, 1, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s1_end, sc.s1);
     span.next("expander_scan1", chunks * 11 * 2, chunks * 8);
@@ -94,7 +93,7 @@ void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s1_start, sc.s1);
     span.next("expander_chunks2", 36.0 * samples, samples * 4 + chunks * 8);
-    launch_expander_chunks(s_, 2, x, rows, W, sc.n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
+    launch_expander_chunks(s_, 2, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s2_end, sc.s2);
     span.next("expander_scan2", chunks * 11 * 2, chunks * 8);
@@ -102,7 +101,7 @@ void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t
     STN_HIP(hipGetLastError());
     if (probe) out(probe->s2_start, sc.s2);
     span.next("expander_write", 60.0 * samples, samples * (open ? 12 : 8) + chunks * 16);
-    launch_expander_chunks(s_, 3, x, rows, W, sc.n, t, sc.s1, sc.s2, y, open, sc.cmin, sc.ccnt);
+    launch_expander_chunks(s_, 3, x, rows, W, n, t, sc.s1, sc.s2, y, open, sc.cmin, sc.ccnt);
     STN_HIP(hipGetLastError());
     span.next("expander_rows", chunks * 2, chunks * 8 + (double)rows * 12);
     launch_expander_rows(s_, rows, W, t, sc.cmin, sc.ccnt, sc.rmin, sc.rcnt);
@@ -110,7 +109,7 @@ void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t
 }
 
 void Engine::xp_batch(const float* x, int64_t Wo, float* y) {
-    dyn_batch(xp_, ST_EXPANDER, Wo, expander_table, xp_layout, [&](const XpScratch& sc) { xp_enqueue(xp_.tab.t, x, bt_.B, Wo, sc, y, nullptr, nullptr); });
+    dyn_batch(xp_, ST_EXPANDER, Wo, expander_table, xp_layout, [&](const XpScratch& sc, const RowSpans& n) { xp_enqueue(xp_.tab.t, x, bt_.B, Wo, n.n, sc, y, nullptr, nullptr); });
 }
 
 void Engine::batch_expander(float* min_attenuation_db, int64_t* closed_samples) {
@@ -122,7 +121,7 @@ void Engine::batch_expander(float* min_attenuation_db, int64_t* closed_samples) 
 
 void Engine::op_expander(int hz, int rows, int W, const float* x, const stn_expander& c, float* y, XpProbe* probe) {
     dyn_op(xp_, hz, rows, W, x, c, y, probe, expander_table, xp_layout, {probe ? probe->open : nullptr}, expander_staging_form,
-           [&](const ExpTable& t, const XpScratch& sc, const float* dx, float* dy, float* const* tap) { xp_enqueue(t, dx, rows, W, sc, dy, tap[0], probe); });
+           [&](const ExpTable& t, const XpScratch& sc, RowSpans n, const float* dx, float* dy, float* const* tap) { xp_enqueue(t, dx, rows, W, n.n, sc, dy, tap[0], probe); });
 }
 
 }  // namespace stn

@@ -106,23 +106,13 @@ void filter_table(int hz, int n, const stn_filter* f, FilterTable& t) {
     }
 }
 
-void Engine::fl_prepare(FilterTable& t, int hz, int n, const stn_filter* f) {
-    if (t.hz == hz && same_chain(t.f, n, f) && (t.pass.empty() || t.pass[0].dev)) return;
+void Engine::fl_prepare(FlTable& m, int hz, int n, const stn_filter* f) {
+    if (m.t.hz == hz && same_chain(m.t.f, n, f)) return;  // (a table of n >= 1 sections is up once it is here: a fresh one has none)
     FilterTable nt;
     filter_table(hz, n, f, nt);
-    STN_HIP(hipSetDevice(device_));
-    for (LoudTable& T : nt.pass) {
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(&T.dev), T.mpow.size() * sizeof(double)));
-        STN_HIP(hipMemcpyAsync(T.dev, T.mpow.data(), T.mpow.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    }
-    sync();  // (the uploads read nt's host copies, and a fetch may still be reading the old tables)
-    for (LoudTable& T : t.pass) if (T.dev) (void)hipFree(T.dev);
-    t = std::move(nt);
-}
-
-void Engine::fl_release() {
-    for (FilterTable* t : {&fl_, &op_fl_})
-        for (LoudTable& T : t->pass) if (T.dev) { (void)hipFree(T.dev); T.dev = nullptr; }
+    m.t = FilterTable();  // (no chain's table while its device copies change hands)
+    for (size_t p = 0; p < nt.pass.size(); ++p) nt.pass[p].dev = m.dev[p].put(*this, nt.pass[p].mpow);
+    m.t = std::move(nt);
 }
 
 void Engine::set_filters(int n, const stn_filter* f) {
@@ -138,12 +128,11 @@ Engine::FlScratch Engine::fl_layout(char* base, int64_t rows, int64_t W) {
     FlScratch sc{};
     sc.st = c.take<float>(nc * 4);
     sc.pk = c.take<float>(nc);
-    sc.n = c.take<int64_t>((size_t)rows);
     sc.bytes = c.off;
     return sc;
 }
 
-void Engine::fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const FlScratch& sc, float* y, FlProbe* probe) {
+void Engine::fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int64_t W, const int64_t* full, const FlScratch& sc, float* y, FlProbe* probe) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     const size_t st_bytes = (size_t)rows * (size_t)lo_chunks(W) * 16;
     for (size_t p = 0; p < t.pass.size(); ++p) {
@@ -151,11 +140,11 @@ void Engine::fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int6
         const float* src = p == 0 ? x : y;
         if (probe) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, st_bytes / 4, s_));
         StageSpan span(*this, "out", "filter_chunks", 11.0 * samples, samples * 4 + chunks * 20);
-        launch_loudness_chunks(s_, false, src, rows, W, sc.n, T, sc.st, sc.pk, nullptr, nullptr);
+        launch_loudness_chunks(s_, false, src, rows, W, full, T, sc.st, sc.pk, nullptr, nullptr);
         STN_HIP(hipGetLastError());
         if (probe && probe->st_end) STN_HIP(hipMemcpyAsync(probe->st_end + p * (st_bytes / 4), sc.st, st_bytes, hipMemcpyDeviceToHost, s_));
         span.next("filter_scan", chunks * 32.0 * 11, chunks * 32);
-        launch_loudness_scan(s_, rows, W, sc.n, T, sc.st);
+        launch_loudness_scan(s_, rows, W, full, T, sc.st);
         STN_HIP(hipGetLastError());
         span.next("filter_write", 11.0 * samples, samples * 8 + chunks * 16);
         launch_filter_write(s_, src, rows, W, T, sc.st, y);
@@ -169,16 +158,8 @@ void Engine::fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int6
 void Engine::fl_batch(const float* x, int64_t Wo, float* y) {
     const Batch& b = bt_;
     fl_prepare(fl_, output_rate(), (int)fl_set_.size(), fl_set_.data());
-    bool moved = false;
-    char* base = fl_buf_.reserve(*this, fl_layout(nullptr, b.B, Wo).bytes, &moved);
-    const FlScratch sc = fl_layout(base, b.B, Wo);
-    if (moved || fl_n_ptr_ != sc.n || fl_n_rows_ != b.B || fl_n_W_ != Wo) {  // every row's length is Wo: uploaded when the shape changes
-        const std::vector<int64_t> n((size_t)b.B, Wo);
-        STN_HIP(hipMemcpyAsync(sc.n, n.data(), n.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-        sync();  // (n is this frame's)
-        fl_n_ptr_ = sc.n; fl_n_rows_ = b.B; fl_n_W_ = Wo;
-    }
-    fl_enqueue(fl_, x, b.B, Wo, sc, y, nullptr);
+    const FlScratch sc = fl_layout(fl_buf_.reserve(*this, fl_layout(nullptr, b.B, Wo).bytes), b.B, Wo);
+    fl_enqueue(fl_.t, x, b.B, Wo, batch_spans(output_rate(), Wo).dev.full, sc, y, nullptr);
 }
 
 void Engine::op_filter(int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y, FlProbe* probe) {
@@ -188,9 +169,7 @@ void Engine::op_filter(int hz, int rows, int W, const float* x, int n, const stn
     ar_.reset();
     GuardedRows r(*this, (size_t)rows * W, x, probe, probe && probe->x_misalign, false);
     const FlScratch sc = fl_layout(static_cast<char*>(ar_.alloc(fl_layout(nullptr, rows, W).bytes)), rows, W);
-    const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    fl_enqueue(op_fl_, r.dx, rows, W, sc, r.dy, probe);
+    fl_enqueue(op_fl_.t, r.dx, rows, W, op_spans(rows, W, std::vector<int64_t>((size_t)rows, (int64_t)W)).full, sc, r.dy, probe);
     r.download(y);
     if (probe) {
         probe->guard_ok = r.guards_ok();

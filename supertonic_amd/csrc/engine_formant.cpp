@@ -54,7 +54,7 @@ void Engine::op_formant(int hz, int rows, int W, const float* x, const float* y,
     const size_t nx = (size_t)rows * W;
     float* blk[3];
     for (float*& b : blk) b = static_cast<float*>(ar_.alloc((nx + 2 * G) * 4));
-    int64_t* dn = static_cast<int64_t*>(ar_.alloc(nn.size() * sizeof(int64_t)));
+    const int64_t* dn = op_spans(rows, W, nn).n;
     float* dwin = static_cast<float*>(ar_.alloc(win.size() * sizeof(float)));
     const size_t sc_bytes = fm_layout(nullptr, rows, W, f).bytes;
     char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
@@ -66,7 +66,6 @@ void Engine::op_formant(int hz, int rows, int W, const float* x, const float* y,
     }
     STN_HIP(hipMemcpyAsync(blk[0] + G, x, nx * 4, hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(blk[1] + G, y, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dwin, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.lagw, lagw.data(), lagw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
     fm_enqueue(blk[0] + G, blk[1] + G, rows, W, dn, f, dwin, sc);
@@ -84,7 +83,7 @@ void Engine::op_formant(int hz, int rows, int W, const float* x, const float* y,
             STN_HIP(hipMemcpyAsync(guards.data() + (2 * i + 1) * G, blk[i] + G + nx, G * 4, hipMemcpyDeviceToHost, s_));
         }
     }
-    sync();  // (nn, win, lagw and guards are read or written by the copies above until here)
+    sync();  // (win, lagw and guards are read or written by the copies above until here)
     if (probe) probe->guard_ok = std::all_of(guards.begin(), guards.end(), [](uint32_t v) { return v == 0x7FC00000u; });
 }
 

@@ -82,11 +82,10 @@ inline bool same_setting(const Set& a, const Set& b) {
         if (!(x[i].v == y[i].v)) return false;
     return same_tail(a, b);
 }
-// a table's device copies with the host arrays they are made from, in upload order
-struct DevTab { double** dev; const std::vector<double>* host; };
-inline std::array<DevTab, 1> dev_tables(CompTable& t) { return {{{&t.dev, &t.pw}}}; }
-inline std::array<DevTab, 1> dev_tables(ExpTable& t) { return {{{&t.dev, &t.pw}}}; }
-inline std::array<DevTab, 2> dev_tables(DeessTable& t) { return {{{&t.band.dev, &t.band.mpow}, {&t.det.dev, &t.det.pw}}}; }
+// a table's host arrays handed over to their owners d, and its device pointers filled in from them
+inline void to_device(Engine& e, DeviceTable* d, CompTable& t) { t.dev = d[0].put(e, t.pw); }
+inline void to_device(Engine& e, DeviceTable* d, ExpTable& t) { t.dev = d[0].put(e, t.pw); }
+inline void to_device(Engine& e, DeviceTable* d, DeessTable& t) { t.band.dev = d[0].put(e, t.band.mpow); t.det.dev = d[1].put(e, t.det.pw); }
 
 // set_<stage>: off bumps the generation only if the stage was on, the same setting again bumps nothing, a refused one changes nothing
 template <class St, class Set>
@@ -103,51 +102,23 @@ inline void dyn_set(St& st, bool on, const Set* c, const std::string& why) {
     ++st.gen;
 }
 
-template <class St>
-inline void dyn_release(St& st) {
-    for (auto* m : {&st.tab, &st.op_tab})
-        for (DevTab d : dev_tables(m->t))
-            if (*d.dev) { (void)hipFree(*d.dev); *d.dev = nullptr; }
-}
-
 template <class Made, class Set, class Build>
 void Engine::dyn_prepare(Made& m, int hz, const Set& c, Build build) {
-    const auto tabs = dev_tables(m.t);
-    if (m.t.hz == hz && std::all_of(tabs.begin(), tabs.end(), [](const DevTab& d) { return *d.dev != nullptr; }) && same_setting(m.from, c)) return;
-    Made nm;
-    build(hz, c, nm.t);
-    nm.from = c;
-    STN_HIP(hipSetDevice(device_));
-    for (DevTab d : dev_tables(nm.t)) {
-        STN_HIP(hipMalloc(reinterpret_cast<void**>(d.dev), d.host->size() * sizeof(double)));
-        STN_HIP(hipMemcpyAsync(*d.dev, d.host->data(), d.host->size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    }
-    sync();  // (the uploads read nm's host copies, and a fetch may still be reading the old tables)
-    for (DevTab d : tabs)
-        if (*d.dev) (void)hipFree(*d.dev);
-    m = std::move(nm);
+    if (m.dev[0] && m.t.hz == hz && same_setting(m.from, c)) return;
+    decltype(m.t) t;
+    build(hz, c, t);
+    m.t.hz = -1;  // (no rate's table while its device copies change hands)
+    to_device(*this, m.dev, t);
+    m.t = std::move(t);
+    m.from = c;
 }
 
 template <class St, class Build, class Layout, class Run>
 void Engine::dyn_batch(St& st, Stage stage, int64_t Wo, Build build, Layout layout, Run run) {
     const int hz = output_rate();
     dyn_prepare(st.tab, hz, st.set, build);
-    bool moved = false;
-    char* base = st.buf.reserve(*this, layout(nullptr, bt_.B, Wo).bytes, &moved);
-    const auto sc = layout(base, bt_.B, Wo);
-    // row b's valid samples: section 11's span, its reported duration at the output rate; uploaded once per finished batch, with the
-    // width where the stage's launches take one (sc.nw)
-    std::vector<int64_t> n = out_spans(Wo, hz);
-    if (moved || n != st.n || st.n_ptr != sc.n || (sc.nw && st.n_W != Wo)) {
-        st.n = std::move(n);
-        st.n_ptr = sc.n;
-        st.n_W = Wo;
-        const std::vector<int64_t> nw(sc.nw ? (size_t)bt_.B : 0, Wo);
-        STN_HIP(hipMemcpyAsync(sc.n, st.n.data(), st.n.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-        if (sc.nw) STN_HIP(hipMemcpyAsync(sc.nw, nw.data(), nw.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-        sync();  // (the uploads read st.n, which the next batch's lengths replace, and nw, this frame's; once per finished batch, as fl_batch)
-    }
-    run(sc);
+    const auto sc = layout(st.buf.reserve(*this, layout(nullptr, bt_.B, Wo).bytes), bt_.B, Wo);
+    run(sc, batch_spans(hz, Wo).dev);
     st.key = rows_id(stage, Wo);
     st.key_buf = st.buf.get();
     st.valid = true;
@@ -193,10 +164,7 @@ void Engine::dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& 
             if (d) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7FC00000, nx, s_));
         STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
     }
-    const std::vector<int64_t> nn((size_t)rows, (int64_t)W);
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    if (sc.nw) STN_HIP(hipMemcpyAsync(sc.nw, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    run(st.op_tab.t, sc, r.dx, r.dy, dev.data());
+    run(st.op_tab.t, sc, op_spans(rows, W, std::vector<int64_t>((size_t)rows, (int64_t)W)), r.dx, r.dy, dev.data());
     r.download(y);
     size_t i = 0;
     for (float* h : taps) {

@@ -137,11 +137,10 @@ void Engine::op_limiter_ex(int hz, int rows, int W, const float* x, const int64_
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     float* ds = s ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
-    int64_t* dn = static_cast<int64_t*>(ar_.alloc((size_t)rows * 8));
+    const int64_t* dn = op_spans(rows, W, nn).n;
     float* dw = static_cast<float*>(ar_.alloc(w.size() * 4));
     float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
     if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
     lm_enqueue(dx, rows, W, dn, dg, (float)std::pow(10.0, (double)ceiling_dbfs / 20.0), limiter_samples(hz, lookahead_ms), dw, sc, ds, tpm ? &tp : nullptr);
@@ -152,7 +151,7 @@ void Engine::op_limiter_ex(int hz, int rows, int W, const float* x, const int64_
     if (tpm && env) STN_HIP(hipMemcpyAsync(env, tp.env, nx * 4, hipMemcpyDeviceToHost, s_));
     if (tpm && trim) STN_HIP(hipMemcpyAsync(trim, tp.trim, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
     if (!tpm && trim) std::fill(trim, trim + rows, 1.0f);
-    sync();  // (nn and w are read by the copies above until here)
+    sync();  // (w is read by the copy above until here)
 }
 
 }  // namespace stn

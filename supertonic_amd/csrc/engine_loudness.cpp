@@ -1,7 +1,7 @@
 // engine_loudness.cpp — loudness normalization of a handle's fetches: the K-weighting design (host only), the scan's power table, the
 // measurement's scratch, and the measurement the output stage (engine_batch.cpp) and batch_loudness share.  The kernels are
 // kernels_loudness.hip; DESIGN.md section 11 has the contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -102,19 +102,12 @@ std::string loudness_design(int hz, LoudTable& t) {
     return "";
 }
 
-void Engine::lo_prepare(LoudTable& t, int hz) {
-    if (t.dev && t.hz == hz) return;
+void Engine::lo_prepare(OnDevice<LoudTable>& m, int hz) {
+    if (m.t.dev && m.t.hz == hz) return;
     LoudTable n;
     refuse(loudness_design(hz, n));
-    STN_HIP(hipSetDevice(device_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.mpow.size() * sizeof(double)));
-    STN_HIP(hipMemcpyAsync(n.dev, n.mpow.data(), n.mpow.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    if (t.dev) { sync(); (void)hipFree(t.dev); }  // a fetch may still be reading the old table
-    t = std::move(n);
-}
-
-void Engine::lo_release() {
-    for (LoudTable* t : {&lo_, &op_lo_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
+    n.dev = m.dev[0].put(*this, n.mpow);
+    m.t = std::move(n);
 }
 
 void Engine::set_loudness(bool on, float target, float ceiling) {
@@ -139,38 +132,29 @@ Engine::LoScratch Engine::lo_layout(char* base, int64_t rows, int64_t W) {
     sc.pa = c.take<float>(nc);
     sc.pb = c.take<float>(nc);
     sc.res = c.take<float>((size_t)rows * 3);
-    // (the row lengths sit behind the per-chunk arrays: another rows x W moves them, so lo_n_ptr_ remembers where they went)
-    sc.n = c.take<int64_t>((size_t)rows);
-    if (base) sc.out = {sc.res, sc.res + rows, sc.res + 2 * rows, sc.n};
+    if (base) sc.out = {sc.res, sc.res + rows, sc.res + 2 * rows, nullptr};
     sc.bytes = c.off;
     return sc;
 }
 
-Engine::LoScratch Engine::lo_scratch(int64_t rows, int64_t W) {
-    bool moved = false;
-    char* base = lo_buf_.reserve(*this, lo_layout(nullptr, rows, W).bytes, &moved);
-    if (moved) lo_n_.clear();
-    return lo_layout(base, rows, W);
-}
-
-void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const LoScratch& sc, int64_t max_seg, bool on, float target, float ceiling,
-                        float* st_end, bool true_peak) {
+void Engine::lo_measure(const LoudTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoScratch& sc, int64_t max_seg, bool on,
+                        float target, float ceiling, float* st_end, bool true_peak) {
     const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
     StageSpan span(*this, "out", "loudness", 20.0 * samples, samples * 4 + chunks * 20);
     auto next = [&](double flops, double bytes) { STN_HIP(hipGetLastError()); span.next("loudness", flops, bytes); };  // (the launch before it is checked)
-    launch_loudness_chunks(s_, false, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    launch_loudness_chunks(s_, false, x, rows, W, n, t, sc.st, sc.pk, sc.pa, sc.pb);
     if (st_end) STN_HIP(hipMemcpyAsync(st_end, sc.st, (size_t)rows * (size_t)lo_chunks(W) * 16, hipMemcpyDeviceToHost, s_));
     next(chunks * 32.0 * 11, chunks * 32);
-    launch_loudness_scan(s_, rows, W, sc.n, t, sc.st);
+    launch_loudness_scan(s_, rows, W, n, t, sc.st);
     next(22.0 * samples, samples * 4 + chunks * 24);
-    launch_loudness_chunks(s_, true, x, rows, W, sc.n, t, sc.st, sc.pk, sc.pa, sc.pb);
+    launch_loudness_chunks(s_, true, x, rows, W, n, t, sc.st, sc.pk, sc.pa, sc.pb);
     if (true_peak) {  // section 16: pk becomes the per-chunk true peaks, and the gate, untouched, caps the gain by the row's true peak
         STN_HIP(hipGetLastError());
         span.next("true_peak", 97.0 * samples, samples * 4 + chunks * 4);
-        launch_truepeak(s_, x, rows, W, sc.n, nullptr, sc.pk, nullptr);
+        launch_truepeak(s_, x, rows, W, n, nullptr, sc.pk, nullptr);
     }
     next(chunks * 2, chunks * 12 + (double)rows * 12);
-    launch_loudness_gate(s_, rows, W, sc.n, t, sc.pk, sc.pa, sc.pb, max_seg, on, target, ceiling, sc.res);
+    launch_loudness_gate(s_, rows, W, n, t, sc.pk, sc.pa, sc.pb, max_seg, on, target, ceiling, sc.res);
     STN_HIP(hipGetLastError());
 }
 
@@ -180,34 +164,65 @@ void Engine::lo_read_back(const LoRes& m, size_t n, float* lufs, float* peak, fl
     if (gain) STN_HIP(hipMemcpyAsync(gain, m.gain, n * 4, hipMemcpyDeviceToHost, s_));
 }
 
-// row b's span: its reported duration (after /speed) at the output rate, as the reference's hosts cut the file, inside [0, Wo]
-std::vector<int64_t> Engine::out_spans(int64_t Wo, int hz) const {
+// row b's span: its reported duration (after /speed) at hz, as the reference's hosts cut the file, inside [0, W]
+std::vector<int64_t> Engine::out_spans(int64_t W, int hz) const {
     std::vector<int64_t> n((size_t)bt_.B);
-    for (int i = 0; i < bt_.B; ++i) n[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(Wo, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
+    for (int i = 0; i < bt_.B; ++i) n[(size_t)i] = std::max<int64_t>(0, std::min<int64_t>(W, (int64_t)(reported_dur_[(size_t)i] * (float)hz)));
     return n;
+}
+
+// The upload rule of the span table, stated once:
+//  - how often: once per finished batch (ed_seq_) and per (hz, W); the fetches, reports and stages in between find the entry and
+//    upload nothing.  Two entries, so that a fetch with pitch and a rate set finds both of its keys.  A block that moved (more rows
+//    than ever) holds nothing, and another row count puts the entries elsewhere in it.
+//  - no host wait on the way: the upload is enqueued and the fetch goes on (fetch_*_begin stays asynchronous).
+//  - the host copy an upload reads is e.host, an engine member, replaced only behind a drained stream: the batch_upload of a new
+//    batch has drained it since, and a replacement nothing has drained for (another rate within the same batch) waits first.
+const Engine::BatchSpans& Engine::batch_spans(int hz, int64_t W) {
+    const size_t B = (size_t)bt_.B;
+    Carve size{nullptr};
+    for (size_t k = 0; k < std::size(sp_); ++k) size.take<int64_t>(2 * B);
+    bool moved = false;
+    Carve c{sp_buf_.reserve(*this, size.off, &moved)};
+    if (moved) for (BatchSpans& e : sp_) e.dev = RowSpans();
+    int64_t* d = nullptr;
+    const size_t slot = hz == a_.sample_rate && W == native_row_len() ? 0 : 1;
+    for (size_t k = 0; k <= slot; ++k) d = c.take<int64_t>(2 * B);
+    BatchSpans& e = sp_[slot];
+    if (e.seq == ed_seq_ && e.hz == hz && e.W == W && e.host.size() == 2 * B && e.dev.n == d) return e;
+    if (e.drains == drains_) sync();
+    e.host = out_spans(W, hz);
+    e.host.resize(2 * B, W);
+    STN_HIP(hipMemcpyAsync(d, e.host.data(), e.host.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    ++sp_uploads_;
+    e.dev = {d, d + B};
+    e.seq = ed_seq_; e.hz = hz; e.W = W; e.drains = drains_;
+    return e;
+}
+
+RowSpans Engine::op_spans(int rows, int W, std::vector<int64_t> n) {
+    op_sp_ = std::move(n);
+    op_sp_.resize((size_t)rows * 2, (int64_t)W);
+    const int64_t* d = detail::up(ar_, s_, op_sp_.data(), op_sp_.size());
+    return {d, d + rows};
 }
 
 Engine::LoRes Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     const Batch& b = bt_;
     const int hz = output_rate();
     lo_prepare(lo_, hz);
-    return lo_rows(lo_, x, b.B, Wo, out_spans(Wo, hz), on, lo_target_, lo_cap(), lo_true_peak());  // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
+    const BatchSpans& sp = batch_spans(hz, Wo);
+    // (the limiter, when active, enforces the ceiling: DESIGN.md section 15)
+    return lo_rows(lo_.t, x, b.B, Wo, sp.dev.n, lr_max_seg(lo_.t, sp.host.data(), (size_t)b.B), on, lo_target_, lo_cap(), lo_true_peak());
 }
 
-Engine::LoRes Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, std::vector<int64_t> n, bool on, float target,
+Engine::LoRes Engine::lo_rows(const LoudTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, int64_t max_seg, bool on, float target,
                               float ceiling, bool true_peak) {
-    int64_t max_seg = 0;
-    for (int64_t v : n) max_seg = std::max<int64_t>(max_seg, v / t.hop);
     const LoScratch sc = lo_scratch(rows, W);
-    // uploaded once per finished batch (and again only when the scratch moved or other rows were measured in between): later fetches
-    // of the same batch reuse it
-    if (n != lo_n_ || lo_n_ptr_ != sc.n) {
-        lo_n_ = std::move(n);
-        lo_n_ptr_ = sc.n;
-        STN_HIP(hipMemcpyAsync(sc.n, lo_n_.data(), lo_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    }
-    lo_measure(t, x, rows, W, sc, max_seg, on, target, ceiling, nullptr, true_peak);
-    return sc.out;
+    lo_measure(t, x, rows, W, n, sc, max_seg, on, target, ceiling, nullptr, true_peak);
+    LoRes m = sc.out;
+    m.n = n;
+    return m;
 }
 
 void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
@@ -216,23 +231,21 @@ void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
     sync();
 }
 
-void Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
-                   float* peak, float* gain) {
+const int64_t* Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
+                             float* peak, float* gain) {
     STN_HIP(hipSetDevice(device_));
     lo_prepare(op_lo_, hz);
     const std::vector<int64_t> nn = spans("op_loudness", rows, W, n);
-    int64_t max_seg = 0;
-    for (int64_t v : nn) max_seg = std::max<int64_t>(max_seg, v / op_lo_.hop);
+    const int64_t max_seg = lr_max_seg(op_lo_.t, nn.data(), nn.size());
     ar_.reset();
     const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
     float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     const LoScratch sc = lo_scratch(rows, W);
     if (probe)  // every per-chunk array and the results: what a launch fails to write reads back as this, not as an earlier call's value
-        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, (size_t)(reinterpret_cast<char*>(sc.n) - reinterpret_cast<char*>(sc.st)) / 4, s_));
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    lo_n_.clear();  // (the batch's lengths are no longer there)
-    lo_measure(op_lo_, dx, rows, W, sc, max_seg, on, target, ceiling, probe ? probe->st_end : nullptr);
+        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, sc.bytes / 4, s_));
+    const int64_t* dn = op_spans(rows, W, nn).n;
+    lo_measure(op_lo_.t, dx, rows, W, dn, sc, max_seg, on, target, ceiling, probe ? probe->st_end : nullptr);
     lo_read_back(sc.out, (size_t)rows, lufs, peak, gain);
     if (probe) {
         const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
@@ -244,6 +257,7 @@ void Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bo
         probe->form = loudness_staging_form(dx, W);
     }
     sync();
+    return dn;
 }
 
 void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
@@ -252,13 +266,13 @@ void Engine::op_loudness(int hz, int rows, int W, const float* x, const int64_t*
 
 // ---- the loudness report
 
-int64_t Engine::lr_max_seg(const LoudTable& t) const {
+int64_t Engine::lr_max_seg(const LoudTable& t, const int64_t* n, size_t rows) {
     int64_t m = 0;
-    for (int64_t v : lo_n_) m = std::max<int64_t>(m, v / t.hop);
+    for (size_t r = 0; r < rows; ++r) m = std::max<int64_t>(m, n[r] / t.hop);
     return m;
 }
 
-void Engine::lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st) {
+void Engine::lr_report(const LoudTable& t, int64_t rows, int64_t W, const int64_t* n, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st) {
     refuse(loudness_range_check(max_seg));
     const LoScratch sc = lo_scratch(rows, W);  // (as the measurement carved it: the same size moves nothing)
     Carve sz{nullptr};
@@ -270,20 +284,20 @@ void Engine::lr_report(const LoudTable& t, int64_t rows, int64_t W, int64_t max_
     {
         const double chunks = (double)rows * lo_chunks(W);
         StageSpan span(*this, "out", "loudness_range", chunks * 2, chunks * 8 + (double)rows * 16);
-        launch_loudness_range(s_, rows, W, sc.n, t, sc.pa, sc.pb, max_seg, res, nst);
+        launch_loudness_range(s_, rows, W, n, t, sc.pa, sc.pb, max_seg, res, nst);
     }
     STN_HIP(hipGetLastError());
-    const size_t n = (size_t)rows;
-    if (m_max) STN_HIP(hipMemcpyAsync(m_max, res, n * 4, hipMemcpyDeviceToHost, s_));
-    if (s_max) STN_HIP(hipMemcpyAsync(s_max, res + n, n * 4, hipMemcpyDeviceToHost, s_));
-    if (lra) STN_HIP(hipMemcpyAsync(lra, res + 2 * n, n * 4, hipMemcpyDeviceToHost, s_));
-    if (n_st) STN_HIP(hipMemcpyAsync(n_st, nst, n * 4, hipMemcpyDeviceToHost, s_));
+    const size_t nr = (size_t)rows;
+    if (m_max) STN_HIP(hipMemcpyAsync(m_max, res, nr * 4, hipMemcpyDeviceToHost, s_));
+    if (s_max) STN_HIP(hipMemcpyAsync(s_max, res + nr, nr * 4, hipMemcpyDeviceToHost, s_));
+    if (lra) STN_HIP(hipMemcpyAsync(lra, res + 2 * nr, nr * 4, hipMemcpyDeviceToHost, s_));
+    if (n_st) STN_HIP(hipMemcpyAsync(n_st, nst, nr * 4, hipMemcpyDeviceToHost, s_));
 }
 
 void Engine::batch_loudness_range(float* m_max, float* s_max, float* lra, int32_t* n_st) {
     const int64_t Wo = out_row_len();
-    (void)lo_batch(out_source(Wo), Wo, lo_on_);
-    lr_report(lo_, bt_.B, Wo, lr_max_seg(lo_), m_max, s_max, lra, n_st);
+    const LoRes m = lo_batch(out_source(Wo), Wo, lo_on_);
+    lr_report(lo_.t, bt_.B, Wo, m.n, lr_max_seg(lo_.t, batch_spans(output_rate(), Wo).host.data(), (size_t)bt_.B), m_max, s_max, lra, n_st);
     sync();
 }
 
@@ -292,8 +306,8 @@ void Engine::op_loudness_range(int hz, int rows, int W, const float* x, const in
     int64_t max_seg = 0;
     for (int64_t v : spans("op_loudness_range", rows, W, n)) max_seg = std::max<int64_t>(max_seg, v / ((hz + 5) / 10));
     refuse(loudness_range_check(max_seg));  // (before the upload and the measurement, which a longer row passes)
-    lo_op(hz, rows, W, x, n, false, lo_target_, lo_ceiling_, nullptr, nullptr, nullptr, nullptr);
-    lr_report(op_lo_, rows, W, max_seg, m_max, s_max, lra, n_st);
+    const int64_t* dn = lo_op(hz, rows, W, x, n, false, lo_target_, lo_ceiling_, nullptr, nullptr, nullptr, nullptr);
+    lr_report(op_lo_.t, rows, W, dn, max_seg, m_max, s_max, lra, n_st);
     sync();
 }
 

@@ -1,7 +1,7 @@
 // engine_pitch.cpp — the pitch of a handle: a shift of s semitones is a time stretch by a / b ~ 2^(s/12) at the
 // model's rate (WSOLA, kernels_pitch.hip) and a resample by b / a back to the row length (kernels_resample.hip), in front of every other
 // stage of the output stage.  The ratio, the geometry and the window are host/pitch.cpp.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include "host/pitch.hpp"
 
@@ -11,16 +11,13 @@ namespace stn {
 // so a k with min k >= 8000 has max k <= 17280).  stn_op_resample(a k, b k) designs the same table.
 static int ps_rate_scale(int a, int b) { return (RESAMPLE_MIN_HZ + std::min(a, b) - 1) / std::min(a, b); }
 
-void Engine::ps_table(ResampleTable& t, int a, int b) {
+void Engine::ps_table(RsTable& m, int a, int b) {
     const int k = ps_rate_scale(a, b);
-    if (t.dev && t.in_hz == a * k && t.out_hz == b * k) return;
+    if (m.t.dev && m.t.in_hz == a * k && m.t.out_hz == b * k) return;
     ResampleTable n;
     resample_design_pq(b, a, a * k, b * k, n);
-    STN_HIP(hipSetDevice(device_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.taps.size() * sizeof(float)));
-    STN_HIP(hipMemcpyAsync(n.dev, n.taps.data(), n.taps.size() * sizeof(float), hipMemcpyHostToDevice, s_));
-    if (t.dev) { sync(); (void)hipFree(t.dev); }  // a fetch may still be reading the old table
-    t = std::move(n);
+    n.dev = m.dev[0].put(*this, n.taps);
+    m.t = std::move(n);
 }
 
 void Engine::set_pitch(float semitones) {
@@ -33,7 +30,6 @@ void Engine::set_pitch(float semitones) {
 Engine::PsScratch Engine::ps_layout(char* base, int64_t rows, int64_t W, const PitchPlan& p) {
     Carve c{base};
     PsScratch sc;
-    sc.n = c.take<int64_t>((size_t)rows);
     sc.win = c.take<float>((size_t)2 * p.H);
     sc.delta = c.take<int>((size_t)rows * p.M);
     sc.score = c.take<float>((size_t)rows * p.M);
@@ -82,19 +78,18 @@ const float* Engine::ps_batch() {
     const float* res = formant ? fm.out : sc.y;
     const PsKey key{ed_seq_, ps_gen_, W, b.B, base};
     if (!moved && ps_valid_ && key == ps_key_) return res;  // later fetches of the same batch under the same shift and mode reuse the rows
-    ps_n_ = out_spans(W, hz);
+    const int64_t* n = batch_spans(hz, W).dev.n;  // (the spans at the model's rate: the span table's own entry)
     ps_win_ = pitch_window(hz);
-    STN_HIP(hipMemcpyAsync(sc.n, ps_n_.data(), ps_n_.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     STN_HIP(hipMemcpyAsync(sc.win, ps_win_.data(), ps_win_.size() * sizeof(float), hipMemcpyHostToDevice, s_));
     if (formant) {
         fm_lagw_ = formant_lag_window(hz, f.p);
         STN_HIP(hipMemcpyAsync(fm.lagw, fm_lagw_.data(), fm_lagw_.size() * sizeof(double), hipMemcpyHostToDevice, s_));
     }
-    sync();  // (the uploads read ps_n_ and ps_win_, which the next batch or setting replaces; once per finished batch and setting, as cp_batch)
+    sync();  // (the uploads read ps_win_ and fm_lagw_, which the next batch or setting replaces; once per finished batch and setting)
     ps_table(ps_rs_, ps_a_, ps_b_);
-    ps_enqueue(b.wav, b.B, W, sc.n, ps_a_, ps_b_, p, sc.win, sc.delta, sc.score, sc.ys);
-    ps_resample(ps_rs_, sc.ys, b.B, p.Ws, W, sc.y);
-    if (formant) fm_enqueue(b.wav, sc.y, b.B, W, sc.n, f, sc.win, fm);
+    ps_enqueue(b.wav, b.B, W, n, ps_a_, ps_b_, p, sc.win, sc.delta, sc.score, sc.ys);
+    ps_resample(ps_rs_.t, sc.ys, b.B, p.Ws, W, sc.y);
+    if (formant) fm_enqueue(b.wav, sc.y, b.B, W, n, f, sc.win, fm);
     ps_key_ = key;
     ps_valid_ = true;
     return res;
@@ -119,17 +114,17 @@ void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, in
     const size_t nx = (size_t)rows * W;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.n, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
+    const int64_t* dn = op_spans(rows, W, nn).n;
     STN_HIP(hipMemcpyAsync(sc.win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, s_));
     if (y_out) ps_table(op_ps_rs_, a, b);
-    ps_enqueue(dx, rows, W, sc.n, a, b, p, sc.win, sc.delta, sc.score, sc.ys);
+    ps_enqueue(dx, rows, W, dn, a, b, p, sc.win, sc.delta, sc.score, sc.ys);
     if (y_out) {
-        ps_resample(op_ps_rs_, sc.ys, rows, p.Ws, W, sc.y);
+        ps_resample(op_ps_rs_.t, sc.ys, rows, p.Ws, W, sc.y);
         const float* res = sc.y;
         if (formant) {
             const FmScratch fm = fm_layout(static_cast<char*>(ar_.alloc(fm_layout(nullptr, rows, W, f).bytes)), rows, W, f);
             STN_HIP(hipMemcpyAsync(fm.lagw, lagw.data(), lagw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-            fm_enqueue(dx, sc.y, rows, W, sc.n, f, sc.win, fm);
+            fm_enqueue(dx, sc.y, rows, W, dn, f, sc.win, fm);
             res = fm.out;
         }
         STN_HIP(hipMemcpyAsync(y_out, res, nx * 4, hipMemcpyDeviceToHost, s_));
@@ -137,7 +132,7 @@ void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, in
     if (ys_out) STN_HIP(hipMemcpyAsync(ys_out, sc.ys, (size_t)rows * p.Ws * 4, hipMemcpyDeviceToHost, s_));
     if (delta_out) STN_HIP(hipMemcpyAsync(delta_out, sc.delta, (size_t)rows * p.M * sizeof(int), hipMemcpyDeviceToHost, s_));
     if (score_out) STN_HIP(hipMemcpyAsync(score_out, sc.score, (size_t)rows * p.M * 4, hipMemcpyDeviceToHost, s_));
-    sync();  // (nn, win and lagw are read by the copies above until here)
+    sync();  // (win and lagw are read by the copies above until here)
 }
 
 void Engine::op_time_stretch(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int* delta, float* score) {

@@ -75,20 +75,13 @@ void resample_design_pq(int P, int Q, int in_hz, int out_hz, ResampleTable& f) {
     }
 }
 
-void Engine::rs_prepare(ResampleTable& t, int in_hz, int out_hz) {
-    if (t.dev && t.in_hz == in_hz && t.out_hz == out_hz) return;
+void Engine::rs_prepare(RsTable& m, int in_hz, int out_hz) {
+    if (m.t.dev && m.t.in_hz == in_hz && m.t.out_hz == out_hz) return;
     ResampleTable n;
     const std::string why = resample_design(in_hz, out_hz, n);
     if (!why.empty()) throw std::invalid_argument(why);
-    STN_HIP(hipSetDevice(device_));
-    STN_HIP(hipMalloc(reinterpret_cast<void**>(&n.dev), n.taps.size() * sizeof(float)));
-    STN_HIP(hipMemcpyAsync(n.dev, n.taps.data(), n.taps.size() * sizeof(float), hipMemcpyHostToDevice, s_));
-    if (t.dev) { sync(); (void)hipFree(t.dev); }  // a fetch may still be reading the old table
-    t = std::move(n);
-}
-
-void Engine::rs_release() {
-    for (ResampleTable* t : {&rs_, &op_rs_, &ps_rs_, &op_ps_rs_}) if (t->dev) { (void)hipFree(t->dev); t->dev = nullptr; }
+    n.dev = m.dev[0].put(*this, n.taps);
+    m.t = std::move(n);
 }
 
 void Engine::set_output_rate(int hz) {
@@ -107,7 +100,7 @@ void Engine::set_output_rate(int hz) {
 
 const ResampleTable& Engine::rs_table() {
     rs_prepare(rs_, a_.sample_rate, out_hz_);  // (re)designed when the rate or the model's rate changed
-    return rs_;
+    return rs_.t;
 }
 
 int64_t Engine::out_len(int64_t W) const {
@@ -129,19 +122,19 @@ void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t ro
 void Engine::op_resample(int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm) {
     STN_HIP(hipSetDevice(device_));
     rs_prepare(op_rs_, in_hz, out_hz);
-    const int64_t W_out = resample_out_len(W, op_rs_.P, op_rs_.Q);
+    const int64_t W_out = resample_out_len(W, op_rs_.t.P, op_rs_.t.Q);
     ar_.reset();
     const size_t nx = (size_t)rows * W, ny = (size_t)rows * W_out;
     float* dx = static_cast<float*>(ar_.alloc(nx * 4));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
     if (y) {
         float* dy = static_cast<float*>(ar_.alloc(ny * 4));
-        resample_enqueue(op_rs_, dx, rows, W, ENC_F32, dy, W_out);
+        resample_enqueue(op_rs_.t, dx, rows, W, ENC_F32, dy, W_out);
         STN_HIP(hipMemcpyAsync(y, dy, ny * 4, hipMemcpyDeviceToHost, s_));
     }
     if (pcm) {
         int16_t* dp = static_cast<int16_t*>(ar_.alloc(ny * 2));
-        resample_enqueue(op_rs_, dx, rows, W, ENC_PCM16, dp, W_out);
+        resample_enqueue(op_rs_.t, dx, rows, W, ENC_PCM16, dp, W_out);
         STN_HIP(hipMemcpyAsync(pcm, dp, ny * 2, hipMemcpyDeviceToHost, s_));
     }
     sync();

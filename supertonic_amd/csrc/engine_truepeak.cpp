@@ -114,20 +114,19 @@ const char* Engine::op_true_peak(int hz, int rows, int W, const float* x, const 
     const size_t nx = (size_t)rows * W, nc = (size_t)rows * (size_t)lo_chunks(W), off = x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
     float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
     const TpScratch sc = tp_layout(static_cast<char*>(ar_.alloc(tp_layout(nullptr, rows, W, env != nullptr).bytes)), rows, W, env != nullptr);
-    int64_t* dn = static_cast<int64_t*>(ar_.alloc((size_t)rows * 8));
+    const int64_t* dn = op_spans(rows, W, nn).n;
     float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
     // what a launch fails to write reads back as the quiet NaN, not as an earlier call's value
     if (sc.env) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.env), 0x7FC00000, nx, s_));
     STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pk), 0x7FC00000, nc, s_));
     STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.tp_in), 0x7FC00000, (size_t)rows, s_));
     STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dn, nn.data(), nn.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
     if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
     tp_rows(dx, rows, W, dn, dg, sc.pk, sc.env, 1.0f, sc.tp_in, nullptr);
     if (tp) STN_HIP(hipMemcpyAsync(tp, sc.tp_in, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
     if (env) STN_HIP(hipMemcpyAsync(env, sc.env, nx * 4, hipMemcpyDeviceToHost, s_));
     if (pk) STN_HIP(hipMemcpyAsync(pk, sc.pk, nc * 4, hipMemcpyDeviceToHost, s_));
-    sync();  // (nn is read by the copy above until here)
+    sync();
     return truepeak_staging_form(dx, W, sc.env);
 }
 

@@ -508,7 +508,7 @@ struct ResampleTable {
     int in_hz = 0, out_hz = 0;
     int P = 0, Q = 0, T = 0, off = 0;  // T: taps per phase (a multiple of 8); off: taps ahead of the centre tap
     std::vector<float> taps;            // host copy, [P][T]
-    float* dev = nullptr;               // device copy (owned by whoever uploaded it)
+    float* dev = nullptr;               // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
 constexpr int RESAMPLE_MIN_HZ = 8000, RESAMPLE_MAX_HZ = 192000, RESAMPLE_MAX_P = 640;
 inline int64_t resample_out_len(int64_t W, int P, int Q) { return (W * P + Q - 1) / Q; }
@@ -575,7 +575,7 @@ struct LoudTable {
     int hz = 0, hop = 0;              // hop = (hz + 5) / 10 samples (100 ms)
     LoudCoef coef{};
     std::vector<double> mpow;         // host copy, [LO_SCAN][16]: M^(i+1) row-major, M = A^LO_CHUNK of the fp32 coefficients
-    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
+    double* dev = nullptr;            // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
 // fills t (not t.dev); empty string, or why hz is refused
 std::string loudness_design(int hz, LoudTable& t);
@@ -621,7 +621,7 @@ struct CompTable {
     int hz = 0;
     CompCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: D^(i+1) then E^(i+1), D = (1 - kR)^LO_CHUNK, E = (1 - kA)^LO_CHUNK
-    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
+    double* dev = nullptr;            // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
 // pass 1: s1[row][k] = y1 at the end of chunk k from zero.  pass 2: s1 = y1 at the chunk's start -> s2[row][k] = yL at its end from
 // zero.  pass 3: s1, s2 = the start values -> y (row stride W; may be x), gr (rows x W yL, or null), cmax[row][k] = max of yL over the
@@ -647,7 +647,7 @@ struct ExpTable {
     int64_t hold = 0;                 // Hs, the hold in samples
     ExpCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: (i + 1) LO_CHUNK delta then E^(i+1), E = (1 - kA)^LO_CHUNK
-    double* dev = nullptr;            // device copy (owned by whoever uploaded it)
+    double* dev = nullptr;            // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
 // pass 1: s1[row][k] = u at the end of chunk k from zero.  pass 2: s1 = u at the chunk's start -> s2[row][k] = yL at its end from zero.
 // pass 3: s1, s2 = the start values -> y (row stride W; may be x), open (rows x W yL, or null), cmin[row][k] = min of R - yL and

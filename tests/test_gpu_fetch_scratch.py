@@ -10,6 +10,7 @@ from supertonic_amd import binding
 from supertonic_amd.arch import tiny_arch
 from gpu_util import make_inputs
 import fetch_rows
+from fetch_take import assert_same as _assert_same, take as _take
 
 pytestmark = pytest.mark.gpu
 RATE, TARGET, CEIL, MS, SPEED = 16000, -12.0, -1.0, 5.0, 1.05
@@ -39,30 +40,6 @@ def _load(a, e, batch, rate=RATE):
     W = L * a.base_chunk_size * a.chunk_compress_factor
     spans = [min(W, int(np.float32(d / np.float32(SPEED)) * np.float32(a.sample_rate))) for d in durs]
     e.dbg_batch_set_wav(fetch_rows.rows(a.sample_rate, W, spans, rate, MS, 40 + seed))
-
-
-def _take(e, slot):
-    """every fetch path and every report of the finished batch, as name -> array"""
-    B = e.batch_dims()[0]
-    out = {}
-    out["f32"], out["dur"] = e.batch_fetch()
-    out["pcm16"] = e.batch_fetch_encoded("pcm16")[0]
-    join = ([B - B // 2, B // 2], [120, 60], [0.1, 0.05])
-    for scope in ("programme", "row"):
-        out["join_" + scope], out["plen_" + scope], out["pdur_" + scope] = e.batch_fetch_joined(*join, gain_scope=scope, cut=False)
-    e.fetch_pcm16_begin(slot)
-    out["slot"] = e.fetch_pcm16_end(slot)[0]
-    out["lufs"], out["peak"], out["gain"] = e.batch_loudness()
-    out["red"], out["limited"] = e.batch_limiter()
-    out["tp_in"], out["tp_out"], out["trim"] = e.batch_true_peak()
-    out["start"], out["end"] = e.batch_silence_edges()
-    return {k: np.asarray(v) for k, v in out.items()}
-
-
-def _assert_same(got, want, what):
-    assert got.keys() == want.keys()
-    for k in want:
-        assert got[k].shape == want[k].shape and got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), (what, k)
 
 
 @pytest.fixture(scope="module")
