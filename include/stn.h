@@ -542,6 +542,66 @@ int stn_op_loudness_range(stn_handle* h, int hz, int rows, int W, const float* x
  * against this function. */
 int stn_loudness_range_rule(int hop, int64_t nseg, const double* seg, double* m_max, double* s_max, double* lra, int32_t* n_st);
 
+/* ---- f0 ------------------------------------------------------------------------------------------------
+ * A report, not a setting: the fundamental-frequency track of each row and its statistics, by YIN (de Cheveigne and Kawahara 2002,
+ * steps 1 to 5), of the signal stn_batch_loudness measures: the rows at the output rate, behind pitch, filters, expander, de-esser
+ * and compressor, row b's first n_b samples, BEFORE the loudness gain.  Nothing is launched unless a report is asked for: no fetch,
+ * setting or captured graph changes.
+ * Parameters stn_f0_params: the search range [fmin_hz, fmax_hz], the threshold of step 4 and the level gate gate_db (dB re full
+ * scale, mean square).  Defaults 60, 500, 0.15, -60 (stn_f0_defaults).  Valid: 30 <= fmin < fmax <= 1000, 0 < threshold < 1,
+ * -120 <= gate_db <= 0 and tau_min >= 2; anything else is STN_ERR_INVALID, and stn_f0_error(hz, params) gives the message.
+ * For a row x of span n at rate hz (8000 to 192000), everything below in exact arithmetic:
+ *   1. analysis signal: k = max(1, hz div 16000), ha = hz / k (a real number below 32000), u[j] = (x[jk] + .. + x[jk+k-1]) / k for
+ *      j < n_a = n div k.  A box average is a poor low-pass (its first null is at ha, so the band above ha / 2 folds back attenuated
+ *      by 4 dB at worst); it is enough for a detector whose shortest lag is ha / fmax >= 8 samples, and it needs no design table.
+ *   2. geometry: hop Hh = floor(ha / 100 + 0.5), tau_max = ceil(ha / fmin), tau_min = floor(ha / fmax).  Frame t starts at s = t Hh
+ *      and reads u[s .. s + 2 tau_max).  Frames are the whole ones inside the span: F = 0 if n_a < 2 tau_max, else
+ *      (n_a - 2 tau_max) div Hh + 1.  The centre time of frame t is (s + tau_max) k / hz seconds.  Nothing behind the span is read.
+ *   3. difference function: d(tau) = sum_{j < tau_max} (u[s+j] - u[s+j+tau])^2 for tau = 0 .. tau_max; d'(0) = 1 and
+ *      d'(tau) = d(tau) tau / sum_{i=1..tau} d(i), 1 where that sum is 0.
+ *   4. decision: the frame is unvoiced if the mean of u^2 over its first tau_max samples is below 10^(gate_db / 10).  Otherwise take
+ *      the smallest tau in [tau_min, tau_max) with d'(tau) < threshold (none: unvoiced) and walk right while tau + 1 < tau_max and
+ *      d'(tau + 1) < d'(tau): that is tau^.
+ *   5. refinement: with a, b, c = d'(tau^ - 1), d'(tau^), d'(tau^ + 1), tau* = tau^ + clamp((a - c) / (2 (a - 2b + c)), -1, 1), and
+ *      tau* = tau^ when a - 2b + c <= 0.  f0 = ha / tau* (Hz), aperiodicity ap = b.  An unvoiced frame has f0 = 0 and ap = 1.
+ * Statistics stn_f0_stats over a row's voiced frames: median_hz the lower median (element (voiced - 1) div 2 of the ascending sort),
+ * mean_hz the geometric mean 2^(mean of log2 f0), min_hz and max_hz; all four are 0 when no frame is voiced.
+ * The device computes d in fp32 by the direct squared difference (the energy-minus-correlation form cancels in fp32) and the
+ * refinement in double on the fp32 d'; DESIGN.md section 27 derives the bound of f0 and ap against the definition.  A frame's result
+ * depends on its own 2 tau_max k samples, the rate and the parameters only (fixed-order sums, no atomics): not on W, the batch, the
+ * row's place in it or the frames beside it.  A row may hold at most 32768 frames (5 min 27 s): beyond that STN_ERR_INVALID with a
+ * message that names the row's count and the cap, before anything is uploaded or launched.  stn_group has no such report: ask the
+ * ranks' handles.  DESIGN.md section 27 has the decomposition, the LDS layout, the accuracy and the cost. */
+typedef struct stn_f0_params { float fmin_hz, fmax_hz, threshold, gate_db; } stn_f0_params;
+typedef struct stn_f0_stats { int32_t frames, voiced; float median_hz, mean_hz, min_hz, max_hz; } stn_f0_stats;
+/* host only, no device needed */
+void stn_f0_defaults(stn_f0_params* p);
+/* why (hz, params) is refused, or "" (params_or_null = NULL: the defaults); valid until the thread's next call */
+const char* stn_f0_error(int hz, const stn_f0_params* params_or_null);
+/* the geometry of a span of n samples at hz; each pointer may be NULL.  STN_ERR_INVALID for what stn_f0_error refuses or n < 0. */
+int stn_f0_plan(int hz, int64_t n, const stn_f0_params* params_or_null, int* k, int* hop, int* tau_min, int* tau_max, int64_t* frames);
+/* The definition above in double on the CPU: f0 and ap [cap] (either may be NULL), *frames the row's frame count.  STN_ERR_INVALID
+ * for what stn_f0_plan refuses, x NULL with n > 0, or frames > cap with an array given.  The kernels are tested against this function.
+ * stn_f0_rule_lags gives tau^ of each frame instead (0 for an unvoiced one). */
+int stn_f0_rule(int hz, int64_t n, const float* x, const stn_f0_params* params_or_null, int64_t cap, double* f0, double* ap, int64_t* frames);
+int stn_f0_rule_lags(int hz, int64_t n, const float* x, const stn_f0_params* params_or_null, int64_t cap, int32_t* lag, int64_t* frames);
+/* the statistics of a track f0[frames] (fp32, 0 = unvoiced) as defined above, the log2 sum in double in frame order */
+int stn_f0_stats_rule(const float* f0, int64_t frames, stn_f0_stats* out);
+/* frames a workgroup of the track kernel owns (the seam the tests put rows across) and the most frames a row may hold */
+int stn_f0_group(void);
+int64_t stn_f0_max_frames(void);
+/* the finished batch at the current output rate: *max_frames = the most frames any row holds (size f0 / ap with it).  STN_ERR_STATE
+ * without a finished batch. */
+int stn_batch_f0_frames(stn_handle* h, const stn_f0_params* params_or_null, int64_t* max_frames);
+/* the finished batch: f0 and ap [B][cap] floats (ap may be NULL, f0 may be NULL too: statistics only), stats [B] (may be NULL).
+ * Row b's frames are columns 0 .. stats[b].frames - 1; the columns behind them hold f0 = 0 and ap = 1.  STN_ERR_INVALID when a row
+ * holds more than cap frames (with an array given) or more than the report takes. */
+int stn_batch_f0(stn_handle* h, const stn_f0_params* params_or_null, int64_t cap, float* f0, float* ap_or_null, stn_f0_stats* stats);
+/* op-level, host operands: rows x W fp32 at hz, row r's first n[r] samples (n_or_null = NULL: all W); results as stn_batch_f0.
+ * 1 <= rows <= 65535. */
+int stn_op_f0(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n_or_null, const stn_f0_params* params_or_null, int64_t cap,
+              float* f0, float* ap_or_null, stn_f0_stats* stats);
+
 /* ---- silence trimming --------------------------------------------------------------------------------
  * With trimming on, every fetch path delivers each row without the silence in front of and behind its speech, found by level on the
  * GPU at fetch time.  It composes with the rate, the loudness, the encoding and the join; the latent geometry, the reported durations,

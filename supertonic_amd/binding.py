@@ -690,6 +690,9 @@ def load():
     L.stn_group_set_loudness.argtypes = [vp, ci, cf, cf]
     L.stn_batch_loudness_range.argtypes = [vp, vp, vp, vp, vp]
     L.stn_op_loudness_range.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, vp, vp, vp]
+    L.stn_batch_f0_frames.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
+    L.stn_batch_f0.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.stn_op_f0.argtypes = [vp, ci, ci, ci, _f32p, vp, vp, ctypes.c_int64, vp, vp, vp]
     L.stn_set_silence_trim.argtypes = [vp, ci, cf, cf, cf]
     L.stn_get_silence_trim.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(cf), ctypes.POINTER(cf), ctypes.POINTER(cf)]
     L.stn_batch_silence_edges.argtypes = [vp, vp, vp]
@@ -1059,6 +1062,96 @@ def loudness_range_rule(seg, hop):
     if rc != 0:
         raise StnError(rc, f"stn_loudness_range_rule: hop {hop} must be at least 1")
     return m.value, s.value, r.value, k.value
+
+
+class StnF0Params(ctypes.Structure):
+    _fields_ = [("fmin_hz", ctypes.c_float), ("fmax_hz", ctypes.c_float), ("threshold", ctypes.c_float), ("gate_db", ctypes.c_float)]
+
+
+F0_STATS = np.dtype([("frames", np.int32), ("voiced", np.int32), ("median_hz", np.float32), ("mean_hz", np.float32), ("min_hz", np.float32),
+                     ("max_hz", np.float32)])
+F0_DEFAULTS = {"fmin_hz": 60.0, "fmax_hz": 500.0, "threshold": 0.15, "gate_db": -60.0}
+
+
+def _f0_lib():
+    L = load()
+    ci, i64, vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+    L.stn_f0_error.argtypes = [ci, vp]
+    L.stn_f0_error.restype = ctypes.c_char_p
+    L.stn_f0_plan.argtypes = [ci, i64, vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(i64)]
+    L.stn_f0_rule.argtypes = [ci, i64, vp, vp, i64, vp, vp, ctypes.POINTER(i64)]
+    L.stn_f0_rule_lags.argtypes = [ci, i64, vp, vp, i64, vp, ctypes.POINTER(i64)]
+    L.stn_f0_stats_rule.argtypes = [vp, i64, vp]
+    L.stn_f0_group.restype = ci
+    L.stn_f0_max_frames.restype = i64
+    return L
+
+
+def f0_params(params=None):
+    """A pitch-report parameter argument -> StnF0Params: None is the defaults (60 Hz, 500 Hz, 0.15, -60 dB), a dict overrides some of
+    fmin_hz, fmax_hz, threshold, gate_db.  The limits are the ABI's (f0_error)."""
+    if isinstance(params, StnF0Params):
+        return params
+    p = dict(F0_DEFAULTS)
+    if params:
+        unknown = set(params) - set(p)
+        if unknown:
+            raise ValueError(f"f0 parameters: unknown field(s) {sorted(unknown)}")
+        p.update(params)
+    return StnF0Params(*(float(p[k]) for k in ("fmin_hz", "fmax_hz", "threshold", "gate_db")))
+
+
+def f0_error(hz, params=None):
+    """Why the pitch report refuses (hz, params) (host only; stn_f0_error), or "" for what it takes."""
+    p = f0_params(params)
+    return _f0_lib().stn_f0_error(int(hz), ctypes.addressof(p)).decode()
+
+
+def _f0_refuse(L, hz, p, what):
+    why = L.stn_f0_error(int(hz), ctypes.addressof(p)).decode()
+    raise StnError(-1, why or what)
+
+
+def f0_plan(hz, n, params=None):
+    """stn_f0_plan (host only): the pitch report's geometry of a span of n samples at hz -> dict k, hop, tau_min, tau_max, frames."""
+    L, p = _f0_lib(), f0_params(params)
+    k, hop, lo, hi, fr = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    if L.stn_f0_plan(int(hz), int(n), ctypes.addressof(p), k, hop, lo, hi, fr) != 0:
+        _f0_refuse(L, hz, p, f"stn_f0_plan: n = {n} must not be negative")
+    return {"k": k.value, "hop": hop.value, "tau_min": lo.value, "tau_max": hi.value, "frames": fr.value}
+
+
+def f0_rule(x, hz, params=None, lags=False):
+    """stn_f0_rule (host only): the contract of include/stn.h "f0" in double on one row x (fp32) at hz -> (f0 [frames], ap [frames])
+    float64; with lags=True also tau^ [frames] int32 (0 for an unvoiced frame)."""
+    L, p = _f0_lib(), f0_params(params)
+    xr = np.ascontiguousarray(x, np.float32).reshape(-1)
+    F = f0_plan(hz, xr.size, p)["frames"]
+    f0, ap, lag, fr = np.empty(F, np.float64), np.empty(F, np.float64), np.empty(F, np.int32), ctypes.c_int64()
+    xp = xr.ctypes.data if xr.size else None
+    if L.stn_f0_rule(int(hz), xr.size, xp, ctypes.addressof(p), F, f0.ctypes.data, ap.ctypes.data, fr) != 0 or fr.value != F:
+        _f0_refuse(L, hz, p, "stn_f0_rule failed")
+    if not lags:
+        return f0, ap
+    if L.stn_f0_rule_lags(int(hz), xr.size, xp, ctypes.addressof(p), F, lag.ctypes.data, fr) != 0:
+        _f0_refuse(L, hz, p, "stn_f0_rule_lags failed")
+    return f0, ap, lag
+
+
+def f0_stats_rule(f0):
+    """stn_f0_stats_rule (host only): the statistics of one fp32 track (0 = unvoiced) -> a numpy record of F0_STATS."""
+    L = _f0_lib()
+    t = np.ascontiguousarray(f0, np.float32).reshape(-1)
+    out = np.zeros(1, F0_STATS)
+    if L.stn_f0_stats_rule(t.ctypes.data if t.size else None, t.size, out.ctypes.data) != 0:
+        raise StnError(-1, "stn_f0_stats_rule: bad argument")
+    return out[0]
+
+
+def f0_group():
+    """frames a workgroup of the track kernel owns (stn_f0_group) and the most frames a row may hold (stn_f0_max_frames)"""
+    L = _f0_lib()
+    return L.stn_f0_group(), L.stn_f0_max_frames()
 
 
 LIMITER_MS = 5.0
@@ -1826,6 +1919,40 @@ class Engine:
         out, ptr = self._range_out(rows)
         self._ck(self._lib.stn_op_loudness_range(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, *ptr))
         return out
+
+    @staticmethod
+    def _f0_out(rows, cap):
+        f0, ap, st = np.empty((rows, cap), np.float32), np.empty((rows, cap), np.float32), np.zeros(rows, F0_STATS)
+        return f0, ap, st
+
+    def batch_f0(self, params=None):
+        """The pitch report of the finished batch at the output rate (include/stn.h "f0": YIN on the rows batch_loudness measures, before
+        the loudness gain) -> (f0 [B, Fmax], ap [B, Fmax], stats): f0 in Hz, 0 for an unvoiced frame, ap the aperiodicity d'(tau^);
+        stats a dict of [B] arrays frames, voiced, median_hz, mean_hz, min_hz, max_hz.  Row b's frames are columns 0 .. frames[b] - 1."""
+        p = f0_params(params)
+        cap = ctypes.c_int64()
+        self._ck(self._lib.stn_batch_f0_frames(self._h, ctypes.addressof(p), cap))
+        f0, ap, st = self._f0_out(self.batch_dims()[0], cap.value)
+        self._ck(self._lib.stn_batch_f0(self._h, ctypes.addressof(p), cap.value, f0.ctypes.data, ap.ctypes.data, st.ctypes.data))
+        return f0, ap, {k: st[k].copy() for k in F0_STATS.names}
+
+    def op_f0(self, x, hz, n=None, params=None, cap=None):
+        """rows x W fp32 at hz on the GPU -> (f0, ap, stats) as batch_f0 over row r's first n[r] samples (None: all W).  cap: the
+        columns of f0 / ap (None: the longest row's frame count)."""
+        p = f0_params(params)
+        x = np.ascontiguousarray(np.atleast_2d(x), np.float32)
+        rows, W = x.shape
+        nn = None if n is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int64), (rows,)))
+        if cap is None:
+            why = f0_error(hz, p)
+            if why:
+                raise StnError(-1, why)
+            cap = max((f0_plan(hz, max(0, int(v)), p)["frames"] for v in (nn if nn is not None else [W])), default=0)
+            cap = min(cap, f0_group()[1])  # (a longer row is the engine's to refuse, before it uploads anything)
+        f0, ap, st = self._f0_out(rows, int(cap))
+        self._ck(self._lib.stn_op_f0(self._h, int(hz), rows, W, x, None if nn is None else nn.ctypes.data, ctypes.addressof(p), int(cap),
+                                     f0.ctypes.data, ap.ctypes.data, st.ctypes.data))
+        return f0, ap, {k: st[k].copy() for k in F0_STATS.names}
 
     def op_loudness_ex(self, x, hz, n=None, on=False, target_lufs=-23.0, ceiling_dbfs=-1.0, x_misalign=0):
         """op_loudness with its scratch laid open (poisoned with the quiet NaN 0x7FC00000 first) -> dict: st_end, st_start [rows, Ks, 4]

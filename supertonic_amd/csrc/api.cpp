@@ -847,6 +847,19 @@ int stn_op_loudness_range(stn_handle* h, int hz, int rows, int W, const float* x
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness_range: bad argument (1 <= rows <= 65535, W >= 1, x)");
                  h->eng->op_loudness_range(hz, rows, W, x, n, m_max, s_max, lra, n_st); })
 }
+int stn_f0_group(void) { return stn::F0_GROUP; }
+int64_t stn_f0_max_frames(void) { return stn::F0_MAX_FRAMES; }
+int stn_batch_f0_frames(stn_handle* h, const stn_f0_params* p, int64_t* max_frames) {
+    STN_TRY(h, { need(max_frames != nullptr, "max_frames is null"); need_batch(h); *max_frames = h->eng->batch_f0_frames(p); })
+}
+int stn_batch_f0(stn_handle* h, const stn_f0_params* p, int64_t cap, float* f0, float* ap, stn_f0_stats* stats) {
+    STN_TRY(h, { need_batch(h); h->eng->batch_f0(p, cap, f0, ap, stats); })
+}
+int stn_op_f0(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_f0_params* p, int64_t cap, float* f0, float* ap,
+              stn_f0_stats* stats) {
+    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_f0: bad argument (1 <= rows <= 65535, W >= 1, x)");
+                 h->eng->op_f0(hz, rows, W, x, n, p, cap, f0, ap, stats); })
+}
 int stn_op_join(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, int loudness_on, float target_lufs,
                 float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
     STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && n && j && y, "stn_op_join: bad argument (1 <= rows <= 65535, W >= 1, x, n, j and y)");

@@ -31,7 +31,9 @@
 // of the audio before the shift is put back on the GPU),
 // --loudness-report (after each saved file one line "Loudness: integrated .. LUFS, range .. LU, max momentary .. LUFS, max short-term ..
 // LUFS (N short-term windows), peak .., gain ..": measured on the GPU before the loudness gain, three decimals, a long text as the
-// joined programme; one GPU only).
+// joined programme; one GPU only),
+// --pitch-report (after each saved file one line "Pitch: median .. Hz, min .. Hz, max .. Hz, voiced .. % (V of F frames)": the YIN
+// track of the same signal on the GPU, 60 to 500 Hz at a 10 ms hop, three decimals, a long text pooled over its chunks; one GPU only).
 // Voice styles: paths to voice-style JSON files; when the model assets are absent (synthetic weights) a
 // non-existing path is taken as a voice NAME and mapped to a deterministic synthetic style.
 #include <sys/stat.h>
@@ -76,7 +78,7 @@ int main(int argc, char* argv[]) {
     std::vector<std::string> text = {"This morning, I took a walk in the park, and the sound of the birds and the breeze was so "
                                      "pleasant that I stopped for a long time just to listen."};
     std::vector<std::string> lang = {"en"};
-    bool batch = false, peak_mode_given = false, loudness_report = false;
+    bool batch = false, peak_mode_given = false, loudness_report = false, pitch_report = false;
     std::string xp_spec, xp_preset = "speech";  // --expander and --expander-preset as given so far
     bool xp_spelled = false;
     EngineOptions opts;
@@ -177,6 +179,7 @@ int main(int argc, char* argv[]) {
             if (v.empty() || *end || v[0] == '-') { std::cerr << "Error: --dither-seed '" << v << "': an unsigned integer\n"; return 1; }
         }
         else if (a == "--loudness-report") loudness_report = true;  // one line of loudness figures after each saved file
+        else if (a == "--pitch-report") pitch_report = true;  // one line of pitch figures after each saved file
         else if (a == "--synthetic") opts.allow_synthetic = true;  // no model assets: run the default architecture on synthetic weights
     }
     if (opts.filters.size() > (size_t)STN_MAX_FILTERS) {
@@ -195,8 +198,8 @@ int main(int argc, char* argv[]) {
         std::cerr << "Error: --limiter needs --loudness (the limiter holds the ceiling of the loudness gain)\n";
         return 1;
     }
-    if (loudness_report && (opts.gpus > 1 || opts.devices.size() > 1)) {
-        std::cerr << "Error: --loudness-report needs the batch on one device (leave --gpus N / --devices out)\n";
+    if ((loudness_report || pitch_report) && (opts.gpus > 1 || opts.devices.size() > 1)) {
+        std::cerr << "Error: " << (loudness_report ? "--loudness-report" : "--pitch-report") << " needs the batch on one device (leave --gpus N / --devices out)\n";
         return 1;
     }
     if (voice_style.size() != text.size()) {
@@ -229,6 +232,8 @@ int main(int argc, char* argv[]) {
             const int sr = tts->getSampleRate();
             TextToSpeech::LoudnessReport rep;
             if (loudness_report) rep = tts->loudnessReport();
+            TextToSpeech::PitchReport pit;
+            if (pitch_report) pit = tts->pitchReport();
             const size_t eb = result.wav.empty() ? (size_t)stn_encoding_bytes(result.encoding) : 0;  // 0: the float waveform
             const size_t per = (eb ? result.encoded.size() / eb : result.wav.size()) / (size_t)bsz;
             for (int b = 0; b < bsz; ++b) {
@@ -247,6 +252,11 @@ int main(int argc, char* argv[]) {
                     std::cout << "Loudness: integrated " << db3(rep.integrated[b]) << " LUFS, range " << db3(rep.range[b]) << " LU, max momentary "
                               << db3(rep.max_momentary[b]) << " LUFS, max short-term " << db3(rep.max_short_term[b]) << " LUFS ("
                               << rep.n_short_term[b] << " short-term windows), peak " << db3(rep.peak[b]) << ", gain " << db3(rep.gain[b]) << "\n";
+                if (pitch_report && (size_t)b < pit.stats.size()) {
+                    const stn_f0_stats& s = pit.stats[(size_t)b];
+                    std::cout << "Pitch: median " << db3(s.median_hz) << " Hz, min " << db3(s.min_hz) << " Hz, max " << db3(s.max_hz) << " Hz, voiced "
+                              << db3(s.frames ? 100.0f * (float)s.voiced / (float)s.frames : 0.0f) << " % (" << s.voiced << " of " << s.frames << " frames)\n";
+                }
             }
         }
     } catch (const std::exception& e) {

@@ -489,6 +489,12 @@ class Engine {
     void batch_loudness_range(float* m_max, float* s_max, float* lra, int32_t* n_st);
     void batch_join_loudness_range(const stn_join* j, float* m_max, float* s_max, float* lra, int32_t* n_st);  // [G]
     void op_loudness_range(int hz, int rows, int W, const float* x, const int64_t* n, float* m_max, float* s_max, float* lra, int32_t* n_st);
+    // ---- pitch report (engine_f0.cpp; include/stn.h "f0"): the YIN track of the rows and spans batch_loudness
+    // measures and its per-row statistics.  Two launches (kernels_f0.hip) on out_source's rows; a report only: no fetch launches them.
+    // f0, ap: [rows][cap] host floats, stats [rows]; any may be null.  p null: the defaults.
+    int64_t batch_f0_frames(const stn_f0_params* p);  // the most frames a row of the finished batch holds
+    void batch_f0(const stn_f0_params* p, int64_t cap, float* f0, float* ap, stn_f0_stats* stats);
+    void op_f0(int hz, int rows, int W, const float* x, const int64_t* n, const stn_f0_params* p, int64_t cap, float* f0, float* ap, stn_f0_stats* stats);
 
     // ---- silence trimming (engine_edges.cpp; include/stn.h "silence trimming"): off is the default (every fetch
     // path is then exactly the one without it).  On, every fetch path finds row b's edges [start_b, end_b) by level at the output rate
@@ -997,6 +1003,12 @@ class Engine {
     DevBuf lr_buf_;                    // the report's results: [3][rows] floats, [rows] counts
     static int64_t lr_max_seg(const LoudTable& t, const int64_t* n, size_t rows);
     void lr_report(const LoudTable& t, int64_t rows, int64_t W, const int64_t* n, int64_t max_seg, float* m_max, float* s_max, float* lra, int32_t* n_st);
+    // ---- pitch report (engine_f0.cpp)
+    DevBuf f0_buf_;                    // the report's tracks and statistics: f0, ap [rows][max_frames], stats [rows]
+    // the two launches on rows x W fp32 on the device (x) with spans n (device; nh the same on the host, checked against the cap before
+    // this is called) and the read-back into [rows][cap] host arrays, no sync
+    void f0_report(int hz, const stn_f0_params& p, const float* x, int64_t rows, int64_t W, const int64_t* n, const int64_t* nh, int64_t cap, float* f0,
+                   float* ap, stn_f0_stats* stats);
     // ---- filter chain (engine_filter.cpp)
     std::vector<stn_filter> fl_set_;   // the chain in force
     uint64_t fl_gen_ = 0;              // bumped by every set_filters

@@ -243,6 +243,25 @@ TextToSpeech::LoudnessReport TextToSpeech::loudnessReport() {
     return r;
 }
 
+TextToSpeech::PitchReport TextToSpeech::pitchReport() {
+    if (grp_) throw std::runtime_error("the pitch report needs the batch on one device: a group has none (use one GPU)");
+    int B = 0, L = 0;
+    int64_t W = 0, cap = 0;
+    check(h_, stn_batch_dims(h_, &B, &L, &W));
+    check(h_, stn_batch_f0_frames(h_, nullptr, &cap));
+    PitchReport r;
+    r.stats.resize((size_t)B);
+    std::vector<float> f0((size_t)B * (size_t)cap);
+    check(h_, stn_batch_f0(h_, nullptr, cap, f0.data(), nullptr, r.stats.data()));
+    if (join_members_ > 0) {  // the joined text as call() joined it: one set of statistics over the chunks' frames
+        std::vector<float> pooled;
+        for (int b = 0; b < B; ++b) pooled.insert(pooled.end(), f0.begin() + (size_t)b * cap, f0.begin() + (size_t)b * cap + r.stats[(size_t)b].frames);
+        r.stats.assign(1, stn_f0_stats{});
+        if (stn_f0_stats_rule(pooled.data(), (int64_t)pooled.size(), &r.stats[0]) != STN_OK) throw std::runtime_error("pitch report: a joined text too long to pool");
+    }
+    return r;
+}
+
 void TextToSpeech::setEncoding(int enc) {
     if (stn_encoding_bytes(enc) == 0) throw std::runtime_error("unknown sample encoding " + std::to_string(enc));
     if (grp_ && stn_group_set_encoding(grp_, enc) != STN_OK) throw std::runtime_error(std::string("encoding: ") + stn_group_last_error(grp_));

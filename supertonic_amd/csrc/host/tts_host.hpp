@@ -169,6 +169,11 @@ class TextToSpeech {
     // audio is shorter than 400 ms / 3 s); range in LU; n_short_term the 3 s windows behind the range's gates.  Refused on a group.
     struct LoudnessReport { std::vector<float> integrated, peak, gain, max_momentary, max_short_term, range; std::vector<int32_t> n_short_term; };
     LoudnessReport loudnessReport();
+    // The pitch of what the last batch() / call() returned, tracked on the GPU by YIN on the signal loudnessReport measures (stn.h
+    // "f0"; the default parameters): per row after batch() (and after a call() that was one chunk), one entry for the joined text
+    // after call(), its statistics pooled on the host over the chunks' frames.  Hz; 0 where no frame is voiced.  Refused on a group.
+    struct PitchReport { std::vector<stn_f0_stats> stats; };
+    PitchReport pitchReport();
     int encoding() const { return enc_; }
     stn_handle* engine() const { return h_; }
     stn_group* group() const { return grp_; }  // null with one device

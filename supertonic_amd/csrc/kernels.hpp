@@ -601,6 +601,29 @@ constexpr int LR_MAX_SEG = 8192;      // 100 ms segments per row (13 min 39 s); 
 std::string loudness_range_check(int64_t max_seg);  // why rows of up to max_seg segments are refused (it names the cap), or ""
 void launch_loudness_range(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, const float* pa, const float* pb,
                            int64_t max_seg, float* res, int32_t* nst);
+// The pitch report (kernels_f0.hip; the geometry is host/f0.hpp, the host side engine_f0.cpp; include/stn.h "f0"; DESIGN.md section
+// 27): YIN on rows x W fp32 with row spans n[rows] (device).  The track kernel gives a workgroup F0_GROUP consecutive frames of one
+// row: it box-averages and stages their samples in LDS once, a lane owns one (frame, lag) of the difference function, and one wave per
+// frame scans, decides and refines.  The stats kernel is one workgroup per row over the row's track.  Fixed-order sums, no atomics.
+constexpr int F0_GROUP = 8;           // frames per workgroup of the track kernel
+constexpr int F0_WG = 256;            // its threads: four waves, each owning every fourth frame of the group
+constexpr int F0_STATS_WG = 1024;     // threads of the stats workgroup
+constexpr int F0_MAX_FRAMES = 32768;  // frames per row the stats kernel sorts in LDS (fp32 keys: 128 KiB of the 160 KiB); a power of two
+constexpr int F0_MAX_TAU = 1067;      // ceil(32000 / 30): the longest lag the parameter limits allow
+struct F0Launch {
+    int k = 1, hop = 0, tau_min = 0, tau_max = 0;  // host/f0.hpp's geometry
+    float threshold = 0.f;
+    double ha = 0.0, gate_ms = 0.0;
+};
+std::string f0_frames_check(int64_t row, int64_t frames);  // why a row of `frames` frames is refused (it names the count and the cap), or ""
+// f0, ap [rows][fstride]: row r's frames in columns 0 .. F_r - 1 (F_r from n[r] by the contract), f0 = 0 and ap = 1 behind them up to
+// max_frames (the longest row's count, <= fstride); nothing is read behind n[r]
+void launch_f0_track(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, const F0Launch& g, int64_t max_frames, int64_t fstride,
+                     float* f0, float* ap);
+// stats [rows] (stn_f0_stats: frames, voiced, median, geometric mean, min, max) of the tracks f0 [rows][fstride]
+void launch_f0_stats(hipStream_t s, const float* f0, int64_t rows, int64_t W, const int64_t* n, const F0Launch& g, int64_t max_frames, int64_t fstride,
+                     void* stats);
+
 // the powers M^1 .. M^LO_SCAN ([LO_SCAN][16], double) of M = A^LO_CHUNK for the two-section cascade with the fp32 coefficients c
 // (b0 b1 b2 a1 a2 twice): what the scan reads, for the K-weighting and for a section pass of the filter chain alike (host only)
 void cascade_powers(const LoudCoef& c, std::vector<double>& mpow);

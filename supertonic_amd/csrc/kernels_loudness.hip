@@ -16,6 +16,7 @@
 // Every hand-off between workgroups is a launch boundary, and every sum runs in an order fixed by the sample positions within the
 // row: a row's results depend on its first n_b samples and the rate only, not on W, the batch or the row's place in it.
 #include "kernels_chunk.hpp"
+#include "kernels_sort.hpp"
 #include "host/loudness_range.hpp"
 
 #include <math.h>
@@ -273,15 +274,7 @@ __global__ void __launch_bounds__(LO_GATE) loudness_range_kernel(const int64_t* 
         else key[j] = INFINITY;
     }
     kc = lo_block_sum(kc, red);  // (its barriers also order the writes above before the sort's reads)
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += LO_GATE) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
-                const double a = key[i], b = key[p];
-                if ((a > b) == ((i & k) == 0)) { key[i] = b; key[p] = a; }
-            }
-            __syncthreads();
-        }
+    lds_bitonic_sort<LO_GATE>(key, P);
     if (tid == 0) {
         const int64_t n = (int64_t)kc;
         res[row] = zm < 0.0 ? -INFINITY : (float)lr_level(zm);

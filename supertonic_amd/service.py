@@ -27,6 +27,10 @@ AVAILABLE_LANGS = host.AVAILABLE_LANGS
 # response header -> its entry of TextToSpeech.loudness_report (a request with "loudness_report": true; three decimals, -inf spelled so)
 REPORT_HEADERS = {"X-Loudness-Integrated": "integrated", "X-Loudness-Range": "range", "X-Loudness-Max-Momentary": "max_momentary",
                   "X-Loudness-Max-Short-Term": "max_short_term"}
+# response header -> its entry of TextToSpeech.pitch_report (a request with "pitch_report": true; Hz, three decimals); X-Pitch-Voiced,
+# the share voiced / frames, goes with them
+PITCH_HEADERS = {"X-Pitch-Median-Hz": "median_hz", "X-Pitch-Min-Hz": "min_hz", "X-Pitch-Max-Hz": "max_hz"}
+PITCH_FIELDS = ("frames", "voiced", "median_hz", "mean_hz", "min_hz", "max_hz")
 
 
 # what two requests must share to run as one engine batch (the settings cover a whole batch; every row keeps its own gain)
@@ -87,13 +91,14 @@ def batch_key(model_rate, total_step, speed, sample_rate=None, loudness=None, pe
 
 
 class _Job:
-    __slots__ = ("texts", "lang", "style", "key", "silence", "done", "waves", "durs", "error", "want_report", "report")
+    __slots__ = ("texts", "lang", "style", "key", "silence", "done", "waves", "durs", "error", "want_report", "report", "want_pitch", "pitch")
 
-    def __init__(self, texts, lang, style, key, silence=None, want_report=False):
+    def __init__(self, texts, lang, style, key, silence=None, want_report=False, want_pitch=False):
         self.texts, self.lang, self.style, self.key, self.silence = texts, lang, style, key, silence
         self.done = threading.Event()
         self.waves = self.durs = self.error = None
         self.want_report, self.report = bool(want_report), None
+        self.want_pitch, self.pitch = bool(want_pitch), None
 
 
 class DynamicBatcher:
@@ -110,16 +115,17 @@ class DynamicBatcher:
         self._t = threading.Thread(target=self._run, name="stn-batcher", daemon=True)
         self._t.start()
 
-    def submit(self, texts, lang, style, *request, silence_duration=None, loudness_report=False, **request_kw):
+    def submit(self, texts, lang, style, *request, silence_duration=None, loudness_report=False, pitch_report=False, **request_kw):
         """Blocks until the job's utterances are synthesized; returns (list of waves, durations [n]).  request: total_step, speed and the
         rest of batch_key's arguments.  silence_duration (seconds, not None): the job's utterances are the chunks of one text and come
         back as ONE wave, joined with that much silence on the GPU (one programme per job of the batch's joined fetch, each job its own
         gap), with its duration.  loudness_report (no part of the key: it changes no audio): a third result, the job's entry of
         TextToSpeech.loudness_report for its joined wave as a dict of floats, or None when the synthesizer has no such report or the
-        job is not joined on the GPU."""
+        job is not joined on the GPU.  pitch_report (no part of the key either): one more result behind those, the job's entry of
+        TextToSpeech.pitch_report (pooled over its chunks) as a dict of floats, or None under the same conditions."""
         own = getattr(getattr(self.tts, "settings", None), "pitch_mode", None)
         key = batch_key(self.tts.sample_rate, *request, own_pitch_mode=own, **request_kw)
-        job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration), loudness_report)
+        job = _Job(list(texts), lang, style, key, None if silence_duration is None else float(silence_duration), loudness_report, pitch_report)
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -128,7 +134,7 @@ class DynamicBatcher:
         job.done.wait()
         if job.error is not None:
             raise job.error
-        return (job.waves, job.durs, job.report) if loudness_report else (job.waves, job.durs)
+        return (job.waves, job.durs) + ((job.report,) if loudness_report else ()) + ((job.pitch,) if pitch_report else ())
 
     def close(self):
         with self._cv:
@@ -181,7 +187,8 @@ class DynamicBatcher:
                     # one programme per job, joined by the fetch on the GPU; the report, when a job asked for one, is about the batch
                     # the engine then holds, so nothing else may run on the synthesizer in between
                     report = getattr(self.tts, "loudness_report", None) if any(j.want_report for j in jobs) else None
-                    with getattr(self.tts, "exclusive", contextlib.nullcontext)() if report is not None else contextlib.nullcontext():
+                    pitch = getattr(self.tts, "pitch_report", None) if any(j.want_pitch for j in jobs) else None
+                    with getattr(self.tts, "exclusive", contextlib.nullcontext)() if report or pitch else contextlib.nullcontext():
                         waves, durs = joined(texts, langs, Style(ttl, dp), key.total_step, key.speed, rows=[len(j.texts) for j in jobs],
                                              silence_duration=[j.silence for j in jobs], loudness_scope=key.loudness_scope, trim_chunks=key.trim_chunks, **extra)
                         if report is not None:
@@ -190,6 +197,11 @@ class DynamicBatcher:
                             for g, j in enumerate(jobs):
                                 if j.want_report:
                                     j.report = {k: float(v[g]) for k, v in rep.items()}
+                        if pitch is not None:
+                            rep = pitch(rows=[len(j.texts) for j in jobs], **key.settings.kwargs())
+                            for g, j in enumerate(jobs):
+                                if j.want_pitch:
+                                    j.pitch = {k: float(v[g]) for k, v in rep.items()}
                     self.batches.append(len(texts))
                     for g, j in enumerate(jobs):
                         j.waves, j.durs = [waves[g]], np.asarray(durs[g:g + 1], np.float32)
@@ -280,6 +292,10 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
         loudness_report: Optional[bool] = Field(None, description="True: a single-utterance response carries the headers X-Loudness-Integrated, "
                                                                   "X-Loudness-Range, X-Loudness-Max-Momentary and X-Loudness-Max-Short-Term "
                                                                   "(LUFS / LU, measured on the GPU before the loudness gain).  It changes no audio.")
+        pitch_report: Optional[bool] = Field(None, description="True: a single-utterance response carries the headers X-Pitch-Median-Hz, "
+                                                               "X-Pitch-Min-Hz, X-Pitch-Max-Hz (the YIN track of the audio on the GPU, 60 to "
+                                                               "500 Hz at a 10 ms hop; 0 where nothing is voiced) and X-Pitch-Voiced (the share "
+                                                               "of voiced frames).  It changes no audio.")
         trim_silence: Optional[float] = Field(None, ge=1.0, le=120.0, description="Trim leading and trailing silence by level (on the GPU): frames "
                                                                                  "more than this many dB below the loudest 10 ms frame; null: off.")
         trim_keep_ms: float = Field(20.0, ge=0.0, le=1000.0, description="Milliseconds kept in front of and behind the speech when trimming.")
@@ -432,9 +448,10 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             extra["encoding"] = enc
         # the report of a single-utterance response (a synthesizer without loudness_report yields no headers)
         reporter = getattr(tts, "loudness_report", None) if req.loudness_report and len(texts) == 1 else None
-        report = None
+        pitcher = getattr(tts, "pitch_report", None) if req.pitch_report and len(texts) == 1 else None  # (likewise)
+        report = pitched = None
         if req.batch:
-            with getattr(tts, "exclusive", contextlib.nullcontext)() if reporter else contextlib.nullcontext():
+            with getattr(tts, "exclusive", contextlib.nullcontext)() if reporter or pitcher else contextlib.nullcontext():
                 if ts is not None:  # every wave is its trimmed segment, cut at the length the GPU found
                     if req.max_pause_ms is not None:
                         extra["max_pause"] = req.max_pause_ms
@@ -446,14 +463,20 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
                 if reporter:  # (the settings of the call above, without what is no output setting)
                     kw = {k: v for k, v in extra.items() if k != "encoding"}
                     report = {k: float(v[0]) for k, v in reporter(**(kw if ts is None else dict(kw, trim_silence=ts))).items()}
+                if pitcher:
+                    kw = {k: v for k, v in extra.items() if k != "encoding"}
+                    pitched = {k: float(v[0]) for k, v in pitcher(**(kw if ts is None else dict(kw, trim_silence=ts))).items() if k in PITCH_FIELDS}
         else:
             pieces = host.chunk_text(texts[0], 120 if langs[0] == "ko" else 300)
             more = {"loudness_report": True} if reporter else {}  # (absent otherwise: the call is today's)
+            if pitcher:
+                more["pitch_report"] = True
             waves, durs, *rep = batcher.submit(pieces, langs[0], style, req.total_step, req.speed, req.sample_rate, req.loudness, req.peak_ceiling,
                                                enc, silence_duration=req.silence_duration, loudness_scope=req.loudness_scope,
                                                trim_chunks=req.trim_chunks, trim_silence=ts, limiter_ms=req.limiter_ms, peak_mode=req.peak_mode,
                                                max_pause_ms=req.max_pause_ms, filters=chain, expander=xpd, deesser=dees, compressor=comp,
                                                dither=None if dith is None else (dith or "off"), dither_seed=dith[1] if dith else None, pitch=pitch, pitch_mode=extra.get("pitch_mode"), **more)
+            pitched = rep.pop() if pitcher else None
             report = rep[0] if rep else None
             wav, d = waves[0], float(durs[0])  # the chunks joined by the batch's fetch (join_chunks' result)
             chunks = [wav if ts is not None else wav[: int(sr * d)]]  # (trimmed: the joined wave is already its own length)
@@ -464,6 +487,9 @@ def create_app(tts, max_batch=128, max_wait_ms=3.0, style_loader=None):
             headers["X-Pitch-Cents"] = f"{binding.pitch_cents(in_force):.3f}"  # the realised shift (a / b), 0.000 when off
             if report:
                 headers.update({h: f"{report[k]:.3f}" for h, k in REPORT_HEADERS.items()})
+            if pitched:
+                headers.update({h: f"{pitched[k]:.3f}" for h, k in PITCH_HEADERS.items()})
+                headers["X-Pitch-Voiced"] = f"{pitched['voiced'] / pitched['frames'] if pitched['frames'] else 0.0:.3f}"
             return Response(host.wav_bytes(chunks[0], sr, enc), media_type="audio/wav", headers=headers)
         zbuf = io.BytesIO()
         with zipfile.ZipFile(zbuf, "w", compression=zipfile.ZIP_DEFLATED) as zf:

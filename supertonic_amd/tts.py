@@ -224,6 +224,29 @@ class TextToSpeech:
                 m, s, lra, n_st = self.engine.batch_join_loudness_range(*join)
         return {"integrated": lufs, "peak": peak, "gain": gain, "max_momentary": m, "max_short_term": s, "range": lra, "n_short_term": n_st}
 
+    def pitch_report(self, rows=None, params=None, **out):
+        """The pitch of the batch the engine holds (after batch, solo_batch, joined_batch or __call__; inside exclusive(), like
+        loudness_report), tracked on the GPU by YIN on the signal loudness_report measures (Engine.batch_f0) -> dict of arrays: frames,
+        voiced, median_hz, mean_hz (geometric), min_hz, max_hz (0 where nothing is voiced), and f0 / ap, the tracks [B, Fmax] (f0 in
+        Hz at a 10 ms hop, 0 = unvoiced; row b's frames are its first frames[b]).  rows None: one entry per row of the batch.  rows (as
+        joined_batch's): one entry per joined wave, the statistics pooled on the host over its member rows' frames (the silences
+        between them hold no voiced frame), and no tracks.  params: binding.f0_params' argument (None: 60 to 500 Hz, threshold 0.15,
+        gate -60 dB).  out: the OutputSettings keywords the audio was asked with, when they were a call's and not the instance's."""
+        call = OutputSettings.parse(**out)
+        with self._lock, call.applied(self.engine, self.settings):
+            f0, ap, st = self.engine.batch_f0(params)
+        if rows is None:
+            return {**st, "f0": f0, "ap": ap}
+        rows = [int(r) for r in rows]
+        if any(r < 1 for r in rows) or sum(rows) != f0.shape[0]:
+            raise ValueError(f"rows {rows}: positive counts that add up to the batch's {f0.shape[0]} rows")
+        pooled, b = [], 0
+        for r in rows:
+            track = np.concatenate([f0[i, : st["frames"][i]] for i in range(b, b + r)])
+            pooled.append(binding.f0_stats_rule(track))
+            b += r
+        return {k: np.array([p[k] for p in pooled]) for k in binding.F0_STATS.names}
+
 
 def _trim_setting(v):
     """A trim_silence keyword normalized: (top_db, keep_ms, fade_ms), or None for off.  (The tests of the ranges read this and the next.)"""
