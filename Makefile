@@ -8,7 +8,7 @@ CSRC    := supertonic_amd/csrc
 # device pass (the host pass prints "not a recognized feature", which is expected).
 NOPKF32 := -Xclang -target-feature -Xclang -packed-fp32-ops
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude $(NOPKF32) $(EXTRA)
-KERNELS := $(CSRC)/kernels_gemm.hip $(CSRC)/kernels_dwconv_ln.hip $(CSRC)/kernels_fold.hip $(CSRC)/kernels_layout.hip $(CSRC)/kernels_output.hip $(CSRC)/kernels_attn.hip $(CSRC)/kernels_xattn_hs.hip $(CSRC)/kernels_ffn.hip $(CSRC)/kernels_resample.hip $(CSRC)/kernels_pitch.hip $(CSRC)/kernels_formant.hip $(CSRC)/kernels_loudness.hip $(CSRC)/kernels_f0.hip $(CSRC)/kernels_filter.hip $(CSRC)/kernels_compressor.hip $(CSRC)/kernels_deesser.hip $(CSRC)/kernels_expander.hip $(CSRC)/kernels_edges.hip $(CSRC)/kernels_limiter.hip $(CSRC)/kernels_truepeak.hip
+KERNELS := $(CSRC)/kernels_gemm.hip $(CSRC)/kernels_dwconv_ln.hip $(CSRC)/kernels_fold.hip $(CSRC)/kernels_layout.hip $(CSRC)/kernels_output.hip $(CSRC)/kernels_attn.hip $(CSRC)/kernels_xattn_hs.hip $(CSRC)/kernels_ffn.hip $(CSRC)/kernels_resample.hip $(CSRC)/kernels_pitch.hip $(CSRC)/kernels_formant.hip $(CSRC)/kernels_loudness.hip $(CSRC)/kernels_f0.hip $(CSRC)/kernels_filter.hip $(CSRC)/kernels_dynamics.hip $(CSRC)/kernels_edges.hip $(CSRC)/kernels_limiter.hip $(CSRC)/kernels_truepeak.hip
 HOSTSRC := $(CSRC)/engine.cpp $(CSRC)/engine_batch.cpp $(CSRC)/engine_ops.cpp $(CSRC)/engine_resample.cpp $(CSRC)/engine_pitch.cpp $(CSRC)/engine_formant.cpp $(CSRC)/engine_loudness.cpp $(CSRC)/engine_f0.cpp $(CSRC)/engine_filter.cpp $(CSRC)/engine_compressor.cpp $(CSRC)/engine_deesser.cpp $(CSRC)/engine_expander.cpp $(CSRC)/engine_edges.cpp $(CSRC)/engine_limiter.cpp $(CSRC)/engine_truepeak.cpp $(CSRC)/api.cpp $(CSRC)/group.cpp $(wildcard $(CSRC)/host/*.cpp)
 OBJS    := $(patsubst %.hip,build/%.o,$(KERNELS)) $(patsubst %.cpp,build/%.o,$(HOSTSRC))
 HDRS    := $(wildcard $(CSRC)/*.hpp $(CSRC)/*.inc $(CSRC)/host/*.hpp include/*.h)

@@ -592,54 +592,45 @@ class Engine {
 
     // ---- compressor (engine_compressor.cpp; include/stn.h "compressor"): off is the default (every fetch path is
     // then exactly the one without it).  On, out_source() delivers the rows at the output rate compressed in place in the fetch scratch,
-    // behind the filter chain (kernels_compressor.hip), and everything behind it runs on those.
+    // behind the filter chain (kernels_dynamics.hip), and everything behind it runs on those.
     void set_compressor(bool on, const stn_compressor* c);
     bool compressor_on() const { return cp_.on; }
     const stn_compressor& compressor() const { return cp_.set; }
     void batch_compressor(float* max_reduction_db);
-    // the op-level probe: gr [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
-    struct CpProbe {
+    // what the op-level probes of the three dynamics stages share: the four state arrays [rows][Ks] (host, or null), the poisoned
+    // guards, the staging form
+    struct DynProbe {
         int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
-        float *gr = nullptr, *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
+        float *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
         bool guard_ok = false;   // out
         const char* form = "";   // out
     };
+    // the op-level probe: gr [rows][W] (host, or null)
+    struct CpProbe : DynProbe { float* gr = nullptr; };
     // rows x W fp32 (host) at hz through the compressor c -> y (host)
     void op_compressor(int hz, int rows, int W, const float* x, const stn_compressor& c, float* y, CpProbe* probe);
 
     // ---- de-esser (engine_deesser.cpp; include/stn.h "de-esser"): off is the default (every fetch path is then
     // exactly the one without it).  On, out_source() delivers the rows at the output rate de-essed in place in the fetch scratch, behind
-    // the filter chain and in front of the compressor (kernels_deesser.hip), and everything behind it runs on those.
+    // the filter chain and in front of the compressor (kernels_dynamics.hip), and everything behind it runs on those.
     void set_deesser(bool on, const stn_deesser* c);
     bool deesser_on() const { return ds_.on; }
     const stn_deesser& deesser() const { return ds_.set; }
     void batch_deesser(float* max_reduction_db);
-    // the op-level probe: band and gr [rows][W], the band's states [rows][Ks][4] and the detector's four arrays [rows][Ks] (host, or
-    // null), the poisoned guards, the staging form
-    struct DsProbe {
-        int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
-        float *band = nullptr, *gr = nullptr, *st_end = nullptr, *st_start = nullptr;
-        float *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
-        bool guard_ok = false;   // out
-        const char* form = "";   // out
-    };
+    // the op-level probe: band and gr [rows][W] and the band's states [rows][Ks][4] (host, or null)
+    struct DsProbe : DynProbe { float *band = nullptr, *gr = nullptr, *st_end = nullptr, *st_start = nullptr; };
     // rows x W fp32 (host) at hz through the de-esser c -> y (host)
     void op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe);
 
     // ---- expander (engine_expander.cpp; include/stn.h "expander"): off is the default (every fetch path is then
     // exactly the one without it).  On, out_source() delivers the rows at the output rate expanded in place in the fetch scratch, behind
-    // the filter chain and in front of the de-esser (kernels_expander.hip), and everything behind it runs on those.
+    // the filter chain and in front of the de-esser (kernels_dynamics.hip), and everything behind it runs on those.
     void set_expander(bool on, const stn_expander* c);
     bool expander_on() const { return xp_.on; }
     const stn_expander& expander() const { return xp_.set; }
     void batch_expander(float* min_attenuation_db, int64_t* closed_samples);
-    // the op-level probe: open [rows][W], the four state arrays [rows][Ks] (host, or null), the poisoned guards, the staging form
-    struct XpProbe {
-        int x_misalign = 0, in_place = 0;  // in_place: y is written over x on the device
-        float *open = nullptr, *s1_end = nullptr, *s1_start = nullptr, *s2_end = nullptr, *s2_start = nullptr;
-        bool guard_ok = false;   // out
-        const char* form = "";   // out
-    };
+    // the op-level probe: open [rows][W] (host, or null)
+    struct XpProbe : DynProbe { float* open = nullptr; };
     // rows x W fp32 (host) at hz through the expander c -> y (host)
     void op_expander(int hz, int rows, int W, const float* x, const stn_expander& c, float* y, XpProbe* probe);
 
@@ -1053,13 +1044,24 @@ class Engine {
     // dyn_batch: the fetch hook around `run`, the stage's launches on the carved scratch and the batch's spans (table, scratch, launches, key).
     // dyn_report: a report's preamble around `read`, which is given the scratch to read the rows' results from, or null while the stage
     // is off (zeros).  dyn_op: the op entry around `run`; taps: the per-sample outputs (host, or null), in the order `run` is handed
-    // their device rows.  read_rows: one result per row of the batch device -> host (dev null: zeros; host null: nothing)
+    // their device rows.  read_rows: one result per row of the batch device -> host (dev null: zeros; host null: nothing).
+    // dyn_enqueue: the six launches every stage ends in, with their spans, error checks and probe read-outs, around the stage's launches
+    // `chunks` and `reduce`; DynSeq is what a stage says of itself for them.
+    struct DynSeq {
+        const char* unit;                        // the spans are out.<unit>_chunks1, _scan1, _chunks2, _scan2, _write and _<rows>
+        const char* rows;                        // "rowmax" or "rows"
+        double flop[3], state[3];                // the three chunk passes: flops per sample, bytes per chunk beside the samples
+        double rows_flop, rows_chunk, rows_row;  // the row reduction: flops and bytes per chunk, bytes per row
+    };
+    template <class Tab, class Sc, class Chunks, class Reduce>
+    void dyn_enqueue(const DynSeq& d, const Tab& t, int64_t rows, int64_t W, const Sc& sc, int taps, const DynProbe* probe, StageSpan* open, Chunks chunks,
+                     Reduce reduce);
     template <class Made, class Set, class Build> void dyn_prepare(Made& m, int hz, const Set& c, Build build);
     template <class St, class Build, class Layout, class Run> void dyn_batch(St& st, Stage stage, int64_t Wo, Build build, Layout layout, Run run);
     template <class St, class Layout, class Read> void dyn_report(St& st, Stage stage, Layout layout, bool wanted, Read read);
     template <class St, class Set, class Probe, class Build, class Layout, class Run>
     void dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& c, float* y, Probe* probe, Build build, Layout layout,
-                std::initializer_list<float*> taps, const char* (*form)(const float*, const float*, int64_t), Run run);
+                std::initializer_list<float*> taps, Run run);
     template <class T> void read_rows(T* host, const T* dev);
     // shapes_rows: a stage behind the rate is on (the set enqueue_output's store-from-scratch branch asks for).  out_in_scratch:
     // out_source() returns the fp32 fetch scratch (row stride Wo); otherwise, pitch or nothing, wav_rows(): b.wav or the shifted rows

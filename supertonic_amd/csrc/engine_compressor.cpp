@@ -1,5 +1,5 @@
 // engine_compressor.cpp — the fetch-time dynamic range compressor of a handle: its limits, coefficients and static curve (host only),
-// the scan tables and the scratch, the sequence of launches and the op-level entry.  The kernels are kernels_compressor.hip; the hook
+// the scan tables and the scratch, the sequence of launches and the op-level entry.  The kernels are kernels_dynamics.hip; the hook
 // is Engine::out_source (engine_batch.cpp); DESIGN.md section 20 has the contract.
 #include "engine_internal.hpp"
 
@@ -76,32 +76,11 @@ Engine::CpScratch Engine::cp_layout(char* base, int64_t rows, int64_t W) {
 }
 
 void Engine::cp_enqueue(const CompTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const CpScratch& sc, float* y, float* gr, CpProbe* probe) {
-    const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
-    const size_t st_bytes = (size_t)rows * (size_t)lo_chunks(W) * 4;
-    auto out = [&](float* dst, const float* src) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, st_bytes, hipMemcpyDeviceToHost, s_)); };
     // per sample: log10 (about 20), the gain computer (8), the detector (3), the smoothing (2), the gain 10^x and its product (about 22)
-    StageSpan span(*this, "out", "compressor_chunks1", 31.0 * samples, samples * 4 + chunks * 4);
-    launch_compressor_chunks(s_, 1, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_end, sc.s1);
-    span.next("compressor_scan1", chunks * 11 * 2, chunks * 8);
-    launch_compressor_scan(s_, 1, rows, W, t, sc.s1);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_start, sc.s1);
-    span.next("compressor_chunks2", 33.0 * samples, samples * 4 + chunks * 8);
-    launch_compressor_chunks(s_, 2, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_end, sc.s2);
-    span.next("compressor_scan2", chunks * 11 * 2, chunks * 8);
-    launch_compressor_scan(s_, 2, rows, W, t, sc.s2);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_start, sc.s2);
-    span.next("compressor_write", 56.0 * samples, samples * (gr ? 12 : 8) + chunks * 12);
-    launch_compressor_chunks(s_, 3, x, rows, W, n, t, sc.s1, sc.s2, y, gr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    span.next("compressor_rowmax", chunks, chunks * 4 + (double)rows * 4);
-    launch_compressor_rowmax(s_, rows, W, sc.cmax, sc.rmax);
-    STN_HIP(hipGetLastError());
+    static constexpr DynSeq seq{"compressor", "rowmax", {31.0, 33.0, 56.0}, {4, 8, 12}, 1, 4, 4};
+    dyn_enqueue(seq, t, rows, W, sc, gr ? 1 : 0, probe, nullptr,
+                [&](int pass) { launch_compressor_chunks(s_, pass, x, rows, W, n, t, sc.s1, sc.s2, y, gr, sc.cmax); },
+                [&] { launch_compressor_rowmax(s_, rows, W, sc.cmax, sc.rmax); });
 }
 
 void Engine::cp_batch(const float* x, int64_t Wo, float* y) {
@@ -113,7 +92,7 @@ void Engine::batch_compressor(float* max_reduction_db) {
 }
 
 void Engine::op_compressor(int hz, int rows, int W, const float* x, const stn_compressor& c, float* y, CpProbe* probe) {
-    dyn_op(cp_, hz, rows, W, x, c, y, probe, compressor_table, cp_layout, {probe ? probe->gr : nullptr}, compressor_staging_form,
+    dyn_op(cp_, hz, rows, W, x, c, y, probe, compressor_table, cp_layout, {probe ? probe->gr : nullptr},
            [&](const CompTable& t, const CpScratch& sc, RowSpans n, const float* dx, float* dy, float* const* tap) { cp_enqueue(t, dx, rows, W, n.n, sc, dy, tap[0], probe); });
 }
 

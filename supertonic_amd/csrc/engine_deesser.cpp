@@ -1,6 +1,6 @@
 // engine_deesser.cpp — the fetch-time de-esser of a handle: its limits, band and coefficients (host only), the tables and the scratch,
-// the sequence of eight launches and the op-level entry.  The chunk passes are kernels_deesser.hip, the band's first two launches the
-// loudness measurement's (kernels_loudness.hip), the detector's scans and the row maxima the compressor's (kernels_compressor.hip); the
+// the sequence of eight launches and the op-level entry.  The band's first two launches are the loudness measurement's
+// (kernels_loudness.hip), the six behind them the shared sequence (Engine::dyn_enqueue) on kernels_dynamics.hip; the
 // hook is Engine::out_source (engine_batch.cpp); DESIGN.md section 21 has the contract.
 #include "engine_internal.hpp"
 
@@ -102,28 +102,10 @@ void Engine::ds_enqueue(const DeessTable& t, const float* x, int64_t rows, int64
     if (probe) out(probe->st_start, sc.st, 4);
     // per sample: the two sections (11), log10 (about 20), the gain computer and its cap (9), the detector (3), the smoothing (2), the
     // gain 10^x and its use (about 23)
-    span.next("deesser_chunks1", 43.0 * samples, samples * 4 + chunks * 20);
-    launch_deesser_chunks(s_, 1, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_end, sc.s1, 1);
-    span.next("deesser_scan1", chunks * 11 * 2, chunks * 8);
-    launch_compressor_scan(s_, 1, rows, W, t.det, sc.s1);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_start, sc.s1, 1);
-    span.next("deesser_chunks2", 45.0 * samples, samples * 4 + chunks * 24);
-    launch_deesser_chunks(s_, 2, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, nullptr, nullptr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_end, sc.s2, 1);
-    span.next("deesser_scan2", chunks * 11 * 2, chunks * 8);
-    launch_compressor_scan(s_, 2, rows, W, t.det, sc.s2);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_start, sc.s2, 1);
-    span.next("deesser_write", 68.0 * samples, samples * (8 + (band ? 4 : 0) + (gr ? 4 : 0)) + chunks * 28);
-    launch_deesser_chunks(s_, 3, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, band, gr, sc.cmax);
-    STN_HIP(hipGetLastError());
-    span.next("deesser_rowmax", chunks, chunks * 4 + (double)rows * 4);
-    launch_compressor_rowmax(s_, rows, W, sc.cmax, sc.rmax);
-    STN_HIP(hipGetLastError());
+    static constexpr DynSeq seq{"deesser", "rowmax", {43.0, 45.0, 68.0}, {20, 24, 28}, 1, 4, 4};
+    dyn_enqueue(seq, t.det, rows, W, sc, (band ? 1 : 0) + (gr ? 1 : 0), probe, &span,
+                [&](int pass) { launch_deesser_chunks(s_, pass, x, rows, W, n.n, t, sc.st, sc.s1, sc.s2, y, band, gr, sc.cmax); },
+                [&] { launch_compressor_rowmax(s_, rows, W, sc.cmax, sc.rmax); });
 }
 
 void Engine::ds_batch(const float* x, int64_t Wo, float* y) {
@@ -135,7 +117,7 @@ void Engine::batch_deesser(float* max_reduction_db) {
 }
 
 void Engine::op_deesser(int hz, int rows, int W, const float* x, const stn_deesser& c, float* y, DsProbe* probe) {
-    dyn_op(ds_, hz, rows, W, x, c, y, probe, deesser_table, ds_layout, {probe ? probe->band : nullptr, probe ? probe->gr : nullptr}, deesser_staging_form,
+    dyn_op(ds_, hz, rows, W, x, c, y, probe, deesser_table, ds_layout, {probe ? probe->band : nullptr, probe ? probe->gr : nullptr},
            [&](const DeessTable& t, const DsScratch& sc, RowSpans n, const float* dx, float* dy, float* const* tap) { ds_enqueue(t, dx, rows, W, n, sc, dy, probe, tap[0], tap[1]); });
 }
 

@@ -284,7 +284,7 @@ void Engine::op_silence_edges_ex(int hz, int rows, int W, const float* x, const 
     if (probe.pa) STN_HIP(hipMemcpyAsync(probe.pa, sc.pa, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
     if (probe.pb) STN_HIP(hipMemcpyAsync(probe.pb, sc.pb, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
     if (probe.lev) STN_HIP(hipMemcpyAsync(probe.lev, sc.lev, nf * sizeof(double), hipMemcpyDeviceToHost, s_));
-    probe.form = edges_staging_form(dx, W);
+    probe.form = chunk_staging_form(dx, nullptr, W);
     sync();  // (e and pz are read or written by the copies above until here)
     for (int r = 0; r < rows; ++r) {
         if (start) start[r] = e[(size_t)r * 2];

@@ -1,5 +1,5 @@
 // engine_expander.cpp — the fetch-time downward expander / noise gate of a handle: its limits, coefficients and static curve (host
-// only), the scan tables and the scratch, the sequence of launches and the op-level entry.  The kernels are kernels_expander.hip; the
+// only), the scan tables and the scratch, the sequence of launches and the op-level entry.  The kernels are kernels_dynamics.hip; the
 // hook is Engine::out_source (engine_batch.cpp); DESIGN.md section 25 has the contract.
 #include "engine_internal.hpp"
 
@@ -80,32 +80,11 @@ Engine::XpScratch Engine::xp_layout(char* base, int64_t rows, int64_t W) {
 }
 
 void Engine::xp_enqueue(const ExpTable& t, const float* x, int64_t rows, int64_t W, const int64_t* n, const XpScratch& sc, float* y, float* open, XpProbe* probe) {
-    const double samples = (double)rows * W, chunks = (double)rows * lo_chunks(W);
-    const size_t st_bytes = (size_t)rows * (size_t)lo_chunks(W) * 4;
-    auto out = [&](float* dst, const float* src) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, st_bytes, hipMemcpyDeviceToHost, s_)); };
     // per sample: log10 (about 20), the gain computer (11), the detector (2), the clamp and the smoothing (3), the gain 10^x and its product (about 22)
-    StageSpan span(*this, "out", "expander_chunks1", 33.0 * samples, samples * 4 + chunks * 4);
-    launch_expander_chunks(s_, 1, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_end, sc.s1);
-    span.next("expander_scan1", chunks * 11 * 2, chunks * 8);
-    launch_expander_scan(s_, 1, rows, W, t, sc.s1);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s1_start, sc.s1);
-    span.next("expander_chunks2", 36.0 * samples, samples * 4 + chunks * 8);
-    launch_expander_chunks(s_, 2, x, rows, W, n, t, sc.s1, sc.s2, y, nullptr, sc.cmin, sc.ccnt);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_end, sc.s2);
-    span.next("expander_scan2", chunks * 11 * 2, chunks * 8);
-    launch_expander_scan(s_, 2, rows, W, t, sc.s2);
-    STN_HIP(hipGetLastError());
-    if (probe) out(probe->s2_start, sc.s2);
-    span.next("expander_write", 60.0 * samples, samples * (open ? 12 : 8) + chunks * 16);
-    launch_expander_chunks(s_, 3, x, rows, W, n, t, sc.s1, sc.s2, y, open, sc.cmin, sc.ccnt);
-    STN_HIP(hipGetLastError());
-    span.next("expander_rows", chunks * 2, chunks * 8 + (double)rows * 12);
-    launch_expander_rows(s_, rows, W, t, sc.cmin, sc.ccnt, sc.rmin, sc.rcnt);
-    STN_HIP(hipGetLastError());
+    static constexpr DynSeq seq{"expander", "rows", {33.0, 36.0, 60.0}, {4, 8, 16}, 2, 8, 12};
+    dyn_enqueue(seq, t, rows, W, sc, open ? 1 : 0, probe, nullptr,
+                [&](int pass) { launch_expander_chunks(s_, pass, x, rows, W, n, t, sc.s1, sc.s2, y, open, sc.cmin, sc.ccnt); },
+                [&] { launch_expander_rows(s_, rows, W, t, sc.cmin, sc.ccnt, sc.rmin, sc.rcnt); });
 }
 
 void Engine::xp_batch(const float* x, int64_t Wo, float* y) {
@@ -120,7 +99,7 @@ void Engine::batch_expander(float* min_attenuation_db, int64_t* closed_samples) 
 }
 
 void Engine::op_expander(int hz, int rows, int W, const float* x, const stn_expander& c, float* y, XpProbe* probe) {
-    dyn_op(xp_, hz, rows, W, x, c, y, probe, expander_table, xp_layout, {probe ? probe->open : nullptr}, expander_staging_form,
+    dyn_op(xp_, hz, rows, W, x, c, y, probe, expander_table, xp_layout, {probe ? probe->open : nullptr},
            [&](const ExpTable& t, const XpScratch& sc, RowSpans n, const float* dx, float* dy, float* const* tap) { xp_enqueue(t, dx, rows, W, n.n, sc, dy, tap[0], probe); });
 }
 

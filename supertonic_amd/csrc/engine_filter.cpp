@@ -173,7 +173,7 @@ void Engine::op_filter(int hz, int rows, int W, const float* x, int n, const stn
     r.download(y);
     if (probe) {
         probe->guard_ok = r.guards_ok();
-        probe->form = filter_staging_form(r.dx, r.dy, W);
+        probe->form = chunk_staging_form(r.dx, r.dy, W);
     }
     sync();
 }

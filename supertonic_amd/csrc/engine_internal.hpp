@@ -3,10 +3,12 @@
 // and tools).
 #pragma once
 #include "engine.hpp"
+#include "kernels_chunk.hpp"
 
 #include <algorithm>
 #include <array>
 #include <cstdio>
+#include <optional>
 
 namespace stn {
 namespace detail {
@@ -124,6 +126,47 @@ void Engine::dyn_batch(St& st, Stage stage, int64_t Wo, Build build, Layout layo
     st.valid = true;
 }
 
+// The six launches a dynamics stage ends in, on rows x W fp32 with the scratch sc (its s1 and s2) and the scan table t (comb and the two
+// power tables in dev): chunk pass 1, scan 1, chunk pass 2, scan 2, the write pass, the row reduction.  d: the stage's description.
+// chunks(pass) and reduce() are the stage's launches; taps: how many per-sample outputs the write pass stores; probe (or null): the four
+// state arrays read out where the sequence leaves them; open (or null): the span a prologue of the stage's own left open.
+template <class Tab, class Sc, class Chunks, class Reduce>
+void Engine::dyn_enqueue(const DynSeq& d, const Tab& t, int64_t rows, int64_t W, const Sc& sc, int taps, const DynProbe* probe, StageSpan* open,
+                         Chunks chunks, Reduce reduce) {
+    const double samples = (double)rows * W, nchunks = (double)rows * lo_chunks(W);
+    const size_t st_bytes = (size_t)rows * (size_t)lo_chunks(W) * 4;
+    std::optional<StageSpan> own;
+    auto step = [&](const char* name, double flops, double bytes) {
+        char tag[64];
+        std::snprintf(tag, sizeof(tag), "%s_%s", d.unit, name);
+        if (open) open->next(tag, flops, bytes);
+        else open = &own.emplace(*this, "out", tag, flops, bytes);
+    };
+    auto done = [&](float* dst, const float* src) {
+        STN_HIP(hipGetLastError());
+        if (probe && dst) STN_HIP(hipMemcpyAsync(dst, src, st_bytes, hipMemcpyDeviceToHost, s_));
+    };
+    auto scan = [&](ScanComb comb, int half, float* st) { launch_chunk_scan(s_, comb, d.unit, rows, W, t.dev ? t.dev + half * LO_SCAN : nullptr, st); };
+    step("chunks1", d.flop[0] * samples, samples * 4 + nchunks * d.state[0]);
+    chunks(1);
+    done(probe ? probe->s1_end : nullptr, sc.s1);
+    step("scan1", nchunks * 11 * 2, nchunks * 8);
+    scan(Tab::comb, 0, sc.s1);
+    done(probe ? probe->s1_start : nullptr, sc.s1);
+    step("chunks2", d.flop[1] * samples, samples * 4 + nchunks * d.state[1]);
+    chunks(2);
+    done(probe ? probe->s2_end : nullptr, sc.s2);
+    step("scan2", nchunks * 11 * 2, nchunks * 8);
+    scan(SCAN_LINEAR, 1, sc.s2);
+    done(probe ? probe->s2_start : nullptr, sc.s2);
+    step("write", d.flop[2] * samples, samples * (8 + 4 * taps) + nchunks * d.state[2]);
+    chunks(3);
+    done(nullptr, nullptr);
+    step(d.rows, nchunks * d.rows_flop, nchunks * d.rows_chunk + (double)rows * d.rows_row);
+    reduce();
+    done(nullptr, nullptr);
+}
+
 template <class St, class Layout, class Read>
 void Engine::dyn_report(St& st, Stage stage, Layout layout, bool wanted, Read read) {
     const int64_t Wo = out_row_len();
@@ -148,7 +191,7 @@ void Engine::read_rows(T* host, const T* dev) {
 
 template <class St, class Set, class Probe, class Build, class Layout, class Run>
 void Engine::dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& c, float* y, Probe* probe, Build build, Layout layout,
-                    std::initializer_list<float*> taps, const char* (*form)(const float*, const float*, int64_t), Run run) {
+                    std::initializer_list<float*> taps, Run run) {
     STN_HIP(hipSetDevice(device_));
     dyn_prepare(st.op_tab, hz, c, build);
     ar_.reset();
@@ -173,7 +216,7 @@ void Engine::dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& 
     }
     if (probe) {
         probe->guard_ok = r.guards_ok();
-        probe->form = form(r.dx, r.dy, W);
+        probe->form = chunk_staging_form(r.dx, r.dy, W);
     }
     sync();
 }

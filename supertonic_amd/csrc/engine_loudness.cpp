@@ -254,7 +254,7 @@ const int64_t* Engine::lo_op(int hz, int rows, int W, const float* x, const int6
         out(probe->pk, sc.pk, nc * 4);
         out(probe->pa, sc.pa, nc * 4);
         out(probe->pb, sc.pb, nc * 4);
-        probe->form = loudness_staging_form(dx, W);
+        probe->form = chunk_staging_form(dx, nullptr, W);
     }
     sync();
     return dn;

@@ -491,8 +491,6 @@ inline int64_t edges_frames(int64_t W, int hz) { const int F = edges_frame(hz); 
 void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float* pa, float* pb);
 void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
                        const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog);
-// the staging path the frame pass takes for these rows: "vec" (16-byte loads: W % 4 == 0 and x 16-byte aligned) or "scalar"
-const char* edges_staging_form(const float* x, int64_t W);
 // The pause limit, behind launch_edges_rows on the same stream: lev and edges as that launch left them -> row r's
 // segments seg[r * S .. r * S + count) (the row's [start, end) without the middle of every pause longer than Mp samples, at most S - 1
 // cuts, the first in time order), prog[r] = {len_r, r * S, count} and cuts[r][2 S] = {count - 1, len_r, lo_0, hi_0, lo_1, ...}.
@@ -585,8 +583,6 @@ __host__ __device__ inline int64_t lo_chunks(int64_t W) { return (W + LO_CHUNK -
 // over the chunk's samples in its first 100 ms segment / in the next one, counting only whole segments.  Ks = lo_chunks(W).
 void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
                             float* st, float* pk, float* pa, float* pb);
-// the staging path the two chunk passes take for these rows: "vec" (16-byte loads: W % 4 == 0 and x 16-byte aligned) or "scalar"
-const char* loudness_staging_form(const float* x, int64_t W);
 // in place: st[row][k] (end states) -> the start states of the chunks
 void launch_loudness_scan(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t, float* st);
 // res[0][b] = L_b (-inf when undefined), res[1][b] = peak_b, res[2][b] = g_b (1 when off or L_b undefined); max_seg = max_b n_b / hop
@@ -634,60 +630,55 @@ void cascade_powers(const LoudCoef& c, std::vector<double>& mpow);
 // every chunk from its start state st[row][k] and writes y (row stride W, as x).  y may be x: a workgroup reads its LO_WG * LO_CHUNK
 // samples before it stores any, and touches no other workgroup's.
 void launch_filter_write(hipStream_t s, const float* x, int64_t rows, int64_t W, const LoudTable& t, const float* st, float* y);
-// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
-const char* filter_staging_form(const float* x, const float* y, int64_t W);
 
-// Fetch-time dynamic range compressor (kernels_compressor.hip; the limits, the tables and the sequence are engine_compressor.cpp;
-// DESIGN.md section 20).  Every row W long, chunks of LO_CHUNK samples from sample 0, workgroups of LO_WG chunks, scan tiles of LO_SCAN.
+// The three fetch-time dynamics stages (kernels_dynamics.hip: one chunk kernel over a stage policy, one scan, one row reduction; the
+// limits and the tables are engine_<stage>.cpp, the sequence of launches Engine::dyn_enqueue; DESIGN.md sections 20, 20a, 21, 25).  Every
+// row W long, chunks of LO_CHUNK samples from sample 0, workgroups of LO_WG chunks, scan tiles of LO_SCAN.  A stage's three chunk passes:
+// pass 1: s1[row][k] = the detector at the end of chunk k from zero.  pass 2: s1 = the detector at the chunk's start -> s2[row][k] = yL
+// at its end from zero.  pass 3: s1, s2 = the start values -> y (row stride W; may be x), the per-sample taps (rows x W, or null) and
+// the per-chunk results over the chunk's samples below n[row] (device; null: W).  The staging form of all three is that of (x, y, W)
+// (chunk_staging_form, kernels_chunk.hpp).
+// The scan between them, for every stage whose chunks compose by one of these (pw: LO_SCAN doubles on the device): v + P o, max(v, P o)
+// and max(v, o - P) (the expander's detector, section 25).  In place: st[row][k] end values from zero -> the chunks' start values; unit
+// names the caller in what is refused.  A stage's table names its first scan's combination (comb, on dev[0 .. LO_SCAN)); its second is
+// the linear one on dev[LO_SCAN .. 2 LO_SCAN).
+enum ScanComb { SCAN_LINEAR = 0, SCAN_MAX_TIMES = 1, SCAN_MAX_PLUS = 2 };
+void launch_chunk_scan(hipStream_t s, ScanComb comb, const char* unit, int64_t rows, int64_t W, const double* pw, float* st);
+
+// Compressor: the detector is y1.
 struct CompCoef { float T, S, K, kA, kR, makeup; };  // threshold dB, 1 / ratio - 1, knee dB, attack and release k, makeup dB (fp32)
 struct CompTable {
+    static constexpr ScanComb comb = SCAN_MAX_TIMES;
     int hz = 0;
     CompCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: D^(i+1) then E^(i+1), D = (1 - kR)^LO_CHUNK, E = (1 - kA)^LO_CHUNK
     double* dev = nullptr;            // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
-// pass 1: s1[row][k] = y1 at the end of chunk k from zero.  pass 2: s1 = y1 at the chunk's start -> s2[row][k] = yL at its end from
-// zero.  pass 3: s1, s2 = the start values -> y (row stride W; may be x), gr (rows x W yL, or null), cmax[row][k] = max of yL over the
-// chunk's samples below n[row] (device; null: W).  The staging form of all three is that of (x, y, W).
+// gr: rows x W yL, or null.  cmax[row][k] = max of yL (0 without a valid sample)
 void launch_compressor_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const CompTable& t, float* s1,
                               float* s2, float* y, float* gr, float* cmax);
-// in place: st[row][k] end values from zero -> the chunks' start values; stage 1 the (max, x) scan, stage 2 the linear one
-void launch_compressor_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const CompTable& t, float* st);
-// the scan itself, for every stage whose chunks compose by one of these (pw: LO_SCAN doubles on the device): v + P o, max(v, P o) and
-// max(v, o - P) (the expander's detector, section 25); unit names the caller in what chunk_shape refuses
-enum ScanComb { SCAN_LINEAR = 0, SCAN_MAX_TIMES = 1, SCAN_MAX_PLUS = 2 };
-void launch_chunk_scan(hipStream_t s, ScanComb comb, const char* unit, int64_t rows, int64_t W, const double* pw, float* st);
 // out[row] = max_k cmax[row][k]
 void launch_compressor_rowmax(hipStream_t s, int64_t rows, int64_t W, const float* cmax, float* out);
-// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
-const char* compressor_staging_form(const float* x, const float* y, int64_t W);
 
-// Fetch-time downward expander / noise gate (kernels_expander.hip; the limits, the tables and the sequence are engine_expander.cpp;
-// DESIGN.md section 25).  Every row W long, chunks of LO_CHUNK samples from sample 0, workgroups of LO_WG chunks, scan tiles of LO_SCAN.
+// Downward expander / noise gate: the detector is u.
 struct ExpCoef { float T, S, K, R, kA, delta, Bh; };  // threshold dB, ratio - 1, knee dB, range dB, attack k, release dB per sample, hold boost dB (fp32)
 struct ExpTable {
+    static constexpr ScanComb comb = SCAN_MAX_PLUS;
     int hz = 0;
     int64_t hold = 0;                 // Hs, the hold in samples
     ExpCoef coef{};
     std::vector<double> pw;           // host copy, [2][LO_SCAN]: (i + 1) LO_CHUNK delta then E^(i+1), E = (1 - kA)^LO_CHUNK
     double* dev = nullptr;            // device copy (not owned: the engine keeps the block, a DeviceTable, beside the table)
 };
-// pass 1: s1[row][k] = u at the end of chunk k from zero.  pass 2: s1 = u at the chunk's start -> s2[row][k] = yL at its end from zero.
-// pass 3: s1, s2 = the start values -> y (row stride W; may be x), open (rows x W yL, or null), cmin[row][k] = min of R - yL and
-// ccnt[row][k] = count of yL <= R / 2 over the chunk's samples below n[row] (device; null: W).  The staging form of all three is that
-// of (x, y, W).
+// open: rows x W yL, or null.  cmin[row][k] = min of R - yL and ccnt[row][k] = count of yL <= R / 2 (R and 0 without a valid sample)
 void launch_expander_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const ExpTable& t, float* s1,
                             float* s2, float* y, float* open, float* cmin, int32_t* ccnt);
-// in place: st[row][k] end values from zero -> the chunks' start values; stage 1 the (max, +) scan, stage 2 the linear one
-void launch_expander_scan(hipStream_t s, int stage, int64_t rows, int64_t W, const ExpTable& t, float* st);
 // omin[row] = min_k cmin[row][k], ocnt[row] = sum_k ccnt[row][k]
 void launch_expander_rows(hipStream_t s, int64_t rows, int64_t W, const ExpTable& t, const float* cmin, const int32_t* ccnt, float* omin, int64_t* ocnt);
-// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
-const char* expander_staging_form(const float* x, const float* y, int64_t W);
 
-// Fetch-time de-esser (kernels_deesser.hip; the limits, the tables and the sequence of eight launches are engine_deesser.cpp; DESIGN.md
-// section 21): the compressor's detector on the level of a band h = HP4(x), its gain on the band (split) or on x (wide).  The band's
-// chunk pass and scan are the loudness measurement's on `band`, the detector's scans the compressor's on `det`.
+// De-esser (eight launches): the compressor's detector on the level of a band h = HP4(x), its gain on the band
+// (split) or on x (wide).  The band's chunk pass and scan are the loudness measurement's on `band`, the detector's scans run on `det`,
+// the row maxima are launch_compressor_rowmax.
 struct DeessCoef { LoudCoef band; float T, S, K, kA, kR, range; };  // the two high-pass sections; threshold dB, 1 / ratio - 1, knee dB, k, range dB
 struct DeessTable {
     int hz = 0;
@@ -696,14 +687,10 @@ struct DeessTable {
     LoudTable band;                   // the band's section pass: coefficients and the powers of its M (hop = 1, unused)
     CompTable det;                    // the scans' powers from the same attack and release (makeup 0; its T, S, K are not read)
 };
-// Every pass regenerates h from x and st[row][k], the band's state at the start of chunk k.  pass 1: s1[row][k] = y1 at the end of chunk
-// k from zero.  pass 2: s1 = y1 at the chunk's start -> s2[row][k] = yL at its end from zero.  pass 3: s1, s2 = the start values -> y
-// (row stride W; may be x), band and gr (rows x W h and yL, or null), cmax[row][k] = max of yL over the chunk's samples below n[row]
-// (device; null: W).  The staging form of all three is that of (x, y, W).
+// Every pass regenerates h from x and st[row][k], the band's state at the start of chunk k.  band and gr: rows x W h and yL, or null.
+// cmax as the compressor's
 void launch_deesser_chunks(hipStream_t s, int pass, const float* x, int64_t rows, int64_t W, const int64_t* n, const DeessTable& t, const float* st,
                            float* s1, float* s2, float* y, float* band, float* gr, float* cmax);
-// "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
-const char* deesser_staging_form(const float* x, const float* y, int64_t W);
 
 // Look-ahead peak limiter behind the loudness gain (kernels_limiter.hip; the setting, the window and the scratch are engine_limiter.cpp;
 // DESIGN.md section 15).  rows x W fp32 (row stride W) with row spans n[rows] (device, <= W) and gains gain[rows] (device; null: 1) ->

@@ -1,6 +1,7 @@
 // kernels_chunk.hpp — what the chunk kernels of the fetch-time stages share (kernels_loudness.hip, kernels_edges.hip, kernels_filter.hip,
-// kernels_compressor.hip, kernels_deesser.hip, kernels_expander.hip; DESIGN.md sections 11, 14, 18, 20, 21, 25): the staging of a workgroup's span through LDS,
-// the two-section biquad step, the gain computer and the two detector recurrences, and the host's choice of the staging form.
+// kernels_dynamics.hip; DESIGN.md sections 11, 14, 18, 20, 21, 25): the staging of a workgroup's span through LDS, the two-section
+// biquad step, the gain computers and the detector recurrences, and the host's choice of the staging form (the engine's op entries
+// report it: engine_internal.hpp includes this header for chunk_staging_form).
 // One definition each: a pass and the pass that refilters from the start states the scan formed round identically by construction.
 #pragma once
 #include "kernels.hpp"
@@ -126,6 +127,8 @@ __device__ __forceinline__ float expand_detect(float delta, float t, float u) { 
 inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 // 1: the 16-byte form of chunk_stage_in / chunk_stage_out for rows of stride W read at x and written at y (null: not written)
 inline int chunk_vec(const float* x, const float* y, int64_t W) { return W % 4 == 0 && aligned16(x) && aligned16(y) ? 1 : 0; }
+// that choice as the op-level probes name it: "vec" (16-byte loads and stores: W % 4 == 0, x and y 16-byte aligned) or "scalar"
+inline const char* chunk_staging_form(const float* x, const float* y, int64_t W) { return chunk_vec(x, y, W) ? "vec" : "scalar"; }
 // the limits of a grid (ceil(W / (LO_WG * LO_CHUNK)), rows) whose chunk index is an int
 inline void chunk_shape(const char* unit, int64_t rows, int64_t W) {
     if (rows > 65535) throw std::invalid_argument(std::string(unit) + ": more than 65535 rows");

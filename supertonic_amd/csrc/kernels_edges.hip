@@ -260,8 +260,6 @@ void launch_edges_frames(hipStream_t s, const float* x, int64_t rows, int64_t W,
     STN_KLAUNCH(edges_chunk_kernel, dim3((unsigned)((W + ED_SPAN - 1) / ED_SPAN), (unsigned)rows), dim3(ED_WG), 0, s, x, W, vec, n, ed_chunks(W), F, pa, pb);
 }
 
-const char* edges_staging_form(const float* x, int64_t W) { return chunk_vec(x, nullptr, W) ? "vec" : "scalar"; }
-
 void launch_edges_rows(hipStream_t s, int64_t rows, int64_t W, const int64_t* n, int hz, double top_db, int64_t keep, int64_t fd, const float* pa,
                        const float* pb, double* lev, int64_t* edges, JoinSegT* seg, JoinProg* prog) {
     if (rows <= 0 || W <= 0) return;

@@ -49,8 +49,6 @@ __global__ void __launch_bounds__(LO_WG) filter_write_kernel(const float* x, flo
 
 }  // namespace
 
-const char* filter_staging_form(const float* x, const float* y, int64_t W) { return chunk_vec(x, y, W) ? "vec" : "scalar"; }
-
 void launch_filter_write(hipStream_t s, const float* x, int64_t rows, int64_t W, const LoudTable& t, const float* st, float* y) {
     if (rows <= 0 || W <= 0) return;
     chunk_shape("filter", rows, W);

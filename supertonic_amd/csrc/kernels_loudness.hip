@@ -292,8 +292,6 @@ void lo_check(int64_t rows, int64_t W, const LoudTable& t) {
 
 }  // namespace
 
-const char* loudness_staging_form(const float* x, int64_t W) { return chunk_vec(x, nullptr, W) ? "vec" : "scalar"; }
-
 void launch_loudness_chunks(hipStream_t s, bool energy, const float* x, int64_t rows, int64_t W, const int64_t* n, const LoudTable& t,
                             float* st, float* pk, float* pa, float* pb) {
     if (rows <= 0 || W <= 0) return;

@@ -1,5 +1,5 @@
 """The eight launches of the fetch-time de-esser on an MI355X, through stn_op_deesser_ex (Engine::ds_enqueue itself: the band's chunk pass
-and scan, chunk pass 1, the (max, x) scan, chunk pass 2, the linear scan, the write pass, the row maxima; kernels_deesser.hip; DESIGN.md
+and scan, chunk pass 1, the (max, x) scan, chunk pass 2, the linear scan, the write pass, the row maxima; kernels_dynamics.hip; DESIGN.md
 section 21), its scratch poisoned with NaN and laid open: the band's and both detector stages' chunk end values and start values, h, yL
 and y against the contract's recurrence in float64 on the same fp32 coefficients (tests/deesser_ref.py), on the rows, settings, widths
 and bounds of tests/deesser_cases.py; both staging forms, a row alone / as row 5 of 8 / at a wider W, and in place against out of place,

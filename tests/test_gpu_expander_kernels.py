@@ -1,5 +1,5 @@
 """The five launches of the fetch-time expander on an MI355X, through stn_op_expander_ex (Engine::xp_enqueue itself: chunk pass 1, the
-(max, +) scan, chunk pass 2, the linear scan, the write pass; kernels_expander.hip), its scratch poisoned with
+(max, +) scan, chunk pass 2, the linear scan, the write pass; kernels_dynamics.hip), its scratch poisoned with
 NaN and laid open: both stages' chunk end values and start values, yL (open_db) and y against the contract's recurrence in float64 on
 the same fp32 coefficients (tests/expander_ref.py), on the rows, settings, widths and bounds of tests/expander_cases.py; both staging
 forms, a row alone / as row 5 of 8 / at a wider W, and in place against out of place, bit for bit; the guards around x and y.

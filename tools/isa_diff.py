@@ -7,7 +7,11 @@ Per kernel symbol of the gfx950 code objects (extracted as tests/test_isa_cpu.py
   - the resource fields of its descriptor as the code object's metadata note states them: VGPR, AGPR and SGPR counts, LDS bytes, scratch bytes.
 Prints the symbols present on one side only and the kernels that differ (with the first differing instruction).
 
-usage: tools/isa_diff.py old/libstn.so new/libstn.so      exit code 1 when anything differs.  Needs no GPU.
+usage: tools/isa_diff.py [--map OLD=NEW ...] old/libstn.so new/libstn.so      exit code 1 when anything differs.  Needs no GPU.
+
+--map OLD=NEW pairs a renamed kernel: the one symbol present only in the old build whose name contains OLD with the one present only in
+the new build whose name contains NEW.  A pair is compared like a kept symbol, and its instruction counts and resource fields are
+printed for both sides whether they differ or not.
 """
 import glob
 import os
@@ -54,10 +58,31 @@ def load(lib):
     return out
 
 
+def pair(old, new, maps):
+    """the symbols of `new` that a --map pairs with a symbol of `old` take that symbol's name; returns {old name: new name}"""
+    only_old, only_new = set(old) - set(new), set(new) - set(old)
+    paired = {}
+    for m in maps:
+        a, _, b = m.partition("=")
+        sa, sb = [n for n in only_old if a in n], [n for n in only_new if b in n]
+        if not (a and b and len(sa) == 1 and len(sb) == 1):
+            raise SystemExit(f"--map {m}: {len(sa)} old and {len(sb)} new unpaired symbols match, need one of each")
+        paired[sa[0]] = sb[0]
+        new[sa[0]] = new.pop(sb[0])
+        only_old.discard(sa[0])
+        only_new.discard(sb[0])
+    return paired
+
+
 def main():
-    if len(sys.argv) != 3:
+    args, maps = sys.argv[1:], []
+    while args and args[0] == "--map" and len(args) > 1:
+        maps.append(args[1])
+        args = args[2:]
+    if len(args) != 2:
         raise SystemExit(__doc__)
-    old, new = load(sys.argv[1]), load(sys.argv[2])
+    old, new = load(args[0]), load(args[1])
+    paired = pair(old, new, maps)
     bad = 0
     for side, only in (("old", sorted(set(old) - set(new))), ("new", sorted(set(new) - set(old)))):
         for name in only:
@@ -65,6 +90,8 @@ def main():
         bad += len(only)
     for name in sorted(set(old) & set(new)):
         (ia, ra), (ib, rb) = old[name], new[name]
+        if name in paired:
+            print(f"paired: {name}\n    with {paired[name]}\n    old {len(ia)} instructions {ra}\n    new {len(ib)} instructions {rb}")
         if ra != rb:
             print(f"resources differ: {name}\n    old {ra}\n    new {rb}")
         if ia != ib:
@@ -73,7 +100,7 @@ def main():
             print(f"instructions differ: {name}\n    {len(ia)} against {len(ib)} instructions, first difference at #{at}: {show(ia)}  |  {show(ib)}")
         bad += ra != rb or ia != ib
     kernels = sum(1 for _, r in new.values() if r is not None)
-    print(f"{len(new)} symbols ({kernels} kernels) in {sys.argv[2]}: {bad} missing or different against {sys.argv[1]}")
+    print(f"{len(new)} symbols ({kernels} kernels) in {args[1]}: {bad} missing or different against {args[0]}")
     return 1 if bad else 0
 
 
