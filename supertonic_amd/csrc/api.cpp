@@ -43,6 +43,19 @@ static thread_local std::string g_create_err;
 static void need(bool ok, const char* what) {
     if (!ok) throw std::invalid_argument(what);
 }
+// a finished batch, or "no finished batch" as the error `err` of the entry: STN_ERR_STATE, or, in the older entries, STN_ERR_INVALID
+static void need_batch(stn_handle* h, int err = STN_ERR_STATE) {
+    if (h->eng->batch().B > 0 && h->eng->batch().L > 0) return;
+    if (err == STN_ERR_INVALID) throw std::invalid_argument("no finished batch");
+    throw std::runtime_error("no finished batch");
+}
+// the argument checks the row entries share.  fn: the entry's name, as the messages give it; ptrs: whether every required pointer is
+// there, what: their list as the message gives it; x_misalign, in_place: an _ex entry's 0 / 1 flags (null: it has none)
+static void need_op_rows(const std::string& fn, int rows, int W, bool ptrs, const char* what, const int* x_misalign = nullptr, const int* in_place = nullptr) {
+    need(rows > 0 && rows <= 65535 && W > 0 && ptrs, (fn + ": bad argument (1 <= rows <= 65535, W >= 1, " + what + ")").c_str());
+    auto flag = [](const int* f) { return !f || *f == 0 || *f == 1; };
+    need(flag(x_misalign) && flag(in_place), (fn + (in_place ? ": x_misalign and in_place must be 0 or 1" : ": x_misalign must be 0 or 1")).c_str());
+}
 static void need_model(stn_handle* h) {
     if (!h->eng->loaded()) throw std::runtime_error("no model loaded: call stn_load_synthetic or stn_load_dir first");
 }
@@ -320,7 +333,7 @@ const char* stn_resample_error(int in_hz, int out_hz) {
     return why.c_str();
 }
 int stn_op_resample(stn_handle* h, int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && (y || pcm), "stn_op_resample: bad argument (1 <= rows <= 65535, W >= 1, x and y or pcm)");
+    STN_TRY(h, { need_op_rows("stn_op_resample", rows, W, x && (y || pcm), "x and y or pcm");
                  h->eng->op_resample(in_hz, out_hz, rows, W, x, y, pcm); })
 }
 int stn_dbg_resample_form(int in_hz, int out_hz, int64_t W, char* out, size_t cap) {
@@ -342,17 +355,16 @@ int stn_get_loudness(const stn_handle* h, int* on, float* target_lufs, float* ce
     return STN_OK;
 }
 int stn_batch_loudness(stn_handle* h, float* lufs, float* peak, float* gain) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_loudness(lufs, peak, gain); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_loudness(lufs, peak, gain); })
 }
 int stn_op_loudness(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float* lufs, float* peak) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness: bad argument (1 <= rows <= 65535, W >= 1, x)");
+    STN_TRY(h, { need_op_rows("stn_op_loudness", rows, W, x, "x");
                  h->eng->op_loudness(hz, rows, W, x, n, lufs, peak); })
 }
 int stn_op_loudness_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, int on, float target_lufs, float ceiling_dbfs,
                        int x_misalign, float* st_end, float* st_start, float* pk, float* pa, float* pb, float* lufs, float* peak, float* gain,
                        char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness_ex: bad argument (1 <= rows <= 65535, W >= 1, x)");
-                 need(x_misalign == 0 || x_misalign == 1, "stn_op_loudness_ex: x_misalign must be 0 or 1");
+    STN_TRY(h, { need_op_rows("stn_op_loudness_ex", rows, W, x, "x", &x_misalign);
                  stn::Engine::LoProbe p;
                  p.x_misalign = x_misalign; p.st_end = st_end; p.st_start = st_start; p.pk = pk; p.pa = pa; p.pb = pb;
                  h->eng->op_loudness_ex(hz, rows, W, x, n, on != 0, target_lufs, ceiling_dbfs, p, lufs, peak, gain);
@@ -367,16 +379,16 @@ int stn_get_silence_trim(const stn_handle* h, int* on, float* top_db, float* kee
     return STN_OK;
 }
 int stn_batch_silence_edges(stn_handle* h, int64_t* start, int64_t* end) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_silence_edges(start, end); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_silence_edges(start, end); })
 }
 int stn_op_silence_edges(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, int64_t* start,
                          int64_t* end) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_silence_edges: bad argument (1 <= rows <= 65535, W >= 1, x)");
+    STN_TRY(h, { need_op_rows("stn_op_silence_edges", rows, W, x, "x");
                  h->eng->op_silence_edges(hz, rows, W, x, n, top_db, keep_ms, start, end); })
 }
 int stn_op_silence_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
                         const float* gain, int enc, void* y, int64_t* start, int64_t* end) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_silence_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_silence_trim", rows, W, x && y, "x and y");
                  h->eng->op_silence_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, gain, enc, y, start, end); })
 }
 int stn_set_pause_limit(stn_handle* h, int on, float max_pause_ms) {
@@ -388,19 +400,18 @@ int stn_get_pause_limit(const stn_handle* h, int* on, float* max_pause_ms) {
     return STN_OK;
 }
 int stn_batch_pauses(stn_handle* h, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_pauses(len, n_cuts, cuts, cap_pairs); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_pauses(len, n_cuts, cuts, cap_pairs); })
 }
 int stn_op_pause_trim(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
                       float max_pause_ms, const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts,
                       int64_t* cuts, int cap_pairs) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pause_trim: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_pause_trim", rows, W, x && y, "x and y");
                  h->eng->op_pause_trim(hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, gain, enc, y, start, end, len, n_cuts, cuts, cap_pairs); })
 }
 int stn_op_silence_edges_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms,
                             float max_pause_ms, int x_misalign, float* pa, float* pb, double* lev, int64_t* start, int64_t* end, int64_t* len,
                             int32_t* n_cuts, int64_t* cuts, int cap_pairs, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_silence_edges_ex: bad argument (1 <= rows <= 65535, W >= 1, x)");
-                 need(x_misalign == 0 || x_misalign == 1, "stn_op_silence_edges_ex: x_misalign must be 0 or 1");
+    STN_TRY(h, { need_op_rows("stn_op_silence_edges_ex", rows, W, x, "x", &x_misalign);
                  stn::Engine::EdProbe p;
                  p.x_misalign = x_misalign; p.pa = pa; p.pb = pb; p.lev = lev;
                  h->eng->op_silence_edges_ex(hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, p, start, end, len, n_cuts, cuts, cap_pairs);
@@ -426,11 +437,11 @@ int stn_get_limiter(const stn_handle* h, int* on, float* lookahead_ms) {
     return STN_OK;
 }
 int stn_batch_limiter(stn_handle* h, float* reduction_db, int64_t* limited) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_limiter(reduction_db, limited); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_limiter(reduction_db, limited); })
 }
 int stn_op_limiter(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs,
                    float lookahead_ms, float* y, float* s, float* reduction_db, int64_t* limited) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_limiter: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_limiter", rows, W, x && y, "x and y");
                  h->eng->op_limiter(hz, rows, W, x, n, gain, ceiling_dbfs, lookahead_ms, y, s, reduction_db, limited); })
 }
 int stn_limiter_window(int hz, float lookahead_ms, float* w, int64_t cap, int64_t* n) {
@@ -453,13 +464,12 @@ int stn_get_filters(const stn_handle* h, int* n, stn_filter* out) {
     return STN_OK;
 }
 int stn_op_filter(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && f && y, "stn_op_filter: bad argument (1 <= rows <= 65535, W >= 1, x, f and y)");
+    STN_TRY(h, { need_op_rows("stn_op_filter", rows, W, x && f && y, "x, f and y");
                  h->eng->op_filter(hz, rows, W, x, n, f, y, nullptr); })
 }
 int stn_op_filter_ex(stn_handle* h, int hz, int rows, int W, const float* x, int n, const stn_filter* f, int x_misalign, float* y, float* st_end,
                      float* st_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && f && y, "stn_op_filter_ex: bad argument (1 <= rows <= 65535, W >= 1, x, f and y)");
-                 need(x_misalign == 0 || x_misalign == 1, "stn_op_filter_ex: x_misalign must be 0 or 1");
+    STN_TRY(h, { need_op_rows("stn_op_filter_ex", rows, W, x && f && y, "x, f and y", &x_misalign);
                  stn::Engine::FlProbe p;
                  p.x_misalign = x_misalign; p.st_end = st_end; p.st_start = st_start;
                  h->eng->op_filter(hz, rows, W, x, n, f, y, &p);
@@ -508,11 +518,6 @@ int stn_dbg_filter_geometry(int* chunk, int* wg_span, int* scan_tile_chunks, int
     if (biquads_per_section) *biquads_per_section = 2;
     return STN_OK;
 }
-// the argument checks the op entries of the three dynamics stages share (fn: the entry's name, as the message gives it; the flags: _ex's two)
-static void need_op_rows(const std::string& fn, int rows, int W, const void* x, const void* c, const void* y, int x_misalign = 0, int in_place = 0) {
-    need(rows > 0 && rows <= 65535 && W > 0 && x && c && y, (fn + ": bad argument (1 <= rows <= 65535, W >= 1, x, c and y)").c_str());
-    need((x_misalign == 0 || x_misalign == 1) && (in_place == 0 || in_place == 1), (fn + ": x_misalign and in_place must be 0 or 1").c_str());
-}
 int stn_set_compressor(stn_handle* h, int on, const stn_compressor* c) { STN_TRY(h, { h->eng->set_compressor(on != 0, c); }) }
 int stn_get_compressor(const stn_handle* h, int* on, stn_compressor* out) {
     if (!h) return STN_ERR_INVALID;
@@ -521,15 +526,15 @@ int stn_get_compressor(const stn_handle* h, int* on, stn_compressor* out) {
     return STN_OK;
 }
 int stn_batch_compressor(stn_handle* h, float* max_reduction_db) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_compressor(max_reduction_db); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_compressor(max_reduction_db); })
 }
 int stn_op_compressor(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, float* y) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y");
                  h->eng->op_compressor(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_compressor_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_compressor* c, int x_misalign, int in_place, float* y,
                          float* gr_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y", &x_misalign, &in_place);
                  stn::Engine::CpProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.gr = gr_db;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
@@ -566,16 +571,16 @@ int stn_get_deesser(const stn_handle* h, int* on, stn_deesser* out) {
     return STN_OK;
 }
 int stn_batch_deesser(stn_handle* h, float* max_reduction_db) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_deesser(max_reduction_db); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_deesser(max_reduction_db); })
 }
 int stn_op_deesser(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, float* y) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y");
                  h->eng->op_deesser(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_deesser_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_deesser* c, int x_misalign, int in_place, float* y,
                       float* band, float* gr_db, float* st_end, float* st_start, float* s1_end, float* s1_start, float* s2_end,
                       float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y", &x_misalign, &in_place);
                  stn::Engine::DsProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.band = band; p.gr = gr_db; p.st_end = st_end; p.st_start = st_start;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
@@ -619,15 +624,15 @@ int stn_get_expander(const stn_handle* h, int* on, stn_expander* out) {
     return STN_OK;
 }
 int stn_batch_expander(stn_handle* h, float* min_attenuation_db, int64_t* closed_samples) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_expander(min_attenuation_db, closed_samples); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_expander(min_attenuation_db, closed_samples); })
 }
 int stn_op_expander(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, float* y) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y");
                  h->eng->op_expander(hz, rows, W, x, *c, y, nullptr); })
 }
 int stn_op_expander_ex(stn_handle* h, int hz, int rows, int W, const float* x, const stn_expander* c, int x_misalign, int in_place, float* y,
                        float* open_db, float* s1_end, float* s1_start, float* s2_end, float* s2_start, int* guard_ok, char* form, size_t form_cap) {
-    STN_TRY(h, { need_op_rows(__func__, rows, W, x, c, y, x_misalign, in_place);
+    STN_TRY(h, { need_op_rows(__func__, rows, W, x && c && y, "x, c and y", &x_misalign, &in_place);
                  stn::Engine::XpProbe p;
                  p.x_misalign = x_misalign; p.in_place = in_place; p.open = open_db;
                  p.s1_end = s1_end; p.s1_start = s1_start; p.s2_end = s2_end; p.s2_start = s2_start;
@@ -682,29 +687,29 @@ int stn_get_pitch(const stn_handle* h, float* semitones, int* a, int* b) {
     return STN_OK;
 }
 int stn_op_time_stretch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* y, int32_t* delta, float* score) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_time_stretch: bad argument (1 <= rows <= 65535, W >= 1, x)");
+    STN_TRY(h, { need_op_rows("stn_op_time_stretch", rows, W, x, "x");
                  h->eng->op_time_stretch(hz, rows, W, x, n, a, b, y, delta, score); })
 }
 int stn_op_pitch(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float semitones, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pitch: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_pitch", rows, W, x && y, "x and y");
                  h->eng->op_pitch(hz, rows, W, x, n, semitones, y); })
 }
 int stn_set_pitch_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_pitch_mode(mode); }) }
 int stn_get_pitch_mode(const stn_handle* h) { return h ? h->eng->pitch_mode() : STN_ERR_INVALID; }
 int stn_op_formant(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y && out, "stn_op_formant: bad argument (1 <= rows <= 65535, W >= 1, x, y and out)");
+    STN_TRY(h, { need_op_rows("stn_op_formant", rows, W, x && y && out, "x, y and out");
                  h->eng->op_formant(hz, rows, W, x, y, n, out); })
 }
 int stn_op_formant_ex(stn_handle* h, int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out, float* ax, float* cy, double* g,
                       double* ex, double* ey, int* guard_ok) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y && out, "stn_op_formant_ex: bad argument (1 <= rows <= 65535, W >= 1, x, y and out)");
+    STN_TRY(h, { need_op_rows("stn_op_formant_ex", rows, W, x && y && out, "x, y and out");
                  stn::Engine::FormantProbe p;
                  p.ax = ax; p.cy = cy; p.g = g; p.ex = ex; p.ey = ey;
                  h->eng->op_formant(hz, rows, W, x, y, n, out, &p);
                  if (guard_ok) *guard_ok = p.guard_ok ? 1 : 0; })
 }
 int stn_op_pitch_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float semitones, int mode, float* y) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_pitch_ex: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_pitch_ex", rows, W, x && y, "x and y");
                  h->eng->op_pitch_ex(hz, rows, W, x, n, semitones, mode, y); })
 }
 int stn_set_peak_mode(stn_handle* h, int mode) { STN_TRY(h, { h->eng->set_peak_mode(mode); }) }
@@ -719,22 +724,21 @@ int stn_true_peak_filter(float* taps, size_t cap, int* phases, int* taps_per_pha
     return STN_OK;
 }
 int stn_batch_true_peak(stn_handle* h, float* tp_in, float* tp_out, float* trim) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_true_peak(tp_in, tp_out, trim); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_true_peak(tp_in, tp_out, trim); })
 }
 int stn_op_true_peak(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp,
                      float* env, float* pk, char* form, size_t form_cap) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_true_peak: bad argument (1 <= rows <= 65535, W >= 1, x)");
-                 need(x_misalign == 0 || x_misalign == 1, "stn_op_true_peak: x_misalign must be 0 or 1");
+    STN_TRY(h, { need_op_rows("stn_op_true_peak", rows, W, x, "x", &x_misalign);
                  const char* f = h->eng->op_true_peak(hz, rows, W, x, n, gain, x_misalign, tp, env, pk);
                  if (form && form_cap) std::snprintf(form, form_cap, "%s", f); })
 }
 int stn_op_limiter_ex(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs,
                       float lookahead_ms, float* y, float* s, float* reduction_db, int64_t* limited, int peak_mode, float* env, float* trim) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && y, "stn_op_limiter_ex: bad argument (1 <= rows <= 65535, W >= 1, x and y)");
+    STN_TRY(h, { need_op_rows("stn_op_limiter_ex", rows, W, x && y, "x and y");
                  h->eng->op_limiter_ex(hz, rows, W, x, n, gain, ceiling_dbfs, lookahead_ms, y, s, reduction_db, limited, peak_mode, env, trim); })
 }
 int stn_dbg_batch_set_wav(stn_handle* h, const float* wav) {
-    STN_TRY(h, { need(wav != nullptr, "wav is null"); need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->dbg_batch_set_wav(wav); })
+    STN_TRY(h, { need(wav != nullptr, "wav is null"); need_batch(h, STN_ERR_INVALID); h->eng->dbg_batch_set_wav(wav); })
 }
 int64_t stn_dbg_span_uploads(const stn_handle* h) { return h ? h->eng->span_uploads() : 0; }
 int stn_kweighting_filter(int hz, double* shelf_b, double* shelf_a, double* hp_b, double* hp_a) {
@@ -757,10 +761,10 @@ int stn_loudness_table(int hz, float* coef10, float* mpow, size_t cap, int* hop)
     return STN_OK;
 }
 int stn_batch_fetch(stn_handle* h, float* wav, size_t cap, float* duration) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch(wav, cap, duration); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch(wav, cap, duration); })
 }
 int stn_batch_fetch_pcm16(stn_handle* h, int16_t* pcm, size_t cap, float* duration) {
-    STN_TRY(h, { need(pcm && h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_pcm16(pcm, cap, duration); })
+    STN_TRY(h, { need(pcm != nullptr, "no finished batch"); need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch_pcm16(pcm, cap, duration); })
 }
 int stn_batch_fetch_slot_dims(stn_handle* h, int slot, int* B, int64_t* W) {
     if (!h) return STN_ERR_INVALID;
@@ -772,7 +776,7 @@ int stn_batch_fetch_slot_dims(stn_handle* h, int slot, int* B, int64_t* W) {
     return STN_OK;
 }
 int stn_batch_fetch_pcm16_begin(stn_handle* h, int slot) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_pcm16_begin(slot); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch_pcm16_begin(slot); })
 }
 int stn_batch_fetch_pcm16_end(stn_handle* h, int slot, const int16_t** pcm, size_t* n_samples, float* duration) {
     STN_TRY(h, { h->eng->batch_fetch_pcm16_end(slot, pcm, n_samples, duration); })
@@ -783,7 +787,7 @@ void* stn_host_alloc_pinned(size_t bytes) {
 }
 void stn_host_free_pinned(void* p) { if (p) (void)hipHostFree(p); }
 int stn_batch_fetch_latent(stn_handle* h, float* latent) {
-    STN_TRY(h, { need(latent && h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_latent(latent); })
+    STN_TRY(h, { need(latent != nullptr, "no finished batch"); need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch_latent(latent); })
 }
 int stn_batch_wav_device_ptr(const stn_handle* h, void** ptr) {
     if (!h || !ptr) return STN_ERR_INVALID;
@@ -799,13 +803,13 @@ static_assert(STN_ENC_F32 == stn::ENC_F32 && STN_ENC_PCM16 == stn::ENC_PCM16 && 
               STN_ENC_ALAW == stn::ENC_ALAW, "include/stn.h and kernels.hpp disagree on the encodings");
 int stn_encoding_bytes(int enc) { return stn::enc_bytes(enc); }
 int stn_batch_fetch_encoded(stn_handle* h, int enc, void* dst, size_t cap, float* duration) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_encoded(enc, dst, cap, duration); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch_encoded(enc, dst, cap, duration); })
 }
 int stn_batch_copy_encoded_device(stn_handle* h, int enc, void* dst, int64_t stride) {
     STN_TRY(h, { need(dst != nullptr, "dst is null"); h->eng->batch_copy_encoded_device(enc, dst, stride); })
 }
 int stn_batch_fetch_encoded_begin(stn_handle* h, int slot, int enc) {
-    STN_TRY(h, { need(h->eng->batch().B > 0 && h->eng->batch().L > 0, "no finished batch"); h->eng->batch_fetch_encoded_begin(slot, enc); })
+    STN_TRY(h, { need_batch(h, STN_ERR_INVALID); h->eng->batch_fetch_encoded_begin(slot, enc); })
 }
 int stn_batch_fetch_encoded_end(stn_handle* h, int slot, const void** data, size_t* n_bytes, float* duration) {
     STN_TRY(h, { h->eng->batch_fetch_encoded_end(slot, data, n_bytes, duration); })
@@ -814,9 +818,6 @@ int stn_op_encode(stn_handle* h, int enc, int rows, int W, const float* x, void*
     STN_TRY(h, { need(rows > 0 && W > 0 && x && y, "stn_op_encode: bad argument (rows >= 1, W >= 1, x and y)"); h->eng->op_encode(enc, rows, W, x, y); })
 }
 static_assert(STN_JOIN_WHOLE == 0 && STN_JOIN_TRIM == 1 && STN_JOIN_GAIN_ROW == 0 && STN_JOIN_GAIN_PROG == 1, "include/stn.h: join constants");
-static void need_batch(stn_handle* h) {
-    if (!(h->eng->batch().B > 0 && h->eng->batch().L > 0)) throw std::runtime_error("no finished batch");  // (STN_ERR_STATE)
-}
 int stn_batch_join_dims(stn_handle* h, const stn_join* j, int64_t* W_join, int64_t* prog_len, float* prog_dur) {
     STN_TRY(h, { need(j != nullptr, "join is null"); need_batch(h);
                  const stn::JoinPlan p = h->eng->batch_join_plan(j);
@@ -844,7 +845,7 @@ int stn_batch_join_loudness_range(stn_handle* h, const stn_join* j, float* m_max
 }
 int stn_op_loudness_range(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, float* m_max, float* s_max, float* lra,
                           int32_t* n_st) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_loudness_range: bad argument (1 <= rows <= 65535, W >= 1, x)");
+    STN_TRY(h, { need_op_rows("stn_op_loudness_range", rows, W, x, "x");
                  h->eng->op_loudness_range(hz, rows, W, x, n, m_max, s_max, lra, n_st); })
 }
 int stn_f0_group(void) { return stn::F0_GROUP; }
@@ -857,12 +858,12 @@ int stn_batch_f0(stn_handle* h, const stn_f0_params* p, int64_t cap, float* f0, 
 }
 int stn_op_f0(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_f0_params* p, int64_t cap, float* f0, float* ap,
               stn_f0_stats* stats) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x, "stn_op_f0: bad argument (1 <= rows <= 65535, W >= 1, x)");
+    STN_TRY(h, { need_op_rows("stn_op_f0", rows, W, x, "x");
                  h->eng->op_f0(hz, rows, W, x, n, p, cap, f0, ap, stats); })
 }
 int stn_op_join(stn_handle* h, int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, int loudness_on, float target_lufs,
                 float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
-    STN_TRY(h, { need(rows > 0 && rows <= 65535 && W > 0 && x && n && j && y, "stn_op_join: bad argument (1 <= rows <= 65535, W >= 1, x, n, j and y)");
+    STN_TRY(h, { need_op_rows("stn_op_join", rows, W, x && n && j && y, "x, n, j and y");
                  h->eng->op_join(hz, rows, W, x, n, j, enc, loudness_on != 0, target_lufs, ceiling_dbfs, y, prog_lufs, prog_peak, prog_gain); })
 }
 int stn_batch_copy_wav_device(stn_handle* h, void* dst, int64_t stride) {

@@ -121,6 +121,7 @@ double expander_curve(const stn_expander& c, double in_db);
 void expander_table(int hz, const stn_expander& c, ExpTable& t);
 
 class Engine;
+class OpScope;
 // One grow-only device buffer of the output stage's fetch scratch (not part of the resident batch: growing it re-keys no captured
 // graph).  reserve returns the block, of at least `bytes`; a block too small is replaced, behind a sync of the engine (a fetch in
 // flight may still read it), by one a quarter larger than asked, and *moved (when given) says so: what the old block held is gone.
@@ -839,9 +840,8 @@ class Engine {
     BatchSpans sp_[2];     // at the model's rate and row length (what pitch reads, and everything else while no rate is set); at any other rate
     DevBuf sp_buf_;
     int64_t sp_uploads_ = 0;
-    // an op entry's spans (checked by spans()) and the width beside them, uploaded into the arena; the host copy stays here until the
-    // entry's closing sync()
-    RowSpans op_spans(int rows, int W, std::vector<int64_t> n);
+    // the host copy of an op entry's spans (OpScope::spans), read by their upload until the entry's closing sync()
+    friend class OpScope;
     std::vector<int64_t> op_sp_;
     void enqueue_after_duration(int total_step, const std::function<void()>& take_text_rows);
     // A captured graph holds raw pointers: everything it can have baked in is part of its key — the batch buffers (`gen`, bumped
@@ -1099,6 +1099,9 @@ class Engine {
     // the two detection launches on rows x W fp32 (x) at hz with the spans n (device): the edges and per-row programmes into sc
     // (sc.S > 0: and the pause limit's launch behind them, Mp samples: the rows' segment tables and cut lists into sc)
     void ed_enqueue(const float* x, int64_t rows, int64_t W, const int64_t* n, int hz, float top_db, float keep_ms, float fade_ms, const EdScratch& sc, int64_t Mp = 0);
+    void ed_op(const char* entry, const char* who, bool pauses, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms,
+               float fade_ms, float max_pause_ms, const float* gain, int enc, void* y, EdProbe* probe, int64_t* start, int64_t* end, int64_t* len,
+               int32_t* n_cuts, int64_t* cuts, int cap_pairs);
     // the finished batch's B rows x Wo at the output rate (x): detection enqueued unless the scratch holds it already; pauses: with the
     // cuts under pl_ms_ (the fetch paths pass pause_limit_active())
     EdScratch ed_batch(const float* x, int64_t Wo, bool pauses);

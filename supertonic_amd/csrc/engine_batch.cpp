@@ -658,33 +658,27 @@ void Engine::op_encode_ex(int enc, int rows, int W, const float* x, int x_misali
     if (mode < DITHER_OFF || mode > DITHER_TPDF_HP) throw std::invalid_argument("dither mode " + std::to_string(mode) + ": must be 0 .. 3");
     if (x_misalign < 0 || x_misalign > 3) throw std::invalid_argument("x_misalign must be 0 .. 3 floats");
     if (dst_stride < W) throw std::invalid_argument("dst_stride smaller than the row length");
-    STN_HIP(hipSetDevice(device_));
-    ar_.reset();
+    OpScope op(*this);
     const size_t n = (size_t)rows * W, ny = (size_t)rows * dst_stride * eb;
-    float* dx = static_cast<float*>(ar_.alloc((n + 4) * 4)) + x_misalign;
-    void* dy = ar_.alloc(ny);
-    float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
-    int64_t* di = row_id ? static_cast<int64_t*>(ar_.alloc((size_t)rows * 8)) : nullptr;
-    STN_HIP(hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dy, y, ny, hipMemcpyHostToDevice, s_));
-    if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
-    if (di) STN_HIP(hipMemcpyAsync(di, row_id, (size_t)rows * 8, hipMemcpyHostToDevice, s_));
+    float* dx = op.buf<float>(n + 4) + x_misalign;  // (room for every offset, so that the block behind it never moves with it)
+    op.put(dx, x, n);
+    char* dy = op.up(static_cast<const char*>(y), ny);
+    const float* dg = op.up(gain, (size_t)rows);
+    const int64_t* di = op.up(row_id, (size_t)rows);
     launch_store_rows(s_, dx, rows, W, dg, enc, dy, dst_stride, Dither{mode, seed, DITHER_ROW, di});
     STN_HIP(hipGetLastError());
-    STN_HIP(hipMemcpyAsync(y, dy, ny, hipMemcpyDeviceToHost, s_));
+    op.down(static_cast<char*>(y), dy, ny);
     sync();
 }
 void Engine::op_encode(int enc, int rows, int W, const float* x, void* y) {
     const int eb = need_enc(enc);
-    STN_HIP(hipSetDevice(device_));
-    ar_.reset();
+    OpScope op(*this);
     const size_t n = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(n * 4));
-    void* dy = ar_.alloc(n * eb);
-    STN_HIP(hipMemcpyAsync(dx, x, n * 4, hipMemcpyHostToDevice, s_));
+    const float* dx = op.up(x, n);
+    char* dy = op.buf<char>(n * eb);
     launch_store_rows(s_, dx, rows, W, nullptr, enc, dy, W);
     STN_HIP(hipGetLastError());
-    STN_HIP(hipMemcpyAsync(y, dy, n * eb, hipMemcpyDeviceToHost, s_));
+    op.down(static_cast<char*>(y), dy, n * eb);
     sync();
 }
 // =================================================================================================
@@ -910,7 +904,7 @@ void Engine::batch_join_loudness_range(const stn_join* j, float* m_max, float* s
 void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, const stn_join* j, int enc, bool loudness_on, float target_lufs,
                      float ceiling_dbfs, void* y, float* prog_lufs, float* prog_peak, float* prog_gain) {
     const int eb = need_enc(enc);
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     JoinPlan p;
     stn_join jj = *j;
     jj.mode = STN_JOIN_WHOLE;  // (the lengths are the caller's)
@@ -924,19 +918,15 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
         lo_prepare(op_lo_, hz);
     }
     if (p.W_join == 0) throw std::invalid_argument("join: every programme is empty");
-    ar_.reset();
-    const size_t nx = (size_t)rows * W, ny = (size_t)p.G * p.W_join;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    void* dy = ar_.alloc(ny * eb);
+    const size_t ny = (size_t)p.G * p.W_join;
+    const float* dx = op.up(x, (size_t)rows * W);
+    char* dy = op.buf<char>(ny * eb);
     const std::vector<int64_t> words = join_table_words(p, p.prog_len);  // (a programme is measured over its whole length)
-    int64_t* dt = static_cast<int64_t*>(ar_.alloc(words.size() * sizeof(int64_t)));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dt, words.data(), words.size() * sizeof(int64_t), hipMemcpyHostToDevice, s_));
-    const JoinTables t = join_tables_at(dt, p);
+    const JoinTables t = join_tables_at(op.up(words), p);
     if (!measure) {
         join_enqueue(dx, W, t, p, nullptr, enc, dy, p.W_join);
     } else {
-        float* dj = static_cast<float*>(ar_.alloc(ny * 4));
+        float* dj = op.buf<float>(ny);
         join_enqueue(dx, W, t, p, nullptr, ENC_F32, dj, p.W_join);
         const LoRes res = lo_rows(op_lo_.t, dj, p.G, p.W_join, t.span, lr_max_seg(op_lo_.t, p.prog_len.data(), p.prog_len.size()), loudness_on, target_lufs,
                                   ceiling_dbfs);
@@ -944,7 +934,7 @@ void Engine::op_join(int hz, int rows, int W, const float* x, const int64_t* n, 
         STN_HIP(hipGetLastError());
         lo_read_back(res, (size_t)p.G, prog_lufs, prog_peak, prog_gain);
     }
-    STN_HIP(hipMemcpyAsync(y, dy, ny * eb, hipMemcpyDeviceToHost, s_));
+    op.down(static_cast<char*>(y), dy, ny * eb);
     sync();
 }
 void Engine::batch_fetch_latent(float* latent) {

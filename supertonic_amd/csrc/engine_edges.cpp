@@ -130,13 +130,15 @@ const std::vector<int64_t>& Engine::ed_batch_host(bool pauses) {
     return ed_host_;
 }
 
-void Engine::batch_silence_edges(int64_t* start, int64_t* end) {
-    const std::vector<int64_t>& e = ed_batch_host(pause_limit_active());
-    for (int i = 0; i < bt_.B; ++i) {
-        if (start) start[i] = e[(size_t)i * 2];
-        if (end) end[i] = e[(size_t)i * 2 + 1];
+// row r's words {start, end} of an edge table read back -> the caller's arrays
+static void edges_copy_out(const int64_t* e, int rows, int64_t* start, int64_t* end) {
+    for (int r = 0; r < rows; ++r) {
+        if (start) start[r] = e[(size_t)r * 2];
+        if (end) end[r] = e[(size_t)r * 2 + 1];
     }
 }
+
+void Engine::batch_silence_edges(int64_t* start, int64_t* end) { edges_copy_out(ed_batch_host(pause_limit_active()).data(), bt_.B, start, end); }
 
 void Engine::op_silence_edges(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, int64_t* start, int64_t* end) {
     op_silence_trim(hz, rows, W, x, n, top_db, keep_ms, 0.0f, nullptr, ENC_F32, nullptr, start, end);
@@ -144,40 +146,7 @@ void Engine::op_silence_edges(int hz, int rows, int W, const float* x, const int
 
 void Engine::op_silence_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, const float* gain,
                              int enc, void* y, int64_t* start, int64_t* end) {
-    STN_HIP(hipSetDevice(device_));
-    refuse(silence_check(top_db, keep_ms, fade_ms));
-    refuse(rate_check("silence trim", hz));
-    const int eb = enc_bytes(enc);
-    if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
-    const std::vector<int64_t> nn = spans("op_silence", rows, W, n);
-    ar_.reset();
-    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, 0).bytes)), rows, W, hz, 0);
-    const size_t nx = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc);
-    std::vector<int64_t> e((size_t)rows * 2);
-    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
-    if (y) {
-        const std::vector<float> w = silence_fade_window(hz, fade_ms);
-        float* dw = static_cast<float*>(ar_.alloc(std::max<size_t>(w.size(), 1) * 4));
-        if (!w.empty()) STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
-        float* dg = nullptr;
-        if (gain) {
-            dg = static_cast<float*>(ar_.alloc((size_t)rows * 4));
-            STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
-        }
-        const int64_t Ws = ((int64_t)W + 15) / 16 * 16;  // rows 16-byte aligned in every encoding: the store runs full width
-        void* dy = ar_.alloc((size_t)rows * Ws * eb);
-        launch_join_trim_rows(s_, dx, W, sc.seg, sc.prog, rows, W, dg, dw, enc, dy, Ws);
-        STN_HIP(hipGetLastError());
-        STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
-    }
-    sync();  // (w and e are read or written by the copies above until here)
-    for (int r = 0; r < rows; ++r) {
-        if (start) start[r] = e[(size_t)r * 2];
-        if (end) end[r] = e[(size_t)r * 2 + 1];
-    }
+    ed_op("op_silence_trim", "op_silence", false, hz, rows, W, x, n, top_db, keep_ms, fade_ms, 0.0f, gain, enc, y, nullptr, start, end, nullptr, nullptr, nullptr, 0);
 }
 
 // ---- pause limit
@@ -215,86 +184,61 @@ void Engine::batch_pauses(int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_
 
 void Engine::op_pause_trim(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
                            const float* gain, int enc, void* y, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
-    STN_HIP(hipSetDevice(device_));
-    refuse(silence_check(top_db, keep_ms, fade_ms));
-    refuse(pause_check(max_pause_ms));
-    refuse(rate_check("pause limit", hz));
-    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument("op_pause_trim: cuts needs cap_pairs >= 1");
-    const int eb = enc_bytes(enc);
-    if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
-    const std::vector<int64_t> nn = spans("op_pause", rows, W, n);
-    const int64_t Mp = pause_samples(hz, max_pause_ms);
-    const int S = pause_stride(W, hz, Mp);
-    ar_.reset();
-    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, S).bytes)), rows, W, hz, S);
-    const size_t nx = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc, Mp);
-    std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
-    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
-    STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
-    const std::vector<float> w = silence_fade_window(hz, fade_ms);
-    if (y) {
-        float* dw = static_cast<float*>(ar_.alloc(std::max<size_t>(w.size(), 1) * 4));
-        if (!w.empty()) STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
-        float* dg = nullptr;
-        if (gain) {
-            dg = static_cast<float*>(ar_.alloc((size_t)rows * 4));
-            STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
-        }
-        const int64_t Ws = ((int64_t)W + 15) / 16 * 16;  // rows 16-byte aligned in every encoding: the store runs full width
-        void* dy = ar_.alloc((size_t)rows * Ws * eb);
-        launch_join_trim_rows(s_, dx, W, sc.pseg, sc.pprog, rows, W, dg, dw, enc, dy, Ws);
-        STN_HIP(hipGetLastError());
-        STN_HIP(hipMemcpy2DAsync(y, (size_t)W * eb, dy, (size_t)Ws * eb, (size_t)W * eb, (size_t)rows, hipMemcpyDeviceToHost, s_));
-    }
-    sync();  // (w, e and pz are read or written by the copies above until here)
-    for (int r = 0; r < rows; ++r) {
-        if (start) start[r] = e[(size_t)r * 2];
-        if (end) end[r] = e[(size_t)r * 2 + 1];
-    }
-    pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
+    ed_op("op_pause_trim", "op_pause", true, hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, gain, enc, y, nullptr, start, end, len, n_cuts, cuts, cap_pairs);
 }
 
 void Engine::op_silence_edges_ex(int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms, float fade_ms, float max_pause_ms,
                                  EdProbe& probe, int64_t* start, int64_t* end, int64_t* len, int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
-    STN_HIP(hipSetDevice(device_));
-    const bool pauses = max_pause_ms != 0.0f;
+    ed_op("op_silence_edges_ex", "op_silence", max_pause_ms != 0.0f, hz, rows, W, x, n, top_db, keep_ms, fade_ms, max_pause_ms, nullptr, ENC_F32, nullptr, &probe,
+          start, end, len, n_cuts, cuts, cap_pairs);
+}
+
+// The one body of the three entries above: the detection (with the pause pass when `pauses`), then, with y, the rows cut, faded and
+// stored as enc.  entry and who name the caller in the refusals.  With a probe the rows sit as it asks, the whole scratch (the shares,
+// the levels, the edges and the tables) holds the poison before the first launch, and the shares and levels are read out.
+void Engine::ed_op(const char* entry, const char* who, bool pauses, int hz, int rows, int W, const float* x, const int64_t* n, float top_db, float keep_ms,
+                   float fade_ms, float max_pause_ms, const float* gain, int enc, void* y, EdProbe* probe, int64_t* start, int64_t* end, int64_t* len,
+                   int32_t* n_cuts, int64_t* cuts, int cap_pairs) {
+    OpScope op(*this);
     refuse(silence_check(top_db, keep_ms, fade_ms));
     if (pauses) refuse(pause_check(max_pause_ms));
     refuse(rate_check(pauses ? "pause limit" : "silence trim", hz));
-    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument("op_silence_edges_ex: cuts needs cap_pairs >= 1");
-    const std::vector<int64_t> nn = spans("op_silence", rows, W, n);
+    if (cap_pairs < 0 || (cuts && cap_pairs == 0)) throw std::invalid_argument(std::string(entry) + ": cuts needs cap_pairs >= 1");
+    const int eb = enc_bytes(enc);
+    if (eb == 0) throw std::invalid_argument("unknown sample encoding " + std::to_string(enc));
+    const std::vector<int64_t> nn = spans(who, rows, W, n);
     const int64_t Mp = pauses ? pause_samples(hz, max_pause_ms) : 0;
     const int S = pauses ? pause_stride(W, hz, Mp) : 0;
-    ar_.reset();
-    const EdScratch sc = ed_layout(static_cast<char*>(ar_.alloc(ed_layout(nullptr, rows, W, hz, S).bytes)), rows, W, hz, S);
-    const size_t nx = (size_t)rows * W, off = probe.x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
-    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
-    // the whole scratch, the shares, the levels, the edges and the tables: what a launch fails to write reads back as this, not as an
-    // earlier call's value (every carved array is a multiple of 256 bytes)
-    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pa), 0x7FC00000, sc.bytes / 4, s_));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    ed_enqueue(dx, rows, W, op_spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc, Mp);
+    const EdScratch sc = op.carve_poisoned(probe, ed_layout, rows, W, hz, S);
+    const float* dx = op.up(x, (size_t)rows * W, probe && probe->x_misalign ? 1 : 0);
+    ed_enqueue(dx, rows, W, op.spans(rows, W, nn).n, hz, top_db, keep_ms, fade_ms, sc, Mp);
     std::vector<int64_t> e((size_t)rows * 2), pz((size_t)rows * 2 * S);
-    STN_HIP(hipMemcpyAsync(e.data(), sc.edges, e.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
-    if (S > 0) STN_HIP(hipMemcpyAsync(pz.data(), sc.pcut, pz.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s_));
-    const size_t nc = (size_t)rows * (size_t)ed_chunks(W), nf = (size_t)rows * (size_t)edges_frames(W, hz);
-    if (probe.pa) STN_HIP(hipMemcpyAsync(probe.pa, sc.pa, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
-    if (probe.pb) STN_HIP(hipMemcpyAsync(probe.pb, sc.pb, nc * sizeof(float), hipMemcpyDeviceToHost, s_));
-    if (probe.lev) STN_HIP(hipMemcpyAsync(probe.lev, sc.lev, nf * sizeof(double), hipMemcpyDeviceToHost, s_));
-    probe.form = chunk_staging_form(dx, nullptr, W);
-    sync();  // (e and pz are read or written by the copies above until here)
-    for (int r = 0; r < rows; ++r) {
-        if (start) start[r] = e[(size_t)r * 2];
-        if (end) end[r] = e[(size_t)r * 2 + 1];
-        if (S == 0) {
-            if (len) len[r] = e[(size_t)r * 2 + 1] - e[(size_t)r * 2];
-            if (n_cuts) n_cuts[r] = 0;
-        }
+    op.down(e.data(), sc.edges, e.size());
+    if (S > 0) op.down(pz.data(), sc.pcut, pz.size());
+    const std::vector<float> w = silence_fade_window(hz, fade_ms);
+    if (y) {
+        const float* dw = w.empty() ? op.buf<float>(1) : op.up(w);  // (never null: the kernel's pointer)
+        const float* dg = op.up(gain, (size_t)rows);
+        const int64_t Ws = ((int64_t)W + 15) / 16 * 16;  // rows 16-byte aligned in every encoding: the store runs full width
+        void* dy = op.buf<char>((size_t)rows * Ws * eb);
+        launch_join_trim_rows(s_, dx, W, pauses ? sc.pseg : sc.seg, pauses ? sc.pprog : sc.prog, rows, W, dg, dw, enc, dy, Ws);
+        STN_HIP(hipGetLastError());
+        op.down_rows(y, dy, (size_t)W * eb, (size_t)Ws * eb, (size_t)rows);
     }
-    if (S > 0) pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
+    if (probe) {
+        const size_t nc = (size_t)rows * (size_t)ed_chunks(W), nf = (size_t)rows * (size_t)edges_frames(W, hz);
+        op.down(probe->pa, sc.pa, nc);
+        op.down(probe->pb, sc.pb, nc);
+        op.down(probe->lev, sc.lev, nf);
+        probe->form = chunk_staging_form(dx, nullptr, W);
+    }
+    sync();  // (w, e and pz are read or written by the copies above until here)
+    edges_copy_out(e.data(), rows, start, end);
+    if (S > 0) return pause_copy_out(pz.data(), S, rows, len, n_cuts, cuts, cap_pairs);
+    for (int r = 0; r < rows; ++r) {
+        if (len) len[r] = e[(size_t)r * 2 + 1] - e[(size_t)r * 2];
+        if (n_cuts) n_cuts[r] = 0;
+    }
 }
 
 void Engine::dbg_batch_set_wav(const float* wav) {

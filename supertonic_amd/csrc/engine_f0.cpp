@@ -95,16 +95,13 @@ void Engine::batch_f0(const stn_f0_params* pp, int64_t cap, float* f0, float* ap
 
 void Engine::op_f0(int hz, int rows, int W, const float* x, const int64_t* n, const stn_f0_params* pp, int64_t cap, float* f0, float* ap,
                    stn_f0_stats* stats) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     refuse(f0_check(hz, pp));
     const stn_f0_params p = f0_params(pp);
     const std::vector<int64_t> nn = spans("op_f0", rows, W, n);
     (void)f0_longest(f0_geometry(hz, p), nn.data(), nn.size(), cap, f0 || ap);  // (before the upload)
-    ar_.reset();
-    const size_t nx = (size_t)rows * (size_t)W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    const int64_t* dn = op_spans(rows, W, nn).n;
+    const float* dx = op.up(x, (size_t)rows * (size_t)W);
+    const int64_t* dn = op.spans(rows, W, nn).n;
     f0_report(hz, p, dx, rows, W, dn, nn.data(), cap, f0, ap, stats);
     sync();
 }

@@ -138,7 +138,7 @@ void Engine::fl_enqueue(const FilterTable& t, const float* x, int64_t rows, int6
     for (size_t p = 0; p < t.pass.size(); ++p) {
         const LoudTable& T = t.pass[p];
         const float* src = p == 0 ? x : y;
-        if (probe) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, st_bytes / 4, s_));
+        if (probe) OpScope::poison(s_, sc.st, st_bytes / 4);
         StageSpan span(*this, "out", "filter_chunks", 11.0 * samples, samples * 4 + chunks * 20);
         launch_loudness_chunks(s_, false, src, rows, W, full, T, sc.st, sc.pk, nullptr, nullptr);
         STN_HIP(hipGetLastError());
@@ -163,17 +163,19 @@ void Engine::fl_batch(const float* x, int64_t Wo, float* y) {
 }
 
 void Engine::op_filter(int hz, int rows, int W, const float* x, int n, const stn_filter* f, float* y, FlProbe* probe) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     if (n < 1) throw std::invalid_argument("op_filter: n = " + std::to_string(n) + " must be in [1, " + std::to_string(STN_MAX_FILTERS) + "]");
     fl_prepare(op_fl_, hz, n, f);
-    ar_.reset();
-    GuardedRows r(*this, (size_t)rows * W, x, probe, probe && probe->x_misalign, false);
-    const FlScratch sc = fl_layout(static_cast<char*>(ar_.alloc(fl_layout(nullptr, rows, W).bytes)), rows, W);
-    fl_enqueue(op_fl_.t, r.dx, rows, W, op_spans(rows, W, std::vector<int64_t>((size_t)rows, (int64_t)W)).full, sc, r.dy, probe);
-    r.download(y);
+    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;
+    float* dx = op.guarded(nx, off, probe);
+    float* dy = op.guarded(nx, off, probe);
+    op.put(dx, x, nx);
+    const FlScratch sc = op.carve(fl_layout, rows, W);
+    fl_enqueue(op_fl_.t, dx, rows, W, op.full_spans(rows, W).full, sc, dy, probe);
+    op.down(y, dy, nx);
     if (probe) {
-        probe->guard_ok = r.guards_ok();
-        probe->form = chunk_staging_form(r.dx, r.dy, W);
+        probe->guard_ok = op.guards_ok();
+        probe->form = chunk_staging_form(dx, dy, W);
     }
     sync();
 }

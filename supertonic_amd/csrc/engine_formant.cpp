@@ -41,50 +41,38 @@ void Engine::fm_enqueue(const float* x, const float* y, int64_t rows, int64_t W,
 }
 
 void Engine::op_formant(int hz, int rows, int W, const float* x, const float* y, const int64_t* n, float* out, FormantProbe* probe) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     FormantPlan f;
     refuse(formant_plan(hz, W, f));
     if (W < 1) throw std::invalid_argument("formant: W must be >= 1");
     const std::vector<int64_t> nn = spans("op_formant", rows, W, n);
     const std::vector<float> win = pitch_window(hz);
     const std::vector<double> lagw = formant_lag_window(hz, f.p);
-    ar_.reset();
     // [guard][x][guard], [guard][y][guard] and [guard][out][guard] (the scratch's own rows stay unused here)
-    constexpr size_t G = GuardedRows::G;
     const size_t nx = (size_t)rows * W;
-    float* blk[3];
-    for (float*& b : blk) b = static_cast<float*>(ar_.alloc((nx + 2 * G) * 4));
-    const int64_t* dn = op_spans(rows, W, nn).n;
-    float* dwin = static_cast<float*>(ar_.alloc(win.size() * sizeof(float)));
-    const size_t sc_bytes = fm_layout(nullptr, rows, W, f).bytes;
-    char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
-    FmScratch sc = fm_layout(sb, rows, W, f);
-    sc.out = blk[2] + G;
-    if (probe) {
-        for (float* b : blk) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx + 2 * G, s_));
-        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
-    }
-    STN_HIP(hipMemcpyAsync(blk[0] + G, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(blk[1] + G, y, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dwin, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(sc.lagw, lagw.data(), lagw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
-    fm_enqueue(blk[0] + G, blk[1] + G, rows, W, dn, f, dwin, sc);
-    STN_HIP(hipMemcpyAsync(out, sc.out, nx * 4, hipMemcpyDeviceToHost, s_));
-    std::vector<uint32_t> guards(6 * G);
+    float* dx = op.guarded(nx, 0, probe);
+    float* dy = op.guarded(nx, 0, probe);
+    float* dout = op.guarded(nx, 0, probe);
+    const int64_t* dn = op.spans(rows, W, nn).n;
+    float* dwin = op.buf<float>(win.size());
+    FmScratch sc = op.carve_poisoned(probe, fm_layout, rows, W, f);
+    sc.out = dout;
+    op.put(dx, x, nx);
+    op.put(dy, y, nx);
+    op.put(dwin, win.data(), win.size());
+    op.put(sc.lagw, lagw.data(), lagw.size());
+    fm_enqueue(dx, dy, rows, W, dn, f, dwin, sc);
+    op.down(out, sc.out, nx);
     if (probe) {
         const size_t cells = (size_t)rows * (size_t)f.frames;
-        if (probe->ax) STN_HIP(hipMemcpyAsync(probe->ax, sc.ax, cells * (f.p + 1) * 4, hipMemcpyDeviceToHost, s_));
-        if (probe->cy) STN_HIP(hipMemcpyAsync(probe->cy, sc.cy, cells * (f.p + 1) * 4, hipMemcpyDeviceToHost, s_));
-        if (probe->g) STN_HIP(hipMemcpyAsync(probe->g, sc.g, cells * 8, hipMemcpyDeviceToHost, s_));
-        if (probe->ex) STN_HIP(hipMemcpyAsync(probe->ex, sc.ex, cells * 8, hipMemcpyDeviceToHost, s_));
-        if (probe->ey) STN_HIP(hipMemcpyAsync(probe->ey, sc.ey, cells * 8, hipMemcpyDeviceToHost, s_));
-        for (int i = 0; i < 3; ++i) {
-            STN_HIP(hipMemcpyAsync(guards.data() + 2 * i * G, blk[i], G * 4, hipMemcpyDeviceToHost, s_));
-            STN_HIP(hipMemcpyAsync(guards.data() + (2 * i + 1) * G, blk[i] + G + nx, G * 4, hipMemcpyDeviceToHost, s_));
-        }
+        op.down(probe->ax, sc.ax, cells * (f.p + 1));
+        op.down(probe->cy, sc.cy, cells * (f.p + 1));
+        op.down(probe->g, sc.g, cells);
+        op.down(probe->ex, sc.ex, cells);
+        op.down(probe->ey, sc.ey, cells);
+        probe->guard_ok = op.guards_ok();
     }
-    sync();  // (win, lagw and guards are read or written by the copies above until here)
-    if (probe) probe->guard_ok = std::all_of(guards.begin(), guards.end(), [](uint32_t v) { return v == 0x7FC00000u; });
+    sync();  // (win and lagw are read by the copies above until here)
 }
 
 }  // namespace stn

@@ -37,36 +37,82 @@ inline std::string range_check(const char* unit, const Lims& lim) {
     return "";
 }
 
-// The rows of an op-level entry on the device, from the engine's arena: [guard][x][guard] and [guard][y][guard] (in place: one block),
-// the blocks filled with the quiet NaN 0x7FC00000 when probing, both 4 bytes off a 16-byte boundary when misaligned (the arena's blocks
-// are 256-byte aligned).  x is uploaded; the caller's launches read dx and write dy.
-struct GuardedRows {
-    static constexpr size_t G = 64;
-    Engine& e;
-    size_t nx, off;
-    float *bx, *by, *dx, *dy;
-    GuardedRows(Engine& eng, size_t n, const float* x, bool probing, bool misalign, bool in_place) : e(eng), nx(n), off(misalign ? 1 : 0) {
-        bx = static_cast<float*>(e.arena().alloc((nx + 2 * G + off) * 4));
-        by = in_place ? bx : static_cast<float*>(e.arena().alloc((nx + 2 * G + off) * 4));
-        dx = bx + G + off;
-        dy = by + G + off;
-        if (probing)
-            for (float* b : {bx, by}) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b), 0x7FC00000, nx + 2 * G + off, e.stream()));
-        STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, e.stream()));
+// The scope of one op-level entry: constructed first thing, it selects the engine's device and resets the arena, and
+// every device byte the entry touches goes through it.  Allocations come from the arena in call order (blocks 256-byte aligned);
+// uploads, fills and read-backs are enqueued on the engine's stream, and the host arrays they read or write are the entry's to keep
+// alive until its closing sync().
+class OpScope {
+   public:
+    static constexpr size_t G = 64;                  // floats of guard on either side of a guarded block
+    static constexpr uint32_t POISON = 0x7FC00000u;  // the quiet NaN: what a launch fails to write reads back as this
+    explicit OpScope(Engine& e) : eng_(e) {
+        STN_HIP(hipSetDevice(eng_.device_));
+        eng_.ar_.reset();
     }
-    void download(float* y) const { STN_HIP(hipMemcpyAsync(y, dy, nx * 4, hipMemcpyDeviceToHost, e.stream())); }
-    // every guard word still holds the poison (waits for the stream)
-    bool guards_ok() const {
-        std::vector<uint32_t> g(4 * G + 2 * off);
+    OpScope(const OpScope&) = delete;
+    OpScope& operator=(const OpScope&) = delete;
+
+    template <typename T> T* buf(size_t n) { return static_cast<T*>(eng_.ar_.alloc(n * sizeof(T))); }
+    // host -> a device array the entry already holds
+    template <typename T> void put(T* dev, const T* host, size_t n) { STN_HIP(hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, eng_.s_)); }
+    // host -> arena, the array `off` elements behind its block's boundary; a null host allocates nothing and gives null
+    template <typename T> T* up(const T* host, size_t n, size_t off = 0) {
+        if (!host) return nullptr;
+        T* d = buf<T>(n + off) + off;
+        put(d, host, n);
+        return d;
+    }
+    template <typename T> T* up(const std::vector<T>& host) { return up(host.data(), host.size()); }
+    static void poison(hipStream_t s, void* p, size_t words) { STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), POISON, words, s)); }
+    void poison(void* p, size_t words) { poison(eng_.s_, p, words); }
+    // a scratch layout (xx_layout) on a block of the size it asks for; carve_poisoned: the whole block filled with the poison when `on`
+    template <class Layout, class... A> auto carve_poisoned(bool on, Layout layout, const A&... a) {
+        const size_t bytes = layout(nullptr, a...).bytes;
+        char* b = buf<char>(bytes);
+        if (on) poison(b, bytes / 4);
+        return layout(b, a...);
+    }
+    template <class Layout, class... A> auto carve(Layout layout, const A&... a) { return carve_poisoned(false, layout, a...); }
+    // device -> host; a null host reads nothing.  rows(): `rows` rows of w elements, dev_stride elements apart on the device
+    template <typename T> void down(T* host, const T* dev, size_t n) {
+        if (host) STN_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, eng_.s_));
+    }
+    void down_rows(void* host, const void* dev, size_t w_bytes, size_t dev_stride_bytes, size_t rows) {
+        if (host) STN_HIP(hipMemcpy2DAsync(host, w_bytes, dev, dev_stride_bytes, w_bytes, rows, hipMemcpyDeviceToHost, eng_.s_));
+    }
+    // the entry's spans (checked by stn::spans) and the width beside them; the host copy stays with the engine until the closing sync()
+    RowSpans spans(int rows, int W, std::vector<int64_t> n) {
+        eng_.op_sp_ = std::move(n);
+        eng_.op_sp_.resize((size_t)rows * 2, (int64_t)W);
+        const int64_t* d = up(eng_.op_sp_.data(), eng_.op_sp_.size());
+        return {d, d + rows};
+    }
+    RowSpans full_spans(int rows, int W) { return spans(rows, W, std::vector<int64_t>((size_t)rows, (int64_t)W)); }
+    // [guard][n floats][guard], the n floats `off` floats off the block's boundary; filled with the poison when probing.  guards_ok():
+    // every guard word of every such block still holds it (waits for the stream)
+    float* guarded(size_t n, size_t off, bool probing) {
+        float* b = buf<float>(n + 2 * G + off);
+        if (probing) poison(b, n + 2 * G + off);
+        guards_.push_back({b, n, off});
+        return b + G + off;
+    }
+    bool guards_ok() {
+        std::vector<uint32_t> g;
+        for (const Guarded& b : guards_) g.resize(g.size() + 2 * G + b.off);
         uint32_t* p = g.data();
-        for (float* b : {bx, by}) {
-            STN_HIP(hipMemcpyAsync(p, b, (G + off) * 4, hipMemcpyDeviceToHost, e.stream()));
-            STN_HIP(hipMemcpyAsync(p + G + off, b + G + off + nx, G * 4, hipMemcpyDeviceToHost, e.stream()));
-            p += 2 * G + off;
+        for (const Guarded& b : guards_) {
+            down(p, reinterpret_cast<const uint32_t*>(b.p), G + b.off);
+            down(p + G + b.off, reinterpret_cast<const uint32_t*>(b.p) + G + b.off + b.n, G);
+            p += 2 * G + b.off;
         }
-        e.sync();
-        return std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == 0x7FC00000u; });
+        eng_.sync();
+        return std::all_of(g.begin(), g.end(), [](uint32_t v) { return v == POISON; });
     }
+
+   private:
+    struct Guarded { float* p; size_t n, off; };
+    Engine& eng_;
+    std::vector<Guarded> guards_;
 };
 
 // ---- the host skeleton of the three dynamics stages (DynStage) --------------------------------------------------
@@ -192,31 +238,24 @@ void Engine::read_rows(T* host, const T* dev) {
 template <class St, class Set, class Probe, class Build, class Layout, class Run>
 void Engine::dyn_op(St& st, int hz, int rows, int W, const float* x, const Set& c, float* y, Probe* probe, Build build, Layout layout,
                     std::initializer_list<float*> taps, Run run) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     dyn_prepare(st.op_tab, hz, c, build);
-    ar_.reset();
-    const size_t nx = (size_t)rows * W;
-    GuardedRows r(*this, nx, x, probe, probe && probe->x_misalign, probe && probe->in_place);
+    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;
+    float* dx = op.guarded(nx, off, probe);
+    float* dy = probe && probe->in_place ? dx : op.guarded(nx, off, probe);
+    op.put(dx, x, nx);
     std::vector<float*> dev;
-    for (float* h : taps) dev.push_back(h ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr);
-    const size_t sc_bytes = layout(nullptr, rows, W).bytes;
-    char* sb = static_cast<char*>(ar_.alloc(sc_bytes));
-    const auto sc = layout(sb, rows, W);
-    if (probe) {
-        for (float* d : dev)
-            if (d) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x7FC00000, nx, s_));
-        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sb), 0x7FC00000, sc_bytes / 4, s_));
-    }
-    run(st.op_tab.t, sc, op_spans(rows, W, std::vector<int64_t>((size_t)rows, (int64_t)W)), r.dx, r.dy, dev.data());
-    r.download(y);
+    for (float* h : taps) dev.push_back(h ? op.buf<float>(nx) : nullptr);
+    const auto sc = op.carve_poisoned(probe, layout, rows, W);
+    for (float* d : dev)
+        if (probe && d) op.poison(d, nx);
+    run(st.op_tab.t, sc, op.full_spans(rows, W), dx, dy, dev.data());
+    op.down(y, dy, nx);
     size_t i = 0;
-    for (float* h : taps) {
-        if (h) STN_HIP(hipMemcpyAsync(h, dev[i], nx * 4, hipMemcpyDeviceToHost, s_));
-        ++i;
-    }
+    for (float* h : taps) op.down(h, dev[i++], nx);
     if (probe) {
-        probe->guard_ok = r.guards_ok();
-        probe->form = chunk_staging_form(r.dx, r.dy, W);
+        probe->guard_ok = op.guards_ok();
+        probe->form = chunk_staging_form(dx, dy, W);
     }
     sync();
 }

@@ -1,7 +1,7 @@
 // engine_limiter.cpp — the look-ahead peak limiter behind the loudness gain: the setting, the Hann weights (host only), the fetch
 // scratch that holds the limited fp32 rows, and the step the output stage (engine_batch.cpp) and batch_limiter share.  The kernels are
 // kernels_limiter.hip; DESIGN.md section 15 has the contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -123,7 +123,7 @@ void Engine::op_limiter(int hz, int rows, int W, const float* x, const int64_t* 
 
 void Engine::op_limiter_ex(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, float ceiling_dbfs, float lookahead_ms, float* y,
                            float* s, float* reduction_db, int64_t* limited, int peak_mode, float* env, float* trim) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     if (peak_mode != STN_PEAK_SAMPLE && peak_mode != STN_PEAK_TRUE)
         throw std::invalid_argument("peak mode " + std::to_string(peak_mode) + ": must be STN_PEAK_SAMPLE (0) or STN_PEAK_TRUE (1)");
     const bool tpm = peak_mode == STN_PEAK_TRUE;
@@ -131,25 +131,21 @@ void Engine::op_limiter_ex(int hz, int rows, int W, const float* x, const int64_
     refuse(loudness_check(nullptr, ceiling_dbfs));
     const std::vector<int64_t> nn = spans("op_limiter", rows, W, n);
     const std::vector<float> w = limiter_window(hz, lookahead_ms);
-    ar_.reset();
-    const LmScratch sc = lm_layout(static_cast<char*>(ar_.alloc(lm_layout(nullptr, rows, W).bytes)), rows, W);
-    const TpScratch tp = tpm ? tp_layout(static_cast<char*>(ar_.alloc(tp_layout(nullptr, rows, W, true).bytes)), rows, W, true) : TpScratch{};
+    const LmScratch sc = op.carve(lm_layout, rows, W);
+    const TpScratch tp = tpm ? op.carve(tp_layout, rows, W, true) : TpScratch{};
     const size_t nx = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    float* ds = s ? static_cast<float*>(ar_.alloc(nx * 4)) : nullptr;
-    const int64_t* dn = op_spans(rows, W, nn).n;
-    float* dw = static_cast<float*>(ar_.alloc(w.size() * 4));
-    float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    STN_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s_));
-    if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
+    const float* dx = op.up(x, nx);
+    float* ds = s ? op.buf<float>(nx) : nullptr;
+    const int64_t* dn = op.spans(rows, W, nn).n;
+    const float* dw = op.up(w);
+    const float* dg = op.up(gain, (size_t)rows);
     lm_enqueue(dx, rows, W, dn, dg, (float)std::pow(10.0, (double)ceiling_dbfs / 20.0), limiter_samples(hz, lookahead_ms), dw, sc, ds, tpm ? &tp : nullptr);
-    if (y) STN_HIP(hipMemcpyAsync(y, sc.y, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (s) STN_HIP(hipMemcpyAsync(s, ds, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (reduction_db) STN_HIP(hipMemcpyAsync(reduction_db, sc.red, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
-    if (limited) STN_HIP(hipMemcpyAsync(limited, sc.limited, (size_t)rows * 8, hipMemcpyDeviceToHost, s_));
-    if (tpm && env) STN_HIP(hipMemcpyAsync(env, tp.env, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (tpm && trim) STN_HIP(hipMemcpyAsync(trim, tp.trim, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
+    op.down(y, sc.y, nx);
+    op.down(s, ds, nx);
+    op.down(reduction_db, sc.red, (size_t)rows);
+    op.down(limited, sc.limited, (size_t)rows);
+    if (tpm) op.down(env, tp.env, nx);
+    if (tpm) op.down(trim, tp.trim, (size_t)rows);
     if (!tpm && trim) std::fill(trim, trim + rows, 1.0f);
     sync();  // (w is read by the copy above until here)
 }

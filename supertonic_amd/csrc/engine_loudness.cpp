@@ -200,13 +200,6 @@ const Engine::BatchSpans& Engine::batch_spans(int hz, int64_t W) {
     return e;
 }
 
-RowSpans Engine::op_spans(int rows, int W, std::vector<int64_t> n) {
-    op_sp_ = std::move(n);
-    op_sp_.resize((size_t)rows * 2, (int64_t)W);
-    const int64_t* d = detail::up(ar_, s_, op_sp_.data(), op_sp_.size());
-    return {d, d + rows};
-}
-
 Engine::LoRes Engine::lo_batch(const float* x, int64_t Wo, bool on) {
     const Batch& b = bt_;
     const int hz = output_rate();
@@ -233,27 +226,22 @@ void Engine::batch_loudness(float* lufs, float* peak, float* gain) {
 
 const int64_t* Engine::lo_op(int hz, int rows, int W, const float* x, const int64_t* n, bool on, float target, float ceiling, LoProbe* probe, float* lufs,
                              float* peak, float* gain) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     lo_prepare(op_lo_, hz);
     const std::vector<int64_t> nn = spans("op_loudness", rows, W, n);
     const int64_t max_seg = lr_max_seg(op_lo_.t, nn.data(), nn.size());
-    ar_.reset();
-    const size_t nx = (size_t)rows * W, off = probe && probe->x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
-    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    const float* dx = op.up(x, (size_t)rows * W, probe && probe->x_misalign ? 1 : 0);
     const LoScratch sc = lo_scratch(rows, W);
-    if (probe)  // every per-chunk array and the results: what a launch fails to write reads back as this, not as an earlier call's value
-        STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.st), 0x7FC00000, sc.bytes / 4, s_));
-    const int64_t* dn = op_spans(rows, W, nn).n;
+    if (probe) op.poison(sc.st, sc.bytes / 4);  // every per-chunk array and the results
+    const int64_t* dn = op.spans(rows, W, nn).n;
     lo_measure(op_lo_.t, dx, rows, W, dn, sc, max_seg, on, target, ceiling, probe ? probe->st_end : nullptr);
     lo_read_back(sc.out, (size_t)rows, lufs, peak, gain);
     if (probe) {
         const size_t nc = (size_t)rows * (size_t)lo_chunks(W);
-        auto out = [&](float* dst, const float* src, size_t bytes) { if (dst) STN_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_)); };
-        out(probe->st_start, sc.st, nc * 16);
-        out(probe->pk, sc.pk, nc * 4);
-        out(probe->pa, sc.pa, nc * 4);
-        out(probe->pb, sc.pb, nc * 4);
+        op.down(probe->st_start, sc.st, nc * 4);
+        op.down(probe->pk, sc.pk, nc);
+        op.down(probe->pa, sc.pa, nc);
+        op.down(probe->pb, sc.pb, nc);
         probe->form = chunk_staging_form(dx, nullptr, W);
     }
     sync();

@@ -98,7 +98,7 @@ const float* Engine::ps_batch() {
 // the stretch (and, with y, the resample behind it) on the caller's rows: the launches of ps_batch on arena buffers
 void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, int a, int b, float* ys_out, int* delta_out, float* score_out, float* y_out,
                    int mode) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     PitchPlan p;
     refuse(pitch_plan(hz, W, a, b, p));
     if (W < 1) throw std::invalid_argument("pitch: W must be >= 1");
@@ -109,29 +109,27 @@ void Engine::ps_op(int hz, int rows, int W, const float* x, const int64_t* n, in
     const std::vector<int64_t> nn = spans("op_pitch", rows, W, n);
     const std::vector<float> win = pitch_window(hz);
     const std::vector<double> lagw = formant ? formant_lag_window(hz, f.p) : std::vector<double>();
-    ar_.reset();
-    const PsScratch sc = ps_layout(static_cast<char*>(ar_.alloc(ps_layout(nullptr, rows, W, p).bytes)), rows, W, p);
+    const PsScratch sc = op.carve(ps_layout, rows, W, p);
     const size_t nx = (size_t)rows * W;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    const int64_t* dn = op_spans(rows, W, nn).n;
-    STN_HIP(hipMemcpyAsync(sc.win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice, s_));
+    const float* dx = op.up(x, nx);
+    const int64_t* dn = op.spans(rows, W, nn).n;
+    op.put(sc.win, win.data(), win.size());
     if (y_out) ps_table(op_ps_rs_, a, b);
     ps_enqueue(dx, rows, W, dn, a, b, p, sc.win, sc.delta, sc.score, sc.ys);
     if (y_out) {
         ps_resample(op_ps_rs_.t, sc.ys, rows, p.Ws, W, sc.y);
         const float* res = sc.y;
         if (formant) {
-            const FmScratch fm = fm_layout(static_cast<char*>(ar_.alloc(fm_layout(nullptr, rows, W, f).bytes)), rows, W, f);
-            STN_HIP(hipMemcpyAsync(fm.lagw, lagw.data(), lagw.size() * sizeof(double), hipMemcpyHostToDevice, s_));
+            const FmScratch fm = op.carve(fm_layout, rows, W, f);
+            op.put(fm.lagw, lagw.data(), lagw.size());
             fm_enqueue(dx, sc.y, rows, W, dn, f, sc.win, fm);
             res = fm.out;
         }
-        STN_HIP(hipMemcpyAsync(y_out, res, nx * 4, hipMemcpyDeviceToHost, s_));
+        op.down(y_out, res, nx);
     }
-    if (ys_out) STN_HIP(hipMemcpyAsync(ys_out, sc.ys, (size_t)rows * p.Ws * 4, hipMemcpyDeviceToHost, s_));
-    if (delta_out) STN_HIP(hipMemcpyAsync(delta_out, sc.delta, (size_t)rows * p.M * sizeof(int), hipMemcpyDeviceToHost, s_));
-    if (score_out) STN_HIP(hipMemcpyAsync(score_out, sc.score, (size_t)rows * p.M * 4, hipMemcpyDeviceToHost, s_));
+    op.down(ys_out, sc.ys, (size_t)rows * p.Ws);
+    op.down(delta_out, sc.delta, (size_t)rows * p.M);
+    op.down(score_out, sc.score, (size_t)rows * p.M);
     sync();  // (win and lagw are read by the copies above until here)
 }
 

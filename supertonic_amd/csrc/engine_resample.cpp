@@ -1,6 +1,6 @@
 // engine_resample.cpp — the output rate of a handle: the resampler's filter design (host only), its device table, and the launch
 // the output stage makes when the rate is on (engine_batch.cpp).  The kernel is kernels_resample.hip.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <cmath>
 #include <numeric>
@@ -120,22 +120,20 @@ void Engine::resample_enqueue(const ResampleTable& t, const float* x, int64_t ro
 }
 
 void Engine::op_resample(int in_hz, int out_hz, int rows, int W, const float* x, float* y, int16_t* pcm) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     rs_prepare(op_rs_, in_hz, out_hz);
     const int64_t W_out = resample_out_len(W, op_rs_.t.P, op_rs_.t.Q);
-    ar_.reset();
-    const size_t nx = (size_t)rows * W, ny = (size_t)rows * W_out;
-    float* dx = static_cast<float*>(ar_.alloc(nx * 4));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
+    const size_t ny = (size_t)rows * W_out;
+    const float* dx = op.up(x, (size_t)rows * W);
     if (y) {
-        float* dy = static_cast<float*>(ar_.alloc(ny * 4));
+        float* dy = op.buf<float>(ny);
         resample_enqueue(op_rs_.t, dx, rows, W, ENC_F32, dy, W_out);
-        STN_HIP(hipMemcpyAsync(y, dy, ny * 4, hipMemcpyDeviceToHost, s_));
+        op.down(y, dy, ny);
     }
     if (pcm) {
-        int16_t* dp = static_cast<int16_t*>(ar_.alloc(ny * 2));
+        int16_t* dp = op.buf<int16_t>(ny);
         resample_enqueue(op_rs_.t, dx, rows, W, ENC_PCM16, dp, W_out);
-        STN_HIP(hipMemcpyAsync(pcm, dp, ny * 2, hipMemcpyDeviceToHost, s_));
+        op.down(pcm, dp, ny);
     }
     sync();
 }

@@ -1,7 +1,7 @@
 // engine_truepeak.cpp — the true-peak mode of the loudness ceiling: the 4x oversampling filter (host only), the setting, the fetch
 // scratch, the reporting call and the op-level entries.  The kernels are kernels_truepeak.hip; the measurement (engine_loudness.cpp) and
 // the limiter (engine_limiter.cpp) are its consumers; DESIGN.md section 16 has the contract.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -107,25 +107,21 @@ void Engine::batch_true_peak(float* tp_in, float* tp_out, float* trim) {
 
 const char* Engine::op_true_peak(int hz, int rows, int W, const float* x, const int64_t* n, const float* gain, int x_misalign, float* tp, float* env,
                                  float* pk) {
-    STN_HIP(hipSetDevice(device_));
+    OpScope op(*this);
     refuse(rate_check("true peak", hz));
     const std::vector<int64_t> nn = spans("op_true_peak", rows, W, n);
-    ar_.reset();
-    const size_t nx = (size_t)rows * W, nc = (size_t)rows * (size_t)lo_chunks(W), off = x_misalign ? 1 : 0;  // (the arena's blocks are 256-byte aligned)
-    float* dx = static_cast<float*>(ar_.alloc((nx + off) * 4)) + off;
-    const TpScratch sc = tp_layout(static_cast<char*>(ar_.alloc(tp_layout(nullptr, rows, W, env != nullptr).bytes)), rows, W, env != nullptr);
-    const int64_t* dn = op_spans(rows, W, nn).n;
-    float* dg = gain ? static_cast<float*>(ar_.alloc((size_t)rows * 4)) : nullptr;
-    // what a launch fails to write reads back as the quiet NaN, not as an earlier call's value
-    if (sc.env) STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.env), 0x7FC00000, nx, s_));
-    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.pk), 0x7FC00000, nc, s_));
-    STN_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc.tp_in), 0x7FC00000, (size_t)rows, s_));
-    STN_HIP(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, s_));
-    if (dg) STN_HIP(hipMemcpyAsync(dg, gain, (size_t)rows * 4, hipMemcpyHostToDevice, s_));
+    const size_t nx = (size_t)rows * W, nc = (size_t)rows * (size_t)lo_chunks(W);
+    const float* dx = op.up(x, nx, x_misalign ? 1 : 0);
+    const TpScratch sc = op.carve(tp_layout, rows, W, env != nullptr);
+    const int64_t* dn = op.spans(rows, W, nn).n;
+    const float* dg = op.up(gain, (size_t)rows);
+    if (sc.env) op.poison(sc.env, nx);
+    op.poison(sc.pk, nc);
+    op.poison(sc.tp_in, (size_t)rows);
     tp_rows(dx, rows, W, dn, dg, sc.pk, sc.env, 1.0f, sc.tp_in, nullptr);
-    if (tp) STN_HIP(hipMemcpyAsync(tp, sc.tp_in, (size_t)rows * 4, hipMemcpyDeviceToHost, s_));
-    if (env) STN_HIP(hipMemcpyAsync(env, sc.env, nx * 4, hipMemcpyDeviceToHost, s_));
-    if (pk) STN_HIP(hipMemcpyAsync(pk, sc.pk, nc * 4, hipMemcpyDeviceToHost, s_));
+    op.down(tp, sc.tp_in, (size_t)rows);
+    op.down(env, sc.env, nx);
+    op.down(pk, sc.pk, nc);
     sync();
     return truepeak_staging_form(dx, W, sc.env);
 }
